@@ -6,8 +6,15 @@ One "step" = one batched `Diffusion.forward` over the rank's 8 samples + the DDP
 (pipeline.mojo:87-122), inputs resident in HBM, fp16 storage / fp32 accumulate, random-init weights,
 synthetic latents/context (there is no network for checkpoints or datasets).
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+
+Step i runs index i % 50 of the schedule; every 50 steps the session starts again from the same inputs (run_steps), so any K works.
+A plain run sets up, warms up, times the K steps and prints the line (steps/s, ms_per_step, the weight broadcast).  --full adds,
+each in runs of its own after the timed steps: the per-kernel-class roofline pass, the MFMA probe, the live K-loop model, VAE decode /
+img2img / CFG / full-size UNet timings, the peaked-logits loop and cpu_baseline (--no-<name> skips one of them).
+--dump-outputs DIR writes the latents of the last timed step as DIR/latents.npy (float32, (B, 4, L, L); rank r > 0 of a multi-GPU
+run writes its shard as DIR/latents_rank<r>.npy); the inputs are seeded, so two builds can be compared output for output.
 
 N > 1: one process per GPU; the batch of independent prompts is sharded (8 per rank, weak scaling), the
 only collective is the one-time RCCL broadcast of the packed weights from rank 0 (outside the timed
@@ -41,6 +48,30 @@ def shard_range(total, rank, world):
     lo = (total * rank) // world
     hi = (total * (rank + 1)) // world
     return lo, hi
+
+
+def run_steps(sess, ctx, first, count, n_sched, upload, sync):
+    """Steps first .. first + count - 1 of `sess`; step i runs schedule index i % n_sched, counted from the session's upload.  Each pass
+    of the schedule starts again from the same inputs (`upload()` before every step i > 0 with i % n_sched == 0, not timed): latents
+    carried through t = 0 and back to t = 980 grow with every pass until fp16 overflows (within 220 steps at the headline size).
+    Returns (ms on the library's stream, wall seconds) of the steps alone: one hipEvent pair and one host clock per pass, each pass
+    ending in `sync()`."""
+    ev_ms, wall = 0.0, 0.0
+    i, end = first, first + count
+    while i < end:
+        if i > 0 and i % n_sched == 0:
+            upload()
+            sync()
+        n = min(end - i, n_sched - i % n_sched)
+        t0 = time.perf_counter()
+        ctx.timer_start()
+        for j in range(i, i + n):
+            sess.step(j % n_sched)
+        ev_ms += ctx.timer_stop()  # synchronises the library's stream
+        sync()
+        wall += time.perf_counter() - t0
+        i += n
+    return ev_ms, wall
 
 
 class _DevView:
@@ -195,10 +226,7 @@ def peaked_logits_bench(tsd, ctx, B, L, T, lat, cx, noise, n_sched, K, friendly_
             sess.step(i)
         ctx.synchronize()
         lib().tsd_debug_attn_exact_passes(ctx.h, 1)
-        ctx.timer_start()
-        for i in range(steps):
-            sess.step((warm + i) % n_sched)
-        ms = ctx.timer_stop()
+        ms = run_steps(sess, ctx, warm, steps, n_sched, lambda: sess.upload(lat, cx, None, noise), ctx.synchronize)[0]
         n = lib().tsd_debug_attn_exact_passes(ctx.h, 1)
         ctx.synchronize()  # raises TSD_E_NONFINITE if the scaled model overflowed fp16
         return n / float(steps * wg), ms / steps
@@ -425,9 +453,12 @@ def main():
     ap.add_argument("--batch", type=int, default=8, help="samples per GPU (BASELINE config 2: 8)")
     ap.add_argument("--latent", type=int, default=64, help="latent side (64 = 512x512)")
     ap.add_argument("--tokens", type=int, default=77)
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the roofline pass, the probes, the other BASELINE configs and cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the latents of the last timed step as DIR/latents.npy (float32)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-decode", action="store_true", help="skip the VAE-decode timing used for images/s")
-    # the other BASELINE configs ride along as extra fields (a few seconds in total); --no-extras / --no-<name> skip them
+    # under --full the other BASELINE configs ride along as extra fields; --no-extras / --no-<name> skip them
     ap.add_argument("--no-cfg", action="store_true", help="skip the classifier-free-guidance loop (UNet batch 2B per step)")
     ap.add_argument("--no-img2img", action="store_true",
                     help="skip BASELINE configs[3] (VAE encoder + 30 UNet steps + VAE decoder)")
@@ -439,11 +470,12 @@ def main():
     ap.add_argument("--img2img", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--sd15", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
-    args.cfg = not (args.no_cfg or args.no_extras)
-    args.img2img = not (args.no_img2img or args.no_extras or args.no_decode)
-    args.sd15 = not (args.no_sd15 or args.no_extras)
-    args.peaked = not (args.no_peaked or args.no_extras)
-    args.kloop = not (args.no_kloop or args.no_extras)
+    args.decode = args.full and not args.no_decode
+    args.cfg = args.full and not (args.no_cfg or args.no_extras)
+    args.img2img = args.decode and not (args.no_img2img or args.no_extras)
+    args.sd15 = args.full and not (args.no_sd15 or args.no_extras)
+    args.peaked = args.full and not (args.no_peaked or args.no_extras)
+    args.kloop = args.full and not (args.no_kloop or args.no_extras)
 
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
@@ -493,7 +525,7 @@ def main():
 
     # weights: rank 0 random-initialises on the device; other ranks receive the packed blob over RCCL
     unet = tsd.Diffusion(seed=SEED if rank == 0 else None, ctx=ctx)
-    dec = None if args.no_decode else tsd.Decoder(seed=SEED if rank == 0 else None, ctx=ctx)
+    dec = tsd.Decoder(seed=SEED if rank == 0 else None, ctx=ctx) if args.decode else None
     bcast_s, bcast_bytes, bcast_how = 0.0, 0, "none (single GPU)"
     rccl_ranks = {"torch_distributed": dist.get_world_size() if use_dist else 1, "backend": backend if use_dist else None,
                   "ncclCommCount_native": None}
@@ -539,18 +571,12 @@ def main():
             dist.barrier()
 
     K, W = args.steps, args.warmup
-    for i in range(W):
-        sess.step(i % n_sched)
+    upload = lambda: sess.upload(lat, cx, None, noise)  # noqa: E731
+    run_steps(sess, ctx, 0, W, n_sched, upload, barrier)
     barrier()
     from tsd._lib import lib as _tsd_lib
     _tsd_lib().tsd_debug_attn_exact_passes(ctx.h, 1)
-    t0 = time.perf_counter()
-    ctx.timer_start()
-    for i in range(K):
-        sess.step((W + i) % n_sched)
-    ev_ms = ctx.timer_stop()  # hipEvents on the library's own stream (synchronises the stream)
-    barrier()
-    dt = time.perf_counter() - t0
+    ev_ms, dt = run_steps(sess, ctx, W, K, n_sched, upload, barrier)
     # flash-attention workgroups that had to repeat their softmax exactly inside the timed region (kernels_attn.hip)
     attn_exact_wg = _tsd_lib().tsd_debug_attn_exact_passes(ctx.h, 1)
     rank_rate = (K / (ev_ms * 1e-3), K / (ev_ms * 1e-3))  # (min, max) over ranks of this rank's own steps/s (device events)
@@ -567,187 +593,14 @@ def main():
         derived_s = float(rr[2].item())  # the slowest rank's rebuild
     out_lat = sess.latents()
     finite = bool(np.isfinite(out_lat).all())
+    if args.dump_outputs:  # the latents of the last timed step (the --full passes below step the session further)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "latents.npy" if rank == 0 else f"latents_rank{rank}.npy"), out_lat)
 
     if rank == 0:
-        # ---- per-kernel-class pass (hipEvent pair around every launch, same stream) -> roofline of the dominant kernel
-        P = max(2, min(5, K))
-        ctx.profile_begin()
-        for i in range(P):
-            sess.step((W + i) % n_sched)
-        recs = ctx.profile_records()  # per launch: (class, M, N, K, batch, ms) - read before profile_end() clears them
-        prof = ctx.profile_end()
-        per_step = {k: (ms / P, n // P) for k, (ms, n) in prof.items()}
-        # A hipEvent pair brackets a launch PLUS its dispatch gaps; summed over the ~190 launches of a step the bracketed
-        # times exceed the step measured without events.  That excess, spread evenly per launch, is taken off every
-        # record so the per-class sums add up to the un-instrumented step (and the GEMM average agrees with
-        # `rocprofv3 --kernel-trace --stats`, which times kernels only: 36.6 us there vs 39.2 us uncorrected).
-        n_launch = sum(v[1] for v in per_step.values())
-        ev_overhead_ms = max(0.0, (sum(v[0] for v in per_step.values()) - 1e3 * dt / K) / max(1, n_launch))
-        per_step = {k: (max(0.0, ms - n * ev_overhead_ms), n) for k, (ms, n) in per_step.items()}
-        gemm_ms = per_step["gemm"][0] + per_step["conv3x3"][0]
-        gemm_launches = per_step["gemm"][1] + per_step["conv3x3"][1]
-        # algorithmic FLOP of the GEMM-class launches of one step = conv + linear share of 408.33 GFLOP/sample
-        # (conv 195.22 + linear 137.51 at L=64; attention core is its own kernel)
-        total_gf = tsd.flop_count("diffusion", L, T)
-        attn_gf = 0.0
-        side = L
-        for hd, cnt in ((40, 3), (80, 3), (160, 3)):
-            S = side * side
-            attn_gf += cnt * (2 * 2 * 8 * S * S * hd + 2 * 2 * 8 * S * T * hd) / 1e9
-            side //= 2
-        # the fused attention-tail kernel (kernels_chain.hip) does the six row-local GEMMs of the 64x64-level attention blocks
-        # (32 C^2 flop per token row) and their cross-attention core (4 T C per row) itself: that work is taken OFF the
-        # gemm_kernel's account and reported under the tail kernel's own roofline entry below
-        # (the fused HEAD kernel of the same blocks - GroupNorm-apply, conv_in, LayerNorm, q/k/V^T projections: 8 C^2 per
-        # row - is recorded in the same class with K = 1)
-        chain_recs = [r for r in recs if r[0] == "attn_tail_chain"]
-        chain_lin_gf = sum(r[1] * (8.0 if r[3] == 1 else 32.0) * r[2] * r[2] for r in chain_recs) / P / 1e9
-        chain_att_gf = sum(r[1] * 4.0 * T * r[2] for r in chain_recs if r[3] == 0) / P / 1e9
-        gemm_gf_step = (total_gf - attn_gf) * B - chain_lin_gf
-        achieved = (gemm_gf_step / 1e3) / (gemm_ms / 1e3) if gemm_ms > 0 else 0.0  # TFLOP/s
-        traffic, traffic_src = pmc_traffic_per_gemm_launch()
-        roofline = {"bound": "mfma", "kernel": "gemm_kernel<...> (dense + conv3x3 implicit GEMM)",
-                    "achieved": round(achieved, 2), "peak": PEAK_FP16_TFLOPS, "unit": "TFLOP/s",
-                    "frac": round(achieved / PEAK_FP16_TFLOPS, 4), "traffic": traffic,
-                    "traffic_source": None if traffic is None else f"{traffic_src} (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE "
-                                      "passes over this same command, scripts/gpu_pmc_bench.sh; committed file, NOT measured by this run)",
-                    "launches_per_step": gemm_launches, "avg_launch_us": round(1e3 * gemm_ms / max(1, gemm_launches), 2),
-                    "algorithmic_gflop_per_step": round(gemm_gf_step, 1),
-                    "event_overhead_us_per_launch_removed": round(1e3 * ev_overhead_ms, 3),
-                    "per_class_ms_per_step": {k: round(v[0], 4) for k, v in per_step.items()},
-                    "per_class_launches_per_step": {k: v[1] for k, v in per_step.items()}}
-        # secondary kernels against their own rooflines (same pass, same per-launch correction): attention on the fp16
-        # MFMA peak (algorithmic 4*B*H*Sq*Sk*d per launch), the norms on HBM (algorithmic bytes = read once + write once)
-        sec = {}
-        for cls in ("flash_attention", "attn_tail_chain", "groupnorm", "layernorm"):
-            ms_c, n_c = per_step[cls]
-            if ms_c <= 0:
-                continue
-            rs = [r for r in recs if r[0] == cls]
-            if cls == "attn_tail_chain":
-                tf = (chain_lin_gf + chain_att_gf) / 1e3 / (ms_c / 1e3)
-                sec[cls] = {"bound": "mfma", "achieved": round(tf, 1), "peak": PEAK_FP16_TFLOPS, "unit": "TFLOP/s",
-                            "frac": round(tf / PEAK_FP16_TFLOPS, 4), "ms_per_step": round(ms_c, 4), "launches_per_step": n_c,
-                            "replaces": "14 launches per 64x64-level attention block: head kernel = GroupNorm-apply, conv_in, LN, "
-                                        "q/k projection, V^T projection; tail kernel = out_proj+res, LN, q_proj, cross-attention, "
-                                        "out_proj+res, LN, GEGLU-1, GEGLU-2+res, conv_out+res"}
-            elif cls == "flash_attention":
-                tf = sum(4.0 * r[1] * r[2] * r[3] * r[4] for r in rs) / P / 1e12 / (ms_c / 1e3)
-                sec[cls] = {"bound": "mfma", "achieved": round(tf, 1), "peak": PEAK_FP16_TFLOPS, "unit": "TFLOP/s",
-                            "frac": round(tf / PEAK_FP16_TFLOPS, 4), "ms_per_step": round(ms_c, 4),
-                            # optimistic softmax pass + exact repeat on fp16 overflow: repeats inside the timed region
-                            "exact_pass_workgroups_in_timed_region": attn_exact_wg}
-            else:
-                gbs = sum(2.0 * r[1] * r[2] * 2 for r in rs) / P / 1e9 / (ms_c / 1e3)
-                sec[cls] = {"bound": "hbm", "achieved": round(gbs, 1), "peak": 8000.0, "unit": "GB/s",
-                            "frac": round(gbs / 8000.0, 4), "ms_per_step": round(ms_c, 4)}
-        roofline["secondary_kernels"] = sec
-        # What the matrix pipe of THIS board sustains (register-resident fp16 MFMA loop, ~20 ms, after the timed region): the
-        # nominal 2.5 PF assumes the boost clock, under MFMA load the power limit sets the clock.  `frac` above stays priced
-        # against the nominal peak; this is context for reading it.
-        try:
-            import ctypes as _C
-            _tf, _ghz = _C.c_float(), _C.c_float()
-            if _tsd_lib().tsd_debug_mfma_sustained(ctx.h, 20.0, _C.byref(_tf), _C.byref(_ghz)) == 0:
-                roofline["mfma_sustained_probe"] = {
-                    "tflops": round(_tf.value, 1), "shader_clock_ghz": round(_ghz.value, 3), "unit": "TFLOP/s",
-                    "frac_of_sustained": round(achieved / _tf.value, 4) if _tf.value > 0 else None,
-                    "what": "dense v_mfma_f32_16x16x32_f16 loop from registers, 4 waves/SIMD, no LDS or memory traffic"}
-        except Exception as e:  # a probe must never cost the bench line
-            roofline["mfma_sustained_probe"] = {"error": str(e)}
-        if args.kloop:
-            try:
-                roofline["k_loop_model"] = k_loop_model(tsd, dev_index, in_step=[(r[0], r[1], r[2], r[3], r[4], max(0.0, r[5] - ev_overhead_ms)) for r in recs])
-            except Exception as e:  # a probe must never cost the bench line
-                roofline["k_loop_model"] = {"error": str(e)}
-        # ---- VAE decode time (images/s end-to-end = B / (50 * step + decode)) ----
-        dec_ms = None
-        if dec is not None:
-            sess.decode()
-            ctx.synchronize()
-            ctx.timer_start()
-            sess.decode()
-            dec_ms = ctx.timer_stop()
         ms_per_step = 1e3 * dt / K
         steps_per_s = world * K / dt
-        # ---- classifier-free guidance: conditional + unconditional pass batched (2B samples per UNet call) ----
-        cfg_ms = None
-        if args.cfg:
-            un = np.stack([tsd.rng.normal(SEED, 4000 + i, T * 768).reshape(T, 768) for i in range(lo, hi)])
-            s2 = tsd.Session(unet.model, None, B, L, T, cfg=True)
-            s2.set_schedule(1000, n_sched, 0)
-            s2.upload(lat, cx, un, noise, 7.5)
-            for i in range(2):
-                s2.step(i)
-            ctx.synchronize()
-            ctx.timer_start()
-            for i in range(K):
-                s2.step((2 + i) % n_sched)
-            cfg_ms = ctx.timer_stop() / K
-            s2.close()
-        # ---- the headline loop with peaked attention logits (the flash kernel's exact-repeat path) ----
-        peaked = None
-        if args.peaked:
-            try:
-                peaked = peaked_logits_bench(tsd, ctx, B, L, T, lat, cx, noise, n_sched, K, world * K / dt / world)
-            except Exception as e:  # noqa: BLE001
-                peaked = {"error": str(e)}
-        # ---- BASELINE configs[4]: full-size (SD-1.5-sized) UNet, batch 4, same 50-step schedule ----
-        sd15 = None
-        if args.sd15:
-            B5 = 4
-            big = tsd.Diffusion(seed=SEED, ctx=ctx, variant="diffusion_sd15")
-            s5 = tsd.Session(big.model, None, B5, L, T, cfg=False)
-            s5.set_schedule(1000, n_sched, 0)
-            s5.upload(lat[:B5], cx[:B5], None, noise[:, :B5])
-            for i in range(3):
-                s5.step(i)
-            ctx.synchronize()
-            ctx.timer_start()
-            for i in range(K):
-                s5.step((3 + i) % n_sched)
-            ms5 = ctx.timer_stop() / K
-            gf5 = tsd.flop_count("diffusion_sd15", L, T)
-            sd15 = {"workload": f"full-size UNet (859 M parameters, 12 encoders / bottleneck / 12 decoders), latent 4x{L}x{L}, "
-                                f"batch {B5}, random-init weights (BASELINE configs[4]; graph not defined by the reference)",
-                    "steps_per_s": round(1e3 / ms5, 3), "ms_per_step": round(ms5, 4),
-                    "algorithmic_gflop_per_step": round(gf5 * B5, 1),
-                    "frac_of_fp16_mfma_peak_whole_step": round(gf5 * B5 / ms5 / PEAK_FP16_TFLOPS, 4),
-                    "output_finite": bool(np.isfinite(s5.latents()).all())}
-            s5.close()
-            big.model.close()
-        # ---- BASELINE configs[3] (img2img): VAE encoder on B x (3,512,512) + strength 0.6 of the schedule + decoder ----
-        enc_ms = enc_dev_ms = None
-        if args.img2img and dec is not None:
-            enc = tsd.Encoder(seed=SEED, ctx=ctx)
-            img = tsd.rng.uniform(SEED, 7, B * 3 * 64 * L * L, 1.0).reshape(B, 3, 8 * L, 8 * L)
-            nz = tsd.rng.normal(SEED, 8, B * 4 * L * L).reshape(B, 4, L, L)
-            enc.forward(img, nz)
-            t0 = time.time()
-            enc.forward(img, nz)  # boundary call: host buffers in and out (PCIe-inclusive)
-            enc_ms = 1e3 * (time.time() - t0)
-            ctx.profile_begin()   # device time of the same call: sum of its kernel launches (hipEvent pairs)
-            enc.forward(img, nz)
-            enc_recs = ctx.profile_records()
-            ctx.profile_end()
-            enc_dev_ms = sum(r[5] for r in enc_recs)
-            enc.model.close()
-        images_per_s = (world * B) / ((n_sched * ms_per_step + (dec_ms or 0.0)) / 1e3)
-        cpu = None
-        if not args.no_cpu_baseline and world == 1:  # the CPU baseline is a rank-0, N=1 figure
-            t_sample, c_threads, t_numpy, c_reps = cpu_baseline(L, T)
-            if t_sample is None:  # the C restatement could not be built on this host: the numpy statement is the baseline
-                cpu = {"value": round(1.0 / (B * t_numpy), 6), "unit": "steps/s", "cores": c_threads, "kind": "port", "host_cores": os.cpu_count(),
-                       "sample": f"one sample-step (1/{B} of a batch-{B} step, L={L}, T={T}) on the numpy oracle (im2col + BLAS, "
-                                 f"{c_threads} threads) took {t_numpy:.1f} s; oracle/cref (C + OpenMP) could not be built on this host"}
-            else:
-                cpu = {"value": round(1.0 / (B * t_sample), 6), "unit": "steps/s", "cores": c_threads, "kind": "port",
-                       "host_cores": os.cpu_count(),  # cores = the CPU quota of this process (cgroup cpu.max), the OpenMP team's size
-                       "sample": f"one sample-step (1/{B} of a batch-{B} step: Diffusion.forward + DDPM update, L={L}, T={T}) "
-                                 f"of oracle/cref/cref.c (the reference's loop nests in C, OpenMP over output channels / rows, "
-                                 f"fp32, {c_threads} threads) took {t_sample:.2f} s (mean of {c_reps}); value = 1/({B} x that)",
-                       "numpy_oracle": {"value": round(1.0 / (B * t_numpy), 6), "cores": c_threads,
-                                        "sample": f"the same sample-step on the numpy oracle (im2col + BLAS) took {t_numpy:.1f} s"}}
+        total_gf = tsd.flop_count("diffusion", L, T)
         whole_frac = steps_per_s / world * B * total_gf / 1e3 / PEAK_FP16_TFLOPS
         assert world == args.gpus and rccl_ranks["torch_distributed"] == world, (world, args.gpus, rccl_ranks)
         line = {
@@ -757,32 +610,205 @@ def main():
             "config": {"workload": f"Tiny-SD UNet 512x512 (latent 4x{L}x{L}), batch {B}/GPU, {n_sched}-step DDPM schedule, "
                                    f"{T}-token context, no CFG, random-init weights (BASELINE configs[1])",
                        "global_batch": world * B, "parallelism": f"dp{world} (independent prompts, weights broadcast once)"},
-            "images_per_s_end_to_end": round(images_per_s, 4), "decode_ms": None if dec_ms is None else round(dec_ms, 3),
-            "cfg_ms_per_step": None if cfg_ms is None else round(cfg_ms, 4),
-            "img2img_config4": None if enc_ms is None else {
-                "workload": f"VAE encoder on {B} x (3,{8 * L},{8 * L}) + {int(n_sched * 0.6)} UNet steps + VAE decoder (BASELINE configs[3])",
-                "encode_ms_host_boundary": round(enc_ms, 3), "encode_ms_device": round(enc_dev_ms, 3), "steps": int(n_sched * 0.6),
-                # images_per_s keeps its round-1 definition (encoder timed through the host boundary: upload + kernels + gaps);
-                # the device-only figure has its own key
-                "images_per_s": round(world * B / ((enc_ms + int(n_sched * 0.6) * ms_per_step + dec_ms) / 1e3), 4),
-                "images_per_s_device_encode": round(world * B / ((enc_dev_ms + int(n_sched * 0.6) * ms_per_step + dec_ms) / 1e3), 4)},
-            # the VAE halves of the hot path against the fp16 MFMA peak (algorithmic GFLOP per image: SURVEY.md Appendix B)
-            "vae_roofline": {
-                "decoder": None if dec_ms is None else {
-                    "bound": "mfma", "ms": round(dec_ms, 3), "algorithmic_gflop": round(tsd.flop_count("decoder", L) * B, 1),
-                    "achieved": round(tsd.flop_count("decoder", L) * B / dec_ms, 1), "peak": PEAK_FP16_TFLOPS, "unit": "TFLOP/s",
-                    "frac": round(tsd.flop_count("decoder", L) * B / dec_ms / PEAK_FP16_TFLOPS, 4)},
-                "encoder": None if enc_dev_ms is None else {
-                    "bound": "mfma", "ms": round(enc_dev_ms, 3), "algorithmic_gflop": round(tsd.flop_count("encoder", 8 * L) * B, 1),
-                    "achieved": round(tsd.flop_count("encoder", 8 * L) * B / enc_dev_ms, 1), "peak": PEAK_FP16_TFLOPS, "unit": "TFLOP/s",
-                    "frac": round(tsd.flop_count("encoder", 8 * L) * B / enc_dev_ms / PEAK_FP16_TFLOPS, 4)}},
-            "sd15_config5": sd15, "headline_peaked_logits": peaked,
             "event_ms_per_step": round(ev_ms / K, 4), "output_finite": finite,
             "frac_of_fp16_mfma_peak_whole_step": round(whole_frac, 4),
             "per_rank_steps_per_s": {"min": round(rank_rate[0], 3), "max": round(rank_rate[1], 3)},
             "weight_broadcast_s": round(bcast_s, 4), "derived_buffers_s": round(derived_s, 4), "weight_broadcast_bytes": bcast_bytes, "weight_broadcast": bcast_how,
-            "roofline": roofline, "cpu_baseline": cpu,
         }
+        if args.full:
+            # ---- per-kernel-class pass (hipEvent pair around every launch, same stream) -> roofline of the dominant kernel
+            P = max(2, min(5, K))
+            ctx.profile_begin()
+            for i in range(P):
+                sess.step((W + i) % n_sched)
+            recs = ctx.profile_records()  # per launch: (class, M, N, K, batch, ms) - read before profile_end() clears them
+            prof = ctx.profile_end()
+            per_step = {k: (ms / P, n // P) for k, (ms, n) in prof.items()}
+            # A hipEvent pair brackets a launch PLUS its dispatch gaps; summed over the ~190 launches of a step the bracketed
+            # times exceed the step measured without events.  That excess, spread evenly per launch, is taken off every
+            # record so the per-class sums add up to the un-instrumented step (and the GEMM average agrees with
+            # `rocprofv3 --kernel-trace --stats`, which times kernels only: 36.6 us there vs 39.2 us uncorrected).
+            n_launch = sum(v[1] for v in per_step.values())
+            ev_overhead_ms = max(0.0, (sum(v[0] for v in per_step.values()) - 1e3 * dt / K) / max(1, n_launch))
+            per_step = {k: (max(0.0, ms - n * ev_overhead_ms), n) for k, (ms, n) in per_step.items()}
+            gemm_ms = per_step["gemm"][0] + per_step["conv3x3"][0]
+            gemm_launches = per_step["gemm"][1] + per_step["conv3x3"][1]
+            # algorithmic FLOP of the GEMM-class launches of one step = conv + linear share of 408.33 GFLOP/sample
+            # (conv 195.22 + linear 137.51 at L=64; attention core is its own kernel)
+            attn_gf = 0.0
+            side = L
+            for hd, cnt in ((40, 3), (80, 3), (160, 3)):
+                S = side * side
+                attn_gf += cnt * (2 * 2 * 8 * S * S * hd + 2 * 2 * 8 * S * T * hd) / 1e9
+                side //= 2
+            # the fused attention-tail kernel (kernels_chain.hip) does the six row-local GEMMs of the 64x64-level attention blocks
+            # (32 C^2 flop per token row) and their cross-attention core (4 T C per row) itself: that work is taken OFF the
+            # gemm_kernel's account and reported under the tail kernel's own roofline entry below
+            # (the fused HEAD kernel of the same blocks - GroupNorm-apply, conv_in, LayerNorm, q/k/V^T projections: 8 C^2 per
+            # row - is recorded in the same class with K = 1)
+            chain_recs = [r for r in recs if r[0] == "attn_tail_chain"]
+            chain_lin_gf = sum(r[1] * (8.0 if r[3] == 1 else 32.0) * r[2] * r[2] for r in chain_recs) / P / 1e9
+            chain_att_gf = sum(r[1] * 4.0 * T * r[2] for r in chain_recs if r[3] == 0) / P / 1e9
+            gemm_gf_step = (total_gf - attn_gf) * B - chain_lin_gf
+            achieved = (gemm_gf_step / 1e3) / (gemm_ms / 1e3) if gemm_ms > 0 else 0.0  # TFLOP/s
+            traffic, traffic_src = pmc_traffic_per_gemm_launch()
+            roofline = {"bound": "mfma", "kernel": "gemm_kernel<...> (dense + conv3x3 implicit GEMM)",
+                        "achieved": round(achieved, 2), "peak": PEAK_FP16_TFLOPS, "unit": "TFLOP/s",
+                        "frac": round(achieved / PEAK_FP16_TFLOPS, 4), "traffic": traffic,
+                        "traffic_source": None if traffic is None else f"{traffic_src} (separate rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE "
+                                          "passes over this same command, scripts/gpu_pmc_bench.sh; committed file, NOT measured by this run)",
+                        "launches_per_step": gemm_launches, "avg_launch_us": round(1e3 * gemm_ms / max(1, gemm_launches), 2),
+                        "algorithmic_gflop_per_step": round(gemm_gf_step, 1),
+                        "event_overhead_us_per_launch_removed": round(1e3 * ev_overhead_ms, 3),
+                        "per_class_ms_per_step": {k: round(v[0], 4) for k, v in per_step.items()},
+                        "per_class_launches_per_step": {k: v[1] for k, v in per_step.items()}}
+            # secondary kernels against their own rooflines (same pass, same per-launch correction): attention on the fp16
+            # MFMA peak (algorithmic 4*B*H*Sq*Sk*d per launch), the norms on HBM (algorithmic bytes = read once + write once)
+            sec = {}
+            for cls in ("flash_attention", "attn_tail_chain", "groupnorm", "layernorm"):
+                ms_c, n_c = per_step[cls]
+                if ms_c <= 0:
+                    continue
+                rs = [r for r in recs if r[0] == cls]
+                if cls == "attn_tail_chain":
+                    tf = (chain_lin_gf + chain_att_gf) / 1e3 / (ms_c / 1e3)
+                    sec[cls] = {"bound": "mfma", "achieved": round(tf, 1), "peak": PEAK_FP16_TFLOPS, "unit": "TFLOP/s",
+                                "frac": round(tf / PEAK_FP16_TFLOPS, 4), "ms_per_step": round(ms_c, 4), "launches_per_step": n_c,
+                                "replaces": "14 launches per 64x64-level attention block: head kernel = GroupNorm-apply, conv_in, LN, "
+                                            "q/k projection, V^T projection; tail kernel = out_proj+res, LN, q_proj, cross-attention, "
+                                            "out_proj+res, LN, GEGLU-1, GEGLU-2+res, conv_out+res"}
+                elif cls == "flash_attention":
+                    tf = sum(4.0 * r[1] * r[2] * r[3] * r[4] for r in rs) / P / 1e12 / (ms_c / 1e3)
+                    sec[cls] = {"bound": "mfma", "achieved": round(tf, 1), "peak": PEAK_FP16_TFLOPS, "unit": "TFLOP/s",
+                                "frac": round(tf / PEAK_FP16_TFLOPS, 4), "ms_per_step": round(ms_c, 4),
+                                # optimistic softmax pass + exact repeat on fp16 overflow: repeats inside the timed region
+                                "exact_pass_workgroups_in_timed_region": attn_exact_wg}
+                else:
+                    gbs = sum(2.0 * r[1] * r[2] * 2 for r in rs) / P / 1e9 / (ms_c / 1e3)
+                    sec[cls] = {"bound": "hbm", "achieved": round(gbs, 1), "peak": 8000.0, "unit": "GB/s",
+                                "frac": round(gbs / 8000.0, 4), "ms_per_step": round(ms_c, 4)}
+            roofline["secondary_kernels"] = sec
+            # What the matrix pipe of THIS board sustains (register-resident fp16 MFMA loop, ~20 ms, after the timed region): the
+            # nominal 2.5 PF assumes the boost clock, under MFMA load the power limit sets the clock.  `frac` above stays priced
+            # against the nominal peak; this is context for reading it.
+            try:
+                import ctypes as _C
+                _tf, _ghz = _C.c_float(), _C.c_float()
+                if _tsd_lib().tsd_debug_mfma_sustained(ctx.h, 20.0, _C.byref(_tf), _C.byref(_ghz)) == 0:
+                    roofline["mfma_sustained_probe"] = {
+                        "tflops": round(_tf.value, 1), "shader_clock_ghz": round(_ghz.value, 3), "unit": "TFLOP/s",
+                        "frac_of_sustained": round(achieved / _tf.value, 4) if _tf.value > 0 else None,
+                        "what": "dense v_mfma_f32_16x16x32_f16 loop from registers, 4 waves/SIMD, no LDS or memory traffic"}
+            except Exception as e:  # a probe must never cost the bench line
+                roofline["mfma_sustained_probe"] = {"error": str(e)}
+            if args.kloop:
+                try:
+                    roofline["k_loop_model"] = k_loop_model(tsd, dev_index, in_step=[(r[0], r[1], r[2], r[3], r[4], max(0.0, r[5] - ev_overhead_ms)) for r in recs])
+                except Exception as e:  # a probe must never cost the bench line
+                    roofline["k_loop_model"] = {"error": str(e)}
+            # ---- VAE decode time (images/s end-to-end = B / (50 * step + decode)) ----
+            dec_ms = None
+            if dec is not None:
+                sess.decode()
+                ctx.synchronize()
+                ctx.timer_start()
+                sess.decode()
+                dec_ms = ctx.timer_stop()
+            # ---- classifier-free guidance: conditional + unconditional pass batched (2B samples per UNet call) ----
+            cfg_ms = None
+            if args.cfg:
+                un = np.stack([tsd.rng.normal(SEED, 4000 + i, T * 768).reshape(T, 768) for i in range(lo, hi)])
+                s2 = tsd.Session(unet.model, None, B, L, T, cfg=True)
+                s2.set_schedule(1000, n_sched, 0)
+                s2.upload(lat, cx, un, noise, 7.5)
+                for i in range(2):
+                    s2.step(i)
+                ctx.synchronize()
+                cfg_ms = run_steps(s2, ctx, 2, K, n_sched, lambda: s2.upload(lat, cx, un, noise, 7.5), ctx.synchronize)[0] / K
+                s2.close()
+            # ---- the headline loop with peaked attention logits (the flash kernel's exact-repeat path) ----
+            peaked = None
+            if args.peaked:
+                try:
+                    peaked = peaked_logits_bench(tsd, ctx, B, L, T, lat, cx, noise, n_sched, K, world * K / dt / world)
+                except Exception as e:  # noqa: BLE001
+                    peaked = {"error": str(e)}
+            # ---- BASELINE configs[4]: full-size (SD-1.5-sized) UNet, batch 4, same 50-step schedule ----
+            sd15 = None
+            if args.sd15:
+                B5 = 4
+                big = tsd.Diffusion(seed=SEED, ctx=ctx, variant="diffusion_sd15")
+                s5 = tsd.Session(big.model, None, B5, L, T, cfg=False)
+                s5.set_schedule(1000, n_sched, 0)
+                s5.upload(lat[:B5], cx[:B5], None, noise[:, :B5])
+                for i in range(3):
+                    s5.step(i)
+                ctx.synchronize()
+                ms5 = run_steps(s5, ctx, 3, K, n_sched, lambda: s5.upload(lat[:B5], cx[:B5], None, noise[:, :B5]), ctx.synchronize)[0] / K
+                gf5 = tsd.flop_count("diffusion_sd15", L, T)
+                sd15 = {"workload": f"full-size UNet (859 M parameters, 12 encoders / bottleneck / 12 decoders), latent 4x{L}x{L}, "
+                                    f"batch {B5}, random-init weights (BASELINE configs[4]; graph not defined by the reference)",
+                        "steps_per_s": round(1e3 / ms5, 3), "ms_per_step": round(ms5, 4),
+                        "algorithmic_gflop_per_step": round(gf5 * B5, 1),
+                        "frac_of_fp16_mfma_peak_whole_step": round(gf5 * B5 / ms5 / PEAK_FP16_TFLOPS, 4),
+                        "output_finite": bool(np.isfinite(s5.latents()).all())}
+                s5.close()
+                big.model.close()
+            # ---- BASELINE configs[3] (img2img): VAE encoder on B x (3,512,512) + strength 0.6 of the schedule + decoder ----
+            enc_ms = enc_dev_ms = None
+            if args.img2img and dec is not None:
+                enc = tsd.Encoder(seed=SEED, ctx=ctx)
+                img = tsd.rng.uniform(SEED, 7, B * 3 * 64 * L * L, 1.0).reshape(B, 3, 8 * L, 8 * L)
+                nz = tsd.rng.normal(SEED, 8, B * 4 * L * L).reshape(B, 4, L, L)
+                enc.forward(img, nz)
+                t0 = time.time()
+                enc.forward(img, nz)  # boundary call: host buffers in and out (PCIe-inclusive)
+                enc_ms = 1e3 * (time.time() - t0)
+                ctx.profile_begin()   # device time of the same call: sum of its kernel launches (hipEvent pairs)
+                enc.forward(img, nz)
+                enc_recs = ctx.profile_records()
+                ctx.profile_end()
+                enc_dev_ms = sum(r[5] for r in enc_recs)
+                enc.model.close()
+            images_per_s = (world * B) / ((n_sched * ms_per_step + (dec_ms or 0.0)) / 1e3)
+            cpu = None
+            if not args.no_cpu_baseline and world == 1:  # the CPU baseline is a rank-0, N=1 figure
+                t_sample, c_threads, t_numpy, c_reps = cpu_baseline(L, T)
+                if t_sample is None:  # the C restatement could not be built on this host: the numpy statement is the baseline
+                    cpu = {"value": round(1.0 / (B * t_numpy), 6), "unit": "steps/s", "cores": c_threads, "kind": "port", "host_cores": os.cpu_count(),
+                           "sample": f"one sample-step (1/{B} of a batch-{B} step, L={L}, T={T}) on the numpy oracle (im2col + BLAS, "
+                                     f"{c_threads} threads) took {t_numpy:.1f} s; oracle/cref (C + OpenMP) could not be built on this host"}
+                else:
+                    cpu = {"value": round(1.0 / (B * t_sample), 6), "unit": "steps/s", "cores": c_threads, "kind": "port",
+                           "host_cores": os.cpu_count(),  # cores = the CPU quota of this process (cgroup cpu.max), the OpenMP team's size
+                           "sample": f"one sample-step (1/{B} of a batch-{B} step: Diffusion.forward + DDPM update, L={L}, T={T}) "
+                                     f"of oracle/cref/cref.c (the reference's loop nests in C, OpenMP over output channels / rows, "
+                                     f"fp32, {c_threads} threads) took {t_sample:.2f} s (mean of {c_reps}); value = 1/({B} x that)",
+                           "numpy_oracle": {"value": round(1.0 / (B * t_numpy), 6), "cores": c_threads,
+                                            "sample": f"the same sample-step on the numpy oracle (im2col + BLAS) took {t_numpy:.1f} s"}}
+            line.update({
+                "images_per_s_end_to_end": round(images_per_s, 4), "decode_ms": None if dec_ms is None else round(dec_ms, 3),
+                "cfg_ms_per_step": None if cfg_ms is None else round(cfg_ms, 4),
+                "img2img_config4": None if enc_ms is None else {
+                    "workload": f"VAE encoder on {B} x (3,{8 * L},{8 * L}) + {int(n_sched * 0.6)} UNet steps + VAE decoder (BASELINE configs[3])",
+                    "encode_ms_host_boundary": round(enc_ms, 3), "encode_ms_device": round(enc_dev_ms, 3), "steps": int(n_sched * 0.6),
+                    # images_per_s keeps its round-1 definition (encoder timed through the host boundary: upload + kernels + gaps);
+                    # the device-only figure has its own key
+                    "images_per_s": round(world * B / ((enc_ms + int(n_sched * 0.6) * ms_per_step + dec_ms) / 1e3), 4),
+                    "images_per_s_device_encode": round(world * B / ((enc_dev_ms + int(n_sched * 0.6) * ms_per_step + dec_ms) / 1e3), 4)},
+                # the VAE halves of the hot path against the fp16 MFMA peak (algorithmic GFLOP per image: SURVEY.md Appendix B)
+                "vae_roofline": {
+                    "decoder": None if dec_ms is None else {
+                        "bound": "mfma", "ms": round(dec_ms, 3), "algorithmic_gflop": round(tsd.flop_count("decoder", L) * B, 1),
+                        "achieved": round(tsd.flop_count("decoder", L) * B / dec_ms, 1), "peak": PEAK_FP16_TFLOPS, "unit": "TFLOP/s",
+                        "frac": round(tsd.flop_count("decoder", L) * B / dec_ms / PEAK_FP16_TFLOPS, 4)},
+                    "encoder": None if enc_dev_ms is None else {
+                        "bound": "mfma", "ms": round(enc_dev_ms, 3), "algorithmic_gflop": round(tsd.flop_count("encoder", 8 * L) * B, 1),
+                        "achieved": round(tsd.flop_count("encoder", 8 * L) * B / enc_dev_ms, 1), "peak": PEAK_FP16_TFLOPS, "unit": "TFLOP/s",
+                        "frac": round(tsd.flop_count("encoder", 8 * L) * B / enc_dev_ms / PEAK_FP16_TFLOPS, 4)}},
+                "sd15_config5": sd15, "headline_peaked_logits": peaked,
+                "roofline": roofline, "cpu_baseline": cpu,
+            })
         print(json.dumps(line), flush=True)
     barrier()
     if dist is not None:

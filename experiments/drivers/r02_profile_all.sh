@@ -16,5 +16,5 @@ rm -rf /tmp/prof_sd15
 B=4 VARIANT=diffusion_sd15 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_sd15 -o r -- python $R/scripts/profile_step.py > $O/prof_sd15.log 2>&1
 find /tmp/prof_sd15 -name "*kernel_stats*.csv" -exec cp {} $O/kernel_stats_sd15.csv \;
 cd $R
-timeout 900 python bench.py --steps 50 --warmup 10 --no-cpu-baseline > $O/bench.json 2> $O/bench.err
+timeout 900 python bench.py --full --steps 50 --warmup 10 --no-cpu-baseline > $O/bench.json 2> $O/bench.err
 tail -c 600 $O/bench.json

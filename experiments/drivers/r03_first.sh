@@ -8,7 +8,7 @@ cd $R; export TMPDIR=/tmp HIP_FORCE_DEV_KERNARG=1
 ./scripts/micro/lds_read_rate > $O/lds_read_rate.txt 2>&1; cat $O/lds_read_rate.txt
 timeout 2400 python -m pytest tests -q -m gpu -s -x > $O/pytest_gpu.log 2>&1; grep -E "passed|failed|error" $O/pytest_gpu.log | tail -3
 grep "\[parity\]" $O/pytest_gpu.log > $O/parity.log
-timeout 900 python bench.py --steps 50 --warmup 10 > $O/bench.json 2> $O/bench.err; tail -c 600 $O/bench.json
+timeout 900 python bench.py --full --steps 50 --warmup 10 > $O/bench.json 2> $O/bench.err; tail -c 600 $O/bench.json
 WHAT=unet TOP=80 timeout 600 python scripts/profile_step.py > $O/shapes_unet.txt 2>&1
 cd /tmp; rm -rf /tmp/prof_unet
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_unet -o r -- python $R/bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-decode --no-extras > $O/prof_unet.log 2>&1

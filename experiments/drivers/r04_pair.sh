@@ -4,8 +4,8 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"; mkdir -p gpurun_out; export TMPDIR=/tmp
 timeout 900 python -m pytest tests/test_gpu_range.py -m gpu -q -p no:cacheprovider 2>&1 | tail -n 5 > gpurun_out/r04_range_v2.log
 out=gpurun_out/r04_pair_ab.txt; : > $out
 for rep in 1 2 3; do
-  echo "== separate launches $rep" >> $out; timeout 600 python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-decode --no-extras 2>&1 | tail -n 1 | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print(d['value'], d['ms_per_step'], d['roofline']['per_class_ms_per_step'])" >> $out
-  echo "== pairs (timing only) $rep" >> $out; TSD_EXP_PAIR=1 timeout 600 python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-decode --no-extras 2>&1 | tail -n 1 | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print(d['value'], d['ms_per_step'], d['roofline']['per_class_ms_per_step'])" >> $out
+  echo "== separate launches $rep" >> $out; timeout 600 python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-decode --no-extras 2>&1 | tail -n 1 | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print(d['value'], d['ms_per_step'], d['roofline']['per_class_ms_per_step'])" >> $out
+  echo "== pairs (timing only) $rep" >> $out; TSD_EXP_PAIR=1 timeout 600 python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-decode --no-extras 2>&1 | tail -n 1 | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print(d['value'], d['ms_per_step'], d['roofline']['per_class_ms_per_step'])" >> $out
 done
 for mode in 0 1; do
   rm -rf /tmp/prof$mode

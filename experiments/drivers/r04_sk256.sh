@@ -5,7 +5,7 @@ for v in 3; do TSD_GEMM_SK256=$v timeout 900 python -m pytest tests/test_gpu_ops
 for rep in 1 2 3; do
   for v in 0 1 2 3; do
     echo "== TSD_GEMM_SK256=$v ($rep)" >> $out
-    TSD_GEMM_SK256=$v timeout 600 python bench.py --steps 100 --warmup 10 --no-cpu-baseline --no-decode --no-extras 2>&1 | tail -n 1 | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print(d['value'], d['ms_per_step'], d['roofline']['per_class_ms_per_step']['conv3x3'], d['roofline']['per_class_ms_per_step']['gemm'])" >> $out
+    TSD_GEMM_SK256=$v timeout 600 python bench.py --full --steps 100 --warmup 10 --no-cpu-baseline --no-decode --no-extras 2>&1 | tail -n 1 | python -c "import sys,json; d=json.loads(sys.stdin.readline()); print(d['value'], d['ms_per_step'], d['roofline']['per_class_ms_per_step']['conv3x3'], d['roofline']['per_class_ms_per_step']['gemm'])" >> $out
   done
 done
 cat $out

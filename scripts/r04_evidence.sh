@@ -14,7 +14,7 @@ R="${GRAFT_REPO_ROOT:-/root/repo}"; O=$R/gpurun_out/r04f; mkdir -p $O
 cd $R; export TMPDIR=/tmp HIP_FORCE_DEV_KERNARG=1
 timeout 2400 python -m pytest tests -q -m gpu -s > $O/pytest_gpu.log 2>&1; grep -E "passed|failed" $O/pytest_gpu.log | tail -2
 grep "\[parity\]" $O/pytest_gpu.log > $O/parity.log; tail -1 $O/pytest_gpu.log >> $O/parity.log
-timeout 900 python bench.py --steps 50 --warmup 10 > $O/bench.json 2> $O/bench.err
+timeout 900 python bench.py --full --steps 50 --warmup 10 > $O/bench.json 2> $O/bench.err
 for w in unet dec enc; do WHAT=$w TOP=80 timeout 600 python scripts/profile_step.py > $O/shapes_$w.txt 2>&1; done
 B=4 VARIANT=diffusion_sd15 TOP=80 timeout 600 python scripts/profile_step.py > $O/shapes_sd15.txt 2>&1
 cd /tmp

@@ -16,7 +16,7 @@ R="${GRAFT_REPO_ROOT:-/root/repo}"; O=$R/gpurun_out/r06f; mkdir -p $O
 cd $R; export TMPDIR=/tmp HIP_FORCE_DEV_KERNARG=1
 timeout 2400 python -m pytest tests -q -m gpu -s > $O/pytest_gpu.log 2>&1; grep -E "passed|failed" $O/pytest_gpu.log | tail -2
 grep "\[parity\]" $O/pytest_gpu.log > $O/parity.log; tail -1 $O/pytest_gpu.log >> $O/parity.log
-timeout 900 python bench.py --steps 50 --warmup 10 > $O/bench.json 2> $O/bench.err
+timeout 900 python bench.py --full --steps 50 --warmup 10 > $O/bench.json 2> $O/bench.err
 python scripts/kloop_probe.py > $O/kloop_probe.txt 2>&1   # bench.py's own probe list through the same function: the two must agree within the spreads
 ALL=1 ROUNDS=5 timeout 300 python scripts/attn8_probe.py > $O/attn8_probe.txt 2>&1
 for w in unet dec enc; do WHAT=$w TOP=80 timeout 600 python scripts/profile_step.py > $O/shapes_$w.txt 2>&1; done

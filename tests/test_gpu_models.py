@@ -547,6 +547,25 @@ def test_bench_distributed_path_single_rank(gpu_ctx):
     assert d["weight_broadcast"].startswith("rccl broadcast") and d["weight_broadcast_bytes"] > 5e8
 
 
+def test_bench_restarts_the_schedule_and_dumps_the_last_step(gpu_ctx, tmp_path):
+    """`bench.py --dump-outputs DIR` writes the latents of the last timed step (float32, batch 8 at the headline latent).  Every 50 steps
+    the session starts again from the same inputs, so 10 + 120 steps end on schedule index 29 of a fresh pass - the same bits as 10 + 20
+    steps (without the restart the latents grow with every pass until fp16 overflows).  A plain run's line carries the
+    headline and none of the --full measurements."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    outs = []
+    for steps in (20, 120):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "10",
+                            "--dump-outputs", str(tmp_path / f"run{steps}")], capture_output=True, text=True, timeout=900)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == steps and d["ms_per_step"] > 0 and d["value"] > 10 and d["output_finite"]
+        assert not {"roofline", "cpu_baseline", "decode_ms", "sd15_config5", "headline_peaked_logits"} & d.keys(), sorted(d)
+        outs.append(np.load(tmp_path / f"run{steps}" / "latents.npy"))
+    assert outs[0].dtype == np.float32 and outs[0].shape == (8, 4, 64, 64) and np.isfinite(outs[0]).all()
+    np.testing.assert_array_equal(outs[1], outs[0])
+
 
 def test_encoder_512px_batch8_properties(gpu_ctx, tsd_mod):
     """BASELINE configs[3] front end at full size: the VAE encoder on 8 x (3, 512, 512) - finite, bitwise repeatable,

@@ -95,6 +95,36 @@ def test_shard_range_partitions(total, world):
     assert seen == list(range(total))
 
 
+def test_run_steps_restarts_every_pass_of_the_schedule():
+    """bench.run_steps: step i runs schedule index i % n_sched, the inputs are uploaded again (untimed) before each pass after the
+    first, and every pass is timed by its own event pair."""
+    sys.path.insert(0, ROOT)
+    import bench
+    log = []
+
+    class Sess:
+        def step(self, i):
+            log.append(i)
+
+    class Ctx:
+        def timer_start(self):
+            log.append("start")
+
+        def timer_stop(self):
+            log.append("stop")
+            return 2.0
+
+    ev_ms, wall = bench.run_steps(Sess(), Ctx(), 45, 60, 50, lambda: log.append("upload"), lambda: None)
+    assert log == (["start"] + list(range(45, 50)) + ["stop", "upload", "start"] + list(range(50)) + ["stop", "upload", "start"]
+                   + list(range(5)) + ["stop"])
+    assert ev_ms == 6.0 and wall >= 0.0
+    log.clear()
+    assert bench.run_steps(Sess(), Ctx(), 0, 50, 50, lambda: log.append("upload"), lambda: None)[0] == 2.0
+    assert log == ["start"] + list(range(50)) + ["stop"]
+    log.clear()
+    assert bench.run_steps(Sess(), Ctx(), 7, 0, 50, lambda: log.append("upload"), lambda: None) == (0.0, 0.0) and log == []
+
+
 # ---- bench.py --gpus N started plainly: it launches its own N ranks and refuses to print a line about another N --------------------
 def _run_bench(args, env_extra, timeout=300):
     import subprocess
