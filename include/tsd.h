@@ -310,7 +310,50 @@ int tsd_debug_gemm_bench(tsd_ctx* ctx, int conv, int B, int H, int W, int Cin, i
 /* Run one problem with tile configuration `cfg` and with `ref_cfg`; max |difference| and max |reference|. */
 int tsd_debug_gemm_check(tsd_ctx* ctx, int conv, int B, int H, int W, int Cin, int N, int stride, int ups, int cfg,
                          int ref_cfg, float* max_abs_diff, float* max_abs_ref);
-/* Same for the fused attention core: Q,K [B][S][H*d], V^T [B][H*d][Sk]. */
+/* ---- GEMM / conv3x3 launch descriptors (test infrastructure: tests/gemm_ref.py holds every launch to an fp64 reference) ----
+ * One internal GEMM launch as int64 fields, one per GemmArgs field (csrc/common.h).  Pitches and strides are in elements.
+ * K0: the dense concat split (K when there is no second source).  PAD: top/left padding; HO / WO carry what an asymmetric pad
+ * implies.  W_KTS: 1 when the launch reads the K-tile-major weight copy.  OUT_SCALE: the float's bits.  ALIAS: bit 0 R == C
+ * (in-place residual), bit 1 A1 == A0, bit 2 A2 == A1.  SK_BIG: the context's long-K split setting at the launch.  CFG / WAYS:
+ * tile configuration and split-K slices that ran (written by the dispatcher). */
+enum tsd_gemm_desc_field {
+  TSD_GD_VERSION = 0, TSD_GD_CONV, TSD_GD_M, TSD_GD_N, TSD_GD_K, TSD_GD_K0,
+  TSD_GD_LDA0, TSD_GD_LDA1, TSD_GD_LDA2, TSD_GD_LDW, TSD_GD_LDW1, TSD_GD_LDR, TSD_GD_LDC,
+  TSD_GD_BATCH, TSD_GD_SA, TSD_GD_SW, TSD_GD_SC, TSD_GD_SR,
+  TSD_GD_HS, TSD_GD_WS, TSD_GD_HO, TSD_GD_WO, TSD_GD_CIN, TSD_GD_STRIDE, TSD_GD_PAD, TSD_GD_UPS,
+  TSD_GD_CIN1, TSD_GD_CIN2, TSD_GD_W_KTS,
+  TSD_GD_EPI, TSD_GD_OUT_SCALE, TSD_GD_ROWVEC_LD, TSD_GD_ROWS_PER_BATCH,
+  TSD_GD_VT, TSD_GD_VT_N0, TSD_GD_VT_LD, TSD_GD_VT_S, TSD_GD_VT_SB,
+  TSD_GD_GN_GROUPS, TSD_GD_GN_RPS, TSD_GD_GN_NSLAB, TSD_GD_RPS_HINT, TSD_GD_SK_BIG, TSD_GD_ALIAS,
+  TSD_GD_CFG, TSD_GD_WAYS,
+  TSD_GD_COUNT
+};
+#define TSD_GD_VERSION_1 1
+/* Operand slots of tsd_debug_gemm_run: inputs A0 A1 A2 W Wt1 R (fp16) bias rowvec (fp32); outputs C (fp16, fp32 under
+ * EPI_OUT_F32), Vt (fp16), GroupNorm partials (fp32). */
+enum tsd_gemm_operand { TSD_GO_A0 = 0, TSD_GO_A1, TSD_GO_A2, TSD_GO_W, TSD_GO_WT1, TSD_GO_R, TSD_GO_BIAS, TSD_GO_ROWVEC, TSD_GO_C,
+                        TSD_GO_VT, TSD_GO_GN, TSD_GO_COUNT };
+/* on != 0: clear the list and record the descriptor of every GEMM launch enqueued on this context from now on (planning passes
+ * do not count); on == 0: stop.  Returns the number of descriptors held. */
+int tsd_debug_gemm_record(tsd_ctx* ctx, int on);
+/* Copy recorded descriptor i (n >= TSD_GD_COUNT fields) into desc; returns TSD_GD_COUNT. */
+int tsd_debug_gemm_recorded(tsd_ctx* ctx, int i, int64_t* desc, int n);
+/* Run one launch described by desc on caller operands (host_in[TSD_GO_A0 .. TSD_GO_ROWVEC]; NULL for unused slots) and return
+ * its outputs (host_out[TSD_GO_C .. TSD_GO_GN] at index slot - TSD_GO_C).  Every operand is passed in its device layout - element
+ * i of slot s at offset i, ext[s] elements - except W under W_KTS, which is row-major [N][K] (the entry builds the K-tile-major
+ * copy).  host_in == NULL only sizes (ctx may be NULL): ext[TSD_GO_COUNT] receives every slot's extent (0 = unused).
+ * cfg < 0: the dispatcher's choice (split-K included, SK_BIG applied for the call); cfg >= 0: that tile configuration, no split.
+ * Inputs and outputs sit between 4 KiB guard bands of a NaN pattern; outputs are pre-filled with it (C with R when ALIAS bit 0).
+ * info[0] configuration, [1] split-K slices that ran, [2] guard / pitch-gap elements the launch changed.  The outputs are
+ * returned even when the launch is refused (its status is the return value). */
+int tsd_debug_gemm_run(tsd_ctx* ctx, const int64_t* desc, int n, int cfg, const void* const* host_in, void* const* host_out,
+                       int64_t* ext, int64_t* info);
+/* Attention blocks that run op by op (C = 640 / 1280) fold GEGLU's second linear into the output 1x1 convolution at tsd_model_prepare:
+ * wf [C][5C] fp16 = [W_out . W_2 | W_out], bf [C] = W_out . b_2 + b_out.  Copies block `block`'s (index into the UNet's layers; NULL
+ * pointers only ask) and returns C, 0 when that block does not fold.  tsd_model_prepare returns TSD_E_NONFINITE when a folded weight
+ * leaves fp16. */
+int tsd_debug_model_fold(tsd_model* m, int block, void* wf, float* bf);
+/* tsd_debug_gemm_bench for the fused attention core: Q,K [B][S][H*d], V^T [B][H*d][Sk]. */
 int tsd_debug_attn_bench(tsd_ctx* ctx, int B, int H, int d, int Sq, int Sk, int iters, float* ms);
 /* The fused attention core runs an optimistic softmax pass (reference fixed after the first key tile) and repeats a
  * workgroup exactly when one of its rows overflowed fp16: number of workgroups that repeated since the last reset

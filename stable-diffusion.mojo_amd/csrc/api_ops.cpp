@@ -3,6 +3,9 @@
 // kernels the module path uses, converts back and synchronises - these are the parity/drop-in
 // surface of the individual reference structs, not the measured path.
 #include <math.h>
+#include <string.h>
+
+#include <algorithm>
 
 #include "graph.h"
 
@@ -542,4 +545,277 @@ extern "C" int tsd_vae_attention_block_f32(tsd_ctx* ctx, const float* x, int C, 
     TSD_TRY(launch_nhwc_f16_to_chw_f32(ctx, out.p, 1, C, H, W, C, dy));
     return d.out(y, dy, (int64_t)C * H * W);
   });
+}
+
+// ---- GEMM launch descriptors: record and replay (tests/gemm_ref.py holds each launch to an fp64 reference) -------------------
+void gemm_describe(const tsd_ctx* ctx, const GemmArgs& a, int64_t* d) {
+  for (int i = 0; i < TSD_GD_COUNT; i++) d[i] = 0;
+  d[TSD_GD_VERSION] = TSD_GD_VERSION_1;
+  d[TSD_GD_CONV] = a.conv; d[TSD_GD_M] = a.M; d[TSD_GD_N] = a.N; d[TSD_GD_K] = a.K;
+  d[TSD_GD_K0] = (!a.conv && a.A1) ? a.K0 : a.K;  // what launch_gemm hands the kernel
+  d[TSD_GD_LDA0] = a.lda0; d[TSD_GD_LDA1] = a.lda1; d[TSD_GD_LDA2] = a.lda2; d[TSD_GD_LDW] = a.ldw; d[TSD_GD_LDW1] = a.ldw1;
+  d[TSD_GD_LDR] = a.ldr; d[TSD_GD_LDC] = a.ldc;
+  d[TSD_GD_BATCH] = a.batch; d[TSD_GD_SA] = a.sA; d[TSD_GD_SW] = a.sW; d[TSD_GD_SC] = a.sC; d[TSD_GD_SR] = a.sR;
+  if (a.conv) {
+    d[TSD_GD_HS] = a.Hs; d[TSD_GD_WS] = a.Ws; d[TSD_GD_HO] = a.Ho; d[TSD_GD_WO] = a.Wo; d[TSD_GD_CIN] = a.Cin;
+    d[TSD_GD_STRIDE] = a.stride; d[TSD_GD_PAD] = a.pad; d[TSD_GD_UPS] = a.ups; d[TSD_GD_CIN1] = a.Cin1; d[TSD_GD_CIN2] = a.Cin2;
+  }
+  d[TSD_GD_W_KTS] = a.w_kts ? 1 : 0;
+  d[TSD_GD_EPI] = a.epi;
+  uint32_t bits;
+  memcpy(&bits, &a.out_scale, 4);
+  d[TSD_GD_OUT_SCALE] = bits;
+  d[TSD_GD_ROWVEC_LD] = a.rowvec_ld; d[TSD_GD_ROWS_PER_BATCH] = a.rows_per_batch;
+  if (a.Vt) { d[TSD_GD_VT] = 1; d[TSD_GD_VT_N0] = a.vt_n0; d[TSD_GD_VT_LD] = a.vt_ld; d[TSD_GD_VT_S] = a.vt_S; d[TSD_GD_VT_SB] = a.vt_sB; }
+  d[TSD_GD_GN_GROUPS] = a.gn_groups; d[TSD_GD_GN_RPS] = a.gn_rows_per_sample; d[TSD_GD_GN_NSLAB] = a.gn_nslab;
+  d[TSD_GD_RPS_HINT] = a.rows_per_sample_hint; d[TSD_GD_SK_BIG] = ctx->opt.sk_big_graph;
+  d[TSD_GD_ALIAS] = (a.R && (const void*)a.R == a.C ? 1 : 0) | (a.A1 && a.A1 == a.A0 ? 2 : 0) | (a.A2 && a.A2 == a.A1 ? 4 : 0);
+  d[TSD_GD_CFG] = -1; d[TSD_GD_WAYS] = 0;
+}
+
+extern "C" int tsd_debug_gemm_record(tsd_ctx* ctx, int on) {
+  NOTNULL(ctx);
+  if (on) ctx->gemm_rec.clear();
+  ctx->gemm_rec_on = on != 0;
+  return (int)(ctx->gemm_rec.size() / TSD_GD_COUNT);
+}
+
+extern "C" int tsd_debug_gemm_recorded(tsd_ctx* ctx, int i, int64_t* desc, int n) {
+  NOTNULL(ctx); NOTNULL(desc);
+  if (n < TSD_GD_COUNT || i < 0 || (size_t)(i + 1) * TSD_GD_COUNT > ctx->gemm_rec.size())
+    TSD_FAIL(TSD_E_ARG, "gemm_recorded: no descriptor %d (capacity %d)", i, n);
+  memcpy(desc, &ctx->gemm_rec[(size_t)i * TSD_GD_COUNT], TSD_GD_COUNT * sizeof(int64_t));
+  return TSD_GD_COUNT;
+}
+
+namespace {
+constexpr size_t GD_GUARD = 4096;                     // bytes of NaN pattern before and after every operand
+constexpr uint16_t GD_NAN16 = 0x7E5A;                 // fp16 quiet NaN
+constexpr uint32_t GD_NAN32 = 0x7FC5A5A5u;            // fp32 quiet NaN (a byte-wise fill that is an fp16 NaN is a finite fp32)
+int gd_elem_bytes(int slot, const int64_t* d) {
+  if (slot == TSD_GO_BIAS || slot == TSD_GO_ROWVEC || slot == TSD_GO_GN) return 4;
+  if (slot == TSD_GO_C && (d[TSD_GD_EPI] & EPI_OUT_F32)) return 4;
+  return 2;
+}
+// Columns of C the launch stores (the Vt tail's columns go to Vt instead, GEGLU halves the width)
+int64_t gd_c_cols(const int64_t* d) {
+  if (d[TSD_GD_VT]) return d[TSD_GD_VT_N0];
+  return (d[TSD_GD_EPI] & EPI_GEGLU) ? d[TSD_GD_N] / 2 : d[TSD_GD_N];
+}
+// Element extent of every operand the descriptor reads or writes, including the kernel's clamped loads (bias / row vector at
+// N - 4, residual at N - 8: all inside [0, N)).  Refuses what it cannot size; the combinations launch_gemm itself refuses are left to it.
+int gd_extents(const int64_t* d, int64_t* e) {
+  for (int i = 0; i < TSD_GO_COUNT; i++) e[i] = 0;
+#define GD_REQ(cond) \
+  if (!(cond)) TSD_FAIL(TSD_E_ARG, "gemm_run: descriptor cannot be sized (%s)", #cond)
+  GD_REQ(d[TSD_GD_VERSION] == TSD_GD_VERSION_1);
+  const int64_t M = d[TSD_GD_M], N = d[TSD_GD_N], K = d[TSD_GD_K], K0 = d[TSD_GD_K0], batch = d[TSD_GD_BATCH], epi = d[TSD_GD_EPI];
+  const int64_t lim = 1LL << 30;
+  GD_REQ(M > 0 && N > 0 && K > 0 && M < (1 << 26) && N <= 65536 && K <= 65536 && N % 4 == 0);
+  GD_REQ(batch >= 1 && batch <= 4096 && epi >= 0 && epi < 256);
+  for (int f : {TSD_GD_LDA0, TSD_GD_LDA1, TSD_GD_LDA2, TSD_GD_LDW, TSD_GD_LDW1, TSD_GD_LDR, TSD_GD_LDC, TSD_GD_ROWVEC_LD, TSD_GD_VT_LD})
+    GD_REQ(d[f] >= 0 && d[f] <= 65536);
+  for (int f : {TSD_GD_SA, TSD_GD_SW, TSD_GD_SC, TSD_GD_SR, TSD_GD_VT_SB}) GD_REQ(d[f] >= 0 && d[f] <= lim);
+  const int64_t sA = d[TSD_GD_SA], sW = d[TSD_GD_SW], sC = d[TSD_GD_SC], sR = d[TSD_GD_SR];
+  int64_t KW = K, B = 1;
+  if (d[TSD_GD_CONV]) {
+    const int64_t Hs = d[TSD_GD_HS], Ws = d[TSD_GD_WS], Ho = d[TSD_GD_HO], Wo = d[TSD_GD_WO], Cin = d[TSD_GD_CIN];
+    const int64_t Cin1 = d[TSD_GD_CIN1], Cin2 = d[TSD_GD_CIN2];
+    GD_REQ(Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0 && Hs < 2048 && Ws < 2048 && Ho < 2048 && Wo < 2048 && Cin > 0 && Cin <= 8192);
+    GD_REQ(batch == 1 && M % (Ho * Wo) == 0 && d[TSD_GD_LDA0] >= Cin);
+    GD_REQ((d[TSD_GD_STRIDE] == 1 || d[TSD_GD_STRIDE] == 2) && (d[TSD_GD_UPS] == 0 || d[TSD_GD_UPS] == 1) && d[TSD_GD_PAD] >= 0 && d[TSD_GD_PAD] <= 1);
+    {  // Ho / Wo must follow from the source, stride, pad and a bottom / right pad of 0 or 1: the kernel packs each output pixel's
+       // first tap (o * stride - pad + 1) into an 11-bit field with the sample index above it, so a larger one would read another image
+      const int64_t st = d[TSD_GD_STRIDE], pad = d[TSD_GD_PAD], up = d[TSD_GD_UPS] ? 2 : 1;
+      bool geo = false;
+      for (int64_t br = 0; br <= 1; br++)
+        geo = geo || ((up * Hs + pad + br - 3) / st + 1 == Ho && (up * Ws + pad + br - 3) / st + 1 == Wo && up * Hs + pad + br >= 3 && up * Ws + pad + br >= 3);
+      GD_REQ(geo && (Ho - 1) * st - pad + 2 < 2048 && (Wo - 1) * st - pad + 2 < 2048);
+    }
+    B = M / (Ho * Wo);
+    const int64_t px = B * Hs * Ws;
+    e[TSD_GO_A0] = (px - 1) * d[TSD_GD_LDA0] + Cin;
+    KW = 9 * Cin;
+    GD_REQ(Cin1 >= 0 && Cin2 >= 0 && (Cin1 > 0 || Cin2 == 0));
+    if (Cin1 > 0) {  // the skip sources are read at the output pixel: same resolution
+      GD_REQ(Ho == Hs && Wo == Ws && d[TSD_GD_LDA1] >= Cin1 && d[TSD_GD_LDW1] >= Cin1 + Cin2);
+      e[TSD_GO_A1] = (px - 1) * d[TSD_GD_LDA1] + Cin1;
+      if (Cin2 > 0) {
+        GD_REQ(d[TSD_GD_LDA2] >= Cin2);
+        e[TSD_GO_A2] = (px - 1) * d[TSD_GD_LDA2] + Cin2;
+      }
+      e[TSD_GO_WT1] = (N - 1) * d[TSD_GD_LDW1] + Cin1 + Cin2;
+    }
+  } else {
+    GD_REQ(K0 > 0 && K0 <= K && d[TSD_GD_LDA0] >= K0);
+    e[TSD_GO_A0] = (batch - 1) * sA + (M - 1) * d[TSD_GD_LDA0] + K0;
+    if (K0 < K) {
+      GD_REQ(d[TSD_GD_LDA1] >= K - K0);
+      e[TSD_GO_A1] = (batch - 1) * sA + (M - 1) * d[TSD_GD_LDA1] + (K - K0);
+    }
+  }
+  if (d[TSD_GD_W_KTS]) {
+    GD_REQ(batch == 1 && KW % 64 == 0);
+    e[TSD_GO_W] = N * KW;  // passed row-major [N][KW]
+  } else {
+    GD_REQ(d[TSD_GD_LDW] >= KW);
+    e[TSD_GO_W] = (batch - 1) * sW + (N - 1) * d[TSD_GD_LDW] + KW;
+  }
+  const int64_t ccols = gd_c_cols(d);
+  GD_REQ(ccols > 0 && ccols <= N && d[TSD_GD_LDC] >= ccols);
+  e[TSD_GO_C] = (batch - 1) * sC + (M - 1) * d[TSD_GD_LDC] + ccols;
+  if (epi & (EPI_BIAS_N | EPI_BIAS_M)) e[TSD_GO_BIAS] = std::max((epi & EPI_BIAS_N) ? N : 0, (epi & EPI_BIAS_M) ? M : 0);
+  if (epi & EPI_ROWVEC) {
+    GD_REQ(d[TSD_GD_ROWS_PER_BATCH] >= 1 && (d[TSD_GD_ROWVEC_LD] == 0 || d[TSD_GD_ROWVEC_LD] >= N));
+    e[TSD_GO_ROWVEC] = ((M - 1) / d[TSD_GD_ROWS_PER_BATCH]) * d[TSD_GD_ROWVEC_LD] + N;
+  }
+  if (epi & EPI_RESIDUAL) {
+    if (d[TSD_GD_ALIAS] & 1) {  // in place: R is C's initial content
+      GD_REQ(!(epi & (EPI_RES_UPS | EPI_GEGLU | EPI_OUT_F32)) && !d[TSD_GD_VT] && d[TSD_GD_LDR] == d[TSD_GD_LDC] && sR == sC);
+      e[TSD_GO_R] = e[TSD_GO_C];
+    } else {
+      int64_t rows = M;
+      if (d[TSD_GD_CONV] && (epi & EPI_RES_UPS)) {
+        GD_REQ(d[TSD_GD_HO] % 2 == 0 && d[TSD_GD_WO] % 2 == 0);
+        rows = B * (d[TSD_GD_HO] / 2) * (d[TSD_GD_WO] / 2);
+      }
+      GD_REQ(d[TSD_GD_LDR] >= N);
+      e[TSD_GO_R] = (batch - 1) * sR + (rows - 1) * d[TSD_GD_LDR] + N;
+    }
+  }
+  if (d[TSD_GD_VT]) {
+    const int64_t n0 = d[TSD_GD_VT_N0], S = d[TSD_GD_VT_S];
+    GD_REQ(n0 > 0 && n0 < N && S > 0 && M % S == 0 && d[TSD_GD_VT_LD] >= S && d[TSD_GD_VT_SB] >= (N - n0 - 1) * d[TSD_GD_VT_LD] + S);
+    e[TSD_GO_VT] = (M / S - 1) * d[TSD_GD_VT_SB] + (N - n0 - 1) * d[TSD_GD_VT_LD] + S;
+  }
+  if (epi & EPI_GNSTATS) {
+    const int64_t G = d[TSD_GD_GN_GROUPS], rps = d[TSD_GD_GN_RPS], ns = d[TSD_GD_GN_NSLAB];
+    GD_REQ(G > 0 && G <= N && rps > 0 && M % rps == 0 && ns > 0 && ns * 32 <= rps);
+    e[TSD_GO_GN] = (M / rps) * ns * G * 2;
+  }
+  for (int s = 0; s < TSD_GO_COUNT; s++) GD_REQ(e[s] >= 0 && e[s] <= lim);
+#undef GD_REQ
+  return TSD_OK;
+}
+// Elements of output slot s that the launch may write (1) - everything else of its extent is a pitch gap
+std::vector<char> gd_logical(int s, const int64_t* d, int64_t ext) {
+  std::vector<char> m((size_t)ext, s == TSD_GO_GN ? 1 : 0);
+  if (s == TSD_GO_C) {
+    const int64_t cols = gd_c_cols(d);
+    for (int64_t b = 0; b < d[TSD_GD_BATCH]; b++)
+      for (int64_t r = 0; r < d[TSD_GD_M]; r++) memset(&m[(size_t)(b * d[TSD_GD_SC] + r * d[TSD_GD_LDC])], 1, (size_t)cols);
+  } else if (s == TSD_GO_VT) {
+    for (int64_t b = 0; b < d[TSD_GD_M] / d[TSD_GD_VT_S]; b++)
+      for (int64_t c = 0; c < d[TSD_GD_N] - d[TSD_GD_VT_N0]; c++)
+        memset(&m[(size_t)(b * d[TSD_GD_VT_SB] + c * d[TSD_GD_VT_LD])], 1, (size_t)d[TSD_GD_VT_S]);
+  }
+  return m;
+}
+struct GdBufs {
+  char* p[TSD_GO_COUNT + 1] = {};  // + the K-tile-major weight copy
+  ~GdBufs() { for (char* q : p) if (q) (void)hipFree(q); }
+};
+}  // namespace
+
+extern "C" int tsd_debug_gemm_run(tsd_ctx* ctx, const int64_t* desc, int n, int cfg, const void* const* host_in,
+                                  void* const* host_out, int64_t* ext, int64_t* info) {
+  NOTNULL(desc); NOTNULL(ext);
+  if (n < TSD_GD_COUNT || cfg >= 64) TSD_FAIL(TSD_E_ARG, "gemm_run: %d descriptor fields, cfg %d", n, cfg);
+  TSD_TRY(gd_extents(desc, ext));
+  if (!host_in) return TSD_OK;  // sizing only: no context or device needed
+  NOTNULL(ctx); NOTNULL(host_out); NOTNULL(info);
+  const int64_t* d = desc;
+  const bool alias = (d[TSD_GD_EPI] & EPI_RESIDUAL) && (d[TSD_GD_ALIAS] & 1);
+  for (int s = 0; s < TSD_GO_COUNT; s++) {
+    if (!ext[s]) continue;
+    if (s < TSD_GO_C ? !host_in[s] : !host_out[s - TSD_GO_C]) TSD_FAIL(TSD_E_ARG, "gemm_run: operand slot %d is NULL", s);
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  GdBufs bufs;
+  std::vector<char> init[TSD_GO_COUNT];  // outputs: guards + extent as filled before the launch
+  auto fill = [&](char* p, size_t elems, int es) -> int {
+    if (es == 2) HIP_TRY(hipMemsetD16Async((hipDeviceptr_t)p, GD_NAN16, elems, st));
+    else HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)p, (int)GD_NAN32, elems, st));
+    return TSD_OK;
+  };
+  for (int s = 0; s < TSD_GO_COUNT; s++) {
+    if (!ext[s] || (s == TSD_GO_R && alias)) continue;
+    const int es = gd_elem_bytes(s, d);
+    const size_t bytes = 2 * GD_GUARD + (size_t)ext[s] * es;
+    HIP_TRY(hipMalloc((void**)&bufs.p[s], bytes));
+    TSD_TRY(fill(bufs.p[s], bytes / es, es));
+    if (s < TSD_GO_C) HIP_TRY(hipMemcpyAsync(bufs.p[s] + GD_GUARD, host_in[s], (size_t)ext[s] * es, hipMemcpyHostToDevice, st));
+    else {
+      init[s].resize(bytes);
+      for (size_t i = 0; i < bytes; i += es) {
+        if (es == 2) memcpy(&init[s][i], &GD_NAN16, 2);
+        else memcpy(&init[s][i], &GD_NAN32, 4);
+      }
+      if (s == TSD_GO_C && alias) {
+        HIP_TRY(hipMemcpyAsync(bufs.p[s] + GD_GUARD, host_in[TSD_GO_R], (size_t)ext[s] * es, hipMemcpyHostToDevice, st));
+        memcpy(&init[s][GD_GUARD], host_in[TSD_GO_R], (size_t)ext[s] * es);
+      }
+    }
+  }
+  auto at = [&](int s) -> void* { return bufs.p[s] ? (void*)(bufs.p[s] + GD_GUARD) : nullptr; };
+  GemmArgs g;
+  g.conv = (int)d[TSD_GD_CONV]; g.M = (int)d[TSD_GD_M]; g.N = (int)d[TSD_GD_N]; g.K = (int)d[TSD_GD_K];
+  g.A0 = (const half_t*)at(TSD_GO_A0); g.lda0 = (int)d[TSD_GD_LDA0];
+  g.A1 = (const half_t*)at(TSD_GO_A1); g.lda1 = (int)d[TSD_GD_LDA1]; g.K0 = (int)d[TSD_GD_K0];
+  g.A2 = (const half_t*)at(TSD_GO_A2); g.lda2 = (int)d[TSD_GD_LDA2];
+  g.Wt = (const half_t*)at(TSD_GO_W); g.ldw = (int)d[TSD_GD_LDW];
+  g.Wt1 = (const half_t*)at(TSD_GO_WT1); g.ldw1 = (int)d[TSD_GD_LDW1];
+  g.batch = (int)d[TSD_GD_BATCH]; g.sA = d[TSD_GD_SA]; g.sW = d[TSD_GD_SW]; g.sC = d[TSD_GD_SC]; g.sR = d[TSD_GD_SR];
+  if (g.conv) {
+    g.Hs = (int)d[TSD_GD_HS]; g.Ws = (int)d[TSD_GD_WS]; g.Ho = (int)d[TSD_GD_HO]; g.Wo = (int)d[TSD_GD_WO]; g.Cin = (int)d[TSD_GD_CIN];
+    g.stride = (int)d[TSD_GD_STRIDE]; g.pad = (int)d[TSD_GD_PAD]; g.ups = (int)d[TSD_GD_UPS];
+    g.Cin1 = (int)d[TSD_GD_CIN1]; g.Cin2 = (int)d[TSD_GD_CIN2];
+  }
+  g.epi = (int)d[TSD_GD_EPI];
+  const uint32_t bits = (uint32_t)d[TSD_GD_OUT_SCALE];
+  memcpy(&g.out_scale, &bits, 4);
+  g.bias = (const float*)at(TSD_GO_BIAS);
+  g.rowvec = (const float*)at(TSD_GO_ROWVEC); g.rowvec_ld = (int)d[TSD_GD_ROWVEC_LD]; g.rows_per_batch = (int)d[TSD_GD_ROWS_PER_BATCH];
+  g.R = (const half_t*)(alias ? at(TSD_GO_C) : at(TSD_GO_R)); g.ldr = (int)d[TSD_GD_LDR];
+  g.C = at(TSD_GO_C); g.ldc = (int)d[TSD_GD_LDC];
+  if (d[TSD_GD_VT]) { g.Vt = (half_t*)at(TSD_GO_VT); g.vt_n0 = (int)d[TSD_GD_VT_N0]; g.vt_ld = (int)d[TSD_GD_VT_LD]; g.vt_S = (int)d[TSD_GD_VT_S]; g.vt_sB = d[TSD_GD_VT_SB]; }
+  g.gn_part = (float*)at(TSD_GO_GN); g.gn_groups = (int)d[TSD_GD_GN_GROUPS]; g.gn_rows_per_sample = (int)d[TSD_GD_GN_RPS]; g.gn_nslab = (int)d[TSD_GD_GN_NSLAB];
+  g.rows_per_sample_hint = (int)d[TSD_GD_RPS_HINT];
+  if (d[TSD_GD_W_KTS]) {  // the K-tile-major copy the model path builds for weight-heavy layers
+    const int KW = g.conv ? 9 * g.Cin : g.K;
+    HIP_TRY(hipMalloc((void**)&bufs.p[TSD_GO_COUNT], 2 * GD_GUARD + (size_t)g.N * KW * 2));
+    TSD_TRY(fill(bufs.p[TSD_GO_COUNT], (2 * GD_GUARD) / 2 + (size_t)g.N * KW, 2));
+    half_t* tm = (half_t*)(bufs.p[TSD_GO_COUNT] + GD_GUARD);
+    TSD_TRY(launch_pack_tile_major(ctx, g.Wt, g.N, KW, tm));
+    g.Wt = tm; g.ldw = 64; g.w_kts = g.N * 128;
+  }
+  // the dispatcher's choice (with the recorded graph's long-K split) or a forced tile; a replay is not recorded
+  const int prev_force = ctx->opt.force_cfg, prev_big = ctx->opt.sk_big_graph;
+  const bool prev_rec = ctx->gemm_rec_on;
+  ctx->opt.force_cfg = cfg >= 0 ? cfg : -1;
+  if (cfg < 0) ctx->opt.sk_big_graph = (int)d[TSD_GD_SK_BIG];
+  ctx->gemm_rec_on = false;
+  ctx->gemm_last_cfg = -1; ctx->gemm_last_ways = 0;
+  const int r = run_planned(ctx, [&]() -> int { return launch_gemm(ctx, g); });
+  ctx->opt.force_cfg = prev_force; ctx->opt.sk_big_graph = prev_big; ctx->gemm_rec_on = prev_rec;
+  HIP_TRY(hipStreamSynchronize(st));
+  info[0] = ctx->gemm_last_cfg; info[1] = ctx->gemm_last_ways;
+  int64_t changed = 0;
+  for (int s = TSD_GO_C; s < TSD_GO_COUNT; s++) {
+    if (!ext[s]) continue;
+    const int es = gd_elem_bytes(s, d);
+    std::vector<char> got(init[s].size());
+    HIP_TRY(hipMemcpy(got.data(), bufs.p[s], got.size(), hipMemcpyDeviceToHost));
+    const std::vector<char> logical = gd_logical(s, d, ext[s]);
+    const int64_t g0 = (int64_t)(GD_GUARD / es), total = (int64_t)(got.size() / es);
+    for (int64_t i = 0; i < total; i++) {
+      const int64_t j = i - g0;
+      if (j >= 0 && j < ext[s] && logical[(size_t)j]) continue;
+      if (memcmp(&got[(size_t)i * es], &init[s][(size_t)i * es], es)) changed++;
+    }
+    memcpy(host_out[s - TSD_GO_C], &got[GD_GUARD], (size_t)ext[s] * es);
+  }
+  info[2] = changed;
+  return r;
 }

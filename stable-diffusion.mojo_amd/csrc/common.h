@@ -108,6 +108,10 @@ struct tsd_ctx {
   std::vector<int> prof_kern;   // kernel dispatches per record
   std::vector<int> prof_shape;  // 4 ints per record (M, N, K, batch) - 0 when not a GEMM
   size_t prof_n = 0;
+  // tsd_debug_gemm_record: TSD_GD_COUNT descriptor fields per GEMM launch enqueued while on; the dispatcher's last choice
+  bool gemm_rec_on = false;
+  std::vector<int64_t> gemm_rec;
+  int gemm_last_cfg = -1, gemm_last_ways = 0;
 };
 
 enum KernelClass : int {
@@ -246,6 +250,8 @@ struct GemmArgs {
   int rows_per_sample_hint = 0;
 };
 int launch_gemm(tsd_ctx* ctx, const GemmArgs& a);
+// the launch as a tsd_debug_gemm_* descriptor (TSD_GD_COUNT fields; api_ops.cpp)
+void gemm_describe(const tsd_ctx* ctx, const GemmArgs& a, int64_t* desc);
 // slices of the long-K split launches (K >= 8192, 16x16 level) for the graph being enqueued on this context; returns the previous value
 int gemm_set_splitk_big(tsd_ctx* ctx, int ways);
 int gemm_gnstats_slabs(const tsd_ctx* ctx, int M, int N, int K, int batch, int conv, int rows_per_sample, int groups);  // 0: not available

@@ -1365,7 +1365,10 @@ static void cfg_wave_tile(int id, int* bmw, int* bnw) {
 int gemm_gnstats_slabs(const tsd_ctx* ctx, int M, int N, int K, int batch, int conv, int rows_per_sample, int groups) {
   if (groups <= 0 || N % groups || (N & 7) || batch != 1) return 0;
   int bmw, bnw;
-  cfg_wave_tile(choose_cfg(ctx->opt, M, N, K, batch, conv != 0, rows_per_sample), &bmw, &bnw);
+  // the tile that will run: a forced configuration (tsd_debug_gemm_run) must be judged by its own wave tile - one whose wave columns
+  // split a group would write that group's slot from two waves
+  const int id = ctx->opt.force_cfg >= 0 ? ctx->opt.force_cfg : choose_cfg(ctx->opt, M, N, K, batch, conv != 0, rows_per_sample);
+  cfg_wave_tile(id, &bmw, &bnw);
   const int cpg = N / groups;
   if (!bmw || bnw % cpg || rows_per_sample % bmw || M % rows_per_sample) return 0;
   return rows_per_sample / 32;  // one slab per 32-row epilogue pass, independent of the tile shape
@@ -1384,6 +1387,11 @@ static int dispatch(tsd_ctx* ctx, const GemmK& k, int batch) {
   // the scratch is gone (conv_tap_ptrs); TSD_GEMM_SKIP128=0 restores the detour for A/B runs
   if (CONV && force_cfg < 0 && k.Cin1 > 0 && id == 2 && !o.skip128) id = 3;
   if ((id == 30 || id == 32) && !(CONV && hx_shape_ok(k) && k.w_kts == 128u)) TSD_FAIL(TSD_E_ARG, "gemm: halo-x tile configuration %d on an ineligible problem", id);
+  ctx->gemm_last_cfg = id; ctx->gemm_last_ways = k.splitk;
+  if (ctx->gemm_rec_on && ctx->gemm_rec.size() >= TSD_GD_COUNT) {  // launch_gemm recorded this launch's descriptor last
+    int64_t* d = &ctx->gemm_rec[ctx->gemm_rec.size() - TSD_GD_COUNT];
+    d[TSD_GD_CFG] = id; d[TSD_GD_WAYS] = k.splitk;
+  }
   return launch_by_id<CONV>(ctx, k, batch, id);
 }
 
@@ -1598,6 +1606,10 @@ int launch_gemm(tsd_ctx* ctx, const GemmArgs& a) {
     if (!sk_ws) TSD_FAIL(TSD_E_ALLOC, "gemm: split-K workspace exhausted");
   }
   if (!ctx->launch()) return TSD_OK;
+  if (ctx->gemm_rec_on) {
+    ctx->gemm_rec.resize(ctx->gemm_rec.size() + TSD_GD_COUNT);
+    gemm_describe(ctx, a, &ctx->gemm_rec[ctx->gemm_rec.size() - TSD_GD_COUNT]);
+  }
   ProfScope prof(ctx, a.conv ? KC_CONV : KC_GEMM, a.M, a.N, a.K, a.batch);
   GemmK k;
   k.A0 = a.A0; k.A1 = a.A1; k.Wt = a.Wt; k.R = a.R; k.zeros = ctx->zeros;

@@ -1,5 +1,6 @@
 // model.cpp - device-resident packed weights: one blob per model (what RCCL broadcasts),
 // per-parameter upload/pack, synthetic counter-RNG init, and the resolved weight trees.
+#include <math.h>
 #include <string.h>
 
 #include "model.h"
@@ -311,6 +312,32 @@ static int model_build_derived(tsd_model* m) {
       off += 2 * wb + ((((size_t)C * 4) + 255) & ~size_t(255));
     }
   }
+  // A folded weight is a product of two weight matrices rounded to fp16 once: one that leaves fp16 (or a non-finite bias) must not be
+  // silent.  Host-side scan, once per build of the derived buffers.
+  if (r == TSD_OK && !fold.empty()) {
+    hipError_t e = hipStreamSynchronize(ctx->stream);
+    for (size_t i = 0; i < fold.size() && r == TSD_OK && e == hipSuccess; i++) {
+      const AttnW* a = fold[i];
+      const int C = a->C;
+      std::vector<uint16_t> hw((size_t)C * 5 * C);
+      std::vector<float> hb(C);
+      e = hipMemcpy(hw.data(), a->fold_w, hw.size() * 2, hipMemcpyDeviceToHost);
+      if (e == hipSuccess) e = hipMemcpy(hb.data(), a->fold_b, hb.size() * 4, hipMemcpyDeviceToHost);
+      if (e != hipSuccess) break;
+      int64_t bad = 0;
+      for (uint16_t v : hw) bad += (v & 0x7C00) == 0x7C00;
+      for (float v : hb) bad += !(fabsf(v) <= 3.4028235e38f);
+      if (bad) {
+        fold[i]->fold_w = nullptr; fold[i]->fold_w_tm = nullptr; fold[i]->fold_b = nullptr;
+        tsd_set_error("attention block with C = %d: %lld folded weights / biases are not finite (W_out . W_2 leaves fp16)", C, (long long)bad);
+        r = TSD_E_NONFINITE;
+      }
+    }
+    if (e != hipSuccess && r == TSD_OK) {
+      tsd_set_error("fold check: %s", hipGetErrorString(e));
+      r = TSD_E_HIP;
+    }
+  }
   ctx->arena.planning = was_planning;
   return r;
 }
@@ -331,6 +358,22 @@ extern "C" int tsd_model_prepare(tsd_model* m) {
   TSD_TRY(model_check_ready(m));
   HIP_TRY(hipStreamSynchronize(m->ctx->stream));
   return TSD_OK;
+}
+
+// Debug entry: the folded [C][5C] fp16 weight and fp32 bias of attention block `block` (index into the UNet's layers); returns C,
+// 0 when that block does not fold
+extern "C" int tsd_debug_model_fold(tsd_model* m, int block, void* wf, float* bf) {
+  if (!m) TSD_FAIL(TSD_E_ARG, "NULL model");
+  if (!is_diffusion_kind(m->kind) || block < 0 || block >= (int)m->unet.attn.size())
+    TSD_FAIL(TSD_E_ARG, "model_fold: no attention block %d in this model", block);
+  HIP_TRY(hipSetDevice(m->ctx->device));
+  TSD_TRY(model_check_ready(m));
+  const AttnW& a = m->unet.attn[block];
+  if (!a.fold_w) return 0;
+  HIP_TRY(hipStreamSynchronize(m->ctx->stream));
+  if (wf) HIP_TRY(hipMemcpy(wf, a.fold_w, (size_t)a.C * 5 * a.C * 2, hipMemcpyDeviceToHost));
+  if (bf) HIP_TRY(hipMemcpy(bf, a.fold_b, (size_t)a.C * 4, hipMemcpyDeviceToHost));
+  return a.C;
 }
 
 ConvW model_conv(const tsd_model* m, const std::string& prefix) {

@@ -120,6 +120,10 @@ def _declare(l):
         "tsd_debug_set_qkv_fuse": ([vp, i], i),
         "tsd_debug_mfma_sustained": ([vp, C.c_float, fp, fp], i),
         "tsd_debug_gemm_check": ([vp, i, i, i, i, i, i, i, i, i, i, fp, fp], i),
+        "tsd_debug_gemm_record": ([vp, i], i),
+        "tsd_debug_gemm_recorded": ([vp, i, C.POINTER(i64), i], i),
+        "tsd_debug_model_fold": ([vp, i, vp, fp], i),
+        "tsd_debug_gemm_run": ([vp, C.POINTER(i64), i, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(l, name)

@@ -1,0 +1,474 @@
+"""fp64 reference and element-wise error bound for one GEMM / conv3x3 launch of csrc/kernels_gemm.hip (test infrastructure).
+
+A launch is a descriptor: the int64 TSD_GD_* fields of include/tsd.h, one per GemmArgs field, parsed from the header so the two
+sides cannot drift.  Operands are flat numpy arrays in the device layout (pitches, batch strides) - fp16 for A0 / A1 / A2 / W /
+Wt1 / R, fp32 for the bias and the row vector - exactly what tsd_debug_gemm_run uploads; W is row-major [N][KW] (KW = 9*Cin for a
+convolution, K for a dense GEMM) whatever the launch reads.  Elements that no launch may read (pitch gaps) hold NaN, so an
+over-read shows up as a non-finite output.
+
+`reference(desc, ops, rows)` computes, in float64 from those fp16 values, what the kernel computes for the selected output rows:
+
+    v = out_scale * sum_k a[m][k] w[n][k] + bias[m] + bias[n] + rowvec[(m / rows_per_batch) * rowvec_ld + n] + R[m'][n]
+
+(m' = m, or the pixel of the 2x-upsampled (Ho/2, Wo/2) residual under EPI_RES_UPS), then either GEGLU on the interleaved
+(a, g) column pairs, out[m][n/2] = a * gelu_tanh(g), or the plain store; with a V^T tail the columns n >= vt_n0 go to
+Vt[(m / vt_S) * vt_sB + (n - vt_n0) * vt_ld + m % vt_S] instead of C.
+
+The bound (`bound`) follows the rounding points of the kernel, u = 2^-24 (fp32 unit roundoff):
+  * products of two fp16 values are exact in fp32; the K-long fp32 accumulation (MFMA adds, the split-K hand-off) loses at
+    most K * u' per add relative to the sum of |products|, and u' = 2u because the matrix core's internal adds may truncate
+    instead of rounding: e_acc = 2 K u |out_scale| sum_k |a||w|.  (The scale multiply adds one more u |out_scale * acc|.)
+  * every epilogue add (bias_m, bias_n, rowvec, residual) rounds once in fp32: at most u times the running magnitude, bounded
+    by S = |out_scale| sum|a||w| + |bias_m| + |bias_n| + |rowvec| + |r|, so e_add = (terms + 1) u S.
+  * e32 = e_acc + e_add is the error of the fp32 value y32 the kernel stores or rounds.  The fp16 store adds at most
+    2^-11 |y32| <= 2^-11 (|ref| + e32) (round to nearest), plus 2^-25 in fp16's subnormal range.  EPI_OUT_F32 drops that term.
+  * GEGLU: with e_a, e_g the fp32 errors of the two columns, |a gelu(g) - a' gelu(g')| <= |gelu(g)| e_a + (|a| + e_a) max|gelu'| e_g
+    (max |gelu_tanh'| < 1.13), plus gelu_tanh_f's own error: its exp2 / rcp are 1-ulp approximations and the argument
+    c (x + 0.044715 x^3) carries a few roundings, which move exp2's result by ln2 |arg| ulps - (6 + 4 |arg|) u relative to the
+    product covers them and the final multiply.
+So the bound is |y - ref| <= 2^-11 |ref| + (1 + 2^-11) e + 2^-25 with e the fp32 error above.  With operands scaled so that the
+product, bias, row vector and residual are of the same order, a missing, doubled or misplaced epilogue term is far above it.
+
+GroupNorm statistics (EPI_GNSTATS) are checked against fp64 sums over the device's own fp16 output (what the kernel sums):
+per (sample, 32-row slab, group) sum x and sum x^2, each an fp32 sum of 32 * cpg terms.
+"""
+import os
+import re
+
+import numpy as np
+
+_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_HDR = os.path.join(_ROOT, "include", "tsd.h")
+_COMMON = os.path.join(_ROOT, "stable-diffusion.mojo_amd", "csrc", "common.h")
+U32 = 2.0 ** -24
+GELU_DMAX = 1.13
+NAN16 = np.array([0x7E5A], np.uint16).view(np.float16)[0]
+NAN32 = np.array([0x7FC5A5A5], np.uint32).view(np.float32)[0]
+
+
+def _enum(txt, name):
+    body = re.search(r"enum\s+" + name + r"\s*\{(.*?)\}", txt, re.S).group(1)
+    out, v = {}, 0
+    for item in body.split(","):
+        item = item.strip()
+        if not item:
+            continue
+        if "=" in item:
+            k, val = (s.strip() for s in item.split("="))
+            v = int(val, 0)
+        else:
+            k = item
+        out[k] = v
+        v += 1
+    return out
+
+
+def _parse():
+    txt = re.sub(r"/\*.*?\*/", "", open(_HDR).read(), flags=re.S)
+    gd = {k[len("TSD_GD_"):]: v for k, v in _enum(txt, "tsd_gemm_desc_field").items()}
+    go = {k[len("TSD_GO_"):]: v for k, v in _enum(txt, "tsd_gemm_operand").items()}
+    ver = int(re.search(r"#define\s+TSD_GD_VERSION_1\s+(\d+)", txt).group(1))
+    ctxt = re.sub(r"//[^\n]*", "", open(_COMMON).read())
+    epi = {k: int(v) for k, v in re.findall(r"\bEPI_([A-Z0-9_]+)\s*=\s*(\d+)", ctxt)}
+    return gd, go, ver, epi
+
+
+GD, GO, GD_VERSION, EPI = _parse()
+COUNT = GD["COUNT"]
+INPUTS = ("A0", "A1", "A2", "W", "WT1", "R", "BIAS", "ROWVEC")
+OUTPUTS = ("C", "VT", "GN")
+
+
+def f32_bits(x):
+    return int(np.array([x], np.float32).view(np.uint32)[0])
+
+
+def new_desc(**f):
+    """Descriptor with defaults (batch 1, out_scale 1, one row per batch, pad 1, stride 1); keys are TSD_GD_* names, lower case."""
+    d = np.zeros(COUNT, np.int64)
+    d[GD["VERSION"]] = GD_VERSION
+    d[GD["BATCH"]] = 1
+    d[GD["OUT_SCALE"]] = f32_bits(1.0)
+    d[GD["ROWS_PER_BATCH"]] = 1
+    d[GD["STRIDE"]] = 1
+    d[GD["PAD"]] = 1
+    d[GD["CFG"]] = -1
+    for k, v in f.items():
+        if k == "out_scale":
+            v = f32_bits(v)
+        d[GD[k.upper()]] = int(v)
+    return d
+
+
+def conv_desc(B, Hs, Ws, Cin, N, stride=1, pad=1, pad_br=None, ups=0, Cin1=0, Cin2=0, lda0=None, lda1=None, lda2=None,
+              ldc=None, ldr=None, **f):
+    """conv3x3 over B images [Hs][Ws][lda0] with top/left padding `pad` and bottom/right `pad_br` (default = pad)."""
+    pad_br = pad if pad_br is None else pad_br
+    Hi, Wi = (2 * Hs, 2 * Ws) if ups else (Hs, Ws)
+    Ho, Wo = (Hi + pad + pad_br - 3) // stride + 1, (Wi + pad + pad_br - 3) // stride + 1
+    K = 9 * Cin + Cin1 + Cin2
+    return new_desc(conv=1, m=B * Ho * Wo, n=N, k=K, k0=K, hs=Hs, ws=Ws, ho=Ho, wo=Wo, cin=Cin, stride=stride, pad=pad, ups=ups,
+                    cin1=Cin1, cin2=Cin2, lda0=lda0 or Cin, lda1=(lda1 or Cin1) if Cin1 else 0, lda2=(lda2 or Cin2) if Cin2 else 0,
+                    ldw=9 * Cin, ldw1=Cin1 + Cin2, ldc=ldc or N, ldr=ldr or N, **f)
+
+
+def dense_desc(M, N, K, K0=None, lda0=None, lda1=None, ldw=None, ldc=None, ldr=None, **f):
+    K0 = K if K0 is None else K0
+    geglu = f.get("epi", 0) & EPI["GEGLU"]
+    return new_desc(conv=0, m=M, n=N, k=K, k0=K0, lda0=lda0 or K0, lda1=(lda1 or K - K0) if K0 < K else 0, ldw=ldw or K,
+                    ldc=ldc or (N // 2 if geglu else N), ldr=ldr or N, **f)
+
+
+def _g(d, k):
+    return int(d[GD[k]])
+
+
+def out_scale(d):
+    return float(np.array([_g(d, "OUT_SCALE")], np.uint32).view(np.float32)[0])
+
+
+def c_cols(d):
+    if _g(d, "VT"):
+        return _g(d, "VT_N0")
+    return _g(d, "N") // 2 if _g(d, "EPI") & EPI["GEGLU"] else _g(d, "N")
+
+
+def kw(d):
+    return 9 * _g(d, "CIN") if _g(d, "CONV") else _g(d, "K")
+
+
+def samples(d):
+    return _g(d, "M") // (_g(d, "HO") * _g(d, "WO")) if _g(d, "CONV") else 1
+
+
+def extents(d):
+    """Element extent of every operand slot (0 = unused): the restatement of the entry's sizing, held against it on the GPU."""
+    e = dict.fromkeys(INPUTS + OUTPUTS, 0)
+    M, N, K, K0, B, epi = (_g(d, k) for k in ("M", "N", "K", "K0", "BATCH", "EPI"))
+    sA, sW, sC, sR = (_g(d, k) for k in ("SA", "SW", "SC", "SR"))
+    if _g(d, "CONV"):
+        px = samples(d) * _g(d, "HS") * _g(d, "WS")
+        e["A0"] = (px - 1) * _g(d, "LDA0") + _g(d, "CIN")
+        c1, c2 = _g(d, "CIN1"), _g(d, "CIN2")
+        if c1:
+            e["A1"] = (px - 1) * _g(d, "LDA1") + c1
+            if c2:
+                e["A2"] = (px - 1) * _g(d, "LDA2") + c2
+            e["WT1"] = (N - 1) * _g(d, "LDW1") + c1 + c2
+    else:
+        e["A0"] = (B - 1) * sA + (M - 1) * _g(d, "LDA0") + K0
+        if K0 < K:
+            e["A1"] = (B - 1) * sA + (M - 1) * _g(d, "LDA1") + K - K0
+    e["W"] = N * kw(d) if _g(d, "W_KTS") else (B - 1) * sW + (N - 1) * _g(d, "LDW") + kw(d)
+    e["C"] = (B - 1) * sC + (M - 1) * _g(d, "LDC") + c_cols(d)
+    if epi & (EPI["BIAS_N"] | EPI["BIAS_M"]):
+        e["BIAS"] = max(N if epi & EPI["BIAS_N"] else 0, M if epi & EPI["BIAS_M"] else 0)
+    if epi & EPI["ROWVEC"]:
+        e["ROWVEC"] = ((M - 1) // _g(d, "ROWS_PER_BATCH")) * _g(d, "ROWVEC_LD") + N
+    if epi & EPI["RESIDUAL"]:
+        if _g(d, "ALIAS") & 1:
+            e["R"] = e["C"]
+        else:
+            rows = M
+            if _g(d, "CONV") and epi & EPI["RES_UPS"]:
+                rows = samples(d) * (_g(d, "HO") // 2) * (_g(d, "WO") // 2)
+            e["R"] = (B - 1) * sR + (rows - 1) * _g(d, "LDR") + N
+    if _g(d, "VT"):
+        S = _g(d, "VT_S")
+        e["VT"] = (M // S - 1) * _g(d, "VT_SB") + (N - _g(d, "VT_N0") - 1) * _g(d, "VT_LD") + S
+    if epi & EPI["GNSTATS"]:
+        e["GN"] = (M // _g(d, "GN_RPS")) * _g(d, "GN_NSLAB") * _g(d, "GN_GROUPS") * 2
+    return e
+
+
+def _mask_rows(ext, starts, width):
+    m = np.zeros(ext, bool)
+    starts = np.asarray(starts, np.int64)
+    if len(starts) == 1 or (np.diff(starts) == width).all():  # packed rows: one contiguous run
+        m[starts[0]:starts[-1] + width] = True
+        return m
+    idx = (np.asarray(starts, np.int64)[:, None] + np.arange(width)[None, :]).ravel()
+    m[idx] = True
+    return m
+
+
+def input_masks(d):
+    """Elements of each input the launch may read (True); the rest are pitch gaps."""
+    e = extents(d)
+    M, N, K, K0, B = (_g(d, k) for k in ("M", "N", "K", "K0", "BATCH"))
+    out = {}
+    rows_b = lambda s, ld, n_rows: (np.arange(B)[:, None] * s + np.arange(n_rows)[None, :] * ld).ravel()  # noqa: E731
+    if _g(d, "CONV"):
+        px = samples(d) * _g(d, "HS") * _g(d, "WS")
+        out["A0"] = _mask_rows(e["A0"], np.arange(px) * _g(d, "LDA0"), _g(d, "CIN"))
+        if e["A1"]:
+            out["A1"] = _mask_rows(e["A1"], np.arange(px) * _g(d, "LDA1"), _g(d, "CIN1"))
+        if e["A2"]:
+            out["A2"] = _mask_rows(e["A2"], np.arange(px) * _g(d, "LDA2"), _g(d, "CIN2"))
+        if e["WT1"]:
+            out["WT1"] = _mask_rows(e["WT1"], np.arange(N) * _g(d, "LDW1"), _g(d, "CIN1") + _g(d, "CIN2"))
+    else:
+        out["A0"] = _mask_rows(e["A0"], rows_b(_g(d, "SA"), _g(d, "LDA0"), M), K0)
+        if e["A1"]:
+            out["A1"] = _mask_rows(e["A1"], rows_b(_g(d, "SA"), _g(d, "LDA1"), M), K - K0)
+    if _g(d, "W_KTS"):
+        out["W"] = np.ones(e["W"], bool)
+    else:
+        out["W"] = _mask_rows(e["W"], rows_b(_g(d, "SW"), _g(d, "LDW"), N), kw(d))
+    for s in ("BIAS", "ROWVEC"):
+        if e[s]:
+            m = np.zeros(e[s], bool)
+            if s == "BIAS":
+                m[:] = True
+            else:
+                ld, rpb = _g(d, "ROWVEC_LD"), _g(d, "ROWS_PER_BATCH")
+                for r in range((M - 1) // rpb + 1):
+                    m[r * ld:r * ld + N] = True
+            out[s] = m
+    if e["R"]:
+        if _g(d, "ALIAS") & 1:
+            out["R"] = output_mask(d, "C")
+        else:
+            rows = M
+            if _g(d, "CONV") and _g(d, "EPI") & EPI["RES_UPS"]:
+                rows = samples(d) * (_g(d, "HO") // 2) * (_g(d, "WO") // 2)
+            out["R"] = _mask_rows(e["R"], rows_b(_g(d, "SR"), _g(d, "LDR"), rows), N)
+    return out
+
+
+def output_mask(d, slot):
+    e = extents(d)[slot]
+    M, N, B = _g(d, "M"), _g(d, "N"), _g(d, "BATCH")
+    if slot == "C":
+        starts = (np.arange(B)[:, None] * _g(d, "SC") + np.arange(M)[None, :] * _g(d, "LDC")).ravel()
+        return _mask_rows(e, starts, c_cols(d))
+    if slot == "VT":
+        S, n0 = _g(d, "VT_S"), _g(d, "VT_N0")
+        starts = (np.arange(M // S)[:, None] * _g(d, "VT_SB") + np.arange(N - n0)[None, :] * _g(d, "VT_LD")).ravel()
+        return _mask_rows(e, starts, S)
+    return np.ones(e, bool)
+
+
+def make_operands(d, seed, scale=None):
+    """Seeded operands in the device layout, NaN in every pitch gap.  Default scales put the product (A, W ~ U(-1, 1) / sqrt(K)
+    per term), the biases, the row vector and the residual at the same order (~0.3 - 0.6)."""
+    rng = np.random.default_rng(seed)
+    K = _g(d, "K")
+    sc = {"A0": 1.0, "A1": 1.0, "A2": 1.0, "W": 1.7 / np.sqrt(K), "WT1": 1.7 / np.sqrt(K), "R": 0.5, "BIAS": 0.5, "ROWVEC": 0.5}
+    if scale:
+        sc.update(scale)
+    masks = input_masks(d)
+    ops = {}
+    for s, n in extents(d).items():
+        if not n or s in OUTPUTS:
+            continue
+        dt = np.float32 if s in ("BIAS", "ROWVEC") else np.float16
+        x = (rng.uniform(-1.0, 1.0, n) * sc[s]).astype(dt)
+        x[~masks[s]] = NAN32 if dt == np.float32 else NAN16
+        ops[s] = x
+    return ops
+
+
+def _rows_geometry(d, rows):
+    """(batch index, row in batch) of flat output rows r in [0, batch * M)."""
+    M = _g(d, "M")
+    rows = np.asarray(rows, np.int64)
+    return rows // M, rows % M
+
+
+def gather_a(d, ops, rows):
+    """A[r][k] in float64 for the selected flat rows (conv: the implicit im2col, zero outside the image)."""
+    rows = np.asarray(rows, np.int64)
+    bz, m = _rows_geometry(d, rows)
+    K, K0 = _g(d, "K"), _g(d, "K0")
+    A = np.zeros((len(rows), K), np.float64)
+    if not _g(d, "CONV"):
+        a0 = ops["A0"].astype(np.float64)
+        base0 = bz * _g(d, "SA") + m * _g(d, "LDA0")
+        A[:, :K0] = a0[base0[:, None] + np.arange(K0)[None, :]]
+        if K0 < K:
+            a1 = ops["A1"].astype(np.float64)
+            base1 = bz * _g(d, "SA") + m * _g(d, "LDA1")
+            A[:, K0:] = a1[base1[:, None] + np.arange(K - K0)[None, :]]
+        return A
+    Hs, Ws, Ho, Wo, Cin = (_g(d, k) for k in ("HS", "WS", "HO", "WO", "CIN"))
+    st, pad, ups = _g(d, "STRIDE"), _g(d, "PAD"), _g(d, "UPS")
+    b, rem = m // (Ho * Wo), m % (Ho * Wo)
+    oy, ox = rem // Wo, rem % Wo
+    He, We = (2 * Hs, 2 * Ws) if ups else (Hs, Ws)
+    a0 = ops["A0"].astype(np.float64)
+    for t in range(9):
+        kh, kwi = divmod(t, 3)
+        iy, ix = oy * st - pad + kh, ox * st - pad + kwi
+        ok = (iy >= 0) & (iy < He) & (ix >= 0) & (ix < We)
+        sy, sx = (iy >> 1, ix >> 1) if ups else (iy, ix)
+        pix = np.where(ok, (b * Hs + sy) * Ws + sx, 0)
+        v = a0[pix[:, None] * _g(d, "LDA0") + np.arange(Cin)[None, :]]
+        A[:, t * Cin:(t + 1) * Cin] = np.where(ok[:, None], v, 0.0)
+    c1, c2 = _g(d, "CIN1"), _g(d, "CIN2")
+    if c1:
+        pix = (b * Hs + oy) * Ws + ox
+        A[:, 9 * Cin:9 * Cin + c1] = ops["A1"].astype(np.float64)[pix[:, None] * _g(d, "LDA1") + np.arange(c1)[None, :]]
+        if c2:
+            A[:, 9 * Cin + c1:] = ops["A2"].astype(np.float64)[pix[:, None] * _g(d, "LDA2") + np.arange(c2)[None, :]]
+    return A
+
+
+def weight(d, ops, bz=0):
+    """W[n][k] in float64 ([N][K]: the nine taps, then the fused skip's Cin1 + Cin2 channels)."""
+    N, KW = _g(d, "N"), kw(d)
+    w = ops["W"].astype(np.float64)
+    if _g(d, "W_KTS"):
+        Wm = w.reshape(N, KW)
+    else:
+        Wm = w[bz * _g(d, "SW") + np.arange(N)[:, None] * _g(d, "LDW") + np.arange(KW)[None, :]]
+    c = _g(d, "CIN1") + _g(d, "CIN2") if _g(d, "CONV") else 0
+    if c:
+        w1 = ops["WT1"].astype(np.float64)[np.arange(N)[:, None] * _g(d, "LDW1") + np.arange(c)[None, :]]
+        Wm = np.concatenate([Wm, w1], axis=1)
+    return Wm
+
+
+def gelu_tanh64(x):
+    return 0.5 * x * (1.0 + np.tanh(np.sqrt(2.0 / np.pi) * (x + 0.044715 * x ** 3)))
+
+
+def reference(d, ops, rows):
+    """Returns (v, e32, cout): v [len(rows)][N] fp64 pre-store values (after GEGLU: [len(rows)][N/2]), e32 their fp32 error
+    bound, cout the column count of the result."""
+    rows = np.asarray(rows, np.int64)
+    bz, m = _rows_geometry(d, rows)
+    N, K, epi = _g(d, "N"), _g(d, "K"), _g(d, "EPI")
+    s = out_scale(d)
+    A = gather_a(d, ops, rows)
+    acc = np.empty((len(rows), N))
+    sabs = np.empty((len(rows), N))
+    for b in np.unique(bz):
+        sel = bz == b
+        Wm = weight(d, ops, int(b))
+        acc[sel] = A[sel] @ Wm.T
+        sabs[sel] = np.abs(A[sel]) @ np.abs(Wm).T
+    v = s * acc
+    mag = abs(s) * sabs
+    e = 2 * K * U32 * mag + U32 * mag
+    terms = 0
+    if epi & EPI["BIAS_M"]:
+        t = ops["BIAS"].astype(np.float64)[m][:, None]
+        v, mag, terms = v + t, mag + np.abs(t), terms + 1
+    if epi & EPI["BIAS_N"]:
+        t = ops["BIAS"].astype(np.float64)[:N][None, :]
+        v, mag, terms = v + t, mag + np.abs(t), terms + 1
+    if epi & EPI["ROWVEC"] and _g(d, "CONV"):
+        rv = ops["ROWVEC"].astype(np.float64)
+        t = rv[(m // _g(d, "ROWS_PER_BATCH"))[:, None] * _g(d, "ROWVEC_LD") + np.arange(N)[None, :]]
+        v, mag, terms = v + t, mag + np.abs(t), terms + 1
+    if epi & EPI["RESIDUAL"]:
+        rrow = m
+        if _g(d, "CONV") and epi & EPI["RES_UPS"]:
+            Ho, Wo = _g(d, "HO"), _g(d, "WO")
+            bb, rem = m // (Ho * Wo), m % (Ho * Wo)
+            oy, ox = rem // Wo, rem % Wo
+            rrow = (bb * (Ho // 2) + oy // 2) * (Wo // 2) + ox // 2
+        R = ops["R"].astype(np.float64)
+        t = R[(bz * _g(d, "SR") + rrow * _g(d, "LDR"))[:, None] + np.arange(N)[None, :]]
+        v, mag, terms = v + t, mag + np.abs(t), terms + 1
+    e = e + (terms + 1) * U32 * mag
+    if epi & EPI["GEGLU"] and not _g(d, "CONV"):
+        a, g = v[:, 0::2], v[:, 1::2]
+        ea, eg = e[:, 0::2], e[:, 1::2]
+        gl = gelu_tanh64(g)
+        arg = np.abs(np.sqrt(2.0 / np.pi) * 2.0 * np.log2(np.e) * (g + 0.044715 * g ** 3))
+        y = a * gl
+        ey = np.abs(gl) * ea + (np.abs(a) + ea) * GELU_DMAX * eg + np.abs(y) * (6.0 + 4.0 * arg) * U32
+        return y, ey, N // 2
+    return v, e, N
+
+
+def bound(d, ref, e32):
+    if _g(d, "EPI") & EPI["OUT_F32"]:
+        return e32 + 2.0 ** -140
+    return 2.0 ** -11 * np.abs(ref) + (1.0 + 2.0 ** -11) * e32 + 2.0 ** -25
+
+
+def device_rows(d, out, rows, slot="C"):
+    """The device's values at the selected rows: C [len(rows)][cols] or the Vt tail [len(rows)][N - vt_n0], as float64."""
+    rows = np.asarray(rows, np.int64)
+    bz, m = _rows_geometry(d, rows)
+    if slot == "VT":
+        S, n0, N = _g(d, "VT_S"), _g(d, "VT_N0"), _g(d, "N")
+        idx = ((m // S) * _g(d, "VT_SB") + m % S)[:, None] + np.arange(N - n0)[None, :] * _g(d, "VT_LD")
+        return out.astype(np.float64)[idx]
+    cols = c_cols(d)
+    return out.astype(np.float64)[(bz * _g(d, "SC") + m * _g(d, "LDC"))[:, None] + np.arange(cols)[None, :]]
+
+
+def check(d, ops, outs, rows):
+    """Every sampled element of C (and Vt) within the bound.  Returns a list of failure strings (empty: pass)."""
+    rows = np.asarray(sorted(set(int(r) for r in rows)), np.int64)
+    ref, e32, _ = reference(d, ops, rows)
+    bd = bound(d, ref, e32)
+    fails = []
+    parts = [("C", ref[:, :c_cols(d)], bd[:, :c_cols(d)])]
+    if _g(d, "VT"):
+        n0 = _g(d, "VT_N0")
+        parts.append(("VT", ref[:, n0:], bd[:, n0:]))
+    for slot, r, b in parts:
+        got = device_rows(d, outs[slot], rows, slot)
+        err = np.abs(got - r)
+        bad = ~(err <= b)  # NaN fails
+        if bad.any():
+            i, j = np.argwhere(bad)[0]
+            fails.append(f"{slot}: {int(bad.sum())} of {bad.size} elements outside the bound; first row {rows[i]} col {j}: "
+                         f"got {got[i, j]!r} ref {r[i, j]:.6g} bound {b[i, j]:.3g}")
+    return fails
+
+
+def gn_reference(d, c_out):
+    """fp64 (sum, sum of squares) per (sample, 32-row slab, group) of the device's fp16 C, laid out like gn_part."""
+    M, N, G, rps, ns = (_g(d, k) for k in ("M", "N", "GN_GROUPS", "GN_RPS", "GN_NSLAB"))
+    cpg = N // G
+    y = device_rows(d, c_out, np.arange(M))  # [M][N]
+    y = y.reshape(M // rps, rps // 32, 32, G, cpg)[:, :ns]
+    s1 = y.sum(axis=(2, 4))
+    s2 = (y * y).sum(axis=(2, 4))
+    return np.stack([s1, s2], axis=-1).ravel(), np.stack([np.abs(y).sum(axis=(2, 4)), s2], axis=-1).ravel(), 32 * cpg
+
+
+def check_gn(d, c_out, gn):
+    """The partial sums: fp32 sums of 32 * cpg fp16-exact terms (squares rounded once) - n u per term magnitude, u' = 2u."""
+    ref, mag, n = gn_reference(d, c_out)
+    b = 2.0 * (n + 1) * U32 * mag + 2.0 ** -60
+    err = np.abs(gn.astype(np.float64) - ref)
+    bad = ~(err <= b)
+    if bad.any():
+        i = int(np.argmax(bad))
+        return [f"GN: {int(bad.sum())} of {bad.size} partials off; first index {i}: got {gn[i]!r} ref {ref[i]:.6g} bound {b[i]:.3g}"]
+    return []
+
+
+def sample_rows(d, seed, n_random=256):
+    """Row sample: first and last row of every 64-row block, sample boundaries +- 1, image-border pixels of conv outputs,
+    and `n_random` seeded rows (flat over the batch)."""
+    M, B = _g(d, "M"), _g(d, "BATCH")
+    tot = M * B
+    r = set()
+    for s in range(0, tot, 64):
+        r.update((s, min(s + 63, tot - 1)))
+    if _g(d, "CONV"):
+        Ho, Wo = _g(d, "HO"), _g(d, "WO")
+        hw = Ho * Wo
+        for b in range(M // hw):
+            for x in range(Wo):
+                r.update((b * hw + x, b * hw + (Ho - 1) * Wo + x))
+            for y in range(Ho):
+                r.update((b * hw + y * Wo, b * hw + y * Wo + Wo - 1))
+        bound_step = hw
+    else:
+        bound_step = _g(d, "RPS_HINT") or _g(d, "GN_RPS") or _g(d, "VT_S") or M
+    for s in range(0, tot + 1, max(bound_step, 1)):
+        r.update(x for x in (s - 1, s, s + 1) if 0 <= x < tot)
+    for s in range(0, tot + 1, M):
+        r.update(x for x in (s - 1, s, s + 1) if 0 <= x < tot)
+    rng = np.random.default_rng(seed)
+    r.update(int(x) for x in rng.integers(0, tot, n_random))
+    return np.array(sorted(r), np.int64)
