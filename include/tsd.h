@@ -246,6 +246,37 @@ int tsd_tokenizer_encode(const tsd_tokenizer* t, const char* text, int32_t* ids,
 /* pipeline.mojo:127 `rescale((-1,1),(0,255),clamp=True)` (helpers/utils.mojo:577-597). */
 int tsd_rescale_images_f32(tsd_ctx* ctx, const float* x, int64_t n, float* y);
 
+/* ---- samplers (EXTENSION: the reference has `DDPMSampler` only, sampler.mojo:5-124) ------------------------------------
+ * DDPM, DDIM(eta) and DPM-Solver++(2M) are one per-element update with per-step scalars,
+ *     e  = (eps - eps_uncond) * cfg_scale + eps_uncond        (pipeline.mojo:117-119; e = eps without eps_uncond)
+ *     x0 = (x - sigma_t e) / alpha_t                          alpha_t = sqrt(abar_t), sigma_t = sqrt(1 - abar_t)
+ *     x' = c_x x + c_e e + c_h h + c_n z                      h = the x0 of the previous step, z ~ N(0,1)
+ *     h' = x0
+ * TSD_SAMPLER_DDPM: Ho et al. 2020, eq. 7 (posterior mean and variance; what `DDPMSampler.step` sampler.mojo:75-109 computes).
+ * TSD_SAMPLER_DDIM: Song et al. 2021, eq. 12 with sigma = eta * (eq. 16); eta = 0 is deterministic, eta = 1 is DDPM.
+ * TSD_SAMPLER_DPMPP_2M: Lu et al. 2022, algorithm 2 (DPM-Solver++(2M), data prediction); first order (D = x0) on the first step,
+ *   on the step onto the clean sample and whenever no valid history exists.  Takes no noise.
+ * TSD_SPACING_LEADING: timesteps i * (N // n), the reference's (sampler.mojo:40-43).  TSD_SPACING_TRAILING:
+ *   round(N - k N/n) - 1, k = 0..n-1: starts at N - 1, what few-step sampling needs.  The previous timestep of step i is entry
+ *   i + 1 of the list; after the last entry comes the clean sample (abar = 1). */
+typedef enum tsd_sampler_kind { TSD_SAMPLER_DDPM = 0, TSD_SAMPLER_DDIM = 1, TSD_SAMPLER_DPMPP_2M = 2 } tsd_sampler_kind;
+typedef enum tsd_timestep_spacing { TSD_SPACING_LEADING = 0, TSD_SPACING_TRAILING = 1 } tsd_timestep_spacing;
+/* Host only, no GPU (like tsd_model_param_info).  The timestep list with the first `start_step` entries dropped (`set_strength`):
+ * writes min(count, cap) entries (timesteps may be NULL) and returns the count; < 0 on a bad argument. */
+int tsd_sampler_timesteps(int spacing, int n_train, int n_infer, int start_step, int* timesteps, int cap);
+/* Host only, no GPU.  The scalars of step i of that list, computed in double from the fp32 alphas_cumprod table (sampler.mojo:28-32):
+ * out[8] = { t, t_prev (-1 = the clean sample), alpha_t, sigma_t, c_x, c_e, c_h, c_n }.  eta is read by DDIM only; have_history by
+ * DPM-Solver++(2M) only (0 = first order).  A session with DDIM or DPM-Solver++(2M) steps with exactly these scalars rounded to
+ * float; a DDPM session keeps the reference's fp32 scalar arithmetic and update order (`DDPMSampler.step`), which this entry's
+ * DDPM row restates in double. */
+int tsd_sampler_coeffs(int kind, double eta, int spacing, int n_train, int n_infer, int start_step, int i, int have_history,
+                       double out[8]);
+/* Op level, host fp32 in/out like the other ops: one update of n elements with caller-given scalars
+ * c[6] = { alpha_t, sigma_t, c_x, c_e, c_h, c_n } - the kernel a DDIM / DPM-Solver++(2M) session launches.  eps_uncond, hist,
+ * noise and hist_out may be NULL (the term / the output is skipped).  x_out and hist_out may alias nothing. */
+int tsd_sampler_step_f32(tsd_ctx* ctx, const float* x, const float* eps, const float* eps_uncond, float cfg_scale,
+                         const float* hist, const float* noise, int64_t n, const float* c, float* x_out, float* hist_out);
+
 /* ---- device-resident denoise loop (pipeline.mojo:57-127 + sampler.mojo:15-124) --------- */
 
 /* B samples, latent side L, T context tokens; cfg != 0 runs the UNet on 2B (cond + uncond,
@@ -255,6 +286,12 @@ int tsd_session_destroy(tsd_session* s);
 /* `DDPMSampler.__init__` + `set_inference_timesteps` sampler.mojo:15-44 (+ `set_strength` :67-73 via
  * start_step: the first `start_step` timesteps are dropped).  beta 0.00085..0.012 scaled-linear. */
 int tsd_session_set_schedule(tsd_session* s, int num_training_steps, int num_inference_steps, int start_step);
+/* Choose the sampler (see "samplers" above; default TSD_SAMPLER_DDPM / TSD_SPACING_LEADING = the reference).  eta is read by DDIM
+ * only.  Rebuilds the timestep list and invalidates the upload exactly as tsd_session_set_schedule does: step() returns
+ * TSD_E_STATE until upload().  DPM-Solver++(2M) keeps the previous step's x0 on the device; it is valid for step i only if the
+ * previous call on the session was step(i - 1) since the last upload() / add_noise() / set_*() - otherwise step i runs first order.
+ * With DDPM or DDIM(eta > 0) and no uploaded noise the update is noiseless; DPM-Solver++(2M) ignores the noise. */
+int tsd_session_set_sampler(tsd_session* s, int kind, float eta, int spacing);
 int tsd_session_num_steps(tsd_session* s);
 int tsd_session_timestep(tsd_session* s, int i); /* i-th timestep of the schedule */
 /* Upload state.  latents [B,4,L,L]; context [B,T,768]; uncond_context [B,T,768] or NULL;
@@ -262,7 +299,7 @@ int tsd_session_timestep(tsd_session* s, int i); /* i-th timestep of the schedul
 int tsd_session_upload(tsd_session* s, const float* latents, const float* context, const float* uncond_context,
                        const float* noise, float cfg_scale);
 /* Enqueue step i: time embedding -> Diffusion.forward (x1 or x2 with CFG combine) -> DDPMSampler.step
- * (sampler.mojo:75-109).  Asynchronous on the context stream. */
+ * (sampler.mojo:75-109), or the update of the sampler chosen with tsd_session_set_sampler.  Asynchronous on the context stream. */
 int tsd_session_step(tsd_session* s, int i);
 /* `add_noise` sampler.mojo:111-124 at timestep index i (img2img), noise [B,4,L,L] host. */
 int tsd_session_add_noise(tsd_session* s, int i, const float* noise);

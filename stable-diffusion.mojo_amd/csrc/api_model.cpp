@@ -130,11 +130,18 @@ struct tsd_session {
   float* temb = nullptr;      // [16][320]
   float* noise = nullptr;     // [nsteps,B,4,L,L] or null
   float* images = nullptr;    // [B,3,8L,8L]
+  float* hist = nullptr;      // [B,4,L,L] fp32: the data prediction x0 of the previous step (DPM-Solver++(2M))
   size_t noise_cap = 0;
   // schedule (sampler.mojo:15-44)
   int n_train = 1000, n_infer = 50, start = 0;
   std::vector<float> alphas_cumprod;
   std::vector<int> timesteps;
+  // sampler (tsd_session_set_sampler); the default is the reference's DDPMSampler on its own timestep rule
+  int sampler = TSD_SAMPLER_DDPM, spacing = TSD_SPACING_LEADING;
+  float eta = 0.f;
+  // step index for which `hist` holds the previous step's x0: i + 1 after step(i), -1 after upload() / add_noise() / set_*() and
+  // after a sampler that keeps no history.  A step with any other index runs first order.
+  int hist_valid_for = -1;
   bool uploaded = false, has_noise = false;
   size_t plan_unet = 0, plan_dec = 0;
   unsigned opt_gen = 0;  // generation of the context's options the workspace was sized for (upload)
@@ -163,24 +170,17 @@ static bool host_all_finite(const float* p, size_t n) {
                "download); its state is unusable until upload() replaces it");                                              \
   } while (0)
 
-static void build_schedule(tsd_session* s) {
-  // betas = linspace(sqrt(b0), sqrt(b1), N)^2 ; alphas_cumprod = cumprod(1 - betas)   (sampler.mojo:28-32), fp32
-  const int N = s->n_train;
-  s->alphas_cumprod.resize(N);
-  const float b0 = sqrtf(0.00085f), b1 = sqrtf(0.0120f);
-  float prod = 1.f;
-  for (int i = 0; i < N; i++) {
-    const float step = N > 1 ? (b1 - b0) / (float)(N - 1) : 0.f;  // numpy.linspace order: i*step + start
-    const float v = (float)i * step + b0;
-    const float beta = v * v;
-    prod *= (1.f - beta);
-    s->alphas_cumprod[i] = prod;
-  }
-  // timesteps = round(arange(n)[::-1] * (N // n))  (sampler.mojo:40-43), then drop `start` (set_strength, App.A D21)
-  s->timesteps.clear();
-  const int ratio = N / s->n_infer;
-  for (int i = s->n_infer - 1; i >= 0; i--) s->timesteps.push_back(i * ratio);
-  if (s->start > 0) s->timesteps.erase(s->timesteps.begin(), s->timesteps.begin() + std::min<size_t>(s->start, s->timesteps.size()));
+// alphas_cumprod (sampler.mojo:28-32) and the timestep list of the session's spacing with `start` entries dropped (sampler.cpp)
+static int build_schedule(tsd_session* s) {
+  sampler_alphas_cumprod(s->n_train, s->alphas_cumprod);
+  return sampler_timesteps(s->spacing, s->n_train, s->n_infer, s->start, s->timesteps);
+}
+// the device noise buffer and the workspace plan were sized for the OLD schedule, the history and the images belong to it: a new
+// upload() is required
+static void schedule_changed(tsd_session* s) {
+  s->uploaded = false; s->has_noise = false;
+  s->hist_valid_for = -1;
+  s->decoded = false;
 }
 
 extern "C" int tsd_session_create(tsd_model* diffusion, tsd_model* decoder, int B, int L, int T, int cfg,
@@ -201,7 +201,7 @@ extern "C" int tsd_session_create(tsd_model* diffusion, tsd_model* decoder, int 
   auto carve = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~size_t(255); return o; };
   const size_t o_lat = carve(nl * 4), o_lat2 = carve(2 * nl * 4), o_ctx = carve((size_t)Bu * s->Tp * 768 * 2),
                o_eps = carve((size_t)Bu * 4 * L * L * 4), o_t = carve(16 * 4), o_te = carve(16 * 320 * 4),
-               o_img = carve(decoder ? (size_t)B * 3 * 64 * L * L * 4 : 0);
+               o_img = carve(decoder ? (size_t)B * 3 * 64 * L * L * 4 : 0), o_hist = carve(nl * 4);
   hipError_t e = hipMalloc((void**)&s->state, off);
   if (e != hipSuccess) { delete s; TSD_FAIL(TSD_E_ALLOC, "session: hipMalloc(%zu) failed: %s", off, hipGetErrorString(e)); }
   if (ctx->opt.debug_poison >= 0 && (ctx->opt.debug_poison_what & 4)) hipMemsetAsync(s->state, ctx->opt.debug_poison & 255, off, ctx->stream);
@@ -209,7 +209,8 @@ extern "C" int tsd_session_create(tsd_model* diffusion, tsd_model* decoder, int 
   s->ctx16 = (half_t*)(s->state + o_ctx); s->eps = (float*)(s->state + o_eps);
   s->tdev = (float*)(s->state + o_t); s->temb = (float*)(s->state + o_te);
   s->images = decoder ? (float*)(s->state + o_img) : nullptr;
-  build_schedule(s);
+  s->hist = (float*)(s->state + o_hist);
+  if (build_schedule(s) != TSD_OK) { hipFree(s->state); delete s; return TSD_E_ARG; }
   *out = s;
   return TSD_OK;
 }
@@ -231,10 +232,19 @@ extern "C" int tsd_session_set_schedule(tsd_session* s, int num_training_steps, 
       start_step < 0 || start_step >= num_inference_steps)
     TSD_FAIL(TSD_E_ARG, "schedule: train=%d infer=%d start=%d", num_training_steps, num_inference_steps, start_step);
   s->n_train = num_training_steps; s->n_infer = num_inference_steps; s->start = start_step;
-  build_schedule(s);
-  // the device noise buffer and the workspace plan were sized for the OLD schedule: a new upload() is required
-  s->uploaded = false; s->has_noise = false;
-  return TSD_OK;
+  schedule_changed(s);
+  return build_schedule(s);
+}
+extern "C" int tsd_session_set_sampler(tsd_session* s, int kind, float eta, int spacing) {
+  NOTNULL(s);
+  if (kind != TSD_SAMPLER_DDPM && kind != TSD_SAMPLER_DDIM && kind != TSD_SAMPLER_DPMPP_2M)
+    TSD_FAIL(TSD_E_ARG, "sampler: kind %d (0 DDPM, 1 DDIM, 2 DPM-Solver++(2M))", kind);
+  if (spacing != TSD_SPACING_LEADING && spacing != TSD_SPACING_TRAILING)
+    TSD_FAIL(TSD_E_ARG, "sampler: timestep spacing %d (0 leading, 1 trailing)", spacing);
+  if (!(eta >= 0.f)) TSD_FAIL(TSD_E_ARG, "sampler: eta %g < 0", (double)eta);
+  s->sampler = kind; s->eta = eta; s->spacing = spacing;
+  schedule_changed(s);  // the timestep list may have changed: as after set_schedule
+  return build_schedule(s);
 }
 extern "C" int tsd_session_num_steps(tsd_session* s) { return s ? (int)s->timesteps.size() : TSD_E_ARG; }
 extern "C" int tsd_session_timestep(tsd_session* s, int i) {
@@ -295,12 +305,13 @@ extern "C" int tsd_session_upload(tsd_session* s, const float* latents, const fl
   s->uploaded = true;
   s->poisoned = false;
   s->decoded = false;
+  s->hist_valid_for = -1;
   return TSD_OK;
 }
 
-// scalar coefficients of `DDPMSampler.step` sampler.mojo:81-98 and `get_variance` :53-65 (fp32 like the reference)
-static void ddpm_coeffs(const tsd_session* s, int t, float* sa, float* sb, float* c_x0, float* c_xt, float* sigma) {
-  const int prev = t - s->n_train / s->n_infer;
+// scalar coefficients of `DDPMSampler.step` sampler.mojo:81-98 and `get_variance` :53-65 (fp32 like the reference).  `prev` is the
+// reference's t - N // n (get_previous_timestep :46-51) under LEADING spacing and the next entry of the list under TRAILING.
+static void ddpm_coeffs(const tsd_session* s, int t, int prev, float* sa, float* sb, float* c_x0, float* c_xt, float* sigma) {
   const float a_t = s->alphas_cumprod[t];
   const float a_prev = prev >= 0 ? s->alphas_cumprod[prev] : 1.f;
   const float b_t = 1.f - a_t, b_prev = 1.f - a_prev;
@@ -323,6 +334,9 @@ extern "C" int tsd_session_step(tsd_session* s, int i) {
   const int B = s->B, L = s->L, Bu = s->cfg ? 2 * B : B;
   const size_t nl = (size_t)B * 4 * L * L;
   const int t = s->timesteps[i];
+  const bool have_hist = s->sampler == TSD_SAMPLER_DPMPP_2M && s->hist_valid_for == i;
+  s->hist_valid_for = -1;  // until this step's update is enqueued
+  s->decoded = false;      // the images are not those of the latents any more
   // time embedding on the device (get_time_embedding, pipeline.mojo:89): same t for every sample
   TSD_TRY(launch_time_embedding(ctx, nullptr, (float)t, Bu, s->temb));
   const float* lat_in = s->latents;
@@ -336,11 +350,26 @@ extern "C" int tsd_session_step(tsd_session* s, int i) {
   const bool eps_nhwc = s->unet->unet.final_conv.Opad == 4;  // g_unet_forward's condition for writing that layout
   TSD_TRY(g_unet_forward(s->unet, lat_in, s->ctx16, s->T, s->Tp, s->temb, Bu, L, s->eps, eps_nhwc));
   ctx->arena.top = 0;
-  float sa, sb, c_x0, c_xt, sigma;
-  ddpm_coeffs(s, t, &sa, &sb, &c_x0, &c_xt, &sigma);
-  const float* nz = (s->has_noise && t > 0) ? s->noise + (size_t)i * nl : nullptr;
-  return launch_ddpm_step(ctx, s->latents, s->eps, s->cfg ? s->eps + nl : nullptr, s->cfg_scale, nz, (int64_t)nl, sa, sb,
-                          c_x0, c_xt, sigma, eps_nhwc ? L * L : 0);
+  const float* eps_u = s->cfg ? s->eps + nl : nullptr;
+  if (s->sampler == TSD_SAMPLER_DDPM) {
+    float sa, sb, c_x0, c_xt, sigma;
+    const int prev = s->spacing == TSD_SPACING_LEADING ? t - s->n_train / s->n_infer
+                                                       : (i + 1 < (int)s->timesteps.size() ? s->timesteps[i + 1] : -1);
+    ddpm_coeffs(s, t, prev, &sa, &sb, &c_x0, &c_xt, &sigma);
+    const float* nz = (s->has_noise && t > 0) ? s->noise + (size_t)i * nl : nullptr;
+    return launch_ddpm_step(ctx, s->latents, s->eps, eps_u, s->cfg_scale, nz, (int64_t)nl, sa, sb, c_x0, c_xt, sigma,
+                            eps_nhwc ? L * L : 0);
+  }
+  // DDIM / DPM-Solver++(2M): the scalars of tsd_sampler_coeffs (double), rounded to float once here
+  double cd[8];
+  TSD_TRY(sampler_coeffs(s->sampler, s->eta, s->alphas_cumprod, s->timesteps, i, have_hist ? 1 : 0, cd));
+  const SamplerCoeffs c = {(float)cd[2], (float)cd[3], (float)cd[4], (float)cd[5], (float)cd[6], (float)cd[7]};
+  const bool multistep = s->sampler == TSD_SAMPLER_DPMPP_2M;  // the only one that reads or keeps the history, and it takes no noise
+  const float* nz = (!multistep && s->has_noise && c.c_n != 0.f) ? s->noise + (size_t)i * nl : nullptr;
+  TSD_TRY(launch_sampler_step(ctx, s->latents, s->eps, eps_u, s->cfg_scale, have_hist ? s->hist : nullptr, nz, (int64_t)nl, c,
+                              eps_nhwc ? L * L : 0, s->latents, multistep ? s->hist : nullptr));
+  if (multistep) s->hist_valid_for = i + 1;
+  return TSD_OK;
 }
 
 extern "C" int tsd_session_add_noise(tsd_session* s, int i, const float* noise) {
@@ -349,6 +378,8 @@ extern "C" int tsd_session_add_noise(tsd_session* s, int i, const float* noise) 
   tsd_ctx* ctx = s->ctx;
   const size_t nl = (size_t)s->B * 4 * s->L * s->L;
   TSD_TRY(ctx_reserve_staging(ctx, nl * 4));
+  s->hist_valid_for = -1;  // the latents are no longer those the history was predicted from
+  s->decoded = false;
   HIP_TRY(hipMemcpyAsync(ctx->staging, noise, nl * 4, hipMemcpyHostToDevice, ctx->stream));
   const float a = s->alphas_cumprod[s->timesteps[i]];
   TSD_TRY(launch_add_noise(ctx, s->latents, (const float*)ctx->staging, (int64_t)nl, sqrtf(a), sqrtf(1.f - a)));

@@ -245,6 +245,29 @@ extern "C" int tsd_silu_f32(tsd_ctx* ctx, const float* x, int64_t n, float* y) {
 extern "C" int tsd_gelu_tanh_f32(tsd_ctx* ctx, const float* x, int64_t n, float* y) { return unary_op(ctx, 1, x, n, y); }
 extern "C" int tsd_rescale_images_f32(tsd_ctx* ctx, const float* x, int64_t n, float* y) { return unary_op(ctx, 2, x, n, y); }
 
+// one update of the linear-multistep samplers (kernels_sampler.hip) on host tensors: the kernel the denoise session launches
+extern "C" int tsd_sampler_step_f32(tsd_ctx* ctx, const float* x, const float* eps, const float* eps_uncond, float cfg_scale,
+                                    const float* hist, const float* noise, int64_t n, const float* c, float* x_out,
+                                    float* hist_out) {
+  NOTNULL(x); NOTNULL(eps); NOTNULL(c); NOTNULL(x_out);
+  if (n <= 0) TSD_FAIL(TSD_E_SHAPE, "sampler step: n=%lld", (long long)n);
+  const SamplerCoeffs sc = {c[0], c[1], c[2], c[3], c[4], c[5]};
+  return run_op(ctx, [&]() -> int {
+    Dev d{ctx};
+    float* dx = d.in(x, n);
+    float* de = d.in(eps, n);
+    float* du = eps_uncond ? d.in(eps_uncond, n) : nullptr;
+    float* dh = hist ? d.in(hist, n) : nullptr;
+    float* dz = noise ? d.in(noise, n) : nullptr;
+    float* dy = d.buf<float>(n);
+    float* dho = hist_out ? d.buf<float>(n) : nullptr;
+    if (d.err) return d.err;
+    TSD_TRY(launch_sampler_step(ctx, dx, de, du, cfg_scale, dh, dz, n, sc, 0, dy, dho));
+    if (hist_out) TSD_TRY(d.out(hist_out, dho, n));
+    return d.out(x_out, dy, n);
+  });
+}
+
 extern "C" int tsd_linear_f32(tsd_ctx* ctx, const float* x, int M, int K, const float* w, const float* bias, int N,
                               float* y) {
   NOTNULL(x); NOTNULL(w); NOTNULL(y);

@@ -301,6 +301,30 @@ int launch_ddpm_step(tsd_ctx* ctx, float* latents, const float* eps, const float
                      const float* noise, int64_t n, float inv_sqrt_a, float sqrt_b, float c_x0, float c_xt,
                      float sigma, int eps_hw = 0);  // eps_hw > 0: eps in the output convolution's layout [B][eps_hw][4]
 int launch_add_noise(tsd_ctx* ctx, float* latents, const float* noise, int64_t n, float sa, float sb);
+
+// ---- linear-multistep sampler update (kernels_sampler.hip) and its host schedule (sampler.cpp) ------------------------------
+// e = (eps - eps_u) * cfg_scale + eps_u ; x0 = (x - sigma_t e) / alpha_t ; x_out = c_x x + c_e e + c_h hist_in + c_n noise ; hist_out = x0
+struct SamplerCoeffs {
+  float alpha_t, sigma_t, c_x, c_e, c_h, c_n;
+};
+// eps_uncond / hist_in / noise / hist_out may be nullptr (the term or the store is skipped); x_out may be x and hist_out may be
+// hist_in (every element is read and written by one thread); eps_hw as in launch_ddpm_step
+int launch_sampler_step(tsd_ctx* ctx, const float* x, const float* eps, const float* eps_uncond, float cfg_scale,
+                        const float* hist_in, const float* noise, int64_t n, const SamplerCoeffs& c, int eps_hw, float* x_out,
+                        float* hist_out);
+// alphas_cumprod of the scaled-linear beta schedule (sampler.mojo:28-32), fp32 like the reference's Tensor
+void sampler_alphas_cumprod(int n_train, std::vector<float>& out);
+// timestep list of `spacing` (tsd_timestep_spacing) with the first `start_step` entries dropped; TSD_E_ARG on a bad argument
+int sampler_timesteps(int spacing, int n_train, int n_infer, int start_step, std::vector<int>& out);
+// scalars of step i of `timesteps` as double: out[8] = { t, t_prev (-1: the clean sample), alpha_t, sigma_t, c_x, c_e, c_h, c_n }
+int sampler_coeffs(int kind, double eta, const std::vector<float>& alphas_cumprod, const std::vector<int>& timesteps, int i,
+                   int have_history, double out[8]);
+
+// ---- non-finite accounting (kernels_elementwise.hip explains where it is reported) -------------------------------------------
+__device__ __forceinline__ bool nonfinite_f(float v) { return !(fabsf(v) <= 3.4028234e38f); }  // inf or NaN
+__device__ __forceinline__ void nonfinite_report(int* counter, int nbad) {
+  if (nbad) atomicAdd(counter, nbad);  // rare path
+}
 int launch_encoder_sample(tsd_ctx* ctx, const float* moments_nhwc, int B, int HW, int ld, const float* noise_chw,
                           float* latents_chw);
 

@@ -143,10 +143,7 @@ int launch_fold_linear_conv1x1(tsd_ctx* ctx, const half_t* wo, int ldo, const fl
 // activations as fp16 (|x| <= 65504).  An overflow turns into inf / NaN that the following norms and GEMMs spread, so it reaches
 // the tensors that LEAVE the device: every kernel that produces a caller-visible tensor counts the non-finite values it writes in
 // the context's status word, and the synchronisation points of the ABI turn a non-zero count into TSD_E_NONFINITE (runtime.cpp).
-__device__ __forceinline__ bool nonfinite_f(float v) { return !(fabsf(v) <= 3.4028234e38f); }  // inf or NaN
-__device__ __forceinline__ void nonfinite_report(int* counter, int nbad) {
-  if (nbad) atomicAdd(counter, nbad);  // rare path
-}
+// nonfinite_f / nonfinite_report live in common.h (kernels_sampler.hip counts the same way).
 
 template <class T>
 __global__ void k_nhwc_to_chw(const T* __restrict__ src, int C, int HW, int ld, float* __restrict__ dst,

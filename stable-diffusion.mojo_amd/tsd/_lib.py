@@ -22,6 +22,18 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
 
 MODEL_DIFFUSION, MODEL_DECODER, MODEL_ENCODER, MODEL_CLIP, MODEL_DIFFUSION_SD15, MODEL_DIFFUSION_SD15_TORCH = 1, 2, 3, 4, 5, 6
 MODEL_CLIP_TORCH, MODEL_DECODER_TORCH, MODEL_ENCODER_TORCH = 7, 8, 9
+SAMPLER_KINDS = {"ddpm": 0, "ddim": 1, "dpmpp_2m": 2}      # tsd_sampler_kind
+TIMESTEP_SPACINGS = {"leading": 0, "trailing": 1}          # tsd_timestep_spacing
+
+
+def sampler_kind(kind):
+    """"ddpm" | "ddim" | "dpmpp_2m" (or the enum value) -> tsd_sampler_kind; an unknown name goes to the library, which refuses it."""
+    return SAMPLER_KINDS.get(kind.lower(), -1) if isinstance(kind, str) else int(kind)
+
+
+def timestep_spacing(spacing):
+    """"leading" | "trailing" (or the enum value) -> tsd_timestep_spacing."""
+    return TIMESTEP_SPACINGS.get(spacing.lower(), -1) if isinstance(spacing, str) else int(spacing)
 
 
 class TsdError(RuntimeError):
@@ -99,6 +111,10 @@ def _declare(l):
         "tsd_tokenizer_encode": ([vp, C.c_char_p, C.POINTER(C.c_int32), i, C.POINTER(C.c_int), C.POINTER(C.c_int)], i),
         "tsd_session_create": ([vp, vp, i, i, i, i, pp], i), "tsd_session_destroy": ([vp], i),
         "tsd_session_set_schedule": ([vp, i, i, i], i), "tsd_session_num_steps": ([vp], i),
+        "tsd_session_set_sampler": ([vp, i, f, i], i),
+        "tsd_sampler_timesteps": ([i, i, i, i, C.POINTER(i), i], i),
+        "tsd_sampler_coeffs": ([i, C.c_double, i, i, i, i, i, i, C.POINTER(C.c_double)], i),
+        "tsd_sampler_step_f32": ([vp, fp, fp, fp, f, fp, fp, i64, fp, fp, fp], i),
         "tsd_session_timestep": ([vp, i], i),
         "tsd_session_upload": ([vp, fp, fp, fp, fp, f], i), "tsd_session_step": ([vp, i], i),
         "tsd_session_add_noise": ([vp, i, fp], i), "tsd_session_decode": ([vp], i),

@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check, f32, lib, ptr, vp
+from ._lib import check, f32, lib, ptr, sampler_kind, timestep_spacing, vp
 
 KINDS = {"diffusion": _lib.MODEL_DIFFUSION, "decoder": _lib.MODEL_DECODER, "encoder": _lib.MODEL_ENCODER,
          "clip": _lib.MODEL_CLIP, "diffusion_sd15": _lib.MODEL_DIFFUSION_SD15,
@@ -90,6 +90,11 @@ class Session:
 
     def set_schedule(self, num_training_steps=1000, num_inference_steps=50, start_step=0):
         check(lib().tsd_session_set_schedule(self.h, num_training_steps, num_inference_steps, start_step))
+
+    def set_sampler(self, kind="ddpm", eta=0.0, spacing="leading"):
+        """"ddpm" (the reference's, default) | "ddim" (eta = 0 deterministic) | "dpmpp_2m"; spacing "leading" | "trailing".
+        Like set_schedule it invalidates the upload."""
+        check(lib().tsd_session_set_sampler(self.h, sampler_kind(kind), float(eta), timestep_spacing(spacing)))
 
     @property
     def num_steps(self):

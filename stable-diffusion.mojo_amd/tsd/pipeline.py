@@ -24,8 +24,12 @@ def encode_prompts(prompts, tokenizer, clip):
 
 def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg=True, cfg_scale=7.5,
              inference_steps=50, seed_val=0, input_image=None, encoder=None, latents=None, noise=None,
-             num_training_steps=1000, L=64, return_latents=False):
+             num_training_steps=1000, L=64, return_latents=False, sampler="ddpm", eta=0.0, spacing="leading"):
     """context (B,T,768); returns images (B,3,8L,8L) in [0,255] like pipeline.mojo:127.
+
+    sampler "ddpm" (the reference's, about 50 steps) | "ddim" (eta = 0: deterministic) | "dpmpp_2m" (second-order multistep, 20-25
+    steps); spacing "leading" (the reference's timesteps) | "trailing" (starts at N - 1: few-step sampling).  The defaults are the
+    reference's loop.  Noise is read by "ddpm" and by "ddim" with eta > 0.
 
     latents / noise default to N(0,1) from the counter RNG keyed by seed_val (App.A D19)."""
     context = np.asarray(context, dtype=np.float32)
@@ -39,6 +43,8 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
     start = 0
     if input_image is not None:
         start = inference_steps - int(inference_steps * strength)  # sampler.mojo:68-70
+    if (sampler, eta, spacing) != ("ddpm", 0.0, "leading"):  # the default session is the reference's: nothing to set
+        sess.set_sampler(sampler, eta, spacing)
     sess.set_schedule(num_training_steps, inference_steps, start)
     n = sess.num_steps
     nl = B * 4 * L * L

@@ -1,6 +1,7 @@
 """Host-side mirror of `sampler.mojo` (DDPMSampler).  The schedule scalars are host code exactly as in the
 reference (a few fp32 scalars per step); the per-step tensor update runs on the GPU inside the
-session (`tsd_session_step`: fused CFG combine + posterior mean + noise, SURVEY.md App.D K9)."""
+session (`tsd_session_step`: fused CFG combine + posterior mean + noise, SURVEY.md App.D K9).
+DDIMSampler and DPMSolverMultistepSampler have no reference counterpart: they mirror the samplers `Session.set_sampler` selects."""
 import numpy as np
 
 
@@ -38,3 +39,78 @@ class DDPMSampler:
         start = self.num_inference_steps - int(self.num_inference_steps * strength)
         self.timesteps = self.timesteps[start:]
         self.start_step = start
+
+
+class _LinearMultistepSampler(DDPMSampler):
+    """Host mirror of the samplers the device session runs through `k_sampler_step` (include/tsd.h "samplers"):
+    x' = c_x x + c_e e + c_h h + c_n z with x0 = (x - sigma_t e) / alpha_t and h the previous step's x0.  The scalars are
+    restated here in float64 on the same fp32 alphas_cumprod table; `tsd_sampler_coeffs` is the implementation the session uses."""
+
+    def __init__(self, num_training_steps=1000, spacing="leading", **kw):
+        super().__init__(num_training_steps=num_training_steps, **kw)
+        if spacing not in ("leading", "trailing"):
+            raise ValueError(f"spacing must be 'leading' or 'trailing', got {spacing!r}")
+        self.spacing = spacing
+
+    def set_inference_timesteps(self, num_inference_steps=1):
+        if self.spacing == "leading":
+            return super().set_inference_timesteps(num_inference_steps)
+        self.num_inference_steps = num_inference_steps
+        N = self.num_training_steps                         # round(N - k N/n) - 1: starts at N - 1 (halves to even)
+        self.timesteps = np.round(N - np.arange(num_inference_steps) * (N / num_inference_steps)).astype(np.int64) - 1
+
+    def _step_scalars(self, i):
+        """(t, t_prev, abar_t, abar_prev): the previous timestep of step i is the next entry; then the clean sample (abar = 1)."""
+        t = int(self.timesteps[i])
+        tp = int(self.timesteps[i + 1]) if i + 1 < len(self.timesteps) else -1
+        return t, tp, float(self.alphas_cumprod[t]), float(self.alphas_cumprod[tp]) if tp >= 0 else 1.0
+
+    def coefficients(self, i, have_history=False):
+        """-> (t, t_prev, alpha_t, sigma_t, c_x, c_e, c_h, c_n), the out[8] of `tsd_sampler_coeffs`."""
+        raise NotImplementedError
+
+    def step(self, i, latents, model_output, history=None, noise=None):
+        """One update in float64 -> (x', x0); `history` is the x0 the previous step returned (None: first order)."""
+        _, _, al, sg, c_x, c_e, c_h, c_n = self.coefficients(i, history is not None)
+        x, e = np.asarray(latents, dtype=np.float64), np.asarray(model_output, dtype=np.float64)
+        out = c_x * x + c_e * e
+        if history is not None:
+            out = out + c_h * np.asarray(history, dtype=np.float64)
+        if noise is not None:
+            out = out + c_n * np.asarray(noise, dtype=np.float64)
+        return out, (x - sg * e) / al
+
+
+class DDIMSampler(_LinearMultistepSampler):
+    """DDIM (Song et al. 2021, eq. 12; sigma = eta * eq. 16).  eta = 0 is deterministic, eta = 1 is the DDPM posterior."""
+
+    def __init__(self, num_training_steps=1000, eta=0.0, spacing="leading", **kw):
+        super().__init__(num_training_steps, spacing, **kw)
+        self.eta = float(eta)
+
+    def coefficients(self, i, have_history=False):
+        t, tp, a_t, a_p = self._step_scalars(i)
+        var = self.eta ** 2 * (1.0 - a_p) / (1.0 - a_t) * (1.0 - a_t / a_p)
+        c_x = np.sqrt(a_p / a_t)
+        c_e = np.sqrt(max(1.0 - a_p - var, 0.0)) - c_x * np.sqrt(1.0 - a_t)
+        return t, tp, np.sqrt(a_t), np.sqrt(1.0 - a_t), c_x, c_e, 0.0, np.sqrt(var)
+
+
+class DPMSolverMultistepSampler(_LinearMultistepSampler):
+    """DPM-Solver++(2M) (Lu et al. 2022, algorithm 2, data prediction): second order from the previous step's x0; first order on
+    the first step, on the step onto the clean sample and without history.  Deterministic (c_n = 0)."""
+
+    def coefficients(self, i, have_history=False):
+        t, tp, a_t, a_p = self._step_scalars(i)
+        al, sg = np.sqrt(a_t), np.sqrt(1.0 - a_t)
+        if tp < 0:                                          # lambda_prev is infinite: x' = x0
+            return t, tp, al, sg, 1.0 / al, -sg / al, 0.0, 0.0
+        lam = lambda a: 0.5 * np.log(a / (1.0 - a))  # noqa: E731
+        h = lam(a_p) - lam(a_t)
+        g = -np.sqrt(a_p) * np.expm1(-h)                    # x' = (sigma_prev / sigma_t) x + g D
+        w1 = 0.0
+        if have_history and i > 0:                          # D = (1 + 1/(2r)) x0 - 1/(2r) x0_prev, r = h_prev / h
+            r = (lam(a_t) - lam(float(self.alphas_cumprod[int(self.timesteps[i - 1])]))) / h
+            w1 = 1.0 / (2.0 * r)
+        w0 = 1.0 + w1
+        return t, tp, al, sg, np.sqrt(1.0 - a_p) / sg + g * w0 / al, -g * w0 * sg / al, -g * w1, 0.0
