@@ -415,6 +415,15 @@ int tsd_debug_set_res_fuse_skip(tsd_ctx* ctx, int on);
  * H*W % 32 == 0); on = 0 runs the q/k GEMM and the swapped-operand V^T GEMM as two launches.  Environment: TSD_QKV_FUSE.  Returns
  * the previous setting. */
 int tsd_debug_set_qkv_fuse(tsd_ctx* ctx, int on);
+/* A denoise session computes what a step's UNet forward derives from the timestep and the context alone - the time MLP and the time
+ * projections of every schedule entry, the context K / V^T of all attention blocks - once per tsd_session_upload, with the launches
+ * the step would make, and its steps read them (on = 1, default): five launches per step fewer, the same bits.  A parameter set
+ * after upload() makes the next step rebuild them.  on = 0: every step computes them again.  Like every tsd_debug_set_* call a
+ * change asks the context's sessions for a new upload().  Environment: TSD_SESSION_HOIST.  Returns the previous setting. */
+int tsd_debug_set_session_hoist(tsd_ctx* ctx, int on);
+/* info[6] of a session: [0] 1 when the steps of the current upload() read the hoisted buffers, [1] device address of the time table,
+ * [2] of the context K and [3] V^T buffers, [4] bytes allocated for them, [5] times they have been built (uploads + rebuilds). */
+int tsd_debug_session_hoist_info(tsd_session* s, int64_t* info);
 /* What this board sustains on the matrix pipe: a register-resident dense fp16 MFMA loop (no LDS, no memory) run for about
  * `ms_target` ms at 4 waves per SIMD; reports the achieved TFLOP/s and the shader clock (GHz) during the run.  The nominal
  * dense peak assumes the boost clock; under matrix-pipe load the board's power limit sets the clock. */

@@ -2,6 +2,7 @@
 // session (pipeline.mojo:57-127 + sampler.mojo:15-124) and the RCCL weight broadcast.
 #include <dlfcn.h>
 #include <math.h>
+#include <stdint.h>
 #include <string.h>
 
 #include <vector>
@@ -132,6 +133,16 @@ struct tsd_session {
   float* images = nullptr;    // [B,3,8L,8L]
   float* hist = nullptr;      // [B,4,L,L] fp32: the data prediction x0 of the previous step (DPM-Solver++(2M))
   size_t noise_cap = 0;
+  // What a step's UNet forward computes from the timestep and the context alone (graph.h UNetPre), made once per upload() by
+  // session_build_invariants when the context's session_hoist is on: own allocations, grown at upload() like `noise`, never in a step.
+  char* kv = nullptr;         // kc_all [Bu*Tp][CK] | vtc_all [Bu][CK][Tp] fp16: the context K / V^T of all attention blocks
+  half_t* kc_all = nullptr;
+  half_t* vtc_all = nullptr;
+  float* ttab = nullptr;      // [timesteps.size()][tproj.N] fp32: the time projections of every schedule entry (one row serves every sample)
+  size_t kv_cap = 0, ttab_cap = 0;
+  bool hoist = false;         // the steps of this upload() run on them
+  unsigned model_gen = 0;     // generation of the UNet's parameters (tsd_model::gen) at the last upload() / rebuild
+  int inv_builds = 0;         // session_build_invariants calls so far (tsd_debug_session_hoist_info)
   // schedule (sampler.mojo:15-44)
   int n_train = 1000, n_infer = 50, start = 0;
   std::vector<float> alphas_cumprod;
@@ -177,6 +188,46 @@ static int build_schedule(tsd_session* s) {
 }
 // the device noise buffer and the workspace plan were sized for the OLD schedule, the history and the images belong to it: a new
 // upload() is required
+// Fill the session's step-invariant buffers on the context's stream, with the launches (same kernels, same arguments, same batch) a
+// step's forward would make for them, so their contents are the bits the per-step path computes:
+//   * context K / V^T: the forward's own projection launch, once;
+//   * time table: per schedule entry, the time embedding of its timestep for Bu samples and the three small linears behind it; every
+//     sample sees the same timestep, so the Bu rows are equal and row 0 is kept (the forward reads it with a per-sample stride of 0).
+// The arena (sized by upload() for this too) is scratch; nothing here synchronises.
+static int session_build_invariants(tsd_session* s) {
+  tsd_ctx* ctx = s->ctx;
+  tsd_model* m = s->unet;
+  const int Bu = s->cfg ? 2 * s->B : s->B, N = m->unet.tproj.N;
+  ctx->arena.top = 0;
+  TSD_TRY(g_unet_ctx_kv(m, s->ctx16, s->Tp, Bu, s->kc_all, s->vtc_all));
+  for (size_t i = 0; i < s->timesteps.size(); i++) {
+    ctx->arena.top = 0;
+    TSD_TRY(launch_time_embedding(ctx, nullptr, (float)s->timesteps[i], Bu, s->temb));
+    const float* tvec = nullptr;
+    TSD_TRY(g_unet_time_path(m, s->temb, Bu, &tvec));
+    HIP_TRY(hipMemcpyAsync(s->ttab + i * (size_t)N, tvec, (size_t)N * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  ctx->arena.top = 0;
+  s->model_gen = m->gen;
+  s->inv_builds++;
+  return TSD_OK;
+}
+static UNetPre session_pre(const tsd_session* s, int i) {
+  UNetPre p;
+  p.tvec = s->ttab + (size_t)i * s->unet->unet.tproj.N; p.tld = 0;
+  p.kc_all = s->kc_all; p.vtc_all = s->vtc_all;
+  return p;
+}
+extern "C" int tsd_debug_set_session_hoist(tsd_ctx* ctx, int on) {
+  return ctx_set_option(ctx, &TsdOptions::session_hoist, on ? 1 : 0, 0, 1);
+}
+extern "C" int tsd_debug_session_hoist_info(tsd_session* s, int64_t* info) {
+  NOTNULL(s); NOTNULL(info);
+  info[0] = s->uploaded && s->hoist; info[1] = (int64_t)(uintptr_t)s->ttab; info[2] = (int64_t)(uintptr_t)s->kc_all;
+  info[3] = (int64_t)(uintptr_t)s->vtc_all; info[4] = (int64_t)(s->kv_cap + s->ttab_cap); info[5] = s->inv_builds;
+  return TSD_OK;
+}
+
 static void schedule_changed(tsd_session* s) {
   s->uploaded = false; s->has_noise = false;
   s->hist_valid_for = -1;
@@ -221,6 +272,8 @@ extern "C" int tsd_session_destroy(tsd_session* s) {
   hipStreamSynchronize(s->ctx->stream);
   if (s->state) hipFree(s->state);
   if (s->noise) hipFree(s->noise);
+  if (s->kv) hipFree(s->kv);
+  if (s->ttab) hipFree(s->ttab);
   delete s;
   return TSD_OK;
 }
@@ -290,9 +343,36 @@ extern "C" int tsd_session_upload(tsd_session* s, const float* latents, const fl
   if (s->dec) TSD_TRY(model_check_ready(s->dec));
   Arena& a = ctx->arena;
   const int Bu = s->cfg ? 2 * B : B;
+  s->hoist = ctx->opt.session_hoist != 0;
+  s->uploaded = false;  // until this upload() is complete: the buffers below may move
+  if (s->hoist) {  // the buffers of session_build_invariants; sizes depend on the session's shape and the schedule's length only
+    const int CK = s->unet->unet.kproj_all.N, N = s->unet->unet.tproj.N;
+    const size_t kc_bytes = ((size_t)Bu * Tp * CK * 2 + 255) & ~size_t(255), kv_bytes = 2 * kc_bytes;
+    const size_t tt_bytes = s->timesteps.size() * (size_t)N * 4;
+    if (kv_bytes > s->kv_cap) {
+      if (s->kv) HIP_TRY(hipFree(s->kv));
+      s->kv = nullptr; s->kv_cap = 0;
+      if (hipMalloc((void**)&s->kv, kv_bytes) != hipSuccess) TSD_FAIL(TSD_E_ALLOC, "session: context K/V hipMalloc(%zu) failed", kv_bytes);
+      s->kv_cap = kv_bytes;
+    }
+    s->kc_all = (half_t*)s->kv; s->vtc_all = (half_t*)(s->kv + kc_bytes);
+    if (tt_bytes > s->ttab_cap) {
+      if (s->ttab) HIP_TRY(hipFree(s->ttab));
+      s->ttab = nullptr; s->ttab_cap = 0;
+      if (hipMalloc((void**)&s->ttab, tt_bytes) != hipSuccess) TSD_FAIL(TSD_E_ALLOC, "session: time table hipMalloc(%zu) failed", tt_bytes);
+      s->ttab_cap = tt_bytes;
+    }
+  }
   a.planning = true; a.top = 0; a.peak = 0;
-  int r = g_unet_forward(s->unet, s->lat2, s->ctx16, T, Tp, s->temb, Bu, L, s->eps);
+  const UNetPre pre0 = s->hoist ? session_pre(s, 0) : UNetPre();
+  int r = g_unet_forward(s->unet, s->lat2, s->ctx16, T, Tp, s->temb, Bu, L, s->eps, false, s->hoist ? &pre0 : nullptr);
   size_t need = a.peak;
+  if (r == TSD_OK && s->hoist) {  // session_build_invariants' scratch
+    const float* tv = nullptr;
+    a.top = 0; a.peak = 0;
+    r = g_unet_time_path(s->unet, s->temb, Bu, &tv);
+    need = std::max(need, a.peak);
+  }
   if (r == TSD_OK && s->dec) {
     a.top = 0; a.peak = 0;
     r = g_decoder_forward(s->dec, s->latents, B, L, s->images);
@@ -301,6 +381,8 @@ extern "C" int tsd_session_upload(tsd_session* s, const float* latents, const fl
   a.planning = false; a.top = 0; a.peak = 0;
   if (r != TSD_OK) return r;
   TSD_TRY(ctx_reserve_arena(ctx, need));
+  s->model_gen = s->unet->gen;
+  if (s->hoist) TSD_TRY(session_build_invariants(s));
   s->opt_gen = ctx->opt.gen;
   s->uploaded = true;
   s->poisoned = false;
@@ -337,8 +419,13 @@ extern "C" int tsd_session_step(tsd_session* s, int i) {
   const bool have_hist = s->sampler == TSD_SAMPLER_DPMPP_2M && s->hist_valid_for == i;
   s->hist_valid_for = -1;  // until this step's update is enqueued
   s->decoded = false;      // the images are not those of the latents any more
+  if (s->model_gen != s->unet->gen) {  // parameters were set since upload(): the derived weights, then what this session derived from them
+    TSD_TRY(model_check_ready(s->unet));
+    if (s->hoist) TSD_TRY(session_build_invariants(s));
+    s->model_gen = s->unet->gen;
+  }
   // time embedding on the device (get_time_embedding, pipeline.mojo:89): same t for every sample
-  TSD_TRY(launch_time_embedding(ctx, nullptr, (float)t, Bu, s->temb));
+  if (!s->hoist) TSD_TRY(launch_time_embedding(ctx, nullptr, (float)t, Bu, s->temb));
   const float* lat_in = s->latents;
   if (s->cfg) {  // model_input for both passes is the same latents (pipeline.mojo:107-108)
     HIP_TRY(hipMemcpyAsync(s->lat2, s->latents, nl * 4, hipMemcpyDeviceToDevice, ctx->stream));
@@ -348,7 +435,8 @@ extern "C" int tsd_session_step(tsd_session* s, int i) {
   ctx->arena.top = 0;
   // eps stays in the output convolution's layout ([B][L*L][4]); the DDPM update reads it as such (no conversion launch)
   const bool eps_nhwc = s->unet->unet.final_conv.Opad == 4;  // g_unet_forward's condition for writing that layout
-  TSD_TRY(g_unet_forward(s->unet, lat_in, s->ctx16, s->T, s->Tp, s->temb, Bu, L, s->eps, eps_nhwc));
+  const UNetPre pre = s->hoist ? session_pre(s, i) : UNetPre();
+  TSD_TRY(g_unet_forward(s->unet, lat_in, s->ctx16, s->T, s->Tp, s->temb, Bu, L, s->eps, eps_nhwc, s->hoist ? &pre : nullptr));
   ctx->arena.top = 0;
   const float* eps_u = s->cfg ? s->eps + nl : nullptr;
   if (s->sampler == TSD_SAMPLER_DDPM) {

@@ -416,22 +416,12 @@ int g_vae_attn(tsd_ctx* ctx, const Act& x, const VaeAttnW& w, Act& out) {
   return TSD_OK;
 }
 
-// ---- `Diffusion.forward` diffusion.mojo:309-318 -------------------------------------------------------
-static int g_unet_full_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, int T, int Tp,
-                               const float* temb, int B, int L, float* eps_out_chw, bool eps_nhwc);
-
-int g_unet_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, int T, int Tp, const float* temb, int B,
-                   int L, float* eps_out_chw, bool eps_nhwc) {
-  if (is_full_unet_kind(m->kind)) {
-    const int prev = gemm_set_splitk_big(m->ctx, 4);  // measured for this graph at its batch of 4 (BASELINE configs[4]): +4.3 %
-    const int r = g_unet_full_forward(m, latents_chw, ctx16, T, Tp, temb, B, L, eps_out_chw, eps_nhwc);
-    gemm_set_splitk_big(m->ctx, prev);
-    return r;
-  }
+// ---- the two parts of `Diffusion.forward` that do not read the latents ----------------------------------
+// Time path (diffusion.mojo:17-21 and :61-62 for all residual blocks): temb [B][320] -> t1 -> time -> tvec [B][tproj.N], all three in
+// the arena.  A denoise session runs it once per schedule entry at upload() (api_model.cpp) and hands the rows to the forward (UNetPre).
+int g_unet_time_path(tsd_model* m, const float* temb, int B, const float** tvec_out) {
   tsd_ctx* ctx = m->ctx;
   const UNetW& u = m->unet;
-  if (L % 8) TSD_FAIL(TSD_E_SHAPE, "UNet: latent side %d must be a multiple of 8", L);
-  // ---- time path (diffusion.mojo:17-21 and :61-62 for all nine residual blocks) ----
   float* t1 = arena_alloc<float>(ctx, (int64_t)B * 1280); CHECK_ALLOC(t1);
   float* time = arena_alloc<float>(ctx, (int64_t)B * 1280); CHECK_ALLOC(time);
   float* tvec = arena_alloc<float>(ctx, (int64_t)B * u.tproj.N); CHECK_ALLOC(tvec);
@@ -439,7 +429,58 @@ int g_unet_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, 
   TSD_TRY(launch_small_linear(ctx, t1, B, 1280, 1280, u.t2.w, u.t2.Kpad, u.t2.b, 1280, 1, time, 1280));
   TSD_TRY(launch_small_linear(ctx, time, B, 1280, 1280, u.tproj.w, u.tproj.Kpad, u.tproj.b, u.tproj.N, 1, tvec,
                               u.tproj.N));
-  const int tld = u.tproj.N;
+  *tvec_out = tvec;
+  return TSD_OK;
+}
+
+// Context K and V^T projections of all attention blocks (helpers/attention.mojo:102-103; the k_proj / v_proj weights are contiguous
+// in the blob): K_all [B*Tp][CK], V^T_all [B][CK][Tp], CK = kproj_all.N.  The context and the weights are the same for every step of
+// a denoise session, which fills buffers of its own with this launch once per upload().
+int g_unet_ctx_kv(tsd_model* m, const half_t* ctx16, int Tp, int B, half_t* kc_all, half_t* vtc_all) {
+  tsd_ctx* ctx = m->ctx;
+  const UNetW& u = m->unet;
+  const int CK = u.kproj_all.N;
+  if (ctx_kv_fused_ok(ctx, u, Tp)) {  // k_proj | v_proj rows are adjacent in the blob: one GEMM, the V half stored transposed (GemmArgs::Vt)
+    GemmArgs g;
+    g.A0 = ctx16; g.lda0 = u.kproj_all.Kpad; g.Wt = u.kproj_all.w; g.ldw = u.kproj_all.Kpad;
+    g.M = B * Tp; g.N = 2 * CK; g.K = u.kproj_all.Kpad; g.C = kc_all; g.ldc = CK;
+    if (u.kproj_all.w_tm) { g.Wt = u.kproj_all.w_tm; g.ldw = 64; g.w_kts = 2 * CK * 128; }
+    g.Vt = vtc_all; g.vt_n0 = CK; g.vt_ld = Tp; g.vt_S = Tp; g.vt_sB = (int64_t)CK * Tp;
+    TSD_TRY(launch_gemm(ctx, g));
+  } else {
+    GemmArgs g;
+    g.A0 = ctx16; g.lda0 = u.kproj_all.Kpad; g.Wt = u.kproj_all.w; g.ldw = u.kproj_all.Kpad;
+    g.M = B * Tp; g.N = CK; g.K = u.kproj_all.Kpad; g.C = kc_all; g.ldc = CK;
+    TSD_TRY(launch_gemm(ctx, g));
+    GemmArgs v;
+    v.A0 = u.vproj_all.w; v.lda0 = u.vproj_all.Kpad; v.sA = 0;
+    v.Wt = ctx16; v.ldw = u.vproj_all.Kpad; v.sW = (int64_t)Tp * u.vproj_all.Kpad;
+    v.M = CK; v.N = Tp; v.K = u.vproj_all.Kpad; v.batch = B;
+    v.C = vtc_all; v.ldc = Tp; v.sC = (int64_t)CK * Tp;
+    TSD_TRY(launch_gemm(ctx, v));
+  }
+  return TSD_OK;
+}
+
+// ---- `Diffusion.forward` diffusion.mojo:309-318 -------------------------------------------------------
+static int g_unet_full_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, int T, int Tp,
+                               const float* temb, int B, int L, float* eps_out_chw, bool eps_nhwc, const UNetPre* pre);
+
+int g_unet_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, int T, int Tp, const float* temb, int B,
+                   int L, float* eps_out_chw, bool eps_nhwc, const UNetPre* pre) {
+  if (is_full_unet_kind(m->kind)) {
+    const int prev = gemm_set_splitk_big(m->ctx, 4);  // measured for this graph at its batch of 4 (BASELINE configs[4]): +4.3 %
+    const int r = g_unet_full_forward(m, latents_chw, ctx16, T, Tp, temb, B, L, eps_out_chw, eps_nhwc, pre);
+    gemm_set_splitk_big(m->ctx, prev);
+    return r;
+  }
+  tsd_ctx* ctx = m->ctx;
+  const UNetW& u = m->unet;
+  if (L % 8) TSD_FAIL(TSD_E_SHAPE, "UNet: latent side %d must be a multiple of 8", L);
+  // ---- time path (diffusion.mojo:17-21 and :61-62 for all nine residual blocks) ----
+  const float* tvec = pre ? pre->tvec : nullptr;
+  const int tld = pre ? pre->tld : u.tproj.N;
+  if (!pre) TSD_TRY(g_unet_time_path(m, temb, B, &tvec));
   // ---- input ----
   // `Conv2D(4, 320, 3)` (diffusion.mojo:236): the latent's 4 channels padded to a 64-channel NHWC tensor made the implicit GEMM walk
   // nine K tiles with 4 of 64 columns live; gathered to im2col rows at the boundary (36 of 64 columns live) it is ONE K tile
@@ -466,26 +507,13 @@ int g_unet_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, 
   // context K and V^T projections of all nine attention blocks in two GEMMs (helpers/attention.mojo:102-103;
   // the k_proj / v_proj weights are contiguous in the blob): K_all [B*Tp][6720], V^T_all [B][6720][Tp]
   const int CK = u.kproj_all.N;
-  half_t* kc_all = arena_alloc<half_t>(ctx, (int64_t)B * Tp * CK); CHECK_ALLOC(kc_all);
-  half_t* vtc_all = arena_alloc<half_t>(ctx, (int64_t)B * CK * Tp); CHECK_ALLOC(vtc_all);
-  if (ctx_kv_fused_ok(ctx, u, Tp)) {  // k_proj | v_proj rows are adjacent in the blob: one GEMM, the V half stored transposed (GemmArgs::Vt)
-    GemmArgs g;
-    g.A0 = ctx16; g.lda0 = u.kproj_all.Kpad; g.Wt = u.kproj_all.w; g.ldw = u.kproj_all.Kpad;
-    g.M = B * Tp; g.N = 2 * CK; g.K = u.kproj_all.Kpad; g.C = kc_all; g.ldc = CK;
-    if (u.kproj_all.w_tm) { g.Wt = u.kproj_all.w_tm; g.ldw = 64; g.w_kts = 2 * CK * 128; }
-    g.Vt = vtc_all; g.vt_n0 = CK; g.vt_ld = Tp; g.vt_S = Tp; g.vt_sB = (int64_t)CK * Tp;
-    TSD_TRY(launch_gemm(ctx, g));
-  } else {
-    GemmArgs g;
-    g.A0 = ctx16; g.lda0 = u.kproj_all.Kpad; g.Wt = u.kproj_all.w; g.ldw = u.kproj_all.Kpad;
-    g.M = B * Tp; g.N = CK; g.K = u.kproj_all.Kpad; g.C = kc_all; g.ldc = CK;
-    TSD_TRY(launch_gemm(ctx, g));
-    GemmArgs v;
-    v.A0 = u.vproj_all.w; v.lda0 = u.vproj_all.Kpad; v.sA = 0;
-    v.Wt = ctx16; v.ldw = u.vproj_all.Kpad; v.sW = (int64_t)Tp * u.vproj_all.Kpad;
-    v.M = CK; v.N = Tp; v.K = u.vproj_all.Kpad; v.batch = B;
-    v.C = vtc_all; v.ldc = Tp; v.sC = (int64_t)CK * Tp;
-    TSD_TRY(launch_gemm(ctx, v));
+  const half_t* kc_all = pre ? pre->kc_all : nullptr;
+  const half_t* vtc_all = pre ? pre->vtc_all : nullptr;
+  if (!pre) {
+    half_t* kc = arena_alloc<half_t>(ctx, (int64_t)B * Tp * CK); CHECK_ALLOC(kc);
+    half_t* vtc = arena_alloc<half_t>(ctx, (int64_t)B * CK * Tp); CHECK_ALLOC(vtc);
+    TSD_TRY(g_unet_ctx_kv(m, ctx16, Tp, B, kc, vtc));
+    kc_all = kc; vtc_all = vtc;
   }
   auto attn = [&](int i) -> int {
     TSD_TRY(alloc_out(i, a[i - 1].H, a[i - 1].C));
@@ -542,18 +570,13 @@ int g_unet_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, 
 // Encoders push their output; every decoder residual block reads concat(x, popped skip) through the two-source views;
 // Upsample + conv3x3 is one implicit-GEMM launch that reads its input through the nearest-2x addressing.
 static int g_unet_full_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, int T, int Tp,
-                               const float* temb, int B, int L, float* eps_out_chw, bool eps_nhwc) {
+                               const float* temb, int B, int L, float* eps_out_chw, bool eps_nhwc, const UNetPre* pre) {
   tsd_ctx* ctx = m->ctx;
   const UNetW& u = m->unet;
   if (L % 16) TSD_FAIL(TSD_E_SHAPE, "full-size UNet: latent side %d must be a multiple of 16", L);
-  float* t1 = arena_alloc<float>(ctx, (int64_t)B * 1280); CHECK_ALLOC(t1);
-  float* time = arena_alloc<float>(ctx, (int64_t)B * 1280); CHECK_ALLOC(time);
-  float* tvec = arena_alloc<float>(ctx, (int64_t)B * u.tproj.N); CHECK_ALLOC(tvec);
-  TSD_TRY(launch_small_linear(ctx, temb, B, 320, 320, u.t1.w, u.t1.Kpad, u.t1.b, 1280, 0, t1, 1280));
-  TSD_TRY(launch_small_linear(ctx, t1, B, 1280, 1280, u.t2.w, u.t2.Kpad, u.t2.b, 1280, 1, time, 1280));
-  TSD_TRY(launch_small_linear(ctx, time, B, 1280, 1280, u.tproj.w, u.tproj.Kpad, u.tproj.b, u.tproj.N, 1, tvec,
-                              u.tproj.N));
-  const int tld = u.tproj.N;
+  const float* tvec = pre ? pre->tvec : nullptr;
+  const int tld = pre ? pre->tld : u.tproj.N;
+  if (!pre) TSD_TRY(g_unet_time_path(m, temb, B, &tvec));
   const bool in_im2col = ctx->opt.conv_in_im2col && u.conv_in_im2col && !u.conv.empty() && u.conv[0].I == 4 && SD15_STEPS[0].l.kind == L_CONV &&
                          SD15_STEPS[0].l.d == 1;  // as in g_unet_forward: the 4-channel input convolution as one im2col K tile
   Act x0 = act_alloc(ctx, B, L, L, 64); CHECK_ALLOC(x0.p);
@@ -561,26 +584,13 @@ static int g_unet_full_forward(tsd_model* m, const float* latents_chw, const hal
   else TSD_TRY(launch_chw_f32_to_nhwc_f16(ctx, latents_chw, B, 4, L, L, 4, 1.f, x0.p, 64));
   // context K and V^T of all sixteen attention blocks in two GEMMs
   const int CK = u.kproj_all.N;
-  half_t* kc_all = arena_alloc<half_t>(ctx, (int64_t)B * Tp * CK); CHECK_ALLOC(kc_all);
-  half_t* vtc_all = arena_alloc<half_t>(ctx, (int64_t)B * CK * Tp); CHECK_ALLOC(vtc_all);
-  if (ctx_kv_fused_ok(ctx, u, Tp)) {  // k_proj | v_proj rows are adjacent in the blob: one GEMM, the V half stored transposed (GemmArgs::Vt)
-    GemmArgs g;
-    g.A0 = ctx16; g.lda0 = u.kproj_all.Kpad; g.Wt = u.kproj_all.w; g.ldw = u.kproj_all.Kpad;
-    g.M = B * Tp; g.N = 2 * CK; g.K = u.kproj_all.Kpad; g.C = kc_all; g.ldc = CK;
-    if (u.kproj_all.w_tm) { g.Wt = u.kproj_all.w_tm; g.ldw = 64; g.w_kts = 2 * CK * 128; }
-    g.Vt = vtc_all; g.vt_n0 = CK; g.vt_ld = Tp; g.vt_S = Tp; g.vt_sB = (int64_t)CK * Tp;
-    TSD_TRY(launch_gemm(ctx, g));
-  } else {
-    GemmArgs g;
-    g.A0 = ctx16; g.lda0 = u.kproj_all.Kpad; g.Wt = u.kproj_all.w; g.ldw = u.kproj_all.Kpad;
-    g.M = B * Tp; g.N = CK; g.K = u.kproj_all.Kpad; g.C = kc_all; g.ldc = CK;
-    TSD_TRY(launch_gemm(ctx, g));
-    GemmArgs v;
-    v.A0 = u.vproj_all.w; v.lda0 = u.vproj_all.Kpad; v.sA = 0;
-    v.Wt = ctx16; v.ldw = u.vproj_all.Kpad; v.sW = (int64_t)Tp * u.vproj_all.Kpad;
-    v.M = CK; v.N = Tp; v.K = u.vproj_all.Kpad; v.batch = B;
-    v.C = vtc_all; v.ldc = Tp; v.sC = (int64_t)CK * Tp;
-    TSD_TRY(launch_gemm(ctx, v));
+  const half_t* kc_all = pre ? pre->kc_all : nullptr;
+  const half_t* vtc_all = pre ? pre->vtc_all : nullptr;
+  if (!pre) {
+    half_t* kc = arena_alloc<half_t>(ctx, (int64_t)B * Tp * CK); CHECK_ALLOC(kc);
+    half_t* vtc = arena_alloc<half_t>(ctx, (int64_t)B * CK * Tp); CHECK_ALLOC(vtc);
+    TSD_TRY(g_unet_ctx_kv(m, ctx16, Tp, B, kc, vtc));
+    kc_all = kc; vtc_all = vtc;
   }
   std::vector<Act> skips;
   Act cur = x0;

@@ -57,8 +57,18 @@ int g_qkv_proj(tsd_ctx* ctx, const half_t* x, int B, int S, int C, const LinW& i
 // latents: fp32 CHW [B,4,L,L]; context16: fp16 [B][Tp][768]; temb: fp32 [B][320]; eps_out: fp32 CHW [B,4,L,L]
 // eps_nhwc: eps_out receives the output convolution's own layout, fp32 [B][L*L][4], instead of CHW (the denoise session's DDPM update
 // reads it directly: one conversion launch per step less)
+// pre: what the forward computes from the timestep and the context alone, made ahead by the caller (the denoise session keeps both
+// across the steps of an upload()).  Absent, the forward launches the two helpers below itself; present, it launches nothing for them
+// and reads neither `temb` nor, for the K / V^T projections, `ctx16`.
+struct UNetPre {
+  const float* tvec = nullptr; int tld = 0;  // time projections of all residual blocks [.][tproj.N]; tld: per-sample stride (0 = one row for all)
+  const half_t* kc_all = nullptr;            // context K of all attention blocks [B*Tp][CK], CK = kproj_all.N
+  const half_t* vtc_all = nullptr;           // context V^T [B][CK][Tp]
+};
 int g_unet_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, int T, int Tp, const float* temb, int B,
-                   int L, float* eps_out_chw, bool eps_nhwc = false);
+                   int L, float* eps_out_chw, bool eps_nhwc = false, const UNetPre* pre = nullptr);
+int g_unet_time_path(tsd_model* m, const float* temb, int B, const float** tvec_out);  // -> tvec [B][tproj.N] in the arena
+int g_unet_ctx_kv(tsd_model* m, const half_t* ctx16, int Tp, int B, half_t* kc_all, half_t* vtc_all);
 int g_decoder_forward(tsd_model* m, const float* latents_chw, int B, int L, float* images_chw);
 int g_encoder_forward(tsd_model* m, const float* images_chw, const float* noise_chw, int B, int S, float* latents_chw);
 

@@ -22,6 +22,7 @@ bool attn_head_weights_ok(const AttnW& w) {
 // parameters changed: derived buffers are stale until the next model_check_ready()
 static void model_invalidate_derived(tsd_model* m) {
   m->ready = false;
+  m->gen++;
   for (auto& a : m->unet.attn) { a.tail_stream = nullptr; a.head_stream = nullptr; a.fold_w = nullptr; a.fold_w_tm = nullptr; a.fold_b = nullptr; }
   m->unet.conv_in_im2col = nullptr;
   m->vae.conv_in_im2col = nullptr;

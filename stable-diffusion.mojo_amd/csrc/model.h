@@ -125,6 +125,8 @@ struct tsd_model {
   size_t blob_bytes = 0;
   std::vector<char> loaded;
   bool ready = false;
+  unsigned gen = 0;  // parameter generation: moves whenever `ready` is cleared (set_param, init_random, mark_loaded); a denoise session
+                     // remembers the one its step-invariant buffers were built from
   UNetW unet;
   VaeW vae;
   ClipW clip;

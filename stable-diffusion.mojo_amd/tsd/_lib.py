@@ -134,6 +134,8 @@ def _declare(l):
         "tsd_debug_set_attn_diag": ([vp, i], i),
         "tsd_debug_set_res_fuse_skip": ([vp, i], i),
         "tsd_debug_set_qkv_fuse": ([vp, i], i),
+        "tsd_debug_set_session_hoist": ([vp, i], i),
+        "tsd_debug_session_hoist_info": ([vp, C.POINTER(i64)], i),
         "tsd_debug_mfma_sustained": ([vp, C.c_float, fp, fp], i),
         "tsd_debug_gemm_check": ([vp, i, i, i, i, i, i, i, i, i, i, fp, fp], i),
         "tsd_debug_gemm_record": ([vp, i], i),

@@ -145,6 +145,12 @@ class Session:
         check(lib().tsd_session_download_images(self.h, 1 if rescale else 0, ptr(out)))
         return out
 
+    def hoist_info(self):
+        """{active, time_table, ctx_k, ctx_vt (device addresses), bytes, builds} of the step-invariant buffers (tsd_debug_session_hoist_info)."""
+        info = (C.c_int64 * 6)()
+        check(lib().tsd_debug_session_hoist_info(self.h, info))
+        return dict(zip(("active", "time_table", "ctx_k", "ctx_vt", "bytes", "builds"), (int(v) for v in info)))
+
     def close(self):
         if self.h:
             lib().tsd_session_destroy(self.h)
