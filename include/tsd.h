@@ -277,6 +277,24 @@ int tsd_sampler_coeffs(int kind, double eta, int spacing, int n_train, int n_inf
 int tsd_sampler_step_f32(tsd_ctx* ctx, const float* x, const float* eps, const float* eps_uncond, float cfg_scale,
                          const float* hist, const float* noise, int64_t n, const float* c, float* x_out, float* hist_out);
 
+/* ---- masked denoising / inpainting (EXTENSION: the reference has txt2img and img2img only) ---------------------------------
+ * The classic 4-channel inpainting: after each sampler update the known region of the latents is replaced by the original
+ * latents, noised to the timestep the update has just reached,
+ *     k  = a_prev * known + s_prev * noise                    a_prev = sqrt(abar_prev), s_prev = sqrt(1 - abar_prev)
+ *     x' = m * x + (1 - m) * k                                m = 1: regenerate, m = 0: keep
+ * every product, sum and difference one fp32 rounding in this order, so m = 1 returns x and m = 0 returns k bitwise (finite operands).
+ * TSD_MASK_AREA: a latent cell's mask is the mean of its 8x8 pixel block.  TSD_MASK_ANY: 1 if any pixel of the block is >= 0.5,
+ * else 0 - a cell that touches a masked pixel is regenerated. */
+typedef enum tsd_mask_mode { TSD_MASK_AREA = 0, TSD_MASK_ANY = 1 } tsd_mask_mode;
+/* Op level, host fp32 in/out, synchronous.  mask_px [B][8L][8L] -> mask_lat [B][L][L].  Every value must be finite and in [0, 1]
+ * (TSD_E_ARG, like an unknown mode); TSD_E_SHAPE for B <= 0 or L <= 0. */
+int tsd_latent_mask_f32(tsd_ctx* ctx, const float* mask_px, int B, int L, int mode, float* mask_lat);
+/* Op level, host fp32 in/out, synchronous: the blend above on x / known / noise / x_out CHW [B][4][hw] and mask [B][hw] (one mask
+ * value serves the 4 channels) - the kernel a session with inpainting launches after its sampler update.  noise may be NULL (k =
+ * a_prev * known).  x_out may be x.  A non-finite output is counted (TSD_E_NONFINITE): an inf in x under m = 0 comes out as NaN. */
+int tsd_inpaint_blend_f32(tsd_ctx* ctx, const float* x, const float* mask, const float* known, const float* noise, int B,
+                          int64_t hw, float a_prev, float s_prev, float* x_out);
+
 /* ---- device-resident denoise loop (pipeline.mojo:57-127 + sampler.mojo:15-124) --------- */
 
 /* B samples, latent side L, T context tokens; cfg != 0 runs the UNet on 2B (cond + uncond,
@@ -303,6 +321,17 @@ int tsd_session_upload(tsd_session* s, const float* latents, const float* contex
 int tsd_session_step(tsd_session* s, int i);
 /* `add_noise` sampler.mojo:111-124 at timestep index i (img2img), noise [B,4,L,L] host. */
 int tsd_session_add_noise(tsd_session* s, int i, const float* noise);
+/* Masked denoising (see "masked denoising" above) for the steps of the current upload: mask [B][L][L] (1 = regenerate, 0 = keep),
+ * known [B,4,L,L] (the original latents), noise [B,4,L,L] or NULL for a noiseless known region; all host, copied into buffers the
+ * session owns; synchronous.  While it is on, step(i) launches the blend in place on the latents after its sampler update, with the
+ * scalars of the timestep the update lands on: entry i + 1 of the list (tsd_sampler_coeffs(..., i + 1, ...) out[2], out[3] rounded to
+ * float), (1, 0) after the last entry - the same for all three samplers.  mask == NULL turns it off (known and noise are ignored).
+ * It belongs to one upload: TSD_E_STATE before tsd_session_upload; upload(), set_schedule and set_sampler turn it off.  TSD_E_ARG,
+ * with the previous state unchanged, for a mask value that is not finite or outside [0, 1], for a missing known and for inf / NaN in
+ * known or noise.  The latents are not modified; like add_noise it drops the DPM-Solver++(2M) history (the next step runs first order)
+ * and the decoded images.  A session that never calls it enqueues exactly the launches it enqueued before. */
+int tsd_session_set_inpaint(tsd_session* s, const float* mask, const float* known, const float* noise);
+int tsd_session_inpaint_active(tsd_session* s); /* 1 / 0; < 0 on a NULL session */
 int tsd_session_decode(tsd_session* s); /* Decoder.forward on the current latents (async) */
 int tsd_session_download_latents(tsd_session* s, float* latents);
 int tsd_session_download_images(tsd_session* s, int rescale_0_255, float* images);

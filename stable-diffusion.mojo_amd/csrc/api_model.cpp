@@ -132,6 +132,10 @@ struct tsd_session {
   float* noise = nullptr;     // [nsteps,B,4,L,L] or null
   float* images = nullptr;    // [B,3,8L,8L]
   float* hist = nullptr;      // [B,4,L,L] fp32: the data prediction x0 of the previous step (DPM-Solver++(2M))
+  // masked denoising (tsd_session_set_inpaint): carved from `state` like the rest, filled by set_inpaint, read by the blend of a step
+  float* ip_mask = nullptr;   // [B][L*L] fp32 in [0,1]: 1 = regenerate, 0 = keep `ip_known`
+  float* ip_known = nullptr;  // [B,4,L,L] the original latents
+  float* ip_noise = nullptr;  // [B,4,L,L] the noise they are re-noised with
   size_t noise_cap = 0;
   // What a step's UNet forward computes from the timestep and the context alone (graph.h UNetPre), made once per upload() by
   // session_build_invariants when the context's session_hoist is on: own allocations, grown at upload() like `noise`, never in a step.
@@ -154,6 +158,8 @@ struct tsd_session {
   // after a sampler that keeps no history.  A step with any other index runs first order.
   int hist_valid_for = -1;
   bool uploaded = false, has_noise = false;
+  // inpainting belongs to one upload(): off after upload() and after set_schedule / set_sampler; ip_has_noise: ip_noise was given
+  bool inpaint = false, ip_has_noise = false;
   size_t plan_unet = 0, plan_dec = 0;
   unsigned opt_gen = 0;  // generation of the context's options the workspace was sized for (upload)
   // Latched when the host scan of a download found inf / NaN in THIS session's latents: the context's counter is cleared once reported,
@@ -230,6 +236,7 @@ extern "C" int tsd_debug_session_hoist_info(tsd_session* s, int64_t* info) {
 
 static void schedule_changed(tsd_session* s) {
   s->uploaded = false; s->has_noise = false;
+  s->inpaint = false;
   s->hist_valid_for = -1;
   s->decoded = false;
 }
@@ -252,7 +259,8 @@ extern "C" int tsd_session_create(tsd_model* diffusion, tsd_model* decoder, int 
   auto carve = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~size_t(255); return o; };
   const size_t o_lat = carve(nl * 4), o_lat2 = carve(2 * nl * 4), o_ctx = carve((size_t)Bu * s->Tp * 768 * 2),
                o_eps = carve((size_t)Bu * 4 * L * L * 4), o_t = carve(16 * 4), o_te = carve(16 * 320 * 4),
-               o_img = carve(decoder ? (size_t)B * 3 * 64 * L * L * 4 : 0), o_hist = carve(nl * 4);
+               o_img = carve(decoder ? (size_t)B * 3 * 64 * L * L * 4 : 0), o_hist = carve(nl * 4),
+               o_ipm = carve((size_t)B * L * L * 4), o_ipk = carve(nl * 4), o_ipn = carve(nl * 4);
   hipError_t e = hipMalloc((void**)&s->state, off);
   if (e != hipSuccess) { delete s; TSD_FAIL(TSD_E_ALLOC, "session: hipMalloc(%zu) failed: %s", off, hipGetErrorString(e)); }
   if (ctx->opt.debug_poison >= 0 && (ctx->opt.debug_poison_what & 4)) hipMemsetAsync(s->state, ctx->opt.debug_poison & 255, off, ctx->stream);
@@ -261,6 +269,7 @@ extern "C" int tsd_session_create(tsd_model* diffusion, tsd_model* decoder, int 
   s->tdev = (float*)(s->state + o_t); s->temb = (float*)(s->state + o_te);
   s->images = decoder ? (float*)(s->state + o_img) : nullptr;
   s->hist = (float*)(s->state + o_hist);
+  s->ip_mask = (float*)(s->state + o_ipm); s->ip_known = (float*)(s->state + o_ipk); s->ip_noise = (float*)(s->state + o_ipn);
   if (build_schedule(s) != TSD_OK) { hipFree(s->state); delete s; return TSD_E_ARG; }
   *out = s;
   return TSD_OK;
@@ -345,6 +354,7 @@ extern "C" int tsd_session_upload(tsd_session* s, const float* latents, const fl
   const int Bu = s->cfg ? 2 * B : B;
   s->hoist = ctx->opt.session_hoist != 0;
   s->uploaded = false;  // until this upload() is complete: the buffers below may move
+  s->inpaint = false;   // the mask and the known latents belonged to the previous upload()
   if (s->hoist) {  // the buffers of session_build_invariants; sizes depend on the session's shape and the schedule's length only
     const int CK = s->unet->unet.kproj_all.N, N = s->unet->unet.tproj.N;
     const size_t kc_bytes = ((size_t)Bu * Tp * CK * 2 + 255) & ~size_t(255), kv_bytes = 2 * kc_bytes;
@@ -406,6 +416,20 @@ static void ddpm_coeffs(const tsd_session* s, int t, int prev, float* sa, float*
   *sigma = t > 0 ? sqrtf(var) : 0.f;
 }
 
+// The launch a step with inpainting adds after its sampler update: the known region of `latents` is replaced by the original latents
+// noised to the timestep the update has just reached - entry i + 1 of the list, the clean sample (1, 0) after the last entry; under
+// LEADING spacing that entry is the reference's t - N // n.  a_prev = sqrt(abar), s_prev = sqrt(1 - abar) in double from the fp32 table,
+// rounded to float once: what tsd_sampler_coeffs reports as out[2], out[3] for step i + 1.  The same rule for all three samplers.
+static int session_inpaint_blend(tsd_session* s, int i) {
+  double a_prev = 1.0, s_prev = 0.0;
+  if (i + 1 < (int)s->timesteps.size()) {
+    const double abar = s->alphas_cumprod[s->timesteps[i + 1]];
+    a_prev = sqrt(abar); s_prev = sqrt(1.0 - abar);
+  }
+  return launch_inpaint_blend(s->ctx, s->latents, s->ip_mask, s->ip_known, s->ip_has_noise ? s->ip_noise : nullptr, s->B,
+                              (int64_t)s->L * s->L, (float)a_prev, (float)s_prev, s->latents);
+}
+
 extern "C" int tsd_session_step(tsd_session* s, int i) {
   NOTNULL(s);
   if (!s->uploaded) TSD_FAIL(TSD_E_STATE, "session: upload() before step()");
@@ -445,8 +469,9 @@ extern "C" int tsd_session_step(tsd_session* s, int i) {
                                                        : (i + 1 < (int)s->timesteps.size() ? s->timesteps[i + 1] : -1);
     ddpm_coeffs(s, t, prev, &sa, &sb, &c_x0, &c_xt, &sigma);
     const float* nz = (s->has_noise && t > 0) ? s->noise + (size_t)i * nl : nullptr;
-    return launch_ddpm_step(ctx, s->latents, s->eps, eps_u, s->cfg_scale, nz, (int64_t)nl, sa, sb, c_x0, c_xt, sigma,
-                            eps_nhwc ? L * L : 0);
+    TSD_TRY(launch_ddpm_step(ctx, s->latents, s->eps, eps_u, s->cfg_scale, nz, (int64_t)nl, sa, sb, c_x0, c_xt, sigma,
+                             eps_nhwc ? L * L : 0));
+    return s->inpaint ? session_inpaint_blend(s, i) : TSD_OK;
   }
   // DDIM / DPM-Solver++(2M): the scalars of tsd_sampler_coeffs (double), rounded to float once here
   double cd[8];
@@ -456,7 +481,8 @@ extern "C" int tsd_session_step(tsd_session* s, int i) {
   const float* nz = (!multistep && s->has_noise && c.c_n != 0.f) ? s->noise + (size_t)i * nl : nullptr;
   TSD_TRY(launch_sampler_step(ctx, s->latents, s->eps, eps_u, s->cfg_scale, have_hist ? s->hist : nullptr, nz, (int64_t)nl, c,
                               eps_nhwc ? L * L : 0, s->latents, multistep ? s->hist : nullptr));
-  if (multistep) s->hist_valid_for = i + 1;
+  if (s->inpaint) TSD_TRY(session_inpaint_blend(s, i));  // a failed step leaves no valid history
+  if (multistep) s->hist_valid_for = i + 1;  // the blend changed the latents, not the prediction the next step extrapolates from
   return TSD_OK;
 }
 
@@ -474,6 +500,32 @@ extern "C" int tsd_session_add_noise(tsd_session* s, int i, const float* noise) 
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return TSD_OK;
 }
+
+extern "C" int tsd_session_set_inpaint(tsd_session* s, const float* mask, const float* known, const float* noise) {
+  NOTNULL(s);
+  if (!s->uploaded) TSD_FAIL(TSD_E_STATE, "session: upload() before set_inpaint() (inpainting belongs to one upload)");
+  tsd_ctx* ctx = s->ctx;
+  const size_t hw = (size_t)s->L * s->L, nm = (size_t)s->B * hw, nl = 4 * nm;
+  if (mask) {  // every refusal comes before the first copy: a refused call leaves the previous mask, tensors and history as they were
+    NOTNULL(known);
+    bool in_range = true;
+    for (size_t k = 0; k < nm; k++) in_range &= (mask[k] >= 0.f) & (mask[k] <= 1.f);  // false for NaN
+    if (!in_range) TSD_FAIL(TSD_E_ARG, "session: every inpainting mask value must be finite and in [0, 1]");
+    if (!host_all_finite(known, nl)) TSD_FAIL(TSD_E_ARG, "session: inf / NaN in the known latents of set_inpaint()");
+    if (noise && !host_all_finite(noise, nl)) TSD_FAIL(TSD_E_ARG, "session: inf / NaN in the noise of set_inpaint()");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(s->ip_mask, mask, nm * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(s->ip_known, known, nl * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (noise) HIP_TRY(hipMemcpyAsync(s->ip_noise, noise, nl * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // the host tensors are the caller's again on return
+  }
+  s->inpaint = mask != nullptr;
+  s->ip_has_noise = mask && noise;
+  s->hist_valid_for = -1;  // the steps that follow run on other latents than the history was predicted for: as after add_noise()
+  s->decoded = false;
+  return TSD_OK;
+}
+extern "C" int tsd_session_inpaint_active(tsd_session* s) { return s ? (s->uploaded && s->inpaint ? 1 : 0) : TSD_E_ARG; }
 
 extern "C" int tsd_session_decode(tsd_session* s) {
   NOTNULL(s);

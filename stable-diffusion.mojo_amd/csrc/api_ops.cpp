@@ -268,6 +268,50 @@ extern "C" int tsd_sampler_step_f32(tsd_ctx* ctx, const float* x, const float* e
   });
 }
 
+// inf / NaN or a value outside [lo, hi] in a host tensor (the argument scans of the masked-denoising entries)
+static bool host_all_in_range(const float* p, size_t n, float lo, float hi) {
+  bool ok = true;
+  for (size_t i = 0; i < n; i++) ok &= (p[i] >= lo) & (p[i] <= hi);  // false for NaN
+  return ok;
+}
+
+// pixel mask -> latent mask (kernels_sampler.hip k_latent_mask) on host tensors
+extern "C" int tsd_latent_mask_f32(tsd_ctx* ctx, const float* mask_px, int B, int L, int mode, float* mask_lat) {
+  NOTNULL(ctx); NOTNULL(mask_px); NOTNULL(mask_lat);
+  if (mode != TSD_MASK_AREA && mode != TSD_MASK_ANY) TSD_FAIL(TSD_E_ARG, "latent mask: mode %d (0 area, 1 any)", mode);
+  if (B <= 0 || L <= 0) TSD_FAIL(TSD_E_SHAPE, "latent mask: B=%d L=%d", B, L);
+  const int64_t npx = (int64_t)B * 64 * L * L, nl = (int64_t)B * L * L;
+  if (!host_all_in_range(mask_px, (size_t)npx, 0.f, 1.f)) TSD_FAIL(TSD_E_ARG, "latent mask: every mask value must be finite and in [0, 1]");
+  return run_op(ctx, [&]() -> int {
+    Dev d{ctx};
+    float* dm = d.in(mask_px, npx);
+    float* dy = d.buf<float>(nl);
+    if (d.err) return d.err;
+    TSD_TRY(launch_latent_mask(ctx, dm, B, L, mode, dy));
+    return d.out(mask_lat, dy, nl);
+  });
+}
+
+// the masked-denoising blend (kernels_sampler.hip k_inpaint_blend) on host tensors: the launch a session with inpainting adds to a step.
+// On the device the blend runs in place (x_out is x) when the host pointers are the same, as the session runs it.
+extern "C" int tsd_inpaint_blend_f32(tsd_ctx* ctx, const float* x, const float* mask, const float* known, const float* noise, int B,
+                                     int64_t hw, float a_prev, float s_prev, float* x_out) {
+  NOTNULL(ctx); NOTNULL(x); NOTNULL(mask); NOTNULL(known); NOTNULL(x_out);
+  if (B <= 0 || hw <= 0) TSD_FAIL(TSD_E_SHAPE, "inpaint blend: B=%d hw=%lld", B, (long long)hw);
+  const int64_t n = (int64_t)B * 4 * hw;
+  return run_op(ctx, [&]() -> int {
+    Dev d{ctx};
+    float* dx = d.in(x, n);
+    float* dm = d.in(mask, (int64_t)B * hw);
+    float* dk = d.in(known, n);
+    float* dz = noise ? d.in(noise, n) : nullptr;
+    float* dy = x_out == x ? dx : d.buf<float>(n);
+    if (d.err) return d.err;
+    TSD_TRY(launch_inpaint_blend(ctx, dx, dm, dk, dz, B, hw, a_prev, s_prev, dy));
+    return d.out(x_out, dy, n);
+  });
+}
+
 extern "C" int tsd_linear_f32(tsd_ctx* ctx, const float* x, int M, int K, const float* w, const float* bias, int N,
                               float* y) {
   NOTNULL(x); NOTNULL(w); NOTNULL(y);

@@ -313,6 +313,12 @@ struct SamplerCoeffs {
 int launch_sampler_step(tsd_ctx* ctx, const float* x, const float* eps, const float* eps_uncond, float cfg_scale,
                         const float* hist_in, const float* noise, int64_t n, const SamplerCoeffs& c, int eps_hw, float* x_out,
                         float* hist_out);
+// masked denoising (kernels_sampler.hip): x_out = m x + (1 - m)(a_prev known + s_prev noise); x / known / noise / x_out CHW [B][4][hw],
+// mask [B][hw]; noise may be nullptr (that term is skipped); x_out may be x
+int launch_inpaint_blend(tsd_ctx* ctx, const float* x, const float* mask, const float* known, const float* noise, int B, int64_t hw,
+                         float a_prev, float s_prev, float* x_out);
+// pixel mask [B][8L][8L] -> latent mask [B][L][L] by 8x8 blocks; mode is a tsd_mask_mode
+int launch_latent_mask(tsd_ctx* ctx, const float* mask_px, int B, int L, int mode, float* mask_lat);
 // alphas_cumprod of the scaled-linear beta schedule (sampler.mojo:28-32), fp32 like the reference's Tensor
 void sampler_alphas_cumprod(int n_train, std::vector<float>& out);
 // timestep list of `spacing` (tsd_timestep_spacing) with the first `start_step` entries dropped; TSD_E_ARG on a bad argument

@@ -68,3 +68,80 @@ int launch_sampler_step(tsd_ctx* ctx, const float* x, const float* eps, const fl
   HIP_TRY(hipGetLastError());
   return TSD_OK;
 }
+
+// ---- masked denoising (inpainting): hold the known region of the latents after a sampler update -------------------------------------
+//   k     = a_prev * known + s_prev * noise        the original latents noised to the timestep the update has just reached
+//   x_out = m * x + (1 - m) * k                    m = 1: regenerate (keep the sampler's x), m = 0: keep the known region
+// x / known / noise / x_out are CHW [B][4][hw] fp32, mask is [B][hw] and serves the 4 channels of its sample.  noise may be nullptr:
+// its term is skipped and k = a_prev * known.  Every product, sum and difference is ONE fp32 rounding (contraction into fma is off), in
+// this order:
+//   ka = a_prev * known ; kn = s_prev * noise ; k = ka + kn ; om = 1 - m ; tx = m * x ; tk = om * k ; x_out = tx + tk
+// Roundings that reach the output through its worst term (a_prev * known, or s_prev * noise): the product, k's sum, om, tk and the final
+// sum = 5 (4 without noise: no sum in k; the m * x term sees 2).  The dependency chain itself is 4 deep, om rounds beside k; 5 is what
+// tests/test_gpu_inpaint.py bounds the kernel with.  This form, not k + m (x - k), has exact ends for finite operands: m = 1 gives
+// om = 0, tk = +-0 and x_out = x bitwise (an x of -0 comes out as +0 or -0, equal as floats); m = 0 gives tx = +-0 and x_out = k bitwise.
+// A non-finite x under m = 0 is 0 * inf = NaN in the output and is counted, never replaced.
+// x_out may be x: element i is read and written by the same thread only.
+__global__ void k_inpaint_blend(const float* x, const float* __restrict__ mask, const float* __restrict__ known,
+                                const float* __restrict__ noise, int64_t n, int64_t hw, float a_prev, float s_prev, float* x_out,
+                                int* __restrict__ nonfinite) {
+#pragma clang fp contract(off)
+  int nbad = 0;
+  const int64_t chw = 4 * hw;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = i / chw, pix = (i - b * chw) % hw;
+    const float m = mask[b * hw + pix];
+    float k = a_prev * known[i];
+    if (noise) {
+      const float kn = s_prev * noise[i];
+      k = k + kn;
+    }
+    const float om = 1.f - m;
+    const float tx = m * x[i];
+    const float tk = om * k;
+    const float o = tx + tk;
+    nbad += nonfinite_f(o);
+    x_out[i] = o;
+  }
+  nonfinite_report(nonfinite, nbad);
+}
+int launch_inpaint_blend(tsd_ctx* ctx, const float* x, const float* mask, const float* known, const float* noise, int B, int64_t hw,
+                         float a_prev, float s_prev, float* x_out) {
+  if (!ctx->launch()) return TSD_OK;
+  ProfScope prof(ctx, KC_ELEMENTWISE);
+  const int64_t n = (int64_t)B * 4 * hw;
+  hipLaunchKernelGGL(k_inpaint_blend, GRID1D(n, 256), dim3(256), 0, ctx->stream, x, mask, known, noise, n, hw, a_prev, s_prev, x_out,
+                     ctx->status);
+  HIP_TRY(hipGetLastError());
+  return TSD_OK;
+}
+
+// Pixel mask [B][8L][8L] -> latent mask [B][L][L]: one thread per latent cell reduces its 8x8 block, rows top to bottom and left to
+// right within a row (a fixed order; one rounding per addition).
+//   TSD_MASK_AREA: the sum of the 64 values times 1/64 (a power of two: exact)
+//   TSD_MASK_ANY:  1 if the block's maximum is >= 0.5, else 0 - a latent cell that touches any masked pixel is regenerated
+__global__ void k_latent_mask(const float* __restrict__ mask_px, int B, int L, int mode, float* __restrict__ mask_lat) {
+#pragma clang fp contract(off)
+  const int64_t n = (int64_t)B * L * L;
+  const int W = 8 * L;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = i / ((int64_t)L * L);
+    const int cell = (int)(i - b * L * L), cy = cell / L, cx = cell - cy * L;
+    const float* src = mask_px + (b * W + (int64_t)cy * 8) * W + cx * 8;
+    float sum = 0.f, mx = 0.f;
+    for (int r = 0; r < 8; r++)
+      for (int c = 0; c < 8; c++) {
+        const float v = src[(int64_t)r * W + c];
+        sum = sum + v;
+        mx = fmaxf(mx, v);
+      }
+    mask_lat[i] = mode == TSD_MASK_ANY ? (mx >= 0.5f ? 1.f : 0.f) : sum * 0.015625f;
+  }
+}
+int launch_latent_mask(tsd_ctx* ctx, const float* mask_px, int B, int L, int mode, float* mask_lat) {
+  if (!ctx->launch()) return TSD_OK;
+  ProfScope prof(ctx, KC_ELEMENTWISE);
+  hipLaunchKernelGGL(k_latent_mask, GRID1D((int64_t)B * L * L, 256), dim3(256), 0, ctx->stream, mask_px, B, L, mode, mask_lat);
+  HIP_TRY(hipGetLastError());
+  return TSD_OK;
+}

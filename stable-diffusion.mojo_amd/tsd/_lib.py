@@ -24,6 +24,7 @@ MODEL_DIFFUSION, MODEL_DECODER, MODEL_ENCODER, MODEL_CLIP, MODEL_DIFFUSION_SD15,
 MODEL_CLIP_TORCH, MODEL_DECODER_TORCH, MODEL_ENCODER_TORCH = 7, 8, 9
 SAMPLER_KINDS = {"ddpm": 0, "ddim": 1, "dpmpp_2m": 2}      # tsd_sampler_kind
 TIMESTEP_SPACINGS = {"leading": 0, "trailing": 1}          # tsd_timestep_spacing
+MASK_MODES = {"area": 0, "any": 1}                         # tsd_mask_mode
 
 
 def sampler_kind(kind):
@@ -34,6 +35,11 @@ def sampler_kind(kind):
 def timestep_spacing(spacing):
     """"leading" | "trailing" (or the enum value) -> tsd_timestep_spacing."""
     return TIMESTEP_SPACINGS.get(spacing.lower(), -1) if isinstance(spacing, str) else int(spacing)
+
+
+def mask_mode(mode):
+    """"area" | "any" (or the enum value) -> tsd_mask_mode."""
+    return MASK_MODES.get(mode.lower(), -1) if isinstance(mode, str) else int(mode)
 
 
 class TsdError(RuntimeError):
@@ -115,6 +121,9 @@ def _declare(l):
         "tsd_sampler_timesteps": ([i, i, i, i, C.POINTER(i), i], i),
         "tsd_sampler_coeffs": ([i, C.c_double, i, i, i, i, i, i, C.POINTER(C.c_double)], i),
         "tsd_sampler_step_f32": ([vp, fp, fp, fp, f, fp, fp, i64, fp, fp, fp], i),
+        "tsd_latent_mask_f32": ([vp, fp, i, i, i, fp], i),
+        "tsd_inpaint_blend_f32": ([vp, fp, fp, fp, fp, i, i64, f, f, fp], i),
+        "tsd_session_set_inpaint": ([vp, fp, fp, fp], i), "tsd_session_inpaint_active": ([vp], i),
         "tsd_session_timestep": ([vp, i], i),
         "tsd_session_upload": ([vp, fp, fp, fp, fp, f], i), "tsd_session_step": ([vp, i], i),
         "tsd_session_add_noise": ([vp, i, fp], i), "tsd_session_decode": ([vp], i),

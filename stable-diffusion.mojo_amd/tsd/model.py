@@ -132,6 +132,33 @@ class Session:
     def add_noise(self, i, noise):
         check(lib().tsd_session_add_noise(self.h, int(i), ptr(f32(noise))))
 
+    def set_inpaint(self, mask, known=None, noise=None):
+        """Masked denoising for the steps of the current upload(): mask (B,L,L) or (B,1,L,L) in [0,1], 1 = regenerate and 0 = keep
+        `known` (B,4,L,L), the original latents, re-noised after every step with `noise` (B,4,L,L; None: a noiseless known region).
+        mask=None turns it off.  upload(), set_schedule() and set_sampler() turn it off as well."""
+        if mask is None:
+            check(lib().tsd_session_set_inpaint(self.h, None, None, None))
+            return
+        B, L = self.B, self.L
+        m = f32(mask)
+        if m.shape == (B, 1, L, L):
+            m = np.ascontiguousarray(m.reshape(B, L, L))
+        if m.shape != (B, L, L):
+            raise ValueError(f"mask must have shape {(B, L, L)} or {(B, 1, L, L)}, got {m.shape}")
+        if known is None:
+            raise ValueError("set_inpaint with a mask needs the known latents")
+        kn = f32(known)
+        if kn.shape != (B, 4, L, L):
+            raise ValueError(f"known must have shape {(B, 4, L, L)}, got {kn.shape}")
+        nz = f32(noise) if noise is not None else None
+        if nz is not None and nz.shape != (B, 4, L, L):
+            raise ValueError(f"noise must have shape {(B, 4, L, L)}, got {nz.shape}")
+        check(lib().tsd_session_set_inpaint(self.h, ptr(m), ptr(kn), ptr(nz)))
+
+    @property
+    def inpaint_active(self):
+        return lib().tsd_session_inpaint_active(self.h) == 1
+
     def decode(self):
         check(lib().tsd_session_decode(self.h))
 

@@ -6,7 +6,7 @@ import numpy as np
 
 from . import rng
 from .model import Session
-from .utils import rescale
+from .utils import latent_mask, rescale
 
 
 def encode_prompts(prompts, tokenizer, clip):
@@ -24,21 +24,30 @@ def encode_prompts(prompts, tokenizer, clip):
 
 def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg=True, cfg_scale=7.5,
              inference_steps=50, seed_val=0, input_image=None, encoder=None, latents=None, noise=None,
-             num_training_steps=1000, L=64, return_latents=False, sampler="ddpm", eta=0.0, spacing="leading"):
+             num_training_steps=1000, L=64, return_latents=False, sampler="ddpm", eta=0.0, spacing="leading", mask=None,
+             mask_mode="any"):
     """context (B,T,768); returns images (B,3,8L,8L) in [0,255] like pipeline.mojo:127.
 
     sampler "ddpm" (the reference's, about 50 steps) | "ddim" (eta = 0: deterministic) | "dpmpp_2m" (second-order multistep, 20-25
     steps); spacing "leading" (the reference's timesteps) | "trailing" (starts at N - 1: few-step sampling).  The defaults are the
     reference's loop.  Noise is read by "ddpm" and by "ddim" with eta > 0.
 
+    mask (B,1,8L,8L) or (B,8L,8L) in [0,1] with input_image and encoder: inpainting, 1 = regenerate, 0 = keep the image.  The loop is
+    img2img's with the known region of the latents put back after every step (`Session.set_inpaint`), re-noised with the noise
+    `add_noise` used; mask_mode "any" (a latent cell that touches a masked pixel is regenerated) | "area" (`latent_mask`).
+
     latents / noise default to N(0,1) from the counter RNG keyed by seed_val (App.A D19)."""
     context = np.asarray(context, dtype=np.float32)
     if context.ndim == 2:
         context = context[None]
     B, T, _ = context.shape
+    if mask is not None and (input_image is None or encoder is None):
+        raise ValueError("generate(mask=...) needs input_image and encoder: the mask says which part of that image to keep")
     if not (0.0 <= strength <= 1.0):  # pipeline.mojo:23-29
         print("Strength must be between 0 and 1. Returning empty matrix")
         return np.zeros((0, 0, 0), dtype=np.float32)
+    if mask is not None and np.shape(mask) not in ((B, 1, 8 * L, 8 * L), (B, 8 * L, 8 * L)):
+        raise ValueError(f"mask must have shape {(B, 1, 8 * L, 8 * L)} or {(B, 8 * L, 8 * L)}, got {np.shape(mask)}")
     sess = Session(diffusion.model, decoder.model if decoder is not None else None, B, L, T, cfg=cfg)
     start = 0
     if input_image is not None:
@@ -52,13 +61,18 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
         img = rescale(input_image, (0, 255), (-1, 1))
         enc_noise = rng.normal(seed_val, 1, nl).reshape(B, 4, L, L)
         latents = encoder.forward(img, enc_noise)
+        if mask is not None:
+            mask_lat = latent_mask(mask, mask_mode, diffusion.model.ctx)
     elif latents is None:
         latents = rng.normal(seed_val, 2, nl).reshape(B, 4, L, L)
     if noise is None:
         noise = rng.normal(seed_val, 3, n * nl).reshape(n, B, 4, L, L)
     sess.upload(latents, context, uncond_context if cfg else None, noise, cfg_scale)
     if input_image is not None:
-        sess.add_noise(0, rng.normal(seed_val, 4, nl).reshape(B, 4, L, L))  # sampler.mojo:111-124 at timesteps[0]
+        z4 = rng.normal(seed_val, 4, nl).reshape(B, 4, L, L)
+        sess.add_noise(0, z4)  # sampler.mojo:111-124 at timesteps[0]
+        if mask is not None:
+            sess.set_inpaint(mask_lat, latents, z4)
     for i in range(n):  # pipeline.mojo:87-122
         sess.step(i)
     out_lat = sess.latents()

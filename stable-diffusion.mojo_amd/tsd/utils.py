@@ -180,6 +180,34 @@ def Softmax(matrix, dim=2, ctx=None):
     return y
 
 
+def latent_mask(mask, mode="any", ctx=None):
+    """Pixel mask (B,8L,8L) or (B,1,8L,8L) in [0,1] -> latent mask (B,L,L) by 8x8 blocks (`tsd_latent_mask_f32`): "area" is the
+    block's mean, "any" is 1 where any pixel of the block is >= 0.5 (a cell that touches a masked pixel is regenerated)."""
+    m = f32(mask)
+    if m.ndim == 4 and m.shape[1] == 1:
+        m = np.ascontiguousarray(m[:, 0])
+    if m.ndim != 3 or m.shape[1] != m.shape[2] or m.shape[1] % 8 or m.shape[1] == 0:
+        raise ValueError(f"mask must have shape (B, 8L, 8L) or (B, 1, 8L, 8L), got {np.shape(mask)}")
+    B, L = m.shape[0], m.shape[1] // 8
+    y = np.empty((B, L, L), dtype=np.float32)
+    check(lib().tsd_latent_mask_f32(_ctx(ctx), ptr(m), B, L, _lib.mask_mode(mode), ptr(y)))
+    return y
+
+
+def inpaint_blend(x, mask, known, noise, a_prev, s_prev, ctx=None):
+    """x' = m x + (1 - m)(a_prev known + s_prev noise) (`tsd_inpaint_blend_f32`): x / known / noise (B,4,...) and mask (B,...) with one
+    value for the 4 channels; noise may be None.  The launch a session with `set_inpaint` adds to a step."""
+    x, m, kn = f32(x), f32(mask), f32(known)
+    nz = f32(noise) if noise is not None else None
+    B = x.shape[0]
+    hw = m.size // B if B else 0
+    if x.ndim < 2 or x.shape[1] != 4 or m.shape[0] != B or x.size != B * 4 * hw or kn.shape != x.shape or (nz is not None and nz.shape != x.shape):
+        raise ValueError(f"inpaint_blend: x {x.shape}, mask {m.shape}, known {kn.shape}" + (f", noise {nz.shape}" if nz is not None else ""))
+    y = np.empty_like(x)
+    check(lib().tsd_inpaint_blend_f32(_ctx(ctx), ptr(x), ptr(m), ptr(kn), ptr(nz), B, hw, float(a_prev), float(s_prev), ptr(y)))
+    return y
+
+
 def get_time_embedding(timestep, ctx=None):
     """`get_time_embedding` helpers/utils.mojo:353-370 -> (1,1,320)."""
     y = np.empty(320, dtype=np.float32)
