@@ -295,6 +295,16 @@ int tsd_latent_mask_f32(tsd_ctx* ctx, const float* mask_px, int B, int L, int mo
 int tsd_inpaint_blend_f32(tsd_ctx* ctx, const float* x, const float* mask, const float* known, const float* noise, int B,
                           int64_t hw, float a_prev, float s_prev, float* x_out);
 
+/* ---- seeded noise (EXTENSION: the reference draws from Mojo's stdlib PRNG) ------------------------------------------------------
+ * N(0,1) as a pure function of (seed, stream id, element counter j), computed on the device in fp32:
+ *     base = seed * 0x9E3779B97F4A7C15 + stream * 0xBF58476D1CE4E5B9        (uint64, wrapping; the rule of tsd_model_init_random)
+ *     k1 = mix64(base + 2j) >> 40, k2 = mix64(base + 2j + 1) >> 40          (24 bits each; mix64 = the splitmix64 finaliser)
+ *     z  = sqrt(-2 ln((k1 + 1) 2^-24)) * cos(pi k2 2^-23)                   |z| <= 5.77
+ * tsd/rng.py normal_counter is the float64 host twin; the device value is within 14 * 2^-24 relative of it (csrc/counter_rng.h), not
+ * bitwise equal: logf and cospif are the device library's. */
+/* Op level, host out, synchronous: out[e] = z at counter offset + e of the stream (seed, stream), e < n.  TSD_E_SHAPE for n <= 0. */
+int tsd_normal_fill_f32(tsd_ctx* ctx, uint64_t seed, uint64_t stream, uint64_t offset, int64_t n, float* out);
+
 /* ---- device-resident denoise loop (pipeline.mojo:57-127 + sampler.mojo:15-124) --------- */
 
 /* B samples, latent side L, T context tokens; cfg != 0 runs the UNet on 2B (cond + uncond,
@@ -332,6 +342,25 @@ int tsd_session_add_noise(tsd_session* s, int i, const float* noise);
  * and the decoded images.  A session that never calls it enqueues exactly the launches it enqueued before. */
 int tsd_session_set_inpaint(tsd_session* s, const float* mask, const float* known, const float* noise);
 int tsd_session_inpaint_active(tsd_session* s); /* 1 / 0; < 0 on a NULL session */
+/* Seeded device-side noise (see "seeded noise" above) for the steps of the current upload, one seed per sample: seeds [B] host, NULL
+ * turns it off.  While it is on, a DDPM step (t > 0) and a DDIM(eta > 0) step draw their noise inside the update kernel from stream
+ * 16 + i of seeds[b] - i the step index, the counter the element's index inside its sample (c*L + y)*L + x - with no noise buffer and no
+ * extra launch; the result is bitwise that of a session whose uploaded noise[i][b] is tsd_normal_fill_f32(seeds[b], 16 + i, 0, 4*L*L).
+ * A sample's noise depends on its seed alone, never on B or on its slot in the batch.  DPM-Solver++(2M) takes no noise and ignores it.
+ * It belongs to one upload: TSD_E_STATE before tsd_session_upload and when that upload carried a noise tensor (one source of noise per
+ * upload); upload(), set_schedule and set_sampler turn it off.  Like add_noise it drops the DPM-Solver++(2M) history and the decoded
+ * images.  A session that never calls it enqueues exactly the launches, and computes the bits, it did before. */
+int tsd_session_set_seeds(tsd_session* s, const uint64_t* seeds);
+int tsd_session_seeds_active(tsd_session* s); /* 1 / 0; < 0 on a NULL session */
+/* Replace the latents by stream 2 of each sample's seed (txt2img's initial latents; asynchronous).  TSD_E_STATE without seeds. */
+int tsd_session_seed_latents(tsd_session* s);
+/* tsd_session_add_noise at timestep index i with stream 4 of each sample's seed instead of a host tensor: the same scalars, the same
+ * kernel.  TSD_E_STATE without seeds, TSD_E_ARG for an index outside the schedule. */
+int tsd_session_add_noise_seeded(tsd_session* s, int i);
+/* tsd_session_set_inpaint whose noise is stream 4 of each sample's seed (the values add_noise_seeded used), filled into the session's
+ * buffer on the device.  Validation and state rules are set_inpaint's; TSD_E_STATE for a mask without seeds.  mask == NULL turns
+ * inpainting off. */
+int tsd_session_set_inpaint_seeded(tsd_session* s, const float* mask, const float* known);
 int tsd_session_decode(tsd_session* s); /* Decoder.forward on the current latents (async) */
 int tsd_session_download_latents(tsd_session* s, float* latents);
 int tsd_session_download_images(tsd_session* s, int rescale_0_255, float* images);

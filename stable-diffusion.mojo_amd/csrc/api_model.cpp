@@ -160,6 +160,10 @@ struct tsd_session {
   bool uploaded = false, has_noise = false;
   // inpainting belongs to one upload(): off after upload() and after set_schedule / set_sampler; ip_has_noise: ip_noise was given
   bool inpaint = false, ip_has_noise = false;
+  // seeded device-side noise (tsd_session_set_seeds) belongs to one upload() like inpainting: while on, a DDPM / DDIM(eta > 0) step draws
+  // its noise in the update kernel from stream 16 + i of seeds[b] (counter_rng.h), no buffer and no extra launch
+  bool seeded = false;
+  uint64_t seeds[16] = {};
   size_t plan_unet = 0, plan_dec = 0;
   unsigned opt_gen = 0;  // generation of the context's options the workspace was sized for (upload)
   // Latched when the host scan of a download found inf / NaN in THIS session's latents: the context's counter is cleared once reported,
@@ -237,6 +241,7 @@ extern "C" int tsd_debug_session_hoist_info(tsd_session* s, int64_t* info) {
 static void schedule_changed(tsd_session* s) {
   s->uploaded = false; s->has_noise = false;
   s->inpaint = false;
+  s->seeded = false;
   s->hist_valid_for = -1;
   s->decoded = false;
 }
@@ -355,6 +360,7 @@ extern "C" int tsd_session_upload(tsd_session* s, const float* latents, const fl
   s->hoist = ctx->opt.session_hoist != 0;
   s->uploaded = false;  // until this upload() is complete: the buffers below may move
   s->inpaint = false;   // the mask and the known latents belonged to the previous upload()
+  s->seeded = false;    // and so did the seeds
   if (s->hoist) {  // the buffers of session_build_invariants; sizes depend on the session's shape and the schedule's length only
     const int CK = s->unet->unet.kproj_all.N, N = s->unet->unet.tproj.N;
     const size_t kc_bytes = ((size_t)Bu * Tp * CK * 2 + 255) & ~size_t(255), kv_bytes = 2 * kc_bytes;
@@ -399,6 +405,15 @@ extern "C" int tsd_session_upload(tsd_session* s, const float* latents, const fl
   s->decoded = false;
   s->hist_valid_for = -1;
   return TSD_OK;
+}
+
+// Streams of the seeded noise, per sample b with seeds[b]: 2 the initial latents, 4 the add_noise / inpainting noise, 16 + i the noise of
+// schedule step i; the counter is the element's index inside its sample, (c*L + y)*L + x.  Nothing depends on B or on the sample's slot.
+enum { NOISE_STREAM_LATENTS = 2, NOISE_STREAM_ADD = 4, NOISE_STREAM_STEP0 = 16 };
+static NormalBases session_bases(const tsd_session* s, uint64_t stream) {
+  NormalBases nb = {};
+  for (int b = 0; b < s->B; b++) nb.base[b] = counter_rng_base(s->seeds[b], stream);
+  return nb;
 }
 
 // scalar coefficients of `DDPMSampler.step` sampler.mojo:81-98 and `get_variance` :53-65 (fp32 like the reference).  `prev` is the
@@ -469,8 +484,12 @@ extern "C" int tsd_session_step(tsd_session* s, int i) {
                                                        : (i + 1 < (int)s->timesteps.size() ? s->timesteps[i + 1] : -1);
     ddpm_coeffs(s, t, prev, &sa, &sb, &c_x0, &c_xt, &sigma);
     const float* nz = (s->has_noise && t > 0) ? s->noise + (size_t)i * nl : nullptr;
-    TSD_TRY(launch_ddpm_step(ctx, s->latents, s->eps, eps_u, s->cfg_scale, nz, (int64_t)nl, sa, sb, c_x0, c_xt, sigma,
-                             eps_nhwc ? L * L : 0));
+    if (s->seeded && t > 0)  // one source of noise per upload: has_noise is off
+      TSD_TRY(launch_ddpm_step_seeded(ctx, s->latents, s->eps, eps_u, s->cfg_scale, session_bases(s, NOISE_STREAM_STEP0 + (uint64_t)i),
+                                      (int64_t)4 * L * L, (int64_t)nl, sa, sb, c_x0, c_xt, sigma, eps_nhwc ? L * L : 0));
+    else
+      TSD_TRY(launch_ddpm_step(ctx, s->latents, s->eps, eps_u, s->cfg_scale, nz, (int64_t)nl, sa, sb, c_x0, c_xt, sigma,
+                               eps_nhwc ? L * L : 0));
     return s->inpaint ? session_inpaint_blend(s, i) : TSD_OK;
   }
   // DDIM / DPM-Solver++(2M): the scalars of tsd_sampler_coeffs (double), rounded to float once here
@@ -479,8 +498,12 @@ extern "C" int tsd_session_step(tsd_session* s, int i) {
   const SamplerCoeffs c = {(float)cd[2], (float)cd[3], (float)cd[4], (float)cd[5], (float)cd[6], (float)cd[7]};
   const bool multistep = s->sampler == TSD_SAMPLER_DPMPP_2M;  // the only one that reads or keeps the history, and it takes no noise
   const float* nz = (!multistep && s->has_noise && c.c_n != 0.f) ? s->noise + (size_t)i * nl : nullptr;
-  TSD_TRY(launch_sampler_step(ctx, s->latents, s->eps, eps_u, s->cfg_scale, have_hist ? s->hist : nullptr, nz, (int64_t)nl, c,
-                              eps_nhwc ? L * L : 0, s->latents, multistep ? s->hist : nullptr));
+  if (s->seeded && !multistep && c.c_n != 0.f)
+    TSD_TRY(launch_sampler_step_seeded(ctx, s->latents, s->eps, eps_u, s->cfg_scale, nullptr, session_bases(s, NOISE_STREAM_STEP0 + (uint64_t)i),
+                                       (int64_t)4 * L * L, (int64_t)nl, c, eps_nhwc ? L * L : 0, s->latents, nullptr));
+  else
+    TSD_TRY(launch_sampler_step(ctx, s->latents, s->eps, eps_u, s->cfg_scale, have_hist ? s->hist : nullptr, nz, (int64_t)nl, c,
+                                eps_nhwc ? L * L : 0, s->latents, multistep ? s->hist : nullptr));
   if (s->inpaint) TSD_TRY(session_inpaint_blend(s, i));  // a failed step leaves no valid history
   if (multistep) s->hist_valid_for = i + 1;  // the blend changed the latents, not the prediction the next step extrapolates from
   return TSD_OK;
@@ -501,9 +524,52 @@ extern "C" int tsd_session_add_noise(tsd_session* s, int i, const float* noise) 
   return TSD_OK;
 }
 
-extern "C" int tsd_session_set_inpaint(tsd_session* s, const float* mask, const float* known, const float* noise) {
+// seeds: one per sample, or NULL = off.  One source of noise per upload(): refused when the upload carried a noise tensor.
+extern "C" int tsd_session_set_seeds(tsd_session* s, const uint64_t* seeds) {
   NOTNULL(s);
+  if (!s->uploaded) TSD_FAIL(TSD_E_STATE, "session: upload() before set_seeds() (the seeds belong to one upload)");
+  if (seeds && s->has_noise) TSD_FAIL(TSD_E_STATE, "session: this upload() carried a noise tensor; one source of noise per upload");
+  s->seeded = seeds != nullptr;
+  if (seeds) memcpy(s->seeds, seeds, (size_t)s->B * sizeof(uint64_t));
+  s->hist_valid_for = -1;  // as after add_noise()
+  s->decoded = false;
+  return TSD_OK;
+}
+extern "C" int tsd_session_seeds_active(tsd_session* s) { return s ? (s->uploaded && s->seeded ? 1 : 0) : TSD_E_ARG; }
+
+// the latents become stream 2 of each sample's seed: what a txt2img caller would have uploaded, drawn on the device.  Asynchronous.
+extern "C" int tsd_session_seed_latents(tsd_session* s) {
+  NOTNULL(s);
+  if (!s->uploaded || !s->seeded) TSD_FAIL(TSD_E_STATE, "session: upload() and set_seeds() before seed_latents()");
+  HIP_TRY(hipSetDevice(s->ctx->device));
+  const int64_t chw = (int64_t)4 * s->L * s->L;
+  s->hist_valid_for = -1;
+  s->decoded = false;
+  return launch_fill_normal(s->ctx, s->latents, s->B * chw, chw, session_bases(s, NOISE_STREAM_LATENTS), 0);
+}
+
+// add_noise at index i with stream 4 of each sample's seed instead of a host tensor: the same scalars and the same kernel
+extern "C" int tsd_session_add_noise_seeded(tsd_session* s, int i) {
+  NOTNULL(s);
+  if (!s->uploaded || !s->seeded) TSD_FAIL(TSD_E_STATE, "session: upload() and set_seeds() before add_noise_seeded()");
+  if (i < 0 || i >= (int)s->timesteps.size()) TSD_FAIL(TSD_E_ARG, "session: step %d out of range", i);
+  tsd_ctx* ctx = s->ctx;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const int64_t chw = (int64_t)4 * s->L * s->L, nl = s->B * chw;
+  TSD_TRY(ctx_reserve_staging(ctx, (size_t)nl * 4));
+  s->hist_valid_for = -1;
+  s->decoded = false;
+  TSD_TRY(launch_fill_normal(ctx, (float*)ctx->staging, nl, chw, session_bases(s, NOISE_STREAM_ADD), 0));
+  const float a = s->alphas_cumprod[s->timesteps[i]];
+  TSD_TRY(launch_add_noise(ctx, s->latents, (const float*)ctx->staging, nl, sqrtf(a), sqrtf(1.f - a)));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));  // the staging buffer is the context's again on return, as after add_noise()
+  return TSD_OK;
+}
+
+// set_inpaint and set_inpaint_seeded: `seeded` fills ip_noise with stream 4 of each sample's seed on the device instead of copying `noise`
+static int session_set_inpaint(tsd_session* s, const float* mask, const float* known, const float* noise, bool seeded) {
   if (!s->uploaded) TSD_FAIL(TSD_E_STATE, "session: upload() before set_inpaint() (inpainting belongs to one upload)");
+  if (seeded && mask && !s->seeded) TSD_FAIL(TSD_E_STATE, "session: set_seeds() before set_inpaint_seeded()");
   tsd_ctx* ctx = s->ctx;
   const size_t hw = (size_t)s->L * s->L, nm = (size_t)s->B * hw, nl = 4 * nm;
   if (mask) {  // every refusal comes before the first copy: a refused call leaves the previous mask, tensors and history as they were
@@ -517,13 +583,22 @@ extern "C" int tsd_session_set_inpaint(tsd_session* s, const float* mask, const 
     HIP_TRY(hipMemcpyAsync(s->ip_mask, mask, nm * 4, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(s->ip_known, known, nl * 4, hipMemcpyHostToDevice, ctx->stream));
     if (noise) HIP_TRY(hipMemcpyAsync(s->ip_noise, noise, nl * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (seeded) TSD_TRY(launch_fill_normal(ctx, s->ip_noise, (int64_t)nl, (int64_t)(4 * hw), session_bases(s, NOISE_STREAM_ADD), 0));
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // the host tensors are the caller's again on return
   }
   s->inpaint = mask != nullptr;
-  s->ip_has_noise = mask && noise;
+  s->ip_has_noise = mask && (noise || seeded);
   s->hist_valid_for = -1;  // the steps that follow run on other latents than the history was predicted for: as after add_noise()
   s->decoded = false;
   return TSD_OK;
+}
+extern "C" int tsd_session_set_inpaint(tsd_session* s, const float* mask, const float* known, const float* noise) {
+  NOTNULL(s);
+  return session_set_inpaint(s, mask, known, noise, false);
+}
+extern "C" int tsd_session_set_inpaint_seeded(tsd_session* s, const float* mask, const float* known) {
+  NOTNULL(s);
+  return session_set_inpaint(s, mask, known, nullptr, true);
 }
 extern "C" int tsd_session_inpaint_active(tsd_session* s) { return s ? (s->uploaded && s->inpaint ? 1 : 0) : TSD_E_ARG; }
 

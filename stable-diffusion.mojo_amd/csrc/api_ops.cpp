@@ -268,6 +268,22 @@ extern "C" int tsd_sampler_step_f32(tsd_ctx* ctx, const float* x, const float* e
   });
 }
 
+// N(0,1) of the counter RNG (kernels_sampler.hip k_fill_normal, counter_rng.h) on a host tensor: element e is value offset + e of the
+// stream (seed, stream) - the values a seeded denoise session draws on the device
+extern "C" int tsd_normal_fill_f32(tsd_ctx* ctx, uint64_t seed, uint64_t stream, uint64_t offset, int64_t n, float* out) {
+  NOTNULL(ctx); NOTNULL(out);
+  if (n <= 0) TSD_FAIL(TSD_E_SHAPE, "normal fill: n=%lld", (long long)n);
+  NormalBases nb = {};
+  nb.base[0] = counter_rng_base(seed, stream);
+  return run_op(ctx, [&]() -> int {
+    Dev d{ctx};
+    float* dy = d.buf<float>(n);
+    if (d.err) return d.err;
+    TSD_TRY(launch_fill_normal(ctx, dy, n, n, nb, offset));
+    return d.out(out, dy, n);
+  });
+}
+
 // inf / NaN or a value outside [lo, hi] in a host tensor (the argument scans of the masked-denoising entries)
 static bool host_all_in_range(const float* p, size_t n, float lo, float hi) {
   bool ok = true;

@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "../../include/tsd.h"
+#include "counter_rng.h"
 
 typedef _Float16 half_t;
 
@@ -301,6 +302,11 @@ int launch_transpose_f32_to_f16(tsd_ctx* ctx, const float* src, int batch, int K
 int launch_ddpm_step(tsd_ctx* ctx, float* latents, const float* eps, const float* eps_uncond, float cfg_scale,
                      const float* noise, int64_t n, float inv_sqrt_a, float sqrt_b, float c_x0, float c_xt,
                      float sigma, int eps_hw = 0);  // eps_hw > 0: eps in the output convolution's layout [B][eps_hw][4]
+// the same update with the noise drawn in the kernel: element j of sample b (chw elements each, n <= 16 chw) takes
+// normal_counter(bases.base[b], j) where launch_ddpm_step reads noise[b * chw + j]; the noise is always added
+int launch_ddpm_step_seeded(tsd_ctx* ctx, float* latents, const float* eps, const float* eps_uncond, float cfg_scale,
+                            const NormalBases& bases, int64_t chw, int64_t n, float inv_sqrt_a, float sqrt_b, float c_x0, float c_xt,
+                            float sigma, int eps_hw = 0);
 int launch_add_noise(tsd_ctx* ctx, float* latents, const float* noise, int64_t n, float sa, float sb);
 
 // ---- linear-multistep sampler update (kernels_sampler.hip) and its host schedule (sampler.cpp) ------------------------------
@@ -313,6 +319,13 @@ struct SamplerCoeffs {
 int launch_sampler_step(tsd_ctx* ctx, const float* x, const float* eps, const float* eps_uncond, float cfg_scale,
                         const float* hist_in, const float* noise, int64_t n, const SamplerCoeffs& c, int eps_hw, float* x_out,
                         float* hist_out);
+// the same update with c_n z drawn in the kernel (launch_ddpm_step_seeded's rule); no noise pointer
+int launch_sampler_step_seeded(tsd_ctx* ctx, const float* x, const float* eps, const float* eps_uncond, float cfg_scale,
+                               const float* hist_in, const NormalBases& bases, int64_t chw, int64_t n, const SamplerCoeffs& c,
+                               int eps_hw, float* x_out, float* hist_out);
+// dst[b * per_sample + j] = normal_counter(bases.base[b], first + j) for the n = (samples) * per_sample elements of dst, n <= 16 per_sample
+// (kernels_sampler.hip k_fill_normal): N(0,1) of the counter RNG, the values the seeded updates draw inline
+int launch_fill_normal(tsd_ctx* ctx, float* dst, int64_t n, int64_t per_sample, const NormalBases& bases, uint64_t first);
 // masked denoising (kernels_sampler.hip): x_out = m x + (1 - m)(a_prev known + s_prev noise); x / known / noise / x_out CHW [B][4][hw],
 // mask [B][hw]; noise may be nullptr (that term is skipped); x_out may be x
 int launch_inpaint_blend(tsd_ctx* ctx, const float* x, const float* mask, const float* known, const float* noise, int B, int64_t hw,

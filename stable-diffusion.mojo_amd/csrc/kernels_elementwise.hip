@@ -573,13 +573,7 @@ int launch_small_linear(tsd_ctx* ctx, const float* x, int B, int K, int ldx, con
   return TSD_OK;
 }
 
-// ---- counter RNG (bit-identical to tsd/rng.py and oracle/rng.py) ---------------------------------
-__device__ __forceinline__ uint64_t mix64(uint64_t z) {
-  z ^= z >> 30; z *= 0xBF58476D1CE4E5B9ull;
-  z ^= z >> 27; z *= 0x94D049BB133111EBull;
-  z ^= z >> 31;
-  return z;
-}
+// ---- counter RNG (bit-identical to tsd/rng.py and oracle/rng.py); mix64 lives in counter_rng.h ----
 __global__ void k_fill_uniform(float* __restrict__ dst, int64_t n, uint64_t base, float bound) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
     const uint64_t h = mix64((uint64_t)i + base);
@@ -689,28 +683,49 @@ int launch_pack_bias(tsd_ctx* ctx, const float* src, int N, float* dst, int Npad
 
 // ---- DDPM update + CFG combine (sampler.mojo:75-109, pipeline.mojo:117-119; App.D K9) ------------
 // eps_hw > 0: eps / eps_u are the UNet output convolution's own layout [B][eps_hw][4] (x and noise stay CHW [B][4][eps_hw])
+// One element of the update.  SEEDED: the noise is drawn where the other flavour reads noise[i] - normal_counter(bases.base[b], j) for element j of
+// sample b (chw elements per sample, counter_rng.h) - and is always added; without it the instantiation is the kernel as it always was.
+template <bool SEEDED>
+__device__ __forceinline__ int ddpm_step_element(int64_t i, float* __restrict__ x, const float* __restrict__ eps,
+                                                 const float* __restrict__ eps_u, float cfg_scale, const float* __restrict__ noise,
+                                                 const NormalBases& bases, int64_t chw, float sa, float sb, float c_x0, float c_xt,
+                                                 float sigma, int eps_hw) {
+  int64_t ie = i;
+  if (eps_hw > 0) {
+    const int64_t bc = i / eps_hw, pix = i - bc * eps_hw, b = bc >> 2;
+    ie = (b * eps_hw + pix) * 4 + (bc & 3);
+  }
+  float e = eps[ie];
+  if (eps_u) {
+    const float u = eps_u[ie];
+    e = (e - u) * cfg_scale + u;
+  }
+  const float xv = x[i];
+  const float x0 = (xv - e * sb) / sa;
+  float o = x0 * c_x0 + xv * c_xt;
+  if constexpr (SEEDED) {
+    const int64_t b = i / chw;
+    o += normal_counter(bases.base[b], (uint64_t)(i - b * chw)) * sigma;
+  } else {
+    if (noise) o += noise[i] * sigma;
+  }
+  x[i] = o;
+  return nonfinite_f(o);  // a non-finite UNet output (fp16 overflow upstream) lands here every step
+}
 __global__ void k_ddpm_step(float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ eps_u,
                             float cfg_scale, const float* __restrict__ noise, int64_t n, float sa, float sb,
                             float c_x0, float c_xt, float sigma, int eps_hw, int* __restrict__ nonfinite) {
   int nbad = 0;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    int64_t ie = i;
-    if (eps_hw > 0) {
-      const int64_t bc = i / eps_hw, pix = i - bc * eps_hw, b = bc >> 2;
-      ie = (b * eps_hw + pix) * 4 + (bc & 3);
-    }
-    float e = eps[ie];
-    if (eps_u) {
-      const float u = eps_u[ie];
-      e = (e - u) * cfg_scale + u;
-    }
-    const float xv = x[i];
-    const float x0 = (xv - e * sb) / sa;
-    float o = x0 * c_x0 + xv * c_xt;
-    if (noise) o += noise[i] * sigma;
-    nbad += nonfinite_f(o);  // a non-finite UNet output (fp16 overflow upstream) lands here every step
-    x[i] = o;
-  }
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    nbad += ddpm_step_element<false>(i, x, eps, eps_u, cfg_scale, noise, NormalBases(), 0, sa, sb, c_x0, c_xt, sigma, eps_hw);
+  nonfinite_report(nonfinite, nbad);
+}
+__global__ void k_ddpm_step_seeded(float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ eps_u,
+                                   float cfg_scale, NormalBases bases, int64_t chw, int64_t n, float sa, float sb,
+                                   float c_x0, float c_xt, float sigma, int eps_hw, int* __restrict__ nonfinite) {
+  int nbad = 0;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    nbad += ddpm_step_element<true>(i, x, eps, eps_u, cfg_scale, nullptr, bases, chw, sa, sb, c_x0, c_xt, sigma, eps_hw);
   nonfinite_report(nonfinite, nbad);
 }
 int launch_ddpm_step(tsd_ctx* ctx, float* latents, const float* eps, const float* eps_uncond, float cfg_scale,
@@ -719,6 +734,17 @@ int launch_ddpm_step(tsd_ctx* ctx, float* latents, const float* eps, const float
   ProfScope prof(ctx, KC_ELEMENTWISE);
   hipLaunchKernelGGL(k_ddpm_step, GRID1D(n, 256), dim3(256), 0, ctx->stream, latents, eps, eps_uncond, cfg_scale,
                      noise, n, sa, sb, c_x0, c_xt, sigma, eps_hw, ctx->status);
+  HIP_TRY(hipGetLastError());
+  return TSD_OK;
+}
+int launch_ddpm_step_seeded(tsd_ctx* ctx, float* latents, const float* eps, const float* eps_uncond, float cfg_scale,
+                            const NormalBases& bases, int64_t chw, int64_t n, float sa, float sb, float c_x0, float c_xt, float sigma,
+                            int eps_hw) {
+  if (chw <= 0 || n > 16 * chw) TSD_FAIL(TSD_E_SHAPE, "seeded ddpm step: n=%lld is more than 16 samples of %lld", (long long)n, (long long)chw);
+  if (!ctx->launch()) return TSD_OK;
+  ProfScope prof(ctx, KC_ELEMENTWISE);
+  hipLaunchKernelGGL(k_ddpm_step_seeded, GRID1D(n, 256), dim3(256), 0, ctx->stream, latents, eps, eps_uncond, cfg_scale, bases, chw,
+                     n, sa, sb, c_x0, c_xt, sigma, eps_hw, ctx->status);
   HIP_TRY(hipGetLastError());
   return TSD_OK;
 }

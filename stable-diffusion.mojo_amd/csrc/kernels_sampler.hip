@@ -18,44 +18,66 @@
 // which is what tests/test_gpu_sampler.py bounds the kernel with.
 // eps_hw > 0: eps / eps_u are the UNet output convolution's own layout [B][eps_hw][4] (x, hist and noise stay CHW [B][4][eps_hw]).
 // x_out may be x and hist_out may be hist_in: element i is read and written by the same thread only.
-__global__ void k_sampler_step(const float* x, const float* __restrict__ eps, const float* __restrict__ eps_u, float cfg_scale,
-                               const float* hist_in, const float* __restrict__ noise, int64_t n, SamplerCoeffs c, int eps_hw,
-                               float* x_out, float* hist_out, int* __restrict__ nonfinite) {
+// One element of the update.  SEEDED: z is drawn where the other flavour reads noise[i] - normal_counter(bases.base[b], j) for element j of sample b (chw
+// elements per sample, counter_rng.h) - and its term is always added; without it the instantiation is the kernel as it always was.
+template <bool SEEDED>
+__device__ __forceinline__ int sampler_step_element(int64_t i, const float* x, const float* __restrict__ eps,
+                                                    const float* __restrict__ eps_u, float cfg_scale, const float* hist_in,
+                                                    const float* __restrict__ noise, const NormalBases& bases, int64_t chw,
+                                                    const SamplerCoeffs& c, int eps_hw, float* x_out, float* hist_out) {
 #pragma clang fp contract(off)
-  int nbad = 0;
-  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    int64_t ie = i;
-    if (eps_hw > 0) {
-      const int64_t bc = i / eps_hw, pix = i - bc * eps_hw, b = bc >> 2;
-      ie = (b * eps_hw + pix) * 4 + (bc & 3);
-    }
-    float e = eps[ie];
-    if (eps_u) {
-      const float u = eps_u[ie];
-      const float d = e - u;
-      const float ds = d * cfg_scale;
-      e = ds + u;
-    }
-    const float xv = x[i];
-    float o = c.c_x * xv;
-    const float te = c.c_e * e;
-    o = o + te;
-    if (hist_in) {
-      const float th = c.c_h * hist_in[i];
-      o = o + th;
-    }
+  int64_t ie = i;
+  if (eps_hw > 0) {
+    const int64_t bc = i / eps_hw, pix = i - bc * eps_hw, b = bc >> 2;
+    ie = (b * eps_hw + pix) * 4 + (bc & 3);
+  }
+  float e = eps[ie];
+  if (eps_u) {
+    const float u = eps_u[ie];
+    const float d = e - u;
+    const float ds = d * cfg_scale;
+    e = ds + u;
+  }
+  const float xv = x[i];
+  float o = c.c_x * xv;
+  const float te = c.c_e * e;
+  o = o + te;
+  if (hist_in) {
+    const float th = c.c_h * hist_in[i];
+    o = o + th;
+  }
+  if constexpr (SEEDED) {
+    const int64_t b = i / chw;
+    const float tn = c.c_n * normal_counter(bases.base[b], (uint64_t)(i - b * chw));
+    o = o + tn;
+  } else {
     if (noise) {
       const float tn = c.c_n * noise[i];
       o = o + tn;
     }
-    if (hist_out) {
-      const float se = c.sigma_t * e;
-      const float xs = xv - se;
-      hist_out[i] = xs / c.alpha_t;
-    }
-    nbad += nonfinite_f(o);  // a non-finite UNet output (fp16 overflow upstream) lands here every step
-    x_out[i] = o;
   }
+  if (hist_out) {
+    const float se = c.sigma_t * e;
+    const float xs = xv - se;
+    hist_out[i] = xs / c.alpha_t;
+  }
+  x_out[i] = o;
+  return nonfinite_f(o);  // a non-finite UNet output (fp16 overflow upstream) lands here every step
+}
+__global__ void k_sampler_step(const float* x, const float* __restrict__ eps, const float* __restrict__ eps_u, float cfg_scale,
+                               const float* hist_in, const float* __restrict__ noise, int64_t n, SamplerCoeffs c, int eps_hw,
+                               float* x_out, float* hist_out, int* __restrict__ nonfinite) {
+  int nbad = 0;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    nbad += sampler_step_element<false>(i, x, eps, eps_u, cfg_scale, hist_in, noise, NormalBases(), 0, c, eps_hw, x_out, hist_out);
+  nonfinite_report(nonfinite, nbad);
+}
+__global__ void k_sampler_step_seeded(const float* x, const float* __restrict__ eps, const float* __restrict__ eps_u, float cfg_scale,
+                                      const float* hist_in, NormalBases bases, int64_t chw, int64_t n, SamplerCoeffs c, int eps_hw,
+                                      float* x_out, float* hist_out, int* __restrict__ nonfinite) {
+  int nbad = 0;
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
+    nbad += sampler_step_element<true>(i, x, eps, eps_u, cfg_scale, hist_in, nullptr, bases, chw, c, eps_hw, x_out, hist_out);
   nonfinite_report(nonfinite, nbad);
 }
 int launch_sampler_step(tsd_ctx* ctx, const float* x, const float* eps, const float* eps_uncond, float cfg_scale,
@@ -65,6 +87,35 @@ int launch_sampler_step(tsd_ctx* ctx, const float* x, const float* eps, const fl
   ProfScope prof(ctx, KC_ELEMENTWISE);
   hipLaunchKernelGGL(k_sampler_step, GRID1D(n, 256), dim3(256), 0, ctx->stream, x, eps, eps_uncond, cfg_scale, hist_in, noise, n,
                      c, eps_hw, x_out, hist_out, ctx->status);
+  HIP_TRY(hipGetLastError());
+  return TSD_OK;
+}
+int launch_sampler_step_seeded(tsd_ctx* ctx, const float* x, const float* eps, const float* eps_uncond, float cfg_scale,
+                               const float* hist_in, const NormalBases& bases, int64_t chw, int64_t n, const SamplerCoeffs& c,
+                               int eps_hw, float* x_out, float* hist_out) {
+  if (chw <= 0 || n > 16 * chw) TSD_FAIL(TSD_E_SHAPE, "seeded sampler step: n=%lld is more than 16 samples of %lld", (long long)n, (long long)chw);
+  if (!ctx->launch()) return TSD_OK;
+  ProfScope prof(ctx, KC_ELEMENTWISE);
+  hipLaunchKernelGGL(k_sampler_step_seeded, GRID1D(n, 256), dim3(256), 0, ctx->stream, x, eps, eps_uncond, cfg_scale, hist_in, bases,
+                     chw, n, c, eps_hw, x_out, hist_out, ctx->status);
+  HIP_TRY(hipGetLastError());
+  return TSD_OK;
+}
+
+// ---- N(0,1) fill from the counter RNG (counter_rng.h): the latents, the add_noise / inpainting noise and the op-level entry -------------
+// Grid-stride over n elements in CHW per sample: element j of sample b is value first + j of the stream bases.base[b].  The seeded updates
+// above call the same normal_counter with first = 0, so a buffer filled here and read by the unseeded update gives their bits.
+__global__ void k_fill_normal(float* __restrict__ dst, int64_t n, int64_t per_sample, NormalBases bases, uint64_t first) {
+  for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = i / per_sample;
+    dst[i] = normal_counter(bases.base[b], first + (uint64_t)(i - b * per_sample));
+  }
+}
+int launch_fill_normal(tsd_ctx* ctx, float* dst, int64_t n, int64_t per_sample, const NormalBases& bases, uint64_t first) {
+  if (per_sample <= 0 || n > 16 * per_sample) TSD_FAIL(TSD_E_SHAPE, "normal fill: n=%lld is more than 16 samples of %lld", (long long)n, (long long)per_sample);
+  if (!ctx->launch()) return TSD_OK;
+  ProfScope prof(ctx, KC_ELEMENTWISE);
+  hipLaunchKernelGGL(k_fill_normal, GRID1D(n, 256), dim3(256), 0, ctx->stream, dst, n, per_sample, bases, first);
   HIP_TRY(hipGetLastError());
   return TSD_OK;
 }

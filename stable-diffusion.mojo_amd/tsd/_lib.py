@@ -124,6 +124,10 @@ def _declare(l):
         "tsd_latent_mask_f32": ([vp, fp, i, i, i, fp], i),
         "tsd_inpaint_blend_f32": ([vp, fp, fp, fp, fp, i, i64, f, f, fp], i),
         "tsd_session_set_inpaint": ([vp, fp, fp, fp], i), "tsd_session_inpaint_active": ([vp], i),
+        "tsd_normal_fill_f32": ([vp, u64, u64, u64, i64, fp], i),
+        "tsd_session_set_seeds": ([vp, C.POINTER(u64)], i), "tsd_session_seeds_active": ([vp], i),
+        "tsd_session_seed_latents": ([vp], i), "tsd_session_add_noise_seeded": ([vp, i], i),
+        "tsd_session_set_inpaint_seeded": ([vp, fp, fp], i),
         "tsd_session_timestep": ([vp, i], i),
         "tsd_session_upload": ([vp, fp, fp, fp, fp, f], i), "tsd_session_step": ([vp, i], i),
         "tsd_session_add_noise": ([vp, i, fp], i), "tsd_session_decode": ([vp], i),

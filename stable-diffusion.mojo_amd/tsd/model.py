@@ -132,10 +132,40 @@ class Session:
     def add_noise(self, i, noise):
         check(lib().tsd_session_add_noise(self.h, int(i), ptr(f32(noise))))
 
-    def set_inpaint(self, mask, known=None, noise=None):
+    def set_seeds(self, seeds):
+        """Seeded device-side noise for the steps of the current upload(): `seeds` is a sequence of B ints (uint64), one per sample; None
+        turns it off.  A DDPM / DDIM(eta > 0) step then draws its noise in the update kernel from stream 16 + i of the sample's seed -
+        the same values wherever the sample sits in the batch.  Needs an upload() without a noise tensor; upload(), set_schedule() and
+        set_sampler() turn it off."""
+        if seeds is None:
+            check(lib().tsd_session_set_seeds(self.h, None))
+            return
+        seeds = [int(v) for v in seeds]
+        if len(seeds) != self.B:
+            raise ValueError(f"seeds must have one entry per sample ({self.B}), got {len(seeds)}")
+        if any(v < 0 or v >= 1 << 64 for v in seeds):
+            raise ValueError("every seed must fit an unsigned 64-bit integer")
+        check(lib().tsd_session_set_seeds(self.h, (C.c_uint64 * self.B)(*seeds)))
+
+    @property
+    def seeds_active(self):
+        return lib().tsd_session_seeds_active(self.h) == 1
+
+    def seed_latents(self):
+        """Replace the latents by stream 2 of each sample's seed (after set_seeds)."""
+        check(lib().tsd_session_seed_latents(self.h))
+
+    def add_noise_seeded(self, i):
+        """add_noise at timestep index i with stream 4 of each sample's seed, drawn on the device (after set_seeds)."""
+        check(lib().tsd_session_add_noise_seeded(self.h, int(i)))
+
+    def set_inpaint(self, mask, known=None, noise=None, seeded=False):
         """Masked denoising for the steps of the current upload(): mask (B,L,L) or (B,1,L,L) in [0,1], 1 = regenerate and 0 = keep
         `known` (B,4,L,L), the original latents, re-noised after every step with `noise` (B,4,L,L; None: a noiseless known region).
+        seeded=True (after set_seeds, no `noise`): the noise is stream 4 of each sample's seed, drawn on the device.
         mask=None turns it off.  upload(), set_schedule() and set_sampler() turn it off as well."""
+        if seeded and noise is not None:
+            raise ValueError("set_inpaint(seeded=True) draws its noise on the device: pass no noise tensor")
         if mask is None:
             check(lib().tsd_session_set_inpaint(self.h, None, None, None))
             return
@@ -153,6 +183,9 @@ class Session:
         nz = f32(noise) if noise is not None else None
         if nz is not None and nz.shape != (B, 4, L, L):
             raise ValueError(f"noise must have shape {(B, 4, L, L)}, got {nz.shape}")
+        if seeded:
+            check(lib().tsd_session_set_inpaint_seeded(self.h, ptr(m), ptr(kn)))
+            return
         check(lib().tsd_session_set_inpaint(self.h, ptr(m), ptr(kn), ptr(nz)))
 
     @property

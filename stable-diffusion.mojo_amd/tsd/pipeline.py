@@ -25,7 +25,7 @@ def encode_prompts(prompts, tokenizer, clip):
 def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg=True, cfg_scale=7.5,
              inference_steps=50, seed_val=0, input_image=None, encoder=None, latents=None, noise=None,
              num_training_steps=1000, L=64, return_latents=False, sampler="ddpm", eta=0.0, spacing="leading", mask=None,
-             mask_mode="any"):
+             mask_mode="any", seeds=None):
     """context (B,T,768); returns images (B,3,8L,8L) in [0,255] like pipeline.mojo:127.
 
     sampler "ddpm" (the reference's, about 50 steps) | "ddim" (eta = 0: deterministic) | "dpmpp_2m" (second-order multistep, 20-25
@@ -36,7 +36,14 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
     img2img's with the known region of the latents put back after every step (`Session.set_inpaint`), re-noised with the noise
     `add_noise` used; mask_mode "any" (a latent cell that touches a masked pixel is regenerated) | "area" (`latent_mask`).
 
-    latents / noise default to N(0,1) from the counter RNG keyed by seed_val (App.A D19)."""
+    latents / noise default to N(0,1) from the counter RNG keyed by seed_val (App.A D19).
+
+    seeds: a sequence of B ints, one per sample - the initial latents, the img2img / inpainting noise and every step's noise are drawn
+    on the device from that sample's seed (`Session.set_seeds`), so a seed gives the same image wherever its sample sits in the batch
+    and no noise tensor crosses the bus; only the encoder's noise input stays a host tensor keyed by seed_val.  Not with `noise` or
+    `latents`."""
+    if seeds is not None and (noise is not None or latents is not None):
+        raise ValueError("generate(seeds=...) draws latents and noise on the device: pass neither noise nor latents")
     context = np.asarray(context, dtype=np.float32)
     if context.ndim == 2:
         context = context[None]
@@ -64,11 +71,19 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
         if mask is not None:
             mask_lat = latent_mask(mask, mask_mode, diffusion.model.ctx)
     elif latents is None:
-        latents = rng.normal(seed_val, 2, nl).reshape(B, 4, L, L)
-    if noise is None:
+        latents = np.zeros((B, 4, L, L), dtype=np.float32) if seeds is not None else rng.normal(seed_val, 2, nl).reshape(B, 4, L, L)
+    if noise is None and seeds is None:
         noise = rng.normal(seed_val, 3, n * nl).reshape(n, B, 4, L, L)
     sess.upload(latents, context, uncond_context if cfg else None, noise, cfg_scale)
-    if input_image is not None:
+    if seeds is not None:
+        sess.set_seeds(seeds)
+        if input_image is None:
+            sess.seed_latents()
+        else:
+            sess.add_noise_seeded(0)
+            if mask is not None:
+                sess.set_inpaint(mask_lat, latents, seeded=True)
+    elif input_image is not None:
         z4 = rng.normal(seed_val, 4, nl).reshape(B, 4, L, L)
         sess.add_noise(0, z4)  # sampler.mojo:111-124 at timesteps[0]
         if mask is not None:

@@ -4,6 +4,10 @@ Host (numpy) twin of the device kernel `k_fill_uniform` (csrc/kernels_elementwis
 bit-identical float32 values, so synthetic weights never have to be shipped: the reference
 random-initialises every struct in `__init__` (helpers/utils.mojo:1716-1727, :1938-1945) from Mojo's
 irreproducible stdlib PRNG, hence weights/noise are INPUTS here (SURVEY.md App.A rule 3).
+
+`normal_counter` is the float64 host twin of the device's `normal_counter` (csrc/counter_rng.h: `k_fill_normal` and the seeded update
+kernels of the denoise session).  Its contract is NOT bit equality - the device computes log, sqrt and cospi in fp32 - but a relative
+error bound of 14 * 2^-24.  `normal` is the older host-only Box-Muller stream and stays as it is.
 """
 import numpy as np
 
@@ -41,6 +45,21 @@ def normal(seed, tensor_id, n):
     u1 = ((h[:n] >> np.uint64(11)).astype(np.float64) + 0.5) * (2.0 ** -53)
     u2 = ((h[n:] >> np.uint64(11)).astype(np.float64) + 0.5) * (2.0 ** -53)
     return (np.sqrt(-2.0 * np.log(u1)) * np.cos(2.0 * np.pi * u2)).astype(np.float32)
+
+
+def normal_counter(seed, stream, n, offset=0):
+    """N(0,1) float32, values offset .. offset + n - 1 of the stream (seed, stream): the float64 host twin of the device's
+    `normal_counter` (csrc/counter_rng.h; `tsd.normal_fill`, the seeded denoise session).  A pure function of (seed, stream, counter j):
+    k1, k2 = mix64(base + 2j) >> 40, mix64(base + 2j + 1) >> 40; z = sqrt(-2 ln((k1 + 1) 2^-24)) cos(pi k2 2^-23), rounded to float32
+    once.  The device computes the same integers and the transcendentals in fp32: within 14 * 2^-24 relative, not bitwise."""
+    with np.errstate(over="ignore"):
+        base = np.uint64(seed) * _M1 + np.uint64(stream) * _M2
+        c = base + np.uint64(2) * (np.arange(n, dtype=np.uint64) + np.uint64(offset))
+        k1 = _mix(c) >> np.uint64(40)
+        k2 = _mix(c + np.uint64(1)) >> np.uint64(40)
+    u1 = (k1.astype(np.float64) + 1.0) * 2.0 ** -24
+    v = k2.astype(np.float64) * 2.0 ** -23
+    return (np.sqrt(-2.0 * np.log(u1)) * np.cos(np.pi * v)).astype(np.float32)
 
 
 _next_id = [1 << 20]

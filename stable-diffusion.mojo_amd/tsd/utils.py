@@ -194,6 +194,15 @@ def latent_mask(mask, mode="any", ctx=None):
     return y
 
 
+def normal_fill(seed, stream, n, offset=0, ctx=None):
+    """N(0,1) float32 values offset .. offset + n - 1 of the device's counter stream (seed, stream) (`tsd_normal_fill_f32`): what a seeded
+    session draws on the device (streams 2 latents, 4 add_noise / inpainting, 16 + i step i).  `rng.normal_counter` is its float64 twin."""
+    y = np.empty(int(n), dtype=np.float32)
+    mask = (1 << 64) - 1
+    check(lib().tsd_normal_fill_f32(_ctx(ctx), int(seed) & mask, int(stream) & mask, int(offset) & mask, int(n), ptr(y)))
+    return y
+
+
 def inpaint_blend(x, mask, known, noise, a_prev, s_prev, ctx=None):
     """x' = m x + (1 - m)(a_prev known + s_prev noise) (`tsd_inpaint_blend_f32`): x / known / noise (B,4,...) and mask (B,...) with one
     value for the 4 channels; noise may be None.  The launch a session with `set_inpaint` adds to a step."""
