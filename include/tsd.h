@@ -443,6 +443,43 @@ int tsd_debug_gemm_recorded(tsd_ctx* ctx, int i, int64_t* desc, int n);
  * returned even when the launch is refused (its status is the return value). */
 int tsd_debug_gemm_run(tsd_ctx* ctx, const int64_t* desc, int n, int cfg, const void* const* host_in, void* const* host_out,
                        int64_t* ext, int64_t* info);
+/* ---- GroupNorm / LayerNorm launch descriptors (test infrastructure: tests/norm_ref.py holds every statistics path of
+ * csrc/kernels_norm.hip to an fp64 reference) ----
+ * One int64 per argument of launch_groupnorm / launch_gn_stats / launch_gn_finalize / launch_layernorm.  EPS and GAMMA hold the bits
+ * of a float.  C0 < C: channels [C0, C) come from the second source (X1, pitch LD1).  HAS_W / HAS_B / TORCH_RSTD: the NormAffine
+ * extension (none set: reference semantics, no NormAffine passed).  STATS (groupnorm mode only): where the statistics come from -
+ * 0 the launch's own pass over x, 1 one table of NSLAB producer partials per sample (PART0, [B][NSLAB][GROUPS][2]), 2 a GnComposite
+ * of NSLAB slabs: G0 fine groups in PART0 ([B][NSLAB][G0][2]), G1 in PART1 (G1 == 0: no second table), COMB fine groups per group.
+ * gn_finalize mode reads PART0 [B][NSLAB][GROUPS][2] and no x.  layernorm mode: ROWS rows of C channels, x at pitch LD0, y at LDY. */
+enum tsd_norm_desc_field {
+  TSD_ND_VERSION = 0, TSD_ND_MODE, TSD_ND_B, TSD_ND_HW, TSD_ND_C, TSD_ND_C0, TSD_ND_LD0, TSD_ND_LD1, TSD_ND_LDY, TSD_ND_GROUPS,
+  TSD_ND_EPS, TSD_ND_GAMMA, TSD_ND_SILU, TSD_ND_HAS_W, TSD_ND_HAS_B, TSD_ND_TORCH_RSTD,
+  TSD_ND_STATS, TSD_ND_NSLAB, TSD_ND_G0, TSD_ND_G1, TSD_ND_COMB, TSD_ND_ROWS,
+  TSD_ND_COUNT
+};
+#define TSD_ND_VERSION_1 1
+enum tsd_norm_mode { TSD_NM_GROUPNORM = 0, TSD_NM_GN_STATS, TSD_NM_GN_FINALIZE, TSD_NM_LAYERNORM };
+/* Operand slots: inputs X0 X1 (fp16) PART0 PART1 W BIAS (fp32); outputs Y (fp16), STATS (fp32 [B][GROUPS][2] (mean, scale)). */
+enum tsd_norm_operand { TSD_NO_X0 = 0, TSD_NO_X1, TSD_NO_PART0, TSD_NO_PART1, TSD_NO_W, TSD_NO_BIAS, TSD_NO_Y, TSD_NO_STATS, TSD_NO_COUNT };
+/* info: guard / pitch-gap elements the launches changed, then the plan the GroupNorm launch took (all 0 when it was refused, and
+ * for layernorm): the slab count the statistics were finished from, whether the launch ran its own statistics pass, k_gn_prereduce,
+ * the separate k_gn_finalize launch, whether the composite was accepted, pixels per statistics slab and per apply block, pixel
+ * lanes per block. */
+enum tsd_norm_info { TSD_NI_CHANGED = 0, TSD_NI_NSLAB, TSD_NI_OWN_PASS, TSD_NI_PREREDUCE, TSD_NI_FINALIZE, TSD_NI_COMPOSITE,
+                     TSD_NI_SLAB_PIXELS, TSD_NI_APPLY_PIXELS, TSD_NI_PL, TSD_NI_COUNT };
+/* Run the launch described by desc (n >= TSD_ND_COUNT fields) on caller operands in their device layout (host_in[TSD_NO_X0 ..
+ * TSD_NO_BIAS], NULL for unused slots) and return its outputs (host_out[slot - TSD_NO_Y]).  host_in == NULL only sizes (ctx may be
+ * NULL, no device is touched): ext[TSD_NO_COUNT] receives every slot's extent (0 = unused) and, when info is given, info[] the plan
+ * under the default options.  A descriptor that cannot be sized is refused before any launch.  Every operand sits between 4 KiB
+ * guard bands of a NaN pattern and the outputs are pre-filled with it; they are returned even when the launch is refused (its
+ * status is the return value). */
+int tsd_debug_norm_run(tsd_ctx* ctx, const int64_t* desc, int n, const void* const* host_in, void* const* host_out, int64_t* ext,
+                       int64_t* info);
+/* GroupNorm launches enqueued on this context since the last reset, per statistics path: counts[0] all, [1] own statistics pass,
+ * [2] one producer table finished inside the apply blocks, [3] one producer table finished by the k_gn_finalize launch,
+ * [4] k_gn_prereduce, [5] composite accepted, [6] k_gn_finalize launches (any source), [7] composites offered.  n >= 8; reset != 0
+ * clears them. */
+int tsd_debug_gn_path_counts(tsd_ctx* ctx, int64_t* counts, int n, int reset);
 /* Attention blocks that run op by op (C = 640 / 1280) fold GEGLU's second linear into the output 1x1 convolution at tsd_model_prepare:
  * wf [C][5C] fp16 = [W_out . W_2 | W_out], bf [C] = W_out . b_2 + b_out.  Copies block `block`'s (index into the UNet's layers; NULL
  * pointers only ask) and returns C, 0 when that block does not fold.  tsd_model_prepare returns TSD_E_NONFINITE when a folded weight

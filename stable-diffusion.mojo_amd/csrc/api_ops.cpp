@@ -902,3 +902,180 @@ extern "C" int tsd_debug_gemm_run(tsd_ctx* ctx, const int64_t* desc, int n, int 
   info[2] = changed;
   return r;
 }
+
+// ---- GroupNorm / LayerNorm launches on caller operands (tests/norm_ref.py holds every statistics path to an fp64 reference) ------
+namespace {
+float nd_float(int64_t bits) {
+  const uint32_t b = (uint32_t)bits;
+  float f;
+  memcpy(&f, &b, 4);
+  return f;
+}
+// Element extent of every operand the described launch reads or writes.  Refuses what it cannot size; the shapes the launches
+// themselves refuse (C % 8, C % groups, widths, pitches that are no multiple of 8) are sized and left to them.
+int nd_extents(const int64_t* d, int64_t* e) {
+  for (int i = 0; i < TSD_NO_COUNT; i++) e[i] = 0;
+#define ND_REQ(cond) \
+  if (!(cond)) TSD_FAIL(TSD_E_ARG, "norm_run: descriptor cannot be sized (%s)", #cond)
+  ND_REQ(d[TSD_ND_VERSION] == TSD_ND_VERSION_1);
+  const int64_t mode = d[TSD_ND_MODE], C = d[TSD_ND_C], lim = 1LL << 28;
+  ND_REQ(mode >= TSD_NM_GROUPNORM && mode <= TSD_NM_LAYERNORM);
+  ND_REQ(C > 0 && C <= 65536);
+  for (int f : {TSD_ND_LD0, TSD_ND_LD1, TSD_ND_LDY}) ND_REQ(d[f] >= 0 && d[f] <= 65536);
+  for (int f : {TSD_ND_SILU, TSD_ND_HAS_W, TSD_ND_HAS_B, TSD_ND_TORCH_RSTD}) ND_REQ(d[f] == 0 || d[f] == 1);
+  if (d[TSD_ND_HAS_W]) e[TSD_NO_W] = C;
+  if (d[TSD_ND_HAS_B]) e[TSD_NO_BIAS] = C;
+  if (mode == TSD_NM_LAYERNORM) {
+    const int64_t rows = d[TSD_ND_ROWS];
+    ND_REQ(rows > 0 && rows < lim && d[TSD_ND_LD0] >= C && d[TSD_ND_LDY] >= C);
+    e[TSD_NO_X0] = (rows - 1) * d[TSD_ND_LD0] + C;
+    e[TSD_NO_Y] = (rows - 1) * d[TSD_ND_LDY] + C;
+  } else {
+    const int64_t B = d[TSD_ND_B], HW = d[TSD_ND_HW], G = d[TSD_ND_GROUPS], C0 = d[TSD_ND_C0], ns = d[TSD_ND_NSLAB];
+    ND_REQ(B > 0 && B <= 4096 && HW > 0 && HW < lim && B * HW < lim && G > 0 && G <= C);
+    if (mode == TSD_NM_GN_FINALIZE) {
+      ND_REQ(ns > 0 && ns <= 65536);
+      e[TSD_NO_PART0] = B * ns * G * 2;
+      e[TSD_NO_STATS] = B * G * 2;
+    } else {
+      const int64_t px = B * HW;
+      ND_REQ(C0 > 0 && C0 <= C && d[TSD_ND_LD0] >= C0);
+      ND_REQ(mode == TSD_NM_GROUPNORM || C0 == C);
+      e[TSD_NO_X0] = (px - 1) * d[TSD_ND_LD0] + C0;
+      if (C0 < C) {
+        ND_REQ(d[TSD_ND_LD1] >= C - C0);
+        e[TSD_NO_X1] = (px - 1) * d[TSD_ND_LD1] + (C - C0);
+      }
+      if (mode == TSD_NM_GN_STATS) e[TSD_NO_STATS] = B * G * 2;
+      else {
+        ND_REQ(d[TSD_ND_LDY] >= C);
+        e[TSD_NO_Y] = (px - 1) * d[TSD_ND_LDY] + C;
+        const int64_t st = d[TSD_ND_STATS];
+        ND_REQ(st >= 0 && st <= 2);
+        if (st == 1) {
+          ND_REQ(ns > 0 && ns <= 65536);
+          e[TSD_NO_PART0] = B * ns * G * 2;
+        } else if (st == 2) {
+          const int64_t G0 = d[TSD_ND_G0], G1 = d[TSD_ND_G1];
+          ND_REQ(ns > 0 && ns <= 65536 && G0 > 0 && G0 <= 65536 && G1 >= 0 && G1 <= 65536 && d[TSD_ND_COMB] >= 0 && d[TSD_ND_COMB] <= 65536);
+          e[TSD_NO_PART0] = B * ns * G0 * 2;
+          e[TSD_NO_PART1] = B * ns * G1 * 2;
+        }
+      }
+    }
+  }
+  for (int s = 0; s < TSD_NO_COUNT; s++) ND_REQ(e[s] >= 0 && e[s] <= lim);
+#undef ND_REQ
+  return TSD_OK;
+}
+int nd_elem_bytes(int slot) { return slot == TSD_NO_X0 || slot == TSD_NO_X1 || slot == TSD_NO_Y ? 2 : 4; }
+void nd_plan_info(const GnPlan& p, int64_t* info) {
+  info[TSD_NI_NSLAB] = p.nslab; info[TSD_NI_OWN_PASS] = p.nslab > 0 && !p.have_stats ? 1 : 0; info[TSD_NI_PREREDUCE] = p.prereduce ? 1 : 0;
+  info[TSD_NI_FINALIZE] = p.stats_ready; info[TSD_NI_COMPOSITE] = p.composite ? 1 : 0; info[TSD_NI_SLAB_PIXELS] = p.slab_pixels;
+  info[TSD_NI_APPLY_PIXELS] = p.apply_pixels; info[TSD_NI_PL] = p.PL;
+}
+struct NdBufs {
+  char* p[TSD_NO_COUNT] = {};
+  ~NdBufs() { for (char* q : p) if (q) (void)hipFree(q); }
+};
+}  // namespace
+
+extern "C" int tsd_debug_norm_run(tsd_ctx* ctx, const int64_t* desc, int n, const void* const* host_in, void* const* host_out,
+                                  int64_t* ext, int64_t* info) {
+  NOTNULL(desc); NOTNULL(ext);
+  if (n < TSD_ND_COUNT) TSD_FAIL(TSD_E_ARG, "norm_run: %d descriptor fields", n);
+  TSD_TRY(nd_extents(desc, ext));
+  const int64_t* d = desc;
+  const int mode = (int)d[TSD_ND_MODE], B = (int)d[TSD_ND_B], HW = (int)d[TSD_ND_HW], C = (int)d[TSD_ND_C], G = (int)d[TSD_ND_GROUPS];
+  const int ns = (int)d[TSD_ND_NSLAB];
+  if (info) for (int i = 0; i < TSD_NI_COUNT; i++) info[i] = 0;
+  // a non-NULL marker stands for the tables: the plan looks at which pointers are given, never through them
+  static const float marker = 0.f;
+  auto composite_of = [&](const float* p0, const float* p1) {
+    GnComposite gc;
+    gc.part0 = p0; gc.G0 = (int)d[TSD_ND_G0]; gc.part1 = d[TSD_ND_G1] > 0 ? p1 : nullptr; gc.G1 = (int)d[TSD_ND_G1];
+    gc.nslab = ns; gc.comb = (int)d[TSD_ND_COMB];
+    return gc;
+  };
+  if (!host_in) {  // sizing only: no context or device needed; the plan under the default options
+    if (info && (mode == TSD_NM_GROUPNORM || mode == TSD_NM_GN_STATS) && C % 8 == 0 && C % G == 0 && C <= 4096) {
+      const int st = mode == TSD_NM_GROUPNORM ? (int)d[TSD_ND_STATS] : 0;
+      const GnComposite gc = composite_of(&marker, &marker);
+      GnPlan p = gn_plan(TsdOptions(), HW, C, G, st == 1 ? &marker : nullptr, st == 1 ? ns : 0, st == 2 ? &gc : nullptr);
+      if (mode == TSD_NM_GN_STATS) p.stats_ready = 1;
+      nd_plan_info(p, info);
+    }
+    return TSD_OK;
+  }
+  NOTNULL(ctx); NOTNULL(host_out); NOTNULL(info);
+  for (int s = 0; s < TSD_NO_COUNT; s++) {
+    if (!ext[s]) continue;
+    if (s < TSD_NO_Y ? !host_in[s] : !host_out[s - TSD_NO_Y]) TSD_FAIL(TSD_E_ARG, "norm_run: operand slot %d is NULL", s);
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  NdBufs bufs;
+  for (int s = 0; s < TSD_NO_COUNT; s++) {
+    if (!ext[s]) continue;
+    const int es = nd_elem_bytes(s);
+    const size_t bytes = 2 * GD_GUARD + (size_t)ext[s] * es;
+    HIP_TRY(hipMalloc((void**)&bufs.p[s], bytes));
+    if (es == 2) HIP_TRY(hipMemsetD16Async((hipDeviceptr_t)bufs.p[s], GD_NAN16, bytes / 2, st));
+    else HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)bufs.p[s], (int)GD_NAN32, bytes / 4, st));
+    if (s < TSD_NO_Y) HIP_TRY(hipMemcpyAsync(bufs.p[s] + GD_GUARD, host_in[s], (size_t)ext[s] * es, hipMemcpyHostToDevice, st));
+  }
+  auto at = [&](int s) -> void* { return bufs.p[s] ? (void*)(bufs.p[s] + GD_GUARD) : nullptr; };
+  const float eps = nd_float(d[TSD_ND_EPS]), gamma = nd_float(d[TSD_ND_GAMMA]);
+  NormAffine aff;
+  aff.w = (const float*)at(TSD_NO_W); aff.b = (const float*)at(TSD_NO_BIAS); aff.torch_rstd = (int)d[TSD_ND_TORCH_RSTD];
+  const NormAffine* affp = (aff.w || aff.b || aff.torch_rstd) ? &aff : nullptr;
+  ctx->gn_last = GnPlan();
+  const int r = run_planned(ctx, [&]() -> int {
+    if (mode == TSD_NM_LAYERNORM)
+      return launch_layernorm(ctx, (const half_t*)at(TSD_NO_X0), d[TSD_ND_ROWS], C, (int)d[TSD_ND_LD0], eps, (half_t*)at(TSD_NO_Y),
+                              (int)d[TSD_ND_LDY], affp);
+    if (mode == TSD_NM_GN_FINALIZE)
+      return launch_gn_finalize(ctx, (const float*)at(TSD_NO_PART0), ns, B, HW, C, G, eps, gamma, (float*)at(TSD_NO_STATS));
+    if (mode == TSD_NM_GN_STATS)
+      return launch_gn_stats(ctx, (const half_t*)at(TSD_NO_X0), (int)d[TSD_ND_LD0], B, HW, C, G, eps, gamma, (float*)at(TSD_NO_STATS));
+    NormSrc src;
+    src.x0 = (const half_t*)at(TSD_NO_X0); src.ld0 = (int)d[TSD_ND_LD0]; src.C0 = (int)d[TSD_ND_C0];
+    src.x1 = (const half_t*)at(TSD_NO_X1); src.ld1 = (int)d[TSD_ND_LD1];
+    const int sm = (int)d[TSD_ND_STATS];
+    const GnComposite gc = composite_of((const float*)at(TSD_NO_PART0), (const float*)at(TSD_NO_PART1));
+    return launch_groupnorm(ctx, src, B, HW, C, G, eps, gamma, (int)d[TSD_ND_SILU], (half_t*)at(TSD_NO_Y), (int)d[TSD_ND_LDY],
+                            sm == 1 ? (const float*)at(TSD_NO_PART0) : nullptr, sm == 1 ? ns : 0, affp, sm == 2 ? &gc : nullptr);
+  });
+  HIP_TRY(hipStreamSynchronize(st));
+  nd_plan_info(ctx->gn_last, info);  // what the launch itself planned (zeros when it was refused)
+  int64_t changed = 0;
+  for (int s = 0; s < TSD_NO_COUNT; s++) {  // inputs too: a norm launch writes none of them
+    if (!ext[s]) continue;
+    const int es = nd_elem_bytes(s);
+    const size_t bytes = 2 * GD_GUARD + (size_t)ext[s] * es;
+    std::vector<char> got(bytes);
+    HIP_TRY(hipMemcpy(got.data(), bufs.p[s], bytes, hipMemcpyDeviceToHost));
+    const int64_t g0 = (int64_t)(GD_GUARD / es), total = (int64_t)(bytes / es);
+    const int64_t width = C, pitch = s == TSD_NO_Y ? d[TSD_ND_LDY] : 0;
+    for (int64_t i = 0; i < total; i++) {
+      const int64_t j = i - g0;
+      const bool inside = j >= 0 && j < ext[s];
+      if (inside && s < TSD_NO_Y) continue;                              // input payload
+      if (inside && s == TSD_NO_STATS) continue;                         // dense output
+      if (inside && s == TSD_NO_Y && j % pitch < width) continue;        // logical element of y
+      const bool same = es == 2 ? memcmp(&got[(size_t)i * 2], &GD_NAN16, 2) == 0 : memcmp(&got[(size_t)i * 4], &GD_NAN32, 4) == 0;
+      if (!same) changed++;
+    }
+    if (s >= TSD_NO_Y) memcpy(host_out[s - TSD_NO_Y], &got[GD_GUARD], (size_t)ext[s] * es);
+  }
+  info[TSD_NI_CHANGED] = changed;
+  return r;
+}
+
+extern "C" int tsd_debug_gn_path_counts(tsd_ctx* ctx, int64_t* counts, int n, int reset) {
+  NOTNULL(ctx); NOTNULL(counts);
+  if (n < 8) TSD_FAIL(TSD_E_ARG, "gn_path_counts: %d slots (8 needed)", n);
+  for (int i = 0; i < 8; i++) counts[i] = ctx->gn_paths[i];
+  if (reset) for (int i = 0; i < 8; i++) ctx->gn_paths[i] = 0;
+  return TSD_OK;
+}

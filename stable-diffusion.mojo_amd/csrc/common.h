@@ -86,6 +86,22 @@ struct TsdOptions {
 };
 void options_from_env(TsdOptions& o);
 
+// Host-side plan of one GroupNorm launch (kernels_norm.hip gn_plan): where the statistics come from and how the passes are cut.
+// launch_groupnorm / launch_gn_stats act on it and leave it in tsd_ctx::gn_last; tsd_debug_norm_run reports it.
+struct GnComposite;
+struct GnPlan {
+  int PL = 0;             // pixel lanes per 256-thread block
+  int slab_pixels = 0;    // pixels per slab of the own statistics pass
+  int apply_pixels = 0;   // pixels per apply block
+  int nslab = 0;          // slabs per sample the statistics are finished from (own slabs, the producer's, or 64 prereduced chunks)
+  bool composite = false;   // the GnComposite was accepted
+  bool have_stats = false;  // producer partials are used: no own pass over the tensor
+  bool prereduce = false;   // k_gn_prereduce runs first
+  int stats_ready = 0;      // a separate k_gn_finalize launch finishes the statistics
+  const float* part = nullptr; int part_nslab = 0;  // the producer table (composite: its first table)
+};
+GnPlan gn_plan(const TsdOptions& opt, int HW, int C, int groups, const float* pre_part, int pre_nslab, const GnComposite* comp);
+
 struct tsd_ctx {
   int device = 0;
   TsdOptions opt;
@@ -114,6 +130,8 @@ struct tsd_ctx {
   bool gemm_rec_on = false;
   std::vector<int64_t> gemm_rec;
   int gemm_last_cfg = -1, gemm_last_ways = 0;
+  GnPlan gn_last;             // plan of the last GroupNorm launch enqueued (tsd_debug_norm_run)
+  int64_t gn_paths[8] = {};   // tsd_debug_gn_path_counts
 };
 
 enum KernelClass : int {

@@ -279,6 +279,31 @@ __global__ __launch_bounds__(256) void k_gn_apply(const GnK p) {
   }
 }
 
+// The host-side decisions of a GroupNorm launch in one place: slab sizing of the own pass, acceptance of a composite, the
+// prereduce of a large producer table and the separate finalize launch.  C and groups are already validated by the caller.
+GnPlan gn_plan(const TsdOptions& opt, int HW, int C, int groups, const float* pre_part, int pre_nslab, const GnComposite* comp) {
+  GnPlan pl;
+  const int nch = C / 8;
+  pl.PL = nch <= 256 ? 256 / nch : 1;
+  // stats pass: 2*GN_UNROLL pixels per thread, at most 512 slabs per sample ; apply pass: GN_UNROLL pixels per thread
+  pl.slab_pixels = std::max(2 * GN_UNROLL * pl.PL, ceil_div(HW, 64));  // <= 64 slabs: every apply block re-reduces them
+  pl.nslab = ceil_div(HW, pl.slab_pixels);
+  pl.apply_pixels = (opt.gn_apply_mult > 0 ? opt.gn_apply_mult : 2) * GN_UNROLL * pl.PL;
+  // statistics already emitted by the producer's epilogue (EPI_GNSTATS, same [B][nslab][G][2] layout): no partial pass
+  // composite: the statistics are sums of the producers' finer-grained partials (two concat sources, or one source emitted for a
+  // finer grouping) - no statistics pass over the concatenated tensor
+  pl.composite = comp && comp->part0 && comp->comb >= 1 && comp->nslab > 0 && comp->nslab <= 256 &&
+                 (comp->G0 + (comp->part1 ? comp->G1 : 0)) == groups * comp->comb;
+  if (pl.composite) { pre_part = comp->part0; pre_nslab = comp->nslab; }
+  pl.have_stats = pre_part != nullptr && pre_nslab > 0;
+  pl.prereduce = !pl.composite && pl.have_stats && pre_nslab > 256 && groups <= 256;  // large images (VAE): 64 chunks per sample first
+  pl.part = pl.have_stats ? pre_part : nullptr; pl.part_nslab = pl.have_stats ? pre_nslab : 0;
+  if (pl.have_stats && !pl.prereduce) pl.nslab = pre_nslab;
+  else if (pl.prereduce) pl.nslab = 64;
+  pl.stats_ready = (int64_t)pl.nslab * groups >= opt.gn_finalize_min ? 1 : 0;
+  return pl;
+}
+
 int launch_groupnorm(tsd_ctx* ctx, const NormSrc& src, int B, int HW, int C, int groups, float eps, float gamma,
                      int silu, half_t* y, int ldy, const float* pre_part, int pre_nslab, const NormAffine* aff,
                      const GnComposite* comp) {
@@ -289,21 +314,13 @@ int launch_groupnorm(tsd_ctx* ctx, const NormSrc& src, int B, int HW, int C, int
   GnK k;
   k.x0 = src.x0; k.x1 = src.x1; k.ld0 = src.ld0; k.ld1 = src.ld1; k.C0 = C0; k.C = C; k.HW = HW; k.G = groups;
   k.cpg = C / groups;
-  const int nch = C / 8, PL = nch <= 256 ? 256 / nch : 1;
-  // stats pass: 2*GN_UNROLL pixels per thread, at most 512 slabs per sample ; apply pass: GN_UNROLL pixels per thread
-  k.slab_pixels = std::max(2 * GN_UNROLL * PL, ceil_div(HW, 64));  // <= 64 slabs: every apply block re-reduces them
-  k.nslab = ceil_div(HW, k.slab_pixels);
-  k.apply_pixels = (ctx->opt.gn_apply_mult > 0 ? ctx->opt.gn_apply_mult : 2) * GN_UNROLL * PL;
-  // statistics already emitted by the producer's epilogue (EPI_GNSTATS, same [B][nslab][G][2] layout): no partial pass
-  // composite: the statistics are sums of the producers' finer-grained partials (two concat sources, or one source emitted for a
-  // finer grouping) - no statistics pass over the concatenated tensor
-  const bool composite = comp && comp->part0 && comp->comb >= 1 && comp->nslab > 0 && comp->nslab <= 256 &&
-                         (comp->G0 + (comp->part1 ? comp->G1 : 0)) == groups * comp->comb;
-  if (composite) { pre_part = comp->part0; pre_nslab = comp->nslab; }
-  const bool have_stats = pre_part != nullptr && pre_nslab > 0;
-  const bool prereduce = !composite && have_stats && pre_nslab > 256 && groups <= 256;  // large images (VAE): 64 chunks per sample first
-  if (have_stats && !prereduce) { k.partial = const_cast<float*>(pre_part); k.nslab = pre_nslab; }
-  else if (prereduce) { k.partial = arena_alloc<float>(ctx, (int64_t)B * 64 * groups * 2); k.nslab = 64; }
+  const GnPlan pl = gn_plan(ctx->opt, HW, C, groups, pre_part, pre_nslab, comp);
+  const int PL = pl.PL;
+  const bool composite = pl.composite, have_stats = pl.have_stats, prereduce = pl.prereduce;
+  pre_part = pl.part; pre_nslab = pl.part_nslab;
+  k.slab_pixels = pl.slab_pixels; k.nslab = pl.nslab; k.apply_pixels = pl.apply_pixels;
+  if (have_stats && !prereduce) k.partial = const_cast<float*>(pre_part);
+  else if (prereduce) k.partial = arena_alloc<float>(ctx, (int64_t)B * 64 * groups * 2);
   else k.partial = arena_alloc<float>(ctx, (int64_t)B * k.nslab * groups * 2);
   k.stats = arena_alloc<float>(ctx, (int64_t)B * groups * 2);
   if (!k.partial || !k.stats) TSD_FAIL(TSD_E_ALLOC, "groupnorm: workspace exhausted");
@@ -313,7 +330,15 @@ int launch_groupnorm(tsd_ctx* ctx, const NormSrc& src, int B, int HW, int C, int
   k.aw = aff ? aff->w : nullptr; k.ab = aff ? aff->b : nullptr; k.torch_rstd = aff ? aff->torch_rstd : 0;
   if (!ctx->launch()) return TSD_OK;
   ProfScope prof(ctx, KC_GROUPNORM, B * HW, C, 0, 1);
-  k.stats_ready = (int64_t)k.nslab * groups >= ctx->opt.gn_finalize_min ? 1 : 0;
+  k.stats_ready = pl.stats_ready;
+  ctx->gn_last = pl;
+  ctx->gn_paths[0]++;
+  if (!have_stats) ctx->gn_paths[1]++;
+  else if (prereduce) ctx->gn_paths[4]++;
+  else if (composite) ctx->gn_paths[5]++;
+  else ctx->gn_paths[k.stats_ready ? 3 : 2]++;
+  if (k.stats_ready) ctx->gn_paths[6]++;
+  if (comp && comp->part0) ctx->gn_paths[7]++;
   prof.kernels = 1 + ((!have_stats || prereduce) ? 1 : 0) + (k.stats_ready ? 1 : 0);
   if (!have_stats) {
     hipLaunchKernelGGL(k_gn_partial, dim3(k.nslab, B), dim3(256), (size_t)PL * 2 * C * sizeof(float), ctx->stream, k);
@@ -354,13 +379,16 @@ int launch_gn_stats(tsd_ctx* ctx, const half_t* x, int ld, int B, int HW, int C,
   if (C % 8 || C % groups || C > 256 * 8 * GN_MAX_CPT || ld % 8) TSD_FAIL(TSD_E_SHAPE, "gn_stats: C=%d groups=%d unsupported", C, groups);
   GnK k = {};
   k.x0 = x; k.ld0 = ld; k.C0 = C; k.C = C; k.HW = HW; k.G = groups; k.cpg = C / groups;
-  const int nch = C / 8, PL = nch <= 256 ? 256 / nch : 1;
-  k.slab_pixels = std::max(2 * GN_UNROLL * PL, ceil_div(HW, 64));
-  k.nslab = ceil_div(HW, k.slab_pixels);
+  GnPlan pl = gn_plan(ctx->opt, HW, C, groups, nullptr, 0, nullptr);
+  pl.stats_ready = 1;  // statistics only: always finished by the finalize launch
+  const int PL = pl.PL;
+  k.slab_pixels = pl.slab_pixels;
+  k.nslab = pl.nslab;
   k.partial = arena_alloc<float>(ctx, (int64_t)B * k.nslab * groups * 2);
   if (!k.partial) TSD_FAIL(TSD_E_ALLOC, "gn_stats: workspace exhausted");
   k.stats = stats; k.eps = eps; k.gamma = gamma;
   if (!ctx->launch()) return TSD_OK;
+  ctx->gn_last = pl;
   ProfScope prof(ctx, KC_GROUPNORM, B * HW, C, 0, 1);
   prof.kernels = 2;
   hipLaunchKernelGGL(k_gn_partial, dim3(k.nslab, B), dim3(256), (size_t)PL * 2 * C * sizeof(float), ctx->stream, k);
@@ -494,6 +522,7 @@ static void launch_layernorm_t(tsd_ctx* ctx, const half_t* x, int64_t rows, int 
 int launch_layernorm(tsd_ctx* ctx, const half_t* x, int64_t rows, int C, int ldx, float eps, half_t* y, int ldy,
                      const NormAffine* aff) {
   if (C % 8 || C > 64 * 8 * LN_MAX_CH) TSD_FAIL(TSD_E_SHAPE, "layernorm: C=%d unsupported", C);
+  if (ldx % 8 || ldy % 8) TSD_FAIL(TSD_E_SHAPE, "layernorm: pitches must be multiples of 8");  // 16-B row loads and stores
   if (!ctx->launch()) return TSD_OK;
   ProfScope prof(ctx, KC_LAYERNORM, (int)rows, C, 0, 1);
   LnAff a{aff ? aff->w : nullptr, aff ? aff->b : nullptr, aff ? aff->torch_rstd : 0};

@@ -150,6 +150,7 @@ def _ln_torch_case(name, M, C, affine=True):
 
 
 _ln_torch_case("layernorm_torch_320", 37, 320)
+_ln_torch_case("layernorm_torch_640", 21, 640)      # k_layernorm_grp<16>: 16 rows per block, one full block and a partial one
 _ln_torch_case("layernorm_torch_768", 11, 768)
 _ln_torch_case("layernorm_torch_1280_no_affine", 9, 1280, affine=False)
 
