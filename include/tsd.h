@@ -485,6 +485,15 @@ int tsd_debug_gn_path_counts(tsd_ctx* ctx, int64_t* counts, int n, int reset);
  * pointers only ask) and returns C, 0 when that block does not fold.  tsd_model_prepare returns TSD_E_NONFINITE when a folded weight
  * leaves fp16. */
 int tsd_debug_model_fold(tsd_model* m, int block, void* wf, float* bf);
+/* UNet layer 10 reads the channel concat of ONE tensor with itself (diffusion.mojo:253-256).  With TSD_FOLD_DUP (default 1, read by
+ * tsd_ctx_create) tsd_model_prepare adds the two input-channel halves of its conv1 and 1x1 skip weights - exact sum, one rounding to
+ * fp16, nearest-even - and the block runs as cin/2 -> cout with GroupNorm(groups/2).  tsd_debug_model_dup_fold copies the folded conv1
+ * [Opad][9][cin/2] and skip [Opad][cin/2] fp16 weights (NULL pointers only ask) and returns cin/2, 0 when the model does not fold;
+ * tsd_model_prepare returns TSD_E_NONFINITE when a sum leaves fp16.  tsd_debug_dup_fold_host is that arithmetic on host memory (no
+ * device needed): out[r][t][c] = w[r][t][c] + w[r][t][half + c] for c < half, 0 for half <= c < ldo, on fp16 bit patterns
+ * w [rows][taps][ldw], out [rows][taps][ldo]; returns the number of sums that are not finite, < 0 on a bad argument. */
+int tsd_debug_model_dup_fold(tsd_model* m, void* conv1_w, void* skip_w);
+int64_t tsd_debug_dup_fold_host(const void* w, int rows, int taps, int ldw, int half, void* out, int ldo);
 /* tsd_debug_gemm_bench for the fused attention core: Q,K [B][S][H*d], V^T [B][H*d][Sk]. */
 int tsd_debug_attn_bench(tsd_ctx* ctx, int B, int H, int d, int Sq, int Sk, int iters, float* ms);
 /* The fused attention core runs an optimistic softmax pass (reference fixed after the first key tile) and repeats a

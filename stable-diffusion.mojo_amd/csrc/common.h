@@ -60,6 +60,7 @@ struct TsdOptions {
   int conv_in_im2col = 1;  // TSD_CONV_IN_IM2COL: the 4-channel input convolution as one im2col K tile
   int chain = 1;           // TSD_CHAIN: fused head / tail kernels of the 64x64-level attention blocks
   int fold_out = 1;        // TSD_FOLD_OUT: op-by-op attention blocks (C = 640 / 1280): GEGLU's second linear + the output 1x1 conv as one GEMM over [h | r]
+  int fold_dup = 1;        // TSD_FOLD_DUP: layer 10's concat(x, x) folded into its conv1 / skip weights (UNetW::res_dup): a 1280 -> 1280 block instead of 2560 -> 1280
   int session_hoist = 1;   // TSD_SESSION_HOIST: a denoise session computes the time path of every schedule entry and the context K / V^T once per upload(), not once per step
   // derived weight copies (model.cpp; read when a model's derived buffers are built)
   int conv_w_tm_mib = 2, lin_w_tm = 1, lin_w_tm_kib = 1024;  // TSD_CONV_W_TM, TSD_LIN_W_TM, TSD_LIN_W_TM_KIB

@@ -128,18 +128,25 @@ int g_resblock(tsd_ctx* ctx, const CatSrc& x, int B, int Hin, int Win, int ups, 
   const size_t mark = ctx->arena.mark();
   // GN -> SiLU (only the first cin channels are normalised/consumed: App.A D11)
   Act h = act_alloc(ctx, B, Hin, Win, cin); CHECK_ALLOC(h.p);
-  const bool x_stats = !(x.p1 && cin > x.C0) && x.gn_part0 && x.gn_groups0 == w.groups && x.C0 == cin;
+  const int g_in = w.groups_in > 0 ? w.groups_in : w.groups;  // groups of the first norm (the folded duplicate-concat block: half of `groups`)
+  const bool x_stats = !(x.p1 && cin > x.C0) && x.gn_part0 && x.gn_groups0 == g_in && x.C0 == cin;
   // channel concat (diffusion.mojo:253-270): the norm's groups are sums of whole groups of the two producers' statistics when both
   // were emitted at one granularity that divides the concat's group size - no statistics pass over the concatenated tensor
   GnComposite gc;
   if (ctx->opt.gn_composite && x.p1 && cin == x.C0 + x.C1 && x.gn_part0 && x.gn_part1 && x.gn_groups0 > 0 && x.gn_groups1 > 0 &&
-      x.gn_nslab0 == x.gn_nslab1 && x.gn_nslab0 > 0 && x.C0 % x.gn_groups0 == 0 && x.C1 % x.gn_groups1 == 0 && cin % w.groups == 0) {
-    const int cf = x.C0 / x.gn_groups0, cpg = cin / w.groups;
+      x.gn_nslab0 == x.gn_nslab1 && x.gn_nslab0 > 0 && x.C0 % x.gn_groups0 == 0 && x.C1 % x.gn_groups1 == 0 && cin % g_in == 0) {
+    const int cf = x.C0 / x.gn_groups0, cpg = cin / g_in;
     if (cf == x.C1 / x.gn_groups1 && cpg % cf == 0) {
       gc.part0 = x.gn_part0; gc.G0 = x.gn_groups0; gc.part1 = x.gn_part1; gc.G1 = x.gn_groups1; gc.nslab = x.gn_nslab0; gc.comb = cpg / cf;
     }
+  } else if (ctx->opt.gn_composite && !x_stats && !(x.p1 && cin > x.C0) && x.C0 == cin && x.gn_part0 && x.gn_nslab0 > 0 && x.gn_groups0 > g_in &&
+             x.gn_groups0 % g_in == 0 && cin % x.gn_groups0 == 0) {
+    // one source whose producer emitted its statistics for a finer grouping (the folded duplicate-concat block: 32 groups of 40 channels
+    // emitted, 16 of 80 wanted): each group is the sum of `comb` consecutive fine groups - the same partials in the same order as the
+    // two-source composite over [x | x] adds for either half
+    gc.part0 = x.gn_part0; gc.G0 = x.gn_groups0; gc.nslab = x.gn_nslab0; gc.comb = x.gn_groups0 / g_in;
   }
-  TSD_TRY(launch_groupnorm(ctx, norm_src(x, cin), B, Hin * Win, cin, w.groups, w.eps, 1.f, 1, h.p, h.ld,
+  TSD_TRY(launch_groupnorm(ctx, norm_src(x, cin), B, Hin * Win, cin, g_in, w.eps, 1.f, 1, h.p, h.ld,
                            x_stats ? x.gn_part0 : nullptr, x.gn_nslab0, w.gn1.w ? &w.gn1 : nullptr, gc.part0 ? &gc : nullptr));
   Act t1 = act_alloc_gn(ctx, B, H, W, cout, w.groups); CHECK_ALLOC(t1.p);
   TSD_TRY(g_conv3x3(ctx, h, w.conv1, 1, 1, 1, ups, tvec ? tvec + w.time_off : nullptr, tld, nullptr, 0, false, t1.p, t1.ld, &t1));
@@ -540,6 +547,13 @@ int g_unet_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, 
   TSD_TRY(attn(9));
   // decoders (diffusion.mojo:253-272); skip4 / skip2 are dead (App.A D11): layers 15 and 20 declare
   // fewer input channels than the concat provides and only read the first in_channels.
+  // layer 10 concatenates the bottleneck's output with ITSELF (diffusion.mojo:253-256): with the two input-channel halves of its conv1 /
+  // skip weights added at model_check_ready (UNetW::res_dup) it is a 1280 -> 1280 block over the one tensor.  The choice depends on the
+  // model and the context's options alone, so the planning pass and the real pass take the same branch.
+  if (u.res_dup_on && ctx->opt.fold_dup && a[9].C == u.res_dup.cin) {
+    TSD_TRY(alloc_out(10, L2, u.res_dup.cout));
+    TSD_TRY(g_resblock(ctx, cat1(a[9]), B, L2, L2, 0, u.res_dup, tvec, tld, a[10]));
+  } else
   TSD_TRY(res(10, cat2(a[9], a[9]), L2, 0));
   TSD_TRY(attn(11));
   TSD_TRY(res(12, cat2(a[11], a[7]), L2, 0));

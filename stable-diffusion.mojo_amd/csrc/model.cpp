@@ -19,10 +19,76 @@ bool attn_head_weights_ok(const AttnW& w) {
          w.conv_in.k == 1 && w.conv_in.Ipad == C && w.conv_in.Opad == C && !w.sa_in.b && w.sa_in.Kpad == C && w.sa_in.N == 3 * C;
 }
 
+// ---- duplicate-concat fold (UNetW::res_dup): host arithmetic on fp16 bit patterns, no HIP -------------------------------------------
+// fp16 -> double is exact; the sum of two fp16 values spans at most 40 binades + 11 bits < 53, so the double sum is exact and the
+// conversion back is the ONE rounding (nearest, ties to even; overflow -> inf; NaN keeps its top payload bits).
+static double f16_bits_to_f64(uint16_t h) {
+  const uint64_t sign = (uint64_t)(h & 0x8000) << 48;
+  const int e = (h >> 10) & 31;
+  const uint64_t m = h & 0x3FF;
+  uint64_t u;
+  if (e == 31) u = sign | (0x7FFull << 52) | (m << 42);
+  else if (e == 0) {
+    const double v = ldexp((double)m, -24);
+    return sign ? -v : v;
+  } else u = sign | ((uint64_t)(e - 15 + 1023) << 52) | (m << 42);
+  double d;
+  memcpy(&d, &u, 8);
+  return d;
+}
+
+static uint16_t f64_to_f16_bits_rne(double v) {
+  uint64_t u;
+  memcpy(&u, &v, 8);
+  const uint16_t sign = (uint16_t)((u >> 48) & 0x8000);
+  const int e = (int)((u >> 52) & 0x7FF);
+  uint64_t m = u & ((1ull << 52) - 1);
+  if (e == 0x7FF) {
+    uint16_t r = (uint16_t)(0x7C00 + (m >> 42));
+    if (m && r == 0x7C00) r++;  // a NaN stays a NaN
+    return sign | r;
+  }
+  if (e == 0) return sign;  // zero (a double subnormal is no sum of fp16 values)
+  const int E = e - 1023;
+  m |= 1ull << 52;  // v = m * 2^(E - 52); one fp16 ulp is 2^(E - 10) for a normal result, 2^-24 below 2^-14
+  const int shift = 42 + (E < -14 ? -14 - E : 0);
+  if (shift > 63) return sign;
+  uint64_t q = m >> shift;
+  const uint64_t rem = m & ((1ull << shift) - 1), half = 1ull << (shift - 1);
+  if (rem > half || (rem == half && (q & 1))) q++;
+  // normal: q in [2^10, 2^11] and the exponent field is E + 15 - a carry out of the mantissa moves it up by itself; subnormal: q is the pattern
+  uint64_t bits = E >= -14 ? ((uint64_t)(E + 14) << 10) + q : q;
+  if (bits >= 0x7C00) bits = 0x7C00;
+  return sign | (uint16_t)bits;
+}
+
+// out[o][t][c] = w[o][t][c] + w[o][t][half + c] for c < half, 0 for half <= c < ldo; w is [rows][taps][ldw] with ldw >= 2 * half.
+// Returns how many sums are not finite.
+static int64_t dup_fold_host(const uint16_t* w, int64_t rows, int taps, int ldw, int half, uint16_t* out, int ldo) {
+  int64_t bad = 0;
+  for (int64_t rt = 0; rt < rows * taps; rt++) {
+    const uint16_t* s = w + rt * ldw;
+    uint16_t* d = out + rt * ldo;
+    for (int c = 0; c < half; c++) {
+      const uint16_t a = s[c], b = s[half + c];
+      d[c] = f64_to_f16_bits_rne(f16_bits_to_f64(a) + f16_bits_to_f64(b));
+      bad += (d[c] & 0x7C00) == 0x7C00;
+    }
+    for (int c = half; c < ldo; c++) d[c] = 0;
+  }
+  return bad;
+}
+
+extern "C" int64_t tsd_debug_dup_fold_host(const void* w, int rows, int taps, int ldw, int half, void* out, int ldo) {
+  if (!w || !out || rows <= 0 || taps <= 0 || half <= 0 || ldw < 2 * half || ldo < half) TSD_FAIL(TSD_E_ARG, "dup_fold_host: bad argument");
+  return dup_fold_host((const uint16_t*)w, rows, taps, ldw, half, (uint16_t*)out, ldo);
+}
+
 // parameters changed: derived buffers are stale until the next model_check_ready()
 static void model_invalidate_derived(tsd_model* m) {
   m->ready = false;
   m->gen++;
+  m->unet.res_dup_on = false; m->unet.res_dup = ResW();
   for (auto& a : m->unet.attn) { a.tail_stream = nullptr; a.head_stream = nullptr; a.fold_w = nullptr; a.fold_w_tm = nullptr; a.fold_b = nullptr; }
   m->unet.conv_in_im2col = nullptr;
   m->vae.conv_in_im2col = nullptr;
@@ -203,12 +269,31 @@ static int model_build_derived(tsd_model* m) {
   // 800-KB 640 x 640 projections of the 32x32 level join in: measured equal, 205.65 vs 205.60 steps/s)
   const int tml_kib = ctx->opt.lin_w_tm_kib;
   const size_t tml_bytes = (size_t)(tml_kib > 0 ? tml_kib : 1024) << 10;
+  // Layer 10 of the Tiny-SD graph reads concat(a[9], a[9]) (g_unet_forward; diffusion.mojo:253-256): its conv1 / skip weights with the two
+  // input-channel halves added (UNetW::res_dup).  Structure only: an even split into multiples of 64 channels, an even group count whose
+  // groups do not straddle the halves, and no per-channel affine (that would differ between the halves).
+  bool dup = false;
+  if (ctx->opt.fold_dup && !is_full_unet_kind(m->kind) && m->unet.res.size() > 9 && m->unet.attn.size() > 8) {
+    const ResW& r = m->unet.res[9];
+    const int half = r.cin / 2;
+    dup = r.cin > 0 && r.cin % 2 == 0 && half % 64 == 0 && m->unet.attn[8].C == half && r.groups % 2 == 0 && half % (r.groups / 2) == 0 &&
+          r.conv1.w && r.conv1.k == 3 && r.conv1.Ipad == r.cin && r.has_skip && r.skip.w && r.skip.k == 1 && r.skip.Ipad == r.cin &&
+          r.skip.Opad == r.conv1.Opad && !r.gn1.w && !r.gn1.b;  // (NormAffine::torch_rstd only counts when the affine is passed: g_resblock)
+  }
+  size_t dup_w1_b = 0, dup_sk_b = 0, dup_tm_b = 0;
+  if (dup) {
+    const ResW& r = m->unet.res[9];
+    dup_w1_b = (((size_t)r.conv1.Opad * 9 * (r.cin / 2) * 2) + 255) & ~size_t(255);
+    dup_sk_b = (((size_t)r.skip.Opad * (r.cin / 2) * 2) + 255) & ~size_t(255);
+    if (tm_mib > 0 && (size_t)r.conv1.Opad * 9 * (r.cin / 2) * 2 >= (size_t)tm_mib << 20) dup_tm_b = dup_w1_b;
+  }
   std::vector<ConvW*> tm;
   size_t tm_b = 0;
   if (tm_mib > 0)
     for (auto& r : m->unet.res)
       for (ConvW* c : {&r.conv1, &r.conv2})
-        if (c->w && c->k == 3 && (size_t)c->Opad * 9 * c->Ipad * 2 >= (size_t)tm_mib << 20) { tm.push_back(c); tm_b += (((size_t)c->Opad * 9 * c->Ipad * 2) + 255) & ~size_t(255); }
+        // (the graph runs the folded conv1 of layer 10: no tile-major copy of the unfolded one)
+        if (!(dup && c == &m->unet.res[9].conv1) && c->w && c->k == 3 && (size_t)c->Opad * 9 * c->Ipad * 2 >= (size_t)tm_mib << 20) { tm.push_back(c); tm_b += (((size_t)c->Opad * 9 * c->Ipad * 2) + 255) & ~size_t(255); }
   if (tm_mib > 0) {  // downsampling / upsampling convs outside the residual blocks
     for (ConvW* c : {&m->unet.conv4, &m->unet.conv7})
       if (c->w && c->k == 3 && (size_t)c->Opad * 9 * c->Ipad * 2 >= (size_t)tm_mib << 20) { tm.push_back(c); tm_b += (((size_t)c->Opad * 9 * c->Ipad * 2) + 255) & ~size_t(255); }
@@ -244,9 +329,9 @@ static int model_build_derived(tsd_model* m) {
         fold.push_back(&a);
         fold_b += 2 * ((((size_t)a.C * 5 * a.C * 2) + 255) & ~size_t(255)) + ((((size_t)a.C * 4) + 255) & ~size_t(255));
       }
-  if (el.empty() && !cin_ok && tm.empty() && tml.empty() && !kv && fold.empty()) return TSD_OK;
+  if (el.empty() && !cin_ok && tm.empty() && tml.empty() && !kv && fold.empty() && !dup) return TSD_OK;
   const size_t tail_b = (attn_tail_stream_bytes() + 255) & ~size_t(255), head_b = (attn_head_stream_bytes() + 255) & ~size_t(255);
-  const size_t each = tail_b + head_b, need = each * el.size() + cin_b + tm_b + fold_b;
+  const size_t each = tail_b + head_b, need = each * el.size() + cin_b + tm_b + fold_b + dup_w1_b + dup_sk_b + dup_tm_b;
   HIP_TRY(hipSetDevice(ctx->device));
   if (m->derived_bytes < need) {
     if (m->derived) HIP_TRY(hipFree(m->derived));
@@ -312,6 +397,47 @@ static int model_build_derived(tsd_model* m) {
       if (r == TSD_OK) { a->fold_w = wf; a->fold_w_tm = wf_tm; a->fold_b = bf; }
       off += 2 * wb + ((((size_t)C * 4) + 255) & ~size_t(255));
     }
+    if (dup && r == TSD_OK) {
+      // Host-side and exact: both halves to the host, summed in double (two fp16 values can be 40 binades apart), rounded to fp16 once.
+      // Once per build of the derived buffers; a sum that leaves fp16 must not be silent (as for the attention blocks' fold below).
+      const ResW& r10 = m->unet.res[9];
+      const int half = r10.cin / 2;
+      const size_t n1 = (size_t)r10.conv1.Opad * 9 * r10.cin, ns = (size_t)r10.skip.Opad * r10.cin;
+      std::vector<uint16_t> src(std::max(n1, ns)), dst(std::max(n1, ns) / 2);
+      half_t* w1 = (half_t*)(m->derived + off);
+      half_t* wsk = (half_t*)(m->derived + off + dup_w1_b);
+      half_t* w1_tm = dup_tm_b ? (half_t*)(m->derived + off + dup_w1_b + dup_sk_b) : nullptr;
+      off += dup_w1_b + dup_sk_b + dup_tm_b;
+      int64_t bad = 0;
+      hipError_t e = hipStreamSynchronize(ctx->stream);
+      for (int k = 0; k < 2 && e == hipSuccess; k++) {
+        const ConvW& c = k ? r10.skip : r10.conv1;
+        const size_t n = k ? ns : n1;
+        e = hipMemcpy(src.data(), c.w, n * 2, hipMemcpyDeviceToHost);
+        if (e != hipSuccess) break;
+        bad += dup_fold_host(src.data(), c.Opad, c.k * c.k, c.Ipad, half, dst.data(), half);
+        e = hipMemcpyAsync(k ? wsk : w1, dst.data(), n, hipMemcpyHostToDevice, ctx->stream);  // n / 2 folded weights of 2 bytes
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+      }
+      if (e != hipSuccess) {
+        tsd_set_error("duplicate-concat fold: %s", hipGetErrorString(e));
+        r = TSD_E_HIP;
+      } else if (bad) {
+        tsd_set_error("unet.layer10: %lld folded conv1 / skip weights are not finite (the sum of the two input-channel halves leaves fp16)",
+                      (long long)bad);
+        r = TSD_E_NONFINITE;
+      } else {
+        ResW d = r10;  // conv2 (with the tile-major copy made above), biases, time projection, second norm: shared
+        d.cin = half; d.groups_in = r10.groups / 2;
+        d.conv1.w = w1; d.conv1.I = half; d.conv1.Ipad = half; d.conv1.w_tm = nullptr;
+        d.skip.w = wsk; d.skip.I = half; d.skip.Ipad = half; d.skip.w_tm = nullptr;
+        if (w1_tm) {
+          r = launch_pack_tile_major(ctx, w1, d.conv1.Opad, 9 * half, w1_tm);
+          if (r == TSD_OK) d.conv1.w_tm = w1_tm;
+        }
+        if (r == TSD_OK) { m->unet.res_dup = d; m->unet.res_dup_on = true; }
+      }
+    }
   }
   // A folded weight is a product of two weight matrices rounded to fp16 once: one that leaves fp16 (or a non-finite bias) must not be
   // silent.  Host-side scan, once per build of the derived buffers.
@@ -375,6 +501,21 @@ extern "C" int tsd_debug_model_fold(tsd_model* m, int block, void* wf, float* bf
   if (wf) HIP_TRY(hipMemcpy(wf, a.fold_w, (size_t)a.C * 5 * a.C * 2, hipMemcpyDeviceToHost));
   if (bf) HIP_TRY(hipMemcpy(bf, a.fold_b, (size_t)a.C * 4, hipMemcpyDeviceToHost));
   return a.C;
+}
+
+// Debug entry: the folded conv1 [Opad][9][cin/2] and skip [Opad][cin/2] fp16 weights of the duplicate-concat block (UNet layer 10);
+// returns cin/2, 0 when this model / context does not fold
+extern "C" int tsd_debug_model_dup_fold(tsd_model* m, void* conv1_w, void* skip_w) {
+  if (!m) TSD_FAIL(TSD_E_ARG, "NULL model");
+  if (!is_diffusion_kind(m->kind)) TSD_FAIL(TSD_E_ARG, "model_dup_fold: not a diffusion model");
+  HIP_TRY(hipSetDevice(m->ctx->device));
+  TSD_TRY(model_check_ready(m));
+  if (!m->unet.res_dup_on) return 0;
+  const ResW& d = m->unet.res_dup;
+  HIP_TRY(hipStreamSynchronize(m->ctx->stream));
+  if (conv1_w) HIP_TRY(hipMemcpy(conv1_w, d.conv1.w, (size_t)d.conv1.Opad * 9 * d.conv1.Ipad * 2, hipMemcpyDeviceToHost));
+  if (skip_w) HIP_TRY(hipMemcpy(skip_w, d.skip.w, (size_t)d.skip.Opad * d.skip.Ipad * 2, hipMemcpyDeviceToHost));
+  return d.cin;
 }
 
 ConvW model_conv(const tsd_model* m, const std::string& prefix) {

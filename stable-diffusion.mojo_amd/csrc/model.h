@@ -53,6 +53,7 @@ struct ResW {
   ConvW conv1, conv2, skip;
   LinW time;       // UNet only (kept for the op-level path; the model path uses the concatenated table)
   int cin = 0, cout = 0, groups = 32;
+  int groups_in = 0;  // groups of the FIRST GroupNorm when they differ from `groups` (0: the same) - the folded duplicate-concat block only
   bool has_skip = false;
   int time_off = 0;  // column offset into the concatenated time projection [B][6720]
   NormAffine gn1, gn2;  // torch-norm extension (kind 6): per-channel affine of the two GroupNorms (w == nullptr: reference)
@@ -94,6 +95,13 @@ struct UNetW {
   std::vector<ResW> res;    // indexed by flat layer position (23 entries, or SD15_N)
   std::vector<AttnW> attn;
   std::vector<ConvW> conv;  // full-size UNet only: input, downsample and upsample convolutions
+  // derived (TSD_FOLD_DUP): layer 10 reads concat(x, x) of ONE tensor (diffusion.mojo:253-256), so GroupNorm(32) over [x | x] is
+  // [g | g] with g = GroupNorm(16)(x) and conv1 / the 1x1 skip over the concat are convolutions of the single tensor with the two
+  // input-channel halves of their weights added (exact sum, one rounding to fp16): an ordinary cin/2 -> cout block.  res_dup shares
+  // everything else with res[9]; res_dup_on is false when the block does not qualify or the parameters changed since
+  // model_check_ready().  Decided from the graph's structure, never from the data.
+  ResW res_dup;
+  bool res_dup_on = false;
   NormAffine final_gn;      // torch-norm extension (kind 6)
   int final_groups = 320;   // UNet_Output_Layer's GroupNorm (diffusion.mojo:287-291); 32 with torch norms
 };

@@ -154,6 +154,8 @@ def _declare(l):
         "tsd_debug_gemm_record": ([vp, i], i),
         "tsd_debug_gemm_recorded": ([vp, i, C.POINTER(i64), i], i),
         "tsd_debug_model_fold": ([vp, i, vp, fp], i),
+        "tsd_debug_model_dup_fold": ([vp, vp, vp], i),
+        "tsd_debug_dup_fold_host": ([vp, i, i, i, i, vp, i], i64),
         "tsd_debug_gemm_run": ([vp, C.POINTER(i64), i, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)], i),
         "tsd_debug_norm_run": ([vp, C.POINTER(i64), i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)], i),
         "tsd_debug_gn_path_counts": ([vp, C.POINTER(i64), i, i], i),
