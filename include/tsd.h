@@ -494,6 +494,19 @@ int tsd_debug_model_fold(tsd_model* m, int block, void* wf, float* bf);
  * w [rows][taps][ldw], out [rows][taps][ldo]; returns the number of sums that are not finite, < 0 on a bad argument. */
 int tsd_debug_model_dup_fold(tsd_model* m, void* conv1_w, void* skip_w);
 int64_t tsd_debug_dup_fold_host(const void* w, int rows, int taps, int ldw, int half, void* out, int ldo);
+/* The residual blocks behind a nearest-2x upsample (layers 15 and 20 of the 23-layer UNet) run conv1 over the upsampled grid.  Its nine
+ * taps read 2 x 2 source pixels per output pixel, so tsd_model_prepare sums the taps that share one: four 2x2 kernels, one per output
+ * parity q = 2 py + px, rows {0},{1,2} for parity 0 and {0,1},{2} for parity 1, columns alike - exact sum, one rounding to fp16,
+ * nearest-even - and with TSD_UPS_FOLD (default 1; tsd_debug_set_ups_fold returns the previous value) the launch executes K = 4 Cin on
+ * them where the source plane is a multiple of 256 pixels (TSD_GD_UPS = 2 in its descriptor, which still states the 3x3 problem).
+ * tsd_debug_ups_fold_host is the arithmetic on host memory (no device needed): fp16 bit patterns w [O][3][3][Ipad] with row pitch
+ * ldw >= 9 Ipad -> out [4][O][2][2][Ipad]; returns the number of sums that are not finite, < 0 on a bad argument.
+ * tsd_debug_model_ups_fold copies the device copy of residual block `block` (index into the UNet's layers; NULL only asks): per parity
+ * that matrix K-tile-major, [4 Ipad / 64][Opad][64]; returns Ipad, 0 when the block does not fold.  tsd_model_prepare returns
+ * TSD_E_NONFINITE when a sum leaves fp16. */
+int64_t tsd_debug_ups_fold_host(const void* w, int O, int Ipad, int ldw, void* out);
+int tsd_debug_model_ups_fold(tsd_model* m, int block, void* out);
+int tsd_debug_set_ups_fold(tsd_ctx* ctx, int on);
 /* tsd_debug_gemm_bench for the fused attention core: Q,K [B][S][H*d], V^T [B][H*d][Sk]. */
 int tsd_debug_attn_bench(tsd_ctx* ctx, int B, int H, int d, int Sq, int Sk, int iters, float* ms);
 /* The fused attention core runs an optimistic softmax pass (reference fixed after the first key tile) and repeats a

@@ -706,7 +706,7 @@ int gd_extents(const int64_t* d, int64_t* e) {
     const int64_t Cin1 = d[TSD_GD_CIN1], Cin2 = d[TSD_GD_CIN2];
     GD_REQ(Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0 && Hs < 2048 && Ws < 2048 && Ho < 2048 && Wo < 2048 && Cin > 0 && Cin <= 8192);
     GD_REQ(batch == 1 && M % (Ho * Wo) == 0 && d[TSD_GD_LDA0] >= Cin);
-    GD_REQ((d[TSD_GD_STRIDE] == 1 || d[TSD_GD_STRIDE] == 2) && (d[TSD_GD_UPS] == 0 || d[TSD_GD_UPS] == 1) && d[TSD_GD_PAD] >= 0 && d[TSD_GD_PAD] <= 1);
+    GD_REQ((d[TSD_GD_STRIDE] == 1 || d[TSD_GD_STRIDE] == 2) && (d[TSD_GD_UPS] >= 0 && d[TSD_GD_UPS] <= 2) && d[TSD_GD_PAD] >= 0 && d[TSD_GD_PAD] <= 1);
     {  // Ho / Wo must follow from the source, stride, pad and a bottom / right pad of 0 or 1: the kernel packs each output pixel's
        // first tap (o * stride - pad + 1) into an 11-bit field with the sample index above it, so a larger one would read another image
       const int64_t st = d[TSD_GD_STRIDE], pad = d[TSD_GD_PAD], up = d[TSD_GD_UPS] ? 2 : 1;
@@ -795,7 +795,7 @@ std::vector<char> gd_logical(int s, const int64_t* d, int64_t ext) {
   return m;
 }
 struct GdBufs {
-  char* p[TSD_GO_COUNT + 1] = {};  // + the K-tile-major weight copy
+  char* p[TSD_GO_COUNT + 2] = {};  // + the K-tile-major weight copy, + the upsample-folded copies
   ~GdBufs() { for (char* q : p) if (q) (void)hipFree(q); }
 };
 }  // namespace
@@ -872,6 +872,19 @@ extern "C" int tsd_debug_gemm_run(tsd_ctx* ctx, const int64_t* desc, int n, int 
     half_t* tm = (half_t*)(bufs.p[TSD_GO_COUNT] + GD_GUARD);
     TSD_TRY(launch_pack_tile_major(ctx, g.Wt, g.N, KW, tm));
     g.Wt = tm; g.ldw = 64; g.w_kts = g.N * 128;
+  }
+  if (g.conv && g.ups == 2 && g.Cin % 64 == 0 && host_in[TSD_GO_W]) {
+    // the folded parity copies, made from the row-major W the caller passed by the routine tsd_model_prepare uses (model.cpp); whether the
+    // launch may run them is launch_gemm's decision
+    const int ld = d[TSD_GD_W_KTS] ? 9 * g.Cin : (int)d[TSD_GD_LDW];
+    const size_t nf = (size_t)16 * g.N * g.Cin;
+    std::vector<uint16_t> folded(nf);
+    (void)ups_fold_pack_host((const uint16_t*)host_in[TSD_GO_W], g.N, g.Cin, ld, folded.data());
+    HIP_TRY(hipMalloc((void**)&bufs.p[TSD_GO_COUNT + 1], 2 * GD_GUARD + nf * 2));
+    TSD_TRY(fill(bufs.p[TSD_GO_COUNT + 1], (2 * GD_GUARD) / 2 + nf, 2));
+    HIP_TRY(hipMemcpyAsync(bufs.p[TSD_GO_COUNT + 1] + GD_GUARD, folded.data(), nf * 2, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    g.Wuf = (const half_t*)(bufs.p[TSD_GO_COUNT + 1] + GD_GUARD);
   }
   // the dispatcher's choice (with the recorded graph's long-K split) or a forced tile; a replay is not recorded
   const int prev_force = ctx->opt.force_cfg, prev_big = ctx->opt.sk_big_graph;

@@ -60,6 +60,7 @@ struct TsdOptions {
   int conv_in_im2col = 1;  // TSD_CONV_IN_IM2COL: the 4-channel input convolution as one im2col K tile
   int chain = 1;           // TSD_CHAIN: fused head / tail kernels of the 64x64-level attention blocks
   int fold_out = 1;        // TSD_FOLD_OUT: op-by-op attention blocks (C = 640 / 1280): GEGLU's second linear + the output 1x1 conv as one GEMM over [h | r]
+  int ups_fold = 1;        // TSD_UPS_FOLD: conv1 of the residual blocks behind a nearest-2x upsample as four 2x2 parity convolutions on folded weights (ConvW::w_uf): K = 4 Cin instead of 9 Cin
   int fold_dup = 1;        // TSD_FOLD_DUP: layer 10's concat(x, x) folded into its conv1 / skip weights (UNetW::res_dup): a 1280 -> 1280 block instead of 2560 -> 1280
   int session_hoist = 1;   // TSD_SESSION_HOIST: a denoise session computes the time path of every schedule entry and the context K / V^T once per upload(), not once per step
   // derived weight copies (model.cpp; read when a model's derived buffers are built)
@@ -219,6 +220,9 @@ struct ConvW {  // fp16 [Opad][k*k][Ipad] (K-major for the implicit GEMM), fp32 
   // derived (model_check_ready, weight-heavy 3x3 convs only): the same weights K-tile-major, [k*k*Ipad / 64][Opad][64] - the 160 x 64
   // tile a workgroup stages per K step is 20 KB of consecutive bytes instead of 160 rows a whole weight row (up to 46 KB) apart
   const half_t* w_tm = nullptr;
+  // derived (model_check_ready, conv1 of the residual blocks the graph runs behind a nearest-2x upsample): the upsample folded into the
+  // weights - four parity copies [q = 2 py + px][4 * Ipad / 64][Opad][64] of the 2x2 kernels, K-tile-major, contiguous (GemmArgs::Wuf)
+  const half_t* w_uf = nullptr;
 };
 struct LinW {  // fp16 [N][Kpad], fp32 bias [N] (nullptr when the reference passes use_bias=False)
   const half_t* w = nullptr;
@@ -252,6 +256,10 @@ struct GemmArgs {
   const half_t* A2 = nullptr; int lda2 = 0; int Cin1 = 0, Cin2 = 0;
   const half_t* Wt1 = nullptr; int ldw1 = 0;
   const half_t* Wt = nullptr; int ldw = 0;  // "W" operand [N][K]
+  // conv3x3, ups == 2 (upsample fold): the launch is DESCRIBED by Wt / ldw / w_kts / K = 9 * Cin of the original 3x3 weights, like ups == 1,
+  // and EXECUTES K = 4 * Cin on Wuf - the four parity copies of the folded 2x2 weights, each K-tile-major [4 * Cin / 64][N][64], contiguous
+  // (model.cpp ups_fold_host; gemm_ups_fold_ok is the eligibility rule, launch_gemm refuses everything else and writes nothing)
+  const half_t* Wuf = nullptr;
   int w_kts = 0;  // bytes from one 64-deep K tile of W to the next; 0 = 128 (row-major [N][K]).  K-tile-major [K/64][N][64]: ldw = 64, w_kts = N * 128
   int M = 0, N = 0, K = 0;
   int batch = 1; int64_t sA = 0, sW = 0, sC = 0, sR = 0;  // element strides per batch
@@ -271,6 +279,11 @@ struct GemmArgs {
   int rows_per_sample_hint = 0;
 };
 int launch_gemm(tsd_ctx* ctx, const GemmArgs& a);
+bool gemm_ups_fold_ok(const tsd_ctx* ctx, const GemmArgs& a);  // may this conv3x3 over a 2x-upsampled source run with ups = 2?
+// host fold of 3x3 weights [O][3][3][Ipad] (row pitch ldw >= 9 * Ipad, fp16 bits) into [4][O][2][2][Ipad]; returns the non-finite sums (model.cpp)
+int64_t ups_fold_host(const uint16_t* w, int O, int Ipad, int ldw, uint16_t* out);
+// ... and the same in the device layout GemmArgs::Wuf reads: per parity K-tile-major [4 * Ipad / 64][O][64], contiguous (Ipad % 64 == 0)
+int64_t ups_fold_pack_host(const uint16_t* w, int O, int Ipad, int ldw, uint16_t* out_tm);
 // the launch as a tsd_debug_gemm_* descriptor (TSD_GD_COUNT fields; api_ops.cpp)
 void gemm_describe(const tsd_ctx* ctx, const GemmArgs& a, int64_t* desc);
 // slices of the long-K split launches (K >= 8192, 16x16 level) for the graph being enqueued on this context; returns the previous value

@@ -68,8 +68,20 @@ int g_conv3x3(tsd_ctx* ctx, const Act& x, const ConvW& w, int stride, int pad, i
   }
   g.C = y; g.ldc = ldy;
   g.rows_per_sample_hint = Ho * Wo;
+  // Behind a nearest-2x upsample the nine taps of an output pixel read 2 x 2 source pixels: with the taps that share one summed at
+  // model_check_ready (ConvW::w_uf) the launch executes K = 4 Cin.  Model, options and the layer's shape decide - never the batch - so the
+  // planning pass and the real pass take the same branch.  A one-parity tile holds no 32-raster-row slab: no statistics from this epilogue
+  // (the consumer norm runs its own pass).
+  if (ups == 1 && w.w_uf && ctx->opt.ups_fold && gemm_ups_fold_ok(ctx, g)) {
+    g.ups = 2; g.Wuf = w.w_uf;
+    return launch_gemm(ctx, g);
+  }
   gn_emit(ctx, g, stat, Ho * Wo);
   return launch_gemm(ctx, g);
+}
+
+extern "C" int tsd_debug_set_ups_fold(tsd_ctx* ctx, int on) {
+  return ctx_set_option(ctx, &TsdOptions::ups_fold, on, 0, 1);
 }
 
 int g_linear(tsd_ctx* ctx, const CatSrc& a, int64_t M, const half_t* w, int ldw, int N, int K, const float* bias,

@@ -126,6 +126,12 @@ __global__ __launch_bounds__((WGM * WGN + LW) * 64, LW ? (WGM * WGN + LW) / 4 : 
   constexpr int NI = LW ? LW : NW;  // waves that issue DMA
   constexpr bool HX = CV == 1;  // conv variant: 1 = halo-x K order, 2 = fused 1x1 skip source (K runs on past the nine taps)
   constexpr bool SK = CV == 2;
+  // UF ("upsample fold", CV == 3): a 3x3 convolution of a nearest-2x upsampled source as four 2x2 convolutions of the source itself, one per
+  // output parity q = 2*py + px, with the taps that read the same source pixel summed into one weight on the host (model.cpp
+  // ups_fold_host): K = 4*Cin instead of 9*Cin.  Tile rows are parity-planar - row m = (b, q, yi, xi), S = Hs*Ws rows per plane, every
+  // tile inside ONE plane (the host checks S % 256 == 0) - so a block reads ONE of four contiguous K-tile-major weight copies, picked by a
+  // base offset; the epilogue scatters row m to output pixel (2*yi + py, 2*xi + px).
+  constexpr bool UF = CV == 3;
   static_assert(CV == 0 || CONV, "conv variants");
   static_assert(LW == 0 || (LW == 4 && !PP && !HX), "loader waves: one per SIMD, plain ring schedules only");
   constexpr int BM = WGM * FM * 16, BN = WGN * FN * 16;
@@ -183,6 +189,8 @@ __global__ __launch_bounds__((WGM * WGN + LW) * 64, LW ? (WGM * WGN + LW) / 4 : 
   const half_t* A0 = p.A0 + (long long)bz * p.sA;
   const half_t* A1 = p.A1 ? p.A1 + (long long)bz * p.sA : nullptr;
   const half_t* Wt = p.Wt + (long long)bz * p.sW;
+  const int uf_S = UF ? p.Hs * p.Ws : 1;
+  if constexpr (UF) Wt += (long long)((m0 / uf_S) & 3) * (p.K >> 6) * (p.w_kts >> 1);  // this tile's parity: its copy of the folded weights
   // Fused-skip sources as DIFFERENCES to the main ones, picked by mask arithmetic below.  Written as `c ? A0 : c2 ? A1 : A2`
   // inside the staging lambdas, hipcc turns the three by-reference captures into one load at a run-time offset into the closure
   // object; the closure then stays in memory, and with it every variable it refers to - 500-700 B of scratch per lane.
@@ -221,6 +229,13 @@ __global__ __launch_bounds__((WGM * WGN + LW) * 64, LW ? (WGM * WGN + LW) / 4 : 
       a_off[i] = ((unsigned)m * (unsigned)p.lda0 + cch * 8) * 2;
       a_off1[i] = ((unsigned)m * (unsigned)p.lda1 + cch * 8) * 2;
       a_pk[i] = 0;
+    } else if constexpr (UF) {
+      // source pixel of the plane's tap (0, 0) + 1: rows {yi - 1, yi} for py = 0, {yi, yi + 1} for py = 1; columns alike
+      const int b = m / (4 * uf_S), r4 = m - b * 4 * uf_S, q = r4 / uf_S, rem = r4 - q * uf_S;
+      const int yi = rem / p.Ws, xi = rem - yi * p.Ws;
+      a_pk[i] = (unsigned)(yi + (q >> 1)) | (unsigned)(xi + (q & 1)) << 11 | (ok ? (unsigned)b : 1023u) << 22;
+      a_off[i] = 0;
+      a_off1[i] = PAD_OFF;
     } else {
       const int hw = p.Ho * p.Wo;
       const int b = m / hw, rem = m - b * hw;
@@ -246,7 +261,7 @@ __global__ __launch_bounds__((WGM * WGN + LW) * 64, LW ? (WGM * WGN + LW) / 4 : 
   // conv: running (tap, channel-chunk) of the NEXT tile to stage
   const int cpt = CONV ? (p.Cin >> 6) : 1;
   const int cpt1 = SK ? (p.Cin1 >> 6) : 0, cpt2 = SK ? (p.Cin2 >> 6) : 0;  // fused 1x1 skip sources
-  const int ntaps = SK ? 9 + (cpt1 > 0) + (cpt2 > 0) : 9;
+  const int ntaps = SK ? 9 + (cpt1 > 0) + (cpt2 > 0) : (UF ? 4 : 9);
   int st_tap = kt0 / cpt, st_cc = kt0 - (kt0 / cpt) * cpt;
   if (SK && kt0 >= 9 * cpt) {  // a split-K slice that starts inside the skip segment
     st_tap = 9; st_cc = kt0 - 9 * cpt;
@@ -258,6 +273,17 @@ __global__ __launch_bounds__((WGM * WGN + LW) * 64, LW ? (WGM * WGN + LW) / 4 : 
 #pragma unroll
       for (int i = 0; i < A_PWX; i++) {
         const int iy = (int)(a_pk[i] & 2047u) - 1 + tap - 1, ix = (int)((a_pk[i] >> 11) & 2047u) - 1;
+        const unsigned b = a_pk[i] >> 22;
+        const bool ok = b != 1023u && (unsigned)iy < (unsigned)p.Hs && (unsigned)ix < (unsigned)p.Ws;
+        a_off1[i] = ok ? ((unsigned)(((int)b * p.Hs + iy) * p.Ws + ix) * (unsigned)p.lda0 + cch * 8) * 2 : PAD_OFF;
+      }
+      return;
+    }
+    if constexpr (UF) {  // tap = 2 * kh2 + kw2 of the plane's 2x2 kernel, on the source grid itself
+      const int kh = tap >> 1, kw = tap & 1;
+#pragma unroll
+      for (int i = 0; i < A_PW; i++) {
+        const int iy = (int)(a_pk[i] & 2047u) - 1 + kh, ix = (int)((a_pk[i] >> 11) & 2047u) - 1 + kw;
         const unsigned b = a_pk[i] >> 22;
         const bool ok = b != 1023u && (unsigned)iy < (unsigned)p.Hs && (unsigned)ix < (unsigned)p.Ws;
         a_off1[i] = ok ? ((unsigned)(((int)b * p.Hs + iy) * p.Ws + ix) * (unsigned)p.lda0 + cch * 8) * 2 : PAD_OFF;
@@ -807,6 +833,16 @@ __global__ __launch_bounds__((WGM * WGN + LW) * 64, LW ? (WGM * WGN + LW) / 4 : 
   // GEGLU / per-row bias exist for dense GEMMs only, the time-embedding row vector / upsampled residual for conv3x3 only
   const int epi = p.epi & (CONV ? ~(EPI_GEGLU | EPI_BIAS_M) : ~(EPI_ROWVEC | EPI_RES_UPS));
   const int nb = n0 + wn * BNw + g * (4 * FN);
+  // row of C that tile row m is stored to (UF: parity-planar row (b, q, yi, xi) -> output pixel (b, 2*yi + py, 2*xi + px))
+  auto c_row = [&](int m) -> long long {
+    if constexpr (UF) {
+      const int b = m / (4 * uf_S), r4 = m - b * 4 * uf_S, q = r4 / uf_S, rem = r4 - q * uf_S;
+      const int yi = rem / p.Ws, xi = rem - yi * p.Ws;
+      return ((long long)b * p.Ho + 2 * yi + (q >> 1)) * p.Wo + 2 * xi + (q & 1);
+    } else {
+      return m;
+    }
+  };
 
   // Coalesced path (every tile shape but the thin N <= 16 one, N % 8 == 0).  The MFMA layout leaves each lane with
   // 4*FN consecutive columns of one row, i.e. 8-byte pieces 8*FN bytes apart across the wave - store-issue bound
@@ -952,7 +988,7 @@ __global__ __launch_bounds__((WGM * WGN + LW) * 64, LW ? (WGM * WGN + LW) / 4 : 
             h8 o;
 #pragma unroll
             for (int j = 0; j < 8; j++) o[j] = (half_t)v[j];
-            *(h8*)((half_t*)p.C + (long long)bz * p.sC + (long long)m * p.ldc + n) = o;
+            *(h8*)((half_t*)p.C + (long long)bz * p.sC + c_row(m) * p.ldc + n) = o;
             if (gn_on) *(h8*)(ep + r * EPP + c * 8) = o;  // back into the slot just read (same-wave LDS ops are ordered)
           }
         }
@@ -1058,7 +1094,7 @@ __global__ __launch_bounds__((WGM * WGN + LW) * 64, LW ? (WGM * WGN + LW) / 4 : 
       for (int b = 0; b < FN; b++)
         if (nb + b * 4 < p.N) *(f4*)(cp + b * 4) = f4{v[b * 4], v[b * 4 + 1], v[b * 4 + 2], v[b * 4 + 3]};
     } else {
-      half_t* cp = (half_t*)p.C + (long long)bz * p.sC + (long long)m * p.ldc + nb;
+      half_t* cp = (half_t*)p.C + (long long)bz * p.sC + c_row(m) * p.ldc + nb;
 #pragma unroll
       for (int b = 0; b < FN; b++)
         if (nb + b * 4 < p.N) {
@@ -1135,10 +1171,27 @@ static int launch_cfg(tsd_ctx* ctx, const GemmK& k, int batch) {
 //  13  256x128   3      144 KiB   8 waves
 constexpr int N_GEMM_CFG = 56;
 
+// The upsample-fold variant (GemmK::ups == 2, CV = 3) exists for the tile configurations choose_cfg can return for a non-thin, unsplit
+// conv3x3 with N % 160 == 0; any other one is refused (launch_gemm's eligibility rule keeps the dispatcher inside this list)
+static int launch_ups_fold(tsd_ctx* ctx, const GemmK& k, int batch, int id) {
+  switch (id) {
+    case 0: return launch_cfg<2, 2, 4, 5, true, 2, false, 3>(ctx, k, batch);
+    case 1: return launch_cfg<2, 2, 2, 5, true, 2, false, 3>(ctx, k, batch);
+    case 5: return launch_cfg<2, 2, 4, 5, true, 3, false, 3>(ctx, k, batch);
+    case 6: return launch_cfg<2, 2, 2, 5, true, 4, false, 3>(ctx, k, batch);
+    case 7: return launch_cfg<2, 2, 2, 5, true, 3, false, 3>(ctx, k, batch);
+    case 51: return launch_cfg<4, 2, 4, 5, true, 3, false, 3, 4>(ctx, k, batch);
+    default: break;
+  }
+  TSD_FAIL(TSD_E_ARG, "gemm: tile configuration %d has no upsample-fold variant", id);
+}
+static bool ups_fold_cfg(int id) { return id == 0 || id == 1 || id == 5 || id == 6 || id == 7 || id == 51; }
+
 // SKV = 2 for a conv3x3 with a fused 1x1 skip source (GemmK::Cin1 > 0), else 0: the plain kernels carry none of its scalar state
 template <bool CONV, int SKV = 0>
 static int launch_by_id(tsd_ctx* ctx, const GemmK& k, int batch, int id) {
   if constexpr (CONV && SKV == 0) {
+    if (k.ups == 2) return launch_ups_fold(ctx, k, batch, id);
     if (k.Cin1 > 0) return launch_by_id<CONV, 2>(ctx, k, batch, id);
   }
   switch (id) {
@@ -1557,6 +1610,21 @@ extern "C" int tsd_debug_splitk_errors(tsd_ctx* ctx) {
   return v;
 }
 
+// Upsample fold (GemmArgs::ups == 2): may this conv3x3 over a nearest-2x upsampled source run as four parity-planar 2x2 convolutions?
+// Decided on the LAYER (source plane, channels, width, epilogue) and never on M: which kernel runs must not change with the batch.
+//  * stride 1, pad 1, no fused skip, no residual / statistics / fp32 epilogue (a one-parity tile holds no 32-raster-row slab);
+//  * Cin % 64 == 0 (whole K tiles per folded tap) and N % 160 == 0 (the tile family the variant is built for);
+//  * Hs * Ws % 256 == 0: every tile height the dispatcher can choose divides a parity plane;
+//  * no split-K for the executed problem (rows per sample, N, 4 * Cin).
+bool gemm_ups_fold_ok(const tsd_ctx* ctx, const GemmArgs& a) {
+  if (!a.conv || a.stride != 1 || a.pad != 1 || a.Cin1 || a.Cin2 || a.batch != 1 || a.Vt) return false;
+  if (a.epi & (EPI_RESIDUAL | EPI_RES_UPS | EPI_GNSTATS | EPI_OUT_F32)) return false;
+  if (a.Cin <= 0 || a.Cin % 64 || a.N % 160 || a.K != 9 * a.Cin) return false;
+  const long long S = (long long)a.Hs * a.Ws;
+  if (a.Hs <= 0 || a.Ws <= 0 || a.Hs >= 2040 || a.Ws >= 2040 || S % 256 || a.Ho != 2 * a.Hs || a.Wo != 2 * a.Ws || a.M <= 0 || a.M % (4 * S)) return false;
+  return splitk_plan(ctx->opt, a.M, a.N, 4 * a.Cin, a.batch, a.Ho * a.Wo, nullptr) == 1;
+}
+
 int launch_gemm(tsd_ctx* ctx, const GemmArgs& a) {
   if (a.M <= 0 || a.N <= 0 || a.K <= 0) TSD_FAIL(TSD_E_SHAPE, "gemm: empty problem M=%d N=%d K=%d", a.M, a.N, a.K);
   if (a.K % 64) TSD_FAIL(TSD_E_SHAPE, "gemm: K=%d must be a multiple of 64 (pad at pack time)", a.K);
@@ -1572,6 +1640,11 @@ int launch_gemm(tsd_ctx* ctx, const GemmArgs& a) {
         TSD_FAIL(TSD_E_ARG, "conv3x3: fused skip source (%d + %d channels) does not fit this convolution", a.Cin1, a.Cin2);
     }
     if (a.batch != 1) TSD_FAIL(TSD_E_ARG, "conv3x3: batch is folded into M");
+    if (a.ups == 2) {  // refused before anything is enqueued: the outputs stay as they were
+      if (!a.Wuf || !gemm_ups_fold_ok(ctx, a)) TSD_FAIL(TSD_E_ARG, "conv3x3: this launch cannot run the upsample fold (ups = 2)");
+      if (ctx->opt.force_cfg >= 0 && !ups_fold_cfg(ctx->opt.force_cfg))
+        TSD_FAIL(TSD_E_ARG, "conv3x3: tile configuration %d has no upsample-fold variant", ctx->opt.force_cfg);
+    } else if (a.ups < 0 || a.ups > 2) TSD_FAIL(TSD_E_ARG, "conv3x3: ups = %d", a.ups);
   } else {
     if (a.K0 % 64) TSD_FAIL(TSD_E_SHAPE, "gemm: concat split K0=%d must be a multiple of 64", a.K0);
   }
@@ -1598,7 +1671,8 @@ int launch_gemm(tsd_ctx* ctx, const GemmArgs& a) {
   // split-K workspace (arena: the planning pass sees the same allocation) and the per-context arrival flags
   float* sk_ws = nullptr;
   int sk_cfg = 0;
-  const int ways = ctx->opt.force_cfg < 0 ? splitk_plan(ctx->opt, a.M, a.N, a.K, a.batch, a.rows_per_sample_hint, &sk_cfg) : 1;
+  const bool uf = a.conv && a.ups == 2;  // runs K = 4 * Cin on the folded copies; the launch stays DESCRIBED (record, profile) as the 3x3 it computes
+  const int ways = uf ? 1 : ctx->opt.force_cfg < 0 ? splitk_plan(ctx->opt, a.M, a.N, a.K, a.batch, a.rows_per_sample_hint, &sk_cfg) : 1;
   const bool splitk = ways > 1;
   if (splitk) {
     const int BN = (a.N % 160 == 0) ? 160 : 128, BM = (sk_cfg == 7 || sk_cfg == 10 || sk_cfg == 6 || sk_cfg == 9) ? 64 : (sk_cfg == 51 ? 256 : 128);
@@ -1623,6 +1697,7 @@ int launch_gemm(tsd_ctx* ctx, const GemmArgs& a) {
   k.epi = a.epi; k.tiles_n = 0; k.out_scale = a.out_scale;
   k.w_kts = a.w_kts ? (unsigned)a.w_kts : 128u;
   if (a.w_kts && (a.ldw != 64 || a.w_kts < a.N * 128)) TSD_FAIL(TSD_E_ARG, "gemm: K-tile-major W needs ldw = 64 and a tile stride >= N * 128");
+  if (uf) { k.Wt = a.Wuf; k.ldw = 64; k.w_kts = (unsigned)a.N * 128u; k.K = 4 * a.Cin; }  // four K-tile-major copies [q][4 Cin / 64][N][64]
   k.gn_part = a.gn_part; k.gn_cpg = a.gn_groups > 0 ? a.N / a.gn_groups : 1; k.gn_G = a.gn_groups; k.gn_hw = a.gn_rows_per_sample;
   k.gn_nslab = a.gn_nslab;
   k.vt = a.Vt; k.vt_sB = a.vt_sB; k.vt_n0 = a.vt_n0; k.vt_ld = a.vt_ld; k.vt_S = a.vt_S;

@@ -3,6 +3,8 @@
 #include <math.h>
 #include <string.h>
 
+#include <vector>
+
 #include "model.h"
 
 bool attn_tail_weights_ok(const AttnW& w) {
@@ -84,6 +86,67 @@ extern "C" int64_t tsd_debug_dup_fold_host(const void* w, int rows, int taps, in
   return dup_fold_host((const uint16_t*)w, rows, taps, ldw, half, (uint16_t*)out, ldo);
 }
 
+// ---- upsample fold (ConvW::w_uf): a 3x3 convolution of a nearest-2x upsampled image as four 2x2 convolutions of the image itself ----------
+// Output pixel (2 yi + py, 2 xi + px) reads source rows {yi - 1, yi} through kernel rows {0}, {1, 2} when py = 0 and rows {yi, yi + 1} through
+// {0, 1}, {2} when py = 1; columns alike.  A group never straddles the border of the upsampled image, so its zero padding is the source's.
+// out[q = 2 py + px][o][kh2][kw2][c] = the sum of w[o][kh][kw][c] over the two groups.  Up to four fp16 values: an integer multiple of 2^-24
+// below 2^18, exact in double whatever the order; ONE rounding to fp16, nearest-even.  Returns how many sums are not finite.
+static inline int uf_lo(int parity, int k2) { return parity == 0 ? (k2 == 0 ? 0 : 1) : (k2 == 0 ? 0 : 2); }
+static inline int uf_hi(int parity, int k2) { return parity == 0 ? (k2 == 0 ? 0 : 2) : (k2 == 0 ? 1 : 2); }
+int64_t ups_fold_host(const uint16_t* w, int O, int Ipad, int ldw, uint16_t* out) {
+  // fp16 -> double through a table of all 65536 patterns (built once): the fold of the two production layers converts 50 M weights
+  static const std::vector<double> f64_of = [] {
+    std::vector<double> t(65536);
+    for (int i = 0; i < 65536; i++) t[i] = f16_bits_to_f64((uint16_t)i);
+    return t;
+  }();
+  int64_t bad = 0;
+  for (int q = 0; q < 4; q++)
+    for (int o = 0; o < O; o++)
+      for (int t = 0; t < 4; t++) {
+        const int py = q >> 1, px = q & 1, kh2 = t >> 1, kw2 = t & 1;
+        uint16_t* d = out + (((size_t)q * O + o) * 4 + t) * Ipad;
+        const uint16_t* s = w + (size_t)o * ldw;
+        for (int c = 0; c < Ipad; c++) {
+          double sum = 0.0;
+          bool first = true;  // (the first term is taken as it is: a lone -0 stays -0)
+          for (int kh = uf_lo(py, kh2); kh <= uf_hi(py, kh2); kh++)
+            for (int kw = uf_lo(px, kw2); kw <= uf_hi(px, kw2); kw++) {
+              const double v = f64_of[s[(size_t)(kh * 3 + kw) * Ipad + c]];
+              sum = first ? v : sum + v;
+              first = false;
+            }
+          d[c] = f64_to_f16_bits_rne(sum);
+          bad += (d[c] & 0x7C00) == 0x7C00;
+        }
+      }
+  return bad;
+}
+// the device layout of the fold: per parity the [O][4 * Ipad] matrix K-tile-major, [4 * Ipad / 64][O][64] (what launch_pack_tile_major makes
+// of it), the four copies contiguous.  Ipad % 64 == 0.
+int64_t ups_fold_pack_host(const uint16_t* w, int O, int Ipad, int ldw, uint16_t* out_tm) {
+  const int K = 4 * Ipad;
+  std::vector<uint16_t> f((size_t)4 * O * K);
+  const int64_t bad = ups_fold_host(w, O, Ipad, ldw, f.data());
+  for (int q = 0; q < 4; q++)
+    for (int kt = 0; kt < K / 64; kt++)
+      for (int o = 0; o < O; o++)
+        memcpy(out_tm + (((size_t)q * (K / 64) + kt) * O + o) * 64, f.data() + ((size_t)q * O + o) * K + (size_t)kt * 64, 128);
+  return bad;
+}
+
+extern "C" int64_t tsd_debug_ups_fold_host(const void* w, int O, int Ipad, int ldw, void* out) {
+  if (!w || !out || O <= 0 || Ipad <= 0 || ldw < 9 * Ipad) TSD_FAIL(TSD_E_ARG, "ups_fold_host: bad argument");
+  return ups_fold_host((const uint16_t*)w, O, Ipad, ldw, (uint16_t*)out);
+}
+
+// residual blocks of the 23-layer graph that read their input through the nearest-2x upsample (g_unet_forward: res(15, .., 1), res(20, .., 1))
+static const int UPS_RES_BLOCKS[2] = {14, 19};
+// structure only: a 3x3 conv1 over the block's own channels, whole K tiles per tap, the 160-column tile family
+static bool ups_fold_weights_ok(const ResW& r) {
+  return r.conv1.w && r.conv1.k == 3 && r.conv1.Ipad > 0 && r.conv1.Ipad % 64 == 0 && r.conv1.Ipad == r.cin && r.conv1.Opad % 160 == 0;
+}
+
 // parameters changed: derived buffers are stale until the next model_check_ready()
 static void model_invalidate_derived(tsd_model* m) {
   m->ready = false;
@@ -92,7 +155,7 @@ static void model_invalidate_derived(tsd_model* m) {
   for (auto& a : m->unet.attn) { a.tail_stream = nullptr; a.head_stream = nullptr; a.fold_w = nullptr; a.fold_w_tm = nullptr; a.fold_b = nullptr; }
   m->unet.conv_in_im2col = nullptr;
   m->vae.conv_in_im2col = nullptr;
-  for (auto& r : m->unet.res) { r.conv1.w_tm = nullptr; r.conv2.w_tm = nullptr; }
+  for (auto& r : m->unet.res) { r.conv1.w_tm = nullptr; r.conv2.w_tm = nullptr; r.conv1.w_uf = nullptr; }
   m->unet.conv4.w_tm = nullptr; m->unet.conv7.w_tm = nullptr; m->unet.kproj_all.w_tm = nullptr;
   for (auto& cv : m->unet.conv) cv.w_tm = nullptr;
   for (auto& a : m->unet.attn) {
@@ -329,9 +392,20 @@ static int model_build_derived(tsd_model* m) {
         fold.push_back(&a);
         fold_b += 2 * ((((size_t)a.C * 5 * a.C * 2) + 255) & ~size_t(255)) + ((((size_t)a.C * 4) + 255) & ~size_t(255));
       }
-  if (el.empty() && !cin_ok && tm.empty() && tml.empty() && !kv && fold.empty() && !dup) return TSD_OK;
+  // conv1 of the blocks behind a nearest-2x upsample: the upsample folded into four 2x2 parity kernels (ConvW::w_uf).  Built whatever
+  // TSD_UPS_FOLD says - the option is read per forward, by the graph - and keyed on structure only, never on a batch or a latent size.
+  std::vector<ConvW*> uf;
+  size_t uf_b = 0;
+  if (!is_full_unet_kind(m->kind))
+    for (int bi : UPS_RES_BLOCKS)
+      if (bi < (int)m->unet.res.size() && ups_fold_weights_ok(m->unet.res[bi])) {
+        ConvW* c = &m->unet.res[bi].conv1;
+        uf.push_back(c);
+        uf_b += (((size_t)16 * c->Opad * c->Ipad * 2) + 255) & ~size_t(255);
+      }
+  if (el.empty() && !cin_ok && tm.empty() && tml.empty() && !kv && fold.empty() && !dup && uf.empty()) return TSD_OK;
   const size_t tail_b = (attn_tail_stream_bytes() + 255) & ~size_t(255), head_b = (attn_head_stream_bytes() + 255) & ~size_t(255);
-  const size_t each = tail_b + head_b, need = each * el.size() + cin_b + tm_b + fold_b + dup_w1_b + dup_sk_b + dup_tm_b;
+  const size_t each = tail_b + head_b, need = each * el.size() + cin_b + tm_b + fold_b + dup_w1_b + dup_sk_b + dup_tm_b + uf_b;
   HIP_TRY(hipSetDevice(ctx->device));
   if (m->derived_bytes < need) {
     if (m->derived) HIP_TRY(hipFree(m->derived));
@@ -438,6 +512,32 @@ static int model_build_derived(tsd_model* m) {
         if (r == TSD_OK) { m->unet.res_dup = d; m->unet.res_dup_on = true; }
       }
     }
+    for (size_t i = 0; i < uf.size() && r == TSD_OK; i++) {
+      // host-side and exact like the duplicate-concat fold above; a sum that leaves fp16 must not be silent
+      ConvW* c = uf[i];
+      const size_t nsrc = (size_t)c->Opad * 9 * c->Ipad, ndst = (size_t)16 * c->Opad * c->Ipad;
+      std::vector<uint16_t> src(nsrc), dst(ndst);
+      half_t* dev = (half_t*)(m->derived + off);
+      off += ((ndst * 2) + 255) & ~size_t(255);
+      hipError_t e = hipStreamSynchronize(ctx->stream);
+      if (e == hipSuccess) e = hipMemcpy(src.data(), c->w, nsrc * 2, hipMemcpyDeviceToHost);
+      int64_t bad = 0;
+      if (e == hipSuccess) {
+        bad = ups_fold_pack_host(src.data(), c->Opad, c->Ipad, 9 * c->Ipad, dst.data());
+        e = hipMemcpyAsync(dev, dst.data(), ndst * 2, hipMemcpyHostToDevice, ctx->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+      }
+      if (e != hipSuccess) {
+        tsd_set_error("upsample fold: %s", hipGetErrorString(e));
+        r = TSD_E_HIP;
+      } else if (bad) {
+        tsd_set_error("residual block behind an upsample (%d -> %d): %lld folded conv1 weights are not finite (a sum of up to four taps leaves fp16)",
+                      c->Ipad, c->Opad, (long long)bad);
+        r = TSD_E_NONFINITE;
+      } else {
+        c->w_uf = dev;
+      }
+    }
   }
   // A folded weight is a product of two weight matrices rounded to fp16 once: one that leaves fp16 (or a non-finite bias) must not be
   // silent.  Host-side scan, once per build of the derived buffers.
@@ -516,6 +616,21 @@ extern "C" int tsd_debug_model_dup_fold(tsd_model* m, void* conv1_w, void* skip_
   if (conv1_w) HIP_TRY(hipMemcpy(conv1_w, d.conv1.w, (size_t)d.conv1.Opad * 9 * d.conv1.Ipad * 2, hipMemcpyDeviceToHost));
   if (skip_w) HIP_TRY(hipMemcpy(skip_w, d.skip.w, (size_t)d.skip.Opad * d.skip.Ipad * 2, hipMemcpyDeviceToHost));
   return d.cin;
+}
+
+// Debug entry: the device copy of residual block `block`'s folded conv1 (index into the UNet's layers) - four parity copies, each
+// [4 * Ipad / 64][Opad][64] fp16; returns Ipad, 0 when the block does not fold
+extern "C" int tsd_debug_model_ups_fold(tsd_model* m, int block, void* out) {
+  if (!m) TSD_FAIL(TSD_E_ARG, "NULL model");
+  if (!is_diffusion_kind(m->kind) || block < 0 || block >= (int)m->unet.res.size())
+    TSD_FAIL(TSD_E_ARG, "model_ups_fold: no residual block %d in this model", block);
+  HIP_TRY(hipSetDevice(m->ctx->device));
+  TSD_TRY(model_check_ready(m));
+  const ConvW& c = m->unet.res[block].conv1;
+  if (!c.w_uf) return 0;
+  HIP_TRY(hipStreamSynchronize(m->ctx->stream));
+  if (out) HIP_TRY(hipMemcpy(out, c.w_uf, (size_t)16 * c.Opad * c.Ipad * 2, hipMemcpyDeviceToHost));
+  return c.Ipad;
 }
 
 ConvW model_conv(const tsd_model* m, const std::string& prefix) {

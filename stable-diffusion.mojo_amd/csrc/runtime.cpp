@@ -24,6 +24,7 @@ void options_from_env(TsdOptions& o) {
   o.conv_in_im2col = env_int("TSD_CONV_IN_IM2COL", o.conv_in_im2col);
   o.chain = env_int("TSD_CHAIN", o.chain) ? 1 : 0;
   o.fold_out = env_int("TSD_FOLD_OUT", o.fold_out) ? 1 : 0;
+  o.ups_fold = env_int("TSD_UPS_FOLD", o.ups_fold) ? 1 : 0;
   o.fold_dup = env_int("TSD_FOLD_DUP", o.fold_dup) ? 1 : 0;
   o.session_hoist = env_int("TSD_SESSION_HOIST", o.session_hoist) ? 1 : 0;
   o.conv_w_tm_mib = env_int("TSD_CONV_W_TM", o.conv_w_tm_mib);

@@ -156,6 +156,9 @@ def _declare(l):
         "tsd_debug_model_fold": ([vp, i, vp, fp], i),
         "tsd_debug_model_dup_fold": ([vp, vp, vp], i),
         "tsd_debug_dup_fold_host": ([vp, i, i, i, i, vp, i], i64),
+        "tsd_debug_ups_fold_host": ([vp, i, i, i, vp], i64),
+        "tsd_debug_model_ups_fold": ([vp, i, vp], i),
+        "tsd_debug_set_ups_fold": ([vp, i], i),
         "tsd_debug_gemm_run": ([vp, C.POINTER(i64), i, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)], i),
         "tsd_debug_norm_run": ([vp, C.POINTER(i64), i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)], i),
         "tsd_debug_gn_path_counts": ([vp, C.POINTER(i64), i, i], i),
