@@ -475,6 +475,53 @@ enum tsd_norm_info { TSD_NI_CHANGED = 0, TSD_NI_NSLAB, TSD_NI_OWN_PASS, TSD_NI_P
  * status is the return value). */
 int tsd_debug_norm_run(tsd_ctx* ctx, const int64_t* desc, int n, const void* const* host_in, void* const* host_out, int64_t* ext,
                        int64_t* info);
+/* ---- attention-core / row-softmax launch descriptors (test infrastructure: tests/attn_ref.py holds flash_attn_kernel<40,1>, <40,2>,
+ * <80,1>, <160,1>, flash_attn8_kernel<40> and the k_softmax_rows kernels to an fp64 reference, element-wise) ----
+ * One int64 per argument of launch_flash_attention: pitches and batch strides in elements, SCALE the bits of a float.  KERNEL: the d = 40
+ * kernel mode of tsd_debug_set_attn_qb for this call (0 = by shape); DIAG: tsd_debug_set_attn_diag for this call.  Both are restored.
+ * softmax_rows mode: ROWS rows of COLS columns at pitch LD; DTYPE 0 = fp32 (launch_softmax_rows_f32: dense, LD == COLS, X -> O), 1 = fp16
+ * in place (launch_softmax_rows_f16; with CAUSAL > 0 launch_softmax_rows_f16_causal, period CAUSAL, columns [kept, ZERO_TO) zeroed).
+ *
+ * The V^T pad-column contract.  The kernels stream V^T in 8-column chunks and the last key tile reads every chunk that starts below
+ * Skv = min(round_up(Sk, 8), ldvt): columns [Sk, Skv) reach the P.V MFMA with P = 0, and 0 x NaN = NaN, so they must hold FINITE values
+ * (columns >= Skv, the K pitch gap and K rows >= Sk are never read).  Every producer of a V^T operand writes them (csrc/, read for this):
+ *   - cross-attention, Sk = T (77), pitch Tp = round_up(T, 8).  The context is converted by launch_f32_to_f16_rows with rows_dst = Tp,
+ *     which writes rows [T, Tp) as zeros (kernels_elementwise.hip k_f32_to_f16_rows; called at api_ops.cpp:482 and :604,
+ *     api_model.cpp:56 and :339 - the session's context).  Every V^T GEMM then computes all Tp columns from those rows: the swapped-operand
+ *     GEMMs with N = Tp (api_ops.cpp:489, graph.cpp:276-281 and :474-479) and the fused K | V^T GEMM over M = B * Tp rows with vt_S = Tp
+ *     (graph.cpp:462-468, which also builds the session's hoisted context V^T, api_model.cpp:212).  Columns [T, Tp) hold W_v . 0 (+ b_v):
+ *     finite, whatever the arena held.
+ *   - self-attention, Sk = S = H * W.  The fused q | k | V^T GEMM (graph.cpp:236-242, :391-397) and the fused block head (graph.cpp:217-225)
+ *     run only where Sp == S (no pad columns).  Otherwise g_unet_attn zeroes the whole V^T buffer before the swapped-operand GEMM writes its
+ *     S columns (graph.cpp:232); tsd_self_attention_f32 and the VAE block refuse T % 8 != 0 (api_ops.cpp:435, graph.cpp:415).
+ * No path leaves arena contents there.  tests/test_gpu_attn_ref.py runs the core with 0 and with +-60000 in those columns (same bits) and
+ * tsd_cross_attention_f32 at T = 77 on an arena filled with an fp16 NaN pattern and with zeros (same bits, finite). */
+enum tsd_attn_desc_field {
+  TSD_AD_VERSION = 0, TSD_AD_MODE, TSD_AD_B, TSD_AD_H, TSD_AD_D, TSD_AD_SQ, TSD_AD_SK, TSD_AD_LDQ, TSD_AD_LDK, TSD_AD_LDVT, TSD_AD_LDO,
+  TSD_AD_SQB, TSD_AD_SKB, TSD_AD_SVTB, TSD_AD_SOB, TSD_AD_SCALE, TSD_AD_KERNEL, TSD_AD_DIAG,
+  TSD_AD_ROWS, TSD_AD_COLS, TSD_AD_LD, TSD_AD_DTYPE, TSD_AD_CAUSAL, TSD_AD_ZERO_TO,
+  TSD_AD_COUNT
+};
+#define TSD_AD_VERSION_1 1
+enum tsd_attn_mode { TSD_AM_ATTN = 0, TSD_AM_SOFTMAX_ROWS };
+/* Operand slots: inputs Q [B][Sq][ldq], K [B][Sk][ldk], V^T [B][H*d][ldvt] (fp16), X (softmax_rows input: fp32, or the fp16 rows the
+ * launch overwrites); output O (attention: [B][Sq][ldo] fp16; softmax_rows: the rows, in X's type and layout). */
+enum tsd_attn_operand { TSD_AO_Q = 0, TSD_AO_K, TSD_AO_VT, TSD_AO_X, TSD_AO_O, TSD_AO_COUNT };
+enum tsd_attn_kernel { TSD_AK_NONE = 0, TSD_AK_40_1, TSD_AK_40_2, TSD_AK_40_8W, TSD_AK_80, TSD_AK_160 };
+/* info: guard / pitch-gap elements the launch changed; the kernel that ran (tsd_attn_kernel; softmax_rows: 1 k_softmax_rows<float>,
+ * 2 k_softmax_rows<half_t>, 3 / 4 k_softmax_rows_h8<1> / <2>); workgroups that took the exact repeat in this launch; the diag and xcd_map
+ * values passed to the kernel. */
+enum tsd_attn_info { TSD_AI_CHANGED = 0, TSD_AI_KERNEL, TSD_AI_EXACT_WGS, TSD_AI_DIAG, TSD_AI_XCD_MAP, TSD_AI_COUNT };
+/* Run the launch described by desc (n >= TSD_AD_COUNT fields) on caller operands in their device layout (host_in[TSD_AO_Q .. TSD_AO_X],
+ * NULL for unused slots) through launch_flash_attention / launch_softmax_rows_* and return its output (host_out[0]).  host_in == NULL only
+ * sizes (ctx may be NULL, no device is touched): ext[TSD_AO_COUNT] receives every slot's extent (0 = unused) and, when info is given,
+ * info[TSD_AI_KERNEL / DIAG / XCD_MAP] what the dispatcher chooses under the default options (with the descriptor's KERNEL and DIAG).  A
+ * descriptor that cannot be sized is refused before any launch; the shapes the launchers refuse (head dimension, misaligned pitches, empty
+ * sequence: sized as one row) are sized and left to them.  Every operand sits between 4 KiB guard bands of a NaN pattern and O is
+ * pre-filled with it (fp16 softmax_rows: with X); the output is returned even when the launch is refused (its status is the return
+ * value). */
+int tsd_debug_attn_run(tsd_ctx* ctx, const int64_t* desc, int n, const void* const* host_in, void* const* host_out, int64_t* ext,
+                       int64_t* info);
 /* GroupNorm launches enqueued on this context since the last reset, per statistics path: counts[0] all, [1] own statistics pass,
  * [2] one producer table finished inside the apply blocks, [3] one producer table finished by the k_gn_finalize launch,
  * [4] k_gn_prereduce, [5] composite accepted, [6] k_gn_finalize launches (any source), [7] composites offered.  n >= 8; reset != 0

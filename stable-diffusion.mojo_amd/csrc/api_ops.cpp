@@ -1085,6 +1085,158 @@ extern "C" int tsd_debug_norm_run(tsd_ctx* ctx, const int64_t* desc, int n, cons
   return r;
 }
 
+// ---- attention core / row softmax on caller operands (tests/attn_ref.py holds every kernel to an fp64 reference) ---------------------
+namespace {
+int ad_elem_bytes(int slot, const int64_t* d) {
+  return d[TSD_AD_MODE] == TSD_AM_SOFTMAX_ROWS && d[TSD_AD_DTYPE] == 0 && (slot == TSD_AO_X || slot == TSD_AO_O) ? 4 : 2;
+}
+// Element extent of every operand the described launch reads or writes.  An empty sequence is sized as one row (the launcher refuses it).
+int ad_extents(const int64_t* d, int64_t* e) {
+  for (int i = 0; i < TSD_AO_COUNT; i++) e[i] = 0;
+#define AD_REQ(cond) \
+  if (!(cond)) TSD_FAIL(TSD_E_ARG, "attn_run: descriptor cannot be sized (%s)", #cond)
+  AD_REQ(d[TSD_AD_VERSION] == TSD_AD_VERSION_1);
+  const int64_t mode = d[TSD_AD_MODE], lim = 1LL << 28;
+  AD_REQ(mode == TSD_AM_ATTN || mode == TSD_AM_SOFTMAX_ROWS);
+  if (mode == TSD_AM_ATTN) {
+    const int64_t B = d[TSD_AD_B], H = d[TSD_AD_H], hd = d[TSD_AD_D];
+    const int64_t Sq = std::max<int64_t>(d[TSD_AD_SQ], 1), Sk = std::max<int64_t>(d[TSD_AD_SK], 1);
+    AD_REQ(B > 0 && B <= 4096 && H > 0 && H <= 4096 && hd > 0 && hd <= 4096 && H * hd <= 65536);
+    AD_REQ(d[TSD_AD_SQ] >= 0 && d[TSD_AD_SK] >= 0 && Sq <= (1 << 20) && Sk <= (1 << 20));
+    AD_REQ(d[TSD_AD_KERNEL] >= 0 && d[TSD_AD_KERNEL] <= 3 && (d[TSD_AD_DIAG] == 0 || d[TSD_AD_DIAG] == 1));
+    const int64_t C = H * hd;
+    for (int f : {TSD_AD_LDQ, TSD_AD_LDK, TSD_AD_LDO}) AD_REQ(d[f] >= C && d[f] <= (1 << 20));
+    AD_REQ(d[TSD_AD_LDVT] >= Sk && d[TSD_AD_LDVT] <= (1 << 21));
+    const int64_t Skv = std::min((Sk + 7) / 8 * 8, d[TSD_AD_LDVT]);
+    AD_REQ(d[TSD_AD_SQB] >= Sq * d[TSD_AD_LDQ] && d[TSD_AD_SKB] >= Sk * d[TSD_AD_LDK] && d[TSD_AD_SVTB] >= C * d[TSD_AD_LDVT] &&
+           d[TSD_AD_SOB] >= Sq * d[TSD_AD_LDO]);
+    for (int f : {TSD_AD_SQB, TSD_AD_SKB, TSD_AD_SVTB, TSD_AD_SOB}) AD_REQ(d[f] < lim);
+    e[TSD_AO_Q] = (B - 1) * d[TSD_AD_SQB] + (Sq - 1) * d[TSD_AD_LDQ] + C;
+    e[TSD_AO_K] = (B - 1) * d[TSD_AD_SKB] + (Sk - 1) * d[TSD_AD_LDK] + C;
+    e[TSD_AO_VT] = (B - 1) * d[TSD_AD_SVTB] + (C - 1) * d[TSD_AD_LDVT] + Skv;
+    e[TSD_AO_O] = (B - 1) * d[TSD_AD_SOB] + (Sq - 1) * d[TSD_AD_LDO] + C;
+  } else {
+    const int64_t rows = d[TSD_AD_ROWS], cols = d[TSD_AD_COLS], ld = d[TSD_AD_LD], zt = d[TSD_AD_ZERO_TO];
+    AD_REQ(rows > 0 && rows <= (1 << 20) && cols > 0 && cols <= (1 << 20) && ld >= cols && ld <= (1 << 20));
+    AD_REQ(d[TSD_AD_DTYPE] == 0 || d[TSD_AD_DTYPE] == 1);
+    AD_REQ(d[TSD_AD_CAUSAL] >= 0 && d[TSD_AD_CAUSAL] <= (1 << 20) && zt >= 0);
+    if (d[TSD_AD_DTYPE] == 0) AD_REQ(ld == cols && d[TSD_AD_CAUSAL] == 0 && zt == 0);  // launch_softmax_rows_f32 is dense and never causal
+    if (d[TSD_AD_CAUSAL] == 0) AD_REQ(zt == 0);
+    AD_REQ(zt <= ld);  // a wider ZERO_TO would be written outside the operand; launch_softmax_rows_f16_causal refuses it as well
+    e[TSD_AO_X] = e[TSD_AO_O] = (rows - 1) * ld + std::max(cols, zt);
+  }
+  for (int s = 0; s < TSD_AO_COUNT; s++) AD_REQ(e[s] >= 0 && e[s] <= lim);
+#undef AD_REQ
+  return TSD_OK;
+}
+struct AdBufs {
+  char* p[TSD_AO_COUNT] = {};
+  ~AdBufs() { for (char* q : p) if (q) (void)hipFree(q); }
+};
+}  // namespace
+
+extern "C" int tsd_debug_attn_run(tsd_ctx* ctx, const int64_t* desc, int n, const void* const* host_in, void* const* host_out,
+                                  int64_t* ext, int64_t* info) {
+  NOTNULL(desc); NOTNULL(ext);
+  if (n < TSD_AD_COUNT) TSD_FAIL(TSD_E_ARG, "attn_run: %d descriptor fields", n);
+  TSD_TRY(ad_extents(desc, ext));
+  const int64_t* d = desc;
+  const bool attn = d[TSD_AD_MODE] == TSD_AM_ATTN;
+  if (info) for (int i = 0; i < TSD_AI_COUNT; i++) info[i] = 0;
+  if (!host_in) {  // sizing only: no context or device needed; the dispatcher's choice under the default options
+    if (info && attn && attn_fused_supported((int)d[TSD_AD_D]) && d[TSD_AD_SQ] > 0 && d[TSD_AD_SK] > 0) {
+      TsdOptions o;
+      o.attn_qb_force = (int)d[TSD_AD_KERNEL]; o.attn_diag = (int)d[TSD_AD_DIAG];
+      const AttnPlan p = attn_plan(o, (int)d[TSD_AD_B], (int)d[TSD_AD_H], (int)d[TSD_AD_D], (int)d[TSD_AD_SQ], (int)d[TSD_AD_SK]);
+      info[TSD_AI_KERNEL] = p.kernel; info[TSD_AI_DIAG] = p.diag; info[TSD_AI_XCD_MAP] = p.xcd_map;
+    }
+    return TSD_OK;
+  }
+  NOTNULL(ctx); NOTNULL(host_out); NOTNULL(info);
+  const bool inplace = !attn && d[TSD_AD_DTYPE] == 1;
+  for (int s = 0; s < TSD_AO_COUNT; s++) {
+    if (!ext[s]) continue;
+    if (s < TSD_AO_O ? !host_in[s] : !host_out[0]) TSD_FAIL(TSD_E_ARG, "attn_run: operand slot %d is NULL", s);
+  }
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipStream_t st = ctx->stream;
+  AdBufs bufs;
+  for (int s = 0; s < TSD_AO_COUNT; s++) {
+    if (!ext[s]) continue;
+    const int es = ad_elem_bytes(s, d);
+    const size_t bytes = 2 * GD_GUARD + (size_t)ext[s] * es;
+    HIP_TRY(hipMalloc((void**)&bufs.p[s], bytes));
+    if (es == 2) HIP_TRY(hipMemsetD16Async((hipDeviceptr_t)bufs.p[s], GD_NAN16, bytes / 2, st));
+    else HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)bufs.p[s], (int)GD_NAN32, bytes / 4, st));
+    const void* src = s < TSD_AO_O ? host_in[s] : (inplace ? host_in[TSD_AO_X] : nullptr);  // fp16 rows are overwritten in place: O starts as X
+    if (src) HIP_TRY(hipMemcpyAsync(bufs.p[s] + GD_GUARD, src, (size_t)ext[s] * es, hipMemcpyHostToDevice, st));
+  }
+  auto at = [&](int s) -> void* { return bufs.p[s] ? (void*)(bufs.p[s] + GD_GUARD) : nullptr; };
+  int exact0 = 0, exact1 = 0;
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipMemcpy(&exact0, ctx->status + 2, sizeof(int), hipMemcpyDeviceToHost));
+  const int prev_force = ctx->opt.attn_qb_force, prev_diag = ctx->opt.attn_diag;
+  ctx->attn_last = AttnPlan();
+  int r;
+  if (attn) {
+    ctx->opt.attn_qb_force = (int)d[TSD_AD_KERNEL]; ctx->opt.attn_diag = (int)d[TSD_AD_DIAG];
+    AttnArgs a;
+    a.Q = (const half_t*)at(TSD_AO_Q); a.ldq = (int)d[TSD_AD_LDQ]; a.sQ = d[TSD_AD_SQB];
+    a.K = (const half_t*)at(TSD_AO_K); a.ldk = (int)d[TSD_AD_LDK]; a.sK = d[TSD_AD_SKB];
+    a.Vt = (const half_t*)at(TSD_AO_VT); a.ldvt = (int)d[TSD_AD_LDVT]; a.sVt = d[TSD_AD_SVTB];
+    a.O = (half_t*)at(TSD_AO_O); a.ldo = (int)d[TSD_AD_LDO]; a.sO = d[TSD_AD_SOB];
+    a.B = (int)d[TSD_AD_B]; a.H = (int)d[TSD_AD_H]; a.d = (int)d[TSD_AD_D]; a.Sq = (int)d[TSD_AD_SQ]; a.Sk = (int)d[TSD_AD_SK];
+    a.scale = nd_float(d[TSD_AD_SCALE]);
+    r = run_planned(ctx, [&]() -> int { return launch_flash_attention(ctx, a); });
+    ctx->opt.attn_qb_force = prev_force; ctx->opt.attn_diag = prev_diag;
+  } else {
+    const int64_t rows = d[TSD_AD_ROWS];
+    const int cols = (int)d[TSD_AD_COLS], ld = (int)d[TSD_AD_LD];
+    r = run_planned(ctx, [&]() -> int {
+      if (d[TSD_AD_DTYPE] == 0) return launch_softmax_rows_f32(ctx, (const float*)at(TSD_AO_X), rows, cols, (float*)at(TSD_AO_O));
+      if (d[TSD_AD_CAUSAL] > 0)
+        return launch_softmax_rows_f16_causal(ctx, (half_t*)at(TSD_AO_O), rows, cols, ld, (int)d[TSD_AD_CAUSAL], (int)d[TSD_AD_ZERO_TO]);
+      return launch_softmax_rows_f16(ctx, (half_t*)at(TSD_AO_O), rows, cols, ld);
+    });
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipMemcpy(&exact1, ctx->status + 2, sizeof(int), hipMemcpyDeviceToHost));
+  info[TSD_AI_KERNEL] = attn ? ctx->attn_last.kernel : ctx->attn_last.softmax;
+  info[TSD_AI_DIAG] = ctx->attn_last.diag; info[TSD_AI_XCD_MAP] = ctx->attn_last.xcd_map;
+  info[TSD_AI_EXACT_WGS] = exact1 - exact0;
+  int64_t changed = 0;
+  for (int s = 0; s < TSD_AO_COUNT; s++) {  // inputs too: the launch writes none of them
+    if (!ext[s]) continue;
+    const int es = ad_elem_bytes(s, d);
+    const size_t bytes = 2 * GD_GUARD + (size_t)ext[s] * es;
+    std::vector<char> got(bytes);
+    HIP_TRY(hipMemcpy(got.data(), bufs.p[s], bytes, hipMemcpyDeviceToHost));
+    const int64_t g0 = (int64_t)(GD_GUARD / es), total = (int64_t)(bytes / es);
+    const char* x0 = inplace ? (const char*)host_in[TSD_AO_X] : nullptr;
+    for (int64_t i = 0; i < total; i++) {
+      const int64_t j = i - g0;
+      const bool inside = j >= 0 && j < ext[s];
+      if (inside && s < TSD_AO_O) continue;  // input payload
+      if (inside && attn) {                  // logical element of O: [b][q][c < H*d]
+        const int64_t jb = j % d[TSD_AD_SOB], b = j / d[TSD_AD_SOB];
+        if (b < d[TSD_AD_B] && jb / d[TSD_AD_LDO] < d[TSD_AD_SQ] && jb % d[TSD_AD_LDO] < d[TSD_AD_H] * d[TSD_AD_D]) continue;
+      }
+      if (inside && !attn) {
+        if (j % d[TSD_AD_LD] < std::max(d[TSD_AD_COLS], d[TSD_AD_ZERO_TO])) continue;
+        if (x0) {  // a pitch gap of rows processed in place keeps what the caller put there
+          if (memcmp(&got[(size_t)i * 2], x0 + (size_t)j * 2, 2)) changed++;
+          continue;
+        }
+      }
+      const bool same = es == 2 ? memcmp(&got[(size_t)i * 2], &GD_NAN16, 2) == 0 : memcmp(&got[(size_t)i * 4], &GD_NAN32, 4) == 0;
+      if (!same) changed++;
+    }
+    if (s == TSD_AO_O) memcpy(host_out[0], &got[GD_GUARD], (size_t)ext[s] * es);
+  }
+  info[TSD_AI_CHANGED] = changed;
+  return r;
+}
+
 extern "C" int tsd_debug_gn_path_counts(tsd_ctx* ctx, int64_t* counts, int n, int reset) {
   NOTNULL(ctx); NOTNULL(counts);
   if (n < 8) TSD_FAIL(TSD_E_ARG, "gn_path_counts: %d slots (8 needed)", n);

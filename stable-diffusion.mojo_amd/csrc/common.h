@@ -104,6 +104,16 @@ struct GnPlan {
 };
 GnPlan gn_plan(const TsdOptions& opt, int HW, int C, int groups, const float* pre_part, int pre_nslab, const GnComposite* comp);
 
+// Host-side plan of one attention-core launch (kernels_attn.hip attn_plan): the kernel launch_flash_attention picks and the switches it
+// passes to it.  launch_flash_attention acts on it and leaves it in tsd_ctx::attn_last; tsd_debug_attn_run reports it.  `softmax` is
+// set by the launch_softmax_rows_* launchers instead (1 k_softmax_rows<float>, 2 k_softmax_rows<half_t>, 3 / 4 k_softmax_rows_h8<1> / <2>).
+struct AttnPlan {
+  int kernel = 0;   // tsd_attn_kernel: 1 flash_attn_kernel<40,1>, 2 <40,2>, 3 flash_attn8_kernel<40>, 4 <80,1>, 5 <160,1>; 0 = none ran
+  int diag = 0, xcd_map = 0;
+  int softmax = 0;
+};
+AttnPlan attn_plan(const TsdOptions& opt, int B, int H, int d, int Sq, int Sk);
+
 struct tsd_ctx {
   int device = 0;
   TsdOptions opt;
@@ -134,6 +144,7 @@ struct tsd_ctx {
   int gemm_last_cfg = -1, gemm_last_ways = 0;
   GnPlan gn_last;             // plan of the last GroupNorm launch enqueued (tsd_debug_norm_run)
   int64_t gn_paths[8] = {};   // tsd_debug_gn_path_counts
+  AttnPlan attn_last;         // plan of the last attention-core / row-softmax launch enqueued (tsd_debug_attn_run)
 };
 
 enum KernelClass : int {

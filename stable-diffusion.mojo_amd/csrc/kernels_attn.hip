@@ -518,6 +518,33 @@ static int launch_fa(tsd_ctx* ctx, const AttnK& k, int B, int H, int Sq) {
   return TSD_OK;
 }
 
+// The kernel and the switches of one launch, from the options and the layer shape alone (d is a supported head dim).
+AttnPlan attn_plan(const TsdOptions& opt, int B, int H, int d, int Sq, int Sk) {
+  AttnPlan p;
+  p.diag = (opt.attn_diag && Sq == Sk) ? 1 : 0;
+  // long key loops only (the K / V^T stream of a head is what the remap saves); results do not depend on the block order.
+  // Measured (profiles/r03_attn_xcd_ab.txt): FETCH_SIZE of the 4096 x 4096 d = 40 call 366 -> 144 MB, of the 1024 x 1024 d = 80 call
+  // 103 -> 33 MB (-0.9 GB of a step's 10.9 GB) and 201.1 against 201.5 steps/s - the kernel is not bound by that stream (all of it
+  // Infinity-Cache hits) and eight whole heads per XCD (5.2 MB of K / V^T) no longer fit its 4 MB L2.  OFF by default (TSD_ATTN_XCD=1).
+  p.xcd_map = (opt.attn_xcd && (B * H) % 8 == 0 && Sk >= 512) ? 1 : 0;
+  switch (d) {
+    case 40:
+      // 64 queries per wave when the key loop is long enough to matter: 4096 x 4096 at B*H = 64 runs 253 -> 243 us (half the
+      // K / V^T fragment reads per MFMA); 77-key cross attention is better off with the 128-query workgroup
+      // The choice keys on the layer (Sq, Sk, H), never on the batch: the two variants are bitwise equal only while no
+      // workgroup repeats exactly (the repeat is decided per 128- / 256-query workgroup and moves the reference per 32 / 64
+      // rows), so a sample computed alone must run the same variant as its row of a batch (bitwise batch invariance).
+      // Eight waves in two staggered groups (kernels_attn8.hip) for the long key loops of a big grid - the 64x64 level's 4096 x 4096 call
+      if (opt.attn_qb_force ? opt.attn_qb_force == 3 : (opt.attn_wg8 && Sk >= 512 && (long long)ceil_div(Sq, 512) * H >= 64)) p.kernel = 3;
+      else if (opt.attn_qb_force ? opt.attn_qb_force == 2 : (opt.attn_qb == 2 && Sk >= 512 && (long long)ceil_div(Sq, 256) * H >= 64)) p.kernel = 2;
+      else p.kernel = 1;
+      break;
+    case 80: p.kernel = 4; break;
+    default: p.kernel = 5; break;
+  }
+  return p;
+}
+
 int launch_flash_attention(tsd_ctx* ctx, const AttnArgs& a) {
   if (!attn_fused_supported(a.d)) TSD_FAIL(TSD_E_SHAPE, "flash attention: head dim %d unsupported", a.d);
   if (a.ldq % 8 || a.ldk % 8 || a.ldvt % 8 || a.ldo % 4) TSD_FAIL(TSD_E_SHAPE, "flash attention: misaligned pitches");
@@ -531,26 +558,15 @@ int launch_flash_attention(tsd_ctx* ctx, const AttnArgs& a) {
   k.H = a.H; k.Sq = a.Sq; k.Sk = a.Sk; k.Skv = std::min(round_up(a.Sk, 8), a.ldvt);
   k.c = a.scale * 1.4426950408889634f;
   k.exact_ctr = ctx->status + 2;
-  k.diag = (ctx->opt.attn_diag && a.Sq == a.Sk) ? 1 : 0;
-  // long key loops only (the K / V^T stream of a head is what the remap saves); results do not depend on the block order.
-  // Measured (profiles/r03_attn_xcd_ab.txt): FETCH_SIZE of the 4096 x 4096 d = 40 call 366 -> 144 MB, of the 1024 x 1024 d = 80 call
-  // 103 -> 33 MB (-0.9 GB of a step's 10.9 GB) and 201.1 against 201.5 steps/s - the kernel is not bound by that stream (all of it
-  // Infinity-Cache hits) and eight whole heads per XCD (5.2 MB of K / V^T) no longer fit its 4 MB L2.  OFF by default (TSD_ATTN_XCD=1).
-  k.xcd_map = (ctx->opt.attn_xcd && (a.B * a.H) % 8 == 0 && a.Sk >= 512) ? 1 : 0;
-  switch (a.d) {
-    case 40:
-      // 64 queries per wave when the key loop is long enough to matter: 4096 x 4096 at B*H = 64 runs 253 -> 243 us (half the
-      // K / V^T fragment reads per MFMA); 77-key cross attention is better off with the 128-query workgroup
-      // The choice keys on the layer (Sq, Sk, H), never on the batch: the two variants are bitwise equal only while no
-      // workgroup repeats exactly (the repeat is decided per 128- / 256-query workgroup and moves the reference per 32 / 64
-      // rows), so a sample computed alone must run the same variant as its row of a batch (bitwise batch invariance).
-      // Eight waves in two staggered groups (kernels_attn8.hip) for the long key loops of a big grid - the 64x64 level's 4096 x 4096 call
-      if (ctx->opt.attn_qb_force ? ctx->opt.attn_qb_force == 3 : (ctx->opt.attn_wg8 && a.Sk >= 512 && (long long)ceil_div(a.Sq, 512) * a.H >= 64))
-        return launch_flash_attention8(ctx, k, a.B, a.H, a.Sq, a.d, ctx->opt.attn8_var);
-      if (ctx->opt.attn_qb_force ? ctx->opt.attn_qb_force == 2 : (ctx->opt.attn_qb == 2 && a.Sk >= 512 && (long long)ceil_div(a.Sq, 256) * a.H >= 64))
-        return launch_fa<40, 2>(ctx, k, a.B, a.H, a.Sq);
-      return launch_fa<40, 1>(ctx, k, a.B, a.H, a.Sq);
-    case 80: return launch_fa<80, 1>(ctx, k, a.B, a.H, a.Sq);
+  const AttnPlan plan = attn_plan(ctx->opt, a.B, a.H, a.d, a.Sq, a.Sk);
+  ctx->attn_last = plan;
+  k.diag = plan.diag;
+  k.xcd_map = plan.xcd_map;
+  switch (plan.kernel) {
+    case 3: return launch_flash_attention8(ctx, k, a.B, a.H, a.Sq, a.d, ctx->opt.attn8_var);
+    case 2: return launch_fa<40, 2>(ctx, k, a.B, a.H, a.Sq);
+    case 1: return launch_fa<40, 1>(ctx, k, a.B, a.H, a.Sq);
+    case 4: return launch_fa<80, 1>(ctx, k, a.B, a.H, a.Sq);
     default: return launch_fa<160, 1>(ctx, k, a.B, a.H, a.Sq);
   }
 }

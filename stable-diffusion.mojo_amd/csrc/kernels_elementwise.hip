@@ -366,6 +366,7 @@ __global__ __launch_bounds__(256) void k_softmax_rows_h8(half_t* __restrict__ x,
 }
 int launch_softmax_rows_f32(tsd_ctx* ctx, const float* x, int64_t rows, int cols, float* y) {
   if (!ctx->launch()) return TSD_OK;
+  ctx->attn_last.softmax = 1;
   hipLaunchKernelGGL(k_softmax_rows<float>, dim3((unsigned)rows), dim3(256), 0, ctx->stream, x, cols, cols, y, cols, 0, 0);
   HIP_TRY(hipGetLastError());
   return TSD_OK;
@@ -374,11 +375,13 @@ int launch_softmax_rows_f16(tsd_ctx* ctx, half_t* x, int64_t rows, int cols, int
   if (!ctx->launch()) return TSD_OK;
   ProfScope prof(ctx, KC_SOFTMAX);
   if (cols % 8 == 0 && ld % 8 == 0 && cols <= 256 * 8 * 2) {  // register-resident rows
+    ctx->attn_last.softmax = cols <= 256 * 8 ? 3 : 4;
     if (cols <= 256 * 8) hipLaunchKernelGGL(k_softmax_rows_h8<1>, dim3((unsigned)rows), dim3(256), 0, ctx->stream, x, cols, ld);
     else hipLaunchKernelGGL(k_softmax_rows_h8<2>, dim3((unsigned)rows), dim3(256), 0, ctx->stream, x, cols, ld);
     HIP_TRY(hipGetLastError());
     return TSD_OK;
   }
+  ctx->attn_last.softmax = 2;
   hipLaunchKernelGGL(k_softmax_rows<half_t>, dim3((unsigned)rows), dim3(256), 0, ctx->stream, (const half_t*)x, cols,
                      ld, x, ld, 0, 0);
   HIP_TRY(hipGetLastError());
@@ -388,6 +391,7 @@ int launch_softmax_rows_f16_causal(tsd_ctx* ctx, half_t* x, int64_t rows, int co
   if (period <= 0 || zero_to > ld) TSD_FAIL(TSD_E_ARG, "causal softmax: bad period / padding");
   if (!ctx->launch()) return TSD_OK;
   ProfScope prof(ctx, KC_SOFTMAX);
+  ctx->attn_last.softmax = 2;
   hipLaunchKernelGGL(k_softmax_rows<half_t>, dim3((unsigned)rows), dim3(256), 0, ctx->stream, (const half_t*)x, cols,
                      ld, x, ld, period, zero_to);
   HIP_TRY(hipGetLastError());
