@@ -9,8 +9,8 @@
 
 #include "graph.h"
 
-#define NOTNULL(p) \
-  if (!(p)) TSD_FAIL(TSD_E_ARG, "%s: argument '%s' is NULL", __func__, #p)
+// Every entry point opens with NOTNULL(p) on its pointer arguments (graph.h): TSD_E_ARG and the argument's name in
+// tsd_last_error.
 
 namespace {
 int h2d(tsd_ctx* c, void* dst, const void* src, size_t bytes) {

@@ -94,8 +94,8 @@ int run_op(tsd_ctx* ctx, F&& fn) {
 }
 }  // namespace
 
-#define NOTNULL(p) \
-  if (!(p)) TSD_FAIL(TSD_E_ARG, "%s: argument '%s' is NULL", __func__, #p)
+// Every entry point opens with NOTNULL(p) on its pointer arguments: TSD_E_ARG and the argument's name in tsd_last_error.
+// The macro is in graph.h; the replay entries (api_replay.cpp) use it as well.
 
 extern "C" int tsd_conv2d_f32(tsd_ctx* ctx, const float* x, int C, int H, int W, const float* w, const float* bias,
                               int I, int O, int k, int pad_h, int pad_w, int stride_h, int stride_w, float* y) {
@@ -628,613 +628,6 @@ extern "C" int tsd_vae_attention_block_f32(tsd_ctx* ctx, const float* x, int C, 
     TSD_TRY(launch_nhwc_f16_to_chw_f32(ctx, out.p, 1, C, H, W, C, dy));
     return d.out(y, dy, (int64_t)C * H * W);
   });
-}
-
-// ---- GEMM launch descriptors: record and replay (tests/gemm_ref.py holds each launch to an fp64 reference) -------------------
-void gemm_describe(const tsd_ctx* ctx, const GemmArgs& a, int64_t* d) {
-  for (int i = 0; i < TSD_GD_COUNT; i++) d[i] = 0;
-  d[TSD_GD_VERSION] = TSD_GD_VERSION_1;
-  d[TSD_GD_CONV] = a.conv; d[TSD_GD_M] = a.M; d[TSD_GD_N] = a.N; d[TSD_GD_K] = a.K;
-  d[TSD_GD_K0] = (!a.conv && a.A1) ? a.K0 : a.K;  // what launch_gemm hands the kernel
-  d[TSD_GD_LDA0] = a.lda0; d[TSD_GD_LDA1] = a.lda1; d[TSD_GD_LDA2] = a.lda2; d[TSD_GD_LDW] = a.ldw; d[TSD_GD_LDW1] = a.ldw1;
-  d[TSD_GD_LDR] = a.ldr; d[TSD_GD_LDC] = a.ldc;
-  d[TSD_GD_BATCH] = a.batch; d[TSD_GD_SA] = a.sA; d[TSD_GD_SW] = a.sW; d[TSD_GD_SC] = a.sC; d[TSD_GD_SR] = a.sR;
-  if (a.conv) {
-    d[TSD_GD_HS] = a.Hs; d[TSD_GD_WS] = a.Ws; d[TSD_GD_HO] = a.Ho; d[TSD_GD_WO] = a.Wo; d[TSD_GD_CIN] = a.Cin;
-    d[TSD_GD_STRIDE] = a.stride; d[TSD_GD_PAD] = a.pad; d[TSD_GD_UPS] = a.ups; d[TSD_GD_CIN1] = a.Cin1; d[TSD_GD_CIN2] = a.Cin2;
-  }
-  d[TSD_GD_W_KTS] = a.w_kts ? 1 : 0;
-  d[TSD_GD_EPI] = a.epi;
-  uint32_t bits;
-  memcpy(&bits, &a.out_scale, 4);
-  d[TSD_GD_OUT_SCALE] = bits;
-  d[TSD_GD_ROWVEC_LD] = a.rowvec_ld; d[TSD_GD_ROWS_PER_BATCH] = a.rows_per_batch;
-  if (a.Vt) { d[TSD_GD_VT] = 1; d[TSD_GD_VT_N0] = a.vt_n0; d[TSD_GD_VT_LD] = a.vt_ld; d[TSD_GD_VT_S] = a.vt_S; d[TSD_GD_VT_SB] = a.vt_sB; }
-  d[TSD_GD_GN_GROUPS] = a.gn_groups; d[TSD_GD_GN_RPS] = a.gn_rows_per_sample; d[TSD_GD_GN_NSLAB] = a.gn_nslab;
-  d[TSD_GD_RPS_HINT] = a.rows_per_sample_hint; d[TSD_GD_SK_BIG] = ctx->opt.sk_big_graph;
-  d[TSD_GD_ALIAS] = (a.R && (const void*)a.R == a.C ? 1 : 0) | (a.A1 && a.A1 == a.A0 ? 2 : 0) | (a.A2 && a.A2 == a.A1 ? 4 : 0);
-  d[TSD_GD_CFG] = -1; d[TSD_GD_WAYS] = 0;
-}
-
-extern "C" int tsd_debug_gemm_record(tsd_ctx* ctx, int on) {
-  NOTNULL(ctx);
-  if (on) ctx->gemm_rec.clear();
-  ctx->gemm_rec_on = on != 0;
-  return (int)(ctx->gemm_rec.size() / TSD_GD_COUNT);
-}
-
-extern "C" int tsd_debug_gemm_recorded(tsd_ctx* ctx, int i, int64_t* desc, int n) {
-  NOTNULL(ctx); NOTNULL(desc);
-  if (n < TSD_GD_COUNT || i < 0 || (size_t)(i + 1) * TSD_GD_COUNT > ctx->gemm_rec.size())
-    TSD_FAIL(TSD_E_ARG, "gemm_recorded: no descriptor %d (capacity %d)", i, n);
-  memcpy(desc, &ctx->gemm_rec[(size_t)i * TSD_GD_COUNT], TSD_GD_COUNT * sizeof(int64_t));
-  return TSD_GD_COUNT;
-}
-
-namespace {
-constexpr size_t GD_GUARD = 4096;                     // bytes of NaN pattern before and after every operand
-constexpr uint16_t GD_NAN16 = 0x7E5A;                 // fp16 quiet NaN
-constexpr uint32_t GD_NAN32 = 0x7FC5A5A5u;            // fp32 quiet NaN (a byte-wise fill that is an fp16 NaN is a finite fp32)
-int gd_elem_bytes(int slot, const int64_t* d) {
-  if (slot == TSD_GO_BIAS || slot == TSD_GO_ROWVEC || slot == TSD_GO_GN) return 4;
-  if (slot == TSD_GO_C && (d[TSD_GD_EPI] & EPI_OUT_F32)) return 4;
-  return 2;
-}
-// Columns of C the launch stores (the Vt tail's columns go to Vt instead, GEGLU halves the width)
-int64_t gd_c_cols(const int64_t* d) {
-  if (d[TSD_GD_VT]) return d[TSD_GD_VT_N0];
-  return (d[TSD_GD_EPI] & EPI_GEGLU) ? d[TSD_GD_N] / 2 : d[TSD_GD_N];
-}
-// Element extent of every operand the descriptor reads or writes, including the kernel's clamped loads (bias / row vector at
-// N - 4, residual at N - 8: all inside [0, N)).  Refuses what it cannot size; the combinations launch_gemm itself refuses are left to it.
-int gd_extents(const int64_t* d, int64_t* e) {
-  for (int i = 0; i < TSD_GO_COUNT; i++) e[i] = 0;
-#define GD_REQ(cond) \
-  if (!(cond)) TSD_FAIL(TSD_E_ARG, "gemm_run: descriptor cannot be sized (%s)", #cond)
-  GD_REQ(d[TSD_GD_VERSION] == TSD_GD_VERSION_1);
-  const int64_t M = d[TSD_GD_M], N = d[TSD_GD_N], K = d[TSD_GD_K], K0 = d[TSD_GD_K0], batch = d[TSD_GD_BATCH], epi = d[TSD_GD_EPI];
-  const int64_t lim = 1LL << 30;
-  GD_REQ(M > 0 && N > 0 && K > 0 && M < (1 << 26) && N <= 65536 && K <= 65536 && N % 4 == 0);
-  GD_REQ(batch >= 1 && batch <= 4096 && epi >= 0 && epi < 256);
-  for (int f : {TSD_GD_LDA0, TSD_GD_LDA1, TSD_GD_LDA2, TSD_GD_LDW, TSD_GD_LDW1, TSD_GD_LDR, TSD_GD_LDC, TSD_GD_ROWVEC_LD, TSD_GD_VT_LD})
-    GD_REQ(d[f] >= 0 && d[f] <= 65536);
-  for (int f : {TSD_GD_SA, TSD_GD_SW, TSD_GD_SC, TSD_GD_SR, TSD_GD_VT_SB}) GD_REQ(d[f] >= 0 && d[f] <= lim);
-  const int64_t sA = d[TSD_GD_SA], sW = d[TSD_GD_SW], sC = d[TSD_GD_SC], sR = d[TSD_GD_SR];
-  int64_t KW = K, B = 1;
-  if (d[TSD_GD_CONV]) {
-    const int64_t Hs = d[TSD_GD_HS], Ws = d[TSD_GD_WS], Ho = d[TSD_GD_HO], Wo = d[TSD_GD_WO], Cin = d[TSD_GD_CIN];
-    const int64_t Cin1 = d[TSD_GD_CIN1], Cin2 = d[TSD_GD_CIN2];
-    GD_REQ(Hs > 0 && Ws > 0 && Ho > 0 && Wo > 0 && Hs < 2048 && Ws < 2048 && Ho < 2048 && Wo < 2048 && Cin > 0 && Cin <= 8192);
-    GD_REQ(batch == 1 && M % (Ho * Wo) == 0 && d[TSD_GD_LDA0] >= Cin);
-    GD_REQ((d[TSD_GD_STRIDE] == 1 || d[TSD_GD_STRIDE] == 2) && (d[TSD_GD_UPS] >= 0 && d[TSD_GD_UPS] <= 2) && d[TSD_GD_PAD] >= 0 && d[TSD_GD_PAD] <= 1);
-    {  // Ho / Wo must follow from the source, stride, pad and a bottom / right pad of 0 or 1: the kernel packs each output pixel's
-       // first tap (o * stride - pad + 1) into an 11-bit field with the sample index above it, so a larger one would read another image
-      const int64_t st = d[TSD_GD_STRIDE], pad = d[TSD_GD_PAD], up = d[TSD_GD_UPS] ? 2 : 1;
-      bool geo = false;
-      for (int64_t br = 0; br <= 1; br++)
-        geo = geo || ((up * Hs + pad + br - 3) / st + 1 == Ho && (up * Ws + pad + br - 3) / st + 1 == Wo && up * Hs + pad + br >= 3 && up * Ws + pad + br >= 3);
-      GD_REQ(geo && (Ho - 1) * st - pad + 2 < 2048 && (Wo - 1) * st - pad + 2 < 2048);
-    }
-    B = M / (Ho * Wo);
-    const int64_t px = B * Hs * Ws;
-    e[TSD_GO_A0] = (px - 1) * d[TSD_GD_LDA0] + Cin;
-    KW = 9 * Cin;
-    GD_REQ(Cin1 >= 0 && Cin2 >= 0 && (Cin1 > 0 || Cin2 == 0));
-    if (Cin1 > 0) {  // the skip sources are read at the output pixel: same resolution
-      GD_REQ(Ho == Hs && Wo == Ws && d[TSD_GD_LDA1] >= Cin1 && d[TSD_GD_LDW1] >= Cin1 + Cin2);
-      e[TSD_GO_A1] = (px - 1) * d[TSD_GD_LDA1] + Cin1;
-      if (Cin2 > 0) {
-        GD_REQ(d[TSD_GD_LDA2] >= Cin2);
-        e[TSD_GO_A2] = (px - 1) * d[TSD_GD_LDA2] + Cin2;
-      }
-      e[TSD_GO_WT1] = (N - 1) * d[TSD_GD_LDW1] + Cin1 + Cin2;
-    }
-  } else {
-    GD_REQ(K0 > 0 && K0 <= K && d[TSD_GD_LDA0] >= K0);
-    e[TSD_GO_A0] = (batch - 1) * sA + (M - 1) * d[TSD_GD_LDA0] + K0;
-    if (K0 < K) {
-      GD_REQ(d[TSD_GD_LDA1] >= K - K0);
-      e[TSD_GO_A1] = (batch - 1) * sA + (M - 1) * d[TSD_GD_LDA1] + (K - K0);
-    }
-  }
-  if (d[TSD_GD_W_KTS]) {
-    GD_REQ(batch == 1 && KW % 64 == 0);
-    e[TSD_GO_W] = N * KW;  // passed row-major [N][KW]
-  } else {
-    GD_REQ(d[TSD_GD_LDW] >= KW);
-    e[TSD_GO_W] = (batch - 1) * sW + (N - 1) * d[TSD_GD_LDW] + KW;
-  }
-  const int64_t ccols = gd_c_cols(d);
-  GD_REQ(ccols > 0 && ccols <= N && d[TSD_GD_LDC] >= ccols);
-  e[TSD_GO_C] = (batch - 1) * sC + (M - 1) * d[TSD_GD_LDC] + ccols;
-  if (epi & (EPI_BIAS_N | EPI_BIAS_M)) e[TSD_GO_BIAS] = std::max((epi & EPI_BIAS_N) ? N : 0, (epi & EPI_BIAS_M) ? M : 0);
-  if (epi & EPI_ROWVEC) {
-    GD_REQ(d[TSD_GD_ROWS_PER_BATCH] >= 1 && (d[TSD_GD_ROWVEC_LD] == 0 || d[TSD_GD_ROWVEC_LD] >= N));
-    e[TSD_GO_ROWVEC] = ((M - 1) / d[TSD_GD_ROWS_PER_BATCH]) * d[TSD_GD_ROWVEC_LD] + N;
-  }
-  if (epi & EPI_RESIDUAL) {
-    if (d[TSD_GD_ALIAS] & 1) {  // in place: R is C's initial content
-      GD_REQ(!(epi & (EPI_RES_UPS | EPI_GEGLU | EPI_OUT_F32)) && !d[TSD_GD_VT] && d[TSD_GD_LDR] == d[TSD_GD_LDC] && sR == sC);
-      e[TSD_GO_R] = e[TSD_GO_C];
-    } else {
-      int64_t rows = M;
-      if (d[TSD_GD_CONV] && (epi & EPI_RES_UPS)) {
-        GD_REQ(d[TSD_GD_HO] % 2 == 0 && d[TSD_GD_WO] % 2 == 0);
-        rows = B * (d[TSD_GD_HO] / 2) * (d[TSD_GD_WO] / 2);
-      }
-      GD_REQ(d[TSD_GD_LDR] >= N);
-      e[TSD_GO_R] = (batch - 1) * sR + (rows - 1) * d[TSD_GD_LDR] + N;
-    }
-  }
-  if (d[TSD_GD_VT]) {
-    const int64_t n0 = d[TSD_GD_VT_N0], S = d[TSD_GD_VT_S];
-    GD_REQ(n0 > 0 && n0 < N && S > 0 && M % S == 0 && d[TSD_GD_VT_LD] >= S && d[TSD_GD_VT_SB] >= (N - n0 - 1) * d[TSD_GD_VT_LD] + S);
-    e[TSD_GO_VT] = (M / S - 1) * d[TSD_GD_VT_SB] + (N - n0 - 1) * d[TSD_GD_VT_LD] + S;
-  }
-  if (epi & EPI_GNSTATS) {
-    const int64_t G = d[TSD_GD_GN_GROUPS], rps = d[TSD_GD_GN_RPS], ns = d[TSD_GD_GN_NSLAB];
-    GD_REQ(G > 0 && G <= N && rps > 0 && M % rps == 0 && ns > 0 && ns * 32 <= rps);
-    e[TSD_GO_GN] = (M / rps) * ns * G * 2;
-  }
-  for (int s = 0; s < TSD_GO_COUNT; s++) GD_REQ(e[s] >= 0 && e[s] <= lim);
-#undef GD_REQ
-  return TSD_OK;
-}
-// Elements of output slot s that the launch may write (1) - everything else of its extent is a pitch gap
-std::vector<char> gd_logical(int s, const int64_t* d, int64_t ext) {
-  std::vector<char> m((size_t)ext, s == TSD_GO_GN ? 1 : 0);
-  if (s == TSD_GO_C) {
-    const int64_t cols = gd_c_cols(d);
-    for (int64_t b = 0; b < d[TSD_GD_BATCH]; b++)
-      for (int64_t r = 0; r < d[TSD_GD_M]; r++) memset(&m[(size_t)(b * d[TSD_GD_SC] + r * d[TSD_GD_LDC])], 1, (size_t)cols);
-  } else if (s == TSD_GO_VT) {
-    for (int64_t b = 0; b < d[TSD_GD_M] / d[TSD_GD_VT_S]; b++)
-      for (int64_t c = 0; c < d[TSD_GD_N] - d[TSD_GD_VT_N0]; c++)
-        memset(&m[(size_t)(b * d[TSD_GD_VT_SB] + c * d[TSD_GD_VT_LD])], 1, (size_t)d[TSD_GD_VT_S]);
-  }
-  return m;
-}
-struct GdBufs {
-  char* p[TSD_GO_COUNT + 2] = {};  // + the K-tile-major weight copy, + the upsample-folded copies
-  ~GdBufs() { for (char* q : p) if (q) (void)hipFree(q); }
-};
-}  // namespace
-
-extern "C" int tsd_debug_gemm_run(tsd_ctx* ctx, const int64_t* desc, int n, int cfg, const void* const* host_in,
-                                  void* const* host_out, int64_t* ext, int64_t* info) {
-  NOTNULL(desc); NOTNULL(ext);
-  if (n < TSD_GD_COUNT || cfg >= 64) TSD_FAIL(TSD_E_ARG, "gemm_run: %d descriptor fields, cfg %d", n, cfg);
-  TSD_TRY(gd_extents(desc, ext));
-  if (!host_in) return TSD_OK;  // sizing only: no context or device needed
-  NOTNULL(ctx); NOTNULL(host_out); NOTNULL(info);
-  const int64_t* d = desc;
-  const bool alias = (d[TSD_GD_EPI] & EPI_RESIDUAL) && (d[TSD_GD_ALIAS] & 1);
-  for (int s = 0; s < TSD_GO_COUNT; s++) {
-    if (!ext[s]) continue;
-    if (s < TSD_GO_C ? !host_in[s] : !host_out[s - TSD_GO_C]) TSD_FAIL(TSD_E_ARG, "gemm_run: operand slot %d is NULL", s);
-  }
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  GdBufs bufs;
-  std::vector<char> init[TSD_GO_COUNT];  // outputs: guards + extent as filled before the launch
-  auto fill = [&](char* p, size_t elems, int es) -> int {
-    if (es == 2) HIP_TRY(hipMemsetD16Async((hipDeviceptr_t)p, GD_NAN16, elems, st));
-    else HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)p, (int)GD_NAN32, elems, st));
-    return TSD_OK;
-  };
-  for (int s = 0; s < TSD_GO_COUNT; s++) {
-    if (!ext[s] || (s == TSD_GO_R && alias)) continue;
-    const int es = gd_elem_bytes(s, d);
-    const size_t bytes = 2 * GD_GUARD + (size_t)ext[s] * es;
-    HIP_TRY(hipMalloc((void**)&bufs.p[s], bytes));
-    TSD_TRY(fill(bufs.p[s], bytes / es, es));
-    if (s < TSD_GO_C) HIP_TRY(hipMemcpyAsync(bufs.p[s] + GD_GUARD, host_in[s], (size_t)ext[s] * es, hipMemcpyHostToDevice, st));
-    else {
-      init[s].resize(bytes);
-      for (size_t i = 0; i < bytes; i += es) {
-        if (es == 2) memcpy(&init[s][i], &GD_NAN16, 2);
-        else memcpy(&init[s][i], &GD_NAN32, 4);
-      }
-      if (s == TSD_GO_C && alias) {
-        HIP_TRY(hipMemcpyAsync(bufs.p[s] + GD_GUARD, host_in[TSD_GO_R], (size_t)ext[s] * es, hipMemcpyHostToDevice, st));
-        memcpy(&init[s][GD_GUARD], host_in[TSD_GO_R], (size_t)ext[s] * es);
-      }
-    }
-  }
-  auto at = [&](int s) -> void* { return bufs.p[s] ? (void*)(bufs.p[s] + GD_GUARD) : nullptr; };
-  GemmArgs g;
-  g.conv = (int)d[TSD_GD_CONV]; g.M = (int)d[TSD_GD_M]; g.N = (int)d[TSD_GD_N]; g.K = (int)d[TSD_GD_K];
-  g.A0 = (const half_t*)at(TSD_GO_A0); g.lda0 = (int)d[TSD_GD_LDA0];
-  g.A1 = (const half_t*)at(TSD_GO_A1); g.lda1 = (int)d[TSD_GD_LDA1]; g.K0 = (int)d[TSD_GD_K0];
-  g.A2 = (const half_t*)at(TSD_GO_A2); g.lda2 = (int)d[TSD_GD_LDA2];
-  g.Wt = (const half_t*)at(TSD_GO_W); g.ldw = (int)d[TSD_GD_LDW];
-  g.Wt1 = (const half_t*)at(TSD_GO_WT1); g.ldw1 = (int)d[TSD_GD_LDW1];
-  g.batch = (int)d[TSD_GD_BATCH]; g.sA = d[TSD_GD_SA]; g.sW = d[TSD_GD_SW]; g.sC = d[TSD_GD_SC]; g.sR = d[TSD_GD_SR];
-  if (g.conv) {
-    g.Hs = (int)d[TSD_GD_HS]; g.Ws = (int)d[TSD_GD_WS]; g.Ho = (int)d[TSD_GD_HO]; g.Wo = (int)d[TSD_GD_WO]; g.Cin = (int)d[TSD_GD_CIN];
-    g.stride = (int)d[TSD_GD_STRIDE]; g.pad = (int)d[TSD_GD_PAD]; g.ups = (int)d[TSD_GD_UPS];
-    g.Cin1 = (int)d[TSD_GD_CIN1]; g.Cin2 = (int)d[TSD_GD_CIN2];
-  }
-  g.epi = (int)d[TSD_GD_EPI];
-  const uint32_t bits = (uint32_t)d[TSD_GD_OUT_SCALE];
-  memcpy(&g.out_scale, &bits, 4);
-  g.bias = (const float*)at(TSD_GO_BIAS);
-  g.rowvec = (const float*)at(TSD_GO_ROWVEC); g.rowvec_ld = (int)d[TSD_GD_ROWVEC_LD]; g.rows_per_batch = (int)d[TSD_GD_ROWS_PER_BATCH];
-  g.R = (const half_t*)(alias ? at(TSD_GO_C) : at(TSD_GO_R)); g.ldr = (int)d[TSD_GD_LDR];
-  g.C = at(TSD_GO_C); g.ldc = (int)d[TSD_GD_LDC];
-  if (d[TSD_GD_VT]) { g.Vt = (half_t*)at(TSD_GO_VT); g.vt_n0 = (int)d[TSD_GD_VT_N0]; g.vt_ld = (int)d[TSD_GD_VT_LD]; g.vt_S = (int)d[TSD_GD_VT_S]; g.vt_sB = d[TSD_GD_VT_SB]; }
-  g.gn_part = (float*)at(TSD_GO_GN); g.gn_groups = (int)d[TSD_GD_GN_GROUPS]; g.gn_rows_per_sample = (int)d[TSD_GD_GN_RPS]; g.gn_nslab = (int)d[TSD_GD_GN_NSLAB];
-  g.rows_per_sample_hint = (int)d[TSD_GD_RPS_HINT];
-  if (d[TSD_GD_W_KTS]) {  // the K-tile-major copy the model path builds for weight-heavy layers
-    const int KW = g.conv ? 9 * g.Cin : g.K;
-    HIP_TRY(hipMalloc((void**)&bufs.p[TSD_GO_COUNT], 2 * GD_GUARD + (size_t)g.N * KW * 2));
-    TSD_TRY(fill(bufs.p[TSD_GO_COUNT], (2 * GD_GUARD) / 2 + (size_t)g.N * KW, 2));
-    half_t* tm = (half_t*)(bufs.p[TSD_GO_COUNT] + GD_GUARD);
-    TSD_TRY(launch_pack_tile_major(ctx, g.Wt, g.N, KW, tm));
-    g.Wt = tm; g.ldw = 64; g.w_kts = g.N * 128;
-  }
-  if (g.conv && g.ups == 2 && g.Cin % 64 == 0 && host_in[TSD_GO_W]) {
-    // the folded parity copies, made from the row-major W the caller passed by the routine tsd_model_prepare uses (model.cpp); whether the
-    // launch may run them is launch_gemm's decision
-    const int ld = d[TSD_GD_W_KTS] ? 9 * g.Cin : (int)d[TSD_GD_LDW];
-    const size_t nf = (size_t)16 * g.N * g.Cin;
-    std::vector<uint16_t> folded(nf);
-    (void)ups_fold_pack_host((const uint16_t*)host_in[TSD_GO_W], g.N, g.Cin, ld, folded.data());
-    HIP_TRY(hipMalloc((void**)&bufs.p[TSD_GO_COUNT + 1], 2 * GD_GUARD + nf * 2));
-    TSD_TRY(fill(bufs.p[TSD_GO_COUNT + 1], (2 * GD_GUARD) / 2 + nf, 2));
-    HIP_TRY(hipMemcpyAsync(bufs.p[TSD_GO_COUNT + 1] + GD_GUARD, folded.data(), nf * 2, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    g.Wuf = (const half_t*)(bufs.p[TSD_GO_COUNT + 1] + GD_GUARD);
-  }
-  // the dispatcher's choice (with the recorded graph's long-K split) or a forced tile; a replay is not recorded
-  const int prev_force = ctx->opt.force_cfg, prev_big = ctx->opt.sk_big_graph;
-  const bool prev_rec = ctx->gemm_rec_on;
-  ctx->opt.force_cfg = cfg >= 0 ? cfg : -1;
-  if (cfg < 0) ctx->opt.sk_big_graph = (int)d[TSD_GD_SK_BIG];
-  ctx->gemm_rec_on = false;
-  ctx->gemm_last_cfg = -1; ctx->gemm_last_ways = 0;
-  const int r = run_planned(ctx, [&]() -> int { return launch_gemm(ctx, g); });
-  ctx->opt.force_cfg = prev_force; ctx->opt.sk_big_graph = prev_big; ctx->gemm_rec_on = prev_rec;
-  HIP_TRY(hipStreamSynchronize(st));
-  info[0] = ctx->gemm_last_cfg; info[1] = ctx->gemm_last_ways;
-  int64_t changed = 0;
-  for (int s = TSD_GO_C; s < TSD_GO_COUNT; s++) {
-    if (!ext[s]) continue;
-    const int es = gd_elem_bytes(s, d);
-    std::vector<char> got(init[s].size());
-    HIP_TRY(hipMemcpy(got.data(), bufs.p[s], got.size(), hipMemcpyDeviceToHost));
-    const std::vector<char> logical = gd_logical(s, d, ext[s]);
-    const int64_t g0 = (int64_t)(GD_GUARD / es), total = (int64_t)(got.size() / es);
-    for (int64_t i = 0; i < total; i++) {
-      const int64_t j = i - g0;
-      if (j >= 0 && j < ext[s] && logical[(size_t)j]) continue;
-      if (memcmp(&got[(size_t)i * es], &init[s][(size_t)i * es], es)) changed++;
-    }
-    memcpy(host_out[s - TSD_GO_C], &got[GD_GUARD], (size_t)ext[s] * es);
-  }
-  info[2] = changed;
-  return r;
-}
-
-// ---- GroupNorm / LayerNorm launches on caller operands (tests/norm_ref.py holds every statistics path to an fp64 reference) ------
-namespace {
-float nd_float(int64_t bits) {
-  const uint32_t b = (uint32_t)bits;
-  float f;
-  memcpy(&f, &b, 4);
-  return f;
-}
-// Element extent of every operand the described launch reads or writes.  Refuses what it cannot size; the shapes the launches
-// themselves refuse (C % 8, C % groups, widths, pitches that are no multiple of 8) are sized and left to them.
-int nd_extents(const int64_t* d, int64_t* e) {
-  for (int i = 0; i < TSD_NO_COUNT; i++) e[i] = 0;
-#define ND_REQ(cond) \
-  if (!(cond)) TSD_FAIL(TSD_E_ARG, "norm_run: descriptor cannot be sized (%s)", #cond)
-  ND_REQ(d[TSD_ND_VERSION] == TSD_ND_VERSION_1);
-  const int64_t mode = d[TSD_ND_MODE], C = d[TSD_ND_C], lim = 1LL << 28;
-  ND_REQ(mode >= TSD_NM_GROUPNORM && mode <= TSD_NM_LAYERNORM);
-  ND_REQ(C > 0 && C <= 65536);
-  for (int f : {TSD_ND_LD0, TSD_ND_LD1, TSD_ND_LDY}) ND_REQ(d[f] >= 0 && d[f] <= 65536);
-  for (int f : {TSD_ND_SILU, TSD_ND_HAS_W, TSD_ND_HAS_B, TSD_ND_TORCH_RSTD}) ND_REQ(d[f] == 0 || d[f] == 1);
-  if (d[TSD_ND_HAS_W]) e[TSD_NO_W] = C;
-  if (d[TSD_ND_HAS_B]) e[TSD_NO_BIAS] = C;
-  if (mode == TSD_NM_LAYERNORM) {
-    const int64_t rows = d[TSD_ND_ROWS];
-    ND_REQ(rows > 0 && rows < lim && d[TSD_ND_LD0] >= C && d[TSD_ND_LDY] >= C);
-    e[TSD_NO_X0] = (rows - 1) * d[TSD_ND_LD0] + C;
-    e[TSD_NO_Y] = (rows - 1) * d[TSD_ND_LDY] + C;
-  } else {
-    const int64_t B = d[TSD_ND_B], HW = d[TSD_ND_HW], G = d[TSD_ND_GROUPS], C0 = d[TSD_ND_C0], ns = d[TSD_ND_NSLAB];
-    ND_REQ(B > 0 && B <= 4096 && HW > 0 && HW < lim && B * HW < lim && G > 0 && G <= C);
-    if (mode == TSD_NM_GN_FINALIZE) {
-      ND_REQ(ns > 0 && ns <= 65536);
-      e[TSD_NO_PART0] = B * ns * G * 2;
-      e[TSD_NO_STATS] = B * G * 2;
-    } else {
-      const int64_t px = B * HW;
-      ND_REQ(C0 > 0 && C0 <= C && d[TSD_ND_LD0] >= C0);
-      ND_REQ(mode == TSD_NM_GROUPNORM || C0 == C);
-      e[TSD_NO_X0] = (px - 1) * d[TSD_ND_LD0] + C0;
-      if (C0 < C) {
-        ND_REQ(d[TSD_ND_LD1] >= C - C0);
-        e[TSD_NO_X1] = (px - 1) * d[TSD_ND_LD1] + (C - C0);
-      }
-      if (mode == TSD_NM_GN_STATS) e[TSD_NO_STATS] = B * G * 2;
-      else {
-        ND_REQ(d[TSD_ND_LDY] >= C);
-        e[TSD_NO_Y] = (px - 1) * d[TSD_ND_LDY] + C;
-        const int64_t st = d[TSD_ND_STATS];
-        ND_REQ(st >= 0 && st <= 2);
-        if (st == 1) {
-          ND_REQ(ns > 0 && ns <= 65536);
-          e[TSD_NO_PART0] = B * ns * G * 2;
-        } else if (st == 2) {
-          const int64_t G0 = d[TSD_ND_G0], G1 = d[TSD_ND_G1];
-          ND_REQ(ns > 0 && ns <= 65536 && G0 > 0 && G0 <= 65536 && G1 >= 0 && G1 <= 65536 && d[TSD_ND_COMB] >= 0 && d[TSD_ND_COMB] <= 65536);
-          e[TSD_NO_PART0] = B * ns * G0 * 2;
-          e[TSD_NO_PART1] = B * ns * G1 * 2;
-        }
-      }
-    }
-  }
-  for (int s = 0; s < TSD_NO_COUNT; s++) ND_REQ(e[s] >= 0 && e[s] <= lim);
-#undef ND_REQ
-  return TSD_OK;
-}
-int nd_elem_bytes(int slot) { return slot == TSD_NO_X0 || slot == TSD_NO_X1 || slot == TSD_NO_Y ? 2 : 4; }
-void nd_plan_info(const GnPlan& p, int64_t* info) {
-  info[TSD_NI_NSLAB] = p.nslab; info[TSD_NI_OWN_PASS] = p.nslab > 0 && !p.have_stats ? 1 : 0; info[TSD_NI_PREREDUCE] = p.prereduce ? 1 : 0;
-  info[TSD_NI_FINALIZE] = p.stats_ready; info[TSD_NI_COMPOSITE] = p.composite ? 1 : 0; info[TSD_NI_SLAB_PIXELS] = p.slab_pixels;
-  info[TSD_NI_APPLY_PIXELS] = p.apply_pixels; info[TSD_NI_PL] = p.PL;
-}
-struct NdBufs {
-  char* p[TSD_NO_COUNT] = {};
-  ~NdBufs() { for (char* q : p) if (q) (void)hipFree(q); }
-};
-}  // namespace
-
-extern "C" int tsd_debug_norm_run(tsd_ctx* ctx, const int64_t* desc, int n, const void* const* host_in, void* const* host_out,
-                                  int64_t* ext, int64_t* info) {
-  NOTNULL(desc); NOTNULL(ext);
-  if (n < TSD_ND_COUNT) TSD_FAIL(TSD_E_ARG, "norm_run: %d descriptor fields", n);
-  TSD_TRY(nd_extents(desc, ext));
-  const int64_t* d = desc;
-  const int mode = (int)d[TSD_ND_MODE], B = (int)d[TSD_ND_B], HW = (int)d[TSD_ND_HW], C = (int)d[TSD_ND_C], G = (int)d[TSD_ND_GROUPS];
-  const int ns = (int)d[TSD_ND_NSLAB];
-  if (info) for (int i = 0; i < TSD_NI_COUNT; i++) info[i] = 0;
-  // a non-NULL marker stands for the tables: the plan looks at which pointers are given, never through them
-  static const float marker = 0.f;
-  auto composite_of = [&](const float* p0, const float* p1) {
-    GnComposite gc;
-    gc.part0 = p0; gc.G0 = (int)d[TSD_ND_G0]; gc.part1 = d[TSD_ND_G1] > 0 ? p1 : nullptr; gc.G1 = (int)d[TSD_ND_G1];
-    gc.nslab = ns; gc.comb = (int)d[TSD_ND_COMB];
-    return gc;
-  };
-  if (!host_in) {  // sizing only: no context or device needed; the plan under the default options
-    if (info && (mode == TSD_NM_GROUPNORM || mode == TSD_NM_GN_STATS) && C % 8 == 0 && C % G == 0 && C <= 4096) {
-      const int st = mode == TSD_NM_GROUPNORM ? (int)d[TSD_ND_STATS] : 0;
-      const GnComposite gc = composite_of(&marker, &marker);
-      GnPlan p = gn_plan(TsdOptions(), HW, C, G, st == 1 ? &marker : nullptr, st == 1 ? ns : 0, st == 2 ? &gc : nullptr);
-      if (mode == TSD_NM_GN_STATS) p.stats_ready = 1;
-      nd_plan_info(p, info);
-    }
-    return TSD_OK;
-  }
-  NOTNULL(ctx); NOTNULL(host_out); NOTNULL(info);
-  for (int s = 0; s < TSD_NO_COUNT; s++) {
-    if (!ext[s]) continue;
-    if (s < TSD_NO_Y ? !host_in[s] : !host_out[s - TSD_NO_Y]) TSD_FAIL(TSD_E_ARG, "norm_run: operand slot %d is NULL", s);
-  }
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  NdBufs bufs;
-  for (int s = 0; s < TSD_NO_COUNT; s++) {
-    if (!ext[s]) continue;
-    const int es = nd_elem_bytes(s);
-    const size_t bytes = 2 * GD_GUARD + (size_t)ext[s] * es;
-    HIP_TRY(hipMalloc((void**)&bufs.p[s], bytes));
-    if (es == 2) HIP_TRY(hipMemsetD16Async((hipDeviceptr_t)bufs.p[s], GD_NAN16, bytes / 2, st));
-    else HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)bufs.p[s], (int)GD_NAN32, bytes / 4, st));
-    if (s < TSD_NO_Y) HIP_TRY(hipMemcpyAsync(bufs.p[s] + GD_GUARD, host_in[s], (size_t)ext[s] * es, hipMemcpyHostToDevice, st));
-  }
-  auto at = [&](int s) -> void* { return bufs.p[s] ? (void*)(bufs.p[s] + GD_GUARD) : nullptr; };
-  const float eps = nd_float(d[TSD_ND_EPS]), gamma = nd_float(d[TSD_ND_GAMMA]);
-  NormAffine aff;
-  aff.w = (const float*)at(TSD_NO_W); aff.b = (const float*)at(TSD_NO_BIAS); aff.torch_rstd = (int)d[TSD_ND_TORCH_RSTD];
-  const NormAffine* affp = (aff.w || aff.b || aff.torch_rstd) ? &aff : nullptr;
-  ctx->gn_last = GnPlan();
-  const int r = run_planned(ctx, [&]() -> int {
-    if (mode == TSD_NM_LAYERNORM)
-      return launch_layernorm(ctx, (const half_t*)at(TSD_NO_X0), d[TSD_ND_ROWS], C, (int)d[TSD_ND_LD0], eps, (half_t*)at(TSD_NO_Y),
-                              (int)d[TSD_ND_LDY], affp);
-    if (mode == TSD_NM_GN_FINALIZE)
-      return launch_gn_finalize(ctx, (const float*)at(TSD_NO_PART0), ns, B, HW, C, G, eps, gamma, (float*)at(TSD_NO_STATS));
-    if (mode == TSD_NM_GN_STATS)
-      return launch_gn_stats(ctx, (const half_t*)at(TSD_NO_X0), (int)d[TSD_ND_LD0], B, HW, C, G, eps, gamma, (float*)at(TSD_NO_STATS));
-    NormSrc src;
-    src.x0 = (const half_t*)at(TSD_NO_X0); src.ld0 = (int)d[TSD_ND_LD0]; src.C0 = (int)d[TSD_ND_C0];
-    src.x1 = (const half_t*)at(TSD_NO_X1); src.ld1 = (int)d[TSD_ND_LD1];
-    const int sm = (int)d[TSD_ND_STATS];
-    const GnComposite gc = composite_of((const float*)at(TSD_NO_PART0), (const float*)at(TSD_NO_PART1));
-    return launch_groupnorm(ctx, src, B, HW, C, G, eps, gamma, (int)d[TSD_ND_SILU], (half_t*)at(TSD_NO_Y), (int)d[TSD_ND_LDY],
-                            sm == 1 ? (const float*)at(TSD_NO_PART0) : nullptr, sm == 1 ? ns : 0, affp, sm == 2 ? &gc : nullptr);
-  });
-  HIP_TRY(hipStreamSynchronize(st));
-  nd_plan_info(ctx->gn_last, info);  // what the launch itself planned (zeros when it was refused)
-  int64_t changed = 0;
-  for (int s = 0; s < TSD_NO_COUNT; s++) {  // inputs too: a norm launch writes none of them
-    if (!ext[s]) continue;
-    const int es = nd_elem_bytes(s);
-    const size_t bytes = 2 * GD_GUARD + (size_t)ext[s] * es;
-    std::vector<char> got(bytes);
-    HIP_TRY(hipMemcpy(got.data(), bufs.p[s], bytes, hipMemcpyDeviceToHost));
-    const int64_t g0 = (int64_t)(GD_GUARD / es), total = (int64_t)(bytes / es);
-    const int64_t width = C, pitch = s == TSD_NO_Y ? d[TSD_ND_LDY] : 0;
-    for (int64_t i = 0; i < total; i++) {
-      const int64_t j = i - g0;
-      const bool inside = j >= 0 && j < ext[s];
-      if (inside && s < TSD_NO_Y) continue;                              // input payload
-      if (inside && s == TSD_NO_STATS) continue;                         // dense output
-      if (inside && s == TSD_NO_Y && j % pitch < width) continue;        // logical element of y
-      const bool same = es == 2 ? memcmp(&got[(size_t)i * 2], &GD_NAN16, 2) == 0 : memcmp(&got[(size_t)i * 4], &GD_NAN32, 4) == 0;
-      if (!same) changed++;
-    }
-    if (s >= TSD_NO_Y) memcpy(host_out[s - TSD_NO_Y], &got[GD_GUARD], (size_t)ext[s] * es);
-  }
-  info[TSD_NI_CHANGED] = changed;
-  return r;
-}
-
-// ---- attention core / row softmax on caller operands (tests/attn_ref.py holds every kernel to an fp64 reference) ---------------------
-namespace {
-int ad_elem_bytes(int slot, const int64_t* d) {
-  return d[TSD_AD_MODE] == TSD_AM_SOFTMAX_ROWS && d[TSD_AD_DTYPE] == 0 && (slot == TSD_AO_X || slot == TSD_AO_O) ? 4 : 2;
-}
-// Element extent of every operand the described launch reads or writes.  An empty sequence is sized as one row (the launcher refuses it).
-int ad_extents(const int64_t* d, int64_t* e) {
-  for (int i = 0; i < TSD_AO_COUNT; i++) e[i] = 0;
-#define AD_REQ(cond) \
-  if (!(cond)) TSD_FAIL(TSD_E_ARG, "attn_run: descriptor cannot be sized (%s)", #cond)
-  AD_REQ(d[TSD_AD_VERSION] == TSD_AD_VERSION_1);
-  const int64_t mode = d[TSD_AD_MODE], lim = 1LL << 28;
-  AD_REQ(mode == TSD_AM_ATTN || mode == TSD_AM_SOFTMAX_ROWS);
-  if (mode == TSD_AM_ATTN) {
-    const int64_t B = d[TSD_AD_B], H = d[TSD_AD_H], hd = d[TSD_AD_D];
-    const int64_t Sq = std::max<int64_t>(d[TSD_AD_SQ], 1), Sk = std::max<int64_t>(d[TSD_AD_SK], 1);
-    AD_REQ(B > 0 && B <= 4096 && H > 0 && H <= 4096 && hd > 0 && hd <= 4096 && H * hd <= 65536);
-    AD_REQ(d[TSD_AD_SQ] >= 0 && d[TSD_AD_SK] >= 0 && Sq <= (1 << 20) && Sk <= (1 << 20));
-    AD_REQ(d[TSD_AD_KERNEL] >= 0 && d[TSD_AD_KERNEL] <= 3 && (d[TSD_AD_DIAG] == 0 || d[TSD_AD_DIAG] == 1));
-    const int64_t C = H * hd;
-    for (int f : {TSD_AD_LDQ, TSD_AD_LDK, TSD_AD_LDO}) AD_REQ(d[f] >= C && d[f] <= (1 << 20));
-    AD_REQ(d[TSD_AD_LDVT] >= Sk && d[TSD_AD_LDVT] <= (1 << 21));
-    const int64_t Skv = std::min((Sk + 7) / 8 * 8, d[TSD_AD_LDVT]);
-    AD_REQ(d[TSD_AD_SQB] >= Sq * d[TSD_AD_LDQ] && d[TSD_AD_SKB] >= Sk * d[TSD_AD_LDK] && d[TSD_AD_SVTB] >= C * d[TSD_AD_LDVT] &&
-           d[TSD_AD_SOB] >= Sq * d[TSD_AD_LDO]);
-    for (int f : {TSD_AD_SQB, TSD_AD_SKB, TSD_AD_SVTB, TSD_AD_SOB}) AD_REQ(d[f] < lim);
-    e[TSD_AO_Q] = (B - 1) * d[TSD_AD_SQB] + (Sq - 1) * d[TSD_AD_LDQ] + C;
-    e[TSD_AO_K] = (B - 1) * d[TSD_AD_SKB] + (Sk - 1) * d[TSD_AD_LDK] + C;
-    e[TSD_AO_VT] = (B - 1) * d[TSD_AD_SVTB] + (C - 1) * d[TSD_AD_LDVT] + Skv;
-    e[TSD_AO_O] = (B - 1) * d[TSD_AD_SOB] + (Sq - 1) * d[TSD_AD_LDO] + C;
-  } else {
-    const int64_t rows = d[TSD_AD_ROWS], cols = d[TSD_AD_COLS], ld = d[TSD_AD_LD], zt = d[TSD_AD_ZERO_TO];
-    AD_REQ(rows > 0 && rows <= (1 << 20) && cols > 0 && cols <= (1 << 20) && ld >= cols && ld <= (1 << 20));
-    AD_REQ(d[TSD_AD_DTYPE] == 0 || d[TSD_AD_DTYPE] == 1);
-    AD_REQ(d[TSD_AD_CAUSAL] >= 0 && d[TSD_AD_CAUSAL] <= (1 << 20) && zt >= 0);
-    if (d[TSD_AD_DTYPE] == 0) AD_REQ(ld == cols && d[TSD_AD_CAUSAL] == 0 && zt == 0);  // launch_softmax_rows_f32 is dense and never causal
-    if (d[TSD_AD_CAUSAL] == 0) AD_REQ(zt == 0);
-    AD_REQ(zt <= ld);  // a wider ZERO_TO would be written outside the operand; launch_softmax_rows_f16_causal refuses it as well
-    e[TSD_AO_X] = e[TSD_AO_O] = (rows - 1) * ld + std::max(cols, zt);
-  }
-  for (int s = 0; s < TSD_AO_COUNT; s++) AD_REQ(e[s] >= 0 && e[s] <= lim);
-#undef AD_REQ
-  return TSD_OK;
-}
-struct AdBufs {
-  char* p[TSD_AO_COUNT] = {};
-  ~AdBufs() { for (char* q : p) if (q) (void)hipFree(q); }
-};
-}  // namespace
-
-extern "C" int tsd_debug_attn_run(tsd_ctx* ctx, const int64_t* desc, int n, const void* const* host_in, void* const* host_out,
-                                  int64_t* ext, int64_t* info) {
-  NOTNULL(desc); NOTNULL(ext);
-  if (n < TSD_AD_COUNT) TSD_FAIL(TSD_E_ARG, "attn_run: %d descriptor fields", n);
-  TSD_TRY(ad_extents(desc, ext));
-  const int64_t* d = desc;
-  const bool attn = d[TSD_AD_MODE] == TSD_AM_ATTN;
-  if (info) for (int i = 0; i < TSD_AI_COUNT; i++) info[i] = 0;
-  if (!host_in) {  // sizing only: no context or device needed; the dispatcher's choice under the default options
-    if (info && attn && attn_fused_supported((int)d[TSD_AD_D]) && d[TSD_AD_SQ] > 0 && d[TSD_AD_SK] > 0) {
-      TsdOptions o;
-      o.attn_qb_force = (int)d[TSD_AD_KERNEL]; o.attn_diag = (int)d[TSD_AD_DIAG];
-      const AttnPlan p = attn_plan(o, (int)d[TSD_AD_B], (int)d[TSD_AD_H], (int)d[TSD_AD_D], (int)d[TSD_AD_SQ], (int)d[TSD_AD_SK]);
-      info[TSD_AI_KERNEL] = p.kernel; info[TSD_AI_DIAG] = p.diag; info[TSD_AI_XCD_MAP] = p.xcd_map;
-    }
-    return TSD_OK;
-  }
-  NOTNULL(ctx); NOTNULL(host_out); NOTNULL(info);
-  const bool inplace = !attn && d[TSD_AD_DTYPE] == 1;
-  for (int s = 0; s < TSD_AO_COUNT; s++) {
-    if (!ext[s]) continue;
-    if (s < TSD_AO_O ? !host_in[s] : !host_out[0]) TSD_FAIL(TSD_E_ARG, "attn_run: operand slot %d is NULL", s);
-  }
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipStream_t st = ctx->stream;
-  AdBufs bufs;
-  for (int s = 0; s < TSD_AO_COUNT; s++) {
-    if (!ext[s]) continue;
-    const int es = ad_elem_bytes(s, d);
-    const size_t bytes = 2 * GD_GUARD + (size_t)ext[s] * es;
-    HIP_TRY(hipMalloc((void**)&bufs.p[s], bytes));
-    if (es == 2) HIP_TRY(hipMemsetD16Async((hipDeviceptr_t)bufs.p[s], GD_NAN16, bytes / 2, st));
-    else HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)bufs.p[s], (int)GD_NAN32, bytes / 4, st));
-    const void* src = s < TSD_AO_O ? host_in[s] : (inplace ? host_in[TSD_AO_X] : nullptr);  // fp16 rows are overwritten in place: O starts as X
-    if (src) HIP_TRY(hipMemcpyAsync(bufs.p[s] + GD_GUARD, src, (size_t)ext[s] * es, hipMemcpyHostToDevice, st));
-  }
-  auto at = [&](int s) -> void* { return bufs.p[s] ? (void*)(bufs.p[s] + GD_GUARD) : nullptr; };
-  int exact0 = 0, exact1 = 0;
-  HIP_TRY(hipStreamSynchronize(st));
-  HIP_TRY(hipMemcpy(&exact0, ctx->status + 2, sizeof(int), hipMemcpyDeviceToHost));
-  const int prev_force = ctx->opt.attn_qb_force, prev_diag = ctx->opt.attn_diag;
-  ctx->attn_last = AttnPlan();
-  int r;
-  if (attn) {
-    ctx->opt.attn_qb_force = (int)d[TSD_AD_KERNEL]; ctx->opt.attn_diag = (int)d[TSD_AD_DIAG];
-    AttnArgs a;
-    a.Q = (const half_t*)at(TSD_AO_Q); a.ldq = (int)d[TSD_AD_LDQ]; a.sQ = d[TSD_AD_SQB];
-    a.K = (const half_t*)at(TSD_AO_K); a.ldk = (int)d[TSD_AD_LDK]; a.sK = d[TSD_AD_SKB];
-    a.Vt = (const half_t*)at(TSD_AO_VT); a.ldvt = (int)d[TSD_AD_LDVT]; a.sVt = d[TSD_AD_SVTB];
-    a.O = (half_t*)at(TSD_AO_O); a.ldo = (int)d[TSD_AD_LDO]; a.sO = d[TSD_AD_SOB];
-    a.B = (int)d[TSD_AD_B]; a.H = (int)d[TSD_AD_H]; a.d = (int)d[TSD_AD_D]; a.Sq = (int)d[TSD_AD_SQ]; a.Sk = (int)d[TSD_AD_SK];
-    a.scale = nd_float(d[TSD_AD_SCALE]);
-    r = run_planned(ctx, [&]() -> int { return launch_flash_attention(ctx, a); });
-    ctx->opt.attn_qb_force = prev_force; ctx->opt.attn_diag = prev_diag;
-  } else {
-    const int64_t rows = d[TSD_AD_ROWS];
-    const int cols = (int)d[TSD_AD_COLS], ld = (int)d[TSD_AD_LD];
-    r = run_planned(ctx, [&]() -> int {
-      if (d[TSD_AD_DTYPE] == 0) return launch_softmax_rows_f32(ctx, (const float*)at(TSD_AO_X), rows, cols, (float*)at(TSD_AO_O));
-      if (d[TSD_AD_CAUSAL] > 0)
-        return launch_softmax_rows_f16_causal(ctx, (half_t*)at(TSD_AO_O), rows, cols, ld, (int)d[TSD_AD_CAUSAL], (int)d[TSD_AD_ZERO_TO]);
-      return launch_softmax_rows_f16(ctx, (half_t*)at(TSD_AO_O), rows, cols, ld);
-    });
-  }
-  HIP_TRY(hipStreamSynchronize(st));
-  HIP_TRY(hipMemcpy(&exact1, ctx->status + 2, sizeof(int), hipMemcpyDeviceToHost));
-  info[TSD_AI_KERNEL] = attn ? ctx->attn_last.kernel : ctx->attn_last.softmax;
-  info[TSD_AI_DIAG] = ctx->attn_last.diag; info[TSD_AI_XCD_MAP] = ctx->attn_last.xcd_map;
-  info[TSD_AI_EXACT_WGS] = exact1 - exact0;
-  int64_t changed = 0;
-  for (int s = 0; s < TSD_AO_COUNT; s++) {  // inputs too: the launch writes none of them
-    if (!ext[s]) continue;
-    const int es = ad_elem_bytes(s, d);
-    const size_t bytes = 2 * GD_GUARD + (size_t)ext[s] * es;
-    std::vector<char> got(bytes);
-    HIP_TRY(hipMemcpy(got.data(), bufs.p[s], bytes, hipMemcpyDeviceToHost));
-    const int64_t g0 = (int64_t)(GD_GUARD / es), total = (int64_t)(bytes / es);
-    const char* x0 = inplace ? (const char*)host_in[TSD_AO_X] : nullptr;
-    for (int64_t i = 0; i < total; i++) {
-      const int64_t j = i - g0;
-      const bool inside = j >= 0 && j < ext[s];
-      if (inside && s < TSD_AO_O) continue;  // input payload
-      if (inside && attn) {                  // logical element of O: [b][q][c < H*d]
-        const int64_t jb = j % d[TSD_AD_SOB], b = j / d[TSD_AD_SOB];
-        if (b < d[TSD_AD_B] && jb / d[TSD_AD_LDO] < d[TSD_AD_SQ] && jb % d[TSD_AD_LDO] < d[TSD_AD_H] * d[TSD_AD_D]) continue;
-      }
-      if (inside && !attn) {
-        if (j % d[TSD_AD_LD] < std::max(d[TSD_AD_COLS], d[TSD_AD_ZERO_TO])) continue;
-        if (x0) {  // a pitch gap of rows processed in place keeps what the caller put there
-          if (memcmp(&got[(size_t)i * 2], x0 + (size_t)j * 2, 2)) changed++;
-          continue;
-        }
-      }
-      const bool same = es == 2 ? memcmp(&got[(size_t)i * 2], &GD_NAN16, 2) == 0 : memcmp(&got[(size_t)i * 4], &GD_NAN32, 4) == 0;
-      if (!same) changed++;
-    }
-    if (s == TSD_AO_O) memcpy(host_out[0], &got[GD_GUARD], (size_t)ext[s] * es);
-  }
-  info[TSD_AI_CHANGED] = changed;
-  return r;
 }
 
 extern "C" int tsd_debug_gn_path_counts(tsd_ctx* ctx, int64_t* counts, int n, int reset) {

@@ -3,6 +3,10 @@
 #pragma once
 #include "model.h"
 
+// how the C-ABI entry points (api_ops.cpp, api_model.cpp, api_replay.cpp) refuse a NULL pointer argument
+#define NOTNULL(p) \
+  if (!(p)) TSD_FAIL(TSD_E_ARG, "%s: argument '%s' is NULL", __func__, #p)
+
 // channel-concat view of up to two NHWC tensors with identical (B,H,W) (diffusion.mojo:253-270)
 struct CatSrc {
   const half_t* p0 = nullptr; int ld0 = 0; int C0 = 0;

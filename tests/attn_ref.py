@@ -51,15 +51,11 @@ output; columns [kept, zero_to) of the causal form are exact zeros) and `softmax
 """
 import functools
 import math
-import os
-import re
-
 import numpy as np
 
-from gemm_ref import NAN16, NAN32, _enum, f32_bits
+import replay
+from replay import NAN16, NAN32, bits_f32, f32_bits
 
-_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_HDR = os.path.join(_ROOT, "include", "tsd.h")
 U32 = 2.0 ** -24
 H16 = 2.0 ** -11
 LOG2E = 1.4426950408889634
@@ -69,11 +65,9 @@ EXP_ULPS = 4.0
 
 
 def _parse():
-    txt = re.sub(r"/\*.*?\*/", "", open(_HDR).read(), flags=re.S)
-    strip = lambda e, p: {k[len(p):]: v for k, v in _enum(txt, e).items()}
-    ver = int(re.search(r"#define\s+TSD_AD_VERSION_1\s+(\d+)", txt).group(1))
-    return (strip("tsd_attn_desc_field", "TSD_AD_"), strip("tsd_attn_operand", "TSD_AO_"), strip("tsd_attn_info", "TSD_AI_"),
-            strip("tsd_attn_mode", "TSD_AM_"), strip("tsd_attn_kernel", "TSD_AK_"), ver)
+    txt = replay.header()
+    return replay.enums(txt, {"TSD_AD_": "tsd_attn_desc_field", "TSD_AO_": "tsd_attn_operand", "TSD_AI_": "tsd_attn_info",
+                              "TSD_AM_": "tsd_attn_mode", "TSD_AK_": "tsd_attn_kernel"}) + [replay.version(txt, "TSD_AD_VERSION_1")]
 
 
 AD, AO, AI, AM, AK, AD_VERSION = _parse()
@@ -117,11 +111,15 @@ def softmax_desc(rows, cols, ld=None, dtype=1, causal=0, zero_to=0):
 
 
 def scale_of(d):
-    return float(np.array([F(d, "SCALE")], np.uint32).view(np.float32)[0])
+    return bits_f32(F(d, "SCALE"))
 
 
 def skv_of(d):
     return min(round_up(max(F(d, "SK"), 1), 8), F(d, "LDVT"))
+
+
+def dtype_of(s, d):
+    return np.float32 if F(d, "MODE") == AM["SOFTMAX_ROWS"] and F(d, "DTYPE") == 0 and s in ("X", "O") else np.float16
 
 
 def extents(d):

@@ -37,50 +37,26 @@ import re
 
 import numpy as np
 
-_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_HDR = os.path.join(_ROOT, "include", "tsd.h")
-_COMMON = os.path.join(_ROOT, "stable-diffusion.mojo_amd", "csrc", "common.h")
+import replay
+from replay import NAN16, NAN32, bits_f32, f32_bits
+
+_COMMON = os.path.join(replay.ROOT, "stable-diffusion.mojo_amd", "csrc", "common.h")
 U32 = 2.0 ** -24
 GELU_DMAX = 1.13
-NAN16 = np.array([0x7E5A], np.uint16).view(np.float16)[0]
-NAN32 = np.array([0x7FC5A5A5], np.uint32).view(np.float32)[0]
-
-
-def _enum(txt, name):
-    body = re.search(r"enum\s+" + name + r"\s*\{(.*?)\}", txt, re.S).group(1)
-    out, v = {}, 0
-    for item in body.split(","):
-        item = item.strip()
-        if not item:
-            continue
-        if "=" in item:
-            k, val = (s.strip() for s in item.split("="))
-            v = int(val, 0)
-        else:
-            k = item
-        out[k] = v
-        v += 1
-    return out
 
 
 def _parse():
-    txt = re.sub(r"/\*.*?\*/", "", open(_HDR).read(), flags=re.S)
-    gd = {k[len("TSD_GD_"):]: v for k, v in _enum(txt, "tsd_gemm_desc_field").items()}
-    go = {k[len("TSD_GO_"):]: v for k, v in _enum(txt, "tsd_gemm_operand").items()}
-    ver = int(re.search(r"#define\s+TSD_GD_VERSION_1\s+(\d+)", txt).group(1))
+    txt = replay.header()
+    gd, go = replay.enums(txt, {"TSD_GD_": "tsd_gemm_desc_field", "TSD_GO_": "tsd_gemm_operand"})
     ctxt = re.sub(r"//[^\n]*", "", open(_COMMON).read())
     epi = {k: int(v) for k, v in re.findall(r"\bEPI_([A-Z0-9_]+)\s*=\s*(\d+)", ctxt)}
-    return gd, go, ver, epi
+    return gd, go, replay.version(txt, "TSD_GD_VERSION_1"), epi
 
 
 GD, GO, GD_VERSION, EPI = _parse()
 COUNT = GD["COUNT"]
 INPUTS = ("A0", "A1", "A2", "W", "WT1", "R", "BIAS", "ROWVEC")
 OUTPUTS = ("C", "VT", "GN")
-
-
-def f32_bits(x):
-    return int(np.array([x], np.float32).view(np.uint32)[0])
 
 
 def new_desc(**f):
@@ -124,7 +100,7 @@ def _g(d, k):
 
 
 def out_scale(d):
-    return float(np.array([_g(d, "OUT_SCALE")], np.uint32).view(np.float32)[0])
+    return bits_f32(_g(d, "OUT_SCALE"))
 
 
 def c_cols(d):
@@ -139,6 +115,12 @@ def kw(d):
 
 def samples(d):
     return _g(d, "M") // (_g(d, "HO") * _g(d, "WO")) if _g(d, "CONV") else 1
+
+
+def dtype_of(s, d):
+    """numpy type of operand slot s (the entry's gd_elem_bytes)."""
+    f32 = s in ("BIAS", "ROWVEC", "GN") or (s == "C" and _g(d, "EPI") & EPI["OUT_F32"])
+    return np.float32 if f32 else np.float16
 
 
 def extents(d):
@@ -262,7 +244,7 @@ def make_operands(d, seed, scale=None):
     for s, n in extents(d).items():
         if not n or s in OUTPUTS:
             continue
-        dt = np.float32 if s in ("BIAS", "ROWVEC") else np.float16
+        dt = dtype_of(s, d)
         x = (rng.uniform(-1.0, 1.0, n) * sc[s]).astype(dt)
         x[~masks[s]] = NAN32 if dt == np.float32 else NAN16
         ops[s] = x

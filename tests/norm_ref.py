@@ -43,15 +43,12 @@ below 2^-10 (|ref| + 1) at every element.
 `emulate` restates the device arithmetic in numpy - fp32 sums in the kernel's order, double finish, fp32 apply, fp16 store - with
 seeded mutations (a dropped slab, a shifted chunk boundary, ...) that the bound must reject.
 """
-import os
-import re
-
 import numpy as np
 
-from gemm_ref import NAN16, NAN32, _enum, f32_bits
+import replay
+from replay import NAN16, NAN32, f32_bits
+from replay import bits_f32 as _f32
 
-_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-_HDR = os.path.join(_ROOT, "include", "tsd.h")
 U32 = 2.0 ** -24
 H16 = 2.0 ** -11
 SILU_DMAX = 1.1          # max |silu'(x)| = 1.0998
@@ -65,13 +62,9 @@ LOG2E32 = float(np.float32(1.4426950408889634))
 
 
 def _parse():
-    txt = re.sub(r"/\*.*?\*/", "", open(_HDR).read(), flags=re.S)
-    nd = {k[len("TSD_ND_"):]: v for k, v in _enum(txt, "tsd_norm_desc_field").items()}
-    no = {k[len("TSD_NO_"):]: v for k, v in _enum(txt, "tsd_norm_operand").items()}
-    ni = {k[len("TSD_NI_"):]: v for k, v in _enum(txt, "tsd_norm_info").items()}
-    nm = {k[len("TSD_NM_"):]: v for k, v in _enum(txt, "tsd_norm_mode").items()}
-    ver = int(re.search(r"#define\s+TSD_ND_VERSION_1\s+(\d+)", txt).group(1))
-    return nd, no, ni, nm, ver
+    txt = replay.header()
+    return replay.enums(txt, {"TSD_ND_": "tsd_norm_desc_field", "TSD_NO_": "tsd_norm_operand", "TSD_NI_": "tsd_norm_info",
+                              "TSD_NM_": "tsd_norm_mode"}) + [replay.version(txt, "TSD_ND_VERSION_1")]
 
 
 ND, NO, NI, NM, ND_VERSION = _parse()
@@ -79,10 +72,6 @@ COUNT = ND["COUNT"]
 INPUTS = ("X0", "X1", "PART0", "PART1", "W", "BIAS")
 OUTPUTS = ("Y", "STATS")
 GN_UNROLL = 4
-
-
-def _f32(bits):
-    return float(np.array([bits], np.uint32).view(np.float32)[0])
 
 
 def gn_desc(HW, C, groups, B=3, mode="GROUPNORM", C0=None, ld0=None, ld1=None, ldy=None, eps=1e-5, gamma=1.0, silu=0, has_w=0,
@@ -110,6 +99,10 @@ def F(d, k):
 
 def mode_of(d):
     return {v: k for k, v in NM.items()}[F(d, "MODE")]
+
+
+def dtype_of(s, d):
+    return np.float16 if s in ("X0", "X1", "Y") else np.float32
 
 
 def extents(d):

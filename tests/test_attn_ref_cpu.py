@@ -3,26 +3,20 @@ csrc/kernels_attn.hip / kernels_attn8.hip and of the row-softmax kernels - is it
 attention; the operand extents and the dispatcher's choice agree with tsd_debug_attn_run's sizing-only mode (production shapes and one
 shape just below each threshold pinned); the emulation stays inside the bound on every sweep input and takes the exact repeat where
 the prediction says it must; every seeded defect that can change an output is rejected on a sweep input the GPU test runs too."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import attn_ref as A
+import replay
 from oracle import ops as O
 
-_i64p = C.POINTER(C.c_int64)
 SWEEP = A.sweep()
 NAMES = [s[0] for s in SWEEP]
 
 
 def _size(tsd_mod, d, n=None):
-    lib = tsd_mod._lib.lib()
-    d = np.ascontiguousarray(d, np.int64)
-    ext = np.zeros(A.AO["COUNT"], np.int64)
     info = np.full(A.AI["COUNT"], -1, np.int64)
-    rc = lib.tsd_debug_attn_run(None, d.ctypes.data_as(_i64p), len(d) if n is None else n, None, None, ext.ctypes.data_as(_i64p),
-                                info.ctypes.data_as(_i64p))
+    rc, ext = replay.size("tsd_debug_attn_run", d, n, info)
     return rc, {s: int(ext[A.AO[s]]) for s in A.INPUTS + ("O",)}, {k: int(info[v]) for k, v in A.AI.items() if k != "COUNT"}
 
 

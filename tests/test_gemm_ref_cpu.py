@@ -7,6 +7,7 @@ import torch
 import torch.nn.functional as F
 
 import gemm_ref as G
+import replay
 from oracle import ops as oops
 
 E = G.EPI
@@ -269,14 +270,10 @@ def test_replay_entry_sizes_like_the_reference_and_refuses_inconsistent_geometry
     """tsd_debug_gemm_run with no operands only sizes (no device needed).  Its extents equal gemm_ref's; a conv descriptor whose
     output size does not follow from source, stride and padding - or whose first-tap coordinate would not fit the kernel's
     11-bit field - is refused before anything is allocated."""
-    import ctypes as C
     from tsd._lib import lib
-    p = C.POINTER(C.c_int64)
 
     def size(d):
-        d = np.ascontiguousarray(d, np.int64)
-        ext = np.zeros(G.GO["COUNT"], np.int64)
-        return lib().tsd_debug_gemm_run(None, d.ctypes.data_as(p), len(d), -1, None, None, ext.ctypes.data_as(p), None), ext
+        return replay.size("tsd_debug_gemm_run", d, extra=(-1,))
 
     assert lib().tsd_debug_gemm_run(None, None, 0, -1, None, None, None, None) != 0
     good = [G.conv_desc(B=2, Hs=9, Ws=7, Cin=64, N=20, stride=2, epi=PROD), G.conv_desc(B=1, Hs=8, Ws=6, Cin=64, N=8, stride=2, pad=0, pad_br=1),

@@ -18,23 +18,15 @@ prediction.  Row softmax: fp16 0.999 (one fp16 rounding: an output half an ulp f
 
 Dispatcher mode 0 on H = 8, Sq = 4096 (the shape at which it picks the 8-wave / 64-query kernels) is asserted through the sizing call
 only (tests/test_attn_ref_cpu.py): its fp64 reference is too large for a test of a few seconds; here mode 0 runs at a small shape."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import attn_ref as A
+import replay
 
 pytestmark = pytest.mark.gpu
-_i64p = C.POINTER(C.c_int64)
 SWEEP = A.sweep()
 NAMES = [s[0] for s in SWEEP]
-NAN16_BITS = A.NAN16.view(np.uint16)
-
-
-def _lib():
-    from tsd._lib import lib
-    return lib()
 
 
 @pytest.fixture(scope="module")
@@ -46,36 +38,18 @@ def ctx(gpu_ctx, tsd_mod):
 
 def run(ctx, d, ops):
     """(status, flat output, info {CHANGED, KERNEL, EXACT_WGS, DIAG, XCD_MAP})."""
-    lib = _lib()
-    d = np.ascontiguousarray(d, np.int64)
-    ext = np.zeros(A.AO["COUNT"], np.int64)
-    assert lib.tsd_debug_attn_run(ctx.h, d.ctypes.data_as(_i64p), len(d), None, None, ext.ctypes.data_as(_i64p), None) == 0, \
-        lib.tsd_last_error().decode()
-    want = A.extents(d)
-    assert {s: int(ext[A.AO[s]]) for s in want} == want, "the entry and tests/attn_ref.py size the operands differently"
-    ins = (C.c_void_p * len(A.INPUTS))()
-    for s in A.INPUTS:
-        if want[s]:
-            assert ops[s].size == want[s] and ops[s].flags.c_contiguous, s
-            ins[A.AO[s]] = ops[s].ctypes.data
-    softmax32 = A.F(d, "MODE") == A.AM["SOFTMAX_ROWS"] and A.F(d, "DTYPE") == 0
-    out = np.empty(want["O"], np.float32 if softmax32 else np.float16)
-    outp = (C.c_void_p * 1)(out.ctypes.data)
-    info = np.zeros(A.AI["COUNT"], np.int64)
-    rc = lib.tsd_debug_attn_run(ctx.h, d.ctypes.data_as(_i64p), len(d), ins, outp, ext.ctypes.data_as(_i64p), info.ctypes.data_as(_i64p))
-    return rc, out, {k: int(info[v]) for k, v in A.AI.items() if k != "COUNT"}
+    rc, outs, info = replay.run("tsd_debug_attn_run", ctx, d, ops, A.AO, A.INPUTS, ("O",), A.dtype_of, A.extents)
+    return rc, outs["O"], {k: int(info[v]) for k, v in A.AI.items() if k != "COUNT"}
 
 
 def verify(ctx, name, d, ops, ref=None, xcd=0):
     """Run d and hold it to the reference; returns (flat output, info, worst error / bound)."""
     rc, out, info = run(ctx, d, ops)
-    assert rc == 0, f"{name}: status {rc}: {_lib().tsd_last_error().decode()}"
+    assert rc == 0, f"{name}: status {rc}: {replay.lib().tsd_last_error().decode()}"
     p = A.plan(d, attn_xcd=xcd)
     assert {k: info[k] for k in p} == p, f"{name}: the launch took another path: {info}, expected {p}"
     assert info["CHANGED"] == 0, f"{name}: {info['CHANGED']} guard / pitch-gap elements written"
-    gap = np.ones(out.size, bool)
-    gap[A.o_index(d).ravel()] = False
-    assert (out.view(np.uint16)[gap] == NAN16_BITS).all(), f"{name}: a pitch gap of O was written"
+    replay.assert_gaps_hold_fill(out, A.o_index(d), f"{name}: O")
     pr = A.predict_repeat(d, ops)
     must, may = int((pr == 1).sum()), int((pr == 0).sum())
     fails, ratio = A.check(d, ops, out, ref=ref)
@@ -109,17 +83,9 @@ def test_dispatcher_by_shape_at_a_small_shape(ctx):
 
 
 # ---- the XCD map ------------------------------------------------------------------------------------------------------------------
-def _ctx_with(tsd_mod, gpu_ctx, monkeypatch, var, value):
-    """A context created with an option in the environment (read once, by tsd_ctx_create); the environment is restored at once."""
-    monkeypatch.setenv(var, str(value))
-    c = tsd_mod.Context(gpu_ctx.device)
-    monkeypatch.delenv(var)
-    return c
-
-
 @pytest.mark.parametrize("hd", (40, 80))
 def test_xcd_map_gives_the_same_bits(ctx, gpu_ctx, tsd_mod, monkeypatch, hd):
-    c = _ctx_with(tsd_mod, gpu_ctx, monkeypatch, "TSD_ATTN_XCD", 1)
+    c = replay.ctx_with(tsd_mod, gpu_ctx, monkeypatch, "TSD_ATTN_XCD", 1)
     try:
         for mode in ((1, 2, 3) if hd == 40 else (0,)):
             d = A.attn_desc(2, 8, hd, 256, 512, kernel=mode)
@@ -161,7 +127,7 @@ def test_public_cross_attention_at_77_keys_does_not_read_the_arena(gpu_ctx, tsd_
     m = tsd_mod.Cross_Attention(8, 320, 768, seed=3)      # one set of weights; only the context differs
     ys = []
     for byte in (0x7E, 0x00):
-        m.ctx = _ctx_with(tsd_mod, gpu_ctx, monkeypatch, "TSD_DEBUG_POISON", byte)
+        m.ctx = replay.ctx_with(tsd_mod, gpu_ctx, monkeypatch, "TSD_DEBUG_POISON", byte)
         try:
             ys.append(m.forward(x, context))
         finally:
@@ -192,7 +158,7 @@ def test_refused_launches_leave_the_output_untouched(ctx, name, d):
     rc, out, info = run(ctx, d, ops)
     assert rc != 0, f"{name} was not refused"
     assert all(v == 0 for v in info.values()), info
-    assert (out.view(np.uint16) == NAN16_BITS).all(), f"{name}: O was written"
+    replay.assert_untouched({"O": out}, name)
 
 
 # ---- row softmax -------------------------------------------------------------------------------------------------------------------
@@ -203,7 +169,7 @@ SM_SWEEP = A.softmax_sweep()
 def test_softmax_rows_match_the_fp64_reference(ctx, name, d):
     x = A.softmax_inputs(d, seed=5)
     rc, out, info = run(ctx, d, {"X": x})
-    assert rc == 0, _lib().tsd_last_error().decode()
+    assert rc == 0, replay.lib().tsd_last_error().decode()
     assert info["KERNEL"] == A.softmax_kernel(d), f"{name}: the launcher took kernel {info['KERNEL']}"
     assert info["CHANGED"] == 0, f"{name}: {info['CHANGED']} guard / pitch-gap elements written"
     fails, ratio = A.softmax_check(d, x, out)

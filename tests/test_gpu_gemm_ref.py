@@ -9,16 +9,12 @@ import numpy as np
 import pytest
 
 import gemm_ref as G
+import replay
 
 pytestmark = pytest.mark.gpu
 E = G.EPI
 SEED = 1234
 _i64p = C.POINTER(C.c_int64)
-
-
-def _lib():
-    from tsd._lib import lib
-    return lib()
 
 
 @pytest.fixture(scope="module")
@@ -30,35 +26,14 @@ def ctx(gpu_ctx, tsd_mod):
 
 def run(ctx, d, ops, cfg=-1):
     """(status, outputs {C, VT, GN}, info [cfg, ways, guard / gap writes])."""
-    lib = _lib()
-    d = np.ascontiguousarray(d, np.int64)
-    ext = np.zeros(G.GO["COUNT"], np.int64)
-    assert lib.tsd_debug_gemm_run(ctx.h, d.ctypes.data_as(_i64p), len(d), cfg, None, None, ext.ctypes.data_as(_i64p), None) == 0
-    want = G.extents(d)
-    assert {s: int(ext[G.GO[s]]) for s in want} == want, "the entry and tests/gemm_ref.py size the operands differently"
-    ins = (C.c_void_p * G.GO["COUNT"])()
-    for s in G.INPUTS:
-        if want[s]:
-            assert ops[s].size == want[s]
-            ins[G.GO[s]] = ops[s].ctypes.data
-    outs = {}
-    outp = (C.c_void_p * 3)()
-    for i, s in enumerate(G.OUTPUTS):
-        if want[s]:
-            dt = np.float32 if s == "GN" or (s == "C" and int(d[G.GD["EPI"]]) & E["OUT_F32"]) else np.float16
-            outs[s] = np.empty(want[s], dt)
-            outp[i] = outs[s].ctypes.data
-    info = np.zeros(4, np.int64)
-    rc = lib.tsd_debug_gemm_run(ctx.h, d.ctypes.data_as(_i64p), len(d), cfg, ins, outp, ext.ctypes.data_as(_i64p),
-                                info.ctypes.data_as(_i64p))
-    return rc, outs, info
+    return replay.run("tsd_debug_gemm_run", ctx, d, ops, G.GO, G.INPUTS, G.OUTPUTS, G.dtype_of, G.extents, extra=(cfg,))
 
 
 def verify(ctx, d, cfg=-1, seed=0, rows=None, twice=False):
     """Run d on seeded operands and hold it to the reference; returns info."""
     ops = G.make_operands(d, seed)
     rc, outs, info = run(ctx, d, ops, cfg)
-    assert rc == 0, f"cfg {cfg}: status {rc}: {_lib().tsd_last_error().decode()}"
+    assert rc == 0, f"cfg {cfg}: status {rc}: {replay.lib().tsd_last_error().decode()}"
     assert info[2] == 0, f"cfg {info[0]}: {info[2]} guard / pitch-gap elements written"
     M, B = int(d[G.GD["M"]]), int(d[G.GD["BATCH"]])
     rows = np.arange(M * B) if rows is None else rows
@@ -76,7 +51,7 @@ def verify(ctx, d, cfg=-1, seed=0, rows=None, twice=False):
 
 # ---- (a) production replay ---------------------------------------------------------------------------------------------------
 def _recorded(ctx, fn):
-    lib = _lib()
+    lib = replay.lib()
     lib.tsd_debug_gemm_record(ctx.h, 1)
     try:
         fn()
@@ -134,7 +109,7 @@ def test_production_launches_replay_within_the_fp64_bound(ctx, production):
         info = verify(ctx, d, -1, seed=100 + i, rows=G.sample_rows(d, 7 + i), twice=True)
         assert (int(info[0]), int(info[1])) == (int(d[G.GD["CFG"]]), int(d[G.GD["WAYS"]])), "replay chose another tile / split"
         cov[(int(info[0]), int(info[1]))] += 1
-    assert _lib().tsd_debug_splitk_errors(ctx.h) == 0
+    assert replay.lib().tsd_debug_splitk_errors(ctx.h) == 0
     print("\nreplayed launches per (configuration, split-K ways):")
     for (cfg, ways), n in sorted(cov.items()):
         print(f"  cfg {cfg:3d}  ways {ways}  : {n}")
@@ -240,7 +215,7 @@ def test_every_tile_configuration_matches_the_fp64_reference(ctx):
             cpg = int(d[G.GD["N"]]) // int(d[G.GD["GN_GROUPS"]])
             want = {c for c in cfgs if BNW[c] % cpg == 0}
             assert want and gn_ran == want, f"{name}: statistics ran on {sorted(gn_ran)}, expected {sorted(want)}"
-    assert _lib().tsd_debug_splitk_errors(ctx.h) == 0
+    assert replay.lib().tsd_debug_splitk_errors(ctx.h) == 0
     print("\nsweep cases per configuration: " + ", ".join(f"{c}: {n}" for c, n in sorted(counts.items())))
     assert set(counts) >= set(N160 + N128 + THIN + (30, 32)), counts
 
@@ -265,7 +240,7 @@ SPLITS = [
 def test_split_k_matches_the_fp64_reference(ctx, name, d, ways):
     info = verify(ctx, d, -1, seed=3, twice=True)
     assert int(info[1]) == ways, f"{name}: {int(info[1])} slices"
-    assert _lib().tsd_debug_splitk_errors(ctx.h) == 0
+    assert replay.lib().tsd_debug_splitk_errors(ctx.h) == 0
 
 
 def test_optin_256_row_split_matches_the_fp64_reference(gpu_ctx, tsd_mod, monkeypatch):
@@ -276,7 +251,7 @@ def test_optin_256_row_split_matches_the_fp64_reference(gpu_ctx, tsd_mod, monkey
         d = G.dense_desc(M=1024, N=1280, K=5120, epi=E["BIAS_N"] | E["RESIDUAL"], rps_hint=256)
         info = verify(c, d, -1, seed=4, twice=True)
         assert (int(info[0]), int(info[1])) == (51, 4)
-        assert _lib().tsd_debug_splitk_errors(c.h) == 0
+        assert replay.lib().tsd_debug_splitk_errors(c.h) == 0
     finally:
         c.close()
 
@@ -308,15 +283,13 @@ def test_refused_launches_leave_the_outputs_untouched(ctx, name, d, cfg):
     rc, outs, info = run(ctx, d, G.make_operands(d, 6), cfg)
     assert rc != 0, f"{name} was not refused"
     assert info[2] == 0
-    for s, o in outs.items():
-        pat = G.NAN32 if o.dtype == np.float32 else G.NAN16
-        assert np.array_equal(o.view(np.uint8), np.full_like(o, pat).view(np.uint8)), f"{name}: {s} was written"
+    replay.assert_untouched(outs, name)
 
 
 # ---- (4) the folded GEGLU-2 / conv_out weights against fp64 -------------------------------------------------------------------
 def _fold(model, block):
     """(C, folded weight [C][5C] fp16, bias [C] fp32) of a prepared model's attention block; C = 0 when it does not fold."""
-    lib = _lib()
+    lib = replay.lib()
     C_ = lib.tsd_debug_model_fold(model.h, block, None, None)
     assert C_ >= 0, lib.tsd_last_error().decode()
     if not C_:
@@ -358,7 +331,7 @@ def test_folded_weights_match_fp64_and_heavy_tails_replay(ctx, tsd_mod, unet_par
         unet.model.prepare()
         blocks, b = [], 0
         while True:
-            c_ = _lib().tsd_debug_model_fold(unet.model.h, b, None, None)
+            c_ = replay.lib().tsd_debug_model_fold(unet.model.h, b, None, None)
             if c_ < 0:
                 break
             if c_ > 0:
@@ -404,14 +377,14 @@ def test_a_fold_that_leaves_fp16_is_reported(ctx, tsd_mod, unet_params):
     try:
         unet.model.prepare()
         blk = 0
-        while _lib().tsd_debug_model_fold(unet.model.h, blk, None, None) == 0:
+        while replay.lib().tsd_debug_model_fold(unet.model.h, blk, None, None) == 0:
             blk += 1
-        assert _lib().tsd_debug_model_fold(unet.model.h, blk, None, None) > 0, "no attention block folds"
+        assert replay.lib().tsd_debug_model_fold(unet.model.h, blk, None, None) > 0, "no attention block folds"
         wo, _, w2, _ = (np.array(x, np.float32) for x in _fold_params(unet_params, blk))
         n = f"unet.layer{blk + 1}"
         unet.model.set_param(_param_index(unet.model, n + ".layer10.kernel"), np.full_like(wo, 16.0))
         unet.model.set_param(_param_index(unet.model, n + ".layer9.weight"), np.full_like(w2, 16.0))  # 640 * 256 > 65504
-        assert _lib().tsd_model_prepare(unet.model.h) == -7, "a folded weight outside fp16 was accepted"
-        assert "not finite" in _lib().tsd_last_error().decode()
+        assert replay.lib().tsd_model_prepare(unet.model.h) == -7, "a folded weight outside fp16 was accepted"
+        assert "not finite" in replay.lib().tsd_last_error().decode()
     finally:
         unet.model.close()

@@ -13,17 +13,13 @@ import numpy as np
 import pytest
 
 import norm_ref as N
+import replay
 
 pytestmark = pytest.mark.gpu
 _i64p = C.POINTER(C.c_int64)
 SEED = 1234
 SWEEP = N.sweep()
 BY_NAME = {s[0]: s for s in SWEEP}
-
-
-def _lib():
-    from tsd._lib import lib
-    return lib()
 
 
 @pytest.fixture(scope="module")
@@ -35,32 +31,14 @@ def ctx(gpu_ctx, tsd_mod):
 
 def run(ctx, d, ops):
     """(status, outputs {Y, STATS}, info {CHANGED, NSLAB, OWN_PASS, ...})."""
-    lib = _lib()
-    d = np.ascontiguousarray(d, np.int64)
-    ext = np.zeros(N.NO["COUNT"], np.int64)
-    assert lib.tsd_debug_norm_run(ctx.h, d.ctypes.data_as(_i64p), len(d), None, None, ext.ctypes.data_as(_i64p), None) == 0, \
-        lib.tsd_last_error().decode()
-    want = N.extents(d)
-    assert {s: int(ext[N.NO[s]]) for s in want} == want, "the entry and tests/norm_ref.py size the operands differently"
-    ins = (C.c_void_p * len(N.INPUTS))()
-    for s in N.INPUTS:
-        if want[s]:
-            assert ops[s].size == want[s] and ops[s].dtype == (np.float16 if s in ("X0", "X1") else np.float32), s
-            ins[N.NO[s]] = ops[s].ctypes.data
-    outs, outp = {}, (C.c_void_p * len(N.OUTPUTS))()
-    for i, s in enumerate(N.OUTPUTS):
-        if want[s]:
-            outs[s] = np.empty(want[s], np.float16 if s == "Y" else np.float32)
-            outp[i] = outs[s].ctypes.data
-    info = np.zeros(N.NI["COUNT"], np.int64)
-    rc = lib.tsd_debug_norm_run(ctx.h, d.ctypes.data_as(_i64p), len(d), ins, outp, ext.ctypes.data_as(_i64p), info.ctypes.data_as(_i64p))
+    rc, outs, info = replay.run("tsd_debug_norm_run", ctx, d, ops, N.NO, N.INPUTS, N.OUTPUTS, N.dtype_of, N.extents)
     return rc, outs, {k: int(info[v]) for k, v in N.NI.items() if k != "COUNT"}
 
 
 def verify(ctx, name, d, ops, expect=None):
     """Run d and hold it to the reference; returns (output, info, worst error / bound)."""
     rc, outs, info = run(ctx, d, ops)
-    assert rc == 0, f"{name}: status {rc}: {_lib().tsd_last_error().decode()}"
+    assert rc == 0, f"{name}: status {rc}: {replay.lib().tsd_last_error().decode()}"
     if expect is not None:
         assert {k: info[k] for k in expect} == expect, f"{name}: the launch took another path: {info}"
     assert info["CHANGED"] == 0, f"{name}: {info['CHANGED']} guard / pitch-gap elements written"
@@ -70,9 +48,7 @@ def verify(ctx, name, d, ops, expect=None):
     assert not fails, f"{name}: " + "; ".join(fails)
     if "Y" in outs:  # the pitch gaps of y still hold the fill
         rows = N.F(d, "ROWS") if N.mode_of(d) == "LAYERNORM" else N.F(d, "B") * N.F(d, "HW")
-        gap = np.ones(out.size, bool)
-        gap[(np.arange(rows)[:, None] * N.F(d, "LDY") + np.arange(N.F(d, "C"))[None, :]).ravel()] = False
-        assert (out.view(np.uint16)[gap] == N.NAN16.view(np.uint16)).all(), f"{name}: a pitch gap of y was written"
+        replay.assert_gaps_hold_fill(out, np.arange(rows)[:, None] * N.F(d, "LDY") + np.arange(N.F(d, "C"))[None, :], f"{name}: y")
     return out, info, ratio
 
 
@@ -91,21 +67,13 @@ def test_groupnorm_path_matches_the_fp64_reference(ctx, name, d, slab_rows, expe
         assert info["OWN_PASS"] == 1 and info["PREREDUCE"] == 0 and info["COMPOSITE"] == 0
 
 
-def _ctx_with(tsd_mod, gpu_ctx, monkeypatch, var, value):
-    """A context created with an option in the environment (read once, by tsd_ctx_create); the environment is restored at once."""
-    monkeypatch.setenv(var, str(value))
-    c = tsd_mod.Context(gpu_ctx.device)
-    monkeypatch.delenv(var)
-    return c
-
-
 FINALIZE_CASES = ("fin_c320_g320_hw576", "fin_c320_g32_hw3072", "table_ns128", "table_ns200", "pre_ns288", "comp_two_tables_finalize")
 
 
 def test_finalize_launch_and_in_block_finish_give_the_same_bits(ctx, gpu_ctx, tsd_mod, monkeypatch):
     """k_gn_finalize and the apply blocks' own finish add the same doubles in the same order: with the threshold out of reach the
     launch disappears and not one bit of the output moves."""
-    c = _ctx_with(tsd_mod, gpu_ctx, monkeypatch, "TSD_GN_FINALIZE_MIN", 1 << 30)
+    c = replay.ctx_with(tsd_mod, gpu_ctx, monkeypatch, "TSD_GN_FINALIZE_MIN", 1 << 30)
     try:
         for name in FINALIZE_CASES:
             _, d, sr, expect = BY_NAME[name]
@@ -120,7 +88,7 @@ def test_finalize_launch_and_in_block_finish_give_the_same_bits(ctx, gpu_ctx, ts
 
 @pytest.mark.parametrize("mult", (1, 4))
 def test_apply_multiplier_does_not_change_a_bit(ctx, gpu_ctx, tsd_mod, monkeypatch, mult):
-    c = _ctx_with(tsd_mod, gpu_ctx, monkeypatch, "TSD_GN_APPLY_MULT", mult)
+    c = replay.ctx_with(tsd_mod, gpu_ctx, monkeypatch, "TSD_GN_APPLY_MULT", mult)
     try:
         for name in ("own_c64_hw1920", "own_c96_pitches", "own_c960_two_sources", "own_c2560_two_chunks", "own_hw333_tail", "table_ns9",
                      "fin_c320_g32_hw3072", "affine_w1b1_rstd1_silu1"):
@@ -234,15 +202,13 @@ def test_refused_launches_leave_the_outputs_untouched(ctx, name, d):
     rc, outs, info = run(ctx, d, ops)
     assert rc != 0, f"{name} was not refused"
     assert all(v == 0 for v in info.values()), info
-    for s, o in outs.items():
-        pat = N.NAN32 if o.dtype == np.float32 else N.NAN16
-        assert np.array_equal(o.view(np.uint8), np.full_like(o, pat).view(np.uint8)), f"{name}: {s} was written"
+    replay.assert_untouched(outs, name)
 
 
 # ---- the product's own graphs reach the paths the sweep checks ----------------------------------------------------------------------
 def _path_counts(ctx, reset=0):
     c = np.zeros(8, np.int64)
-    assert _lib().tsd_debug_gn_path_counts(ctx.h, c.ctypes.data_as(_i64p), 8, reset) == 0
+    assert replay.lib().tsd_debug_gn_path_counts(ctx.h, c.ctypes.data_as(_i64p), 8, reset) == 0
     return dict(zip(("all", "own", "table", "table_finalize", "prereduce", "composite", "finalize", "composite_offered"), map(int, c)))
 
 

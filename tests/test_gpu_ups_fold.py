@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 import gemm_ref as G
+import replay
 import ups_fold_ref as U
 from oracle import models, ops, rng
 from util import TOL_MODEL, TOL_MODEL_MAX, assert_close, rel_l2
@@ -25,46 +26,19 @@ SEED = 1234
 UF_CFGS = (0, 1, 5, 6, 7, 51)      # tile configurations that have the variant (kernels_gemm.hip launch_ups_fold)
 BLOCKS = {14: "unet.layer15.layer2.kernel", 19: "unet.layer20.layer2.kernel"}   # residual block index -> its conv1 parameter
 _i64p = C.POINTER(C.c_int64)
-NAN16_BITS = 0x7E5A
-
-
-def _lib():
-    from tsd._lib import lib
-    return lib()
 
 
 @pytest.fixture(scope="module")
 def ctx(gpu_ctx, tsd_mod):
     c = tsd_mod.Context(gpu_ctx.device)
-    assert _lib().tsd_debug_set_ups_fold(c.h, 1) in (0, 1)   # stated, not inherited
+    assert replay.lib().tsd_debug_set_ups_fold(c.h, 1) in (0, 1)   # stated, not inherited
     yield c
     c.close()
 
 
 def run(ctx, d, ops_, cfg=-1):
-    """(status, C, info [cfg, ways, guard / gap writes]); a descriptor the entry cannot size returns (status, None, None)"""
-    lib = _lib()
-    d = np.ascontiguousarray(d, np.int64)
-    ext = np.zeros(G.GO["COUNT"], np.int64)
-    rc = lib.tsd_debug_gemm_run(ctx.h, d.ctypes.data_as(_i64p), len(d), cfg, None, None, ext.ctypes.data_as(_i64p), None)
-    if rc != 0:
-        return rc, None, None
-    want = G.extents(d)
-    assert {s: int(ext[G.GO[s]]) for s in want} == want
-    ins = (C.c_void_p * G.GO["COUNT"])()
-    for s in G.INPUTS:
-        if want[s]:
-            assert ops_[s].size == want[s]
-            ins[G.GO[s]] = ops_[s].ctypes.data
-    outs, outp = {}, (C.c_void_p * 3)()
-    for i, s in enumerate(G.OUTPUTS):
-        if want[s]:
-            f32 = s == "GN" or (s == "C" and int(d[G.GD["EPI"]]) & E["OUT_F32"])   # the entry returns 4 bytes per element for these
-            outs[s] = np.empty(want[s], np.float32 if f32 else np.float16)
-            outp[i] = outs[s].ctypes.data
-    info = np.zeros(4, np.int64)
-    rc = lib.tsd_debug_gemm_run(ctx.h, d.ctypes.data_as(_i64p), len(d), cfg, ins, outp, ext.ctypes.data_as(_i64p), info.ctypes.data_as(_i64p))
-    return rc, outs, info
+    """(status, outputs, info [cfg, ways, guard / gap writes]); a descriptor the entry cannot size returns (status, None, None)"""
+    return replay.run("tsd_debug_gemm_run", ctx, d, ops_, G.GO, G.INPUTS, G.OUTPUTS, G.dtype_of, G.extents, extra=(cfg,), unsizable_ok=True)
 
 
 # ---- (1) the kernel against float64, with the folded weights -------------------------------------------------------------------
@@ -148,7 +122,7 @@ def cases():
 def test_every_configuration_with_the_variant_against_fp64(ctx, cases, name, cfg):
     d, ops_, v, bnd = cases[name]
     rc, outs, info = run(ctx, d, ops_, cfg)
-    assert rc == 0, _lib().tsd_last_error().decode()
+    assert rc == 0, replay.lib().tsd_last_error().decode()
     assert int(info[0]) == cfg and int(info[1]) == 1
     _hold(d, outs, info, v, bnd, f"{name} forced {cfg}")
 
@@ -157,7 +131,7 @@ def test_every_configuration_with_the_variant_against_fp64(ctx, cases, name, cfg
 def test_the_dispatchers_choice_twice_with_equal_bits(ctx, cases, name):
     d, ops_, v, bnd = cases[name]
     rc, outs, info = run(ctx, d, ops_)
-    assert rc == 0, _lib().tsd_last_error().decode()
+    assert rc == 0, replay.lib().tsd_last_error().decode()
     assert int(info[0]) in UF_CFGS and int(info[1]) == 1
     _hold(d, outs, info, v, bnd, f"{name} dispatcher")
     rc2, outs2, info2 = run(ctx, d, ops_)
@@ -173,7 +147,7 @@ def test_row_major_description_and_no_row_vector(ctx, cases):
     ops_ = G.make_operands(d, 950)
     v, bnd = _expected(d, ops_)
     rc, outs, info = run(ctx, d, ops_)
-    assert rc == 0, _lib().tsd_last_error().decode()
+    assert rc == 0, replay.lib().tsd_last_error().decode()
     _hold(d, outs, info, v, bnd, "row-major W, bias only")
 
 
@@ -185,10 +159,8 @@ def _refused(ctx, d, cfg=-1, seed=970):
     if outs is None:
         return "sizing"     # refused before any buffer existed
     assert info[2] == 0
-    for s, o in outs.items():
-        bits = o.view(np.uint16 if o.dtype == np.float16 else np.uint32)
-        assert (bits == (NAN16_BITS if o.dtype == np.float16 else 0x7FC5A5A5)).all(), f"a refused launch wrote {s}"
-    return _lib().tsd_last_error().decode()
+    replay.assert_untouched(outs, "a refused launch")
+    return replay.lib().tsd_last_error().decode()
 
 
 def test_refusals_leave_the_outputs_untouched(ctx):
@@ -233,11 +205,11 @@ class _fold:
         self.ctx, self.on = ctx, on
 
     def __enter__(self):
-        self.prev = _lib().tsd_debug_set_ups_fold(self.ctx.h, self.on)
+        self.prev = replay.lib().tsd_debug_set_ups_fold(self.ctx.h, self.on)
         assert self.prev in (0, 1)
 
     def __exit__(self, *a):
-        _lib().tsd_debug_set_ups_fold(self.ctx.h, self.prev)
+        replay.lib().tsd_debug_set_ups_fold(self.ctx.h, self.prev)
 
 
 def _inputs(B, L, T=77, tag=1700):
@@ -258,7 +230,7 @@ def _numpy_fold_tm(w):
 
 
 def _read_fold(model, block, O, I):
-    lib = _lib()
+    lib = replay.lib()
     n = lib.tsd_debug_model_ups_fold(model.h, block, None)
     if n <= 0:
         return n, None
@@ -268,7 +240,7 @@ def _read_fold(model, block, O, I):
 
 
 def test_set_option_returns_the_previous_value(ctx):
-    lib = _lib()
+    lib = replay.lib()
     assert lib.tsd_debug_set_ups_fold(ctx.h, 0) == 1
     assert lib.tsd_debug_set_ups_fold(ctx.h, 1) == 0
     assert lib.tsd_debug_set_ups_fold(ctx.h, 1) == 1
@@ -281,7 +253,7 @@ def test_folded_weights_on_the_device_are_the_numpy_fold_bit_for_bit(unet, unet_
         n, got = _read_fold(unet.model, block, w.shape[0], w.shape[1])
         assert n == w.shape[1], f"block {block} did not fold"
         assert np.array_equal(got, _numpy_fold_tm(w)), f"block {block}"
-    assert _lib().tsd_debug_model_ups_fold(unet.model.h, 9, None) == 0, "a block without an upsample folded"
+    assert replay.lib().tsd_debug_model_ups_fold(unet.model.h, 9, None) == 0, "a block without an upsample folded"
 
 
 def test_forward_inside_the_oracle_tolerance_with_the_fold_on_and_off(ctx, unet, unet_params):
@@ -315,7 +287,7 @@ def test_batch_invariance_is_bitwise_with_the_fold(ctx, unet):
 
 
 def _recorded_step(ctx, tsd_mod, unet, B, L):
-    lib = _lib()
+    lib = replay.lib()
     lat, cond, _ = _inputs(B, L, tag=1740)
     counts = np.zeros(8, np.int64)
     s = tsd_mod.Session(unet.model, None, B, L, 77, cfg=False)
@@ -387,7 +359,7 @@ def test_a_sum_that_leaves_fp16_is_refused_by_prepare(ctx, tsd_mod, unet_params)
     name = BLOCKS[14]
     w = np.array(unet_params[name], np.float32)
     w[17, 33, 1, 0] = 30000.0; w[17, 33, 2, 0] = 30000.0; w[17, 33, 1, 1] = 30000.0
-    lib = _lib()
+    lib = replay.lib()
     a = tsd_mod.Diffusion(seed=SEED, ctx=ctx)
     try:
         a.model.set_param(_param_index(a.model, name), w)

@@ -2,26 +2,21 @@
 tested.  The reference agrees with the oracle's norms on the op-level case shapes; its operand extents and its restatement of the
 launch plan agree with tsd_debug_norm_run's sizing-only mode; the statistics share of the bound stays under its cap on every sweep
 input; the emulation of the device arithmetic stays inside the bound on every sweep input, and every seeded defect is rejected."""
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import norm_ref as N
+import replay
 from cases import CASES
 from oracle import ops as O
 
-_i64p = C.POINTER(C.c_int64)
 SWEEP = N.sweep()
 LN_SWEEP = N.ln_sweep()
 
 
-def _size(tsd_mod, d):
-    lib = tsd_mod._lib.lib()
-    d = np.ascontiguousarray(d, np.int64)
-    ext = np.zeros(N.NO["COUNT"], np.int64)
+def _size(tsd_mod, d, n=None):
     info = np.full(N.NI["COUNT"], -1, np.int64)
-    rc = lib.tsd_debug_norm_run(None, d.ctypes.data_as(_i64p), len(d), None, None, ext.ctypes.data_as(_i64p), info.ctypes.data_as(_i64p))
+    rc, ext = replay.size("tsd_debug_norm_run", d, n, info)
     return rc, {s: int(ext[N.NO[s]]) for s in N.INPUTS + N.OUTPUTS}, {k: int(info[v]) for k, v in N.NI.items() if k != "COUNT"}
 
 
@@ -115,9 +110,7 @@ def test_unsizable_descriptors_are_refused(tsd_mod):
     assert _size(tsd_mod, d)[0] != 0
     d = N.ln_desc(0, 64)
     assert _size(tsd_mod, d)[0] != 0
-    lib = tsd_mod._lib.lib()
-    ext = np.zeros(N.NO["COUNT"], np.int64)
-    assert lib.tsd_debug_norm_run(None, good.ctypes.data_as(_i64p), N.COUNT - 1, None, None, ext.ctypes.data_as(_i64p), None) != 0
+    assert replay.size("tsd_debug_norm_run", good, n=N.COUNT - 1)[0] != 0
 
 
 # ---- the emulation inside the bound, the cap on the reference alone ------------------------------------------------------------------
