@@ -212,6 +212,34 @@ int tsd_model_mark_loaded(tsd_model* m); /* after an external write (RCCL broadc
  * time that step next to the broadcast (bench.py `derived_buffers_s`).  TSD_E_STATE if a used parameter was never set. */
 int tsd_model_prepare(tsd_model* m);
 
+/* ---- LoRA adapters (EXTENSION: the reference can only random-initialise) ----------------------------------------------------------
+ * A model keeps the packed fp16 weights only, so a low-rank adapter is MERGED on the device, in the weights' own layout:
+ *     W'[o][c] = rn16( W[o][c] + scale * sum_j up[o - row0][j] * down[j][c] )     row0 <= o < row0 + rows
+ * fp32 operands and accumulation on the exact-fp32 matrix instruction, ONE rounding to fp16 (nearest-even).  `index` names a weight
+ * matrix (conv kernel or linear weight); up [rows][rank] and down [rank][cols] are host fp32 in reference coordinates: cols = I for a
+ * linear layer, I * k * k (i * k * k + tap, the flattened [I][k][k]) for a convolution.  Synchronous.
+ * The first add on a parameter snapshots its packed bytes (the base); repeated adds on one parameter stack, each costing one rounding -
+ * two stacked adapters are not bit-equal to one merge of their sum.  tsd_model_lora_clear restores every touched parameter bit for
+ * bit and frees the snapshots; tsd_model_lora_count is the number of parameters that currently differ from their base.
+ * Both move the parameter generation like tsd_model_set_param, so an open session rebuilds its hoisted buffers on its next step.
+ * tsd_model_set_param(index) makes the new value the base of that parameter (its snapshot is dropped); tsd_model_init_random and
+ * tsd_model_mark_loaded drop every snapshot.
+ * Errors leave the weights, the snapshots and the count exactly as they were: TSD_E_ARG (NULL pointer, a bias / norm parameter, a
+ * parameter the forward never reads, rank outside 1..1024, a non-finite scale), TSD_E_SHAPE (row range outside the parameter),
+ * TSD_E_STATE (the parameter was never set), TSD_E_NONFINITE (a merged weight leaves fp16, or up / down hold inf / NaN). */
+int tsd_model_lora_add(tsd_model* m, int index, int row0, int rows, const float* up, const float* down, int rank, float scale);
+int tsd_model_lora_clear(tsd_model* m);
+int tsd_model_lora_count(tsd_model* m);
+/* Parameter `index` as the forward reads it, unpacked to the reference layout in fp32 (numel must match): every weight is exactly an
+ * fp16 value - there are no fp32 masters -, biases and norm parameters are the fp32 that was set; a parameter the forward never
+ * reads comes back as zeros.  TSD_E_STATE if it was never set. */
+int tsd_model_get_param(tsd_model* m, int index, float* out, int64_t numel);
+/* Op level, host fp32 in/out, synchronous: the merge above on w [O][I] (k = 0; interleave != 0: packed with the GEGLU row interleave)
+ * or [O][I][k][k] (k = 1, 3), packed as a model packs it, merged by the same kernel and returned unpacked - every value of out is
+ * exactly an fp16.  TSD_E_NONFINITE when a merged value is not finite. */
+int tsd_lora_merge_f32(tsd_ctx* ctx, const float* w, int O, int I, int k, int interleave, int row0, int rows, const float* up,
+                       const float* down, int rank, float scale, float* out);
+
 /* `Diffusion.forward` diffusion.mojo:309-318, batched.  latents [B,4,L,L], context [B,T,768],
  * time_emb [B,320] (= get_time_embedding(t) per sample) -> out [B,4,L,L]. */
 int tsd_diffusion_forward(tsd_model* m, const float* latents, const float* context, const float* time_emb, int B,
@@ -554,6 +582,9 @@ int64_t tsd_debug_dup_fold_host(const void* w, int rows, int taps, int ldw, int 
 int64_t tsd_debug_ups_fold_host(const void* w, int O, int Ipad, int ldw, void* out);
 int tsd_debug_model_ups_fold(tsd_model* m, int block, void* out);
 int tsd_debug_set_ups_fold(tsd_ctx* ctx, int on);
+/* Raw packed bytes of parameter `index` (the device layout: fp16 [N][Kpad] / [Opad][k*k][Ipad], fp32 biases).  out == NULL asks for
+ * the size; returns the byte count (0 for a parameter the forward never reads), TSD_E_ARG when cap is too small. */
+int tsd_debug_model_packed_param(tsd_model* m, int index, void* out, size_t cap);
 /* tsd_debug_gemm_bench for the fused attention core: Q,K [B][S][H*d], V^T [B][H*d][Sk]. */
 int tsd_debug_attn_bench(tsd_ctx* ctx, int B, int H, int d, int Sq, int Sk, int iters, float* ms);
 /* The fused attention core runs an optimistic softmax pass (reference fixed after the first key tile) and repeats a

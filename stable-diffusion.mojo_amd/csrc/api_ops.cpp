@@ -328,6 +328,44 @@ extern "C" int tsd_inpaint_blend_f32(tsd_ctx* ctx, const float* x, const float* 
   });
 }
 
+// the low-rank merge (kernels_lora.hip k_lora_merge) on host tensors: `w` is packed as a model packs it - launch_pack_linear for k = 0
+// ([O][I], `interleave`: GEGLU rows), launch_pack_conv for k = 1, 3 ([O][I][k][k], Opad as model_spec.cpp pads a convolution) - merged in
+// place by the kernel tsd_model_lora_add runs, and returned unpacked in the reference layout: every value of `out` is exactly an fp16.
+extern "C" int tsd_lora_merge_f32(tsd_ctx* ctx, const float* w, int O, int I, int k, int interleave, int row0, int rows, const float* up,
+                                  const float* down, int rank, float scale, float* out) {
+  NOTNULL(ctx); NOTNULL(w); NOTNULL(up); NOTNULL(down); NOTNULL(out);
+  if (k != 0 && k != 1 && k != 3) TSD_FAIL(TSD_E_ARG, "lora merge: kernel size %d (0 linear, 1 or 3)", k);
+  if (rank < 1 || rank > 1024) TSD_FAIL(TSD_E_ARG, "lora merge: rank %d outside 1..1024", rank);
+  if (!(fabsf(scale) <= 3.4028235e38f)) TSD_FAIL(TSD_E_ARG, "lora merge: scale is not finite");
+  if (interleave && (k != 0 || (O & 1))) TSD_FAIL(TSD_E_ARG, "lora merge: the GEGLU interleave needs a linear layer with an even row count");
+  if (O <= 0 || I <= 0 || (int64_t)O * I * (k ? k * k : 1) > (int64_t)1 << 28) TSD_FAIL(TSD_E_SHAPE, "lora merge: bad dims O=%d I=%d", O, I);
+  if (row0 < 0 || rows <= 0 || row0 > O - rows) TSD_FAIL(TSD_E_SHAPE, "lora merge: rows [%d, %d) outside %d rows", row0, row0 + rows, O);
+  const int kk = k ? k * k : 1, ld = round_up(I, 64), Opad = k ? ((O < 64) ? 64 : round_up(O, 4)) : O;
+  const int64_t npacked = (int64_t)Opad * kk * ld, nw = (int64_t)O * I * kk;
+  std::vector<uint16_t> packed((size_t)npacked);
+  HIP_TRY(hipSetDevice(ctx->device));
+  int r = run_planned(ctx, [&]() -> int {
+    Dev d{ctx};
+    float* dw = d.in(w, nw);
+    float* du = d.in(up, (int64_t)rows * rank);
+    float* dd = d.in(down, (int64_t)rank * I * kk);
+    half_t* pw = d.buf<half_t>(npacked);
+    if (d.err) return d.err;
+    if (k) TSD_TRY(launch_pack_conv(ctx, dw, O, I, k, pw, Opad, ld));
+    else TSD_TRY(launch_pack_linear(ctx, dw, O, I, pw, ld, interleave));
+    TSD_TRY(launch_lora_merge(ctx, pw, O, I, k, ld, interleave, row0, rows, du, dd, rank, scale));
+    return d.out((uint16_t*)packed.data(), (const uint16_t*)pw, npacked);
+  });
+  if (r != TSD_OK) {
+    hipStreamSynchronize(ctx->stream);
+    return r;
+  }
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  TSD_TRY(ctx_check_status(ctx));
+  unpack_weight_host(packed.data(), O, I, k, ld, interleave, out);
+  return TSD_OK;
+}
+
 extern "C" int tsd_linear_f32(tsd_ctx* ctx, const float* x, int M, int K, const float* w, const float* bias, int N,
                               float* y) {
   NOTNULL(x); NOTNULL(w); NOTNULL(y);

@@ -342,6 +342,13 @@ int launch_pack_linear(tsd_ctx* ctx, const float* src, int N, int K, half_t* dst
 int launch_pack_bias(tsd_ctx* ctx, const float* src, int N, float* dst, int Npad, int geglu_interleave);
 int launch_transpose_f32_to_f16(tsd_ctx* ctx, const float* src, int batch, int K, int N, half_t* dst, int Kpad,
                                 int Npad);
+// low-rank merge into ONE packed weight, in place (kernels_lora.hip): W[o][c] = rn16(W[o][c] + scale * sum_j up[o - row0][j] down[j][c]) for the
+// reference rows [row0, row0 + rows) of a packed linear [N][ld] (k = 0; `interleave`: GEGLU rows) or convolution [Opad][k*k][ld] (k = 1, 3);
+// up [rows][rank] / down [rank][I * max(k*k, 1)] device fp32, columns in the reference order; pad rows / channels are never written
+int launch_lora_merge(tsd_ctx* ctx, half_t* W, int N, int I, int k, int ld, int interleave, int row0, int rows, const float* up,
+                      const float* down, int rank, float scale);
+// host inverse of launch_pack_linear / launch_pack_conv on fp16 bit patterns (model.cpp): packed -> fp32 in the reference layout
+void unpack_weight_host(const uint16_t* packed, int N, int I, int k, int ld, int interleave, float* out);
 int launch_ddpm_step(tsd_ctx* ctx, float* latents, const float* eps, const float* eps_uncond, float cfg_scale,
                      const float* noise, int64_t n, float inv_sqrt_a, float sqrt_b, float c_x0, float c_xt,
                      float sigma, int eps_hw = 0);  // eps_hw > 0: eps in the output convolution's layout [B][eps_hw][4]

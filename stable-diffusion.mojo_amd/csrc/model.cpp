@@ -219,8 +219,19 @@ extern "C" int tsd_model_destroy(tsd_model* m) {
   hipStreamSynchronize(m->ctx->stream);
   if (m->blob) hipFree(m->blob);
   if (m->derived) hipFree(m->derived);
+  for (auto& kv : m->lora_base) hipFree(kv.second);
   delete m;
   return TSD_OK;
+}
+
+// Forget the adapter snapshots (all of them, or the one of parameter `index`) WITHOUT restoring anything: what the blob holds now is the base.
+// Call after the stream is idle.
+static void lora_drop(tsd_model* m, int index = -1) {
+  for (auto it = m->lora_base.begin(); it != m->lora_base.end();) {
+    if (index >= 0 && it->first != index) { ++it; continue; }
+    (void)hipFree(it->second);
+    it = m->lora_base.erase(it);
+  }
 }
 
 // pack parameter `i` from a device fp32 tensor in the reference layout
@@ -255,6 +266,7 @@ extern "C" int tsd_model_set_param(tsd_model* m, int index, const float* data, i
   HIP_TRY(hipMemcpyAsync(ctx->staging, data, (size_t)numel * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
   TSD_TRY(pack_param(m, index, (const float*)ctx->staging));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
+  lora_drop(m, index);  // the new value is the new base of this parameter
   model_invalidate_derived(m);
   return TSD_OK;
 }
@@ -277,6 +289,7 @@ extern "C" int tsd_model_init_random(tsd_model* m, uint64_t seed) {
     TSD_TRY(pack_param(m, (int)i, tmp));
   }
   HIP_TRY(hipStreamSynchronize(ctx->stream));
+  lora_drop(m);
   model_invalidate_derived(m);
   return TSD_OK;
 }
@@ -291,8 +304,141 @@ extern "C" int tsd_model_packed_blob(tsd_model* m, void** device_ptr, size_t* by
 extern "C" int tsd_model_mark_loaded(tsd_model* m) {
   if (!m) TSD_FAIL(TSD_E_ARG, "NULL model");
   std::fill(m->loaded.begin(), m->loaded.end(), 1);
+  if (!m->lora_base.empty()) {  // the blob was written from outside (a weight broadcast): it is the base now
+    HIP_TRY(hipSetDevice(m->ctx->device));
+    HIP_TRY(hipStreamSynchronize(m->ctx->stream));
+    lora_drop(m);
+  }
   model_invalidate_derived(m);
   return TSD_OK;
+}
+
+// ---- reading a parameter back ---------------------------------------------------------------------------------------------------------
+// host inverse of k_pack_linear / k_pack_conv on fp16 bit patterns: out is fp32 in the reference layout ([N][I], or [N][I][k][k])
+void unpack_weight_host(const uint16_t* packed, int N, int I, int k, int ld, int interleave, float* out) {
+  const int kk = k ? k * k : 1;
+  for (int o = 0; o < N; o++) {
+    const int prow = interleave ? (o < N / 2 ? 2 * o : 2 * (o - N / 2) + 1) : o;
+    for (int t = 0; t < kk; t++) {
+      const uint16_t* s = packed + ((size_t)prow * kk + t) * ld;
+      float* d = out + (size_t)o * I * kk + t;
+      for (int i = 0; i < I; i++) d[(size_t)i * kk] = (float)f16_bits_to_f64(s[i]);
+    }
+  }
+}
+
+static int param_checked(tsd_model* m, int index, const char* who) {
+  if (!m) TSD_FAIL(TSD_E_ARG, "%s: NULL model", who);
+  if (index < 0 || index >= (int)m->params.size()) TSD_FAIL(TSD_E_ARG, "%s: param index %d out of range", who, index);
+  return TSD_OK;
+}
+
+// raw packed bytes of one parameter (debug / tests): out == NULL asks for the size; returns the byte count (0: the parameter is not used)
+extern "C" int tsd_debug_model_packed_param(tsd_model* m, int index, void* out, size_t cap) {
+  TSD_TRY(param_checked(m, index, "tsd_debug_model_packed_param"));
+  const ParamSpec& p = m->params[index];
+  if (!out || !p.bytes) return (int)p.bytes;
+  if (cap < p.bytes) TSD_FAIL(TSD_E_ARG, "packed_param %s: %zu bytes do not fit %zu", p.name.c_str(), p.bytes, cap);
+  HIP_TRY(hipSetDevice(m->ctx->device));
+  HIP_TRY(hipStreamSynchronize(m->ctx->stream));
+  HIP_TRY(hipMemcpy(out, m->blob + p.off, p.bytes, hipMemcpyDeviceToHost));
+  return (int)p.bytes;
+}
+
+// The parameter as the forward reads it, unpacked to the reference layout in fp32: every weight is exactly an fp16 value (the model keeps
+// no fp32 masters), biases and norm parameters are the fp32 that was set.  A parameter the forward never reads reads back as zeros.
+extern "C" int tsd_model_get_param(tsd_model* m, int index, float* out, int64_t numel) {
+  TSD_TRY(param_checked(m, index, "tsd_model_get_param"));
+  if (!out) TSD_FAIL(TSD_E_ARG, "tsd_model_get_param: NULL argument");
+  const ParamSpec& p = m->params[index];
+  if (numel != p.numel())
+    TSD_FAIL(TSD_E_SHAPE, "param %s: room for %lld elements, it has %lld", p.name.c_str(), (long long)numel, (long long)p.numel());
+  if (!p.used) { memset(out, 0, (size_t)numel * sizeof(float)); return TSD_OK; }
+  if (!m->loaded[index]) TSD_FAIL(TSD_E_STATE, "model parameter %s was never set", p.name.c_str());
+  std::vector<char> raw(p.bytes);
+  HIP_TRY(hipSetDevice(m->ctx->device));
+  HIP_TRY(hipStreamSynchronize(m->ctx->stream));
+  HIP_TRY(hipMemcpy(raw.data(), m->blob + p.off, p.bytes, hipMemcpyDeviceToHost));
+  const int N = (int)p.shape[0];
+  if (p.kind == P_CONV_W) unpack_weight_host((const uint16_t*)raw.data(), N, (int)p.shape[1], (int)p.shape[2], p.Kpad, 0, out);
+  else if (p.kind == P_LIN_W) unpack_weight_host((const uint16_t*)raw.data(), N, (int)p.shape[1], 0, p.Kpad, p.interleave, out);
+  else {
+    const float* s = (const float*)raw.data();
+    const bool inter = p.kind == P_LIN_B && p.interleave;
+    for (int o = 0; o < N; o++) out[o] = s[inter ? (o < N / 2 ? 2 * o : 2 * (o - N / 2) + 1) : o];
+  }
+  return TSD_OK;
+}
+
+// ---- low-rank adapters (LoRA): W <- rn16(W + scale * up . down) on the packed fp16 weights, the base bits kept for an exact removal ------------
+// Rows [row0, row0 + rows) of weight parameter `index`, host fp32 up [rows][rank] and down [rank][cols], cols in the reference column order
+// (I for a linear layer, i * k * k + tap for a convolution).  The merge runs on a copy in the context's staging buffer (kernels_lora.hip) and
+// replaces the parameter only when every merged value is finite: on any error the weights, the snapshots and lora_count are as before.
+// The first merge into a parameter snapshots its packed bytes; later merges stack on the merged value, ONE rounding to fp16 each (so two
+// stacked adapters are not bit-equal to one merge of their sum).  Synchronous.
+extern "C" int tsd_model_lora_add(tsd_model* m, int index, int row0, int rows, const float* up, const float* down, int rank, float scale) {
+  if (!m || !up || !down) TSD_FAIL(TSD_E_ARG, "tsd_model_lora_add: NULL argument");
+  TSD_TRY(param_checked(m, index, "tsd_model_lora_add"));
+  const ParamSpec& p = m->params[index];
+  if (p.kind != P_CONV_W && p.kind != P_LIN_W) TSD_FAIL(TSD_E_ARG, "lora_add: %s is a bias / norm parameter, not a weight matrix", p.name.c_str());
+  if (!p.used) TSD_FAIL(TSD_E_ARG, "lora_add: %s is never read by the forward", p.name.c_str());
+  if (rank < 1 || rank > 1024) TSD_FAIL(TSD_E_ARG, "lora_add: rank %d outside 1..1024", rank);
+  if (!(fabsf(scale) <= 3.4028235e38f)) TSD_FAIL(TSD_E_ARG, "lora_add: scale is not finite");
+  const int N = (int)p.shape[0], I = (int)p.shape[1], k = p.kind == P_CONV_W ? (int)p.shape[2] : 0;
+  if (row0 < 0 || rows <= 0 || row0 > N - rows) TSD_FAIL(TSD_E_SHAPE, "lora_add: rows [%d, %d) outside %s (%d rows)", row0, row0 + rows, p.name.c_str(), N);
+  if (!m->loaded[index]) TSD_FAIL(TSD_E_STATE, "model parameter %s was never set", p.name.c_str());
+  tsd_ctx* ctx = m->ctx;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const size_t cols = (size_t)I * (k ? k * k : 1);
+  const size_t wb = (p.bytes + 255) & ~size_t(255), ub = ((size_t)rows * rank * 4 + 255) & ~size_t(255), db = (size_t)rank * cols * 4;
+  TSD_TRY(ctx_reserve_staging(ctx, wb + ub + db));
+  char* st = (char*)ctx->staging;
+  HIP_TRY(hipMemcpyAsync(st, m->blob + p.off, p.bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(st + wb, up, (size_t)rows * rank * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(st + wb + ub, down, db, hipMemcpyHostToDevice, ctx->stream));
+  const bool was_planning = ctx->arena.planning;
+  ctx->arena.planning = false;
+  const int r = launch_lora_merge(ctx, (half_t*)st, N, I, k, p.Kpad, p.interleave, row0, rows, (const float*)(st + wb), (const float*)(st + wb + ub), rank, scale);
+  ctx->arena.planning = was_planning;
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  TSD_TRY(r);
+  TSD_TRY(ctx_check_status(ctx));  // TSD_E_NONFINITE (reported once, then cleared): a merged weight left fp16, or up / down held inf / NaN
+  if (!m->lora_base.count(index)) {
+    char* snap = nullptr;
+    hipError_t e = hipMalloc((void**)&snap, p.bytes);
+    if (e != hipSuccess) TSD_FAIL(TSD_E_ALLOC, "lora_add: hipMalloc(%zu) for the base of %s failed: %s", p.bytes, p.name.c_str(), hipGetErrorString(e));
+    // on the context's stream, like the copy over the parameter below: a device-to-device hipMemcpy on the null stream may still be reading
+    // the base when that copy starts
+    e = hipMemcpyAsync(snap, m->blob + p.off, p.bytes, hipMemcpyDeviceToDevice, ctx->stream);
+    if (e != hipSuccess) { (void)hipFree(snap); TSD_FAIL(TSD_E_HIP, "lora_add: snapshot of %s: %s", p.name.c_str(), hipGetErrorString(e)); }
+    m->lora_base[index] = snap;
+  }
+  HIP_TRY(hipMemcpyAsync(m->blob + p.off, st, p.bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  model_invalidate_derived(m);
+  return TSD_OK;
+}
+
+// every touched parameter back to its base, bit for bit; the snapshots are freed
+extern "C" int tsd_model_lora_clear(tsd_model* m) {
+  if (!m) TSD_FAIL(TSD_E_ARG, "tsd_model_lora_clear: NULL model");
+  if (m->lora_base.empty()) return TSD_OK;
+  tsd_ctx* ctx = m->ctx;
+  HIP_TRY(hipSetDevice(ctx->device));
+  for (auto& kv : m->lora_base) {
+    const ParamSpec& p = m->params[kv.first];
+    HIP_TRY(hipMemcpyAsync(m->blob + p.off, kv.second, p.bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  lora_drop(m);
+  model_invalidate_derived(m);
+  return TSD_OK;
+}
+
+// parameters that currently differ from their base
+extern "C" int tsd_model_lora_count(tsd_model* m) {
+  if (!m) TSD_FAIL(TSD_E_ARG, "tsd_model_lora_count: NULL model");
+  return (int)m->lora_base.size();
 }
 
 // derived device buffers (not part of the broadcast blob: every rank rebuilds them from the packed weights)

@@ -141,6 +141,10 @@ struct tsd_model {
   std::map<PlanKey, size_t> plans;  // workspace high-water mark per problem shape
   char* derived = nullptr;          // derived device buffers rebuilt by model_check_ready(): fused-tail weight streams
   size_t derived_bytes = 0;
+  // low-rank adapters (tsd_model_lora_add): parameter index -> device copy of its packed bytes as they were before the first merge (the
+  // base).  tsd_model_lora_clear copies them back bit for bit; set_param drops the entry of its parameter (the new value is the new base),
+  // init_random / mark_loaded drop all of them.
+  std::map<int, char*> lora_base;
 };
 
 int model_resolve(tsd_model* m);                      // fill unet / vae from the packed blob

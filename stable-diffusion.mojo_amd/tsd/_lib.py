@@ -105,6 +105,9 @@ def _declare(l):
         "tsd_model_create": ([vp, i, pp], i), "tsd_model_destroy": ([vp], i),
         "tsd_model_set_param": ([vp, i, fp, i64], i), "tsd_model_init_random": ([vp, u64], i),
         "tsd_model_packed_blob": ([vp, pp, C.POINTER(sz)], i), "tsd_model_mark_loaded": ([vp], i), "tsd_model_prepare": ([vp], i),
+        "tsd_model_lora_add": ([vp, i, i, i, fp, fp, i, f], i), "tsd_model_lora_clear": ([vp], i), "tsd_model_lora_count": ([vp], i),
+        "tsd_model_get_param": ([vp, i, fp, i64], i), "tsd_debug_model_packed_param": ([vp, i, vp, sz], i),
+        "tsd_lora_merge_f32": ([vp, fp, i, i, i, i, i, i, fp, fp, i, f, fp], i),
         "tsd_diffusion_forward": ([vp, fp, fp, fp, i, i, i, fp], i),
         "tsd_decoder_forward": ([vp, fp, i, i, fp], i),
         "tsd_encoder_forward": ([vp, fp, fp, i, i, fp], i),

@@ -71,6 +71,64 @@ class Model:
         """Build the derived device buffers now (per rank, after the weights are in place) and wait for them."""
         check(lib().tsd_model_prepare(self.h))
 
+    def param_index(self, name_or_index):
+        """Index of a parameter given its name (struct-field path, `param_specs`) or its index."""
+        if isinstance(name_or_index, str):
+            for i, spec in enumerate(self.specs):
+                if spec[0] == name_or_index:
+                    return i
+            raise KeyError(f"no parameter {name_or_index}")
+        i = int(name_or_index)
+        if not 0 <= i < len(self.specs):
+            raise IndexError(f"parameter index {i} out of range")
+        return i
+
+    def get_param(self, name_or_index):
+        """The parameter as the forward reads it, in the reference layout (fp32 array): every weight is exactly an fp16 value (the
+        device keeps no fp32 masters), biases and norm parameters are what was set."""
+        i = self.param_index(name_or_index)
+        out = np.empty(self.specs[i][1], dtype=np.float32)
+        check(lib().tsd_model_get_param(self.h, i, ptr(out), out.size))
+        return out
+
+    def packed_param(self, name_or_index):
+        """Raw packed bytes of the parameter (uint8 array; the device layout) - for tests of what a merge may touch."""
+        i = self.param_index(name_or_index)
+        n = lib().tsd_debug_model_packed_param(self.h, i, None, 0)
+        if n < 0:
+            check(n)
+        out = np.empty(n, dtype=np.uint8)
+        if n:
+            r = lib().tsd_debug_model_packed_param(self.h, i, out.ctypes.data_as(vp), n)
+            if r < 0:
+                check(r)
+        return out
+
+    def lora_add(self, name_or_index, up, down, scale, row0=0):
+        """Merge a low-rank adapter into rows [row0, row0 + up.shape[0]) of a weight, on the device: W <- rn16(W + scale * up @ down),
+        fp32 product, one rounding to fp16.  up (rows, rank); down (rank, cols) or a conv-shaped (rank, I, k, k), flattened to the
+        reference column order.  The first add on a parameter keeps its base bits for `lora_clear`; repeated adds stack, one rounding
+        each."""
+        i = self.param_index(name_or_index)
+        u, d = f32(up), f32(down)
+        u = u.reshape(u.shape[0], -1)
+        d = np.ascontiguousarray(d.reshape(d.shape[0], -1))
+        shape = self.specs[i][1]
+        if u.shape[1] != d.shape[0]:
+            raise ValueError(f"up {u.shape} and down {d.shape} do not share a rank")
+        if len(shape) >= 2 and d.shape[1] != int(np.prod(shape[1:])):
+            raise ValueError(f"{self.specs[i][0]}: down has {d.shape[1]} columns, the parameter {int(np.prod(shape[1:]))}")
+        check(lib().tsd_model_lora_add(self.h, i, int(row0), u.shape[0], ptr(u), ptr(d), u.shape[1], float(scale)))
+
+    def lora_clear(self):
+        """Every parameter touched by `lora_add` back to its base, bit for bit."""
+        check(lib().tsd_model_lora_clear(self.h))
+
+    @property
+    def lora_count(self):
+        """Parameters that currently differ from their base."""
+        return lib().tsd_model_lora_count(self.h)
+
     def close(self):
         if self.h:
             lib().tsd_model_destroy(self.h)
