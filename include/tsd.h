@@ -471,6 +471,16 @@ int tsd_debug_gemm_recorded(tsd_ctx* ctx, int i, int64_t* desc, int n);
  * returned even when the launch is refused (its status is the return value). */
 int tsd_debug_gemm_run(tsd_ctx* ctx, const int64_t* desc, int n, int cfg, const void* const* host_in, void* const* host_out,
                        int64_t* ext, int64_t* info);
+/* The host plan of the launch desc describes (csrc/gemm_plan.cpp: what launch_gemm acts on), without running it: plan[TSD_GP_COUNT]
+ * receives the tile configuration that would run and its split-K slices (what tsd_debug_gemm_run reports as info[0], info[1]), the conv
+ * variant (0 plain, 1 halo-x, 2 fused 1x1 skip, 3 upsample fold), the tile and one wave's sub-tile, the K the launch executes (4 * CIN
+ * under the upsample fold), the split-K workspace in floats, the LDS bytes, and the GroupNorm statistics slabs per sample the tile can
+ * emit for the descriptor's GN_RPS / GN_GROUPS (0: none).  cfg as in tsd_debug_gemm_run.  No device is touched: ctx == NULL plans under
+ * the options of the environment (the defaults when no TSD_* variable is set) and the descriptor's SK_BIG.  TSD_E_ARG for a tile
+ * configuration the build does not have, or one without the variant the launch needs. */
+enum tsd_gemm_plan_field { TSD_GP_CFG = 0, TSD_GP_WAYS, TSD_GP_VARIANT, TSD_GP_BM, TSD_GP_BN, TSD_GP_BMW, TSD_GP_BNW, TSD_GP_K,
+                           TSD_GP_WS_FLOATS, TSD_GP_LDS_BYTES, TSD_GP_GN_NSLAB, TSD_GP_COUNT };
+int tsd_debug_gemm_plan(tsd_ctx* ctx, const int64_t* desc, int n, int cfg, int64_t* plan);
 /* ---- GroupNorm / LayerNorm launch descriptors (test infrastructure: tests/norm_ref.py holds every statistics path of
  * csrc/kernels_norm.hip to an fp64 reference) ----
  * One int64 per argument of launch_groupnorm / launch_gn_stats / launch_gn_finalize / launch_layernorm.  EPS and GAMMA hold the bits

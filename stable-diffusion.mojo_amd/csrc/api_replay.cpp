@@ -8,6 +8,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "gemm_tiles.h"
 #include "graph.h"
 #include "replay_scan.h"
 
@@ -66,15 +67,6 @@ class GuardedOperands {
   };
   hipStream_t st_;
   std::vector<Slot> s_;
-};
-
-// A context option set for one launch: the previous value is back when the scope ends, on every path out of it
-template <class T>
-struct Override {
-  T& ref;
-  const T prev;
-  Override(T& r, T now) : ref(r), prev(r) { ref = now; }
-  ~Override() { ref = prev; }
 };
 
 int check_fields(const char* who, int n, int need) {
@@ -149,7 +141,8 @@ int64_t gd_c_cols(const int64_t* d) {
 }
 // Element extent of every operand the descriptor reads or writes, including the kernel's clamped loads (bias / row vector at
 // N - 4, residual at N - 8: all inside [0, N)).  Refuses what it cannot size; the combinations launch_gemm itself refuses are left to it.
-int gd_extents(const int64_t* d, int64_t* e) {
+// allocatable = false (planning only): the extents may exceed what one replay operand may hold.
+int gd_extents(const int64_t* d, int64_t* e, bool allocatable = true) {
   for (int i = 0; i < TSD_GO_COUNT; i++) e[i] = 0;
 #define GD_REQ(cond) \
   if (!(cond)) TSD_FAIL(TSD_E_ARG, "gemm_run: descriptor cannot be sized (%s)", #cond)
@@ -238,16 +231,57 @@ int gd_extents(const int64_t* d, int64_t* e) {
     GD_REQ(G > 0 && G <= N && rps > 0 && M % rps == 0 && ns > 0 && ns * 32 <= rps);
     e[TSD_GO_GN] = (M / rps) * ns * G * 2;
   }
-  for (int s = 0; s < TSD_GO_COUNT; s++) GD_REQ(e[s] >= 0 && e[s] <= lim);
+  for (int s = 0; s < TSD_GO_COUNT; s++) GD_REQ(e[s] >= 0 && (e[s] <= lim || !allocatable));
 #undef GD_REQ
   return TSD_OK;
 }
+// The launch a descriptor describes, without its operands: every GemmArgs field that is no pointer (what gemm_plan reads)
+GemmArgs gd_args(const int64_t* d) {
+  GemmArgs g;
+  g.conv = (int)d[TSD_GD_CONV]; g.M = (int)d[TSD_GD_M]; g.N = (int)d[TSD_GD_N]; g.K = (int)d[TSD_GD_K];
+  g.lda0 = (int)d[TSD_GD_LDA0]; g.lda1 = (int)d[TSD_GD_LDA1]; g.K0 = (int)d[TSD_GD_K0]; g.lda2 = (int)d[TSD_GD_LDA2];
+  g.ldw = (int)d[TSD_GD_LDW]; g.ldw1 = (int)d[TSD_GD_LDW1];
+  if (d[TSD_GD_W_KTS]) { g.ldw = 64; g.w_kts = g.N * 128; }  // the K-tile-major copy the model path builds for weight-heavy layers
+  g.batch = (int)d[TSD_GD_BATCH]; g.sA = d[TSD_GD_SA]; g.sW = d[TSD_GD_SW]; g.sC = d[TSD_GD_SC]; g.sR = d[TSD_GD_SR];
+  if (g.conv) {
+    g.Hs = (int)d[TSD_GD_HS]; g.Ws = (int)d[TSD_GD_WS]; g.Ho = (int)d[TSD_GD_HO]; g.Wo = (int)d[TSD_GD_WO]; g.Cin = (int)d[TSD_GD_CIN];
+    g.stride = (int)d[TSD_GD_STRIDE]; g.pad = (int)d[TSD_GD_PAD]; g.ups = (int)d[TSD_GD_UPS];
+    g.Cin1 = (int)d[TSD_GD_CIN1]; g.Cin2 = (int)d[TSD_GD_CIN2];
+  }
+  g.epi = (int)d[TSD_GD_EPI];
+  g.out_scale = f32_of(d[TSD_GD_OUT_SCALE]);
+  g.rowvec_ld = (int)d[TSD_GD_ROWVEC_LD]; g.rows_per_batch = (int)d[TSD_GD_ROWS_PER_BATCH];
+  g.ldr = (int)d[TSD_GD_LDR]; g.ldc = (int)d[TSD_GD_LDC];
+  if (d[TSD_GD_VT]) { g.vt_n0 = (int)d[TSD_GD_VT_N0]; g.vt_ld = (int)d[TSD_GD_VT_LD]; g.vt_S = (int)d[TSD_GD_VT_S]; g.vt_sB = d[TSD_GD_VT_SB]; }
+  g.gn_groups = (int)d[TSD_GD_GN_GROUPS]; g.gn_rows_per_sample = (int)d[TSD_GD_GN_RPS]; g.gn_nslab = (int)d[TSD_GD_GN_NSLAB];
+  g.rows_per_sample_hint = (int)d[TSD_GD_RPS_HINT];
+  return g;
+}
 }  // namespace
+
+// The plan of the launch desc describes, without a device: ctx == NULL plans under the options of the environment
+extern "C" int tsd_debug_gemm_plan(tsd_ctx* ctx, const int64_t* desc, int n, int cfg, int64_t* plan) {
+  NOTNULL(desc); NOTNULL(plan);
+  TSD_TRY(check_fields("gemm_plan", n, TSD_GD_COUNT));
+  int64_t ext[TSD_GO_COUNT];
+  TSD_TRY(gd_extents(desc, ext, false));  // a well-formed launch, of any size
+  TsdOptions opt;
+  if (ctx) opt = ctx->opt; else options_from_env(opt);
+  opt.force_cfg = cfg >= 0 ? cfg : -1;
+  if (cfg < 0) opt.sk_big_graph = (int)desc[TSD_GD_SK_BIG];
+  const GemmPlan p = gemm_plan(opt, gd_args(desc));
+  if (p.refused) TSD_FAIL(TSD_E_ARG, "gemm_plan: %s (tile configuration %d)", p.refused, p.cfg);
+  plan[TSD_GP_CFG] = p.cfg; plan[TSD_GP_WAYS] = p.ways; plan[TSD_GP_VARIANT] = p.variant;
+  plan[TSD_GP_BM] = p.BM; plan[TSD_GP_BN] = p.BN; plan[TSD_GP_BMW] = p.BMw; plan[TSD_GP_BNW] = p.BNw;
+  plan[TSD_GP_K] = p.K; plan[TSD_GP_WS_FLOATS] = p.ws_floats; plan[TSD_GP_LDS_BYTES] = p.lds_bytes;
+  plan[TSD_GP_GN_NSLAB] = p.gn_slabs((int)desc[TSD_GD_GN_RPS], (int)desc[TSD_GD_GN_GROUPS]);
+  return TSD_OK;
+}
 
 extern "C" int tsd_debug_gemm_run(tsd_ctx* ctx, const int64_t* desc, int n, int cfg, const void* const* host_in,
                                   void* const* host_out, int64_t* ext, int64_t* info) {
   NOTNULL(desc); NOTNULL(ext);
-  if (cfg >= 64) TSD_FAIL(TSD_E_ARG, "gemm_run: %d descriptor fields, cfg %d", n, cfg);
+  if (cfg >= 0 && !gemm_tile(cfg)) TSD_FAIL(TSD_E_ARG, "gemm_run: unknown tile configuration %d", cfg);
   TSD_TRY(check_fields("gemm_run", n, TSD_GD_COUNT));
   TSD_TRY(gd_extents(desc, ext));
   if (!host_in) return TSD_OK;  // sizing only: no context or device needed
@@ -266,34 +300,20 @@ extern "C" int tsd_debug_gemm_run(tsd_ctx* ctx, const int64_t* desc, int n, int 
   for (int s = TSD_GO_C; s < TSD_GO_COUNT; s++)
     if (ext[s])
       TSD_TRY(ops.add(s, ext[s], gd_elem_bytes(s, d), s == TSD_GO_C && alias ? host_in[TSD_GO_R] : nullptr, host_out[s - TSD_GO_C], logical[s - TSD_GO_C]));
-  GemmArgs g;
-  g.conv = (int)d[TSD_GD_CONV]; g.M = (int)d[TSD_GD_M]; g.N = (int)d[TSD_GD_N]; g.K = (int)d[TSD_GD_K];
-  g.A0 = (const half_t*)ops.at(TSD_GO_A0); g.lda0 = (int)d[TSD_GD_LDA0];
-  g.A1 = (const half_t*)ops.at(TSD_GO_A1); g.lda1 = (int)d[TSD_GD_LDA1]; g.K0 = (int)d[TSD_GD_K0];
-  g.A2 = (const half_t*)ops.at(TSD_GO_A2); g.lda2 = (int)d[TSD_GD_LDA2];
-  g.Wt = (const half_t*)ops.at(TSD_GO_W); g.ldw = (int)d[TSD_GD_LDW];
-  g.Wt1 = (const half_t*)ops.at(TSD_GO_WT1); g.ldw1 = (int)d[TSD_GD_LDW1];
-  g.batch = (int)d[TSD_GD_BATCH]; g.sA = d[TSD_GD_SA]; g.sW = d[TSD_GD_SW]; g.sC = d[TSD_GD_SC]; g.sR = d[TSD_GD_SR];
-  if (g.conv) {
-    g.Hs = (int)d[TSD_GD_HS]; g.Ws = (int)d[TSD_GD_WS]; g.Ho = (int)d[TSD_GD_HO]; g.Wo = (int)d[TSD_GD_WO]; g.Cin = (int)d[TSD_GD_CIN];
-    g.stride = (int)d[TSD_GD_STRIDE]; g.pad = (int)d[TSD_GD_PAD]; g.ups = (int)d[TSD_GD_UPS];
-    g.Cin1 = (int)d[TSD_GD_CIN1]; g.Cin2 = (int)d[TSD_GD_CIN2];
-  }
-  g.epi = (int)d[TSD_GD_EPI];
-  g.out_scale = f32_of(d[TSD_GD_OUT_SCALE]);
-  g.bias = (const float*)ops.at(TSD_GO_BIAS);
-  g.rowvec = (const float*)ops.at(TSD_GO_ROWVEC); g.rowvec_ld = (int)d[TSD_GD_ROWVEC_LD]; g.rows_per_batch = (int)d[TSD_GD_ROWS_PER_BATCH];
-  g.R = (const half_t*)(alias ? ops.at(TSD_GO_C) : ops.at(TSD_GO_R)); g.ldr = (int)d[TSD_GD_LDR];
-  g.C = ops.at(TSD_GO_C); g.ldc = (int)d[TSD_GD_LDC];
-  if (d[TSD_GD_VT]) { g.Vt = (half_t*)ops.at(TSD_GO_VT); g.vt_n0 = (int)d[TSD_GD_VT_N0]; g.vt_ld = (int)d[TSD_GD_VT_LD]; g.vt_S = (int)d[TSD_GD_VT_S]; g.vt_sB = d[TSD_GD_VT_SB]; }
-  g.gn_part = (float*)ops.at(TSD_GO_GN); g.gn_groups = (int)d[TSD_GD_GN_GROUPS]; g.gn_rows_per_sample = (int)d[TSD_GD_GN_RPS]; g.gn_nslab = (int)d[TSD_GD_GN_NSLAB];
-  g.rows_per_sample_hint = (int)d[TSD_GD_RPS_HINT];
-  if (d[TSD_GD_W_KTS]) {  // the K-tile-major copy the model path builds for weight-heavy layers
+  GemmArgs g = gd_args(d);
+  g.A0 = (const half_t*)ops.at(TSD_GO_A0); g.A1 = (const half_t*)ops.at(TSD_GO_A1); g.A2 = (const half_t*)ops.at(TSD_GO_A2);
+  g.Wt = (const half_t*)ops.at(TSD_GO_W); g.Wt1 = (const half_t*)ops.at(TSD_GO_WT1);
+  g.bias = (const float*)ops.at(TSD_GO_BIAS); g.rowvec = (const float*)ops.at(TSD_GO_ROWVEC);
+  g.R = (const half_t*)(alias ? ops.at(TSD_GO_C) : ops.at(TSD_GO_R));
+  g.C = ops.at(TSD_GO_C);
+  if (d[TSD_GD_VT]) g.Vt = (half_t*)ops.at(TSD_GO_VT);
+  g.gn_part = (float*)ops.at(TSD_GO_GN);
+  if (d[TSD_GD_W_KTS]) {  // the K-tile-major copy, made from the row-major W the caller passed
     const int KW = g.conv ? 9 * g.Cin : g.K;
     TSD_TRY(ops.add(W_TILE_MAJOR, (int64_t)g.N * KW, 2, nullptr));
     half_t* tm = (half_t*)ops.at(W_TILE_MAJOR);
     TSD_TRY(launch_pack_tile_major(ctx, g.Wt, g.N, KW, tm));
-    g.Wt = tm; g.ldw = 64; g.w_kts = g.N * 128;
+    g.Wt = tm;
   }
   if (g.conv && g.ups == 2 && g.Cin % 64 == 0 && host_in[TSD_GO_W]) {
     // the folded parity copies, made from the row-major W the caller passed by the routine tsd_model_prepare uses (model.cpp); whether the
@@ -305,7 +325,7 @@ extern "C" int tsd_debug_gemm_run(tsd_ctx* ctx, const int64_t* desc, int n, int 
     HIP_TRY(hipStreamSynchronize(ctx->stream));  // the upload reads `folded`
     g.Wuf = (const half_t*)ops.at(W_UPS_FOLDED);
   }
-  ctx->gemm_last_cfg = -1; ctx->gemm_last_ways = 0;
+  ctx->gemm_last = GemmPlan();
   int r;
   {  // the dispatcher's choice (with the recorded graph's long-K split) or a forced tile; a replay is not recorded
     Override<int> force(ctx->opt.force_cfg, cfg >= 0 ? cfg : -1);
@@ -314,7 +334,7 @@ extern "C" int tsd_debug_gemm_run(tsd_ctx* ctx, const int64_t* desc, int n, int 
     r = run_planned(ctx, [&]() -> int { return launch_gemm(ctx, g); });
   }
   HIP_TRY(hipStreamSynchronize(ctx->stream));
-  info[0] = ctx->gemm_last_cfg; info[1] = ctx->gemm_last_ways;
+  info[0] = ctx->gemm_last.cfg; info[1] = ctx->gemm_last.cfg >= 0 ? ctx->gemm_last.ways : 0;
   TSD_TRY(ops.read_back(&info[2]));
   return r;
 }

@@ -72,7 +72,7 @@ struct TsdOptions {
   int attn8_var = 0;       // TSD_ATTN8_VAR: timing / A-B variant of that kernel (builds with -DTSD_ATTN8_VARIANTS only)
   int attn_diag = 1;       // tsd_debug_set_attn_diag: second optimistic reference (the query's own key block)
   int attn_xcd = 0;        // TSD_ATTN_XCD: XCD-aware (head, query tile) map
-  // GEMM / conv dispatch (kernels_gemm.hip)
+  // GEMM / conv dispatch (gemm_plan.cpp)
   int xcdn = 0, conv_halo = 0, splitk = 1, splitk_mink = 4096, splitk_tiles = 256, splitk_small = 8, splitk_wide = 1, splitk_ring4 = 0,
       splitk_big = 0, sk_cfg = 5, thin_cfg = 0, tune = 15, sk256 = 0, skip128 = 1;  // sk256: TSD_GEMM_SK256 (256-row tiles for split-K launches)
   int force_cfg = -1;      // tsd_debug_gemm_bench / _check: tile configuration forced for the launches of this context
@@ -114,6 +114,27 @@ struct AttnPlan {
 };
 AttnPlan attn_plan(const TsdOptions& opt, int B, int H, int d, int Sq, int Sk);
 
+// Host-side plan of one GEMM / conv3x3 launch (gemm_plan.cpp): the tile configuration (a row of gemm_tiles.h) that runs, in how many
+// split-K slices, as which conv variant - what fixes the fp32 summation tree of the launch.  launch_gemm acts on it and leaves it in
+// tsd_ctx::gemm_last; the graph asks it for the statistics geometry; tsd_debug_gemm_run / _plan report it.  It does not depend on the epilogue.
+struct GemmArgs;
+struct GemmPlan {
+  const char* refused = nullptr;  // why this launch cannot run (TSD_E_ARG; cfg holds the offending id) - nothing else is filled in then
+  int cfg = -1;          // the tile configuration that runs: the dispatcher's choice after its halo-x / skip128 adjustments, or opt.force_cfg
+  int ways = 1;          // split-K slices (1: none)
+  int variant = 0;       // gemm_kernel's CV: 0 plain, 1 halo-x, 2 fused 1x1 skip source, 3 upsample fold
+  int BM = 0, BN = 0;    // tile
+  int BMw = 0, BNw = 0;  // one wave's sub-tile
+  int K = 0;             // the K the launch executes (4 * Cin under the upsample fold)
+  int lds_bytes = 0;
+  int64_t ws_floats = 0; // split-K workspace
+  bool gn_stats = false; // the tile's epilogue can emit GroupNorm statistics
+  int M = 0, N = 0, batch = 0;
+  // EPI_GNSTATS geometry: slabs per sample this launch emits for `groups` groups over its N channels, or 0 when its tile cannot
+  int gn_slabs(int rows_per_sample, int groups) const;
+};
+GemmPlan gemm_plan(const TsdOptions& opt, const GemmArgs& a);
+
 struct tsd_ctx {
   int device = 0;
   TsdOptions opt;
@@ -138,10 +159,10 @@ struct tsd_ctx {
   std::vector<int> prof_kern;   // kernel dispatches per record
   std::vector<int> prof_shape;  // 4 ints per record (M, N, K, batch) - 0 when not a GEMM
   size_t prof_n = 0;
-  // tsd_debug_gemm_record: TSD_GD_COUNT descriptor fields per GEMM launch enqueued while on; the dispatcher's last choice
+  // tsd_debug_gemm_record: TSD_GD_COUNT descriptor fields per GEMM launch enqueued while on
   bool gemm_rec_on = false;
   std::vector<int64_t> gemm_rec;
-  int gemm_last_cfg = -1, gemm_last_ways = 0;
+  GemmPlan gemm_last;         // plan of the last GEMM / conv3x3 launch enqueued (tsd_debug_gemm_run)
   GnPlan gn_last;             // plan of the last GroupNorm launch enqueued (tsd_debug_norm_run)
   int64_t gn_paths[8] = {};   // tsd_debug_gn_path_counts
   AttnPlan attn_last;         // plan of the last attention-core / row-softmax launch enqueued (tsd_debug_attn_run)
@@ -290,16 +311,15 @@ struct GemmArgs {
   int rows_per_sample_hint = 0;
 };
 int launch_gemm(tsd_ctx* ctx, const GemmArgs& a);
-bool gemm_ups_fold_ok(const tsd_ctx* ctx, const GemmArgs& a);  // may this conv3x3 over a 2x-upsampled source run with ups = 2?
+bool gemm_ups_fold_ok(const TsdOptions& opt, const GemmArgs& a);  // may this conv3x3 over a 2x-upsampled source run with ups = 2? (gemm_plan.cpp)
 // host fold of 3x3 weights [O][3][3][Ipad] (row pitch ldw >= 9 * Ipad, fp16 bits) into [4][O][2][2][Ipad]; returns the non-finite sums (model.cpp)
 int64_t ups_fold_host(const uint16_t* w, int O, int Ipad, int ldw, uint16_t* out);
 // ... and the same in the device layout GemmArgs::Wuf reads: per parity K-tile-major [4 * Ipad / 64][O][64], contiguous (Ipad % 64 == 0)
 int64_t ups_fold_pack_host(const uint16_t* w, int O, int Ipad, int ldw, uint16_t* out_tm);
-// the launch as a tsd_debug_gemm_* descriptor (TSD_GD_COUNT fields; api_ops.cpp)
+// the launch as a tsd_debug_gemm_* descriptor (TSD_GD_COUNT fields; api_replay.cpp)
 void gemm_describe(const tsd_ctx* ctx, const GemmArgs& a, int64_t* desc);
 // slices of the long-K split launches (K >= 8192, 16x16 level) for the graph being enqueued on this context; returns the previous value
 int gemm_set_splitk_big(tsd_ctx* ctx, int ways);
-int gemm_gnstats_slabs(const tsd_ctx* ctx, int M, int N, int K, int batch, int conv, int rows_per_sample, int groups);  // 0: not available
 
 // ---- other kernel launchers -----------------------------------------------------------
 // layout / elementwise (kernels_elementwise.hip)

@@ -26,7 +26,7 @@ Act act_alloc_gn(tsd_ctx* ctx, int B, int H, int W, int C, int groups) {
 // geometry that cannot do it leaves dst->gn_part NULL and the consumer runs its own statistics pass.
 static void gn_emit(const tsd_ctx* ctx, GemmArgs& g, Act* dst, int rows_per_sample) {
   if (!dst || !dst->gn_buf || dst->gn_groups <= 0 || g.N != dst->C || (g.epi & (EPI_OUT_F32 | EPI_GEGLU))) return;
-  const int ns = gemm_gnstats_slabs(ctx, g.M, g.N, g.K, g.batch, g.conv, rows_per_sample, dst->gn_groups);
+  const int ns = gemm_plan(ctx->opt, g).gn_slabs(rows_per_sample, dst->gn_groups);
   // up to 128 slabs the apply blocks (or k_gn_finalize) reduce them directly; beyond 256 (the VAE's 128^2 ... 512^2 images)
   // launch_groupnorm pre-reduces them to 64 chunks per sample (k_gn_prereduce) - either way no statistics pass over the tensor
   if (ns <= 0 || ns > ceil_div(rows_per_sample, 32) || (ns > 128 && ns <= 256) || (ns > 256 && dst->gn_groups > 256)) return;  // the 256-group limit is k_gn_prereduce's
@@ -72,7 +72,7 @@ int g_conv3x3(tsd_ctx* ctx, const Act& x, const ConvW& w, int stride, int pad, i
   // model_check_ready (ConvW::w_uf) the launch executes K = 4 Cin.  Model, options and the layer's shape decide - never the batch - so the
   // planning pass and the real pass take the same branch.  A one-parity tile holds no 32-raster-row slab: no statistics from this epilogue
   // (the consumer norm runs its own pass).
-  if (ups == 1 && w.w_uf && ctx->opt.ups_fold && gemm_ups_fold_ok(ctx, g)) {
+  if (ups == 1 && w.w_uf && ctx->opt.ups_fold && gemm_ups_fold_ok(ctx->opt, g)) {
     g.ups = 2; g.Wuf = w.w_uf;
     return launch_gemm(ctx, g);
   }

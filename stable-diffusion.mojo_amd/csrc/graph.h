@@ -6,6 +6,15 @@
 // how the C-ABI entry points (api_ops.cpp, api_model.cpp, api_replay.cpp) refuse a NULL pointer argument
 #define NOTNULL(p) \
   if (!(p)) TSD_FAIL(TSD_E_ARG, "%s: argument '%s' is NULL", __func__, #p)
+// A context option set for a scope (one replayed launch, one bench entry): the previous value is back when the scope ends, on every
+// path out of it - an early HIP_TRY / TSD_TRY return must not leave later launches of the context pinned
+template <class T>
+struct Override {
+  T& ref;
+  const T prev;
+  Override(T& r, T now) : ref(r), prev(r) { ref = now; }
+  ~Override() { ref = prev; }
+};
 
 // channel-concat view of up to two NHWC tensors with identical (B,H,W) (diffusion.mojo:253-270)
 struct CatSrc {

@@ -33,7 +33,8 @@
 #include <atomic>
 #include <vector>
 
-#include "common.h"
+#include "gemm_tiles.h"
+#include "graph.h"
 #include "lds_dma.h"
 
 #define TSD_STR2(x) #x
@@ -1152,40 +1153,23 @@ static int launch_cfg(tsd_ctx* ctx, const GemmK& k, int batch) {
   return TSD_OK;
 }
 
-// tile configurations: {wave grid M x N, fragments per wave M x N, LDS ring depth}
-//  id  tile      stages  LDS      use
-//   0  128x160   2       72 KiB   big-M UNet widths (N % 160 == 0), 2 blocks/CU
-//   1   64x160   2       56 KiB   mid-M
-//   2  128x128   2       64 KiB   VAE widths
-//   3   64x128   2       48 KiB
-//   4  128x16    2       36 KiB   N <= 16, many tiles (decoder 128->3)
-//  24   64x16    4       40 KiB   N <= 16, few tiles (UNet 320->4)
-//   5  128x160   3      108 KiB   deep ring, 1 block/CU
-//   6   64x160   4      112 KiB   few-tile problems (M = 2048 level)
-//   7   64x160   3       84 KiB
-//   8  128x128   3       96 KiB
-//   9   64x128   4       96 KiB
-//  10   64x128   3       72 KiB
-//  11  256x160   3      156 KiB   8 waves, 1 block/CU, two K-tiles of DMA in flight
-//  12  256x160   2      104 KiB   8 waves
-//  13  256x128   3      144 KiB   8 waves
-constexpr int N_GEMM_CFG = 56;
-
-// The upsample-fold variant (GemmK::ups == 2, CV = 3) exists for the tile configurations choose_cfg can return for a non-thin, unsplit
-// conv3x3 with N % 160 == 0; any other one is refused (launch_gemm's eligibility rule keeps the dispatcher inside this list)
+// The launch switches, generated from the tile table (gemm_tiles.h) in the order the kernels have always been instantiated in: the
+// upsample-fold variants (GemmK::ups == 2, CV = 3) of the tiles that have one, then per tile the plain variant (dense and conv3x3) and
+// the conv3x3 one with a fused 1x1 skip source, then the halo-x variants.  gemm_plan refuses an id that has no row (or no such variant)
+// before anything is enqueued; the defaults below only keep a switch total.
+#define UF_Y(...) __VA_ARGS__
+#define UF_N(...)
+#define HX_Y(...) __VA_ARGS__
+#define HX_N(...)
 static int launch_ups_fold(tsd_ctx* ctx, const GemmK& k, int batch, int id) {
   switch (id) {
-    case 0: return launch_cfg<2, 2, 4, 5, true, 2, false, 3>(ctx, k, batch);
-    case 1: return launch_cfg<2, 2, 2, 5, true, 2, false, 3>(ctx, k, batch);
-    case 5: return launch_cfg<2, 2, 4, 5, true, 3, false, 3>(ctx, k, batch);
-    case 6: return launch_cfg<2, 2, 2, 5, true, 4, false, 3>(ctx, k, batch);
-    case 7: return launch_cfg<2, 2, 2, 5, true, 3, false, 3>(ctx, k, batch);
-    case 51: return launch_cfg<4, 2, 4, 5, true, 3, false, 3, 4>(ctx, k, batch);
+#define TSD_TILE_CASE(ID, WGM, WGN, FM, FN, NS, PP, LW, UF, HX) UF(case ID: return launch_cfg<WGM, WGN, FM, FN, true, NS, PP, 3, LW>(ctx, k, batch);)
+    GEMM_TILES_MAIN(TSD_TILE_CASE)
+#undef TSD_TILE_CASE
     default: break;
   }
   TSD_FAIL(TSD_E_ARG, "gemm: tile configuration %d has no upsample-fold variant", id);
 }
-static bool ups_fold_cfg(int id) { return id == 0 || id == 1 || id == 5 || id == 6 || id == 7 || id == 51; }
 
 // SKV = 2 for a conv3x3 with a fused 1x1 skip source (GemmK::Cin1 > 0), else 0: the plain kernels carry none of its scalar state
 template <bool CONV, int SKV = 0>
@@ -1195,67 +1179,26 @@ static int launch_by_id(tsd_ctx* ctx, const GemmK& k, int batch, int id) {
     if (k.Cin1 > 0) return launch_by_id<CONV, 2>(ctx, k, batch, id);
   }
   switch (id) {
-    case 0: return launch_cfg<2, 2, 4, 5, CONV, 2, false, SKV>(ctx, k, batch);
-    case 1: return launch_cfg<2, 2, 2, 5, CONV, 2, false, SKV>(ctx, k, batch);
-    case 2: return launch_cfg<2, 2, 4, 4, CONV, 2, false, SKV>(ctx, k, batch);
-    case 3: return launch_cfg<2, 2, 2, 4, CONV, 2, false, SKV>(ctx, k, batch);
-    case 4: return launch_cfg<4, 1, 2, 1, CONV, 2, false, SKV>(ctx, k, batch);
-    case 5: return launch_cfg<2, 2, 4, 5, CONV, 3, false, SKV>(ctx, k, batch);
-    case 6: return launch_cfg<2, 2, 2, 5, CONV, 4, false, SKV>(ctx, k, batch);
-    case 7: return launch_cfg<2, 2, 2, 5, CONV, 3, false, SKV>(ctx, k, batch);
-    case 8: return launch_cfg<2, 2, 4, 4, CONV, 3, false, SKV>(ctx, k, batch);
-    case 9: return launch_cfg<2, 2, 2, 4, CONV, 4, false, SKV>(ctx, k, batch);
-    case 10: return launch_cfg<2, 2, 2, 4, CONV, 3, false, SKV>(ctx, k, batch);
-    case 11: return launch_cfg<4, 2, 4, 5, CONV, 3, false, SKV>(ctx, k, batch);
-    case 13: return launch_cfg<4, 2, 4, 4, CONV, 3, false, SKV>(ctx, k, batch);
-    // thin tile (N <= 16) with 64 rows and a 4-slot ring: few-tile problems (the UNet's 320 -> 4 output convolution)
-    case 24: return launch_cfg<4, 1, 1, 1, CONV, 4, false, SKV>(ctx, k, batch);
-    // loader-wave variants (LW = 4): 40 + the id of the 4-wave one-block-per-CU configuration they extend, 51 = cfg 11 + loaders
-    case 45: return launch_cfg<2, 2, 4, 5, CONV, 3, false, SKV, 4>(ctx, k, batch);
-    case 46: return launch_cfg<2, 2, 2, 5, CONV, 4, false, SKV, 4>(ctx, k, batch);
-    case 47: return launch_cfg<2, 2, 2, 5, CONV, 3, false, SKV, 4>(ctx, k, batch);
-    case 48: return launch_cfg<2, 2, 4, 4, CONV, 3, false, SKV, 4>(ctx, k, batch);
-    case 49: return launch_cfg<2, 2, 2, 4, CONV, 4, false, SKV, 4>(ctx, k, batch);
-    case 50: return launch_cfg<2, 2, 2, 4, CONV, 3, false, SKV, 4>(ctx, k, batch);
-    case 51: return launch_cfg<4, 2, 4, 5, CONV, 3, false, SKV, 4>(ctx, k, batch);
-    case 53: return launch_cfg<4, 2, 4, 4, CONV, 3, false, SKV, 4>(ctx, k, batch);
-    case 54: return launch_cfg<4, 2, 2, 5, CONV, 3, false, SKV, 4>(ctx, k, batch);  // 128x160, staggered: 8 compute waves of 32x80
-    case 55: return launch_cfg<4, 2, 2, 4, CONV, 3, false, SKV, 4>(ctx, k, batch);  // 128x128
-    // halo-x variants of 0 and 2 (conv3x3, stride 1: hx_eligible)
-    case 30: if constexpr (CONV && SKV == 0) return launch_cfg<2, 2, 4, 5, CONV, 2, false, 1>(ctx, k, batch); else break;
-    case 32: if constexpr (CONV && SKV == 0) return launch_cfg<2, 2, 4, 4, CONV, 2, false, 1>(ctx, k, batch); else break;
-#ifdef TSD_GEMM_EXPERIMENTAL  // measured, not faster: built only to reproduce those numbers
-    case 12: return launch_cfg<4, 2, 4, 5, CONV, 2, false, SKV>(ctx, k, batch);
-    case 14: return launch_cfg<2, 2, 8, 5, CONV, 3, false, SKV>(ctx, k, batch);
-    case 15: return launch_cfg<2, 2, 8, 5, CONV, 2, false, SKV>(ctx, k, batch);
-    case 16: return launch_cfg<4, 2, 4, 5, CONV, 3, true, SKV>(ctx, k, batch);  // 256x160 ping-pong
-    case 17: return launch_cfg<4, 2, 2, 5, CONV, 3, true, SKV>(ctx, k, batch);  // 128x160 ping-pong
-    case 18: return launch_cfg<4, 2, 4, 4, CONV, 3, true, SKV>(ctx, k, batch);  // 256x128 ping-pong
-    case 19: return launch_cfg<4, 2, 2, 4, CONV, 3, true, SKV>(ctx, k, batch);  // 128x128 ping-pong
-    case 20: return launch_cfg<2, 2, 2, 5, CONV, 5, false, SKV>(ctx, k, batch);  // 64x160, 5-slot ring: slower than 4 slots (667 vs 821 TF)
-    case 21: return launch_cfg<2, 2, 2, 4, CONV, 6, false, SKV>(ctx, k, batch);  // 64x128, 6-slot ring
-#endif
+#define TSD_TILE_CASE(ID, WGM, WGN, FM, FN, NS, PP, LW, UF, HX) case ID: return launch_cfg<WGM, WGN, FM, FN, CONV, NS, PP, SKV, LW>(ctx, k, batch);
+    GEMM_TILES_MAIN(TSD_TILE_CASE)
+#undef TSD_TILE_CASE
+    // halo-x variants (conv3x3, stride 1: gemm_plan.cpp hx_shape_ok)
+#define TSD_TILE_CASE(ID, WGM, WGN, FM, FN, NS, PP, LW, UF, HX) \
+  HX(case ID + GEMM_HX_ID: if constexpr (CONV && SKV == 0) return launch_cfg<WGM, WGN, FM, FN, CONV, NS, PP, 1, LW>(ctx, k, batch); else break;)
+    GEMM_TILES_MAIN(TSD_TILE_CASE)
+#undef TSD_TILE_CASE
+#define TSD_TILE_CASE(ID, WGM, WGN, FM, FN, NS, PP, LW, UF, HX) case ID: return launch_cfg<WGM, WGN, FM, FN, CONV, NS, PP, SKV, LW>(ctx, k, batch);
+    GEMM_TILES_EXPERIMENTAL(TSD_TILE_CASE)
+#undef TSD_TILE_CASE
     default: break;
   }
   TSD_FAIL(TSD_E_ARG, "gemm: unknown tile configuration %d", id);
 }
+#undef UF_Y
+#undef UF_N
+#undef HX_Y
+#undef HX_N
 
-// conv3x3 problems the halo-x K order can run: stride 1 on the source grid, whole 128-pixel tiles made of 64- or 128-pixel
-// image-row segments, no split-K
-// OFF by default: the halo-x order sums K in a different order than every other tile configuration, and which
-// configuration runs depends on M - a sample computed alone would no longer equal its row of a batch bit for bit.  Measured
-// with it on (TSD_CONV_HALO=1: the 128x128-tile convs, 2: the 128x160 ones too): decoder 26.1 -> 25.7 ms, encoder 13.95 ->
-// 13.70 ms, UNet step unchanged.  tests/test_gpu_ops.py keeps the path correct against the plain configurations.
-static bool hx_shape_ok(const GemmK& k);
-static bool hx_eligible(const TsdOptions& o, const GemmK& k) { return o.conv_halo > 0 && hx_shape_ok(k); }
-static bool hx_shape_ok(const GemmK& k) {
-  return k.stride == 1 && !k.ups && k.pad == 1 && k.splitk <= 1 && !k.Cin1 && k.Hs == k.Ho && k.Ws == k.Wo && k.Cin % 64 == 0 &&
-         (k.Wo == 64 || k.Wo % 128 == 0) && ((long long)k.Ho * k.Wo) % 128 == 0 && k.M % 128 == 0 && k.Ho < 2040 && k.Wo < 2040;
-}
-
-// Split-K by 2 pays when a 128-row tiling leaves about half the CUs idle and K is long: the M = 2048 level of the UNet
-// (16 x 8 tiles of 128x160, K = 5120..23040).  64-row tiles fill the chip there but move 46 flop per LDS-DMA byte and
-// are bound by the per-CU DMA rate; two 128-row half-K blocks move 71 flop/B.
 // Workgroup -> XCD placement probe (HW_REG_XCC_ID).  The split-K hand-off is placement-independent (sc1 stores/loads),
 // so this only tells whether the same-XCD pairing of its two blocks - a speed choice - holds on this device.
 __global__ void k_probe_xcc(int* out) {
@@ -1285,186 +1228,13 @@ extern "C" int tsd_debug_xcd_round_robin(void) { return xcd_round_robin() ? 1 : 
 
 // slices for K >= 8192 at the 16x16 level asked for by the graph being enqueued on this context (0: default)
 int gemm_set_splitk_big(tsd_ctx* ctx, int ways) { const int prev = ctx->opt.sk_big_graph; ctx->opt.sk_big_graph = ways; return prev; }
-// Split-K plan: number of K slices (1 = none) and the tile configuration the split launch runs with.
-static int splitk_plan(const TsdOptions& o, int M, int N, int K, int batch, int rps, int* cfg) {
-  const int on = o.splitk;
-  // The decision must not depend on the batch size (bitwise batch invariance: a split changes the fp32 summation
-  // tree), so it keys on the layer: rows per sample, N and K.
-  //  * rps <= 256 (the 16x16 level of a 64x64 latent): 2 slices of 128-row tiles once K >= 4096;
-  //  * rps <= 64 (an 8x8 level: the full-size UNet's deepest at a 64x64 latent, the 23-layer graph's at 32x32): M is
-  //    a few hundred rows, so 64-row tiles and up to 8 slices - 32 tiles x 8 fill the chip where 16 tiles x 2 left
-  //    7/8 of it idle.
-  const int min_k = o.splitk_mink, max_tiles = o.splitk_tiles, small_ways = o.splitk_small;
-  // Round 3 (late): two more layer classes that left half the chip idle at batch 8 -
-  //  * rps <= 256 with at most 4 tile columns (the 32x32 -> 16x16 downsampling conv, N = 640, K = 5760: 64 tiles): 4 slices;
-  //  * rps <= 1024 with N * rps <= 320 * 1024 (the 64x64 -> 32x32 downsampling conv, N = 320, K = 2880: 128 tiles): 2 slices.
-  const int wide = o.splitk_wide;
-  const bool mid = wide && rps > 256 && rps <= 1024 && (long long)N * rps <= 320LL * 1024 && K >= 2880;
-  // Round 4 (TSD_GEMM_SK256): 256x160 tiles (the staggered loader-wave configuration 51) for split launches, with twice the slices so
-  // that the grid stays the same: a K tile then pulls 52 KB from the L2 for twice the products of a 128x160 tile's 36 KB (98 instead of
-  // 71 flop per L2 byte; the K loops of these layers run on the L2 -> CU path).  Bit 0: the 16x16-level layers that split
-  // already; bit 1: the 32x32-level 640-wide convolutions (K >= 5760: 256 tiles of 128x160 today, no split).  Keyed on the layer only.
-  const bool mid256 = (o.sk256 & 2) && rps == 1024 && N == 640 && K >= 5760;
-  if (!on || batch != 1 || N <= 16 || rps <= 0 || (rps > 256 && !mid && !mid256)) return 1;
-  const bool n160 = (N % 160 == 0);
-  const int BN = n160 ? 160 : 128;
-  int ways = 1, BM = 128;
-  if (rps <= 64 && small_ways > 1) {
-    ways = K >= 8192 ? 8 : (K >= 2048 ? 4 : (K >= 1024 ? 2 : 1));
-    if (ways > small_ways) ways = small_ways;
-    BM = 64;
-    const int deep = o.splitk_ring4;
-    if (cfg) *cfg = deep ? (n160 ? 6 : 9) : (n160 ? 7 : 10);
-  } else {
-    const int big_env = o.splitk_big;
-    // 2 slices for the 23-layer UNet at batch 8; the full-size UNet's graph asks for 4 (gemm_set_splitk_big: +4.3 % at its batch of 4,
-    // -0.8 % on the headline).  A per-GRAPH choice, so every batch size of a model sums in the same tree.
-    const int big_ways = big_env ? big_env : (o.sk_big_graph ? o.sk_big_graph : 2);
-    ways = K >= 8192 ? big_ways : (K >= min_k ? 2 : 1);
-    if (wide && ways == 2 && ceil_div(N, BN) <= 4) ways = 4;
-    if (mid) ways = 2;
-    const int sk128 = o.sk_cfg;  // 45: the same tile with loader waves
-    if (cfg) *cfg = n160 ? sk128 : 8;
-    const int tn = ceil_div(N, BN);
-    const bool xcd256 = tn % 8 == 0 || (wide && rps % 256 == 0 && (tn * (rps / 256)) % 8 == 0);  // a tile's slices stay on one XCD
-    if (n160 && xcd256 && ((mid256 && !mid) || ((o.sk256 & 1) && rps == 256 && ways >= 2 && ways <= 4))) {
-      ways = mid256 ? 2 : ways * 2;
-      BM = 256;
-      if (cfg) *cfg = 51;
-    }
-  }
-  // Eligibility looks at N only (8 | N-tiles keeps a tile's slices on one XCD for any M): a condition on the tile
-  // count would make the split - and with it the fp32 summation tree - depend on the batch.  The two M-dependent
-  // guards below cannot trigger inside the API's limits (B <= 16 with rps <= 256 gives at most 256 tiles).
-  // (round 3: 8 | tiles of one sample does the same for the layers with fewer tile columns)
-  const int tiles_n = ceil_div(N, BN), tiles = ceil_div(M, BM) * tiles_n;
-  const bool xcd_ok = tiles_n % 8 == 0 || (wide && rps % BM == 0 && (tiles_n * (rps / BM)) % 8 == 0);
-  if (ways == 1 || !xcd_ok || tiles > 2 * max_tiles || (ways - 1) * tiles > 4095) return 1;
-  return ways;
-}
-static int choose_cfg(const TsdOptions& o, int M, int N, int K, int batch, bool conv, int rps = 0) {
-  {  // tuning aid: TSD_GEMM_CFG_OVERRIDE="M,N,K:cfg[;M,N,K:cfg...]" forces a tile configuration for exact shapes inside a real step
-    const char* ov = o.cfg_override;
-    if (ov[0]) {
-      for (const char* q = ov; q && *q;) {
-        int m = 0, n = 0, k = 0, c = 0;
-        if (sscanf(q, "%d,%d,%d:%d", &m, &n, &k, &c) == 4 && m == M && n == N && k == K) return c;
-        q = strchr(q, ';');
-        if (q) q++;
-      }
-    }
-  }
-  if (N <= 16) {
-    // the UNet's 320 -> 4 output convolution is one 128-row block per CU walking 45 K tiles behind a 2-slot ring: 64-row tiles with
-    // a 4-slot ring (two blocks per CU, three tiles in flight) take 20 us where it took 33 in the step; with thousands of tiles
-    // (the decoder's 128 -> 3 at 512 x 512) the 128-row tile stays ahead (277 vs 329 us).  Bitwise the same results either way.
-    const int thin = o.thin_cfg;
-    if (thin) return thin;
-    return (long long)ceil_div(M, 128) * batch <= 1024 ? 24 : 4;
-  }
-  {
-    int sk_cfg = 0;
-    if (splitk_plan(o, M, N, K, batch, rps, &sk_cfg) > 1) return sk_cfg;
-  }
-  const bool n160 = (N % 160 == 0);
-  const int BN = n160 ? 160 : 128;
-  // measured on MI355X (scripts/bench_gemm.py with REAL_EPI=1, pinned issue order):
-  //  * >= 2 tiles of 128 rows per CU: two 4-wave blocks per CU (cfg 0/2);
-  //  * dense GEMMs whose 256x160 tiling is exactly one or two full rounds of the 256 CUs: the 8-wave tile (cfg 11)
-  //    halves the operand traffic per flop and its prologue/epilogue count;
-  //  * around one 128-row tile per CU: long K -> one 128-row block with a 3-slot DMA ring (one wave per SIMD, the
-  //    pinned schedule keeps its MFMA pipe fed), short K -> 64-row tiles, two blocks per CU (fixed costs overlap);
-  //  * fewer tiles than that: 64-row tiles with 3 ring slots, 4 when K is long.
-  const long long t128 = (long long)ceil_div(M, 128) * ceil_div(N, BN) * batch;
-  const long long t256 = (long long)ceil_div(M, 256) * ceil_div(N, BN) * batch;
-  const int tune = o.tune;  // A/B switch for the rules below
-  // Round 3: the staggered wave-specialised 256-row tiles (51 / 53: 8 compute waves in two groups + 4 loader waves) where a
-  // 256-row tiling gives every CU whole tiles - measured -5...-10 % against configurations 0 / 2 / 11 on these shapes
-  // (profiles/r03_loader_waves_ab.txt); TSD_GEMM_TUNE bit 2 turns them off.  Results are bitwise those of every other tile.
-  if ((tune & 4) && M % 256 == 0) {
-    if (n160 && conv && t256 >= 256 && t256 % 256 == 0) return 51;
-    if (n160 && !conv && K >= 256 && (t256 == 256 || t256 == 384 || t256 == 512 || (t256 >= 192 && t256 < 256))) return 51;  // K < 256 (the im2col input conv, one K tile): nothing for loaders to do, 128x160 is 15 us against 20  // 192: the 16x16 level's fused q/k/v projection (23 us against 26-33 for the other tiles)
-    if (!n160 && conv && N % 128 == 0 && N >= 256 && t256 >= 512 && K >= 2304) return 53;  // K = 1152 (128 -> 256 at 256 x 256): 128x128 tiles, 0.42 vs 0.45 ms in-step
-  }
-  if ((tune & 1) && !conv && n160 && K >= 256 && (t256 == 256 || t256 == 512) && M % 256 == 0) return 11;
-  if (t128 >= 512) return n160 ? 0 : 2;
-  // Round 3 (late), measured INSIDE the step (TSD_GEMM_CFG_OVERRIDE + experiments/drivers/instep_sweep.sh; the repeated-launch microbenchmark
-  // keeps the operands in the L2 and ranks these the other way round): dense GEMMs with exactly one 128-row tile per CU run the
-  // staggered 128x160 tile with loader waves (54: 8192x640x640 19.4 -> 17.7 us, 8192x640x2560 42 -> 39.7 us), and the 256-tile
-  // 64-row problems of the 16x16 level the 64x160 tile with loader waves (47: 2048x1280x1280 20.2 -> 19.2 us); TSD_GEMM_TUNE bit 3
-  if ((tune & 8) && !conv && n160 && t128 == 256 && M % 128 == 0 && K < 5760) return 54;
-  if ((tune & 8) && !conv && n160 && N >= 8192 && t128 >= 384) return 0;  // few rows, very wide (context K | V^T: 34 -> 29 us)
-  if (t128 >= 192) return (K >= 2560 || !(tune & 2)) ? (n160 ? 5 : 8) : (n160 ? 1 : 3);
-  if (K >= 5760) return n160 ? 6 : 9;
-  {  // 256 tiles: measured on 2048x1280x1280; 128 tiles: the full-size UNet's 1024x1280x1280 at batch 4 (0.483 -> 0.463 ms for its 25 launches)
-    const long long t64 = (long long)ceil_div(M, 64) * ceil_div(N, BN) * batch;
-    if ((tune & 8) && !conv && n160 && (t64 == 256 || t64 == 128) && M % 64 == 0 && N >= 1280) return 47;
-  }
-  return n160 ? 7 : 10;
-}
-
-// rows / columns of one wave's output sub-tile for tile configuration `id` (FM*16, FN*16)
-static void cfg_wave_tile(int id, int* bmw, int* bnw) {
-  switch (id) {
-    case 0: case 5: case 11: case 45: case 51: *bmw = 64; *bnw = 80; break;
-    case 1: case 6: case 7: case 46: case 47: case 54: *bmw = 32; *bnw = 80; break;
-    case 2: case 8: case 13: case 48: case 53: *bmw = 64; *bnw = 64; break;
-    case 3: case 9: case 10: case 49: case 50: case 55: *bmw = 32; *bnw = 64; break;
-    default: *bmw = 0; *bnw = 0; break;  // thin / experimental tiles: no epilogue statistics
-  }
-}
-// EPI_GNSTATS geometry for a launch of this shape: slabs per sample (rows_per_sample / wave rows), or 0 when the tile
-// it would run with cannot emit statistics for `groups` groups over N channels.
-int gemm_gnstats_slabs(const tsd_ctx* ctx, int M, int N, int K, int batch, int conv, int rows_per_sample, int groups) {
-  if (groups <= 0 || N % groups || (N & 7) || batch != 1) return 0;
-  int bmw, bnw;
-  // the tile that will run: a forced configuration (tsd_debug_gemm_run) must be judged by its own wave tile - one whose wave columns
-  // split a group would write that group's slot from two waves
-  const int id = ctx->opt.force_cfg >= 0 ? ctx->opt.force_cfg : choose_cfg(ctx->opt, M, N, K, batch, conv != 0, rows_per_sample);
-  cfg_wave_tile(id, &bmw, &bnw);
-  const int cpg = N / groups;
-  if (!bmw || bnw % cpg || rows_per_sample % bmw || M % rows_per_sample) return 0;
-  return rows_per_sample / 32;  // one slab per 32-row epilogue pass, independent of the tile shape
-}
-
-template <bool CONV>
-static int dispatch(tsd_ctx* ctx, const GemmK& k, int batch) {
-  const TsdOptions& o = ctx->opt;
-  const int force_cfg = o.force_cfg;
-  int id = force_cfg >= 0 ? force_cfg : (k.splitk > 1 ? k.sk_cfg : choose_cfg(o, k.M, k.N, k.K, batch, CONV));
-  // halo-x measured: -3...5 % on the 128x128-tile convs of the VAE (N = 128 / 256 / 512), nothing on the 128x160 ones (TSD_CONV_HALO=2 turns those on too)
-  // (the halo-x K order addresses W row-major: a launch that reads the K-tile-major weight copy keeps its plain tile)
-  if (CONV && force_cfg < 0 && k.w_kts == 128u && hx_eligible(o, k) && (id == 2 || (id == 0 && o.conv_halo >= 2))) id += 30;
-  // rounds 3-4: the fused-skip variant of the 128x128 two-blocks-per-CU tile kept its offset tables in scratch (48 B per lane) and the
-  // decoder's 256 -> 128 residual block at 512 x 512 (K = 1152 + 256) ran its 64-row sibling instead (1.18 ms against 1.35).  Round 5:
-  // the scratch is gone (conv_tap_ptrs); TSD_GEMM_SKIP128=0 restores the detour for A/B runs
-  if (CONV && force_cfg < 0 && k.Cin1 > 0 && id == 2 && !o.skip128) id = 3;
-  if ((id == 30 || id == 32) && !(CONV && hx_shape_ok(k) && k.w_kts == 128u)) TSD_FAIL(TSD_E_ARG, "gemm: halo-x tile configuration %d on an ineligible problem", id);
-  ctx->gemm_last_cfg = id; ctx->gemm_last_ways = k.splitk;
-  if (ctx->gemm_rec_on && ctx->gemm_rec.size() >= TSD_GD_COUNT) {  // launch_gemm recorded this launch's descriptor last
-    int64_t* d = &ctx->gemm_rec[ctx->gemm_rec.size() - TSD_GD_COUNT];
-    d[TSD_GD_CFG] = id; d[TSD_GD_WAYS] = k.splitk;
-  }
-  return launch_by_id<CONV>(ctx, k, batch, id);
-}
-
-// The bench / check entries below pin the tile configuration through the context; the guard puts "dispatcher's choice" back on EVERY
-// way out (a HIP_TRY / TSD_TRY early return used to leave later launches of the context pinned: ADVICE r04)
-namespace {
-struct ForceCfgGuard {
-  tsd_ctx* ctx;
-  ForceCfgGuard(tsd_ctx* c, int cfg) : ctx(c) { ctx->opt.force_cfg = cfg; }
-  ~ForceCfgGuard() { ctx->opt.force_cfg = -1; }
-  void set(int cfg) { ctx->opt.force_cfg = cfg; }
-};
-}  // namespace
 
 // Debug/bench entry: time `iters` launches of one GEMM / conv3x3 problem on synthetic device data with a forced
 // tile configuration (cfg < 0: the dispatcher's choice).  conv: M = B*Ho*Wo from (B,H,W,stride,ups), K = 9*Cin.
 extern "C" int tsd_debug_gemm_bench(tsd_ctx* ctx, int conv, int B, int H, int W, int Cin, int N, int stride, int ups,
                                     int cfg, int iters, float* ms) {
   if (!ctx || !ms || iters <= 0) TSD_FAIL(TSD_E_ARG, "gemm_bench: bad argument");
-  if (cfg >= N_GEMM_CFG) TSD_FAIL(TSD_E_ARG, "gemm_bench: cfg %d out of range", cfg);
+  if (cfg >= 0 && !gemm_tile(cfg)) TSD_FAIL(TSD_E_ARG, "gemm_bench: unknown tile configuration %d", cfg);
   HIP_TRY(hipSetDevice(ctx->device));
   const int Hi = ups ? 2 * H : H, Wi = ups ? 2 * W : W;
   const int Ho = conv ? (Hi + 2 - 3) / stride + 1 : H, Wo = conv ? (Wi + 2 - 3) / stride + 1 : W;
@@ -1499,7 +1269,7 @@ extern "C" int tsd_debug_gemm_bench(tsd_ctx* ctx, int conv, int B, int H, int W,
     if (epi_mode == 1) { HIP_TRY(hipMemsetAsync(R, 0, (size_t)nc * 2, ctx->stream)); g.R = R; g.ldr = N; g.epi |= EPI_RESIDUAL; }
     else { g.epi |= EPI_GEGLU; g.ldc = N / 2; }
   }
-  ForceCfgGuard forced(ctx, cfg);
+  Override<int> forced(ctx->opt.force_cfg, cfg);  // "dispatcher's choice" is back on EVERY way out
   int r = launch_gemm(ctx, g);
   if (r == TSD_OK) r = launch_gemm(ctx, g);
 #ifdef TSD_GEMM_TS
@@ -1538,7 +1308,7 @@ extern "C" int tsd_debug_gemm_bench(tsd_ctx* ctx, int conv, int B, int H, int W,
   HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
   const int alt = ctx->opt.bench_altcfg;  // alternate two kernels (cold I-cache probe)
   for (int i = 0; i < iters && r == TSD_OK; i++) {
-    if (alt >= 0) forced.set((i & 1) ? alt : cfg);
+    if (alt >= 0) ctx->opt.force_cfg = (i & 1) ? alt : cfg;
     g.Wt = Wt + (int64_t)(i % wrot) * nw1;
     r = launch_gemm(ctx, g);
   }
@@ -1556,7 +1326,7 @@ extern "C" int tsd_debug_gemm_bench(tsd_ctx* ctx, int conv, int B, int H, int W,
 extern "C" int tsd_debug_gemm_check(tsd_ctx* ctx, int conv, int B, int H, int W, int Cin, int N, int stride, int ups,
                                     int cfg, int ref_cfg, float* max_abs_diff, float* max_abs_ref) {
   if (!ctx || !max_abs_diff || !max_abs_ref) TSD_FAIL(TSD_E_ARG, "gemm_check: bad argument");
-  if (cfg >= N_GEMM_CFG || ref_cfg >= N_GEMM_CFG) TSD_FAIL(TSD_E_ARG, "gemm_check: cfg out of range");
+  if ((cfg >= 0 && !gemm_tile(cfg)) || (ref_cfg >= 0 && !gemm_tile(ref_cfg))) TSD_FAIL(TSD_E_ARG, "gemm_check: unknown tile configuration");
   HIP_TRY(hipSetDevice(ctx->device));
   const int Hi = ups ? 2 * H : H, Wi = ups ? 2 * W : W;
   const int Ho = conv ? (Hi + 2 - 3) / stride + 1 : H, Wo = conv ? (Wi + 2 - 3) / stride + 1 : W;
@@ -1579,10 +1349,10 @@ extern "C" int tsd_debug_gemm_check(tsd_ctx* ctx, int conv, int B, int H, int W,
   if (conv) { g.conv = 1; g.Hs = H; g.Ws = W; g.Ho = Ho; g.Wo = Wo; g.Cin = Cin; g.stride = stride; g.pad = 1; g.ups = ups; }
   int r;
   {
-    ForceCfgGuard forced(ctx, ref_cfg);
+    Override<int> forced(ctx->opt.force_cfg, ref_cfg);
     g.C = C0;
     r = launch_gemm(ctx, g);
-    g.C = C1; forced.set(cfg);
+    g.C = C1; ctx->opt.force_cfg = cfg;
     if (r == TSD_OK) r = launch_gemm(ctx, g);
   }
   if (r != TSD_OK) return r;
@@ -1610,21 +1380,6 @@ extern "C" int tsd_debug_splitk_errors(tsd_ctx* ctx) {
   return v;
 }
 
-// Upsample fold (GemmArgs::ups == 2): may this conv3x3 over a nearest-2x upsampled source run as four parity-planar 2x2 convolutions?
-// Decided on the LAYER (source plane, channels, width, epilogue) and never on M: which kernel runs must not change with the batch.
-//  * stride 1, pad 1, no fused skip, no residual / statistics / fp32 epilogue (a one-parity tile holds no 32-raster-row slab);
-//  * Cin % 64 == 0 (whole K tiles per folded tap) and N % 160 == 0 (the tile family the variant is built for);
-//  * Hs * Ws % 256 == 0: every tile height the dispatcher can choose divides a parity plane;
-//  * no split-K for the executed problem (rows per sample, N, 4 * Cin).
-bool gemm_ups_fold_ok(const tsd_ctx* ctx, const GemmArgs& a) {
-  if (!a.conv || a.stride != 1 || a.pad != 1 || a.Cin1 || a.Cin2 || a.batch != 1 || a.Vt) return false;
-  if (a.epi & (EPI_RESIDUAL | EPI_RES_UPS | EPI_GNSTATS | EPI_OUT_F32)) return false;
-  if (a.Cin <= 0 || a.Cin % 64 || a.N % 160 || a.K != 9 * a.Cin) return false;
-  const long long S = (long long)a.Hs * a.Ws;
-  if (a.Hs <= 0 || a.Ws <= 0 || a.Hs >= 2040 || a.Ws >= 2040 || S % 256 || a.Ho != 2 * a.Hs || a.Wo != 2 * a.Ws || a.M <= 0 || a.M % (4 * S)) return false;
-  return splitk_plan(ctx->opt, a.M, a.N, 4 * a.Cin, a.batch, a.Ho * a.Wo, nullptr) == 1;
-}
-
 int launch_gemm(tsd_ctx* ctx, const GemmArgs& a) {
   if (a.M <= 0 || a.N <= 0 || a.K <= 0) TSD_FAIL(TSD_E_SHAPE, "gemm: empty problem M=%d N=%d K=%d", a.M, a.N, a.K);
   if (a.K % 64) TSD_FAIL(TSD_E_SHAPE, "gemm: K=%d must be a multiple of 64 (pad at pack time)", a.K);
@@ -1640,11 +1395,7 @@ int launch_gemm(tsd_ctx* ctx, const GemmArgs& a) {
         TSD_FAIL(TSD_E_ARG, "conv3x3: fused skip source (%d + %d channels) does not fit this convolution", a.Cin1, a.Cin2);
     }
     if (a.batch != 1) TSD_FAIL(TSD_E_ARG, "conv3x3: batch is folded into M");
-    if (a.ups == 2) {  // refused before anything is enqueued: the outputs stay as they were
-      if (!a.Wuf || !gemm_ups_fold_ok(ctx, a)) TSD_FAIL(TSD_E_ARG, "conv3x3: this launch cannot run the upsample fold (ups = 2)");
-      if (ctx->opt.force_cfg >= 0 && !ups_fold_cfg(ctx->opt.force_cfg))
-        TSD_FAIL(TSD_E_ARG, "conv3x3: tile configuration %d has no upsample-fold variant", ctx->opt.force_cfg);
-    } else if (a.ups < 0 || a.ups > 2) TSD_FAIL(TSD_E_ARG, "conv3x3: ups = %d", a.ups);
+    if (a.ups < 0 || a.ups > 2 || (a.ups == 2 && !a.Wuf)) TSD_FAIL(TSD_E_ARG, "conv3x3: ups = %d%s", a.ups, a.ups == 2 ? " without the folded weights" : "");
   } else {
     if (a.K0 % 64) TSD_FAIL(TSD_E_SHAPE, "gemm: concat split K0=%d must be a multiple of 64", a.K0);
   }
@@ -1657,6 +1408,10 @@ int launch_gemm(tsd_ctx* ctx, const GemmArgs& a) {
     if (a_bytes > lim || w_bytes > lim || s_bytes > lim)
       TSD_FAIL(TSD_E_SHAPE, "gemm: operand slice of %lld / %lld bytes exceeds the 2 GiB addressing window", a_bytes, w_bytes);
   }
+  if (a.w_kts && (a.ldw != 64 || a.w_kts < a.N * 128)) TSD_FAIL(TSD_E_ARG, "gemm: K-tile-major W needs ldw = 64 and a tile stride >= N * 128");
+  // the one host decision of this launch (gemm_plan.cpp); a refusal comes before anything is enqueued: the outputs stay as they were
+  const GemmPlan plan = gemm_plan(ctx->opt, a);
+  if (plan.refused) TSD_FAIL(TSD_E_ARG, "gemm: %s (tile configuration %d)", plan.refused, plan.cfg);
   if (a.Vt) {
     const int BNt = (a.N % 160 == 0) ? 160 : 128;
     if (a.conv || a.batch != 1 || (a.epi & ~(EPI_BIAS_N)) || a.N % 8 || a.N <= 16 || a.vt_n0 <= 0 || a.vt_n0 % BNt || a.vt_S <= 0 || a.vt_S % 8 ||
@@ -1665,24 +1420,23 @@ int launch_gemm(tsd_ctx* ctx, const GemmArgs& a) {
   }
   if (a.epi & EPI_GNSTATS) {
     if ((a.epi & (EPI_GEGLU | EPI_OUT_F32)) || !a.gn_part ||
-        a.gn_nslab != gemm_gnstats_slabs(ctx, a.M, a.N, a.K, a.batch, a.conv, a.gn_rows_per_sample, a.gn_groups) || a.gn_nslab <= 0)
+        a.gn_nslab != plan.gn_slabs(a.gn_rows_per_sample, a.gn_groups) || a.gn_nslab <= 0)
       TSD_FAIL(TSD_E_ARG, "gemm: GroupNorm statistics requested for a shape/tile that cannot emit them");
   }
   // split-K workspace (arena: the planning pass sees the same allocation) and the per-context arrival flags
   float* sk_ws = nullptr;
-  int sk_cfg = 0;
-  const bool uf = a.conv && a.ups == 2;  // runs K = 4 * Cin on the folded copies; the launch stays DESCRIBED (record, profile) as the 3x3 it computes
-  const int ways = uf ? 1 : ctx->opt.force_cfg < 0 ? splitk_plan(ctx->opt, a.M, a.N, a.K, a.batch, a.rows_per_sample_hint, &sk_cfg) : 1;
-  const bool splitk = ways > 1;
+  const bool uf = plan.variant == 3, splitk = plan.ways > 1;
   if (splitk) {
-    const int BN = (a.N % 160 == 0) ? 160 : 128, BM = (sk_cfg == 7 || sk_cfg == 10 || sk_cfg == 6 || sk_cfg == 9) ? 64 : (sk_cfg == 51 ? 256 : 128);
-    sk_ws = arena_alloc<float>(ctx, (int64_t)(ways - 1) * ceil_div(a.M, BM) * ceil_div(a.N, BN) * BM * BN);
+    sk_ws = arena_alloc<float>(ctx, plan.ws_floats);
     if (!sk_ws) TSD_FAIL(TSD_E_ALLOC, "gemm: split-K workspace exhausted");
   }
   if (!ctx->launch()) return TSD_OK;
+  ctx->gemm_last = plan;
   if (ctx->gemm_rec_on) {
     ctx->gemm_rec.resize(ctx->gemm_rec.size() + TSD_GD_COUNT);
-    gemm_describe(ctx, a, &ctx->gemm_rec[ctx->gemm_rec.size() - TSD_GD_COUNT]);
+    int64_t* d = &ctx->gemm_rec[ctx->gemm_rec.size() - TSD_GD_COUNT];
+    gemm_describe(ctx, a, d);
+    d[TSD_GD_CFG] = plan.cfg; d[TSD_GD_WAYS] = plan.ways;
   }
   ProfScope prof(ctx, a.conv ? KC_CONV : KC_GEMM, a.M, a.N, a.K, a.batch);
   GemmK k;
@@ -1696,12 +1450,11 @@ int launch_gemm(tsd_ctx* ctx, const GemmArgs& a) {
   k.A2 = a.A2; k.Wt1 = a.Wt1; k.lda2 = a.lda2; k.Cin1 = a.conv ? a.Cin1 : 0; k.Cin2 = a.conv ? a.Cin2 : 0; k.ldw1 = a.ldw1;
   k.epi = a.epi; k.tiles_n = 0; k.out_scale = a.out_scale;
   k.w_kts = a.w_kts ? (unsigned)a.w_kts : 128u;
-  if (a.w_kts && (a.ldw != 64 || a.w_kts < a.N * 128)) TSD_FAIL(TSD_E_ARG, "gemm: K-tile-major W needs ldw = 64 and a tile stride >= N * 128");
-  if (uf) { k.Wt = a.Wuf; k.ldw = 64; k.w_kts = (unsigned)a.N * 128u; k.K = 4 * a.Cin; }  // four K-tile-major copies [q][4 Cin / 64][N][64]
+  if (uf) { k.Wt = a.Wuf; k.ldw = 64; k.w_kts = (unsigned)a.N * 128u; k.K = plan.K; }  // four K-tile-major copies [q][4 Cin / 64][N][64]
   k.gn_part = a.gn_part; k.gn_cpg = a.gn_groups > 0 ? a.N / a.gn_groups : 1; k.gn_G = a.gn_groups; k.gn_hw = a.gn_rows_per_sample;
   k.gn_nslab = a.gn_nslab;
   k.vt = a.Vt; k.vt_sB = a.vt_sB; k.vt_n0 = a.vt_n0; k.vt_ld = a.vt_ld; k.vt_S = a.vt_S;
-  k.splitk = splitk ? ways : 1; k.sk_cfg = sk_cfg; k.sk_ws = sk_ws; k.sk_flags = nullptr; k.sk_epoch = 0;
+  k.splitk = plan.ways; k.sk_cfg = splitk ? plan.cfg : 0; k.sk_ws = sk_ws; k.sk_flags = nullptr; k.sk_epoch = 0;
   if (splitk) {
     if (!ctx->sk_flags) {
       HIP_TRY(hipMalloc((void**)&ctx->sk_flags, 4096 * sizeof(int)));
@@ -1711,7 +1464,7 @@ int launch_gemm(tsd_ctx* ctx, const GemmArgs& a) {
     if (++ctx->sk_epoch == 0) ctx->sk_epoch = 1;
     k.sk_epoch = (int)ctx->sk_epoch;
   }
-  return a.conv ? dispatch<true>(ctx, k, a.batch) : dispatch<false>(ctx, k, a.batch);
+  return a.conv ? launch_by_id<true>(ctx, k, a.batch, plan.cfg) : launch_by_id<false>(ctx, k, a.batch, plan.cfg);
 }
 
 // ---- what this board sustains: register-resident dense fp16 MFMA loop (no LDS, no memory) ------------------------------

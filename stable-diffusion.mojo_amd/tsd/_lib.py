@@ -163,6 +163,7 @@ def _declare(l):
         "tsd_debug_model_ups_fold": ([vp, i, vp], i),
         "tsd_debug_set_ups_fold": ([vp, i], i),
         "tsd_debug_gemm_run": ([vp, C.POINTER(i64), i, i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)], i),
+        "tsd_debug_gemm_plan": ([vp, C.POINTER(i64), i, i, C.POINTER(i64)], i),
         "tsd_debug_norm_run": ([vp, C.POINTER(i64), i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)], i),
         "tsd_debug_attn_run": ([vp, C.POINTER(i64), i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)], i),
         "tsd_debug_gn_path_counts": ([vp, C.POINTER(i64), i, i], i),

@@ -55,6 +55,11 @@ def _parse():
 
 GD, GO, GD_VERSION, EPI = _parse()
 COUNT = GD["COUNT"]
+GP, = replay.enums(replay.header(), {"TSD_GP_": "tsd_gemm_plan_field"})  # fields of tsd_debug_gemm_plan
+# tile configurations (csrc/gemm_tiles.h) by column family: 160-wide tiles, 128-wide tiles, the thin N <= 16 ones
+N160 = (0, 1, 5, 6, 7, 11, 45, 46, 47, 51, 54)
+N128 = (2, 3, 8, 9, 10, 13, 48, 49, 50, 53, 55)
+THIN = (4, 24)
 INPUTS = ("A0", "A1", "A2", "W", "WT1", "R", "BIAS", "ROWVEC")
 OUTPUTS = ("C", "VT", "GN")
 

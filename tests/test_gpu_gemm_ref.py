@@ -29,6 +29,15 @@ def run(ctx, d, ops, cfg=-1):
     return replay.run("tsd_debug_gemm_run", ctx, d, ops, G.GO, G.INPUTS, G.OUTPUTS, G.dtype_of, G.extents, extra=(cfg,))
 
 
+def planned(ctx, d, cfg=-1):
+    """(configuration, split-K slices) of the host plan for d on this context: tsd_debug_gemm_plan, no launch."""
+    d = np.ascontiguousarray(d, np.int64)
+    p = np.zeros(G.GP["COUNT"], np.int64)
+    rc = replay.lib().tsd_debug_gemm_plan(ctx.h, d.ctypes.data_as(_i64p), len(d), cfg, p.ctypes.data_as(_i64p))
+    assert rc == 0, f"cfg {cfg}: plan status {rc}: {replay.lib().tsd_last_error().decode()}"
+    return int(p[G.GP["CFG"]]), int(p[G.GP["WAYS"]])
+
+
 def verify(ctx, d, cfg=-1, seed=0, rows=None, twice=False):
     """Run d on seeded operands and hold it to the reference; returns info."""
     ops = G.make_operands(d, seed)
@@ -108,6 +117,7 @@ def test_production_launches_replay_within_the_fp64_bound(ctx, production):
     for i, d in enumerate(production):
         info = verify(ctx, d, -1, seed=100 + i, rows=G.sample_rows(d, 7 + i), twice=True)
         assert (int(info[0]), int(info[1])) == (int(d[G.GD["CFG"]]), int(d[G.GD["WAYS"]])), "replay chose another tile / split"
+        assert planned(ctx, d) == (int(info[0]), int(info[1])), "the plan is not what ran"
         cov[(int(info[0]), int(info[1]))] += 1
     assert replay.lib().tsd_debug_splitk_errors(ctx.h) == 0
     print("\nreplayed launches per (configuration, split-K ways):")
@@ -119,9 +129,7 @@ def test_production_launches_replay_within_the_fp64_bound(ctx, production):
 
 
 # ---- (b) configuration sweep ----------------------------------------------------------------------------------------------------
-N160 = (0, 1, 5, 6, 7, 11, 45, 46, 47, 51, 54)
-N128 = (2, 3, 8, 9, 10, 13, 48, 49, 50, 53, 55)
-THIN = (4, 24)
+N160, N128, THIN = G.N160, G.N128, G.THIN
 PROD_CONV = E["BIAS_N"] | E["RESIDUAL"]
 
 
@@ -189,7 +197,7 @@ def _sweep_cases():
 SWEEP = _sweep_cases()
 
 
-BNW = {**{c: 80 for c in N160}, **{c: 64 for c in N128}}  # wave-tile columns (cfg_wave_tile); thin tiles emit no statistics
+BNW = {**{c: 80 for c in N160}, **{c: 64 for c in N128}}  # wave-tile columns (FN * 16 of csrc/gemm_tiles.h); thin tiles emit no statistics
 
 
 def test_every_tile_configuration_matches_the_fp64_reference(ctx):
@@ -207,7 +215,8 @@ def test_every_tile_configuration_matches_the_fp64_reference(ctx):
                     continue
                 gn_ran.add(cfg)
             try:
-                verify(ctx, d, cfg, seed=cfg)
+                info = verify(ctx, d, cfg, seed=cfg)
+                assert planned(ctx, d, cfg) == (int(info[0]), int(info[1])), "the plan is not what ran"
             except AssertionError as e:
                 raise AssertionError(f"{name}: {e}") from None
             counts[cfg] += 1
