@@ -393,6 +393,44 @@ int tsd_session_decode(tsd_session* s); /* Decoder.forward on the current latent
 int tsd_session_download_latents(tsd_session* s, float* latents);
 int tsd_session_download_images(tsd_session* s, int rescale_0_255, float* images);
 
+/* ---- slot sessions (EXTENSION: the reference denoises one prompt from step 0 to the end, pipeline.mojo:86-124) ------------------------
+ * Continuous batching: each of the B samples of a session is a SLOT holding its own request - context, seed, guidance scale - and its
+ * own index into the session's timestep list.  One advance() runs ONE UNet forward over all samples and gives every active slot the
+ * sampler update of its own index; a slot that has finished is refilled by slot_start while the others keep going.  Each entry point
+ * stands in for the body of `pipeline.generate`'s loop (pipeline.mojo:86-124: time embedding, Diffusion.forward, the CFG combine :117-119,
+ * DDPMSampler.step), per sample.  All slots share the session's sampler, spacing and timestep list.  Noise is always the seeded noise
+ * above: streams 2 / 4 / 16 + i of the slot's seed.  A slot's latents are bit for bit those of a lockstep session of the same B running
+ * the same request in the same sample position (upload + set_seeds + seed_latents | add_noise_seeded + step start_index..n-1).
+ * Inpainting in slots is out of scope: set_inpaint* are refused in slot mode.
+ * A session that never calls slots_open enqueues exactly the launches, and computes the bits, it did before. */
+/* Enter slot mode, after set_sampler / set_schedule and in place of upload(): sizes the workspace and the hoisted buffers by upload()'s
+ * planning pass, zeroes the latents and the context, marks all B slots idle.  upload(), set_schedule and set_sampler leave slot mode.
+ * In slot mode step, add_noise*, set_seeds, seed_latents, set_inpaint*, decode, download_latents and download_images return
+ * TSD_E_STATE. */
+int tsd_session_slots_open(tsd_session* s);
+/* Put a request into slot b (idle, done or active: an active slot's request is replaced).  context [T,768]; uncond_context [T,768]
+ * (NULL only without CFG); latents [4,L,L] or NULL = stream 2 of `seed` (tsd_session_seed_latents' rule); with latents and
+ * noise_at_start != 0 they are noised to timesteps[start_index] with stream 4 of `seed` (tsd_session_add_noise_seeded's scalars and
+ * kernel, img2img).  The slot's next step is start_index; its DPM-Solver++(2M) history is dropped.  Synchronous.  Every refusal comes
+ * before the first copy and leaves all slots as they were: TSD_E_ARG for b or start_index out of range, a missing uncond_context on a
+ * CFG session, inf / NaN in a host tensor or in cfg_scale; TSD_E_STATE outside slot mode.  Other slots' buffers are never touched: with
+ * the step invariants hoisted, only this sample's context K / V^T are rebuilt, in place. */
+int tsd_session_slot_start(tsd_session* s, int b, const float* context, const float* uncond_context, const float* latents,
+                           int noise_at_start, uint64_t seed, int start_index, float cfg_scale);
+/* One tick, asynchronous like tsd_session_step: one forward over all samples, then every ACTIVE slot b takes the update of its index
+ * i_b with its own cfg_scale, its noise from stream 16 + i_b of its seed (where the sampler takes noise) and its own DPM-Solver++(2M)
+ * history; i_b grows by one, a slot that reaches tsd_session_num_steps becomes done and sets bit b of *finished_mask (may be NULL).
+ * Idle and done slots ride through the forward: their output is ignored, their latents and history are not written and they are not
+ * counted as non-finite.  The per-slot scalars travel as kernel arguments: no host-to-device copy, no allocation.  TSD_E_STATE with no
+ * active slot or outside slot mode; otherwise tsd_session_step's guards (a parameter change rebuilds the invariants of all samples). */
+int tsd_session_advance(tsd_session* s, uint32_t* finished_mask);
+/* *index = the slot's next schedule index (num_steps when done), *state = 0 idle, 1 active, 2 done; either may be NULL. */
+int tsd_session_slot_state(tsd_session* s, int b, int* index, int* state);
+/* One slot's latents [4,L,L] (synchronises).  TSD_E_STATE on an idle slot.  tsd_session_download_latents' finite check, on that slot's
+ * buffer only: inf / NaN there returns TSD_E_NONFINITE and latches the session until slots_open() or upload(). */
+int tsd_session_slot_download(tsd_session* s, int b, float* latents);
+int tsd_session_slots_active(tsd_session* s); /* number of active slots (0 outside slot mode); < 0 on a NULL session */
+
 /* ---- multi-GPU: RCCL over xGMI (one process per GPU) ----------------------------------- */
 /* unique_id: 128 bytes from tsd_dist_unique_id on rank 0, shared out-of-band (e.g. torch.distributed). */
 int tsd_dist_unique_id(void* id128);
@@ -422,6 +460,9 @@ int tsd_debug_xcd_round_robin(void);
  * entry points, tsd_ctx_synchronize and the session downloads return TSD_E_NONFINITE when the count is non-zero (and clear it).
  * This call reads the count without failing (reset != 0 clears it); < 0 on error.  Synchronises the context's stream. */
 int tsd_debug_nonfinite_count(tsd_ctx* ctx, int reset);
+/* Test infrastructure: the session's raw latent buffer [B,4,L,L] as it is on the device - in any mode, idle slots included, with no
+ * finite check and no effect on the session's state.  Synchronises. */
+int tsd_debug_session_latents(tsd_session* s, float* latents);
 /* A/B switch for the fused attention-block kernels of the 64x64 level (kernels_chain.hip): 0 = op-by-op graph, 1 = fused
  * (default; TSD_CHAIN=0 in the environment has the same effect).  Returns the previous setting. */
 int tsd_debug_set_fused_attention(tsd_ctx* ctx, int on);

@@ -172,6 +172,19 @@ struct tsd_session {
   // models of the context (bench.py's scaled "peaked" model copy); its code is still returned at the synchronisation point that sees it.
   bool poisoned = false;
   bool decoded = false;  // decode() has run since the last upload(): images are defined
+  // Slot mode (tsd_session_slots_open): every sample is a slot with its own request, schedule index and guidance scale; advance() moves
+  // all active slots by one step with one forward.  `uploaded` stays false in slot mode - the lockstep entry points refuse by name
+  // (SESSION_NOT_SLOTS) - and upload(), set_schedule and set_sampler leave it.  The index, not a timestep list, is the unit of state.
+  bool slots = false;
+  struct Slot {
+    int state = 0;            // 0 idle, 1 active, 2 done
+    int index = 0;            // next schedule index; num_steps when done
+    float cfg_scale = 7.5f;
+    uint64_t seed = 0;
+    bool hist_valid = false;  // `hist` of this sample holds the x0 of the slot's previous step (DPM-Solver++(2M))
+  } slot[16];
+  float* trows = nullptr;     // [Bu][tproj.N] fp32: row i_b of ttab per sample, gathered by every advance (own allocation, grown at slots_open)
+  size_t trows_cap = 0;
 };
 
 // inf / NaN scan of a downloaded tensor (exponent bits all ones); the buffers at this boundary are 0.5 - 25 MB
@@ -189,6 +202,13 @@ static bool host_all_finite(const float* p, size_t n) {
     if ((s)->poisoned)                                                                                                       \
       TSD_FAIL(TSD_E_NONFINITE, "session: inf / NaN was found in this session's latents or images (reported at an earlier " \
                "download); its state is unusable until upload() replaces it");                                              \
+  } while (0)
+
+#define SESSION_NOT_SLOTS(s, what)                                                                                           \
+  do {                                                                                                                       \
+    if ((s)->slots)                                                                                                          \
+      TSD_FAIL(TSD_E_STATE, "session: " what " moves the batch in lockstep and the session is in slot mode (slots_open); use the " \
+               "slot entry points, or upload() to leave slot mode");                                                        \
   } while (0)
 
 // alphas_cumprod (sampler.mojo:28-32) and the timestep list of the session's spacing with `start` entries dropped (sampler.cpp)
@@ -233,13 +253,14 @@ extern "C" int tsd_debug_set_session_hoist(tsd_ctx* ctx, int on) {
 }
 extern "C" int tsd_debug_session_hoist_info(tsd_session* s, int64_t* info) {
   NOTNULL(s); NOTNULL(info);
-  info[0] = s->uploaded && s->hoist; info[1] = (int64_t)(uintptr_t)s->ttab; info[2] = (int64_t)(uintptr_t)s->kc_all;
+  info[0] = (s->uploaded || s->slots) && s->hoist; info[1] = (int64_t)(uintptr_t)s->ttab; info[2] = (int64_t)(uintptr_t)s->kc_all;
   info[3] = (int64_t)(uintptr_t)s->vtc_all; info[4] = (int64_t)(s->kv_cap + s->ttab_cap); info[5] = s->inv_builds;
   return TSD_OK;
 }
 
 static void schedule_changed(tsd_session* s) {
   s->uploaded = false; s->has_noise = false;
+  s->slots = false;
   s->inpaint = false;
   s->seeded = false;
   s->hist_valid_for = -1;
@@ -288,6 +309,7 @@ extern "C" int tsd_session_destroy(tsd_session* s) {
   if (s->noise) hipFree(s->noise);
   if (s->kv) hipFree(s->kv);
   if (s->ttab) hipFree(s->ttab);
+  if (s->trows) hipFree(s->trows);
   delete s;
   return TSD_OK;
 }
@@ -319,39 +341,11 @@ extern "C" int tsd_session_timestep(tsd_session* s, int i) {
   return s->timesteps[i];
 }
 
-extern "C" int tsd_session_upload(tsd_session* s, const float* latents, const float* context,
-                                  const float* uncond_context, const float* noise, float cfg_scale) {
-  NOTNULL(s); NOTNULL(latents); NOTNULL(context);
-  if (s->cfg && !uncond_context) TSD_FAIL(TSD_E_ARG, "session: CFG session needs uncond_context");
+// What upload() and slots_open() share once the session's buffers hold their data: size the workspace once for this session's shapes (no
+// allocation inside the timed loop), size and fill the step-invariant buffers, and mark the session ready.
+static int session_prepare(tsd_session* s) {
   tsd_ctx* ctx = s->ctx;
-  HIP_TRY(hipSetDevice(ctx->device));
   const int B = s->B, L = s->L, T = s->T, Tp = s->Tp;
-  const size_t nl = (size_t)B * 4 * L * L;
-  s->cfg_scale = cfg_scale;
-  HIP_TRY(hipMemcpyAsync(s->latents, latents, nl * 4, hipMemcpyHostToDevice, ctx->stream));
-  // context -> fp16 [Bu][Tp][768], zero padded rows (cond first, then uncond: pipeline.mojo:49)
-  TSD_TRY(ctx_reserve_staging(ctx, (size_t)B * T * 768 * 4));
-  for (int part = 0; part < (s->cfg ? 2 : 1); part++) {
-    const float* src = part == 0 ? context : uncond_context;
-    HIP_TRY(hipMemcpyAsync(ctx->staging, src, (size_t)B * T * 768 * 4, hipMemcpyHostToDevice, ctx->stream));
-    for (int b = 0; b < B; b++)
-      TSD_TRY(launch_f32_to_f16_rows(ctx, (const float*)ctx->staging + (size_t)b * T * 768, T, 768,
-                                     s->ctx16 + ((size_t)part * B + b) * Tp * 768, 768, Tp));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-  }
-  s->has_noise = noise != nullptr;
-  if (noise) {
-    const size_t bytes = s->timesteps.size() * nl * 4;
-    if (bytes > s->noise_cap) {
-      if (s->noise) HIP_TRY(hipFree(s->noise));
-      s->noise = nullptr; s->noise_cap = 0;
-      hipError_t e = hipMalloc((void**)&s->noise, bytes);
-      if (e != hipSuccess) TSD_FAIL(TSD_E_ALLOC, "session: noise hipMalloc(%zu) failed", bytes);
-      s->noise_cap = bytes;
-    }
-    HIP_TRY(hipMemcpyAsync(s->noise, noise, bytes, hipMemcpyHostToDevice, ctx->stream));
-  }
-  HIP_TRY(hipStreamSynchronize(ctx->stream));
   // size the workspace once for this session's shapes (no allocation inside the timed loop)
   TSD_TRY(model_check_ready(s->unet));
   if (s->dec) TSD_TRY(model_check_ready(s->dec));
@@ -407,6 +401,43 @@ extern "C" int tsd_session_upload(tsd_session* s, const float* latents, const fl
   return TSD_OK;
 }
 
+extern "C" int tsd_session_upload(tsd_session* s, const float* latents, const float* context,
+                                  const float* uncond_context, const float* noise, float cfg_scale) {
+  NOTNULL(s); NOTNULL(latents); NOTNULL(context);
+  if (s->cfg && !uncond_context) TSD_FAIL(TSD_E_ARG, "session: CFG session needs uncond_context");
+  tsd_ctx* ctx = s->ctx;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const int B = s->B, L = s->L, T = s->T, Tp = s->Tp;
+  const size_t nl = (size_t)B * 4 * L * L;
+  s->cfg_scale = cfg_scale;
+  s->slots = false;  // upload() leaves slot mode
+  HIP_TRY(hipMemcpyAsync(s->latents, latents, nl * 4, hipMemcpyHostToDevice, ctx->stream));
+  // context -> fp16 [Bu][Tp][768], zero padded rows (cond first, then uncond: pipeline.mojo:49)
+  TSD_TRY(ctx_reserve_staging(ctx, (size_t)B * T * 768 * 4));
+  for (int part = 0; part < (s->cfg ? 2 : 1); part++) {
+    const float* src = part == 0 ? context : uncond_context;
+    HIP_TRY(hipMemcpyAsync(ctx->staging, src, (size_t)B * T * 768 * 4, hipMemcpyHostToDevice, ctx->stream));
+    for (int b = 0; b < B; b++)
+      TSD_TRY(launch_f32_to_f16_rows(ctx, (const float*)ctx->staging + (size_t)b * T * 768, T, 768,
+                                     s->ctx16 + ((size_t)part * B + b) * Tp * 768, 768, Tp));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+  }
+  s->has_noise = noise != nullptr;
+  if (noise) {
+    const size_t bytes = s->timesteps.size() * nl * 4;
+    if (bytes > s->noise_cap) {
+      if (s->noise) HIP_TRY(hipFree(s->noise));
+      s->noise = nullptr; s->noise_cap = 0;
+      hipError_t e = hipMalloc((void**)&s->noise, bytes);
+      if (e != hipSuccess) TSD_FAIL(TSD_E_ALLOC, "session: noise hipMalloc(%zu) failed", bytes);
+      s->noise_cap = bytes;
+    }
+    HIP_TRY(hipMemcpyAsync(s->noise, noise, bytes, hipMemcpyHostToDevice, ctx->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return session_prepare(s);
+}
+
 // Streams of the seeded noise, per sample b with seeds[b]: 2 the initial latents, 4 the add_noise / inpainting noise, 16 + i the noise of
 // schedule step i; the counter is the element's index inside its sample, (c*L + y)*L + x.  Nothing depends on B or on the sample's slot.
 enum { NOISE_STREAM_LATENTS = 2, NOISE_STREAM_ADD = 4, NOISE_STREAM_STEP0 = 16 };
@@ -447,6 +478,7 @@ static int session_inpaint_blend(tsd_session* s, int i) {
 
 extern "C" int tsd_session_step(tsd_session* s, int i) {
   NOTNULL(s);
+  SESSION_NOT_SLOTS(s, "step()");
   if (!s->uploaded) TSD_FAIL(TSD_E_STATE, "session: upload() before step()");
   SESSION_NOT_POISONED(s);
   if (s->opt_gen != s->ctx->opt.gen) TSD_FAIL(TSD_E_STATE, "session: a tsd_debug_set_* call changed this context's options after upload() sized the workspace; upload() again");
@@ -511,6 +543,7 @@ extern "C" int tsd_session_step(tsd_session* s, int i) {
 
 extern "C" int tsd_session_add_noise(tsd_session* s, int i, const float* noise) {
   NOTNULL(s); NOTNULL(noise);
+  SESSION_NOT_SLOTS(s, "add_noise()");
   if (i < 0 || i >= (int)s->timesteps.size()) TSD_FAIL(TSD_E_ARG, "session: step %d out of range", i);
   tsd_ctx* ctx = s->ctx;
   const size_t nl = (size_t)s->B * 4 * s->L * s->L;
@@ -527,6 +560,7 @@ extern "C" int tsd_session_add_noise(tsd_session* s, int i, const float* noise) 
 // seeds: one per sample, or NULL = off.  One source of noise per upload(): refused when the upload carried a noise tensor.
 extern "C" int tsd_session_set_seeds(tsd_session* s, const uint64_t* seeds) {
   NOTNULL(s);
+  SESSION_NOT_SLOTS(s, "set_seeds()");
   if (!s->uploaded) TSD_FAIL(TSD_E_STATE, "session: upload() before set_seeds() (the seeds belong to one upload)");
   if (seeds && s->has_noise) TSD_FAIL(TSD_E_STATE, "session: this upload() carried a noise tensor; one source of noise per upload");
   s->seeded = seeds != nullptr;
@@ -540,6 +574,7 @@ extern "C" int tsd_session_seeds_active(tsd_session* s) { return s ? (s->uploade
 // the latents become stream 2 of each sample's seed: what a txt2img caller would have uploaded, drawn on the device.  Asynchronous.
 extern "C" int tsd_session_seed_latents(tsd_session* s) {
   NOTNULL(s);
+  SESSION_NOT_SLOTS(s, "seed_latents()");
   if (!s->uploaded || !s->seeded) TSD_FAIL(TSD_E_STATE, "session: upload() and set_seeds() before seed_latents()");
   HIP_TRY(hipSetDevice(s->ctx->device));
   const int64_t chw = (int64_t)4 * s->L * s->L;
@@ -551,6 +586,7 @@ extern "C" int tsd_session_seed_latents(tsd_session* s) {
 // add_noise at index i with stream 4 of each sample's seed instead of a host tensor: the same scalars and the same kernel
 extern "C" int tsd_session_add_noise_seeded(tsd_session* s, int i) {
   NOTNULL(s);
+  SESSION_NOT_SLOTS(s, "add_noise_seeded()");
   if (!s->uploaded || !s->seeded) TSD_FAIL(TSD_E_STATE, "session: upload() and set_seeds() before add_noise_seeded()");
   if (i < 0 || i >= (int)s->timesteps.size()) TSD_FAIL(TSD_E_ARG, "session: step %d out of range", i);
   tsd_ctx* ctx = s->ctx;
@@ -568,6 +604,7 @@ extern "C" int tsd_session_add_noise_seeded(tsd_session* s, int i) {
 
 // set_inpaint and set_inpaint_seeded: `seeded` fills ip_noise with stream 4 of each sample's seed on the device instead of copying `noise`
 static int session_set_inpaint(tsd_session* s, const float* mask, const float* known, const float* noise, bool seeded) {
+  SESSION_NOT_SLOTS(s, "set_inpaint()");
   if (!s->uploaded) TSD_FAIL(TSD_E_STATE, "session: upload() before set_inpaint() (inpainting belongs to one upload)");
   if (seeded && mask && !s->seeded) TSD_FAIL(TSD_E_STATE, "session: set_seeds() before set_inpaint_seeded()");
   tsd_ctx* ctx = s->ctx;
@@ -604,6 +641,7 @@ extern "C" int tsd_session_inpaint_active(tsd_session* s) { return s ? (s->uploa
 
 extern "C" int tsd_session_decode(tsd_session* s) {
   NOTNULL(s);
+  SESSION_NOT_SLOTS(s, "decode()");
   if (!s->dec) TSD_FAIL(TSD_E_STATE, "session: created without a decoder");
   if (!s->uploaded) TSD_FAIL(TSD_E_STATE, "session: upload() before decode()");
   SESSION_NOT_POISONED(s);
@@ -617,6 +655,7 @@ extern "C" int tsd_session_decode(tsd_session* s) {
 
 extern "C" int tsd_session_download_latents(tsd_session* s, float* latents) {
   NOTNULL(s); NOTNULL(latents);
+  SESSION_NOT_SLOTS(s, "download_latents()");
   if (!s->uploaded) TSD_FAIL(TSD_E_STATE, "session: upload() before download_latents() (the state is not defined yet)");
   const size_t n = (size_t)s->B * 4 * s->L * s->L;
   HIP_TRY(hipMemcpyAsync(latents, s->latents, n * 4, hipMemcpyDeviceToHost, s->ctx->stream));
@@ -632,6 +671,7 @@ extern "C" int tsd_session_download_latents(tsd_session* s, float* latents) {
 
 extern "C" int tsd_session_download_images(tsd_session* s, int rescale_0_255, float* images) {
   NOTNULL(s); NOTNULL(images);
+  SESSION_NOT_SLOTS(s, "download_images()");
   if (!s->dec) TSD_FAIL(TSD_E_STATE, "session: created without a decoder");
   if (!s->decoded) TSD_FAIL(TSD_E_STATE, "session: decode() before download_images() (no image has been computed since upload())");
   tsd_ctx* ctx = s->ctx;
@@ -649,6 +689,232 @@ extern "C" int tsd_session_download_images(tsd_session* s, int rescale_0_255, fl
   SESSION_NOT_POISONED(s);
   // a non-finite IMAGE is reported, it does not poison latents that may be fine (decode again after the cause is removed)
   if (!host_all_finite(images, (size_t)n)) TSD_FAIL(TSD_E_NONFINITE, "session: inf / NaN in the decoded images");
+  return TSD_OK;
+}
+
+// ---- slot sessions: the body of `pipeline.generate`'s loop (pipeline.mojo:86-124), per sample ---------------------------------------
+// Every sample of the session is a slot with its own request (context, seed, guidance scale) and its own index into the session's
+// timestep list.  advance() runs ONE forward over all Bu samples and one update launch whose per-sample table gives each active slot
+// the step of its own index; a finished slot is refilled by slot_start while the others keep going.  What the lockstep step() passes
+// as scalars for the whole batch is computed here per slot by the same host code (slot_entry), and applied by the same per-element
+// functions (update_element.h): a slot's latents are bit for bit those of a lockstep session of the same batch shape running its request.
+#define SESSION_IN_SLOTS(s)                                                                                   \
+  do {                                                                                                        \
+    if (!(s)->slots) TSD_FAIL(TSD_E_STATE, "session: slots_open() first (the session is not in slot mode)"); \
+  } while (0)
+
+extern "C" int tsd_session_slots_open(tsd_session* s) {
+  NOTNULL(s);
+  tsd_ctx* ctx = s->ctx;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const int B = s->B, L = s->L, Bu = s->cfg ? 2 * B : B;
+  s->slots = false;
+  s->has_noise = false;
+  // idle slots ride through every forward: zero latents and a zero context keep them finite
+  HIP_TRY(hipMemsetAsync(s->latents, 0, (size_t)B * 4 * L * L * 4, ctx->stream));
+  HIP_TRY(hipMemsetAsync(s->ctx16, 0, (size_t)Bu * s->Tp * 768 * 2, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (ctx->opt.session_hoist) {  // the per-sample time rows of an advance: sized by the session's shape alone
+    const size_t bytes = (size_t)Bu * s->unet->unet.tproj.N * 4;
+    if (bytes > s->trows_cap) {
+      if (s->trows) HIP_TRY(hipFree(s->trows));
+      s->trows = nullptr; s->trows_cap = 0;
+      if (hipMalloc((void**)&s->trows, bytes) != hipSuccess) TSD_FAIL(TSD_E_ALLOC, "session: time rows hipMalloc(%zu) failed", bytes);
+      s->trows_cap = bytes;
+    }
+  }
+  TSD_TRY(session_prepare(s));  // the planning pass and the hoist buffers of upload(); K / V^T of the zero context, the whole time table
+  s->uploaded = false;          // the lockstep entry points stay closed
+  for (int b = 0; b < 16; b++) s->slot[b] = tsd_session::Slot();
+  s->slots = true;
+  return TSD_OK;
+}
+
+extern "C" int tsd_session_slot_start(tsd_session* s, int b, const float* context, const float* uncond_context, const float* latents,
+                                      int noise_at_start, uint64_t seed, int start_index, float cfg_scale) {
+  NOTNULL(s); NOTNULL(context);
+  SESSION_IN_SLOTS(s);
+  SESSION_NOT_POISONED(s);
+  tsd_ctx* ctx = s->ctx;
+  const int B = s->B, L = s->L, T = s->T, Tp = s->Tp;
+  const size_t chw = (size_t)4 * L * L, nc = (size_t)T * 768;
+  // every refusal comes before the first copy: a refused call leaves the slot, and everyone else's, as it was
+  if (b < 0 || b >= B) TSD_FAIL(TSD_E_ARG, "session: slot %d out of range (0..%d)", b, B - 1);
+  if (start_index < 0 || start_index >= (int)s->timesteps.size())
+    TSD_FAIL(TSD_E_ARG, "session: start index %d out of range (0..%d)", start_index, (int)s->timesteps.size() - 1);
+  if (s->cfg && !uncond_context) TSD_FAIL(TSD_E_ARG, "session: a slot of a CFG session needs uncond_context");
+  if (!host_all_finite(&cfg_scale, 1)) TSD_FAIL(TSD_E_ARG, "session: cfg_scale of slot_start() is not finite");
+  if (!host_all_finite(context, nc)) TSD_FAIL(TSD_E_ARG, "session: inf / NaN in the context of slot_start()");
+  if (s->cfg && !host_all_finite(uncond_context, nc)) TSD_FAIL(TSD_E_ARG, "session: inf / NaN in the uncond_context of slot_start()");
+  if (latents && !host_all_finite(latents, chw)) TSD_FAIL(TSD_E_ARG, "session: inf / NaN in the latents of slot_start()");
+  HIP_TRY(hipSetDevice(ctx->device));
+  TSD_TRY(ctx_reserve_staging(ctx, std::max(nc, chw) * 4));
+  tsd_session::Slot& sl = s->slot[b];
+  sl.state = 0;  // until the request is in place
+  // context rows b and B + b -> fp16 [Tp][768], zero padded (upload()'s conversion, one sample)
+  for (int part = 0; part < (s->cfg ? 2 : 1); part++) {
+    const size_t row = (size_t)part * B + b;
+    HIP_TRY(hipMemcpyAsync(ctx->staging, part == 0 ? context : uncond_context, nc * 4, hipMemcpyHostToDevice, ctx->stream));
+    TSD_TRY(launch_f32_to_f16_rows(ctx, (const float*)ctx->staging, T, 768, s->ctx16 + row * Tp * 768, 768, Tp));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+  }
+  // Under the hoist only this sample's K / V^T change: the forward's own projection at batch 1, into the sample's region.  The GEMM's
+  // summation tree keys on the layer, never on the batch (gemm_plan.cpp), so these are the bits of the all-sample build.  After a
+  // parameter change the next advance() rebuilds every sample from ctx16, this one included.
+  if (s->hoist && s->model_gen == s->unet->gen) {
+    const int CK = s->unet->unet.kproj_all.N;
+    for (int part = 0; part < (s->cfg ? 2 : 1); part++) {
+      const size_t row = (size_t)part * B + b;
+      ctx->arena.top = 0;
+      TSD_TRY(g_unet_ctx_kv(s->unet, s->ctx16 + row * Tp * 768, Tp, 1, s->kc_all + row * Tp * CK, s->vtc_all + row * CK * Tp));
+    }
+    ctx->arena.top = 0;
+  }
+  float* lat = s->latents + (size_t)b * chw;
+  NormalBases nb = {};
+  if (!latents) {  // seed_latents()' rule for one sample: stream 2 of the seed
+    nb.base[0] = counter_rng_base(seed, NOISE_STREAM_LATENTS);
+    TSD_TRY(launch_fill_normal(ctx, lat, (int64_t)chw, (int64_t)chw, nb, 0));
+  } else {
+    HIP_TRY(hipMemcpyAsync(lat, latents, chw * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (noise_at_start) {  // add_noise_seeded(start_index) on this slot: stream 4 of the seed, the same scalars, the same kernel
+      nb.base[0] = counter_rng_base(seed, NOISE_STREAM_ADD);
+      TSD_TRY(launch_fill_normal(ctx, (float*)ctx->staging, (int64_t)chw, (int64_t)chw, nb, 0));
+      const float a = s->alphas_cumprod[s->timesteps[start_index]];
+      TSD_TRY(launch_add_noise(ctx, lat, (const float*)ctx->staging, (int64_t)chw, sqrtf(a), sqrtf(1.f - a)));
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(ctx->stream));  // the host tensors and the staging buffer are free again on return
+  sl.index = start_index; sl.cfg_scale = cfg_scale; sl.seed = seed;
+  sl.hist_valid = false;
+  sl.state = 1;
+  return TSD_OK;
+}
+
+// Entry b of the update table for an active slot at index i: the scalars tsd_session_step computes for step i, by the same code.
+static int slot_entry(const tsd_session* s, const tsd_session::Slot& sl, SlotEntry* e, uint64_t* base, bool* keeps_hist) {
+  const int i = sl.index, t = s->timesteps[i];
+  e->cfg_scale = sl.cfg_scale;
+  e->flags = 0;
+  *base = counter_rng_base(sl.seed, NOISE_STREAM_STEP0 + (uint64_t)i);
+  *keeps_hist = false;
+  if (s->sampler == TSD_SAMPLER_DDPM) {
+    const int prev = s->spacing == TSD_SPACING_LEADING ? t - s->n_train / s->n_infer
+                                                       : (i + 1 < (int)s->timesteps.size() ? s->timesteps[i + 1] : -1);
+    e->mode = SLOT_DDPM;
+    ddpm_coeffs(s, t, prev, &e->c[0], &e->c[1], &e->c[2], &e->c[3], &e->c[4]);
+    e->c[5] = 0.f;
+    if (t > 0) e->flags |= SLOT_NOISE;
+    return TSD_OK;
+  }
+  const bool multistep = s->sampler == TSD_SAMPLER_DPMPP_2M, have_hist = multistep && sl.hist_valid;
+  double cd[8];
+  TSD_TRY(sampler_coeffs(s->sampler, s->eta, s->alphas_cumprod, s->timesteps, i, have_hist ? 1 : 0, cd));
+  e->mode = SLOT_LMS;
+  for (int k = 0; k < 6; k++) e->c[k] = (float)cd[2 + k];
+  if (have_hist) e->flags |= SLOT_HIST_IN;
+  if (multistep) e->flags |= SLOT_HIST_OUT;
+  if (!multistep && e->c[5] != 0.f) e->flags |= SLOT_NOISE;
+  *keeps_hist = multistep;
+  return TSD_OK;
+}
+
+extern "C" int tsd_session_advance(tsd_session* s, uint32_t* finished_mask) {
+  NOTNULL(s);
+  SESSION_IN_SLOTS(s);
+  SESSION_NOT_POISONED(s);
+  if (s->opt_gen != s->ctx->opt.gen) TSD_FAIL(TSD_E_STATE, "session: a tsd_debug_set_* call changed this context's options after slots_open() sized the workspace; slots_open() again");
+  tsd_ctx* ctx = s->ctx;
+  const int B = s->B, L = s->L, Bu = s->cfg ? 2 * B : B, n = (int)s->timesteps.size();
+  const size_t nl = (size_t)B * 4 * L * L;
+  int active = 0;
+  for (int b = 0; b < B; b++) active += s->slot[b].state == 1;
+  if (!active) TSD_FAIL(TSD_E_STATE, "session: advance() with no active slot");
+  if (s->model_gen != s->unet->gen) {  // parameters were set since the last build: the derived weights, then the invariants of all samples
+    TSD_TRY(model_check_ready(s->unet));
+    if (s->hoist) TSD_TRY(session_build_invariants(s));
+    s->model_gen = s->unet->gen;
+  }
+  // the update table, built before anything is enqueued: the per-slot scalars travel as kernel arguments
+  SlotTable tab = {};
+  bool keeps_hist[16] = {};
+  for (int b = 0; b < B; b++)
+    if (s->slot[b].state == 1) TSD_TRY(slot_entry(s, s->slot[b], &tab.e[b], &tab.bases.base[b], &keeps_hist[b]));
+  // per-sample time rows (cond and uncond halves alike); an idle or finished slot reads entry 0
+  UNetPre pre;
+  if (s->hoist) {
+    SlotRows rows = {};
+    for (int b = 0; b < Bu; b++) rows.row[b] = s->slot[b % B].state == 1 ? s->slot[b % B].index : 0;
+    const int N = s->unet->unet.tproj.N;
+    TSD_TRY(launch_slot_time_rows(ctx, s->ttab, N, rows, Bu, s->trows));
+    pre.tvec = s->trows; pre.tld = N; pre.kc_all = s->kc_all; pre.vtc_all = s->vtc_all;
+  } else {
+    SlotTimes ts = {};
+    for (int b = 0; b < Bu; b++) ts.t[b] = (float)s->timesteps[s->slot[b % B].state == 1 ? s->slot[b % B].index : 0];
+    TSD_TRY(launch_slot_timesteps(ctx, ts, Bu, s->tdev));
+    TSD_TRY(launch_time_embedding(ctx, s->tdev, 0.f, Bu, s->temb));
+  }
+  const float* lat_in = s->latents;
+  if (s->cfg) {
+    HIP_TRY(hipMemcpyAsync(s->lat2, s->latents, nl * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(s->lat2 + nl, s->latents, nl * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    lat_in = s->lat2;
+  }
+  ctx->arena.top = 0;
+  const bool eps_nhwc = s->unet->unet.final_conv.Opad == 4;
+  TSD_TRY(g_unet_forward(s->unet, lat_in, s->ctx16, s->T, s->Tp, s->temb, Bu, L, s->eps, eps_nhwc, s->hoist ? &pre : nullptr));
+  ctx->arena.top = 0;
+  TSD_TRY(launch_slot_update(ctx, s->latents, s->eps, s->cfg ? s->eps + nl : nullptr, s->hist, tab, B, (int64_t)4 * L * L,
+                             eps_nhwc ? L * L : 0));
+  uint32_t done = 0;
+  for (int b = 0; b < B; b++) {
+    tsd_session::Slot& sl = s->slot[b];
+    if (sl.state != 1) continue;
+    sl.hist_valid = keeps_hist[b];
+    if (++sl.index >= n) { sl.state = 2; done |= 1u << b; }
+  }
+  if (finished_mask) *finished_mask = done;
+  return TSD_OK;
+}
+
+extern "C" int tsd_session_slot_state(tsd_session* s, int b, int* index, int* state) {
+  NOTNULL(s);
+  SESSION_IN_SLOTS(s);
+  if (b < 0 || b >= s->B) TSD_FAIL(TSD_E_ARG, "session: slot %d out of range (0..%d)", b, s->B - 1);
+  if (index) *index = s->slot[b].index;
+  if (state) *state = s->slot[b].state;
+  return TSD_OK;
+}
+
+extern "C" int tsd_session_slot_download(tsd_session* s, int b, float* latents) {
+  NOTNULL(s); NOTNULL(latents);
+  SESSION_IN_SLOTS(s);
+  if (b < 0 || b >= s->B) TSD_FAIL(TSD_E_ARG, "session: slot %d out of range (0..%d)", b, s->B - 1);
+  if (s->slot[b].state == 0) TSD_FAIL(TSD_E_STATE, "session: slot %d is idle (no request has defined its latents)", b);
+  const size_t chw = (size_t)4 * s->L * s->L;
+  HIP_TRY(hipMemcpyAsync(latents, s->latents + (size_t)b * chw, chw * 4, hipMemcpyDeviceToHost, s->ctx->stream));
+  HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+  const int r = ctx_check_status(s->ctx);
+  if (!host_all_finite(latents, chw)) s->poisoned = true;  // download_latents()' check, on this slot's buffer alone
+  if (r != TSD_OK) return r;
+  SESSION_NOT_POISONED(s);
+  return TSD_OK;
+}
+
+extern "C" int tsd_session_slots_active(tsd_session* s) {
+  if (!s) return TSD_E_ARG;
+  int n = 0;
+  if (s->slots)
+    for (int b = 0; b < s->B; b++) n += s->slot[b].state == 1;
+  return n;
+}
+
+// the raw latent buffer [B,4,L,L], whatever the mode and the slot states, unchecked: lets a test see that an idle slot is never written
+extern "C" int tsd_debug_session_latents(tsd_session* s, float* latents) {
+  NOTNULL(s); NOTNULL(latents);
+  HIP_TRY(hipSetDevice(s->ctx->device));
+  HIP_TRY(hipMemcpyAsync(latents, s->latents, (size_t)s->B * 4 * s->L * s->L * 4, hipMemcpyDeviceToHost, s->ctx->stream));
+  HIP_TRY(hipStreamSynchronize(s->ctx->stream));
   return TSD_OK;
 }
 

@@ -402,6 +402,38 @@ int launch_inpaint_blend(tsd_ctx* ctx, const float* x, const float* mask, const 
                          float a_prev, float s_prev, float* x_out);
 // pixel mask [B][8L][8L] -> latent mask [B][L][L] by 8x8 blocks; mode is a tsd_mask_mode
 int launch_latent_mask(tsd_ctx* ctx, const float* mask_px, int B, int L, int mode, float* mask_lat);
+// ---- slot sessions (kernels_slots.hip): every sample of the batch at its own schedule index ------------------------------------
+// One by-value table serves the whole batch: entry b holds what launch_ddpm_step_seeded / launch_sampler_step(_seeded) would be given for
+// sample b alone.  c[]: SLOT_DDPM { sqrt(abar), sqrt(1 - abar), c_x0, c_xt, sigma } (ddpm_coeffs), SLOT_LMS the SamplerCoeffs in field order.
+// The noise bases sit beside the entries as the NormalBases the element functions index by sample.  40 * 16 + 128 = 768 bytes of kernel
+// arguments, read-only, entry b through scalar loads (b is the block's y index).
+enum { SLOT_SKIP = 0, SLOT_DDPM = 1, SLOT_LMS = 2 };               // SlotEntry::mode; SKIP: the sample is not read, written or counted
+enum { SLOT_HIST_IN = 1, SLOT_HIST_OUT = 2, SLOT_NOISE = 4 };      // SlotEntry::flags
+struct SlotEntry {
+  int mode, flags;
+  float cfg_scale;
+  float c[6];
+  int pad_;
+};
+struct SlotTable {
+  SlotEntry e[16];
+  NormalBases bases;  // stream 16 + i_b of the slot's seed (read under SLOT_NOISE only)
+};
+// x [B][4][hw] CHW in place, hist [B][4][hw] in place (read under SLOT_HIST_IN, written under SLOT_HIST_OUT), eps / eps_uncond as in
+// launch_ddpm_step (eps_hw > 0: [B][eps_hw][4]); chw = 4 * hw elements per sample
+int launch_slot_update(tsd_ctx* ctx, float* x, const float* eps, const float* eps_uncond, float* hist, const SlotTable& tab, int B,
+                       int64_t chw, int eps_hw);
+// rows of the hoisted time table for samples at different schedule indices: out[b][0..N) = ttab[row[b]][0..N), b < Bu <= 16
+struct SlotRows {
+  int row[16];
+};
+int launch_slot_time_rows(tsd_ctx* ctx, const float* ttab, int N, const SlotRows& rows, int Bu, float* out);
+// the same without the table: tdev[b] = t[b], the per-sample timesteps launch_time_embedding reads
+struct SlotTimes {
+  float t[16];
+};
+int launch_slot_timesteps(tsd_ctx* ctx, const SlotTimes& t, int Bu, float* tdev);
+
 // alphas_cumprod of the scaled-linear beta schedule (sampler.mojo:28-32), fp32 like the reference's Tensor
 void sampler_alphas_cumprod(int n_train, std::vector<float>& out);
 // timestep list of `spacing` (tsd_timestep_spacing) with the first `start_step` entries dropped; TSD_E_ARG on a bad argument

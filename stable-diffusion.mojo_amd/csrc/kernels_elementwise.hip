@@ -4,6 +4,7 @@
 #include <atomic>
 
 #include "common.h"
+#include "update_element.h"
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef _Float16 h4 __attribute__((ext_vector_type(4)));
@@ -685,37 +686,7 @@ int launch_pack_bias(tsd_ctx* ctx, const float* src, int N, float* dst, int Npad
   return TSD_OK;
 }
 
-// ---- DDPM update + CFG combine (sampler.mojo:75-109, pipeline.mojo:117-119; App.D K9) ------------
-// eps_hw > 0: eps / eps_u are the UNet output convolution's own layout [B][eps_hw][4] (x and noise stay CHW [B][4][eps_hw])
-// One element of the update.  SEEDED: the noise is drawn where the other flavour reads noise[i] - normal_counter(bases.base[b], j) for element j of
-// sample b (chw elements per sample, counter_rng.h) - and is always added; without it the instantiation is the kernel as it always was.
-template <bool SEEDED>
-__device__ __forceinline__ int ddpm_step_element(int64_t i, float* __restrict__ x, const float* __restrict__ eps,
-                                                 const float* __restrict__ eps_u, float cfg_scale, const float* __restrict__ noise,
-                                                 const NormalBases& bases, int64_t chw, float sa, float sb, float c_x0, float c_xt,
-                                                 float sigma, int eps_hw) {
-  int64_t ie = i;
-  if (eps_hw > 0) {
-    const int64_t bc = i / eps_hw, pix = i - bc * eps_hw, b = bc >> 2;
-    ie = (b * eps_hw + pix) * 4 + (bc & 3);
-  }
-  float e = eps[ie];
-  if (eps_u) {
-    const float u = eps_u[ie];
-    e = (e - u) * cfg_scale + u;
-  }
-  const float xv = x[i];
-  const float x0 = (xv - e * sb) / sa;
-  float o = x0 * c_x0 + xv * c_xt;
-  if constexpr (SEEDED) {
-    const int64_t b = i / chw;
-    o += normal_counter(bases.base[b], (uint64_t)(i - b * chw)) * sigma;
-  } else {
-    if (noise) o += noise[i] * sigma;
-  }
-  x[i] = o;
-  return nonfinite_f(o);  // a non-finite UNet output (fp16 overflow upstream) lands here every step
-}
+// ---- DDPM update + CFG combine (sampler.mojo:75-109, pipeline.mojo:117-119; App.D K9): ddpm_step_element, update_element.h ------------
 __global__ void k_ddpm_step(float* __restrict__ x, const float* __restrict__ eps, const float* __restrict__ eps_u,
                             float cfg_scale, const float* __restrict__ noise, int64_t n, float sa, float sb,
                             float c_x0, float c_xt, float sigma, int eps_hw, int* __restrict__ nonfinite) {

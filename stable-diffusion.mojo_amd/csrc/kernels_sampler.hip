@@ -9,61 +9,11 @@
 #include <algorithm>
 
 #include "common.h"
+#include "update_element.h"
 
 #define GRID1D(n, bs) dim3((unsigned)std::min<int64_t>(((n) + (bs)-1) / (bs), 1 << 20))
 
-// Every product and sum below is ONE fp32 rounding, in this order, whatever the eps layout and whichever optional pointers are set
-// (contraction into fma is off: an absent term is skipped, the others round as before).  Roundings on the longest path
-//   x_out: e (sub, mul, add) -> * c_e -> + c_x x -> + c_h h -> + c_n z = 7;   h_out: e (3) -> * sigma_t -> x - . -> / alpha_t = 6
-// which is what tests/test_gpu_sampler.py bounds the kernel with.
-// eps_hw > 0: eps / eps_u are the UNet output convolution's own layout [B][eps_hw][4] (x, hist and noise stay CHW [B][4][eps_hw]).
-// x_out may be x and hist_out may be hist_in: element i is read and written by the same thread only.
-// One element of the update.  SEEDED: z is drawn where the other flavour reads noise[i] - normal_counter(bases.base[b], j) for element j of sample b (chw
-// elements per sample, counter_rng.h) - and its term is always added; without it the instantiation is the kernel as it always was.
-template <bool SEEDED>
-__device__ __forceinline__ int sampler_step_element(int64_t i, const float* x, const float* __restrict__ eps,
-                                                    const float* __restrict__ eps_u, float cfg_scale, const float* hist_in,
-                                                    const float* __restrict__ noise, const NormalBases& bases, int64_t chw,
-                                                    const SamplerCoeffs& c, int eps_hw, float* x_out, float* hist_out) {
-#pragma clang fp contract(off)
-  int64_t ie = i;
-  if (eps_hw > 0) {
-    const int64_t bc = i / eps_hw, pix = i - bc * eps_hw, b = bc >> 2;
-    ie = (b * eps_hw + pix) * 4 + (bc & 3);
-  }
-  float e = eps[ie];
-  if (eps_u) {
-    const float u = eps_u[ie];
-    const float d = e - u;
-    const float ds = d * cfg_scale;
-    e = ds + u;
-  }
-  const float xv = x[i];
-  float o = c.c_x * xv;
-  const float te = c.c_e * e;
-  o = o + te;
-  if (hist_in) {
-    const float th = c.c_h * hist_in[i];
-    o = o + th;
-  }
-  if constexpr (SEEDED) {
-    const int64_t b = i / chw;
-    const float tn = c.c_n * normal_counter(bases.base[b], (uint64_t)(i - b * chw));
-    o = o + tn;
-  } else {
-    if (noise) {
-      const float tn = c.c_n * noise[i];
-      o = o + tn;
-    }
-  }
-  if (hist_out) {
-    const float se = c.sigma_t * e;
-    const float xs = xv - se;
-    hist_out[i] = xs / c.alpha_t;
-  }
-  x_out[i] = o;
-  return nonfinite_f(o);  // a non-finite UNet output (fp16 overflow upstream) lands here every step
-}
+// One element of the update: sampler_step_element (update_element.h, with its rounding order), shared with the per-slot kernel.
 __global__ void k_sampler_step(const float* x, const float* __restrict__ eps, const float* __restrict__ eps_u, float cfg_scale,
                                const float* hist_in, const float* __restrict__ noise, int64_t n, SamplerCoeffs c, int eps_hw,
                                float* x_out, float* hist_out, int* __restrict__ nonfinite) {

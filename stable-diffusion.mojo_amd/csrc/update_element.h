@@ -1,0 +1,92 @@
+// update_element.h - one element of a sampler update, shared by every kernel that applies one: k_ddpm_step / k_ddpm_step_seeded
+// (kernels_elementwise.hip), k_sampler_step / k_sampler_step_seeded (kernels_sampler.hip) and k_slot_update (kernels_slots.hip).  The
+// lockstep kernels and the per-slot kernel inline the SAME function, so a slot's update gives the bits of the lockstep step it stands for.
+// Include after common.h.
+#pragma once
+#include "common.h"
+
+// ---- DDPM update + CFG combine (sampler.mojo:75-109, pipeline.mojo:117-119; App.D K9) ------------
+// eps_hw > 0: eps / eps_u are the UNet output convolution's own layout [B][eps_hw][4] (x and noise stay CHW [B][4][eps_hw])
+// One element of the update.  SEEDED: the noise is drawn where the other flavour reads noise[i] - normal_counter(bases.base[b], j) for element j of
+// sample b (chw elements per sample, counter_rng.h) - and is always added; without it the instantiation is the kernel as it always was.
+template <bool SEEDED>
+__device__ __forceinline__ int ddpm_step_element(int64_t i, float* __restrict__ x, const float* __restrict__ eps,
+                                                 const float* __restrict__ eps_u, float cfg_scale, const float* __restrict__ noise,
+                                                 const NormalBases& bases, int64_t chw, float sa, float sb, float c_x0, float c_xt,
+                                                 float sigma, int eps_hw) {
+  int64_t ie = i;
+  if (eps_hw > 0) {
+    const int64_t bc = i / eps_hw, pix = i - bc * eps_hw, b = bc >> 2;
+    ie = (b * eps_hw + pix) * 4 + (bc & 3);
+  }
+  float e = eps[ie];
+  if (eps_u) {
+    const float u = eps_u[ie];
+    e = (e - u) * cfg_scale + u;
+  }
+  const float xv = x[i];
+  const float x0 = (xv - e * sb) / sa;
+  float o = x0 * c_x0 + xv * c_xt;
+  if constexpr (SEEDED) {
+    const int64_t b = i / chw;
+    o += normal_counter(bases.base[b], (uint64_t)(i - b * chw)) * sigma;
+  } else {
+    if (noise) o += noise[i] * sigma;
+  }
+  x[i] = o;
+  return nonfinite_f(o);  // a non-finite UNet output (fp16 overflow upstream) lands here every step
+}
+
+// ---- linear-multistep update (DDIM, DPM-Solver++(2M); kernels_sampler.hip states the formula) ------------
+// Every product and sum below is ONE fp32 rounding, in this order, whatever the eps layout and whichever optional pointers are set
+// (contraction into fma is off: an absent term is skipped, the others round as before).  Roundings on the longest path
+//   x_out: e (sub, mul, add) -> * c_e -> + c_x x -> + c_h h -> + c_n z = 7;   h_out: e (3) -> * sigma_t -> x - . -> / alpha_t = 6
+// which is what tests/test_gpu_sampler.py bounds the kernel with.
+// eps_hw > 0: eps / eps_u are the UNet output convolution's own layout [B][eps_hw][4] (x, hist and noise stay CHW [B][4][eps_hw]).
+// x_out may be x and hist_out may be hist_in: element i is read and written by the same thread only.
+// One element of the update.  SEEDED: z is drawn where the other flavour reads noise[i] - normal_counter(bases.base[b], j) for element j of sample b (chw
+// elements per sample, counter_rng.h) - and its term is always added; without it the instantiation is the kernel as it always was.
+template <bool SEEDED>
+__device__ __forceinline__ int sampler_step_element(int64_t i, const float* x, const float* __restrict__ eps,
+                                                    const float* __restrict__ eps_u, float cfg_scale, const float* hist_in,
+                                                    const float* __restrict__ noise, const NormalBases& bases, int64_t chw,
+                                                    const SamplerCoeffs& c, int eps_hw, float* x_out, float* hist_out) {
+#pragma clang fp contract(off)
+  int64_t ie = i;
+  if (eps_hw > 0) {
+    const int64_t bc = i / eps_hw, pix = i - bc * eps_hw, b = bc >> 2;
+    ie = (b * eps_hw + pix) * 4 + (bc & 3);
+  }
+  float e = eps[ie];
+  if (eps_u) {
+    const float u = eps_u[ie];
+    const float d = e - u;
+    const float ds = d * cfg_scale;
+    e = ds + u;
+  }
+  const float xv = x[i];
+  float o = c.c_x * xv;
+  const float te = c.c_e * e;
+  o = o + te;
+  if (hist_in) {
+    const float th = c.c_h * hist_in[i];
+    o = o + th;
+  }
+  if constexpr (SEEDED) {
+    const int64_t b = i / chw;
+    const float tn = c.c_n * normal_counter(bases.base[b], (uint64_t)(i - b * chw));
+    o = o + tn;
+  } else {
+    if (noise) {
+      const float tn = c.c_n * noise[i];
+      o = o + tn;
+    }
+  }
+  if (hist_out) {
+    const float se = c.sigma_t * e;
+    const float xs = xv - se;
+    hist_out[i] = xs / c.alpha_t;
+  }
+  x_out[i] = o;
+  return nonfinite_f(o);  // a non-finite UNet output (fp16 overflow upstream) lands here every step
+}

@@ -135,6 +135,9 @@ def _declare(l):
         "tsd_session_upload": ([vp, fp, fp, fp, fp, f], i), "tsd_session_step": ([vp, i], i),
         "tsd_session_add_noise": ([vp, i, fp], i), "tsd_session_decode": ([vp], i),
         "tsd_session_download_latents": ([vp, fp], i), "tsd_session_download_images": ([vp, i, fp], i),
+        "tsd_session_slots_open": ([vp], i), "tsd_session_slot_start": ([vp, i, fp, fp, fp, i, u64, i, f], i),
+        "tsd_session_advance": ([vp, C.POINTER(C.c_uint32)], i), "tsd_session_slot_state": ([vp, i, C.POINTER(i), C.POINTER(i)], i),
+        "tsd_session_slot_download": ([vp, i, fp], i), "tsd_session_slots_active": ([vp], i),
         "tsd_dist_unique_id": ([vp], i), "tsd_dist_init": ([vp, i, i, vp], i),
         "tsd_dist_broadcast_weights": ([vp, i], i), "tsd_dist_finalize": ([vp], i),
         "tsd_dist_comm_count": ([vp, C.POINTER(i)], i),
@@ -152,6 +155,7 @@ def _declare(l):
         "tsd_debug_set_qkv_fuse": ([vp, i], i),
         "tsd_debug_set_session_hoist": ([vp, i], i),
         "tsd_debug_session_hoist_info": ([vp, C.POINTER(i64)], i),
+        "tsd_debug_session_latents": ([vp, fp], i),
         "tsd_debug_mfma_sustained": ([vp, C.c_float, fp, fp], i),
         "tsd_debug_gemm_check": ([vp, i, i, i, i, i, i, i, i, i, i, fp, fp], i),
         "tsd_debug_gemm_record": ([vp, i], i),

@@ -263,6 +263,72 @@ class Session:
         check(lib().tsd_session_download_images(self.h, 1 if rescale else 0, ptr(out)))
         return out
 
+    # ---- slot mode: every sample its own request, schedule index and guidance scale (tsd.h "slot sessions"; tsd/serve.py drives it) ----
+    SLOT_IDLE, SLOT_ACTIVE, SLOT_DONE = 0, 1, 2
+
+    def slots_open(self):
+        """Enter slot mode, after set_sampler / set_schedule and in place of upload(): all B slots idle.  upload(), set_schedule() and
+        set_sampler() leave it; the lockstep calls (step, set_seeds, decode, latents, ...) are refused while it is on."""
+        check(lib().tsd_session_slots_open(self.h))
+
+    def slot_start(self, b, context, uncond_context=None, latents=None, noise_at_start=False, seed=0, start_index=0, cfg_scale=7.5):
+        """Put a request into slot b: context (T,768), uncond_context (T,768) on a CFG session, latents (4,L,L) or None (stream 2 of
+        `seed`); noise_at_start noises given latents to timesteps[start_index] with stream 4 of `seed` (img2img)."""
+        T, L = self.T, self.L
+        cx = f32(context)
+        if cx.shape == (1, T, 768):
+            cx = cx[0]
+        if cx.shape != (T, 768):
+            raise ValueError(f"context must have shape {(T, 768)}, got {cx.shape}")
+        uc = None
+        if uncond_context is not None:
+            uc = f32(uncond_context)
+            if uc.shape == (1, T, 768):
+                uc = uc[0]
+            if uc.shape != (T, 768):
+                raise ValueError(f"uncond_context must have shape {(T, 768)}, got {uc.shape}")
+        la = None
+        if latents is not None:
+            la = f32(latents)
+            if la.shape == (1, 4, L, L):
+                la = la[0]
+            if la.shape != (4, L, L):
+                raise ValueError(f"latents must have shape {(4, L, L)}, got {la.shape}")
+        seed = int(seed)
+        if seed < 0 or seed >= 1 << 64:
+            raise ValueError("the seed must fit an unsigned 64-bit integer")
+        check(lib().tsd_session_slot_start(self.h, int(b), ptr(cx), ptr(uc), ptr(la), 1 if noise_at_start else 0, seed, int(start_index),
+                                           float(cfg_scale)))
+
+    def advance(self):
+        """One tick: one forward over all slots, every active slot one step further.  Returns the slots that finished (ascending)."""
+        mask = C.c_uint32(0)
+        check(lib().tsd_session_advance(self.h, C.byref(mask)))
+        return [b for b in range(self.B) if mask.value >> b & 1]
+
+    def slot_state(self, b):
+        """(next schedule index, state) of slot b; state is SLOT_IDLE / SLOT_ACTIVE / SLOT_DONE."""
+        idx, st = C.c_int(0), C.c_int(0)
+        check(lib().tsd_session_slot_state(self.h, int(b), C.byref(idx), C.byref(st)))
+        return idx.value, st.value
+
+    def slot_latents(self, b):
+        out = np.empty((4, self.L, self.L), dtype=np.float32)
+        check(lib().tsd_session_slot_download(self.h, int(b), ptr(out)))
+        return out
+
+    def slots_active(self):
+        n = lib().tsd_session_slots_active(self.h)
+        if n < 0:
+            check(n)
+        return n
+
+    def raw_latents(self):
+        """The device's latent buffer (B,4,L,L) as it is, in any mode and unchecked (tsd_debug_session_latents; for tests)."""
+        out = np.empty((self.B, 4, self.L, self.L), dtype=np.float32)
+        check(lib().tsd_debug_session_latents(self.h, ptr(out)))
+        return out
+
     def hoist_info(self):
         """{active, time_table, ctx_k, ctx_vt (device addresses), bytes, builds} of the step-invariant buffers (tsd_debug_session_hoist_info)."""
         info = (C.c_int64 * 6)()

@@ -1,0 +1,109 @@
+"""tsd.serve - host-side continuous batching over a slot session (no reference counterpart: pipeline.mojo denoises one prompt at a time).
+
+A `Session` in slot mode (`Session.slots_open`) gives every sample of its batch its own request, schedule index and guidance scale; one
+`advance()` is one UNet forward for all of them.  `SlotScheduler` keeps the slots full from an iterator of requests: before every advance
+each free slot takes the next request, a slot that finishes yields its latents and is free again.  A request that arrives while the
+others are at step 3 of 50 starts at once; img2img requests of different strength - different start indices - share the batch.
+
+The scheduler only calls the slot methods (`B`, `num_steps`, `slot_start`, `advance`, `slot_latents`), so it runs against any object that
+has them (tests/test_slots_cpu.py drives it without a GPU).
+"""
+from collections import namedtuple
+
+import numpy as np
+
+# One request.  latents None: txt2img from `seed`.  latents (4,L,L) with strength s in [0,1]: img2img by the rule of `generate`
+# (sampler.mojo:68-70) - the first n - int(n * s) steps are skipped and the latents are noised to that timestep from `seed`.
+Request = namedtuple("Request", "id context uncond seed cfg_scale latents strength")
+Request.__new__.__defaults__ = (None, 0, 7.5, None, None)
+
+
+def start_index(num_steps, strength):
+    """`generate`'s img2img rule: the schedule index a request of this strength starts at (None: 0, the whole schedule)."""
+    if strength is None:
+        return 0
+    if not (0.0 <= strength <= 1.0):
+        raise ValueError(f"strength must be between 0 and 1, got {strength}")
+    return num_steps - int(num_steps * strength)
+
+
+class SlotScheduler:
+    """Iterate to run: yields (id, latents (4,L,L)) as slots finish, in slot order within one advance.
+
+    Greedy filling: before each advance every free slot takes the next request of the queue, so no advance runs with a free slot while
+    a request waits.  `advances`, `active_ticks` and `occupancy` (active slot-ticks over B * advances) describe the run so far.
+    A request whose strength leaves no step (start index == num_steps) is yielded as given, without taking a slot."""
+
+    def __init__(self, session, requests):
+        self.session, self.requests = session, iter(requests)
+        self.B, self.n = session.B, session.num_steps
+        self.owner = [None] * self.B  # request id per slot, None = free
+        self.advances = 0
+        self.active_ticks = 0
+        self._exhausted = False
+
+    @property
+    def occupancy(self):
+        return self.active_ticks / (self.B * self.advances) if self.advances else 0.0
+
+    def _fill(self):
+        """Start queued requests in the free slots; returns the requests that need no step at all."""
+        passed = []
+        for b in range(self.B):
+            while self.owner[b] is None and not self._exhausted:
+                try:
+                    r = next(self.requests)
+                except StopIteration:
+                    self._exhausted = True
+                    break
+                if not isinstance(r, Request):
+                    r = Request(*r)
+                i0 = start_index(self.n, r.strength if r.latents is not None else None)
+                if i0 >= self.n:  # strength 0: the image as it is
+                    passed.append((r.id, np.asarray(r.latents, dtype=np.float32)))
+                    continue
+                self.session.slot_start(b, r.context, r.uncond, latents=r.latents, noise_at_start=r.latents is not None, seed=r.seed,
+                                        start_index=i0, cfg_scale=r.cfg_scale)
+                self.owner[b] = r.id
+        return passed
+
+    def __iter__(self):
+        while True:
+            for item in self._fill():
+                yield item
+            busy = sum(o is not None for o in self.owner)
+            if not busy:
+                return
+            finished = self.session.advance()
+            self.advances += 1
+            self.active_ticks += busy
+            for b in finished:
+                rid, self.owner[b] = self.owner[b], None
+                yield rid, self.session.slot_latents(b)
+
+
+def generate_stream(diffusion, decoder, requests, B, L, T=77, cfg=True, inference_steps=50, num_training_steps=1000, sampler="ddpm",
+                    eta=0.0, spacing="leading", return_latents=False, stats=None):
+    """Continuous batching of `generate`: `requests` is an iterator of `Request`s (or tuples in its field order); yields (id, image
+    (3,8L,8L) in [0,255]) - or (id, latents) with return_latents or without a decoder - as requests finish, B at a time on the device.
+    A txt2img request gives what `generate(..., seeds=[...])` gives for it in the same sample position.  An img2img request indexes the
+    FULL timestep list (its step i draws stream 16 + i of its seed), where `generate` drops the skipped entries and counts from 0.
+    Finished latents are decoded through `decoder.forward`, one image per call.  `stats`, a dict, receives advances / active_ticks / occupancy when the stream ends."""
+    from .model import Session
+    from .utils import _unary
+    sess = Session(diffusion.model, None, B, L, T, cfg=cfg)
+    try:
+        if (sampler, eta, spacing) != ("ddpm", 0.0, "leading"):
+            sess.set_sampler(sampler, eta, spacing)
+        sess.set_schedule(num_training_steps, inference_steps, 0)
+        sess.slots_open()
+        sched = SlotScheduler(sess, requests)
+        for rid, lat in sched:
+            if decoder is None or return_latents:
+                yield rid, lat
+            else:
+                yield rid, _unary("tsd_rescale_images_f32", decoder.forward(lat), diffusion.model.ctx)  # pipeline.mojo:127
+        if stats is not None:
+            stats.update(advances=sched.advances, active_ticks=sched.active_ticks, occupancy=sched.occupancy)
+    finally:
+        sess.close()
