@@ -601,6 +601,50 @@ enum tsd_attn_info { TSD_AI_CHANGED = 0, TSD_AI_KERNEL, TSD_AI_EXACT_WGS, TSD_AI
  * value). */
 int tsd_debug_attn_run(tsd_ctx* ctx, const int64_t* desc, int n, const void* const* host_in, void* const* host_out, int64_t* ext,
                        int64_t* info);
+/* ---- fused attention-block head / tail launch descriptors (test infrastructure: tests/chain_ref.py holds attn_chain_kernel<KIND_HEAD>,
+ * attn_chain_kernel<KIND_TAIL> and the two weight-stream packers of csrc/kernels_chain.hip to an fp64 reference, element-wise) ----
+ * One int64 per argument of launch_attn_tail / launch_attn_head (AttnTailArgs / AttnHeadArgs, csrc/common.h): B samples of S token rows
+ * (M = B * S), T context keys, pitches and per-sample strides in elements, SCALE and EPS the bits of a float.  C, D, HEADS are the
+ * block's width, head dimension and head count: the kernels exist for 320 / 40 / 8 only and every other value is refused by the launch,
+ * not by the sizing.  GN (tail, 0 / 1): emit the output's GroupNorm(32) partials, one slab per 32 rows (nslab = S / 32).  LDW_*: the
+ * pitch of each row-major weight (tail: SO, Q, CO, 1, 2, OUT; head: C, IN).  The entry builds the packed weight stream itself
+ * (launch_attn_tail_pack / launch_attn_head_pack, into a guarded scratch operand) from the caller's row-major weights.
+ *
+ * The tail's pad contract for the context operands (csrc/kernels_chain.hip, the context staging): K rows >= T are never read - their
+ * lanes fetch at PAD_OFF, beyond the buffer descriptor, which returns zeros; V^T is staged in 8-column chunks and every chunk that starts
+ * below round_up(T, 8) is read whole: columns [T, round_up(T, 8)) reach the P.V MFMA with P = 0, and 0 x NaN = NaN, so they must hold
+ * FINITE values; columns >= round_up(T, 8) (and the pitch gaps of K) are never read.  The producers of the context V^T write those
+ * columns (see the attention entry's note above: the context is padded with zero rows to round_up(T, 8)). */
+enum tsd_chain_desc_field {
+  TSD_CD_VERSION = 0, TSD_CD_MODE, TSD_CD_B, TSD_CD_S, TSD_CD_T, TSD_CD_C, TSD_CD_D, TSD_CD_HEADS,
+  TSD_CD_LD_AO, TSD_CD_LD_TOK, TSD_CD_LD_X, TSD_CD_LD_OUT, TSD_CD_LDK, TSD_CD_SKB, TSD_CD_LDVT, TSD_CD_SVTB, TSD_CD_SCALE, TSD_CD_EPS,
+  TSD_CD_GN, TSD_CD_LD_QK, TSD_CD_LD_VT, TSD_CD_S_VT,
+  TSD_CD_LDW_SO, TSD_CD_LDW_Q, TSD_CD_LDW_CO, TSD_CD_LDW_1, TSD_CD_LDW_2, TSD_CD_LDW_OUT, TSD_CD_LDW_C, TSD_CD_LDW_IN,
+  TSD_CD_COUNT
+};
+#define TSD_CD_VERSION_1 1
+enum tsd_chain_mode { TSD_CM_HEAD = 0, TSD_CM_TAIL };
+/* Operand slots, in the device layout.  Tail inputs: AO, TOK, X [M][ld] fp16; KC [B][>= T][LDK]; VT [B][C][LDVT]; WSO, WQ, WCO, WOUT
+ * [C][ldw], W1 [8C][ldw] and B1 [8C] in the interleaved (a, g) row order of k_pack_linear (row 2q = "a" unit q, row 2q + 1 = gate q), W2
+ * [C][ldw] of 4C columns (fp16); BSO, BCO, B1, B2, BOUT fp32.  Head inputs: X; GN_STATS [B][32][2] fp32 (mean, 1 / (sigma + eps)); WC
+ * [C][ldw], WIN [3C][ldw] (fp16); B_IN fp32.  Tail outputs: OUT [M][LD_OUT] fp16, GN_PART [B][S / 32][32][2] fp32 (GN = 1).  Head
+ * outputs: HTOK [M][LD_TOK], QK [M][LD_QK] (q | k), HVT [B][C][LD_VT] at stride S_VT (fp16). */
+enum tsd_chain_operand {
+  TSD_CO_AO = 0, TSD_CO_TOK, TSD_CO_X, TSD_CO_KC, TSD_CO_VT, TSD_CO_WSO, TSD_CO_WQ, TSD_CO_WCO, TSD_CO_W1, TSD_CO_W2, TSD_CO_WOUT,
+  TSD_CO_BSO, TSD_CO_BCO, TSD_CO_B1, TSD_CO_B2, TSD_CO_BOUT, TSD_CO_GN_STATS, TSD_CO_WC, TSD_CO_WIN, TSD_CO_B_IN,
+  TSD_CO_OUT, TSD_CO_GN_PART, TSD_CO_HTOK, TSD_CO_QK, TSD_CO_HVT, TSD_CO_COUNT
+};
+/* info: guard / pitch-gap elements the launches changed; 1 when the fused kernel was launched (0: the packer or the launcher refused). */
+enum tsd_chain_info { TSD_CI_CHANGED = 0, TSD_CI_RAN, TSD_CI_COUNT };
+/* Run the launch described by desc (n >= TSD_CD_COUNT fields) on caller operands (host_in[TSD_CO_AO .. TSD_CO_B_IN], NULL for unused
+ * slots) through launch_attn_tail / launch_attn_head and return its outputs (host_out[slot - TSD_CO_OUT]).  host_in == NULL only sizes
+ * (ctx may be NULL, no device is touched): ext[TSD_CO_COUNT] receives every slot's extent (0 = unused).  A descriptor that cannot be
+ * sized is refused before any launch; what the launchers refuse (S % 64, T outside 1 .. 80, pitches below 320 or no multiple of 8, LDVT
+ * < round_up(T, 8), LD_VT < S, C / D / HEADS other than 320 / 40 / 8, the fused path switched off by tsd_debug_set_fused_attention) is
+ * sized and left to them.  Every operand sits between 4 KiB guard bands of a NaN pattern and the outputs are pre-filled with it; they are
+ * returned even when the launch is refused (its status is the return value). */
+int tsd_debug_chain_run(tsd_ctx* ctx, const int64_t* desc, int n, const void* const* host_in, void* const* host_out, int64_t* ext,
+                        int64_t* info);
 /* GroupNorm launches enqueued on this context since the last reset, per statistics path: counts[0] all, [1] own statistics pass,
  * [2] one producer table finished inside the apply blocks, [3] one producer table finished by the k_gn_finalize launch,
  * [4] k_gn_prereduce, [5] composite accepted, [6] k_gn_finalize launches (any source), [7] composites offered.  n >= 8; reset != 0

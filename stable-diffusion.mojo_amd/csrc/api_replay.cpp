@@ -1,6 +1,6 @@
 // api_replay.cpp - the replay entries: one launch of a kernel family, described by an int64 descriptor, run on caller operands in
-// their device layout so that tests can hold it to an fp64 reference element-wise (tsd_debug_gemm_run / _norm_run / _attn_run, and
-// the recording of the GEMM descriptors the product's graphs launch).  Test infrastructure, not the measured path.  What the three
+// their device layout so that tests can hold it to an fp64 reference element-wise (tsd_debug_gemm_run / _norm_run / _attn_run / _chain_run,
+// and the recording of the GEMM descriptors the product's graphs launch).  Test infrastructure, not the measured path.  What the four
 // entries share - the guarded device operands, the scan for writes outside an output's logical elements (replay_scan.h), the slot
 // checks and the scoped option overrides - is written once here; sizing, marshalling and the reported plan stay with each family.
 #include <string.h>
@@ -573,5 +573,129 @@ extern "C" int tsd_debug_attn_run(tsd_ctx* ctx, const int64_t* desc, int n, cons
   info[TSD_AI_DIAG] = ctx->attn_last.diag; info[TSD_AI_XCD_MAP] = ctx->attn_last.xcd_map;
   info[TSD_AI_EXACT_WGS] = exact1 - exact0;
   TSD_TRY(ops.read_back(&info[TSD_AI_CHANGED]));
+  return r;
+}
+
+// ---- fused attention-block head / tail on caller operands (tests/chain_ref.py holds both kernels and the packers to an fp64 reference) ----
+// (The tail's pad contract for the context operands is stated beside the entry's declaration, include/tsd.h.)
+namespace {
+int cd_elem_bytes(int slot) {
+  return (slot >= TSD_CO_BSO && slot <= TSD_CO_GN_STATS) || slot == TSD_CO_B_IN || slot == TSD_CO_GN_PART ? 4 : 2;
+}
+// Element extent of every operand the described launch reads or writes.  Refuses what it cannot size; what the launchers refuse (S % 64,
+// T outside 1 .. 80 - sized as one key -, narrow or misaligned pitches, other C / d / heads, the fused path switched off) is left to them.
+int cd_extents(const int64_t* d, int64_t* e) {
+  for (int i = 0; i < TSD_CO_COUNT; i++) e[i] = 0;
+#define CD_REQ(cond) \
+  if (!(cond)) TSD_FAIL(TSD_E_ARG, "chain_run: descriptor cannot be sized (%s)", #cond)
+  CD_REQ(d[TSD_CD_VERSION] == TSD_CD_VERSION_1);
+  const int64_t mode = d[TSD_CD_MODE], B = d[TSD_CD_B], S = d[TSD_CD_S], C = d[TSD_CD_C], lim = 1LL << 28;
+  CD_REQ(mode == TSD_CM_HEAD || mode == TSD_CM_TAIL);
+  CD_REQ(B > 0 && B <= 4096 && S > 0 && S <= (1 << 20) && B * S < (1 << 24));
+  CD_REQ(C > 0 && C <= 4096 && d[TSD_CD_D] > 0 && d[TSD_CD_D] <= 4096 && d[TSD_CD_HEADS] > 0 && d[TSD_CD_HEADS] <= 4096);
+  const int64_t M = B * S, ld_max = 1 << 21;  // one cap for every pitch: the head's V^T pitch spans a sample's S <= 2^20 tokens
+  auto rows = [&](int64_t n, int f, int64_t width) { return (n - 1) * d[f] + width; };
+  if (mode == TSD_CM_TAIL) {
+    const int64_t T = d[TSD_CD_T], Tk = std::max<int64_t>(T, 1);
+    CD_REQ(T >= 0 && T <= 4096 && (d[TSD_CD_GN] == 0 || d[TSD_CD_GN] == 1));
+    for (int f : {TSD_CD_LD_AO, TSD_CD_LD_TOK, TSD_CD_LD_X, TSD_CD_LD_OUT, TSD_CD_LDK, TSD_CD_LDVT, TSD_CD_LDW_SO, TSD_CD_LDW_Q, TSD_CD_LDW_CO,
+                  TSD_CD_LDW_1, TSD_CD_LDW_2, TSD_CD_LDW_OUT})
+      CD_REQ(d[f] > 0 && d[f] <= ld_max);
+    const int64_t Tv = std::min((Tk + 7) / 8 * 8, d[TSD_CD_LDVT]);
+    CD_REQ(d[TSD_CD_SKB] >= Tk * d[TSD_CD_LDK] && d[TSD_CD_SVTB] >= C * d[TSD_CD_LDVT] && d[TSD_CD_SKB] < lim && d[TSD_CD_SVTB] < lim);
+    e[TSD_CO_AO] = rows(M, TSD_CD_LD_AO, C); e[TSD_CO_TOK] = rows(M, TSD_CD_LD_TOK, C); e[TSD_CO_X] = rows(M, TSD_CD_LD_X, C);
+    e[TSD_CO_KC] = (B - 1) * d[TSD_CD_SKB] + rows(Tk, TSD_CD_LDK, C);
+    e[TSD_CO_VT] = (B - 1) * d[TSD_CD_SVTB] + rows(C, TSD_CD_LDVT, Tv);
+    e[TSD_CO_WSO] = rows(C, TSD_CD_LDW_SO, C); e[TSD_CO_WQ] = rows(C, TSD_CD_LDW_Q, C); e[TSD_CO_WCO] = rows(C, TSD_CD_LDW_CO, C);
+    e[TSD_CO_W1] = rows(8 * C, TSD_CD_LDW_1, C); e[TSD_CO_W2] = rows(C, TSD_CD_LDW_2, 4 * C); e[TSD_CO_WOUT] = rows(C, TSD_CD_LDW_OUT, C);
+    e[TSD_CO_BSO] = e[TSD_CO_BCO] = e[TSD_CO_B2] = e[TSD_CO_BOUT] = C;
+    e[TSD_CO_B1] = 8 * C;
+    e[TSD_CO_OUT] = rows(M, TSD_CD_LD_OUT, C);
+    if (d[TSD_CD_GN]) e[TSD_CO_GN_PART] = B * (S / 32) * 32 * 2;  // nslab = S / 32, as the launch is given it
+  } else {
+    for (int f : {TSD_CD_LD_X, TSD_CD_LD_TOK, TSD_CD_LD_QK, TSD_CD_LD_VT, TSD_CD_LDW_C, TSD_CD_LDW_IN}) CD_REQ(d[f] > 0 && d[f] <= ld_max);
+    CD_REQ(d[TSD_CD_S_VT] >= C * d[TSD_CD_LD_VT] && d[TSD_CD_S_VT] < lim);
+    e[TSD_CO_X] = rows(M, TSD_CD_LD_X, C);
+    e[TSD_CO_GN_STATS] = B * 32 * 2;
+    e[TSD_CO_WC] = rows(C, TSD_CD_LDW_C, C); e[TSD_CO_WIN] = rows(3 * C, TSD_CD_LDW_IN, C);
+    e[TSD_CO_B_IN] = C;
+    e[TSD_CO_HTOK] = rows(M, TSD_CD_LD_TOK, C); e[TSD_CO_QK] = rows(M, TSD_CD_LD_QK, 2 * C);
+    e[TSD_CO_HVT] = (B - 1) * d[TSD_CD_S_VT] + rows(C, TSD_CD_LD_VT, S);
+  }
+  for (int s = 0; s < TSD_CO_COUNT; s++) CD_REQ(e[s] >= 0 && e[s] <= lim);
+#undef CD_REQ
+  return TSD_OK;
+}
+}  // namespace
+
+extern "C" int tsd_debug_chain_run(tsd_ctx* ctx, const int64_t* desc, int n, const void* const* host_in, void* const* host_out,
+                                   int64_t* ext, int64_t* info) {
+  NOTNULL(desc); NOTNULL(ext);
+  TSD_TRY(check_fields("chain_run", n, TSD_CD_COUNT));
+  TSD_TRY(cd_extents(desc, ext));
+  const int64_t* d = desc;
+  if (info) for (int i = 0; i < TSD_CI_COUNT; i++) info[i] = 0;
+  if (!host_in) return TSD_OK;  // sizing only: no context or device needed
+  NOTNULL(ctx); NOTNULL(host_out); NOTNULL(info);
+  TSD_TRY(check_slots("chain_run", ext, TSD_CO_COUNT, TSD_CO_OUT, host_in, host_out));
+  HIP_TRY(hipSetDevice(ctx->device));
+  const bool tail = d[TSD_CD_MODE] == TSD_CM_TAIL;
+  const int64_t B = d[TSD_CD_B], S = d[TSD_CD_S], M = B * S, C = d[TSD_CD_C];
+  enum { W_STREAM = TSD_CO_COUNT, SLOTS };  // the packed weight stream the model path would have made: an input like the others
+  GuardedOperands ops(ctx, SLOTS);
+  for (int s = 0; s < TSD_CO_OUT; s++)
+    if (ext[s]) TSD_TRY(ops.add(s, ext[s], cd_elem_bytes(s), host_in[s]));
+  const replay::Box logical[] = {{1, 0, M, d[TSD_CD_LD_OUT], C},
+                                 replay::Box::dense(ext[TSD_CO_GN_PART]),
+                                 {1, 0, M, d[TSD_CD_LD_TOK], C},
+                                 {1, 0, M, d[TSD_CD_LD_QK], 2 * C},
+                                 {B, d[TSD_CD_S_VT], C, d[TSD_CD_LD_VT], S}};
+  for (int s = TSD_CO_OUT; s < TSD_CO_COUNT; s++)
+    if (ext[s]) TSD_TRY(ops.add(s, ext[s], cd_elem_bytes(s), nullptr, host_out[s - TSD_CO_OUT], logical[s - TSD_CO_OUT]));
+  auto h = [&](int s) { return (const half_t*)ops.at(s); };
+  auto f = [&](int s) { return (const float*)ops.at(s); };
+  // the packers read fixed 320-wide shapes: they see the caller's weights only when those have that shape (every other C is refused by
+  // the launch below, with the stream left as the fill)
+  const bool packable = C == 320;
+  TSD_TRY(ops.add(W_STREAM, (int64_t)((tail ? attn_tail_stream_bytes() : attn_head_stream_bytes()) / 2), 2, nullptr));
+  half_t* ws = (half_t*)ops.at(W_STREAM);
+  int r = TSD_OK;
+  if (packable)
+    r = tail ? launch_attn_tail_pack(ctx, h(TSD_CO_WSO), (int)d[TSD_CD_LDW_SO], h(TSD_CO_WQ), (int)d[TSD_CD_LDW_Q], h(TSD_CO_WCO),
+                                     (int)d[TSD_CD_LDW_CO], h(TSD_CO_W1), (int)d[TSD_CD_LDW_1], h(TSD_CO_W2), (int)d[TSD_CD_LDW_2],
+                                     h(TSD_CO_WOUT), (int)d[TSD_CD_LDW_OUT], ws)
+             : launch_attn_head_pack(ctx, h(TSD_CO_WC), (int)d[TSD_CD_LDW_C], h(TSD_CO_WIN), (int)d[TSD_CD_LDW_IN], ws);
+  bool ran = false;
+  if (r == TSD_OK)
+    r = run_planned(ctx, [&]() -> int {
+      if (tail) {
+        AttnTailArgs a;
+        a.ao = h(TSD_CO_AO); a.ld_ao = (int)d[TSD_CD_LD_AO]; a.tok = h(TSD_CO_TOK); a.ld_tok = (int)d[TSD_CD_LD_TOK];
+        a.x = h(TSD_CO_X); a.ld_x = (int)d[TSD_CD_LD_X]; a.out = (half_t*)ops.at(TSD_CO_OUT); a.ld_out = (int)d[TSD_CD_LD_OUT];
+        a.wstream = ws;
+        a.bso = f(TSD_CO_BSO); a.bco = f(TSD_CO_BCO); a.b1 = f(TSD_CO_B1); a.b2 = f(TSD_CO_B2); a.bout = f(TSD_CO_BOUT);
+        a.Kc = h(TSD_CO_KC); a.ldk = (int)d[TSD_CD_LDK]; a.sK = d[TSD_CD_SKB];
+        a.Vt = h(TSD_CO_VT); a.ldvt = (int)d[TSD_CD_LDVT]; a.sVt = d[TSD_CD_SVTB];
+        a.C = (int)C; a.d = (int)d[TSD_CD_D]; a.heads = (int)d[TSD_CD_HEADS]; a.T = (int)d[TSD_CD_T]; a.S = (int)S; a.M = M;
+        a.scale = f32_of(d[TSD_CD_SCALE]); a.eps = f32_of(d[TSD_CD_EPS]);
+        if (d[TSD_CD_GN]) { a.gn_part = (float*)ops.at(TSD_CO_GN_PART); a.gn_nslab = (int)(S / 32); }
+        TSD_TRY(launch_attn_tail(ctx, a));
+      } else {
+        // launch_attn_head takes no width: its callers ask attn_tail_supported first (g_unet_attn), and so does this one
+        if (!attn_tail_supported(ctx, (int)C, (int)d[TSD_CD_D], (int)d[TSD_CD_HEADS], 1, M, (int)S))
+          TSD_FAIL(TSD_E_SHAPE, "attention head: unsupported shape");
+        AttnHeadArgs a;
+        a.x = h(TSD_CO_X); a.ld_x = (int)d[TSD_CD_LD_X]; a.gn_stats = f(TSD_CO_GN_STATS); a.wstream = ws; a.b_in = f(TSD_CO_B_IN);
+        a.tok = (half_t*)ops.at(TSD_CO_HTOK); a.ld_tok = (int)d[TSD_CD_LD_TOK]; a.qk = (half_t*)ops.at(TSD_CO_QK); a.ld_qk = (int)d[TSD_CD_LD_QK];
+        a.vt = (half_t*)ops.at(TSD_CO_HVT); a.ld_vt = (int)d[TSD_CD_LD_VT]; a.s_vt = d[TSD_CD_S_VT];
+        a.M = M; a.S = (int)S; a.eps = f32_of(d[TSD_CD_EPS]);
+        TSD_TRY(launch_attn_head(ctx, a));
+      }
+      ran = ctx->launch();
+      return TSD_OK;
+    });
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  info[TSD_CI_RAN] = ran ? 1 : 0;
+  TSD_TRY(ops.read_back(&info[TSD_CI_CHANGED]));
   return r;
 }

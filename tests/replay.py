@@ -1,4 +1,5 @@
-"""What the tests of the replay entries (tsd_debug_gemm_run, tsd_debug_norm_run, tsd_debug_attn_run: csrc/api_replay.cpp) share: the
+"""What the tests of the replay entries (tsd_debug_gemm_run, tsd_debug_norm_run, tsd_debug_attn_run, tsd_debug_chain_run:
+csrc/api_replay.cpp) share: the
 fill patterns of the guarded operands, the enum reader of include/tsd.h, the sizing-only call, the run on caller operands, and the two
 statements about an output's bytes that every family makes (a refused launch wrote nothing; the pitch gaps still hold the fill)."""
 import ctypes as C
@@ -12,7 +13,7 @@ HDR = os.path.join(ROOT, "include", "tsd.h")
 NAN16 = np.array([0x7E5A], np.uint16).view(np.float16)[0]
 NAN32 = np.array([0x7FC5A5A5], np.uint32).view(np.float32)[0]
 _i64p = C.POINTER(C.c_int64)
-_SLOTS = 16          # no entry has more operand slots or info fields
+_SLOTS = 32          # no entry has more operand slots or info fields
 
 
 def f32_bits(x):
