@@ -565,10 +565,10 @@ int tsd_debug_norm_run(tsd_ctx* ctx, const int64_t* desc, int n, const void* con
  * Skv = min(round_up(Sk, 8), ldvt): columns [Sk, Skv) reach the P.V MFMA with P = 0, and 0 x NaN = NaN, so they must hold FINITE values
  * (columns >= Skv, the K pitch gap and K rows >= Sk are never read).  Every producer of a V^T operand writes them (csrc/, read for this):
  *   - cross-attention, Sk = T (77), pitch Tp = round_up(T, 8).  The context is converted by launch_f32_to_f16_rows with rows_dst = Tp,
- *     which writes rows [T, Tp) as zeros (kernels_elementwise.hip k_f32_to_f16_rows; called at api_ops.cpp:482 and :604,
- *     api_model.cpp:56 and :339 - the session's context).  Every V^T GEMM then computes all Tp columns from those rows: the swapped-operand
+ *     which writes rows [T, Tp) as zeros (kernels_elementwise.hip k_f32_to_f16_rows; called at api_ops.cpp:482 and :604, by
+ *     tsd_diffusion_forward and by session_put_context, session.cpp - the session's context).  Every V^T GEMM then computes all Tp columns from those rows: the swapped-operand
  *     GEMMs with N = Tp (api_ops.cpp:489, graph.cpp:276-281 and :474-479) and the fused K | V^T GEMM over M = B * Tp rows with vt_S = Tp
- *     (graph.cpp:462-468, which also builds the session's hoisted context V^T, api_model.cpp:212).  Columns [T, Tp) hold W_v . 0 (+ b_v):
+ *     (graph.cpp:462-468, which also builds the session's hoisted context V^T, session_build_invariants).  Columns [T, Tp) hold W_v . 0 (+ b_v):
  *     finite, whatever the arena held.
  *   - self-attention, Sk = S = H * W.  The fused q | k | V^T GEMM (graph.cpp:236-242, :391-397) and the fused block head (graph.cpp:217-225)
  *     run only where Sp == S (no pad columns).  Otherwise g_unet_attn zeroes the whole V^T buffer before the swapped-operand GEMM writes its

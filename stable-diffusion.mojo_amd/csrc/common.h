@@ -51,7 +51,7 @@ struct Arena {
 // Every tuning / A-B switch of the library.  Read from the environment ONCE, by tsd_ctx_create, into the context that the launches
 // run on: no dispatch code calls getenv and no switch is process-global, so two contexts (one per GPU, one host thread each - SURVEY.md
 // section 8b "Threading") can run different settings side by side.  The tsd_debug_set_* entry points change ONE context and bump its
-// `gen`; a denoise session remembers the generation it sized its workspace for (api_model.cpp).  Defaults = the measured optimum.
+// `gen`; a denoise session remembers the generation it sized its workspace for (session.cpp).  Defaults = the measured optimum.
 struct TsdOptions {
   // graph shape (graph.cpp)
   int qkv_fuse = 1;        // TSD_QKV_FUSE: q | k | V^T (and the context K | V^T of all blocks) from ONE GEMM with a transposed tail
@@ -441,6 +441,12 @@ int sampler_timesteps(int spacing, int n_train, int n_infer, int start_step, std
 // scalars of step i of `timesteps` as double: out[8] = { t, t_prev (-1: the clean sample), alpha_t, sigma_t, c_x, c_e, c_h, c_n }
 int sampler_coeffs(int kind, double eta, const std::vector<float>& alphas_cumprod, const std::vector<int>& timesteps, int i,
                    int have_history, double out[8]);
+// The plan of step i: what its update launch is given, whoever launches it (session.cpp: the lockstep step and every slot of an advance).
+// Fills e->mode (SLOT_DDPM / SLOT_LMS), e->c[] in the order documented at SlotEntry and e->flags: SLOT_NOISE the update adds noise,
+// SLOT_HIST_IN it reads the previous step's x0 (hist_valid: the caller holds it for step i), SLOT_HIST_OUT it keeps its own.
+// cfg_scale is the caller's.  DDPM's previous timestep is t - n_train / n_infer under LEADING spacing, the next list entry under TRAILING.
+int sampler_step_plan(int kind, double eta, int spacing, int n_train, int n_infer, const std::vector<float>& alphas_cumprod,
+                      const std::vector<int>& timesteps, int i, bool hist_valid, SlotEntry* e);
 
 // ---- non-finite accounting (kernels_elementwise.hip explains where it is reported) -------------------------------------------
 __device__ __forceinline__ bool nonfinite_f(float v) { return !(fabsf(v) <= 3.4028234e38f); }  // inf or NaN

@@ -437,7 +437,7 @@ int g_vae_attn(tsd_ctx* ctx, const Act& x, const VaeAttnW& w, Act& out) {
 
 // ---- the two parts of `Diffusion.forward` that do not read the latents ----------------------------------
 // Time path (diffusion.mojo:17-21 and :61-62 for all residual blocks): temb [B][320] -> t1 -> time -> tvec [B][tproj.N], all three in
-// the arena.  A denoise session runs it once per schedule entry at upload() (api_model.cpp) and hands the rows to the forward (UNetPre).
+// the arena.  A denoise session runs it once per schedule entry at upload() (session.cpp) and hands the rows to the forward (UNetPre).
 int g_unet_time_path(tsd_model* m, const float* temb, int B, const float** tvec_out) {
   tsd_ctx* ctx = m->ctx;
   const UNetW& u = m->unet;

@@ -3,7 +3,7 @@
 #pragma once
 #include "model.h"
 
-// how the C-ABI entry points (api_ops.cpp, api_model.cpp, api_replay.cpp) refuse a NULL pointer argument
+// how the C-ABI entry points (api_ops.cpp, api_model.cpp, session.cpp, api_replay.cpp) refuse a NULL pointer argument
 #define NOTNULL(p) \
   if (!(p)) TSD_FAIL(TSD_E_ARG, "%s: argument '%s' is NULL", __func__, #p)
 // A context option set for a scope (one replayed launch, one bench entry): the previous value is back when the scope ends, on every

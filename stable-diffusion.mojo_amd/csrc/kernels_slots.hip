@@ -1,4 +1,4 @@
-// kernels_slots.hip - the kernels of a slot session (tsd_session_slots_open / _slot_start / _advance, api_model.cpp): the samples of one
+// kernels_slots.hip - the kernels of a slot session (tsd_session_slots_open / _slot_start / _advance, session.cpp): the samples of one
 // batch sit at different indices of the schedule, so what the lockstep kernels take as scalars for the whole batch arrives here as a
 // by-value table with one entry per sample.
 //   k_slot_update      one launch updates every active sample with the coefficients, guidance scale, history flags and noise base of ITS

@@ -1,7 +1,8 @@
 // sampler.cpp - host side of the denoise schedule: the alphas_cumprod table, the timestep lists and the per-step scalars of the
 // samplers (no GPU).  The table is the reference's fp32 Tensor (sampler.mojo:28-32); everything derived from it here is computed in
 // double and rounded to float once, where the kernel takes it (kernels_sampler.hip).  The session's DDPM path does not come through
-// sampler_coeffs: it keeps the reference's fp32 scalars (api_model.cpp ddpm_coeffs) and its own kernel.
+// sampler_coeffs: it keeps the reference's fp32 scalars (ddpm_coeffs below) and its own kernel.  sampler_step_plan is the one place
+// that turns a schedule index into what an update launch is given, for the lockstep step and for a slot alike (session.cpp).
 #include <math.h>
 
 #include <algorithm>
@@ -90,6 +91,47 @@ int sampler_coeffs(int kind, double eta, const std::vector<float>& ac, const std
   }
   out[0] = t; out[1] = tp; out[2] = alpha_t; out[3] = sigma_t;
   out[4] = c_x; out[5] = c_e; out[6] = c_h; out[7] = c_n;
+  return TSD_OK;
+}
+
+// scalar coefficients of `DDPMSampler.step` sampler.mojo:81-98 and `get_variance` :53-65 (fp32 like the reference).  `prev` is the
+// reference's t - N // n (get_previous_timestep :46-51) under LEADING spacing and the next entry of the list under TRAILING.
+static void ddpm_coeffs(const std::vector<float>& ac, int t, int prev, float* sa, float* sb, float* c_x0, float* c_xt, float* sigma) {
+  const float a_t = ac[t];
+  const float a_prev = prev >= 0 ? ac[prev] : 1.f;
+  const float b_t = 1.f - a_t, b_prev = 1.f - a_prev;
+  const float cur_a = a_t / a_prev, cur_b = 1.f - cur_a;
+  *sa = sqrtf(a_t); *sb = sqrtf(b_t);
+  *c_x0 = sqrtf(a_prev) * cur_b / b_t;
+  *c_xt = sqrtf(cur_a) * b_prev / b_t;
+  float var = b_prev / b_t * cur_b;
+  if (var < 1e-20f) var = 1e-20f;
+  *sigma = t > 0 ? sqrtf(var) : 0.f;
+}
+
+int sampler_step_plan(int kind, double eta, int spacing, int n_train, int n_infer, const std::vector<float>& ac,
+                      const std::vector<int>& ts, int i, bool hist_valid, SlotEntry* e) {
+  if (i < 0 || i >= (int)ts.size()) TSD_FAIL(TSD_E_ARG, "sampler: step %d out of range (%d steps)", i, (int)ts.size());
+  e->flags = 0;
+  if (kind == TSD_SAMPLER_DDPM) {  // takes noise on every step that does not land on t = 0; no history
+    const int t = ts[i];
+    const int prev = spacing == TSD_SPACING_LEADING ? t - n_train / n_infer : (i + 1 < (int)ts.size() ? ts[i + 1] : -1);
+    e->mode = SLOT_DDPM;
+    ddpm_coeffs(ac, t, prev, &e->c[0], &e->c[1], &e->c[2], &e->c[3], &e->c[4]);
+    e->c[5] = 0.f;
+    if (t > 0) e->flags |= SLOT_NOISE;
+    return TSD_OK;
+  }
+  // DDIM / DPM-Solver++(2M): the scalars of sampler_coeffs (double), rounded to float once here.  DPM-Solver++(2M) is the only one that
+  // reads or keeps the history, and it takes no noise.
+  const bool multistep = kind == TSD_SAMPLER_DPMPP_2M, have_hist = multistep && hist_valid;
+  double cd[8];
+  TSD_TRY(sampler_coeffs(kind, eta, ac, ts, i, have_hist ? 1 : 0, cd));
+  e->mode = SLOT_LMS;
+  for (int k = 0; k < 6; k++) e->c[k] = (float)cd[2 + k];
+  if (have_hist) e->flags |= SLOT_HIST_IN;
+  if (multistep) e->flags |= SLOT_HIST_OUT;
+  if (!multistep && e->c[5] != 0.f) e->flags |= SLOT_NOISE;
   return TSD_OK;
 }
 

@@ -1,0 +1,769 @@
+// session.cpp - the device-resident denoise session (pipeline.mojo:57-127 + sampler.mojo:15-124): lockstep steps and slot mode.
+// A step's scalars come from one place, sampler_step_plan (sampler.cpp); what the entry points share is the session_* helpers below.
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <algorithm>
+#include <vector>
+
+#include "graph.h"
+
+// Every entry point opens with NOTNULL(p) on its pointer arguments (graph.h): TSD_E_ARG and the argument's name in
+// tsd_last_error.
+
+struct tsd_session {
+  tsd_model* unet = nullptr;
+  tsd_model* dec = nullptr;
+  tsd_ctx* ctx = nullptr;
+  int B = 0, L = 0, T = 0, Tp = 0, cfg = 0;
+  float cfg_scale = 7.5f;
+  // persistent device state (own allocation, not the arena)
+  char* state = nullptr;
+  float* latents = nullptr;   // [B,4,L,L] fp32 CHW (the reference's own layout)
+  float* lat2 = nullptr;      // [2B,4,L,L] duplicated latents for the CFG batch
+  half_t* ctx16 = nullptr;    // [B or 2B][Tp][768]
+  float* eps = nullptr;       // [B or 2B,4,L,L]
+  float* tdev = nullptr;      // [16] timestep per sample
+  float* temb = nullptr;      // [16][320]
+  float* noise = nullptr;     // [nsteps,B,4,L,L] or null
+  float* images = nullptr;    // [B,3,8L,8L]
+  float* hist = nullptr;      // [B,4,L,L] fp32: the data prediction x0 of the previous step (DPM-Solver++(2M))
+  // masked denoising (tsd_session_set_inpaint): carved from `state` like the rest, filled by set_inpaint, read by the blend of a step
+  float* ip_mask = nullptr;   // [B][L*L] fp32 in [0,1]: 1 = regenerate, 0 = keep `ip_known`
+  float* ip_known = nullptr;  // [B,4,L,L] the original latents
+  float* ip_noise = nullptr;  // [B,4,L,L] the noise they are re-noised with
+  size_t noise_cap = 0;
+  // What a step's UNet forward computes from the timestep and the context alone (graph.h UNetPre), made once per upload() by
+  // session_build_invariants when the context's session_hoist is on: own allocations, grown at upload() like `noise`, never in a step.
+  char* kv = nullptr;         // kc_all [Bu*Tp][CK] | vtc_all [Bu][CK][Tp] fp16: the context K / V^T of all attention blocks
+  half_t* kc_all = nullptr;
+  half_t* vtc_all = nullptr;
+  float* ttab = nullptr;      // [timesteps.size()][tproj.N] fp32: the time projections of every schedule entry (one row serves every sample)
+  size_t kv_cap = 0, ttab_cap = 0;
+  bool hoist = false;         // the steps of this upload() run on them
+  unsigned model_gen = 0;     // generation of the UNet's parameters (tsd_model::gen) at the last upload() / rebuild
+  int inv_builds = 0;         // session_build_invariants calls so far (tsd_debug_session_hoist_info)
+  // schedule (sampler.mojo:15-44)
+  int n_train = 1000, n_infer = 50, start = 0;
+  std::vector<float> alphas_cumprod;
+  std::vector<int> timesteps;
+  // sampler (tsd_session_set_sampler); the default is the reference's DDPMSampler on its own timestep rule
+  int sampler = TSD_SAMPLER_DDPM, spacing = TSD_SPACING_LEADING;
+  float eta = 0.f;
+  // step index for which `hist` holds the previous step's x0: i + 1 after step(i), -1 after upload() / add_noise() / set_*() and
+  // after a sampler that keeps no history.  A step with any other index runs first order.
+  int hist_valid_for = -1;
+  bool uploaded = false, has_noise = false;
+  // inpainting belongs to one upload(): off after upload() and after set_schedule / set_sampler; ip_has_noise: ip_noise was given
+  bool inpaint = false, ip_has_noise = false;
+  // seeded device-side noise (tsd_session_set_seeds) belongs to one upload() like inpainting: while on, a DDPM / DDIM(eta > 0) step draws
+  // its noise in the update kernel from stream 16 + i of seeds[b] (counter_rng.h), no buffer and no extra launch
+  bool seeded = false;
+  uint64_t seeds[16] = {};
+  size_t plan_unet = 0, plan_dec = 0;
+  unsigned opt_gen = 0;  // generation of the context's options the workspace was sized for (upload)
+  // Latched when the host scan of a download found inf / NaN in THIS session's latents: the context's counter is cleared once reported,
+  // the latents stay what they are - every later step, decode and download of this session fails with TSD_E_NONFINITE until upload()
+  // replaces the state.  The context-wide counter alone does not latch it: it also counts other sessions and
+  // models of the context (bench.py's scaled "peaked" model copy); its code is still returned at the synchronisation point that sees it.
+  bool poisoned = false;
+  bool decoded = false;  // decode() has run since the last upload(): images are defined
+  // Slot mode (tsd_session_slots_open): every sample is a slot with its own request, schedule index and guidance scale; advance() moves
+  // all active slots by one step with one forward.  `uploaded` stays false in slot mode - the lockstep entry points refuse by name
+  // (SESSION_NOT_SLOTS) - and upload(), set_schedule and set_sampler leave it.  The index, not a timestep list, is the unit of state.
+  bool slots = false;
+  struct Slot {
+    int state = 0;            // 0 idle, 1 active, 2 done
+    int index = 0;            // next schedule index; num_steps when done
+    float cfg_scale = 7.5f;
+    uint64_t seed = 0;
+    bool hist_valid = false;  // `hist` of this sample holds the x0 of the slot's previous step (DPM-Solver++(2M))
+  } slot[16];
+  float* trows = nullptr;     // [Bu][tproj.N] fp32: row i_b of ttab per sample, gathered by every advance (own allocation, grown at slots_open)
+  size_t trows_cap = 0;
+};
+
+// inf / NaN scan of a downloaded tensor (exponent bits all ones); the buffers at this boundary are 0.5 - 25 MB
+static bool host_all_finite(const float* p, size_t n) {
+  unsigned bad = 0;
+  for (size_t i = 0; i < n; i++) {
+    unsigned u;
+    memcpy(&u, p + i, 4);
+    bad |= ((u & 0x7f800000u) == 0x7f800000u);
+  }
+  return bad == 0;
+}
+#define SESSION_NOT_POISONED(s)                                                                                              \
+  do {                                                                                                                       \
+    if ((s)->poisoned)                                                                                                       \
+      TSD_FAIL(TSD_E_NONFINITE, "session: inf / NaN was found in this session's latents or images (reported at an earlier " \
+               "download); its state is unusable until upload() replaces it");                                              \
+  } while (0)
+
+#define SESSION_NOT_SLOTS(s, what)                                                                                           \
+  do {                                                                                                                       \
+    if ((s)->slots)                                                                                                          \
+      TSD_FAIL(TSD_E_STATE, "session: " what " moves the batch in lockstep and the session is in slot mode (slots_open); use the " \
+               "slot entry points, or upload() to leave slot mode");                                                        \
+  } while (0)
+
+#define SESSION_IN_SLOTS(s)                                                                                   \
+  do {                                                                                                        \
+    if (!(s)->slots) TSD_FAIL(TSD_E_STATE, "session: slots_open() first (the session is not in slot mode)"); \
+  } while (0)
+
+// ---- what the entry points share ---------------------------------------------------------------------------------------------
+// The workspace was sized under the context's options of upload() / slots_open() (`sized_by`); a tsd_debug_set_* call since then is refused.
+static int session_options_unchanged(const tsd_session* s, const char* sized_by) {
+  if (s->opt_gen != s->ctx->opt.gen)
+    TSD_FAIL(TSD_E_STATE, "session: a tsd_debug_set_* call changed this context's options after %s sized the workspace; %s again",
+             sized_by, sized_by);
+  return TSD_OK;
+}
+// The latents are no longer those the history was predicted from, and the images are not theirs any more.
+static void session_latents_changed(tsd_session* s) {
+  s->hist_valid_for = -1;
+  s->decoded = false;
+}
+// One of the session's own growable device buffers holds `bytes`: kept while large enough, else replaced (the contents are lost).
+static int session_grow(void** ptr, size_t* cap, size_t bytes, const char* what) {
+  if (bytes <= *cap) return TSD_OK;
+  if (*ptr) HIP_TRY(hipFree(*ptr));
+  *ptr = nullptr; *cap = 0;
+  if (hipMalloc(ptr, bytes) != hipSuccess) TSD_FAIL(TSD_E_ALLOC, "session: %s hipMalloc(%zu) failed", what, bytes);
+  *cap = bytes;
+  return TSD_OK;
+}
+// `samples` host contexts [T][768] fp32 -> rows first .. first + samples of ctx16, fp16 [Tp][768] with ZERO pad rows: the conversion the
+// V^T pad-column contract rests on (include/tsd.h).  Through the staging buffer, which the caller reserved; synchronises, so `src` and
+// the staging buffer are free again on return.
+static int session_put_context(tsd_session* s, const float* src, size_t first, int samples) {
+  tsd_ctx* ctx = s->ctx;
+  const size_t nc = (size_t)s->T * 768;
+  HIP_TRY(hipMemcpyAsync(ctx->staging, src, samples * nc * 4, hipMemcpyHostToDevice, ctx->stream));
+  for (int b = 0; b < samples; b++)
+    TSD_TRY(launch_f32_to_f16_rows(ctx, (const float*)ctx->staging + b * nc, s->T, 768, s->ctx16 + (first + b) * s->Tp * 768, 768, s->Tp));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return TSD_OK;
+}
+// add_noise at schedule index i on n floats at `lat` (sampler.mojo:100-124, fp32 scalars like the reference)
+static int session_add_noise(tsd_session* s, int i, float* lat, int64_t n, const float* noise) {
+  const float a = s->alphas_cumprod[s->timesteps[i]];
+  return launch_add_noise(s->ctx, lat, noise, n, sqrtf(a), sqrtf(1.f - a));
+}
+// n latents leave the device.  What leaves HERE is checked itself: the context's count may have been reported (and cleared) at another
+// model's synchronisation point, and it may be another session's - only this session's own buffer latches the poison.
+static int session_fetch_latents(tsd_session* s, const float* dev, size_t n, float* host) {
+  HIP_TRY(hipMemcpyAsync(host, dev, n * 4, hipMemcpyDeviceToHost, s->ctx->stream));
+  HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+  const int r = ctx_check_status(s->ctx);
+  if (!host_all_finite(host, n)) s->poisoned = true;
+  if (r != TSD_OK) return r;
+  SESSION_NOT_POISONED(s);
+  return TSD_OK;
+}
+
+// alphas_cumprod (sampler.mojo:28-32) and the timestep list of the session's spacing with `start` entries dropped (sampler.cpp)
+static int build_schedule(tsd_session* s) {
+  sampler_alphas_cumprod(s->n_train, s->alphas_cumprod);
+  return sampler_timesteps(s->spacing, s->n_train, s->n_infer, s->start, s->timesteps);
+}
+// Fill the session's step-invariant buffers on the context's stream, with the launches (same kernels, same arguments, same batch) a
+// step's forward would make for them, so their contents are the bits the per-step path computes:
+//   * context K / V^T: the forward's own projection launch, once;
+//   * time table: per schedule entry, the time embedding of its timestep for Bu samples and the three small linears behind it; every
+//     sample sees the same timestep, so the Bu rows are equal and row 0 is kept (the forward reads it with a per-sample stride of 0).
+// The arena (sized by upload() for this too) is scratch; nothing here synchronises.
+static int session_build_invariants(tsd_session* s) {
+  tsd_ctx* ctx = s->ctx;
+  tsd_model* m = s->unet;
+  const int Bu = s->cfg ? 2 * s->B : s->B, N = m->unet.tproj.N;
+  ctx->arena.top = 0;
+  TSD_TRY(g_unet_ctx_kv(m, s->ctx16, s->Tp, Bu, s->kc_all, s->vtc_all));
+  for (size_t i = 0; i < s->timesteps.size(); i++) {
+    ctx->arena.top = 0;
+    TSD_TRY(launch_time_embedding(ctx, nullptr, (float)s->timesteps[i], Bu, s->temb));
+    const float* tvec = nullptr;
+    TSD_TRY(g_unet_time_path(m, s->temb, Bu, &tvec));
+    HIP_TRY(hipMemcpyAsync(s->ttab + i * (size_t)N, tvec, (size_t)N * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  ctx->arena.top = 0;
+  s->model_gen = m->gen;
+  s->inv_builds++;
+  return TSD_OK;
+}
+static UNetPre session_pre(const tsd_session* s, int i) {
+  UNetPre p;
+  p.tvec = s->ttab + (size_t)i * s->unet->unet.tproj.N; p.tld = 0;
+  p.kc_all = s->kc_all; p.vtc_all = s->vtc_all;
+  return p;
+}
+// Parameters were set since the last build: the derived weights, then what this session derived from them (all samples).
+static int session_refresh(tsd_session* s) {
+  if (s->model_gen == s->unet->gen) return TSD_OK;
+  TSD_TRY(model_check_ready(s->unet));
+  if (s->hoist) TSD_TRY(session_build_invariants(s));
+  s->model_gen = s->unet->gen;
+  return TSD_OK;
+}
+// The UNet forward of a step or an advance: latents (twice under CFG: model_input for both passes is the same latents,
+// pipeline.mojo:107-108) -> eps.  `pre` is read under the hoist only.  eps stays in the output convolution's layout ([B][L*L][4])
+// where the forward can write it; the updates read it as such (no conversion launch): *eps_hw is their eps_hw argument.
+static int session_forward(tsd_session* s, const UNetPre* pre, int* eps_hw) {
+  tsd_ctx* ctx = s->ctx;
+  const int Bu = s->cfg ? 2 * s->B : s->B;
+  const size_t nl = (size_t)s->B * 4 * s->L * s->L;
+  const float* lat_in = s->latents;
+  if (s->cfg) {
+    HIP_TRY(hipMemcpyAsync(s->lat2, s->latents, nl * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(s->lat2 + nl, s->latents, nl * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    lat_in = s->lat2;
+  }
+  ctx->arena.top = 0;
+  const bool eps_nhwc = s->unet->unet.final_conv.Opad == 4;  // g_unet_forward's condition for writing that layout
+  TSD_TRY(g_unet_forward(s->unet, lat_in, s->ctx16, s->T, s->Tp, s->temb, Bu, s->L, s->eps, eps_nhwc, s->hoist ? pre : nullptr));
+  ctx->arena.top = 0;
+  *eps_hw = eps_nhwc ? s->L * s->L : 0;
+  return TSD_OK;
+}
+// The scalars and flags of step i of this session's schedule (sampler_step_plan fills mode, flags and c[]; cfg_scale is the caller's)
+static int session_plan(const tsd_session* s, int i, bool hist_valid, SlotEntry* e) {
+  return sampler_step_plan(s->sampler, s->eta, s->spacing, s->n_train, s->n_infer, s->alphas_cumprod, s->timesteps, i, hist_valid, e);
+}
+
+extern "C" int tsd_debug_set_session_hoist(tsd_ctx* ctx, int on) {
+  return ctx_set_option(ctx, &TsdOptions::session_hoist, on ? 1 : 0, 0, 1);
+}
+extern "C" int tsd_debug_session_hoist_info(tsd_session* s, int64_t* info) {
+  NOTNULL(s); NOTNULL(info);
+  info[0] = (s->uploaded || s->slots) && s->hoist; info[1] = (int64_t)(uintptr_t)s->ttab; info[2] = (int64_t)(uintptr_t)s->kc_all;
+  info[3] = (int64_t)(uintptr_t)s->vtc_all; info[4] = (int64_t)(s->kv_cap + s->ttab_cap); info[5] = s->inv_builds;
+  return TSD_OK;
+}
+
+// the device noise buffer and the workspace plan were sized for the OLD schedule, the history and the images belong to it: a new
+// upload() is required
+static void schedule_changed(tsd_session* s) {
+  s->uploaded = false; s->has_noise = false;
+  s->slots = false;
+  s->inpaint = false;
+  s->seeded = false;
+  session_latents_changed(s);
+}
+
+extern "C" int tsd_session_create(tsd_model* diffusion, tsd_model* decoder, int B, int L, int T, int cfg,
+                                  tsd_session** out) {
+  NOTNULL(diffusion); NOTNULL(out);
+  if (!is_diffusion_kind(diffusion->kind)) TSD_FAIL(TSD_E_ARG, "session: first model must be a Diffusion");
+  if (decoder && (!is_decoder_kind(decoder->kind) || decoder->ctx != diffusion->ctx))
+    TSD_FAIL(TSD_E_ARG, "session: decoder must be a Decoder on the same context");
+  const int Bu = cfg ? 2 * B : B;
+  if (B <= 0 || Bu > 16 || L <= 0 || L % 8 || T <= 0) TSD_FAIL(TSD_E_SHAPE, "session: B=%d (UNet batch %d <= 16) L=%d T=%d", B, Bu, L, T);
+  tsd_ctx* ctx = diffusion->ctx;
+  HIP_TRY(hipSetDevice(ctx->device));
+  tsd_session* s = new tsd_session();
+  s->unet = diffusion; s->dec = decoder; s->ctx = ctx;
+  s->B = B; s->L = L; s->T = T; s->Tp = round_up(T, 8); s->cfg = cfg ? 1 : 0;
+  const size_t nl = (size_t)B * 4 * L * L;
+  size_t off = 0;
+  auto carve = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~size_t(255); return o; };
+  const size_t o_lat = carve(nl * 4), o_lat2 = carve(2 * nl * 4), o_ctx = carve((size_t)Bu * s->Tp * 768 * 2),
+               o_eps = carve((size_t)Bu * 4 * L * L * 4), o_t = carve(16 * 4), o_te = carve(16 * 320 * 4),
+               o_img = carve(decoder ? (size_t)B * 3 * 64 * L * L * 4 : 0), o_hist = carve(nl * 4),
+               o_ipm = carve((size_t)B * L * L * 4), o_ipk = carve(nl * 4), o_ipn = carve(nl * 4);
+  hipError_t e = hipMalloc((void**)&s->state, off);
+  if (e != hipSuccess) { delete s; TSD_FAIL(TSD_E_ALLOC, "session: hipMalloc(%zu) failed: %s", off, hipGetErrorString(e)); }
+  if (ctx->opt.debug_poison >= 0 && (ctx->opt.debug_poison_what & 4)) hipMemsetAsync(s->state, ctx->opt.debug_poison & 255, off, ctx->stream);
+  s->latents = (float*)(s->state + o_lat); s->lat2 = (float*)(s->state + o_lat2);
+  s->ctx16 = (half_t*)(s->state + o_ctx); s->eps = (float*)(s->state + o_eps);
+  s->tdev = (float*)(s->state + o_t); s->temb = (float*)(s->state + o_te);
+  s->images = decoder ? (float*)(s->state + o_img) : nullptr;
+  s->hist = (float*)(s->state + o_hist);
+  s->ip_mask = (float*)(s->state + o_ipm); s->ip_known = (float*)(s->state + o_ipk); s->ip_noise = (float*)(s->state + o_ipn);
+  if (build_schedule(s) != TSD_OK) { hipFree(s->state); delete s; return TSD_E_ARG; }
+  *out = s;
+  return TSD_OK;
+}
+
+extern "C" int tsd_session_destroy(tsd_session* s) {
+  if (!s) return TSD_OK;
+  hipSetDevice(s->ctx->device);
+  hipStreamSynchronize(s->ctx->stream);
+  if (s->state) hipFree(s->state);
+  if (s->noise) hipFree(s->noise);
+  if (s->kv) hipFree(s->kv);
+  if (s->ttab) hipFree(s->ttab);
+  if (s->trows) hipFree(s->trows);
+  delete s;
+  return TSD_OK;
+}
+
+extern "C" int tsd_session_set_schedule(tsd_session* s, int num_training_steps, int num_inference_steps,
+                                        int start_step) {
+  NOTNULL(s);
+  if (num_training_steps <= 0 || num_inference_steps <= 0 || num_inference_steps > num_training_steps ||
+      start_step < 0 || start_step >= num_inference_steps)
+    TSD_FAIL(TSD_E_ARG, "schedule: train=%d infer=%d start=%d", num_training_steps, num_inference_steps, start_step);
+  s->n_train = num_training_steps; s->n_infer = num_inference_steps; s->start = start_step;
+  schedule_changed(s);
+  return build_schedule(s);
+}
+extern "C" int tsd_session_set_sampler(tsd_session* s, int kind, float eta, int spacing) {
+  NOTNULL(s);
+  if (kind != TSD_SAMPLER_DDPM && kind != TSD_SAMPLER_DDIM && kind != TSD_SAMPLER_DPMPP_2M)
+    TSD_FAIL(TSD_E_ARG, "sampler: kind %d (0 DDPM, 1 DDIM, 2 DPM-Solver++(2M))", kind);
+  if (spacing != TSD_SPACING_LEADING && spacing != TSD_SPACING_TRAILING)
+    TSD_FAIL(TSD_E_ARG, "sampler: timestep spacing %d (0 leading, 1 trailing)", spacing);
+  if (!(eta >= 0.f)) TSD_FAIL(TSD_E_ARG, "sampler: eta %g < 0", (double)eta);
+  s->sampler = kind; s->eta = eta; s->spacing = spacing;
+  schedule_changed(s);  // the timestep list may have changed: as after set_schedule
+  return build_schedule(s);
+}
+extern "C" int tsd_session_num_steps(tsd_session* s) { return s ? (int)s->timesteps.size() : TSD_E_ARG; }
+extern "C" int tsd_session_timestep(tsd_session* s, int i) {
+  if (!s || i < 0 || i >= (int)s->timesteps.size()) return TSD_E_ARG;
+  return s->timesteps[i];
+}
+
+// What upload() and slots_open() share once the session's buffers hold their data: size the workspace once for this session's shapes (no
+// allocation inside the timed loop), size and fill the step-invariant buffers, and mark the session ready.
+static int session_prepare(tsd_session* s) {
+  tsd_ctx* ctx = s->ctx;
+  const int B = s->B, L = s->L, T = s->T, Tp = s->Tp;
+  // size the workspace once for this session's shapes (no allocation inside the timed loop)
+  TSD_TRY(model_check_ready(s->unet));
+  if (s->dec) TSD_TRY(model_check_ready(s->dec));
+  Arena& a = ctx->arena;
+  const int Bu = s->cfg ? 2 * B : B;
+  s->hoist = ctx->opt.session_hoist != 0;
+  s->uploaded = false;  // until this upload() is complete: the buffers below may move
+  s->inpaint = false;   // the mask and the known latents belonged to the previous upload()
+  s->seeded = false;    // and so did the seeds
+  if (s->hoist) {  // the buffers of session_build_invariants; sizes depend on the session's shape and the schedule's length only
+    const int CK = s->unet->unet.kproj_all.N, N = s->unet->unet.tproj.N;
+    const size_t kc_bytes = ((size_t)Bu * Tp * CK * 2 + 255) & ~size_t(255);
+    TSD_TRY(session_grow((void**)&s->kv, &s->kv_cap, 2 * kc_bytes, "context K/V"));
+    s->kc_all = (half_t*)s->kv; s->vtc_all = (half_t*)(s->kv + kc_bytes);
+    TSD_TRY(session_grow((void**)&s->ttab, &s->ttab_cap, s->timesteps.size() * (size_t)N * 4, "time table"));
+  }
+  a.planning = true; a.top = 0; a.peak = 0;
+  const UNetPre pre0 = s->hoist ? session_pre(s, 0) : UNetPre();
+  int r = g_unet_forward(s->unet, s->lat2, s->ctx16, T, Tp, s->temb, Bu, L, s->eps, false, s->hoist ? &pre0 : nullptr);
+  size_t need = a.peak;
+  if (r == TSD_OK && s->hoist) {  // session_build_invariants' scratch
+    const float* tv = nullptr;
+    a.top = 0; a.peak = 0;
+    r = g_unet_time_path(s->unet, s->temb, Bu, &tv);
+    need = std::max(need, a.peak);
+  }
+  if (r == TSD_OK && s->dec) {
+    a.top = 0; a.peak = 0;
+    r = g_decoder_forward(s->dec, s->latents, B, L, s->images);
+    need = std::max(need, a.peak);
+  }
+  a.planning = false; a.top = 0; a.peak = 0;
+  if (r != TSD_OK) return r;
+  TSD_TRY(ctx_reserve_arena(ctx, need));
+  s->model_gen = s->unet->gen;
+  if (s->hoist) TSD_TRY(session_build_invariants(s));
+  s->opt_gen = ctx->opt.gen;
+  s->uploaded = true;
+  s->poisoned = false;
+  session_latents_changed(s);
+  return TSD_OK;
+}
+
+extern "C" int tsd_session_upload(tsd_session* s, const float* latents, const float* context,
+                                  const float* uncond_context, const float* noise, float cfg_scale) {
+  NOTNULL(s); NOTNULL(latents); NOTNULL(context);
+  if (s->cfg && !uncond_context) TSD_FAIL(TSD_E_ARG, "session: CFG session needs uncond_context");
+  tsd_ctx* ctx = s->ctx;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const int B = s->B;
+  const size_t nl = (size_t)B * 4 * s->L * s->L;
+  s->cfg_scale = cfg_scale;
+  s->slots = false;  // upload() leaves slot mode
+  HIP_TRY(hipMemcpyAsync(s->latents, latents, nl * 4, hipMemcpyHostToDevice, ctx->stream));
+  // context -> fp16 [Bu][Tp][768], zero padded rows (cond first, then uncond: pipeline.mojo:49)
+  TSD_TRY(ctx_reserve_staging(ctx, (size_t)B * s->T * 768 * 4));
+  for (int part = 0; part < (s->cfg ? 2 : 1); part++)
+    TSD_TRY(session_put_context(s, part == 0 ? context : uncond_context, (size_t)part * B, B));
+  s->has_noise = noise != nullptr;
+  if (noise) {
+    const size_t bytes = s->timesteps.size() * nl * 4;
+    TSD_TRY(session_grow((void**)&s->noise, &s->noise_cap, bytes, "noise"));
+    HIP_TRY(hipMemcpyAsync(s->noise, noise, bytes, hipMemcpyHostToDevice, ctx->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return session_prepare(s);
+}
+
+// Streams of the seeded noise, per sample b with seeds[b]: 2 the initial latents, 4 the add_noise / inpainting noise, 16 + i the noise of
+// schedule step i; the counter is the element's index inside its sample, (c*L + y)*L + x.  Nothing depends on B or on the sample's slot.
+enum { NOISE_STREAM_LATENTS = 2, NOISE_STREAM_ADD = 4, NOISE_STREAM_STEP0 = 16 };
+static NormalBases session_bases(const tsd_session* s, uint64_t stream) {
+  NormalBases nb = {};
+  for (int b = 0; b < s->B; b++) nb.base[b] = counter_rng_base(s->seeds[b], stream);
+  return nb;
+}
+
+// The launch a step with inpainting adds after its sampler update: the known region of `latents` is replaced by the original latents
+// noised to the timestep the update has just reached - entry i + 1 of the list, the clean sample (1, 0) after the last entry; under
+// LEADING spacing that entry is the reference's t - N // n.  a_prev = sqrt(abar), s_prev = sqrt(1 - abar) in double from the fp32 table,
+// rounded to float once: what tsd_sampler_coeffs reports as out[2], out[3] for step i + 1.  The same rule for all three samplers.
+static int session_inpaint_blend(tsd_session* s, int i) {
+  double a_prev = 1.0, s_prev = 0.0;
+  if (i + 1 < (int)s->timesteps.size()) {
+    const double abar = s->alphas_cumprod[s->timesteps[i + 1]];
+    a_prev = sqrt(abar); s_prev = sqrt(1.0 - abar);
+  }
+  return launch_inpaint_blend(s->ctx, s->latents, s->ip_mask, s->ip_known, s->ip_has_noise ? s->ip_noise : nullptr, s->B,
+                              (int64_t)s->L * s->L, (float)a_prev, (float)s_prev, s->latents);
+}
+
+extern "C" int tsd_session_step(tsd_session* s, int i) {
+  NOTNULL(s);
+  SESSION_NOT_SLOTS(s, "step()");
+  if (!s->uploaded) TSD_FAIL(TSD_E_STATE, "session: upload() before step()");
+  SESSION_NOT_POISONED(s);
+  TSD_TRY(session_options_unchanged(s, "upload()"));
+  if (i < 0 || i >= (int)s->timesteps.size()) TSD_FAIL(TSD_E_ARG, "session: step %d out of range", i);
+  tsd_ctx* ctx = s->ctx;
+  const int B = s->B, L = s->L, Bu = s->cfg ? 2 * B : B;
+  const int64_t chw = (int64_t)4 * L * L, nl = B * chw;
+  const bool hist_valid = s->hist_valid_for == i;
+  session_latents_changed(s);  // no valid history until this step's update is enqueued
+  TSD_TRY(session_refresh(s));
+  // time embedding on the device (get_time_embedding, pipeline.mojo:89): same t for every sample
+  if (!s->hoist) TSD_TRY(launch_time_embedding(ctx, nullptr, (float)s->timesteps[i], Bu, s->temb));
+  const UNetPre pre = s->hoist ? session_pre(s, i) : UNetPre();
+  int eps_hw = 0;
+  TSD_TRY(session_forward(s, &pre, &eps_hw));
+  SlotEntry p;
+  TSD_TRY(session_plan(s, i, hist_valid, &p));
+  // the update launch of the plan: its noise read from the uploaded tensor, drawn in the kernel (one source of noise per upload:
+  // has_noise is off under seeds) or absent; only DPM-Solver++(2M) reads or keeps the history, and it takes no noise
+  const float* eps_u = s->cfg ? s->eps + nl : nullptr;
+  const bool noisy = (p.flags & SLOT_NOISE) != 0, draws = noisy && s->seeded;
+  const float* nz = (noisy && s->has_noise) ? s->noise + (size_t)i * nl : nullptr;
+  const float* hist_in = (p.flags & SLOT_HIST_IN) ? s->hist : nullptr;
+  float* hist_out = (p.flags & SLOT_HIST_OUT) ? s->hist : nullptr;
+  const NormalBases nb = draws ? session_bases(s, NOISE_STREAM_STEP0 + (uint64_t)i) : NormalBases();
+  const float* c = p.c;
+  const SamplerCoeffs sc = {c[0], c[1], c[2], c[3], c[4], c[5]};
+  if (p.mode == SLOT_DDPM && draws)
+    TSD_TRY(launch_ddpm_step_seeded(ctx, s->latents, s->eps, eps_u, s->cfg_scale, nb, chw, nl, c[0], c[1], c[2], c[3], c[4], eps_hw));
+  else if (p.mode == SLOT_DDPM)
+    TSD_TRY(launch_ddpm_step(ctx, s->latents, s->eps, eps_u, s->cfg_scale, nz, nl, c[0], c[1], c[2], c[3], c[4], eps_hw));
+  else if (draws)
+    TSD_TRY(launch_sampler_step_seeded(ctx, s->latents, s->eps, eps_u, s->cfg_scale, hist_in, nb, chw, nl, sc, eps_hw, s->latents, hist_out));
+  else
+    TSD_TRY(launch_sampler_step(ctx, s->latents, s->eps, eps_u, s->cfg_scale, hist_in, nz, nl, sc, eps_hw, s->latents, hist_out));
+  if (s->inpaint) TSD_TRY(session_inpaint_blend(s, i));  // a failed step leaves no valid history
+  if (hist_out) s->hist_valid_for = i + 1;  // the blend changed the latents, not the prediction the next step extrapolates from
+  return TSD_OK;
+}
+
+extern "C" int tsd_session_add_noise(tsd_session* s, int i, const float* noise) {
+  NOTNULL(s); NOTNULL(noise);
+  SESSION_NOT_SLOTS(s, "add_noise()");
+  if (i < 0 || i >= (int)s->timesteps.size()) TSD_FAIL(TSD_E_ARG, "session: step %d out of range", i);
+  tsd_ctx* ctx = s->ctx;
+  const size_t nl = (size_t)s->B * 4 * s->L * s->L;
+  TSD_TRY(ctx_reserve_staging(ctx, nl * 4));
+  session_latents_changed(s);
+  HIP_TRY(hipMemcpyAsync(ctx->staging, noise, nl * 4, hipMemcpyHostToDevice, ctx->stream));
+  TSD_TRY(session_add_noise(s, i, s->latents, (int64_t)nl, (const float*)ctx->staging));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return TSD_OK;
+}
+
+// seeds: one per sample, or NULL = off.  One source of noise per upload(): refused when the upload carried a noise tensor.
+extern "C" int tsd_session_set_seeds(tsd_session* s, const uint64_t* seeds) {
+  NOTNULL(s);
+  SESSION_NOT_SLOTS(s, "set_seeds()");
+  if (!s->uploaded) TSD_FAIL(TSD_E_STATE, "session: upload() before set_seeds() (the seeds belong to one upload)");
+  if (seeds && s->has_noise) TSD_FAIL(TSD_E_STATE, "session: this upload() carried a noise tensor; one source of noise per upload");
+  s->seeded = seeds != nullptr;
+  if (seeds) memcpy(s->seeds, seeds, (size_t)s->B * sizeof(uint64_t));
+  session_latents_changed(s);  // as after add_noise()
+  return TSD_OK;
+}
+extern "C" int tsd_session_seeds_active(tsd_session* s) { return s ? (s->uploaded && s->seeded ? 1 : 0) : TSD_E_ARG; }
+
+// the latents become stream 2 of each sample's seed: what a txt2img caller would have uploaded, drawn on the device.  Asynchronous.
+extern "C" int tsd_session_seed_latents(tsd_session* s) {
+  NOTNULL(s);
+  SESSION_NOT_SLOTS(s, "seed_latents()");
+  if (!s->uploaded || !s->seeded) TSD_FAIL(TSD_E_STATE, "session: upload() and set_seeds() before seed_latents()");
+  HIP_TRY(hipSetDevice(s->ctx->device));
+  const int64_t chw = (int64_t)4 * s->L * s->L;
+  session_latents_changed(s);
+  return launch_fill_normal(s->ctx, s->latents, s->B * chw, chw, session_bases(s, NOISE_STREAM_LATENTS), 0);
+}
+
+// add_noise at index i with stream 4 of each sample's seed instead of a host tensor: the same scalars and the same kernel
+extern "C" int tsd_session_add_noise_seeded(tsd_session* s, int i) {
+  NOTNULL(s);
+  SESSION_NOT_SLOTS(s, "add_noise_seeded()");
+  if (!s->uploaded || !s->seeded) TSD_FAIL(TSD_E_STATE, "session: upload() and set_seeds() before add_noise_seeded()");
+  if (i < 0 || i >= (int)s->timesteps.size()) TSD_FAIL(TSD_E_ARG, "session: step %d out of range", i);
+  tsd_ctx* ctx = s->ctx;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const int64_t chw = (int64_t)4 * s->L * s->L, nl = s->B * chw;
+  TSD_TRY(ctx_reserve_staging(ctx, (size_t)nl * 4));
+  session_latents_changed(s);
+  TSD_TRY(launch_fill_normal(ctx, (float*)ctx->staging, nl, chw, session_bases(s, NOISE_STREAM_ADD), 0));
+  TSD_TRY(session_add_noise(s, i, s->latents, nl, (const float*)ctx->staging));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));  // the staging buffer is the context's again on return, as after add_noise()
+  return TSD_OK;
+}
+
+// set_inpaint and set_inpaint_seeded: `seeded` fills ip_noise with stream 4 of each sample's seed on the device instead of copying `noise`
+static int session_set_inpaint(tsd_session* s, const float* mask, const float* known, const float* noise, bool seeded) {
+  SESSION_NOT_SLOTS(s, "set_inpaint()");
+  if (!s->uploaded) TSD_FAIL(TSD_E_STATE, "session: upload() before set_inpaint() (inpainting belongs to one upload)");
+  if (seeded && mask && !s->seeded) TSD_FAIL(TSD_E_STATE, "session: set_seeds() before set_inpaint_seeded()");
+  tsd_ctx* ctx = s->ctx;
+  const size_t hw = (size_t)s->L * s->L, nm = (size_t)s->B * hw, nl = 4 * nm;
+  if (mask) {  // every refusal comes before the first copy: a refused call leaves the previous mask, tensors and history as they were
+    NOTNULL(known);
+    bool in_range = true;
+    for (size_t k = 0; k < nm; k++) in_range &= (mask[k] >= 0.f) & (mask[k] <= 1.f);  // false for NaN
+    if (!in_range) TSD_FAIL(TSD_E_ARG, "session: every inpainting mask value must be finite and in [0, 1]");
+    if (!host_all_finite(known, nl)) TSD_FAIL(TSD_E_ARG, "session: inf / NaN in the known latents of set_inpaint()");
+    if (noise && !host_all_finite(noise, nl)) TSD_FAIL(TSD_E_ARG, "session: inf / NaN in the noise of set_inpaint()");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(s->ip_mask, mask, nm * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(s->ip_known, known, nl * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (noise) HIP_TRY(hipMemcpyAsync(s->ip_noise, noise, nl * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (seeded) TSD_TRY(launch_fill_normal(ctx, s->ip_noise, (int64_t)nl, (int64_t)(4 * hw), session_bases(s, NOISE_STREAM_ADD), 0));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // the host tensors are the caller's again on return
+  }
+  s->inpaint = mask != nullptr;
+  s->ip_has_noise = mask && (noise || seeded);
+  session_latents_changed(s);  // the steps that follow run on other latents than the history was predicted for: as after add_noise()
+  return TSD_OK;
+}
+extern "C" int tsd_session_set_inpaint(tsd_session* s, const float* mask, const float* known, const float* noise) {
+  NOTNULL(s);
+  return session_set_inpaint(s, mask, known, noise, false);
+}
+extern "C" int tsd_session_set_inpaint_seeded(tsd_session* s, const float* mask, const float* known) {
+  NOTNULL(s);
+  return session_set_inpaint(s, mask, known, nullptr, true);
+}
+extern "C" int tsd_session_inpaint_active(tsd_session* s) { return s ? (s->uploaded && s->inpaint ? 1 : 0) : TSD_E_ARG; }
+
+extern "C" int tsd_session_decode(tsd_session* s) {
+  NOTNULL(s);
+  SESSION_NOT_SLOTS(s, "decode()");
+  if (!s->dec) TSD_FAIL(TSD_E_STATE, "session: created without a decoder");
+  if (!s->uploaded) TSD_FAIL(TSD_E_STATE, "session: upload() before decode()");
+  SESSION_NOT_POISONED(s);
+  TSD_TRY(session_options_unchanged(s, "upload()"));
+  s->ctx->arena.top = 0;
+  int r = g_decoder_forward(s->dec, s->latents, s->B, s->L, s->images);
+  s->ctx->arena.top = 0;
+  if (r == TSD_OK) s->decoded = true;
+  return r;
+}
+
+extern "C" int tsd_session_download_latents(tsd_session* s, float* latents) {
+  NOTNULL(s); NOTNULL(latents);
+  SESSION_NOT_SLOTS(s, "download_latents()");
+  if (!s->uploaded) TSD_FAIL(TSD_E_STATE, "session: upload() before download_latents() (the state is not defined yet)");
+  return session_fetch_latents(s, s->latents, (size_t)s->B * 4 * s->L * s->L, latents);
+}
+
+extern "C" int tsd_session_download_images(tsd_session* s, int rescale_0_255, float* images) {
+  NOTNULL(s); NOTNULL(images);
+  SESSION_NOT_SLOTS(s, "download_images()");
+  if (!s->dec) TSD_FAIL(TSD_E_STATE, "session: created without a decoder");
+  if (!s->decoded) TSD_FAIL(TSD_E_STATE, "session: decode() before download_images() (no image has been computed since upload())");
+  tsd_ctx* ctx = s->ctx;
+  const int64_t n = (int64_t)s->B * 3 * 64 * s->L * s->L;
+  const float* src = s->images;
+  if (rescale_0_255) {  // pipeline.mojo:127
+    TSD_TRY(ctx_reserve_staging(ctx, (size_t)n * 4));
+    TSD_TRY(launch_unary_f32(ctx, 2, s->images, n, (float*)ctx->staging));
+    src = (const float*)ctx->staging;
+  }
+  HIP_TRY(hipMemcpyAsync(images, src, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  const int r = ctx_check_status(ctx);
+  if (r != TSD_OK) return r;
+  SESSION_NOT_POISONED(s);
+  // a non-finite IMAGE is reported, it does not poison latents that may be fine (decode again after the cause is removed)
+  if (!host_all_finite(images, (size_t)n)) TSD_FAIL(TSD_E_NONFINITE, "session: inf / NaN in the decoded images");
+  return TSD_OK;
+}
+
+// ---- slot sessions: the body of `pipeline.generate`'s loop (pipeline.mojo:86-124), per sample ---------------------------------------
+// Every sample of the session is a slot with its own request (context, seed, guidance scale) and its own index into the session's
+// timestep list.  advance() runs ONE forward over all Bu samples and one update launch whose per-sample table gives each active slot
+// the step of its own index; a finished slot is refilled by slot_start while the others keep going.  What the lockstep step() passes
+// as scalars for the whole batch is the same plan (session_plan) taken per slot, and applied by the same per-element functions
+// (update_element.h): a slot's latents are bit for bit those of a lockstep session of the same batch shape running its request.
+extern "C" int tsd_session_slots_open(tsd_session* s) {
+  NOTNULL(s);
+  tsd_ctx* ctx = s->ctx;
+  HIP_TRY(hipSetDevice(ctx->device));
+  const int B = s->B, L = s->L, Bu = s->cfg ? 2 * B : B;
+  s->slots = false;
+  s->has_noise = false;
+  // idle slots ride through every forward: zero latents and a zero context keep them finite
+  HIP_TRY(hipMemsetAsync(s->latents, 0, (size_t)B * 4 * L * L * 4, ctx->stream));
+  HIP_TRY(hipMemsetAsync(s->ctx16, 0, (size_t)Bu * s->Tp * 768 * 2, ctx->stream));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  if (ctx->opt.session_hoist)  // the per-sample time rows of an advance: sized by the session's shape alone
+    TSD_TRY(session_grow((void**)&s->trows, &s->trows_cap, (size_t)Bu * s->unet->unet.tproj.N * 4, "time rows"));
+  TSD_TRY(session_prepare(s));  // the planning pass and the hoist buffers of upload(); K / V^T of the zero context, the whole time table
+  s->uploaded = false;          // the lockstep entry points stay closed
+  for (int b = 0; b < 16; b++) s->slot[b] = tsd_session::Slot();
+  s->slots = true;
+  return TSD_OK;
+}
+
+extern "C" int tsd_session_slot_start(tsd_session* s, int b, const float* context, const float* uncond_context, const float* latents,
+                                      int noise_at_start, uint64_t seed, int start_index, float cfg_scale) {
+  NOTNULL(s); NOTNULL(context);
+  SESSION_IN_SLOTS(s);
+  SESSION_NOT_POISONED(s);
+  tsd_ctx* ctx = s->ctx;
+  const int B = s->B, L = s->L, T = s->T, Tp = s->Tp;
+  const size_t chw = (size_t)4 * L * L, nc = (size_t)T * 768;
+  // every refusal comes before the first copy: a refused call leaves the slot, and everyone else's, as it was
+  if (b < 0 || b >= B) TSD_FAIL(TSD_E_ARG, "session: slot %d out of range (0..%d)", b, B - 1);
+  if (start_index < 0 || start_index >= (int)s->timesteps.size())
+    TSD_FAIL(TSD_E_ARG, "session: start index %d out of range (0..%d)", start_index, (int)s->timesteps.size() - 1);
+  if (s->cfg && !uncond_context) TSD_FAIL(TSD_E_ARG, "session: a slot of a CFG session needs uncond_context");
+  if (!host_all_finite(&cfg_scale, 1)) TSD_FAIL(TSD_E_ARG, "session: cfg_scale of slot_start() is not finite");
+  if (!host_all_finite(context, nc)) TSD_FAIL(TSD_E_ARG, "session: inf / NaN in the context of slot_start()");
+  if (s->cfg && !host_all_finite(uncond_context, nc)) TSD_FAIL(TSD_E_ARG, "session: inf / NaN in the uncond_context of slot_start()");
+  if (latents && !host_all_finite(latents, chw)) TSD_FAIL(TSD_E_ARG, "session: inf / NaN in the latents of slot_start()");
+  HIP_TRY(hipSetDevice(ctx->device));
+  TSD_TRY(ctx_reserve_staging(ctx, std::max(nc, chw) * 4));
+  tsd_session::Slot& sl = s->slot[b];
+  sl.state = 0;  // until the request is in place
+  // context rows b and B + b: upload()'s conversion, one sample
+  for (int part = 0; part < (s->cfg ? 2 : 1); part++)
+    TSD_TRY(session_put_context(s, part == 0 ? context : uncond_context, (size_t)part * B + b, 1));
+  // Under the hoist only this sample's K / V^T change: the forward's own projection at batch 1, into the sample's region.  The GEMM's
+  // summation tree keys on the layer, never on the batch (gemm_plan.cpp), so these are the bits of the all-sample build.  After a
+  // parameter change the next advance() rebuilds every sample from ctx16, this one included.
+  if (s->hoist && s->model_gen == s->unet->gen) {
+    const int CK = s->unet->unet.kproj_all.N;
+    for (int part = 0; part < (s->cfg ? 2 : 1); part++) {
+      const size_t row = (size_t)part * B + b;
+      ctx->arena.top = 0;
+      TSD_TRY(g_unet_ctx_kv(s->unet, s->ctx16 + row * Tp * 768, Tp, 1, s->kc_all + row * Tp * CK, s->vtc_all + row * CK * Tp));
+    }
+    ctx->arena.top = 0;
+  }
+  float* lat = s->latents + (size_t)b * chw;
+  NormalBases nb = {};
+  if (!latents) {  // seed_latents()' rule for one sample: stream 2 of the seed
+    nb.base[0] = counter_rng_base(seed, NOISE_STREAM_LATENTS);
+    TSD_TRY(launch_fill_normal(ctx, lat, (int64_t)chw, (int64_t)chw, nb, 0));
+  } else {
+    HIP_TRY(hipMemcpyAsync(lat, latents, chw * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (noise_at_start) {  // add_noise_seeded(start_index) on this slot: stream 4 of the seed, the same scalars, the same kernel
+      nb.base[0] = counter_rng_base(seed, NOISE_STREAM_ADD);
+      TSD_TRY(launch_fill_normal(ctx, (float*)ctx->staging, (int64_t)chw, (int64_t)chw, nb, 0));
+      TSD_TRY(session_add_noise(s, start_index, lat, (int64_t)chw, (const float*)ctx->staging));
+    }
+  }
+  HIP_TRY(hipStreamSynchronize(ctx->stream));  // the host tensors and the staging buffer are free again on return
+  sl.index = start_index; sl.cfg_scale = cfg_scale; sl.seed = seed;
+  sl.hist_valid = false;
+  sl.state = 1;
+  return TSD_OK;
+}
+
+// Entry b of the update table for an active slot at index i: the plan of step i, plus the slot's guidance scale and the base of its noise
+static int slot_entry(const tsd_session* s, const tsd_session::Slot& sl, SlotEntry* e, uint64_t* base) {
+  e->cfg_scale = sl.cfg_scale;
+  *base = counter_rng_base(sl.seed, NOISE_STREAM_STEP0 + (uint64_t)sl.index);
+  return session_plan(s, sl.index, sl.hist_valid, e);
+}
+
+extern "C" int tsd_session_advance(tsd_session* s, uint32_t* finished_mask) {
+  NOTNULL(s);
+  SESSION_IN_SLOTS(s);
+  SESSION_NOT_POISONED(s);
+  TSD_TRY(session_options_unchanged(s, "slots_open()"));
+  tsd_ctx* ctx = s->ctx;
+  const int B = s->B, L = s->L, Bu = s->cfg ? 2 * B : B, n = (int)s->timesteps.size();
+  const size_t nl = (size_t)B * 4 * L * L;
+  int active = 0;
+  for (int b = 0; b < B; b++) active += s->slot[b].state == 1;
+  if (!active) TSD_FAIL(TSD_E_STATE, "session: advance() with no active slot");
+  TSD_TRY(session_refresh(s));
+  // the update table, built before anything is enqueued: the per-slot scalars travel as kernel arguments
+  SlotTable tab = {};
+  for (int b = 0; b < B; b++)
+    if (s->slot[b].state == 1) TSD_TRY(slot_entry(s, s->slot[b], &tab.e[b], &tab.bases.base[b]));
+  // per-sample time rows (cond and uncond halves alike); an idle or finished slot reads entry 0
+  UNetPre pre;
+  if (s->hoist) {
+    SlotRows rows = {};
+    for (int b = 0; b < Bu; b++) rows.row[b] = s->slot[b % B].state == 1 ? s->slot[b % B].index : 0;
+    const int N = s->unet->unet.tproj.N;
+    TSD_TRY(launch_slot_time_rows(ctx, s->ttab, N, rows, Bu, s->trows));
+    pre.tvec = s->trows; pre.tld = N; pre.kc_all = s->kc_all; pre.vtc_all = s->vtc_all;
+  } else {
+    SlotTimes ts = {};
+    for (int b = 0; b < Bu; b++) ts.t[b] = (float)s->timesteps[s->slot[b % B].state == 1 ? s->slot[b % B].index : 0];
+    TSD_TRY(launch_slot_timesteps(ctx, ts, Bu, s->tdev));
+    TSD_TRY(launch_time_embedding(ctx, s->tdev, 0.f, Bu, s->temb));
+  }
+  int eps_hw = 0;
+  TSD_TRY(session_forward(s, &pre, &eps_hw));
+  TSD_TRY(launch_slot_update(ctx, s->latents, s->eps, s->cfg ? s->eps + nl : nullptr, s->hist, tab, B, (int64_t)4 * L * L, eps_hw));
+  uint32_t done = 0;
+  for (int b = 0; b < B; b++) {
+    tsd_session::Slot& sl = s->slot[b];
+    if (sl.state != 1) continue;
+    sl.hist_valid = (tab.e[b].flags & SLOT_HIST_OUT) != 0;
+    if (++sl.index >= n) { sl.state = 2; done |= 1u << b; }
+  }
+  if (finished_mask) *finished_mask = done;
+  return TSD_OK;
+}
+
+extern "C" int tsd_session_slot_state(tsd_session* s, int b, int* index, int* state) {
+  NOTNULL(s);
+  SESSION_IN_SLOTS(s);
+  if (b < 0 || b >= s->B) TSD_FAIL(TSD_E_ARG, "session: slot %d out of range (0..%d)", b, s->B - 1);
+  if (index) *index = s->slot[b].index;
+  if (state) *state = s->slot[b].state;
+  return TSD_OK;
+}
+
+extern "C" int tsd_session_slot_download(tsd_session* s, int b, float* latents) {
+  NOTNULL(s); NOTNULL(latents);
+  SESSION_IN_SLOTS(s);
+  if (b < 0 || b >= s->B) TSD_FAIL(TSD_E_ARG, "session: slot %d out of range (0..%d)", b, s->B - 1);
+  if (s->slot[b].state == 0) TSD_FAIL(TSD_E_STATE, "session: slot %d is idle (no request has defined its latents)", b);
+  const size_t chw = (size_t)4 * s->L * s->L;
+  return session_fetch_latents(s, s->latents + (size_t)b * chw, chw, latents);  // download_latents()' check, on this slot's buffer alone
+}
+
+extern "C" int tsd_session_slots_active(tsd_session* s) {
+  if (!s) return TSD_E_ARG;
+  int n = 0;
+  if (s->slots)
+    for (int b = 0; b < s->B; b++) n += s->slot[b].state == 1;
+  return n;
+}
+
+// the raw latent buffer [B,4,L,L], whatever the mode and the slot states, unchecked: lets a test see that an idle slot is never written
+extern "C" int tsd_debug_session_latents(tsd_session* s, float* latents) {
+  NOTNULL(s); NOTNULL(latents);
+  HIP_TRY(hipSetDevice(s->ctx->device));
+  HIP_TRY(hipMemcpyAsync(latents, s->latents, (size_t)s->B * 4 * s->L * s->L * 4, hipMemcpyDeviceToHost, s->ctx->stream));
+  HIP_TRY(hipStreamSynchronize(s->ctx->stream));
+  return TSD_OK;
+}

@@ -14,8 +14,8 @@ SEED = 1234
 N_TRAIN, STEPS = 1000, 4
 B, L, T = 3, 8, 77
 CHW = 4 * L * L
-SAMPLERS = [("ddpm", 0.0, "leading"), ("ddim", 0.5, "trailing"), ("dpmpp_2m", 0.0, "trailing")]
-IDS = [s[0] for s in SAMPLERS]
+SAMPLERS = [("ddpm", 0.0, "leading"), ("ddim", 0.5, "trailing"), ("dpmpp_2m", 0.0, "trailing"), ("ddpm", 0.0, "trailing")]
+IDS = ["ddpm", "ddim", "dpmpp_2m", "ddpm_trailing"]  # the last: DDPM's previous timestep from the list, the final step onto -1 with noise
 SCALES = (7.5, 3.0, 1.0)
 K_PROJ, T_PROJ = "unet.layer3.layer6.k_proj.weight", "unet.layer2.layer3.weight"
 
