@@ -401,7 +401,8 @@ int tsd_session_download_images(tsd_session* s, int rescale_0_255, float* images
  * DDPMSampler.step), per sample.  All slots share the session's sampler, spacing and timestep list.  Noise is always the seeded noise
  * above: streams 2 / 4 / 16 + i of the slot's seed.  A slot's latents are bit for bit those of a lockstep session of the same B running
  * the same request in the same sample position (upload + set_seeds + seed_latents | add_noise_seeded + step start_index..n-1).
- * Inpainting in slots is out of scope: set_inpaint* are refused in slot mode.
+ * Inpainting is per slot: tsd_session_slot_set_inpaint gives one request a mask and known latents, and the update launch of an advance
+ * blends them in (no extra launch); the lockstep set_inpaint* stay refused in slot mode.
  * A session that never calls slots_open enqueues exactly the launches, and computes the bits, it did before. */
 /* Enter slot mode, after set_sampler / set_schedule and in place of upload(): sizes the workspace and the hoisted buffers by upload()'s
  * planning pass, zeroes the latents and the context, marks all B slots idle.  upload(), set_schedule and set_sampler leave slot mode.
@@ -426,6 +427,18 @@ int tsd_session_slot_start(tsd_session* s, int b, const float* context, const fl
 int tsd_session_advance(tsd_session* s, uint32_t* finished_mask);
 /* *index = the slot's next schedule index (num_steps when done), *state = 0 idle, 1 active, 2 done; either may be NULL. */
 int tsd_session_slot_state(tsd_session* s, int b, int* index, int* state);
+/* Masked denoising for the request of ACTIVE slot b - right after slot_start, or mid-flight: mask [L,L] in [0,1] (1 = regenerate, 0 = keep)
+ * and known [4,L,L], the original latents, are copied into sample b's region of the session's inpainting buffers; the noise they are
+ * re-noised with is stream 4 of the slot's seed, filled on the device - the values tsd_session_set_inpaint_seeded fills for that sample
+ * and slot_start(noise_at_start) adds.  From then on the update of every advance holds the slot's known region at the timestep ITS step
+ * reaches (entry i_b + 1 of the list, the clean sample after the last), inside the update kernel: an advance with inpainting slots
+ * enqueues the launches of one without.  The slot's latents are bit for bit sample b of a lockstep session running set_inpaint_seeded with
+ * this mask.  mask == NULL turns the slot's inpainting off.  Either way the slot's DPM-Solver++(2M) history is dropped.  slot_start and
+ * slots_open turn it off: a refilled slot never inherits a mask.  Synchronous.  Every refusal comes before the first copy and leaves all
+ * slots as they were: TSD_E_ARG for b out of range, a mask value that is not finite or not in [0, 1], a missing `known`, inf / NaN in
+ * `known`; TSD_E_STATE outside slot mode and on an idle or done slot.  Other slots' buffers are never written. */
+int tsd_session_slot_set_inpaint(tsd_session* s, int b, const float* mask, const float* known);
+int tsd_session_slot_inpaint_active(tsd_session* s, int b); /* 1 / 0; < 0 on error (NULL session, outside slot mode, b out of range) */
 /* One slot's latents [4,L,L] (synchronises).  TSD_E_STATE on an idle slot.  tsd_session_download_latents' finite check, on that slot's
  * buffer only: inf / NaN there returns TSD_E_NONFINITE and latches the session until slots_open() or upload(). */
 int tsd_session_slot_download(tsd_session* s, int b, float* latents);

@@ -423,6 +423,22 @@ struct SlotTable {
 // launch_ddpm_step (eps_hw > 0: [B][eps_hw][4]); chw = 4 * hw elements per sample
 int launch_slot_update(tsd_ctx* ctx, float* x, const float* eps, const float* eps_uncond, float* hist, const SlotTable& tab, int B,
                        int64_t chw, int eps_hw);
+// The same update with the masked-denoising blend of launch_inpaint_blend applied before the store, per slot: entry b of a second by-value
+// table holds the blend's scalars for sample b (a_prev, s_prev of the timestep ITS update reaches) and whether it blends at all.
+// 16 * 16 = 256 bytes beside the 768 of SlotTable: 1104 bytes of explicit arguments with the pointers and scalars, a kernel argument
+// segment of 1360 bytes with the hidden ones (limit 4 KiB).
+// mask [B][hw], known / noise [B][4][hw] are read for `on` entries only; an entry that is off stores what launch_slot_update stores.
+struct SlotBlend {
+  int on;
+  float a_prev, s_prev;
+  int pad_;
+};
+struct SlotBlendTable {
+  SlotBlend e[16];
+};
+int launch_slot_update_blend(tsd_ctx* ctx, float* x, const float* eps, const float* eps_uncond, float* hist, const SlotTable& tab,
+                             const SlotBlendTable& blend, const float* mask, const float* known, const float* noise, int B, int64_t chw,
+                             int eps_hw);
 // rows of the hoisted time table for samples at different schedule indices: out[b][0..N) = ttab[row[b]][0..N), b < Bu <= 16
 struct SlotRows {
   int row[16];

@@ -79,6 +79,7 @@ struct tsd_session {
     float cfg_scale = 7.5f;
     uint64_t seed = 0;
     bool hist_valid = false;  // `hist` of this sample holds the x0 of the slot's previous step (DPM-Solver++(2M))
+    bool inpaint = false;     // slot_set_inpaint: sample b of ip_mask / ip_known / ip_noise is this request's; off after slot_start
   } slot[16];
   float* trows = nullptr;     // [Bu][tproj.N] fp32: row i_b of ttab per sample, gathered by every advance (own allocation, grown at slots_open)
   size_t trows_cap = 0;
@@ -412,14 +413,20 @@ static NormalBases session_bases(const tsd_session* s, uint64_t stream) {
 // noised to the timestep the update has just reached - entry i + 1 of the list, the clean sample (1, 0) after the last entry; under
 // LEADING spacing that entry is the reference's t - N // n.  a_prev = sqrt(abar), s_prev = sqrt(1 - abar) in double from the fp32 table,
 // rounded to float once: what tsd_sampler_coeffs reports as out[2], out[3] for step i + 1.  The same rule for all three samplers.
-static int session_inpaint_blend(tsd_session* s, int i) {
-  double a_prev = 1.0, s_prev = 0.0;
+// session_blend_scalars is that rule, for the lockstep launch and for every slot of an advance (the slot's own index).
+static void session_blend_scalars(const tsd_session* s, int i, float* a_prev, float* s_prev) {
+  double a = 1.0, sg = 0.0;
   if (i + 1 < (int)s->timesteps.size()) {
     const double abar = s->alphas_cumprod[s->timesteps[i + 1]];
-    a_prev = sqrt(abar); s_prev = sqrt(1.0 - abar);
+    a = sqrt(abar); sg = sqrt(1.0 - abar);
   }
+  *a_prev = (float)a; *s_prev = (float)sg;
+}
+static int session_inpaint_blend(tsd_session* s, int i) {
+  float a_prev, s_prev;
+  session_blend_scalars(s, i, &a_prev, &s_prev);
   return launch_inpaint_blend(s->ctx, s->latents, s->ip_mask, s->ip_known, s->ip_has_noise ? s->ip_noise : nullptr, s->B,
-                              (int64_t)s->L * s->L, (float)a_prev, (float)s_prev, s->latents);
+                              (int64_t)s->L * s->L, a_prev, s_prev, s->latents);
 }
 
 extern "C" int tsd_session_step(tsd_session* s, int i) {
@@ -647,6 +654,7 @@ extern "C" int tsd_session_slot_start(tsd_session* s, int b, const float* contex
   TSD_TRY(ctx_reserve_staging(ctx, std::max(nc, chw) * 4));
   tsd_session::Slot& sl = s->slot[b];
   sl.state = 0;  // until the request is in place
+  sl.inpaint = false;  // a refilled slot never inherits the previous request's mask
   // context rows b and B + b: upload()'s conversion, one sample
   for (int part = 0; part < (s->cfg ? 2 : 1); part++)
     TSD_TRY(session_put_context(s, part == 0 ? context : uncond_context, (size_t)part * B + b, 1));
@@ -682,6 +690,43 @@ extern "C" int tsd_session_slot_start(tsd_session* s, int b, const float* contex
   return TSD_OK;
 }
 
+// Inpainting for the request of ACTIVE slot b, right after slot_start or mid-flight: what set_inpaint_seeded does for sample b of a
+// lockstep session, on this sample's regions of the three buffers alone.  mask [L][L], known [4][L][L]; the noise is stream 4 of the slot's
+// seed, the values slot_start(noise_at_start) added.  mask == NULL turns it off.  Either way the slot's history is dropped, as set_inpaint
+// drops the session's.  Every refusal comes before the first copy and leaves all slots as they were.  Synchronous.
+extern "C" int tsd_session_slot_set_inpaint(tsd_session* s, int b, const float* mask, const float* known) {
+  NOTNULL(s);
+  SESSION_IN_SLOTS(s);
+  if (b < 0 || b >= s->B) TSD_FAIL(TSD_E_ARG, "session: slot %d out of range (0..%d)", b, s->B - 1);
+  tsd_session::Slot& sl = s->slot[b];
+  if (sl.state != 1) TSD_FAIL(TSD_E_STATE, "session: slot %d is %s; slot_set_inpaint() belongs to an active request", b, sl.state ? "done" : "idle");
+  tsd_ctx* ctx = s->ctx;
+  const size_t hw = (size_t)s->L * s->L, chw = 4 * hw;
+  if (mask) {
+    NOTNULL(known);
+    bool in_range = true;
+    for (size_t k = 0; k < hw; k++) in_range &= (mask[k] >= 0.f) & (mask[k] <= 1.f);  // false for NaN
+    if (!in_range) TSD_FAIL(TSD_E_ARG, "session: every inpainting mask value must be finite and in [0, 1]");
+    if (!host_all_finite(known, chw)) TSD_FAIL(TSD_E_ARG, "session: inf / NaN in the known latents of slot_set_inpaint()");
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(s->ip_mask + (size_t)b * hw, mask, hw * 4, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(s->ip_known + (size_t)b * chw, known, chw * 4, hipMemcpyHostToDevice, ctx->stream));
+    NormalBases nb = {};
+    nb.base[0] = counter_rng_base(sl.seed, NOISE_STREAM_ADD);
+    TSD_TRY(launch_fill_normal(ctx, s->ip_noise + (size_t)b * chw, (int64_t)chw, (int64_t)chw, nb, 0));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));  // the host tensors are the caller's again on return
+  }
+  sl.inpaint = mask != nullptr;
+  sl.hist_valid = false;  // the steps that follow run on other latents than the history was predicted for
+  return TSD_OK;
+}
+extern "C" int tsd_session_slot_inpaint_active(tsd_session* s, int b) {
+  NOTNULL(s);
+  SESSION_IN_SLOTS(s);
+  if (b < 0 || b >= s->B) TSD_FAIL(TSD_E_ARG, "session: slot %d out of range (0..%d)", b, s->B - 1);
+  return s->slot[b].state == 1 && s->slot[b].inpaint ? 1 : 0;
+}
+
 // Entry b of the update table for an active slot at index i: the plan of step i, plus the slot's guidance scale and the base of its noise
 static int slot_entry(const tsd_session* s, const tsd_session::Slot& sl, SlotEntry* e, uint64_t* base) {
   e->cfg_scale = sl.cfg_scale;
@@ -705,6 +750,16 @@ extern "C" int tsd_session_advance(tsd_session* s, uint32_t* finished_mask) {
   SlotTable tab = {};
   for (int b = 0; b < B; b++)
     if (s->slot[b].state == 1) TSD_TRY(slot_entry(s, s->slot[b], &tab.e[b], &tab.bases.base[b]));
+  // the blend table: an inpainting slot holds its known region at the timestep ITS update reaches (session_blend_scalars at its index)
+  SlotBlendTable blend = {};
+  bool blending = false;
+  for (int b = 0; b < B; b++) {
+    const tsd_session::Slot& sl = s->slot[b];
+    if (sl.state != 1 || !sl.inpaint) continue;
+    blend.e[b].on = 1;
+    session_blend_scalars(s, sl.index, &blend.e[b].a_prev, &blend.e[b].s_prev);
+    blending = true;
+  }
   // per-sample time rows (cond and uncond halves alike); an idle or finished slot reads entry 0
   UNetPre pre;
   if (s->hoist) {
@@ -721,7 +776,13 @@ extern "C" int tsd_session_advance(tsd_session* s, uint32_t* finished_mask) {
   }
   int eps_hw = 0;
   TSD_TRY(session_forward(s, &pre, &eps_hw));
-  TSD_TRY(launch_slot_update(ctx, s->latents, s->eps, s->cfg ? s->eps + nl : nullptr, s->hist, tab, B, (int64_t)4 * L * L, eps_hw));
+  // the update launch: with an inpainting slot among the active ones, the kernel that also blends (no further launch either way)
+  const float* eps_u = s->cfg ? s->eps + nl : nullptr;
+  if (blending)
+    TSD_TRY(launch_slot_update_blend(ctx, s->latents, s->eps, eps_u, s->hist, tab, blend, s->ip_mask, s->ip_known, s->ip_noise, B,
+                                     (int64_t)4 * L * L, eps_hw));
+  else
+    TSD_TRY(launch_slot_update(ctx, s->latents, s->eps, eps_u, s->hist, tab, B, (int64_t)4 * L * L, eps_hw));
   uint32_t done = 0;
   for (int b = 0; b < B; b++) {
     tsd_session::Slot& sl = s->slot[b];

@@ -1,19 +1,59 @@
 // update_element.h - one element of a sampler update, shared by every kernel that applies one: k_ddpm_step / k_ddpm_step_seeded
-// (kernels_elementwise.hip), k_sampler_step / k_sampler_step_seeded (kernels_sampler.hip) and k_slot_update (kernels_slots.hip).  The
-// lockstep kernels and the per-slot kernel inline the SAME function, so a slot's update gives the bits of the lockstep step it stands for.
+// (kernels_elementwise.hip), k_sampler_step / k_sampler_step_seeded (kernels_sampler.hip) and k_slot_update / k_slot_update_blend
+// (kernels_slots.hip).  The lockstep kernels and the per-slot kernels inline the SAME function, so a slot's update gives the bits of the
+// lockstep step it stands for.
 // Include after common.h.
 #pragma once
 #include "common.h"
+
+// What an element function does with the updated value o between computing and storing it: post(i, o, nbad) returns what is stored at
+// x[i] and adds what it counts as non-finite to nbad.  StoreAsIs, the default, is the update as it always was (the lockstep kernels
+// and k_slot_update).
+struct StoreAsIs {
+  __device__ __forceinline__ float operator()(int64_t, float o, int&) const { return o; }
+};
+// The masked-denoising blend of k_inpaint_blend (kernels_sampler.hip states the formula and why this form) on one sample, applied to the
+// update's value before its single store: the same seven operations in the same order, ONE fp32 rounding each (no fma), so the stored
+// value is bit for bit what the lockstep update launch followed by the lockstep blend launch leaves.  The blended value is counted like
+// the blend launch counts it (the update's own value is counted by the element function, like the update launch does).
+// first = b * chw, the sample's first global element; mask is the SAMPLE's [hw] plane (it serves the 4 channels), known / noise are the
+// whole CHW [B][4][hw] tensors, indexed like x.
+struct InpaintBlend {
+  const float* __restrict__ mask;
+  const float* __restrict__ known;
+  const float* __restrict__ noise;
+  int64_t first, hw;
+  float a_prev, s_prev;
+  __device__ __forceinline__ float operator()(int64_t i, float x, int& nbad) const {
+#pragma clang fp contract(off)
+    // The update's value is final here.  ddpm_step_element leaves contraction to the compiler, which decides per expression tree: without
+    // this fence the blend's operations join the update's tree and the update rounds differently than in the lockstep kernels.
+    asm volatile("" : "+v"(x));
+    int64_t pix = i - first;  // < 4 hw: the channel is peeled off without a division
+    if (pix >= 2 * hw) pix -= 2 * hw;
+    if (pix >= hw) pix -= hw;
+    const float m = mask[pix];
+    const float ka = a_prev * known[i];
+    const float kn = s_prev * noise[i];
+    const float k = ka + kn;
+    const float om = 1.f - m;
+    const float tx = m * x;
+    const float tk = om * k;
+    const float o = tx + tk;
+    nbad += nonfinite_f(o);
+    return o;
+  }
+};
 
 // ---- DDPM update + CFG combine (sampler.mojo:75-109, pipeline.mojo:117-119; App.D K9) ------------
 // eps_hw > 0: eps / eps_u are the UNet output convolution's own layout [B][eps_hw][4] (x and noise stay CHW [B][4][eps_hw])
 // One element of the update.  SEEDED: the noise is drawn where the other flavour reads noise[i] - normal_counter(bases.base[b], j) for element j of
 // sample b (chw elements per sample, counter_rng.h) - and is always added; without it the instantiation is the kernel as it always was.
-template <bool SEEDED>
+template <bool SEEDED, class Post = StoreAsIs>
 __device__ __forceinline__ int ddpm_step_element(int64_t i, float* __restrict__ x, const float* __restrict__ eps,
                                                  const float* __restrict__ eps_u, float cfg_scale, const float* __restrict__ noise,
                                                  const NormalBases& bases, int64_t chw, float sa, float sb, float c_x0, float c_xt,
-                                                 float sigma, int eps_hw) {
+                                                 float sigma, int eps_hw, const Post& post = Post()) {
   int64_t ie = i;
   if (eps_hw > 0) {
     const int64_t bc = i / eps_hw, pix = i - bc * eps_hw, b = bc >> 2;
@@ -33,8 +73,9 @@ __device__ __forceinline__ int ddpm_step_element(int64_t i, float* __restrict__ 
   } else {
     if (noise) o += noise[i] * sigma;
   }
-  x[i] = o;
-  return nonfinite_f(o);  // a non-finite UNet output (fp16 overflow upstream) lands here every step
+  int nbad = nonfinite_f(o);  // a non-finite UNet output (fp16 overflow upstream) lands here every step
+  x[i] = post(i, o, nbad);
+  return nbad;
 }
 
 // ---- linear-multistep update (DDIM, DPM-Solver++(2M); kernels_sampler.hip states the formula) ------------
@@ -46,11 +87,12 @@ __device__ __forceinline__ int ddpm_step_element(int64_t i, float* __restrict__ 
 // x_out may be x and hist_out may be hist_in: element i is read and written by the same thread only.
 // One element of the update.  SEEDED: z is drawn where the other flavour reads noise[i] - normal_counter(bases.base[b], j) for element j of sample b (chw
 // elements per sample, counter_rng.h) - and its term is always added; without it the instantiation is the kernel as it always was.
-template <bool SEEDED>
+template <bool SEEDED, class Post = StoreAsIs>
 __device__ __forceinline__ int sampler_step_element(int64_t i, const float* x, const float* __restrict__ eps,
                                                     const float* __restrict__ eps_u, float cfg_scale, const float* hist_in,
                                                     const float* __restrict__ noise, const NormalBases& bases, int64_t chw,
-                                                    const SamplerCoeffs& c, int eps_hw, float* x_out, float* hist_out) {
+                                                    const SamplerCoeffs& c, int eps_hw, float* x_out, float* hist_out,
+                                                    const Post& post = Post()) {
 #pragma clang fp contract(off)
   int64_t ie = i;
   if (eps_hw > 0) {
@@ -87,6 +129,7 @@ __device__ __forceinline__ int sampler_step_element(int64_t i, const float* x, c
     const float xs = xv - se;
     hist_out[i] = xs / c.alpha_t;
   }
-  x_out[i] = o;
-  return nonfinite_f(o);  // a non-finite UNet output (fp16 overflow upstream) lands here every step
+  int nbad = nonfinite_f(o);  // a non-finite UNet output (fp16 overflow upstream) lands here every step
+  x_out[i] = post(i, o, nbad);
+  return nbad;
 }

@@ -138,6 +138,7 @@ def _declare(l):
         "tsd_session_slots_open": ([vp], i), "tsd_session_slot_start": ([vp, i, fp, fp, fp, i, u64, i, f], i),
         "tsd_session_advance": ([vp, C.POINTER(C.c_uint32)], i), "tsd_session_slot_state": ([vp, i, C.POINTER(i), C.POINTER(i)], i),
         "tsd_session_slot_download": ([vp, i, fp], i), "tsd_session_slots_active": ([vp], i),
+        "tsd_session_slot_set_inpaint": ([vp, i, fp, fp], i), "tsd_session_slot_inpaint_active": ([vp, i], i),
         "tsd_dist_unique_id": ([vp], i), "tsd_dist_init": ([vp, i, i, vp], i),
         "tsd_dist_broadcast_weights": ([vp, i], i), "tsd_dist_finalize": ([vp], i),
         "tsd_dist_comm_count": ([vp, C.POINTER(i)], i),

@@ -300,6 +300,34 @@ class Session:
         check(lib().tsd_session_slot_start(self.h, int(b), ptr(cx), ptr(uc), ptr(la), 1 if noise_at_start else 0, seed, int(start_index),
                                            float(cfg_scale)))
 
+    def slot_set_inpaint(self, b, mask, known=None):
+        """Masked denoising for the request of active slot b: mask (L,L) or (1,L,L) in [0,1], 1 = regenerate and 0 = keep `known`
+        (4,L,L), the original latents, re-noised after every step with stream 4 of the slot's seed.  mask=None turns it off;
+        slot_start() and slots_open() turn it off as well."""
+        if mask is None:
+            check(lib().tsd_session_slot_set_inpaint(self.h, int(b), None, None))
+            return
+        L = self.L
+        m = f32(mask)
+        if m.shape == (1, L, L):
+            m = np.ascontiguousarray(m[0])
+        if m.shape != (L, L):
+            raise ValueError(f"mask must have shape {(L, L)} or {(1, L, L)}, got {m.shape}")
+        if known is None:
+            raise ValueError("slot_set_inpaint with a mask needs the known latents")
+        kn = f32(known)
+        if kn.shape == (1, 4, L, L):
+            kn = np.ascontiguousarray(kn[0])
+        if kn.shape != (4, L, L):
+            raise ValueError(f"known must have shape {(4, L, L)}, got {kn.shape}")
+        check(lib().tsd_session_slot_set_inpaint(self.h, int(b), ptr(m), ptr(kn)))
+
+    def slot_inpaint_active(self, b):
+        r = lib().tsd_session_slot_inpaint_active(self.h, int(b))
+        if r < 0:
+            check(r)
+        return r == 1
+
     def advance(self):
         """One tick: one forward over all slots, every active slot one step further.  Returns the slots that finished (ascending)."""
         mask = C.c_uint32(0)

@@ -5,8 +5,8 @@ A `Session` in slot mode (`Session.slots_open`) gives every sample of its batch 
 each free slot takes the next request, a slot that finishes yields its latents and is free again.  A request that arrives while the
 others are at step 3 of 50 starts at once; img2img requests of different strength - different start indices - share the batch.
 
-The scheduler only calls the slot methods (`B`, `num_steps`, `slot_start`, `advance`, `slot_latents`), so it runs against any object that
-has them (tests/test_slots_cpu.py drives it without a GPU).
+The scheduler only calls the slot methods (`B`, `L`, `num_steps`, `slot_start`, `slot_set_inpaint`, `advance`, `slot_latents`), so it runs
+against any object that has them (tests/test_slots_cpu.py and tests/test_slot_inpaint_cpu.py drive it without a GPU).
 """
 from collections import namedtuple
 
@@ -14,8 +14,29 @@ import numpy as np
 
 # One request.  latents None: txt2img from `seed`.  latents (4,L,L) with strength s in [0,1]: img2img by the rule of `generate`
 # (sampler.mojo:68-70) - the first n - int(n * s) steps are skipped and the latents are noised to that timestep from `seed`.
-Request = namedtuple("Request", "id context uncond seed cfg_scale latents strength")
-Request.__new__.__defaults__ = (None, 0, 7.5, None, None)
+# mask: inpainting - `latents` are the known latents and the mask says where to regenerate (1) and where to keep them (0): a latent mask
+# (L,L) / (1,L,L) is used as given, a pixel mask (8L,8L) / (1,8L,8L) goes through `tsd.utils.latent_mask` with `mask_mode`.
+Request = namedtuple("Request", "id context uncond seed cfg_scale latents strength mask mask_mode")
+Request.__new__.__defaults__ = (None, 0, 7.5, None, None, None, "any")
+
+
+def request_latent_mask(r, session):
+    """The latent mask (L,L) float32 of request r for `session` (its L, its context for a pixel mask), or None without a mask.
+    ValueError for a mask without latents or of another shape."""
+    if r.mask is None:
+        return None
+    if r.latents is None:
+        raise ValueError(f"request {r.id!r}: a mask needs `latents`, the known latents it keeps")
+    L, ctx = session.L, getattr(session, "ctx", None)
+    m = np.ascontiguousarray(r.mask, dtype=np.float32)
+    if m.ndim == 3 and m.shape[0] == 1:
+        m = m[0]
+    if m.shape == (L, L):
+        return np.ascontiguousarray(m)
+    if m.shape == (8 * L, 8 * L):
+        from . import utils
+        return np.ascontiguousarray(utils.latent_mask(m[None], r.mask_mode, ctx=ctx)[0])
+    raise ValueError(f"request {r.id!r}: mask must have shape {(L, L)} or {(8 * L, 8 * L)} (with or without a leading 1), got {np.shape(r.mask)}")
 
 
 def start_index(num_steps, strength):
@@ -58,12 +79,16 @@ class SlotScheduler:
                     break
                 if not isinstance(r, Request):
                     r = Request(*r)
+                # a request that cannot run raises here, before its slot (or any other) is touched
+                mask = request_latent_mask(r, self.session)
                 i0 = start_index(self.n, r.strength if r.latents is not None else None)
                 if i0 >= self.n:  # strength 0: the image as it is
                     passed.append((r.id, np.asarray(r.latents, dtype=np.float32)))
                     continue
                 self.session.slot_start(b, r.context, r.uncond, latents=r.latents, noise_at_start=r.latents is not None, seed=r.seed,
                                         start_index=i0, cfg_scale=r.cfg_scale)
+                if mask is not None:
+                    self.session.slot_set_inpaint(b, mask, r.latents)
                 self.owner[b] = r.id
         return passed
 
@@ -88,6 +113,7 @@ def generate_stream(diffusion, decoder, requests, B, L, T=77, cfg=True, inferenc
     (3,8L,8L) in [0,255]) - or (id, latents) with return_latents or without a decoder - as requests finish, B at a time on the device.
     A txt2img request gives what `generate(..., seeds=[...])` gives for it in the same sample position.  An img2img request indexes the
     FULL timestep list (its step i draws stream 16 + i of its seed), where `generate` drops the skipped entries and counts from 0.
+    A request with a `mask` is inpainted in its slot (`Session.slot_set_inpaint`) next to the others: no drain, no extra launch.
     Finished latents are decoded through `decoder.forward`, one image per call.  `stats`, a dict, receives advances / active_ticks / occupancy when the stream ends."""
     from .model import Session
     from .utils import _unary
