@@ -658,6 +658,54 @@ enum tsd_chain_info { TSD_CI_CHANGED = 0, TSD_CI_RAN, TSD_CI_COUNT };
  * returned even when the launch is refused (its status is the return value). */
 int tsd_debug_chain_run(tsd_ctx* ctx, const int64_t* desc, int n, const void* const* host_in, void* const* host_out, int64_t* ext,
                         int64_t* info);
+/* ---- elementwise / layout / packing launch descriptors (test infrastructure: tests/elem_ref.py holds the time path, the activations,
+ * the boundary conversions and the packers of csrc/kernels_elementwise.hip to an fp64 reference, element-wise) ----
+ * One descriptor is one launch of the launch_* function its MODE names; the other fields are that function's arguments (unused ones 0).
+ * Pitches in elements, SCALE and T_BITS the bits of a float.  Per mode (X, W, BIAS: inputs; Y: output):
+ *   SMALL_LINEAR      launch_small_linear: X fp32 [B][LDX], W fp16 [N][LDW], BIAS fp32 [N] (HAS_BIAS) -> Y fp32 [B][LDY]; K, SILU
+ *   TIME_EMBEDDING    launch_time_embedding: X fp32 [B] (HAS_T; else the scalar T_BITS for every row) -> Y fp32 [B][320]
+ *   GEGLU_ERF         launch_geglu_erf_f16: X fp16 [ROWS][2 COLS] ((a, gate) interleaved) -> Y fp16 [ROWS][COLS]
+ *   QUICK_GELU        launch_quick_gelu_f16: X fp16 [N], in place (Y starts as X)
+ *   UNARY             launch_unary_f32: OP 0 silu, 1 gelu-tanh, 2 to-pixel; X fp32 [N] -> Y fp32 [N]
+ *   CLIP_EMBED        launch_clip_embed: X int32 tokens [B T], W fp16 table [V][D], BIAS fp32 positions [T][D] -> Y fp16 [B T][D]
+ *   CHW_TO_NHWC       launch_chw_f32_to_nhwc_f16: X fp32 [B][C][H W] -> Y fp16 [B H W][CDST]; CUSE, SCALE
+ *   IM2COL3X3         launch_chw_f32_to_im2col3x3_f16: X fp32 [B][C][H W] -> Y fp16 [B H W][64]; SCALE
+ *   NHWC_TO_CHW       launch_nhwc_f16_to_chw_f32 (DTYPE 1) / launch_nhwc_f32_to_chw_f32 (DTYPE 0): X [B H W][LD] -> Y fp32 [B][C][H W]
+ *   F32_TO_F16_ROWS   launch_f32_to_f16_rows: X fp32 [ROWS][COLS] -> Y fp16 [ROWS_DST][LD], zero padded
+ *   F16_TO_F32_ROWS   launch_f16_to_f32_rows: X fp16 [ROWS][LD] -> Y fp32 [ROWS][COLS]
+ *   TRANSPOSE_TO_F16  launch_transpose_f32_to_f16: X fp32 [B][K][N] -> Y fp16 [B][NPAD][KPAD]
+ *   PACK_CONV         launch_pack_conv: X fp32 [O][I][KSIZE][KSIZE] -> Y fp16 [OPAD][KSIZE KSIZE][IPAD]
+ *   PACK_LINEAR       launch_pack_linear: X fp32 [N][K] -> Y fp16 [N][KPAD]; INTERLEAVE
+ *   PACK_BIAS         launch_pack_bias: X fp32 [N] -> Y fp32 [NPAD]; INTERLEAVE
+ *   PACK_IM2COL_W     launch_pack_im2col_w: X fp16 [O][9][IPAD] -> Y fp16 [O][64]; C
+ *   ENCODER_SAMPLE    launch_encoder_sample: X fp32 moments [B][HW][LD], W fp32 noise [B][4][HW] -> Y fp32 [B][4][HW] */
+enum tsd_elem_desc_field {
+  TSD_ED_VERSION = 0, TSD_ED_MODE, TSD_ED_B, TSD_ED_K, TSD_ED_N, TSD_ED_LDX, TSD_ED_LDW, TSD_ED_LDY, TSD_ED_SILU, TSD_ED_HAS_BIAS,
+  TSD_ED_HAS_T, TSD_ED_T_BITS, TSD_ED_ROWS, TSD_ED_COLS, TSD_ED_OP, TSD_ED_T, TSD_ED_V, TSD_ED_D,
+  TSD_ED_C, TSD_ED_H, TSD_ED_W, TSD_ED_HW, TSD_ED_CUSE, TSD_ED_CDST, TSD_ED_SCALE, TSD_ED_DTYPE, TSD_ED_LD, TSD_ED_ROWS_DST,
+  TSD_ED_KPAD, TSD_ED_NPAD, TSD_ED_O, TSD_ED_I, TSD_ED_KSIZE, TSD_ED_OPAD, TSD_ED_IPAD, TSD_ED_INTERLEAVE,
+  TSD_ED_COUNT
+};
+#define TSD_ED_VERSION_1 1
+enum tsd_elem_mode {
+  TSD_EM_SMALL_LINEAR = 0, TSD_EM_TIME_EMBEDDING, TSD_EM_GEGLU_ERF, TSD_EM_QUICK_GELU, TSD_EM_UNARY, TSD_EM_CLIP_EMBED,
+  TSD_EM_CHW_TO_NHWC, TSD_EM_IM2COL3X3, TSD_EM_NHWC_TO_CHW, TSD_EM_F32_TO_F16_ROWS, TSD_EM_F16_TO_F32_ROWS, TSD_EM_TRANSPOSE_TO_F16,
+  TSD_EM_PACK_CONV, TSD_EM_PACK_LINEAR, TSD_EM_PACK_BIAS, TSD_EM_PACK_IM2COL_W, TSD_EM_ENCODER_SAMPLE, TSD_EM_COUNT
+};
+/* Operand slots: inputs X, W, BIAS; output Y.  Elements are 2 or 4 bytes as the mode states (token ids: int32 in a 4-byte slot). */
+enum tsd_elem_operand { TSD_EO_X = 0, TSD_EO_W, TSD_EO_BIAS, TSD_EO_Y, TSD_EO_COUNT };
+/* info: guard / pitch-gap elements the launch changed; the change of the context's non-finite count across the launch (the count is
+ * cleared afterwards, as tsd_debug_nonfinite_count(ctx, 1) does); SMALL_LINEAR: the k_small_linear<NB> instance that ran and its K
+ * passes (0 when the launch was refused). */
+enum tsd_elem_info { TSD_EI_CHANGED = 0, TSD_EI_NONFINITE, TSD_EI_NB, TSD_EI_PASSES, TSD_EI_COUNT };
+/* Run the launch described by desc (n >= TSD_ED_COUNT fields) on caller operands in their device layout (host_in[TSD_EO_X .. TSD_EO_BIAS],
+ * NULL for unused slots) and return its output (host_out[0]).  host_in == NULL only sizes (ctx may be NULL, no device is touched):
+ * ext[TSD_EO_COUNT] receives every slot's extent (0 = unused).  A descriptor that cannot be sized is refused before any launch; what the
+ * launchers refuse (B > 16, K % 8, misaligned pitches, B K beyond the LDS, widths that are no multiple of their vector) is sized and left
+ * to them.  Every operand sits between 4 KiB guard bands of a NaN pattern and Y is pre-filled with it (QUICK_GELU: with X); the output is
+ * returned even when the launch is refused (its status is the return value). */
+int tsd_debug_elem_run(tsd_ctx* ctx, const int64_t* desc, int n, const void* const* host_in, void* const* host_out, int64_t* ext,
+                       int64_t* info);
 /* GroupNorm launches enqueued on this context since the last reset, per statistics path: counts[0] all, [1] own statistics pass,
  * [2] one producer table finished inside the apply blocks, [3] one producer table finished by the k_gn_finalize launch,
  * [4] k_gn_prereduce, [5] composite accepted, [6] k_gn_finalize launches (any source), [7] composites offered.  n >= 8; reset != 0

@@ -1,6 +1,6 @@
 // api_replay.cpp - the replay entries: one launch of a kernel family, described by an int64 descriptor, run on caller operands in
-// their device layout so that tests can hold it to an fp64 reference element-wise (tsd_debug_gemm_run / _norm_run / _attn_run / _chain_run,
-// and the recording of the GEMM descriptors the product's graphs launch).  Test infrastructure, not the measured path.  What the four
+// their device layout so that tests can hold it to an fp64 reference element-wise (tsd_debug_gemm_run / _norm_run / _attn_run / _chain_run /
+// _elem_run, and the recording of the GEMM descriptors the product's graphs launch).  Test infrastructure, not the measured path.  What the five
 // entries share - the guarded device operands, the scan for writes outside an output's logical elements (replay_scan.h), the slot
 // checks and the scoped option overrides - is written once here; sizing, marshalling and the reported plan stay with each family.
 #include <string.h>
@@ -697,5 +697,194 @@ extern "C" int tsd_debug_chain_run(tsd_ctx* ctx, const int64_t* desc, int n, con
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   info[TSD_CI_RAN] = ran ? 1 : 0;
   TSD_TRY(ops.read_back(&info[TSD_CI_CHANGED]));
+  return r;
+}
+
+// ---- time path / activations / layout conversions / packers on caller operands (tests/elem_ref.py holds each to an fp64 reference) ----
+namespace {
+int ed_elem_bytes(int mode, int slot, const int64_t* d) {
+  const bool y = slot == TSD_EO_Y;
+  switch (mode) {
+    case TSD_EM_SMALL_LINEAR: return slot == TSD_EO_W ? 2 : 4;
+    case TSD_EM_GEGLU_ERF: case TSD_EM_QUICK_GELU: case TSD_EM_PACK_IM2COL_W: return 2;
+    case TSD_EM_CLIP_EMBED: return slot == TSD_EO_W || y ? 2 : 4;
+    case TSD_EM_CHW_TO_NHWC: case TSD_EM_IM2COL3X3: case TSD_EM_F32_TO_F16_ROWS: case TSD_EM_TRANSPOSE_TO_F16: case TSD_EM_PACK_CONV:
+    case TSD_EM_PACK_LINEAR: return y ? 2 : 4;
+    case TSD_EM_NHWC_TO_CHW: return !y && d[TSD_ED_DTYPE] == 1 ? 2 : 4;
+    case TSD_EM_F16_TO_F32_ROWS: return y ? 4 : 2;
+    default: return 4;  // TIME_EMBEDDING, UNARY, PACK_BIAS, ENCODER_SAMPLE
+  }
+}
+// Element extent of every operand the described launch reads or writes, and the output's logical elements.  Refuses what it cannot size;
+// the shapes the launchers themselves refuse are sized and left to them.
+int ed_extents(const int64_t* d, int64_t* e, replay::Box* box) {
+  for (int i = 0; i < TSD_EO_COUNT; i++) e[i] = 0;
+#define ED_REQ(cond) \
+  if (!(cond)) TSD_FAIL(TSD_E_ARG, "elem_run: descriptor cannot be sized (%s)", #cond)
+  ED_REQ(d[TSD_ED_VERSION] == TSD_ED_VERSION_1);
+  const int64_t mode = d[TSD_ED_MODE], lim = 1LL << 26, dim = 1 << 20;
+  ED_REQ(mode >= 0 && mode < TSD_EM_COUNT);
+  for (int f = TSD_ED_B; f < TSD_ED_COUNT; f++)
+    if (f != TSD_ED_SCALE && f != TSD_ED_T_BITS) ED_REQ(d[f] >= 0 && d[f] <= (f == TSD_ED_N ? lim : dim));
+  for (int f : {TSD_ED_SILU, TSD_ED_HAS_BIAS, TSD_ED_HAS_T, TSD_ED_INTERLEAVE, TSD_ED_DTYPE}) ED_REQ(d[f] == 0 || d[f] == 1);
+  const int64_t B = d[TSD_ED_B], K = d[TSD_ED_K], N = d[TSD_ED_N], C = d[TSD_ED_C], HW = d[TSD_ED_H] * d[TSD_ED_W];
+  const int64_t rows = d[TSD_ED_ROWS], cols = d[TSD_ED_COLS], ld = d[TSD_ED_LD];
+  int64_t &x = e[TSD_EO_X], &w = e[TSD_EO_W], &bias = e[TSD_EO_BIAS], &y = e[TSD_EO_Y];
+  *box = replay::Box();
+  switch (mode) {
+    case TSD_EM_SMALL_LINEAR:
+      ED_REQ(B > 0 && B <= 64 && K > 0 && K <= 65536 && N > 0 && N <= 65536);
+      ED_REQ(d[TSD_ED_LDX] >= K && d[TSD_ED_LDW] >= K && d[TSD_ED_LDY] >= N);
+      x = (B - 1) * d[TSD_ED_LDX] + K; w = (N - 1) * d[TSD_ED_LDW] + K; bias = d[TSD_ED_HAS_BIAS] ? N : 0;
+      y = (B - 1) * d[TSD_ED_LDY] + N;
+      *box = replay::Box{1, 0, B, d[TSD_ED_LDY], N};
+      break;
+    case TSD_EM_TIME_EMBEDDING:
+      ED_REQ(B > 0 && B <= 4096);
+      x = d[TSD_ED_HAS_T] ? B : 0; y = B * 320;
+      break;
+    case TSD_EM_GEGLU_ERF:
+      ED_REQ(rows > 0 && cols > 0);
+      x = rows * 2 * cols; y = rows * cols;
+      break;
+    case TSD_EM_QUICK_GELU:
+      ED_REQ(N > 0);
+      x = y = N;
+      break;
+    case TSD_EM_UNARY:
+      ED_REQ(N > 0 && d[TSD_ED_OP] <= 2);
+      x = y = N;
+      break;
+    case TSD_EM_CLIP_EMBED:
+      ED_REQ(B > 0 && d[TSD_ED_T] > 0 && d[TSD_ED_V] > 0 && d[TSD_ED_D] > 0 && B * d[TSD_ED_T] <= dim);
+      x = B * d[TSD_ED_T]; w = d[TSD_ED_V] * d[TSD_ED_D]; bias = d[TSD_ED_T] * d[TSD_ED_D]; y = x * d[TSD_ED_D];
+      break;
+    case TSD_EM_CHW_TO_NHWC:
+      ED_REQ(B > 0 && C > 0 && HW > 0 && HW <= lim && d[TSD_ED_CUSE] <= C && d[TSD_ED_CDST] > 0);
+      x = B * C * HW; y = B * HW * d[TSD_ED_CDST];
+      break;
+    case TSD_EM_IM2COL3X3:
+      ED_REQ(B > 0 && C > 0 && HW > 0 && HW <= lim);
+      x = B * C * HW; y = B * HW * 64;
+      break;
+    case TSD_EM_NHWC_TO_CHW:
+      ED_REQ(B > 0 && C > 0 && HW > 0 && HW <= lim && B * HW <= lim && ld >= C);
+      x = (B * HW - 1) * ld + C; y = B * C * HW;
+      break;
+    case TSD_EM_F32_TO_F16_ROWS:
+      ED_REQ(rows > 0 && cols > 0 && ld >= cols && d[TSD_ED_ROWS_DST] >= rows);
+      x = rows * cols; y = d[TSD_ED_ROWS_DST] * ld;
+      break;
+    case TSD_EM_F16_TO_F32_ROWS:
+      ED_REQ(rows > 0 && cols > 0 && ld >= cols);
+      x = (rows - 1) * ld + cols; y = rows * cols;
+      break;
+    case TSD_EM_TRANSPOSE_TO_F16:
+      ED_REQ(B > 0 && B <= 4096 && K > 0 && K <= 65536 && N > 0 && N <= 65536 && d[TSD_ED_KPAD] >= K && d[TSD_ED_NPAD] >= N && d[TSD_ED_KPAD] <= 65536 &&
+             d[TSD_ED_NPAD] <= 65536);
+      x = B * K * N; y = B * d[TSD_ED_NPAD] * d[TSD_ED_KPAD];
+      break;
+    case TSD_EM_PACK_CONV: {
+      const int64_t O = d[TSD_ED_O], I = d[TSD_ED_I], k = d[TSD_ED_KSIZE];
+      ED_REQ(O > 0 && O <= 65536 && I > 0 && I <= 65536 && k > 0 && k <= 7 && d[TSD_ED_OPAD] >= O && d[TSD_ED_OPAD] <= 65536 && d[TSD_ED_IPAD] >= I &&
+             d[TSD_ED_IPAD] <= 65536);
+      x = O * I * k * k; y = d[TSD_ED_OPAD] * k * k * d[TSD_ED_IPAD];
+      break;
+    }
+    case TSD_EM_PACK_LINEAR:
+      ED_REQ(N > 0 && N <= 65536 && K > 0 && K <= 65536 && d[TSD_ED_KPAD] >= K && d[TSD_ED_KPAD] <= 65536 && (!d[TSD_ED_INTERLEAVE] || N % 2 == 0));
+      x = N * K; y = N * d[TSD_ED_KPAD];
+      break;
+    case TSD_EM_PACK_BIAS:
+      ED_REQ(N > 0 && N <= dim && d[TSD_ED_NPAD] >= N && (!d[TSD_ED_INTERLEAVE] || N % 2 == 0));
+      x = N; y = d[TSD_ED_NPAD];
+      break;
+    case TSD_EM_PACK_IM2COL_W:
+      ED_REQ(d[TSD_ED_O] > 0 && d[TSD_ED_O] <= 65536 && d[TSD_ED_IPAD] > 0 && d[TSD_ED_IPAD] <= 65536 && C > 0);
+      x = d[TSD_ED_O] * 9 * d[TSD_ED_IPAD]; y = d[TSD_ED_O] * 64;
+      break;
+    default: {  // TSD_EM_ENCODER_SAMPLE
+      const int64_t hw = d[TSD_ED_HW];
+      ED_REQ(B > 0 && B <= 4096 && hw > 0 && B * hw <= lim && ld >= 8);
+      x = (B * hw - 1) * ld + 8; w = y = B * 4 * hw;
+      break;
+    }
+  }
+  if (mode != TSD_EM_SMALL_LINEAR) *box = replay::Box::dense(y);
+  for (int s = 0; s < TSD_EO_COUNT; s++) ED_REQ(e[s] >= 0 && e[s] <= lim);
+#undef ED_REQ
+  return TSD_OK;
+}
+}  // namespace
+
+extern "C" int tsd_debug_elem_run(tsd_ctx* ctx, const int64_t* desc, int n, const void* const* host_in, void* const* host_out, int64_t* ext,
+                                  int64_t* info) {
+  NOTNULL(desc); NOTNULL(ext);
+  TSD_TRY(check_fields("elem_run", n, TSD_ED_COUNT));
+  replay::Box logical;
+  TSD_TRY(ed_extents(desc, ext, &logical));
+  const int64_t* d = desc;
+  if (info) for (int i = 0; i < TSD_EI_COUNT; i++) info[i] = 0;
+  if (!host_in) return TSD_OK;  // sizing only: no context or device needed
+  NOTNULL(ctx); NOTNULL(host_out); NOTNULL(info);
+  TSD_TRY(check_slots("elem_run", ext, TSD_EO_COUNT, TSD_EO_Y, host_in, host_out));
+  HIP_TRY(hipSetDevice(ctx->device));
+  const int mode = (int)d[TSD_ED_MODE];
+  GuardedOperands ops(ctx, TSD_EO_COUNT);
+  for (int s = 0; s < TSD_EO_Y; s++)
+    if (ext[s]) TSD_TRY(ops.add(s, ext[s], ed_elem_bytes(mode, s, d), host_in[s]));
+  // quick-GELU overwrites its rows in place: Y starts as X
+  TSD_TRY(ops.add(TSD_EO_Y, ext[TSD_EO_Y], ed_elem_bytes(mode, TSD_EO_Y, d), mode == TSD_EM_QUICK_GELU ? host_in[TSD_EO_X] : nullptr, host_out[0], logical));
+  int bad0 = 0, bad1 = 0;
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  HIP_TRY(hipMemcpy(&bad0, ctx->status, sizeof(int), hipMemcpyDeviceToHost));
+  ctx->sl_last = SmallLinearPlan();
+  const int B = (int)d[TSD_ED_B], K = (int)d[TSD_ED_K], C = (int)d[TSD_ED_C], H = (int)d[TSD_ED_H], W = (int)d[TSD_ED_W];
+  const int64_t N = d[TSD_ED_N], rows = d[TSD_ED_ROWS];
+  const int cols = (int)d[TSD_ED_COLS], ld = (int)d[TSD_ED_LD], inter = (int)d[TSD_ED_INTERLEAVE];
+  const float scale = f32_of(d[TSD_ED_SCALE]);
+  const void* x = ops.at(TSD_EO_X);
+  const void* w = ops.at(TSD_EO_W);
+  const void* bias = ops.at(TSD_EO_BIAS);
+  void* y = ops.at(TSD_EO_Y);
+  const int r = run_planned(ctx, [&]() -> int {
+    switch (mode) {
+      case TSD_EM_SMALL_LINEAR:
+        return launch_small_linear(ctx, (const float*)x, B, K, (int)d[TSD_ED_LDX], (const half_t*)w, (int)d[TSD_ED_LDW], (const float*)bias, (int)N,
+                                   (int)d[TSD_ED_SILU], (float*)y, (int)d[TSD_ED_LDY]);
+      case TSD_EM_TIME_EMBEDDING: return launch_time_embedding(ctx, (const float*)x, f32_of(d[TSD_ED_T_BITS]), B, (float*)y);
+      case TSD_EM_GEGLU_ERF: return launch_geglu_erf_f16(ctx, (const half_t*)x, rows, cols, (half_t*)y);
+      case TSD_EM_QUICK_GELU: return launch_quick_gelu_f16(ctx, (half_t*)y, N);
+      case TSD_EM_UNARY: return launch_unary_f32(ctx, (int)d[TSD_ED_OP], (const float*)x, N, (float*)y);
+      case TSD_EM_CLIP_EMBED:
+        return launch_clip_embed(ctx, (const int*)x, (const half_t*)w, (int)d[TSD_ED_V], (int)d[TSD_ED_D], (const float*)bias, B, (int)d[TSD_ED_T], (half_t*)y);
+      case TSD_EM_CHW_TO_NHWC:
+        return launch_chw_f32_to_nhwc_f16(ctx, (const float*)x, B, C, H, W, (int)d[TSD_ED_CUSE], scale, (half_t*)y, (int)d[TSD_ED_CDST]);
+      case TSD_EM_IM2COL3X3: return launch_chw_f32_to_im2col3x3_f16(ctx, (const float*)x, B, C, H, W, (half_t*)y, scale);
+      case TSD_EM_NHWC_TO_CHW:
+        return d[TSD_ED_DTYPE] == 1 ? launch_nhwc_f16_to_chw_f32(ctx, (const half_t*)x, B, C, H, W, ld, (float*)y)
+                                    : launch_nhwc_f32_to_chw_f32(ctx, (const float*)x, B, C, H, W, ld, (float*)y);
+      case TSD_EM_F32_TO_F16_ROWS: return launch_f32_to_f16_rows(ctx, (const float*)x, rows, cols, (half_t*)y, ld, d[TSD_ED_ROWS_DST]);
+      case TSD_EM_F16_TO_F32_ROWS: return launch_f16_to_f32_rows(ctx, (const half_t*)x, rows, cols, ld, (float*)y);
+      case TSD_EM_TRANSPOSE_TO_F16:
+        return launch_transpose_f32_to_f16(ctx, (const float*)x, B, K, (int)N, (half_t*)y, (int)d[TSD_ED_KPAD], (int)d[TSD_ED_NPAD]);
+      case TSD_EM_PACK_CONV:
+        return launch_pack_conv(ctx, (const float*)x, (int)d[TSD_ED_O], (int)d[TSD_ED_I], (int)d[TSD_ED_KSIZE], (half_t*)y, (int)d[TSD_ED_OPAD],
+                                (int)d[TSD_ED_IPAD]);
+      case TSD_EM_PACK_LINEAR: return launch_pack_linear(ctx, (const float*)x, (int)N, K, (half_t*)y, (int)d[TSD_ED_KPAD], inter);
+      case TSD_EM_PACK_BIAS: return launch_pack_bias(ctx, (const float*)x, (int)N, (float*)y, (int)d[TSD_ED_NPAD], inter);
+      case TSD_EM_PACK_IM2COL_W: return launch_pack_im2col_w(ctx, (const half_t*)x, (int)d[TSD_ED_O], (int)d[TSD_ED_IPAD], C, (half_t*)y);
+      default: return launch_encoder_sample(ctx, (const float*)x, B, (int)d[TSD_ED_HW], ld, (const float*)w, (float*)y);
+    }
+  });
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  HIP_TRY(hipMemcpy(&bad1, ctx->status, sizeof(int), hipMemcpyDeviceToHost));
+  if (bad1) {  // counted, not reported: the context stays usable
+    const int zero = 0;
+    HIP_TRY(hipMemcpy(ctx->status, &zero, sizeof(int), hipMemcpyHostToDevice));
+  }
+  info[TSD_EI_NONFINITE] = bad1 - bad0;
+  info[TSD_EI_NB] = ctx->sl_last.nb; info[TSD_EI_PASSES] = ctx->sl_last.passes;
+  TSD_TRY(ops.read_back(&info[TSD_EI_CHANGED]));
   return r;
 }

@@ -113,6 +113,11 @@ struct AttnPlan {
   int softmax = 0;
 };
 AttnPlan attn_plan(const TsdOptions& opt, int B, int H, int d, int Sq, int Sk);
+// What launch_small_linear launched (kernels_elementwise.hip), left in tsd_ctx::sl_last; tsd_debug_elem_run reports it.
+struct SmallLinearPlan {
+  int nb = 0;      // the k_small_linear<NB> instance: 1, 2, 4, 8 or 16; 0 = none ran
+  int passes = 0;  // K passes of 128 * SL_KIT columns
+};
 
 // Host-side plan of one GEMM / conv3x3 launch (gemm_plan.cpp): the tile configuration (a row of gemm_tiles.h) that runs, in how many
 // split-K slices, as which conv variant - what fixes the fp32 summation tree of the launch.  launch_gemm acts on it and leaves it in
@@ -166,6 +171,7 @@ struct tsd_ctx {
   GnPlan gn_last;             // plan of the last GroupNorm launch enqueued (tsd_debug_norm_run)
   int64_t gn_paths[8] = {};   // tsd_debug_gn_path_counts
   AttnPlan attn_last;         // plan of the last attention-core / row-softmax launch enqueued (tsd_debug_attn_run)
+  SmallLinearPlan sl_last;    // the last tiny-M linear launch enqueued (tsd_debug_elem_run)
 };
 
 enum KernelClass : int {

@@ -554,26 +554,27 @@ __global__ __launch_bounds__(256) void k_small_linear(const float* __restrict__ 
 int launch_small_linear(tsd_ctx* ctx, const float* x, int B, int K, int ldx, const half_t* w, int ldw, const float* bias,
                         int N, int silu_in, float* y, int ldy) {
   if (B > SL_MAXB) TSD_FAIL(TSD_E_SHAPE, "small_linear: B=%d > %d", B, SL_MAXB);
-  if (K % 8 || ldx % 4) TSD_FAIL(TSD_E_SHAPE, "small_linear: K=%d must be a multiple of 8 (ldx=%d of 4)", K, ldx);
+  if (K % 8 || ldx % 4 || ldw % 8) TSD_FAIL(TSD_E_SHAPE, "small_linear: K=%d must be a multiple of 8 (ldx=%d of 4, ldw=%d of 8)", K, ldx, ldw);
   if (!ctx->launch()) return TSD_OK;
   ProfScope prof(ctx, KC_SMALL_LINEAR, B, N, K, 1);
   const size_t lds = (size_t)B * K * sizeof(float);
   if (lds > 160 * 1024) TSD_FAIL(TSD_E_SHAPE, "small_linear: B*K too large for LDS");
   static std::atomic<unsigned long long> attr_set[5];  // per DEVICE: the attribute is stored per device (one bit each); zero-initialised
   const int slot = B <= 1 ? 0 : B <= 2 ? 1 : B <= 4 ? 2 : B <= 8 ? 3 : 4;
-  auto launch = [&](auto fn) -> int {
+  auto launch = [&](auto fn, int nb) -> int {
     if (!((attr_set[slot].load(std::memory_order_relaxed) >> (ctx->device & 63)) & 1)) {
       HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       attr_set[slot].fetch_or(1ull << (ctx->device & 63), std::memory_order_relaxed);
     }
     hipLaunchKernelGGL(fn, dim3(ceil_div(N, 16)), dim3(256), lds, ctx->stream, x, B, K, ldx, w, ldw, bias, N, silu_in, y, ldy);
+    ctx->sl_last.nb = nb; ctx->sl_last.passes = ceil_div(K, 128 * SL_KIT);
     return TSD_OK;
   };
-  if (B <= 1) TSD_TRY(launch(k_small_linear<1>));
-  else if (B <= 2) TSD_TRY(launch(k_small_linear<2>));
-  else if (B <= 4) TSD_TRY(launch(k_small_linear<4>));
-  else if (B <= 8) TSD_TRY(launch(k_small_linear<8>));
-  else TSD_TRY(launch(k_small_linear<16>));
+  if (B <= 1) TSD_TRY(launch(k_small_linear<1>, 1));
+  else if (B <= 2) TSD_TRY(launch(k_small_linear<2>, 2));
+  else if (B <= 4) TSD_TRY(launch(k_small_linear<4>, 4));
+  else if (B <= 8) TSD_TRY(launch(k_small_linear<8>, 8));
+  else TSD_TRY(launch(k_small_linear<16>, 16));
   HIP_TRY(hipGetLastError());
   return TSD_OK;
 }

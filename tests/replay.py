@@ -1,5 +1,5 @@
-"""What the tests of the replay entries (tsd_debug_gemm_run, tsd_debug_norm_run, tsd_debug_attn_run, tsd_debug_chain_run:
-csrc/api_replay.cpp) share: the
+"""What the tests of the five replay entries (tsd_debug_gemm_run, tsd_debug_norm_run, tsd_debug_attn_run, tsd_debug_chain_run,
+tsd_debug_elem_run: csrc/api_replay.cpp) share: the
 fill patterns of the guarded operands, the enum reader of include/tsd.h, the sizing-only call, the run on caller operands, and the two
 statements about an output's bytes that every family makes (a refused launch wrote nothing; the pitch gaps still hold the fill)."""
 import ctypes as C
@@ -106,9 +106,12 @@ def assert_untouched(outs, what):
 
 
 def assert_gaps_hold_fill(out, logical_index, what):
-    """The elements of the fp16 output that are no logical element still hold the fill."""
+    """The elements of the fp16 (or fp32) output that are no logical element still hold the fill."""
     gap = np.ones(out.size, bool)
     gap[np.asarray(logical_index).ravel()] = False
+    if out.dtype == np.float32:
+        assert (out.view(np.uint32)[gap] == NAN32.view(np.uint32)).all(), f"{what}: a pitch gap was written"
+        return
     assert (out.view(np.uint16)[gap] == NAN16.view(np.uint16)).all(), f"{what}: a pitch gap was written"
 
 
