@@ -304,6 +304,28 @@ int tsd_sampler_coeffs(int kind, double eta, int spacing, int n_train, int n_inf
  * noise and hist_out may be NULL (the term / the output is skipped).  x_out and hist_out may alias nothing. */
 int tsd_sampler_step_f32(tsd_ctx* ctx, const float* x, const float* eps, const float* eps_uncond, float cfg_scale,
                          const float* hist, const float* noise, int64_t n, const float* c, float* x_out, float* hist_out);
+/* Op level, host fp32 in/out, synchronous: the update of step i of a DDPM session with this schedule (spacing, n_train, n_infer,
+ * start_step as in tsd_sampler_coeffs) on n elements - the kernel and the fp32 scalars of `DDPMSampler.step` the session launches.
+ * eps_uncond and noise may be NULL; like the session, the noise is added only on a step that does not land on t = 0. */
+int tsd_ddpm_step_f32(tsd_ctx* ctx, const float* x, const float* eps, const float* eps_uncond, float cfg_scale, const float* noise,
+                      int64_t n, int spacing, int n_train, int n_infer, int start_step, int i, float* x_out);
+
+/* ---- guidance rescale (EXTENSION: the reference combines cond and uncond with a fixed formula, pipeline.mojo:117-119) ----------
+ * Lin et al. 2023, "Common Diffusion Noise Schedules and Sample Steps are Flawed", eq. 15-16 (diffusers: guidance_rescale).  Per
+ * sample, with c the conditional and u the unconditional eps, n = 4*L*L elements, s the guidance scale and phi in [0, 1]:
+ *     e_i   = (c_i - u_i) * s + u_i                      the update's own combine: three fp32 roundings
+ *     var_c = sum c^2 / n - (sum c / n)^2, var_e likewise over e                 sums and moments in fp64
+ *     g     = phi * sqrt(var_c / var_e) + (1 - phi)      in fp64, rounded once to fp32
+ *     c'_i  = g * c_i,  u'_i = g * u_i                   one fp32 rounding each
+ * and the sampler update then runs on c', u' unchanged: its combine gives g * e up to rounding, and the DPM-Solver++(2M) history is the
+ * x0 of the rescaled prediction.  g = 1 exactly (the sample passes through) when var_e is not finite, var_e <= 0 or var_c is not
+ * finite; a var_c below zero counts as zero.  A sample's g is bitwise the same run to run, at every B and in every position of the
+ * batch.  phi = 0 leaves a sample unread and unwritten. */
+/* Op level, host fp32 in/out, synchronous: eps / eps_uncond / the outputs [B][chw], cfg_scale [B], phi [B], g_out [B] or NULL (1 for a
+ * sample with phi = 0).  The outputs may be the inputs.  TSD_E_SHAPE for B outside 1..16 or chw <= 0; TSD_E_ARG for a phi that is not
+ * finite or outside [0, 1] and for a cfg_scale that is not finite.  Non-finite inputs are not counted here (the update counts them). */
+int tsd_cfg_rescale_f32(tsd_ctx* ctx, const float* eps, const float* eps_uncond, int B, int64_t chw, const float* cfg_scale,
+                        const float* phi, float* eps_out, float* eps_uncond_out, float* g_out);
 
 /* ---- masked denoising / inpainting (EXTENSION: the reference has txt2img and img2img only) ---------------------------------
  * The classic 4-channel inpainting: after each sampler update the known region of the latents is replaced by the original
@@ -389,6 +411,15 @@ int tsd_session_add_noise_seeded(tsd_session* s, int i);
  * buffer on the device.  Validation and state rules are set_inpaint's; TSD_E_STATE for a mask without seeds.  mask == NULL turns
  * inpainting off. */
 int tsd_session_set_inpaint_seeded(tsd_session* s, const float* mask, const float* known);
+/* Guidance rescale (see "guidance rescale" above) for the steps of the current upload, one phi for the batch; 0 turns it off.  While
+ * phi > 0, step(i) enqueues two short launches between the forward and the sampler update that scale every sample's cond and uncond
+ * eps in place by its g - no host-to-device copy, no allocation, no synchronisation - with all three samplers, with or without seeds,
+ * inpainting and the hoist.  It belongs to one upload: TSD_E_STATE before tsd_session_upload and on a session created with cfg = 0;
+ * upload(), set_schedule and set_sampler turn it off.  TSD_E_ARG for a phi that is not finite or outside [0, 1].  It touches neither
+ * the latents, the history nor the decoded images.  With phi = 0, or never called, a session enqueues exactly the launches, and
+ * computes the bits, it did before. */
+int tsd_session_set_guidance_rescale(tsd_session* s, float phi);
+int tsd_session_guidance_rescale(tsd_session* s, float* phi); /* *phi = the value in force (0 = off, also before upload()) */
 int tsd_session_decode(tsd_session* s); /* Decoder.forward on the current latents (async) */
 int tsd_session_download_latents(tsd_session* s, float* latents);
 int tsd_session_download_images(tsd_session* s, int rescale_0_255, float* images);
@@ -439,6 +470,14 @@ int tsd_session_slot_state(tsd_session* s, int b, int* index, int* state);
  * `known`; TSD_E_STATE outside slot mode and on an idle or done slot.  Other slots' buffers are never written. */
 int tsd_session_slot_set_inpaint(tsd_session* s, int b, const float* mask, const float* known);
 int tsd_session_slot_inpaint_active(tsd_session* s, int b); /* 1 / 0; < 0 on error (NULL session, outside slot mode, b out of range) */
+/* Guidance rescale for the request of ACTIVE slot b, per request like cfg_scale: an advance with some active slot at phi > 0 enqueues
+ * the two launches of tsd_session_set_guidance_rescale with a per-sample table; idle and done slots and slots at phi = 0 are neither
+ * read nor written by them, and an advance with no such slot enqueues what it always did.  The slot's latents are bit for bit sample b
+ * of a lockstep session running its request with the same phi.  slot_start and slots_open clear it: a refilled slot never inherits
+ * it.  TSD_E_ARG for b out of range and a phi that is not finite or outside [0, 1]; TSD_E_STATE outside slot mode, on an idle or done
+ * slot and on a session created with cfg = 0.  The latents and the history are not touched. */
+int tsd_session_slot_set_guidance_rescale(tsd_session* s, int b, float phi);
+int tsd_session_slot_guidance_rescale(tsd_session* s, int b, float* phi); /* *phi = the active slot's value, 0 otherwise */
 /* One slot's latents [4,L,L] (synchronises).  TSD_E_STATE on an idle slot.  tsd_session_download_latents' finite check, on that slot's
  * buffer only: inf / NaN there returns TSD_E_NONFINITE and latches the session until slots_open() or upload(). */
 int tsd_session_slot_download(tsd_session* s, int b, float* latents);

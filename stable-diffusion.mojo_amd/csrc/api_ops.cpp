@@ -268,6 +268,61 @@ extern "C" int tsd_sampler_step_f32(tsd_ctx* ctx, const float* x, const float* e
   });
 }
 
+// the update of step i of a DDPM session (kernels_elementwise.hip k_ddpm_step, the scalars of sampler_step_plan) on host tensors;
+// like the session, the noise is added only on a step that does not land on t = 0
+extern "C" int tsd_ddpm_step_f32(tsd_ctx* ctx, const float* x, const float* eps, const float* eps_uncond, float cfg_scale,
+                                 const float* noise, int64_t n, int spacing, int n_train, int n_infer, int start_step, int i,
+                                 float* x_out) {
+  NOTNULL(x); NOTNULL(eps); NOTNULL(x_out);
+  if (n <= 0) TSD_FAIL(TSD_E_SHAPE, "ddpm step: n=%lld", (long long)n);
+  std::vector<int> ts;
+  TSD_TRY(sampler_timesteps(spacing, n_train, n_infer, start_step, ts));
+  std::vector<float> ac;
+  sampler_alphas_cumprod(n_train, ac);
+  SlotEntry p;
+  TSD_TRY(sampler_step_plan(TSD_SAMPLER_DDPM, 0.0, spacing, n_train, n_infer, ac, ts, i, false, &p));
+  return run_op(ctx, [&]() -> int {
+    Dev d{ctx};
+    float* dx = d.in(x, n);
+    float* de = d.in(eps, n);
+    float* du = eps_uncond ? d.in(eps_uncond, n) : nullptr;
+    float* dz = (noise && (p.flags & SLOT_NOISE)) ? d.in(noise, n) : nullptr;
+    if (d.err) return d.err;
+    TSD_TRY(launch_ddpm_step(ctx, dx, de, du, cfg_scale, dz, n, p.c[0], p.c[1], p.c[2], p.c[3], p.c[4], 0));
+    return d.out(x_out, dx, n);
+  });
+}
+
+// guidance rescale (kernels_guidance.hip) on host tensors: the two launches a session with tsd_session_set_guidance_rescale adds to a step
+extern "C" int tsd_cfg_rescale_f32(tsd_ctx* ctx, const float* eps, const float* eps_uncond, int B, int64_t chw, const float* cfg_scale,
+                                   const float* phi, float* eps_out, float* eps_uncond_out, float* g_out) {
+  NOTNULL(eps); NOTNULL(eps_uncond); NOTNULL(cfg_scale); NOTNULL(phi); NOTNULL(eps_out); NOTNULL(eps_uncond_out);
+  if (B <= 0 || B > 16 || chw <= 0) TSD_FAIL(TSD_E_SHAPE, "cfg rescale: B=%d (1..16) chw=%lld", B, (long long)chw);
+  CfgRescaleTable tab = {};
+  for (int b = 0; b < B; b++) {
+    if (!(phi[b] >= 0.f && phi[b] <= 1.f)) TSD_FAIL(TSD_E_ARG, "cfg rescale: phi[%d] = %g is not in [0, 1]", b, (double)phi[b]);
+    if (!(fabsf(cfg_scale[b]) <= 3.4028235e38f)) TSD_FAIL(TSD_E_ARG, "cfg rescale: cfg_scale[%d] is not finite", b);
+    tab.e[b].on = phi[b] > 0.f;
+    tab.e[b].cfg_scale = cfg_scale[b];
+    tab.e[b].phi = phi[b];
+  }
+  const int64_t n = (int64_t)B * chw;
+  float ones[16];
+  for (int b = 0; b < 16; b++) ones[b] = 1.f;
+  return run_op(ctx, [&]() -> int {
+    Dev d{ctx};
+    float* dc = d.in(eps, n);
+    float* du = d.in(eps_uncond, n);
+    float* dg = d.in(ones, B);  // a sample with phi = 0 is not touched: its g stays 1
+    double* part = d.buf<double>(CFG_RESCALE_PARTIAL_DOUBLES);
+    if (d.err) return d.err;
+    TSD_TRY(launch_cfg_rescale(ctx, dc, du, tab, B, chw, part, dg));
+    if (g_out) TSD_TRY(d.out(g_out, dg, B));
+    TSD_TRY(d.out(eps_uncond_out, du, n));
+    return d.out(eps_out, dc, n);
+  });
+}
+
 // N(0,1) of the counter RNG (kernels_sampler.hip k_fill_normal, counter_rng.h) on a host tensor: element e is value offset + e of the
 // stream (seed, stream) - the values a seeded denoise session draws on the device
 extern "C" int tsd_normal_fill_f32(tsd_ctx* ctx, uint64_t seed, uint64_t stream, uint64_t offset, int64_t n, float* out) {

@@ -456,6 +456,23 @@ struct SlotTimes {
 };
 int launch_slot_timesteps(tsd_ctx* ctx, const SlotTimes& t, int Bu, float* tdev);
 
+// ---- guidance rescale (kernels_guidance.hip states the formula): a pre-pass over eps / eps_uncond between the forward and the update ----
+// Entry b of the by-value table: on = 0 leaves sample b unread and unwritten (phi = 0, an idle or finished slot).  256 bytes of arguments.
+struct CfgRescaleEntry {
+  int on;
+  float cfg_scale, phi;
+  int pad_;
+};
+struct CfgRescaleTable {
+  CfgRescaleEntry e[16];
+};
+enum { CFG_RESCALE_GMAX = 64, CFG_RESCALE_PARTIAL_DOUBLES = 16 * CFG_RESCALE_GMAX * 4 };  // partial [B <= 16][G <= 64][4] fp64: 32 KiB
+int cfg_rescale_blocks(int64_t chw);  // G: partials (and blocks) per sample, a function of chw alone
+// eps / eps_uncond [B][chw] in place (either eps layout: a sample's chw floats are contiguous in both); partial: CFG_RESCALE_PARTIAL_DOUBLES
+// doubles of scratch; g_out [B] or nullptr, written for `on` entries only.  Two launches, no copy, no synchronisation.
+int launch_cfg_rescale(tsd_ctx* ctx, float* eps, float* eps_uncond, const CfgRescaleTable& tab, int B, int64_t chw, double* partial,
+                       float* g_out);
+
 // alphas_cumprod of the scaled-linear beta schedule (sampler.mojo:28-32), fp32 like the reference's Tensor
 void sampler_alphas_cumprod(int n_train, std::vector<float>& out);
 // timestep list of `spacing` (tsd_timestep_spacing) with the first `start_step` entries dropped; TSD_E_ARG on a bad argument

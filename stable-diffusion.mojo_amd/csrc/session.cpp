@@ -33,6 +33,7 @@ struct tsd_session {
   float* ip_mask = nullptr;   // [B][L*L] fp32 in [0,1]: 1 = regenerate, 0 = keep `ip_known`
   float* ip_known = nullptr;  // [B,4,L,L] the original latents
   float* ip_noise = nullptr;  // [B,4,L,L] the noise they are re-noised with
+  double* gr_part = nullptr;  // [16][CFG_RESCALE_GMAX][4] fp64: the partial moments of a step's guidance rescale (kernels_guidance.hip)
   size_t noise_cap = 0;
   // What a step's UNet forward computes from the timestep and the context alone (graph.h UNetPre), made once per upload() by
   // session_build_invariants when the context's session_hoist is on: own allocations, grown at upload() like `noise`, never in a step.
@@ -61,6 +62,9 @@ struct tsd_session {
   // its noise in the update kernel from stream 16 + i of seeds[b] (counter_rng.h), no buffer and no extra launch
   bool seeded = false;
   uint64_t seeds[16] = {};
+  // guidance rescale (tsd_session_set_guidance_rescale) belongs to one upload() as well: phi > 0 puts launch_cfg_rescale between the
+  // forward and the update of a step; 0 = off, and a step enqueues what it always did
+  float rescale = 0.f;
   size_t plan_unet = 0, plan_dec = 0;
   unsigned opt_gen = 0;  // generation of the context's options the workspace was sized for (upload)
   // Latched when the host scan of a download found inf / NaN in THIS session's latents: the context's counter is cleared once reported,
@@ -80,6 +84,7 @@ struct tsd_session {
     uint64_t seed = 0;
     bool hist_valid = false;  // `hist` of this sample holds the x0 of the slot's previous step (DPM-Solver++(2M))
     bool inpaint = false;     // slot_set_inpaint: sample b of ip_mask / ip_known / ip_noise is this request's; off after slot_start
+    float rescale = 0.f;      // slot_set_guidance_rescale: this request's phi; 0 after slot_start
   } slot[16];
   float* trows = nullptr;     // [Bu][tproj.N] fp32: row i_b of ttab per sample, gathered by every advance (own allocation, grown at slots_open)
   size_t trows_cap = 0;
@@ -250,6 +255,7 @@ static void schedule_changed(tsd_session* s) {
   s->slots = false;
   s->inpaint = false;
   s->seeded = false;
+  s->rescale = 0.f;
   session_latents_changed(s);
 }
 
@@ -272,7 +278,8 @@ extern "C" int tsd_session_create(tsd_model* diffusion, tsd_model* decoder, int 
   const size_t o_lat = carve(nl * 4), o_lat2 = carve(2 * nl * 4), o_ctx = carve((size_t)Bu * s->Tp * 768 * 2),
                o_eps = carve((size_t)Bu * 4 * L * L * 4), o_t = carve(16 * 4), o_te = carve(16 * 320 * 4),
                o_img = carve(decoder ? (size_t)B * 3 * 64 * L * L * 4 : 0), o_hist = carve(nl * 4),
-               o_ipm = carve((size_t)B * L * L * 4), o_ipk = carve(nl * 4), o_ipn = carve(nl * 4);
+               o_ipm = carve((size_t)B * L * L * 4), o_ipk = carve(nl * 4), o_ipn = carve(nl * 4),
+               o_grp = carve((size_t)CFG_RESCALE_PARTIAL_DOUBLES * sizeof(double));
   hipError_t e = hipMalloc((void**)&s->state, off);
   if (e != hipSuccess) { delete s; TSD_FAIL(TSD_E_ALLOC, "session: hipMalloc(%zu) failed: %s", off, hipGetErrorString(e)); }
   if (ctx->opt.debug_poison >= 0 && (ctx->opt.debug_poison_what & 4)) hipMemsetAsync(s->state, ctx->opt.debug_poison & 255, off, ctx->stream);
@@ -282,6 +289,7 @@ extern "C" int tsd_session_create(tsd_model* diffusion, tsd_model* decoder, int 
   s->images = decoder ? (float*)(s->state + o_img) : nullptr;
   s->hist = (float*)(s->state + o_hist);
   s->ip_mask = (float*)(s->state + o_ipm); s->ip_known = (float*)(s->state + o_ipk); s->ip_noise = (float*)(s->state + o_ipn);
+  s->gr_part = (double*)(s->state + o_grp);
   if (build_schedule(s) != TSD_OK) { hipFree(s->state); delete s; return TSD_E_ARG; }
   *out = s;
   return TSD_OK;
@@ -341,6 +349,7 @@ static int session_prepare(tsd_session* s) {
   s->uploaded = false;  // until this upload() is complete: the buffers below may move
   s->inpaint = false;   // the mask and the known latents belonged to the previous upload()
   s->seeded = false;    // and so did the seeds
+  s->rescale = 0.f;     // and the guidance rescale
   if (s->hoist) {  // the buffers of session_build_invariants; sizes depend on the session's shape and the schedule's length only
     const int CK = s->unet->unet.kproj_all.N, N = s->unet->unet.tproj.N;
     const size_t kc_bytes = ((size_t)Bu * Tp * CK * 2 + 255) & ~size_t(255);
@@ -449,6 +458,12 @@ extern "C" int tsd_session_step(tsd_session* s, int i) {
   TSD_TRY(session_forward(s, &pre, &eps_hw));
   SlotEntry p;
   TSD_TRY(session_plan(s, i, hist_valid, &p));
+  // guidance rescale: every sample's cond and uncond eps scaled in place by its g before the update reads them (two launches)
+  if (s->rescale > 0.f) {
+    CfgRescaleTable gr = {};
+    for (int b = 0; b < B; b++) gr.e[b] = {1, s->cfg_scale, s->rescale, 0};
+    TSD_TRY(launch_cfg_rescale(ctx, s->eps, s->eps + nl, gr, B, chw, s->gr_part, nullptr));
+  }
   // the update launch of the plan: its noise read from the uploaded tensor, drawn in the kernel (one source of noise per upload:
   // has_noise is off under seeds) or absent; only DPM-Solver++(2M) reads or keeps the history, and it takes no noise
   const float* eps_u = s->cfg ? s->eps + nl : nullptr;
@@ -498,6 +513,26 @@ extern "C" int tsd_session_set_seeds(tsd_session* s, const uint64_t* seeds) {
   return TSD_OK;
 }
 extern "C" int tsd_session_seeds_active(tsd_session* s) { return s ? (s->uploaded && s->seeded ? 1 : 0) : TSD_E_ARG; }
+
+// phi in [0, 1]: 0 = off.  Only a flag of the steps that follow: the latents, the history and the decoded images stay what they are.
+static int rescale_phi_ok(float phi) {
+  if (!(phi >= 0.f && phi <= 1.f)) TSD_FAIL(TSD_E_ARG, "session: guidance rescale %g is not in [0, 1]", (double)phi);
+  return TSD_OK;
+}
+extern "C" int tsd_session_set_guidance_rescale(tsd_session* s, float phi) {
+  NOTNULL(s);
+  SESSION_NOT_SLOTS(s, "set_guidance_rescale()");
+  if (!s->uploaded) TSD_FAIL(TSD_E_STATE, "session: upload() before set_guidance_rescale() (it belongs to one upload)");
+  if (!s->cfg) TSD_FAIL(TSD_E_STATE, "session: guidance rescale needs a session created with cfg != 0");
+  TSD_TRY(rescale_phi_ok(phi));
+  s->rescale = phi;
+  return TSD_OK;
+}
+extern "C" int tsd_session_guidance_rescale(tsd_session* s, float* phi) {
+  NOTNULL(s); NOTNULL(phi);
+  *phi = s->uploaded ? s->rescale : 0.f;
+  return TSD_OK;
+}
 
 // the latents become stream 2 of each sample's seed: what a txt2img caller would have uploaded, drawn on the device.  Asynchronous.
 extern "C" int tsd_session_seed_latents(tsd_session* s) {
@@ -655,6 +690,7 @@ extern "C" int tsd_session_slot_start(tsd_session* s, int b, const float* contex
   tsd_session::Slot& sl = s->slot[b];
   sl.state = 0;  // until the request is in place
   sl.inpaint = false;  // a refilled slot never inherits the previous request's mask
+  sl.rescale = 0.f;    // nor its guidance rescale
   // context rows b and B + b: upload()'s conversion, one sample
   for (int part = 0; part < (s->cfg ? 2 : 1); part++)
     TSD_TRY(session_put_context(s, part == 0 ? context : uncond_context, (size_t)part * B + b, 1));
@@ -727,6 +763,28 @@ extern "C" int tsd_session_slot_inpaint_active(tsd_session* s, int b) {
   return s->slot[b].state == 1 && s->slot[b].inpaint ? 1 : 0;
 }
 
+// Guidance rescale for the request of ACTIVE slot b, like cfg_scale per request.  Only a flag of the advances that follow: the slot's
+// latents and history stay what they are.
+extern "C" int tsd_session_slot_set_guidance_rescale(tsd_session* s, int b, float phi) {
+  NOTNULL(s);
+  SESSION_IN_SLOTS(s);
+  if (b < 0 || b >= s->B) TSD_FAIL(TSD_E_ARG, "session: slot %d out of range (0..%d)", b, s->B - 1);
+  tsd_session::Slot& sl = s->slot[b];
+  if (sl.state != 1)
+    TSD_FAIL(TSD_E_STATE, "session: slot %d is %s; slot_set_guidance_rescale() belongs to an active request", b, sl.state ? "done" : "idle");
+  if (!s->cfg) TSD_FAIL(TSD_E_STATE, "session: guidance rescale needs a session created with cfg != 0");
+  TSD_TRY(rescale_phi_ok(phi));
+  sl.rescale = phi;
+  return TSD_OK;
+}
+extern "C" int tsd_session_slot_guidance_rescale(tsd_session* s, int b, float* phi) {
+  NOTNULL(s); NOTNULL(phi);
+  SESSION_IN_SLOTS(s);
+  if (b < 0 || b >= s->B) TSD_FAIL(TSD_E_ARG, "session: slot %d out of range (0..%d)", b, s->B - 1);
+  *phi = s->slot[b].state == 1 ? s->slot[b].rescale : 0.f;
+  return TSD_OK;
+}
+
 // Entry b of the update table for an active slot at index i: the plan of step i, plus the slot's guidance scale and the base of its noise
 static int slot_entry(const tsd_session* s, const tsd_session::Slot& sl, SlotEntry* e, uint64_t* base) {
   e->cfg_scale = sl.cfg_scale;
@@ -760,6 +818,15 @@ extern "C" int tsd_session_advance(tsd_session* s, uint32_t* finished_mask) {
     session_blend_scalars(s, sl.index, &blend.e[b].a_prev, &blend.e[b].s_prev);
     blending = true;
   }
+  // the guidance-rescale table: an active slot with phi > 0 is `on`; everyone else is neither read nor written by its launches
+  CfgRescaleTable gr = {};
+  bool rescaling = false;
+  for (int b = 0; b < B; b++) {
+    const tsd_session::Slot& sl = s->slot[b];
+    if (sl.state != 1 || !(sl.rescale > 0.f)) continue;
+    gr.e[b] = {1, sl.cfg_scale, sl.rescale, 0};
+    rescaling = true;
+  }
   // per-sample time rows (cond and uncond halves alike); an idle or finished slot reads entry 0
   UNetPre pre;
   if (s->hoist) {
@@ -778,6 +845,7 @@ extern "C" int tsd_session_advance(tsd_session* s, uint32_t* finished_mask) {
   TSD_TRY(session_forward(s, &pre, &eps_hw));
   // the update launch: with an inpainting slot among the active ones, the kernel that also blends (no further launch either way)
   const float* eps_u = s->cfg ? s->eps + nl : nullptr;
+  if (rescaling) TSD_TRY(launch_cfg_rescale(ctx, s->eps, s->eps + nl, gr, B, (int64_t)4 * L * L, s->gr_part, nullptr));
   if (blending)
     TSD_TRY(launch_slot_update_blend(ctx, s->latents, s->eps, eps_u, s->hist, tab, blend, s->ip_mask, s->ip_known, s->ip_noise, B,
                                      (int64_t)4 * L * L, eps_hw));

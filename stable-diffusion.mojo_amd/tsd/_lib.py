@@ -42,6 +42,16 @@ def mask_mode(mode):
     return MASK_MODES.get(mode.lower(), -1) if isinstance(mode, str) else int(mode)
 
 
+def check_guidance_rescale(phi, cfg=True):
+    """A guidance rescale in [0, 1] as a float; ValueError outside it (NaN included) and for a positive value without CFG."""
+    phi = float(phi)
+    if not (0.0 <= phi <= 1.0):
+        raise ValueError(f"guidance_rescale must be between 0 and 1, got {phi}")
+    if phi > 0.0 and not cfg:
+        raise ValueError("guidance_rescale rescales the classifier-free-guidance combine: it needs cfg=True")
+    return phi
+
+
 class TsdError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"libtsd error {code}: {msg}")
@@ -124,6 +134,10 @@ def _declare(l):
         "tsd_sampler_timesteps": ([i, i, i, i, C.POINTER(i), i], i),
         "tsd_sampler_coeffs": ([i, C.c_double, i, i, i, i, i, i, C.POINTER(C.c_double)], i),
         "tsd_sampler_step_f32": ([vp, fp, fp, fp, f, fp, fp, i64, fp, fp, fp], i),
+        "tsd_ddpm_step_f32": ([vp, fp, fp, fp, f, fp, i64, i, i, i, i, i, fp], i),
+        "tsd_cfg_rescale_f32": ([vp, fp, fp, i, i64, fp, fp, fp, fp, fp], i),
+        "tsd_session_set_guidance_rescale": ([vp, f], i), "tsd_session_guidance_rescale": ([vp, fp], i),
+        "tsd_session_slot_set_guidance_rescale": ([vp, i, f], i), "tsd_session_slot_guidance_rescale": ([vp, i, fp], i),
         "tsd_latent_mask_f32": ([vp, fp, i, i, i, fp], i),
         "tsd_inpaint_blend_f32": ([vp, fp, fp, fp, fp, i, i64, f, f, fp], i),
         "tsd_session_set_inpaint": ([vp, fp, fp, fp], i), "tsd_session_inpaint_active": ([vp], i),

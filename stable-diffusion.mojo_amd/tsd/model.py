@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check, f32, lib, ptr, sampler_kind, timestep_spacing, vp
+from ._lib import check, check_guidance_rescale, f32, lib, ptr, sampler_kind, timestep_spacing, vp
 
 KINDS = {"diffusion": _lib.MODEL_DIFFUSION, "decoder": _lib.MODEL_DECODER, "encoder": _lib.MODEL_ENCODER,
          "clip": _lib.MODEL_CLIP, "diffusion_sd15": _lib.MODEL_DIFFUSION_SD15,
@@ -250,6 +250,20 @@ class Session:
     def inpaint_active(self):
         return lib().tsd_session_inpaint_active(self.h) == 1
 
+    def set_guidance_rescale(self, phi):
+        """Guidance rescale (Lin et al. 2023, eq. 15-16; diffusers' `guidance_rescale`) for the steps of the current upload(): phi in
+        [0, 1], 0 = off.  Every step then scales each sample's cond and uncond eps by g = phi std(cond) / std(combined) + 1 - phi on the
+        device before its update (`tsd.cfg_rescale` is the same launches on host tensors).  Needs a CFG session; upload(),
+        set_schedule() and set_sampler() turn it off."""
+        phi = check_guidance_rescale(phi, self.cfg)
+        check(lib().tsd_session_set_guidance_rescale(self.h, phi))
+
+    @property
+    def guidance_rescale(self):
+        phi = C.c_float(0.0)
+        check(lib().tsd_session_guidance_rescale(self.h, C.byref(phi)))
+        return phi.value
+
     def decode(self):
         check(lib().tsd_session_decode(self.h))
 
@@ -327,6 +341,17 @@ class Session:
         if r < 0:
             check(r)
         return r == 1
+
+    def slot_set_guidance_rescale(self, b, phi):
+        """Guidance rescale for the request of active slot b, per request like cfg_scale: phi in [0, 1], 0 = off.  slot_start() and
+        slots_open() clear it."""
+        phi = check_guidance_rescale(phi, self.cfg)
+        check(lib().tsd_session_slot_set_guidance_rescale(self.h, int(b), phi))
+
+    def slot_guidance_rescale(self, b):
+        phi = C.c_float(0.0)
+        check(lib().tsd_session_slot_guidance_rescale(self.h, int(b), C.byref(phi)))
+        return phi.value
 
     def advance(self):
         """One tick: one forward over all slots, every active slot one step further.  Returns the slots that finished (ascending)."""

@@ -5,6 +5,7 @@ over independent prompts (the reference is batch 1; `pipeline.mojo:12` suggests 
 import numpy as np
 
 from . import rng
+from ._lib import check_guidance_rescale
 from .model import Session
 from .utils import latent_mask, rescale
 
@@ -25,7 +26,7 @@ def encode_prompts(prompts, tokenizer, clip):
 def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg=True, cfg_scale=7.5,
              inference_steps=50, seed_val=0, input_image=None, encoder=None, latents=None, noise=None,
              num_training_steps=1000, L=64, return_latents=False, sampler="ddpm", eta=0.0, spacing="leading", mask=None,
-             mask_mode="any", seeds=None):
+             mask_mode="any", seeds=None, guidance_rescale=0.0):
     """context (B,T,768); returns images (B,3,8L,8L) in [0,255] like pipeline.mojo:127.
 
     sampler "ddpm" (the reference's, about 50 steps) | "ddim" (eta = 0: deterministic) | "dpmpp_2m" (second-order multistep, 20-25
@@ -41,7 +42,12 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
     seeds: a sequence of B ints, one per sample - the initial latents, the img2img / inpainting noise and every step's noise are drawn
     on the device from that sample's seed (`Session.set_seeds`), so a seed gives the same image wherever its sample sits in the batch
     and no noise tensor crosses the bus; only the encoder's noise input stays a host tensor keyed by seed_val.  Not with `noise` or
-    `latents`."""
+    `latents`.
+
+    guidance_rescale in [0, 1] (Lin et al. 2023, eq. 15-16; diffusers' argument of the same name), with cfg=True: every step scales
+    the guided prediction back towards the conditional prediction's per-sample standard deviation (`Session.set_guidance_rescale`);
+    0.7 is the paper's value against the over-saturation of guidance scales of 7 and more.  0 is the reference's loop."""
+    guidance_rescale = check_guidance_rescale(guidance_rescale, cfg)
     if seeds is not None and (noise is not None or latents is not None):
         raise ValueError("generate(seeds=...) draws latents and noise on the device: pass neither noise nor latents")
     context = np.asarray(context, dtype=np.float32)
@@ -88,6 +94,8 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
         sess.add_noise(0, z4)  # sampler.mojo:111-124 at timesteps[0]
         if mask is not None:
             sess.set_inpaint(mask_lat, latents, z4)
+    if guidance_rescale > 0.0:
+        sess.set_guidance_rescale(guidance_rescale)
     for i in range(n):  # pipeline.mojo:87-122
         sess.step(i)
     out_lat = sess.latents()

@@ -5,19 +5,40 @@ A `Session` in slot mode (`Session.slots_open`) gives every sample of its batch 
 each free slot takes the next request, a slot that finishes yields its latents and is free again.  A request that arrives while the
 others are at step 3 of 50 starts at once; img2img requests of different strength - different start indices - share the batch.
 
-The scheduler only calls the slot methods (`B`, `L`, `num_steps`, `slot_start`, `slot_set_inpaint`, `advance`, `slot_latents`), so it runs
-against any object that has them (tests/test_slots_cpu.py and tests/test_slot_inpaint_cpu.py drive it without a GPU).
+The scheduler only calls the slot methods (`B`, `L`, `num_steps`, `slot_start`, `slot_set_inpaint`, `advance`, `slot_latents` - and
+`slot_set_guidance_rescale` for a request that asks for it), so it runs against any object that has them (tests/test_slots_cpu.py and
+tests/test_slot_inpaint_cpu.py drive it without a GPU).
 """
 from collections import namedtuple
 
 import numpy as np
 
+from ._lib import check_guidance_rescale
+
 # One request.  latents None: txt2img from `seed`.  latents (4,L,L) with strength s in [0,1]: img2img by the rule of `generate`
 # (sampler.mojo:68-70) - the first n - int(n * s) steps are skipped and the latents are noised to that timestep from `seed`.
 # mask: inpainting - `latents` are the known latents and the mask says where to regenerate (1) and where to keep them (0): a latent mask
 # (L,L) / (1,L,L) is used as given, a pixel mask (8L,8L) / (1,8L,8L) goes through `tsd.utils.latent_mask` with `mask_mode`.
-Request = namedtuple("Request", "id context uncond seed cfg_scale latents strength mask mask_mode")
-Request.__new__.__defaults__ = (None, 0, 7.5, None, None, None, "any")
+_RequestFields = namedtuple("Request", "id context uncond seed cfg_scale latents strength mask mask_mode")
+_RequestFields.__new__.__defaults__ = (None, 0, 7.5, None, None, None, "any")
+
+
+class Request(_RequestFields):
+    """The nine positional fields above - the tuple a queue may hold in place of a Request - and, by keyword only, guidance_rescale in
+    [0, 1]: the request's guidance rescale (`Session.slot_set_guidance_rescale`), per request like cfg_scale; 0 = off.  The keyword is
+    an attribute beside the tuple: `_fields`, unpacking and comparison stay those of the nine fields; `_replace` keeps it."""
+    guidance_rescale = 0.0   # for an instance made without __new__ (`_make`)
+
+    def __new__(cls, *fields, guidance_rescale=0.0, **kw):
+        self = super().__new__(cls, *fields, **kw)
+        self.guidance_rescale = check_guidance_rescale(guidance_rescale)   # ValueError outside [0, 1]; CFG is the session's to check
+        return self
+
+    def _replace(self, **kw):
+        phi = kw.pop("guidance_rescale", self.guidance_rescale)
+        r = super()._replace(**kw)
+        r.guidance_rescale = phi
+        return r
 
 
 def request_latent_mask(r, session):
@@ -81,6 +102,7 @@ class SlotScheduler:
                     r = Request(*r)
                 # a request that cannot run raises here, before its slot (or any other) is touched
                 mask = request_latent_mask(r, self.session)
+                phi = check_guidance_rescale(r.guidance_rescale, getattr(self.session, "cfg", True))
                 i0 = start_index(self.n, r.strength if r.latents is not None else None)
                 if i0 >= self.n:  # strength 0: the image as it is
                     passed.append((r.id, np.asarray(r.latents, dtype=np.float32)))
@@ -89,6 +111,8 @@ class SlotScheduler:
                                         start_index=i0, cfg_scale=r.cfg_scale)
                 if mask is not None:
                     self.session.slot_set_inpaint(b, mask, r.latents)
+                if phi > 0.0:
+                    self.session.slot_set_guidance_rescale(b, phi)
                 self.owner[b] = r.id
         return passed
 
@@ -114,6 +138,8 @@ def generate_stream(diffusion, decoder, requests, B, L, T=77, cfg=True, inferenc
     A txt2img request gives what `generate(..., seeds=[...])` gives for it in the same sample position.  An img2img request indexes the
     FULL timestep list (its step i draws stream 16 + i of its seed), where `generate` drops the skipped entries and counts from 0.
     A request with a `mask` is inpainted in its slot (`Session.slot_set_inpaint`) next to the others: no drain, no extra launch.
+    A request with `guidance_rescale` > 0 is rescaled in its slot (`Session.slot_set_guidance_rescale`), as `generate(...,
+    guidance_rescale=...)` rescales it; it needs cfg=True.
     Finished latents are decoded through `decoder.forward`, one image per call.  `stats`, a dict, receives advances / active_ticks / occupancy when the stream ends."""
     from .model import Session
     from .utils import _unary

@@ -217,6 +217,39 @@ def inpaint_blend(x, mask, known, noise, a_prev, s_prev, ctx=None):
     return y
 
 
+def cfg_rescale(eps, eps_uncond, cfg_scale=7.5, phi=0.7, ctx=None):
+    """Guidance rescale (`tsd_cfg_rescale_f32`; Lin et al. 2023, eq. 15-16): eps / eps_uncond (B, ...), cfg_scale and phi scalars or one
+    value per sample -> (eps', eps_uncond', g) with g (B,) = phi std(eps) / std((eps - eps_uncond) cfg_scale + eps_uncond) + 1 - phi per
+    sample and eps' = g eps, eps_uncond' = g eps_uncond.  The launches a session with `set_guidance_rescale` adds to a step."""
+    c, u = f32(eps), f32(eps_uncond)
+    if c.ndim < 2 or u.shape != c.shape:
+        raise ValueError(f"cfg_rescale: eps {c.shape} and eps_uncond {u.shape} must be the same (B, ...) shape")
+    B = c.shape[0]
+    s = np.ascontiguousarray(np.broadcast_to(np.asarray(cfg_scale, dtype=np.float32), (B,)))
+    p = np.ascontiguousarray(np.broadcast_to(np.asarray(phi, dtype=np.float32), (B,)))
+    if not np.all((p >= 0.0) & (p <= 1.0)):
+        raise ValueError(f"cfg_rescale: every phi must be between 0 and 1, got {p.tolist()}")
+    if not np.isfinite(s).all():
+        raise ValueError(f"cfg_rescale: every cfg_scale must be finite, got {s.tolist()}")
+    co, uo, g = np.empty_like(c), np.empty_like(u), np.empty(B, dtype=np.float32)
+    check(lib().tsd_cfg_rescale_f32(_ctx(ctx), ptr(c), ptr(u), B, c.size // B if B else 0, ptr(s), ptr(p), ptr(co), ptr(uo), ptr(g)))
+    return co, uo, g
+
+
+def ddpm_step(x, eps, eps_uncond, cfg_scale, noise, i, num_inference_steps, num_training_steps=1000, start_step=0, spacing="leading",
+              ctx=None):
+    """The update of step i of a DDPM session with this schedule (`tsd_ddpm_step_f32`) on host tensors; eps_uncond and noise may be None."""
+    x, e = f32(x), f32(eps)
+    u = f32(eps_uncond) if eps_uncond is not None else None
+    z = f32(noise) if noise is not None else None
+    if e.shape != x.shape or (u is not None and u.shape != x.shape) or (z is not None and z.shape != x.shape):
+        raise ValueError(f"ddpm_step: x {x.shape}, eps {e.shape} and the optional tensors must have one shape")
+    y = np.empty_like(x)
+    check(lib().tsd_ddpm_step_f32(_ctx(ctx), ptr(x), ptr(e), ptr(u), float(cfg_scale), ptr(z), x.size, _lib.timestep_spacing(spacing),
+                                  int(num_training_steps), int(num_inference_steps), int(start_step), int(i), ptr(y)))
+    return y
+
+
 def get_time_embedding(timestep, ctx=None):
     """`get_time_embedding` helpers/utils.mojo:353-370 -> (1,1,320)."""
     y = np.empty(320, dtype=np.float32)
