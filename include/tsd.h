@@ -750,6 +750,12 @@ int tsd_debug_elem_run(tsd_ctx* ctx, const int64_t* desc, int n, const void* con
  * [4] k_gn_prereduce, [5] composite accepted, [6] k_gn_finalize launches (any source), [7] composites offered.  n >= 8; reset != 0
  * clears them. */
 int tsd_debug_gn_path_counts(tsd_ctx* ctx, int64_t* counts, int n, int reset);
+/* The -DTSD_JITTER build (`make jitter`: random wave-level delays where waves meet) shows that it detects a hazard: n (1 .. 64) launches
+ * of a two-wave kernel in which wave 0 reads an LDS word that wave 1 writes, with a jitter point in each wave and no barrier between
+ * the two accesses (csrc/kernels_elementwise.hip, k_jitter_selftest: in bounds, nothing waits).  Returns the number of DISTINCT words the
+ * launches stored - 2 when both orders occurred, 1 on a build that keeps one schedule.  The shipped library has no such kernel: there
+ * the entry launches nothing and returns TSD_E_ARG ("not supported in this build"), like a tile configuration the build does not have. */
+int tsd_debug_jitter_selftest(tsd_ctx* ctx, int n);
 /* Attention blocks that run op by op (C = 640 / 1280) fold GEGLU's second linear into the output 1x1 convolution at tsd_model_prepare:
  * wf [C][5C] fp16 = [W_out . W_2 | W_out], bf [C] = W_out . b_2 + b_out.  Copies block `block`'s (index into the UNet's layers; NULL
  * pointers only ask) and returns C, 0 when that block does not fold.  tsd_model_prepare returns TSD_E_NONFINITE when a folded weight

@@ -723,6 +723,28 @@ extern "C" int tsd_vae_attention_block_f32(tsd_ctx* ctx, const float* x, int C, 
   });
 }
 
+// the jitter build shows that it makes a hazard visible: n launches of k_jitter_selftest, the number of distinct words they stored
+extern "C" int tsd_debug_jitter_selftest(tsd_ctx* ctx, int n) {
+  NOTNULL(ctx);
+  if (n < 1 || n > 64) TSD_FAIL(TSD_E_ARG, "jitter_selftest: n=%d (1..64)", n);
+  unsigned seen[64];
+  const int r = run_op(ctx, [&]() -> int {
+    Dev d{ctx};
+    unsigned* dv = d.buf<unsigned>(n);
+    if (d.err) return d.err;
+    TSD_TRY(launch_jitter_selftest(ctx, dv, n));
+    return d.out(seen, dv, n);
+  });
+  if (r != TSD_OK) return r;
+  int distinct = 0;
+  for (int i = 0; i < n; i++) {
+    bool first = true;
+    for (int j = 0; j < i; j++) first &= seen[j] != seen[i];
+    distinct += first;
+  }
+  return distinct;
+}
+
 extern "C" int tsd_debug_gn_path_counts(tsd_ctx* ctx, int64_t* counts, int n, int reset) {
   NOTNULL(ctx); NOTNULL(counts);
   if (n < 8) TSD_FAIL(TSD_E_ARG, "gn_path_counts: %d slots (8 needed)", n);

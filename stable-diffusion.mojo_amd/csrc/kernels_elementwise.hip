@@ -4,6 +4,7 @@
 #include <atomic>
 
 #include "common.h"
+#include "lds_dma.h"
 #include "update_element.h"
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
@@ -305,12 +306,14 @@ __global__ __launch_bounds__(256) void k_softmax_rows(const T* __restrict__ x, i
   for (int c = tid; c < cols; c += 256) m = fmaxf(m, (float)xr[c]);
   m = wave_max(m);
   if (lane == 0) red[wave] = m;
+  tsd_jitter();
   __syncthreads();
   m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
   float s = 0.f;
   for (int c = tid; c < cols; c += 256) s += __expf((float)xr[c] - m);
   s = wave_sum(s);
   if (lane == 0) red[4 + wave] = s;
+  tsd_jitter();
   __syncthreads();
   s = red[4] + red[5] + red[6] + red[7];
   const float inv = 1.f / s;
@@ -337,6 +340,7 @@ __global__ __launch_bounds__(256) void k_softmax_rows_h8(half_t* __restrict__ x,
   }
   m = wave_max(m);
   if (lane == 0) red[wave] = m;
+  tsd_jitter();
   __syncthreads();
   m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
   float e[NV][8];
@@ -351,6 +355,7 @@ __global__ __launch_bounds__(256) void k_softmax_rows_h8(half_t* __restrict__ x,
   }
   s = wave_sum(s);
   if (lane == 0) red[4 + wave] = s;
+  tsd_jitter();
   __syncthreads();
   s = red[4] + red[5] + red[6] + red[7];
   const float inv = 1.f / s;
@@ -515,6 +520,7 @@ __global__ __launch_bounds__(256) void k_small_linear(const float* __restrict__ 
       }
     }
   }
+  tsd_jitter();
   __syncthreads();
   float acc[NB];
 #pragma unroll
@@ -780,4 +786,40 @@ int launch_transpose_f32_to_f16(tsd_ctx* ctx, const float* src, int batch, int K
                      total);
   HIP_TRY(hipGetLastError());
   return TSD_OK;
+}
+
+// ---- the jitter build's self-test: a hazard on purpose, to show that tsd_jitter() makes one visible (tsd_debug_jitter_selftest) ----
+// One workgroup of two waves and one LDS word.  Lane 0 of wave 1 stores JITTER_SELFTEST_WRITTEN after its jitter point; lane 0 of wave 0
+// loads the word after its own jitter point - NO barrier orders the two - and stores what it saw (the word's initial 0, or the written
+// value) to its one output word.  A kernel the jitter build leaves on one schedule gives one value launch after launch; with the delays
+// both orders occur.  Nothing waits on anything: no loop on a flag, both waves meet at one barrier and return, every access is in bounds.
+// Compiled into -DTSD_JITTER builds only: the shipped library has neither the kernel nor a launch of it.
+constexpr unsigned JITTER_SELFTEST_WRITTEN = 0x5A17C0DEu;
+#ifdef TSD_JITTER
+__global__ __launch_bounds__(128) void k_jitter_selftest(unsigned* __restrict__ out) {
+  __shared__ unsigned word;
+  volatile unsigned* w = &word;
+  if (threadIdx.x == 0) *w = 0u;
+  __syncthreads();
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  tsd_jitter();
+  if (wave == 1) {
+    if (lane == 0) *w = JITTER_SELFTEST_WRITTEN;
+  } else {
+    const unsigned seen = *w;  // the hazard: unordered against wave 1's store
+    if (lane == 0) *out = seen;
+  }
+  __syncthreads();
+}
+#endif
+// n launches, launch i stores to out[i].  TSD_E_ARG in a build without -DTSD_JITTER (nothing is launched).
+int launch_jitter_selftest(tsd_ctx* ctx, unsigned* out, int n) {
+#ifdef TSD_JITTER
+  if (!ctx->launch()) return TSD_OK;
+  for (int i = 0; i < n; i++) hipLaunchKernelGGL(k_jitter_selftest, dim3(1), dim3(128), 0, ctx->stream, out + i);
+  HIP_TRY(hipGetLastError());
+  return TSD_OK;
+#else
+  TSD_FAIL(TSD_E_ARG, "jitter_selftest: not supported in this build (the kernel exists under -DTSD_JITTER only: make jitter)");
+#endif
 }

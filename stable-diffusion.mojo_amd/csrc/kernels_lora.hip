@@ -6,6 +6,7 @@
 // layer, i * k * k + tap for a convolution); the GEGLU row interleave (k_pack_linear) and the tap-major K of the packed convolution
 // (k_pack_conv) are resolved here.  Nothing but the addressed elements is written: no pad row, no pad channel, no other row.
 #include "common.h"
+#include "lds_dma.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
@@ -46,6 +47,7 @@ __global__ __launch_bounds__(256) void k_lora_merge(LoraArgs a, int* __restrict_
       const int k = e / LORA_TN, c = e % LORA_TN;
       s_dn[k][c] = (k0 + k < a.rank && c0 + c < a.cols) ? a.down[(int64_t)(k0 + k) * a.cols + c0 + c] : 0.f;
     }
+    tsd_jitter();
     __syncthreads();
 #pragma unroll
     for (int kq = 0; kq < LORA_KC; kq += 4) {  // lane l: A[l & 15][l >> 4], B[l >> 4][l & 15]
@@ -53,6 +55,7 @@ __global__ __launch_bounds__(256) void k_lora_merge(LoraArgs a, int* __restrict_
       acc0 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, s_dn[kq + ak][cw + ar], acc0, 0, 0, 0);
       acc1 = __builtin_amdgcn_mfma_f32_16x16x4f32(av, s_dn[kq + ak][cw + 16 + ar], acc1, 0, 0, 0);
     }
+    tsd_jitter();  // the next rank chunk overwrites s_up / s_dn: a wave still in its MFMAs meets a wave that is early staging
     __syncthreads();
   }
   // C / D: column = lane & 15, row = 4 * (lane >> 4) + register

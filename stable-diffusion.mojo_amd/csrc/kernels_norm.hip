@@ -15,6 +15,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "lds_dma.h"
 
 typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 typedef float f2 __attribute__((ext_vector_type(2)));
@@ -104,6 +105,7 @@ __global__ __launch_bounds__(256) void k_gn_partial(const GnK p) {
       }
     }
   }
+  tsd_jitter();
   __syncthreads();
   // fixed-order (deterministic) reduction: pixel lanes, then the channels of each group
   for (int g = tid; g < p.G; g += 256) {
@@ -187,12 +189,14 @@ __global__ __launch_bounds__(256) void k_gn_prereduce(const float* __restrict__ 
         t2 += (double)o[1];
       }
     red[threadIdx.x][0] = t1; red[threadIdx.x][1] = t2;
+    tsd_jitter();
     __syncthreads();
     if (l == 0 && g < G) {
       for (int k = 1; k < LN; k++) { t1 += red[threadIdx.x + k * G][0]; t2 += red[threadIdx.x + k * G][1]; }  // fixed order
       float* o = out + (((int64_t)b * nchunk + c) * G + g) * 2;
       o[0] = (float)t1; o[1] = (float)t2;
     }
+    tsd_jitter();  // the next round of groups overwrites red[]: a wave that is late reading it meets a wave that is early writing
     __syncthreads();
   }
 }
@@ -215,6 +219,7 @@ __global__ __launch_bounds__(256) void k_gn_apply(const GnK p) {
   } else {  // few slabs: every block finishes the statistics itself (a few KB of partials from L2), no extra launch
     for (int g0 = 0; g0 < p.G; g0 += 32) gn_finish_groups(p, b, g0, tid, st);
   }
+  tsd_jitter();
   __syncthreads();
   const GnMap m = gn_map(p.C, tid);
   if (!m.active) return;

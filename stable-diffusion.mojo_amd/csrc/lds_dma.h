@@ -43,6 +43,12 @@ __device__ __forceinline__ void wait_alt_end() { asm volatile("; tsd-wait-alt en
 // Hazard hunting (-DTSD_JITTER builds only, never shipped): a random wave-level delay at the points where waves meet or part.  A kernel
 // whose waves are correctly ordered gives the same bits whatever the delays; a hazard that a fixed schedule hides becomes a run-to-run
 // difference within a few launches (scripts/diag_race3.py counts distinct results).
+// Where the points are: kernels_gemm.hip (8: tile steps, ring hand-offs, the split-K hand-off, the epilogue), kernels_attn.hip (1) and
+// kernels_attn8.hip (2: the tile loops), kernels_chain.hip (3), kernels_guidance.hip (1: k_cfg_moments), kernels_norm.hip (4: every barrier of
+// k_gn_partial, k_gn_prereduce and k_gn_apply), kernels_elementwise.hip (5: both barriers of k_softmax_rows and k_softmax_rows_h8, the one of
+// k_small_linear; plus k_jitter_selftest, a hazard on purpose that shows the delays make one visible) and kernels_lora.hip (2: k_lora_merge).
+// tests/jitter_manifest.py lists the kernels (JITTER_KERNELS); a CPU test finds the point - a clock read and a sleep the shipped listing does
+// not have - in every instantiation's jitter listing, and no clock read in the shipped one.
 __device__ __forceinline__ void tsd_jitter() {
 #ifdef TSD_JITTER
   const unsigned t = (unsigned)__builtin_amdgcn_s_memtime();

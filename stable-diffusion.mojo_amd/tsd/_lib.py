@@ -188,6 +188,7 @@ def _declare(l):
         "tsd_debug_chain_run": ([vp, C.POINTER(i64), i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)], i),
         "tsd_debug_elem_run": ([vp, C.POINTER(i64), i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)], i),
         "tsd_debug_gn_path_counts": ([vp, C.POINTER(i64), i, i], i),
+        "tsd_debug_jitter_selftest": ([vp, i], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(l, name)

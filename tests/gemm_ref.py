@@ -459,3 +459,92 @@ def sample_rows(d, seed, n_random=256):
     rng = np.random.default_rng(seed)
     r.update(int(x) for x in rng.integers(0, tot, n_random))
     return np.array(sorted(r), np.int64)
+
+
+# ---- the launch tables of tests/test_gpu_gemm_ref.py (shared with tests/jitter_manifest.py: the same cases under perturbed timing) ----
+PROD_CONV = EPI["BIAS_N"] | EPI["RESIDUAL"]
+
+
+def _sweep_cases():
+    """(name, descriptor, configurations that take it)."""
+    out = []
+
+    def both(name, make):  # one shape per column family: N = 320 (160-wide tiles) and N = 256 / 132 (128-wide)
+        out.append((name + "/n160", make(320), N160 + N128))
+        out.append((name + "/n128", make(256), N128))
+
+    # M: conv images that straddle tiles (12 x 12 per sample, B = 3), stride 2 on odd / even sizes (Wo 13), H != W, tiny images
+    both("conv_b3_12x12_res_rowvec", lambda N: conv_desc(B=3, Hs=12, Ws=12, Cin=64, N=N, epi=PROD_CONV | EPI["ROWVEC"],
+                                                           rowvec_ld=N, rows_per_batch=144))
+    both("conv_s2_odd_wo13", lambda N: conv_desc(B=1, Hs=25, Ws=25, Cin=64, N=N, stride=2, epi=EPI["BIAS_N"]))
+    both("conv_s2_even_pad01", lambda N: conv_desc(B=2, Hs=16, Ws=10, Cin=128, N=N, stride=2, pad=0, pad_br=1, epi=EPI["BIAS_N"]))
+    both("conv_pad0_hw", lambda N: conv_desc(B=1, Hs=7, Ws=11, Cin=64, N=N, pad=0, epi=EPI["BIAS_N"] | EPI["OUT_F32"], out_scale=0.5))
+    both("conv_ups_wo24_resups", lambda N: conv_desc(B=2, Hs=12, Ws=12, Cin=64, N=N, ups=1, epi=PROD_CONV | EPI["RES_UPS"]))
+    both("conv_1x1_2x2", lambda N: conv_desc(B=4, Hs=2, Ws=2, Cin=64, N=N, epi=EPI["BIAS_N"], ldc=N + 8))
+    both("conv_cin320_wkts", lambda N: conv_desc(B=1, Hs=8, Ws=8, Cin=320, N=N, epi=PROD_CONV, w_kts=1))
+    both("conv_skip_wkts", lambda N: conv_desc(B=2, Hs=8, Ws=5, Cin=64, N=N, Cin1=128, Cin2=64, lda1=136, epi=PROD_CONV,
+                                                 w_kts=1, rows_per_batch=40))
+    both("conv_wo40", lambda N: conv_desc(B=1, Hs=40, Ws=40, Cin=64, N=N, epi=EPI["BIAS_N"]))
+    # each epilogue flag on its own, a scaled fp16 store, the fused skip on row-major weights (its bias in the pitch-0 row vector)
+    both("conv_plain", lambda N: conv_desc(B=2, Hs=6, Ws=7, Cin=64, N=N))
+    both("conv_rowvec_only", lambda N: conv_desc(B=2, Hs=6, Ws=7, Cin=64, N=N, epi=EPI["ROWVEC"], rowvec_ld=N, rows_per_batch=42))
+    both("conv_res_only_scaled", lambda N: conv_desc(B=2, Hs=6, Ws=7, Cin=64, N=N, epi=EPI["RESIDUAL"], out_scale=0.25))
+    both("conv_skip_rowmajor", lambda N: conv_desc(B=2, Hs=7, Ws=6, Cin=128, N=N, Cin1=64, epi=PROD_CONV | EPI["ROWVEC"],
+                                                     rowvec_ld=0, rows_per_batch=42))
+    both("dense_biasm_only", lambda N: dense_desc(M=70, N=N, K=128, epi=EPI["BIAS_M"]))
+    both("dense_geglu_only", lambda N: dense_desc(M=70, N=N, K=128, epi=EPI["GEGLU"]))
+    both("dense_f32_only", lambda N: dense_desc(M=70, N=N, K=128, epi=EPI["OUT_F32"]))
+    both("dense_scaled_f16", lambda N: dense_desc(M=70, N=N, K=192, epi=EPI["BIAS_N"] | EPI["RESIDUAL"], out_scale=2.0))
+    # dense: M below one tile and BM * t +- 1, K = 64, few K tiles, K0 at 64 and mid-K, batched strides, GEGLU, BIAS_M, f32
+    both("dense_m40_k64", lambda N: dense_desc(M=40, N=N, K=64, epi=EPI["BIAS_N"]))
+    both("dense_m255_k128_res_inplace", lambda N: dense_desc(M=255, N=N, K=128, epi=EPI["BIAS_N"] | EPI["RESIDUAL"], alias=1))
+    both("dense_m257_concat64", lambda N: dense_desc(M=257, N=N, K=320, K0=64, lda0=72, epi=EPI["BIAS_N"] | EPI["RESIDUAL"]))
+    both("dense_m129_concat_mid_wkts", lambda N: dense_desc(M=129, N=N, K=640, K0=320, epi=EPI["BIAS_N"], w_kts=1))
+    both("dense_geglu", lambda N: dense_desc(M=200, N=N, K=192, epi=EPI["BIAS_N"] | EPI["GEGLU"]))
+    both("dense_biasm_f32_scaled", lambda N: dense_desc(M=130, N=N, K=256, epi=EPI["BIAS_M"] | EPI["BIAS_N"] | EPI["OUT_F32"],
+                                                          out_scale=0.125))
+    both("dense_batched", lambda N: dense_desc(M=65, N=N, K=128, batch=3, sa=65 * 128 + 64, sw=N * 128 + 64,
+                                                 sc=65 * N + 8, sr=65 * N + 16, epi=EPI["BIAS_N"] | EPI["RESIDUAL"]))
+    # N % 8 == 4: the non-coalesced epilogue; partial last column tile
+    out.append(("dense_n132", dense_desc(M=100, N=132, K=128, epi=EPI["BIAS_N"] | EPI["RESIDUAL"]), N128))
+    out.append(("conv_n132", conv_desc(B=1, Hs=9, Ws=9, Cin=64, N=132, epi=PROD_CONV), N128))
+    # thin tiles (N <= 16)
+    for N in (4, 8, 16):
+        out.append((f"conv_thin_n{N}", conv_desc(B=2, Hs=9, Ws=7, Cin=128, N=N, epi=EPI["BIAS_N"] | EPI["OUT_F32"]), THIN))
+    out.append(("dense_thin_n12", dense_desc(M=131, N=12, K=192, epi=EPI["BIAS_N"]), THIN))
+    # GroupNorm statistics: channels per group 1, 4, 8, 10, 16, 20, 40; several samples stacked in M
+    for N, groups in ((320, 320), (128, 32), (256, 32), (320, 32), (512, 32), (640, 32), (1280, 32)):
+        out.append((f"conv_gn_n{N}_g{groups}", conv_desc(B=3, Hs=8, Ws=8, Cin=64, N=N, epi=EPI["BIAS_N"] | EPI["GNSTATS"],
+                                                           gn_groups=groups, gn_rps=64, gn_nslab=2),
+                    N160 + N128 if N % 160 == 0 else N128))
+    # XCD grid remap: tile grids that select xcd_n 1, 2, 4, 8 (tiles_n x tiles_m factorisations of 8)
+    for N, M in ((1280, 256), (640, 512), (320, 1024), (160, 2048)):
+        out.append((f"dense_xcd_n{N}", dense_desc(M=M, N=N, K=128, epi=EPI["BIAS_N"]), (0, 5, 7, 11, 51, 54)))
+    # halo-x variants (opt-in): stride 1, Wo = 64, whole 128-pixel tiles
+    for N in (256, 320):
+        out.append((f"conv_halo_n{N}", conv_desc(B=1, Hs=4, Ws=64, Cin=64, N=N, epi=PROD_CONV), (30, 32)))
+    return out
+
+
+BNW = {**{c: 80 for c in N160}, **{c: 64 for c in N128}}  # wave-tile columns (FN * 16 of csrc/gemm_tiles.h); thin tiles emit no statistics
+
+# dispatcher-only modes: (name, descriptor, split-K slices the dispatcher must choose)
+SPLITS = [
+    # rows per sample <= 64: 64-row tiles, 2 / 4 / 8 slices by K
+    ("dense_rps64_k1024", dense_desc(M=256, N=1280, K=1024, epi=EPI["BIAS_N"] | EPI["RESIDUAL"], rps_hint=64), 2),
+    ("dense_rps64_k2048", dense_desc(M=256, N=1280, K=2048, epi=EPI["BIAS_N"], rps_hint=64), 4),
+    ("dense_rps64_k8192", dense_desc(M=256, N=1280, K=8192, epi=EPI["BIAS_N"] | EPI["RESIDUAL"], rps_hint=64), 8),
+    # fused skip: slices that end inside the skip segment (18 main K tiles of 32; 9 of 21)
+    ("conv_skip_4way", conv_desc(B=2, Hs=8, Ws=8, Cin=128, N=1024, Cin1=512, Cin2=384, epi=PROD_CONV, rps_hint=64), 4),
+    ("conv_skip_2way", conv_desc(B=2, Hs=8, Ws=8, Cin=64, N=1280, Cin1=512, Cin2=256, epi=PROD_CONV, rps_hint=64), 2),
+    # 16x16 level: 128-row tiles, K >= 4096 -> 2; at most 4 tile columns -> 4; the graph's long-K setting (K >= 8192) -> 4
+    ("conv_s2_wide_4way", conv_desc(B=2, Hs=32, Ws=32, Cin=640, N=640, stride=2, epi=EPI["BIAS_N"], rps_hint=256), 4),
+    ("dense_rps256_k5120", dense_desc(M=512, N=1280, K=5120, epi=EPI["BIAS_N"] | EPI["RESIDUAL"], rps_hint=256), 2),
+    ("dense_rps256_k10240_big4", dense_desc(M=512, N=1280, K=10240, epi=EPI["BIAS_N"], rps_hint=256, sk_big=4), 4),
+]
+
+
+def _vt_desc():
+    S, C_ = 256, 320
+    return dense_desc(M=2 * S, N=3 * C_, K=320, ldc=2 * C_, epi=EPI["BIAS_N"], vt=1, vt_n0=2 * C_, vt_ld=S, vt_s=S, vt_sb=C_ * S,
+                        rps_hint=S)

@@ -130,74 +130,10 @@ def test_production_launches_replay_within_the_fp64_bound(ctx, production):
 
 # ---- (b) configuration sweep ----------------------------------------------------------------------------------------------------
 N160, N128, THIN = G.N160, G.N128, G.THIN
-PROD_CONV = E["BIAS_N"] | E["RESIDUAL"]
-
-
-def _sweep_cases():
-    """(name, descriptor, configurations that take it)."""
-    out = []
-
-    def both(name, make):  # one shape per column family: N = 320 (160-wide tiles) and N = 256 / 132 (128-wide)
-        out.append((name + "/n160", make(320), N160 + N128))
-        out.append((name + "/n128", make(256), N128))
-
-    # M: conv images that straddle tiles (12 x 12 per sample, B = 3), stride 2 on odd / even sizes (Wo 13), H != W, tiny images
-    both("conv_b3_12x12_res_rowvec", lambda N: G.conv_desc(B=3, Hs=12, Ws=12, Cin=64, N=N, epi=PROD_CONV | E["ROWVEC"],
-                                                           rowvec_ld=N, rows_per_batch=144))
-    both("conv_s2_odd_wo13", lambda N: G.conv_desc(B=1, Hs=25, Ws=25, Cin=64, N=N, stride=2, epi=E["BIAS_N"]))
-    both("conv_s2_even_pad01", lambda N: G.conv_desc(B=2, Hs=16, Ws=10, Cin=128, N=N, stride=2, pad=0, pad_br=1, epi=E["BIAS_N"]))
-    both("conv_pad0_hw", lambda N: G.conv_desc(B=1, Hs=7, Ws=11, Cin=64, N=N, pad=0, epi=E["BIAS_N"] | E["OUT_F32"], out_scale=0.5))
-    both("conv_ups_wo24_resups", lambda N: G.conv_desc(B=2, Hs=12, Ws=12, Cin=64, N=N, ups=1, epi=PROD_CONV | E["RES_UPS"]))
-    both("conv_1x1_2x2", lambda N: G.conv_desc(B=4, Hs=2, Ws=2, Cin=64, N=N, epi=E["BIAS_N"], ldc=N + 8))
-    both("conv_cin320_wkts", lambda N: G.conv_desc(B=1, Hs=8, Ws=8, Cin=320, N=N, epi=PROD_CONV, w_kts=1))
-    both("conv_skip_wkts", lambda N: G.conv_desc(B=2, Hs=8, Ws=5, Cin=64, N=N, Cin1=128, Cin2=64, lda1=136, epi=PROD_CONV,
-                                                 w_kts=1, rows_per_batch=40))
-    both("conv_wo40", lambda N: G.conv_desc(B=1, Hs=40, Ws=40, Cin=64, N=N, epi=E["BIAS_N"]))
-    # each epilogue flag on its own, a scaled fp16 store, the fused skip on row-major weights (its bias in the pitch-0 row vector)
-    both("conv_plain", lambda N: G.conv_desc(B=2, Hs=6, Ws=7, Cin=64, N=N))
-    both("conv_rowvec_only", lambda N: G.conv_desc(B=2, Hs=6, Ws=7, Cin=64, N=N, epi=E["ROWVEC"], rowvec_ld=N, rows_per_batch=42))
-    both("conv_res_only_scaled", lambda N: G.conv_desc(B=2, Hs=6, Ws=7, Cin=64, N=N, epi=E["RESIDUAL"], out_scale=0.25))
-    both("conv_skip_rowmajor", lambda N: G.conv_desc(B=2, Hs=7, Ws=6, Cin=128, N=N, Cin1=64, epi=PROD_CONV | E["ROWVEC"],
-                                                     rowvec_ld=0, rows_per_batch=42))
-    both("dense_biasm_only", lambda N: G.dense_desc(M=70, N=N, K=128, epi=E["BIAS_M"]))
-    both("dense_geglu_only", lambda N: G.dense_desc(M=70, N=N, K=128, epi=E["GEGLU"]))
-    both("dense_f32_only", lambda N: G.dense_desc(M=70, N=N, K=128, epi=E["OUT_F32"]))
-    both("dense_scaled_f16", lambda N: G.dense_desc(M=70, N=N, K=192, epi=E["BIAS_N"] | E["RESIDUAL"], out_scale=2.0))
-    # dense: M below one tile and BM * t +- 1, K = 64, few K tiles, K0 at 64 and mid-K, batched strides, GEGLU, BIAS_M, f32
-    both("dense_m40_k64", lambda N: G.dense_desc(M=40, N=N, K=64, epi=E["BIAS_N"]))
-    both("dense_m255_k128_res_inplace", lambda N: G.dense_desc(M=255, N=N, K=128, epi=E["BIAS_N"] | E["RESIDUAL"], alias=1))
-    both("dense_m257_concat64", lambda N: G.dense_desc(M=257, N=N, K=320, K0=64, lda0=72, epi=E["BIAS_N"] | E["RESIDUAL"]))
-    both("dense_m129_concat_mid_wkts", lambda N: G.dense_desc(M=129, N=N, K=640, K0=320, epi=E["BIAS_N"], w_kts=1))
-    both("dense_geglu", lambda N: G.dense_desc(M=200, N=N, K=192, epi=E["BIAS_N"] | E["GEGLU"]))
-    both("dense_biasm_f32_scaled", lambda N: G.dense_desc(M=130, N=N, K=256, epi=E["BIAS_M"] | E["BIAS_N"] | E["OUT_F32"],
-                                                          out_scale=0.125))
-    both("dense_batched", lambda N: G.dense_desc(M=65, N=N, K=128, batch=3, sa=65 * 128 + 64, sw=N * 128 + 64,
-                                                 sc=65 * N + 8, sr=65 * N + 16, epi=E["BIAS_N"] | E["RESIDUAL"]))
-    # N % 8 == 4: the non-coalesced epilogue; partial last column tile
-    out.append(("dense_n132", G.dense_desc(M=100, N=132, K=128, epi=E["BIAS_N"] | E["RESIDUAL"]), N128))
-    out.append(("conv_n132", G.conv_desc(B=1, Hs=9, Ws=9, Cin=64, N=132, epi=PROD_CONV), N128))
-    # thin tiles (N <= 16)
-    for N in (4, 8, 16):
-        out.append((f"conv_thin_n{N}", G.conv_desc(B=2, Hs=9, Ws=7, Cin=128, N=N, epi=E["BIAS_N"] | E["OUT_F32"]), THIN))
-    out.append(("dense_thin_n12", G.dense_desc(M=131, N=12, K=192, epi=E["BIAS_N"]), THIN))
-    # GroupNorm statistics: channels per group 1, 4, 8, 10, 16, 20, 40; several samples stacked in M
-    for N, groups in ((320, 320), (128, 32), (256, 32), (320, 32), (512, 32), (640, 32), (1280, 32)):
-        out.append((f"conv_gn_n{N}_g{groups}", G.conv_desc(B=3, Hs=8, Ws=8, Cin=64, N=N, epi=E["BIAS_N"] | E["GNSTATS"],
-                                                           gn_groups=groups, gn_rps=64, gn_nslab=2),
-                    N160 + N128 if N % 160 == 0 else N128))
-    # XCD grid remap: tile grids that select xcd_n 1, 2, 4, 8 (tiles_n x tiles_m factorisations of 8)
-    for N, M in ((1280, 256), (640, 512), (320, 1024), (160, 2048)):
-        out.append((f"dense_xcd_n{N}", G.dense_desc(M=M, N=N, K=128, epi=E["BIAS_N"]), (0, 5, 7, 11, 51, 54)))
-    # halo-x variants (opt-in): stride 1, Wo = 64, whole 128-pixel tiles
-    for N in (256, 320):
-        out.append((f"conv_halo_n{N}", G.conv_desc(B=1, Hs=4, Ws=64, Cin=64, N=N, epi=PROD_CONV), (30, 32)))
-    return out
+BNW, SPLITS, _sweep_cases, _vt_desc = G.BNW, G.SPLITS, G._sweep_cases, G._vt_desc
 
 
 SWEEP = _sweep_cases()
-
-
-BNW = {**{c: 80 for c in N160}, **{c: 64 for c in N128}}  # wave-tile columns (FN * 16 of csrc/gemm_tiles.h); thin tiles emit no statistics
 
 
 def test_every_tile_configuration_matches_the_fp64_reference(ctx):
@@ -230,21 +166,6 @@ def test_every_tile_configuration_matches_the_fp64_reference(ctx):
 
 
 # ---- (c) dispatcher-only modes --------------------------------------------------------------------------------------------------
-SPLITS = [
-    # rows per sample <= 64: 64-row tiles, 2 / 4 / 8 slices by K
-    ("dense_rps64_k1024", G.dense_desc(M=256, N=1280, K=1024, epi=E["BIAS_N"] | E["RESIDUAL"], rps_hint=64), 2),
-    ("dense_rps64_k2048", G.dense_desc(M=256, N=1280, K=2048, epi=E["BIAS_N"], rps_hint=64), 4),
-    ("dense_rps64_k8192", G.dense_desc(M=256, N=1280, K=8192, epi=E["BIAS_N"] | E["RESIDUAL"], rps_hint=64), 8),
-    # fused skip: slices that end inside the skip segment (18 main K tiles of 32; 9 of 21)
-    ("conv_skip_4way", G.conv_desc(B=2, Hs=8, Ws=8, Cin=128, N=1024, Cin1=512, Cin2=384, epi=PROD_CONV, rps_hint=64), 4),
-    ("conv_skip_2way", G.conv_desc(B=2, Hs=8, Ws=8, Cin=64, N=1280, Cin1=512, Cin2=256, epi=PROD_CONV, rps_hint=64), 2),
-    # 16x16 level: 128-row tiles, K >= 4096 -> 2; at most 4 tile columns -> 4; the graph's long-K setting (K >= 8192) -> 4
-    ("conv_s2_wide_4way", G.conv_desc(B=2, Hs=32, Ws=32, Cin=640, N=640, stride=2, epi=E["BIAS_N"], rps_hint=256), 4),
-    ("dense_rps256_k5120", G.dense_desc(M=512, N=1280, K=5120, epi=E["BIAS_N"] | E["RESIDUAL"], rps_hint=256), 2),
-    ("dense_rps256_k10240_big4", G.dense_desc(M=512, N=1280, K=10240, epi=E["BIAS_N"], rps_hint=256, sk_big=4), 4),
-]
-
-
 @pytest.mark.parametrize("name,d,ways", SPLITS, ids=[s[0] for s in SPLITS])
 def test_split_k_matches_the_fp64_reference(ctx, name, d, ways):
     info = verify(ctx, d, -1, seed=3, twice=True)
@@ -263,12 +184,6 @@ def test_optin_256_row_split_matches_the_fp64_reference(gpu_ctx, tsd_mod, monkey
         assert replay.lib().tsd_debug_splitk_errors(c.h) == 0
     finally:
         c.close()
-
-
-def _vt_desc():
-    S, C_ = 256, 320
-    return G.dense_desc(M=2 * S, N=3 * C_, K=320, ldc=2 * C_, epi=E["BIAS_N"], vt=1, vt_n0=2 * C_, vt_ld=S, vt_s=S, vt_sb=C_ * S,
-                        rps_hint=S)
 
 
 def test_vt_tail_matches_the_fp64_reference(ctx):
