@@ -250,6 +250,14 @@ int tsd_decoder_forward(tsd_model* m, const float* latents, int B, int L, float*
 /* `Encoder.forward` vae.mojo:131-159 (+ metrics_evals :118-129), batched.  images [B,3,S,S] in
  * [-1,1], noise [B,4,S/8,S/8] -> latents [B,4,S/8,S/8]. */
 int tsd_encoder_forward(tsd_model* m, const float* images, const float* noise, int B, int S, float* latents);
+/* Rectangular forms of the three forwards; the square entries above are their LH == LW == L (SH == SW == S) case, the same launches
+ * and the same bits.  latents / out [B,4,LH,LW], images [B,3,8LH,8LW] (encoder: images [B,3,SH,SW], noise and latents
+ * [B,4,SH/8,SW/8]).  Per side the square rules: LH and LW multiples of 8 (16 for the full-size UNet kinds), SH and SW multiples of 64;
+ * TSD_E_SHAPE otherwise, before any launch or copy. */
+int tsd_diffusion_forward_hw(tsd_model* m, const float* latents, const float* context, const float* time_emb, int B,
+                             int LH, int LW, int T, float* out);
+int tsd_decoder_forward_hw(tsd_model* m, const float* latents, int B, int LH, int LW, float* images);
+int tsd_encoder_forward_hw(tsd_model* m, const float* images, const float* noise, int B, int SH, int SW, float* latents);
 
 /* `CLIP.forward` clip.mojo:90-109 (the step before the hot path), intended semantics
  * (App.A D3/D8/D15/D20): tokens [B][T] int32 ids (T <= 77; rows are zero-padded to 77 like clip.mojo:91-93)
@@ -339,6 +347,8 @@ typedef enum tsd_mask_mode { TSD_MASK_AREA = 0, TSD_MASK_ANY = 1 } tsd_mask_mode
 /* Op level, host fp32 in/out, synchronous.  mask_px [B][8L][8L] -> mask_lat [B][L][L].  Every value must be finite and in [0, 1]
  * (TSD_E_ARG, like an unknown mode); TSD_E_SHAPE for B <= 0 or L <= 0. */
 int tsd_latent_mask_f32(tsd_ctx* ctx, const float* mask_px, int B, int L, int mode, float* mask_lat);
+/* The same for a rectangular mask: mask_px [B][8LH][8LW] -> mask_lat [B][LH][LW]; LH == LW gives the bits of the entry above. */
+int tsd_latent_mask_hw_f32(tsd_ctx* ctx, const float* mask_px, int B, int LH, int LW, int mode, float* mask_lat);
 /* Op level, host fp32 in/out, synchronous: the blend above on x / known / noise / x_out CHW [B][4][hw] and mask [B][hw] (one mask
  * value serves the 4 channels) - the kernel a session with inpainting launches after its sampler update.  noise may be NULL (k =
  * a_prev * known).  x_out may be x.  A non-finite output is counted (TSD_E_NONFINITE): an inf in x under m = 0 comes out as NaN. */
@@ -360,6 +370,12 @@ int tsd_normal_fill_f32(tsd_ctx* ctx, uint64_t seed, uint64_t stream, uint64_t o
 /* B samples, latent side L, T context tokens; cfg != 0 runs the UNet on 2B (cond + uncond,
  * SURVEY.md App.A D10).  `decoder` may be NULL when only latents are wanted. */
 int tsd_session_create(tsd_model* diffusion, tsd_model* decoder, int B, int L, int T, int cfg, tsd_session** out);
+/* A session of rectangular latents [.,4,LH,LW] (images [.,3,8LH,8LW]); tsd_session_create is its LH == LW == L case.  LH and LW are
+ * multiples of 8 (16 for the full-size UNet kinds), TSD_E_SHAPE otherwise.  One session has one shape: every entry below keeps its
+ * signature, and where its comment says L,L the tensor is LH,LW - latents, noise, known [.,4,LH,LW], masks [.,LH,LW], images
+ * [.,3,8LH,8LW] - and L*L is LH*LW.  The seeded-noise counter is the element's index inside its sample, (c*LH + y)*LW + x. */
+int tsd_session_create_hw(tsd_model* diffusion, tsd_model* decoder, int B, int LH, int LW, int T, int cfg, tsd_session** out);
+int tsd_session_shape(tsd_session* s, int* LH, int* LW); /* the session's latent sides */
 int tsd_session_destroy(tsd_session* s);
 /* `DDPMSampler.__init__` + `set_inference_timesteps` sampler.mojo:15-44 (+ `set_strength` :67-73 via
  * start_step: the first `start_step` timesteps are dropped).  beta 0.00085..0.012 scaled-linear. */
@@ -372,7 +388,7 @@ int tsd_session_set_schedule(tsd_session* s, int num_training_steps, int num_inf
 int tsd_session_set_sampler(tsd_session* s, int kind, float eta, int spacing);
 int tsd_session_num_steps(tsd_session* s);
 int tsd_session_timestep(tsd_session* s, int i); /* i-th timestep of the schedule */
-/* Upload state.  latents [B,4,L,L]; context [B,T,768]; uncond_context [B,T,768] or NULL;
+/* Upload state.  latents [B,4,LH,LW] (L,L below: the session's LH,LW); context [B,T,768]; uncond_context [B,T,768] or NULL;
  * noise [nsteps,B,4,L,L] ~ N(0,1) (an input: App.A D19) or NULL for a noiseless update. */
 int tsd_session_upload(tsd_session* s, const float* latents, const float* context, const float* uncond_context,
                        const float* noise, float cfg_scale);

@@ -33,15 +33,18 @@ int run_model(tsd_model* m, F&& fn) {
 }
 }  // namespace
 
-extern "C" int tsd_diffusion_forward(tsd_model* m, const float* latents, const float* context, const float* time_emb,
-                                     int B, int L, int T, float* out) {
+// The square entries are the LH == LW == L case of the *_hw entries below them: one body each.
+extern "C" int tsd_diffusion_forward_hw(tsd_model* m, const float* latents, const float* context, const float* time_emb,
+                                        int B, int LH, int LW, int T, float* out) {
   NOTNULL(m); NOTNULL(latents); NOTNULL(context); NOTNULL(time_emb); NOTNULL(out);
   if (!is_diffusion_kind(m->kind)) TSD_FAIL(TSD_E_ARG, "tsd_diffusion_forward: model is not a Diffusion");
-  if (B <= 0 || B > 16 || L <= 0 || T <= 0) TSD_FAIL(TSD_E_SHAPE, "diffusion: B=%d (1..16) L=%d T=%d", B, L, T);
+  if (B <= 0 || B > 16 || LH <= 0 || LW <= 0 || T <= 0) TSD_FAIL(TSD_E_SHAPE, "diffusion: B=%d (1..16) L=%dx%d T=%d", B, LH, LW, T);
+  const int mult = is_full_unet_kind(m->kind) ? 16 : 8;  // the graph's own rule (graph.cpp), refused here before anything is planned
+  if (LH % mult || LW % mult) TSD_FAIL(TSD_E_SHAPE, "diffusion: latent sides %d x %d must be multiples of %d", LH, LW, mult);
   tsd_ctx* ctx = m->ctx;
   return run_model(m, [&]() -> int {
     const int Tp = round_up(T, 8);
-    const int64_t nl = (int64_t)B * 4 * L * L;
+    const int64_t nl = (int64_t)B * 4 * LH * LW;
     float* dl = arena_alloc<float>(ctx, nl);
     float* dc = arena_alloc<float>(ctx, (int64_t)B * T * 768);
     float* dt = arena_alloc<float>(ctx, (int64_t)B * 320);
@@ -53,45 +56,55 @@ extern "C" int tsd_diffusion_forward(tsd_model* m, const float* latents, const f
     TSD_TRY(h2d(ctx, dt, time_emb, (size_t)B * 320 * 4));
     for (int b = 0; b < B; b++)  // [T][768] -> zero-padded [Tp][768] per sample
       TSD_TRY(launch_f32_to_f16_rows(ctx, dc + (int64_t)b * T * 768, T, 768, c16 + (int64_t)b * Tp * 768, 768, Tp));
-    TSD_TRY(g_unet_forward(m, dl, c16, T, Tp, dt, B, L, de));
+    TSD_TRY(g_unet_forward(m, dl, c16, T, Tp, dt, B, LH, LW, de));
     return d2h(ctx, out, de, nl * 4);
   });
 }
+extern "C" int tsd_diffusion_forward(tsd_model* m, const float* latents, const float* context, const float* time_emb,
+                                     int B, int L, int T, float* out) {
+  return tsd_diffusion_forward_hw(m, latents, context, time_emb, B, L, L, T, out);
+}
 
-extern "C" int tsd_decoder_forward(tsd_model* m, const float* latents, int B, int L, float* images) {
+extern "C" int tsd_decoder_forward_hw(tsd_model* m, const float* latents, int B, int LH, int LW, float* images) {
   NOTNULL(m); NOTNULL(latents); NOTNULL(images);
   if (!is_decoder_kind(m->kind)) TSD_FAIL(TSD_E_ARG, "tsd_decoder_forward: model is not a Decoder");
-  if (B <= 0 || L <= 0) TSD_FAIL(TSD_E_SHAPE, "decoder: B=%d L=%d", B, L);
+  if (B <= 0 || LH <= 0 || LW <= 0 || LH % 8 || LW % 8) TSD_FAIL(TSD_E_SHAPE, "decoder: B=%d L=%dx%d (multiples of 8)", B, LH, LW);
   tsd_ctx* ctx = m->ctx;
   return run_model(m, [&]() -> int {
-    const int64_t nl = (int64_t)B * 4 * L * L, ni = (int64_t)B * 3 * 64 * L * L;
+    const int64_t nl = (int64_t)B * 4 * LH * LW, ni = (int64_t)B * 3 * 64 * LH * LW;
     float* dl = arena_alloc<float>(ctx, nl);
     float* di = arena_alloc<float>(ctx, ni);
     if (!dl || !di) TSD_FAIL(TSD_E_ALLOC, "workspace arena exhausted");
     TSD_TRY(h2d(ctx, dl, latents, nl * 4));
-    TSD_TRY(g_decoder_forward(m, dl, B, L, di));
+    TSD_TRY(g_decoder_forward(m, dl, B, LH, LW, di));
     return d2h(ctx, images, di, ni * 4);
   });
 }
+extern "C" int tsd_decoder_forward(tsd_model* m, const float* latents, int B, int L, float* images) {
+  return tsd_decoder_forward_hw(m, latents, B, L, L, images);
+}
 
-extern "C" int tsd_encoder_forward(tsd_model* m, const float* images, const float* noise, int B, int S,
-                                   float* latents) {
+extern "C" int tsd_encoder_forward_hw(tsd_model* m, const float* images, const float* noise, int B, int SH, int SW,
+                                      float* latents) {
   NOTNULL(m); NOTNULL(images); NOTNULL(noise); NOTNULL(latents);
   if (!is_encoder_kind(m->kind)) TSD_FAIL(TSD_E_ARG, "tsd_encoder_forward: model is not an Encoder");
-  if (B <= 0 || S <= 0 || S % 8) TSD_FAIL(TSD_E_SHAPE, "encoder: B=%d S=%d", B, S);
+  if (B <= 0 || SH <= 0 || SW <= 0 || SH % 64 || SW % 64) TSD_FAIL(TSD_E_SHAPE, "encoder: B=%d S=%dx%d (multiples of 64)", B, SH, SW);
   tsd_ctx* ctx = m->ctx;
   return run_model(m, [&]() -> int {
-    const int L = S / 8;
-    const int64_t ni = (int64_t)B * 3 * S * S, nl = (int64_t)B * 4 * L * L;
+    const int64_t ni = (int64_t)B * 3 * SH * SW, nl = (int64_t)B * 4 * (SH / 8) * (SW / 8);
     float* di = arena_alloc<float>(ctx, ni);
     float* dn = arena_alloc<float>(ctx, nl);
     float* dl = arena_alloc<float>(ctx, nl);
     if (!di || !dn || !dl) TSD_FAIL(TSD_E_ALLOC, "workspace arena exhausted");
     TSD_TRY(h2d(ctx, di, images, ni * 4));
     TSD_TRY(h2d(ctx, dn, noise, nl * 4));
-    TSD_TRY(g_encoder_forward(m, di, dn, B, S, dl));
+    TSD_TRY(g_encoder_forward(m, di, dn, B, SH, SW, dl));
     return d2h(ctx, latents, dl, nl * 4);
   });
+}
+extern "C" int tsd_encoder_forward(tsd_model* m, const float* images, const float* noise, int B, int S,
+                                   float* latents) {
+  return tsd_encoder_forward_hw(m, images, noise, B, S, S, latents);
 }
 
 extern "C" int tsd_clip_forward(tsd_model* m, const int32_t* tokens, int B, int T, float* context) {

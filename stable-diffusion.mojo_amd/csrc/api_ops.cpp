@@ -347,20 +347,23 @@ static bool host_all_in_range(const float* p, size_t n, float lo, float hi) {
 }
 
 // pixel mask -> latent mask (kernels_sampler.hip k_latent_mask) on host tensors
-extern "C" int tsd_latent_mask_f32(tsd_ctx* ctx, const float* mask_px, int B, int L, int mode, float* mask_lat) {
+extern "C" int tsd_latent_mask_hw_f32(tsd_ctx* ctx, const float* mask_px, int B, int LH, int LW, int mode, float* mask_lat) {
   NOTNULL(ctx); NOTNULL(mask_px); NOTNULL(mask_lat);
   if (mode != TSD_MASK_AREA && mode != TSD_MASK_ANY) TSD_FAIL(TSD_E_ARG, "latent mask: mode %d (0 area, 1 any)", mode);
-  if (B <= 0 || L <= 0) TSD_FAIL(TSD_E_SHAPE, "latent mask: B=%d L=%d", B, L);
-  const int64_t npx = (int64_t)B * 64 * L * L, nl = (int64_t)B * L * L;
+  if (B <= 0 || LH <= 0 || LW <= 0) TSD_FAIL(TSD_E_SHAPE, "latent mask: B=%d L=%dx%d", B, LH, LW);
+  const int64_t npx = (int64_t)B * 64 * LH * LW, nl = (int64_t)B * LH * LW;
   if (!host_all_in_range(mask_px, (size_t)npx, 0.f, 1.f)) TSD_FAIL(TSD_E_ARG, "latent mask: every mask value must be finite and in [0, 1]");
   return run_op(ctx, [&]() -> int {
     Dev d{ctx};
     float* dm = d.in(mask_px, npx);
     float* dy = d.buf<float>(nl);
     if (d.err) return d.err;
-    TSD_TRY(launch_latent_mask(ctx, dm, B, L, mode, dy));
+    TSD_TRY(launch_latent_mask(ctx, dm, B, LH, LW, mode, dy));
     return d.out(mask_lat, dy, nl);
   });
+}
+extern "C" int tsd_latent_mask_f32(tsd_ctx* ctx, const float* mask_px, int B, int L, int mode, float* mask_lat) {
+  return tsd_latent_mask_hw_f32(ctx, mask_px, B, L, L, mode, mask_lat);
 }
 
 // the masked-denoising blend (kernels_sampler.hip k_inpaint_blend) on host tensors: the launch a session with inpainting adds to a step.

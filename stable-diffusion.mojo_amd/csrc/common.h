@@ -409,7 +409,7 @@ int launch_fill_normal(tsd_ctx* ctx, float* dst, int64_t n, int64_t per_sample, 
 int launch_inpaint_blend(tsd_ctx* ctx, const float* x, const float* mask, const float* known, const float* noise, int B, int64_t hw,
                          float a_prev, float s_prev, float* x_out);
 // pixel mask [B][8L][8L] -> latent mask [B][L][L] by 8x8 blocks; mode is a tsd_mask_mode
-int launch_latent_mask(tsd_ctx* ctx, const float* mask_px, int B, int L, int mode, float* mask_lat);
+int launch_latent_mask(tsd_ctx* ctx, const float* mask_px, int B, int LH, int LW, int mode, float* mask_lat);
 // ---- slot sessions (kernels_slots.hip): every sample of the batch at its own schedule index ------------------------------------
 // One by-value table serves the whole batch: entry b holds what launch_ddpm_step_seeded / launch_sampler_step(_seeded) would be given for
 // sample b alone.  c[]: SLOT_DDPM { sqrt(abar), sqrt(1 - abar), c_x0, c_xt, sigma } (ddpm_coeffs), SLOT_LMS the SamplerCoeffs in field order.

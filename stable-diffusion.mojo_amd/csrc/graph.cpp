@@ -483,19 +483,19 @@ int g_unet_ctx_kv(tsd_model* m, const half_t* ctx16, int Tp, int B, half_t* kc_a
 
 // ---- `Diffusion.forward` diffusion.mojo:309-318 -------------------------------------------------------
 static int g_unet_full_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, int T, int Tp,
-                               const float* temb, int B, int L, float* eps_out_chw, bool eps_nhwc, const UNetPre* pre);
+                               const float* temb, int B, int LH, int LW, float* eps_out_chw, bool eps_nhwc, const UNetPre* pre);
 
 int g_unet_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, int T, int Tp, const float* temb, int B,
-                   int L, float* eps_out_chw, bool eps_nhwc, const UNetPre* pre) {
+                   int LH, int LW, float* eps_out_chw, bool eps_nhwc, const UNetPre* pre) {
   if (is_full_unet_kind(m->kind)) {
     const int prev = gemm_set_splitk_big(m->ctx, 4);  // measured for this graph at its batch of 4 (BASELINE configs[4]): +4.3 %
-    const int r = g_unet_full_forward(m, latents_chw, ctx16, T, Tp, temb, B, L, eps_out_chw, eps_nhwc, pre);
+    const int r = g_unet_full_forward(m, latents_chw, ctx16, T, Tp, temb, B, LH, LW, eps_out_chw, eps_nhwc, pre);
     gemm_set_splitk_big(m->ctx, prev);
     return r;
   }
   tsd_ctx* ctx = m->ctx;
   const UNetW& u = m->unet;
-  if (L % 8) TSD_FAIL(TSD_E_SHAPE, "UNet: latent side %d must be a multiple of 8", L);
+  if (LH <= 0 || LW <= 0 || LH % 8 || LW % 8) TSD_FAIL(TSD_E_SHAPE, "UNet: latent sides %d x %d must be multiples of 8", LH, LW);
   // ---- time path (diffusion.mojo:17-21 and :61-62 for all nine residual blocks) ----
   const float* tvec = pre ? pre->tvec : nullptr;
   const int tld = pre ? pre->tld : u.tproj.N;
@@ -504,24 +504,24 @@ int g_unet_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, 
   // `Conv2D(4, 320, 3)` (diffusion.mojo:236): the latent's 4 channels padded to a 64-channel NHWC tensor made the implicit GEMM walk
   // nine K tiles with 4 of 64 columns live; gathered to im2col rows at the boundary (36 of 64 columns live) it is ONE K tile
   const bool in_im2col = ctx->opt.conv_in_im2col && u.conv_in_im2col && u.conv1.I == 4;
-  Act x0 = act_alloc(ctx, B, L, L, 64); CHECK_ALLOC(x0.p);
-  if (in_im2col) TSD_TRY(launch_chw_f32_to_im2col3x3_f16(ctx, latents_chw, B, 4, L, L, x0.p));
-  else TSD_TRY(launch_chw_f32_to_nhwc_f16(ctx, latents_chw, B, 4, L, L, 4, 1.f, x0.p, 64));
+  Act x0 = act_alloc(ctx, B, LH, LW, 64); CHECK_ALLOC(x0.p);
+  if (in_im2col) TSD_TRY(launch_chw_f32_to_im2col3x3_f16(ctx, latents_chw, B, 4, LH, LW, x0.p));
+  else TSD_TRY(launch_chw_f32_to_nhwc_f16(ctx, latents_chw, B, 4, LH, LW, 4, 1.f, x0.p, 64));
   Act a[24];
   // every layer output feeds a GroupNorm (the next block's first norm: 32 groups; the output layer's: 320), so it is
   // allocated with room for the statistics its producer's epilogue emits
-  auto alloc_out = [&](int i, int side, int C) -> int {
+  auto alloc_out = [&](int i, int H, int W, int C) -> int {
     // layers 11 and 16 feed GroupNorm(32) over a concat with a narrower skip (1280 + 640, 640 + 320): statistics in the skip's granularity
     const int groups = i == 23 ? 320 : (i == 11 ? concat_stat_groups(C, 640, 32) : (i == 16 ? concat_stat_groups(C, 320, 32) : 32));
-    a[i] = act_alloc_gn(ctx, B, side, side, C, groups);
+    a[i] = act_alloc_gn(ctx, B, H, W, C, groups);
     CHECK_ALLOC(a[i].p);
     return TSD_OK;
   };
-  const int L1 = L / 2, L2 = L / 4;
-  auto res = [&](int i, const CatSrc& src, int side_in, int ups) -> int {
+  const int H1 = LH / 2, W1 = LW / 2, H2 = LH / 4, W2 = LW / 4;
+  auto res = [&](int i, const CatSrc& src, int H_in, int W_in, int ups) -> int {
     const ResW& w = u.res[i - 1];
-    TSD_TRY(alloc_out(i, ups ? side_in * 2 : side_in, w.cout));
-    return g_resblock(ctx, src, B, side_in, side_in, ups, w, tvec, tld, a[i]);
+    TSD_TRY(alloc_out(i, ups ? H_in * 2 : H_in, ups ? W_in * 2 : W_in, w.cout));
+    return g_resblock(ctx, src, B, H_in, W_in, ups, w, tvec, tld, a[i]);
   };
   // context K and V^T projections of all nine attention blocks in two GEMMs (helpers/attention.mojo:102-103;
   // the k_proj / v_proj weights are contiguous in the blob): K_all [B*Tp][6720], V^T_all [B][6720][Tp]
@@ -535,7 +535,7 @@ int g_unet_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, 
     kc_all = kc; vtc_all = vtc;
   }
   auto attn = [&](int i) -> int {
-    TSD_TRY(alloc_out(i, a[i - 1].H, a[i - 1].C));
+    TSD_TRY(alloc_out(i, a[i - 1].H, a[i - 1].W, a[i - 1].C));
     const AttnW& w = u.attn[i - 1];
     CtxKV kv;
     kv.K = kc_all + w.kv_off; kv.ldk = CK; kv.sK = (int64_t)Tp * CK;
@@ -543,19 +543,19 @@ int g_unet_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, 
     return g_unet_attn(ctx, a[i - 1], w, ctx16, T, Tp, a[i], &kv);
   };
   // encoders (diffusion.mojo:236-250)
-  TSD_TRY(alloc_out(1, L, 320));
-  if (in_im2col) TSD_TRY(g_linear(ctx, cat1(x0), (int64_t)B * L * L, u.conv_in_im2col, 64, u.conv1.Opad, 64, u.conv1.b, nullptr, 0, 0, a[1].p,
-                                  a[1].ld, &a[1], L * L));
+  TSD_TRY(alloc_out(1, LH, LW, 320));
+  if (in_im2col) TSD_TRY(g_linear(ctx, cat1(x0), (int64_t)B * LH * LW, u.conv_in_im2col, 64, u.conv1.Opad, 64, u.conv1.b, nullptr, 0, 0, a[1].p,
+                                  a[1].ld, &a[1], LH * LW));
   else TSD_TRY(g_conv3x3(ctx, x0, u.conv1, 1, 1, 1, 0, nullptr, 0, nullptr, 0, false, a[1].p, a[1].ld, &a[1]));
-  TSD_TRY(res(2, cat1(a[1]), L, 0));
+  TSD_TRY(res(2, cat1(a[1]), LH, LW, 0));
   TSD_TRY(attn(3));
-  TSD_TRY(alloc_out(4, L1, 320));
+  TSD_TRY(alloc_out(4, H1, W1, 320));
   TSD_TRY(g_conv3x3(ctx, a[3], u.conv4, 2, 1, 1, 0, nullptr, 0, nullptr, 0, false, a[4].p, a[4].ld, &a[4]));
-  TSD_TRY(res(5, cat1(a[4]), L1, 0));
+  TSD_TRY(res(5, cat1(a[4]), H1, W1, 0));
   TSD_TRY(attn(6));
-  TSD_TRY(alloc_out(7, L2, 640));
+  TSD_TRY(alloc_out(7, H2, W2, 640));
   TSD_TRY(g_conv3x3(ctx, a[6], u.conv7, 2, 1, 1, 0, nullptr, 0, nullptr, 0, false, a[7].p, a[7].ld, &a[7]));
-  TSD_TRY(res(8, cat1(a[7]), L2, 0));
+  TSD_TRY(res(8, cat1(a[7]), H2, W2, 0));
   TSD_TRY(attn(9));
   // decoders (diffusion.mojo:253-272); skip4 / skip2 are dead (App.A D11): layers 15 and 20 declare
   // fewer input channels than the concat provides and only read the first in_channels.
@@ -563,32 +563,32 @@ int g_unet_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, 
   // skip weights added at model_check_ready (UNetW::res_dup) it is a 1280 -> 1280 block over the one tensor.  The choice depends on the
   // model and the context's options alone, so the planning pass and the real pass take the same branch.
   if (u.res_dup_on && ctx->opt.fold_dup && a[9].C == u.res_dup.cin) {
-    TSD_TRY(alloc_out(10, L2, u.res_dup.cout));
-    TSD_TRY(g_resblock(ctx, cat1(a[9]), B, L2, L2, 0, u.res_dup, tvec, tld, a[10]));
+    TSD_TRY(alloc_out(10, H2, W2, u.res_dup.cout));
+    TSD_TRY(g_resblock(ctx, cat1(a[9]), B, H2, W2, 0, u.res_dup, tvec, tld, a[10]));
   } else
-  TSD_TRY(res(10, cat2(a[9], a[9]), L2, 0));
+  TSD_TRY(res(10, cat2(a[9], a[9]), H2, W2, 0));
   TSD_TRY(attn(11));
-  TSD_TRY(res(12, cat2(a[11], a[7]), L2, 0));
+  TSD_TRY(res(12, cat2(a[11], a[7]), H2, W2, 0));
   TSD_TRY(attn(13));
-  TSD_TRY(res(15, cat1(a[13]), L2, 1));  // layer14 Upsample folded into the conv/residual addressing
+  TSD_TRY(res(15, cat1(a[13]), H2, W2, 1));  // layer14 Upsample folded into the conv/residual addressing
   a[14] = a[15];
   TSD_TRY(attn(16));
-  TSD_TRY(res(17, cat2(a[16], a[4]), L1, 0));
+  TSD_TRY(res(17, cat2(a[16], a[4]), H1, W1, 0));
   TSD_TRY(attn(18));
-  TSD_TRY(res(20, cat1(a[18]), L1, 1));  // layer19 Upsample folded
+  TSD_TRY(res(20, cat1(a[18]), H1, W1, 1));  // layer19 Upsample folded
   a[19] = a[20];
   TSD_TRY(attn(21));
-  TSD_TRY(res(22, cat2(a[21], a[1]), L, 0));
+  TSD_TRY(res(22, cat2(a[21], a[1]), LH, LW, 0));
   TSD_TRY(attn(23));
   // `UNet_Output_Layer` diffusion.mojo:287-291: GroupNorm(320 groups) -> SiLU -> Conv3x3(320,4)
-  Act hf = act_alloc(ctx, B, L, L, 320); CHECK_ALLOC(hf.p);
-  TSD_TRY(launch_groupnorm(ctx, norm_src(cat1(a[23]), 320), B, L * L, 320, 320, 1e-5f, 1.f, 1, hf.p, hf.ld,
+  Act hf = act_alloc(ctx, B, LH, LW, 320); CHECK_ALLOC(hf.p);
+  TSD_TRY(launch_groupnorm(ctx, norm_src(cat1(a[23]), 320), B, LH * LW, 320, 320, 1e-5f, 1.f, 1, hf.p, hf.ld,
                            a[23].gn_groups == 320 ? a[23].gn_part : nullptr, a[23].gn_nslab));
-  if (eps_nhwc && u.final_conv.Opad == 4)  // the caller reads [B][L*L][4] directly
+  if (eps_nhwc && u.final_conv.Opad == 4)  // the caller reads [B][LH*LW][4] directly
     return g_conv3x3(ctx, hf, u.final_conv, 1, 1, 1, 0, nullptr, 0, nullptr, 0, true, eps_out_chw, 4);
-  float* eps_tmp = arena_alloc<float>(ctx, (int64_t)B * L * L * 4); CHECK_ALLOC(eps_tmp);
+  float* eps_tmp = arena_alloc<float>(ctx, (int64_t)B * LH * LW * 4); CHECK_ALLOC(eps_tmp);
   TSD_TRY(g_conv3x3(ctx, hf, u.final_conv, 1, 1, 1, 0, nullptr, 0, nullptr, 0, true, eps_tmp, 4));
-  TSD_TRY(launch_nhwc_f32_to_chw_f32(ctx, eps_tmp, B, 4, L, L, 4, eps_out_chw));
+  TSD_TRY(launch_nhwc_f32_to_chw_f32(ctx, eps_tmp, B, 4, LH, LW, 4, eps_out_chw));
   return TSD_OK;
 }
 
@@ -596,18 +596,18 @@ int g_unet_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, 
 // Encoders push their output; every decoder residual block reads concat(x, popped skip) through the two-source views;
 // Upsample + conv3x3 is one implicit-GEMM launch that reads its input through the nearest-2x addressing.
 static int g_unet_full_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, int T, int Tp,
-                               const float* temb, int B, int L, float* eps_out_chw, bool eps_nhwc, const UNetPre* pre) {
+                               const float* temb, int B, int LH, int LW, float* eps_out_chw, bool eps_nhwc, const UNetPre* pre) {
   tsd_ctx* ctx = m->ctx;
   const UNetW& u = m->unet;
-  if (L % 16) TSD_FAIL(TSD_E_SHAPE, "full-size UNet: latent side %d must be a multiple of 16", L);
+  if (LH <= 0 || LW <= 0 || LH % 16 || LW % 16) TSD_FAIL(TSD_E_SHAPE, "full-size UNet: latent sides %d x %d must be multiples of 16", LH, LW);
   const float* tvec = pre ? pre->tvec : nullptr;
   const int tld = pre ? pre->tld : u.tproj.N;
   if (!pre) TSD_TRY(g_unet_time_path(m, temb, B, &tvec));
   const bool in_im2col = ctx->opt.conv_in_im2col && u.conv_in_im2col && !u.conv.empty() && u.conv[0].I == 4 && SD15_STEPS[0].l.kind == L_CONV &&
                          SD15_STEPS[0].l.d == 1;  // as in g_unet_forward: the 4-channel input convolution as one im2col K tile
-  Act x0 = act_alloc(ctx, B, L, L, 64); CHECK_ALLOC(x0.p);
-  if (in_im2col) TSD_TRY(launch_chw_f32_to_im2col3x3_f16(ctx, latents_chw, B, 4, L, L, x0.p));
-  else TSD_TRY(launch_chw_f32_to_nhwc_f16(ctx, latents_chw, B, 4, L, L, 4, 1.f, x0.p, 64));
+  Act x0 = act_alloc(ctx, B, LH, LW, 64); CHECK_ALLOC(x0.p);
+  if (in_im2col) TSD_TRY(launch_chw_f32_to_im2col3x3_f16(ctx, latents_chw, B, 4, LH, LW, x0.p));
+  else TSD_TRY(launch_chw_f32_to_nhwc_f16(ctx, latents_chw, B, 4, LH, LW, 4, 1.f, x0.p, 64));
   // context K and V^T of all sixteen attention blocks in two GEMMs
   const int CK = u.kproj_all.N;
   const half_t* kc_all = pre ? pre->kc_all : nullptr;
@@ -634,11 +634,10 @@ static int g_unet_full_forward(tsd_model* m, const float* latents_chw, const hal
     };
     Act y;
     if (l.kind == L_CONV) {
-      const int side = cur.H / l.d;
-      y = act_alloc_gn(ctx, B, side, side, l.b, next_groups); CHECK_ALLOC(y.p);
+      y = act_alloc_gn(ctx, B, cur.H / l.d, cur.W / l.d, l.b, next_groups); CHECK_ALLOC(y.p);
       if (i == 0 && in_im2col)
-        TSD_TRY(g_linear(ctx, cat1(cur), (int64_t)B * L * L, u.conv_in_im2col, 64, u.conv[0].Opad, 64, u.conv[0].b, nullptr, 0, 0, y.p, y.ld,
-                         &y, L * L));
+        TSD_TRY(g_linear(ctx, cat1(cur), (int64_t)B * LH * LW, u.conv_in_im2col, 64, u.conv[0].Opad, 64, u.conv[0].b, nullptr, 0, 0, y.p, y.ld,
+                         &y, LH * LW));
       else
       TSD_TRY(g_conv3x3(ctx, cur, u.conv[i], l.d, 1, 1, 0, nullptr, 0, nullptr, 0, false, y.p, y.ld, &y));
     } else if (l.kind == L_UPCONV) {
@@ -649,7 +648,7 @@ static int g_unet_full_forward(tsd_model* m, const float* latents_chw, const hal
       if (st.flags & U_POP) {
         if (skips.empty()) TSD_FAIL(TSD_E_STATE, "full-size UNet: skip stack underflow at layer %d", i + 1);
         const Act sk = skips.back(); skips.pop_back();
-        if (sk.H != cur.H || cur.C + sk.C != l.a) TSD_FAIL(TSD_E_STATE, "full-size UNet: skip mismatch at layer %d", i + 1);
+        if (sk.H != cur.H || sk.W != cur.W || cur.C + sk.C != l.a) TSD_FAIL(TSD_E_STATE, "full-size UNet: skip mismatch at layer %d", i + 1);
         src = cat2(cur, sk);
       }
       y = act_alloc_gn(ctx, B, cur.H, cur.W, l.b, stat_groups(l.b)); CHECK_ALLOC(y.p);
@@ -665,15 +664,15 @@ static int g_unet_full_forward(tsd_model* m, const float* latents_chw, const hal
     cur = y;
     if (st.flags & U_PUSH) skips.push_back(cur);
   }
-  Act hf = act_alloc(ctx, B, L, L, 320); CHECK_ALLOC(hf.p);
-  TSD_TRY(launch_groupnorm(ctx, norm_src(cat1(cur), 320), B, L * L, 320, u.final_groups, 1e-5f, 1.f, 1, hf.p, hf.ld,
+  Act hf = act_alloc(ctx, B, LH, LW, 320); CHECK_ALLOC(hf.p);
+  TSD_TRY(launch_groupnorm(ctx, norm_src(cat1(cur), 320), B, LH * LW, 320, u.final_groups, 1e-5f, 1.f, 1, hf.p, hf.ld,
                            cur.gn_groups == u.final_groups ? cur.gn_part : nullptr, cur.gn_nslab,
                            u.final_gn.w ? &u.final_gn : nullptr));
-  if (eps_nhwc && u.final_conv.Opad == 4)  // the caller reads [B][L*L][4] directly
+  if (eps_nhwc && u.final_conv.Opad == 4)  // the caller reads [B][LH*LW][4] directly
     return g_conv3x3(ctx, hf, u.final_conv, 1, 1, 1, 0, nullptr, 0, nullptr, 0, true, eps_out_chw, 4);
-  float* eps_tmp = arena_alloc<float>(ctx, (int64_t)B * L * L * 4); CHECK_ALLOC(eps_tmp);
+  float* eps_tmp = arena_alloc<float>(ctx, (int64_t)B * LH * LW * 4); CHECK_ALLOC(eps_tmp);
   TSD_TRY(g_conv3x3(ctx, hf, u.final_conv, 1, 1, 1, 0, nullptr, 0, nullptr, 0, true, eps_tmp, 4));
-  TSD_TRY(launch_nhwc_f32_to_chw_f32(ctx, eps_tmp, B, 4, L, L, 4, eps_out_chw));
+  TSD_TRY(launch_nhwc_f32_to_chw_f32(ctx, eps_tmp, B, 4, LH, LW, 4, eps_out_chw));
   return TSD_OK;
 }
 
@@ -684,7 +683,7 @@ static bool vae_in_im2col(const tsd_model* m, const LayerDef* layers) {
   return m->ctx->opt.conv_in_im2col && m->vae.conv_in_im2col && layers[0].kind == L_CONV && layers[0].c == 3 && !m->vae.conv.empty() && m->vae.conv[0].I <= 7;
 }
 static int run_vae(tsd_model* m, const LayerDef* layers, int n_layers, Act cur, bool final_f32, float* out_nhwc_f32,
-                   int* out_side, int* out_ld) {
+                   int* out_H, int* out_W, int* out_ld) {
   tsd_ctx* ctx = m->ctx;
   const VaeW& v = m->vae;
   const int B = cur.B;
@@ -720,26 +719,26 @@ static int run_vae(tsd_model* m, const LayerDef* layers, int n_layers, Act cur, 
       const int stride = l.kind == L_CONV_S2 ? 2 : 1;
       const int pad = l.kind == L_CONV_S2 ? 0 : (l.c == 3 ? 1 : 0);
       const int pad_br = l.kind == L_CONV_S2 ? 1 : pad;  // two_stride_pad (0,1),(0,1), vae.mojo:115-116
-      const int side_in = pending_up ? cur.H * 2 : cur.H;
-      const int side = l.kind == L_CONV_S2 ? side_in / 2 : side_in;
+      const int H_in = pending_up ? cur.H * 2 : cur.H, W_in = pending_up ? cur.W * 2 : cur.W;
+      const int Ho = l.kind == L_CONV_S2 ? H_in / 2 : H_in, Wo = l.kind == L_CONV_S2 ? W_in / 2 : W_in;
       if (last && final_f32) {
         if (l.c == 3) TSD_TRY(g_conv3x3(ctx, cur, w, stride, pad, pad_br, pending_up, nullptr, 0, nullptr, 0, true, out_nhwc_f32, w.Opad));
         else {
           GemmArgs g;
-          g.A0 = cur.p; g.lda0 = cur.ld; g.Wt = w.w; g.ldw = w.Ipad; g.M = B * side * side; g.N = w.Opad; g.K = w.Ipad;
+          g.A0 = cur.p; g.lda0 = cur.ld; g.Wt = w.w; g.ldw = w.Ipad; g.M = B * Ho * Wo; g.N = w.Opad; g.K = w.Ipad;
           g.epi = EPI_BIAS_N | EPI_OUT_F32; g.bias = w.b; g.C = out_nhwc_f32; g.ldc = w.Opad;
           TSD_TRY(launch_gemm(ctx, g));
         }
-        *out_side = side; *out_ld = w.Opad;
+        *out_H = Ho; *out_W = Wo; *out_ld = w.Opad;
         return TSD_OK;
       }
-      Act y = act_alloc_gn(ctx, B, side, side, w.Opad, next_groups(i)); CHECK_ALLOC(y.p);
+      Act y = act_alloc_gn(ctx, B, Ho, Wo, w.Opad, next_groups(i)); CHECK_ALLOC(y.p);
       if (i == 0 && vae_in_im2col(m, layers))  // cur holds im2col rows [B*H*W][64]
-        TSD_TRY(g_linear(ctx, cat1(cur), (int64_t)B * side * side, v.conv_in_im2col, 64, w.Opad, 64, w.b, nullptr, 0, 0, y.p, y.ld, &y,
-                         side * side));
+        TSD_TRY(g_linear(ctx, cat1(cur), (int64_t)B * Ho * Wo, v.conv_in_im2col, 64, w.Opad, 64, w.b, nullptr, 0, 0, y.p, y.ld, &y,
+                         Ho * Wo));
       else if (l.c == 3) TSD_TRY(g_conv3x3(ctx, cur, w, stride, pad, pad_br, pending_up, nullptr, 0, nullptr, 0, false, y.p, y.ld, &y));
-      else TSD_TRY(g_linear(ctx, cat1(cur), (int64_t)B * side * side, w.w, w.Ipad, w.Opad, w.Ipad, w.b, nullptr, 0, 0, y.p, y.ld, &y,
-                            side * side));
+      else TSD_TRY(g_linear(ctx, cat1(cur), (int64_t)B * Ho * Wo, w.w, w.Ipad, w.Opad, w.Ipad, w.b, nullptr, 0, 0, y.p, y.ld, &y,
+                            Ho * Wo));
       pending_up = 0;
       cur = y;
       continue;
@@ -758,33 +757,33 @@ static int run_vae(tsd_model* m, const LayerDef* layers, int n_layers, Act cur, 
   return TSD_OK;
 }
 
-int g_decoder_forward(tsd_model* m, const float* latents_chw, int B, int L, float* images_chw) {
+int g_decoder_forward(tsd_model* m, const float* latents_chw, int B, int LH, int LW, float* images_chw) {
   tsd_ctx* ctx = m->ctx;
-  if (L % 8) TSD_FAIL(TSD_E_SHAPE, "decoder: latent side %d must be a multiple of 8", L);
-  Act x0 = act_alloc(ctx, B, L, L, 64); CHECK_ALLOC(x0.p);
-  if (vae_in_im2col(m, DECODER_LAYERS)) TSD_TRY(launch_chw_f32_to_im2col3x3_f16(ctx, latents_chw, B, 4, L, L, x0.p, 1.f / 0.18215f));
-  else TSD_TRY(launch_chw_f32_to_nhwc_f16(ctx, latents_chw, B, 4, L, L, 4, 1.f / 0.18215f, x0.p, 64));  // vae.mojo:222
-  const int S = 8 * L;
-  float* img = arena_alloc<float>(ctx, (int64_t)B * S * S * 4); CHECK_ALLOC(img);
-  int side = 0, ld = 0;
-  TSD_TRY(run_vae(m, DECODER_LAYERS, 26, x0, true, img, &side, &ld));
-  if (ctx->launch() && (side != S || ld != 4)) TSD_FAIL(TSD_E_STATE, "decoder: unexpected output %d/%d", side, ld);
-  TSD_TRY(launch_nhwc_f32_to_chw_f32(ctx, img, B, 3, S, S, 4, images_chw));
+  if (LH <= 0 || LW <= 0 || LH % 8 || LW % 8) TSD_FAIL(TSD_E_SHAPE, "decoder: latent sides %d x %d must be multiples of 8", LH, LW);
+  Act x0 = act_alloc(ctx, B, LH, LW, 64); CHECK_ALLOC(x0.p);
+  if (vae_in_im2col(m, DECODER_LAYERS)) TSD_TRY(launch_chw_f32_to_im2col3x3_f16(ctx, latents_chw, B, 4, LH, LW, x0.p, 1.f / 0.18215f));
+  else TSD_TRY(launch_chw_f32_to_nhwc_f16(ctx, latents_chw, B, 4, LH, LW, 4, 1.f / 0.18215f, x0.p, 64));  // vae.mojo:222
+  const int SH = 8 * LH, SW = 8 * LW;
+  float* img = arena_alloc<float>(ctx, (int64_t)B * SH * SW * 4); CHECK_ALLOC(img);
+  int oh = 0, ow = 0, ld = 0;
+  TSD_TRY(run_vae(m, DECODER_LAYERS, 26, x0, true, img, &oh, &ow, &ld));
+  if (ctx->launch() && (oh != SH || ow != SW || ld != 4)) TSD_FAIL(TSD_E_STATE, "decoder: unexpected output %dx%d/%d", oh, ow, ld);
+  TSD_TRY(launch_nhwc_f32_to_chw_f32(ctx, img, B, 3, SH, SW, 4, images_chw));
   return TSD_OK;
 }
 
-int g_encoder_forward(tsd_model* m, const float* images_chw, const float* noise_chw, int B, int S, float* latents_chw) {
+int g_encoder_forward(tsd_model* m, const float* images_chw, const float* noise_chw, int B, int SH, int SW, float* latents_chw) {
   tsd_ctx* ctx = m->ctx;
-  if (S % 64) TSD_FAIL(TSD_E_SHAPE, "encoder: image side %d must be a multiple of 64", S);
-  Act x0 = act_alloc(ctx, B, S, S, 64); CHECK_ALLOC(x0.p);
-  if (vae_in_im2col(m, ENCODER_LAYERS)) TSD_TRY(launch_chw_f32_to_im2col3x3_f16(ctx, images_chw, B, 3, S, S, x0.p));
-  else TSD_TRY(launch_chw_f32_to_nhwc_f16(ctx, images_chw, B, 3, S, S, 3, 1.f, x0.p, 64));
-  const int L = S / 8;
-  float* mom = arena_alloc<float>(ctx, (int64_t)B * L * L * 8); CHECK_ALLOC(mom);
-  int side = 0, ld = 0;
-  TSD_TRY(run_vae(m, ENCODER_LAYERS, 19, x0, true, mom, &side, &ld));
-  if (ctx->launch() && (side != L || ld != 8)) TSD_FAIL(TSD_E_STATE, "encoder: unexpected output %d/%d", side, ld);
-  TSD_TRY(launch_encoder_sample(ctx, mom, B, L * L, 8, noise_chw, latents_chw));
+  if (SH <= 0 || SW <= 0 || SH % 64 || SW % 64) TSD_FAIL(TSD_E_SHAPE, "encoder: image sides %d x %d must be multiples of 64", SH, SW);
+  Act x0 = act_alloc(ctx, B, SH, SW, 64); CHECK_ALLOC(x0.p);
+  if (vae_in_im2col(m, ENCODER_LAYERS)) TSD_TRY(launch_chw_f32_to_im2col3x3_f16(ctx, images_chw, B, 3, SH, SW, x0.p));
+  else TSD_TRY(launch_chw_f32_to_nhwc_f16(ctx, images_chw, B, 3, SH, SW, 3, 1.f, x0.p, 64));
+  const int LH = SH / 8, LW = SW / 8;
+  float* mom = arena_alloc<float>(ctx, (int64_t)B * LH * LW * 8); CHECK_ALLOC(mom);
+  int oh = 0, ow = 0, ld = 0;
+  TSD_TRY(run_vae(m, ENCODER_LAYERS, 19, x0, true, mom, &oh, &ow, &ld));
+  if (ctx->launch() && (oh != LH || ow != LW || ld != 8)) TSD_FAIL(TSD_E_STATE, "encoder: unexpected output %dx%d/%d", oh, ow, ld);
+  TSD_TRY(launch_encoder_sample(ctx, mom, B, LH * LW, 8, noise_chw, latents_chw));
   return TSD_OK;
 }
 

@@ -67,8 +67,8 @@ int g_attn_core(tsd_ctx* ctx, const AttnArgs& fa);
 int g_qkv_proj(tsd_ctx* ctx, const half_t* x, int B, int S, int C, const LinW& in_proj, half_t* qk, half_t* vt, int Sp);
 
 // module forwards on device buffers
-// latents: fp32 CHW [B,4,L,L]; context16: fp16 [B][Tp][768]; temb: fp32 [B][320]; eps_out: fp32 CHW [B,4,L,L]
-// eps_nhwc: eps_out receives the output convolution's own layout, fp32 [B][L*L][4], instead of CHW (the denoise session's DDPM update
+// latents: fp32 CHW [B,4,LH,LW]; context16: fp16 [B][Tp][768]; temb: fp32 [B][320]; eps_out: fp32 CHW [B,4,LH,LW]
+// eps_nhwc: eps_out receives the output convolution's own layout, fp32 [B][LH*LW][4], instead of CHW (the denoise session's DDPM update
 // reads it directly: one conversion launch per step less)
 // pre: what the forward computes from the timestep and the context alone, made ahead by the caller (the denoise session keeps both
 // across the steps of an upload()).  Absent, the forward launches the two helpers below itself; present, it launches nothing for them
@@ -79,11 +79,11 @@ struct UNetPre {
   const half_t* vtc_all = nullptr;           // context V^T [B][CK][Tp]
 };
 int g_unet_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, int T, int Tp, const float* temb, int B,
-                   int L, float* eps_out_chw, bool eps_nhwc = false, const UNetPre* pre = nullptr);
+                   int LH, int LW, float* eps_out_chw, bool eps_nhwc = false, const UNetPre* pre = nullptr);
 int g_unet_time_path(tsd_model* m, const float* temb, int B, const float** tvec_out);  // -> tvec [B][tproj.N] in the arena
 int g_unet_ctx_kv(tsd_model* m, const half_t* ctx16, int Tp, int B, half_t* kc_all, half_t* vtc_all);
-int g_decoder_forward(tsd_model* m, const float* latents_chw, int B, int L, float* images_chw);
-int g_encoder_forward(tsd_model* m, const float* images_chw, const float* noise_chw, int B, int S, float* latents_chw);
+int g_decoder_forward(tsd_model* m, const float* latents_chw, int B, int LH, int LW, float* images_chw);
+int g_encoder_forward(tsd_model* m, const float* images_chw, const float* noise_chw, int B, int SH, int SW, float* latents_chw);
 
 // run `fn` once in planning mode to size the arena, reserve it, then for real
 template <class F>

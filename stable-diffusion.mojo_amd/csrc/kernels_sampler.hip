@@ -117,18 +117,18 @@ int launch_inpaint_blend(tsd_ctx* ctx, const float* x, const float* mask, const 
   return TSD_OK;
 }
 
-// Pixel mask [B][8L][8L] -> latent mask [B][L][L]: one thread per latent cell reduces its 8x8 block, rows top to bottom and left to
+// Pixel mask [B][8LH][8LW] -> latent mask [B][LH][LW]: one thread per latent cell reduces its 8x8 block, rows top to bottom and left to
 // right within a row (a fixed order; one rounding per addition).
 //   TSD_MASK_AREA: the sum of the 64 values times 1/64 (a power of two: exact)
 //   TSD_MASK_ANY:  1 if the block's maximum is >= 0.5, else 0 - a latent cell that touches any masked pixel is regenerated
-__global__ void k_latent_mask(const float* __restrict__ mask_px, int B, int L, int mode, float* __restrict__ mask_lat) {
+__global__ void k_latent_mask(const float* __restrict__ mask_px, int B, int LH, int LW, int mode, float* __restrict__ mask_lat) {
 #pragma clang fp contract(off)
-  const int64_t n = (int64_t)B * L * L;
-  const int W = 8 * L;
+  const int64_t hw = (int64_t)LH * LW, n = B * hw;
+  const int H = 8 * LH, W = 8 * LW;
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const int64_t b = i / ((int64_t)L * L);
-    const int cell = (int)(i - b * L * L), cy = cell / L, cx = cell - cy * L;
-    const float* src = mask_px + (b * W + (int64_t)cy * 8) * W + cx * 8;
+    const int64_t b = i / hw;
+    const int cell = (int)(i - b * hw), cy = cell / LW, cx = cell - cy * LW;
+    const float* src = mask_px + (b * H + (int64_t)cy * 8) * W + cx * 8;
     float sum = 0.f, mx = 0.f;
     for (int r = 0; r < 8; r++)
       for (int c = 0; c < 8; c++) {
@@ -139,10 +139,10 @@ __global__ void k_latent_mask(const float* __restrict__ mask_px, int B, int L, i
     mask_lat[i] = mode == TSD_MASK_ANY ? (mx >= 0.5f ? 1.f : 0.f) : sum * 0.015625f;
   }
 }
-int launch_latent_mask(tsd_ctx* ctx, const float* mask_px, int B, int L, int mode, float* mask_lat) {
+int launch_latent_mask(tsd_ctx* ctx, const float* mask_px, int B, int LH, int LW, int mode, float* mask_lat) {
   if (!ctx->launch()) return TSD_OK;
   ProfScope prof(ctx, KC_ELEMENTWISE);
-  hipLaunchKernelGGL(k_latent_mask, GRID1D((int64_t)B * L * L, 256), dim3(256), 0, ctx->stream, mask_px, B, L, mode, mask_lat);
+  hipLaunchKernelGGL(k_latent_mask, GRID1D((int64_t)B * LH * LW, 256), dim3(256), 0, ctx->stream, mask_px, B, LH, LW, mode, mask_lat);
   HIP_TRY(hipGetLastError());
   return TSD_OK;
 }

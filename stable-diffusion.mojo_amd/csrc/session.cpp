@@ -16,23 +16,23 @@ struct tsd_session {
   tsd_model* unet = nullptr;
   tsd_model* dec = nullptr;
   tsd_ctx* ctx = nullptr;
-  int B = 0, L = 0, T = 0, Tp = 0, cfg = 0;
+  int B = 0, LH = 0, LW = 0, T = 0, Tp = 0, cfg = 0;  // one shape per session: latents [.,4,LH,LW]
   float cfg_scale = 7.5f;
   // persistent device state (own allocation, not the arena)
   char* state = nullptr;
-  float* latents = nullptr;   // [B,4,L,L] fp32 CHW (the reference's own layout)
-  float* lat2 = nullptr;      // [2B,4,L,L] duplicated latents for the CFG batch
+  float* latents = nullptr;   // [B,4,LH,LW] fp32 CHW (the reference's own layout)
+  float* lat2 = nullptr;      // [2B,4,LH,LW] duplicated latents for the CFG batch
   half_t* ctx16 = nullptr;    // [B or 2B][Tp][768]
-  float* eps = nullptr;       // [B or 2B,4,L,L]
+  float* eps = nullptr;       // [B or 2B,4,LH,LW]
   float* tdev = nullptr;      // [16] timestep per sample
   float* temb = nullptr;      // [16][320]
-  float* noise = nullptr;     // [nsteps,B,4,L,L] or null
-  float* images = nullptr;    // [B,3,8L,8L]
-  float* hist = nullptr;      // [B,4,L,L] fp32: the data prediction x0 of the previous step (DPM-Solver++(2M))
+  float* noise = nullptr;     // [nsteps,B,4,LH,LW] or null
+  float* images = nullptr;    // [B,3,8LH,8LW]
+  float* hist = nullptr;      // [B,4,LH,LW] fp32: the data prediction x0 of the previous step (DPM-Solver++(2M))
   // masked denoising (tsd_session_set_inpaint): carved from `state` like the rest, filled by set_inpaint, read by the blend of a step
-  float* ip_mask = nullptr;   // [B][L*L] fp32 in [0,1]: 1 = regenerate, 0 = keep `ip_known`
-  float* ip_known = nullptr;  // [B,4,L,L] the original latents
-  float* ip_noise = nullptr;  // [B,4,L,L] the noise they are re-noised with
+  float* ip_mask = nullptr;   // [B][LH*LW] fp32 in [0,1]: 1 = regenerate, 0 = keep `ip_known`
+  float* ip_known = nullptr;  // [B,4,LH,LW] the original latents
+  float* ip_noise = nullptr;  // [B,4,LH,LW] the noise they are re-noised with
   double* gr_part = nullptr;  // [16][CFG_RESCALE_GMAX][4] fp64: the partial moments of a step's guidance rescale (kernels_guidance.hip)
   size_t noise_cap = 0;
   // What a step's UNet forward computes from the timestep and the context alone (graph.h UNetPre), made once per upload() by
@@ -214,12 +214,12 @@ static int session_refresh(tsd_session* s) {
   return TSD_OK;
 }
 // The UNet forward of a step or an advance: latents (twice under CFG: model_input for both passes is the same latents,
-// pipeline.mojo:107-108) -> eps.  `pre` is read under the hoist only.  eps stays in the output convolution's layout ([B][L*L][4])
+// pipeline.mojo:107-108) -> eps.  `pre` is read under the hoist only.  eps stays in the output convolution's layout ([B][LH*LW][4])
 // where the forward can write it; the updates read it as such (no conversion launch): *eps_hw is their eps_hw argument.
 static int session_forward(tsd_session* s, const UNetPre* pre, int* eps_hw) {
   tsd_ctx* ctx = s->ctx;
   const int Bu = s->cfg ? 2 * s->B : s->B;
-  const size_t nl = (size_t)s->B * 4 * s->L * s->L;
+  const size_t nl = (size_t)s->B * 4 * s->LH * s->LW;
   const float* lat_in = s->latents;
   if (s->cfg) {
     HIP_TRY(hipMemcpyAsync(s->lat2, s->latents, nl * 4, hipMemcpyDeviceToDevice, ctx->stream));
@@ -228,9 +228,9 @@ static int session_forward(tsd_session* s, const UNetPre* pre, int* eps_hw) {
   }
   ctx->arena.top = 0;
   const bool eps_nhwc = s->unet->unet.final_conv.Opad == 4;  // g_unet_forward's condition for writing that layout
-  TSD_TRY(g_unet_forward(s->unet, lat_in, s->ctx16, s->T, s->Tp, s->temb, Bu, s->L, s->eps, eps_nhwc, s->hoist ? pre : nullptr));
+  TSD_TRY(g_unet_forward(s->unet, lat_in, s->ctx16, s->T, s->Tp, s->temb, Bu, s->LH, s->LW, s->eps, eps_nhwc, s->hoist ? pre : nullptr));
   ctx->arena.top = 0;
-  *eps_hw = eps_nhwc ? s->L * s->L : 0;
+  *eps_hw = eps_nhwc ? s->LH * s->LW : 0;
   return TSD_OK;
 }
 // The scalars and flags of step i of this session's schedule (sampler_step_plan fills mode, flags and c[]; cfg_scale is the caller's)
@@ -259,26 +259,28 @@ static void schedule_changed(tsd_session* s) {
   session_latents_changed(s);
 }
 
-extern "C" int tsd_session_create(tsd_model* diffusion, tsd_model* decoder, int B, int L, int T, int cfg,
-                                  tsd_session** out) {
+extern "C" int tsd_session_create_hw(tsd_model* diffusion, tsd_model* decoder, int B, int LH, int LW, int T, int cfg,
+                                     tsd_session** out) {
   NOTNULL(diffusion); NOTNULL(out);
   if (!is_diffusion_kind(diffusion->kind)) TSD_FAIL(TSD_E_ARG, "session: first model must be a Diffusion");
   if (decoder && (!is_decoder_kind(decoder->kind) || decoder->ctx != diffusion->ctx))
     TSD_FAIL(TSD_E_ARG, "session: decoder must be a Decoder on the same context");
   const int Bu = cfg ? 2 * B : B;
-  if (B <= 0 || Bu > 16 || L <= 0 || L % 8 || T <= 0) TSD_FAIL(TSD_E_SHAPE, "session: B=%d (UNet batch %d <= 16) L=%d T=%d", B, Bu, L, T);
+  const int mult = is_full_unet_kind(diffusion->kind) ? 16 : 8;  // the UNet graph's rule per side (graph.cpp)
+  if (B <= 0 || Bu > 16 || LH <= 0 || LW <= 0 || LH % mult || LW % mult || T <= 0)
+    TSD_FAIL(TSD_E_SHAPE, "session: B=%d (UNet batch %d <= 16) L=%dx%d (multiples of %d) T=%d", B, Bu, LH, LW, mult, T);
   tsd_ctx* ctx = diffusion->ctx;
   HIP_TRY(hipSetDevice(ctx->device));
   tsd_session* s = new tsd_session();
   s->unet = diffusion; s->dec = decoder; s->ctx = ctx;
-  s->B = B; s->L = L; s->T = T; s->Tp = round_up(T, 8); s->cfg = cfg ? 1 : 0;
-  const size_t nl = (size_t)B * 4 * L * L;
+  s->B = B; s->LH = LH; s->LW = LW; s->T = T; s->Tp = round_up(T, 8); s->cfg = cfg ? 1 : 0;
+  const size_t hw = (size_t)LH * LW, nl = (size_t)B * 4 * hw;
   size_t off = 0;
   auto carve = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~size_t(255); return o; };
   const size_t o_lat = carve(nl * 4), o_lat2 = carve(2 * nl * 4), o_ctx = carve((size_t)Bu * s->Tp * 768 * 2),
-               o_eps = carve((size_t)Bu * 4 * L * L * 4), o_t = carve(16 * 4), o_te = carve(16 * 320 * 4),
-               o_img = carve(decoder ? (size_t)B * 3 * 64 * L * L * 4 : 0), o_hist = carve(nl * 4),
-               o_ipm = carve((size_t)B * L * L * 4), o_ipk = carve(nl * 4), o_ipn = carve(nl * 4),
+               o_eps = carve((size_t)Bu * 4 * hw * 4), o_t = carve(16 * 4), o_te = carve(16 * 320 * 4),
+               o_img = carve(decoder ? (size_t)B * 3 * 64 * hw * 4 : 0), o_hist = carve(nl * 4),
+               o_ipm = carve((size_t)B * hw * 4), o_ipk = carve(nl * 4), o_ipn = carve(nl * 4),
                o_grp = carve((size_t)CFG_RESCALE_PARTIAL_DOUBLES * sizeof(double));
   hipError_t e = hipMalloc((void**)&s->state, off);
   if (e != hipSuccess) { delete s; TSD_FAIL(TSD_E_ALLOC, "session: hipMalloc(%zu) failed: %s", off, hipGetErrorString(e)); }
@@ -292,6 +294,15 @@ extern "C" int tsd_session_create(tsd_model* diffusion, tsd_model* decoder, int 
   s->gr_part = (double*)(s->state + o_grp);
   if (build_schedule(s) != TSD_OK) { hipFree(s->state); delete s; return TSD_E_ARG; }
   *out = s;
+  return TSD_OK;
+}
+extern "C" int tsd_session_create(tsd_model* diffusion, tsd_model* decoder, int B, int L, int T, int cfg,
+                                  tsd_session** out) {
+  return tsd_session_create_hw(diffusion, decoder, B, L, L, T, cfg, out);
+}
+extern "C" int tsd_session_shape(tsd_session* s, int* LH, int* LW) {
+  NOTNULL(s); NOTNULL(LH); NOTNULL(LW);
+  *LH = s->LH; *LW = s->LW;
   return TSD_OK;
 }
 
@@ -339,7 +350,7 @@ extern "C" int tsd_session_timestep(tsd_session* s, int i) {
 // allocation inside the timed loop), size and fill the step-invariant buffers, and mark the session ready.
 static int session_prepare(tsd_session* s) {
   tsd_ctx* ctx = s->ctx;
-  const int B = s->B, L = s->L, T = s->T, Tp = s->Tp;
+  const int B = s->B, LH = s->LH, LW = s->LW, T = s->T, Tp = s->Tp;
   // size the workspace once for this session's shapes (no allocation inside the timed loop)
   TSD_TRY(model_check_ready(s->unet));
   if (s->dec) TSD_TRY(model_check_ready(s->dec));
@@ -359,7 +370,7 @@ static int session_prepare(tsd_session* s) {
   }
   a.planning = true; a.top = 0; a.peak = 0;
   const UNetPre pre0 = s->hoist ? session_pre(s, 0) : UNetPre();
-  int r = g_unet_forward(s->unet, s->lat2, s->ctx16, T, Tp, s->temb, Bu, L, s->eps, false, s->hoist ? &pre0 : nullptr);
+  int r = g_unet_forward(s->unet, s->lat2, s->ctx16, T, Tp, s->temb, Bu, LH, LW, s->eps, false, s->hoist ? &pre0 : nullptr);
   size_t need = a.peak;
   if (r == TSD_OK && s->hoist) {  // session_build_invariants' scratch
     const float* tv = nullptr;
@@ -369,7 +380,7 @@ static int session_prepare(tsd_session* s) {
   }
   if (r == TSD_OK && s->dec) {
     a.top = 0; a.peak = 0;
-    r = g_decoder_forward(s->dec, s->latents, B, L, s->images);
+    r = g_decoder_forward(s->dec, s->latents, B, LH, LW, s->images);
     need = std::max(need, a.peak);
   }
   a.planning = false; a.top = 0; a.peak = 0;
@@ -391,7 +402,7 @@ extern "C" int tsd_session_upload(tsd_session* s, const float* latents, const fl
   tsd_ctx* ctx = s->ctx;
   HIP_TRY(hipSetDevice(ctx->device));
   const int B = s->B;
-  const size_t nl = (size_t)B * 4 * s->L * s->L;
+  const size_t nl = (size_t)B * 4 * s->LH * s->LW;
   s->cfg_scale = cfg_scale;
   s->slots = false;  // upload() leaves slot mode
   HIP_TRY(hipMemcpyAsync(s->latents, latents, nl * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -410,7 +421,7 @@ extern "C" int tsd_session_upload(tsd_session* s, const float* latents, const fl
 }
 
 // Streams of the seeded noise, per sample b with seeds[b]: 2 the initial latents, 4 the add_noise / inpainting noise, 16 + i the noise of
-// schedule step i; the counter is the element's index inside its sample, (c*L + y)*L + x.  Nothing depends on B or on the sample's slot.
+// schedule step i; the counter is the element's index inside its sample, (c*LH + y)*LW + x.  Nothing depends on B or on the sample's slot.
 enum { NOISE_STREAM_LATENTS = 2, NOISE_STREAM_ADD = 4, NOISE_STREAM_STEP0 = 16 };
 static NormalBases session_bases(const tsd_session* s, uint64_t stream) {
   NormalBases nb = {};
@@ -435,7 +446,7 @@ static int session_inpaint_blend(tsd_session* s, int i) {
   float a_prev, s_prev;
   session_blend_scalars(s, i, &a_prev, &s_prev);
   return launch_inpaint_blend(s->ctx, s->latents, s->ip_mask, s->ip_known, s->ip_has_noise ? s->ip_noise : nullptr, s->B,
-                              (int64_t)s->L * s->L, a_prev, s_prev, s->latents);
+                              (int64_t)s->LH * s->LW, a_prev, s_prev, s->latents);
 }
 
 extern "C" int tsd_session_step(tsd_session* s, int i) {
@@ -446,8 +457,8 @@ extern "C" int tsd_session_step(tsd_session* s, int i) {
   TSD_TRY(session_options_unchanged(s, "upload()"));
   if (i < 0 || i >= (int)s->timesteps.size()) TSD_FAIL(TSD_E_ARG, "session: step %d out of range", i);
   tsd_ctx* ctx = s->ctx;
-  const int B = s->B, L = s->L, Bu = s->cfg ? 2 * B : B;
-  const int64_t chw = (int64_t)4 * L * L, nl = B * chw;
+  const int B = s->B, Bu = s->cfg ? 2 * B : B;
+  const int64_t chw = (int64_t)4 * s->LH * s->LW, nl = B * chw;
   const bool hist_valid = s->hist_valid_for == i;
   session_latents_changed(s);  // no valid history until this step's update is enqueued
   TSD_TRY(session_refresh(s));
@@ -492,7 +503,7 @@ extern "C" int tsd_session_add_noise(tsd_session* s, int i, const float* noise) 
   SESSION_NOT_SLOTS(s, "add_noise()");
   if (i < 0 || i >= (int)s->timesteps.size()) TSD_FAIL(TSD_E_ARG, "session: step %d out of range", i);
   tsd_ctx* ctx = s->ctx;
-  const size_t nl = (size_t)s->B * 4 * s->L * s->L;
+  const size_t nl = (size_t)s->B * 4 * s->LH * s->LW;
   TSD_TRY(ctx_reserve_staging(ctx, nl * 4));
   session_latents_changed(s);
   HIP_TRY(hipMemcpyAsync(ctx->staging, noise, nl * 4, hipMemcpyHostToDevice, ctx->stream));
@@ -540,7 +551,7 @@ extern "C" int tsd_session_seed_latents(tsd_session* s) {
   SESSION_NOT_SLOTS(s, "seed_latents()");
   if (!s->uploaded || !s->seeded) TSD_FAIL(TSD_E_STATE, "session: upload() and set_seeds() before seed_latents()");
   HIP_TRY(hipSetDevice(s->ctx->device));
-  const int64_t chw = (int64_t)4 * s->L * s->L;
+  const int64_t chw = (int64_t)4 * s->LH * s->LW;
   session_latents_changed(s);
   return launch_fill_normal(s->ctx, s->latents, s->B * chw, chw, session_bases(s, NOISE_STREAM_LATENTS), 0);
 }
@@ -553,7 +564,7 @@ extern "C" int tsd_session_add_noise_seeded(tsd_session* s, int i) {
   if (i < 0 || i >= (int)s->timesteps.size()) TSD_FAIL(TSD_E_ARG, "session: step %d out of range", i);
   tsd_ctx* ctx = s->ctx;
   HIP_TRY(hipSetDevice(ctx->device));
-  const int64_t chw = (int64_t)4 * s->L * s->L, nl = s->B * chw;
+  const int64_t chw = (int64_t)4 * s->LH * s->LW, nl = s->B * chw;
   TSD_TRY(ctx_reserve_staging(ctx, (size_t)nl * 4));
   session_latents_changed(s);
   TSD_TRY(launch_fill_normal(ctx, (float*)ctx->staging, nl, chw, session_bases(s, NOISE_STREAM_ADD), 0));
@@ -568,7 +579,7 @@ static int session_set_inpaint(tsd_session* s, const float* mask, const float* k
   if (!s->uploaded) TSD_FAIL(TSD_E_STATE, "session: upload() before set_inpaint() (inpainting belongs to one upload)");
   if (seeded && mask && !s->seeded) TSD_FAIL(TSD_E_STATE, "session: set_seeds() before set_inpaint_seeded()");
   tsd_ctx* ctx = s->ctx;
-  const size_t hw = (size_t)s->L * s->L, nm = (size_t)s->B * hw, nl = 4 * nm;
+  const size_t hw = (size_t)s->LH * s->LW, nm = (size_t)s->B * hw, nl = 4 * nm;
   if (mask) {  // every refusal comes before the first copy: a refused call leaves the previous mask, tensors and history as they were
     NOTNULL(known);
     bool in_range = true;
@@ -606,7 +617,7 @@ extern "C" int tsd_session_decode(tsd_session* s) {
   SESSION_NOT_POISONED(s);
   TSD_TRY(session_options_unchanged(s, "upload()"));
   s->ctx->arena.top = 0;
-  int r = g_decoder_forward(s->dec, s->latents, s->B, s->L, s->images);
+  int r = g_decoder_forward(s->dec, s->latents, s->B, s->LH, s->LW, s->images);
   s->ctx->arena.top = 0;
   if (r == TSD_OK) s->decoded = true;
   return r;
@@ -616,7 +627,7 @@ extern "C" int tsd_session_download_latents(tsd_session* s, float* latents) {
   NOTNULL(s); NOTNULL(latents);
   SESSION_NOT_SLOTS(s, "download_latents()");
   if (!s->uploaded) TSD_FAIL(TSD_E_STATE, "session: upload() before download_latents() (the state is not defined yet)");
-  return session_fetch_latents(s, s->latents, (size_t)s->B * 4 * s->L * s->L, latents);
+  return session_fetch_latents(s, s->latents, (size_t)s->B * 4 * s->LH * s->LW, latents);
 }
 
 extern "C" int tsd_session_download_images(tsd_session* s, int rescale_0_255, float* images) {
@@ -625,7 +636,7 @@ extern "C" int tsd_session_download_images(tsd_session* s, int rescale_0_255, fl
   if (!s->dec) TSD_FAIL(TSD_E_STATE, "session: created without a decoder");
   if (!s->decoded) TSD_FAIL(TSD_E_STATE, "session: decode() before download_images() (no image has been computed since upload())");
   tsd_ctx* ctx = s->ctx;
-  const int64_t n = (int64_t)s->B * 3 * 64 * s->L * s->L;
+  const int64_t n = (int64_t)s->B * 3 * 64 * s->LH * s->LW;
   const float* src = s->images;
   if (rescale_0_255) {  // pipeline.mojo:127
     TSD_TRY(ctx_reserve_staging(ctx, (size_t)n * 4));
@@ -652,11 +663,11 @@ extern "C" int tsd_session_slots_open(tsd_session* s) {
   NOTNULL(s);
   tsd_ctx* ctx = s->ctx;
   HIP_TRY(hipSetDevice(ctx->device));
-  const int B = s->B, L = s->L, Bu = s->cfg ? 2 * B : B;
+  const int B = s->B, Bu = s->cfg ? 2 * B : B;
   s->slots = false;
   s->has_noise = false;
   // idle slots ride through every forward: zero latents and a zero context keep them finite
-  HIP_TRY(hipMemsetAsync(s->latents, 0, (size_t)B * 4 * L * L * 4, ctx->stream));
+  HIP_TRY(hipMemsetAsync(s->latents, 0, (size_t)B * 4 * s->LH * s->LW * 4, ctx->stream));
   HIP_TRY(hipMemsetAsync(s->ctx16, 0, (size_t)Bu * s->Tp * 768 * 2, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   if (ctx->opt.session_hoist)  // the per-sample time rows of an advance: sized by the session's shape alone
@@ -674,8 +685,8 @@ extern "C" int tsd_session_slot_start(tsd_session* s, int b, const float* contex
   SESSION_IN_SLOTS(s);
   SESSION_NOT_POISONED(s);
   tsd_ctx* ctx = s->ctx;
-  const int B = s->B, L = s->L, T = s->T, Tp = s->Tp;
-  const size_t chw = (size_t)4 * L * L, nc = (size_t)T * 768;
+  const int B = s->B, T = s->T, Tp = s->Tp;
+  const size_t chw = (size_t)4 * s->LH * s->LW, nc = (size_t)T * 768;
   // every refusal comes before the first copy: a refused call leaves the slot, and everyone else's, as it was
   if (b < 0 || b >= B) TSD_FAIL(TSD_E_ARG, "session: slot %d out of range (0..%d)", b, B - 1);
   if (start_index < 0 || start_index >= (int)s->timesteps.size())
@@ -727,7 +738,7 @@ extern "C" int tsd_session_slot_start(tsd_session* s, int b, const float* contex
 }
 
 // Inpainting for the request of ACTIVE slot b, right after slot_start or mid-flight: what set_inpaint_seeded does for sample b of a
-// lockstep session, on this sample's regions of the three buffers alone.  mask [L][L], known [4][L][L]; the noise is stream 4 of the slot's
+// lockstep session, on this sample's regions of the three buffers alone.  mask [LH][LW], known [4][LH][LW]; the noise is stream 4 of the slot's
 // seed, the values slot_start(noise_at_start) added.  mask == NULL turns it off.  Either way the slot's history is dropped, as set_inpaint
 // drops the session's.  Every refusal comes before the first copy and leaves all slots as they were.  Synchronous.
 extern "C" int tsd_session_slot_set_inpaint(tsd_session* s, int b, const float* mask, const float* known) {
@@ -737,7 +748,7 @@ extern "C" int tsd_session_slot_set_inpaint(tsd_session* s, int b, const float* 
   tsd_session::Slot& sl = s->slot[b];
   if (sl.state != 1) TSD_FAIL(TSD_E_STATE, "session: slot %d is %s; slot_set_inpaint() belongs to an active request", b, sl.state ? "done" : "idle");
   tsd_ctx* ctx = s->ctx;
-  const size_t hw = (size_t)s->L * s->L, chw = 4 * hw;
+  const size_t hw = (size_t)s->LH * s->LW, chw = 4 * hw;
   if (mask) {
     NOTNULL(known);
     bool in_range = true;
@@ -798,8 +809,9 @@ extern "C" int tsd_session_advance(tsd_session* s, uint32_t* finished_mask) {
   SESSION_NOT_POISONED(s);
   TSD_TRY(session_options_unchanged(s, "slots_open()"));
   tsd_ctx* ctx = s->ctx;
-  const int B = s->B, L = s->L, Bu = s->cfg ? 2 * B : B, n = (int)s->timesteps.size();
-  const size_t nl = (size_t)B * 4 * L * L;
+  const int B = s->B, Bu = s->cfg ? 2 * B : B, n = (int)s->timesteps.size();
+  const int64_t chw = (int64_t)4 * s->LH * s->LW;
+  const size_t nl = (size_t)B * chw;
   int active = 0;
   for (int b = 0; b < B; b++) active += s->slot[b].state == 1;
   if (!active) TSD_FAIL(TSD_E_STATE, "session: advance() with no active slot");
@@ -845,12 +857,12 @@ extern "C" int tsd_session_advance(tsd_session* s, uint32_t* finished_mask) {
   TSD_TRY(session_forward(s, &pre, &eps_hw));
   // the update launch: with an inpainting slot among the active ones, the kernel that also blends (no further launch either way)
   const float* eps_u = s->cfg ? s->eps + nl : nullptr;
-  if (rescaling) TSD_TRY(launch_cfg_rescale(ctx, s->eps, s->eps + nl, gr, B, (int64_t)4 * L * L, s->gr_part, nullptr));
+  if (rescaling) TSD_TRY(launch_cfg_rescale(ctx, s->eps, s->eps + nl, gr, B, chw, s->gr_part, nullptr));
   if (blending)
     TSD_TRY(launch_slot_update_blend(ctx, s->latents, s->eps, eps_u, s->hist, tab, blend, s->ip_mask, s->ip_known, s->ip_noise, B,
-                                     (int64_t)4 * L * L, eps_hw));
+                                     chw, eps_hw));
   else
-    TSD_TRY(launch_slot_update(ctx, s->latents, s->eps, eps_u, s->hist, tab, B, (int64_t)4 * L * L, eps_hw));
+    TSD_TRY(launch_slot_update(ctx, s->latents, s->eps, eps_u, s->hist, tab, B, chw, eps_hw));
   uint32_t done = 0;
   for (int b = 0; b < B; b++) {
     tsd_session::Slot& sl = s->slot[b];
@@ -876,7 +888,7 @@ extern "C" int tsd_session_slot_download(tsd_session* s, int b, float* latents) 
   SESSION_IN_SLOTS(s);
   if (b < 0 || b >= s->B) TSD_FAIL(TSD_E_ARG, "session: slot %d out of range (0..%d)", b, s->B - 1);
   if (s->slot[b].state == 0) TSD_FAIL(TSD_E_STATE, "session: slot %d is idle (no request has defined its latents)", b);
-  const size_t chw = (size_t)4 * s->L * s->L;
+  const size_t chw = (size_t)4 * s->LH * s->LW;
   return session_fetch_latents(s, s->latents + (size_t)b * chw, chw, latents);  // download_latents()' check, on this slot's buffer alone
 }
 
@@ -888,11 +900,11 @@ extern "C" int tsd_session_slots_active(tsd_session* s) {
   return n;
 }
 
-// the raw latent buffer [B,4,L,L], whatever the mode and the slot states, unchecked: lets a test see that an idle slot is never written
+// the raw latent buffer [B,4,LH,LW], whatever the mode and the slot states, unchecked: lets a test see that an idle slot is never written
 extern "C" int tsd_debug_session_latents(tsd_session* s, float* latents) {
   NOTNULL(s); NOTNULL(latents);
   HIP_TRY(hipSetDevice(s->ctx->device));
-  HIP_TRY(hipMemcpyAsync(latents, s->latents, (size_t)s->B * 4 * s->L * s->L * 4, hipMemcpyDeviceToHost, s->ctx->stream));
+  HIP_TRY(hipMemcpyAsync(latents, s->latents, (size_t)s->B * 4 * s->LH * s->LW * 4, hipMemcpyDeviceToHost, s->ctx->stream));
   HIP_TRY(hipStreamSynchronize(s->ctx->stream));
   return TSD_OK;
 }

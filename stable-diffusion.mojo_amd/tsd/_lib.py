@@ -121,6 +121,9 @@ def _declare(l):
         "tsd_diffusion_forward": ([vp, fp, fp, fp, i, i, i, fp], i),
         "tsd_decoder_forward": ([vp, fp, i, i, fp], i),
         "tsd_encoder_forward": ([vp, fp, fp, i, i, fp], i),
+        "tsd_diffusion_forward_hw": ([vp, fp, fp, fp, i, i, i, i, fp], i),
+        "tsd_decoder_forward_hw": ([vp, fp, i, i, i, fp], i),
+        "tsd_encoder_forward_hw": ([vp, fp, fp, i, i, i, fp], i),
         "tsd_clip_forward": ([vp, C.POINTER(C.c_int32), i, i, fp], i),
         "tsd_tokenizer_create": ([C.c_char_p, i, C.POINTER(vp)], i),
         "tsd_tokenizer_create_from_memory": ([C.c_char_p, C.c_size_t, i, C.POINTER(vp)], i),
@@ -129,6 +132,7 @@ def _declare(l):
         "tsd_tokenizer_token": ([vp, i, C.c_char_p, i, fp], i),
         "tsd_tokenizer_encode": ([vp, C.c_char_p, C.POINTER(C.c_int32), i, C.POINTER(C.c_int), C.POINTER(C.c_int)], i),
         "tsd_session_create": ([vp, vp, i, i, i, i, pp], i), "tsd_session_destroy": ([vp], i),
+        "tsd_session_create_hw": ([vp, vp, i, i, i, i, i, pp], i), "tsd_session_shape": ([vp, C.POINTER(i), C.POINTER(i)], i),
         "tsd_session_set_schedule": ([vp, i, i, i], i), "tsd_session_num_steps": ([vp], i),
         "tsd_session_set_sampler": ([vp, i, f, i], i),
         "tsd_sampler_timesteps": ([i, i, i, i, C.POINTER(i), i], i),
@@ -139,6 +143,7 @@ def _declare(l):
         "tsd_session_set_guidance_rescale": ([vp, f], i), "tsd_session_guidance_rescale": ([vp, fp], i),
         "tsd_session_slot_set_guidance_rescale": ([vp, i, f], i), "tsd_session_slot_guidance_rescale": ([vp, i, fp], i),
         "tsd_latent_mask_f32": ([vp, fp, i, i, i, fp], i),
+        "tsd_latent_mask_hw_f32": ([vp, fp, i, i, i, i, fp], i),
         "tsd_inpaint_blend_f32": ([vp, fp, fp, fp, fp, i, i64, f, f, fp], i),
         "tsd_session_set_inpaint": ([vp, fp, fp, fp], i), "tsd_session_inpaint_active": ([vp], i),
         "tsd_normal_fill_f32": ([vp, u64, u64, u64, i64, fp], i),
@@ -221,6 +226,21 @@ def check(code, null_shape=None):
         print(msg + ". Returning null matrix")  # helpers/utils.mojo:1550-1552 convention
         return True
     raise TsdError(code, msg)
+
+
+def latent_shape(L):
+    """(LH, LW) of a latent size given as one side (an int: square) or as a pair (LH, LW) of positive ints.  ValueError for anything else;
+    which multiples a side must be is the library's to say (TSD_E_SHAPE)."""
+    import numbers
+    if isinstance(L, numbers.Integral) and not isinstance(L, bool):
+        return int(L), int(L)
+    try:
+        sides = tuple(L)
+    except TypeError:
+        sides = ()
+    if len(sides) != 2 or any(not isinstance(v, numbers.Integral) or isinstance(v, bool) or v <= 0 for v in sides):
+        raise ValueError(f"the latent size must be an int or a pair (LH, LW) of positive ints, got {L!r}")
+    return int(sides[0]), int(sides[1])
 
 
 def f32(a):

@@ -153,7 +153,7 @@ class UNet_Output_Layer:
 class Diffusion:
     """`Diffusion` diffusion.mojo:294-318 - device-resident weights; forward is ONE libtsd call.
 
-    forward(x, context, time): x (4,L,L) or (B,4,L,L); context (T,768)/(1,T,768) or (B,T,768);
+    forward(x, context, time): x (4,LH,LW) or (B,4,LH,LW), square or not; context (T,768)/(1,T,768) or (B,T,768);
     time = get_time_embedding(t): (1,1,320) or (B,320)."""
 
     def __init__(self, seed=0, ctx=None, params=None, variant="diffusion"):
@@ -168,7 +168,9 @@ class Diffusion:
         x = f32(x)
         single = x.ndim == 3
         xb = x[None] if single else x
-        B, _, L, _ = xb.shape
+        if xb.ndim != 4 or xb.shape[1] != 4:
+            raise ValueError(f"latents must have shape (4, LH, LW) or (B, 4, LH, LW), got {x.shape}")
+        B, _, LH, LW = xb.shape
         c = f32(context)
         if c.ndim == 2:
             c = c[None]
@@ -179,7 +181,7 @@ class Diffusion:
             t = np.repeat(t, B, axis=0)
         c, t = f32(c), f32(t)
         out = np.empty_like(xb)
-        code = lib().tsd_diffusion_forward(self.model.h, ptr(xb), ptr(c), ptr(t), B, L, c.shape[1], ptr(out))
+        code = lib().tsd_diffusion_forward_hw(self.model.h, ptr(xb), ptr(c), ptr(t), B, LH, LW, c.shape[1], ptr(out))
         if check(code, True):
             return NULL_MATRIX()
         return out[0] if single else out

@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check, check_guidance_rescale, f32, lib, ptr, sampler_kind, timestep_spacing, vp
+from ._lib import check, check_guidance_rescale, f32, latent_shape, lib, ptr, sampler_kind, timestep_spacing, vp
 
 KINDS = {"diffusion": _lib.MODEL_DIFFUSION, "decoder": _lib.MODEL_DECODER, "encoder": _lib.MODEL_ENCODER,
          "clip": _lib.MODEL_CLIP, "diffusion_sd15": _lib.MODEL_DIFFUSION_SD15,
@@ -136,13 +136,16 @@ class Model:
 
 
 class Session:
-    """Device-resident denoise loop (pipeline.mojo:57-127 + sampler.mojo)."""
+    """Device-resident denoise loop (pipeline.mojo:57-127 + sampler.mojo).  L: the latent side, or a pair (LH, LW) for a rectangular
+    session; `LH` / `LW` are the sides, `L` stays what the caller passed.  Where a method's text says L,L the tensor is LH,LW."""
 
     def __init__(self, diffusion, decoder, B, L, T=77, cfg=False):
+        LH, LW = latent_shape(L)
         h = vp()
-        check(lib().tsd_session_create(diffusion.h, decoder.h if decoder is not None else None, B, L, T, 1 if cfg else 0,
-                                       C.byref(h)))
+        check(lib().tsd_session_create_hw(diffusion.h, decoder.h if decoder is not None else None, B, LH, LW, T, 1 if cfg else 0,
+                                          C.byref(h)))
         self.h, self.B, self.L, self.T, self.cfg = h, B, L, T, cfg
+        self.LH, self.LW = LH, LW
         self.ctx = diffusion.ctx
         self.has_decoder = decoder is not None
 
@@ -166,9 +169,9 @@ class Session:
         uc = f32(uncond_context) if uncond_context is not None else None
         nz = f32(noise) if noise is not None else None
         # the C side reads exactly B*4*L*L / B*T*768 / steps*B*4*L*L floats from these pointers: check the shapes here
-        B, L, T = self.B, self.L, self.T
-        if la.shape != (B, 4, L, L):
-            raise ValueError(f"latents must have shape {(B, 4, L, L)}, got {la.shape}")
+        B, LH, LW, T = self.B, self.LH, self.LW, self.T
+        if la.shape != (B, 4, LH, LW):
+            raise ValueError(f"latents must have shape {(B, 4, LH, LW)}, got {la.shape}")
         if cx.shape != (B, T, 768):
             raise ValueError(f"context must have shape {(B, T, 768)}, got {cx.shape}")
         if self.cfg and uc is None:
@@ -180,15 +183,18 @@ class Session:
                 uc = np.ascontiguousarray(np.broadcast_to(uc, (B, T, 768)))
             if uc.shape != (B, T, 768):
                 raise ValueError(f"uncond_context must have shape {(B, T, 768)} (or one shared (T, 768) row), got {uc.shape}")
-        if nz is not None and nz.shape != (self.num_steps, B, 4, L, L):
-            raise ValueError(f"noise must have shape {(self.num_steps, B, 4, L, L)}, got {nz.shape}")
+        if nz is not None and nz.shape != (self.num_steps, B, 4, LH, LW):
+            raise ValueError(f"noise must have shape {(self.num_steps, B, 4, LH, LW)}, got {nz.shape}")
         check(lib().tsd_session_upload(self.h, ptr(la), ptr(cx), ptr(uc), ptr(nz), float(cfg_scale)))
 
     def step(self, i):
         check(lib().tsd_session_step(self.h, int(i)))
 
     def add_noise(self, i, noise):
-        check(lib().tsd_session_add_noise(self.h, int(i), ptr(f32(noise))))
+        nz = f32(noise)
+        if nz.size != self.B * 4 * self.LH * self.LW or (nz.ndim == 4 and nz.shape != (self.B, 4, self.LH, self.LW)):
+            raise ValueError(f"noise must have shape {(self.B, 4, self.LH, self.LW)}, got {nz.shape}")
+        check(lib().tsd_session_add_noise(self.h, int(i), ptr(nz)))
 
     def set_seeds(self, seeds):
         """Seeded device-side noise for the steps of the current upload(): `seeds` is a sequence of B ints (uint64), one per sample; None
@@ -227,20 +233,20 @@ class Session:
         if mask is None:
             check(lib().tsd_session_set_inpaint(self.h, None, None, None))
             return
-        B, L = self.B, self.L
+        B, LH, LW = self.B, self.LH, self.LW
         m = f32(mask)
-        if m.shape == (B, 1, L, L):
-            m = np.ascontiguousarray(m.reshape(B, L, L))
-        if m.shape != (B, L, L):
-            raise ValueError(f"mask must have shape {(B, L, L)} or {(B, 1, L, L)}, got {m.shape}")
+        if m.shape == (B, 1, LH, LW):
+            m = np.ascontiguousarray(m.reshape(B, LH, LW))
+        if m.shape != (B, LH, LW):
+            raise ValueError(f"mask must have shape {(B, LH, LW)} or {(B, 1, LH, LW)}, got {m.shape}")
         if known is None:
             raise ValueError("set_inpaint with a mask needs the known latents")
         kn = f32(known)
-        if kn.shape != (B, 4, L, L):
-            raise ValueError(f"known must have shape {(B, 4, L, L)}, got {kn.shape}")
+        if kn.shape != (B, 4, LH, LW):
+            raise ValueError(f"known must have shape {(B, 4, LH, LW)}, got {kn.shape}")
         nz = f32(noise) if noise is not None else None
-        if nz is not None and nz.shape != (B, 4, L, L):
-            raise ValueError(f"noise must have shape {(B, 4, L, L)}, got {nz.shape}")
+        if nz is not None and nz.shape != (B, 4, LH, LW):
+            raise ValueError(f"noise must have shape {(B, 4, LH, LW)}, got {nz.shape}")
         if seeded:
             check(lib().tsd_session_set_inpaint_seeded(self.h, ptr(m), ptr(kn)))
             return
@@ -268,12 +274,12 @@ class Session:
         check(lib().tsd_session_decode(self.h))
 
     def latents(self):
-        out = np.empty((self.B, 4, self.L, self.L), dtype=np.float32)
+        out = np.empty((self.B, 4, self.LH, self.LW), dtype=np.float32)
         check(lib().tsd_session_download_latents(self.h, ptr(out)))
         return out
 
     def images(self, rescale=True):
-        out = np.empty((self.B, 3, 8 * self.L, 8 * self.L), dtype=np.float32)
+        out = np.empty((self.B, 3, 8 * self.LH, 8 * self.LW), dtype=np.float32)
         check(lib().tsd_session_download_images(self.h, 1 if rescale else 0, ptr(out)))
         return out
 
@@ -288,7 +294,7 @@ class Session:
     def slot_start(self, b, context, uncond_context=None, latents=None, noise_at_start=False, seed=0, start_index=0, cfg_scale=7.5):
         """Put a request into slot b: context (T,768), uncond_context (T,768) on a CFG session, latents (4,L,L) or None (stream 2 of
         `seed`); noise_at_start noises given latents to timesteps[start_index] with stream 4 of `seed` (img2img)."""
-        T, L = self.T, self.L
+        T, LH, LW = self.T, self.LH, self.LW
         cx = f32(context)
         if cx.shape == (1, T, 768):
             cx = cx[0]
@@ -304,10 +310,10 @@ class Session:
         la = None
         if latents is not None:
             la = f32(latents)
-            if la.shape == (1, 4, L, L):
+            if la.shape == (1, 4, LH, LW):
                 la = la[0]
-            if la.shape != (4, L, L):
-                raise ValueError(f"latents must have shape {(4, L, L)}, got {la.shape}")
+            if la.shape != (4, LH, LW):
+                raise ValueError(f"latents must have shape {(4, LH, LW)}, got {la.shape}")
         seed = int(seed)
         if seed < 0 or seed >= 1 << 64:
             raise ValueError("the seed must fit an unsigned 64-bit integer")
@@ -321,19 +327,19 @@ class Session:
         if mask is None:
             check(lib().tsd_session_slot_set_inpaint(self.h, int(b), None, None))
             return
-        L = self.L
+        LH, LW = self.LH, self.LW
         m = f32(mask)
-        if m.shape == (1, L, L):
+        if m.shape == (1, LH, LW):
             m = np.ascontiguousarray(m[0])
-        if m.shape != (L, L):
-            raise ValueError(f"mask must have shape {(L, L)} or {(1, L, L)}, got {m.shape}")
+        if m.shape != (LH, LW):
+            raise ValueError(f"mask must have shape {(LH, LW)} or {(1, LH, LW)}, got {m.shape}")
         if known is None:
             raise ValueError("slot_set_inpaint with a mask needs the known latents")
         kn = f32(known)
-        if kn.shape == (1, 4, L, L):
+        if kn.shape == (1, 4, LH, LW):
             kn = np.ascontiguousarray(kn[0])
-        if kn.shape != (4, L, L):
-            raise ValueError(f"known must have shape {(4, L, L)}, got {kn.shape}")
+        if kn.shape != (4, LH, LW):
+            raise ValueError(f"known must have shape {(4, LH, LW)}, got {kn.shape}")
         check(lib().tsd_session_slot_set_inpaint(self.h, int(b), ptr(m), ptr(kn)))
 
     def slot_inpaint_active(self, b):
@@ -366,7 +372,7 @@ class Session:
         return idx.value, st.value
 
     def slot_latents(self, b):
-        out = np.empty((4, self.L, self.L), dtype=np.float32)
+        out = np.empty((4, self.LH, self.LW), dtype=np.float32)
         check(lib().tsd_session_slot_download(self.h, int(b), ptr(out)))
         return out
 
@@ -378,7 +384,7 @@ class Session:
 
     def raw_latents(self):
         """The device's latent buffer (B,4,L,L) as it is, in any mode and unchecked (tsd_debug_session_latents; for tests)."""
-        out = np.empty((self.B, 4, self.L, self.L), dtype=np.float32)
+        out = np.empty((self.B, 4, self.LH, self.LW), dtype=np.float32)
         check(lib().tsd_debug_session_latents(self.h, ptr(out)))
         return out
 

@@ -5,7 +5,7 @@ over independent prompts (the reference is batch 1; `pipeline.mojo:12` suggests 
 import numpy as np
 
 from . import rng
-from ._lib import check_guidance_rescale
+from ._lib import check_guidance_rescale, latent_shape
 from .model import Session
 from .utils import latent_mask, rescale
 
@@ -27,7 +27,8 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
              inference_steps=50, seed_val=0, input_image=None, encoder=None, latents=None, noise=None,
              num_training_steps=1000, L=64, return_latents=False, sampler="ddpm", eta=0.0, spacing="leading", mask=None,
              mask_mode="any", seeds=None, guidance_rescale=0.0):
-    """context (B,T,768); returns images (B,3,8L,8L) in [0,255] like pipeline.mojo:127.
+    """context (B,T,768); returns images (B,3,8LH,8LW) in [0,255] like pipeline.mojo:127.  L is the latent side (64: 512x512) or a pair
+    (LH, LW) for a rectangular image ((96, 64): 512 wide, 768 high); where the text below says L,L the tensor is LH,LW.
 
     sampler "ddpm" (the reference's, about 50 steps) | "ddim" (eta = 0: deterministic) | "dpmpp_2m" (second-order multistep, 20-25
     steps); spacing "leading" (the reference's timesteps) | "trailing" (starts at N - 1: few-step sampling).  The defaults are the
@@ -54,13 +55,16 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
     if context.ndim == 2:
         context = context[None]
     B, T, _ = context.shape
+    LH, LW = latent_shape(L)
     if mask is not None and (input_image is None or encoder is None):
         raise ValueError("generate(mask=...) needs input_image and encoder: the mask says which part of that image to keep")
     if not (0.0 <= strength <= 1.0):  # pipeline.mojo:23-29
         print("Strength must be between 0 and 1. Returning empty matrix")
         return np.zeros((0, 0, 0), dtype=np.float32)
-    if mask is not None and np.shape(mask) not in ((B, 1, 8 * L, 8 * L), (B, 8 * L, 8 * L)):
-        raise ValueError(f"mask must have shape {(B, 1, 8 * L, 8 * L)} or {(B, 8 * L, 8 * L)}, got {np.shape(mask)}")
+    if mask is not None and np.shape(mask) not in ((B, 1, 8 * LH, 8 * LW), (B, 8 * LH, 8 * LW)):
+        raise ValueError(f"mask must have shape {(B, 1, 8 * LH, 8 * LW)} or {(B, 8 * LH, 8 * LW)}, got {np.shape(mask)}")
+    if input_image is not None and np.shape(input_image)[-2:] != (8 * LH, 8 * LW):
+        raise ValueError(f"input_image must be {(8 * LH, 8 * LW)} pixels (rows, columns), got {np.shape(input_image)}")
     sess = Session(diffusion.model, decoder.model if decoder is not None else None, B, L, T, cfg=cfg)
     start = 0
     if input_image is not None:
@@ -69,17 +73,17 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
         sess.set_sampler(sampler, eta, spacing)
     sess.set_schedule(num_training_steps, inference_steps, start)
     n = sess.num_steps
-    nl = B * 4 * L * L
+    nl = B * 4 * LH * LW
     if input_image is not None:  # pipeline.mojo:66-79
         img = rescale(input_image, (0, 255), (-1, 1))
-        enc_noise = rng.normal(seed_val, 1, nl).reshape(B, 4, L, L)
+        enc_noise = rng.normal(seed_val, 1, nl).reshape(B, 4, LH, LW)
         latents = encoder.forward(img, enc_noise)
         if mask is not None:
             mask_lat = latent_mask(mask, mask_mode, diffusion.model.ctx)
     elif latents is None:
-        latents = np.zeros((B, 4, L, L), dtype=np.float32) if seeds is not None else rng.normal(seed_val, 2, nl).reshape(B, 4, L, L)
+        latents = np.zeros((B, 4, LH, LW), dtype=np.float32) if seeds is not None else rng.normal(seed_val, 2, nl).reshape(B, 4, LH, LW)
     if noise is None and seeds is None:
-        noise = rng.normal(seed_val, 3, n * nl).reshape(n, B, 4, L, L)
+        noise = rng.normal(seed_val, 3, n * nl).reshape(n, B, 4, LH, LW)
     sess.upload(latents, context, uncond_context if cfg else None, noise, cfg_scale)
     if seeds is not None:
         sess.set_seeds(seeds)
@@ -90,7 +94,7 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
             if mask is not None:
                 sess.set_inpaint(mask_lat, latents, seeded=True)
     elif input_image is not None:
-        z4 = rng.normal(seed_val, 4, nl).reshape(B, 4, L, L)
+        z4 = rng.normal(seed_val, 4, nl).reshape(B, 4, LH, LW)
         sess.add_noise(0, z4)  # sampler.mojo:111-124 at timesteps[0]
         if mask is not None:
             sess.set_inpaint(mask_lat, latents, z4)

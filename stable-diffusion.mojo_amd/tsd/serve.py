@@ -5,7 +5,7 @@ A `Session` in slot mode (`Session.slots_open`) gives every sample of its batch 
 each free slot takes the next request, a slot that finishes yields its latents and is free again.  A request that arrives while the
 others are at step 3 of 50 starts at once; img2img requests of different strength - different start indices - share the batch.
 
-The scheduler only calls the slot methods (`B`, `L`, `num_steps`, `slot_start`, `slot_set_inpaint`, `advance`, `slot_latents` - and
+The scheduler only calls the slot methods (`B`, `LH` / `LW` or else `L`, `num_steps`, `slot_start`, `slot_set_inpaint`, `advance`, `slot_latents` - and
 `slot_set_guidance_rescale` for a request that asks for it), so it runs against any object that has them (tests/test_slots_cpu.py and
 tests/test_slot_inpaint_cpu.py drive it without a GPU).
 """
@@ -13,12 +13,13 @@ from collections import namedtuple
 
 import numpy as np
 
-from ._lib import check_guidance_rescale
+from ._lib import check_guidance_rescale, latent_shape
 
 # One request.  latents None: txt2img from `seed`.  latents (4,L,L) with strength s in [0,1]: img2img by the rule of `generate`
 # (sampler.mojo:68-70) - the first n - int(n * s) steps are skipped and the latents are noised to that timestep from `seed`.
 # mask: inpainting - `latents` are the known latents and the mask says where to regenerate (1) and where to keep them (0): a latent mask
-# (L,L) / (1,L,L) is used as given, a pixel mask (8L,8L) / (1,8L,8L) goes through `tsd.utils.latent_mask` with `mask_mode`.
+# (LH,LW) / (1,LH,LW) is used as given, a pixel mask (8LH,8LW) / (1,8LH,8LW) goes through `tsd.utils.latent_mask` with `mask_mode`.
+# LH, LW are the session's sides (`session_shape`): its `LH` / `LW`, or its `L` twice for a session object that has only that.
 _RequestFields = namedtuple("Request", "id context uncond seed cfg_scale latents strength mask mask_mode")
 _RequestFields.__new__.__defaults__ = (None, 0, 7.5, None, None, None, "any")
 
@@ -41,23 +42,30 @@ class Request(_RequestFields):
         return r
 
 
+def session_shape(session):
+    """(LH, LW) of a session: its `LH` / `LW` attributes, or `L` (an int or a pair) for an object that has only that."""
+    if hasattr(session, "LH") and hasattr(session, "LW"):
+        return int(session.LH), int(session.LW)
+    return latent_shape(session.L)
+
+
 def request_latent_mask(r, session):
-    """The latent mask (L,L) float32 of request r for `session` (its L, its context for a pixel mask), or None without a mask.
+    """The latent mask (LH,LW) float32 of request r for `session` (its shape, its context for a pixel mask), or None without a mask.
     ValueError for a mask without latents or of another shape."""
     if r.mask is None:
         return None
     if r.latents is None:
         raise ValueError(f"request {r.id!r}: a mask needs `latents`, the known latents it keeps")
-    L, ctx = session.L, getattr(session, "ctx", None)
+    (LH, LW), ctx = session_shape(session), getattr(session, "ctx", None)
     m = np.ascontiguousarray(r.mask, dtype=np.float32)
     if m.ndim == 3 and m.shape[0] == 1:
         m = m[0]
-    if m.shape == (L, L):
+    if m.shape == (LH, LW):
         return np.ascontiguousarray(m)
-    if m.shape == (8 * L, 8 * L):
+    if m.shape == (8 * LH, 8 * LW):
         from . import utils
         return np.ascontiguousarray(utils.latent_mask(m[None], r.mask_mode, ctx=ctx)[0])
-    raise ValueError(f"request {r.id!r}: mask must have shape {(L, L)} or {(8 * L, 8 * L)} (with or without a leading 1), got {np.shape(r.mask)}")
+    raise ValueError(f"request {r.id!r}: mask must have shape {(LH, LW)} or {(8 * LH, 8 * LW)} (with or without a leading 1), got {np.shape(r.mask)}")
 
 
 def start_index(num_steps, strength):
@@ -134,7 +142,8 @@ class SlotScheduler:
 def generate_stream(diffusion, decoder, requests, B, L, T=77, cfg=True, inference_steps=50, num_training_steps=1000, sampler="ddpm",
                     eta=0.0, spacing="leading", return_latents=False, stats=None):
     """Continuous batching of `generate`: `requests` is an iterator of `Request`s (or tuples in its field order); yields (id, image
-    (3,8L,8L) in [0,255]) - or (id, latents) with return_latents or without a decoder - as requests finish, B at a time on the device.
+    (3,8LH,8LW) in [0,255]) - or (id, latents) with return_latents or without a decoder - as requests finish, B at a time on the device.
+    L is the latent side or a pair (LH, LW): one shape for the whole stream.
     A txt2img request gives what `generate(..., seeds=[...])` gives for it in the same sample position.  An img2img request indexes the
     FULL timestep list (its step i draws stream 16 + i of its seed), where `generate` drops the skipped entries and counts from 0.
     A request with a `mask` is inpainted in its slot (`Session.slot_set_inpaint`) next to the others: no drain, no extra launch.

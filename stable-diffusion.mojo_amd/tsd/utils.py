@@ -181,16 +181,16 @@ def Softmax(matrix, dim=2, ctx=None):
 
 
 def latent_mask(mask, mode="any", ctx=None):
-    """Pixel mask (B,8L,8L) or (B,1,8L,8L) in [0,1] -> latent mask (B,L,L) by 8x8 blocks (`tsd_latent_mask_f32`): "area" is the
+    """Pixel mask (B,8LH,8LW) or (B,1,8LH,8LW) in [0,1] -> latent mask (B,LH,LW) by 8x8 blocks (`tsd_latent_mask_hw_f32`): "area" is the
     block's mean, "any" is 1 where any pixel of the block is >= 0.5 (a cell that touches a masked pixel is regenerated)."""
     m = f32(mask)
     if m.ndim == 4 and m.shape[1] == 1:
         m = np.ascontiguousarray(m[:, 0])
-    if m.ndim != 3 or m.shape[1] != m.shape[2] or m.shape[1] % 8 or m.shape[1] == 0:
-        raise ValueError(f"mask must have shape (B, 8L, 8L) or (B, 1, 8L, 8L), got {np.shape(mask)}")
-    B, L = m.shape[0], m.shape[1] // 8
-    y = np.empty((B, L, L), dtype=np.float32)
-    check(lib().tsd_latent_mask_f32(_ctx(ctx), ptr(m), B, L, _lib.mask_mode(mode), ptr(y)))
+    if m.ndim != 3 or m.shape[1] % 8 or m.shape[2] % 8 or m.shape[1] == 0 or m.shape[2] == 0:
+        raise ValueError(f"mask must have shape (B, 8LH, 8LW) or (B, 1, 8LH, 8LW), got {np.shape(mask)}")
+    B, LH, LW = m.shape[0], m.shape[1] // 8, m.shape[2] // 8
+    y = np.empty((B, LH, LW), dtype=np.float32)
+    check(lib().tsd_latent_mask_hw_f32(_ctx(ctx), ptr(m), B, LH, LW, _lib.mask_mode(mode), ptr(y)))
     return y
 
 

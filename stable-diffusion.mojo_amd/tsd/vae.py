@@ -52,7 +52,7 @@ class Res_Block:
 
 
 class Decoder:
-    """`Decoder` vae.mojo:162-250.  forward(x): (4,L,L) or (B,4,L,L) -> (3,8L,8L) / (B,3,8L,8L)."""
+    """`Decoder` vae.mojo:162-250.  forward(x): (4,LH,LW) or (B,4,LH,LW) -> (3,8LH,8LW) / (B,3,8LH,8LW)."""
 
     def __init__(self, seed=0, ctx=None, params=None, variant="decoder"):
         """variant "decoder_torch" (extension): the trained VAE's norms (32 groups, per-channel affine) for real
@@ -65,16 +65,18 @@ class Decoder:
         x = f32(x)
         single = x.ndim == 3
         xb = x[None] if single else x
-        B, _, L, _ = xb.shape
-        out = np.empty((B, 3, 8 * L, 8 * L), dtype=np.float32)
-        code = lib().tsd_decoder_forward(self.model.h, ptr(xb), B, L, ptr(out))
+        if xb.ndim != 4 or xb.shape[1] != 4:
+            raise ValueError(f"latents must have shape (4, LH, LW) or (B, 4, LH, LW), got {x.shape}")
+        B, _, LH, LW = xb.shape
+        out = np.empty((B, 3, 8 * LH, 8 * LW), dtype=np.float32)
+        code = lib().tsd_decoder_forward_hw(self.model.h, ptr(xb), B, LH, LW, ptr(out))
         if check(code, True):
             return NULL_MATRIX()
         return out[0] if single else out
 
 
 class Encoder:
-    """`Encoder` vae.mojo:70-159.  forward(x, noise): (3,S,S),(4,S/8,S/8) -> (4,S/8,S/8) (batched variants too)."""
+    """`Encoder` vae.mojo:70-159.  forward(x, noise): (3,SH,SW),(4,SH/8,SW/8) -> (4,SH/8,SW/8) (batched variants too)."""
 
     def __init__(self, seed=0, ctx=None, params=None, variant="encoder"):
         self.model = Model(variant, ctx=ctx, seed=None if params is not None else seed)
@@ -86,9 +88,13 @@ class Encoder:
         single = x.ndim == 3
         xb = x[None] if single else x
         nb = noise[None] if noise.ndim == 3 else noise
-        B, _, S, _ = xb.shape
-        out = np.empty((B, 4, S // 8, S // 8), dtype=np.float32)
-        code = lib().tsd_encoder_forward(self.model.h, ptr(xb), ptr(f32(nb)), B, S, ptr(out))
+        if xb.ndim != 4 or xb.shape[1] != 3:
+            raise ValueError(f"images must have shape (3, SH, SW) or (B, 3, SH, SW), got {x.shape}")
+        B, _, SH, SW = xb.shape
+        if nb.shape != (B, 4, SH // 8, SW // 8):  # the library reads exactly that many floats
+            raise ValueError(f"noise must have shape {(B, 4, SH // 8, SW // 8)}, got {noise.shape}")
+        out = np.empty((B, 4, SH // 8, SW // 8), dtype=np.float32)
+        code = lib().tsd_encoder_forward_hw(self.model.h, ptr(xb), ptr(f32(nb)), B, SH, SW, ptr(out))
         if check(code, True):
             return NULL_MATRIX()
         return out[0] if single else out
