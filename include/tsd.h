@@ -312,6 +312,36 @@ int tsd_sampler_coeffs(int kind, double eta, int spacing, int n_train, int n_inf
  * noise and hist_out may be NULL (the term / the output is skipped).  x_out and hist_out may alias nothing. */
 int tsd_sampler_step_f32(tsd_ctx* ctx, const float* x, const float* eps, const float* eps_uncond, float cfg_scale,
                          const float* hist, const float* noise, int64_t n, const float* c, float* x_out, float* hist_out);
+/* ---- v-prediction and zero-terminal-SNR schedules (EXTENSION; Salimans & Ho 2022; Lin et al. 2023, section 3.1 and algorithm 1) ----
+ * TSD_PRED_V: the model output means v = alpha_t e - sigma_t x0, hence x0 = alpha_t x - sigma_t v and e = sigma_t x + alpha_t v, and the
+ * update is
+ *     v  = (v_c - v_u) * cfg_scale + v_u                      the same combine
+ *     x' = c_x x + c_v v + c_h h + c_n z                      the same arithmetic, v in place of e
+ *     h' = alpha_t x - sigma_t v                              the data prediction: two products and a difference, no division
+ * for all three samplers: under TSD_PRED_V a DDPM session runs this update as well, with the posterior's scalars in double rounded once
+ * to float (the fp32 `DDPMSampler.step` kernel restates a reference that has no v-prediction and stays the epsilon path only), and it
+ * takes noise on every step with c_n != 0.
+ * Zero-terminal-SNR table: from the fp32 alphas_cumprod table ac[], in double, s_i = sqrt(ac[i]),
+ *     s'_i = (s_i - s_{N-1}) * s_0 / (s_0 - s_{N-1}),   ac'[i] = (float)(s'_i^2)           one rounding to float per entry
+ * so ac'[N-1] is exactly 0, ac'[0] equals ac[0] to rounding and the table strictly decreases.  diffusers (rescale_zero_terminal_snr)
+ * goes back through fp32 betas and a second cumprod: its table differs from this one in the last bits.  Needs n_train >= 2.
+ * At a timestep with abar = 0 (the first of a trailing list on that table) alpha_t = 0, sigma_t = 1, x0 = -v: the v rows are finite
+ * there (DPM-Solver++(2M)'s step is the DDIM(0) step; the step after it is first order, c_h = 0), the epsilon rows do not exist.
+ * Epsilon-prediction on the zero-terminal-SNR table is therefore allowed only while no timestep of the list has abar = 0 (leading
+ * spacing, or a start_step that drops it): TSD_E_ARG otherwise. */
+typedef enum tsd_prediction_type { TSD_PRED_EPSILON = 0, TSD_PRED_V = 1 } tsd_prediction_type;
+/* Host only, no GPU.  The alphas_cumprod table of n_train entries: zero_terminal_snr = 0 the table every session used so far (bitwise),
+ * 1 its rescale above.  Writes min(n_train, cap) entries (out may be NULL) and returns n_train; < 0 on a bad argument. */
+int tsd_sampler_alphas_cumprod(int n_train, int zero_terminal_snr, float* out, int cap);
+/* Host only, no GPU.  tsd_sampler_coeffs for a prediction type and a table choice; (TSD_PRED_EPSILON, 0) returns tsd_sampler_coeffs'
+ * doubles.  Under TSD_PRED_V out[5] multiplies v.  TSD_E_ARG for unknown values and for the refused combination above. */
+int tsd_sampler_coeffs_ex(int kind, double eta, int spacing, int n_train, int n_infer, int start_step, int i, int have_history,
+                          int prediction, int zero_terminal_snr, double out[8]);
+/* Op level, host fp32 in/out: the v update on n elements with caller-given scalars c[6] = { alpha_t, sigma_t, c_x, c_v, c_h, c_n } - the
+ * kernel a v-prediction session launches; the twin of tsd_sampler_step_f32, with the same optional pointers.  With the same c[2..5]
+ * its x_out is bitwise tsd_sampler_step_f32's; hist_out is alpha_t x - sigma_t v. */
+int tsd_sampler_step_v_f32(tsd_ctx* ctx, const float* x, const float* v, const float* v_uncond, float cfg_scale, const float* hist,
+                           const float* noise, int64_t n, const float* c, float* x_out, float* hist_out);
 /* Op level, host fp32 in/out, synchronous: the update of step i of a DDPM session with this schedule (spacing, n_train, n_infer,
  * start_step as in tsd_sampler_coeffs) on n elements - the kernel and the fp32 scalars of `DDPMSampler.step` the session launches.
  * eps_uncond and noise may be NULL; like the session, the noise is added only on a step that does not land on t = 0. */
@@ -386,6 +416,16 @@ int tsd_session_set_schedule(tsd_session* s, int num_training_steps, int num_inf
  * previous call on the session was step(i - 1) since the last upload() / add_noise() / set_*() - otherwise step i runs first order.
  * With DDPM or DDIM(eta > 0) and no uploaded noise the update is noiseless; DPM-Solver++(2M) ignores the noise. */
 int tsd_session_set_sampler(tsd_session* s, int kind, float eta, int spacing);
+/* What the model output means (a tsd_prediction_type) and which alphas_cumprod table the session runs on (zero_terminal_snr 0 / 1; see
+ * "v-prediction" above).  Session configuration like set_sampler: rebuilds the table and the step plans and invalidates the upload
+ * (TSD_E_STATE until upload() / slots_open()); it persists across uploads; the default is (TSD_PRED_EPSILON, 0), with which a session
+ * enqueues the launches and computes the bits it always did.  Everything that reads the table follows it: add_noise*, the inpainting
+ * blend's scalars (lockstep and per slot) and slot_start's noise at the start - at the index of abar = 0, add_noise leaves exactly the
+ * noise.  All slots share it.  Guidance rescale is unchanged: it scales the model output whatever it means.
+ * TSD_E_ARG for unknown values, and from whichever of set_schedule, set_sampler and set_prediction completes epsilon-prediction on a
+ * timestep list with abar = 0; a refused call leaves the session as it was. */
+int tsd_session_set_prediction(tsd_session* s, int prediction, int zero_terminal_snr);
+int tsd_session_prediction(tsd_session* s, int* prediction, int* zero_terminal_snr);
 int tsd_session_num_steps(tsd_session* s);
 int tsd_session_timestep(tsd_session* s, int i); /* i-th timestep of the schedule */
 /* Upload state.  latents [B,4,LH,LW] (L,L below: the session's LH,LW); context [B,T,768]; uncond_context [B,T,768] or NULL;

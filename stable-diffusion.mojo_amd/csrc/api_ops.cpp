@@ -268,6 +268,29 @@ extern "C" int tsd_sampler_step_f32(tsd_ctx* ctx, const float* x, const float* e
   });
 }
 
+// one update of a v-prediction session (kernels_vpred.hip k_sampler_step_v) on host tensors: tsd_sampler_step_f32's twin
+extern "C" int tsd_sampler_step_v_f32(tsd_ctx* ctx, const float* x, const float* v, const float* v_uncond, float cfg_scale,
+                                      const float* hist, const float* noise, int64_t n, const float* c, float* x_out,
+                                      float* hist_out) {
+  NOTNULL(x); NOTNULL(v); NOTNULL(c); NOTNULL(x_out);
+  if (n <= 0) TSD_FAIL(TSD_E_SHAPE, "sampler step (v): n=%lld", (long long)n);
+  const SamplerCoeffs sc = {c[0], c[1], c[2], c[3], c[4], c[5]};
+  return run_op(ctx, [&]() -> int {
+    Dev d{ctx};
+    float* dx = d.in(x, n);
+    float* dv = d.in(v, n);
+    float* du = v_uncond ? d.in(v_uncond, n) : nullptr;
+    float* dh = hist ? d.in(hist, n) : nullptr;
+    float* dz = noise ? d.in(noise, n) : nullptr;
+    float* dy = d.buf<float>(n);
+    float* dho = hist_out ? d.buf<float>(n) : nullptr;
+    if (d.err) return d.err;
+    TSD_TRY(launch_sampler_step_v(ctx, dx, dv, du, cfg_scale, dh, dz, n, sc, 0, dy, dho));
+    if (hist_out) TSD_TRY(d.out(hist_out, dho, n));
+    return d.out(x_out, dy, n);
+  });
+}
+
 // the update of step i of a DDPM session (kernels_elementwise.hip k_ddpm_step, the scalars of sampler_step_plan) on host tensors;
 // like the session, the noise is added only on a step that does not land on t = 0
 extern "C" int tsd_ddpm_step_f32(tsd_ctx* ctx, const float* x, const float* eps, const float* eps_uncond, float cfg_scale,
@@ -280,7 +303,7 @@ extern "C" int tsd_ddpm_step_f32(tsd_ctx* ctx, const float* x, const float* eps,
   std::vector<float> ac;
   sampler_alphas_cumprod(n_train, ac);
   SlotEntry p;
-  TSD_TRY(sampler_step_plan(TSD_SAMPLER_DDPM, 0.0, spacing, n_train, n_infer, ac, ts, i, false, &p));
+  TSD_TRY(sampler_step_plan(TSD_SAMPLER_DDPM, 0.0, spacing, n_train, n_infer, ac, ts, i, false, TSD_PRED_EPSILON, &p));
   return run_op(ctx, [&]() -> int {
     Dev d{ctx};
     float* dx = d.in(x, n);

@@ -401,6 +401,13 @@ int launch_sampler_step(tsd_ctx* ctx, const float* x, const float* eps, const fl
 int launch_sampler_step_seeded(tsd_ctx* ctx, const float* x, const float* eps, const float* eps_uncond, float cfg_scale,
                                const float* hist_in, const NormalBases& bases, int64_t chw, int64_t n, const SamplerCoeffs& c,
                                int eps_hw, float* x_out, float* hist_out);
+// The two updates for a model output that means v = alpha e - sigma x0 (kernels_vpred.hip): the same x_out arithmetic with v in place of e
+// (c.c_e multiplies v) and hist_out = alpha_t x - sigma_t v, which divides by nothing.  Arguments as above.
+int launch_sampler_step_v(tsd_ctx* ctx, const float* x, const float* v, const float* v_uncond, float cfg_scale, const float* hist_in,
+                          const float* noise, int64_t n, const SamplerCoeffs& c, int eps_hw, float* x_out, float* hist_out);
+int launch_sampler_step_v_seeded(tsd_ctx* ctx, const float* x, const float* v, const float* v_uncond, float cfg_scale,
+                                 const float* hist_in, const NormalBases& bases, int64_t chw, int64_t n, const SamplerCoeffs& c,
+                                 int eps_hw, float* x_out, float* hist_out);
 // dst[b * per_sample + j] = normal_counter(bases.base[b], first + j) for the n = (samples) * per_sample elements of dst, n <= 16 per_sample
 // (kernels_sampler.hip k_fill_normal): N(0,1) of the counter RNG, the values the seeded updates draw inline
 int launch_fill_normal(tsd_ctx* ctx, float* dst, int64_t n, int64_t per_sample, const NormalBases& bases, uint64_t first);
@@ -447,6 +454,13 @@ struct SlotBlendTable {
 int launch_slot_update_blend(tsd_ctx* ctx, float* x, const float* eps, const float* eps_uncond, float* hist, const SlotTable& tab,
                              const SlotBlendTable& blend, const float* mask, const float* known, const float* noise, int B, int64_t chw,
                              int eps_hw);
+// The two slot updates of a v-prediction session (kernels_vpred.hip): every entry is SLOT_SKIP or SLOT_LMS (TSD_E_ARG for SLOT_DDPM: a v
+// session never plans it), applied by the v element function.  The prediction type belongs to the launch: all slots share the model.
+int launch_slot_update_v(tsd_ctx* ctx, float* x, const float* v, const float* v_uncond, float* hist, const SlotTable& tab, int B,
+                         int64_t chw, int eps_hw);
+int launch_slot_update_blend_v(tsd_ctx* ctx, float* x, const float* v, const float* v_uncond, float* hist, const SlotTable& tab,
+                               const SlotBlendTable& blend, const float* mask, const float* known, const float* noise, int B,
+                               int64_t chw, int eps_hw);
 // rows of the hoisted time table for samples at different schedule indices: out[b][0..N) = ttab[row[b]][0..N), b < Bu <= 16
 struct SlotRows {
   int row[16];
@@ -477,6 +491,9 @@ int launch_cfg_rescale(tsd_ctx* ctx, float* eps, float* eps_uncond, const CfgRes
 
 // alphas_cumprod of the scaled-linear beta schedule (sampler.mojo:28-32), fp32 like the reference's Tensor
 void sampler_alphas_cumprod(int n_train, std::vector<float>& out);
+// the same table (zero_terminal_snr = 0, bitwise) or its zero-terminal-SNR rescale (1; Lin et al. 2023, algorithm 1 on sqrt(abar), in
+// double, one rounding to float per entry; the last entry is exactly 0).  TSD_E_ARG for another flag value, and for n_train < 2 under 1.
+int sampler_alphas_cumprod(int n_train, int zero_terminal_snr, std::vector<float>& out);
 // timestep list of `spacing` (tsd_timestep_spacing) with the first `start_step` entries dropped; TSD_E_ARG on a bad argument
 int sampler_timesteps(int spacing, int n_train, int n_infer, int start_step, std::vector<int>& out);
 // scalars of step i of `timesteps` as double: out[8] = { t, t_prev (-1: the clean sample), alpha_t, sigma_t, c_x, c_e, c_h, c_n }
@@ -486,8 +503,16 @@ int sampler_coeffs(int kind, double eta, const std::vector<float>& alphas_cumpro
 // Fills e->mode (SLOT_DDPM / SLOT_LMS), e->c[] in the order documented at SlotEntry and e->flags: SLOT_NOISE the update adds noise,
 // SLOT_HIST_IN it reads the previous step's x0 (hist_valid: the caller holds it for step i), SLOT_HIST_OUT it keeps its own.
 // cfg_scale is the caller's.  DDPM's previous timestep is t - n_train / n_infer under LEADING spacing, the next list entry under TRAILING.
+// prediction (tsd_prediction_type) says what the model output means.  Under TSD_PRED_V every sampler, DDPM included, is a SLOT_LMS entry
+// whose c[3] multiplies v, for the v kernels (launch_sampler_step_v ..): never SLOT_DDPM, and SLOT_NOISE wherever c_n != 0.
 int sampler_step_plan(int kind, double eta, int spacing, int n_train, int n_infer, const std::vector<float>& alphas_cumprod,
-                      const std::vector<int>& timesteps, int i, bool hist_valid, SlotEntry* e);
+                      const std::vector<int>& timesteps, int i, bool hist_valid, int prediction, SlotEntry* e);
+// TSD_E_ARG for an unknown prediction type, and for epsilon-prediction on a list with a timestep of alpha_bar = 0 (x0 does not exist)
+int sampler_prediction_ok(int prediction, const std::vector<float>& alphas_cumprod, const std::vector<int>& timesteps);
+// sampler_coeffs for either prediction type (checked by sampler_prediction_ok); under TSD_PRED_V out[5] multiplies v and no row
+// divides by alpha_t: finite at alpha_bar_t = 0
+int sampler_coeffs_ex(int kind, double eta, const std::vector<float>& alphas_cumprod, const std::vector<int>& timesteps, int i,
+                      int have_history, int prediction, double out[8]);
 
 // ---- non-finite accounting (kernels_elementwise.hip explains where it is reported) -------------------------------------------
 __device__ __forceinline__ bool nonfinite_f(float v) { return !(fabsf(v) <= 3.4028234e38f); }  // inf or NaN

@@ -52,6 +52,9 @@ struct tsd_session {
   // sampler (tsd_session_set_sampler); the default is the reference's DDPMSampler on its own timestep rule
   int sampler = TSD_SAMPLER_DDPM, spacing = TSD_SPACING_LEADING;
   float eta = 0.f;
+  // what the model output means and which table alphas_cumprod is (tsd_session_set_prediction); persists across uploads.  Under
+  // TSD_PRED_V every plan is SLOT_LMS and step() / advance() launch the v kernels (kernels_vpred.hip)
+  int prediction = TSD_PRED_EPSILON, ztsnr = 0;
   // step index for which `hist` holds the previous step's x0: i + 1 after step(i), -1 after upload() / add_noise() / set_*() and
   // after a sampler that keeps no history.  A step with any other index runs first order.
   int hist_valid_for = -1;
@@ -170,10 +173,31 @@ static int session_fetch_latents(tsd_session* s, const float* dev, size_t n, flo
   return TSD_OK;
 }
 
-// alphas_cumprod (sampler.mojo:28-32) and the timestep list of the session's spacing with `start` entries dropped (sampler.cpp)
-static int build_schedule(tsd_session* s) {
-  sampler_alphas_cumprod(s->n_train, s->alphas_cumprod);
-  return sampler_timesteps(s->spacing, s->n_train, s->n_infer, s->start, s->timesteps);
+// The session's configuration: what set_schedule, set_sampler and set_prediction each change a part of.
+struct SessionConfig {
+  int n_train, n_infer, start, sampler, spacing, prediction, ztsnr;
+  float eta;
+};
+static SessionConfig session_config(const tsd_session* s) {
+  return {s->n_train, s->n_infer, s->start, s->sampler, s->spacing, s->prediction, s->ztsnr, s->eta};
+}
+static void schedule_changed(tsd_session* s);
+// alphas_cumprod (sampler.mojo:28-32, or its zero-terminal-SNR rescale) and the timestep list of the spacing with `start` entries dropped
+// (sampler.cpp), built aside and checked as a whole - epsilon-prediction cannot run a list with a timestep of alpha_bar = 0 - before the
+// session takes any of it: a refused configuration leaves the session, its upload included, as it was.
+static int session_configure(tsd_session* s, const SessionConfig& c) {
+  std::vector<float> ac;
+  std::vector<int> ts;
+  TSD_TRY(sampler_alphas_cumprod(c.n_train, c.ztsnr, ac));
+  TSD_TRY(sampler_timesteps(c.spacing, c.n_train, c.n_infer, c.start, ts));
+  TSD_TRY(sampler_prediction_ok(c.prediction, ac, ts));
+  s->n_train = c.n_train; s->n_infer = c.n_infer; s->start = c.start;
+  s->sampler = c.sampler; s->spacing = c.spacing; s->eta = c.eta;
+  s->prediction = c.prediction; s->ztsnr = c.ztsnr;
+  s->alphas_cumprod.swap(ac);
+  s->timesteps.swap(ts);
+  schedule_changed(s);
+  return TSD_OK;
 }
 // Fill the session's step-invariant buffers on the context's stream, with the launches (same kernels, same arguments, same batch) a
 // step's forward would make for them, so their contents are the bits the per-step path computes:
@@ -235,7 +259,8 @@ static int session_forward(tsd_session* s, const UNetPre* pre, int* eps_hw) {
 }
 // The scalars and flags of step i of this session's schedule (sampler_step_plan fills mode, flags and c[]; cfg_scale is the caller's)
 static int session_plan(const tsd_session* s, int i, bool hist_valid, SlotEntry* e) {
-  return sampler_step_plan(s->sampler, s->eta, s->spacing, s->n_train, s->n_infer, s->alphas_cumprod, s->timesteps, i, hist_valid, e);
+  return sampler_step_plan(s->sampler, s->eta, s->spacing, s->n_train, s->n_infer, s->alphas_cumprod, s->timesteps, i, hist_valid,
+                           s->prediction, e);
 }
 
 extern "C" int tsd_debug_set_session_hoist(tsd_ctx* ctx, int on) {
@@ -292,7 +317,7 @@ extern "C" int tsd_session_create_hw(tsd_model* diffusion, tsd_model* decoder, i
   s->hist = (float*)(s->state + o_hist);
   s->ip_mask = (float*)(s->state + o_ipm); s->ip_known = (float*)(s->state + o_ipk); s->ip_noise = (float*)(s->state + o_ipn);
   s->gr_part = (double*)(s->state + o_grp);
-  if (build_schedule(s) != TSD_OK) { hipFree(s->state); delete s; return TSD_E_ARG; }
+  if (session_configure(s, session_config(s)) != TSD_OK) { hipFree(s->state); delete s; return TSD_E_ARG; }
   *out = s;
   return TSD_OK;
 }
@@ -325,9 +350,9 @@ extern "C" int tsd_session_set_schedule(tsd_session* s, int num_training_steps, 
   if (num_training_steps <= 0 || num_inference_steps <= 0 || num_inference_steps > num_training_steps ||
       start_step < 0 || start_step >= num_inference_steps)
     TSD_FAIL(TSD_E_ARG, "schedule: train=%d infer=%d start=%d", num_training_steps, num_inference_steps, start_step);
-  s->n_train = num_training_steps; s->n_infer = num_inference_steps; s->start = start_step;
-  schedule_changed(s);
-  return build_schedule(s);
+  SessionConfig c = session_config(s);
+  c.n_train = num_training_steps; c.n_infer = num_inference_steps; c.start = start_step;
+  return session_configure(s, c);
 }
 extern "C" int tsd_session_set_sampler(tsd_session* s, int kind, float eta, int spacing) {
   NOTNULL(s);
@@ -336,9 +361,23 @@ extern "C" int tsd_session_set_sampler(tsd_session* s, int kind, float eta, int 
   if (spacing != TSD_SPACING_LEADING && spacing != TSD_SPACING_TRAILING)
     TSD_FAIL(TSD_E_ARG, "sampler: timestep spacing %d (0 leading, 1 trailing)", spacing);
   if (!(eta >= 0.f)) TSD_FAIL(TSD_E_ARG, "sampler: eta %g < 0", (double)eta);
-  s->sampler = kind; s->eta = eta; s->spacing = spacing;
-  schedule_changed(s);  // the timestep list may have changed: as after set_schedule
-  return build_schedule(s);
+  SessionConfig c = session_config(s);
+  c.sampler = kind; c.eta = eta; c.spacing = spacing;
+  return session_configure(s, c);  // the timestep list may have changed: as after set_schedule
+}
+extern "C" int tsd_session_set_prediction(tsd_session* s, int prediction, int zero_terminal_snr) {
+  NOTNULL(s);
+  if (prediction != TSD_PRED_EPSILON && prediction != TSD_PRED_V)
+    TSD_FAIL(TSD_E_ARG, "session: prediction type %d (0 epsilon, 1 v)", prediction);
+  if (zero_terminal_snr != 0 && zero_terminal_snr != 1) TSD_FAIL(TSD_E_ARG, "session: zero_terminal_snr %d (0 or 1)", zero_terminal_snr);
+  SessionConfig c = session_config(s);
+  c.prediction = prediction; c.ztsnr = zero_terminal_snr;
+  return session_configure(s, c);  // the table and every step's plan may have changed: as after set_schedule
+}
+extern "C" int tsd_session_prediction(tsd_session* s, int* prediction, int* zero_terminal_snr) {
+  NOTNULL(s); NOTNULL(prediction); NOTNULL(zero_terminal_snr);
+  *prediction = s->prediction; *zero_terminal_snr = s->ztsnr;
+  return TSD_OK;
 }
 extern "C" int tsd_session_num_steps(tsd_session* s) { return s ? (int)s->timesteps.size() : TSD_E_ARG; }
 extern "C" int tsd_session_timestep(tsd_session* s, int i) {
@@ -485,7 +524,11 @@ extern "C" int tsd_session_step(tsd_session* s, int i) {
   const NormalBases nb = draws ? session_bases(s, NOISE_STREAM_STEP0 + (uint64_t)i) : NormalBases();
   const float* c = p.c;
   const SamplerCoeffs sc = {c[0], c[1], c[2], c[3], c[4], c[5]};
-  if (p.mode == SLOT_DDPM && draws)
+  if (s->prediction == TSD_PRED_V && draws)  // a v plan is SLOT_LMS for every sampler: the v twins of the two launches below
+    TSD_TRY(launch_sampler_step_v_seeded(ctx, s->latents, s->eps, eps_u, s->cfg_scale, hist_in, nb, chw, nl, sc, eps_hw, s->latents, hist_out));
+  else if (s->prediction == TSD_PRED_V)
+    TSD_TRY(launch_sampler_step_v(ctx, s->latents, s->eps, eps_u, s->cfg_scale, hist_in, nz, nl, sc, eps_hw, s->latents, hist_out));
+  else if (p.mode == SLOT_DDPM && draws)
     TSD_TRY(launch_ddpm_step_seeded(ctx, s->latents, s->eps, eps_u, s->cfg_scale, nb, chw, nl, c[0], c[1], c[2], c[3], c[4], eps_hw));
   else if (p.mode == SLOT_DDPM)
     TSD_TRY(launch_ddpm_step(ctx, s->latents, s->eps, eps_u, s->cfg_scale, nz, nl, c[0], c[1], c[2], c[3], c[4], eps_hw));
@@ -858,7 +901,12 @@ extern "C" int tsd_session_advance(tsd_session* s, uint32_t* finished_mask) {
   // the update launch: with an inpainting slot among the active ones, the kernel that also blends (no further launch either way)
   const float* eps_u = s->cfg ? s->eps + nl : nullptr;
   if (rescaling) TSD_TRY(launch_cfg_rescale(ctx, s->eps, s->eps + nl, gr, B, chw, s->gr_part, nullptr));
-  if (blending)
+  if (s->prediction == TSD_PRED_V && blending)  // the prediction type belongs to the launch: all slots share the model
+    TSD_TRY(launch_slot_update_blend_v(ctx, s->latents, s->eps, eps_u, s->hist, tab, blend, s->ip_mask, s->ip_known, s->ip_noise, B,
+                                       chw, eps_hw));
+  else if (s->prediction == TSD_PRED_V)
+    TSD_TRY(launch_slot_update_v(ctx, s->latents, s->eps, eps_u, s->hist, tab, B, chw, eps_hw));
+  else if (blending)
     TSD_TRY(launch_slot_update_blend(ctx, s->latents, s->eps, eps_u, s->hist, tab, blend, s->ip_mask, s->ip_known, s->ip_noise, B,
                                      chw, eps_hw));
   else

@@ -1,6 +1,6 @@
 // update_element.h - one element of a sampler update, shared by every kernel that applies one: k_ddpm_step / k_ddpm_step_seeded
 // (kernels_elementwise.hip), k_sampler_step / k_sampler_step_seeded (kernels_sampler.hip) and k_slot_update / k_slot_update_blend
-// (kernels_slots.hip).  The lockstep kernels and the per-slot kernels inline the SAME function, so a slot's update gives the bits of the
+// (kernels_slots.hip), and by their v-prediction siblings (kernels_vpred.hip).  The lockstep kernels and the per-slot kernels inline the SAME function, so a slot's update gives the bits of the
 // lockstep step it stands for.
 // Include after common.h.
 #pragma once
@@ -128,6 +128,63 @@ __device__ __forceinline__ int sampler_step_element(int64_t i, const float* x, c
     const float se = c.sigma_t * e;
     const float xs = xv - se;
     hist_out[i] = xs / c.alpha_t;
+  }
+  int nbad = nonfinite_f(o);  // a non-finite UNet output (fp16 overflow upstream) lands here every step
+  x_out[i] = post(i, o, nbad);
+  return nbad;
+}
+
+// ---- the same update for a model output that means v = alpha e - sigma x0 (Salimans & Ho 2022; kernels_vpred.hip) ------------
+// x0 = alpha_t x - sigma_t v and e = sigma_t x + alpha_t v, so the scalars fold into c_x and c.c_e (which multiplies v here) on the host
+// and x_out is sampler_step_element's sequence with v in place of e: the same operations in the same order, ONE fp32 rounding each.
+// What differs is the history store,
+//   hx = alpha_t x ; hv = sigma_t v ; h_out = hx - hv
+// which divides by nothing: at the terminal step of a zero-terminal-SNR table (alpha_t = 0, sigma_t = 1) it is 0 - v = -v exactly,
+// where the eps form is 0 / 0.  Roundings on the longest path
+//   x_out: v (sub, mul, add) -> * c_v -> + c_x x -> + c_h h -> + c_n z = 7;   h_out: v (3) -> * sigma_t -> hx - . = 5
+// which is what tests/test_gpu_vpred.py bounds the kernels with.  A sibling of sampler_step_element, not a parameter of it: the eps
+// instantiations keep the instruction streams they were blessed with (isa_contract.json).
+template <bool SEEDED, class Post = StoreAsIs>
+__device__ __forceinline__ int sampler_step_v_element(int64_t i, const float* x, const float* __restrict__ vp,
+                                                      const float* __restrict__ vp_u, float cfg_scale, const float* hist_in,
+                                                      const float* __restrict__ noise, const NormalBases& bases, int64_t chw,
+                                                      const SamplerCoeffs& c, int eps_hw, float* x_out, float* hist_out,
+                                                      const Post& post = Post()) {
+#pragma clang fp contract(off)
+  int64_t ie = i;
+  if (eps_hw > 0) {
+    const int64_t bc = i / eps_hw, pix = i - bc * eps_hw, b = bc >> 2;
+    ie = (b * eps_hw + pix) * 4 + (bc & 3);
+  }
+  float v = vp[ie];
+  if (vp_u) {
+    const float u = vp_u[ie];
+    const float d = v - u;
+    const float ds = d * cfg_scale;
+    v = ds + u;
+  }
+  const float xv = x[i];
+  float o = c.c_x * xv;
+  const float tv = c.c_e * v;
+  o = o + tv;
+  if (hist_in) {
+    const float th = c.c_h * hist_in[i];
+    o = o + th;
+  }
+  if constexpr (SEEDED) {
+    const int64_t b = i / chw;
+    const float tn = c.c_n * normal_counter(bases.base[b], (uint64_t)(i - b * chw));
+    o = o + tn;
+  } else {
+    if (noise) {
+      const float tn = c.c_n * noise[i];
+      o = o + tn;
+    }
+  }
+  if (hist_out) {
+    const float hx = c.alpha_t * xv;
+    const float hv = c.sigma_t * v;
+    hist_out[i] = hx - hv;
   }
   int nbad = nonfinite_f(o);  // a non-finite UNet output (fp16 overflow upstream) lands here every step
   x_out[i] = post(i, o, nbad);

@@ -19,8 +19,8 @@ from . import _lib, rng  # noqa: F401
 from . import ext  # noqa: F401  (non-reference extensions: torch-style norms)
 from ._lib import Context, TsdError, default_context, set_default_context, set_strict  # noqa: F401
 from .model import Model, Session, flop_count, param_specs  # noqa: F401
-from .utils import (Conv2D, Gelu, GroupNorm, LayerNorm, Linear, SiLU, Softmax, Upsample, cfg_rescale, concat,  # noqa: F401
-                    ddpm_step, get_time_embedding, inpaint_blend, latent_mask, matmul, normal_fill, pad, rescale)
+from .utils import (Conv2D, Gelu, GroupNorm, LayerNorm, Linear, SiLU, Softmax, Upsample, alphas_cumprod, cfg_rescale, concat,  # noqa: F401
+                    ddpm_step, get_time_embedding, inpaint_blend, latent_mask, matmul, normal_fill, pad, rescale, sampler_step_v)
 from .attention import Cross_Attention, Self_Attention  # noqa: F401
 from .diffusion import (Diffusion, Time_Embedding, UNet, UNet_Output_Layer, Unet_Attention_Block,  # noqa: F401
                         Unet_Residual_Block)

@@ -25,6 +25,7 @@ MODEL_CLIP_TORCH, MODEL_DECODER_TORCH, MODEL_ENCODER_TORCH = 7, 8, 9
 SAMPLER_KINDS = {"ddpm": 0, "ddim": 1, "dpmpp_2m": 2}      # tsd_sampler_kind
 TIMESTEP_SPACINGS = {"leading": 0, "trailing": 1}          # tsd_timestep_spacing
 MASK_MODES = {"area": 0, "any": 1}                         # tsd_mask_mode
+PREDICTION_TYPES = {"epsilon": 0, "v": 1}                  # tsd_prediction_type ("v_prediction": diffusers' name for "v")
 
 
 def sampler_kind(kind):
@@ -40,6 +41,14 @@ def timestep_spacing(spacing):
 def mask_mode(mode):
     """"area" | "any" (or the enum value) -> tsd_mask_mode."""
     return MASK_MODES.get(mode.lower(), -1) if isinstance(mode, str) else int(mode)
+
+
+def prediction_type(prediction):
+    """"epsilon" | "v" | "v_prediction" (or the enum value) -> tsd_prediction_type; an unknown name goes to the library, which refuses it."""
+    if isinstance(prediction, str):
+        name = prediction.lower()
+        return PREDICTION_TYPES.get("v" if name == "v_prediction" else name, -1)
+    return int(prediction)
 
 
 def check_guidance_rescale(phi, cfg=True):
@@ -138,6 +147,10 @@ def _declare(l):
         "tsd_sampler_timesteps": ([i, i, i, i, C.POINTER(i), i], i),
         "tsd_sampler_coeffs": ([i, C.c_double, i, i, i, i, i, i, C.POINTER(C.c_double)], i),
         "tsd_sampler_step_f32": ([vp, fp, fp, fp, f, fp, fp, i64, fp, fp, fp], i),
+        "tsd_sampler_alphas_cumprod": ([i, i, fp, i], i),
+        "tsd_sampler_coeffs_ex": ([i, C.c_double, i, i, i, i, i, i, i, i, C.POINTER(C.c_double)], i),
+        "tsd_sampler_step_v_f32": ([vp, fp, fp, fp, f, fp, fp, i64, fp, fp, fp], i),
+        "tsd_session_set_prediction": ([vp, i, i], i), "tsd_session_prediction": ([vp, C.POINTER(i), C.POINTER(i)], i),
         "tsd_ddpm_step_f32": ([vp, fp, fp, fp, f, fp, i64, i, i, i, i, i, fp], i),
         "tsd_cfg_rescale_f32": ([vp, fp, fp, i, i64, fp, fp, fp, fp, fp], i),
         "tsd_session_set_guidance_rescale": ([vp, f], i), "tsd_session_guidance_rescale": ([vp, fp], i),

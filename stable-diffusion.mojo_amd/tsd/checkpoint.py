@@ -321,3 +321,35 @@ def load_vae(path_or_state, which="decoder", ctx=None):
                 raise KeyError(f"checkpoint has no tensor for {name}")
             params[name] = np.zeros(shape, np.float32)
     return (Decoder if which == "decoder" else Encoder)(ctx=ctx, params=params, variant=which + "_torch")
+
+
+# ---- scheduler_config.json (diffusers) -> the keywords of `generate` / `generate_stream` ---------------------------------------------
+def read_scheduler_config(path):
+    """A diffusers scheduler_config.json -> {"prediction", "zero_terminal_snr", "spacing", "num_training_steps"}, the keywords `generate`
+    and `generate_stream` take (the sampler itself is the caller's choice).  Reads prediction_type ("epsilon" | "v_prediction"),
+    rescale_betas_zero_snr, timestep_spacing ("leading" | "trailing") and num_train_timesteps; a missing key has diffusers' default.
+    ValueError for what the engine does not have: another beta schedule than "scaled_linear", other beta_start / beta_end than 0.00085 /
+    0.012 (the one table, `tsd.alphas_cumprod`), trained_betas, "sample" prediction, "linspace" spacing."""
+    with open(path, "r", encoding="utf-8") as f:
+        cfg = json.load(f)
+    if not isinstance(cfg, dict):
+        raise ValueError(f"{path}: a scheduler config is a JSON object")
+    sched = cfg.get("beta_schedule", "scaled_linear")
+    if sched != "scaled_linear":
+        raise ValueError(f"{path}: beta_schedule {sched!r} is not supported (the engine's table is 'scaled_linear')")
+    if cfg.get("trained_betas") is not None:
+        raise ValueError(f"{path}: trained_betas is not supported (the engine's table is scaled_linear 0.00085 .. 0.012)")
+    b0, b1 = cfg.get("beta_start", 0.00085), cfg.get("beta_end", 0.012)
+    if abs(float(b0) - 0.00085) > 1e-12 or abs(float(b1) - 0.012) > 1e-12:
+        raise ValueError(f"{path}: beta_start / beta_end {b0} / {b1} are not supported (the engine's table is 0.00085 .. 0.012)")
+    pred = {"epsilon": "epsilon", "v_prediction": "v"}.get(cfg.get("prediction_type", "epsilon"))
+    if pred is None:
+        raise ValueError(f"{path}: prediction_type {cfg.get('prediction_type')!r} is not supported ('epsilon' or 'v_prediction')")
+    spacing = cfg.get("timestep_spacing", "leading")
+    if spacing not in ("leading", "trailing"):
+        raise ValueError(f"{path}: timestep_spacing {spacing!r} is not supported ('leading' or 'trailing')")
+    n_train = cfg.get("num_train_timesteps", 1000)
+    if not isinstance(n_train, int) or isinstance(n_train, bool) or n_train <= 0:
+        raise ValueError(f"{path}: num_train_timesteps {n_train!r} is not a positive integer")
+    return {"prediction": pred, "zero_terminal_snr": bool(cfg.get("rescale_betas_zero_snr", False)), "spacing": spacing,
+            "num_training_steps": n_train}

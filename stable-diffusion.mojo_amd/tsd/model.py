@@ -4,7 +4,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import check, check_guidance_rescale, f32, latent_shape, lib, ptr, sampler_kind, timestep_spacing, vp
+from ._lib import check, check_guidance_rescale, f32, latent_shape, lib, prediction_type, ptr, sampler_kind, timestep_spacing, vp
 
 KINDS = {"diffusion": _lib.MODEL_DIFFUSION, "decoder": _lib.MODEL_DECODER, "encoder": _lib.MODEL_ENCODER,
          "clip": _lib.MODEL_CLIP, "diffusion_sd15": _lib.MODEL_DIFFUSION_SD15,
@@ -156,6 +156,20 @@ class Session:
         """"ddpm" (the reference's, default) | "ddim" (eta = 0 deterministic) | "dpmpp_2m"; spacing "leading" | "trailing".
         Like set_schedule it invalidates the upload."""
         check(lib().tsd_session_set_sampler(self.h, sampler_kind(kind), float(eta), timestep_spacing(spacing)))
+
+    def set_prediction(self, prediction="epsilon", zero_terminal_snr=False):
+        """What the model output means, "epsilon" (default) | "v" (Salimans & Ho 2022; diffusers' "v_prediction" is accepted), and whether
+        the session runs on the zero-terminal-SNR rescale of the alphas_cumprod table (Lin et al. 2023, algorithm 1).  Session
+        configuration like set_sampler: it invalidates the upload and persists across uploads.  Epsilon-prediction on a timestep list
+        that contains the terminal timestep of that table (trailing spacing) is refused."""
+        check(lib().tsd_session_set_prediction(self.h, prediction_type(prediction), 1 if zero_terminal_snr else 0))
+
+    @property
+    def prediction(self):
+        """(prediction, zero_terminal_snr) as set_prediction takes them."""
+        p, z = C.c_int(0), C.c_int(0)
+        check(lib().tsd_session_prediction(self.h, C.byref(p), C.byref(z)))
+        return ("epsilon", "v")[p.value], bool(z.value)
 
     @property
     def num_steps(self):

@@ -26,7 +26,7 @@ def encode_prompts(prompts, tokenizer, clip):
 def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg=True, cfg_scale=7.5,
              inference_steps=50, seed_val=0, input_image=None, encoder=None, latents=None, noise=None,
              num_training_steps=1000, L=64, return_latents=False, sampler="ddpm", eta=0.0, spacing="leading", mask=None,
-             mask_mode="any", seeds=None, guidance_rescale=0.0):
+             mask_mode="any", seeds=None, guidance_rescale=0.0, prediction="epsilon", zero_terminal_snr=False):
     """context (B,T,768); returns images (B,3,8LH,8LW) in [0,255] like pipeline.mojo:127.  L is the latent side (64: 512x512) or a pair
     (LH, LW) for a rectangular image ((96, 64): 512 wide, 768 high); where the text below says L,L the tensor is LH,LW.
 
@@ -47,7 +47,12 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
 
     guidance_rescale in [0, 1] (Lin et al. 2023, eq. 15-16; diffusers' argument of the same name), with cfg=True: every step scales
     the guided prediction back towards the conditional prediction's per-sample standard deviation (`Session.set_guidance_rescale`);
-    0.7 is the paper's value against the over-saturation of guidance scales of 7 and more.  0 is the reference's loop."""
+    0.7 is the paper's value against the over-saturation of guidance scales of 7 and more.  0 is the reference's loop.
+
+    prediction "epsilon" (the reference's models) | "v" (v-prediction models: SD-2.x-768-style checkpoints and v fine-tunes), and
+    zero_terminal_snr=True for a model trained on the rescaled schedule of Lin et al. 2023 (algorithm 1), which wants "v" and
+    spacing="trailing" so that sampling starts from pure noise (`Session.set_prediction`; `checkpoint.read_scheduler_config` maps a
+    diffusers scheduler_config.json to these keywords).  The defaults are the reference's loop."""
     guidance_rescale = check_guidance_rescale(guidance_rescale, cfg)
     if seeds is not None and (noise is not None or latents is not None):
         raise ValueError("generate(seeds=...) draws latents and noise on the device: pass neither noise nor latents")
@@ -69,6 +74,8 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
     start = 0
     if input_image is not None:
         start = inference_steps - int(inference_steps * strength)  # sampler.mojo:68-70
+    if (prediction, bool(zero_terminal_snr)) != ("epsilon", False):  # likewise: the default session never hears of it
+        sess.set_prediction(prediction, zero_terminal_snr)
     if (sampler, eta, spacing) != ("ddpm", 0.0, "leading"):  # the default session is the reference's: nothing to set
         sess.set_sampler(sampler, eta, spacing)
     sess.set_schedule(num_training_steps, inference_steps, start)

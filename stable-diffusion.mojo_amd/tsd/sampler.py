@@ -44,13 +44,42 @@ class DDPMSampler:
 class _LinearMultistepSampler(DDPMSampler):
     """Host mirror of the samplers the device session runs through `k_sampler_step` (include/tsd.h "samplers"):
     x' = c_x x + c_e e + c_h h + c_n z with x0 = (x - sigma_t e) / alpha_t and h the previous step's x0.  The scalars are
-    restated here in float64 on the same fp32 alphas_cumprod table; `tsd_sampler_coeffs` is the implementation the session uses."""
+    restated here in float64 on the same fp32 alphas_cumprod table; `tsd_sampler_coeffs` is the implementation the session uses.
 
-    def __init__(self, num_training_steps=1000, spacing="leading", **kw):
+    prediction "v" (the model output means v = alpha e - sigma x0: x0 = alpha_t x - sigma_t v, and c_e multiplies v) and
+    zero_terminal_snr=True (the rescaled table of `tsd.alphas_cumprod`) mirror `Session.set_prediction`.  With either, the table and the
+    scalars are the library's own (`tsd_sampler_alphas_cumprod`, `tsd_sampler_coeffs_ex`; host code, no GPU), not a restatement: the
+    restatement of the v rows is tests/vpred_ref.py."""
+    KIND = None  # tsd_sampler_kind of the subclass
+
+    def __init__(self, num_training_steps=1000, spacing="leading", prediction="epsilon", zero_terminal_snr=False, **kw):
         super().__init__(num_training_steps=num_training_steps, **kw)
         if spacing not in ("leading", "trailing"):
             raise ValueError(f"spacing must be 'leading' or 'trailing', got {spacing!r}")
+        if prediction == "v_prediction":
+            prediction = "v"
+        if prediction not in ("epsilon", "v"):
+            raise ValueError(f"prediction must be 'epsilon' or 'v', got {prediction!r}")
         self.spacing = spacing
+        self.prediction = prediction
+        self.zero_terminal_snr = bool(zero_terminal_snr)
+        self._ex = prediction != "epsilon" or self.zero_terminal_snr
+        if self._ex:
+            if kw.get("beta_start", 0.00085) != 0.00085 or kw.get("beta_end", 0.0120) != 0.0120:
+                raise ValueError("prediction / zero_terminal_snr run on the library's table: beta_start and beta_end must be the defaults")
+            from .utils import alphas_cumprod
+            self.alphas_cumprod = alphas_cumprod(num_training_steps, self.zero_terminal_snr)
+
+    def _coefficients_ex(self, i, have_history, eta=0.0):
+        """The out[8] of `tsd_sampler_coeffs_ex` for this sampler's schedule, prediction type and table."""
+        import ctypes as C
+        from ._lib import PREDICTION_TYPES, TIMESTEP_SPACINGS, check, lib
+        out = (C.c_double * 8)()
+        check(lib().tsd_sampler_coeffs_ex(self.KIND, float(eta), TIMESTEP_SPACINGS[self.spacing], self.num_training_steps,
+                                          self.num_inference_steps, self.start_step, int(i), 1 if have_history else 0,
+                                          PREDICTION_TYPES[self.prediction], 1 if self.zero_terminal_snr else 0, out))
+        t, tp = int(out[0]), int(out[1])
+        return (t, tp) + tuple(float(v) for v in out[2:])
 
     def set_inference_timesteps(self, num_inference_steps=1):
         if self.spacing == "leading":
@@ -78,17 +107,21 @@ class _LinearMultistepSampler(DDPMSampler):
             out = out + c_h * np.asarray(history, dtype=np.float64)
         if noise is not None:
             out = out + c_n * np.asarray(noise, dtype=np.float64)
-        return out, (x - sg * e) / al
+        return out, (al * x - sg * e) if self.prediction == "v" else (x - sg * e) / al
 
 
 class DDIMSampler(_LinearMultistepSampler):
     """DDIM (Song et al. 2021, eq. 12; sigma = eta * eq. 16).  eta = 0 is deterministic, eta = 1 is the DDPM posterior."""
+
+    KIND = 1
 
     def __init__(self, num_training_steps=1000, eta=0.0, spacing="leading", **kw):
         super().__init__(num_training_steps, spacing, **kw)
         self.eta = float(eta)
 
     def coefficients(self, i, have_history=False):
+        if self._ex:
+            return self._coefficients_ex(i, have_history, self.eta)
         t, tp, a_t, a_p = self._step_scalars(i)
         var = self.eta ** 2 * (1.0 - a_p) / (1.0 - a_t) * (1.0 - a_t / a_p)
         c_x = np.sqrt(a_p / a_t)
@@ -99,8 +132,11 @@ class DDIMSampler(_LinearMultistepSampler):
 class DPMSolverMultistepSampler(_LinearMultistepSampler):
     """DPM-Solver++(2M) (Lu et al. 2022, algorithm 2, data prediction): second order from the previous step's x0; first order on
     the first step, on the step onto the clean sample and without history.  Deterministic (c_n = 0)."""
+    KIND = 2
 
     def coefficients(self, i, have_history=False):
+        if self._ex:
+            return self._coefficients_ex(i, have_history)
         t, tp, a_t, a_p = self._step_scalars(i)
         al, sg = np.sqrt(a_t), np.sqrt(1.0 - a_t)
         if tp < 0:                                          # lambda_prev is infinite: x' = x0

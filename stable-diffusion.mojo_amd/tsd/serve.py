@@ -140,7 +140,7 @@ class SlotScheduler:
 
 
 def generate_stream(diffusion, decoder, requests, B, L, T=77, cfg=True, inference_steps=50, num_training_steps=1000, sampler="ddpm",
-                    eta=0.0, spacing="leading", return_latents=False, stats=None):
+                    eta=0.0, spacing="leading", return_latents=False, stats=None, prediction="epsilon", zero_terminal_snr=False):
     """Continuous batching of `generate`: `requests` is an iterator of `Request`s (or tuples in its field order); yields (id, image
     (3,8LH,8LW) in [0,255]) - or (id, latents) with return_latents or without a decoder - as requests finish, B at a time on the device.
     L is the latent side or a pair (LH, LW): one shape for the whole stream.
@@ -149,11 +149,15 @@ def generate_stream(diffusion, decoder, requests, B, L, T=77, cfg=True, inferenc
     A request with a `mask` is inpainted in its slot (`Session.slot_set_inpaint`) next to the others: no drain, no extra launch.
     A request with `guidance_rescale` > 0 is rescaled in its slot (`Session.slot_set_guidance_rescale`), as `generate(...,
     guidance_rescale=...)` rescales it; it needs cfg=True.
+    prediction / zero_terminal_snr are `generate`'s keywords (`Session.set_prediction`): they belong to the model, so to the whole stream,
+    never to a request.
     Finished latents are decoded through `decoder.forward`, one image per call.  `stats`, a dict, receives advances / active_ticks / occupancy when the stream ends."""
     from .model import Session
     from .utils import _unary
     sess = Session(diffusion.model, None, B, L, T, cfg=cfg)
     try:
+        if (prediction, bool(zero_terminal_snr)) != ("epsilon", False):
+            sess.set_prediction(prediction, zero_terminal_snr)
         if (sampler, eta, spacing) != ("ddpm", 0.0, "leading"):
             sess.set_sampler(sampler, eta, spacing)
         sess.set_schedule(num_training_steps, inference_steps, 0)

@@ -250,6 +250,34 @@ def ddpm_step(x, eps, eps_uncond, cfg_scale, noise, i, num_inference_steps, num_
     return y
 
 
+def sampler_step_v(x, v, v_uncond, cfg_scale, hist, noise, c, want_hist=True, ctx=None):
+    """One update of a v-prediction session (`tsd_sampler_step_v_f32`) on host tensors with the scalars c = (alpha_t, sigma_t, c_x, c_v,
+    c_h, c_n), e.g. out[2:] of `tsd_sampler_coeffs_ex`: -> (x', h') with h' = alpha_t x - sigma_t v the data prediction (None without
+    want_hist).  v_uncond, hist and noise may be None: the term is skipped."""
+    x, vv = f32(x), f32(v)
+    u, h, z = (f32(a) if a is not None else None for a in (v_uncond, hist, noise))
+    if vv.shape != x.shape or any(a is not None and a.shape != x.shape for a in (u, h, z)):
+        raise ValueError(f"sampler_step_v: x {x.shape}, v {vv.shape} and the optional tensors must have one shape")
+    c6 = np.ascontiguousarray(np.asarray(c, dtype=np.float32).reshape(-1))
+    if c6.size != 6:
+        raise ValueError(f"sampler_step_v: c must hold the 6 scalars (alpha_t, sigma_t, c_x, c_v, c_h, c_n), got {c6.size}")
+    y = np.empty_like(x)
+    ho = np.empty_like(x) if want_hist else None
+    check(lib().tsd_sampler_step_v_f32(_ctx(ctx), ptr(x), ptr(vv), ptr(u), float(cfg_scale), ptr(h), ptr(z), x.size, ptr(c6), ptr(y), ptr(ho)))
+    return y, ho
+
+
+def alphas_cumprod(num_training_steps=1000, zero_terminal_snr=False):
+    """The alphas_cumprod table a session runs on (`tsd_sampler_alphas_cumprod`, host only): the reference's fp32 table, or its
+    zero-terminal-SNR rescale (Lin et al. 2023, algorithm 1), whose last entry is exactly 0."""
+    n = int(num_training_steps)
+    out = np.empty(max(n, 0), dtype=np.float32)
+    rc = lib().tsd_sampler_alphas_cumprod(n, 1 if zero_terminal_snr else 0, ptr(out), n)
+    if rc < 0:
+        check(rc)
+    return out
+
+
 def get_time_embedding(timestep, ctx=None):
     """`get_time_embedding` helpers/utils.mojo:353-370 -> (1,1,320)."""
     y = np.empty(320, dtype=np.float32)
