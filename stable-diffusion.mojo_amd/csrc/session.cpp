@@ -17,7 +17,7 @@ struct tsd_session {
   tsd_model* dec = nullptr;
   tsd_ctx* ctx = nullptr;
   int B = 0, LH = 0, LW = 0, T = 0, Tp = 0, cfg = 0;  // one shape per session: latents [.,4,LH,LW]
-  float cfg_scale = 7.5f;
+  int Bu = 0;                                         // the UNet's batch: 2B under CFG, else B
   // persistent device state (own allocation, not the arena)
   char* state = nullptr;
   float* latents = nullptr;   // [B,4,LH,LW] fp32 CHW (the reference's own layout)
@@ -59,15 +59,10 @@ struct tsd_session {
   // after a sampler that keeps no history.  A step with any other index runs first order.
   int hist_valid_for = -1;
   bool uploaded = false, has_noise = false;
-  // inpainting belongs to one upload(): off after upload() and after set_schedule / set_sampler; ip_has_noise: ip_noise was given
-  bool inpaint = false, ip_has_noise = false;
-  // seeded device-side noise (tsd_session_set_seeds) belongs to one upload() like inpainting: while on, a DDPM / DDIM(eta > 0) step draws
-  // its noise in the update kernel from stream 16 + i of seeds[b] (counter_rng.h), no buffer and no extra launch
+  bool ip_has_noise = false;  // lockstep inpainting: ip_noise was given (a slot's always is)
+  // seeded device-side noise (tsd_session_set_seeds) belongs to one upload(): while on, a DDPM / DDIM(eta > 0) step draws its noise in the
+  // update kernel from stream 16 + i of the sample's seed (counter_rng.h), no buffer and no extra launch.  Slots always draw.
   bool seeded = false;
-  uint64_t seeds[16] = {};
-  // guidance rescale (tsd_session_set_guidance_rescale) belongs to one upload() as well: phi > 0 puts launch_cfg_rescale between the
-  // forward and the update of a step; 0 = off, and a step enqueues what it always did
-  float rescale = 0.f;
   size_t plan_unet = 0, plan_dec = 0;
   unsigned opt_gen = 0;  // generation of the context's options the workspace was sized for (upload)
   // Latched when the host scan of a download found inf / NaN in THIS session's latents: the context's counter is cleared once reported,
@@ -80,14 +75,17 @@ struct tsd_session {
   // all active slots by one step with one forward.  `uploaded` stays false in slot mode - the lockstep entry points refuse by name
   // (SESSION_NOT_SLOTS) - and upload(), set_schedule and set_sampler leave it.  The index, not a timestep list, is the unit of state.
   bool slots = false;
+  // What one request asks of sample b, in both modes: a slot's own, or what upload() and the lockstep setters wrote for all B samples.  It
+  // belongs to one slot_start() / one upload(); a default-constructed record is "no request" (session_reset_requests).  state, index and
+  // hist_valid are the slot's progress; lockstep keeps its own in hist_valid_for and the step's argument.
   struct Slot {
     int state = 0;            // 0 idle, 1 active, 2 done
     int index = 0;            // next schedule index; num_steps when done
     float cfg_scale = 7.5f;
-    uint64_t seed = 0;
+    uint64_t seed = 0;        // set_seeds / slot_start: the streams of this sample's noise
     bool hist_valid = false;  // `hist` of this sample holds the x0 of the slot's previous step (DPM-Solver++(2M))
-    bool inpaint = false;     // slot_set_inpaint: sample b of ip_mask / ip_known / ip_noise is this request's; off after slot_start
-    float rescale = 0.f;      // slot_set_guidance_rescale: this request's phi; 0 after slot_start
+    bool inpaint = false;     // set_inpaint / slot_set_inpaint: sample b of ip_mask / ip_known / ip_noise is blended in after every step
+    float rescale = 0.f;      // set_guidance_rescale / slot_set_guidance_rescale: phi > 0 puts launch_cfg_rescale before the update
   } slot[16];
   float* trows = nullptr;     // [Bu][tproj.N] fp32: row i_b of ttab per sample, gathered by every advance (own allocation, grown at slots_open)
   size_t trows_cap = 0;
@@ -122,6 +120,15 @@ static bool host_all_finite(const float* p, size_t n) {
     if (!(s)->slots) TSD_FAIL(TSD_E_STATE, "session: slots_open() first (the session is not in slot mode)"); \
   } while (0)
 
+// The argument checks of the slot and step entry points, in NOTNULL's form (graph.h): slot b exists, is active, step i is in the list
+#define SLOT_IN_RANGE(s, b) \
+  if ((b) < 0 || (b) >= (s)->B) TSD_FAIL(TSD_E_ARG, "session: slot %d out of range (0..%d)", (b), (s)->B - 1)
+#define SLOT_IS_ACTIVE(s, b, what) \
+  if ((s)->slot[b].state != 1)     \
+  TSD_FAIL(TSD_E_STATE, "session: slot %d is %s; " what " belongs to an active request", (b), (s)->slot[b].state ? "done" : "idle")
+#define STEP_IN_RANGE(s, i) \
+  if ((i) < 0 || (i) >= (int)(s)->timesteps.size()) TSD_FAIL(TSD_E_ARG, "session: step %d out of range", (i))
+
 // ---- what the entry points share ---------------------------------------------------------------------------------------------
 // The workspace was sized under the context's options of upload() / slots_open() (`sized_by`); a tsd_debug_set_* call since then is refused.
 static int session_options_unchanged(const tsd_session* s, const char* sized_by) {
@@ -129,6 +136,10 @@ static int session_options_unchanged(const tsd_session* s, const char* sized_by)
     TSD_FAIL(TSD_E_STATE, "session: a tsd_debug_set_* call changed this context's options after %s sized the workspace; %s again",
              sized_by, sized_by);
   return TSD_OK;
+}
+// What belonged to one upload() / one slot_start() is gone: `count` request records from `first` are "no request" again.
+static void session_reset_requests(tsd_session* s, int first = 0, int count = 16) {
+  for (int b = first; b < first + count; b++) s->slot[b] = tsd_session::Slot();
 }
 // The latents are no longer those the history was predicted from, and the images are not theirs any more.
 static void session_latents_changed(tsd_session* s) {
@@ -181,7 +192,15 @@ struct SessionConfig {
 static SessionConfig session_config(const tsd_session* s) {
   return {s->n_train, s->n_infer, s->start, s->sampler, s->spacing, s->prediction, s->ztsnr, s->eta};
 }
-static void schedule_changed(tsd_session* s);
+// the device noise buffer and the workspace plan were sized for the OLD schedule, the history and the images belong to it: a new
+// upload() is required
+static void schedule_changed(tsd_session* s) {
+  s->uploaded = false; s->has_noise = false;
+  s->slots = false;
+  s->seeded = false;
+  session_reset_requests(s);
+  session_latents_changed(s);
+}
 // alphas_cumprod (sampler.mojo:28-32, or its zero-terminal-SNR rescale) and the timestep list of the spacing with `start` entries dropped
 // (sampler.cpp), built aside and checked as a whole - epsilon-prediction cannot run a list with a timestep of alpha_bar = 0 - before the
 // session takes any of it: a refused configuration leaves the session, its upload included, as it was.
@@ -208,7 +227,7 @@ static int session_configure(tsd_session* s, const SessionConfig& c) {
 static int session_build_invariants(tsd_session* s) {
   tsd_ctx* ctx = s->ctx;
   tsd_model* m = s->unet;
-  const int Bu = s->cfg ? 2 * s->B : s->B, N = m->unet.tproj.N;
+  const int Bu = s->Bu, N = m->unet.tproj.N;
   ctx->arena.top = 0;
   TSD_TRY(g_unet_ctx_kv(m, s->ctx16, s->Tp, Bu, s->kc_all, s->vtc_all));
   for (size_t i = 0; i < s->timesteps.size(); i++) {
@@ -242,7 +261,6 @@ static int session_refresh(tsd_session* s) {
 // where the forward can write it; the updates read it as such (no conversion launch): *eps_hw is their eps_hw argument.
 static int session_forward(tsd_session* s, const UNetPre* pre, int* eps_hw) {
   tsd_ctx* ctx = s->ctx;
-  const int Bu = s->cfg ? 2 * s->B : s->B;
   const size_t nl = (size_t)s->B * 4 * s->LH * s->LW;
   const float* lat_in = s->latents;
   if (s->cfg) {
@@ -252,15 +270,10 @@ static int session_forward(tsd_session* s, const UNetPre* pre, int* eps_hw) {
   }
   ctx->arena.top = 0;
   const bool eps_nhwc = s->unet->unet.final_conv.Opad == 4;  // g_unet_forward's condition for writing that layout
-  TSD_TRY(g_unet_forward(s->unet, lat_in, s->ctx16, s->T, s->Tp, s->temb, Bu, s->LH, s->LW, s->eps, eps_nhwc, s->hoist ? pre : nullptr));
+  TSD_TRY(g_unet_forward(s->unet, lat_in, s->ctx16, s->T, s->Tp, s->temb, s->Bu, s->LH, s->LW, s->eps, eps_nhwc, s->hoist ? pre : nullptr));
   ctx->arena.top = 0;
   *eps_hw = eps_nhwc ? s->LH * s->LW : 0;
   return TSD_OK;
-}
-// The scalars and flags of step i of this session's schedule (sampler_step_plan fills mode, flags and c[]; cfg_scale is the caller's)
-static int session_plan(const tsd_session* s, int i, bool hist_valid, SlotEntry* e) {
-  return sampler_step_plan(s->sampler, s->eta, s->spacing, s->n_train, s->n_infer, s->alphas_cumprod, s->timesteps, i, hist_valid,
-                           s->prediction, e);
 }
 
 extern "C" int tsd_debug_set_session_hoist(tsd_ctx* ctx, int on) {
@@ -271,17 +284,6 @@ extern "C" int tsd_debug_session_hoist_info(tsd_session* s, int64_t* info) {
   info[0] = (s->uploaded || s->slots) && s->hoist; info[1] = (int64_t)(uintptr_t)s->ttab; info[2] = (int64_t)(uintptr_t)s->kc_all;
   info[3] = (int64_t)(uintptr_t)s->vtc_all; info[4] = (int64_t)(s->kv_cap + s->ttab_cap); info[5] = s->inv_builds;
   return TSD_OK;
-}
-
-// the device noise buffer and the workspace plan were sized for the OLD schedule, the history and the images belong to it: a new
-// upload() is required
-static void schedule_changed(tsd_session* s) {
-  s->uploaded = false; s->has_noise = false;
-  s->slots = false;
-  s->inpaint = false;
-  s->seeded = false;
-  s->rescale = 0.f;
-  session_latents_changed(s);
 }
 
 extern "C" int tsd_session_create_hw(tsd_model* diffusion, tsd_model* decoder, int B, int LH, int LW, int T, int cfg,
@@ -298,7 +300,7 @@ extern "C" int tsd_session_create_hw(tsd_model* diffusion, tsd_model* decoder, i
   HIP_TRY(hipSetDevice(ctx->device));
   tsd_session* s = new tsd_session();
   s->unet = diffusion; s->dec = decoder; s->ctx = ctx;
-  s->B = B; s->LH = LH; s->LW = LW; s->T = T; s->Tp = round_up(T, 8); s->cfg = cfg ? 1 : 0;
+  s->B = B; s->LH = LH; s->LW = LW; s->T = T; s->Tp = round_up(T, 8); s->cfg = cfg ? 1 : 0; s->Bu = Bu;
   const size_t hw = (size_t)LH * LW, nl = (size_t)B * 4 * hw;
   size_t off = 0;
   auto carve = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~size_t(255); return o; };
@@ -389,17 +391,15 @@ extern "C" int tsd_session_timestep(tsd_session* s, int i) {
 // allocation inside the timed loop), size and fill the step-invariant buffers, and mark the session ready.
 static int session_prepare(tsd_session* s) {
   tsd_ctx* ctx = s->ctx;
-  const int B = s->B, LH = s->LH, LW = s->LW, T = s->T, Tp = s->Tp;
+  const int B = s->B, Bu = s->Bu, LH = s->LH, LW = s->LW, T = s->T, Tp = s->Tp;
   // size the workspace once for this session's shapes (no allocation inside the timed loop)
   TSD_TRY(model_check_ready(s->unet));
   if (s->dec) TSD_TRY(model_check_ready(s->dec));
   Arena& a = ctx->arena;
-  const int Bu = s->cfg ? 2 * B : B;
   s->hoist = ctx->opt.session_hoist != 0;
   s->uploaded = false;  // until this upload() is complete: the buffers below may move
-  s->inpaint = false;   // the mask and the known latents belonged to the previous upload()
-  s->seeded = false;    // and so did the seeds
-  s->rescale = 0.f;     // and the guidance rescale
+  s->seeded = false;    // the seeds belonged to the previous upload(),
+  session_reset_requests(s);  // and so did the mask, the known latents, the guidance rescale and the guidance scale
   if (s->hoist) {  // the buffers of session_build_invariants; sizes depend on the session's shape and the schedule's length only
     const int CK = s->unet->unet.kproj_all.N, N = s->unet->unet.tproj.N;
     const size_t kc_bytes = ((size_t)Bu * Tp * CK * 2 + 255) & ~size_t(255);
@@ -442,7 +442,6 @@ extern "C" int tsd_session_upload(tsd_session* s, const float* latents, const fl
   HIP_TRY(hipSetDevice(ctx->device));
   const int B = s->B;
   const size_t nl = (size_t)B * 4 * s->LH * s->LW;
-  s->cfg_scale = cfg_scale;
   s->slots = false;  // upload() leaves slot mode
   HIP_TRY(hipMemcpyAsync(s->latents, latents, nl * 4, hipMemcpyHostToDevice, ctx->stream));
   // context -> fp16 [Bu][Tp][768], zero padded rows (cond first, then uncond: pipeline.mojo:49)
@@ -456,36 +455,102 @@ extern "C" int tsd_session_upload(tsd_session* s, const float* latents, const fl
     HIP_TRY(hipMemcpyAsync(s->noise, noise, bytes, hipMemcpyHostToDevice, ctx->stream));
   }
   HIP_TRY(hipStreamSynchronize(ctx->stream));
-  return session_prepare(s);
+  TSD_TRY(session_prepare(s));
+  for (int b = 0; b < B; b++) s->slot[b].cfg_scale = cfg_scale;  // the one request field upload() itself carries
+  return TSD_OK;
 }
 
-// Streams of the seeded noise, per sample b with seeds[b]: 2 the initial latents, 4 the add_noise / inpainting noise, 16 + i the noise of
-// schedule step i; the counter is the element's index inside its sample, (c*LH + y)*LW + x.  Nothing depends on B or on the sample's slot.
+// Streams of the seeded noise, per sample b with its record's seed: 2 the initial latents, 4 the add_noise / inpainting noise, 16 + i the
+// noise of schedule step i; the counter is the element's index inside its sample, (c*LH + y)*LW + x.  Nothing depends on B or on the sample's slot.
 enum { NOISE_STREAM_LATENTS = 2, NOISE_STREAM_ADD = 4, NOISE_STREAM_STEP0 = 16 };
 static NormalBases session_bases(const tsd_session* s, uint64_t stream) {
   NormalBases nb = {};
-  for (int b = 0; b < s->B; b++) nb.base[b] = counter_rng_base(s->seeds[b], stream);
+  for (int b = 0; b < s->B; b++) nb.base[b] = counter_rng_base(s->slot[b].seed, stream);
   return nb;
 }
 
-// The launch a step with inpainting adds after its sampler update: the known region of `latents` is replaced by the original latents
-// noised to the timestep the update has just reached - entry i + 1 of the list, the clean sample (1, 0) after the last entry; under
-// LEADING spacing that entry is the reference's t - N // n.  a_prev = sqrt(abar), s_prev = sqrt(1 - abar) in double from the fp32 table,
-// rounded to float once: what tsd_sampler_coeffs reports as out[2], out[3] for step i + 1.  The same rule for all three samplers.
-// session_blend_scalars is that rule, for the lockstep launch and for every slot of an advance (the slot's own index).
-static void session_blend_scalars(const tsd_session* s, int i, float* a_prev, float* s_prev) {
-  double a = 1.0, sg = 0.0;
-  if (i + 1 < (int)s->timesteps.size()) {
-    const double abar = s->alphas_cumprod[s->timesteps[i + 1]];
-    a = sqrt(abar); sg = sqrt(1.0 - abar);
+// Everything the update of one step is told per sample, assembled in one place from the request records: sample b is active at schedule
+// index idx[b] (hist_valid[b]: `hist` holds its previous x0), or idx[b] < 0 and its entries stay zero - SLOT_SKIP, on = 0: neither read
+// nor written.  advance() passes each slot's own index; step(i) is the same thing with every sample at i.  Host arithmetic only.
+struct StepTables {
+  SlotTable tab;         // the plan of step idx[b] (sampler_step_plan), the request's cfg_scale, the base of stream 16 + idx[b] of its seed
+  SlotBlendTable blend;  // an inpainting request holds its known region at the timestep ITS update reaches
+  CfgRescaleTable gr;    // a request with phi > 0 is `on`; everyone else is neither read nor written by the rescale's launches
+  bool blending, rescaling;  // some entry of blend / gr is on
+};
+static int session_step_tables(const tsd_session* s, const int* idx, const bool* hist_valid, StepTables* t) {
+  *t = StepTables();
+  for (int b = 0; b < s->B; b++) {
+    const int i = idx[b];
+    if (i < 0) continue;
+    const tsd_session::Slot& r = s->slot[b];
+    t->tab.e[b].cfg_scale = r.cfg_scale;
+    t->tab.bases.base[b] = counter_rng_base(r.seed, NOISE_STREAM_STEP0 + (uint64_t)i);
+    TSD_TRY(sampler_step_plan(s->sampler, s->eta, s->spacing, s->n_train, s->n_infer, s->alphas_cumprod, s->timesteps, i, hist_valid[b],
+                              s->prediction, &t->tab.e[b]));
+    // The blend of a step with inpainting: the known region is replaced by the original latents noised to the timestep the update has
+    // just reached - entry i + 1 of the list, the clean sample (1, 0) after the last entry; under LEADING spacing that entry is the
+    // reference's t - N // n.  a_prev = sqrt(abar), s_prev = sqrt(1 - abar) in double from the fp32 table, rounded to float once: what
+    // tsd_sampler_coeffs reports as out[2], out[3] for step i + 1.  The same rule for all three samplers.
+    if (r.inpaint) {
+      const double abar = i + 1 < (int)s->timesteps.size() ? s->alphas_cumprod[s->timesteps[i + 1]] : 1.0;
+      t->blend.e[b] = {1, (float)sqrt(abar), (float)sqrt(1.0 - abar), 0};
+      t->blending = true;
+    }
+    if (r.rescale > 0.f) {
+      t->gr.e[b] = {1, r.cfg_scale, r.rescale, 0};
+      t->rescaling = true;
+    }
   }
-  *a_prev = (float)a; *s_prev = (float)sg;
+  return TSD_OK;
 }
-static int session_inpaint_blend(tsd_session* s, int i) {
-  float a_prev, s_prev;
-  session_blend_scalars(s, i, &a_prev, &s_prev);
-  return launch_inpaint_blend(s->ctx, s->latents, s->ip_mask, s->ip_known, s->ip_has_noise ? s->ip_noise : nullptr, s->B,
-                              (int64_t)s->LH * s->LW, a_prev, s_prev, s->latents);
+
+// The launches between a step's forward and its bookkeeping, and the only place that picks among the ten update launchers: the guidance
+// rescale (every `on` sample's cond and uncond eps scaled in place before the update reads them), the update, and in lockstep the blend.
+// lock_i < 0, an advance: the slot kernels read the tables; with an inpainting slot among the active ones, the kernel that also blends
+// (no further launch either way).  lock_i = i, a lockstep step: every entry is the same plan and the lockstep kernels take entry 0 as
+// scalars - they read the uploaded noise tensor, which no table carries.  Their noise is read from that tensor, drawn in the kernel (one
+// source per upload: has_noise is off under seeds) or absent; only DPM-Solver++(2M) reads or keeps the history, and it takes no noise.
+static int session_update(tsd_session* s, const StepTables& t, int eps_hw, int lock_i) {
+  tsd_ctx* ctx = s->ctx;
+  const int B = s->B;
+  const int64_t hw = (int64_t)s->LH * s->LW, chw = 4 * hw, nl = B * chw;
+  const float* eps_u = s->cfg ? s->eps + nl : nullptr;
+  const bool v = s->prediction == TSD_PRED_V;
+  if (t.rescaling) TSD_TRY(launch_cfg_rescale(ctx, s->eps, s->eps + nl, t.gr, B, chw, s->gr_part, nullptr));
+  if (lock_i < 0) {
+    if (v && t.blending)
+      return launch_slot_update_blend_v(ctx, s->latents, s->eps, eps_u, s->hist, t.tab, t.blend, s->ip_mask, s->ip_known, s->ip_noise, B,
+                                        chw, eps_hw);
+    if (v) return launch_slot_update_v(ctx, s->latents, s->eps, eps_u, s->hist, t.tab, B, chw, eps_hw);
+    if (t.blending)
+      return launch_slot_update_blend(ctx, s->latents, s->eps, eps_u, s->hist, t.tab, t.blend, s->ip_mask, s->ip_known, s->ip_noise, B,
+                                      chw, eps_hw);
+    return launch_slot_update(ctx, s->latents, s->eps, eps_u, s->hist, t.tab, B, chw, eps_hw);
+  }
+  const SlotEntry& p = t.tab.e[0];
+  const bool noisy = (p.flags & SLOT_NOISE) != 0, draws = noisy && s->seeded;
+  const float* nz = (noisy && s->has_noise) ? s->noise + (size_t)lock_i * nl : nullptr;
+  const float* hist_in = (p.flags & SLOT_HIST_IN) ? s->hist : nullptr;
+  float* hist_out = (p.flags & SLOT_HIST_OUT) ? s->hist : nullptr;
+  const float* c = p.c;
+  const SamplerCoeffs sc = {c[0], c[1], c[2], c[3], c[4], c[5]};
+  if (v && draws)
+    TSD_TRY(launch_sampler_step_v_seeded(ctx, s->latents, s->eps, eps_u, p.cfg_scale, hist_in, t.tab.bases, chw, nl, sc, eps_hw, s->latents, hist_out));
+  else if (v)
+    TSD_TRY(launch_sampler_step_v(ctx, s->latents, s->eps, eps_u, p.cfg_scale, hist_in, nz, nl, sc, eps_hw, s->latents, hist_out));
+  else if (p.mode == SLOT_DDPM && draws)
+    TSD_TRY(launch_ddpm_step_seeded(ctx, s->latents, s->eps, eps_u, p.cfg_scale, t.tab.bases, chw, nl, c[0], c[1], c[2], c[3], c[4], eps_hw));
+  else if (p.mode == SLOT_DDPM)
+    TSD_TRY(launch_ddpm_step(ctx, s->latents, s->eps, eps_u, p.cfg_scale, nz, nl, c[0], c[1], c[2], c[3], c[4], eps_hw));
+  else if (draws)
+    TSD_TRY(launch_sampler_step_seeded(ctx, s->latents, s->eps, eps_u, p.cfg_scale, hist_in, t.tab.bases, chw, nl, sc, eps_hw, s->latents, hist_out));
+  else
+    TSD_TRY(launch_sampler_step(ctx, s->latents, s->eps, eps_u, p.cfg_scale, hist_in, nz, nl, sc, eps_hw, s->latents, hist_out));
+  if (t.blending)
+    TSD_TRY(launch_inpaint_blend(ctx, s->latents, s->ip_mask, s->ip_known, s->ip_has_noise ? s->ip_noise : nullptr, B, hw,
+                                 t.blend.e[0].a_prev, t.blend.e[0].s_prev, s->latents));
+  return TSD_OK;
 }
 
 extern "C" int tsd_session_step(tsd_session* s, int i) {
@@ -494,57 +559,31 @@ extern "C" int tsd_session_step(tsd_session* s, int i) {
   if (!s->uploaded) TSD_FAIL(TSD_E_STATE, "session: upload() before step()");
   SESSION_NOT_POISONED(s);
   TSD_TRY(session_options_unchanged(s, "upload()"));
-  if (i < 0 || i >= (int)s->timesteps.size()) TSD_FAIL(TSD_E_ARG, "session: step %d out of range", i);
-  tsd_ctx* ctx = s->ctx;
-  const int B = s->B, Bu = s->cfg ? 2 * B : B;
-  const int64_t chw = (int64_t)4 * s->LH * s->LW, nl = B * chw;
-  const bool hist_valid = s->hist_valid_for == i;
+  STEP_IN_RANGE(s, i);
+  const bool had_hist = s->hist_valid_for == i;
   session_latents_changed(s);  // no valid history until this step's update is enqueued
   TSD_TRY(session_refresh(s));
   // time embedding on the device (get_time_embedding, pipeline.mojo:89): same t for every sample
-  if (!s->hoist) TSD_TRY(launch_time_embedding(ctx, nullptr, (float)s->timesteps[i], Bu, s->temb));
+  if (!s->hoist) TSD_TRY(launch_time_embedding(s->ctx, nullptr, (float)s->timesteps[i], s->Bu, s->temb));
   const UNetPre pre = s->hoist ? session_pre(s, i) : UNetPre();
   int eps_hw = 0;
   TSD_TRY(session_forward(s, &pre, &eps_hw));
-  SlotEntry p;
-  TSD_TRY(session_plan(s, i, hist_valid, &p));
-  // guidance rescale: every sample's cond and uncond eps scaled in place by its g before the update reads them (two launches)
-  if (s->rescale > 0.f) {
-    CfgRescaleTable gr = {};
-    for (int b = 0; b < B; b++) gr.e[b] = {1, s->cfg_scale, s->rescale, 0};
-    TSD_TRY(launch_cfg_rescale(ctx, s->eps, s->eps + nl, gr, B, chw, s->gr_part, nullptr));
-  }
-  // the update launch of the plan: its noise read from the uploaded tensor, drawn in the kernel (one source of noise per upload:
-  // has_noise is off under seeds) or absent; only DPM-Solver++(2M) reads or keeps the history, and it takes no noise
-  const float* eps_u = s->cfg ? s->eps + nl : nullptr;
-  const bool noisy = (p.flags & SLOT_NOISE) != 0, draws = noisy && s->seeded;
-  const float* nz = (noisy && s->has_noise) ? s->noise + (size_t)i * nl : nullptr;
-  const float* hist_in = (p.flags & SLOT_HIST_IN) ? s->hist : nullptr;
-  float* hist_out = (p.flags & SLOT_HIST_OUT) ? s->hist : nullptr;
-  const NormalBases nb = draws ? session_bases(s, NOISE_STREAM_STEP0 + (uint64_t)i) : NormalBases();
-  const float* c = p.c;
-  const SamplerCoeffs sc = {c[0], c[1], c[2], c[3], c[4], c[5]};
-  if (s->prediction == TSD_PRED_V && draws)  // a v plan is SLOT_LMS for every sampler: the v twins of the two launches below
-    TSD_TRY(launch_sampler_step_v_seeded(ctx, s->latents, s->eps, eps_u, s->cfg_scale, hist_in, nb, chw, nl, sc, eps_hw, s->latents, hist_out));
-  else if (s->prediction == TSD_PRED_V)
-    TSD_TRY(launch_sampler_step_v(ctx, s->latents, s->eps, eps_u, s->cfg_scale, hist_in, nz, nl, sc, eps_hw, s->latents, hist_out));
-  else if (p.mode == SLOT_DDPM && draws)
-    TSD_TRY(launch_ddpm_step_seeded(ctx, s->latents, s->eps, eps_u, s->cfg_scale, nb, chw, nl, c[0], c[1], c[2], c[3], c[4], eps_hw));
-  else if (p.mode == SLOT_DDPM)
-    TSD_TRY(launch_ddpm_step(ctx, s->latents, s->eps, eps_u, s->cfg_scale, nz, nl, c[0], c[1], c[2], c[3], c[4], eps_hw));
-  else if (draws)
-    TSD_TRY(launch_sampler_step_seeded(ctx, s->latents, s->eps, eps_u, s->cfg_scale, hist_in, nb, chw, nl, sc, eps_hw, s->latents, hist_out));
-  else
-    TSD_TRY(launch_sampler_step(ctx, s->latents, s->eps, eps_u, s->cfg_scale, hist_in, nz, nl, sc, eps_hw, s->latents, hist_out));
-  if (s->inpaint) TSD_TRY(session_inpaint_blend(s, i));  // a failed step leaves no valid history
-  if (hist_out) s->hist_valid_for = i + 1;  // the blend changed the latents, not the prediction the next step extrapolates from
+  int idx[16];
+  bool hist_valid[16];
+  std::fill(idx, idx + 16, i);  // an advance with every sample at index i, under the lockstep history rule
+  std::fill(hist_valid, hist_valid + 16, had_hist);
+  StepTables t;
+  TSD_TRY(session_step_tables(s, idx, hist_valid, &t));
+  TSD_TRY(session_update(s, t, eps_hw, i));  // a failed step leaves no valid history
+  // the blend changed the latents, not the prediction the next step extrapolates from
+  if (t.tab.e[0].flags & SLOT_HIST_OUT) s->hist_valid_for = i + 1;
   return TSD_OK;
 }
 
 extern "C" int tsd_session_add_noise(tsd_session* s, int i, const float* noise) {
   NOTNULL(s); NOTNULL(noise);
   SESSION_NOT_SLOTS(s, "add_noise()");
-  if (i < 0 || i >= (int)s->timesteps.size()) TSD_FAIL(TSD_E_ARG, "session: step %d out of range", i);
+  STEP_IN_RANGE(s, i);
   tsd_ctx* ctx = s->ctx;
   const size_t nl = (size_t)s->B * 4 * s->LH * s->LW;
   TSD_TRY(ctx_reserve_staging(ctx, nl * 4));
@@ -562,7 +601,7 @@ extern "C" int tsd_session_set_seeds(tsd_session* s, const uint64_t* seeds) {
   if (!s->uploaded) TSD_FAIL(TSD_E_STATE, "session: upload() before set_seeds() (the seeds belong to one upload)");
   if (seeds && s->has_noise) TSD_FAIL(TSD_E_STATE, "session: this upload() carried a noise tensor; one source of noise per upload");
   s->seeded = seeds != nullptr;
-  if (seeds) memcpy(s->seeds, seeds, (size_t)s->B * sizeof(uint64_t));
+  for (int b = 0; seeds && b < s->B; b++) s->slot[b].seed = seeds[b];
   session_latents_changed(s);  // as after add_noise()
   return TSD_OK;
 }
@@ -579,12 +618,12 @@ extern "C" int tsd_session_set_guidance_rescale(tsd_session* s, float phi) {
   if (!s->uploaded) TSD_FAIL(TSD_E_STATE, "session: upload() before set_guidance_rescale() (it belongs to one upload)");
   if (!s->cfg) TSD_FAIL(TSD_E_STATE, "session: guidance rescale needs a session created with cfg != 0");
   TSD_TRY(rescale_phi_ok(phi));
-  s->rescale = phi;
+  for (int b = 0; b < s->B; b++) s->slot[b].rescale = phi;
   return TSD_OK;
 }
 extern "C" int tsd_session_guidance_rescale(tsd_session* s, float* phi) {
   NOTNULL(s); NOTNULL(phi);
-  *phi = s->uploaded ? s->rescale : 0.f;
+  *phi = s->uploaded ? s->slot[0].rescale : 0.f;
   return TSD_OK;
 }
 
@@ -604,7 +643,7 @@ extern "C" int tsd_session_add_noise_seeded(tsd_session* s, int i) {
   NOTNULL(s);
   SESSION_NOT_SLOTS(s, "add_noise_seeded()");
   if (!s->uploaded || !s->seeded) TSD_FAIL(TSD_E_STATE, "session: upload() and set_seeds() before add_noise_seeded()");
-  if (i < 0 || i >= (int)s->timesteps.size()) TSD_FAIL(TSD_E_ARG, "session: step %d out of range", i);
+  STEP_IN_RANGE(s, i);
   tsd_ctx* ctx = s->ctx;
   HIP_TRY(hipSetDevice(ctx->device));
   const int64_t chw = (int64_t)4 * s->LH * s->LW, nl = s->B * chw;
@@ -616,28 +655,38 @@ extern "C" int tsd_session_add_noise_seeded(tsd_session* s, int i) {
   return TSD_OK;
 }
 
+// An inpainting request for samples [first, first + n) of ip_mask / ip_known / ip_noise: checked as a whole - the mask finite and in
+// [0, 1], the known latents and the optional noise finite - before the first copy, so a refused call leaves the previous mask, tensors and
+// history as they were; then copied, ip_noise from `noise` or drawn from `draw` (base k for sample first + k) or left alone.  Synchronises:
+// the host tensors are the caller's again on return.  `who` names the entry point in the message.
+static int session_put_inpaint(tsd_session* s, int first, int n, const float* mask, const float* known, const float* noise,
+                               const NormalBases* draw, const char* who) {
+  tsd_ctx* ctx = s->ctx;
+  const size_t hw = (size_t)s->LH * s->LW, nm = n * hw, nl = 4 * nm, m0 = first * hw, l0 = 4 * m0;
+  bool in_range = true;
+  for (size_t k = 0; k < nm; k++) in_range &= (mask[k] >= 0.f) & (mask[k] <= 1.f);  // false for NaN
+  if (!in_range) TSD_FAIL(TSD_E_ARG, "session: every inpainting mask value must be finite and in [0, 1]");
+  if (!host_all_finite(known, nl)) TSD_FAIL(TSD_E_ARG, "session: inf / NaN in the known latents of %s", who);
+  if (noise && !host_all_finite(noise, nl)) TSD_FAIL(TSD_E_ARG, "session: inf / NaN in the noise of %s", who);
+  HIP_TRY(hipSetDevice(ctx->device));
+  HIP_TRY(hipMemcpyAsync(s->ip_mask + m0, mask, nm * 4, hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(s->ip_known + l0, known, nl * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (noise) HIP_TRY(hipMemcpyAsync(s->ip_noise + l0, noise, nl * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (draw) TSD_TRY(launch_fill_normal(ctx, s->ip_noise + l0, (int64_t)nl, (int64_t)(4 * hw), *draw, 0));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return TSD_OK;
+}
 // set_inpaint and set_inpaint_seeded: `seeded` fills ip_noise with stream 4 of each sample's seed on the device instead of copying `noise`
 static int session_set_inpaint(tsd_session* s, const float* mask, const float* known, const float* noise, bool seeded) {
   SESSION_NOT_SLOTS(s, "set_inpaint()");
   if (!s->uploaded) TSD_FAIL(TSD_E_STATE, "session: upload() before set_inpaint() (inpainting belongs to one upload)");
   if (seeded && mask && !s->seeded) TSD_FAIL(TSD_E_STATE, "session: set_seeds() before set_inpaint_seeded()");
-  tsd_ctx* ctx = s->ctx;
-  const size_t hw = (size_t)s->LH * s->LW, nm = (size_t)s->B * hw, nl = 4 * nm;
-  if (mask) {  // every refusal comes before the first copy: a refused call leaves the previous mask, tensors and history as they were
+  if (mask) {
     NOTNULL(known);
-    bool in_range = true;
-    for (size_t k = 0; k < nm; k++) in_range &= (mask[k] >= 0.f) & (mask[k] <= 1.f);  // false for NaN
-    if (!in_range) TSD_FAIL(TSD_E_ARG, "session: every inpainting mask value must be finite and in [0, 1]");
-    if (!host_all_finite(known, nl)) TSD_FAIL(TSD_E_ARG, "session: inf / NaN in the known latents of set_inpaint()");
-    if (noise && !host_all_finite(noise, nl)) TSD_FAIL(TSD_E_ARG, "session: inf / NaN in the noise of set_inpaint()");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipMemcpyAsync(s->ip_mask, mask, nm * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(s->ip_known, known, nl * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (noise) HIP_TRY(hipMemcpyAsync(s->ip_noise, noise, nl * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (seeded) TSD_TRY(launch_fill_normal(ctx, s->ip_noise, (int64_t)nl, (int64_t)(4 * hw), session_bases(s, NOISE_STREAM_ADD), 0));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));  // the host tensors are the caller's again on return
+    const NormalBases nb = session_bases(s, NOISE_STREAM_ADD);
+    TSD_TRY(session_put_inpaint(s, 0, s->B, mask, known, noise, seeded ? &nb : nullptr, "set_inpaint()"));
   }
-  s->inpaint = mask != nullptr;
+  for (int b = 0; b < s->B; b++) s->slot[b].inpaint = mask != nullptr;
   s->ip_has_noise = mask && (noise || seeded);
   session_latents_changed(s);  // the steps that follow run on other latents than the history was predicted for: as after add_noise()
   return TSD_OK;
@@ -650,7 +699,7 @@ extern "C" int tsd_session_set_inpaint_seeded(tsd_session* s, const float* mask,
   NOTNULL(s);
   return session_set_inpaint(s, mask, known, nullptr, true);
 }
-extern "C" int tsd_session_inpaint_active(tsd_session* s) { return s ? (s->uploaded && s->inpaint ? 1 : 0) : TSD_E_ARG; }
+extern "C" int tsd_session_inpaint_active(tsd_session* s) { return s ? (s->uploaded && s->slot[0].inpaint ? 1 : 0) : TSD_E_ARG; }
 
 extern "C" int tsd_session_decode(tsd_session* s) {
   NOTNULL(s);
@@ -700,13 +749,13 @@ extern "C" int tsd_session_download_images(tsd_session* s, int rescale_0_255, fl
 // Every sample of the session is a slot with its own request (context, seed, guidance scale) and its own index into the session's
 // timestep list.  advance() runs ONE forward over all Bu samples and one update launch whose per-sample table gives each active slot
 // the step of its own index; a finished slot is refilled by slot_start while the others keep going.  What the lockstep step() passes
-// as scalars for the whole batch is the same plan (session_plan) taken per slot, and applied by the same per-element functions
+// as scalars for the whole batch is the same plan (entry 0 of the tables session_step_tables fills for both), and applied by the same per-element functions
 // (update_element.h): a slot's latents are bit for bit those of a lockstep session of the same batch shape running its request.
 extern "C" int tsd_session_slots_open(tsd_session* s) {
   NOTNULL(s);
   tsd_ctx* ctx = s->ctx;
   HIP_TRY(hipSetDevice(ctx->device));
-  const int B = s->B, Bu = s->cfg ? 2 * B : B;
+  const int B = s->B, Bu = s->Bu;
   s->slots = false;
   s->has_noise = false;
   // idle slots ride through every forward: zero latents and a zero context keep them finite
@@ -715,9 +764,9 @@ extern "C" int tsd_session_slots_open(tsd_session* s) {
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   if (ctx->opt.session_hoist)  // the per-sample time rows of an advance: sized by the session's shape alone
     TSD_TRY(session_grow((void**)&s->trows, &s->trows_cap, (size_t)Bu * s->unet->unet.tproj.N * 4, "time rows"));
-  TSD_TRY(session_prepare(s));  // the planning pass and the hoist buffers of upload(); K / V^T of the zero context, the whole time table
-  s->uploaded = false;          // the lockstep entry points stay closed
-  for (int b = 0; b < 16; b++) s->slot[b] = tsd_session::Slot();
+  // the planning pass and the hoist buffers of upload(), K / V^T of the zero context, the whole time table; every slot idle, no request
+  TSD_TRY(session_prepare(s));
+  s->uploaded = false;  // the lockstep entry points stay closed
   s->slots = true;
   return TSD_OK;
 }
@@ -731,7 +780,7 @@ extern "C" int tsd_session_slot_start(tsd_session* s, int b, const float* contex
   const int B = s->B, T = s->T, Tp = s->Tp;
   const size_t chw = (size_t)4 * s->LH * s->LW, nc = (size_t)T * 768;
   // every refusal comes before the first copy: a refused call leaves the slot, and everyone else's, as it was
-  if (b < 0 || b >= B) TSD_FAIL(TSD_E_ARG, "session: slot %d out of range (0..%d)", b, B - 1);
+  SLOT_IN_RANGE(s, b);
   if (start_index < 0 || start_index >= (int)s->timesteps.size())
     TSD_FAIL(TSD_E_ARG, "session: start index %d out of range (0..%d)", start_index, (int)s->timesteps.size() - 1);
   if (s->cfg && !uncond_context) TSD_FAIL(TSD_E_ARG, "session: a slot of a CFG session needs uncond_context");
@@ -742,9 +791,7 @@ extern "C" int tsd_session_slot_start(tsd_session* s, int b, const float* contex
   HIP_TRY(hipSetDevice(ctx->device));
   TSD_TRY(ctx_reserve_staging(ctx, std::max(nc, chw) * 4));
   tsd_session::Slot& sl = s->slot[b];
-  sl.state = 0;  // until the request is in place
-  sl.inpaint = false;  // a refilled slot never inherits the previous request's mask
-  sl.rescale = 0.f;    // nor its guidance rescale
+  session_reset_requests(s, b, 1);  // idle until the request is in place; a refilled slot inherits no mask, rescale or history
   // context rows b and B + b: upload()'s conversion, one sample
   for (int part = 0; part < (s->cfg ? 2 : 1); part++)
     TSD_TRY(session_put_context(s, part == 0 ? context : uncond_context, (size_t)part * B + b, 1));
@@ -775,7 +822,6 @@ extern "C" int tsd_session_slot_start(tsd_session* s, int b, const float* contex
   }
   HIP_TRY(hipStreamSynchronize(ctx->stream));  // the host tensors and the staging buffer are free again on return
   sl.index = start_index; sl.cfg_scale = cfg_scale; sl.seed = seed;
-  sl.hist_valid = false;
   sl.state = 1;
   return TSD_OK;
 }
@@ -787,24 +833,14 @@ extern "C" int tsd_session_slot_start(tsd_session* s, int b, const float* contex
 extern "C" int tsd_session_slot_set_inpaint(tsd_session* s, int b, const float* mask, const float* known) {
   NOTNULL(s);
   SESSION_IN_SLOTS(s);
-  if (b < 0 || b >= s->B) TSD_FAIL(TSD_E_ARG, "session: slot %d out of range (0..%d)", b, s->B - 1);
+  SLOT_IN_RANGE(s, b);
+  SLOT_IS_ACTIVE(s, b, "slot_set_inpaint()");
   tsd_session::Slot& sl = s->slot[b];
-  if (sl.state != 1) TSD_FAIL(TSD_E_STATE, "session: slot %d is %s; slot_set_inpaint() belongs to an active request", b, sl.state ? "done" : "idle");
-  tsd_ctx* ctx = s->ctx;
-  const size_t hw = (size_t)s->LH * s->LW, chw = 4 * hw;
   if (mask) {
     NOTNULL(known);
-    bool in_range = true;
-    for (size_t k = 0; k < hw; k++) in_range &= (mask[k] >= 0.f) & (mask[k] <= 1.f);  // false for NaN
-    if (!in_range) TSD_FAIL(TSD_E_ARG, "session: every inpainting mask value must be finite and in [0, 1]");
-    if (!host_all_finite(known, chw)) TSD_FAIL(TSD_E_ARG, "session: inf / NaN in the known latents of slot_set_inpaint()");
-    HIP_TRY(hipSetDevice(ctx->device));
-    HIP_TRY(hipMemcpyAsync(s->ip_mask + (size_t)b * hw, mask, hw * 4, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(s->ip_known + (size_t)b * chw, known, chw * 4, hipMemcpyHostToDevice, ctx->stream));
     NormalBases nb = {};
     nb.base[0] = counter_rng_base(sl.seed, NOISE_STREAM_ADD);
-    TSD_TRY(launch_fill_normal(ctx, s->ip_noise + (size_t)b * chw, (int64_t)chw, (int64_t)chw, nb, 0));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));  // the host tensors are the caller's again on return
+    TSD_TRY(session_put_inpaint(s, b, 1, mask, known, nullptr, &nb, "slot_set_inpaint()"));
   }
   sl.inpaint = mask != nullptr;
   sl.hist_valid = false;  // the steps that follow run on other latents than the history was predicted for
@@ -813,7 +849,7 @@ extern "C" int tsd_session_slot_set_inpaint(tsd_session* s, int b, const float* 
 extern "C" int tsd_session_slot_inpaint_active(tsd_session* s, int b) {
   NOTNULL(s);
   SESSION_IN_SLOTS(s);
-  if (b < 0 || b >= s->B) TSD_FAIL(TSD_E_ARG, "session: slot %d out of range (0..%d)", b, s->B - 1);
+  SLOT_IN_RANGE(s, b);
   return s->slot[b].state == 1 && s->slot[b].inpaint ? 1 : 0;
 }
 
@@ -822,28 +858,19 @@ extern "C" int tsd_session_slot_inpaint_active(tsd_session* s, int b) {
 extern "C" int tsd_session_slot_set_guidance_rescale(tsd_session* s, int b, float phi) {
   NOTNULL(s);
   SESSION_IN_SLOTS(s);
-  if (b < 0 || b >= s->B) TSD_FAIL(TSD_E_ARG, "session: slot %d out of range (0..%d)", b, s->B - 1);
-  tsd_session::Slot& sl = s->slot[b];
-  if (sl.state != 1)
-    TSD_FAIL(TSD_E_STATE, "session: slot %d is %s; slot_set_guidance_rescale() belongs to an active request", b, sl.state ? "done" : "idle");
+  SLOT_IN_RANGE(s, b);
+  SLOT_IS_ACTIVE(s, b, "slot_set_guidance_rescale()");
   if (!s->cfg) TSD_FAIL(TSD_E_STATE, "session: guidance rescale needs a session created with cfg != 0");
   TSD_TRY(rescale_phi_ok(phi));
-  sl.rescale = phi;
+  s->slot[b].rescale = phi;
   return TSD_OK;
 }
 extern "C" int tsd_session_slot_guidance_rescale(tsd_session* s, int b, float* phi) {
   NOTNULL(s); NOTNULL(phi);
   SESSION_IN_SLOTS(s);
-  if (b < 0 || b >= s->B) TSD_FAIL(TSD_E_ARG, "session: slot %d out of range (0..%d)", b, s->B - 1);
+  SLOT_IN_RANGE(s, b);
   *phi = s->slot[b].state == 1 ? s->slot[b].rescale : 0.f;
   return TSD_OK;
-}
-
-// Entry b of the update table for an active slot at index i: the plan of step i, plus the slot's guidance scale and the base of its noise
-static int slot_entry(const tsd_session* s, const tsd_session::Slot& sl, SlotEntry* e, uint64_t* base) {
-  e->cfg_scale = sl.cfg_scale;
-  *base = counter_rng_base(sl.seed, NOISE_STREAM_STEP0 + (uint64_t)sl.index);
-  return session_plan(s, sl.index, sl.hist_valid, e);
 }
 
 extern "C" int tsd_session_advance(tsd_session* s, uint32_t* finished_mask) {
@@ -852,70 +879,40 @@ extern "C" int tsd_session_advance(tsd_session* s, uint32_t* finished_mask) {
   SESSION_NOT_POISONED(s);
   TSD_TRY(session_options_unchanged(s, "slots_open()"));
   tsd_ctx* ctx = s->ctx;
-  const int B = s->B, Bu = s->cfg ? 2 * B : B, n = (int)s->timesteps.size();
-  const int64_t chw = (int64_t)4 * s->LH * s->LW;
-  const size_t nl = (size_t)B * chw;
-  int active = 0;
-  for (int b = 0; b < B; b++) active += s->slot[b].state == 1;
-  if (!active) TSD_FAIL(TSD_E_STATE, "session: advance() with no active slot");
+  const int B = s->B, Bu = s->Bu, n = (int)s->timesteps.size();
+  if (!tsd_session_slots_active(s)) TSD_FAIL(TSD_E_STATE, "session: advance() with no active slot");
+  int idx[16];  // each slot's own index; an idle or finished slot is inactive
+  bool hist_valid[16];
+  for (int b = 0; b < B; b++) {
+    idx[b] = s->slot[b].state == 1 ? s->slot[b].index : -1;
+    hist_valid[b] = s->slot[b].hist_valid;
+  }
   TSD_TRY(session_refresh(s));
-  // the update table, built before anything is enqueued: the per-slot scalars travel as kernel arguments
-  SlotTable tab = {};
-  for (int b = 0; b < B; b++)
-    if (s->slot[b].state == 1) TSD_TRY(slot_entry(s, s->slot[b], &tab.e[b], &tab.bases.base[b]));
-  // the blend table: an inpainting slot holds its known region at the timestep ITS update reaches (session_blend_scalars at its index)
-  SlotBlendTable blend = {};
-  bool blending = false;
-  for (int b = 0; b < B; b++) {
-    const tsd_session::Slot& sl = s->slot[b];
-    if (sl.state != 1 || !sl.inpaint) continue;
-    blend.e[b].on = 1;
-    session_blend_scalars(s, sl.index, &blend.e[b].a_prev, &blend.e[b].s_prev);
-    blending = true;
-  }
-  // the guidance-rescale table: an active slot with phi > 0 is `on`; everyone else is neither read nor written by its launches
-  CfgRescaleTable gr = {};
-  bool rescaling = false;
-  for (int b = 0; b < B; b++) {
-    const tsd_session::Slot& sl = s->slot[b];
-    if (sl.state != 1 || !(sl.rescale > 0.f)) continue;
-    gr.e[b] = {1, sl.cfg_scale, sl.rescale, 0};
-    rescaling = true;
-  }
+  // the tables, built before anything is enqueued: the per-slot scalars travel as kernel arguments
+  StepTables t;
+  TSD_TRY(session_step_tables(s, idx, hist_valid, &t));
   // per-sample time rows (cond and uncond halves alike); an idle or finished slot reads entry 0
   UNetPre pre;
   if (s->hoist) {
     SlotRows rows = {};
-    for (int b = 0; b < Bu; b++) rows.row[b] = s->slot[b % B].state == 1 ? s->slot[b % B].index : 0;
+    for (int b = 0; b < Bu; b++) rows.row[b] = std::max(idx[b % B], 0);
     const int N = s->unet->unet.tproj.N;
     TSD_TRY(launch_slot_time_rows(ctx, s->ttab, N, rows, Bu, s->trows));
     pre.tvec = s->trows; pre.tld = N; pre.kc_all = s->kc_all; pre.vtc_all = s->vtc_all;
   } else {
     SlotTimes ts = {};
-    for (int b = 0; b < Bu; b++) ts.t[b] = (float)s->timesteps[s->slot[b % B].state == 1 ? s->slot[b % B].index : 0];
+    for (int b = 0; b < Bu; b++) ts.t[b] = (float)s->timesteps[std::max(idx[b % B], 0)];
     TSD_TRY(launch_slot_timesteps(ctx, ts, Bu, s->tdev));
     TSD_TRY(launch_time_embedding(ctx, s->tdev, 0.f, Bu, s->temb));
   }
   int eps_hw = 0;
   TSD_TRY(session_forward(s, &pre, &eps_hw));
-  // the update launch: with an inpainting slot among the active ones, the kernel that also blends (no further launch either way)
-  const float* eps_u = s->cfg ? s->eps + nl : nullptr;
-  if (rescaling) TSD_TRY(launch_cfg_rescale(ctx, s->eps, s->eps + nl, gr, B, chw, s->gr_part, nullptr));
-  if (s->prediction == TSD_PRED_V && blending)  // the prediction type belongs to the launch: all slots share the model
-    TSD_TRY(launch_slot_update_blend_v(ctx, s->latents, s->eps, eps_u, s->hist, tab, blend, s->ip_mask, s->ip_known, s->ip_noise, B,
-                                       chw, eps_hw));
-  else if (s->prediction == TSD_PRED_V)
-    TSD_TRY(launch_slot_update_v(ctx, s->latents, s->eps, eps_u, s->hist, tab, B, chw, eps_hw));
-  else if (blending)
-    TSD_TRY(launch_slot_update_blend(ctx, s->latents, s->eps, eps_u, s->hist, tab, blend, s->ip_mask, s->ip_known, s->ip_noise, B,
-                                     chw, eps_hw));
-  else
-    TSD_TRY(launch_slot_update(ctx, s->latents, s->eps, eps_u, s->hist, tab, B, chw, eps_hw));
+  TSD_TRY(session_update(s, t, eps_hw, -1));
   uint32_t done = 0;
   for (int b = 0; b < B; b++) {
     tsd_session::Slot& sl = s->slot[b];
     if (sl.state != 1) continue;
-    sl.hist_valid = (tab.e[b].flags & SLOT_HIST_OUT) != 0;
+    sl.hist_valid = (t.tab.e[b].flags & SLOT_HIST_OUT) != 0;
     if (++sl.index >= n) { sl.state = 2; done |= 1u << b; }
   }
   if (finished_mask) *finished_mask = done;
@@ -925,7 +922,7 @@ extern "C" int tsd_session_advance(tsd_session* s, uint32_t* finished_mask) {
 extern "C" int tsd_session_slot_state(tsd_session* s, int b, int* index, int* state) {
   NOTNULL(s);
   SESSION_IN_SLOTS(s);
-  if (b < 0 || b >= s->B) TSD_FAIL(TSD_E_ARG, "session: slot %d out of range (0..%d)", b, s->B - 1);
+  SLOT_IN_RANGE(s, b);
   if (index) *index = s->slot[b].index;
   if (state) *state = s->slot[b].state;
   return TSD_OK;
@@ -934,7 +931,7 @@ extern "C" int tsd_session_slot_state(tsd_session* s, int b, int* index, int* st
 extern "C" int tsd_session_slot_download(tsd_session* s, int b, float* latents) {
   NOTNULL(s); NOTNULL(latents);
   SESSION_IN_SLOTS(s);
-  if (b < 0 || b >= s->B) TSD_FAIL(TSD_E_ARG, "session: slot %d out of range (0..%d)", b, s->B - 1);
+  SLOT_IN_RANGE(s, b);
   if (s->slot[b].state == 0) TSD_FAIL(TSD_E_STATE, "session: slot %d is idle (no request has defined its latents)", b);
   const size_t chw = (size_t)4 * s->LH * s->LW;
   return session_fetch_latents(s, s->latents + (size_t)b * chw, chw, latents);  // download_latents()' check, on this slot's buffer alone

@@ -149,11 +149,16 @@ def test_a_mask_without_latents_is_refused_before_any_slot_is_touched(tsd_mod):
 
 
 def test_advance_makes_no_copy_from_the_host():
-    """The per-slot scalars of both update kernels travel as kernel arguments: the text of tsd_session_advance and of the slot launchers
-    names no host-to-device copy (the GPU test counts the launches; a copy is not a launch)."""
+    """The per-slot scalars of both update kernels travel as kernel arguments: the text of tsd_session_advance, of the two functions it
+    builds its tables and picks its update launch with, and of the slot launchers names no host-to-device copy (the GPU test counts the
+    launches; a copy is not a launch)."""
     src = open(os.path.join(ROOT, "stable-diffusion.mojo_amd", "csrc", "session.cpp")).read()
     m = re.search(r'extern "C" int tsd_session_advance\(.*?\n}\n', src, re.S)
-    assert m and "launch_slot_update_blend" in m.group(0) and "launch_slot_update(" in m.group(0)
-    assert "HostToDevice" not in m.group(0) and "hipMemcpy(" not in m.group(0)
+    tables = re.search(r'static int session_step_tables\(.*?\n}\n', src, re.S)
+    update = re.search(r'static int session_update\(.*?\n}\n', src, re.S)
+    assert m and tables and update and "session_step_tables(" in m.group(0) and "session_update(" in m.group(0)
+    assert "launch_slot_update_blend" in update.group(0) and "launch_slot_update(" in update.group(0)
+    for text in (m.group(0), tables.group(0), update.group(0)):
+        assert "HostToDevice" not in text and "hipMemcpy(" not in text
     slots = open(os.path.join(ROOT, "stable-diffusion.mojo_amd", "csrc", "kernels_slots.hip")).read()
     assert "k_slot_update_blend" in slots and "hipMemcpy" not in slots
