@@ -188,7 +188,14 @@ int tsd_vae_attention_block_f32(tsd_ctx* ctx, const float* x, int C, int H, int 
  * norms - 32 groups in the residual blocks (the reference declares 16, vae.mojo:42-43), per-channel weight / bias of
  * every GroupNorm appended to the kind-2 / kind-3 list (`lN.group_norm1`, `lN.group_norm2`, `lN.group_norm`, and
  * `lN` for the stand-alone norm), eps inside the root: the layout of diffusers' AutoencoderKL decoder / encoder. */
-typedef enum tsd_model_kind { TSD_MODEL_DIFFUSION = 1, TSD_MODEL_DECODER = 2, TSD_MODEL_ENCODER = 3, TSD_MODEL_CLIP = 4, TSD_MODEL_DIFFUSION_SD15 = 5, TSD_MODEL_DIFFUSION_SD15_TORCH = 6, TSD_MODEL_CLIP_TORCH = 7, TSD_MODEL_DECODER_TORCH = 8, TSD_MODEL_ENCODER_TORCH = 9 } tsd_model_kind;
+typedef enum tsd_model_kind { TSD_MODEL_DIFFUSION = 1, TSD_MODEL_DECODER = 2, TSD_MODEL_ENCODER = 3, TSD_MODEL_CLIP = 4, TSD_MODEL_DIFFUSION_SD15 = 5, TSD_MODEL_DIFFUSION_SD15_TORCH = 6, TSD_MODEL_CLIP_TORCH = 7, TSD_MODEL_DECODER_TORCH = 8, TSD_MODEL_ENCODER_TORCH = 9, TSD_MODEL_CONTROLNET_SD15 = 10, TSD_MODEL_CONTROLNET_SD15_TORCH = 11 } tsd_model_kind;
+/* TSD_MODEL_CONTROLNET_SD15 (EXTENSION: Zhang et al. 2023; the layout of diffusers' ControlNetModel): the control network of the full-size
+ * UNet.  Parameters in this order: `time_embed.layer1/2`; the hint encoder `hint.conv1 .. hint.conv8` (3x3 convolutions 3->16, 16->16,
+ * 16->32 stride 2, 32->32, 32->96 stride 2, 96->96, 96->256 stride 2, 256->320; SiLU after each but the last, the last initialised to
+ * zero); `unet.layer1 .. unet.layer21`, the full-size UNet's 18 encoder and 3 bottleneck steps under the UNet's own names; the zero convolutions
+ * `zero.skip1 .. zero.skip12` (1x1, one per skip the encoder pushes: 320 x4, 640 x3, 1280 x5 channels) and `zero.mid` (1x1, 1280), all
+ * initialised to zero.  TSD_MODEL_CONTROLNET_SD15_TORCH: the same with the norm parameters of kind 6 appended last, so the shared
+ * indices equal kind 10's.  tsd_flop_count returns -1 for both and tsd_model_lora_add refuses them (TSD_E_ARG). */
 
 /* Parameter inventory in struct-field DFS order: `Diffusion`
  * diffusion.mojo:299-302, `Decoder` vae.mojo:194-219, `Encoder` vae.mojo:94-112.  No GPU needed. */
@@ -257,6 +264,48 @@ int tsd_encoder_forward(tsd_model* m, const float* images, const float* noise, i
 int tsd_diffusion_forward_hw(tsd_model* m, const float* latents, const float* context, const float* time_emb, int B,
                              int LH, int LW, int T, float* out);
 int tsd_decoder_forward_hw(tsd_model* m, const float* latents, int B, int LH, int LW, float* images);
+/* ---- ControlNet (EXTENSION): spatial conditioning of the full-size UNet ------------------------------------------------------------
+ * The control network `cn` (kinds 10 / 11) sees the UNet's inputs and a hint image, hint [B,3,8LH,8LW] fp32 with the values as given:
+ *     h = conv_in(latents) + hint_encoder(hint), then the UNet's encoder and bottleneck on the ControlNet's own weights;
+ *     r_i = zero_i(h_i) for the 12 tensors the encoder pushes as skips (i = 0..11, in push order) and the bottleneck output (i = 12).
+ * tsd_controlnet_forward_hw returns the 13 residuals as fp32 CHW, residuals_out[i] = [B,C_i,H_i,W_i] with (C_i, side) = (320, L) x3,
+ * (320, L/2), (640, L/2) x2, (640, L/4), (1280, L/4) x2, (1280, L/8) x4.
+ * tsd_diffusion_forward_control_hw is tsd_diffusion_forward_hw of `unet` (kinds 5 / 6) with skip_i + scale[b] * r_i in place of every
+ * skip and of the bottleneck output.  Both forwards run inside one plan of one context: the two models must belong to the same tsd_ctx
+ * (TSD_E_ARG otherwise, as for a `unet` that is not full-size or a `cn` that is no ControlNet).  On the device the residuals are fp16
+ * NHWC and the injection is ONE launch between the bottleneck and the first decoder block,
+ *     x = rn16(fmaf(scale[b], (float)r, (float)x))            fp32, one rounding to fp16, in place
+ * which also re-emits the GroupNorm statistics the producers of those tensors emitted, so no decoder block gains a statistics pass.  A
+ * sample whose scale is exactly 0 is neither read nor written by it: its output is the uncontrolled forward's.  Shapes as for
+ * tsd_diffusion_forward_hw (LH, LW multiples of 16), TSD_E_SHAPE otherwise. */
+int tsd_controlnet_forward_hw(tsd_model* cn, const float* latents, const float* context, const float* time_emb, const float* hint, int B,
+                              int LH, int LW, int T, float* const* residuals_out);
+int tsd_diffusion_forward_control_hw(tsd_model* unet, tsd_model* cn, const float* latents, const float* context, const float* time_emb,
+                                     const float* hint, const float* scale, int B, int LH, int LW, int T, float* eps_out);
+/* The hint encoder alone: hint [B,3,8LH,8LW] -> features_out fp32 [B,320,LH,LW].  It depends on the hint only. */
+int tsd_controlnet_hint_hw(tsd_model* cn, const float* hint, int B, int LH, int LW, float* features_out);
+/* ControlNet in a lockstep denoise session on a full-size UNet.  hint: host fp32 [B,3,8LH,8LW] (the session's B and sides; the entry
+ * takes no shape, so the caller owns it - the Python wrapper checks it); scale: one fp32 for every sample; cond_only != 0: under CFG the
+ * uncond half gets scale 0; control is applied on steps first_step <= i <= last_step (last_step < 0: to the end of the list).  cn == NULL
+ * turns control off.  Call after upload().  The hint encoder runs here, once, and its features stay on the device; the per-sample scale
+ * vector is built and uploaded here; the ControlNet's time projections and context K / V^T follow the session's hoist exactly as the
+ * UNet's do (built here and at every later upload() when it is on, per step when off).  A step inside the window runs the ControlNet
+ * forward at the UNet's batch (2B under CFG) on the step's latents, timestep and contexts and then the controlled UNet forward, with no
+ * copy from the host and no allocation; a step outside it, and every step after set_control(NULL), enqueues the launches and gives the
+ * bits of a session without control.  The control stays across upload()s until it is turned off.  Samplers, prediction types, seeds,
+ * inpainting and guidance rescale compose unchanged: only the forward differs.
+ * TSD_E_ARG: the session's UNet is not full-size, cn is no ControlNet or lives on another context, a scale that is not finite, a bad
+ * window.  TSD_E_STATE: before upload(); on a slot session; and tsd_session_slots_open on a session with control (per-slot control is
+ * not supported).  tsd_session_control_active: 1 while a ControlNet is set. */
+int tsd_session_set_control(tsd_session* s, tsd_model* cn, const float* hint, float scale, int cond_only, int first_step, int last_step);
+int tsd_session_control_active(tsd_session* s);
+/* Op level, host fp16 in/out, synchronous: the injection launch alone over a table of n <= 16 tensors.  x[i] / r[i] / y_out[i]: fp16 bits
+ * [B][HW[i]][C[i]] (C a multiple of 8, at most 2048); scale [B]; partial_out[i]: fp32 [B][nslab[i]][groups[i]][2], the (sum, sum of
+ * squares) of the rounded y over slab s = rows [s * ceil(HW / nslab), ...) and group g, summed in fp32 in a fixed order.  groups[i] == 0:
+ * no statistics for that entry (partial_out[i] is ignored; nslab[i] only cuts the work).  Here every sample is computed, a scale of 0
+ * included (y == x).  A sample's y and partials are the same bits run to run and in every batch position. */
+int tsd_control_inject_f16(tsd_ctx* ctx, int n, const void* const* x, const void* const* r, int B, const int* HW, const int* C,
+                           const int* groups, const int* nslab, const float* scale, void* const* y_out, float* const* partial_out);
 int tsd_encoder_forward_hw(tsd_model* m, const float* images, const float* noise, int B, int SH, int SW, float* latents);
 
 /* `CLIP.forward` clip.mojo:90-109 (the step before the hot path), intended semantics
@@ -873,6 +922,9 @@ int tsd_debug_set_qkv_fuse(tsd_ctx* ctx, int on);
  * after upload() makes the next step rebuild them.  on = 0: every step computes them again.  Like every tsd_debug_set_* call a
  * change asks the context's sessions for a new upload().  Environment: TSD_SESSION_HOIST.  Returns the previous setting. */
 int tsd_debug_set_session_hoist(tsd_ctx* ctx, int on);
+/* TSD_CONTROL_STATS (default 1): 0 makes the ControlNet injection discard the statistics of the tensors it rewrites, so every consumer
+ * runs its own statistics pass - the A/B of the statistics hand-over.  Returns the previous value. */
+int tsd_debug_set_control_stats(tsd_ctx* ctx, int on);
 /* info[6] of a session: [0] 1 when the steps of the current upload() read the hoisted buffers, [1] device address of the time table,
  * [2] of the context K and [3] V^T buffers, [4] bytes allocated for them, [5] times they have been built (uploads + rebuilds). */
 int tsd_debug_session_hoist_info(tsd_session* s, int64_t* info);

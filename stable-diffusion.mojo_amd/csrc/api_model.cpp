@@ -1,6 +1,7 @@
 // api_model.cpp - module-level forwards (device-resident weights) and the RCCL weight broadcast.  The device-resident denoise
 // session that runs the forwards step after step is session.cpp.
 #include <dlfcn.h>
+#include <math.h>
 #include <stdint.h>
 #include <string.h>
 
@@ -63,6 +64,113 @@ extern "C" int tsd_diffusion_forward_hw(tsd_model* m, const float* latents, cons
 extern "C" int tsd_diffusion_forward(tsd_model* m, const float* latents, const float* context, const float* time_emb,
                                      int B, int L, int T, float* out) {
   return tsd_diffusion_forward_hw(m, latents, context, time_emb, B, L, L, T, out);
+}
+
+// ---- ControlNet: the residuals alone, and the controlled UNet forward (both models on one context, one plan) --------------------------
+namespace {
+struct CnInputs {
+  float* dl = nullptr; float* dt = nullptr; half_t* c16 = nullptr; float* dh = nullptr;
+  int Tp = 0;
+};
+int cn_check(const tsd_model* cn, int B, int LH, int LW, int T) {
+  if (!is_controlnet_kind(cn->kind)) TSD_FAIL(TSD_E_ARG, "controlnet: model is not a ControlNet");
+  if (B <= 0 || B > 16 || LH <= 0 || LW <= 0 || T <= 0) TSD_FAIL(TSD_E_SHAPE, "controlnet: B=%d (1..16) L=%dx%d T=%d", B, LH, LW, T);
+  if (LH % 16 || LW % 16) TSD_FAIL(TSD_E_SHAPE, "controlnet: latent sides %d x %d must be multiples of 16", LH, LW);
+  return TSD_OK;
+}
+// latents, context (converted to padded fp16 rows), time embedding and hint onto the device
+int cn_upload(tsd_ctx* ctx, const float* latents, const float* context, const float* time_emb, const float* hint, int B, int LH, int LW, int T,
+              CnInputs* in) {
+  const int Tp = round_up(T, 8);
+  const int64_t nl = (int64_t)B * 4 * LH * LW, nh = (int64_t)B * 3 * 64 * LH * LW;
+  in->Tp = Tp;
+  in->dl = arena_alloc<float>(ctx, nl);
+  float* dc = arena_alloc<float>(ctx, (int64_t)B * T * 768);
+  in->dt = arena_alloc<float>(ctx, (int64_t)B * 320);
+  in->c16 = arena_alloc<half_t>(ctx, (int64_t)B * Tp * 768);
+  in->dh = arena_alloc<float>(ctx, nh);
+  if (!in->dl || !dc || !in->dt || !in->c16 || !in->dh) TSD_FAIL(TSD_E_ALLOC, "workspace arena exhausted");
+  TSD_TRY(h2d(ctx, in->dl, latents, nl * 4));
+  TSD_TRY(h2d(ctx, dc, context, (size_t)B * T * 768 * 4));
+  TSD_TRY(h2d(ctx, in->dt, time_emb, (size_t)B * 320 * 4));
+  TSD_TRY(h2d(ctx, in->dh, hint, nh * 4));
+  for (int b = 0; b < B; b++)  // [T][768] -> zero-padded [Tp][768] per sample
+    TSD_TRY(launch_f32_to_f16_rows(ctx, dc + (int64_t)b * T * 768, T, 768, in->c16 + (int64_t)b * Tp * 768, 768, Tp));
+  return TSD_OK;
+}
+}  // namespace
+
+extern "C" int tsd_controlnet_forward_hw(tsd_model* cn, const float* latents, const float* context, const float* time_emb, const float* hint,
+                                         int B, int LH, int LW, int T, float* const* residuals_out) {
+  NOTNULL(cn); NOTNULL(latents); NOTNULL(context); NOTNULL(time_emb); NOTNULL(hint); NOTNULL(residuals_out);
+  for (int k = 0; k < CONTROL_RESIDUALS; k++)
+    if (!residuals_out[k]) TSD_FAIL(TSD_E_ARG, "tsd_controlnet_forward_hw: residuals_out[%d] is NULL", k);
+  TSD_TRY(cn_check(cn, B, LH, LW, T));
+  tsd_ctx* ctx = cn->ctx;
+  return run_model(cn, [&]() -> int {
+    CnInputs in;
+    TSD_TRY(cn_upload(ctx, latents, context, time_emb, hint, B, LH, LW, T, &in));
+    Act hf;
+    TSD_TRY(g_controlnet_hint(cn, in.dh, B, LH, LW, &hf));
+    ControlRes res;
+    TSD_TRY(g_controlnet_forward(cn, in.dl, in.c16, T, in.Tp, in.dt, hf, B, LH, LW, nullptr, &res));
+    for (int k = 0; k < CONTROL_RESIDUALS; k++) {
+      const Act& r = res.r[k];
+      const int64_t n = r.pixels() * r.C;
+      float* d = arena_alloc<float>(ctx, n);
+      if (!d) TSD_FAIL(TSD_E_ALLOC, "workspace arena exhausted");
+      TSD_TRY(launch_nhwc_f16_to_chw_f32(ctx, r.p, B, r.C, r.H, r.W, r.ld, d));
+      TSD_TRY(d2h(ctx, residuals_out[k], d, n * 4));
+    }
+    return TSD_OK;
+  });
+}
+
+// the hint encoder alone: hint [B,3,8LH,8LW] -> features fp32 CHW [B,320,LH,LW] (what a session keeps across its steps)
+extern "C" int tsd_controlnet_hint_hw(tsd_model* cn, const float* hint, int B, int LH, int LW, float* features_out) {
+  NOTNULL(cn); NOTNULL(hint); NOTNULL(features_out);
+  TSD_TRY(cn_check(cn, B, LH, LW, 1));
+  tsd_ctx* ctx = cn->ctx;
+  return run_model(cn, [&]() -> int {
+    const int64_t nh = (int64_t)B * 3 * 64 * LH * LW, nf = (int64_t)B * 320 * LH * LW;
+    float* dh = arena_alloc<float>(ctx, nh);
+    float* df = arena_alloc<float>(ctx, nf);
+    if (!dh || !df) TSD_FAIL(TSD_E_ALLOC, "workspace arena exhausted");
+    TSD_TRY(h2d(ctx, dh, hint, nh * 4));
+    Act hf;
+    TSD_TRY(g_controlnet_hint(cn, dh, B, LH, LW, &hf));
+    TSD_TRY(launch_nhwc_f16_to_chw_f32(ctx, hf.p, B, 320, LH, LW, hf.ld, df));
+    return d2h(ctx, features_out, df, nf * 4);
+  });
+}
+
+extern "C" int tsd_diffusion_forward_control_hw(tsd_model* unet, tsd_model* cn, const float* latents, const float* context,
+                                                const float* time_emb, const float* hint, const float* scale, int B, int LH, int LW, int T,
+                                                float* eps_out) {
+  NOTNULL(unet); NOTNULL(cn); NOTNULL(latents); NOTNULL(context); NOTNULL(time_emb); NOTNULL(hint); NOTNULL(scale); NOTNULL(eps_out);
+  if (!is_full_unet_kind(unet->kind)) TSD_FAIL(TSD_E_ARG, "controlled forward: the UNet must be a full-size kind (the Tiny-SD graph has no ControlNet)");
+  TSD_TRY(cn_check(cn, B, LH, LW, T));
+  if (unet->ctx != cn->ctx) TSD_FAIL(TSD_E_ARG, "controlled forward: the UNet and the ControlNet belong to different contexts (the residuals live in one arena)");
+  for (int b = 0; b < B; b++)
+    if (!(fabsf(scale[b]) <= 3.4028235e38f)) TSD_FAIL(TSD_E_ARG, "controlled forward: scale[%d] is not finite", b);
+  tsd_ctx* ctx = unet->ctx;
+  HIP_TRY(hipSetDevice(ctx->device));
+  TSD_TRY(model_check_ready(cn));
+  return run_model(unet, [&]() -> int {
+    CnInputs in;
+    TSD_TRY(cn_upload(ctx, latents, context, time_emb, hint, B, LH, LW, T, &in));
+    const int64_t nl = (int64_t)B * 4 * LH * LW;
+    float* ds = arena_alloc<float>(ctx, B);
+    float* de = arena_alloc<float>(ctx, nl);
+    if (!ds || !de) TSD_FAIL(TSD_E_ALLOC, "workspace arena exhausted");
+    TSD_TRY(h2d(ctx, ds, scale, (size_t)B * 4));
+    Act hf;
+    TSD_TRY(g_controlnet_hint(cn, in.dh, B, LH, LW, &hf));
+    ControlRes res;
+    TSD_TRY(g_controlnet_forward(cn, in.dl, in.c16, T, in.Tp, in.dt, hf, B, LH, LW, nullptr, &res));
+    TSD_TRY(g_unet_forward(unet, in.dl, in.c16, T, in.Tp, in.dt, B, LH, LW, de, false, nullptr, &res, ds));
+    return d2h(ctx, eps_out, de, nl * 4);
+  });
 }
 
 extern "C" int tsd_decoder_forward_hw(tsd_model* m, const float* latents, int B, int LH, int LW, float* images) {

@@ -346,6 +346,43 @@ extern "C" int tsd_cfg_rescale_f32(tsd_ctx* ctx, const float* eps, const float* 
   });
 }
 
+// ControlNet injection (kernels_control.hip) on host fp16 tensors: the ONE launch a controlled UNet forward adds, over a table of n tensors.
+// x[i] / r[i] / y_out[i]: fp16 bits [B][HW[i]][C[i]]; partial_out[i]: fp32 [B][nslab[i]][groups[i]][2], ignored (may be NULL) for an entry
+// with groups[i] == 0 - that entry gets no statistics.  Every sample is computed, a scale of exactly 0 included.
+extern "C" int tsd_control_inject_f16(tsd_ctx* ctx, int n, const void* const* x, const void* const* r, int B, const int* HW, const int* C,
+                                      const int* groups, const int* nslab, const float* scale, void* const* y_out, float* const* partial_out) {
+  NOTNULL(ctx); NOTNULL(x); NOTNULL(r); NOTNULL(HW); NOTNULL(C); NOTNULL(groups); NOTNULL(nslab); NOTNULL(scale); NOTNULL(y_out);
+  if (n <= 0 || n > CONTROL_MAX_ENTRIES || B <= 0 || B > 16) TSD_FAIL(TSD_E_SHAPE, "control inject: %d entries (1..%d), B=%d (1..16)", n, CONTROL_MAX_ENTRIES, B);
+  for (int i = 0; i < n; i++) {
+    if (!x[i] || !r[i] || !y_out[i]) TSD_FAIL(TSD_E_ARG, "control inject: entry %d: x, r and y_out are required", i);
+    if (HW[i] <= 0 || C[i] <= 0 || groups[i] < 0 || nslab[i] <= 0) TSD_FAIL(TSD_E_SHAPE, "control inject: entry %d: HW=%d C=%d groups=%d nslab=%d", i, HW[i], C[i], groups[i], nslab[i]);
+    if (groups[i] > 0 && (!partial_out || !partial_out[i])) TSD_FAIL(TSD_E_ARG, "control inject: entry %d has groups but no partial_out", i);
+  }
+  return run_op(ctx, [&]() -> int {
+    Dev d{ctx};
+    ControlTable tab = {};
+    tab.n = n;
+    float* ds = d.in(scale, B);
+    float* dp[CONTROL_MAX_ENTRIES] = {};
+    for (int i = 0; i < n; i++) {
+      ControlEntry& e = tab.e[i];
+      const int64_t ne = (int64_t)B * HW[i] * C[i];
+      e.x = (half_t*)d.in((const uint16_t*)x[i], ne);
+      e.r = (const half_t*)d.in((const uint16_t*)r[i], ne);
+      if (groups[i] > 0) dp[i] = d.buf<float>((int64_t)B * nslab[i] * groups[i] * 2);
+      e.part = dp[i];
+      e.ldx = e.ldr = e.C = C[i]; e.HW = HW[i]; e.groups = groups[i]; e.nslab = nslab[i];
+    }
+    if (d.err) return d.err;
+    TSD_TRY(launch_control_inject(ctx, tab, B, ds));
+    for (int i = 0; i < n; i++) {
+      TSD_TRY(d.out((uint16_t*)y_out[i], (const uint16_t*)tab.e[i].x, (int64_t)B * HW[i] * C[i]));
+      if (dp[i]) TSD_TRY(d.out(partial_out[i], (const float*)dp[i], (int64_t)B * nslab[i] * groups[i] * 2));
+    }
+    return TSD_OK;
+  });
+}
+
 // N(0,1) of the counter RNG (kernels_sampler.hip k_fill_normal, counter_rng.h) on a host tensor: element e is value offset + e of the
 // stream (seed, stream) - the values a seeded denoise session draws on the device
 extern "C" int tsd_normal_fill_f32(tsd_ctx* ctx, uint64_t seed, uint64_t stream, uint64_t offset, int64_t n, float* out) {

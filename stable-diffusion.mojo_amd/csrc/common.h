@@ -62,6 +62,7 @@ struct TsdOptions {
   int fold_out = 1;        // TSD_FOLD_OUT: op-by-op attention blocks (C = 640 / 1280): GEGLU's second linear + the output 1x1 conv as one GEMM over [h | r]
   int ups_fold = 1;        // TSD_UPS_FOLD: conv1 of the residual blocks behind a nearest-2x upsample as four 2x2 parity convolutions on folded weights (ConvW::w_uf): K = 4 Cin instead of 9 Cin
   int fold_dup = 1;        // TSD_FOLD_DUP: layer 10's concat(x, x) folded into its conv1 / skip weights (UNetW::res_dup): a 1280 -> 1280 block instead of 2560 -> 1280
+  int control_stats = 1;   // TSD_CONTROL_STATS: the ControlNet injection re-emits the GroupNorm statistics of the tensors it rewrites (0: it discards them and every consumer runs its own statistics pass)
   int session_hoist = 1;   // TSD_SESSION_HOIST: a denoise session computes the time path of every schedule entry and the context K / V^T once per upload(), not once per step
   // derived weight copies (model.cpp; read when a model's derived buffers are built)
   int conv_w_tm_mib = 2, lin_w_tm = 1, lin_w_tm_kib = 1024;  // TSD_CONV_W_TM, TSD_LIN_W_TM, TSD_LIN_W_TM_KIB
@@ -488,6 +489,26 @@ int cfg_rescale_blocks(int64_t chw);  // G: partials (and blocks) per sample, a 
 // doubles of scratch; g_out [B] or nullptr, written for `on` entries only.  Two launches, no copy, no synchronisation.
 int launch_cfg_rescale(tsd_ctx* ctx, float* eps, float* eps_uncond, const CfgRescaleTable& tab, int B, int64_t chw, double* partial,
                        float* g_out);
+
+// ---- ControlNet injection (kernels_control.hip states the formula): x <- rn16(x + s_b r) in place on up to 16 NHWC fp16 tensors in ONE
+// launch, and the GroupNorm partials of the rounded result into each tensor's own table.  56 bytes per entry: 904 bytes of arguments.
+enum { CONTROL_MAX_ENTRIES = 16, CONTROL_RESIDUALS = 13 };  // a ControlNet gives 12 skip residuals and one for the bottleneck output
+struct ControlEntry {
+  half_t* x;        // [B][HW][ldx], written in place
+  const half_t* r;  // [B][HW][ldr]
+  float* part;      // [B][nslab][groups][2] (sum, sum of squares) per slab, or nullptr: no statistics for this tensor
+  int ldx, ldr, HW, C;
+  int groups, nslab;  // what the tensor's producer used; without statistics nslab only cuts the work (groups is ignored)
+  int blk0;           // first block of the entry: the prefix sum of nslab (launch_control_inject fills it)
+  int pad_;
+};
+struct ControlTable {
+  ControlEntry e[CONTROL_MAX_ENTRIES];
+  int n;
+  int skip_zero;  // 1: a sample whose scale is exactly 0 is neither read nor written - its tensor and its producer's statistics stand
+};
+// scale: device fp32 [B]
+int launch_control_inject(tsd_ctx* ctx, ControlTable tab, int B, const float* scale);
 
 // alphas_cumprod of the scaled-linear beta schedule (sampler.mojo:28-32), fp32 like the reference's Tensor
 void sampler_alphas_cumprod(int n_train, std::vector<float>& out);

@@ -483,16 +483,20 @@ int g_unet_ctx_kv(tsd_model* m, const half_t* ctx16, int Tp, int B, half_t* kc_a
 
 // ---- `Diffusion.forward` diffusion.mojo:309-318 -------------------------------------------------------
 static int g_unet_full_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, int T, int Tp,
-                               const float* temb, int B, int LH, int LW, float* eps_out_chw, bool eps_nhwc, const UNetPre* pre);
+                               const float* temb, int B, int LH, int LW, float* eps_out_chw, bool eps_nhwc, const UNetPre* pre,
+                               const ControlRes* control, const float* control_scale);
 
 int g_unet_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, int T, int Tp, const float* temb, int B,
-                   int LH, int LW, float* eps_out_chw, bool eps_nhwc, const UNetPre* pre) {
+                   int LH, int LW, float* eps_out_chw, bool eps_nhwc, const UNetPre* pre, const ControlRes* control,
+                   const float* control_scale) {
+  if (control && !control_scale) TSD_FAIL(TSD_E_ARG, "UNet: control residuals without per-sample scales");
   if (is_full_unet_kind(m->kind)) {
     const int prev = gemm_set_splitk_big(m->ctx, 4);  // measured for this graph at its batch of 4 (BASELINE configs[4]): +4.3 %
-    const int r = g_unet_full_forward(m, latents_chw, ctx16, T, Tp, temb, B, LH, LW, eps_out_chw, eps_nhwc, pre);
+    const int r = g_unet_full_forward(m, latents_chw, ctx16, T, Tp, temb, B, LH, LW, eps_out_chw, eps_nhwc, pre, control, control_scale);
     gemm_set_splitk_big(m->ctx, prev);
     return r;
   }
+  if (control) TSD_FAIL(TSD_E_ARG, "UNet: only the full-size kinds accept ControlNet residuals");
   tsd_ctx* ctx = m->ctx;
   const UNetW& u = m->unet;
   if (LH <= 0 || LW <= 0 || LH % 8 || LW % 8) TSD_FAIL(TSD_E_SHAPE, "UNet: latent sides %d x %d must be multiples of 8", LH, LW);
@@ -595,32 +599,27 @@ int g_unet_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, 
 // Full-size UNet (TSD_MODEL_DIFFUSION_SD15, BASELINE configs[4]): the same blocks driven by the SD15_STEPS table.
 // Encoders push their output; every decoder residual block reads concat(x, popped skip) through the two-source views;
 // Upsample + conv3x3 is one implicit-GEMM launch that reads its input through the nearest-2x addressing.
-static int g_unet_full_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, int T, int Tp,
-                               const float* temb, int B, int LH, int LW, float* eps_out_chw, bool eps_nhwc, const UNetPre* pre) {
+// What the steps of the table share: the model's weights, the time rows and the projected context.
+struct FullRun {
+  tsd_model* m = nullptr;
+  const half_t* ctx16 = nullptr; int T = 0, Tp = 0;
+  const float* tvec = nullptr; int tld = 0;
+  const half_t* kc_all = nullptr; const half_t* vtc_all = nullptr;
+  int B = 0, LH = 0, LW = 0;
+  bool in_im2col = false;
+  const Act* in_res = nullptr;  // added to the input convolution's output through its residual slot (the ControlNet's hint features)
+  // called with every tensor a step has pushed, in push order (the ControlNet's zero convolutions)
+  int (*on_push)(void* self, int k, const Act& a) = nullptr; void* self = nullptr;
+};
+
+// Steps [i0, i1) of SD15_STEPS on `cur` and the skip stack: the UNet runs [0, SD15_ENC_N) and [SD15_ENC_N, SD15_N), a ControlNet the first
+// range on weights of its own.
+static int unet_full_steps(const FullRun& f, int i0, int i1, Act& cur, std::vector<Act>& skips) {
+  tsd_model* m = f.m;
   tsd_ctx* ctx = m->ctx;
   const UNetW& u = m->unet;
-  if (LH <= 0 || LW <= 0 || LH % 16 || LW % 16) TSD_FAIL(TSD_E_SHAPE, "full-size UNet: latent sides %d x %d must be multiples of 16", LH, LW);
-  const float* tvec = pre ? pre->tvec : nullptr;
-  const int tld = pre ? pre->tld : u.tproj.N;
-  if (!pre) TSD_TRY(g_unet_time_path(m, temb, B, &tvec));
-  const bool in_im2col = ctx->opt.conv_in_im2col && u.conv_in_im2col && !u.conv.empty() && u.conv[0].I == 4 && SD15_STEPS[0].l.kind == L_CONV &&
-                         SD15_STEPS[0].l.d == 1;  // as in g_unet_forward: the 4-channel input convolution as one im2col K tile
-  Act x0 = act_alloc(ctx, B, LH, LW, 64); CHECK_ALLOC(x0.p);
-  if (in_im2col) TSD_TRY(launch_chw_f32_to_im2col3x3_f16(ctx, latents_chw, B, 4, LH, LW, x0.p));
-  else TSD_TRY(launch_chw_f32_to_nhwc_f16(ctx, latents_chw, B, 4, LH, LW, 4, 1.f, x0.p, 64));
-  // context K and V^T of all sixteen attention blocks in two GEMMs
-  const int CK = u.kproj_all.N;
-  const half_t* kc_all = pre ? pre->kc_all : nullptr;
-  const half_t* vtc_all = pre ? pre->vtc_all : nullptr;
-  if (!pre) {
-    half_t* kc = arena_alloc<half_t>(ctx, (int64_t)B * Tp * CK); CHECK_ALLOC(kc);
-    half_t* vtc = arena_alloc<half_t>(ctx, (int64_t)B * CK * Tp); CHECK_ALLOC(vtc);
-    TSD_TRY(g_unet_ctx_kv(m, ctx16, Tp, B, kc, vtc));
-    kc_all = kc; vtc_all = vtc;
-  }
-  std::vector<Act> skips;
-  Act cur = x0;
-  for (int i = 0; i < SD15_N; i++) {
+  const int B = f.B, CK = u.kproj_all.N;
+  for (int i = i0; i < i1; i++) {
     const UNetStep& st = SD15_STEPS[i];
     const LayerDef& l = st.l;
     // the next consumer of every layer output starts with GroupNorm(32) (the output layer's has 320 groups)
@@ -635,11 +634,12 @@ static int g_unet_full_forward(tsd_model* m, const float* latents_chw, const hal
     Act y;
     if (l.kind == L_CONV) {
       y = act_alloc_gn(ctx, B, cur.H / l.d, cur.W / l.d, l.b, next_groups); CHECK_ALLOC(y.p);
-      if (i == 0 && in_im2col)
-        TSD_TRY(g_linear(ctx, cat1(cur), (int64_t)B * LH * LW, u.conv_in_im2col, 64, u.conv[0].Opad, 64, u.conv[0].b, nullptr, 0, 0, y.p, y.ld,
-                         &y, LH * LW));
+      const Act* res = i == 0 ? f.in_res : nullptr;
+      if (i == 0 && f.in_im2col)
+        TSD_TRY(g_linear(ctx, cat1(cur), (int64_t)B * f.LH * f.LW, u.conv_in_im2col, 64, u.conv[0].Opad, 64, u.conv[0].b, res ? res->p : nullptr,
+                         res ? res->ld : 0, 0, y.p, y.ld, &y, f.LH * f.LW));
       else
-      TSD_TRY(g_conv3x3(ctx, cur, u.conv[i], l.d, 1, 1, 0, nullptr, 0, nullptr, 0, false, y.p, y.ld, &y));
+      TSD_TRY(g_conv3x3(ctx, cur, u.conv[i], l.d, 1, 1, 0, nullptr, 0, res, 0, false, y.p, y.ld, &y));
     } else if (l.kind == L_UPCONV) {
       y = act_alloc_gn(ctx, B, cur.H * 2, cur.W * 2, l.b, stat_groups(l.b)); CHECK_ALLOC(y.p);
       TSD_TRY(g_conv3x3(ctx, cur, u.conv[i], 1, 1, 1, 1, nullptr, 0, nullptr, 0, false, y.p, y.ld, &y));
@@ -652,18 +652,99 @@ static int g_unet_full_forward(tsd_model* m, const float* latents_chw, const hal
         src = cat2(cur, sk);
       }
       y = act_alloc_gn(ctx, B, cur.H, cur.W, l.b, stat_groups(l.b)); CHECK_ALLOC(y.p);
-      TSD_TRY(g_resblock(ctx, src, B, cur.H, cur.W, 0, u.res[i], tvec, tld, y));
+      TSD_TRY(g_resblock(ctx, src, B, cur.H, cur.W, 0, u.res[i], f.tvec, f.tld, y));
     } else {  // L_ATTN
       y = act_alloc_gn(ctx, B, cur.H, cur.W, cur.C, stat_groups(cur.C)); CHECK_ALLOC(y.p);
       const AttnW& w = u.attn[i];
       CtxKV kv;
-      kv.K = kc_all + w.kv_off; kv.ldk = CK; kv.sK = (int64_t)Tp * CK;
-      kv.Vt = vtc_all + (int64_t)w.kv_off * Tp; kv.ldvt = Tp; kv.sVt = (int64_t)CK * Tp;
-      TSD_TRY(g_unet_attn(ctx, cur, w, ctx16, T, Tp, y, &kv));
+      kv.K = f.kc_all + w.kv_off; kv.ldk = CK; kv.sK = (int64_t)f.Tp * CK;
+      kv.Vt = f.vtc_all + (int64_t)w.kv_off * f.Tp; kv.ldvt = f.Tp; kv.sVt = (int64_t)CK * f.Tp;
+      TSD_TRY(g_unet_attn(ctx, cur, w, f.ctx16, f.T, f.Tp, y, &kv));
     }
     cur = y;
-    if (st.flags & U_PUSH) skips.push_back(cur);
+    if (st.flags & U_PUSH) {
+      skips.push_back(cur);
+      if (f.on_push) TSD_TRY(f.on_push(f.self, (int)skips.size() - 1, cur));
+    }
   }
+  return TSD_OK;
+}
+
+// the part of both full-size graphs in front of the first step: the time rows, the latents as the input convolution reads them, the
+// projected context
+static int unet_full_begin(tsd_model* m, const float* latents_chw, const half_t* ctx16, int T, int Tp, const float* temb, int B, int LH,
+                           int LW, const UNetPre* pre, FullRun* f, Act* x0) {
+  tsd_ctx* ctx = m->ctx;
+  const UNetW& u = m->unet;
+  const float* tvec = pre ? pre->tvec : nullptr;
+  const int tld = pre ? pre->tld : u.tproj.N;
+  if (!pre) TSD_TRY(g_unet_time_path(m, temb, B, &tvec));
+  const bool in_im2col = ctx->opt.conv_in_im2col && u.conv_in_im2col && !u.conv.empty() && u.conv[0].I == 4 && SD15_STEPS[0].l.kind == L_CONV &&
+                         SD15_STEPS[0].l.d == 1;  // as in g_unet_forward: the 4-channel input convolution as one im2col K tile
+  *x0 = act_alloc(ctx, B, LH, LW, 64); CHECK_ALLOC(x0->p);
+  if (in_im2col) TSD_TRY(launch_chw_f32_to_im2col3x3_f16(ctx, latents_chw, B, 4, LH, LW, x0->p));
+  else TSD_TRY(launch_chw_f32_to_nhwc_f16(ctx, latents_chw, B, 4, LH, LW, 4, 1.f, x0->p, 64));
+  // context K and V^T of all attention blocks in two GEMMs
+  const int CK = u.kproj_all.N;
+  const half_t* kc_all = pre ? pre->kc_all : nullptr;
+  const half_t* vtc_all = pre ? pre->vtc_all : nullptr;
+  if (!pre) {
+    half_t* kc = arena_alloc<half_t>(ctx, (int64_t)B * Tp * CK); CHECK_ALLOC(kc);
+    half_t* vtc = arena_alloc<half_t>(ctx, (int64_t)B * CK * Tp); CHECK_ALLOC(vtc);
+    TSD_TRY(g_unet_ctx_kv(m, ctx16, Tp, B, kc, vtc));
+    kc_all = kc; vtc_all = vtc;
+  }
+  f->m = m; f->ctx16 = ctx16; f->T = T; f->Tp = Tp; f->tvec = tvec; f->tld = tld; f->kc_all = kc_all; f->vtc_all = vtc_all;
+  f->B = B; f->LH = LH; f->LW = LW; f->in_im2col = in_im2col;
+  return TSD_OK;
+}
+
+extern "C" int tsd_debug_set_control_stats(tsd_ctx* ctx, int on) {
+  return ctx_set_option(ctx, &TsdOptions::control_stats, on ? 1 : 0, 0, 1);
+}
+
+// x_i <- rn16(x_i + s_b r_i) on the twelve skips and the bottleneck output, in ONE launch (kernels_control.hip), with the GroupNorm
+// statistics their producers emitted re-emitted from the new values - or, under TSD_CONTROL_STATS = 0, dropped, so that every consumer
+// runs its own statistics pass.
+static int unet_control_inject(tsd_ctx* ctx, std::vector<Act>& skips, Act& mid, const ControlRes& control, const float* scale, int B) {
+  if ((int)skips.size() != CONTROL_RESIDUALS - 1) TSD_FAIL(TSD_E_STATE, "controlled UNet: %d skips on the stack, %d residuals", (int)skips.size(), CONTROL_RESIDUALS - 1);
+  ControlTable tab = {};
+  tab.n = CONTROL_RESIDUALS;
+  tab.skip_zero = 1;
+  for (int k = 0; k < CONTROL_RESIDUALS; k++) {
+    Act& a = k < CONTROL_RESIDUALS - 1 ? skips[k] : mid;
+    const Act& r = control.r[k];
+    if (!r.p || r.B != B || r.H != a.H || r.W != a.W || r.C != a.C)
+      TSD_FAIL(TSD_E_SHAPE, "controlled UNet: residual %d is [%d,%d,%d,%d], the tensor [%d,%d,%d,%d]", k, r.B, r.H, r.W, r.C, B, a.H, a.W, a.C);
+    ControlEntry& e = tab.e[k];
+    e.x = a.p; e.ldx = a.ld; e.r = r.p; e.ldr = r.ld; e.HW = a.H * a.W; e.C = a.C;
+    const bool stats = ctx->opt.control_stats && a.gn_part && a.gn_buf && a.gn_groups > 0 && a.gn_nslab > 0;
+    e.part = stats ? a.gn_buf : nullptr;
+    e.groups = stats ? a.gn_groups : 0;
+    e.nslab = stats ? a.gn_nslab : ceil_div(e.HW, 32);
+    if (!stats) { a.gn_part = nullptr; a.gn_nslab = 0; }  // what the producer emitted describes the tensor before the injection
+  }
+  return launch_control_inject(ctx, tab, B, scale);
+}
+
+static int g_unet_full_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, int T, int Tp,
+                               const float* temb, int B, int LH, int LW, float* eps_out_chw, bool eps_nhwc, const UNetPre* pre,
+                               const ControlRes* control, const float* control_scale) {
+  tsd_ctx* ctx = m->ctx;
+  const UNetW& u = m->unet;
+  if (LH <= 0 || LW <= 0 || LH % 16 || LW % 16) TSD_FAIL(TSD_E_SHAPE, "full-size UNet: latent sides %d x %d must be multiples of 16", LH, LW);
+  FullRun f;
+  Act x0;
+  TSD_TRY(unet_full_begin(m, latents_chw, ctx16, T, Tp, temb, B, LH, LW, pre, &f, &x0));
+  std::vector<Act> skips;
+  Act cur = x0;
+  TSD_TRY(unet_full_steps(f, 0, SD15_ENC_N, cur, skips));
+  // The injection writes the skips in place, long after their producers and their encoder-side readers ran and before any decoder block
+  // pops them.  That is safe because the arena is a bump allocator within a forward: a step's output is allocated before the block's own
+  // mark, so the blocks' mark / release pairs recycle their scratch only and no skip (nor a residual of the ControlNet, allocated before
+  // this forward began) is handed out again before the forward returns.
+  if (control) TSD_TRY(unet_control_inject(ctx, skips, cur, *control, control_scale, B));
+  TSD_TRY(unet_full_steps(f, SD15_ENC_N, SD15_N, cur, skips));
   Act hf = act_alloc(ctx, B, LH, LW, 320); CHECK_ALLOC(hf.p);
   TSD_TRY(launch_groupnorm(ctx, norm_src(cat1(cur), 320), B, LH * LW, 320, u.final_groups, 1e-5f, 1.f, 1, hf.p, hf.ld,
                            cur.gn_groups == u.final_groups ? cur.gn_part : nullptr, cur.gn_nslab,
@@ -674,6 +755,79 @@ static int g_unet_full_forward(tsd_model* m, const float* latents_chw, const hal
   TSD_TRY(g_conv3x3(ctx, hf, u.final_conv, 1, 1, 1, 0, nullptr, 0, nullptr, 0, true, eps_tmp, 4));
   TSD_TRY(launch_nhwc_f32_to_chw_f32(ctx, eps_tmp, B, 4, LH, LW, 4, eps_out_chw));
   return TSD_OK;
+}
+
+// ---- ControlNet (kinds 10 / 11) ---------------------------------------------------------------------------------------------------------
+// Hint encoder: eight 3x3 convolutions, SiLU after each but the last, three of them stride 2: fp32 [B,3,8LH,8LW] -> fp16 NHWC [B,LH,LW,320].
+// Each hidden layer leaves its convolution in fp32, applies SiLU there (the elementwise kernel of tsd_silu_f32) and rounds to fp16 once.
+// It reads the hint alone: a denoise loop runs it once.
+int g_controlnet_hint(tsd_model* m, const float* hint_chw, int B, int LH, int LW, Act* out) {
+  tsd_ctx* ctx = m->ctx;
+  const UNetW& u = m->unet;
+  if (!is_controlnet_kind(m->kind)) TSD_FAIL(TSD_E_ARG, "g_controlnet_hint: model is not a ControlNet");
+  if (LH <= 0 || LW <= 0 || LH % 16 || LW % 16) TSD_FAIL(TSD_E_SHAPE, "ControlNet: latent sides %d x %d must be multiples of 16", LH, LW);
+  *out = act_alloc(ctx, B, LH, LW, u.hint[CN_HINT_N - 1].Opad); CHECK_ALLOC(out->p);
+  const size_t mark = ctx->arena.mark();
+  Act cur = act_alloc(ctx, B, 8 * LH, 8 * LW, 64); CHECK_ALLOC(cur.p);
+  TSD_TRY(launch_chw_f32_to_nhwc_f16(ctx, hint_chw, B, 3, 8 * LH, 8 * LW, 3, 1.f, cur.p, 64));
+  for (int i = 0; i < CN_HINT_N; i++) {
+    const ConvW& w = u.hint[i];
+    const int s = CN_HINT_CONVS[i].stride, Ho = cur.H / s, Wo = cur.W / s;
+    if (i == CN_HINT_N - 1) {
+      if (Ho != LH || Wo != LW) TSD_FAIL(TSD_E_STATE, "ControlNet hint encoder: output %d x %d", Ho, Wo);
+      TSD_TRY(g_conv3x3(ctx, cur, w, s, 1, 1, 0, nullptr, 0, nullptr, 0, false, out->p, out->ld));
+      break;
+    }
+    const int64_t rows = (int64_t)B * Ho * Wo;
+    float* y32 = arena_alloc<float>(ctx, rows * w.Opad); CHECK_ALLOC(y32);
+    TSD_TRY(g_conv3x3(ctx, cur, w, s, 1, 1, 0, nullptr, 0, nullptr, 0, true, y32, w.Opad));
+    TSD_TRY(launch_unary_f32(ctx, 0, y32, rows * w.Opad, y32));
+    Act y = act_alloc(ctx, B, Ho, Wo, w.Opad); CHECK_ALLOC(y.p);
+    TSD_TRY(launch_f32_to_f16_rows(ctx, y32, rows, w.Opad, y.p, y.ld, rows));
+    cur = y;
+  }
+  ctx->arena.release(mark);
+  return TSD_OK;
+}
+
+namespace {
+struct ZeroConvs { tsd_model* m; ControlRes* out; };
+int zero_conv(tsd_ctx* ctx, const ConvW& w, const Act& a, Act* r) {
+  if (w.k != 1 || w.Ipad != a.C || w.Opad != a.C) TSD_FAIL(TSD_E_STATE, "ControlNet: zero convolution %d -> %d on a %d-channel tensor", w.Ipad, w.Opad, a.C);
+  *r = act_alloc(ctx, a.B, a.H, a.W, a.C); CHECK_ALLOC(r->p);
+  return g_linear(ctx, cat1(a), a.pixels(), w.w, w.Ipad, w.Opad, w.Ipad, w.b, nullptr, 0, 0, r->p, r->ld, nullptr, a.H * a.W);
+}
+int zero_on_push(void* self, int k, const Act& a) {
+  ZeroConvs* z = (ZeroConvs*)self;
+  if (k < 0 || k >= (int)z->m->unet.zero.size() || k >= CONTROL_RESIDUALS - 1) TSD_FAIL(TSD_E_STATE, "ControlNet: skip %d has no zero convolution", k);
+  return zero_conv(z->m->ctx, z->m->unet.zero[k], a, &z->out->r[k]);
+}
+}  // namespace
+
+// h = conv_in(latents) + hint_feat, the UNet's encoder and bottleneck on the ControlNet's weights, and r_i = zero_i(h_i) for every pushed
+// tensor and for the bottleneck output: 13 fp16 NHWC tensors in the arena (they live until the caller's plan ends).
+int g_controlnet_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, int T, int Tp, const float* temb, const Act& hint_feat,
+                         int B, int LH, int LW, const UNetPre* pre, ControlRes* out) {
+  tsd_ctx* ctx = m->ctx;
+  if (!is_controlnet_kind(m->kind)) TSD_FAIL(TSD_E_ARG, "g_controlnet_forward: model is not a ControlNet");
+  if (LH <= 0 || LW <= 0 || LH % 16 || LW % 16) TSD_FAIL(TSD_E_SHAPE, "ControlNet: latent sides %d x %d must be multiples of 16", LH, LW);
+  if (!hint_feat.p || hint_feat.H != LH || hint_feat.W != LW || hint_feat.C != 320 || hint_feat.B != B)
+    TSD_FAIL(TSD_E_SHAPE, "ControlNet: hint features [%d,%d,%d,%d] for a [%d,%d,%d,320] forward", hint_feat.B, hint_feat.H, hint_feat.W, hint_feat.C, B, LH, LW);
+  const int prev = gemm_set_splitk_big(ctx, 4);  // the graph's setting, as in g_unet_forward
+  FullRun f;
+  Act x0;
+  ZeroConvs z{m, out};
+  int r = unet_full_begin(m, latents_chw, ctx16, T, Tp, temb, B, LH, LW, pre, &f, &x0);
+  if (r == TSD_OK) {
+    f.in_res = &hint_feat; f.on_push = zero_on_push; f.self = &z;
+    std::vector<Act> skips;
+    Act cur = x0;
+    r = unet_full_steps(f, 0, SD15_ENC_N, cur, skips);
+    if (r == TSD_OK && (int)skips.size() != CONTROL_RESIDUALS - 1) { tsd_set_error("ControlNet: %d skips", (int)skips.size()); r = TSD_E_STATE; }
+    if (r == TSD_OK) r = zero_conv(ctx, m->unet.zero_mid, cur, &out->r[CONTROL_RESIDUALS - 1]);
+  }
+  gemm_set_splitk_big(ctx, prev);
+  return r;
 }
 
 // ---- VAE (vae.mojo:131-159, :221-250) -------------------------------------------------------------------

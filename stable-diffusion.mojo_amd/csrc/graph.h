@@ -78,8 +78,18 @@ struct UNetPre {
   const half_t* kc_all = nullptr;            // context K of all attention blocks [B*Tp][CK], CK = kproj_all.N
   const half_t* vtc_all = nullptr;           // context V^T [B][CK][Tp]
 };
+// control: the 13 residuals of a ControlNet forward on the SAME context (fp16 NHWC in its arena: the twelve skips in push order, then the
+// bottleneck output), added to the full-size UNet's skips and bottleneck output scaled by control_scale, a device fp32 [B] - one launch
+// between the bottleneck and the first decoder step.  Absent, the forward enqueues what it always did.  The Tiny-SD graph refuses it.
+struct ControlRes { Act r[CONTROL_RESIDUALS]; };
 int g_unet_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, int T, int Tp, const float* temb, int B,
-                   int LH, int LW, float* eps_out_chw, bool eps_nhwc = false, const UNetPre* pre = nullptr);
+                   int LH, int LW, float* eps_out_chw, bool eps_nhwc = false, const UNetPre* pre = nullptr,
+                   const ControlRes* control = nullptr, const float* control_scale = nullptr);
+// ControlNet (kinds 10 / 11).  hint_chw: device fp32 [B,3,8LH,8LW] -> hint features fp16 NHWC [B,LH,LW,320] in the arena
+int g_controlnet_hint(tsd_model* m, const float* hint_chw, int B, int LH, int LW, Act* out);
+// pre: a UNetPre made from the ControlNet's OWN weights (g_unet_time_path / g_unet_ctx_kv on `m`), or nullptr
+int g_controlnet_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, int T, int Tp, const float* temb, const Act& hint_feat,
+                         int B, int LH, int LW, const UNetPre* pre, ControlRes* out);
 int g_unet_time_path(tsd_model* m, const float* temb, int B, const float** tvec_out);  // -> tvec [B][tproj.N] in the arena
 int g_unet_ctx_kv(tsd_model* m, const half_t* ctx16, int Tp, int B, half_t* kc_all, half_t* vtc_all);
 int g_decoder_forward(tsd_model* m, const float* latents_chw, int B, int LH, int LW, float* images_chw);

@@ -379,6 +379,7 @@ extern "C" int tsd_model_get_param(tsd_model* m, int index, float* out, int64_t 
 extern "C" int tsd_model_lora_add(tsd_model* m, int index, int row0, int rows, const float* up, const float* down, int rank, float scale) {
   if (!m || !up || !down) TSD_FAIL(TSD_E_ARG, "tsd_model_lora_add: NULL argument");
   TSD_TRY(param_checked(m, index, "tsd_model_lora_add"));
+  if (is_controlnet_kind(m->kind)) TSD_FAIL(TSD_E_ARG, "lora_add: adapters on a ControlNet are not supported");
   const ParamSpec& p = m->params[index];
   if (p.kind != P_CONV_W && p.kind != P_LIN_W) TSD_FAIL(TSD_E_ARG, "lora_add: %s is a bias / norm parameter, not a weight matrix", p.name.c_str());
   if (!p.used) TSD_FAIL(TSD_E_ARG, "lora_add: %s is never read by the forward", p.name.c_str());
@@ -465,11 +466,12 @@ static int model_build_derived(tsd_model* m) {
     if (r == TSD_OK) m->vae.conv_in_im2col = (const half_t*)m->derived;
     return r;
   }
-  if (!is_diffusion_kind(m->kind)) return TSD_OK;
+  if (!is_diffusion_kind(m->kind) && !is_controlnet_kind(m->kind)) return TSD_OK;
+  const bool full_graph = is_full_unet_kind(m->kind) || is_controlnet_kind(m->kind);  // a ControlNet is the full-size graph's encoder half
   std::vector<AttnW*> el;
   for (auto& a : m->unet.attn) if (a.C && (attn_tail_weights_ok(a) || attn_head_weights_ok(a))) el.push_back(&a);
   // input convolution (4 latent channels): [Opad][64] im2col weights
-  const ConvW& cin = is_full_unet_kind(m->kind) ? (m->unet.conv.empty() ? m->unet.conv1 : m->unet.conv[0]) : m->unet.conv1;
+  const ConvW& cin = full_graph ? (m->unet.conv.empty() ? m->unet.conv1 : m->unet.conv[0]) : m->unet.conv1;
   const bool cin_ok = cin.w && cin.k == 3 && cin.I > 0 && 9 * cin.I <= 64 && cin.Ipad == 64;
   const size_t cin_b = cin_ok ? ((size_t)cin.Opad * 64 * sizeof(half_t) + 255) & ~size_t(255) : 0;
   // weight-heavy 3x3 convs (>= TSD_CONV_W_TM MiB of weights; 0 = off): K-tile-major copies
@@ -482,7 +484,7 @@ static int model_build_derived(tsd_model* m) {
   // input-channel halves added (UNetW::res_dup).  Structure only: an even split into multiples of 64 channels, an even group count whose
   // groups do not straddle the halves, and no per-channel affine (that would differ between the halves).
   bool dup = false;
-  if (ctx->opt.fold_dup && !is_full_unet_kind(m->kind) && m->unet.res.size() > 9 && m->unet.attn.size() > 8) {
+  if (ctx->opt.fold_dup && !full_graph && m->unet.res.size() > 9 && m->unet.attn.size() > 8) {
     const ResW& r = m->unet.res[9];
     const int half = r.cin / 2;
     dup = r.cin > 0 && r.cin % 2 == 0 && half % 64 == 0 && m->unet.attn[8].C == half && r.groups % 2 == 0 && half % (r.groups / 2) == 0 &&
@@ -542,7 +544,7 @@ static int model_build_derived(tsd_model* m) {
   // TSD_UPS_FOLD says - the option is read per forward, by the graph - and keyed on structure only, never on a batch or a latent size.
   std::vector<ConvW*> uf;
   size_t uf_b = 0;
-  if (!is_full_unet_kind(m->kind))
+  if (!full_graph)
     for (int bi : UPS_RES_BLOCKS)
       if (bi < (int)m->unet.res.size() && ups_fold_weights_ok(m->unet.res[bi])) {
         ConvW* c = &m->unet.res[bi].conv1;
@@ -805,10 +807,11 @@ LinW model_lin(const tsd_model* m, const std::string& prefix, bool use_bias) {
 }
 
 int model_resolve(tsd_model* m) {
-  if (is_diffusion_kind(m->kind)) {
+  if (is_diffusion_kind(m->kind) || is_controlnet_kind(m->kind)) {
     UNetW& u = m->unet;
-    const bool full = is_full_unet_kind(m->kind);
-    const bool torch_norms = m->kind == TSD_MODEL_DIFFUSION_SD15_TORCH;
+    const bool cn = is_controlnet_kind(m->kind);
+    const bool full = is_full_unet_kind(m->kind) || cn;
+    const bool torch_norms = is_torch_unet_kind(m->kind);
     auto aff = [&](const std::string& name) {
       NormAffine a;
       if (torch_norms) {
@@ -818,7 +821,7 @@ int model_resolve(tsd_model* m) {
       }
       return a;
     };
-    const int n_layers = full ? SD15_N : 23;
+    const int n_layers = cn ? SD15_ENC_N : (full ? SD15_N : 23);
     u.res.assign(n_layers, ResW());
     u.attn.assign(n_layers, AttnW());
     u.conv.assign(n_layers, ConvW());
@@ -868,6 +871,14 @@ int model_resolve(tsd_model* m) {
       u.conv1 = model_conv(m, "unet.layer1");
       u.conv4 = model_conv(m, "unet.layer4");
       u.conv7 = model_conv(m, "unet.layer7");
+    }
+    if (cn) {  // no output layer; the hint encoder and the zero convolutions instead
+      for (int i = 0; i < CN_HINT_N; i++) u.hint[i] = model_conv(m, "hint.conv" + std::to_string(i + 1));
+      u.zero.clear();
+      for (int i = 0, k = 0; i < SD15_ENC_N; i++)
+        if (SD15_STEPS[i].flags & U_PUSH) u.zero.push_back(model_conv(m, "zero.skip" + std::to_string(++k)));
+      u.zero_mid = model_conv(m, "zero.mid");
+      return TSD_OK;
     }
     u.final_conv = model_conv(m, "final.layer2");
     u.final_gn = aff("final.layer1");

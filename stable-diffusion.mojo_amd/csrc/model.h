@@ -45,7 +45,15 @@ static inline bool is_clip_kind(int kind) { return kind == TSD_MODEL_CLIP || kin
 static inline bool is_decoder_kind(int kind) { return kind == TSD_MODEL_DECODER || kind == TSD_MODEL_DECODER_TORCH; }
 static inline bool is_encoder_kind(int kind) { return kind == TSD_MODEL_ENCODER || kind == TSD_MODEL_ENCODER_TORCH; }
 static inline bool is_vae_torch_kind(int kind) { return kind == TSD_MODEL_DECODER_TORCH || kind == TSD_MODEL_ENCODER_TORCH; }
-constexpr int TSD_MODEL_KIND_MAX = TSD_MODEL_ENCODER_TORCH;
+// ControlNet of the full-size UNet (kinds 10 / 11): SD15_STEPS[0, SD15_ENC_N) - the encoder and the bottleneck - on weights of its own, a
+// hint encoder in front and one 1x1 "zero" convolution per pushed skip and for the bottleneck output (graph.cpp g_controlnet_forward)
+constexpr int SD15_ENC_N = 21;  // the first U_POP step: 18 encoder steps (12 of them push) and the three of the bottleneck
+constexpr int CN_HINT_N = 8;
+struct HintConvDef { int cin, cout, stride; };
+extern const HintConvDef CN_HINT_CONVS[CN_HINT_N];
+static inline bool is_controlnet_kind(int kind) { return kind == TSD_MODEL_CONTROLNET_SD15 || kind == TSD_MODEL_CONTROLNET_SD15_TORCH; }
+static inline bool is_torch_unet_kind(int kind) { return kind == TSD_MODEL_DIFFUSION_SD15_TORCH || kind == TSD_MODEL_CONTROLNET_SD15_TORCH; }
+constexpr int TSD_MODEL_KIND_MAX = TSD_MODEL_CONTROLNET_SD15_TORCH;
 
 std::vector<ParamSpec> build_param_specs(int model_kind);
 
@@ -102,6 +110,10 @@ struct UNetW {
   // model_check_ready().  Decided from the graph's structure, never from the data.
   ResW res_dup;
   bool res_dup_on = false;
+  // ControlNet kinds only: the hint encoder, the zero convolutions in push order and the one of the bottleneck output
+  ConvW hint[CN_HINT_N];
+  std::vector<ConvW> zero;
+  ConvW zero_mid;
   NormAffine final_gn;      // torch-norm extension (kind 6)
   int final_groups = 320;   // UNet_Output_Layer's GroupNorm (diffusion.mojo:287-291); 32 with torch norms
 };

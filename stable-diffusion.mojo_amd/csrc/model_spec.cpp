@@ -33,6 +33,9 @@ const UNetStep SD15_STEPS[SD15_N] = {
 #undef R
 #undef A
 
+// hint encoder of the ControlNet kinds (diffusers' ControlNetConditioningEmbedding): {cin, cout, stride}, 3x3, SiLU after each but the last
+const HintConvDef CN_HINT_CONVS[CN_HINT_N] = {{3, 16, 1}, {16, 16, 1}, {16, 32, 2}, {32, 32, 1}, {32, 96, 2}, {96, 96, 1}, {96, 256, 2}, {256, 320, 1}};
+
 const LayerDef DECODER_LAYERS[26] = {
     {L_CONV, 4, 4, 1, 1},     {L_CONV, 4, 512, 3, 1},   {L_RES, 512, 512}, {L_ATTN, 512},     {L_RES, 512, 512},
     {L_RES, 512, 512},        {L_RES, 512, 512},        {L_RES, 512, 512}, {L_UP},            {L_CONV, 512, 512, 3, 1},
@@ -152,6 +155,44 @@ std::vector<ParamSpec> build_param_specs(int kind) {
       }
       b.norm("final.layer1", 320);
     }
+  } else if (is_controlnet_kind(kind)) {  // the UNet's encoder half under the UNet's names, between the hint encoder and the zero convolutions
+    b.lin("time_embed.layer1", 320, 1280);
+    b.lin("time_embed.layer2", 1280, 1280);
+    for (int i = 0; i < CN_HINT_N; i++) {
+      // every width is padded to whole 64-channel K chunks with exact zeros (SiLU keeps them zero): the next convolution reads them
+      b.conv("hint.conv" + std::to_string(i + 1), CN_HINT_CONVS[i].cin, CN_HINT_CONVS[i].cout, 3);
+      ParamSpec& w = b.out[b.out.size() - 2];
+      w.Opad = round_up(CN_HINT_CONVS[i].cout, 64);
+      b.out.back().Opad = w.Opad;
+      if (i == CN_HINT_N - 1) w.bound = 0.f;  // zero-initialised: an untrained ControlNet adds nothing
+    }
+    for (int i = 0; i < SD15_ENC_N; i++) {
+      const LayerDef& l = SD15_STEPS[i].l;
+      const std::string n = "unet.layer" + std::to_string(i + 1);
+      if (l.kind == L_CONV) b.conv(n, l.a, l.b, l.c);
+      else if (l.kind == L_RES) b.unet_res(n, l.a, l.b);
+      else if (l.kind == L_ATTN) b.unet_attn(n, l.a, l.b);
+    }
+    int k = 0;
+    for (int i = 0; i < SD15_ENC_N; i++)
+      if (SD15_STEPS[i].flags & U_PUSH) {
+        const LayerDef& l = SD15_STEPS[i].l;
+        const int C = l.kind == L_ATTN ? l.a * l.b : l.b;
+        b.conv("zero.skip" + std::to_string(++k), C, C, 1);
+        b.out[b.out.size() - 2].bound = 0.f;
+      }
+    b.conv("zero.mid", 1280, 1280, 1);
+    b.out[b.out.size() - 2].bound = 0.f;
+    if (kind == TSD_MODEL_CONTROLNET_SD15_TORCH)  // norm parameters appended, so the shared indices equal kind 10's
+      for (int i = 0; i < SD15_ENC_N; i++) {
+        const LayerDef& l = SD15_STEPS[i].l;
+        const std::string n = "unet.layer" + std::to_string(i + 1);
+        if (l.kind == L_RES) { b.norm(n + ".layer1", l.a); b.norm(n + ".layer4", l.b); }
+        else if (l.kind == L_ATTN) {
+          const int C = l.a * l.b;
+          b.norm(n + ".layer1", C); b.norm(n + ".layer3", C); b.norm(n + ".layer5", C); b.norm(n + ".layer7", C);
+        }
+      }
   } else if (is_clip_kind(kind)) {  // clip.mojo:74-88 ; parameter order = oracle/spec.py clip_params()
     ParamSpec t;
     t.name = "embedding.token.weight"; t.ndim = 2; t.shape[0] = 49408; t.shape[1] = 768; t.kind = P_LIN_W;

@@ -27,6 +27,7 @@ void options_from_env(TsdOptions& o) {
   o.ups_fold = env_int("TSD_UPS_FOLD", o.ups_fold) ? 1 : 0;
   o.fold_dup = env_int("TSD_FOLD_DUP", o.fold_dup) ? 1 : 0;
   o.session_hoist = env_int("TSD_SESSION_HOIST", o.session_hoist) ? 1 : 0;
+  o.control_stats = env_int("TSD_CONTROL_STATS", o.control_stats) ? 1 : 0;
   o.conv_w_tm_mib = env_int("TSD_CONV_W_TM", o.conv_w_tm_mib);
   o.lin_w_tm = env_int("TSD_LIN_W_TM", o.lin_w_tm);
   o.lin_w_tm_kib = env_int("TSD_LIN_W_TM_KIB", o.lin_w_tm_kib);

@@ -89,6 +89,20 @@ struct tsd_session {
   } slot[16];
   float* trows = nullptr;     // [Bu][tproj.N] fp32: row i_b of ttab per sample, gathered by every advance (own allocation, grown at slots_open)
   size_t trows_cap = 0;
+  // ControlNet (tsd_session_set_control): lockstep sessions on a full-size UNet.  It stays until set_control(NULL); upload() rebuilds what
+  // depends on the context and the schedule.  A step inside [ctl_first, ctl_last] runs the ControlNet forward at the UNet's batch and then
+  // the controlled UNet forward in one arena; every other step enqueues what it always did.
+  tsd_model* cn = nullptr;    // nullptr: no control
+  int ctl_first = 0, ctl_last = -1;  // ctl_last < 0: to the end of the list
+  char* ctl = nullptr;        // scale [16] fp32 | hint features fp16 [Bu][LH*LW][320]: written by set_control, read by every controlled step
+  float* ctl_scale = nullptr; // per sample of the UNet's batch: the scale, 0 on the uncond half under cond_only
+  half_t* ctl_feat = nullptr;
+  size_t ctl_cap = 0;
+  char* cn_kv = nullptr;      // the ControlNet's own hoisted context K / V^T and time table, like kv / ttab
+  half_t* cn_kc = nullptr; half_t* cn_vtc = nullptr;
+  float* cn_ttab = nullptr;
+  size_t cn_kv_cap = 0, cn_ttab_cap = 0;
+  unsigned cn_gen = 0;        // generation of the ControlNet's parameters at the last build
 };
 
 // inf / NaN scan of a downloaded tensor (exponent bits all ones); the buffers at this boundary are 0.5 - 25 MB
@@ -224,23 +238,41 @@ static int session_configure(tsd_session* s, const SessionConfig& c) {
 //   * time table: per schedule entry, the time embedding of its timestep for Bu samples and the three small linears behind it; every
 //     sample sees the same timestep, so the Bu rows are equal and row 0 is kept (the forward reads it with a per-sample stride of 0).
 // The arena (sized by upload() for this too) is scratch; nothing here synchronises.
-static int session_build_invariants(tsd_session* s) {
+static int session_build_invariants_of(tsd_session* s, tsd_model* m, half_t* kc_all, half_t* vtc_all, float* ttab) {
   tsd_ctx* ctx = s->ctx;
-  tsd_model* m = s->unet;
   const int Bu = s->Bu, N = m->unet.tproj.N;
   ctx->arena.top = 0;
-  TSD_TRY(g_unet_ctx_kv(m, s->ctx16, s->Tp, Bu, s->kc_all, s->vtc_all));
+  TSD_TRY(g_unet_ctx_kv(m, s->ctx16, s->Tp, Bu, kc_all, vtc_all));
   for (size_t i = 0; i < s->timesteps.size(); i++) {
     ctx->arena.top = 0;
     TSD_TRY(launch_time_embedding(ctx, nullptr, (float)s->timesteps[i], Bu, s->temb));
     const float* tvec = nullptr;
     TSD_TRY(g_unet_time_path(m, s->temb, Bu, &tvec));
-    HIP_TRY(hipMemcpyAsync(s->ttab + i * (size_t)N, tvec, (size_t)N * 4, hipMemcpyDeviceToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ttab + i * (size_t)N, tvec, (size_t)N * 4, hipMemcpyDeviceToDevice, ctx->stream));
   }
   ctx->arena.top = 0;
-  s->model_gen = m->gen;
+  return TSD_OK;
+}
+static int session_build_invariants(tsd_session* s) {
+  TSD_TRY(session_build_invariants_of(s, s->unet, s->kc_all, s->vtc_all, s->ttab));
+  s->model_gen = s->unet->gen;
   s->inv_builds++;
   return TSD_OK;
+}
+// the same for the ControlNet of a session with control: its own weights, the session's context and schedule
+static int session_build_control_invariants(tsd_session* s) {
+  TSD_TRY(session_build_invariants_of(s, s->cn, s->cn_kc, s->cn_vtc, s->cn_ttab));
+  s->cn_gen = s->cn->gen;
+  return TSD_OK;
+}
+static UNetPre session_control_pre(const tsd_session* s, int i) {
+  UNetPre p;
+  p.tvec = s->cn_ttab + (size_t)i * s->cn->unet.tproj.N; p.tld = 0;
+  p.kc_all = s->cn_kc; p.vtc_all = s->cn_vtc;
+  return p;
+}
+static bool session_controls(const tsd_session* s, int i) {
+  return s->cn && i >= s->ctl_first && (s->ctl_last < 0 || i <= s->ctl_last);
 }
 static UNetPre session_pre(const tsd_session* s, int i) {
   UNetPre p;
@@ -250,6 +282,11 @@ static UNetPre session_pre(const tsd_session* s, int i) {
 }
 // Parameters were set since the last build: the derived weights, then what this session derived from them (all samples).
 static int session_refresh(tsd_session* s) {
+  if (s->cn && s->cn_gen != s->cn->gen) {
+    TSD_TRY(model_check_ready(s->cn));
+    if (s->hoist) TSD_TRY(session_build_control_invariants(s));
+    s->cn_gen = s->cn->gen;
+  }
   if (s->model_gen == s->unet->gen) return TSD_OK;
   TSD_TRY(model_check_ready(s->unet));
   if (s->hoist) TSD_TRY(session_build_invariants(s));
@@ -259,7 +296,9 @@ static int session_refresh(tsd_session* s) {
 // The UNet forward of a step or an advance: latents (twice under CFG: model_input for both passes is the same latents,
 // pipeline.mojo:107-108) -> eps.  `pre` is read under the hoist only.  eps stays in the output convolution's layout ([B][LH*LW][4])
 // where the forward can write it; the updates read it as such (no conversion launch): *eps_hw is their eps_hw argument.
-static int session_forward(tsd_session* s, const UNetPre* pre, int* eps_hw) {
+// control_i >= 0: step control_i lies in the window of a session with control - the ControlNet forward on the same inputs first, its
+// residuals in the arena, then the UNet forward with them; no copy from the host and no allocation.
+static int session_forward(tsd_session* s, const UNetPre* pre, int* eps_hw, int control_i = -1) {
   tsd_ctx* ctx = s->ctx;
   const size_t nl = (size_t)s->B * 4 * s->LH * s->LW;
   const float* lat_in = s->latents;
@@ -270,7 +309,15 @@ static int session_forward(tsd_session* s, const UNetPre* pre, int* eps_hw) {
   }
   ctx->arena.top = 0;
   const bool eps_nhwc = s->unet->unet.final_conv.Opad == 4;  // g_unet_forward's condition for writing that layout
-  TSD_TRY(g_unet_forward(s->unet, lat_in, s->ctx16, s->T, s->Tp, s->temb, s->Bu, s->LH, s->LW, s->eps, eps_nhwc, s->hoist ? pre : nullptr));
+  ControlRes res;
+  if (control_i >= 0) {
+    Act hf;
+    hf.p = s->ctl_feat; hf.B = s->Bu; hf.H = s->LH; hf.W = s->LW; hf.C = 320; hf.ld = 320;
+    const UNetPre cpre = s->hoist ? session_control_pre(s, control_i) : UNetPre();
+    TSD_TRY(g_controlnet_forward(s->cn, lat_in, s->ctx16, s->T, s->Tp, s->temb, hf, s->Bu, s->LH, s->LW, s->hoist ? &cpre : nullptr, &res));
+  }
+  TSD_TRY(g_unet_forward(s->unet, lat_in, s->ctx16, s->T, s->Tp, s->temb, s->Bu, s->LH, s->LW, s->eps, eps_nhwc, s->hoist ? pre : nullptr,
+                         control_i >= 0 ? &res : nullptr, control_i >= 0 ? s->ctl_scale : nullptr));
   ctx->arena.top = 0;
   *eps_hw = eps_nhwc ? s->LH * s->LW : 0;
   return TSD_OK;
@@ -342,6 +389,9 @@ extern "C" int tsd_session_destroy(tsd_session* s) {
   if (s->kv) hipFree(s->kv);
   if (s->ttab) hipFree(s->ttab);
   if (s->trows) hipFree(s->trows);
+  if (s->ctl) hipFree(s->ctl);
+  if (s->cn_kv) hipFree(s->cn_kv);
+  if (s->cn_ttab) hipFree(s->cn_ttab);
   delete s;
   return TSD_OK;
 }
@@ -387,6 +437,45 @@ extern "C" int tsd_session_timestep(tsd_session* s, int i) {
   return s->timesteps[i];
 }
 
+// A session with control: the workspace for a controlled step (the ControlNet forward and the UNet forward share the arena: the residuals
+// live there while the UNet runs) and, under the hoist, the ControlNet's own context K / V^T and time table.  Called by set_control() and
+// by every upload() while the control is set - never by a step.
+static int session_control_prepare(tsd_session* s) {
+  tsd_ctx* ctx = s->ctx;
+  const int Bu = s->Bu, LH = s->LH, LW = s->LW, T = s->T, Tp = s->Tp;
+  TSD_TRY(model_check_ready(s->cn));
+  if (s->hoist) {
+    const int CK = s->cn->unet.kproj_all.N, N = s->cn->unet.tproj.N;
+    const size_t kc_bytes = ((size_t)Bu * Tp * CK * 2 + 255) & ~size_t(255);
+    TSD_TRY(session_grow((void**)&s->cn_kv, &s->cn_kv_cap, 2 * kc_bytes, "ControlNet context K/V"));
+    s->cn_kc = (half_t*)s->cn_kv; s->cn_vtc = (half_t*)(s->cn_kv + kc_bytes);
+    TSD_TRY(session_grow((void**)&s->cn_ttab, &s->cn_ttab_cap, s->timesteps.size() * (size_t)N * 4, "ControlNet time table"));
+  }
+  Arena& a = ctx->arena;
+  a.planning = true; a.top = 0; a.peak = 0;
+  const UNetPre pre0 = s->hoist ? session_pre(s, 0) : UNetPre();
+  const UNetPre cpre0 = s->hoist ? session_control_pre(s, 0) : UNetPre();
+  Act hf;
+  hf.p = s->ctl_feat; hf.B = Bu; hf.H = LH; hf.W = LW; hf.C = 320; hf.ld = 320;
+  ControlRes res;
+  int r = g_controlnet_forward(s->cn, s->lat2, s->ctx16, T, Tp, s->temb, hf, Bu, LH, LW, s->hoist ? &cpre0 : nullptr, &res);
+  if (r == TSD_OK)
+    r = g_unet_forward(s->unet, s->lat2, s->ctx16, T, Tp, s->temb, Bu, LH, LW, s->eps, false, s->hoist ? &pre0 : nullptr, &res, s->ctl_scale);
+  size_t need = a.peak;
+  if (r == TSD_OK && s->hoist) {  // session_build_control_invariants' scratch
+    const float* tv = nullptr;
+    a.top = 0; a.peak = 0;
+    r = g_unet_time_path(s->cn, s->temb, Bu, &tv);
+    need = std::max(need, a.peak);
+  }
+  a.planning = false; a.top = 0; a.peak = 0;
+  if (r != TSD_OK) return r;
+  TSD_TRY(ctx_reserve_arena(ctx, need));
+  s->cn_gen = s->cn->gen;
+  if (s->hoist) TSD_TRY(session_build_control_invariants(s));
+  return TSD_OK;
+}
+
 // What upload() and slots_open() share once the session's buffers hold their data: size the workspace once for this session's shapes (no
 // allocation inside the timed loop), size and fill the step-invariant buffers, and mark the session ready.
 static int session_prepare(tsd_session* s) {
@@ -427,6 +516,7 @@ static int session_prepare(tsd_session* s) {
   TSD_TRY(ctx_reserve_arena(ctx, need));
   s->model_gen = s->unet->gen;
   if (s->hoist) TSD_TRY(session_build_invariants(s));
+  if (s->cn) TSD_TRY(session_control_prepare(s));  // the control outlives an upload(): what depends on the context and the schedule again
   s->opt_gen = ctx->opt.gen;
   s->uploaded = true;
   s->poisoned = false;
@@ -567,7 +657,7 @@ extern "C" int tsd_session_step(tsd_session* s, int i) {
   if (!s->hoist) TSD_TRY(launch_time_embedding(s->ctx, nullptr, (float)s->timesteps[i], s->Bu, s->temb));
   const UNetPre pre = s->hoist ? session_pre(s, i) : UNetPre();
   int eps_hw = 0;
-  TSD_TRY(session_forward(s, &pre, &eps_hw));
+  TSD_TRY(session_forward(s, &pre, &eps_hw, session_controls(s, i) ? i : -1));
   int idx[16];
   bool hist_valid[16];
   std::fill(idx, idx + 16, i);  // an advance with every sample at index i, under the lockstep history rule
@@ -579,6 +669,54 @@ extern "C" int tsd_session_step(tsd_session* s, int i) {
   if (t.tab.e[0].flags & SLOT_HIST_OUT) s->hist_valid_for = i + 1;
   return TSD_OK;
 }
+
+// ControlNet for the steps first_step <= i <= last_step (last_step < 0: to the end) of a lockstep session on a full-size UNet; cn == NULL
+// turns it off.  hint: host fp32 [B,3,8LH,8LW].  The hint encoder runs here, once, at the UNet's batch (under CFG on the hint twice, the
+// launches of tsd_diffusion_forward_control_hw at that batch) and its features stay on the device; the per-sample scales - `scale`, and 0
+// on the uncond half under cond_only - are built here and uploaded once.  Synchronous.
+extern "C" int tsd_session_set_control(tsd_session* s, tsd_model* cn, const float* hint, float scale, int cond_only, int first_step,
+                                       int last_step) {
+  NOTNULL(s);
+  SESSION_NOT_SLOTS(s, "set_control()");
+  if (!cn) { s->cn = nullptr; return TSD_OK; }
+  NOTNULL(hint);
+  if (!is_full_unet_kind(s->unet->kind)) TSD_FAIL(TSD_E_ARG, "session: set_control needs a full-size UNet (the Tiny-SD graph has no ControlNet)");
+  if (!is_controlnet_kind(cn->kind)) TSD_FAIL(TSD_E_ARG, "session: set_control: the model is not a ControlNet");
+  if (cn->ctx != s->ctx) TSD_FAIL(TSD_E_ARG, "session: set_control: the ControlNet belongs to another context (the residuals live in the session's arena)");
+  if (!(fabsf(scale) <= 3.4028235e38f)) TSD_FAIL(TSD_E_ARG, "session: set_control: the scale is not finite");
+  if (first_step < 0 || (last_step >= 0 && last_step < first_step)) TSD_FAIL(TSD_E_ARG, "session: set_control: window [%d, %d]", first_step, last_step);
+  if (!s->uploaded) TSD_FAIL(TSD_E_STATE, "session: upload() before set_control() (the ControlNet reads the uploaded context)");
+  SESSION_NOT_POISONED(s);
+  TSD_TRY(session_options_unchanged(s, "upload()"));
+  tsd_ctx* ctx = s->ctx;
+  HIP_TRY(hipSetDevice(ctx->device));
+  TSD_TRY(model_check_ready(cn));
+  const int B = s->B, Bu = s->Bu, LH = s->LH, LW = s->LW;
+  const size_t hw = (size_t)LH * LW, nh = (size_t)B * 3 * 64 * hw, feat_bytes = (size_t)Bu * hw * 320 * 2;
+  s->cn = nullptr;  // until everything below succeeded
+  TSD_TRY(session_grow((void**)&s->ctl, &s->ctl_cap, 256 + feat_bytes, "control"));
+  s->ctl_scale = (float*)s->ctl; s->ctl_feat = (half_t*)(s->ctl + 256);
+  float sc[16] = {};
+  for (int b = 0; b < Bu; b++) sc[b] = (b >= B && cond_only) ? 0.f : scale;
+  TSD_TRY(ctx_reserve_staging(ctx, (size_t)Bu * 3 * 64 * hw * 4));
+  float* dh = (float*)ctx->staging;
+  HIP_TRY(hipMemcpyAsync(s->ctl_scale, sc, sizeof(sc), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(dh, hint, nh * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (s->cfg) HIP_TRY(hipMemcpyAsync(dh + nh, dh, nh * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  Act hf;
+  TSD_TRY(run_planned(ctx, [&]() -> int {
+    TSD_TRY(g_controlnet_hint(cn, dh, Bu, LH, LW, &hf));
+    if (ctx->launch()) HIP_TRY(hipMemcpyAsync(s->ctl_feat, hf.p, feat_bytes, hipMemcpyDeviceToDevice, ctx->stream));
+    return TSD_OK;
+  }));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  s->cn = cn; s->ctl_first = first_step; s->ctl_last = last_step;
+  const int r = session_control_prepare(s);
+  if (r != TSD_OK) { s->cn = nullptr; return r; }
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return ctx_check_status(ctx);
+}
+extern "C" int tsd_session_control_active(tsd_session* s) { return s ? (s->cn ? 1 : 0) : TSD_E_ARG; }
 
 extern "C" int tsd_session_add_noise(tsd_session* s, int i, const float* noise) {
   NOTNULL(s); NOTNULL(noise);
@@ -753,6 +891,7 @@ extern "C" int tsd_session_download_images(tsd_session* s, int rescale_0_255, fl
 // (update_element.h): a slot's latents are bit for bit those of a lockstep session of the same batch shape running its request.
 extern "C" int tsd_session_slots_open(tsd_session* s) {
   NOTNULL(s);
+  if (s->cn) TSD_FAIL(TSD_E_STATE, "session: slots_open() on a session with a ControlNet (per-slot control is not supported); set_control(NULL) first");
   tsd_ctx* ctx = s->ctx;
   HIP_TRY(hipSetDevice(ctx->device));
   const int B = s->B, Bu = s->Bu;

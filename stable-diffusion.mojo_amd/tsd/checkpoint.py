@@ -120,12 +120,11 @@ def _layer_kinds():
             for i, f in fields.items()}
 
 
-def diffusers_sd15_unet_to_params(state, prefix=""):
-    """diffusers UNet2DConditionModel state dict -> {our parameter name: array} for kind "diffusion_sd15_torch"."""
+def _layers_from_diffusers(state, prefix, modules, out):
+    """The flat layers `unet.layer1 ..` of `modules` (a prefix of SD15_MODULES) from a diffusers state dict into `out`."""
     g = lambda k: np.asarray(state[prefix + k], dtype=np.float32)  # noqa: E731
-    out = {ours: g(theirs) for ours, theirs in _TOP}
     kinds = _layer_kinds()
-    for i, mod in enumerate(SD15_MODULES, start=1):
+    for i, mod in enumerate(modules, start=1):
         n, kind = f"unet.layer{i}", kinds[i]
         if kind == "conv":
             out[n + ".kernel"], out[n + ".bias"] = g(mod + ".weight"), g(mod + ".bias")
@@ -146,11 +145,10 @@ def diffusers_sd15_unet_to_params(state, prefix=""):
     return out
 
 
-def params_to_diffusers_sd15_unet(params, prefix=""):
-    """Inverse of `diffusers_sd15_unet_to_params` (export; used by the round-trip test)."""
-    out = {prefix + theirs: np.asarray(params[ours], np.float32) for ours, theirs in _TOP}
+def _layers_to_diffusers(params, prefix, modules, out):
+    """Inverse of `_layers_from_diffusers`."""
     kinds = _layer_kinds()
-    for i, mod in enumerate(SD15_MODULES, start=1):
+    for i, mod in enumerate(modules, start=1):
         n, kind = f"unet.layer{i}", kinds[i]
         if kind == "conv":
             out[prefix + mod + ".weight"], out[prefix + mod + ".bias"] = params[n + ".kernel"], params[n + ".bias"]
@@ -170,6 +168,17 @@ def params_to_diffusers_sd15_unet(params, prefix=""):
     return out
 
 
+def diffusers_sd15_unet_to_params(state, prefix=""):
+    """diffusers UNet2DConditionModel state dict -> {our parameter name: array} for kind "diffusion_sd15_torch"."""
+    g = lambda k: np.asarray(state[prefix + k], dtype=np.float32)  # noqa: E731
+    return _layers_from_diffusers(state, prefix, SD15_MODULES, {ours: g(theirs) for ours, theirs in _TOP})
+
+
+def params_to_diffusers_sd15_unet(params, prefix=""):
+    """Inverse of `diffusers_sd15_unet_to_params` (export; used by the round-trip test)."""
+    return _layers_to_diffusers(params, prefix, SD15_MODULES, {prefix + theirs: np.asarray(params[ours], np.float32) for ours, theirs in _TOP})
+
+
 def load_sd15_unet(path, ctx=None, prefix=""):
     """tsd.Diffusion(variant="diffusion_sd15_torch") with the weights of a diffusers SD-1.x UNet safetensors file."""
     from .diffusion import Diffusion
@@ -183,6 +192,57 @@ def load_sd15_unet(path, ctx=None, prefix=""):
         elif tuple(params[name].shape) != tuple(shape):
             raise ValueError(f"{name}: checkpoint shape {params[name].shape}, model expects {shape}")
     return Diffusion(ctx=ctx, params=params, variant="diffusion_sd15_torch")
+
+
+# ---- ControlNet (diffusers `ControlNetModel` for SD-1.x -> model kind "controlnet_sd15_torch") ------------------------------------------
+# the UNet's encoder and bottleneck under the UNet's own names (the first 21 flat layers), the hint encoder and the zero convolutions
+CONTROLNET_LAYERS = 21
+CONTROLNET_MODULES = SD15_MODULES[:CONTROLNET_LAYERS]
+CONTROLNET_HINT_MODULES = (["controlnet_cond_embedding.conv_in"] + [f"controlnet_cond_embedding.blocks.{i}" for i in range(6)]
+                           + ["controlnet_cond_embedding.conv_out"])
+_CN_CONVS = ([(f"hint.conv{i}", m) for i, m in enumerate(CONTROLNET_HINT_MODULES, start=1)]
+             + [(f"zero.skip{i + 1}", f"controlnet_down_blocks.{i}") for i in range(12)] + [("zero.mid", "controlnet_mid_block")])
+_CN_TOP = _TOP[:4]   # the time embedding; a ControlNet has no output layer
+
+
+def diffusers_controlnet_to_params(state, prefix=""):
+    """diffusers ControlNetModel state dict -> {our parameter name: array} for kind "controlnet_sd15_torch"."""
+    g = lambda k: np.asarray(state[prefix + k], dtype=np.float32)  # noqa: E731
+    out = {ours: g(theirs) for ours, theirs in _CN_TOP}
+    for ours, theirs in _CN_CONVS:
+        out[ours + ".kernel"], out[ours + ".bias"] = g(theirs + ".weight"), g(theirs + ".bias")
+    return _layers_from_diffusers(state, prefix, CONTROLNET_MODULES, out)
+
+
+def params_to_diffusers_controlnet(params, prefix=""):
+    """Inverse of `diffusers_controlnet_to_params` (export; used by the round-trip test)."""
+    out = {prefix + theirs: np.asarray(params[ours], np.float32) for ours, theirs in _CN_TOP}
+    for ours, theirs in _CN_CONVS:
+        out[prefix + theirs + ".weight"], out[prefix + theirs + ".bias"] = params[ours + ".kernel"], params[ours + ".bias"]
+    return _layers_to_diffusers(params, prefix, CONTROLNET_MODULES, out)
+
+
+def controlnet_params_complete(params):
+    """`params` with zeros for the fields the reference's structs allocate but never read; KeyError / ValueError for a missing or misshapen
+    tensor that the forward does read."""
+    from .model import param_specs
+    params = dict(params)
+    for name, shape, used, _ in param_specs("controlnet_sd15_torch"):
+        if name not in params:
+            if used:
+                raise KeyError(f"checkpoint has no tensor for {name}")
+            params[name] = np.zeros(shape, np.float32)
+        elif tuple(np.shape(params[name])) != tuple(shape):
+            raise ValueError(f"{name}: checkpoint shape {np.shape(params[name])}, model expects {shape}")
+    return params
+
+
+def load_controlnet(path_or_state, ctx=None, prefix=""):
+    """tsd.ControlNet(variant="controlnet_sd15_torch") with the weights of a diffusers SD-1.x ControlNetModel: a safetensors file, or its
+    state dict."""
+    from .diffusion import ControlNet
+    state = read_safetensors(path_or_state) if isinstance(path_or_state, str) else path_or_state
+    return ControlNet(ctx=ctx, params=controlnet_params_complete(diffusers_controlnet_to_params(state, prefix)), variant="controlnet_sd15_torch")
 
 
 def hf_clip_text_to_params(state):

@@ -164,24 +164,100 @@ class Diffusion:
         if params is not None:
             self.model.load_params(params)
 
-    def forward(self, x, context, time):
-        x = f32(x)
-        single = x.ndim == 3
-        xb = x[None] if single else x
-        if xb.ndim != 4 or xb.shape[1] != 4:
-            raise ValueError(f"latents must have shape (4, LH, LW) or (B, 4, LH, LW), got {x.shape}")
+    def forward(self, x, context, time, control=None, hint=None, control_scale=1.0):
+        """control: a `ControlNet` on the same context, with hint (3,8LH,8LW) or (B,3,8LH,8LW) and control_scale a scalar or one value per
+        sample - the ControlNet's residuals, scaled per sample, are added to the skips and the bottleneck output (full-size variants)."""
+        xb, c, t, single = _forward_inputs(x, context, time)
         B, _, LH, LW = xb.shape
-        c = f32(context)
-        if c.ndim == 2:
-            c = c[None]
-        if c.shape[0] == 1 and B > 1:
-            c = np.repeat(c, B, axis=0)
-        t = f32(time).reshape(-1, 320)
-        if t.shape[0] == 1 and B > 1:
-            t = np.repeat(t, B, axis=0)
-        c, t = f32(c), f32(t)
         out = np.empty_like(xb)
-        code = lib().tsd_diffusion_forward_hw(self.model.h, ptr(xb), ptr(c), ptr(t), B, LH, LW, c.shape[1], ptr(out))
+        if control is None:
+            if hint is not None:
+                raise ValueError("hint is the ControlNet's input: pass control= as well")
+            code = lib().tsd_diffusion_forward_hw(self.model.h, ptr(xb), ptr(c), ptr(t), B, LH, LW, c.shape[1], ptr(out))
+        else:
+            h = _hint_input(hint, B, LH, LW)
+            s = np.ascontiguousarray(np.broadcast_to(np.asarray(control_scale, dtype=np.float32), (B,)))
+            code = lib().tsd_diffusion_forward_control_hw(self.model.h, control.model.h, ptr(xb), ptr(c), ptr(t), ptr(h), ptr(s), B, LH, LW,
+                                                          c.shape[1], ptr(out))
         if check(code, True):
             return NULL_MATRIX()
         return out[0] if single else out
+
+
+def _forward_inputs(x, context, time):
+    """The inputs of `Diffusion.forward` / `ControlNet.forward` as batched contiguous fp32 arrays: (latents, context, time, single)."""
+    x = f32(x)
+    single = x.ndim == 3
+    xb = x[None] if single else x
+    if xb.ndim != 4 or xb.shape[1] != 4:
+        raise ValueError(f"latents must have shape (4, LH, LW) or (B, 4, LH, LW), got {x.shape}")
+    B = xb.shape[0]
+    c = f32(context)
+    if c.ndim == 2:
+        c = c[None]
+    if c.shape[0] == 1 and B > 1:
+        c = np.repeat(c, B, axis=0)
+    t = f32(time).reshape(-1, 320)
+    if t.shape[0] == 1 and B > 1:
+        t = np.repeat(t, B, axis=0)
+    return f32(xb), f32(c), f32(t), single
+
+
+def _hint_input(hint, B, LH, LW):
+    if hint is None:
+        raise ValueError("a ControlNet needs its hint image")
+    h = f32(hint)
+    if h.ndim == 3:
+        h = h[None]
+    if h.shape[0] == 1 and B > 1:
+        h = np.repeat(h, B, axis=0)
+    if h.shape != (B, 3, 8 * LH, 8 * LW):
+        raise ValueError(f"the hint must have shape (3, {8 * LH}, {8 * LW}) or ({B}, 3, {8 * LH}, {8 * LW}), got {np.shape(hint)}")
+    return f32(h)
+
+
+# (C, divisor of the latent side) of the 13 residuals: the twelve skips in push order, then the bottleneck output
+CONTROL_RESIDUAL_SHAPES = ((320, 1), (320, 1), (320, 1), (320, 2), (640, 2), (640, 2), (640, 4), (1280, 4), (1280, 4), (1280, 8), (1280, 8),
+                           (1280, 8), (1280, 8))
+
+
+class ControlNet:
+    """ControlNet of the full-size UNet (Zhang et al. 2023; the layout of diffusers' `ControlNetModel`) - device-resident weights.
+
+    variant: "controlnet_sd15" (the reference's norms, pairs with "diffusion_sd15") or "controlnet_sd15_torch" (the norm semantics and
+    parameters of PyTorch-trained checkpoints, pairs with "diffusion_sd15_torch"; see tsd.checkpoint.load_controlnet).  A seeded init
+    leaves the zero convolutions at zero, as an untrained ControlNet has them: its residuals are all zero.
+    forward(x, context, time, hint) -> the 13 residuals [(B,C_i,H_i,W_i)] (CONTROL_RESIDUAL_SHAPES); `Diffusion.forward(control=...)` runs both models
+    in one call and is the consumer."""
+
+    def __init__(self, seed=0, ctx=None, params=None, variant="controlnet_sd15"):
+        if variant not in ("controlnet_sd15", "controlnet_sd15_torch"):
+            raise ValueError(f"unknown ControlNet variant {variant!r}")
+        self.model = Model(variant, ctx=ctx, seed=None if params is not None else seed)
+        if params is not None:
+            self.model.load_params(params)
+
+    def hint(self, hint):
+        """The hint encoder alone (`tsd_controlnet_hint_hw`): (3,8LH,8LW) or (B,3,8LH,8LW) -> features (320,LH,LW) / (B,320,LH,LW).
+        It depends on the hint only: a denoise session runs it once."""
+        h = f32(hint)
+        single = h.ndim == 3
+        hb = f32(h[None] if single else h)
+        if hb.ndim != 4 or hb.shape[1] != 3 or hb.shape[2] % 8 or hb.shape[3] % 8:
+            raise ValueError(f"the hint must have shape (3, 8LH, 8LW) or (B, 3, 8LH, 8LW), got {h.shape}")
+        B, _, H, W = hb.shape
+        out = np.empty((B, 320, H // 8, W // 8), dtype=np.float32)
+        if check(lib().tsd_controlnet_hint_hw(self.model.h, ptr(hb), B, H // 8, W // 8, ptr(out)), True):
+            return NULL_MATRIX()
+        return out[0] if single else out
+
+    def forward(self, x, context, time, hint):
+        xb, c, t, single = _forward_inputs(x, context, time)
+        B, _, LH, LW = xb.shape
+        h = _hint_input(hint, B, LH, LW)
+        outs = [np.empty((B, ch, LH // d, LW // d), dtype=np.float32) for ch, d in CONTROL_RESIDUAL_SHAPES]
+        arr = (fp * len(outs))(*[ptr(o) for o in outs])
+        code = lib().tsd_controlnet_forward_hw(self.model.h, ptr(xb), ptr(c), ptr(t), ptr(h), B, LH, LW, c.shape[1], arr)
+        if check(code, True):
+            return NULL_MATRIX()
+        return [o[0] for o in outs] if single else outs

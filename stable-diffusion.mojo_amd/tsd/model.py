@@ -9,7 +9,8 @@ from ._lib import check, check_guidance_rescale, f32, latent_shape, lib, predict
 KINDS = {"diffusion": _lib.MODEL_DIFFUSION, "decoder": _lib.MODEL_DECODER, "encoder": _lib.MODEL_ENCODER,
          "clip": _lib.MODEL_CLIP, "diffusion_sd15": _lib.MODEL_DIFFUSION_SD15,
          "diffusion_sd15_torch": _lib.MODEL_DIFFUSION_SD15_TORCH, "clip_torch": _lib.MODEL_CLIP_TORCH,
-         "decoder_torch": _lib.MODEL_DECODER_TORCH, "encoder_torch": _lib.MODEL_ENCODER_TORCH}
+         "decoder_torch": _lib.MODEL_DECODER_TORCH, "encoder_torch": _lib.MODEL_ENCODER_TORCH,
+         "controlnet_sd15": _lib.MODEL_CONTROLNET_SD15, "controlnet_sd15_torch": _lib.MODEL_CONTROLNET_SD15_TORCH}
 
 
 def param_specs(kind):
@@ -277,6 +278,30 @@ class Session:
         set_schedule() and set_sampler() turn it off."""
         phi = check_guidance_rescale(phi, self.cfg)
         check(lib().tsd_session_set_guidance_rescale(self.h, phi))
+
+    def set_control(self, cn, hint=None, scale=1.0, cond_only=False, first_step=0, last_step=None):
+        """ControlNet for the steps first_step <= i <= last_step (None: to the end) of this lockstep session on a full-size UNet
+        (`tsd_session_set_control`): cn a `tsd.ControlNet` on the same context (None turns control off), hint (3,8LH,8LW) or
+        (B,3,8LH,8LW), scale one value for every sample; cond_only: under CFG the uncond half gets scale 0.  Call after upload(); the
+        hint encoder runs here once and every step inside the window runs the ControlNet and the controlled UNet forward on the device.
+        The control stays across upload()s until set_control(None)."""
+        if cn is None:
+            check(lib().tsd_session_set_control(self.h, None, None, 0.0, 0, 0, -1))
+            return
+        h = f32(hint) if hint is not None else None
+        if h is not None and h.ndim == 3:
+            h = np.repeat(h[None], self.B, axis=0) if self.B > 1 else h[None]
+        if h is None or h.shape != (self.B, 3, 8 * self.LH, 8 * self.LW):
+            raise ValueError(f"set_control: the hint must have shape (3, {8 * self.LH}, {8 * self.LW}) or ({self.B}, 3, {8 * self.LH}, "
+                             f"{8 * self.LW}), got {None if hint is None else np.shape(hint)}")
+        h = f32(h)
+        model = getattr(cn, "model", cn)
+        check(lib().tsd_session_set_control(self.h, model.h, ptr(h), float(scale), 1 if cond_only else 0, int(first_step),
+                                            -1 if last_step is None else int(last_step)))
+
+    @property
+    def control_active(self):
+        return lib().tsd_session_control_active(self.h) == 1
 
     @property
     def guidance_rescale(self):

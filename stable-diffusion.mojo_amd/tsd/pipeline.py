@@ -26,7 +26,8 @@ def encode_prompts(prompts, tokenizer, clip):
 def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg=True, cfg_scale=7.5,
              inference_steps=50, seed_val=0, input_image=None, encoder=None, latents=None, noise=None,
              num_training_steps=1000, L=64, return_latents=False, sampler="ddpm", eta=0.0, spacing="leading", mask=None,
-             mask_mode="any", seeds=None, guidance_rescale=0.0, prediction="epsilon", zero_terminal_snr=False):
+             mask_mode="any", seeds=None, guidance_rescale=0.0, prediction="epsilon", zero_terminal_snr=False, controlnet=None,
+             control_image=None, control_scale=1.0, control_cond_only=False, control_start=0.0, control_end=1.0):
     """context (B,T,768); returns images (B,3,8LH,8LW) in [0,255] like pipeline.mojo:127.  L is the latent side (64: 512x512) or a pair
     (LH, LW) for a rectangular image ((96, 64): 512 wide, 768 high); where the text below says L,L the tensor is LH,LW.
 
@@ -52,7 +53,16 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
     prediction "epsilon" (the reference's models) | "v" (v-prediction models: SD-2.x-768-style checkpoints and v fine-tunes), and
     zero_terminal_snr=True for a model trained on the rescaled schedule of Lin et al. 2023 (algorithm 1), which wants "v" and
     spacing="trailing" so that sampling starts from pure noise (`Session.set_prediction`; `checkpoint.read_scheduler_config` maps a
-    diffusers scheduler_config.json to these keywords).  The defaults are the reference's loop."""
+    diffusers scheduler_config.json to these keywords).  The defaults are the reference's loop.
+
+    controlnet, a `tsd.ControlNet` on the diffusion model's context (full-size UNet variants), with control_image (3,8LH,8LW) or
+    (B,3,8LH,8LW), taken as given (diffusers feeds [0, 1]): every step whose index lies in [control_start, control_end] as fractions of
+    the step list (diffusers' control_guidance_start / _end) runs the ControlNet and adds its residuals scaled by control_scale;
+    control_cond_only: with cfg, only the conditional half is controlled (`Session.set_control`)."""
+    if (controlnet is None) != (control_image is None):
+        raise ValueError("generate: controlnet and control_image go together")
+    if controlnet is not None and not (0.0 <= control_start <= control_end <= 1.0):
+        raise ValueError(f"generate: control_start / control_end must satisfy 0 <= start <= end <= 1, got {control_start}, {control_end}")
     guidance_rescale = check_guidance_rescale(guidance_rescale, cfg)
     if seeds is not None and (noise is not None or latents is not None):
         raise ValueError("generate(seeds=...) draws latents and noise on the device: pass neither noise nor latents")
@@ -107,6 +117,11 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
             sess.set_inpaint(mask_lat, latents, z4)
     if guidance_rescale > 0.0:
         sess.set_guidance_rescale(guidance_rescale)
+    if controlnet is not None:  # step i of n is controlled when control_start <= i / n and (i + 1) / n <= control_end, as diffusers keeps it
+        first = int(np.ceil(control_start * n - 1e-9))
+        last = int(np.floor(control_end * n + 1e-9)) - 1
+        if last >= first:
+            sess.set_control(controlnet, control_image, control_scale, control_cond_only, first, last)
     for i in range(n):  # pipeline.mojo:87-122
         sess.step(i)
     out_lat = sess.latents()

@@ -140,7 +140,8 @@ class SlotScheduler:
 
 
 def generate_stream(diffusion, decoder, requests, B, L, T=77, cfg=True, inference_steps=50, num_training_steps=1000, sampler="ddpm",
-                    eta=0.0, spacing="leading", return_latents=False, stats=None, prediction="epsilon", zero_terminal_snr=False):
+                    eta=0.0, spacing="leading", return_latents=False, stats=None, prediction="epsilon", zero_terminal_snr=False, controlnet=None,
+                    control_image=None, **control_keywords):
     """Continuous batching of `generate`: `requests` is an iterator of `Request`s (or tuples in its field order); yields (id, image
     (3,8LH,8LW) in [0,255]) - or (id, latents) with return_latents or without a decoder - as requests finish, B at a time on the device.
     L is the latent side or a pair (LH, LW): one shape for the whole stream.
@@ -151,7 +152,11 @@ def generate_stream(diffusion, decoder, requests, B, L, T=77, cfg=True, inferenc
     guidance_rescale=...)` rescales it; it needs cfg=True.
     prediction / zero_terminal_snr are `generate`'s keywords (`Session.set_prediction`): they belong to the model, so to the whole stream,
     never to a request.
-    Finished latents are decoded through `decoder.forward`, one image per call.  `stats`, a dict, receives advances / active_ticks / occupancy when the stream ends."""
+    Finished latents are decoded through `decoder.forward`, one image per call.  `stats`, a dict, receives advances / active_ticks / occupancy when the stream ends.
+    controlnet / control_image (and generate's other control_* keywords) are refused: the stream runs on a slot session, and per-slot
+    control is not supported (`generate` runs lockstep sessions and takes them)."""
+    if controlnet is not None or control_image is not None or control_keywords:
+        raise ValueError("generate_stream runs on a slot session, which has no ControlNet (per-slot control is not supported); use generate()")
     from .model import Session
     from .utils import _unary
     sess = Session(diffusion.model, None, B, L, T, cfg=cfg)

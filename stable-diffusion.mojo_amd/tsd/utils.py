@@ -5,6 +5,7 @@ call into libtsd.so (HIP kernels on gfx950).  Tensors are numpy float32 arrays i
 layout: (C,H,W) images, (1,T,D) or (T,D) token matrices.  Error behaviour mirrors the reference:
 shape errors print a message and return a null matrix (`Matrix(0,0,0)`).
 """
+import ctypes as C
 import math
 
 import numpy as np
@@ -234,6 +235,31 @@ def cfg_rescale(eps, eps_uncond, cfg_scale=7.5, phi=0.7, ctx=None):
     co, uo, g = np.empty_like(c), np.empty_like(u), np.empty(B, dtype=np.float32)
     check(lib().tsd_cfg_rescale_f32(_ctx(ctx), ptr(c), ptr(u), B, c.size // B if B else 0, ptr(s), ptr(p), ptr(co), ptr(uo), ptr(g)))
     return co, uo, g
+
+
+def control_inject(x, r, scale, groups, nslab, ctx=None):
+    """The ControlNet injection launch alone (`tsd_control_inject_f16`) over a table of tensors: x[i], r[i] float16 (B, HW_i, C_i), scale
+    (B,), groups[i] / nslab[i] the GroupNorm statistics geometry of tensor i (groups 0: none) -> (y, partial) with
+    y[i] = float16(float32(x[i]) + scale_b * float32(r[i])) rounded once and partial[i] float32 (B, nslab_i, groups_i, 2), the (sum, sum of
+    squares) of y[i] per slab of ceil(HW_i / nslab_i) rows and channel group (None for an entry without statistics)."""
+    xs = [np.ascontiguousarray(a, dtype=np.float16) for a in x]
+    rs = [np.ascontiguousarray(a, dtype=np.float16) for a in r]
+    n = len(xs)
+    if n == 0 or len(rs) != n or len(groups) != n or len(nslab) != n:
+        raise ValueError("control_inject: x, r, groups and nslab must be lists of one length")
+    B = xs[0].shape[0]
+    for a, b in zip(xs, rs):
+        if a.ndim != 3 or a.shape != b.shape or a.shape[0] != B:
+            raise ValueError(f"control_inject: x {a.shape} and r {b.shape} must both be (B, HW, C) with one B")
+    s = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, dtype=np.float32), (B,)))
+    ys = [np.empty_like(a) for a in xs]
+    ps = [np.empty((B, int(ns), int(g), 2), dtype=np.float32) if g else None for g, ns in zip(groups, nslab)]
+    I, V = C.c_int * n, C.c_void_p * n
+    vp_of = lambda arrs: V(*[a.ctypes.data for a in arrs])  # noqa: E731
+    parts = (_lib.fp * n)(*[ptr(p) if p is not None else None for p in ps])
+    check(lib().tsd_control_inject_f16(_ctx(ctx), n, vp_of(xs), vp_of(rs), B, I(*[a.shape[1] for a in xs]), I(*[a.shape[2] for a in xs]),
+                                       I(*[int(g) for g in groups]), I(*[int(v) for v in nslab]), ptr(s), vp_of(ys), parts))
+    return ys, ps
 
 
 def ddpm_step(x, eps, eps_uncond, cfg_scale, noise, i, num_inference_steps, num_training_steps=1000, start_step=0, spacing="leading",
