@@ -188,7 +188,7 @@ int tsd_vae_attention_block_f32(tsd_ctx* ctx, const float* x, int C, int H, int 
  * norms - 32 groups in the residual blocks (the reference declares 16, vae.mojo:42-43), per-channel weight / bias of
  * every GroupNorm appended to the kind-2 / kind-3 list (`lN.group_norm1`, `lN.group_norm2`, `lN.group_norm`, and
  * `lN` for the stand-alone norm), eps inside the root: the layout of diffusers' AutoencoderKL decoder / encoder. */
-typedef enum tsd_model_kind { TSD_MODEL_DIFFUSION = 1, TSD_MODEL_DECODER = 2, TSD_MODEL_ENCODER = 3, TSD_MODEL_CLIP = 4, TSD_MODEL_DIFFUSION_SD15 = 5, TSD_MODEL_DIFFUSION_SD15_TORCH = 6, TSD_MODEL_CLIP_TORCH = 7, TSD_MODEL_DECODER_TORCH = 8, TSD_MODEL_ENCODER_TORCH = 9, TSD_MODEL_CONTROLNET_SD15 = 10, TSD_MODEL_CONTROLNET_SD15_TORCH = 11 } tsd_model_kind;
+typedef enum tsd_model_kind { TSD_MODEL_DIFFUSION = 1, TSD_MODEL_DECODER = 2, TSD_MODEL_ENCODER = 3, TSD_MODEL_CLIP = 4, TSD_MODEL_DIFFUSION_SD15 = 5, TSD_MODEL_DIFFUSION_SD15_TORCH = 6, TSD_MODEL_CLIP_TORCH = 7, TSD_MODEL_DECODER_TORCH = 8, TSD_MODEL_ENCODER_TORCH = 9, TSD_MODEL_CONTROLNET_SD15 = 10, TSD_MODEL_CONTROLNET_SD15_TORCH = 11, TSD_MODEL_DIFFUSION_SD2 = 16, TSD_MODEL_CLIP_SD2 = 17 } tsd_model_kind;
 /* TSD_MODEL_CONTROLNET_SD15 (EXTENSION: Zhang et al. 2023; the layout of diffusers' ControlNetModel): the control network of the full-size
  * UNet.  Parameters in this order: `time_embed.layer1/2`; the hint encoder `hint.conv1 .. hint.conv8` (3x3 convolutions 3->16, 16->16,
  * 16->32 stride 2, 32->32, 32->96 stride 2, 96->96, 96->256 stride 2, 256->320; SiLU after each but the last, the last initialised to
@@ -314,6 +314,16 @@ int tsd_encoder_forward_hw(tsd_model* m, const float* images, const float* noise
  * Token embedding + learned position table, 12 x (LayerNorm, causal 12-head self-attention, +res, LayerNorm,
  * Linear 768->3072, quick-GELU x*sigmoid(1.702x), Linear 3072->768, +res), final LayerNorm. */
 int tsd_clip_forward(tsd_model* m, const int32_t* tokens, int B, int T, float* context);
+/* Kinds 12 - 15 are reserved and refused (TSD_E_ARG), like every number that names no kind.
+ * TSD_MODEL_DIFFUSION_SD2 (16): the UNet of the Stable Diffusion 2.x checkpoints - the full-size graph of kind 6 (torch norm semantics,
+ * erf-GELU) on a second step table: every attention block has head dimension 64 (5 / 10 / 20 / 20 heads at C = 320 / 640 / 1280 / 1280)
+ * and its k_proj / v_proj read a 1024-wide context.  Parameter names and order are kind 6's, the norm parameters last.  Sessions, samplers,
+ * seeds, v-prediction, CFG, guidance rescale, inpainting, slots and the hoist work as on kind 6; a ControlNet (an SD-1.x network) is refused.
+ * TSD_MODEL_CLIP_SD2 (17): the OpenCLIP-H text encoder as diffusers ships it for SD-2.x: width 1024, 16 heads of 64, 23 layers, erf-GELU
+ * MLP, torch LayerNorms and the final LayerNorm, 77 positions, vocabulary 49408; parameter names are kind 7's.
+ * tsd_model_context_width: the width of the context rows a UNet (or ControlNet) model reads and of the rows a text encoder writes - 768,
+ * or 1024 for the SD-2.x kinds - so callers can size `context` ([B][T][width] fp32 everywhere); TSD_E_ARG (negative) for a VAE model. */
+int tsd_model_context_width(const tsd_model* m);
 
 /* ---- prompt tokenizer (host only, no GPU): `Tokenizer` + `bpe_encode`, helpers/utils.mojo:229-327, over the
  * tokenizer_clip.bin wire format of tokenizer_creation.py:43-48 (u32 max_token_length; per token f32 score, u32 length,
@@ -739,11 +749,14 @@ enum tsd_attn_desc_field {
   TSD_AD_COUNT
 };
 #define TSD_AD_VERSION_1 1
+/* Version 2 has the fields of version 1 and admits head dimension 64 (flash_attn_kernel<64, 1>, TSD_AK_64).  A version-1 descriptor keeps
+ * what it always did with d = 64: it is sized, the run is refused with the launcher's status, reports kernel 0 and writes nothing. */
+#define TSD_AD_VERSION_2 2
 enum tsd_attn_mode { TSD_AM_ATTN = 0, TSD_AM_SOFTMAX_ROWS };
 /* Operand slots: inputs Q [B][Sq][ldq], K [B][Sk][ldk], V^T [B][H*d][ldvt] (fp16), X (softmax_rows input: fp32, or the fp16 rows the
  * launch overwrites); output O (attention: [B][Sq][ldo] fp16; softmax_rows: the rows, in X's type and layout). */
 enum tsd_attn_operand { TSD_AO_Q = 0, TSD_AO_K, TSD_AO_VT, TSD_AO_X, TSD_AO_O, TSD_AO_COUNT };
-enum tsd_attn_kernel { TSD_AK_NONE = 0, TSD_AK_40_1, TSD_AK_40_2, TSD_AK_40_8W, TSD_AK_80, TSD_AK_160 };
+enum tsd_attn_kernel { TSD_AK_NONE = 0, TSD_AK_40_1, TSD_AK_40_2, TSD_AK_40_8W, TSD_AK_80, TSD_AK_160, TSD_AK_64 };
 /* info: guard / pitch-gap elements the launch changed; the kernel that ran (tsd_attn_kernel; softmax_rows: 1 k_softmax_rows<float>,
  * 2 k_softmax_rows<half_t>, 3 / 4 k_softmax_rows_h8<1> / <2>); workgroups that took the exact repeat in this launch; the diag and xcd_map
  * values passed to the kernel. */

@@ -43,20 +43,21 @@ extern "C" int tsd_diffusion_forward_hw(tsd_model* m, const float* latents, cons
   const int mult = is_full_unet_kind(m->kind) ? 16 : 8;  // the graph's own rule (graph.cpp), refused here before anything is planned
   if (LH % mult || LW % mult) TSD_FAIL(TSD_E_SHAPE, "diffusion: latent sides %d x %d must be multiples of %d", LH, LW, mult);
   tsd_ctx* ctx = m->ctx;
+  const int W = model_context_width(m);  // 768, or 1024 for the SD-2.x UNet
   return run_model(m, [&]() -> int {
     const int Tp = round_up(T, 8);
     const int64_t nl = (int64_t)B * 4 * LH * LW;
     float* dl = arena_alloc<float>(ctx, nl);
-    float* dc = arena_alloc<float>(ctx, (int64_t)B * T * 768);
+    float* dc = arena_alloc<float>(ctx, (int64_t)B * T * W);
     float* dt = arena_alloc<float>(ctx, (int64_t)B * 320);
-    half_t* c16 = arena_alloc<half_t>(ctx, (int64_t)B * Tp * 768);
+    half_t* c16 = arena_alloc<half_t>(ctx, (int64_t)B * Tp * W);
     float* de = arena_alloc<float>(ctx, nl);
     if (!dl || !dc || !dt || !c16 || !de) TSD_FAIL(TSD_E_ALLOC, "workspace arena exhausted");
     TSD_TRY(h2d(ctx, dl, latents, nl * 4));
-    TSD_TRY(h2d(ctx, dc, context, (size_t)B * T * 768 * 4));
+    TSD_TRY(h2d(ctx, dc, context, (size_t)B * T * W * 4));
     TSD_TRY(h2d(ctx, dt, time_emb, (size_t)B * 320 * 4));
-    for (int b = 0; b < B; b++)  // [T][768] -> zero-padded [Tp][768] per sample
-      TSD_TRY(launch_f32_to_f16_rows(ctx, dc + (int64_t)b * T * 768, T, 768, c16 + (int64_t)b * Tp * 768, 768, Tp));
+    for (int b = 0; b < B; b++)  // [T][W] -> zero-padded [Tp][W] per sample
+      TSD_TRY(launch_f32_to_f16_rows(ctx, dc + (int64_t)b * T * W, T, W, c16 + (int64_t)b * Tp * W, W, Tp));
     TSD_TRY(g_unet_forward(m, dl, c16, T, Tp, dt, B, LH, LW, de));
     return d2h(ctx, out, de, nl * 4);
   });
@@ -80,22 +81,22 @@ int cn_check(const tsd_model* cn, int B, int LH, int LW, int T) {
 }
 // latents, context (converted to padded fp16 rows), time embedding and hint onto the device
 int cn_upload(tsd_ctx* ctx, const float* latents, const float* context, const float* time_emb, const float* hint, int B, int LH, int LW, int T,
-              CnInputs* in) {
+              int W, CnInputs* in) {  // W: the context width of the models that read it
   const int Tp = round_up(T, 8);
   const int64_t nl = (int64_t)B * 4 * LH * LW, nh = (int64_t)B * 3 * 64 * LH * LW;
   in->Tp = Tp;
   in->dl = arena_alloc<float>(ctx, nl);
-  float* dc = arena_alloc<float>(ctx, (int64_t)B * T * 768);
+  float* dc = arena_alloc<float>(ctx, (int64_t)B * T * W);
   in->dt = arena_alloc<float>(ctx, (int64_t)B * 320);
-  in->c16 = arena_alloc<half_t>(ctx, (int64_t)B * Tp * 768);
+  in->c16 = arena_alloc<half_t>(ctx, (int64_t)B * Tp * W);
   in->dh = arena_alloc<float>(ctx, nh);
   if (!in->dl || !dc || !in->dt || !in->c16 || !in->dh) TSD_FAIL(TSD_E_ALLOC, "workspace arena exhausted");
   TSD_TRY(h2d(ctx, in->dl, latents, nl * 4));
-  TSD_TRY(h2d(ctx, dc, context, (size_t)B * T * 768 * 4));
+  TSD_TRY(h2d(ctx, dc, context, (size_t)B * T * W * 4));
   TSD_TRY(h2d(ctx, in->dt, time_emb, (size_t)B * 320 * 4));
   TSD_TRY(h2d(ctx, in->dh, hint, nh * 4));
-  for (int b = 0; b < B; b++)  // [T][768] -> zero-padded [Tp][768] per sample
-    TSD_TRY(launch_f32_to_f16_rows(ctx, dc + (int64_t)b * T * 768, T, 768, in->c16 + (int64_t)b * Tp * 768, 768, Tp));
+  for (int b = 0; b < B; b++)  // [T][W] -> zero-padded [Tp][W] per sample
+    TSD_TRY(launch_f32_to_f16_rows(ctx, dc + (int64_t)b * T * W, T, W, in->c16 + (int64_t)b * Tp * W, W, Tp));
   return TSD_OK;
 }
 }  // namespace
@@ -109,7 +110,7 @@ extern "C" int tsd_controlnet_forward_hw(tsd_model* cn, const float* latents, co
   tsd_ctx* ctx = cn->ctx;
   return run_model(cn, [&]() -> int {
     CnInputs in;
-    TSD_TRY(cn_upload(ctx, latents, context, time_emb, hint, B, LH, LW, T, &in));
+    TSD_TRY(cn_upload(ctx, latents, context, time_emb, hint, B, LH, LW, T, model_context_width(cn), &in));
     Act hf;
     TSD_TRY(g_controlnet_hint(cn, in.dh, B, LH, LW, &hf));
     ControlRes res;
@@ -150,6 +151,9 @@ extern "C" int tsd_diffusion_forward_control_hw(tsd_model* unet, tsd_model* cn, 
   NOTNULL(unet); NOTNULL(cn); NOTNULL(latents); NOTNULL(context); NOTNULL(time_emb); NOTNULL(hint); NOTNULL(scale); NOTNULL(eps_out);
   if (!is_full_unet_kind(unet->kind)) TSD_FAIL(TSD_E_ARG, "controlled forward: the UNet must be a full-size kind (the Tiny-SD graph has no ControlNet)");
   TSD_TRY(cn_check(cn, B, LH, LW, T));
+  if (model_context_width(unet) != model_context_width(cn))
+    TSD_FAIL(TSD_E_ARG, "controlled forward: the ControlNet kinds are SD-1.x networks (context width %d); this UNet reads a %d-wide context",
+             model_context_width(cn), model_context_width(unet));
   if (unet->ctx != cn->ctx) TSD_FAIL(TSD_E_ARG, "controlled forward: the UNet and the ControlNet belong to different contexts (the residuals live in one arena)");
   for (int b = 0; b < B; b++)
     if (!(fabsf(scale[b]) <= 3.4028235e38f)) TSD_FAIL(TSD_E_ARG, "controlled forward: scale[%d] is not finite", b);
@@ -158,7 +162,7 @@ extern "C" int tsd_diffusion_forward_control_hw(tsd_model* unet, tsd_model* cn, 
   TSD_TRY(model_check_ready(cn));
   return run_model(unet, [&]() -> int {
     CnInputs in;
-    TSD_TRY(cn_upload(ctx, latents, context, time_emb, hint, B, LH, LW, T, &in));
+    TSD_TRY(cn_upload(ctx, latents, context, time_emb, hint, B, LH, LW, T, model_context_width(cn), &in));
     const int64_t nl = (int64_t)B * 4 * LH * LW;
     float* ds = arena_alloc<float>(ctx, B);
     float* de = arena_alloc<float>(ctx, nl);
@@ -224,7 +228,7 @@ extern "C" int tsd_clip_forward(tsd_model* m, const int32_t* tokens, int B, int 
   for (int b = 0; b < B; b++)
     for (int t = 0; t < T; t++) padded[(size_t)b * 77 + t] = tokens[(size_t)b * T + t];
   return run_model(m, [&]() -> int {
-    const int64_t no = (int64_t)B * 77 * 768;
+    const int64_t no = (int64_t)B * 77 * m->clip.D;
     int* dt = arena_alloc<int>(ctx, (int64_t)B * 77);
     float* dout = arena_alloc<float>(ctx, no);
     if (!dt || !dout) TSD_FAIL(TSD_E_ALLOC, "workspace arena exhausted");
@@ -232,6 +236,13 @@ extern "C" int tsd_clip_forward(tsd_model* m, const int32_t* tokens, int B, int 
     TSD_TRY(g_clip_forward(m, dt, B, dout));
     return d2h(ctx, context, dout, no * 4);
   });
+}
+
+extern "C" int tsd_model_context_width(const tsd_model* m) {
+  if (!m) TSD_FAIL(TSD_E_ARG, "NULL model");
+  const int w = model_context_width(m);
+  if (w <= 0) TSD_FAIL(TSD_E_ARG, "tsd_model_context_width: model kind %d neither reads nor writes a context", m->kind);
+  return w;
 }
 
 // ---- RCCL weight broadcast over xGMI ---------------------------------------

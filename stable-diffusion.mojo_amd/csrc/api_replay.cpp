@@ -479,7 +479,7 @@ int ad_extents(const int64_t* d, int64_t* e) {
   for (int i = 0; i < TSD_AO_COUNT; i++) e[i] = 0;
 #define AD_REQ(cond) \
   if (!(cond)) TSD_FAIL(TSD_E_ARG, "attn_run: descriptor cannot be sized (%s)", #cond)
-  AD_REQ(d[TSD_AD_VERSION] == TSD_AD_VERSION_1);
+  AD_REQ(d[TSD_AD_VERSION] == TSD_AD_VERSION_1 || d[TSD_AD_VERSION] == TSD_AD_VERSION_2);
   const int64_t mode = d[TSD_AD_MODE], lim = 1LL << 28;
   AD_REQ(mode == TSD_AM_ATTN || mode == TSD_AM_SOFTMAX_ROWS);
   if (mode == TSD_AM_ATTN) {
@@ -522,9 +522,11 @@ extern "C" int tsd_debug_attn_run(tsd_ctx* ctx, const int64_t* desc, int n, cons
   TSD_TRY(ad_extents(desc, ext));
   const int64_t* d = desc;
   const bool attn = d[TSD_AD_MODE] == TSD_AM_ATTN;
+  // head dimension 64 came with version 2: a version-1 descriptor is sized and refused as it was before the d = 64 kernel existed
+  const bool v1_d64 = attn && d[TSD_AD_VERSION] == TSD_AD_VERSION_1 && d[TSD_AD_D] == 64;
   if (info) for (int i = 0; i < TSD_AI_COUNT; i++) info[i] = 0;
   if (!host_in) {  // sizing only: no context or device needed; the dispatcher's choice under the default options
-    if (info && attn && attn_fused_supported((int)d[TSD_AD_D]) && d[TSD_AD_SQ] > 0 && d[TSD_AD_SK] > 0) {
+    if (info && attn && !v1_d64 && attn_fused_supported((int)d[TSD_AD_D]) && d[TSD_AD_SQ] > 0 && d[TSD_AD_SK] > 0) {
       TsdOptions o;
       o.attn_qb_force = (int)d[TSD_AD_KERNEL]; o.attn_diag = (int)d[TSD_AD_DIAG];
       const AttnPlan p = attn_plan(o, (int)d[TSD_AD_B], (int)d[TSD_AD_H], (int)d[TSD_AD_D], (int)d[TSD_AD_SQ], (int)d[TSD_AD_SK]);
@@ -556,7 +558,10 @@ extern "C" int tsd_debug_attn_run(tsd_ctx* ctx, const int64_t* desc, int n, cons
     a.O = (half_t*)ops.at(TSD_AO_O); a.ldo = (int)d[TSD_AD_LDO]; a.sO = d[TSD_AD_SOB];
     a.B = (int)d[TSD_AD_B]; a.H = (int)d[TSD_AD_H]; a.d = (int)d[TSD_AD_D]; a.Sq = (int)d[TSD_AD_SQ]; a.Sk = (int)d[TSD_AD_SK];
     a.scale = f32_of(d[TSD_AD_SCALE]);
-    r = run_planned(ctx, [&]() -> int { return launch_flash_attention(ctx, a); });
+    r = run_planned(ctx, [&]() -> int {
+      if (v1_d64) TSD_FAIL(TSD_E_SHAPE, "flash attention: head dim %d unsupported", a.d);
+      return launch_flash_attention(ctx, a);
+    });
   } else {
     const int64_t rows = d[TSD_AD_ROWS];
     const int cols = (int)d[TSD_AD_COLS], ld = (int)d[TSD_AD_LD];

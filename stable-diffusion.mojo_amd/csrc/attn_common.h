@@ -33,6 +33,14 @@ struct AttnK {
 #define TSD_ATTN_CHECK_EVERY 8  // key tiles between two looks at the row sums in the optimistic softmax pass (early abort)
 #endif
 
+// Workgroups per CU that flash_attn_kernel<64, 1> is compiled for (second __launch_bounds__ argument).  From the compiler's register
+// table: unconstrained the kernel takes 151 VGPRs and no scratch; held to 4 workgroups (4 waves per SIMD, 128 VGPRs) it spills 17
+// registers into 60 bytes of scratch, which no MFMA kernel here may do; 3 workgroups (3 waves per SIMD, 168 VGPRs) is what 151 registers
+// allow, and 3 x 34 832 B of LDS fit the CU's 160 KiB.
+#ifndef TSD_ATTN64_WGS
+#define TSD_ATTN64_WGS 3
+#endif
+
 // An (empty) use of a 16-register block.  A device function, so the host pass never sees the "v" constraint.
 __device__ __forceinline__ void keep_alive(const f16v& v) { asm volatile("" ::"v"(v)); }
 

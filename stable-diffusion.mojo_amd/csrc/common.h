@@ -355,6 +355,7 @@ int launch_softmax_rows_f16_causal(tsd_ctx* ctx, half_t* x, int64_t rows, int co
 int launch_clip_embed(tsd_ctx* ctx, const int* tokens, const half_t* table, int n_vocab, int D, const float* pos, int B,
                       int T, half_t* y);
 int launch_quick_gelu_f16(tsd_ctx* ctx, half_t* x, int64_t n);
+int launch_gelu_erf_f16(tsd_ctx* ctx, half_t* x, int64_t n);  // torch's exact GELU in place (the SD-2.x text encoder's MLP)
 int launch_time_embedding(tsd_ctx* ctx, const float* t_dev, float t_scalar, int B, float* out);  // out [B][320]; t_dev NULL -> scalar
 int launch_small_linear(tsd_ctx* ctx, const float* x, int B, int K, int ldx, const half_t* w, int ldw, const float* bias,
                         int N, int silu_in, float* y, int ldy);
@@ -568,7 +569,7 @@ int launch_groupnorm(tsd_ctx* ctx, const NormSrc& src, int B, int HW, int C, int
 int launch_layernorm(tsd_ctx* ctx, const half_t* x, int64_t rows, int C, int ldx, float eps, half_t* y, int ldy,
                      const NormAffine* aff = nullptr);
 
-// attention (kernels_attn.hip): fused flash attention for d_head in {40, 80, 160}.
+// attention (kernels_attn.hip): fused flash attention for d_head in {40, 64, 80, 160}.
 struct AttnArgs {
   const half_t* Q = nullptr; int ldq = 0; int64_t sQ = 0;    // Q[b][s][h*d + j]
   const half_t* K = nullptr; int ldk = 0; int64_t sK = 0;    // K[b][t][h*d + j]

@@ -193,7 +193,7 @@ int g_unet_attn(tsd_ctx* ctx, const Act& x, const AttnW& w, const half_t* ctx16,
   const int C = w.C, B = x.B, S = x.H * x.W, d = w.n_embed, Hh = w.n_head;
   const int64_t M = (int64_t)B * S;
   if (C % 64 || x.C != C) TSD_FAIL(TSD_E_SHAPE, "attention block: C=%d (input %d) unsupported", C, x.C);
-  if (!attn_fused_supported(d)) TSD_FAIL(TSD_E_SHAPE, "attention block: head dim %d unsupported (40/80/160)", d);
+  if (!attn_fused_supported(d)) TSD_FAIL(TSD_E_SHAPE, "attention block: head dim %d unsupported (40/64/80/160)", d);
   if (S % 4) TSD_FAIL(TSD_E_SHAPE, "attention block: H*W=%d must be a multiple of 4", S);
   const size_t mark = ctx->arena.mark();
   const float scale = 1.f / sqrtf((float)d);  // helpers/attention.mojo:57-58
@@ -356,9 +356,12 @@ int g_unet_attn(tsd_ctx* ctx, const Act& x, const AttnW& w, const half_t* ctx16,
 // head dims, otherwise (one head, d % 64 == 0: the VAE's 512-wide head) scores are materialised like the
 // reference does (helpers/attention.mojo:46) - batched GEMM -> row softmax -> batched GEMM.
 int g_attn_core(tsd_ctx* ctx, const AttnArgs& fa) {
-  if (attn_fused_supported(fa.d)) return launch_flash_attention(ctx, fa);
-  if (fa.H != 1 || fa.d % 64 || fa.Sk % 64)
-    TSD_FAIL(TSD_E_SHAPE, "attention: heads=%d d_head=%d Tk=%d unsupported (fused: d in {40,80,160}; unfused: 1 head, "
+  // one head of a width that is a multiple of 64 over whole key tiles went unfused before the d = 64 kernel existed (the VAE's 512-wide
+  // head, a single 64-wide head) and still does: looked at first, so those calls keep their launches and bits
+  const bool unfused = fa.H == 1 && fa.d % 64 == 0 && fa.Sk % 64 == 0;
+  if (!unfused && attn_fused_supported(fa.d)) return launch_flash_attention(ctx, fa);
+  if (!unfused)
+    TSD_FAIL(TSD_E_SHAPE, "attention: heads=%d d_head=%d Tk=%d unsupported (fused: d in {40,64,80,160}; unfused: 1 head, "
              "d%%64==0, Tk%%64==0)", fa.H, fa.d, fa.Sk);
   const int B = fa.B, Sq = fa.Sq, Sk = fa.Sk, C = fa.d;
   const size_t mark = ctx->arena.mark();
@@ -620,14 +623,15 @@ static int unet_full_steps(const FullRun& f, int i0, int i1, Act& cur, std::vect
   const UNetW& u = m->unet;
   const int B = f.B, CK = u.kproj_all.N;
   for (int i = i0; i < i1; i++) {
-    const UNetStep& st = SD15_STEPS[i];
+    const UNetStep* steps = full_unet_steps(m->kind);  // (a ControlNet: SD15_STEPS; the tables differ in the attention blocks' head split only)
+    const UNetStep& st = steps[i];
     const LayerDef& l = st.l;
     // the next consumer of every layer output starts with GroupNorm(32) (the output layer's has 320 groups)
     const int next_groups = i == SD15_N - 1 ? u.final_groups : 32;
     // a decoder layer whose output meets a narrower skip in the next residual block's concat emits its statistics in the skip's
     // granularity (concat_stat_groups), so that block's first GroupNorm needs no statistics pass
     auto stat_groups = [&](int C) -> int {
-      if (i + 1 < SD15_N && SD15_STEPS[i + 1].l.kind == L_RES && (SD15_STEPS[i + 1].flags & U_POP) && !(st.flags & U_PUSH) && !skips.empty())
+      if (i + 1 < SD15_N && steps[i + 1].l.kind == L_RES && (steps[i + 1].flags & U_POP) && !(st.flags & U_PUSH) && !skips.empty())
         return concat_stat_groups(C, skips.back().C, 32);
       return next_groups;
     };
@@ -941,13 +945,13 @@ int g_encoder_forward(tsd_model* m, const float* images_chw, const float* noise_
   return TSD_OK;
 }
 
-// `CLIP.forward` clip.mojo:90-109 on device token ids [B][77] -> fp32 [B][77][768].
-// 77 tokens x 12 heads of 64: the attention core runs unfused per sample (head-batched score GEMM -> masked row
+// `CLIP.forward` clip.mojo:90-109 on device token ids [B][77] -> fp32 [B][77][D].
+// 77 tokens x 12 heads of 64 (16 heads, 23 layers and erf-GELU for the SD-2.x encoder): the attention core runs unfused per sample (head-batched score GEMM -> masked row
 // softmax -> head-batched P.V GEMM with keys zero-padded to 128); it is executed once per prompt, off the denoise loop.
 int g_clip_forward(tsd_model* m, const int* tokens_dev, int B, float* out_f32) {
   tsd_ctx* ctx = m->ctx;
   const ClipW& c = m->clip;
-  const int T = 77, D = 768, H = 12, dh = 64, Tp = 128;
+  const int T = 77, D = c.D, H = c.H, dh = 64, Tp = 128;  // 768 / 12, or 1024 / 16 (TSD_MODEL_CLIP_SD2)
   const int64_t M = (int64_t)B * T;
   half_t* x = arena_alloc<half_t>(ctx, M * D); CHECK_ALLOC(x);
   half_t* x2 = arena_alloc<half_t>(ctx, M * D); CHECK_ALLOC(x2);
@@ -966,13 +970,13 @@ int g_clip_forward(tsd_model* m, const int* tokens_dev, int B, float* out_f32) {
   TSD_TRY(zero_async(ctx, vt, (size_t)B * D * Tp * sizeof(half_t)));  // key padding 77..127 stays zero
   TSD_TRY(launch_clip_embed(ctx, tokens_dev, c.tok, 49408, D, c.pos, B, T, x));  // clip.mojo:17-20
   CatSrc a;
-  for (int l = 0; l < 12; l++) {
+  for (int l = 0; l < c.n_layer; l++) {
     const ClipLayerW& w = c.layer[l];
     // ---- LN -> causal self-attention -> + residue (clip.mojo:37-43) ----
     TSD_TRY(launch_layernorm(ctx, x, M, D, D, 1e-5f, ln, D, w.ln1.w ? &w.ln1 : nullptr));
     a.p0 = ln; a.ld0 = D; a.C0 = D;
     TSD_TRY(g_linear(ctx, a, M, w.in_proj.w, w.in_proj.Kpad, 2 * D, D, w.in_proj.b, nullptr, 0, 0, qk, 2 * D));  // q, k
-    {  // V^T[b] = W_v . ln_b^T + b_v  -> [B][768][128]
+    {  // V^T[b] = W_v . ln_b^T + b_v  -> [B][D][128]
       GemmArgs g;
       g.A0 = w.in_proj.w + (int64_t)2 * D * w.in_proj.Kpad; g.lda0 = w.in_proj.Kpad; g.sA = 0;
       g.Wt = ln; g.ldw = D; g.sW = (int64_t)T * D;
@@ -1003,7 +1007,8 @@ int g_clip_forward(tsd_model* m, const int* tokens_dev, int B, float* out_f32) {
     TSD_TRY(launch_layernorm(ctx, x2, M, D, D, 1e-5f, ln, D, w.ln2.w ? &w.ln2 : nullptr));
     a.p0 = ln;
     TSD_TRY(g_linear(ctx, a, M, w.l4.w, w.l4.Kpad, 4 * D, D, w.l4.b, nullptr, 0, 0, ff, 4 * D));
-    TSD_TRY(launch_quick_gelu_f16(ctx, ff, M * 4 * D));
+    if (c.gelu_erf) TSD_TRY(launch_gelu_erf_f16(ctx, ff, M * 4 * D));
+    else TSD_TRY(launch_quick_gelu_f16(ctx, ff, M * 4 * D));
     a.p0 = ff; a.ld0 = 4 * D; a.C0 = 4 * D;
     TSD_TRY(g_linear(ctx, a, M, w.l5.w, w.l5.Kpad, D, 4 * D, w.l5.b, x2, D, 0, x, D));
   }

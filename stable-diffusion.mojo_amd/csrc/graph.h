@@ -67,7 +67,7 @@ int g_attn_core(tsd_ctx* ctx, const AttnArgs& fa);
 int g_qkv_proj(tsd_ctx* ctx, const half_t* x, int B, int S, int C, const LinW& in_proj, half_t* qk, half_t* vt, int Sp);
 
 // module forwards on device buffers
-// latents: fp32 CHW [B,4,LH,LW]; context16: fp16 [B][Tp][768]; temb: fp32 [B][320]; eps_out: fp32 CHW [B,4,LH,LW]
+// latents: fp32 CHW [B,4,LH,LW]; context16: fp16 [B][Tp][W], W = model_context_width(m) (768; 1024 for the SD-2.x UNet); temb: fp32 [B][320]; eps_out: fp32 CHW [B,4,LH,LW]
 // eps_nhwc: eps_out receives the output convolution's own layout, fp32 [B][LH*LW][4], instead of CHW (the denoise session's DDPM update
 // reads it directly: one conversion launch per step less)
 // pre: what the forward computes from the timestep and the context alone, made ahead by the caller (the denoise session keeps both
@@ -110,5 +110,5 @@ int run_planned(tsd_ctx* ctx, F&& fn) {
   a.top = 0;
   return r;
 }
-// tokens: device int32 [B][77]; out: device fp32 [B][77][768]
+// tokens: device int32 [B][77]; out: device fp32 [B][77][D], D = the encoder's width (768; 1024 for TSD_MODEL_CLIP_SD2)
 int g_clip_forward(tsd_model* m, const int* tokens_dev, int B, float* out_f32);

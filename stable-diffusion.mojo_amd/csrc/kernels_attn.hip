@@ -57,7 +57,7 @@ __device__ unsigned long long g_attn_ts[4 * 65536];  // per block: memtime start
 // that at the price of 2 waves per SIMD instead of 4.
 
 template <int D, int QB>
-__global__ __launch_bounds__(256, D == 40 ? 6 - 2 * QB : 2) void flash_attn_kernel(const AttnK p) {
+__global__ __launch_bounds__(256, D == 40 ? 6 - 2 * QB : D == 64 ? TSD_ATTN64_WGS : 2) void flash_attn_kernel(const AttnK p) {
   constexpr int NST = 2;                   // K / V^T tile buffers
   constexpr int DCH = D / 8;               // 16-B chunks per K row
   constexpr int KSTEPS = (DCH + 1) / 2;    // QK^T k-steps (16 wide)
@@ -240,6 +240,13 @@ __global__ __launch_bounds__(256, D == 40 ? 6 - 2 * QB : 2) void flash_attn_kern
   // query block - raises a flag in LDS in front of the tile's barrier, and all waves leave together behind it.  Same decision as
   // the final check (an inf never leaves the sum), so the results are the ones of the unabridged pass; d = 160 (no ones row, at most
   // 4 tiles at the 16x16 level) keeps the final check only.
+  // d = 64 (no spare V^T row either, but key loops of 64 and 144 tiles) looks at an O accumulator instead.  An fp16 P = +inf of query q is
+  // multiplied with V^T[j][k] for EVERY channel j of the head (all 64 rows of the two d blocks are real channels): inf x v is +-inf, or NaN
+  // at v = 0, in each of the row's accumulators; the optimistic pass never rescales O after tile 0 and inf + x / NaN + x stay inf / NaN, so
+  // accumulator 0 of a lane (channel 0 or 4 of query l31, in both lane halves) is non-finite from the overflowing tile on.  The final check
+  // below repeats exactly when some accumulator or row sum is non-finite (an infinite fp32 P is an infinite fp16 P), so an early hit is a
+  // final hit: the abort changes no result, it only saves the rest of a pass whose result is discarded.
+  constexpr bool EARLY = ONES_ROW || D == 64;
   constexpr int CHECK_EVERY = TSD_ATTN_CHECK_EVERY;  // (a huge value = the round-4 behaviour: final check only; for same-box A/B builds)
   if (tid == 0) *(volatile int*)(smem + FLAG_OFF) = 0;  // published by run()'s first barrier
   auto run = [&](auto exact_c) {
@@ -415,12 +422,15 @@ __global__ __launch_bounds__(256, D == 40 ? 6 - 2 * QB : 2) void flash_attn_kern
 #elif TSD_ATTN_ABL & 64 // ablation: neither the DMA wait nor the barrier
 #else
     // (the EXACT pass never consults the flag - `check` is false there - so the word needs no reset between the passes: ADVICE r05)
-    const bool check = !EXACT && ONES_ROW && (t % CHECK_EVERY) == CHECK_EVERY - 1 && t + 1 < ntiles;  // uniform
-    if constexpr (!EXACT && ONES_ROW) {
+    const bool check = !EXACT && EARLY && (t % CHECK_EVERY) == CHECK_EVERY - 1 && t + 1 < ntiles;  // uniform
+    if constexpr (!EXACT && EARLY) {
       if (check) {
         bool over = false;
 #pragma unroll
-        for (int qb = 0; qb < QB; qb++) over = over || !(o[qb][L_BLK][L_REG] < 1.0e37f);  // inf / NaN (the hi = 1 lanes hold a pad row: 0, or NaN next to an inf P)
+        for (int qb = 0; qb < QB; qb++) {
+          if constexpr (ONES_ROW) over = over || !(o[qb][L_BLK][L_REG] < 1.0e37f);  // inf / NaN (the hi = 1 lanes hold a pad row: 0, or NaN next to an inf P)
+          else over = over || !(fabsf(o[qb][0][0]) < 1.0e37f);                      // +-inf / NaN in a real channel of the row (see above)
+        }
         if (__any(over) && lane == 0) *(volatile int*)(smem + FLAG_OFF) = 1;
       }
     }
@@ -493,7 +503,7 @@ __global__ __launch_bounds__(256, D == 40 ? 6 - 2 * QB : 2) void flash_attn_kern
   }
 }
 
-bool attn_fused_supported(int d) { return d == 40 || d == 80 || d == 160; }
+bool attn_fused_supported(int d) { return d == 40 || d == 64 || d == 80 || d == 160; }
 // per-context switches (TsdOptions): attn_diag 0 = optimistic reference from key tile 0 only (the round-2 behaviour);
 // attn_qb_force 0 = kernel chosen by the layer shape, 1 / 2 = that many query blocks per wave (4-wave workgroups) whenever d = 40,
 // 3 = the 8-wave two-group kernel whenever d = 40
@@ -540,6 +550,7 @@ AttnPlan attn_plan(const TsdOptions& opt, int B, int H, int d, int Sq, int Sk) {
       else p.kernel = 1;
       break;
     case 80: p.kernel = 4; break;
+    case 64: p.kernel = 6; break;  // TSD_AK_64: 32 queries per wave at every shape, so a sample alone runs what its row of a batch runs
     default: p.kernel = 5; break;
   }
   return p;
@@ -567,6 +578,7 @@ int launch_flash_attention(tsd_ctx* ctx, const AttnArgs& a) {
     case 2: return launch_fa<40, 2>(ctx, k, a.B, a.H, a.Sq);
     case 1: return launch_fa<40, 1>(ctx, k, a.B, a.H, a.Sq);
     case 4: return launch_fa<80, 1>(ctx, k, a.B, a.H, a.Sq);
+    case 6: return launch_fa<64, 1>(ctx, k, a.B, a.H, a.Sq);
     default: return launch_fa<160, 1>(ctx, k, a.B, a.H, a.Sq);
   }
 }

@@ -621,6 +621,25 @@ int launch_geglu_erf_f16(tsd_ctx* ctx, const half_t* x, int64_t rows, int n_out,
   HIP_TRY(hipGetLastError());
   return TSD_OK;
 }
+// ---- OpenCLIP text encoder (SD-2.x): torch's exact GELU 0.5 x (1 + erf(x / sqrt 2)) in place on fp16, the pass launch_quick_gelu_f16 is
+// for the SD-1.x encoder (same launch shape: 8 elements per thread, n % 8 == 0) ----
+__global__ __launch_bounds__(256) void k_gelu_erf_f16(half_t* __restrict__ x, int64_t n8) {
+  typedef _Float16 h8v __attribute__((ext_vector_type(8)));
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n8) return;
+  h8v v = *(const h8v*)(x + i * 8);
+#pragma unroll
+  for (int j = 0; j < 8; j++) v[j] = (half_t)gelu_erf_f((float)v[j]);
+  *(h8v*)(x + i * 8) = v;
+}
+int launch_gelu_erf_f16(tsd_ctx* ctx, half_t* x, int64_t n) {
+  if (n % 8) TSD_FAIL(TSD_E_SHAPE, "gelu_erf: n must be a multiple of 8");
+  if (!ctx->launch()) return TSD_OK;
+  ProfScope prof(ctx, KC_ELEMENTWISE);
+  hipLaunchKernelGGL(k_gelu_erf_f16, dim3((unsigned)((n / 8 + 255) / 256)), dim3(256), 0, ctx->stream, x, n / 8);
+  HIP_TRY(hipGetLastError());
+  return TSD_OK;
+}
 __global__ void k_add_const(float* __restrict__ dst, int64_t n, float c) {
   for (int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
     dst[i] = __fadd_rn(dst[i], c);

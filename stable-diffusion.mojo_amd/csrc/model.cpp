@@ -176,7 +176,7 @@ static size_t packed_bytes(const ParamSpec& p) {
 
 extern "C" int tsd_model_create(tsd_ctx* ctx, int kind, tsd_model** out) {
   if (!ctx || !out) TSD_FAIL(TSD_E_ARG, "tsd_model_create: NULL argument");
-  if (kind < TSD_MODEL_DIFFUSION || kind > TSD_MODEL_KIND_MAX) TSD_FAIL(TSD_E_ARG, "bad model kind %d", kind);
+  if (!is_model_kind(kind)) TSD_FAIL(TSD_E_ARG, "bad model kind %d", kind);
   tsd_model* m = new tsd_model();
   m->ctx = ctx;
   m->kind = kind;
@@ -830,7 +830,7 @@ int model_resolve(tsd_model* m) {
     int toff = 0, kvoff = 0;
     bool first = true;
     for (int i = 0; i < n_layers; i++) {
-      const LayerDef& l = full ? SD15_STEPS[i].l : UNET_LAYERS[i];
+      const LayerDef& l = full ? full_unet_steps(m->kind)[i].l : UNET_LAYERS[i];
       const std::string n = "unet.layer" + std::to_string(i + 1);
       if (l.kind == L_RES) {
         ResW& r = u.res[i];
@@ -852,6 +852,7 @@ int model_resolve(tsd_model* m) {
         a.ca_q = model_lin(m, n + ".layer6.q_proj", false);
         a.ca_k = model_lin(m, n + ".layer6.k_proj", false);
         a.ca_v = model_lin(m, n + ".layer6.v_proj", false);
+        a.d_ctx = a.ca_k.K;
         a.ca_out = model_lin(m, n + ".layer6.out_proj", true);
         a.geglu1 = model_lin(m, n + ".layer8", true);
         a.geglu2 = model_lin(m, n + ".layer9", true);
@@ -887,7 +888,7 @@ int model_resolve(tsd_model* m) {
     ClipW& c = m->clip;
     auto aff = [&](const std::string& name) {
       NormAffine a;
-      if (m->kind == TSD_MODEL_CLIP_TORCH) {
+      if (is_torch_clip_kind(m->kind)) {
         a.w = (const float*)(m->blob + m->params[m->index.at(name + ".weight")].off);
         a.b = (const float*)(m->blob + m->params[m->index.at(name + ".bias")].off);
         a.torch_rstd = 1;
@@ -897,7 +898,9 @@ int model_resolve(tsd_model* m) {
     c.final_ln = aff("layernorm");
     c.tok = (const half_t*)(m->blob + m->params[m->index.at("embedding.token.weight")].off);
     c.pos = (const float*)(m->blob + m->params[m->index.at("embedding.position")].off);
-    for (int i = 0; i < 12; i++) {
+    c.D = clip_kind_width(m->kind); c.H = c.D / 64; c.n_layer = clip_kind_layers(m->kind);
+    c.gelu_erf = m->kind == TSD_MODEL_CLIP_SD2;
+    for (int i = 0; i < c.n_layer; i++) {
       const std::string n = "player" + std::to_string(i + 1);
       c.layer[i].in_proj = model_lin(m, n + ".layer2.in_proj", true);
       c.layer[i].out_proj = model_lin(m, n + ".layer2.out_proj", true);

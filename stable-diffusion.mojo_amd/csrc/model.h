@@ -39,9 +39,16 @@ enum { U_POP = 1, U_PUSH = 2 };  // input = concat(x, popped skip) ; output push
 struct UNetStep { LayerDef l; int flags; };
 constexpr int SD15_N = 45;
 extern const UNetStep SD15_STEPS[SD15_N];
-static inline bool is_full_unet_kind(int kind) { return kind == TSD_MODEL_DIFFUSION_SD15 || kind == TSD_MODEL_DIFFUSION_SD15_TORCH; }
+// SD-2.x UNet (TSD_MODEL_DIFFUSION_SD2): SD15_STEPS with every attention block {L_ATTN, C / 64, 64} - the same kinds, widths and flags
+extern const UNetStep SD2_STEPS[SD15_N];
+static inline bool is_sd2_unet_kind(int kind) { return kind == TSD_MODEL_DIFFUSION_SD2; }
+static inline const UNetStep* full_unet_steps(int kind) { return is_sd2_unet_kind(kind) ? SD2_STEPS : SD15_STEPS; }
+static inline bool is_full_unet_kind(int kind) {
+  return kind == TSD_MODEL_DIFFUSION_SD15 || kind == TSD_MODEL_DIFFUSION_SD15_TORCH || kind == TSD_MODEL_DIFFUSION_SD2;
+}
 static inline bool is_diffusion_kind(int kind) { return kind == TSD_MODEL_DIFFUSION || is_full_unet_kind(kind); }
-static inline bool is_clip_kind(int kind) { return kind == TSD_MODEL_CLIP || kind == TSD_MODEL_CLIP_TORCH; }
+static inline bool is_clip_kind(int kind) { return kind == TSD_MODEL_CLIP || kind == TSD_MODEL_CLIP_TORCH || kind == TSD_MODEL_CLIP_SD2; }
+static inline bool is_torch_clip_kind(int kind) { return kind == TSD_MODEL_CLIP_TORCH || kind == TSD_MODEL_CLIP_SD2; }
 static inline bool is_decoder_kind(int kind) { return kind == TSD_MODEL_DECODER || kind == TSD_MODEL_DECODER_TORCH; }
 static inline bool is_encoder_kind(int kind) { return kind == TSD_MODEL_ENCODER || kind == TSD_MODEL_ENCODER_TORCH; }
 static inline bool is_vae_torch_kind(int kind) { return kind == TSD_MODEL_DECODER_TORCH || kind == TSD_MODEL_ENCODER_TORCH; }
@@ -52,8 +59,13 @@ constexpr int CN_HINT_N = 8;
 struct HintConvDef { int cin, cout, stride; };
 extern const HintConvDef CN_HINT_CONVS[CN_HINT_N];
 static inline bool is_controlnet_kind(int kind) { return kind == TSD_MODEL_CONTROLNET_SD15 || kind == TSD_MODEL_CONTROLNET_SD15_TORCH; }
-static inline bool is_torch_unet_kind(int kind) { return kind == TSD_MODEL_DIFFUSION_SD15_TORCH || kind == TSD_MODEL_CONTROLNET_SD15_TORCH; }
-constexpr int TSD_MODEL_KIND_MAX = TSD_MODEL_CONTROLNET_SD15_TORCH;
+static inline bool is_torch_unet_kind(int kind) {
+  return kind == TSD_MODEL_DIFFUSION_SD15_TORCH || kind == TSD_MODEL_CONTROLNET_SD15_TORCH || kind == TSD_MODEL_DIFFUSION_SD2;
+}
+// 1 .. 11 and 16, 17; 12 .. 15 are reserved and refused
+static inline bool is_model_kind(int kind) {
+  return (kind >= TSD_MODEL_DIFFUSION && kind <= TSD_MODEL_CONTROLNET_SD15_TORCH) || kind == TSD_MODEL_DIFFUSION_SD2 || kind == TSD_MODEL_CLIP_SD2;
+}
 
 std::vector<ParamSpec> build_param_specs(int model_kind);
 
@@ -127,10 +139,13 @@ struct VaeW {
 };
 
 struct ClipLayerW { LinW in_proj, out_proj, l4, l5; NormAffine ln1, ln2; };  // ClipPlayer clip.mojo:23-34 (its LayerNorms have no parameters)
+constexpr int CLIP_MAX_LAYERS = 23;
 struct ClipW {
-  const half_t* tok = nullptr;  // [49408][768] fp16
-  const float* pos = nullptr;   // [77][768] fp32
-  ClipLayerW layer[12];
+  int D = 768, H = 12, n_layer = 12;  // width, heads (of 64) and layers: 1024 / 16 / 23 for TSD_MODEL_CLIP_SD2
+  bool gelu_erf = false;              // the MLP's activation: quick-GELU (clip.mojo:49-50), or torch's exact GELU (OpenCLIP)
+  const half_t* tok = nullptr;  // [49408][D] fp16
+  const float* pos = nullptr;   // [77][D] fp32
+  ClipLayerW layer[CLIP_MAX_LAYERS];
   NormAffine final_ln;  // torch-norm extension (kind 7)
 };
 
@@ -163,3 +178,10 @@ int model_resolve(tsd_model* m);                      // fill unet / vae from th
 ConvW model_conv(const tsd_model* m, const std::string& prefix);
 LinW model_lin(const tsd_model* m, const std::string& prefix, bool use_bias);
 int model_check_ready(tsd_model* m);
+// width of the context rows: what a UNet / ControlNet's k_proj reads, what a text encoder writes; 0 for a VAE
+static inline int model_context_width(const tsd_model* m) {
+  if (is_diffusion_kind(m->kind) || is_controlnet_kind(m->kind)) return m->unet.kproj_all.K;
+  return is_clip_kind(m->kind) ? m->clip.D : 0;
+}
+static inline int clip_kind_width(int kind) { return kind == TSD_MODEL_CLIP_SD2 ? 1024 : 768; }
+static inline int clip_kind_layers(int kind) { return kind == TSD_MODEL_CLIP_SD2 ? 23 : 12; }

@@ -30,6 +30,22 @@ const UNetStep SD15_STEPS[SD15_N] = {
     R(1920, 640, U_POP), A(80, 0), R(1280, 640, U_POP), A(80, 0), R(960, 640, U_POP), A(80, 0),
     {{L_UPCONV, 640, 640, 3, 1}, 0},
     R(960, 320, U_POP), A(40, 0), R(640, 320, U_POP), A(40, 0), R(640, 320, U_POP), A(40, 0)};
+#undef A
+// SD-2.x: the same steps with head dimension 64 in every attention block (5 / 10 / 20 heads)
+#define A(dh, f) {{L_ATTN, 8 * dh / 64, 64, 0, 0}, f}
+const UNetStep SD2_STEPS[SD15_N] = {
+    {{L_CONV, 4, 320, 3, 1}, U_PUSH},
+    R(320, 320, 0), A(40, U_PUSH), R(320, 320, 0), A(40, U_PUSH), {{L_CONV, 320, 320, 3, 2}, U_PUSH},
+    R(320, 640, 0), A(80, U_PUSH), R(640, 640, 0), A(80, U_PUSH), {{L_CONV, 640, 640, 3, 2}, U_PUSH},
+    R(640, 1280, 0), A(160, U_PUSH), R(1280, 1280, 0), A(160, U_PUSH), {{L_CONV, 1280, 1280, 3, 2}, U_PUSH},
+    R(1280, 1280, U_PUSH), R(1280, 1280, U_PUSH),
+    R(1280, 1280, 0), A(160, 0), R(1280, 1280, 0),  // bottleneck
+    R(2560, 1280, U_POP), R(2560, 1280, U_POP), R(2560, 1280, U_POP), {{L_UPCONV, 1280, 1280, 3, 1}, 0},
+    R(2560, 1280, U_POP), A(160, 0), R(2560, 1280, U_POP), A(160, 0), R(1920, 1280, U_POP), A(160, 0),
+    {{L_UPCONV, 1280, 1280, 3, 1}, 0},
+    R(1920, 640, U_POP), A(80, 0), R(1280, 640, U_POP), A(80, 0), R(960, 640, U_POP), A(80, 0),
+    {{L_UPCONV, 640, 640, 3, 1}, 0},
+    R(960, 320, U_POP), A(40, 0), R(640, 320, U_POP), A(40, 0), R(640, 320, U_POP), A(40, 0)};
 #undef R
 #undef A
 
@@ -135,17 +151,19 @@ std::vector<ParamSpec> build_param_specs(int kind) {
   } else if (is_full_unet_kind(kind)) {  // same blocks, full layer list; names "unet.layerN" by flat position
     b.lin("time_embed.layer1", 320, 1280);
     b.lin("time_embed.layer2", 1280, 1280);
+    const UNetStep* steps = full_unet_steps(kind);
+    const int dctx = is_sd2_unet_kind(kind) ? 1024 : 768;  // OpenCLIP-H states for SD-2.x
     for (int i = 0; i < SD15_N; i++) {
-      const LayerDef& l = SD15_STEPS[i].l;
+      const LayerDef& l = steps[i].l;
       const std::string n = "unet.layer" + std::to_string(i + 1);
       if (l.kind == L_CONV || l.kind == L_UPCONV) b.conv(n, l.a, l.b, l.c);
       else if (l.kind == L_RES) b.unet_res(n, l.a, l.b);
-      else if (l.kind == L_ATTN) b.unet_attn(n, l.a, l.b);
+      else if (l.kind == L_ATTN) b.unet_attn(n, l.a, l.b, dctx);
     }
     b.conv("final.layer2", 320, 4, 3, true, true);
-    if (kind == TSD_MODEL_DIFFUSION_SD15_TORCH) {  // norm parameters appended, so the shared indices equal kind 5's
+    if (is_torch_unet_kind(kind)) {  // norm parameters appended, so the shared indices equal kind 5's
       for (int i = 0; i < SD15_N; i++) {
-        const LayerDef& l = SD15_STEPS[i].l;
+        const LayerDef& l = steps[i].l;
         const std::string n = "unet.layer" + std::to_string(i + 1);
         if (l.kind == L_RES) { b.norm(n + ".layer1", l.a); b.norm(n + ".layer4", l.b); }
         else if (l.kind == L_ATTN) {
@@ -195,26 +213,27 @@ std::vector<ParamSpec> build_param_specs(int kind) {
       }
   } else if (is_clip_kind(kind)) {  // clip.mojo:74-88 ; parameter order = oracle/spec.py clip_params()
     ParamSpec t;
-    t.name = "embedding.token.weight"; t.ndim = 2; t.shape[0] = 49408; t.shape[1] = 768; t.kind = P_LIN_W;
+    const int W = clip_kind_width(kind), NL = clip_kind_layers(kind);
+    t.name = "embedding.token.weight"; t.ndim = 2; t.shape[0] = 49408; t.shape[1] = W; t.kind = P_LIN_W;
     t.bound = 1.7320508075688772f;  // unit variance like init_weights_normal(0,1), helpers/utils.mojo:2025
-    t.Kpad = 768; t.Opad = 49408;
+    t.Kpad = W; t.Opad = 49408;
     b.out.push_back(t);
     ParamSpec p;
-    p.name = "embedding.position"; p.ndim = 1; p.shape[0] = 77 * 768; p.kind = P_LIN_B; p.bound = 0.02f; p.Opad = 77 * 768;
+    p.name = "embedding.position"; p.ndim = 1; p.shape[0] = 77 * W; p.kind = P_LIN_B; p.bound = 0.02f; p.Opad = 77 * W;
     b.out.push_back(p);
-    for (int i = 1; i <= 12; i++) {
+    for (int i = 1; i <= NL; i++) {
       const std::string n = "player" + std::to_string(i);
-      b.lin(n + ".layer2.in_proj", 768, 3 * 768);
-      b.lin(n + ".layer2.out_proj", 768, 768);
-      b.lin(n + ".layer4", 768, 4 * 768);
-      b.lin(n + ".layer5", 4 * 768, 768);
+      b.lin(n + ".layer2.in_proj", W, 3 * W);
+      b.lin(n + ".layer2.out_proj", W, W);
+      b.lin(n + ".layer4", W, 4 * W);
+      b.lin(n + ".layer5", 4 * W, W);
     }
-    if (kind == TSD_MODEL_CLIP_TORCH) {
-      for (int i = 1; i <= 12; i++) {
-        b.norm("player" + std::to_string(i) + ".layer1", 768);
-        b.norm("player" + std::to_string(i) + ".layer3", 768);
+    if (is_torch_clip_kind(kind)) {
+      for (int i = 1; i <= NL; i++) {
+        b.norm("player" + std::to_string(i) + ".layer1", W);
+        b.norm("player" + std::to_string(i) + ".layer3", W);
       }
-      b.norm("layernorm", 768);
+      b.norm("layernorm", W);
     }
   } else if (is_decoder_kind(kind) || is_encoder_kind(kind)) {
     const LayerDef* L = is_decoder_kind(kind) ? DECODER_LAYERS : ENCODER_LAYERS;
@@ -240,13 +259,13 @@ std::vector<ParamSpec> build_param_specs(int kind) {
 }
 
 extern "C" int tsd_model_param_count(int kind) {
-  if (kind < TSD_MODEL_DIFFUSION || kind > TSD_MODEL_KIND_MAX) return TSD_E_ARG;
+  if (!is_model_kind(kind)) return TSD_E_ARG;
   return (int)build_param_specs(kind).size();
 }
 
 extern "C" int tsd_model_param_info(int kind, int index, char* name, int name_cap, int64_t shape[4], int* ndim,
                                     int* used, float* init_bound) {
-  if (kind < TSD_MODEL_DIFFUSION || kind > TSD_MODEL_KIND_MAX) TSD_FAIL(TSD_E_ARG, "bad model kind %d", kind);
+  if (!is_model_kind(kind)) TSD_FAIL(TSD_E_ARG, "bad model kind %d", kind);
   static thread_local int cached_kind = 0;
   static thread_local std::vector<ParamSpec> cached;
   if (cached_kind != kind) {
@@ -275,10 +294,10 @@ double unet_res_f(double cin, double cout, double hw) {
   return conv_f(cin, cout, 3, hw) + lin_f(1, 1280, cout) + conv_f(cout, cout, 3, hw) +
          (cin != cout ? conv_f(cin, cout, 1, hw) : 0.0);
 }
-double unet_attn_f(double C, double dh, double hw, double T) {
+double unet_attn_f(double C, double dh, double hw, double T, double dctx = 768) {
   const double H = C / dh;
   return 2 * conv_f(C, C, 1, hw) + lin_f(hw, C, 3 * C) + attn_core_f(H, hw, hw, dh) + lin_f(hw, C, C) +
-         lin_f(hw, C, C) + 2 * lin_f(T, 768, C) + attn_core_f(H, hw, T, dh) + lin_f(hw, C, C) + lin_f(hw, C, 8 * C) +
+         lin_f(hw, C, C) + 2 * lin_f(T, dctx, C) + attn_core_f(H, hw, T, dh) + lin_f(hw, C, C) + lin_f(hw, C, 8 * C) +
          lin_f(hw, 4 * C, C);
 }
 double vae_res_f(double cin, double cout, double hw) {
@@ -305,8 +324,9 @@ extern "C" double tsd_flop_count(int kind, int L, int T) {
   } else if (is_full_unet_kind(kind)) {
     f += lin_f(1, 320, 1280) + lin_f(1, 1280, 1280);
     double side = L;
+    const UNetStep* steps = full_unet_steps(kind);
     for (int i = 0; i < SD15_N; i++) {
-      const LayerDef& l = SD15_STEPS[i].l;
+      const LayerDef& l = steps[i].l;
       if (l.kind == L_CONV) {
         if (l.d == 2) side /= 2;
         f += conv_f(l.a, l.b, l.c, side * side);
@@ -314,7 +334,7 @@ extern "C" double tsd_flop_count(int kind, int L, int T) {
         side *= 2;
         f += conv_f(l.a, l.b, l.c, side * side);
       } else if (l.kind == L_RES) f += unet_res_f(l.a, l.b, side * side);
-      else if (l.kind == L_ATTN) f += unet_attn_f((double)l.a * l.b, l.b, side * side, T);
+      else if (l.kind == L_ATTN) f += unet_attn_f((double)l.a * l.b, l.b, side * side, T, is_sd2_unet_kind(kind) ? 1024 : 768);
     }
     f += conv_f(320, 4, 3, (double)L * L);
   } else if (is_decoder_kind(kind) || is_encoder_kind(kind)) {
@@ -330,8 +350,8 @@ extern "C" double tsd_flop_count(int kind, int L, int T) {
       else if (l.kind == L_UP) side *= 2;
     }
   } else if (is_clip_kind(kind)) {  // per prompt: 12 x (in_proj, QK^T, PV, out_proj, 768->3072->768) on 77 tokens
-    const double Tc = 77, D = 768;
-    f = 12.0 * (lin_f(Tc, D, 3 * D) + 2.0 * 2.0 * Tc * Tc * D + lin_f(Tc, D, D) + lin_f(Tc, D, 4 * D) + lin_f(Tc, 4 * D, D));
+    const double Tc = 77, D = clip_kind_width(kind);
+    f = (double)clip_kind_layers(kind) * (lin_f(Tc, D, 3 * D) + 2.0 * 2.0 * Tc * Tc * D + lin_f(Tc, D, D) + lin_f(Tc, D, 4 * D) + lin_f(Tc, 4 * D, D));
   } else {
     return -1.0;
   }

@@ -18,11 +18,12 @@ struct tsd_session {
   tsd_ctx* ctx = nullptr;
   int B = 0, LH = 0, LW = 0, T = 0, Tp = 0, cfg = 0;  // one shape per session: latents [.,4,LH,LW]
   int Bu = 0;                                         // the UNet's batch: 2B under CFG, else B
+  int W = 768;                                        // context width, from the UNet (model_context_width): 1024 for SD-2.x
   // persistent device state (own allocation, not the arena)
   char* state = nullptr;
   float* latents = nullptr;   // [B,4,LH,LW] fp32 CHW (the reference's own layout)
   float* lat2 = nullptr;      // [2B,4,LH,LW] duplicated latents for the CFG batch
-  half_t* ctx16 = nullptr;    // [B or 2B][Tp][768]
+  half_t* ctx16 = nullptr;    // [B or 2B][Tp][W]
   float* eps = nullptr;       // [B or 2B,4,LH,LW]
   float* tdev = nullptr;      // [16] timestep per sample
   float* temb = nullptr;      // [16][320]
@@ -169,15 +170,15 @@ static int session_grow(void** ptr, size_t* cap, size_t bytes, const char* what)
   *cap = bytes;
   return TSD_OK;
 }
-// `samples` host contexts [T][768] fp32 -> rows first .. first + samples of ctx16, fp16 [Tp][768] with ZERO pad rows: the conversion the
+// `samples` host contexts [T][W] fp32 -> rows first .. first + samples of ctx16, fp16 [Tp][W] with ZERO pad rows: the conversion the
 // V^T pad-column contract rests on (include/tsd.h).  Through the staging buffer, which the caller reserved; synchronises, so `src` and
 // the staging buffer are free again on return.
 static int session_put_context(tsd_session* s, const float* src, size_t first, int samples) {
   tsd_ctx* ctx = s->ctx;
-  const size_t nc = (size_t)s->T * 768;
+  const size_t nc = (size_t)s->T * s->W;
   HIP_TRY(hipMemcpyAsync(ctx->staging, src, samples * nc * 4, hipMemcpyHostToDevice, ctx->stream));
   for (int b = 0; b < samples; b++)
-    TSD_TRY(launch_f32_to_f16_rows(ctx, (const float*)ctx->staging + b * nc, s->T, 768, s->ctx16 + (first + b) * s->Tp * 768, 768, s->Tp));
+    TSD_TRY(launch_f32_to_f16_rows(ctx, (const float*)ctx->staging + b * nc, s->T, s->W, s->ctx16 + (first + b) * s->Tp * s->W, s->W, s->Tp));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   return TSD_OK;
 }
@@ -348,10 +349,11 @@ extern "C" int tsd_session_create_hw(tsd_model* diffusion, tsd_model* decoder, i
   tsd_session* s = new tsd_session();
   s->unet = diffusion; s->dec = decoder; s->ctx = ctx;
   s->B = B; s->LH = LH; s->LW = LW; s->T = T; s->Tp = round_up(T, 8); s->cfg = cfg ? 1 : 0; s->Bu = Bu;
+  s->W = model_context_width(diffusion);
   const size_t hw = (size_t)LH * LW, nl = (size_t)B * 4 * hw;
   size_t off = 0;
   auto carve = [&](size_t bytes) { size_t o = off; off = (off + bytes + 255) & ~size_t(255); return o; };
-  const size_t o_lat = carve(nl * 4), o_lat2 = carve(2 * nl * 4), o_ctx = carve((size_t)Bu * s->Tp * 768 * 2),
+  const size_t o_lat = carve(nl * 4), o_lat2 = carve(2 * nl * 4), o_ctx = carve((size_t)Bu * s->Tp * s->W * 2),
                o_eps = carve((size_t)Bu * 4 * hw * 4), o_t = carve(16 * 4), o_te = carve(16 * 320 * 4),
                o_img = carve(decoder ? (size_t)B * 3 * 64 * hw * 4 : 0), o_hist = carve(nl * 4),
                o_ipm = carve((size_t)B * hw * 4), o_ipk = carve(nl * 4), o_ipn = carve(nl * 4),
@@ -534,8 +536,8 @@ extern "C" int tsd_session_upload(tsd_session* s, const float* latents, const fl
   const size_t nl = (size_t)B * 4 * s->LH * s->LW;
   s->slots = false;  // upload() leaves slot mode
   HIP_TRY(hipMemcpyAsync(s->latents, latents, nl * 4, hipMemcpyHostToDevice, ctx->stream));
-  // context -> fp16 [Bu][Tp][768], zero padded rows (cond first, then uncond: pipeline.mojo:49)
-  TSD_TRY(ctx_reserve_staging(ctx, (size_t)B * s->T * 768 * 4));
+  // context -> fp16 [Bu][Tp][W], zero padded rows (cond first, then uncond: pipeline.mojo:49)
+  TSD_TRY(ctx_reserve_staging(ctx, (size_t)B * s->T * s->W * 4));
   for (int part = 0; part < (s->cfg ? 2 : 1); part++)
     TSD_TRY(session_put_context(s, part == 0 ? context : uncond_context, (size_t)part * B, B));
   s->has_noise = noise != nullptr;
@@ -682,6 +684,9 @@ extern "C" int tsd_session_set_control(tsd_session* s, tsd_model* cn, const floa
   NOTNULL(hint);
   if (!is_full_unet_kind(s->unet->kind)) TSD_FAIL(TSD_E_ARG, "session: set_control needs a full-size UNet (the Tiny-SD graph has no ControlNet)");
   if (!is_controlnet_kind(cn->kind)) TSD_FAIL(TSD_E_ARG, "session: set_control: the model is not a ControlNet");
+  if (model_context_width(cn) != s->W)
+    TSD_FAIL(TSD_E_ARG, "session: set_control: the ControlNet kinds are SD-1.x networks (context width %d); this session's UNet reads a %d-wide context",
+             model_context_width(cn), s->W);
   if (cn->ctx != s->ctx) TSD_FAIL(TSD_E_ARG, "session: set_control: the ControlNet belongs to another context (the residuals live in the session's arena)");
   if (!(fabsf(scale) <= 3.4028235e38f)) TSD_FAIL(TSD_E_ARG, "session: set_control: the scale is not finite");
   if (first_step < 0 || (last_step >= 0 && last_step < first_step)) TSD_FAIL(TSD_E_ARG, "session: set_control: window [%d, %d]", first_step, last_step);
@@ -899,7 +904,7 @@ extern "C" int tsd_session_slots_open(tsd_session* s) {
   s->has_noise = false;
   // idle slots ride through every forward: zero latents and a zero context keep them finite
   HIP_TRY(hipMemsetAsync(s->latents, 0, (size_t)B * 4 * s->LH * s->LW * 4, ctx->stream));
-  HIP_TRY(hipMemsetAsync(s->ctx16, 0, (size_t)Bu * s->Tp * 768 * 2, ctx->stream));
+  HIP_TRY(hipMemsetAsync(s->ctx16, 0, (size_t)Bu * s->Tp * s->W * 2, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   if (ctx->opt.session_hoist)  // the per-sample time rows of an advance: sized by the session's shape alone
     TSD_TRY(session_grow((void**)&s->trows, &s->trows_cap, (size_t)Bu * s->unet->unet.tproj.N * 4, "time rows"));
@@ -917,7 +922,7 @@ extern "C" int tsd_session_slot_start(tsd_session* s, int b, const float* contex
   SESSION_NOT_POISONED(s);
   tsd_ctx* ctx = s->ctx;
   const int B = s->B, T = s->T, Tp = s->Tp;
-  const size_t chw = (size_t)4 * s->LH * s->LW, nc = (size_t)T * 768;
+  const size_t chw = (size_t)4 * s->LH * s->LW, nc = (size_t)T * s->W;
   // every refusal comes before the first copy: a refused call leaves the slot, and everyone else's, as it was
   SLOT_IN_RANGE(s, b);
   if (start_index < 0 || start_index >= (int)s->timesteps.size())
@@ -942,7 +947,7 @@ extern "C" int tsd_session_slot_start(tsd_session* s, int b, const float* contex
     for (int part = 0; part < (s->cfg ? 2 : 1); part++) {
       const size_t row = (size_t)part * B + b;
       ctx->arena.top = 0;
-      TSD_TRY(g_unet_ctx_kv(s->unet, s->ctx16 + row * Tp * 768, Tp, 1, s->kc_all + row * Tp * CK, s->vtc_all + row * CK * Tp));
+      TSD_TRY(g_unet_ctx_kv(s->unet, s->ctx16 + row * Tp * s->W, Tp, 1, s->kc_all + row * Tp * CK, s->vtc_all + row * CK * Tp));
     }
     ctx->arena.top = 0;
   }

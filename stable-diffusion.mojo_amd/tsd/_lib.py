@@ -23,6 +23,7 @@ os.environ.setdefault("HIP_FORCE_DEV_KERNARG", "1")
 MODEL_DIFFUSION, MODEL_DECODER, MODEL_ENCODER, MODEL_CLIP, MODEL_DIFFUSION_SD15, MODEL_DIFFUSION_SD15_TORCH = 1, 2, 3, 4, 5, 6
 MODEL_CLIP_TORCH, MODEL_DECODER_TORCH, MODEL_ENCODER_TORCH = 7, 8, 9
 MODEL_CONTROLNET_SD15, MODEL_CONTROLNET_SD15_TORCH = 10, 11
+MODEL_DIFFUSION_SD2, MODEL_CLIP_SD2 = 16, 17    # 12 - 15 are reserved and refused
 SAMPLER_KINDS = {"ddpm": 0, "ddim": 1, "dpmpp_2m": 2}      # tsd_sampler_kind
 TIMESTEP_SPACINGS = {"leading": 0, "trailing": 1}          # tsd_timestep_spacing
 MASK_MODES = {"area": 0, "any": 1}                         # tsd_mask_mode
@@ -135,6 +136,7 @@ def _declare(l):
         "tsd_decoder_forward_hw": ([vp, fp, i, i, i, fp], i),
         "tsd_encoder_forward_hw": ([vp, fp, fp, i, i, i, fp], i),
         "tsd_clip_forward": ([vp, C.POINTER(C.c_int32), i, i, fp], i),
+        "tsd_model_context_width": ([vp], i),
         "tsd_controlnet_forward_hw": ([vp, fp, fp, fp, fp, i, i, i, i, C.POINTER(fp)], i),
         "tsd_diffusion_forward_control_hw": ([vp, vp, fp, fp, fp, fp, fp, i, i, i, i, fp], i),
         "tsd_control_inject_f16": ([vp, i, pp, pp, i, C.POINTER(i), C.POINTER(i), C.POINTER(i), C.POINTER(i), fp, pp, C.POINTER(fp)], i),

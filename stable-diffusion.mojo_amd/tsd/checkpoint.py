@@ -194,6 +194,41 @@ def load_sd15_unet(path, ctx=None, prefix=""):
     return Diffusion(ctx=ctx, params=params, variant="diffusion_sd15_torch")
 
 
+# ---- SD-2.x UNet (diffusers UNet2DConditionModel with attention_head_dim (5, 10, 20, 20), cross_attention_dim 1024 and
+# use_linear_projection -> model kind "diffusion_sd2") ----
+# The modules and the tensor names are SD-1.x's.  use_linear_projection only changes the rank of proj_in / proj_out in the file ([C, C]
+# instead of [C, C, 1, 1]); the head split lives in the model kind, not in any tensor's shape.
+def diffusers_sd2_unet_to_params(state, prefix=""):
+    """diffusers SD-2.x UNet state dict -> {our parameter name: array} for kind "diffusion_sd2"; proj_in / proj_out 2-D or 4-D."""
+    return diffusers_sd15_unet_to_params(state, prefix)
+
+
+def params_to_diffusers_sd2_unet(params, prefix="", linear_projection=True):
+    """Inverse of `diffusers_sd2_unet_to_params`; linear_projection: proj_in / proj_out as [C, C] (how the SD-2.x files hold them)."""
+    out = params_to_diffusers_sd15_unet(params, prefix)
+    if linear_projection:
+        for k in list(out):
+            if k.endswith(("proj_in.weight", "proj_out.weight")) and np.ndim(out[k]) == 4:
+                out[k] = np.asarray(out[k])[:, :, 0, 0]
+    return out
+
+
+def load_sd2_unet(path_or_state, ctx=None, prefix=""):
+    """tsd.Diffusion(variant="diffusion_sd2") with the weights of a diffusers SD-2.x UNet: a safetensors file, or its state dict."""
+    from .diffusion import Diffusion
+    from .model import param_specs
+    state = read_safetensors(path_or_state) if isinstance(path_or_state, str) else path_or_state
+    params = diffusers_sd2_unet_to_params(state, prefix)
+    for name, shape, used, _ in param_specs("diffusion_sd2"):
+        if name not in params:
+            if used:
+                raise KeyError(f"checkpoint has no tensor for {name}")
+            params[name] = np.zeros(shape, np.float32)
+        elif tuple(params[name].shape) != tuple(shape):
+            raise ValueError(f"{name}: checkpoint shape {params[name].shape}, model expects {shape}")
+    return Diffusion(ctx=ctx, params=params, variant="diffusion_sd2")
+
+
 # ---- ControlNet (diffusers `ControlNetModel` for SD-1.x -> model kind "controlnet_sd15_torch") ------------------------------------------
 # the UNet's encoder and bottleneck under the UNet's own names (the first 21 flat layers), the hint encoder and the zero convolutions
 CONTROLNET_LAYERS = 21
@@ -247,7 +282,8 @@ def load_controlnet(path_or_state, ctx=None, prefix=""):
 
 def hf_clip_text_to_params(state):
     """Hugging Face CLIPTextModel state dict (with or without the `text_model.` prefix; tensors or arrays) ->
-    {our parameter name: array} for kind "clip_torch" (q/k/v stacked into the reference's in_proj)."""
+    {our parameter name: array} for kind "clip_torch" (q/k/v stacked into the reference's in_proj), or for kind "clip_sd2" when the
+    state dict is 1024 wide (the SD-2.x text encoder: 23 layers); `clip_text_variant` names the kind."""
     pre = "text_model." if any(k.startswith("text_model.") for k in state) else ""
 
     def g(k):
@@ -257,7 +293,7 @@ def hf_clip_text_to_params(state):
     out = {"embedding.token.weight": g("embeddings.token_embedding.weight"),
            "embedding.position": g("embeddings.position_embedding.weight").reshape(-1),
            "layernorm.weight": g("final_layer_norm.weight"), "layernorm.bias": g("final_layer_norm.bias")}
-    for i in range(12):
+    for i in range(23 if out["embedding.token.weight"].shape[1] == 1024 else 12):
         h, n = f"encoder.layers.{i}.", f"player{i + 1}"
         out[n + ".layer2.in_proj.weight"] = np.concatenate([g(h + f"self_attn.{x}_proj.weight") for x in "qkv"])
         out[n + ".layer2.in_proj.bias"] = np.concatenate([g(h + f"self_attn.{x}_proj.bias") for x in "qkv"])
@@ -267,12 +303,37 @@ def hf_clip_text_to_params(state):
     return out
 
 
+def clip_text_variant(params):
+    """"clip_sd2" for the 1024-wide SD-2.x text encoder, else "clip_torch"."""
+    return "clip_sd2" if np.shape(params["embedding.token.weight"])[1] == 1024 else "clip_torch"
+
+
+def params_to_hf_clip_text(params, prefix="text_model."):
+    """Inverse of `hf_clip_text_to_params` (export; used by the round-trip test)."""
+    p = lambda k: np.asarray(params[k], np.float32)  # noqa: E731
+    width = p("embedding.token.weight").shape[1]
+    out = {prefix + "embeddings.token_embedding.weight": p("embedding.token.weight"),
+           prefix + "embeddings.position_embedding.weight": p("embedding.position").reshape(-1, width),
+           prefix + "final_layer_norm.weight": p("layernorm.weight"), prefix + "final_layer_norm.bias": p("layernorm.bias")}
+    i = 0
+    while f"player{i + 1}.layer4.weight" in params:
+        h, n = prefix + f"encoder.layers.{i}.", f"player{i + 1}"
+        for x, w, b in zip("qkv", np.split(p(n + ".layer2.in_proj.weight"), 3), np.split(p(n + ".layer2.in_proj.bias"), 3)):
+            out[h + f"self_attn.{x}_proj.weight"], out[h + f"self_attn.{x}_proj.bias"] = w, b
+        for ours, theirs in (("layer2.out_proj", "self_attn.out_proj"), ("layer4", "mlp.fc1"), ("layer5", "mlp.fc2"),
+                             ("layer1", "layer_norm1"), ("layer3", "layer_norm2")):
+            out[h + theirs + ".weight"], out[h + theirs + ".bias"] = p(f"{n}.{ours}.weight"), p(f"{n}.{ours}.bias")
+        i += 1
+    return out
+
+
 def load_clip_text(path_or_state, ctx=None):
-    """tsd.CLIP(variant="clip_torch") from a CLIPTextModel safetensors file (e.g. `text_encoder/model.safetensors` of an
-    SD-1.x repository) or an in-memory state dict."""
+    """tsd.CLIP from a CLIPTextModel safetensors file (e.g. `text_encoder/model.safetensors`) or an in-memory state dict: variant
+    "clip_torch" for an SD-1.x repository, "clip_sd2" when the state dict is 1024 wide (SD-2.x)."""
     from .clip import CLIP
     state = read_safetensors(path_or_state) if isinstance(path_or_state, str) else path_or_state
-    return CLIP(ctx=ctx, params=hf_clip_text_to_params(state), variant="clip_torch")
+    params = hf_clip_text_to_params(state)
+    return CLIP(ctx=ctx, params=params, variant=clip_text_variant(params))
 
 
 # ---- VAE (diffusers AutoencoderKL) ---------------------------------------------------------------------------------

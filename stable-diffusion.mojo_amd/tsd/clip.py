@@ -18,7 +18,8 @@ class CLIP:
 
     def __init__(self, seed=0, ctx=None, params=None, variant="clip"):
         """variant "clip_torch" (extension): torch LayerNorms with weight / bias = Hugging Face's CLIPTextModel, for real
-        checkpoints (tsd.checkpoint.load_clip_text)."""
+        checkpoints (tsd.checkpoint.load_clip_text).  variant "clip_sd2": the OpenCLIP-H text encoder as diffusers ships it for SD-2.x -
+        width 1024, 16 heads, 23 layers, erf-GELU; forward gives (77, 1024) / (B, 77, 1024), ids past the prompt are 0."""
         self.model = Model(variant, ctx=ctx, seed=None if params is not None else seed)
         if params is not None:
             self.model.load_params(params)
@@ -28,7 +29,7 @@ class CLIP:
         single = t.ndim == 1
         tb = t[None] if single else t
         B, T = tb.shape
-        out = np.empty((B, 77, 768), dtype=np.float32)
+        out = np.empty((B, 77, self.model.context_width), dtype=np.float32)
         code = lib().tsd_clip_forward(self.model.h, tb.ctypes.data_as(C.POINTER(C.c_int32)), B, T,
                                       out.ctypes.data_as(C.POINTER(C.c_float)))
         if check(code, True):

@@ -159,7 +159,8 @@ class Diffusion:
     def __init__(self, seed=0, ctx=None, params=None, variant="diffusion"):
         """variant: "diffusion" (the reference's 23-layer Tiny-SD graph) or "diffusion_sd15" (full-size 860 M UNet,
         BASELINE configs[4]; same blocks, not defined by the reference) or "diffusion_sd15_torch" (that graph with the
-        norm semantics and parameters of PyTorch-trained SD-1.x checkpoints, see tsd.checkpoint)."""
+        norm semantics and parameters of PyTorch-trained SD-1.x checkpoints, see tsd.checkpoint) or "diffusion_sd2" (the SD-2.x UNet:
+        that graph with head dimension 64 in every attention block and a 1024-wide context, tsd.checkpoint.load_sd2_unet)."""
         self.model = Model(variant, ctx=ctx, seed=None if params is not None else seed)
         if params is not None:
             self.model.load_params(params)
@@ -169,6 +170,9 @@ class Diffusion:
         sample - the ControlNet's residuals, scaled per sample, are added to the skips and the bottleneck output (full-size variants)."""
         xb, c, t, single = _forward_inputs(x, context, time)
         B, _, LH, LW = xb.shape
+        W = self.model.context_width
+        if c.ndim != 3 or c.shape[0] != B or c.shape[2] != W:
+            raise ValueError(f"context must have shape (T, {W}) or ({B}, T, {W}), got {np.shape(context)}: this UNet reads a {W}-wide context")
         out = np.empty_like(xb)
         if control is None:
             if hint is not None:

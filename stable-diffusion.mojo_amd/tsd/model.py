@@ -10,7 +10,8 @@ KINDS = {"diffusion": _lib.MODEL_DIFFUSION, "decoder": _lib.MODEL_DECODER, "enco
          "clip": _lib.MODEL_CLIP, "diffusion_sd15": _lib.MODEL_DIFFUSION_SD15,
          "diffusion_sd15_torch": _lib.MODEL_DIFFUSION_SD15_TORCH, "clip_torch": _lib.MODEL_CLIP_TORCH,
          "decoder_torch": _lib.MODEL_DECODER_TORCH, "encoder_torch": _lib.MODEL_ENCODER_TORCH,
-         "controlnet_sd15": _lib.MODEL_CONTROLNET_SD15, "controlnet_sd15_torch": _lib.MODEL_CONTROLNET_SD15_TORCH}
+         "controlnet_sd15": _lib.MODEL_CONTROLNET_SD15, "controlnet_sd15_torch": _lib.MODEL_CONTROLNET_SD15_TORCH,
+         "diffusion_sd2": _lib.MODEL_DIFFUSION_SD2, "clip_sd2": _lib.MODEL_CLIP_SD2}
 
 
 def param_specs(kind):
@@ -47,6 +48,15 @@ class Model:
 
     def init_random(self, seed):
         check(lib().tsd_model_init_random(self.h, int(seed)))
+
+    @property
+    def context_width(self):
+        """Width of the context rows a UNet / ControlNet reads and a text encoder writes (`tsd_model_context_width`): 768, or 1024 for the
+        SD-2.x kinds."""
+        w = lib().tsd_model_context_width(self.h)
+        if w < 0:
+            check(w)
+        return w
 
     def set_param(self, index, array):
         a = f32(array)
@@ -136,6 +146,15 @@ class Model:
             self.h = None
 
 
+def _context_error(what, want, got):
+    """The message of a context whose shape a model cannot read; a wrong width names both widths (a 768-wide SD-1.x context handed to an
+    SD-2.x UNet, or the reverse, would otherwise be read as too few / too many floats by the C side)."""
+    msg = f"{what} must have shape {want}, got {got}"
+    if len(got) and got[-1] != want[-1]:
+        msg += f": this UNet reads a {want[-1]}-wide context, the one given is {got[-1]} wide"
+    return msg
+
+
 class Session:
     """Device-resident denoise loop (pipeline.mojo:57-127 + sampler.mojo).  L: the latent side, or a pair (LH, LW) for a rectangular
     session; `LH` / `LW` are the sides, `L` stays what the caller passed.  Where a method's text says L,L the tensor is LH,LW."""
@@ -149,6 +168,7 @@ class Session:
         self.LH, self.LW = LH, LW
         self.ctx = diffusion.ctx
         self.has_decoder = decoder is not None
+        self.W = diffusion.context_width   # the C side reads T * W floats per context
 
     def set_schedule(self, num_training_steps=1000, num_inference_steps=50, start_step=0):
         check(lib().tsd_session_set_schedule(self.h, num_training_steps, num_inference_steps, start_step))
@@ -183,21 +203,21 @@ class Session:
         la, cx = f32(latents), f32(context)
         uc = f32(uncond_context) if uncond_context is not None else None
         nz = f32(noise) if noise is not None else None
-        # the C side reads exactly B*4*L*L / B*T*768 / steps*B*4*L*L floats from these pointers: check the shapes here
-        B, LH, LW, T = self.B, self.LH, self.LW, self.T
+        # the C side reads exactly B*4*L*L / B*T*W / steps*B*4*L*L floats from these pointers: check the shapes here
+        B, LH, LW, T, W = self.B, self.LH, self.LW, self.T, self.W
         if la.shape != (B, 4, LH, LW):
             raise ValueError(f"latents must have shape {(B, 4, LH, LW)}, got {la.shape}")
-        if cx.shape != (B, T, 768):
-            raise ValueError(f"context must have shape {(B, T, 768)}, got {cx.shape}")
+        if cx.shape != (B, T, W):
+            raise ValueError(_context_error("context", (B, T, W), cx.shape))
         if self.cfg and uc is None:
             raise ValueError("a CFG session needs uncond_context")
         if uc is not None:
             if uc.ndim == 2:
                 uc = uc[None]
-            if uc.shape == (1, T, 768) and B > 1:  # one shared negative prompt: broadcast it like Diffusion.forward does
-                uc = np.ascontiguousarray(np.broadcast_to(uc, (B, T, 768)))
-            if uc.shape != (B, T, 768):
-                raise ValueError(f"uncond_context must have shape {(B, T, 768)} (or one shared (T, 768) row), got {uc.shape}")
+            if uc.shape == (1, T, W) and B > 1:  # one shared negative prompt: broadcast it like Diffusion.forward does
+                uc = np.ascontiguousarray(np.broadcast_to(uc, (B, T, W)))
+            if uc.shape != (B, T, W):
+                raise ValueError(_context_error("uncond_context", (B, T, W), uc.shape) + f" (or one shared {(T, W)} row)")
         if nz is not None and nz.shape != (self.num_steps, B, 4, LH, LW):
             raise ValueError(f"noise must have shape {(self.num_steps, B, 4, LH, LW)}, got {nz.shape}")
         check(lib().tsd_session_upload(self.h, ptr(la), ptr(cx), ptr(uc), ptr(nz), float(cfg_scale)))
@@ -333,19 +353,19 @@ class Session:
     def slot_start(self, b, context, uncond_context=None, latents=None, noise_at_start=False, seed=0, start_index=0, cfg_scale=7.5):
         """Put a request into slot b: context (T,768), uncond_context (T,768) on a CFG session, latents (4,L,L) or None (stream 2 of
         `seed`); noise_at_start noises given latents to timesteps[start_index] with stream 4 of `seed` (img2img)."""
-        T, LH, LW = self.T, self.LH, self.LW
+        T, LH, LW, W = self.T, self.LH, self.LW, self.W
         cx = f32(context)
-        if cx.shape == (1, T, 768):
+        if cx.shape == (1, T, W):
             cx = cx[0]
-        if cx.shape != (T, 768):
-            raise ValueError(f"context must have shape {(T, 768)}, got {cx.shape}")
+        if cx.shape != (T, W):
+            raise ValueError(_context_error("context", (T, W), cx.shape))
         uc = None
         if uncond_context is not None:
             uc = f32(uncond_context)
-            if uc.shape == (1, T, 768):
+            if uc.shape == (1, T, W):
                 uc = uc[0]
-            if uc.shape != (T, 768):
-                raise ValueError(f"uncond_context must have shape {(T, 768)}, got {uc.shape}")
+            if uc.shape != (T, W):
+                raise ValueError(_context_error("uncond_context", (T, W), uc.shape))
         la = None
         if latents is not None:
             la = f32(latents)
