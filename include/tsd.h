@@ -188,7 +188,7 @@ int tsd_vae_attention_block_f32(tsd_ctx* ctx, const float* x, int C, int H, int 
  * norms - 32 groups in the residual blocks (the reference declares 16, vae.mojo:42-43), per-channel weight / bias of
  * every GroupNorm appended to the kind-2 / kind-3 list (`lN.group_norm1`, `lN.group_norm2`, `lN.group_norm`, and
  * `lN` for the stand-alone norm), eps inside the root: the layout of diffusers' AutoencoderKL decoder / encoder. */
-typedef enum tsd_model_kind { TSD_MODEL_DIFFUSION = 1, TSD_MODEL_DECODER = 2, TSD_MODEL_ENCODER = 3, TSD_MODEL_CLIP = 4, TSD_MODEL_DIFFUSION_SD15 = 5, TSD_MODEL_DIFFUSION_SD15_TORCH = 6, TSD_MODEL_CLIP_TORCH = 7, TSD_MODEL_DECODER_TORCH = 8, TSD_MODEL_ENCODER_TORCH = 9, TSD_MODEL_CONTROLNET_SD15 = 10, TSD_MODEL_CONTROLNET_SD15_TORCH = 11, TSD_MODEL_DIFFUSION_SD2 = 16, TSD_MODEL_CLIP_SD2 = 17 } tsd_model_kind;
+typedef enum tsd_model_kind { TSD_MODEL_DIFFUSION = 1, TSD_MODEL_DECODER = 2, TSD_MODEL_ENCODER = 3, TSD_MODEL_CLIP = 4, TSD_MODEL_DIFFUSION_SD15 = 5, TSD_MODEL_DIFFUSION_SD15_TORCH = 6, TSD_MODEL_CLIP_TORCH = 7, TSD_MODEL_DECODER_TORCH = 8, TSD_MODEL_ENCODER_TORCH = 9, TSD_MODEL_CONTROLNET_SD15 = 10, TSD_MODEL_CONTROLNET_SD15_TORCH = 11, TSD_MODEL_DIFFUSION_SD2 = 16, TSD_MODEL_CLIP_SD2 = 17, TSD_MODEL_IP_ADAPTER_SD15 = 20 } tsd_model_kind;
 /* TSD_MODEL_CONTROLNET_SD15 (EXTENSION: Zhang et al. 2023; the layout of diffusers' ControlNetModel): the control network of the full-size
  * UNet.  Parameters in this order: `time_embed.layer1/2`; the hint encoder `hint.conv1 .. hint.conv8` (3x3 convolutions 3->16, 16->16,
  * 16->32 stride 2, 32->32, 32->96 stride 2, 96->96, 96->256 stride 2, 256->320; SiLU after each but the last, the last initialised to
@@ -306,6 +306,69 @@ int tsd_session_control_active(tsd_session* s);
  * included (y == x).  A sample's y and partials are the same bits run to run and in every batch position. */
 int tsd_control_inject_f16(tsd_ctx* ctx, int n, const void* const* x, const void* const* r, int B, const int* HW, const int* C,
                            const int* groups, const int* nslab, const float* scale, void* const* y_out, float* const* partial_out);
+/* ---- IP-Adapter (EXTENSION: Ye et al. 2023; the layout of the published ip-adapter_sd15 files): image-prompt tokens through decoupled
+ * cross attention.  In every cross-attention block of the full-size SD-1.x UNet a second key / value pair reads N image tokens and its
+ * attention result joins the text result before the shared output projection:
+ *     ao = Attn(q, K_text, V_text) + s_b * Attn(q, K_ip, V_ip)        K_ip = tok . Wk_ip^T,  V_ip = tok . Wv_ip^T,  tok [N][768]
+ * TSD_MODEL_IP_ADAPTER_SD15 (20; the numbers 12 - 15, 18 and 19 stay reserved and refused) holds, under the published names: `image_proj.proj.weight` [N*768][1024] and `.bias`,
+ * `image_proj.norm.weight` / `.bias` [768], and for each of the 16 cross-attention blocks of the full-size step table, in the table's
+ * order (6 encoder, 1 bottleneck, 9 decoder blocks), `ip_adapter.<i>.to_k_ip.weight` and `ip_adapter.<i>.to_v_ip.weight` [C][768] with no
+ * bias, <i> the odd number the published files give the block (1 .. 11 the encoder, 31 the bottleneck, 13 .. 29 the decoder).  N = 4.
+ * The 16 to_k_ip matrices are contiguous in the packed blob and the 16 to_v_ip matrices follow them, so K_ip and V_ip^T of all blocks are
+ * one GEMM (two where the fused form does not apply) over the tokens staged as 16 fp16 rows per sample, rows N .. 15 zero.
+ * tsd_flop_count returns -1 and tsd_model_lora_add refuses the kind.  The CLIP vision encoder and the resampler of the "plus" files are
+ * not part of it: callers bring the 1024-wide image embedding, or the tokens themselves.
+ * tsd_ip_adapter_project: embeds [B][1024] -> tokens_out [B][N][768] = LayerNorm(Linear(embeds)) per token (eps 1e-5); every value is
+ * exactly an fp16.
+ * tsd_diffusion_forward_ip_hw: tsd_diffusion_forward_hw of `unet` (kinds 5 / 6; TSD_E_ARG for the Tiny-SD graph, the SD-2.x kind and a
+ * ControlNet in that place) with the adapter `ip` on tokens [B][N][768], 1 <= N <= 16, scaled per sample by ip_scale [B]; and, when
+ * cn != NULL, with the ControlNet `cn` on hint / control_scale as in tsd_diffusion_forward_control_hw - both in one plan (the adapter does
+ * not apply to the ControlNet's own blocks).  ip == NULL: no adapter (tokens, N, ip_scale are ignored), the launches of the plain or the
+ * controlled entry.  With an adapter every attention block runs op by op and gains ONE launch between its cross-attention core and
+ * out_proj (k_ip_attn_add, csrc/kernels_ipattn.hip):
+ *     O <- rn16( f32(O) + s_b * (sum_j p_j V_ip[j]) / sum_j p_j ),   p_j = rn16( exp(scale (q . K_ip[j]) - max_j) ),  j < N
+ * A sample whose scale is exactly 0 is neither read nor written by it.  All models on one tsd_ctx. */
+int tsd_ip_adapter_project(tsd_model* ip, const float* embeds, int B, float* tokens_out);
+int tsd_diffusion_forward_ip_hw(tsd_model* unet, tsd_model* ip, const float* tokens, int N, const float* ip_scale, tsd_model* cn,
+                                const float* hint, const float* control_scale, const float* latents, const float* context,
+                                const float* time_emb, int B, int LH, int LW, int T, float* eps_out);
+/* Op level, host fp16 in/out, synchronous: the launch alone.  q / o [B][S][H*d], k_ip [B][16][H*d] (rows >= N are not read),
+ * vt_ip [B][H*d][16] (columns >= N do not reach the result), scale [B]; d in {40, 80, 160}, 1 <= N <= 16, S a multiple of 4;
+ * softmax_scale multiplies the scores (1 / sqrt(d) in the graph).  o_out receives o updated; a sample with scale 0 comes back as it went. */
+int tsd_ip_attn_add_f16(tsd_ctx* ctx, const void* q, const void* k_ip, const void* vt_ip, const void* o, const float* scale, int B, int H,
+                        int d, int S, int N, float softmax_scale, void* o_out);
+/* IP-Adapter in a lockstep denoise session on a full-size SD-1.x UNet.  tokens: host fp32 [B][N][768] for the conditional half;
+ * uncond_tokens: the same shape for the unconditional half - required when the session runs CFG (callers pass the projection of a zero
+ * embedding, which is NOT zero tokens), ignored otherwise; scale: one fp32 for every sample of both halves; the adapter applies on steps
+ * first_step <= i <= last_step (last_step < 0: to the end).  ip == NULL turns it off.  Call after upload().  The tokens are staged and
+ * K_ip / V_ip^T of all 16 blocks are projected here, ONCE (they do not depend on the step), and the per-sample scale vector is built and
+ * uploaded here; every step() inside the window runs the adapted forward with no host copy and no allocation; upload() rebuilds nothing
+ * of it; a step outside the window and every step after set_ip_adapter(NULL) enqueues the launches and gives the bits of a session
+ * without an adapter.  It composes with tsd_session_set_control, seeds, inpainting, guidance rescale, every sampler and prediction type
+ * and the hoist.  New parameters of `ip` (tsd_model_set_param) take effect at the next set_ip_adapter.
+ * TSD_E_ARG: the session's UNet is not kind 5 / 6, ip is no IP-Adapter or lives on another context, N outside 1 .. 16, a scale that is not
+ * finite, a bad window, no uncond_tokens under CFG.  TSD_E_STATE: before upload(); on a slot session; and tsd_session_slots_open on a
+ * session with an adapter (per-slot adapters are not supported).  tsd_session_ip_adapter_active: 1 while an adapter is set. */
+int tsd_session_set_ip_adapter(tsd_session* s, tsd_model* ip, const float* tokens, const float* uncond_tokens, int N, float scale,
+                               int first_step, int last_step);
+int tsd_session_ip_adapter_active(tsd_session* s);
+/* Replay entry of launch_ip_attn_add with the conventions of tsd_debug_attn_run (test infrastructure: tests/ipadapter_ref.py holds the
+ * kernel to an fp64 reference, element-wise).  One int64 per argument: pitches and per-sample strides in elements, SCALE the bits of a
+ * float.  Operand slots: inputs Q [B][S][ldq], K [B][16][ldk], V^T [B][H*d][ldvt], S (fp32 [B]) and OIN, the payload O starts from (not
+ * a device operand of its own); output O [B][S][ldo], updated in place.  host_in == NULL only sizes.  info[TSD_PI_CHANGED]: guard and
+ * pitch-gap elements the launch changed.  The shapes the launcher refuses (d, N, S % 4, misaligned pitches) are sized and left to it. */
+enum tsd_ipattn_desc_field {
+  TSD_PD_VERSION = 0, TSD_PD_B, TSD_PD_H, TSD_PD_D, TSD_PD_S, TSD_PD_N, TSD_PD_LDQ, TSD_PD_LDK, TSD_PD_LDVT, TSD_PD_LDO,
+  TSD_PD_SQB, TSD_PD_SKB, TSD_PD_SVTB, TSD_PD_SOB, TSD_PD_SCALE,
+  TSD_PD_COUNT
+};
+#define TSD_PD_VERSION_1 1
+enum tsd_ipattn_operand { TSD_PO_Q = 0, TSD_PO_K, TSD_PO_VT, TSD_PO_S, TSD_PO_OIN, TSD_PO_O, TSD_PO_COUNT };
+enum tsd_ipattn_info { TSD_PI_CHANGED = 0, TSD_PI_COUNT };
+int tsd_debug_ip_attn_run(tsd_ctx* ctx, const int64_t* desc, int n, const void* const* host_in, void* const* host_out, int64_t* ext,
+                          int64_t* info);
+/* Time `iters` launches of k_ip_attn_add on synthetic device data: B samples (<= 16, all at scale 1), S queries, N image tokens. */
+int tsd_debug_ip_attn_bench(tsd_ctx* ctx, int B, int H, int d, int S, int N, int iters, float* ms);
 int tsd_encoder_forward_hw(tsd_model* m, const float* images, const float* noise, int B, int SH, int SW, float* latents);
 
 /* `CLIP.forward` clip.mojo:90-109 (the step before the hot path), intended semantics

@@ -89,12 +89,12 @@ int cn_upload(tsd_ctx* ctx, const float* latents, const float* context, const fl
   float* dc = arena_alloc<float>(ctx, (int64_t)B * T * W);
   in->dt = arena_alloc<float>(ctx, (int64_t)B * 320);
   in->c16 = arena_alloc<half_t>(ctx, (int64_t)B * Tp * W);
-  in->dh = arena_alloc<float>(ctx, nh);
-  if (!in->dl || !dc || !in->dt || !in->c16 || !in->dh) TSD_FAIL(TSD_E_ALLOC, "workspace arena exhausted");
+  in->dh = hint ? arena_alloc<float>(ctx, nh) : nullptr;  // hint == NULL: a forward without a ControlNet (the adapted entry)
+  if (!in->dl || !dc || !in->dt || !in->c16 || (hint && !in->dh)) TSD_FAIL(TSD_E_ALLOC, "workspace arena exhausted");
   TSD_TRY(h2d(ctx, in->dl, latents, nl * 4));
   TSD_TRY(h2d(ctx, dc, context, (size_t)B * T * W * 4));
   TSD_TRY(h2d(ctx, in->dt, time_emb, (size_t)B * 320 * 4));
-  TSD_TRY(h2d(ctx, in->dh, hint, nh * 4));
+  if (hint) TSD_TRY(h2d(ctx, in->dh, hint, nh * 4));
   for (int b = 0; b < B; b++)  // [T][W] -> zero-padded [Tp][W] per sample
     TSD_TRY(launch_f32_to_f16_rows(ctx, dc + (int64_t)b * T * W, T, W, in->c16 + (int64_t)b * Tp * W, W, Tp));
   return TSD_OK;
@@ -173,6 +173,87 @@ extern "C" int tsd_diffusion_forward_control_hw(tsd_model* unet, tsd_model* cn, 
     ControlRes res;
     TSD_TRY(g_controlnet_forward(cn, in.dl, in.c16, T, in.Tp, in.dt, hf, B, LH, LW, nullptr, &res));
     TSD_TRY(g_unet_forward(unet, in.dl, in.c16, T, in.Tp, in.dt, B, LH, LW, de, false, nullptr, &res, ds));
+    return d2h(ctx, eps_out, de, nl * 4);
+  });
+}
+
+// ---- IP-Adapter: the image projection alone, and the adapted UNet forward (with or without a ControlNet, all models on one context) ------
+extern "C" int tsd_ip_adapter_project(tsd_model* ip, const float* embeds, int B, float* tokens_out) {
+  NOTNULL(ip); NOTNULL(embeds); NOTNULL(tokens_out);
+  if (!is_ip_adapter_kind(ip->kind)) TSD_FAIL(TSD_E_ARG, "tsd_ip_adapter_project: model is not an IP-Adapter");
+  if (B <= 0 || B > 16) TSD_FAIL(TSD_E_SHAPE, "ip_adapter_project: B=%d (1..16)", B);
+  tsd_ctx* ctx = ip->ctx;
+  return run_model(ip, [&]() -> int {
+    const int64_t ne = (int64_t)B * IP_EMBED_DIM, nt = (int64_t)B * ip->ip.n_tokens * IP_CTX_DIM;
+    float* de = arena_alloc<float>(ctx, ne);
+    float* dt = arena_alloc<float>(ctx, nt);
+    if (!de || !dt) TSD_FAIL(TSD_E_ALLOC, "workspace arena exhausted");
+    TSD_TRY(h2d(ctx, de, embeds, ne * 4));
+    TSD_TRY(g_ip_project(ip, de, B, dt));
+    return d2h(ctx, tokens_out, dt, nt * 4);
+  });
+}
+
+extern "C" int tsd_diffusion_forward_ip_hw(tsd_model* unet, tsd_model* ip, const float* tokens, int N, const float* ip_scale, tsd_model* cn,
+                                           const float* hint, const float* control_scale, const float* latents, const float* context,
+                                           const float* time_emb, int B, int LH, int LW, int T, float* eps_out) {
+  NOTNULL(unet);
+  if (!ip)  // no adapter: the plain or the controlled entry, launch for launch
+    return cn ? tsd_diffusion_forward_control_hw(unet, cn, latents, context, time_emb, hint, control_scale, B, LH, LW, T, eps_out)
+              : tsd_diffusion_forward_hw(unet, latents, context, time_emb, B, LH, LW, T, eps_out);
+  NOTNULL(tokens); NOTNULL(ip_scale); NOTNULL(latents); NOTNULL(context); NOTNULL(time_emb); NOTNULL(eps_out);
+  if (unet->kind != TSD_MODEL_DIFFUSION_SD15 && unet->kind != TSD_MODEL_DIFFUSION_SD15_TORCH)
+    TSD_FAIL(TSD_E_ARG, "adapted forward: the UNet must be a full-size SD-1.x kind (an IP-Adapter of this kind fits no other graph)");
+  if (!is_ip_adapter_kind(ip->kind)) TSD_FAIL(TSD_E_ARG, "adapted forward: the model is not an IP-Adapter");
+  if (ip->ctx != unet->ctx) TSD_FAIL(TSD_E_ARG, "adapted forward: the UNet and the IP-Adapter belong to different contexts");
+  if (N < 1 || N > IP_MAX_TOKENS) TSD_FAIL(TSD_E_ARG, "adapted forward: %d image tokens (1..%d)", N, IP_MAX_TOKENS);
+  if (B <= 0 || B > 16 || LH <= 0 || LW <= 0 || T <= 0) TSD_FAIL(TSD_E_SHAPE, "diffusion: B=%d (1..16) L=%dx%d T=%d", B, LH, LW, T);
+  if (LH % 16 || LW % 16) TSD_FAIL(TSD_E_SHAPE, "diffusion: latent sides %d x %d must be multiples of 16", LH, LW);
+  for (int b = 0; b < B; b++)
+    if (!(fabsf(ip_scale[b]) <= 3.4028235e38f)) TSD_FAIL(TSD_E_ARG, "adapted forward: ip_scale[%d] is not finite", b);
+  if (cn) {
+    NOTNULL(hint); NOTNULL(control_scale);
+    TSD_TRY(cn_check(cn, B, LH, LW, T));
+    if (unet->ctx != cn->ctx) TSD_FAIL(TSD_E_ARG, "adapted forward: the UNet and the ControlNet belong to different contexts");
+    for (int b = 0; b < B; b++)
+      if (!(fabsf(control_scale[b]) <= 3.4028235e38f)) TSD_FAIL(TSD_E_ARG, "adapted forward: control_scale[%d] is not finite", b);
+  }
+  // every sample at scale 0: the adapter adds nothing to any sample, so the forward is the plain (or the controlled) one, launch for
+  // launch - the attention blocks keep their fused kernels and the result is that entry's, bit for bit
+  bool any = false;
+  for (int b = 0; b < B; b++) any = any || ip_scale[b] != 0.f;
+  if (!any)
+    return cn ? tsd_diffusion_forward_control_hw(unet, cn, latents, context, time_emb, hint, control_scale, B, LH, LW, T, eps_out)
+              : tsd_diffusion_forward_hw(unet, latents, context, time_emb, B, LH, LW, T, eps_out);
+  tsd_ctx* ctx = unet->ctx;
+  HIP_TRY(hipSetDevice(ctx->device));
+  TSD_TRY(model_check_ready(ip));
+  if (cn) TSD_TRY(model_check_ready(cn));
+  return run_model(unet, [&]() -> int {
+    CnInputs in;
+    TSD_TRY(cn_upload(ctx, latents, context, time_emb, cn ? hint : nullptr, B, LH, LW, T, model_context_width(unet), &in));
+    const int64_t nl = (int64_t)B * 4 * LH * LW, ntok = (int64_t)B * N * IP_CTX_DIM, IK = ip->unet.kproj_all.N;
+    float* ds = arena_alloc<float>(ctx, 2 * B);  // ip_scale | control_scale
+    float* de = arena_alloc<float>(ctx, nl);
+    float* dtok = arena_alloc<float>(ctx, ntok);
+    half_t* tok16 = arena_alloc<half_t>(ctx, (int64_t)B * IP_MAX_TOKENS * IP_CTX_DIM);
+    half_t* kip = arena_alloc<half_t>(ctx, (int64_t)B * IP_MAX_TOKENS * IK);
+    half_t* vip = arena_alloc<half_t>(ctx, (int64_t)B * IK * IP_MAX_TOKENS);
+    if (!ds || !de || !dtok || !tok16 || !kip || !vip) TSD_FAIL(TSD_E_ALLOC, "workspace arena exhausted");
+    TSD_TRY(h2d(ctx, ds, ip_scale, (size_t)B * 4));
+    if (cn) TSD_TRY(h2d(ctx, ds + B, control_scale, (size_t)B * 4));
+    TSD_TRY(h2d(ctx, dtok, tokens, (size_t)ntok * 4));
+    TSD_TRY(g_ip_stage_tokens(ctx, dtok, B, N, tok16));
+    TSD_TRY(g_ip_kv(ip, tok16, B, kip, vip));
+    IpRun run;
+    run.ip = ip; run.k_all = kip; run.vt_all = vip; run.N = N; run.scale = ds;
+    ControlRes res;
+    if (cn) {
+      Act hf;
+      TSD_TRY(g_controlnet_hint(cn, in.dh, B, LH, LW, &hf));
+      TSD_TRY(g_controlnet_forward(cn, in.dl, in.c16, T, in.Tp, in.dt, hf, B, LH, LW, nullptr, &res));
+    }
+    TSD_TRY(g_unet_forward(unet, in.dl, in.c16, T, in.Tp, in.dt, B, LH, LW, de, false, nullptr, cn ? &res : nullptr, cn ? ds + B : nullptr, &run));
     return d2h(ctx, eps_out, de, nl * 4);
   });
 }

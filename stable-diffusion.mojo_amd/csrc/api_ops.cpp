@@ -383,6 +383,29 @@ extern "C" int tsd_control_inject_f16(tsd_ctx* ctx, int n, const void* const* x,
   });
 }
 
+// IP-Adapter's decoupled cross attention (kernels_ipattn.hip) on host fp16 tensors: the ONE launch an adapted attention block adds.
+// q / o [B][S][H*d], k_ip [B][16][H*d], vt_ip [B][H*d][16], scale [B]; o_out receives o updated in place on the device.
+extern "C" int tsd_ip_attn_add_f16(tsd_ctx* ctx, const void* q, const void* k_ip, const void* vt_ip, const void* o, const float* scale, int B,
+                                   int H, int d, int S, int N, float softmax_scale, void* o_out) {
+  NOTNULL(ctx); NOTNULL(q); NOTNULL(k_ip); NOTNULL(vt_ip); NOTNULL(o); NOTNULL(scale); NOTNULL(o_out);
+  if (B <= 0 || B > 16 || H <= 0 || H > 64 || d <= 0 || d > 1024 || S <= 0 || S > (1 << 20)) TSD_FAIL(TSD_E_SHAPE, "ip attention: B=%d (1..16) H=%d d=%d S=%d", B, H, d, S);
+  return run_op(ctx, [&]() -> int {
+    Dev dv{ctx};
+    const int C = H * d;
+    const int64_t nq = (int64_t)B * S * C, nk = (int64_t)B * IP_MAX_TOKENS * C;
+    IpAttnArgs a;
+    a.Q = (const half_t*)dv.in((const uint16_t*)q, nq); a.ldq = C; a.sQ = (int64_t)S * C;
+    a.K = (const half_t*)dv.in((const uint16_t*)k_ip, nk); a.ldk = C; a.sK = (int64_t)IP_MAX_TOKENS * C;
+    a.Vt = (const half_t*)dv.in((const uint16_t*)vt_ip, nk); a.ldvt = IP_MAX_TOKENS; a.sVt = (int64_t)C * IP_MAX_TOKENS;
+    a.O = (half_t*)dv.in((const uint16_t*)o, nq); a.ldo = C; a.sO = (int64_t)S * C;
+    a.s = dv.in(scale, B);
+    a.B = B; a.H = H; a.d = d; a.S = S; a.N = N; a.scale = softmax_scale;
+    if (dv.err) return dv.err;
+    TSD_TRY(launch_ip_attn_add(ctx, a));
+    return dv.out((uint16_t*)o_out, (const uint16_t*)a.O, nq);
+  });
+}
+
 // N(0,1) of the counter RNG (kernels_sampler.hip k_fill_normal, counter_rng.h) on a host tensor: element e is value offset + e of the
 // stream (seed, stream) - the values a seeded denoise session draws on the device
 extern "C" int tsd_normal_fill_f32(tsd_ctx* ctx, uint64_t seed, uint64_t stream, uint64_t offset, int64_t n, float* out) {

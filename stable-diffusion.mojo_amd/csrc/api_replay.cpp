@@ -893,3 +893,65 @@ extern "C" int tsd_debug_elem_run(tsd_ctx* ctx, const int64_t* desc, int n, cons
   TSD_TRY(ops.read_back(&info[TSD_EI_CHANGED]));
   return r;
 }
+
+// ---- IP-Adapter's decoupled cross attention on caller operands (tests/ipadapter_ref.py holds k_ip_attn_add to an fp64 reference) -------
+namespace {
+int pd_elem_bytes(int slot) { return slot == TSD_PO_S ? 4 : 2; }
+// Element extent of every operand.  K is sized with all 16 token rows and V^T with 16 columns, whatever N is: rows / columns >= N exist in
+// the product's buffers (they hold W . 0) and must not reach the result.
+int pd_extents(const int64_t* d, int64_t* e) {
+  for (int i = 0; i < TSD_PO_COUNT; i++) e[i] = 0;
+#define PD_REQ(cond) \
+  if (!(cond)) TSD_FAIL(TSD_E_ARG, "ip_attn_run: descriptor cannot be sized (%s)", #cond)
+  PD_REQ(d[TSD_PD_VERSION] == TSD_PD_VERSION_1);
+  const int64_t B = d[TSD_PD_B], H = d[TSD_PD_H], hd = d[TSD_PD_D], lim = 1LL << 28;
+  const int64_t S = std::max<int64_t>(d[TSD_PD_S], 1);
+  PD_REQ(B > 0 && B <= 16 && H > 0 && H <= 4096 && hd > 0 && hd <= 4096 && H * hd <= 65536);
+  PD_REQ(d[TSD_PD_S] >= 0 && S <= (1 << 20) && d[TSD_PD_N] >= 0 && d[TSD_PD_N] <= 4096);
+  const int64_t C = H * hd;
+  for (int f : {TSD_PD_LDQ, TSD_PD_LDK, TSD_PD_LDO}) PD_REQ(d[f] >= C && d[f] <= (1 << 20));
+  PD_REQ(d[TSD_PD_LDVT] >= IP_MAX_TOKENS && d[TSD_PD_LDVT] <= (1 << 20));
+  PD_REQ(d[TSD_PD_SQB] >= S * d[TSD_PD_LDQ] && d[TSD_PD_SKB] >= IP_MAX_TOKENS * d[TSD_PD_LDK] && d[TSD_PD_SVTB] >= C * d[TSD_PD_LDVT] &&
+         d[TSD_PD_SOB] >= S * d[TSD_PD_LDO]);
+  for (int f : {TSD_PD_SQB, TSD_PD_SKB, TSD_PD_SVTB, TSD_PD_SOB}) PD_REQ(d[f] < lim);
+  e[TSD_PO_Q] = (B - 1) * d[TSD_PD_SQB] + (S - 1) * d[TSD_PD_LDQ] + C;
+  e[TSD_PO_K] = (B - 1) * d[TSD_PD_SKB] + (IP_MAX_TOKENS - 1) * d[TSD_PD_LDK] + C;
+  e[TSD_PO_VT] = (B - 1) * d[TSD_PD_SVTB] + (C - 1) * d[TSD_PD_LDVT] + IP_MAX_TOKENS;
+  e[TSD_PO_S] = B;
+  e[TSD_PO_OIN] = e[TSD_PO_O] = (B - 1) * d[TSD_PD_SOB] + (S - 1) * d[TSD_PD_LDO] + C;
+  for (int s = 0; s < TSD_PO_COUNT; s++) PD_REQ(e[s] >= 0 && e[s] <= lim);
+#undef PD_REQ
+  return TSD_OK;
+}
+}  // namespace
+
+extern "C" int tsd_debug_ip_attn_run(tsd_ctx* ctx, const int64_t* desc, int n, const void* const* host_in, void* const* host_out,
+                                     int64_t* ext, int64_t* info) {
+  NOTNULL(desc); NOTNULL(ext);
+  TSD_TRY(check_fields("ip_attn_run", n, TSD_PD_COUNT));
+  TSD_TRY(pd_extents(desc, ext));
+  const int64_t* d = desc;
+  if (info) for (int i = 0; i < TSD_PI_COUNT; i++) info[i] = 0;
+  if (!host_in) return TSD_OK;  // sizing only: no context or device needed
+  NOTNULL(ctx); NOTNULL(host_out); NOTNULL(info);
+  TSD_TRY(check_slots("ip_attn_run", ext, TSD_PO_COUNT, TSD_PO_O, host_in, host_out));
+  HIP_TRY(hipSetDevice(ctx->device));
+  GuardedOperands ops(ctx, TSD_PO_COUNT);
+  for (int s = 0; s < TSD_PO_OIN; s++)
+    if (ext[s]) TSD_TRY(ops.add(s, ext[s], pd_elem_bytes(s), host_in[s]));
+  // O is updated in place: it starts as the OIN payload, which is no device operand of its own
+  const replay::Box logical{d[TSD_PD_B], d[TSD_PD_SOB], d[TSD_PD_S], d[TSD_PD_LDO], d[TSD_PD_H] * d[TSD_PD_D]};
+  TSD_TRY(ops.add(TSD_PO_O, ext[TSD_PO_O], 2, host_in[TSD_PO_OIN], host_out[0], logical));
+  IpAttnArgs a;
+  a.Q = (const half_t*)ops.at(TSD_PO_Q); a.ldq = (int)d[TSD_PD_LDQ]; a.sQ = d[TSD_PD_SQB];
+  a.K = (const half_t*)ops.at(TSD_PO_K); a.ldk = (int)d[TSD_PD_LDK]; a.sK = d[TSD_PD_SKB];
+  a.Vt = (const half_t*)ops.at(TSD_PO_VT); a.ldvt = (int)d[TSD_PD_LDVT]; a.sVt = d[TSD_PD_SVTB];
+  a.O = (half_t*)ops.at(TSD_PO_O); a.ldo = (int)d[TSD_PD_LDO]; a.sO = d[TSD_PD_SOB];
+  a.s = (const float*)ops.at(TSD_PO_S);
+  a.B = (int)d[TSD_PD_B]; a.H = (int)d[TSD_PD_H]; a.d = (int)d[TSD_PD_D]; a.S = (int)d[TSD_PD_S]; a.N = (int)d[TSD_PD_N];
+  a.scale = f32_of(d[TSD_PD_SCALE]);
+  const int r = run_planned(ctx, [&]() -> int { return launch_ip_attn_add(ctx, a); });
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  TSD_TRY(ops.read_back(&info[TSD_PI_CHANGED]));
+  return r;
+}

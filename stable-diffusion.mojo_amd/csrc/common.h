@@ -580,6 +580,21 @@ struct AttnArgs {
 };
 bool attn_fused_supported(int d);
 
+// IP-Adapter's decoupled cross attention (kernels_ipattn.hip states the formula): O <- rn16(O + s_b * Attn(Q, K_ip, V_ip)) in place over
+// N <= 16 image tokens, one launch.  K: [b][j][h*d + c] token-major, at least N rows; Vt: [b][h*d + c][j], ldvt >= 16 (keys j >= N of
+// either operand never reach the result); s: device fp32 [B], a sample whose scale is exactly 0 is neither read nor written.
+enum { IP_MAX_TOKENS = 16 };
+struct IpAttnArgs {
+  const half_t* Q = nullptr; int ldq = 0; int64_t sQ = 0;
+  const half_t* K = nullptr; int ldk = 0; int64_t sK = 0;
+  const half_t* Vt = nullptr; int ldvt = 0; int64_t sVt = 0;
+  half_t* O = nullptr; int ldo = 0; int64_t sO = 0;
+  const float* s = nullptr;
+  int B = 0, H = 0, d = 0, S = 0, N = 0;
+  float scale = 1.f;
+};
+int launch_ip_attn_add(tsd_ctx* ctx, const IpAttnArgs& a);
+
 // fused row-local tail of `Unet_Attention_Block.forward` (kernels_chain.hip): self-attention out_proj + residual, LayerNorm,
 // cross-attention over the projected context, LayerNorm, GEGLU feed-forward, 1x1 conv_out + long residual in ONE kernel.
 struct AttnTailArgs {

@@ -189,7 +189,7 @@ int g_resblock(tsd_ctx* ctx, const CatSrc& x, int B, int Hin, int Win, int ups, 
 
 // `Unet_Attention_Block.forward` diffusion.mojo:112-147 on NHWC tokens
 int g_unet_attn(tsd_ctx* ctx, const Act& x, const AttnW& w, const half_t* ctx16, int T, int Tp, Act& out,
-                const CtxKV* pre) {
+                const CtxKV* pre, const IpKV* ipkv) {
   const int C = w.C, B = x.B, S = x.H * x.W, d = w.n_embed, Hh = w.n_head;
   const int64_t M = (int64_t)B * S;
   if (C % 64 || x.C != C) TSD_FAIL(TSD_E_SHAPE, "attention block: C=%d (input %d) unsupported", C, x.C);
@@ -208,7 +208,8 @@ int g_unet_attn(tsd_ctx* ctx, const Act& x, const AttnW& w, const half_t* ctx16,
   // The block's head - GroupNorm-apply, conv_in, LayerNorm, q / k / V^T projections - is local to a token row as well once
   // the GroupNorm statistics are known (the producer's epilogue emitted them): one kernel at the 64x64 level.
   const half_t* head_stream = w.head_stream;
-  const bool head_ok = Sp == S && x.ld % 8 == 0 && attn_tail_supported(ctx, C, d, Hh, 1, M, S) && attn_head_weights_ok(w);
+  // an IP-Adapter block runs op by op: its launch sits between the cross-attention core and out_proj, inside what the tail kernel fuses
+  const bool head_ok = !ipkv && Sp == S && x.ld % 8 == 0 && attn_tail_supported(ctx, C, d, Hh, 1, M, S) && attn_head_weights_ok(w);
   if (head_ok && !head_stream && !pre) {  // block-level entry: no model, pack on the fly
     half_t* hs = arena_alloc<half_t>(ctx, (int64_t)attn_head_stream_bytes() / 2); CHECK_ALLOC(hs);
     TSD_TRY(launch_attn_head_pack(ctx, w.conv_in.w, w.conv_in.Ipad, w.sa_in.w, w.sa_in.Kpad, hs));
@@ -285,7 +286,7 @@ int g_unet_attn(tsd_ctx* ctx, const Act& x, const AttnW& w, const half_t* ctx16,
   // op-by-op path).
   // The block-level entry (no model) packs the stream into the workspace on the fly.
   const half_t* tail_stream = w.tail_stream;
-  const bool tail_ok = attn_tail_supported(ctx, C, d, Hh, T, M, S) && attn_tail_weights_ok(w);
+  const bool tail_ok = !ipkv && attn_tail_supported(ctx, C, d, Hh, T, M, S) && attn_tail_weights_ok(w);
   if (tail_ok && !tail_stream && !pre) {
     half_t* ts = arena_alloc<half_t>(ctx, (int64_t)attn_tail_stream_bytes() / 2); CHECK_ALLOC(ts);
     TSD_TRY(launch_attn_tail_pack(ctx, w.sa_out.w, w.sa_out.Kpad, w.ca_q.w, w.ca_q.Kpad, w.ca_out.w, w.ca_out.Kpad, w.geglu1.w,
@@ -320,6 +321,15 @@ int g_unet_attn(tsd_ctx* ctx, const Act& x, const AttnW& w, const half_t* ctx16,
   fa.Vt = kv.Vt; fa.ldvt = kv.ldvt; fa.sVt = kv.sVt;
   fa.Sk = T;
   TSD_TRY(launch_flash_attention(ctx, fa));
+  if (ipkv) {  // ao <- ao + s_b * Attn(q, K_ip, V_ip) over the image tokens, in place (kernels_ipattn.hip)
+    IpAttnArgs ia;
+    ia.Q = q; ia.ldq = C; ia.sQ = (int64_t)S * C;
+    ia.K = ipkv->K; ia.ldk = ipkv->ldk; ia.sK = ipkv->sK;
+    ia.Vt = ipkv->Vt; ia.ldvt = ipkv->ldvt; ia.sVt = ipkv->sVt;
+    ia.O = ao; ia.ldo = C; ia.sO = (int64_t)S * C;
+    ia.s = ipkv->scale; ia.B = B; ia.H = Hh; ia.d = d; ia.S = S; ia.N = ipkv->N; ia.scale = scale;
+    TSD_TRY(launch_ip_attn_add(ctx, ia));
+  }
   half_t* tok3 = tok;  // tok (first residual) is dead after tok2 was produced
   a.p0 = ao;
   TSD_TRY(g_linear(ctx, a, M, w.ca_out.w, w.ca_out.Kpad, C, C, w.ca_out.b, tok2, C, 0, tok3, C, nullptr, S, w.ca_out.w_tm));
@@ -487,15 +497,22 @@ int g_unet_ctx_kv(tsd_model* m, const half_t* ctx16, int Tp, int B, half_t* kc_a
 // ---- `Diffusion.forward` diffusion.mojo:309-318 -------------------------------------------------------
 static int g_unet_full_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, int T, int Tp,
                                const float* temb, int B, int LH, int LW, float* eps_out_chw, bool eps_nhwc, const UNetPre* pre,
-                               const ControlRes* control, const float* control_scale);
+                               const ControlRes* control, const float* control_scale, const IpRun* ip);
 
 int g_unet_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, int T, int Tp, const float* temb, int B,
                    int LH, int LW, float* eps_out_chw, bool eps_nhwc, const UNetPre* pre, const ControlRes* control,
-                   const float* control_scale) {
+                   const float* control_scale, const IpRun* ip) {
   if (control && !control_scale) TSD_FAIL(TSD_E_ARG, "UNet: control residuals without per-sample scales");
+  if (ip) {
+    if (m->kind != TSD_MODEL_DIFFUSION_SD15 && m->kind != TSD_MODEL_DIFFUSION_SD15_TORCH)
+      TSD_FAIL(TSD_E_ARG, "UNet: an IP-Adapter applies to the full-size SD-1.x kinds only (this model is kind %d)", m->kind);
+    if (!ip->ip || !is_ip_adapter_kind(ip->ip->kind) || !ip->k_all || !ip->vt_all || !ip->scale) TSD_FAIL(TSD_E_ARG, "UNet: incomplete IP-Adapter operands");
+    if (ip->N < 1 || ip->N > IP_MAX_TOKENS) TSD_FAIL(TSD_E_ARG, "UNet: %d image tokens (1..%d)", ip->N, IP_MAX_TOKENS);
+    if (ip->ip->unet.kproj_all.N != m->unet.kproj_all.N) TSD_FAIL(TSD_E_ARG, "UNet: the IP-Adapter's %d key rows do not match the UNet's %d", ip->ip->unet.kproj_all.N, m->unet.kproj_all.N);
+  }
   if (is_full_unet_kind(m->kind)) {
     const int prev = gemm_set_splitk_big(m->ctx, 4);  // measured for this graph at its batch of 4 (BASELINE configs[4]): +4.3 %
-    const int r = g_unet_full_forward(m, latents_chw, ctx16, T, Tp, temb, B, LH, LW, eps_out_chw, eps_nhwc, pre, control, control_scale);
+    const int r = g_unet_full_forward(m, latents_chw, ctx16, T, Tp, temb, B, LH, LW, eps_out_chw, eps_nhwc, pre, control, control_scale, ip);
     gemm_set_splitk_big(m->ctx, prev);
     return r;
   }
@@ -613,6 +630,7 @@ struct FullRun {
   const Act* in_res = nullptr;  // added to the input convolution's output through its residual slot (the ControlNet's hint features)
   // called with every tensor a step has pushed, in push order (the ControlNet's zero convolutions)
   int (*on_push)(void* self, int k, const Act& a) = nullptr; void* self = nullptr;
+  const IpRun* ip = nullptr;  // IP-Adapter: every attention block of the run reads its slice (the UNet only: a ControlNet's blocks never do)
 };
 
 // Steps [i0, i1) of SD15_STEPS on `cur` and the skip stack: the UNet runs [0, SD15_ENC_N) and [SD15_ENC_N, SD15_N), a ControlNet the first
@@ -663,7 +681,16 @@ static int unet_full_steps(const FullRun& f, int i0, int i1, Act& cur, std::vect
       CtxKV kv;
       kv.K = f.kc_all + w.kv_off; kv.ldk = CK; kv.sK = (int64_t)f.Tp * CK;
       kv.Vt = f.vtc_all + (int64_t)w.kv_off * f.Tp; kv.ldvt = f.Tp; kv.sVt = (int64_t)CK * f.Tp;
-      TSD_TRY(g_unet_attn(ctx, cur, w, f.ctx16, f.T, f.Tp, y, &kv));
+      IpKV ik;
+      if (f.ip) {  // the block's slice of the adapter's own packing
+        const IpAdapterW& iw = f.ip->ip->ip;
+        const int IK = f.ip->ip->unet.kproj_all.N;
+        if (iw.C[i] != w.C) TSD_FAIL(TSD_E_STATE, "full-size UNet: the IP-Adapter has %d channels at layer %d, the block %d", iw.C[i], i + 1, w.C);
+        ik.K = f.ip->k_all + iw.kv_off[i]; ik.ldk = IK; ik.sK = (int64_t)IP_MAX_TOKENS * IK;
+        ik.Vt = f.ip->vt_all + (int64_t)iw.kv_off[i] * IP_MAX_TOKENS; ik.ldvt = IP_MAX_TOKENS; ik.sVt = (int64_t)IK * IP_MAX_TOKENS;
+        ik.N = f.ip->N; ik.scale = f.ip->scale;
+      }
+      TSD_TRY(g_unet_attn(ctx, cur, w, f.ctx16, f.T, f.Tp, y, &kv, f.ip ? &ik : nullptr));
     }
     cur = y;
     if (st.flags & U_PUSH) {
@@ -733,13 +760,14 @@ static int unet_control_inject(tsd_ctx* ctx, std::vector<Act>& skips, Act& mid, 
 
 static int g_unet_full_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, int T, int Tp,
                                const float* temb, int B, int LH, int LW, float* eps_out_chw, bool eps_nhwc, const UNetPre* pre,
-                               const ControlRes* control, const float* control_scale) {
+                               const ControlRes* control, const float* control_scale, const IpRun* ip) {
   tsd_ctx* ctx = m->ctx;
   const UNetW& u = m->unet;
   if (LH <= 0 || LW <= 0 || LH % 16 || LW % 16) TSD_FAIL(TSD_E_SHAPE, "full-size UNet: latent sides %d x %d must be multiples of 16", LH, LW);
   FullRun f;
   Act x0;
   TSD_TRY(unet_full_begin(m, latents_chw, ctx16, T, Tp, temb, B, LH, LW, pre, &f, &x0));
+  f.ip = ip;
   std::vector<Act> skips;
   Act cur = x0;
   TSD_TRY(unet_full_steps(f, 0, SD15_ENC_N, cur, skips));
@@ -758,6 +786,39 @@ static int g_unet_full_forward(tsd_model* m, const float* latents_chw, const hal
   float* eps_tmp = arena_alloc<float>(ctx, (int64_t)B * LH * LW * 4); CHECK_ALLOC(eps_tmp);
   TSD_TRY(g_conv3x3(ctx, hf, u.final_conv, 1, 1, 1, 0, nullptr, 0, nullptr, 0, true, eps_tmp, 4));
   TSD_TRY(launch_nhwc_f32_to_chw_f32(ctx, eps_tmp, B, 4, LH, LW, 4, eps_out_chw));
+  return TSD_OK;
+}
+
+// ---- IP-Adapter (kind 20) ------------------------------------------------------------------------------------------------------------------
+// The adapter has no graph of its own: the image projection, the staging of the tokens as 16 fp16 rows per sample and the K / V^T GEMMs
+// over them; the UNet's attention blocks read the result (IpRun).
+int g_ip_stage_tokens(tsd_ctx* ctx, const float* tokens, int B, int N, half_t* tok16) {
+  if (N < 1 || N > IP_MAX_TOKENS) TSD_FAIL(TSD_E_ARG, "IP-Adapter: %d image tokens (1..%d)", N, IP_MAX_TOKENS);
+  for (int b = 0; b < B; b++)  // [N][768] -> zero-padded [16][768] per sample, as the context is staged
+    TSD_TRY(launch_f32_to_f16_rows(ctx, tokens + (int64_t)b * N * IP_CTX_DIM, N, IP_CTX_DIM, tok16 + (int64_t)b * IP_MAX_TOKENS * IP_CTX_DIM,
+                                   IP_CTX_DIM, IP_MAX_TOKENS));
+  return TSD_OK;
+}
+
+int g_ip_kv(tsd_model* ip, const half_t* tok16, int B, half_t* k_all, half_t* vt_all) {
+  if (!is_ip_adapter_kind(ip->kind)) TSD_FAIL(TSD_E_ARG, "g_ip_kv: model is not an IP-Adapter");
+  return g_unet_ctx_kv(ip, tok16, IP_MAX_TOKENS, B, k_all, vt_all);
+}
+
+int g_ip_project(tsd_model* ip, const float* embeds, int B, float* tokens_out) {
+  tsd_ctx* ctx = ip->ctx;
+  if (!is_ip_adapter_kind(ip->kind)) TSD_FAIL(TSD_E_ARG, "g_ip_project: model is not an IP-Adapter");
+  const IpAdapterW& w = ip->ip;
+  const int NT = w.n_tokens, D = IP_CTX_DIM;
+  const size_t mark = ctx->arena.mark();
+  float* lin = arena_alloc<float>(ctx, (int64_t)B * NT * D); CHECK_ALLOC(lin);
+  half_t* l16 = arena_alloc<half_t>(ctx, (int64_t)B * NT * D); CHECK_ALLOC(l16);
+  half_t* ln = arena_alloc<half_t>(ctx, (int64_t)B * NT * D); CHECK_ALLOC(ln);
+  TSD_TRY(launch_small_linear(ctx, embeds, B, w.proj.K, w.proj.K, w.proj.w, w.proj.Kpad, w.proj.b, NT * D, 0, lin, NT * D));
+  TSD_TRY(launch_f32_to_f16_rows(ctx, lin, (int64_t)B * NT, D, l16, D, (int64_t)B * NT));
+  TSD_TRY(launch_layernorm(ctx, l16, (int64_t)B * NT, D, D, 1e-5f, ln, D, &w.norm));
+  TSD_TRY(launch_f16_to_f32_rows(ctx, ln, (int64_t)B * NT, D, D, tokens_out));
+  ctx->arena.release(mark);
   return TSD_OK;
 }
 

@@ -60,8 +60,17 @@ struct CtxKV {  // projected context keys (token-major) and values (channel-majo
   const half_t* K = nullptr; int ldk = 0; int64_t sK = 0;
   const half_t* Vt = nullptr; int ldvt = 0; int64_t sVt = 0;
 };
+// IP-Adapter: one block's projected image tokens - K_ip token-major [b][16][.], V_ip^T channel-major [b][C][16], N <= 16 of them live - and
+// the per-sample scales, a device fp32 [B].  Present, the block runs op by op (also where the fused head / tail kernels would apply) and
+// launch_ip_attn_add runs between the cross-attention core and out_proj.
+struct IpKV {
+  const half_t* K = nullptr; int ldk = 0; int64_t sK = 0;
+  const half_t* Vt = nullptr; int ldvt = 0; int64_t sVt = 0;
+  int N = 0;
+  const float* scale = nullptr;
+};
 int g_unet_attn(tsd_ctx* ctx, const Act& x, const AttnW& w, const half_t* ctx16, int T, int Tp, Act& out,
-                const CtxKV* pre = nullptr);
+                const CtxKV* pre = nullptr, const IpKV* ipkv = nullptr);
 int g_vae_attn(tsd_ctx* ctx, const Act& x, const VaeAttnW& w, Act& out);
 int g_attn_core(tsd_ctx* ctx, const AttnArgs& fa);
 int g_qkv_proj(tsd_ctx* ctx, const half_t* x, int B, int S, int C, const LinW& in_proj, half_t* qk, half_t* vt, int Sp);
@@ -82,9 +91,25 @@ struct UNetPre {
 // bottleneck output), added to the full-size UNet's skips and bottleneck output scaled by control_scale, a device fp32 [B] - one launch
 // between the bottleneck and the first decoder step.  Absent, the forward enqueues what it always did.  The Tiny-SD graph refuses it.
 struct ControlRes { Act r[CONTROL_RESIDUALS]; };
+struct IpRun;
 int g_unet_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, int T, int Tp, const float* temb, int B,
                    int LH, int LW, float* eps_out_chw, bool eps_nhwc = false, const UNetPre* pre = nullptr,
-                   const ControlRes* control = nullptr, const float* control_scale = nullptr);
+                   const ControlRes* control = nullptr, const float* control_scale = nullptr, const IpRun* ip = nullptr);
+// IP-Adapter (kind 20) on the full-size SD-1.x UNet (kinds 5 / 6; everything else refuses it): the adapter's projected tokens of all 16
+// blocks, k_all [B*16][CK] and vt_all [B][CK][16] (CK = 12480, the adapter's own packing: IpAdapterW::kv_off), N live tokens, scale a
+// device fp32 [B].  Absent, the forward enqueues what it always did.
+struct IpRun {
+  const tsd_model* ip = nullptr;
+  const half_t* k_all = nullptr; const half_t* vt_all = nullptr;
+  int N = 0;
+  const float* scale = nullptr;
+};
+// tokens fp32 [B][N][768] (device) -> tok16 fp16 [B][16][768], rows N .. 15 zero (the pad keys must be finite)
+int g_ip_stage_tokens(tsd_ctx* ctx, const float* tokens, int B, int N, half_t* tok16);
+// K_ip / V_ip^T of all blocks from the staged tokens: g_unet_ctx_kv's GEMMs with Tp = 16 on the adapter's tables
+int g_ip_kv(tsd_model* ip, const half_t* tok16, int B, half_t* k_all, half_t* vt_all);
+// image_proj: embeds fp32 [B][1024] (device) -> tokens fp32 [B][n_tokens][768] (device) = LayerNorm(Linear(e)), every value an fp16
+int g_ip_project(tsd_model* ip, const float* embeds, int B, float* tokens_out);
 // ControlNet (kinds 10 / 11).  hint_chw: device fp32 [B,3,8LH,8LW] -> hint features fp16 NHWC [B,LH,LW,320] in the arena
 int g_controlnet_hint(tsd_model* m, const float* hint_chw, int B, int LH, int LW, Act* out);
 // pre: a UNetPre made from the ControlNet's OWN weights (g_unet_time_path / g_unet_ctx_kv on `m`), or nullptr

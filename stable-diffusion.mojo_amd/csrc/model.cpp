@@ -380,6 +380,7 @@ extern "C" int tsd_model_lora_add(tsd_model* m, int index, int row0, int rows, c
   if (!m || !up || !down) TSD_FAIL(TSD_E_ARG, "tsd_model_lora_add: NULL argument");
   TSD_TRY(param_checked(m, index, "tsd_model_lora_add"));
   if (is_controlnet_kind(m->kind)) TSD_FAIL(TSD_E_ARG, "lora_add: adapters on a ControlNet are not supported");
+  if (is_ip_adapter_kind(m->kind)) TSD_FAIL(TSD_E_ARG, "lora_add: adapters on an IP-Adapter are not supported");
   const ParamSpec& p = m->params[index];
   if (p.kind != P_CONV_W && p.kind != P_LIN_W) TSD_FAIL(TSD_E_ARG, "lora_add: %s is a bias / norm parameter, not a weight matrix", p.name.c_str());
   if (!p.used) TSD_FAIL(TSD_E_ARG, "lora_add: %s is never read by the forward", p.name.c_str());
@@ -807,6 +808,33 @@ LinW model_lin(const tsd_model* m, const std::string& prefix, bool use_bias) {
 }
 
 int model_resolve(tsd_model* m) {
+  if (is_ip_adapter_kind(m->kind)) {
+    IpAdapterW& ip = m->ip;
+    ip.n_tokens = IP_SD15_TOKENS;
+    ip.proj = model_lin(m, "image_proj.proj", true);
+    ip.norm.w = (const float*)(m->blob + m->params[m->index.at("image_proj.norm.weight")].off);
+    ip.norm.b = (const float*)(m->blob + m->params[m->index.at("image_proj.norm.bias")].off);
+    ip.norm.torch_rstd = 1;
+    int kvoff = 0, t = 0;
+    for (int i = 0; i < SD15_N; i++) {
+      const LayerDef& l = SD15_STEPS[i].l;
+      ip.kv_off[i] = 0; ip.C[i] = 0;
+      if (l.kind != L_ATTN) continue;
+      const std::string n = "ip_adapter." + std::to_string(ip_adapter_published_index(t++));
+      const ParamSpec& pk = m->params[m->index.at(n + ".to_k_ip.weight")];
+      const ParamSpec& pv = m->params[m->index.at(n + ".to_v_ip.weight")];
+      if (kvoff == 0) {  // the two tables are contiguous in the blob (regions 3 / 4), in the order of the list
+        LinW& k = m->unet.kproj_all; LinW& v = m->unet.vproj_all;
+        k.w = (const half_t*)(m->blob + pk.off); k.b = nullptr; k.K = (int)pk.shape[1]; k.Kpad = pk.Kpad;
+        v.w = (const half_t*)(m->blob + pv.off); v.b = nullptr; v.K = (int)pv.shape[1]; v.Kpad = pv.Kpad;
+      }
+      ip.kv_off[i] = kvoff; ip.C[i] = l.a * l.b;
+      kvoff += l.a * l.b;
+    }
+    ip.n_blocks = t;
+    m->unet.kproj_all.N = kvoff; m->unet.vproj_all.N = kvoff;  // 12480 rows each
+    return TSD_OK;
+  }
   if (is_diffusion_kind(m->kind) || is_controlnet_kind(m->kind)) {
     UNetW& u = m->unet;
     const bool cn = is_controlnet_kind(m->kind);

@@ -62,9 +62,17 @@ static inline bool is_controlnet_kind(int kind) { return kind == TSD_MODEL_CONTR
 static inline bool is_torch_unet_kind(int kind) {
   return kind == TSD_MODEL_DIFFUSION_SD15_TORCH || kind == TSD_MODEL_CONTROLNET_SD15_TORCH || kind == TSD_MODEL_DIFFUSION_SD2;
 }
-// 1 .. 11 and 16, 17; 12 .. 15 are reserved and refused
+// IP-Adapter of the SD-1.x full-size UNet (kind 20): the image projection and one to_k_ip / to_v_ip pair per cross-attention block of
+// SD15_STEPS, in the table's order; no graph of its own - the UNet's forward reads its projected keys / values (graph.h IpKV)
+constexpr int IP_SD15_TOKENS = 4, IP_EMBED_DIM = 1024, IP_CTX_DIM = 768;
+static inline bool is_ip_adapter_kind(int kind) { return kind == TSD_MODEL_IP_ADAPTER_SD15; }
+// `ip_adapter.<index>` of the published files for the t-th cross-attention block of SD15_STEPS (6 down, 1 mid, 9 up): the files count
+// diffusers' attention processors - down blocks, then up blocks, then the mid block - and the cross-attention ones are the odd numbers
+static inline int ip_adapter_published_index(int t) { return t < 6 ? 2 * t + 1 : (t == 6 ? 31 : 2 * t - 1); }
+// 1 .. 11, 16, 17 and 20; 12 .. 15, 18 and 19 are reserved and refused
 static inline bool is_model_kind(int kind) {
-  return (kind >= TSD_MODEL_DIFFUSION && kind <= TSD_MODEL_CONTROLNET_SD15_TORCH) || kind == TSD_MODEL_DIFFUSION_SD2 || kind == TSD_MODEL_CLIP_SD2;
+  return (kind >= TSD_MODEL_DIFFUSION && kind <= TSD_MODEL_CONTROLNET_SD15_TORCH) || kind == TSD_MODEL_DIFFUSION_SD2 || kind == TSD_MODEL_CLIP_SD2 ||
+         kind == TSD_MODEL_IP_ADAPTER_SD15;
 }
 
 std::vector<ParamSpec> build_param_specs(int model_kind);
@@ -149,6 +157,17 @@ struct ClipW {
   NormAffine final_ln;  // torch-norm extension (kind 7)
 };
 
+struct IpAdapterW {  // kind 20
+  int n_tokens = IP_SD15_TOKENS;
+  LinW proj;        // image_proj.proj: [n_tokens * 768][1024], with bias
+  NormAffine norm;  // image_proj.norm: LayerNorm(768) weight / bias, torch semantics
+  // to_k_ip / to_v_ip of the 16 blocks, contiguous in the blob in the step table's order ([12480][768] each, as kproj_all / vproj_all):
+  // they live in tsd_model::unet.kproj_all / vproj_all so that g_unet_ctx_kv projects the image tokens exactly as it projects a context
+  int n_blocks = 0;
+  int kv_off[SD15_N] = {};  // per flat layer position: row offset of the block in the two tables (as AttnW::kv_off)
+  int C[SD15_N] = {};       // per flat layer position: the block's width, 0 where the step is no attention block
+};
+
 struct PlanKey { int B, L, T; bool operator<(const PlanKey& o) const { return B != o.B ? B < o.B : (L != o.L ? L < o.L : T < o.T); } };
 
 struct tsd_model {
@@ -165,6 +184,7 @@ struct tsd_model {
   UNetW unet;
   VaeW vae;
   ClipW clip;
+  IpAdapterW ip;
   std::map<PlanKey, size_t> plans;  // workspace high-water mark per problem shape
   char* derived = nullptr;          // derived device buffers rebuilt by model_check_ready(): fused-tail weight streams
   size_t derived_bytes = 0;

@@ -96,6 +96,13 @@ struct Builder {
     b.bound = w.bound; b.Opad = fout; b.interleave = interleave; b.region = region == 1 ? 2 : 0;
     out.push_back(b);
   }
+  void linw(const std::string& name, int fin, int fout, int region) {  // a weight matrix with no bias entry behind it (IP-Adapter's to_k_ip / to_v_ip)
+    ParamSpec w;
+    w.name = name + ".weight"; w.ndim = 2; w.shape[0] = fout; w.shape[1] = fin; w.kind = P_LIN_W;
+    w.bound = (float)(1.0 / sqrt((double)fin));
+    w.Kpad = round_up(fin, 64); w.Opad = fout; w.region = region;
+    out.push_back(w);
+  }
   void norm(const std::string& name, int C) {  // torch-norm extension: per-channel weight (1 + U) and bias
     ParamSpec w;
     w.name = name + ".weight"; w.ndim = 1; w.shape[0] = C; w.kind = P_LIN_B; w.bound = 0.3f; w.offset = 1.f; w.Opad = C;
@@ -211,6 +218,16 @@ std::vector<ParamSpec> build_param_specs(int kind) {
           b.norm(n + ".layer1", C); b.norm(n + ".layer3", C); b.norm(n + ".layer5", C); b.norm(n + ".layer7", C);
         }
       }
+  } else if (is_ip_adapter_kind(kind)) {  // the published IP-Adapter files' names; the 16 pairs in the step table's order
+    b.lin("image_proj.proj", IP_EMBED_DIM, IP_SD15_TOKENS * IP_CTX_DIM);
+    b.norm("image_proj.norm", IP_CTX_DIM);
+    for (int i = 0, t = 0; i < SD15_N; i++) {
+      const LayerDef& l = SD15_STEPS[i].l;
+      if (l.kind != L_ATTN) continue;
+      const std::string n = "ip_adapter." + std::to_string(ip_adapter_published_index(t++));
+      b.linw(n + ".to_k_ip", IP_CTX_DIM, l.a * l.b, 3);
+      b.linw(n + ".to_v_ip", IP_CTX_DIM, l.a * l.b, 4);
+    }
   } else if (is_clip_kind(kind)) {  // clip.mojo:74-88 ; parameter order = oracle/spec.py clip_params()
     ParamSpec t;
     const int W = clip_kind_width(kind), NL = clip_kind_layers(kind);

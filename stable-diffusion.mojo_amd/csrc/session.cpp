@@ -104,6 +104,16 @@ struct tsd_session {
   float* cn_ttab = nullptr;
   size_t cn_kv_cap = 0, cn_ttab_cap = 0;
   unsigned cn_gen = 0;        // generation of the ControlNet's parameters at the last build
+  // IP-Adapter (tsd_session_set_ip_adapter): lockstep sessions on a full-size SD-1.x UNet.  Everything it needs is built by the setter,
+  // once - the image tokens do not depend on the step, the context or the schedule - and stays until set_ip_adapter(NULL): upload()
+  // rebuilds nothing of it.  A step inside [ip_first, ip_last] hands the buffers to the forward; every other step enqueues what it always did.
+  tsd_model* ip = nullptr;    // nullptr: no adapter
+  int ip_first = 0, ip_last = -1, ip_N = 0;
+  float ip_scale_host = 0.f;  // the one scale of every sample
+  char* ipb = nullptr;        // scale [16] fp32 | K_ip fp16 [Bu*16][IK] | V_ip^T fp16 [Bu][IK][16]
+  float* ip_scale = nullptr;
+  half_t* ip_k = nullptr; half_t* ip_vt = nullptr;
+  size_t ipb_cap = 0;
 };
 
 // inf / NaN scan of a downloaded tensor (exponent bits all ones); the buffers at this boundary are 0.5 - 25 MB
@@ -299,7 +309,17 @@ static int session_refresh(tsd_session* s) {
 // where the forward can write it; the updates read it as such (no conversion launch): *eps_hw is their eps_hw argument.
 // control_i >= 0: step control_i lies in the window of a session with control - the ControlNet forward on the same inputs first, its
 // residuals in the arena, then the UNet forward with them; no copy from the host and no allocation.
-static int session_forward(tsd_session* s, const UNetPre* pre, int* eps_hw, int control_i = -1) {
+static bool session_adapts(const tsd_session* s, int i) {
+  // at scale 0 the adapter adds nothing: such a step is the plain one, as tsd_diffusion_forward_ip_hw with every scale 0 is the plain forward
+  return s->ip && s->ip_scale_host != 0.f && i >= s->ip_first && (s->ip_last < 0 || i <= s->ip_last);
+}
+static IpRun session_ip_run(const tsd_session* s) {
+  IpRun r;
+  r.ip = s->ip; r.k_all = s->ip_k; r.vt_all = s->ip_vt; r.N = s->ip_N; r.scale = s->ip_scale;
+  return r;
+}
+// adapt: the step lies in the window of a session with an IP-Adapter - the UNet's attention blocks read the keys / values the setter built.
+static int session_forward(tsd_session* s, const UNetPre* pre, int* eps_hw, int control_i = -1, bool adapt = false) {
   tsd_ctx* ctx = s->ctx;
   const size_t nl = (size_t)s->B * 4 * s->LH * s->LW;
   const float* lat_in = s->latents;
@@ -317,8 +337,9 @@ static int session_forward(tsd_session* s, const UNetPre* pre, int* eps_hw, int 
     const UNetPre cpre = s->hoist ? session_control_pre(s, control_i) : UNetPre();
     TSD_TRY(g_controlnet_forward(s->cn, lat_in, s->ctx16, s->T, s->Tp, s->temb, hf, s->Bu, s->LH, s->LW, s->hoist ? &cpre : nullptr, &res));
   }
+  const IpRun ipr = adapt ? session_ip_run(s) : IpRun();
   TSD_TRY(g_unet_forward(s->unet, lat_in, s->ctx16, s->T, s->Tp, s->temb, s->Bu, s->LH, s->LW, s->eps, eps_nhwc, s->hoist ? pre : nullptr,
-                         control_i >= 0 ? &res : nullptr, control_i >= 0 ? s->ctl_scale : nullptr));
+                         control_i >= 0 ? &res : nullptr, control_i >= 0 ? s->ctl_scale : nullptr, adapt ? &ipr : nullptr));
   ctx->arena.top = 0;
   *eps_hw = eps_nhwc ? s->LH * s->LW : 0;
   return TSD_OK;
@@ -394,6 +415,7 @@ extern "C" int tsd_session_destroy(tsd_session* s) {
   if (s->ctl) hipFree(s->ctl);
   if (s->cn_kv) hipFree(s->cn_kv);
   if (s->cn_ttab) hipFree(s->cn_ttab);
+  if (s->ipb) hipFree(s->ipb);
   delete s;
   return TSD_OK;
 }
@@ -461,8 +483,10 @@ static int session_control_prepare(tsd_session* s) {
   hf.p = s->ctl_feat; hf.B = Bu; hf.H = LH; hf.W = LW; hf.C = 320; hf.ld = 320;
   ControlRes res;
   int r = g_controlnet_forward(s->cn, s->lat2, s->ctx16, T, Tp, s->temb, hf, Bu, LH, LW, s->hoist ? &cpre0 : nullptr, &res);
+  const IpRun ipr = s->ip ? session_ip_run(s) : IpRun();  // with an adapter set as well, the larger of the two forwards
   if (r == TSD_OK)
-    r = g_unet_forward(s->unet, s->lat2, s->ctx16, T, Tp, s->temb, Bu, LH, LW, s->eps, false, s->hoist ? &pre0 : nullptr, &res, s->ctl_scale);
+    r = g_unet_forward(s->unet, s->lat2, s->ctx16, T, Tp, s->temb, Bu, LH, LW, s->eps, false, s->hoist ? &pre0 : nullptr, &res, s->ctl_scale,
+                       s->ip ? &ipr : nullptr);
   size_t need = a.peak;
   if (r == TSD_OK && s->hoist) {  // session_build_control_invariants' scratch
     const float* tv = nullptr;
@@ -659,7 +683,7 @@ extern "C" int tsd_session_step(tsd_session* s, int i) {
   if (!s->hoist) TSD_TRY(launch_time_embedding(s->ctx, nullptr, (float)s->timesteps[i], s->Bu, s->temb));
   const UNetPre pre = s->hoist ? session_pre(s, i) : UNetPre();
   int eps_hw = 0;
-  TSD_TRY(session_forward(s, &pre, &eps_hw, session_controls(s, i) ? i : -1));
+  TSD_TRY(session_forward(s, &pre, &eps_hw, session_controls(s, i) ? i : -1, session_adapts(s, i)));
   int idx[16];
   bool hist_valid[16];
   std::fill(idx, idx + 16, i);  // an advance with every sample at index i, under the lockstep history rule
@@ -722,6 +746,77 @@ extern "C" int tsd_session_set_control(tsd_session* s, tsd_model* cn, const floa
   return ctx_check_status(ctx);
 }
 extern "C" int tsd_session_control_active(tsd_session* s) { return s ? (s->cn ? 1 : 0) : TSD_E_ARG; }
+
+// IP-Adapter for the steps first_step <= i <= last_step (last_step < 0: to the end) of a lockstep session on a full-size SD-1.x UNet;
+// ip == NULL turns it off.  tokens / uncond_tokens: host fp32 [B][N][768] for the two halves of the UNet's batch (uncond_tokens is read
+// under CFG only).  The tokens are staged and K_ip / V_ip^T of all 16 blocks are projected here, once, at the UNet's batch - the launches
+// of tsd_diffusion_forward_ip_hw at that batch - into buffers of the session; the per-sample scales are uploaded once.  Synchronous.
+extern "C" int tsd_session_set_ip_adapter(tsd_session* s, tsd_model* ip, const float* tokens, const float* uncond_tokens, int N, float scale,
+                                          int first_step, int last_step) {
+  NOTNULL(s);
+  SESSION_NOT_SLOTS(s, "set_ip_adapter()");
+  if (!ip) { s->ip = nullptr; return TSD_OK; }
+  NOTNULL(tokens);
+  if (s->unet->kind != TSD_MODEL_DIFFUSION_SD15 && s->unet->kind != TSD_MODEL_DIFFUSION_SD15_TORCH)
+    TSD_FAIL(TSD_E_ARG, "session: set_ip_adapter needs a full-size SD-1.x UNet (an IP-Adapter of this kind fits no other graph)");
+  if (!is_ip_adapter_kind(ip->kind)) TSD_FAIL(TSD_E_ARG, "session: set_ip_adapter: the model is not an IP-Adapter");
+  if (ip->ctx != s->ctx) TSD_FAIL(TSD_E_ARG, "session: set_ip_adapter: the IP-Adapter belongs to another context");
+  if (N < 1 || N > IP_MAX_TOKENS) TSD_FAIL(TSD_E_ARG, "session: set_ip_adapter: %d image tokens (1..%d)", N, IP_MAX_TOKENS);
+  if (!(fabsf(scale) <= 3.4028235e38f)) TSD_FAIL(TSD_E_ARG, "session: set_ip_adapter: the scale is not finite");
+  if (first_step < 0 || (last_step >= 0 && last_step < first_step)) TSD_FAIL(TSD_E_ARG, "session: set_ip_adapter: window [%d, %d]", first_step, last_step);
+  if (s->cfg && !uncond_tokens) TSD_FAIL(TSD_E_ARG, "session: set_ip_adapter: a CFG session needs uncond_tokens (the projection of a zero embedding)");
+  if (!s->uploaded) TSD_FAIL(TSD_E_STATE, "session: upload() before set_ip_adapter() (the workspace is sized for the uploaded session)");
+  SESSION_NOT_POISONED(s);
+  TSD_TRY(session_options_unchanged(s, "upload()"));
+  tsd_ctx* ctx = s->ctx;
+  HIP_TRY(hipSetDevice(ctx->device));
+  TSD_TRY(model_check_ready(ip));
+  if (s->cn) TSD_TRY(model_check_ready(s->cn));
+  const int B = s->B, Bu = s->Bu, LH = s->LH, LW = s->LW, T = s->T, Tp = s->Tp;
+  const int IK = ip->unet.kproj_all.N;
+  const size_t ntok = (size_t)B * N * IP_CTX_DIM, k_bytes = ((size_t)Bu * IP_MAX_TOKENS * IK * 2 + 255) & ~size_t(255);
+  s->ip = nullptr;  // until everything below succeeded
+  TSD_TRY(session_grow((void**)&s->ipb, &s->ipb_cap, 256 + 2 * k_bytes, "IP-Adapter K/V"));
+  s->ip_scale = (float*)s->ipb; s->ip_k = (half_t*)(s->ipb + 256); s->ip_vt = (half_t*)(s->ipb + 256 + k_bytes);
+  float sc[16] = {};
+  for (int b = 0; b < Bu; b++) sc[b] = scale;
+  TSD_TRY(ctx_reserve_staging(ctx, (size_t)Bu * N * IP_CTX_DIM * 4));
+  float* dtok = (float*)ctx->staging;
+  HIP_TRY(hipMemcpyAsync(s->ip_scale, sc, sizeof(sc), hipMemcpyHostToDevice, ctx->stream));
+  HIP_TRY(hipMemcpyAsync(dtok, tokens, ntok * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (s->cfg) HIP_TRY(hipMemcpyAsync(dtok + ntok, uncond_tokens, ntok * 4, hipMemcpyHostToDevice, ctx->stream));
+  TSD_TRY(run_planned(ctx, [&]() -> int {
+    half_t* tok16 = arena_alloc<half_t>(ctx, (int64_t)Bu * IP_MAX_TOKENS * IP_CTX_DIM);
+    if (!tok16) TSD_FAIL(TSD_E_ALLOC, "workspace arena exhausted");
+    TSD_TRY(g_ip_stage_tokens(ctx, dtok, Bu, N, tok16));
+    return g_ip_kv(ip, tok16, Bu, s->ip_k, s->ip_vt);
+  }));
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  s->ip = ip; s->ip_N = N; s->ip_first = first_step; s->ip_last = last_step; s->ip_scale_host = scale;
+  // the workspace of an adapted step (every attention block op by op), with the ControlNet's forward in front where one is set
+  Arena& a = ctx->arena;
+  a.planning = true; a.top = 0; a.peak = 0;
+  const UNetPre pre0 = s->hoist ? session_pre(s, 0) : UNetPre();
+  const IpRun ipr = session_ip_run(s);
+  ControlRes res;
+  int r = TSD_OK;
+  if (s->cn) {
+    const UNetPre cpre0 = s->hoist ? session_control_pre(s, 0) : UNetPre();
+    Act hf;
+    hf.p = s->ctl_feat; hf.B = Bu; hf.H = LH; hf.W = LW; hf.C = 320; hf.ld = 320;
+    r = g_controlnet_forward(s->cn, s->lat2, s->ctx16, T, Tp, s->temb, hf, Bu, LH, LW, s->hoist ? &cpre0 : nullptr, &res);
+  }
+  if (r == TSD_OK)
+    r = g_unet_forward(s->unet, s->lat2, s->ctx16, T, Tp, s->temb, Bu, LH, LW, s->eps, false, s->hoist ? &pre0 : nullptr, s->cn ? &res : nullptr,
+                       s->cn ? s->ctl_scale : nullptr, &ipr);
+  const size_t need = a.peak;
+  a.planning = false; a.top = 0; a.peak = 0;
+  if (r == TSD_OK) r = ctx_reserve_arena(ctx, need);
+  if (r != TSD_OK) { s->ip = nullptr; return r; }
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  return ctx_check_status(ctx);
+}
+extern "C" int tsd_session_ip_adapter_active(tsd_session* s) { return s ? (s->ip ? 1 : 0) : TSD_E_ARG; }
 
 extern "C" int tsd_session_add_noise(tsd_session* s, int i, const float* noise) {
   NOTNULL(s); NOTNULL(noise);
@@ -897,6 +992,7 @@ extern "C" int tsd_session_download_images(tsd_session* s, int rescale_0_255, fl
 extern "C" int tsd_session_slots_open(tsd_session* s) {
   NOTNULL(s);
   if (s->cn) TSD_FAIL(TSD_E_STATE, "session: slots_open() on a session with a ControlNet (per-slot control is not supported); set_control(NULL) first");
+  if (s->ip) TSD_FAIL(TSD_E_STATE, "session: slots_open() on a session with an IP-Adapter (per-slot adapters are not supported); set_ip_adapter(NULL) first");
   tsd_ctx* ctx = s->ctx;
   HIP_TRY(hipSetDevice(ctx->device));
   const int B = s->B, Bu = s->Bu;

@@ -3,7 +3,8 @@
   tsd.utils      <-> helpers/utils.mojo     Conv2D, GroupNorm, SiLU, Gelu, Linear, Upsample, LayerNorm, Softmax, ...
   tsd.attention  <-> helpers/attention.mojo Self_Attention, Cross_Attention
   tsd.diffusion  <-> diffusion.mojo         Time_Embedding, Unet_Residual_Block, Unet_Attention_Block, UNet, Diffusion
-                 (+ ControlNet, which has no reference counterpart: spatial conditioning of the full-size UNet, Diffusion.forward(control=...))
+                 (+ ControlNet, which has no reference counterpart: spatial conditioning of the full-size UNet, Diffusion.forward(control=...);
+                  and IPAdapter: image-prompt tokens through decoupled cross attention, Diffusion.forward(ip_adapter=...))
   tsd.vae        <-> vae.mojo               Attention_Block, Res_Block, Decoder, Encoder
   tsd.sampler    <-> sampler.mojo           DDPMSampler (+ DDIMSampler, DPMSolverMultistepSampler: no reference counterpart)
   tsd.clip       <-> clip.mojo              CLIP text encoder (token ids -> context)
@@ -21,9 +22,9 @@ from . import ext  # noqa: F401  (non-reference extensions: torch-style norms)
 from ._lib import Context, TsdError, default_context, set_default_context, set_strict  # noqa: F401
 from .model import Model, Session, flop_count, param_specs  # noqa: F401
 from .utils import (Conv2D, Gelu, GroupNorm, LayerNorm, Linear, SiLU, Softmax, Upsample, alphas_cumprod, cfg_rescale, concat,  # noqa: F401
-                    control_inject, ddpm_step, get_time_embedding, inpaint_blend, latent_mask, matmul, normal_fill, pad, rescale, sampler_step_v)
+                    control_inject, ddpm_step, get_time_embedding, inpaint_blend, ip_attn_add, latent_mask, matmul, normal_fill, pad, rescale, sampler_step_v)
 from .attention import Cross_Attention, Self_Attention  # noqa: F401
-from .diffusion import (ControlNet, Diffusion, Time_Embedding, UNet, UNet_Output_Layer, Unet_Attention_Block,  # noqa: F401
+from .diffusion import (ControlNet, Diffusion, IPAdapter, Time_Embedding, UNet, UNet_Output_Layer, Unet_Attention_Block,  # noqa: F401
                         Unet_Residual_Block)
 from .vae import Attention_Block, Decoder, Encoder, Res_Block  # noqa: F401
 from .clip import CLIP  # noqa: F401

@@ -280,6 +280,63 @@ def load_controlnet(path_or_state, ctx=None, prefix=""):
     return ControlNet(ctx=ctx, params=controlnet_params_complete(diffusers_controlnet_to_params(state, prefix)), variant="controlnet_sd15_torch")
 
 
+# ---- IP-Adapter (the published ip-adapter_sd15 safetensors -> model kind "ip_adapter_sd15") ------------------------------------------------
+# widths of the 16 cross-attention blocks in the published files' order: `ip_adapter.{1, 3, .., 31}`
+IP_ADAPTER_PUBLISHED_WIDTHS = (320, 320, 640, 640, 1280, 1280) + (1280,) * 3 + (640,) * 3 + (320,) * 3 + (1280,)
+
+
+def ip_adapter_to_params(state, prefix=""):
+    """Published IP-Adapter state dict -> {our parameter name: array} for kind "ip_adapter_sd15".
+
+    THE KEY MAP (the single place to correct it).  The published file holds `image_proj.proj.{weight,bias}`, `image_proj.norm.{weight,bias}`
+    and `ip_adapter.<i>.to_k_ip.weight` / `ip_adapter.<i>.to_v_ip.weight` for i = 1, 3, .., 31.  The odd index 2k + 1 is the k-th
+    cross-attention processor in diffusers' module order (every transformer block has a self-attention processor, even index, in front of
+    it): the down blocks (k = 0 .. 5, widths 320, 320, 640, 640, 1280, 1280), then the up blocks (k = 6 .. 14, widths 1280 x3, 640 x3,
+    320 x3), then the mid block (k = 15, width 1280).  The model keeps these names; only its ORDER differs - the step table's: the six
+    encoder blocks (1 .. 11), the bottleneck (31), the nine decoder blocks (13 .. 29).  This order is stated from the layout of diffusers'
+    UNet2DConditionModel, not checked against a real file here: a file whose 16 widths do not follow the sequence above is refused
+    (ValueError), so a different processor order cannot load silently."""
+    g = lambda k: np.asarray(state[prefix + k], dtype=np.float32)  # noqa: E731
+    out = {k: g(k) for k in ("image_proj.proj.weight", "image_proj.proj.bias", "image_proj.norm.weight", "image_proj.norm.bias")}
+    widths = []
+    for k in range(16):
+        for f in ("to_k_ip", "to_v_ip"):
+            name = f"ip_adapter.{2 * k + 1}.{f}.weight"
+            if prefix + name not in state:
+                raise KeyError(f"checkpoint has no tensor {prefix + name}")
+            out[name] = g(name)
+        wk, wv = out[f"ip_adapter.{2 * k + 1}.to_k_ip.weight"].shape, out[f"ip_adapter.{2 * k + 1}.to_v_ip.weight"].shape
+        if wk != wv or len(wk) != 2:
+            raise ValueError(f"ip_adapter.{2 * k + 1}: to_k_ip {wk} and to_v_ip {wv} differ in shape")
+        widths.append(int(wk[0]))
+    if tuple(widths) != IP_ADAPTER_PUBLISHED_WIDTHS:
+        raise ValueError(f"the 16 cross-attention widths of this file are {widths}; the key map assumes {list(IP_ADAPTER_PUBLISHED_WIDTHS)} "
+                         "(down blocks, up blocks, mid block): see ip_adapter_to_params")
+    return out
+
+
+def params_to_ip_adapter(params, prefix=""):
+    """Inverse of `ip_adapter_to_params` (export; used by the round-trip test): the published key layout, in the published order."""
+    names = ["image_proj.proj.weight", "image_proj.proj.bias", "image_proj.norm.weight", "image_proj.norm.bias"]
+    names += [f"ip_adapter.{2 * k + 1}.{f}.weight" for k in range(16) for f in ("to_k_ip", "to_v_ip")]
+    return {prefix + n: np.asarray(params[n], np.float32) for n in names}
+
+
+def load_ip_adapter(path_or_state, ctx=None, prefix=""):
+    """tsd.IPAdapter with the weights of a published SD-1.5 IP-Adapter file (ip-adapter_sd15: 4 image tokens from the 1024-wide CLIP image
+    embedding): a safetensors file, or its state dict.  The "plus" files (a resampler instead of image_proj.proj) are not supported."""
+    from .diffusion import IPAdapter
+    from .model import param_specs
+    state = read_safetensors(path_or_state) if isinstance(path_or_state, str) else path_or_state
+    if prefix + "image_proj.proj.weight" not in state:
+        raise KeyError("checkpoint has no image_proj.proj.weight: not an ip-adapter_sd15 file (the 'plus' files carry a resampler, which is not supported)")
+    params = ip_adapter_to_params(state, prefix)
+    for name, shape, _, _ in param_specs("ip_adapter_sd15"):
+        if tuple(np.shape(params[name])) != tuple(shape):
+            raise ValueError(f"{name}: checkpoint shape {np.shape(params[name])}, model expects {shape}")
+    return IPAdapter(ctx=ctx, params=params)
+
+
 def hf_clip_text_to_params(state):
     """Hugging Face CLIPTextModel state dict (with or without the `text_model.` prefix; tensors or arrays) ->
     {our parameter name: array} for kind "clip_torch" (q/k/v stacked into the reference's in_proj), or for kind "clip_sd2" when the

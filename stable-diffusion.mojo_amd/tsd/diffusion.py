@@ -165,16 +165,31 @@ class Diffusion:
         if params is not None:
             self.model.load_params(params)
 
-    def forward(self, x, context, time, control=None, hint=None, control_scale=1.0):
+    def forward(self, x, context, time, control=None, hint=None, control_scale=1.0, ip_adapter=None, ip_tokens=None, ip_scale=1.0):
         """control: a `ControlNet` on the same context, with hint (3,8LH,8LW) or (B,3,8LH,8LW) and control_scale a scalar or one value per
-        sample - the ControlNet's residuals, scaled per sample, are added to the skips and the bottleneck output (full-size variants)."""
+        sample - the ControlNet's residuals, scaled per sample, are added to the skips and the bottleneck output (full-size variants).
+        ip_adapter: an `IPAdapter` on the same context, with ip_tokens (N,768) or (B,N,768), 1 <= N <= 16 (`IPAdapter.project`, or tokens
+        from outside), and ip_scale a scalar or one value per sample - every cross-attention block adds the attention over the image
+        tokens, scaled per sample, to the text result (full-size SD-1.x variants; `tsd_diffusion_forward_ip_hw`).  Both compose."""
         xb, c, t, single = _forward_inputs(x, context, time)
         B, _, LH, LW = xb.shape
         W = self.model.context_width
         if c.ndim != 3 or c.shape[0] != B or c.shape[2] != W:
             raise ValueError(f"context must have shape (T, {W}) or ({B}, T, {W}), got {np.shape(context)}: this UNet reads a {W}-wide context")
         out = np.empty_like(xb)
-        if control is None:
+        if ip_adapter is None and ip_tokens is not None:
+            raise ValueError("ip_tokens are the IP-Adapter's input: pass ip_adapter= as well")
+        if ip_adapter is not None:
+            tok = _ip_tokens_input(ip_tokens, B)
+            si = np.ascontiguousarray(np.broadcast_to(np.asarray(ip_scale, dtype=np.float32), (B,)))
+            if control is None and hint is not None:
+                raise ValueError("hint is the ControlNet's input: pass control= as well")
+            h = _hint_input(hint, B, LH, LW) if control is not None else None
+            s = np.ascontiguousarray(np.broadcast_to(np.asarray(control_scale, dtype=np.float32), (B,))) if control is not None else None
+            code = lib().tsd_diffusion_forward_ip_hw(self.model.h, ip_adapter.model.h, ptr(tok), tok.shape[1], ptr(si),
+                                                     control.model.h if control is not None else None, ptr(h) if h is not None else None,
+                                                     ptr(s) if s is not None else None, ptr(xb), ptr(c), ptr(t), B, LH, LW, c.shape[1], ptr(out))
+        elif control is None:
             if hint is not None:
                 raise ValueError("hint is the ControlNet's input: pass control= as well")
             code = lib().tsd_diffusion_forward_hw(self.model.h, ptr(xb), ptr(c), ptr(t), B, LH, LW, c.shape[1], ptr(out))
@@ -184,6 +199,46 @@ class Diffusion:
             code = lib().tsd_diffusion_forward_control_hw(self.model.h, control.model.h, ptr(xb), ptr(c), ptr(t), ptr(h), ptr(s), B, LH, LW,
                                                           c.shape[1], ptr(out))
         if check(code, True):
+            return NULL_MATRIX()
+        return out[0] if single else out
+
+
+def _ip_tokens_input(tokens, B):
+    """Image tokens as a contiguous fp32 (B, N, 768) array, 1 <= N <= 16; (N, 768) is repeated for every sample."""
+    if tokens is None:
+        raise ValueError("an IP-Adapter needs its image tokens (IPAdapter.project(image_embeds))")
+    t = f32(tokens)
+    if t.ndim == 2:
+        t = t[None]
+    if t.ndim == 3 and t.shape[0] == 1 and B > 1:
+        t = np.repeat(t, B, axis=0)
+    if t.ndim != 3 or t.shape[0] != B or not (1 <= t.shape[1] <= 16) or t.shape[2] != 768:
+        raise ValueError(f"ip_tokens must have shape (N, 768) or ({B}, N, 768) with 1 <= N <= 16, got {np.shape(tokens)}")
+    return f32(t)
+
+
+class IPAdapter:
+    """IP-Adapter of the full-size SD-1.x UNet (Ye et al. 2023; the layout of the published ip-adapter_sd15 files) - device-resident
+    weights: the image projection and one to_k_ip / to_v_ip pair per cross-attention block (model kind "ip_adapter_sd15").
+    project(image_embeds) -> the N = 4 image tokens; `Diffusion.forward(ip_adapter=, ip_tokens=, ip_scale=)`, `Session.set_ip_adapter`
+    and `generate(ip_adapter=, ip_image_embeds=)` consume them.  The CLIP vision encoder is not part of it: callers bring the 1024-wide
+    image embedding (diffusers' `ip_adapter_image_embeds`).  See tsd.checkpoint.load_ip_adapter."""
+    N_TOKENS = 4
+
+    def __init__(self, seed=0, ctx=None, params=None):
+        self.model = Model("ip_adapter_sd15", ctx=ctx, seed=None if params is not None else seed)
+        if params is not None:
+            self.model.load_params(params)
+
+    def project(self, image_embeds):
+        """(1024,) or (B, 1024) image embeddings -> tokens (4, 768) / (B, 4, 768) = LayerNorm(Linear(e)) (`tsd_ip_adapter_project`)."""
+        e = f32(image_embeds)
+        single = e.ndim == 1
+        eb = f32(e[None] if single else e)
+        if eb.ndim != 2 or eb.shape[1] != 1024:
+            raise ValueError(f"image_embeds must have shape (1024,) or (B, 1024), got {e.shape}")
+        out = np.empty((eb.shape[0], self.N_TOKENS, 768), dtype=np.float32)
+        if check(lib().tsd_ip_adapter_project(self.model.h, ptr(eb), eb.shape[0], ptr(out)), True):
             return NULL_MATRIX()
         return out[0] if single else out
 

@@ -11,6 +11,7 @@ KINDS = {"diffusion": _lib.MODEL_DIFFUSION, "decoder": _lib.MODEL_DECODER, "enco
          "diffusion_sd15_torch": _lib.MODEL_DIFFUSION_SD15_TORCH, "clip_torch": _lib.MODEL_CLIP_TORCH,
          "decoder_torch": _lib.MODEL_DECODER_TORCH, "encoder_torch": _lib.MODEL_ENCODER_TORCH,
          "controlnet_sd15": _lib.MODEL_CONTROLNET_SD15, "controlnet_sd15_torch": _lib.MODEL_CONTROLNET_SD15_TORCH,
+         "ip_adapter_sd15": _lib.MODEL_IP_ADAPTER_SD15,
          "diffusion_sd2": _lib.MODEL_DIFFUSION_SD2, "clip_sd2": _lib.MODEL_CLIP_SD2}
 
 
@@ -322,6 +323,41 @@ class Session:
     @property
     def control_active(self):
         return lib().tsd_session_control_active(self.h) == 1
+
+    def set_ip_adapter(self, ip, tokens=None, uncond_tokens=None, scale=1.0, first_step=0, last_step=None):
+        """IP-Adapter for the steps first_step <= i <= last_step (None: to the end) of this lockstep session on a full-size SD-1.x UNet
+        (`tsd_session_set_ip_adapter`): ip a `tsd.IPAdapter` on the same context (None turns it off), tokens (N,768) or (B,N,768) for the
+        conditional half and, in a CFG session, uncond_tokens of the same shape for the unconditional half - `ip.project(zeros)`, which
+        is not zero tokens; scale one value for every sample.  Call after upload(); the keys and values of all blocks are projected here
+        once, and the adapter stays across upload()s until set_ip_adapter(None)."""
+        if ip is None:
+            check(lib().tsd_session_set_ip_adapter(self.h, None, None, None, 0, 0.0, 0, -1))
+            return
+
+        def shaped(t, what):
+            t = f32(t)
+            if t.ndim == 2:
+                t = np.repeat(t[None], self.B, axis=0) if self.B > 1 else t[None]
+            if t.ndim != 3 or t.shape[0] != self.B or not (1 <= t.shape[1] <= 16) or t.shape[2] != 768:
+                raise ValueError(f"set_ip_adapter: {what} must have shape (N, 768) or ({self.B}, N, 768) with 1 <= N <= 16, got {t.shape}")
+            return f32(t)
+        if tokens is None:
+            raise ValueError("set_ip_adapter: the image tokens are required (IPAdapter.project(image_embeds))")
+        tok = shaped(tokens, "tokens")
+        unc = None
+        if self.cfg:
+            if uncond_tokens is None:
+                raise ValueError("set_ip_adapter: a CFG session needs uncond_tokens (ip.project(zeros))")
+            unc = shaped(uncond_tokens, "uncond_tokens")
+            if unc.shape != tok.shape:
+                raise ValueError(f"set_ip_adapter: tokens {tok.shape} and uncond_tokens {unc.shape} differ in shape")
+        model = getattr(ip, "model", ip)
+        check(lib().tsd_session_set_ip_adapter(self.h, model.h, ptr(tok), ptr(unc) if unc is not None else None, tok.shape[1], float(scale),
+                                               int(first_step), -1 if last_step is None else int(last_step)))
+
+    @property
+    def ip_adapter_active(self):
+        return lib().tsd_session_ip_adapter_active(self.h) == 1
 
     @property
     def guidance_rescale(self):

@@ -27,7 +27,8 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
              inference_steps=50, seed_val=0, input_image=None, encoder=None, latents=None, noise=None,
              num_training_steps=1000, L=64, return_latents=False, sampler="ddpm", eta=0.0, spacing="leading", mask=None,
              mask_mode="any", seeds=None, guidance_rescale=0.0, prediction="epsilon", zero_terminal_snr=False, controlnet=None,
-             control_image=None, control_scale=1.0, control_cond_only=False, control_start=0.0, control_end=1.0):
+             control_image=None, control_scale=1.0, control_cond_only=False, control_start=0.0, control_end=1.0, ip_adapter=None,
+             ip_image_embeds=None, ip_scale=1.0, ip_start=0.0, ip_end=1.0):
     """context (B,T,768); returns images (B,3,8LH,8LW) in [0,255] like pipeline.mojo:127.  L is the latent side (64: 512x512) or a pair
     (LH, LW) for a rectangular image ((96, 64): 512 wide, 768 high); where the text below says L,L the tensor is LH,LW.
 
@@ -58,7 +59,17 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
     controlnet, a `tsd.ControlNet` on the diffusion model's context (full-size UNet variants), with control_image (3,8LH,8LW) or
     (B,3,8LH,8LW), taken as given (diffusers feeds [0, 1]): every step whose index lies in [control_start, control_end] as fractions of
     the step list (diffusers' control_guidance_start / _end) runs the ControlNet and adds its residuals scaled by control_scale;
-    control_cond_only: with cfg, only the conditional half is controlled (`Session.set_control`)."""
+    control_cond_only: with cfg, only the conditional half is controlled (`Session.set_control`).
+
+    ip_adapter, a `tsd.IPAdapter` on the diffusion model's context (full-size SD-1.x variants), with ip_image_embeds (1024,) or (B,1024),
+    the CLIP image embedding of the prompt image (diffusers' ip_adapter_image_embeds; the vision encoder is not part of this package):
+    every step whose index lies in [ip_start, ip_end] as fractions of the step list adds the attention over the projected image tokens,
+    scaled by ip_scale, in every cross-attention block.  With cfg the unconditional half reads the projection of a zero embedding, as
+    diffusers does (`Session.set_ip_adapter`)."""
+    if (ip_adapter is None) != (ip_image_embeds is None):
+        raise ValueError("generate: ip_adapter and ip_image_embeds go together")
+    if ip_adapter is not None and not (0.0 <= ip_start <= ip_end <= 1.0):
+        raise ValueError(f"generate: ip_start / ip_end must satisfy 0 <= start <= end <= 1, got {ip_start}, {ip_end}")
     if (controlnet is None) != (control_image is None):
         raise ValueError("generate: controlnet and control_image go together")
     if controlnet is not None and not (0.0 <= control_start <= control_end <= 1.0):
@@ -122,6 +133,15 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
         last = int(np.floor(control_end * n + 1e-9)) - 1
         if last >= first:
             sess.set_control(controlnet, control_image, control_scale, control_cond_only, first, last)
+    if ip_adapter is not None:
+        first = int(np.ceil(ip_start * n - 1e-9))
+        last = int(np.floor(ip_end * n + 1e-9)) - 1
+        if last >= first:
+            e = np.asarray(ip_image_embeds, dtype=np.float32)
+            e = np.repeat(e[None], B, axis=0) if e.ndim == 1 else e
+            if e.shape != (B, 1024):
+                raise ValueError(f"generate: ip_image_embeds must have shape (1024,) or ({B}, 1024), got {np.shape(ip_image_embeds)}")
+            sess.set_ip_adapter(ip_adapter, ip_adapter.project(e), ip_adapter.project(np.zeros_like(e)) if cfg else None, ip_scale, first, last)
     for i in range(n):  # pipeline.mojo:87-122
         sess.step(i)
     out_lat = sess.latents()

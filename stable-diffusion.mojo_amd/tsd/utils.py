@@ -237,6 +237,29 @@ def cfg_rescale(eps, eps_uncond, cfg_scale=7.5, phi=0.7, ctx=None):
     return co, uo, g
 
 
+def ip_attn_add(q, k_ip, vt_ip, o, scale, n_heads, n_tokens, softmax_scale=None, ctx=None):
+    """The IP-Adapter's attention launch alone (`tsd_ip_attn_add_f16`): q, o float16 (B, S, C); k_ip float16 (B, 16, C), token-major, rows
+    >= n_tokens are not read; vt_ip float16 (B, C, 16), channel-major; scale (B,) ->
+    float16(float32(o) + scale_b * softmax(softmax_scale q k_ip^T) v_ip) per head of C / n_heads channels (40, 80 or 160), rounded once.
+    softmax_scale defaults to 1 / sqrt(C / n_heads).  A sample whose scale is 0 comes back unchanged."""
+    qa, oa = (np.ascontiguousarray(a, dtype=np.float16) for a in (q, o))
+    ka, va = (np.ascontiguousarray(a, dtype=np.float16) for a in (k_ip, vt_ip))
+    if qa.ndim != 3 or oa.shape != qa.shape:
+        raise ValueError(f"ip_attn_add: q {qa.shape} and o {oa.shape} must both be (B, S, C)")
+    B, S, Cc = qa.shape
+    if ka.shape != (B, 16, Cc) or va.shape != (B, Cc, 16):
+        raise ValueError(f"ip_attn_add: k_ip must be ({B}, 16, {Cc}) and vt_ip ({B}, {Cc}, 16), got {ka.shape} and {va.shape}")
+    if Cc % int(n_heads):
+        raise ValueError(f"ip_attn_add: {n_heads} heads do not divide {Cc} channels")
+    d = Cc // int(n_heads)
+    s = np.ascontiguousarray(np.broadcast_to(np.asarray(scale, dtype=np.float32), (B,)))
+    out = np.empty_like(oa)
+    sm = 1.0 / math.sqrt(d) if softmax_scale is None else float(softmax_scale)
+    check(lib().tsd_ip_attn_add_f16(_ctx(ctx), qa.ctypes.data, ka.ctypes.data, va.ctypes.data, oa.ctypes.data, ptr(s), B, int(n_heads), d, S,
+                                    int(n_tokens), sm, out.ctypes.data))
+    return out
+
+
 def control_inject(x, r, scale, groups, nslab, ctx=None):
     """The ControlNet injection launch alone (`tsd_control_inject_f16`) over a table of tensors: x[i], r[i] float16 (B, HW_i, C_i), scale
     (B,), groups[i] / nslab[i] the GroupNorm statistics geometry of tensor i (groups 0: none) -> (y, partial) with
