@@ -188,7 +188,7 @@ int tsd_vae_attention_block_f32(tsd_ctx* ctx, const float* x, int C, int H, int 
  * norms - 32 groups in the residual blocks (the reference declares 16, vae.mojo:42-43), per-channel weight / bias of
  * every GroupNorm appended to the kind-2 / kind-3 list (`lN.group_norm1`, `lN.group_norm2`, `lN.group_norm`, and
  * `lN` for the stand-alone norm), eps inside the root: the layout of diffusers' AutoencoderKL decoder / encoder. */
-typedef enum tsd_model_kind { TSD_MODEL_DIFFUSION = 1, TSD_MODEL_DECODER = 2, TSD_MODEL_ENCODER = 3, TSD_MODEL_CLIP = 4, TSD_MODEL_DIFFUSION_SD15 = 5, TSD_MODEL_DIFFUSION_SD15_TORCH = 6, TSD_MODEL_CLIP_TORCH = 7, TSD_MODEL_DECODER_TORCH = 8, TSD_MODEL_ENCODER_TORCH = 9, TSD_MODEL_CONTROLNET_SD15 = 10, TSD_MODEL_CONTROLNET_SD15_TORCH = 11, TSD_MODEL_DIFFUSION_SD2 = 16, TSD_MODEL_CLIP_SD2 = 17, TSD_MODEL_IP_ADAPTER_SD15 = 20 } tsd_model_kind;
+typedef enum tsd_model_kind { TSD_MODEL_DIFFUSION = 1, TSD_MODEL_DECODER = 2, TSD_MODEL_ENCODER = 3, TSD_MODEL_CLIP = 4, TSD_MODEL_DIFFUSION_SD15 = 5, TSD_MODEL_DIFFUSION_SD15_TORCH = 6, TSD_MODEL_CLIP_TORCH = 7, TSD_MODEL_DECODER_TORCH = 8, TSD_MODEL_ENCODER_TORCH = 9, TSD_MODEL_CONTROLNET_SD15 = 10, TSD_MODEL_CONTROLNET_SD15_TORCH = 11, TSD_MODEL_DIFFUSION_SD2 = 16, TSD_MODEL_CLIP_SD2 = 17, TSD_MODEL_IP_ADAPTER_SD15 = 20, TSD_MODEL_CLIP_VISION_H = 22 } tsd_model_kind;
 /* TSD_MODEL_CONTROLNET_SD15 (EXTENSION: Zhang et al. 2023; the layout of diffusers' ControlNetModel): the control network of the full-size
  * UNet.  Parameters in this order: `time_embed.layer1/2`; the hint encoder `hint.conv1 .. hint.conv8` (3x3 convolutions 3->16, 16->16,
  * 16->32 stride 2, 32->32, 32->96 stride 2, 96->96, 96->256 stride 2, 256->320; SiLU after each but the last, the last initialised to
@@ -316,8 +316,8 @@ int tsd_control_inject_f16(tsd_ctx* ctx, int n, const void* const* x, const void
  * bias, <i> the odd number the published files give the block (1 .. 11 the encoder, 31 the bottleneck, 13 .. 29 the decoder).  N = 4.
  * The 16 to_k_ip matrices are contiguous in the packed blob and the 16 to_v_ip matrices follow them, so K_ip and V_ip^T of all blocks are
  * one GEMM (two where the fused form does not apply) over the tokens staged as 16 fp16 rows per sample, rows N .. 15 zero.
- * tsd_flop_count returns -1 and tsd_model_lora_add refuses the kind.  The CLIP vision encoder and the resampler of the "plus" files are
- * not part of it: callers bring the 1024-wide image embedding, or the tokens themselves.
+ * tsd_flop_count returns -1 and tsd_model_lora_add refuses the kind.  The resampler of the "plus" files is not part of it: callers bring
+ * the 1024-wide image embedding - tsd_clip_vision_forward below computes it from pixels - or the tokens themselves.
  * tsd_ip_adapter_project: embeds [B][1024] -> tokens_out [B][N][768] = LayerNorm(Linear(embeds)) per token (eps 1e-5); every value is
  * exactly an fp16.
  * tsd_diffusion_forward_ip_hw: tsd_diffusion_forward_hw of `unet` (kinds 5 / 6; TSD_E_ARG for the Tiny-SD graph, the SD-2.x kind and a
@@ -370,6 +370,51 @@ int tsd_debug_ip_attn_run(tsd_ctx* ctx, const int64_t* desc, int n, const void* 
 /* Time `iters` launches of k_ip_attn_add on synthetic device data: B samples (<= 16, all at scale 1), S queries, N image tokens. */
 int tsd_debug_ip_attn_bench(tsd_ctx* ctx, int B, int H, int d, int S, int N, int iters, float* ms);
 int tsd_encoder_forward_hw(tsd_model* m, const float* images, const float* noise, int B, int SH, int SW, float* latents);
+/* ---- CLIP vision encoder (EXTENSION: OpenCLIP ViT-H/14 as Hugging Face ships it in the `image_encoder/` folder of h94/IP-Adapter, a
+ * CLIPVisionModelWithProjection): the 1024-wide image embedding the ip-adapter_sd15 files were trained against, from pixels.
+ * TSD_MODEL_CLIP_VISION_H (22; the numbers 12 - 15, 18, 19, 21 and 23 stay reserved and refused): width 1280, 16 heads of 80, 32 pre-LN
+ * layers, erf-GELU MLP of 5120, 14x14 patches of a 224x224 crop (256 patches + 1 class token = 257 tokens), `post_layernorm` on the class
+ * row, a bias-free 1280 -> 1024 projection.  Parameters, in this order: `embeddings.class_embedding` [1280],
+ * `embeddings.patch_embedding.weight` [1280][588] (the flattened HF conv weight [1280][3][14][14]; no bias; K zero-padded to 640 in the
+ * packed blob: the GEMM wants whole 64-deep K tiles), `embeddings.position_embedding.weight` [257][1280] (kept as fp16),
+ * `pre_layrnorm.weight` / `.bias` (HF's spelling), per layer N = 0 .. 31 `layers.N.ln1`, `layers.N.in_proj` ([3840][1280] with bias, q | k | v
+ * stacked), `layers.N.out_proj`, `layers.N.ln2`, `layers.N.fc1` (1280 -> 5120), `layers.N.fc2` (5120 -> 1280), then `post_layernorm` and
+ * `visual_projection.weight` [1024][1280] (no bias).  LayerNorms are torch's (eps 1e-5).  tsd_model_lora_add refuses the kind,
+ * tsd_model_context_width returns TSD_E_ARG for it, tsd_flop_count(kind, 0, 0) returns the GFLOP of ONE image: 32 x (four linears on 257
+ * rows + 4 * 257^2 * 1280 for the attention core) + the patch GEMM + the projection.
+ *
+ * The image front end (k_clip_image_patches, csrc/kernels_vision.hip) is the float-valued form of HF's CLIPImageProcessor: images fp32
+ * [B][3][H][W] on the 0 .. 255 scale (the scale of the VAE encoder's input), 8 <= H, W <= 2048 (TSD_E_SHAPE otherwise) ->
+ *   resize: shortest edge to 224, the other edge to int(224 * long / short); PIL's separable antialiased bicubic (Keys, a = -0.5),
+ *           horizontal pass first.  Per axis scale = n_in / n_out, fs = max(scale, 1), support = 2 fs; output xx has
+ *           center = (xx + 0.5) scale, lo = max(int(center - support + 0.5), 0), hi = min(int(center + support + 0.5), n_in) and the
+ *           weights w((x - center + 0.5) / fs), x in [lo, hi), divided by their sum.  The host builds the two tables in double, rounds
+ *           every weight to fp32 once and keeps them on the context per (H, W);
+ *   centre crop to 224 x 224: top = (RH - 224) / 2, left = (RW - 224) / 2 (integer division);
+ *   normalise: (v / 255 - mean_c) / std_c, mean (0.48145466, 0.4578275, 0.40821073), std (0.26862954, 0.26130258, 0.27577711),
+ *           evaluated as one fma with 1 / (255 std_c) and -mean_c / std_c, rounded ONCE to fp16;
+ * -> patch rows fp16 [B * 256][592]: row b * 256 + py * 16 + px, column c * 196 + kh * 14 + kw (the flattening of the HF conv weight),
+ * columns 588 .. 591 zero.  fp32 sums in tap order; no atomics; a sample's bits do not depend on B or on its batch position.
+ * NOT reproduced: the rounding to uint8 that PIL applies after resizing an 8-bit image (CLIPImageProcessor on a uint8 input) - after the
+ * normalisation at most 0.5 / 255 / std = 7.5e-3 per element.  A 224 x 224 input is resized by the identity (every coefficient row is
+ * 0, 1, 0, 0), so a caller who resizes to 224 x 224 themselves gets HF's numbers.
+ * tsd_clip_image_patches_f16: host in, host out (fp16 bits [B * 256][592]), synchronous; 1 <= B <= 64.
+ * tsd_clip_vision_forward: images as above, 1 <= B <= 16 -> image_embeds fp32 [B][1024] (HF's `image_embeds`) and, when hidden_out is
+ * not NULL, the input of the last layer fp32 [B][257][1280] (HF's `hidden_states[-2]`, no post-LayerNorm: what the "plus" adapters read).
+ * hidden_out costs one conversion launch and a copy, nothing when NULL; image_embeds are the same bits either way. */
+int tsd_clip_image_patches_f16(tsd_ctx* ctx, const float* images, int B, int H, int W, void* patches_out);
+int tsd_clip_vision_forward(tsd_model* m, const float* images, int B, int H, int W, float* image_embeds, float* hidden_out);
+/* Replay entry of the front-end launch with the conventions of tsd_debug_ip_attn_run (test infrastructure: tests/clipvision_ref.py holds
+ * the kernel to an fp64 reference, element-wise).  One int64 per argument; LD is the pitch of the patch rows in elements (>= 592, a
+ * multiple of 8; columns 588 .. LD - 1 are written as zero).  Operand slots: input IMG fp32 [B][3][H][W]; output OUT fp16 [B * 256][LD].
+ * host_in == NULL only sizes.  info[TSD_VI_CHANGED]: guard elements the launch changed; TAPS_H / TAPS_V: the longest coefficient row of
+ * the horizontal / vertical table; ROWS: the most source rows one patch stages; LDS: bytes of LDS of the launch. */
+enum tsd_imgpatch_desc_field { TSD_VD_VERSION = 0, TSD_VD_B, TSD_VD_H, TSD_VD_W, TSD_VD_LD, TSD_VD_COUNT };
+#define TSD_VD_VERSION_1 1
+enum tsd_imgpatch_operand { TSD_VO_IMG = 0, TSD_VO_OUT, TSD_VO_COUNT };
+enum tsd_imgpatch_info { TSD_VI_CHANGED = 0, TSD_VI_TAPS_H, TSD_VI_TAPS_V, TSD_VI_ROWS, TSD_VI_LDS, TSD_VI_COUNT };
+int tsd_debug_image_patches_run(tsd_ctx* ctx, const int64_t* desc, int n, const void* const* host_in, void* const* host_out, int64_t* ext,
+                                int64_t* info);
 
 /* `CLIP.forward` clip.mojo:90-109 (the step before the hot path), intended semantics
  * (App.A D3/D8/D15/D20): tokens [B][T] int32 ids (T <= 77; rows are zero-padded to 77 like clip.mojo:91-93)

@@ -319,6 +319,26 @@ extern "C" int tsd_clip_forward(tsd_model* m, const int32_t* tokens, int B, int 
   });
 }
 
+// CLIP vision encoder: pixels on 0 .. 255 -> the 1024-wide image embedding (and, on request, the input of the last layer)
+extern "C" int tsd_clip_vision_forward(tsd_model* m, const float* images, int B, int H, int W, float* image_embeds, float* hidden_out) {
+  NOTNULL(m); NOTNULL(images); NOTNULL(image_embeds);
+  if (!is_clip_vision_kind(m->kind)) TSD_FAIL(TSD_E_ARG, "tsd_clip_vision_forward: model is not a CLIP vision encoder");
+  if (B <= 0 || B > 16) TSD_FAIL(TSD_E_SHAPE, "clip vision: B=%d (1..16)", B);
+  if (H < 8 || W < 8 || H > 2048 || W > 2048) TSD_FAIL(TSD_E_SHAPE, "clip vision: image sides %d x %d outside 8 .. 2048", H, W);
+  tsd_ctx* ctx = m->ctx;
+  return run_model(m, [&]() -> int {
+    const int64_t ni = (int64_t)B * 3 * H * W, ne = (int64_t)B * CV_EMBED, nh = (int64_t)B * CV_TOKENS * CV_WIDTH;
+    float* di = arena_alloc<float>(ctx, ni);
+    float* de = arena_alloc<float>(ctx, ne);
+    float* dh = hidden_out ? arena_alloc<float>(ctx, nh) : nullptr;
+    if (!di || !de || (hidden_out && !dh)) TSD_FAIL(TSD_E_ALLOC, "workspace arena exhausted");
+    TSD_TRY(h2d(ctx, di, images, (size_t)ni * 4));
+    TSD_TRY(g_clip_vision_forward(m, di, B, H, W, de, dh));
+    if (hidden_out) TSD_TRY(d2h(ctx, hidden_out, dh, (size_t)nh * 4));
+    return d2h(ctx, image_embeds, de, (size_t)ne * 4);
+  });
+}
+
 extern "C" int tsd_model_context_width(const tsd_model* m) {
   if (!m) TSD_FAIL(TSD_E_ARG, "NULL model");
   const int w = model_context_width(m);

@@ -406,6 +406,23 @@ extern "C" int tsd_ip_attn_add_f16(tsd_ctx* ctx, const void* q, const void* k_ip
   });
 }
 
+// The CLIP vision encoder's image front end (kernels_vision.hip) on host tensors: images fp32 [B][3][H][W] on 0 .. 255 -> patch rows fp16
+// [B * 256][592], the ONE launch in front of the patch-embedding GEMM.
+extern "C" int tsd_clip_image_patches_f16(tsd_ctx* ctx, const float* images, int B, int H, int W, void* patches_out) {
+  NOTNULL(ctx); NOTNULL(images); NOTNULL(patches_out);
+  if (B <= 0 || B > 64) TSD_FAIL(TSD_E_SHAPE, "clip image patches: B=%d (1..64)", B);
+  if (H < 8 || W < 8 || H > 2048 || W > 2048) TSD_FAIL(TSD_E_SHAPE, "clip image patches: sides %d x %d outside 8 .. 2048", H, W);
+  return run_op(ctx, [&]() -> int {
+    Dev dv{ctx};
+    const int64_t no = (int64_t)B * CV_PATCHES * CV_PATCH_LD;
+    const float* di = dv.in(images, (int64_t)B * 3 * H * W);
+    uint16_t* dp = dv.buf<uint16_t>(no);
+    if (dv.err) return dv.err;
+    TSD_TRY(launch_clip_image_patches(ctx, di, B, H, W, (half_t*)dp, CV_PATCH_LD));
+    return dv.out((uint16_t*)patches_out, (const uint16_t*)dp, no);
+  });
+}
+
 // N(0,1) of the counter RNG (kernels_sampler.hip k_fill_normal, counter_rng.h) on a host tensor: element e is value offset + e of the
 // stream (seed, stream) - the values a seeded denoise session draws on the device
 extern "C" int tsd_normal_fill_f32(tsd_ctx* ctx, uint64_t seed, uint64_t stream, uint64_t offset, int64_t n, float* out) {

@@ -955,3 +955,37 @@ extern "C" int tsd_debug_ip_attn_run(tsd_ctx* ctx, const int64_t* desc, int n, c
   TSD_TRY(ops.read_back(&info[TSD_PI_CHANGED]));
   return r;
 }
+
+// ---- the CLIP vision encoder's image front end on caller operands (tests/clipvision_ref.py holds k_clip_image_patches to an fp64 reference) ----
+extern "C" int tsd_debug_image_patches_run(tsd_ctx* ctx, const int64_t* desc, int n, const void* const* host_in, void* const* host_out,
+                                           int64_t* ext, int64_t* info) {
+  NOTNULL(desc); NOTNULL(ext);
+  TSD_TRY(check_fields("image_patches_run", n, TSD_VD_COUNT));
+  const int64_t* d = desc;
+  for (int i = 0; i < TSD_VO_COUNT; i++) ext[i] = 0;
+#define VD_REQ(cond) \
+  if (!(cond)) TSD_FAIL(TSD_E_ARG, "image_patches_run: descriptor cannot be sized (%s)", #cond)
+  VD_REQ(d[TSD_VD_VERSION] == TSD_VD_VERSION_1);
+  VD_REQ(d[TSD_VD_B] > 0 && d[TSD_VD_B] <= 64 && d[TSD_VD_H] > 0 && d[TSD_VD_H] <= 4096 && d[TSD_VD_W] > 0 && d[TSD_VD_W] <= 4096);
+  VD_REQ(d[TSD_VD_LD] >= CV_PATCH_K && d[TSD_VD_LD] <= 4096);
+#undef VD_REQ
+  ext[TSD_VO_IMG] = d[TSD_VD_B] * 3 * d[TSD_VD_H] * d[TSD_VD_W];
+  ext[TSD_VO_OUT] = d[TSD_VD_B] * CV_PATCHES * d[TSD_VD_LD];
+  if (info) for (int i = 0; i < TSD_VI_COUNT; i++) info[i] = 0;
+  if (!host_in) return TSD_OK;  // sizing only: no context or device needed
+  NOTNULL(ctx); NOTNULL(host_out); NOTNULL(info);
+  TSD_TRY(check_slots("image_patches_run", ext, TSD_VO_COUNT, TSD_VO_OUT, host_in, host_out));
+  HIP_TRY(hipSetDevice(ctx->device));
+  const int B = (int)d[TSD_VD_B], H = (int)d[TSD_VD_H], W = (int)d[TSD_VD_W], ld = (int)d[TSD_VD_LD];
+  VisionTab t;
+  TSD_TRY(vision_tab(ctx, H, W, &t));  // the sides the launcher refuses are refused here, before anything is allocated
+  info[TSD_VI_TAPS_H] = t.tx; info[TSD_VI_TAPS_V] = t.ty; info[TSD_VI_ROWS] = t.rows; info[TSD_VI_LDS] = (int64_t)3 * t.rows * CV_PATCH * 4;
+  GuardedOperands ops(ctx, TSD_VO_COUNT);
+  TSD_TRY(ops.add(TSD_VO_IMG, ext[TSD_VO_IMG], 4, host_in[TSD_VO_IMG]));
+  // every element of the extent is written (the pad columns as zeros): the whole extent is logical
+  TSD_TRY(ops.add(TSD_VO_OUT, ext[TSD_VO_OUT], 2, nullptr, host_out[0], replay::Box::dense(ext[TSD_VO_OUT])));
+  const int r = run_planned(ctx, [&]() -> int { return launch_clip_image_patches(ctx, (const float*)ops.at(TSD_VO_IMG), B, H, W, (half_t*)ops.at(TSD_VO_OUT), ld); });
+  HIP_TRY(hipStreamSynchronize(ctx->stream));
+  TSD_TRY(ops.read_back(&info[TSD_VI_CHANGED]));
+  return r;
+}

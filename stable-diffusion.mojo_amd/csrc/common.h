@@ -141,6 +141,16 @@ struct GemmPlan {
 };
 GemmPlan gemm_plan(const TsdOptions& opt, const GemmArgs& a);
 
+// Coefficient tables of the CLIP image front end for one input size (kernels_vision.hip vision_tab builds and caches them): per axis the
+// 224 cropped outputs' first source index, tap count and fp32 weights (pitch tx / ty).  One device allocation: int xs[224], xn[224], ys[224],
+// yn[224], float wx[224][tx], wy[224][ty].
+struct VisionTab {
+  int H = 0, W = 0;
+  int tx = 0, ty = 0;   // longest coefficient row of the horizontal / vertical table
+  int rows = 0;         // most source rows the 14 output rows of one patch read
+  void* dev = nullptr;
+};
+
 struct tsd_ctx {
   int device = 0;
   TsdOptions opt;
@@ -173,6 +183,7 @@ struct tsd_ctx {
   int64_t gn_paths[8] = {};   // tsd_debug_gn_path_counts
   AttnPlan attn_last;         // plan of the last attention-core / row-softmax launch enqueued (tsd_debug_attn_run)
   SmallLinearPlan sl_last;    // the last tiny-M linear launch enqueued (tsd_debug_elem_run)
+  std::vector<VisionTab> vision_tabs;  // resize coefficient tables of the CLIP image front end, one per input size (kernels_vision.hip)
 };
 
 enum KernelClass : int {
@@ -635,3 +646,13 @@ int launch_gn_finalize(tsd_ctx* ctx, const float* partial, int nslab, int B, int
 int launch_attn_tail_pack(tsd_ctx* ctx, const half_t* Wso, int ld_so, const half_t* Wq, int ld_q, const half_t* Wco, int ld_co,
                           const half_t* W1, int ld_1, const half_t* W2, int ld_2, const half_t* Wout, int ld_out, half_t* dst);
 int launch_flash_attention(tsd_ctx* ctx, const AttnArgs& a);
+
+// ---- CLIP vision front end (kernels_vision.hip states the formula): images fp32 [B][3][H][W] on 0 .. 255 -> resized (PIL's antialiased
+// bicubic, shortest edge 224), centre-cropped, normalised patch rows fp16 [B * 256][ld], column c * 196 + kh * 14 + kw, columns 588 .. ld - 1
+// zero.  8 <= H, W <= 2048 (TSD_E_SHAPE), ld >= 592 and a multiple of 8.  The coefficient tables are built on the host and kept on the context.
+enum { CV_SIDE = 224, CV_PATCH = 14, CV_GRID = 16, CV_PATCHES = 256, CV_PATCH_K = 588, CV_PATCH_LD = 592 };
+int vision_tab(tsd_ctx* ctx, int H, int W, VisionTab* out);
+int launch_clip_image_patches(tsd_ctx* ctx, const float* img, int B, int H, int W, half_t* out, int ld);
+// x[b * sx + n] = rn16(cls[n] + f32(pos[n])), n < C, b < B: the class rows of the token tensor (the patch rows come from the patch GEMM's
+// residual epilogue)
+int launch_vision_class_rows(tsd_ctx* ctx, const float* cls, const half_t* pos, int B, int C, half_t* x, int64_t sx);

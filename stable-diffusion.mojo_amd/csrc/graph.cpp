@@ -1076,3 +1076,86 @@ int g_clip_forward(tsd_model* m, const int* tokens_dev, int B, float* out_f32) {
   TSD_TRY(launch_layernorm(ctx, x, M, D, D, 1e-5f, ln, D, c.final_ln.w ? &c.final_ln : nullptr));  // clip.mojo:106-108
   return launch_f16_to_f32_rows(ctx, ln, M, D, D, out_f32);
 }
+
+// ---- CLIP vision encoder (kind 22): HF CLIPVisionModelWithProjection of OpenCLIP ViT-H/14 -------------------------------------------------
+// images fp32 [B][3][H][W] on 0 .. 255 -> patch rows (k_clip_image_patches) -> patch GEMM whose residual epilogue adds the position rows and
+// stores token rows 1 .. 256 of every sample -> class rows -> pre-LN -> 32 x (LN, q | k and V^T projections, flash attention at d = 80 over
+// 257 keys, out_proj + residual, LN, fc1, erf-GELU, fc2 + residual) -> LN of the B class rows -> projection, fp32 [B][1024].
+// 257 tokens meet two rules of the existing kernels, as the text encoder's 77 do:
+//  * the GEMM wants N % 4 == 0, and the V^T projection has the token count as its N: it addresses 260 tokens, so `ln` carries three zeroed
+//    slack rows behind the last sample (rows 257 .. 259 of an earlier sample are its successor's first rows: finite);
+//  * the flash kernel reads V^T columns up to round_up(257, 8) = 264: V^T has pitch 264, columns 260 .. 263 stay zero and 257 .. 259 hold the
+//    finite products of the rows above.  Keys >= 257 are masked to P = 0 exactly, so none of them reaches a result.
+// No GEMM of this graph splits K (no rows-per-sample hint is passed, gemm_plan.cpp), so every sample's bits are the same at every B.
+int g_clip_vision_forward(tsd_model* m, const float* images, int B, int H, int W, float* embeds_out, float* hidden_out) {
+  tsd_ctx* ctx = m->ctx;
+  if (!is_clip_vision_kind(m->kind)) TSD_FAIL(TSD_E_ARG, "g_clip_vision_forward: model is not a CLIP vision encoder");
+  const ClipVisionW& v = m->vision;
+  const int T = CV_TOKENS, D = CV_WIDTH, Tn = 260, Tp = 264, KP = v.patch.Kpad;
+  const int64_t M = (int64_t)B * T;
+  half_t* pat = arena_alloc<half_t>(ctx, (int64_t)B * CV_PATCHES * KP); CHECK_ALLOC(pat);
+  half_t* x = arena_alloc<half_t>(ctx, M * D); CHECK_ALLOC(x);
+  half_t* x2 = arena_alloc<half_t>(ctx, M * D); CHECK_ALLOC(x2);
+  half_t* ln = arena_alloc<half_t>(ctx, (M + 3) * D); CHECK_ALLOC(ln);
+  half_t* qk = arena_alloc<half_t>(ctx, M * 2 * D); CHECK_ALLOC(qk);
+  half_t* vt = arena_alloc<half_t>(ctx, (int64_t)B * D * Tp); CHECK_ALLOC(vt);
+  half_t* ao = arena_alloc<half_t>(ctx, M * D); CHECK_ALLOC(ao);
+  half_t* ff = arena_alloc<half_t>(ctx, M * CV_MLP); CHECK_ALLOC(ff);
+  half_t* cls = arena_alloc<half_t>(ctx, (int64_t)B * D); CHECK_ALLOC(cls);
+  TSD_TRY(zero_async(ctx, ln + M * D, (size_t)3 * D * sizeof(half_t)));
+  TSD_TRY(zero_async(ctx, vt, (size_t)B * D * Tp * sizeof(half_t)));
+  TSD_TRY(launch_clip_image_patches(ctx, images, B, H, W, pat, KP));
+  {  // x[b][1 + p] = patch[b][p] . W^T + pos[1 + p]: one launch, a batch per sample, the position rows as the residual of every batch
+    GemmArgs g;
+    g.A0 = pat; g.lda0 = KP; g.sA = (int64_t)CV_PATCHES * KP;
+    g.Wt = v.patch.w; g.ldw = KP; g.sW = 0;
+    g.M = CV_PATCHES; g.N = D; g.K = KP; g.batch = B;
+    g.epi = EPI_RESIDUAL; g.R = v.pos + D; g.ldr = D; g.sR = 0;
+    g.C = x + D; g.ldc = D; g.sC = (int64_t)T * D;
+    TSD_TRY(launch_gemm(ctx, g));
+  }
+  TSD_TRY(launch_vision_class_rows(ctx, v.cls, v.pos, B, D, x, (int64_t)T * D));
+  TSD_TRY(launch_layernorm(ctx, x, M, D, D, 1e-5f, x2, D, &v.pre_ln));
+  half_t* cur = x2;  // the residual stream alternates between x2 and x
+  half_t* oth = x;
+  const half_t* hidden = nullptr;
+  CatSrc a;
+  for (int l = 0; l < CV_LAYERS; l++) {
+    const ClipVisionLayerW& w = v.layer[l];
+    if (l == CV_LAYERS - 1) hidden = cur;  // the input of the last layer: HF's hidden_states[-2]
+    TSD_TRY(launch_layernorm(ctx, cur, M, D, D, 1e-5f, ln, D, &w.ln1));
+    a.p0 = ln; a.ld0 = D; a.C0 = D;
+    TSD_TRY(g_linear(ctx, a, M, w.in_proj.w, w.in_proj.Kpad, 2 * D, D, w.in_proj.b, nullptr, 0, 0, qk, 2 * D));  // q | k
+    {  // V^T[b] = W_v . ln_b^T + b_v -> [B][D][264]
+      GemmArgs g;
+      g.A0 = w.in_proj.w + (int64_t)2 * D * w.in_proj.Kpad; g.lda0 = w.in_proj.Kpad; g.sA = 0;
+      g.Wt = ln; g.ldw = D; g.sW = (int64_t)T * D;
+      g.M = D; g.N = Tn; g.K = D; g.batch = B;
+      g.epi = EPI_BIAS_M; g.bias = w.in_proj.b + 2 * D;
+      g.C = vt; g.ldc = Tp; g.sC = (int64_t)D * Tp;
+      TSD_TRY(launch_gemm(ctx, g));
+    }
+    AttnArgs fa;
+    fa.Q = qk; fa.ldq = 2 * D; fa.sQ = (int64_t)T * 2 * D;
+    fa.K = qk + D; fa.ldk = 2 * D; fa.sK = (int64_t)T * 2 * D;
+    fa.Vt = vt; fa.ldvt = Tp; fa.sVt = (int64_t)D * Tp;
+    fa.O = ao; fa.ldo = D; fa.sO = (int64_t)T * D;
+    fa.B = B; fa.H = CV_HEADS; fa.d = D / CV_HEADS; fa.Sq = T; fa.Sk = T; fa.scale = 1.f / sqrtf((float)(D / CV_HEADS));
+    TSD_TRY(g_attn_core(ctx, fa));
+    a.p0 = ao;
+    TSD_TRY(g_linear(ctx, a, M, w.out_proj.w, w.out_proj.Kpad, D, D, w.out_proj.b, cur, D, 0, oth, D));
+    TSD_TRY(launch_layernorm(ctx, oth, M, D, D, 1e-5f, ln, D, &w.ln2));
+    a.p0 = ln;
+    TSD_TRY(g_linear(ctx, a, M, w.fc1.w, w.fc1.Kpad, CV_MLP, D, w.fc1.b, nullptr, 0, 0, ff, CV_MLP));
+    TSD_TRY(launch_gelu_erf_f16(ctx, ff, M * CV_MLP));
+    CatSrc f; f.p0 = ff; f.ld0 = CV_MLP; f.C0 = CV_MLP;
+    if (l == CV_LAYERS - 1 && hidden_out) {  // `cur` is the hidden state the caller asked for: the last layer must not overwrite it before it is read
+      TSD_TRY(launch_f16_to_f32_rows(ctx, hidden, M, D, D, hidden_out));
+    }
+    TSD_TRY(g_linear(ctx, f, M, w.fc2.w, w.fc2.Kpad, D, CV_MLP, w.fc2.b, oth, D, 0, cur, D));
+  }
+  // post_layernorm of the B class rows (row pitch 257 * 1280), then the bias-free projection, fp32 out
+  TSD_TRY(launch_layernorm(ctx, cur, B, D, T * D, 1e-5f, cls, D, &v.post_ln));
+  a.p0 = cls; a.ld0 = D; a.C0 = D;
+  return g_linear(ctx, a, B, v.proj.w, v.proj.Kpad, CV_EMBED, D, nullptr, nullptr, 0, EPI_OUT_F32, embeds_out, CV_EMBED);
+}

@@ -137,3 +137,6 @@ int run_planned(tsd_ctx* ctx, F&& fn) {
 }
 // tokens: device int32 [B][77]; out: device fp32 [B][77][D], D = the encoder's width (768; 1024 for TSD_MODEL_CLIP_SD2)
 int g_clip_forward(tsd_model* m, const int* tokens_dev, int B, float* out_f32);
+// CLIP vision encoder (kind 22).  images: device fp32 [B][3][H][W] on 0 .. 255; embeds_out: device fp32 [B][1024]; hidden_out: device fp32
+// [B][257][1280], the input of the last layer, or nullptr (one conversion launch less; embeds_out holds the same bits either way)
+int g_clip_vision_forward(tsd_model* m, const float* images, int B, int H, int W, float* embeds_out, float* hidden_out);

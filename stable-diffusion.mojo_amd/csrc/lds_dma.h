@@ -48,7 +48,8 @@ __device__ __forceinline__ void wait_alt_end() { asm volatile("; tsd-wait-alt en
 // k_gn_partial, k_gn_prereduce and k_gn_apply), kernels_elementwise.hip (5: both barriers of k_softmax_rows and k_softmax_rows_h8, the one of
 // k_small_linear; plus k_jitter_selftest, a hazard on purpose that shows the delays make one visible), kernels_lora.hip (2: k_lora_merge) and kernels_control.hip
 // (1: the barrier of k_control_inject; tests/test_gpu_controlnet.py holds it to the shipped bits) and kernels_ipattn.hip (2: the score and
-// the channel-tile loops of k_ip_attn_add; tests/test_gpu_ipadapter.py holds it to the shipped bits).
+// the channel-tile loops of k_ip_attn_add; tests/test_gpu_ipadapter.py holds it to the shipped bits) and kernels_vision.hip (1: the barrier of
+// k_clip_image_patches; tests/test_gpu_clipvision.py holds it to the shipped bits).
 // tests/jitter_manifest.py lists the kernels (JITTER_KERNELS); a CPU test finds the point - a clock read and a sleep the shipped listing does
 // not have - in every instantiation's jitter listing, and no clock read in the shipped one.
 __device__ __forceinline__ void tsd_jitter() {

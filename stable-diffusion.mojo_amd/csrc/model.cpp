@@ -381,6 +381,7 @@ extern "C" int tsd_model_lora_add(tsd_model* m, int index, int row0, int rows, c
   TSD_TRY(param_checked(m, index, "tsd_model_lora_add"));
   if (is_controlnet_kind(m->kind)) TSD_FAIL(TSD_E_ARG, "lora_add: adapters on a ControlNet are not supported");
   if (is_ip_adapter_kind(m->kind)) TSD_FAIL(TSD_E_ARG, "lora_add: adapters on an IP-Adapter are not supported");
+  if (is_clip_vision_kind(m->kind)) TSD_FAIL(TSD_E_ARG, "lora_add: adapters on the CLIP vision encoder are not supported");
   const ParamSpec& p = m->params[index];
   if (p.kind != P_CONV_W && p.kind != P_LIN_W) TSD_FAIL(TSD_E_ARG, "lora_add: %s is a bias / norm parameter, not a weight matrix", p.name.c_str());
   if (!p.used) TSD_FAIL(TSD_E_ARG, "lora_add: %s is never read by the forward", p.name.c_str());
@@ -833,6 +834,38 @@ int model_resolve(tsd_model* m) {
     }
     ip.n_blocks = t;
     m->unet.kproj_all.N = kvoff; m->unet.vproj_all.N = kvoff;  // 12480 rows each
+    return TSD_OK;
+  }
+  if (is_clip_vision_kind(m->kind)) {
+    ClipVisionW& v = m->vision;
+    auto aff = [&](const std::string& name) {
+      NormAffine a;
+      a.w = (const float*)(m->blob + m->params[m->index.at(name + ".weight")].off);
+      a.b = (const float*)(m->blob + m->params[m->index.at(name + ".bias")].off);
+      a.torch_rstd = 1;
+      return a;
+    };
+    auto linw = [&](const std::string& name) {  // a weight with no bias entry behind it
+      const ParamSpec& pw = m->params[m->index.at(name + ".weight")];
+      LinW w;
+      w.w = (const half_t*)(m->blob + pw.off); w.N = (int)pw.shape[0]; w.K = (int)pw.shape[1]; w.Kpad = pw.Kpad;
+      return w;
+    };
+    v.cls = (const float*)(m->blob + m->params[m->index.at("embeddings.class_embedding")].off);
+    v.patch = linw("embeddings.patch_embedding");
+    v.pos = linw("embeddings.position_embedding").w;
+    v.pre_ln = aff("pre_layrnorm");
+    for (int i = 0; i < CV_LAYERS; i++) {
+      const std::string n = "layers." + std::to_string(i);
+      ClipVisionLayerW& l = v.layer[i];
+      l.ln1 = aff(n + ".ln1"); l.ln2 = aff(n + ".ln2");
+      l.in_proj = model_lin(m, n + ".in_proj", true);
+      l.out_proj = model_lin(m, n + ".out_proj", true);
+      l.fc1 = model_lin(m, n + ".fc1", true);
+      l.fc2 = model_lin(m, n + ".fc2", true);
+    }
+    v.post_ln = aff("post_layernorm");
+    v.proj = linw("visual_projection");
     return TSD_OK;
   }
   if (is_diffusion_kind(m->kind) || is_controlnet_kind(m->kind)) {

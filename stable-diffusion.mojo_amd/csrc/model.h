@@ -69,10 +69,13 @@ static inline bool is_ip_adapter_kind(int kind) { return kind == TSD_MODEL_IP_AD
 // `ip_adapter.<index>` of the published files for the t-th cross-attention block of SD15_STEPS (6 down, 1 mid, 9 up): the files count
 // diffusers' attention processors - down blocks, then up blocks, then the mid block - and the cross-attention ones are the odd numbers
 static inline int ip_adapter_published_index(int t) { return t < 6 ? 2 * t + 1 : (t == 6 ? 31 : 2 * t - 1); }
-// 1 .. 11, 16, 17 and 20; 12 .. 15, 18 and 19 are reserved and refused
+// CLIP vision encoder (kind 22): OpenCLIP ViT-H/14 as the `image_encoder/` folder of the IP-Adapter files holds it (graph.cpp g_clip_vision_forward)
+constexpr int CV_WIDTH = 1280, CV_HEADS = 16, CV_LAYERS = 32, CV_MLP = 5120, CV_TOKENS = 257, CV_EMBED = 1024;
+static inline bool is_clip_vision_kind(int kind) { return kind == TSD_MODEL_CLIP_VISION_H; }
+// 1 .. 11, 16, 17, 20 and 22; 12 .. 15, 18, 19, 21 and 23 are reserved and refused
 static inline bool is_model_kind(int kind) {
   return (kind >= TSD_MODEL_DIFFUSION && kind <= TSD_MODEL_CONTROLNET_SD15_TORCH) || kind == TSD_MODEL_DIFFUSION_SD2 || kind == TSD_MODEL_CLIP_SD2 ||
-         kind == TSD_MODEL_IP_ADAPTER_SD15;
+         kind == TSD_MODEL_IP_ADAPTER_SD15 || kind == TSD_MODEL_CLIP_VISION_H;
 }
 
 std::vector<ParamSpec> build_param_specs(int model_kind);
@@ -168,6 +171,16 @@ struct IpAdapterW {  // kind 20
   int C[SD15_N] = {};       // per flat layer position: the block's width, 0 where the step is no attention block
 };
 
+struct ClipVisionLayerW { NormAffine ln1, ln2; LinW in_proj, out_proj, fc1, fc2; };
+struct ClipVisionW {  // kind 22
+  const float* cls = nullptr;   // [1280] fp32
+  LinW patch;                   // [1280][588 -> 640], no bias
+  const half_t* pos = nullptr;  // [257][1280] fp16
+  NormAffine pre_ln, post_ln;
+  ClipVisionLayerW layer[CV_LAYERS];
+  LinW proj;                    // [1024][1280], no bias
+};
+
 struct PlanKey { int B, L, T; bool operator<(const PlanKey& o) const { return B != o.B ? B < o.B : (L != o.L ? L < o.L : T < o.T); } };
 
 struct tsd_model {
@@ -185,6 +198,7 @@ struct tsd_model {
   VaeW vae;
   ClipW clip;
   IpAdapterW ip;
+  ClipVisionW vision;
   std::map<PlanKey, size_t> plans;  // workspace high-water mark per problem shape
   char* derived = nullptr;          // derived device buffers rebuilt by model_check_ready(): fused-tail weight streams
   size_t derived_bytes = 0;

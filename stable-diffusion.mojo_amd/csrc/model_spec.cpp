@@ -228,6 +228,25 @@ std::vector<ParamSpec> build_param_specs(int kind) {
       b.linw(n + ".to_k_ip", IP_CTX_DIM, l.a * l.b, 3);
       b.linw(n + ".to_v_ip", IP_CTX_DIM, l.a * l.b, 4);
     }
+  } else if (is_clip_vision_kind(kind)) {  // HF CLIPVisionModelWithProjection (ViT-H/14), q / k / v stacked into in_proj as in kind 7
+    ParamSpec c;
+    c.name = "embeddings.class_embedding"; c.ndim = 1; c.shape[0] = CV_WIDTH; c.kind = P_LIN_B; c.bound = 1.f; c.Opad = CV_WIDTH;
+    b.out.push_back(c);
+    b.linw("embeddings.patch_embedding", CV_PATCH_K, CV_WIDTH, 0);  // the conv weight [1280][3][14][14] flattened; K padded 588 -> 640
+    b.linw("embeddings.position_embedding", CV_WIDTH, CV_TOKENS, 0);  // [257][1280], kept as fp16: the patch GEMM's residual operand
+    b.out.back().bound = 0.5f;
+    b.norm("pre_layrnorm", CV_WIDTH);
+    for (int i = 0; i < CV_LAYERS; i++) {
+      const std::string n = "layers." + std::to_string(i);
+      b.norm(n + ".ln1", CV_WIDTH);
+      b.lin(n + ".in_proj", CV_WIDTH, 3 * CV_WIDTH);
+      b.lin(n + ".out_proj", CV_WIDTH, CV_WIDTH);
+      b.norm(n + ".ln2", CV_WIDTH);
+      b.lin(n + ".fc1", CV_WIDTH, CV_MLP);
+      b.lin(n + ".fc2", CV_MLP, CV_WIDTH);
+    }
+    b.norm("post_layernorm", CV_WIDTH);
+    b.linw("visual_projection", CV_WIDTH, CV_EMBED, 0);
   } else if (is_clip_kind(kind)) {  // clip.mojo:74-88 ; parameter order = oracle/spec.py clip_params()
     ParamSpec t;
     const int W = clip_kind_width(kind), NL = clip_kind_layers(kind);
@@ -369,6 +388,10 @@ extern "C" double tsd_flop_count(int kind, int L, int T) {
   } else if (is_clip_kind(kind)) {  // per prompt: 12 x (in_proj, QK^T, PV, out_proj, 768->3072->768) on 77 tokens
     const double Tc = 77, D = clip_kind_width(kind);
     f = (double)clip_kind_layers(kind) * (lin_f(Tc, D, 3 * D) + 2.0 * 2.0 * Tc * Tc * D + lin_f(Tc, D, D) + lin_f(Tc, D, 4 * D) + lin_f(Tc, 4 * D, D));
+  } else if (is_clip_vision_kind(kind)) {  // per image (L and T are not read): 32 x (four linears on 257 rows, QK^T and PV) + patch GEMM + projection
+    const double Tv = CV_TOKENS, D = CV_WIDTH;
+    f = (double)CV_LAYERS * (lin_f(Tv, D, 3 * D) + 2.0 * 2.0 * Tv * Tv * D + lin_f(Tv, D, D) + lin_f(Tv, D, CV_MLP) + lin_f(Tv, CV_MLP, D)) +
+        lin_f(CV_PATCHES, CV_PATCH_K, D) + lin_f(1, D, CV_EMBED);
   } else {
     return -1.0;
   }

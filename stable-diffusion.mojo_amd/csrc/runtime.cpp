@@ -110,6 +110,7 @@ extern "C" int tsd_ctx_destroy(tsd_ctx* c) {
   if (c->zeros) hipFree(c->zeros);
   if (c->status) hipFree(c->status);
   if (c->sk_flags) hipFree(c->sk_flags);
+  for (VisionTab& t : c->vision_tabs) if (t.dev) hipFree(t.dev);
   hipEventDestroy(c->ev0);
   hipEventDestroy(c->ev1);
   hipStreamDestroy(c->stream);

@@ -8,6 +8,7 @@
   tsd.vae        <-> vae.mojo               Attention_Block, Res_Block, Decoder, Encoder
   tsd.sampler    <-> sampler.mojo           DDPMSampler (+ DDIMSampler, DPMSolverMultistepSampler: no reference counterpart)
   tsd.clip       <-> clip.mojo              CLIP text encoder (token ids -> context)
+                 (+ CLIPVision, which has no reference counterpart: pixels -> the image embedding an IPAdapter projects)
   tsd.tokenizer  <-> helpers/utils.mojo     Tokenizer, bpe_encode (host-only logic inside libtsd)
   tsd.pipeline   <-> pipeline.mojo          generate (hot loop; the context embedding is an input)
   tsd.serve      (no reference counterpart) continuous batching over a slot session: SlotScheduler, generate_stream
@@ -27,7 +28,7 @@ from .attention import Cross_Attention, Self_Attention  # noqa: F401
 from .diffusion import (ControlNet, Diffusion, IPAdapter, Time_Embedding, UNet, UNet_Output_Layer, Unet_Attention_Block,  # noqa: F401
                         Unet_Residual_Block)
 from .vae import Attention_Block, Decoder, Encoder, Res_Block  # noqa: F401
-from .clip import CLIP  # noqa: F401
+from .clip import CLIP, CLIPVision, clip_image_patches  # noqa: F401
 from .tokenizer import Tokenizer, process_prompt  # noqa: F401
 from .sampler import DDIMSampler, DDPMSampler, DPMSolverMultistepSampler  # noqa: F401
 from .pipeline import encode_prompts, generate  # noqa: F401

@@ -25,6 +25,7 @@ MODEL_CLIP_TORCH, MODEL_DECODER_TORCH, MODEL_ENCODER_TORCH = 7, 8, 9
 MODEL_CONTROLNET_SD15, MODEL_CONTROLNET_SD15_TORCH = 10, 11
 MODEL_DIFFUSION_SD2, MODEL_CLIP_SD2 = 16, 17    # 12 - 15 are reserved and refused
 MODEL_IP_ADAPTER_SD15 = 20                      # 18 and 19 are refused as well
+MODEL_CLIP_VISION_H = 22                        # ... and so are 21 and 23
 SAMPLER_KINDS = {"ddpm": 0, "ddim": 1, "dpmpp_2m": 2}      # tsd_sampler_kind
 TIMESTEP_SPACINGS = {"leading": 0, "trailing": 1}          # tsd_timestep_spacing
 MASK_MODES = {"area": 0, "any": 1}                         # tsd_mask_mode
@@ -150,6 +151,9 @@ def _declare(l):
         "tsd_session_set_ip_adapter": ([vp, vp, fp, fp, i, f, i, i], i), "tsd_session_ip_adapter_active": ([vp], i),
         "tsd_debug_ip_attn_run": ([vp, C.POINTER(i64), i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)], i),
         "tsd_debug_ip_attn_bench": ([vp, i, i, i, i, i, i, fp], i),
+        "tsd_clip_image_patches_f16": ([vp, fp, i, i, i, vp], i),
+        "tsd_clip_vision_forward": ([vp, fp, i, i, i, fp, fp], i),
+        "tsd_debug_image_patches_run": ([vp, C.POINTER(i64), i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)], i),
         "tsd_tokenizer_create": ([C.c_char_p, i, C.POINTER(vp)], i),
         "tsd_tokenizer_create_from_memory": ([C.c_char_p, C.c_size_t, i, C.POINTER(vp)], i),
         "tsd_tokenizer_destroy": ([vp], i),

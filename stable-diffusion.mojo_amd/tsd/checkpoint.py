@@ -337,6 +337,86 @@ def load_ip_adapter(path_or_state, ctx=None, prefix=""):
     return IPAdapter(ctx=ctx, params=params)
 
 
+# ---- CLIP vision encoder (HF CLIPVisionModelWithProjection, the `image_encoder/` folder of the IP-Adapter files -> kind "clip_vision_h") ----
+_CV_LAYER = (("ln1", "layer_norm1"), ("out_proj", "self_attn.out_proj"), ("ln2", "layer_norm2"), ("fc1", "mlp.fc1"), ("fc2", "mlp.fc2"))
+CLIP_VISION_WIDTH = 1280
+
+
+def clip_vision_to_params(state, prefix=""):
+    """Hugging Face CLIPVisionModelWithProjection state dict (tensors or arrays) -> {our parameter name: array} for kind "clip_vision_h".
+
+    THE KEY MAP: `vision_model.embeddings.class_embedding` [1280], `.patch_embedding.weight` [1280][3][14][14] (flattened to [1280][588],
+    column c * 196 + kh * 14 + kw) and `.position_embedding.weight` [257][1280]; `vision_model.pre_layrnorm` (HF's spelling);
+    `vision_model.encoder.layers.N.{layer_norm1, self_attn.{q,k,v,out}_proj, layer_norm2, mlp.fc1, mlp.fc2}` with q / k / v stacked into
+    `layers.N.in_proj`; `vision_model.post_layernorm`; `visual_projection.weight` [1024][1280].  A `position_ids` buffer is ignored.  As
+    many layers as the state dict holds are mapped (the model wants 32).  ValueError for a missing tensor, naming it, and for a state
+    dict of another width (a ViT-L file is 1024 wide)."""
+    def g(k):
+        if prefix + k not in state:
+            raise ValueError(f"checkpoint has no tensor {prefix + k}")
+        v = state[prefix + k]
+        return np.asarray(v.detach().cpu().numpy() if hasattr(v, "detach") else v, dtype=np.float32)
+
+    vm = "vision_model."
+    cls = g(vm + "embeddings.class_embedding").reshape(-1)
+    if cls.shape[0] != CLIP_VISION_WIDTH:
+        raise ValueError(f"this vision tower is {cls.shape[0]} wide; kind clip_vision_h is OpenCLIP ViT-H/14, {CLIP_VISION_WIDTH} wide "
+                         "(a ViT-L/14 file is 1024 wide)")
+    pw = g(vm + "embeddings.patch_embedding.weight")
+    if pw.shape != (CLIP_VISION_WIDTH, 3, 14, 14):
+        raise ValueError(f"{prefix + vm}embeddings.patch_embedding.weight has shape {pw.shape}, expected {(CLIP_VISION_WIDTH, 3, 14, 14)}")
+    out = {"embeddings.class_embedding": cls, "embeddings.patch_embedding.weight": pw.reshape(CLIP_VISION_WIDTH, 588),
+           "embeddings.position_embedding.weight": g(vm + "embeddings.position_embedding.weight")}
+    for ours, theirs in (("pre_layrnorm", vm + "pre_layrnorm"), ("post_layernorm", vm + "post_layernorm")):
+        out[ours + ".weight"], out[ours + ".bias"] = g(theirs + ".weight"), g(theirs + ".bias")
+    i = 0
+    while prefix + vm + f"encoder.layers.{i}.layer_norm1.weight" in state:
+        h, n = vm + f"encoder.layers.{i}.", f"layers.{i}"
+        out[n + ".in_proj.weight"] = np.concatenate([g(h + f"self_attn.{x}_proj.weight") for x in "qkv"])
+        out[n + ".in_proj.bias"] = np.concatenate([g(h + f"self_attn.{x}_proj.bias") for x in "qkv"])
+        for ours, theirs in _CV_LAYER:
+            out[f"{n}.{ours}.weight"], out[f"{n}.{ours}.bias"] = g(h + theirs + ".weight"), g(h + theirs + ".bias")
+        i += 1
+    out["visual_projection.weight"] = g("visual_projection.weight")
+    return out
+
+
+def params_to_clip_vision(params, prefix=""):
+    """Inverse of `clip_vision_to_params` (export; used by the round-trip test): HF's key layout, the patch embedding as a convolution."""
+    p = lambda k: np.asarray(params[k], np.float32)  # noqa: E731
+    vm = prefix + "vision_model."
+    out = {vm + "embeddings.class_embedding": p("embeddings.class_embedding"),
+           vm + "embeddings.patch_embedding.weight": p("embeddings.patch_embedding.weight").reshape(-1, 3, 14, 14),
+           vm + "embeddings.position_embedding.weight": p("embeddings.position_embedding.weight"),
+           prefix + "visual_projection.weight": p("visual_projection.weight")}
+    for ours in ("pre_layrnorm", "post_layernorm"):
+        out[vm + ours + ".weight"], out[vm + ours + ".bias"] = p(ours + ".weight"), p(ours + ".bias")
+    i = 0
+    while f"layers.{i}.ln1.weight" in params:
+        h, n = vm + f"encoder.layers.{i}.", f"layers.{i}"
+        for x, w, b in zip("qkv", np.split(p(n + ".in_proj.weight"), 3), np.split(p(n + ".in_proj.bias"), 3)):
+            out[h + f"self_attn.{x}_proj.weight"], out[h + f"self_attn.{x}_proj.bias"] = w, b
+        for ours, theirs in _CV_LAYER:
+            out[h + theirs + ".weight"], out[h + theirs + ".bias"] = p(f"{n}.{ours}.weight"), p(f"{n}.{ours}.bias")
+        i += 1
+    return out
+
+
+def load_clip_vision(path_or_state, ctx=None, prefix=""):
+    """tsd.CLIPVision with the weights of a CLIPVisionModelWithProjection safetensors file (`image_encoder/model.safetensors` of
+    h94/IP-Adapter: OpenCLIP ViT-H/14) or its state dict.  ValueError for a missing tensor (named), another width, another shape."""
+    from .clip import CLIPVision
+    from .model import param_specs
+    state = read_safetensors(path_or_state) if isinstance(path_or_state, str) else path_or_state
+    params = clip_vision_to_params(state, prefix)
+    for name, shape, _, _ in param_specs("clip_vision_h"):
+        if name not in params:
+            raise ValueError(f"checkpoint has no tensor for {name} (the encoder has 32 layers)")
+        if tuple(np.shape(params[name])) != tuple(shape):
+            raise ValueError(f"{name}: checkpoint shape {np.shape(params[name])}, model expects {shape}")
+    return CLIPVision(ctx=ctx, params=params)
+
+
 def hf_clip_text_to_params(state):
     """Hugging Face CLIPTextModel state dict (with or without the `text_model.` prefix; tensors or arrays) ->
     {our parameter name: array} for kind "clip_torch" (q/k/v stacked into the reference's in_proj), or for kind "clip_sd2" when the

@@ -35,3 +35,56 @@ class CLIP:
         if check(code, True):
             return NULL_MATRIX()
         return out[0] if single else out
+
+
+def _images(images, who):
+    a = np.ascontiguousarray(images, dtype=np.float32)
+    single = a.ndim == 3
+    if single:
+        a = a[None]
+    if a.ndim != 4 or a.shape[1] != 3:
+        raise ValueError(f"{who}: images must have shape (3, H, W) or (B, 3, H, W) on the 0 .. 255 scale, got {np.shape(images)}")
+    return a, single
+
+
+def clip_image_patches(images, ctx=None):
+    """The vision encoder's image front end alone (`tsd_clip_image_patches_f16`): images (3,H,W) or (B,3,H,W) float on 0 .. 255, sides
+    8 .. 2048 -> float16 (256, 592) or (B, 256, 592): resized (PIL's antialiased bicubic, shortest edge 224), centre-cropped to 224x224,
+    normalised with CLIP's mean / std; row py * 16 + px, column c * 196 + kh * 14 + kw, columns 588 .. 591 zero."""
+    from . import _lib
+    a, single = _images(images, "clip_image_patches")
+    B, _, H, W = a.shape
+    out = np.empty((B, 256, 592), dtype=np.float16)
+    check(lib().tsd_clip_image_patches_f16((ctx or _lib.default_context()).h, a.ctypes.data_as(C.POINTER(C.c_float)), B, H, W, out.ctypes.data))
+    return out[0] if single else out
+
+
+class CLIPVision:
+    """The CLIP vision encoder the published `ip-adapter_sd15` files were trained against (no reference counterpart): OpenCLIP ViT-H/14 as
+    Hugging Face ships it in the `image_encoder/` folder of h94/IP-Adapter - 14x14 patches of a 224x224 crop, 257 tokens of width 1280,
+    32 pre-LN layers of 16 heads, erf-GELU MLP, post-LayerNorm of the class token, 1280 -> 1024 projection.
+
+    forward(images): (3,H,W) or (B,3,H,W) float on the 0 .. 255 scale (what `generate(input_image=)` takes), sides 8 .. 2048, B <= 16
+    -> (1024,) or (B,1024) float32, HF's `image_embeds`: the `ip_image_embeds` of `generate` / the input of `IPAdapter.project`.
+    forward(images, hidden=True) -> (image_embeds, hidden) with hidden (257,1280) or (B,257,1280), HF's `hidden_states[-2]` (the input
+    of the last layer, no post-LayerNorm).  The resize is the float form of CLIPImageProcessor's (`clip_image_patches`): it does not
+    round the resized image to uint8; a 224x224 input is not resampled at all."""
+
+    def __init__(self, seed=0, ctx=None, params=None, variant="clip_vision_h"):
+        if variant != "clip_vision_h":
+            raise ValueError(f"CLIPVision: unknown variant {variant!r} (clip_vision_h)")
+        self.model = Model(variant, ctx=ctx, seed=None if params is not None else seed)
+        if params is not None:
+            self.model.load_params(params)
+
+    def forward(self, images, hidden=False):
+        a, single = _images(images, "CLIPVision.forward")
+        B, _, H, W = a.shape
+        fp = C.POINTER(C.c_float)
+        emb = np.empty((B, 1024), dtype=np.float32)
+        hid = np.empty((B, 257, 1280), dtype=np.float32) if hidden else None
+        check(lib().tsd_clip_vision_forward(self.model.h, a.ctypes.data_as(fp), B, H, W, emb.ctypes.data_as(fp),
+                                            hid.ctypes.data_as(fp) if hidden else None))
+        if hidden:
+            return (emb[0], hid[0]) if single else (emb, hid)
+        return emb[0] if single else emb

@@ -221,8 +221,9 @@ class IPAdapter:
     """IP-Adapter of the full-size SD-1.x UNet (Ye et al. 2023; the layout of the published ip-adapter_sd15 files) - device-resident
     weights: the image projection and one to_k_ip / to_v_ip pair per cross-attention block (model kind "ip_adapter_sd15").
     project(image_embeds) -> the N = 4 image tokens; `Diffusion.forward(ip_adapter=, ip_tokens=, ip_scale=)`, `Session.set_ip_adapter`
-    and `generate(ip_adapter=, ip_image_embeds=)` consume them.  The CLIP vision encoder is not part of it: callers bring the 1024-wide
-    image embedding (diffusers' `ip_adapter_image_embeds`).  See tsd.checkpoint.load_ip_adapter."""
+    and `generate(ip_adapter=, ip_image_embeds=)` consume them.  The 1024-wide image embedding (diffusers' `ip_adapter_image_embeds`)
+    comes from the CLIP vision encoder, `tsd.CLIPVision.forward(image)`, or from the caller; `generate(ip_adapter=, ip_image=,
+    image_encoder=)` runs the encoder itself.  See tsd.checkpoint.load_ip_adapter / load_clip_vision."""
     N_TOKENS = 4
 
     def __init__(self, seed=0, ctx=None, params=None):

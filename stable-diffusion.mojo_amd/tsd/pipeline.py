@@ -28,7 +28,7 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
              num_training_steps=1000, L=64, return_latents=False, sampler="ddpm", eta=0.0, spacing="leading", mask=None,
              mask_mode="any", seeds=None, guidance_rescale=0.0, prediction="epsilon", zero_terminal_snr=False, controlnet=None,
              control_image=None, control_scale=1.0, control_cond_only=False, control_start=0.0, control_end=1.0, ip_adapter=None,
-             ip_image_embeds=None, ip_scale=1.0, ip_start=0.0, ip_end=1.0):
+             ip_image_embeds=None, ip_scale=1.0, ip_start=0.0, ip_end=1.0, ip_image=None, image_encoder=None):
     """context (B,T,768); returns images (B,3,8LH,8LW) in [0,255] like pipeline.mojo:127.  L is the latent side (64: 512x512) or a pair
     (LH, LW) for a rectangular image ((96, 64): 512 wide, 768 high); where the text below says L,L the tensor is LH,LW.
 
@@ -62,12 +62,23 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
     control_cond_only: with cfg, only the conditional half is controlled (`Session.set_control`).
 
     ip_adapter, a `tsd.IPAdapter` on the diffusion model's context (full-size SD-1.x variants), with ip_image_embeds (1024,) or (B,1024),
-    the CLIP image embedding of the prompt image (diffusers' ip_adapter_image_embeds; the vision encoder is not part of this package):
-    every step whose index lies in [ip_start, ip_end] as fractions of the step list adds the attention over the projected image tokens,
+    the CLIP image embedding of the prompt image (diffusers' ip_adapter_image_embeds) - or with the prompt image itself: ip_image
+    (3,H,W) or (B,3,H,W) on the 0 .. 255 scale and image_encoder, a `tsd.CLIPVision` on the same context, whose `forward(ip_image)` gives
+    those embeddings (`checkpoint.load_clip_vision` reads the `image_encoder/` folder the adapter files come with).
+    Every step whose index lies in [ip_start, ip_end] as fractions of the step list adds the attention over the projected image tokens,
     scaled by ip_scale, in every cross-attention block.  With cfg the unconditional half reads the projection of a zero embedding, as
     diffusers does (`Session.set_ip_adapter`)."""
-    if (ip_adapter is None) != (ip_image_embeds is None):
-        raise ValueError("generate: ip_adapter and ip_image_embeds go together")
+    if ip_image is not None and ip_image_embeds is not None:
+        raise ValueError("generate: pass ip_image or ip_image_embeds, not both")
+    if ip_image is not None and image_encoder is None:
+        raise ValueError("generate: ip_image needs image_encoder (a tsd.CLIPVision) to turn the pixels into the image embedding")
+    if (ip_adapter is None) != (ip_image_embeds is None and ip_image is None):
+        raise ValueError("generate: ip_adapter goes together with ip_image_embeds or ip_image")
+    if ip_image is not None:
+        if np.ndim(ip_image) not in (3, 4) or np.shape(ip_image)[-3] != 3:
+            raise ValueError(f"generate: ip_image must have shape (3, H, W) or (B, 3, H, W), got {np.shape(ip_image)}")
+        if getattr(image_encoder.model, "ctx", None) is not diffusion.model.ctx:
+            raise ValueError("generate: image_encoder and the diffusion model belong to different contexts")
     if ip_adapter is not None and not (0.0 <= ip_start <= ip_end <= 1.0):
         raise ValueError(f"generate: ip_start / ip_end must satisfy 0 <= start <= end <= 1, got {ip_start}, {ip_end}")
     if (controlnet is None) != (control_image is None):
@@ -137,10 +148,10 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
         first = int(np.ceil(ip_start * n - 1e-9))
         last = int(np.floor(ip_end * n + 1e-9)) - 1
         if last >= first:
-            e = np.asarray(ip_image_embeds, dtype=np.float32)
+            e = np.asarray(image_encoder.forward(ip_image) if ip_image is not None else ip_image_embeds, dtype=np.float32)
             e = np.repeat(e[None], B, axis=0) if e.ndim == 1 else e
             if e.shape != (B, 1024):
-                raise ValueError(f"generate: ip_image_embeds must have shape (1024,) or ({B}, 1024), got {np.shape(ip_image_embeds)}")
+                raise ValueError(f"generate: the image embeddings must have shape (1024,) or ({B}, 1024), got {e.shape}")
             sess.set_ip_adapter(ip_adapter, ip_adapter.project(e), ip_adapter.project(np.zeros_like(e)) if cfg else None, ip_scale, first, last)
     for i in range(n):  # pipeline.mojo:87-122
         sess.step(i)
