@@ -188,7 +188,7 @@ int tsd_vae_attention_block_f32(tsd_ctx* ctx, const float* x, int C, int H, int 
  * norms - 32 groups in the residual blocks (the reference declares 16, vae.mojo:42-43), per-channel weight / bias of
  * every GroupNorm appended to the kind-2 / kind-3 list (`lN.group_norm1`, `lN.group_norm2`, `lN.group_norm`, and
  * `lN` for the stand-alone norm), eps inside the root: the layout of diffusers' AutoencoderKL decoder / encoder. */
-typedef enum tsd_model_kind { TSD_MODEL_DIFFUSION = 1, TSD_MODEL_DECODER = 2, TSD_MODEL_ENCODER = 3, TSD_MODEL_CLIP = 4, TSD_MODEL_DIFFUSION_SD15 = 5, TSD_MODEL_DIFFUSION_SD15_TORCH = 6, TSD_MODEL_CLIP_TORCH = 7, TSD_MODEL_DECODER_TORCH = 8, TSD_MODEL_ENCODER_TORCH = 9, TSD_MODEL_CONTROLNET_SD15 = 10, TSD_MODEL_CONTROLNET_SD15_TORCH = 11, TSD_MODEL_DIFFUSION_SD2 = 16, TSD_MODEL_CLIP_SD2 = 17, TSD_MODEL_IP_ADAPTER_SD15 = 20, TSD_MODEL_CLIP_VISION_H = 22 } tsd_model_kind;
+typedef enum tsd_model_kind { TSD_MODEL_DIFFUSION = 1, TSD_MODEL_DECODER = 2, TSD_MODEL_ENCODER = 3, TSD_MODEL_CLIP = 4, TSD_MODEL_DIFFUSION_SD15 = 5, TSD_MODEL_DIFFUSION_SD15_TORCH = 6, TSD_MODEL_CLIP_TORCH = 7, TSD_MODEL_DECODER_TORCH = 8, TSD_MODEL_ENCODER_TORCH = 9, TSD_MODEL_CONTROLNET_SD15 = 10, TSD_MODEL_CONTROLNET_SD15_TORCH = 11, TSD_MODEL_DIFFUSION_SD2 = 16, TSD_MODEL_CLIP_SD2 = 17, TSD_MODEL_IP_ADAPTER_SD15 = 20, TSD_MODEL_CLIP_VISION_H = 22, TSD_MODEL_IP_ADAPTER_PLUS_SD15 = 24 } tsd_model_kind;
 /* TSD_MODEL_CONTROLNET_SD15 (EXTENSION: Zhang et al. 2023; the layout of diffusers' ControlNetModel): the control network of the full-size
  * UNet.  Parameters in this order: `time_embed.layer1/2`; the hint encoder `hint.conv1 .. hint.conv8` (3x3 convolutions 3->16, 16->16,
  * 16->32 stride 2, 32->32, 32->96 stride 2, 96->96, 96->256 stride 2, 256->320; SiLU after each but the last, the last initialised to
@@ -316,8 +316,9 @@ int tsd_control_inject_f16(tsd_ctx* ctx, int n, const void* const* x, const void
  * bias, <i> the odd number the published files give the block (1 .. 11 the encoder, 31 the bottleneck, 13 .. 29 the decoder).  N = 4.
  * The 16 to_k_ip matrices are contiguous in the packed blob and the 16 to_v_ip matrices follow them, so K_ip and V_ip^T of all blocks are
  * one GEMM (two where the fused form does not apply) over the tokens staged as 16 fp16 rows per sample, rows N .. 15 zero.
- * tsd_flop_count returns -1 and tsd_model_lora_add refuses the kind.  The resampler of the "plus" files is not part of it: callers bring
- * the 1024-wide image embedding - tsd_clip_vision_forward below computes it from pixels - or the tokens themselves.
+ * tsd_flop_count returns -1 and tsd_model_lora_add refuses the kind.  Callers bring the 1024-wide image embedding -
+ * tsd_clip_vision_forward below computes it from pixels - or the tokens themselves.  The "plus" files are a kind of their own, with
+ * their resampler: TSD_MODEL_IP_ADAPTER_PLUS_SD15, "IP-Adapter Plus" below.
  * tsd_ip_adapter_project: embeds [B][1024] -> tokens_out [B][N][768] = LayerNorm(Linear(embeds)) per token (eps 1e-5); every value is
  * exactly an fp16.
  * tsd_diffusion_forward_ip_hw: tsd_diffusion_forward_hw of `unet` (kinds 5 / 6; TSD_E_ARG for the Tiny-SD graph, the SD-2.x kind and a
@@ -329,6 +330,30 @@ int tsd_control_inject_f16(tsd_ctx* ctx, int n, const void* const* x, const void
  *     O <- rn16( f32(O) + s_b * (sum_j p_j V_ip[j]) / sum_j p_j ),   p_j = rn16( exp(scale (q . K_ip[j]) - max_j) ),  j < N
  * A sample whose scale is exactly 0 is neither read nor written by it.  All models on one tsd_ctx. */
 int tsd_ip_adapter_project(tsd_model* ip, const float* embeds, int B, float* tokens_out);
+/* ---- IP-Adapter Plus (EXTENSION: the layout of the published ip-adapter-plus_sd15 / ip-adapter-plus-face_sd15 files): the same adapter
+ * behind a Perceiver resampler.  TSD_MODEL_IP_ADAPTER_PLUS_SD15 (24; 12 - 15, 18, 19, 21 and 23 stay reserved and refused) holds, under the
+ * published names and in the module's state-dict order: `image_proj.latents` [1][16][768] (kept as fp16), `image_proj.proj_in.weight`
+ * [768][1280] and `.bias`, `image_proj.proj_out.weight` [768][768] and `.bias`, `image_proj.norm_out.weight` / `.bias`; per layer L = 0 .. 3
+ * `image_proj.layers.L.0.norm1` and `.0.norm2` (weight / bias), `.0.to_q.weight` [768][768], `.0.to_kv.weight` [1536][768] (K rows first),
+ * `.0.to_out.weight` [768][768], `.1.0.weight` / `.bias` (the feed-forward LayerNorm), `.1.1.weight` [3072][768], `.1.3.weight` [768][3072],
+ * none of these linears with a bias; then the 32 `ip_adapter.<i>.to_k_ip.weight` / `.to_v_ip.weight` entries exactly as kind 20 lists and
+ * packs them: 83 parameters, 49 087 488 elements.  The layout is written from memory of the published module, not checked against a
+ * real file.  tsd_flop_count, tsd_model_lora_add and tsd_model_context_width answer as for kind 20.
+ * tsd_ip_adapter_resample: hidden fp32 [B][S][1280] (tsd_clip_vision_forward's hidden_out at S = 257) -> tokens_out fp32 [B][16][768],
+ * every value exactly an fp16.  For one sample, LayerNorms torch's with eps 1e-5:
+ *     x = hidden . proj_in^T + b_in;  lat = latents;  four times:  xn = LN(x; norm1), ln = LN(lat; norm2), q = ln . Wq^T,
+ *     k | v = concat(ln, xn) . Wkv^T, per head of 64 columns (12 heads) a = softmax(q k^T / 8) v over all S + 16 keys (no mask),
+ *     lat = a . Wo^T + lat,  lat = gelu_erf(LN(lat; ff_norm) . W1^T) . W2^T + lat;   tokens = LN(lat . proj_out^T + b_out; norm_out)
+ * (the 16 latent keys stand in front of the S image keys: softmax does not depend on the order, and the pad behind a sample's keys stays
+ * at one end).  Existing kernels only, about 2 B + 8 launches a layer; activations are fp16, sums fp32; a sample's bits do not depend on B
+ * or on its batch position.  1 <= B <= 16 and 1 <= S <= 1024, TSD_E_SHAPE otherwise; TSD_E_ARG for a kind-20 model, and
+ * tsd_ip_adapter_project on a kind-24 model is TSD_E_ARG with a message that names this entry; a refusal leaves tokens_out untouched.
+ * Host in, host out, synchronous.  A non-finite value in `hidden` (or an fp16 overflow on the way) is not looked for at the entry: it
+ * spreads through the norms and GEMMs, tokens_out is written with the resulting inf / NaN, the launch that writes it counts them and the
+ * call returns TSD_E_NONFINITE - the convention of every entry whose output leaves the device (tsd_debug_nonfinite_count).
+ * The tokens go where kind 20's go: tsd_diffusion_forward_ip_hw and tsd_session_set_ip_adapter take a kind-24 model wherever they take
+ * kind 20, with N the caller's (16 in use); tsd_clip_vision_forward below gives `hidden`. */
+int tsd_ip_adapter_resample(tsd_model* ip, const float* hidden, int B, int S, float* tokens_out);
 int tsd_diffusion_forward_ip_hw(tsd_model* unet, tsd_model* ip, const float* tokens, int N, const float* ip_scale, tsd_model* cn,
                                 const float* hint, const float* control_scale, const float* latents, const float* context,
                                 const float* time_emb, int B, int LH, int LW, int T, float* eps_out);

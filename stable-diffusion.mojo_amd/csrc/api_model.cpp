@@ -181,6 +181,9 @@ extern "C" int tsd_diffusion_forward_control_hw(tsd_model* unet, tsd_model* cn, 
 extern "C" int tsd_ip_adapter_project(tsd_model* ip, const float* embeds, int B, float* tokens_out) {
   NOTNULL(ip); NOTNULL(embeds); NOTNULL(tokens_out);
   if (!is_ip_adapter_kind(ip->kind)) TSD_FAIL(TSD_E_ARG, "tsd_ip_adapter_project: model is not an IP-Adapter");
+  if (is_ip_plus_kind(ip->kind))
+    TSD_FAIL(TSD_E_ARG, "tsd_ip_adapter_project: an IP-Adapter Plus reads the vision encoder's hidden states, not the image embedding: "
+                        "call tsd_ip_adapter_resample");
   if (B <= 0 || B > 16) TSD_FAIL(TSD_E_SHAPE, "ip_adapter_project: B=%d (1..16)", B);
   tsd_ctx* ctx = ip->ctx;
   return run_model(ip, [&]() -> int {
@@ -191,6 +194,26 @@ extern "C" int tsd_ip_adapter_project(tsd_model* ip, const float* embeds, int B,
     TSD_TRY(h2d(ctx, de, embeds, ne * 4));
     TSD_TRY(g_ip_project(ip, de, B, dt));
     return d2h(ctx, tokens_out, dt, nt * 4);
+  });
+}
+
+// the "plus" adapter's image projection: the vision encoder's hidden states -> 16 tokens (graph.cpp g_ip_resample)
+extern "C" int tsd_ip_adapter_resample(tsd_model* ip, const float* hidden, int B, int S, float* tokens_out) {
+  NOTNULL(ip); NOTNULL(hidden); NOTNULL(tokens_out);
+  if (!is_ip_adapter_kind(ip->kind)) TSD_FAIL(TSD_E_ARG, "tsd_ip_adapter_resample: model is not an IP-Adapter");
+  if (!is_ip_plus_kind(ip->kind))
+    TSD_FAIL(TSD_E_ARG, "tsd_ip_adapter_resample: this IP-Adapter has no resampler, it reads the 1024-wide image embedding: "
+                        "call tsd_ip_adapter_project");
+  if (B <= 0 || B > 16 || S <= 0 || S > IPP_MAX_S) TSD_FAIL(TSD_E_SHAPE, "ip_adapter_resample: B=%d (1..16) S=%d (1..%d)", B, S, IPP_MAX_S);
+  tsd_ctx* ctx = ip->ctx;
+  return run_model(ip, [&]() -> int {
+    const int64_t nh = (int64_t)B * S * IPP_EMBED, nt = (int64_t)B * IPP_TOKENS * IP_CTX_DIM;
+    float* dh = arena_alloc<float>(ctx, nh);
+    float* dt = arena_alloc<float>(ctx, nt);
+    if (!dh || !dt) TSD_FAIL(TSD_E_ALLOC, "workspace arena exhausted");
+    TSD_TRY(h2d(ctx, dh, hidden, (size_t)nh * 4));
+    TSD_TRY(g_ip_resample(ip, dh, B, S, dt));
+    return d2h(ctx, tokens_out, dt, (size_t)nt * 4);
   });
 }
 

@@ -808,6 +808,7 @@ int g_ip_kv(tsd_model* ip, const half_t* tok16, int B, half_t* k_all, half_t* vt
 int g_ip_project(tsd_model* ip, const float* embeds, int B, float* tokens_out) {
   tsd_ctx* ctx = ip->ctx;
   if (!is_ip_adapter_kind(ip->kind)) TSD_FAIL(TSD_E_ARG, "g_ip_project: model is not an IP-Adapter");
+  if (is_ip_plus_kind(ip->kind)) TSD_FAIL(TSD_E_ARG, "g_ip_project: an IP-Adapter Plus has no image_proj.proj (g_ip_resample)");
   const IpAdapterW& w = ip->ip;
   const int NT = w.n_tokens, D = IP_CTX_DIM;
   const size_t mark = ctx->arena.mark();
@@ -818,6 +819,91 @@ int g_ip_project(tsd_model* ip, const float* embeds, int B, float* tokens_out) {
   TSD_TRY(launch_f32_to_f16_rows(ctx, lin, (int64_t)B * NT, D, l16, D, (int64_t)B * NT));
   TSD_TRY(launch_layernorm(ctx, l16, (int64_t)B * NT, D, D, 1e-5f, ln, D, &w.norm));
   TSD_TRY(launch_f16_to_f32_rows(ctx, ln, (int64_t)B * NT, D, D, tokens_out));
+  ctx->arena.release(mark);
+  return TSD_OK;
+}
+
+// ---- IP-Adapter Plus (kind 24): the Perceiver resampler, existing launchers only -------------------------------------------------------------
+// hidden fp32 [B][S][1280] -> x = proj_in(hidden) [B*S][768]; lat [B*16][768] starts as the learned queries; four layers of
+//   kvin_b = [ LN(lat_b; norm2) (16 rows) | LN(x_b; norm1) (S rows) | zero rows up to Sp ],  Sp = round_up(S + 16, 8)
+//   q = kvin_b[0..16) . Wq^T;  K | V^T = kvin . Wkv^T in ONE GEMM over all B * Sp rows whose V half is stored transposed (GemmArgs::Vt)
+//   lat = Attn(q, K, V) . Wo^T + lat;  lat = W2 . gelu_erf(W1 . LN(lat; ff_norm)) + lat
+// then LN(proj_out(lat); norm_out) -> fp32.
+// Key order: the 16 latent keys FIRST, the S image keys behind them (softmax does not depend on the order; the published module puts the
+// latents last).  Every sample then owns Sp consecutive rows of kvin, a multiple of 8 as the transposed tail wants, with its live rows in
+// front; the LayerNorms write the live rows only, so rows S + 16 .. Sp - 1 keep the zeros of the one memset below, the GEMM (no bias)
+// turns them into zero K rows and zero V^T columns, and those are the at most 7 pad columns the flash kernel reads (k.Skv) and masks.
+// A LayerNorm launch has one row pitch, so norm1 and norm2 run once per sample: 2 B + 8 launches a layer.
+// No GEMM here passes a rows-per-sample hint, so none splits K (gemm_plan.cpp): a sample's bits are the same at every B and position.
+int g_ip_resample(tsd_model* ip, const float* hidden, int B, int S, float* tokens_out) {
+  tsd_ctx* ctx = ip->ctx;
+  if (!is_ip_plus_kind(ip->kind)) TSD_FAIL(TSD_E_ARG, "g_ip_resample: model is not an IP-Adapter Plus");
+  if (B < 1 || B > 16 || S < 1 || S > IPP_MAX_S) TSD_FAIL(TSD_E_SHAPE, "ip resample: B=%d (1..16) S=%d (1..%d)", B, S, IPP_MAX_S);
+  const IpAdapterW& w = ip->ip;
+  const int D = IP_CTX_DIM, E = IPP_EMBED, NQ = IPP_TOKENS, Sk = S + NQ, Sp = round_up(Sk, 8);
+  const int64_t MX = (int64_t)B * S, MQ = (int64_t)B * NQ, MK = (int64_t)B * Sp;
+  const size_t mark = ctx->arena.mark();
+  half_t* h16 = arena_alloc<half_t>(ctx, MX * E); CHECK_ALLOC(h16);
+  half_t* x = arena_alloc<half_t>(ctx, MX * D); CHECK_ALLOC(x);
+  half_t* kvin = arena_alloc<half_t>(ctx, MK * D); CHECK_ALLOC(kvin);
+  half_t* kk = arena_alloc<half_t>(ctx, MK * D); CHECK_ALLOC(kk);
+  half_t* vt = arena_alloc<half_t>(ctx, (int64_t)B * D * Sp); CHECK_ALLOC(vt);
+  half_t* lat = arena_alloc<half_t>(ctx, MQ * D); CHECK_ALLOC(lat);
+  half_t* lat2 = arena_alloc<half_t>(ctx, MQ * D); CHECK_ALLOC(lat2);
+  half_t* q = arena_alloc<half_t>(ctx, MQ * D); CHECK_ALLOC(q);
+  half_t* ao = arena_alloc<half_t>(ctx, MQ * D); CHECK_ALLOC(ao);
+  half_t* fn = arena_alloc<half_t>(ctx, MQ * D); CHECK_ALLOC(fn);
+  half_t* ff = arena_alloc<half_t>(ctx, MQ * IPP_FF); CHECK_ALLOC(ff);
+  TSD_TRY(zero_async(ctx, kvin, (size_t)MK * D * sizeof(half_t)));  // the pad rows S + 16 .. Sp - 1 of every sample: nothing writes them again
+  TSD_TRY(launch_f32_to_f16_rows(ctx, hidden, MX, E, h16, E, MX));
+  CatSrc a;
+  a.p0 = h16; a.ld0 = E; a.C0 = E;
+  TSD_TRY(g_linear(ctx, a, MX, w.proj_in.w, w.proj_in.Kpad, D, E, w.proj_in.b, nullptr, 0, 0, x, D));
+  if (ctx->launch())  // the learned queries are the same for every sample
+    for (int b = 0; b < B; b++)
+      HIP_TRY(hipMemcpyAsync(lat + (int64_t)b * NQ * D, w.latents, (size_t)NQ * D * sizeof(half_t), hipMemcpyDeviceToDevice, ctx->stream));
+  for (int l = 0; l < IPP_DEPTH; l++) {
+    const IpResampleLayerW& lw = w.layer[l];
+    for (int b = 0; b < B; b++) {
+      half_t* kb = kvin + (int64_t)b * Sp * D;
+      TSD_TRY(launch_layernorm(ctx, lat + (int64_t)b * NQ * D, NQ, D, D, 1e-5f, kb, D, &lw.norm2));
+      TSD_TRY(launch_layernorm(ctx, x + (int64_t)b * S * D, S, D, D, 1e-5f, kb + (int64_t)NQ * D, D, &lw.norm1));
+    }
+    {  // q_b = LN(lat_b) . Wq^T: the first 16 rows of every sample's block, a batch per sample
+      GemmArgs g;
+      g.A0 = kvin; g.lda0 = D; g.sA = (int64_t)Sp * D;
+      g.Wt = lw.to_q.w; g.ldw = lw.to_q.Kpad; g.sW = 0;
+      g.M = NQ; g.N = D; g.K = D; g.batch = B;
+      g.C = q; g.ldc = D; g.sC = (int64_t)NQ * D;
+      TSD_TRY(launch_gemm(ctx, g));
+    }
+    {  // K [B * Sp][768] token-major and V^T [B][768][Sp] from one GEMM (to_kv's rows 768 .. 1535 are the V half)
+      GemmArgs g;
+      g.A0 = kvin; g.lda0 = D; g.Wt = lw.to_kv.w; g.ldw = lw.to_kv.Kpad;
+      g.M = (int)MK; g.N = 2 * D; g.K = D; g.C = kk; g.ldc = D;
+      g.Vt = vt; g.vt_n0 = D; g.vt_ld = Sp; g.vt_S = Sp; g.vt_sB = (int64_t)D * Sp;
+      TSD_TRY(launch_gemm(ctx, g));
+    }
+    AttnArgs fa;
+    fa.Q = q; fa.ldq = D; fa.sQ = (int64_t)NQ * D;
+    fa.K = kk; fa.ldk = D; fa.sK = (int64_t)Sp * D;
+    fa.Vt = vt; fa.ldvt = Sp; fa.sVt = (int64_t)D * Sp;
+    fa.O = ao; fa.ldo = D; fa.sO = (int64_t)NQ * D;
+    fa.B = B; fa.H = IPP_HEADS; fa.d = IPP_DHEAD; fa.Sq = NQ; fa.Sk = Sk; fa.scale = 0.125f;  // (64^-1/4)^2
+    TSD_TRY(launch_flash_attention(ctx, fa));
+    a.p0 = ao; a.ld0 = D; a.C0 = D;
+    TSD_TRY(g_linear(ctx, a, MQ, lw.to_out.w, lw.to_out.Kpad, D, D, nullptr, lat, D, 0, lat2, D));
+    TSD_TRY(launch_layernorm(ctx, lat2, MQ, D, D, 1e-5f, fn, D, &lw.ff_norm));
+    a.p0 = fn;
+    TSD_TRY(g_linear(ctx, a, MQ, lw.ff1.w, lw.ff1.Kpad, IPP_FF, D, nullptr, nullptr, 0, 0, ff, IPP_FF));
+    TSD_TRY(launch_gelu_erf_f16(ctx, ff, MQ * IPP_FF));
+    CatSrc f; f.p0 = ff; f.ld0 = IPP_FF; f.C0 = IPP_FF;
+    TSD_TRY(g_linear(ctx, f, MQ, lw.ff2.w, lw.ff2.Kpad, D, IPP_FF, nullptr, lat2, D, 0, lat, D));
+  }
+  a.p0 = lat; a.ld0 = D; a.C0 = D;
+  TSD_TRY(g_linear(ctx, a, MQ, w.proj_out.w, w.proj_out.Kpad, D, D, w.proj_out.b, nullptr, 0, 0, lat2, D));
+  TSD_TRY(launch_layernorm(ctx, lat2, MQ, D, D, 1e-5f, fn, D, &w.norm_out));
+  TSD_TRY(launch_f16_to_f32_rows(ctx, fn, MQ, D, D, tokens_out));
   ctx->arena.release(mark);
   return TSD_OK;
 }

@@ -110,6 +110,9 @@ int g_ip_stage_tokens(tsd_ctx* ctx, const float* tokens, int B, int N, half_t* t
 int g_ip_kv(tsd_model* ip, const half_t* tok16, int B, half_t* k_all, half_t* vt_all);
 // image_proj: embeds fp32 [B][1024] (device) -> tokens fp32 [B][n_tokens][768] (device) = LayerNorm(Linear(e)), every value an fp16
 int g_ip_project(tsd_model* ip, const float* embeds, int B, float* tokens_out);
+// kind 24's image_proj, the Perceiver resampler: hidden fp32 [B][S][1280] (device; the vision encoder's hidden_out at S = 257) -> tokens
+// fp32 [B][16][768] (device), every value an fp16.  1 <= B <= 16, 1 <= S <= 1024.  One arena mark / release, no allocation, no synchronisation.
+int g_ip_resample(tsd_model* ip, const float* hidden, int B, int S, float* tokens_out);
 // ControlNet (kinds 10 / 11).  hint_chw: device fp32 [B,3,8LH,8LW] -> hint features fp16 NHWC [B,LH,LW,320] in the arena
 int g_controlnet_hint(tsd_model* m, const float* hint_chw, int B, int LH, int LW, Act* out);
 // pre: a UNetPre made from the ControlNet's OWN weights (g_unet_time_path / g_unet_ctx_kv on `m`), or nullptr

@@ -169,7 +169,7 @@ static size_t packed_bytes(const ParamSpec& p) {
   switch (p.kind) {
     case P_CONV_W: return (size_t)p.Opad * p.shape[2] * p.shape[3] * p.Kpad * sizeof(half_t);
     case P_CONV_B: return (size_t)p.Opad * sizeof(float);
-    case P_LIN_W: return (size_t)p.shape[0] * p.Kpad * sizeof(half_t);
+    case P_LIN_W: return (size_t)p.rows() * p.Kpad * sizeof(half_t);
     default: return (size_t)p.shape[0] * sizeof(float);
   }
 }
@@ -246,7 +246,7 @@ static int pack_param(tsd_model* m, int i, const float* dev_src) {
                               p.Kpad);
     case P_CONV_B: return launch_pack_bias(ctx, dev_src, (int)p.shape[0], (float*)dst, p.Opad, 0);
     case P_LIN_W:
-      return launch_pack_linear(ctx, dev_src, (int)p.shape[0], (int)p.shape[1], (half_t*)dst, p.Kpad, p.interleave);
+      return launch_pack_linear(ctx, dev_src, p.rows(), p.cols(), (half_t*)dst, p.Kpad, p.interleave);
     default: return launch_pack_bias(ctx, dev_src, (int)p.shape[0], (float*)dst, (int)p.shape[0], p.interleave);
   }
 }
@@ -361,7 +361,7 @@ extern "C" int tsd_model_get_param(tsd_model* m, int index, float* out, int64_t 
   HIP_TRY(hipMemcpy(raw.data(), m->blob + p.off, p.bytes, hipMemcpyDeviceToHost));
   const int N = (int)p.shape[0];
   if (p.kind == P_CONV_W) unpack_weight_host((const uint16_t*)raw.data(), N, (int)p.shape[1], (int)p.shape[2], p.Kpad, 0, out);
-  else if (p.kind == P_LIN_W) unpack_weight_host((const uint16_t*)raw.data(), N, (int)p.shape[1], 0, p.Kpad, p.interleave, out);
+  else if (p.kind == P_LIN_W) unpack_weight_host((const uint16_t*)raw.data(), p.rows(), p.cols(), 0, p.Kpad, p.interleave, out);
   else {
     const float* s = (const float*)raw.data();
     const bool inter = p.kind == P_LIN_B && p.interleave;
@@ -811,11 +811,37 @@ LinW model_lin(const tsd_model* m, const std::string& prefix, bool use_bias) {
 int model_resolve(tsd_model* m) {
   if (is_ip_adapter_kind(m->kind)) {
     IpAdapterW& ip = m->ip;
-    ip.n_tokens = IP_SD15_TOKENS;
-    ip.proj = model_lin(m, "image_proj.proj", true);
-    ip.norm.w = (const float*)(m->blob + m->params[m->index.at("image_proj.norm.weight")].off);
-    ip.norm.b = (const float*)(m->blob + m->params[m->index.at("image_proj.norm.bias")].off);
-    ip.norm.torch_rstd = 1;
+    auto aff = [&](const std::string& name) {
+      NormAffine a;
+      a.w = (const float*)(m->blob + m->params[m->index.at(name + ".weight")].off);
+      a.b = (const float*)(m->blob + m->params[m->index.at(name + ".bias")].off);
+      a.torch_rstd = 1;
+      return a;
+    };
+    if (is_ip_plus_kind(m->kind)) {  // the resampler in place of image_proj.proj / .norm
+      auto linw = [&](const std::string& name) {  // a weight with no bias entry behind it
+        const ParamSpec& pw = m->params[m->index.at(name + ".weight")];
+        LinW w;
+        w.w = (const half_t*)(m->blob + pw.off); w.N = pw.rows(); w.K = pw.cols(); w.Kpad = pw.Kpad;
+        return w;
+      };
+      ip.n_tokens = IPP_TOKENS;
+      ip.latents = (const half_t*)(m->blob + m->params[m->index.at("image_proj.latents")].off);
+      ip.proj_in = model_lin(m, "image_proj.proj_in", true);
+      ip.proj_out = model_lin(m, "image_proj.proj_out", true);
+      ip.norm_out = aff("image_proj.norm_out");
+      for (int l = 0; l < IPP_DEPTH; l++) {
+        const std::string n = "image_proj.layers." + std::to_string(l);
+        IpResampleLayerW& w = ip.layer[l];
+        w.norm1 = aff(n + ".0.norm1"); w.norm2 = aff(n + ".0.norm2"); w.ff_norm = aff(n + ".1.0");
+        w.to_q = linw(n + ".0.to_q"); w.to_kv = linw(n + ".0.to_kv"); w.to_out = linw(n + ".0.to_out");
+        w.ff1 = linw(n + ".1.1"); w.ff2 = linw(n + ".1.3");
+      }
+    } else {
+      ip.n_tokens = IP_SD15_TOKENS;
+      ip.proj = model_lin(m, "image_proj.proj", true);
+      ip.norm = aff("image_proj.norm");
+    }
     int kvoff = 0, t = 0;
     for (int i = 0; i < SD15_N; i++) {
       const LayerDef& l = SD15_STEPS[i].l;

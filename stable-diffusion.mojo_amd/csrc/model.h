@@ -26,6 +26,9 @@ struct ParamSpec {
     for (int i = 0; i < ndim; i++) n *= shape[i];
     return n;
   }
+  // P_LIN_W as the packer sees it: [rows][cols]; a 3-d entry is [1][rows][cols] (the resampler's `latents`)
+  int rows() const { return (int)shape[ndim == 3 ? 1 : 0]; }
+  int cols() const { return (int)shape[ndim == 3 ? 2 : 1]; }
 };
 
 // layer tables (diffusion.mojo:177-201, vae.mojo:94-112,194-219)
@@ -65,17 +68,22 @@ static inline bool is_torch_unet_kind(int kind) {
 // IP-Adapter of the SD-1.x full-size UNet (kind 20): the image projection and one to_k_ip / to_v_ip pair per cross-attention block of
 // SD15_STEPS, in the table's order; no graph of its own - the UNet's forward reads its projected keys / values (graph.h IpKV)
 constexpr int IP_SD15_TOKENS = 4, IP_EMBED_DIM = 1024, IP_CTX_DIM = 768;
-static inline bool is_ip_adapter_kind(int kind) { return kind == TSD_MODEL_IP_ADAPTER_SD15; }
+// IP-Adapter Plus (kind 24): the same 16 pairs behind a Perceiver resampler - 16 learned queries read the CLIP vision encoder's
+// hidden_states[-2] ([S][1280], S = 257 in use) through 4 layers of cross attention (12 heads of 64) and a 768 -> 3072 -> 768
+// feed-forward (graph.cpp g_ip_resample); the UNet side is kind 20's at N = 16
+constexpr int IPP_TOKENS = 16, IPP_DEPTH = 4, IPP_HEADS = 12, IPP_DHEAD = 64, IPP_EMBED = 1280, IPP_FF = 3072, IPP_MAX_S = 1024;
+static inline bool is_ip_plus_kind(int kind) { return kind == TSD_MODEL_IP_ADAPTER_PLUS_SD15; }
+static inline bool is_ip_adapter_kind(int kind) { return kind == TSD_MODEL_IP_ADAPTER_SD15 || is_ip_plus_kind(kind); }
 // `ip_adapter.<index>` of the published files for the t-th cross-attention block of SD15_STEPS (6 down, 1 mid, 9 up): the files count
 // diffusers' attention processors - down blocks, then up blocks, then the mid block - and the cross-attention ones are the odd numbers
 static inline int ip_adapter_published_index(int t) { return t < 6 ? 2 * t + 1 : (t == 6 ? 31 : 2 * t - 1); }
 // CLIP vision encoder (kind 22): OpenCLIP ViT-H/14 as the `image_encoder/` folder of the IP-Adapter files holds it (graph.cpp g_clip_vision_forward)
 constexpr int CV_WIDTH = 1280, CV_HEADS = 16, CV_LAYERS = 32, CV_MLP = 5120, CV_TOKENS = 257, CV_EMBED = 1024;
 static inline bool is_clip_vision_kind(int kind) { return kind == TSD_MODEL_CLIP_VISION_H; }
-// 1 .. 11, 16, 17, 20 and 22; 12 .. 15, 18, 19, 21 and 23 are reserved and refused
+// 1 .. 11, 16, 17, 20, 22 and 24; 12 .. 15, 18, 19, 21 and 23 are reserved and refused
 static inline bool is_model_kind(int kind) {
   return (kind >= TSD_MODEL_DIFFUSION && kind <= TSD_MODEL_CONTROLNET_SD15_TORCH) || kind == TSD_MODEL_DIFFUSION_SD2 || kind == TSD_MODEL_CLIP_SD2 ||
-         kind == TSD_MODEL_IP_ADAPTER_SD15 || kind == TSD_MODEL_CLIP_VISION_H;
+         is_ip_adapter_kind(kind) || kind == TSD_MODEL_CLIP_VISION_H;
 }
 
 std::vector<ParamSpec> build_param_specs(int model_kind);
@@ -160,10 +168,16 @@ struct ClipW {
   NormAffine final_ln;  // torch-norm extension (kind 7)
 };
 
-struct IpAdapterW {  // kind 20
-  int n_tokens = IP_SD15_TOKENS;
-  LinW proj;        // image_proj.proj: [n_tokens * 768][1024], with bias
-  NormAffine norm;  // image_proj.norm: LayerNorm(768) weight / bias, torch semantics
+struct IpResampleLayerW { NormAffine norm1, norm2, ff_norm; LinW to_q, to_kv, to_out, ff1, ff2; };  // no biases
+struct IpAdapterW {  // kinds 20 / 24
+  int n_tokens = IP_SD15_TOKENS;  // 4; 16 for kind 24
+  LinW proj;        // image_proj.proj: [n_tokens * 768][1024], with bias (kind 20 only)
+  NormAffine norm;  // image_proj.norm: LayerNorm(768) weight / bias, torch semantics (kind 20 only)
+  // kind 24 only: the resampler.  latents [16][768] fp16, proj_in [768][1280] and proj_out [768][768] with bias, norm_out, four layers
+  const half_t* latents = nullptr;
+  LinW proj_in, proj_out;
+  NormAffine norm_out;
+  IpResampleLayerW layer[IPP_DEPTH];
   // to_k_ip / to_v_ip of the 16 blocks, contiguous in the blob in the step table's order ([12480][768] each, as kproj_all / vproj_all):
   // they live in tsd_model::unet.kproj_all / vproj_all so that g_unet_ctx_kv projects the image tokens exactly as it projects a context
   int n_blocks = 0;

@@ -219,8 +219,29 @@ std::vector<ParamSpec> build_param_specs(int kind) {
         }
       }
   } else if (is_ip_adapter_kind(kind)) {  // the published IP-Adapter files' names; the 16 pairs in the step table's order
-    b.lin("image_proj.proj", IP_EMBED_DIM, IP_SD15_TOKENS * IP_CTX_DIM);
-    b.norm("image_proj.norm", IP_CTX_DIM);
+    if (is_ip_plus_kind(kind)) {  // the Resampler's state-dict order
+      ParamSpec q;  // the learned queries [1][16][768], kept as fp16 rows: the first layer's residual stream
+      q.name = "image_proj.latents"; q.ndim = 3; q.shape[0] = 1; q.shape[1] = IPP_TOKENS; q.shape[2] = IP_CTX_DIM; q.kind = P_LIN_W;
+      q.bound = (float)(1.0 / sqrt((double)IP_CTX_DIM)); q.Kpad = IP_CTX_DIM; q.Opad = IPP_TOKENS;
+      b.out.push_back(q);
+      b.lin("image_proj.proj_in", IPP_EMBED, IP_CTX_DIM);
+      b.lin("image_proj.proj_out", IP_CTX_DIM, IP_CTX_DIM);
+      b.norm("image_proj.norm_out", IP_CTX_DIM);
+      for (int l = 0; l < IPP_DEPTH; l++) {
+        const std::string n = "image_proj.layers." + std::to_string(l);
+        b.norm(n + ".0.norm1", IP_CTX_DIM);
+        b.norm(n + ".0.norm2", IP_CTX_DIM);
+        b.linw(n + ".0.to_q", IP_CTX_DIM, IPP_HEADS * IPP_DHEAD, 0);
+        b.linw(n + ".0.to_kv", IP_CTX_DIM, 2 * IPP_HEADS * IPP_DHEAD, 0);
+        b.linw(n + ".0.to_out", IPP_HEADS * IPP_DHEAD, IP_CTX_DIM, 0);
+        b.norm(n + ".1.0", IP_CTX_DIM);
+        b.linw(n + ".1.1", IP_CTX_DIM, IPP_FF, 0);
+        b.linw(n + ".1.3", IPP_FF, IP_CTX_DIM, 0);
+      }
+    } else {
+      b.lin("image_proj.proj", IP_EMBED_DIM, IP_SD15_TOKENS * IP_CTX_DIM);
+      b.norm("image_proj.norm", IP_CTX_DIM);
+    }
     for (int i = 0, t = 0; i < SD15_N; i++) {
       const LayerDef& l = SD15_STEPS[i].l;
       if (l.kind != L_ATTN) continue;

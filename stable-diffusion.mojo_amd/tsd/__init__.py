@@ -28,7 +28,7 @@ from .attention import Cross_Attention, Self_Attention  # noqa: F401
 from .diffusion import (ControlNet, Diffusion, IPAdapter, Time_Embedding, UNet, UNet_Output_Layer, Unet_Attention_Block,  # noqa: F401
                         Unet_Residual_Block)
 from .vae import Attention_Block, Decoder, Encoder, Res_Block  # noqa: F401
-from .clip import CLIP, CLIPVision, clip_image_patches  # noqa: F401
+from .clip import CLIP, CLIPVision, clip_image_patches, clip_neutral_image  # noqa: F401
 from .tokenizer import Tokenizer, process_prompt  # noqa: F401
 from .sampler import DDIMSampler, DDPMSampler, DPMSolverMultistepSampler  # noqa: F401
 from .pipeline import encode_prompts, generate  # noqa: F401

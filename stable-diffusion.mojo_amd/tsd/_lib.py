@@ -26,6 +26,7 @@ MODEL_CONTROLNET_SD15, MODEL_CONTROLNET_SD15_TORCH = 10, 11
 MODEL_DIFFUSION_SD2, MODEL_CLIP_SD2 = 16, 17    # 12 - 15 are reserved and refused
 MODEL_IP_ADAPTER_SD15 = 20                      # 18 and 19 are refused as well
 MODEL_CLIP_VISION_H = 22                        # ... and so are 21 and 23
+MODEL_IP_ADAPTER_PLUS_SD15 = 24
 SAMPLER_KINDS = {"ddpm": 0, "ddim": 1, "dpmpp_2m": 2}      # tsd_sampler_kind
 TIMESTEP_SPACINGS = {"leading": 0, "trailing": 1}          # tsd_timestep_spacing
 MASK_MODES = {"area": 0, "any": 1}                         # tsd_mask_mode
@@ -145,7 +146,7 @@ def _declare(l):
         "tsd_debug_set_control_stats": ([vp, i], i),
         "tsd_controlnet_hint_hw": ([vp, fp, i, i, i, fp], i),
         "tsd_session_set_control": ([vp, vp, fp, f, i, i, i], i), "tsd_session_control_active": ([vp], i),
-        "tsd_ip_adapter_project": ([vp, fp, i, fp], i),
+        "tsd_ip_adapter_project": ([vp, fp, i, fp], i), "tsd_ip_adapter_resample": ([vp, fp, i, i, fp], i),
         "tsd_diffusion_forward_ip_hw": ([vp, vp, fp, i, fp, vp, fp, fp, fp, fp, fp, i, i, i, i, fp], i),
         "tsd_ip_attn_add_f16": ([vp, vp, vp, vp, vp, fp, i, i, i, i, i, f, vp], i),
         "tsd_session_set_ip_adapter": ([vp, vp, fp, fp, i, f, i, i], i), "tsd_session_ip_adapter_active": ([vp], i),

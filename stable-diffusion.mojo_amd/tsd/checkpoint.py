@@ -324,17 +324,91 @@ def params_to_ip_adapter(params, prefix=""):
 
 def load_ip_adapter(path_or_state, ctx=None, prefix=""):
     """tsd.IPAdapter with the weights of a published SD-1.5 IP-Adapter file (ip-adapter_sd15: 4 image tokens from the 1024-wide CLIP image
-    embedding): a safetensors file, or its state dict.  The "plus" files (a resampler instead of image_proj.proj) are not supported."""
+    embedding): a safetensors file, or its state dict.  The "plus" files (a resampler instead of image_proj.proj) are another model
+    kind: `load_ip_adapter_plus` reads them."""
     from .diffusion import IPAdapter
     from .model import param_specs
     state = read_safetensors(path_or_state) if isinstance(path_or_state, str) else path_or_state
     if prefix + "image_proj.proj.weight" not in state:
-        raise KeyError("checkpoint has no image_proj.proj.weight: not an ip-adapter_sd15 file (the 'plus' files carry a resampler, which is not supported)")
+        raise KeyError("checkpoint has no image_proj.proj.weight: not an ip-adapter_sd15 file (the 'plus' files carry a resampler: "
+                       "load_ip_adapter_plus reads those)")
     params = ip_adapter_to_params(state, prefix)
     for name, shape, _, _ in param_specs("ip_adapter_sd15"):
         if tuple(np.shape(params[name])) != tuple(shape):
             raise ValueError(f"{name}: checkpoint shape {np.shape(params[name])}, model expects {shape}")
     return IPAdapter(ctx=ctx, params=params)
+
+
+# ---- IP-Adapter Plus (the published ip-adapter-plus_sd15 / ip-adapter-plus-face_sd15 safetensors -> kind "ip_adapter_plus_sd15") ----------
+IP_ADAPTER_PLUS_DEPTH = 4
+
+
+def ip_adapter_plus_names():
+    """The 83 tensor names of a plus file, in the resampler's state-dict order and then the 16 pairs in the PUBLISHED order (1, 3, .., 31)."""
+    names = ["image_proj.latents", "image_proj.proj_in.weight", "image_proj.proj_in.bias", "image_proj.proj_out.weight",
+             "image_proj.proj_out.bias", "image_proj.norm_out.weight", "image_proj.norm_out.bias"]
+    for l in range(IP_ADAPTER_PLUS_DEPTH):
+        n = f"image_proj.layers.{l}."
+        names += [n + t for t in ("0.norm1.weight", "0.norm1.bias", "0.norm2.weight", "0.norm2.bias", "0.to_q.weight", "0.to_kv.weight",
+                                  "0.to_out.weight", "1.0.weight", "1.0.bias", "1.1.weight", "1.3.weight")]
+    return names + [f"ip_adapter.{2 * k + 1}.{f}.weight" for k in range(16) for f in ("to_k_ip", "to_v_ip")]
+
+
+def ip_adapter_plus_to_params(state, prefix=""):
+    """Published IP-Adapter Plus state dict -> {our parameter name: array} for kind "ip_adapter_plus_sd15".
+
+    The model keeps the published names, so the map is the identity on 83 tensors; what this function does is refuse.  `image_proj` is
+    `Resampler(dim=768, depth=4, dim_head=64, heads=12, num_queries=16, embedding_dim=1280, output_dim=768, ff_mult=4)` of the published
+    IP-Adapter code: `latents` [1][16][768], `proj_in` 1280 -> 768 and `proj_out` 768 -> 768 with bias, `norm_out`, and per layer L
+    `layers.L.0` = PerceiverAttention (norm1 for the image rows, norm2 for the latents, bias-free to_q [768][768], to_kv [1536][768] with
+    the K half first, to_out [768][768]) and `layers.L.1` = Sequential(LayerNorm, Linear(768, 3072), GELU, Linear(3072, 768)), both linears
+    bias-free, hence the indices 0, 1, 3.  These names, shapes and the module's arithmetic (tests/ipplus_ref.py restates it) are written
+    FROM MEMORY of that module, not checked against a real file or the published code here: a file that lacks one of the 83 names is
+    refused by name (KeyError), one whose `latents` are not [1][16][768] or whose `proj_in` is not [768][1280] with the shape named
+    (ValueError; those are the full-face, SDXL and ViT-L files), and the 16 pairs pass `ip_adapter_to_params`'s width-order check."""
+    missing = [n for n in ip_adapter_plus_names() if prefix + n not in state]
+    if missing:
+        if prefix + "image_proj.latents" not in state and prefix + "image_proj.proj.weight" in state:
+            raise KeyError(f"checkpoint has no tensor {prefix}image_proj.latents but an image_proj.proj.weight: an ip-adapter_sd15 file, "
+                           "load_ip_adapter reads it")
+        raise KeyError(f"checkpoint has no tensor {prefix + missing[0]}" + (f" (and {len(missing) - 1} more)" if len(missing) > 1 else ""))
+    out = {n: np.asarray(state[prefix + n], dtype=np.float32) for n in ip_adapter_plus_names()}
+    if out["image_proj.latents"].shape != (1, 16, 768):
+        raise ValueError(f"image_proj.latents has shape {out['image_proj.latents'].shape}, the model expects (1, 16, 768): not an "
+                         "ip-adapter-plus_sd15 file (another query count or width: the SDXL and full-face files)")
+    if out["image_proj.proj_in.weight"].shape != (768, 1280):
+        raise ValueError(f"image_proj.proj_in.weight has shape {out['image_proj.proj_in.weight'].shape}, the model expects (768, 1280): "
+                         "the resampler of this file does not read the ViT-H/14 hidden states (the ViT-L and SDXL files)")
+    widths = []
+    for k in range(16):
+        wk, wv = out[f"ip_adapter.{2 * k + 1}.to_k_ip.weight"].shape, out[f"ip_adapter.{2 * k + 1}.to_v_ip.weight"].shape
+        if wk != wv or len(wk) != 2:
+            raise ValueError(f"ip_adapter.{2 * k + 1}: to_k_ip {wk} and to_v_ip {wv} differ in shape")
+        widths.append(int(wk[0]))
+    if tuple(widths) != IP_ADAPTER_PUBLISHED_WIDTHS:
+        raise ValueError(f"the 16 cross-attention widths of this file are {widths}; the key map assumes {list(IP_ADAPTER_PUBLISHED_WIDTHS)} "
+                         "(down blocks, up blocks, mid block): see ip_adapter_to_params")
+    return out
+
+
+def params_to_ip_adapter_plus(params, prefix=""):
+    """Inverse of `ip_adapter_plus_to_params` (export; used by the round-trip test): the published names, the pairs in the published order."""
+    return {prefix + n: np.asarray(params[n], np.float32) for n in ip_adapter_plus_names()}
+
+
+def load_ip_adapter_plus(path_or_state, ctx=None, prefix=""):
+    """tsd.IPAdapter(variant="ip_adapter_plus_sd15") with the weights of a published SD-1.5 IP-Adapter Plus file (ip-adapter-plus_sd15,
+    ip-adapter-plus-face_sd15: 16 image tokens resampled from the ViT-H/14 hidden states): a safetensors file, or its state dict.  The
+    layout is stated from memory of the published module, not checked against a real file here (`ip_adapter_plus_to_params`); every
+    tensor's shape is checked against the model's inventory before anything is uploaded."""
+    from .diffusion import IPAdapter
+    from .model import param_specs
+    state = read_safetensors(path_or_state) if isinstance(path_or_state, str) else path_or_state
+    params = ip_adapter_plus_to_params(state, prefix)
+    for name, shape, _, _ in param_specs("ip_adapter_plus_sd15"):
+        if tuple(np.shape(params[name])) != tuple(shape):
+            raise ValueError(f"{name}: checkpoint shape {np.shape(params[name])}, model expects {shape}")
+    return IPAdapter(ctx=ctx, params=params, variant="ip_adapter_plus_sd15")
 
 
 # ---- CLIP vision encoder (HF CLIPVisionModelWithProjection, the `image_encoder/` folder of the IP-Adapter files -> kind "clip_vision_h") ----

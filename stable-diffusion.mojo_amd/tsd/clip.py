@@ -59,6 +59,23 @@ def clip_image_patches(images, ctx=None):
     return out[0] if single else out
 
 
+CLIP_IMAGE_MEAN = (0.48145466, 0.4578275, 0.40821073)
+
+
+def clip_neutral_image():
+    """The image the vision encoder's front end normalises to zero: (3, 224, 224) float32, channel c constant at 255 * mean_c.
+
+    The published IP-Adapter Plus pipelines compute the unconditional image tokens from `zeros_like(normalised pixels)`; in this
+    package's pixel convention (0 .. 255 in, normalisation inside the encoder) that input is this image.  At 224 x 224 the front end
+    resamples nothing, and its single fma (v / (255 std_c) - mean_c / std_c on fp32 constants, rounded once to fp16) leaves a few fp16
+    subnormals where the published code has exact zeros: the red channel comes out as -2 subnormal units (-1.2e-7), green and blue as
+    zero; in exact arithmetic the image is within one unit (6e-8) of zero everywhere."""
+    img = np.empty((3, 224, 224), dtype=np.float32)
+    for c, m in enumerate(CLIP_IMAGE_MEAN):
+        img[c] = np.float32(255.0 * m)
+    return img
+
+
 class CLIPVision:
     """The CLIP vision encoder the published `ip-adapter_sd15` files were trained against (no reference counterpart): OpenCLIP ViT-H/14 as
     Hugging Face ships it in the `image_encoder/` folder of h94/IP-Adapter - 14x14 patches of a 224x224 crop, 257 tokens of width 1280,

@@ -223,23 +223,53 @@ class IPAdapter:
     project(image_embeds) -> the N = 4 image tokens; `Diffusion.forward(ip_adapter=, ip_tokens=, ip_scale=)`, `Session.set_ip_adapter`
     and `generate(ip_adapter=, ip_image_embeds=)` consume them.  The 1024-wide image embedding (diffusers' `ip_adapter_image_embeds`)
     comes from the CLIP vision encoder, `tsd.CLIPVision.forward(image)`, or from the caller; `generate(ip_adapter=, ip_image=,
-    image_encoder=)` runs the encoder itself.  See tsd.checkpoint.load_ip_adapter / load_clip_vision."""
-    N_TOKENS = 4
+    image_encoder=)` runs the encoder itself.  See tsd.checkpoint.load_ip_adapter / load_clip_vision.
 
-    def __init__(self, seed=0, ctx=None, params=None):
-        self.model = Model("ip_adapter_sd15", ctx=ctx, seed=None if params is not None else seed)
+    variant "ip_adapter_plus_sd15": the layout of the published ip-adapter-plus_sd15 / ip-adapter-plus-face_sd15 files - the same 16
+    pairs behind a Perceiver resampler (4 layers, 16 learned queries, 12 heads of 64) in place of the linear projection.
+    resample(hidden) -> the N = 16 image tokens from the vision encoder's hidden states, `CLIPVision.forward(image, hidden=True)[1]`;
+    everything that consumes tokens takes them unchanged, and `generate(ip_adapter=, ip_image=, image_encoder=)` or
+    `generate(ip_adapter=, ip_hidden=)` runs the resampler itself.  See tsd.checkpoint.load_ip_adapter_plus."""
+    N_TOKENS = 4
+    VARIANTS = {"ip_adapter_sd15": 4, "ip_adapter_plus_sd15": 16}
+
+    def __init__(self, seed=0, ctx=None, params=None, variant="ip_adapter_sd15"):
+        if variant not in self.VARIANTS:
+            raise ValueError(f"IPAdapter: unknown variant {variant!r} ({', '.join(self.VARIANTS)})")
+        self.variant = variant
+        self.n_tokens = self.VARIANTS[variant]
+        self.model = Model(variant, ctx=ctx, seed=None if params is not None else seed)
         if params is not None:
             self.model.load_params(params)
 
+    @property
+    def is_plus(self):
+        return self.variant == "ip_adapter_plus_sd15"
+
     def project(self, image_embeds):
-        """(1024,) or (B, 1024) image embeddings -> tokens (4, 768) / (B, 4, 768) = LayerNorm(Linear(e)) (`tsd_ip_adapter_project`)."""
+        """(1024,) or (B, 1024) image embeddings -> tokens (4, 768) / (B, 4, 768) = LayerNorm(Linear(e)) (`tsd_ip_adapter_project`).
+        A plus adapter has no such projection: TsdError with the library's message, which names `resample`'s entry."""
         e = f32(image_embeds)
         single = e.ndim == 1
         eb = f32(e[None] if single else e)
         if eb.ndim != 2 or eb.shape[1] != 1024:
             raise ValueError(f"image_embeds must have shape (1024,) or (B, 1024), got {e.shape}")
-        out = np.empty((eb.shape[0], self.N_TOKENS, 768), dtype=np.float32)
+        out = np.empty((eb.shape[0], self.n_tokens, 768), dtype=np.float32)
         if check(lib().tsd_ip_adapter_project(self.model.h, ptr(eb), eb.shape[0], ptr(out)), True):
+            return NULL_MATRIX()
+        return out[0] if single else out
+
+    def resample(self, hidden):
+        """Plus adapters: (S, 1280) or (B, S, 1280) hidden states of the CLIP vision encoder (its `hidden_states[-2]`: S = 257; any
+        1 <= S <= 1024), B <= 16 -> tokens (16, 768) / (B, 16, 768), the Perceiver resampler (`tsd_ip_adapter_resample`); every value is
+        exactly an fp16.  An adapter of the plain kind has no resampler: TsdError with the library's message."""
+        h = f32(hidden)
+        single = h.ndim == 2
+        hb = f32(h[None] if single else h)
+        if hb.ndim != 3 or hb.shape[2] != 1280:
+            raise ValueError(f"hidden must have shape (S, 1280) or (B, S, 1280), got {h.shape}")
+        out = np.empty((hb.shape[0], 16, 768), dtype=np.float32)
+        if check(lib().tsd_ip_adapter_resample(self.model.h, ptr(hb), hb.shape[0], hb.shape[1], ptr(out)), True):
             return NULL_MATRIX()
         return out[0] if single else out
 

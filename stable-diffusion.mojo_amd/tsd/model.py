@@ -12,6 +12,7 @@ KINDS = {"diffusion": _lib.MODEL_DIFFUSION, "decoder": _lib.MODEL_DECODER, "enco
          "decoder_torch": _lib.MODEL_DECODER_TORCH, "encoder_torch": _lib.MODEL_ENCODER_TORCH,
          "controlnet_sd15": _lib.MODEL_CONTROLNET_SD15, "controlnet_sd15_torch": _lib.MODEL_CONTROLNET_SD15_TORCH,
          "ip_adapter_sd15": _lib.MODEL_IP_ADAPTER_SD15, "clip_vision_h": _lib.MODEL_CLIP_VISION_H,
+         "ip_adapter_plus_sd15": _lib.MODEL_IP_ADAPTER_PLUS_SD15,
          "diffusion_sd2": _lib.MODEL_DIFFUSION_SD2, "clip_sd2": _lib.MODEL_CLIP_SD2}
 
 

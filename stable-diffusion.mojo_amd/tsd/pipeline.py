@@ -28,7 +28,8 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
              num_training_steps=1000, L=64, return_latents=False, sampler="ddpm", eta=0.0, spacing="leading", mask=None,
              mask_mode="any", seeds=None, guidance_rescale=0.0, prediction="epsilon", zero_terminal_snr=False, controlnet=None,
              control_image=None, control_scale=1.0, control_cond_only=False, control_start=0.0, control_end=1.0, ip_adapter=None,
-             ip_image_embeds=None, ip_scale=1.0, ip_start=0.0, ip_end=1.0, ip_image=None, image_encoder=None):
+             ip_image_embeds=None, ip_scale=1.0, ip_start=0.0, ip_end=1.0, ip_image=None, image_encoder=None, ip_hidden=None,
+             ip_uncond_hidden=None):
     """context (B,T,768); returns images (B,3,8LH,8LW) in [0,255] like pipeline.mojo:127.  L is the latent side (64: 512x512) or a pair
     (LH, LW) for a rectangular image ((96, 64): 512 wide, 768 high); where the text below says L,L the tensor is LH,LW.
 
@@ -67,18 +68,48 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
     those embeddings (`checkpoint.load_clip_vision` reads the `image_encoder/` folder the adapter files come with).
     Every step whose index lies in [ip_start, ip_end] as fractions of the step list adds the attention over the projected image tokens,
     scaled by ip_scale, in every cross-attention block.  With cfg the unconditional half reads the projection of a zero embedding, as
-    diffusers does (`Session.set_ip_adapter`)."""
+    diffusers does (`Session.set_ip_adapter`).
+
+    A plus adapter (`tsd.IPAdapter(variant="ip_adapter_plus_sd15")`, `checkpoint.load_ip_adapter_plus`) reads the vision encoder's
+    hidden states instead of the embedding: ip_image + image_encoder runs `image_encoder.forward(ip_image, hidden=True)` and
+    `ip_adapter.resample` on the result; ip_hidden (S,1280) or (B,S,1280) is for callers who hold the hidden states (S = 257 from
+    `CLIPVision`).  ip_image_embeds with a plus adapter and ip_hidden with a plain one are refused.  With cfg the unconditional half
+    reads, as the published plus pipelines do, the resampled hidden states of the image that normalises to zero
+    (`tsd.clip_neutral_image()`, a 224x224 constant the front end does not resample; its single fma leaves a few fp16 subnormals where
+    the published code has exact zeros): computed here when image_encoder is given, or passed as ip_uncond_hidden, same shapes as
+    ip_hidden."""
+    plus = bool(getattr(ip_adapter, "is_plus", False))
+    if ip_hidden is not None and (ip_image is not None or ip_image_embeds is not None):
+        raise ValueError("generate: pass one of ip_image, ip_image_embeds and ip_hidden, not both")
     if ip_image is not None and ip_image_embeds is not None:
         raise ValueError("generate: pass ip_image or ip_image_embeds, not both")
+    if ip_uncond_hidden is not None and ip_hidden is None:
+        raise ValueError("generate: ip_uncond_hidden goes with ip_hidden (with ip_image the unconditional hidden states are computed here)")
+    if ip_hidden is not None:
+        if ip_adapter is None:
+            raise ValueError("generate: ip_hidden is the input of an IP-Adapter Plus: pass ip_adapter= as well")
+        if not plus:
+            raise ValueError("generate: ip_hidden is what a plus adapter reads (variant \"ip_adapter_plus_sd15\"); this ip_adapter reads "
+                             "the 1024-wide image embedding: pass ip_image_embeds, or ip_image with image_encoder")
+        if np.ndim(ip_hidden) not in (2, 3) or np.shape(ip_hidden)[-1] != 1280:
+            raise ValueError(f"generate: ip_hidden must have shape (S, 1280) or (B, S, 1280), got {np.shape(ip_hidden)}")
+        if cfg and ip_uncond_hidden is None and image_encoder is None:
+            raise ValueError("generate: ip_hidden under cfg needs the unconditional half's hidden states: pass ip_uncond_hidden "
+                             "(image_encoder.forward(tsd.clip_neutral_image(), hidden=True)[1]) or image_encoder")
+    if plus and ip_image_embeds is not None:
+        raise ValueError("generate: a plus adapter reads the vision encoder's hidden states, (S, 1280) per image, not the 1024-wide image "
+                         "embedding: pass ip_hidden, or ip_image with image_encoder")
     if ip_image is not None and image_encoder is None:
         raise ValueError("generate: ip_image needs image_encoder (a tsd.CLIPVision) to turn the pixels into the image embedding")
-    if (ip_adapter is None) != (ip_image_embeds is None and ip_image is None):
-        raise ValueError("generate: ip_adapter goes together with ip_image_embeds or ip_image")
+    if (ip_adapter is None) != (ip_image_embeds is None and ip_image is None and ip_hidden is None):
+        raise ValueError("generate: ip_adapter goes together with ip_image_embeds, ip_image or ip_hidden")
     if ip_image is not None:
         if np.ndim(ip_image) not in (3, 4) or np.shape(ip_image)[-3] != 3:
             raise ValueError(f"generate: ip_image must have shape (3, H, W) or (B, 3, H, W), got {np.shape(ip_image)}")
         if getattr(image_encoder.model, "ctx", None) is not diffusion.model.ctx:
             raise ValueError("generate: image_encoder and the diffusion model belong to different contexts")
+    elif ip_hidden is not None and cfg and ip_uncond_hidden is None and getattr(image_encoder.model, "ctx", None) is not diffusion.model.ctx:
+        raise ValueError("generate: image_encoder and the diffusion model belong to different contexts")
     if ip_adapter is not None and not (0.0 <= ip_start <= ip_end <= 1.0):
         raise ValueError(f"generate: ip_start / ip_end must satisfy 0 <= start <= end <= 1, got {ip_start}, {ip_end}")
     if (controlnet is None) != (control_image is None):
@@ -147,7 +178,21 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
     if ip_adapter is not None:
         first = int(np.ceil(ip_start * n - 1e-9))
         last = int(np.floor(ip_end * n + 1e-9)) - 1
-        if last >= first:
+        if last >= first and plus:
+            def hidden_rows(h, what):
+                h = np.asarray(h, dtype=np.float32)
+                h = np.repeat(h[None], B, axis=0) if h.ndim == 2 else h
+                if h.ndim != 3 or h.shape[0] != B or h.shape[2] != 1280:
+                    raise ValueError(f"generate: {what} must have shape (S, 1280) or ({B}, S, 1280), got {h.shape}")
+                return h
+            h = hidden_rows(image_encoder.forward(ip_image, hidden=True)[1] if ip_image is not None else ip_hidden, "the hidden states")
+            hu = None
+            if cfg:  # the published pipelines' resample(hidden(encoder(zeros_like(normalised pixels))))
+                from .clip import clip_neutral_image
+                hu = hidden_rows(ip_uncond_hidden if ip_uncond_hidden is not None else image_encoder.forward(clip_neutral_image(), hidden=True)[1],
+                                 "ip_uncond_hidden")
+            sess.set_ip_adapter(ip_adapter, ip_adapter.resample(h), ip_adapter.resample(hu) if cfg else None, ip_scale, first, last)
+        elif last >= first:
             e = np.asarray(image_encoder.forward(ip_image) if ip_image is not None else ip_image_embeds, dtype=np.float32)
             e = np.repeat(e[None], B, axis=0) if e.ndim == 1 else e
             if e.shape != (B, 1024):

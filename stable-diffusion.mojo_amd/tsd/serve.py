@@ -155,7 +155,7 @@ def generate_stream(diffusion, decoder, requests, B, L, T=77, cfg=True, inferenc
     Finished latents are decoded through `decoder.forward`, one image per call.  `stats`, a dict, receives advances / active_ticks / occupancy when the stream ends.
     controlnet / control_image (and generate's other control_* keywords) are refused: the stream runs on a slot session, and per-slot
     control is not supported (`generate` runs lockstep sessions and takes them).  generate's ip_adapter / ip_image_embeds / ip_scale /
-    ip_start / ip_end are refused for the same reason: per-slot adapters are not supported."""
+    ip_start / ip_end / ip_image / ip_hidden / ip_uncond_hidden are refused for the same reason: per-slot adapters are not supported."""
     if any(k.startswith("ip_") for k in control_keywords):
         raise ValueError("generate_stream runs on a slot session, which has no IP-Adapter (per-slot adapters are not supported); use generate()")
     if controlnet is not None or control_image is not None or control_keywords:
