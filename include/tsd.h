@@ -760,6 +760,14 @@ int tsd_debug_xcd_round_robin(void);
  * entry points, tsd_ctx_synchronize and the session downloads return TSD_E_NONFINITE when the count is non-zero (and clear it).
  * This call reads the count without failing (reset != 0 clears it); < 0 on error.  Synchronises the context's stream. */
 int tsd_debug_nonfinite_count(tsd_ctx* ctx, int reset);
+/* Test infrastructure: fill the context's whole workspace arena and whole staging buffer, as allocated now, with `byte` (0..255), on the
+ * context's stream; a region that is not allocated yet is skipped.  Both are per-call scratch (DESIGN.md "Workspace rule"): no result
+ * of any later call may depend on the byte.  Nothing else is touched - not the split-K hand-off flags, not the status words, not a
+ * table, a model or a session.  TSD_E_ARG for a NULL context or a byte outside 0..255.  Does not synchronise.
+ * TSD_DEBUG_POISON=<byte> in the environment of tsd_ctx_create is the same statement about FRESH allocations: those selected by
+ * TSD_DEBUG_POISON_WHAT (default 31: 1 arena, 2 derived weights, 4 session state, 8 every buffer a session allocates or grows
+ * later - context K/V, noise, time table and rows, control, IP-Adapter K/V - 16 staging) are filled with the byte when allocated. */
+int tsd_debug_scribble(tsd_ctx* ctx, int byte);
 /* Test infrastructure: the session's raw latent buffer [B,4,L,L] as it is on the device - in any mode, idle slots included, with no
  * finite check and no effect on the session's state.  Synchronises. */
 int tsd_debug_session_latents(tsd_session* s, float* latents);

@@ -159,6 +159,17 @@ extern "C" int tsd_debug_nonfinite_count(tsd_ctx* c, int reset) {
   return n;
 }
 
+// Overwrite the per-call scratch of the context with `byte`: the whole arena and the whole staging buffer, as they are now, on the
+// context's stream.  Nothing else - not sk_flags (a hand-off in flight keeps its flags), not status, not zeros, no table, model or session.
+extern "C" int tsd_debug_scribble(tsd_ctx* c, int byte) {
+  if (!c) TSD_FAIL(TSD_E_ARG, "tsd_debug_scribble: ctx is NULL");
+  if (byte < 0 || byte > 255) TSD_FAIL(TSD_E_ARG, "tsd_debug_scribble: byte %d is outside 0..255", byte);
+  HIP_TRY(hipSetDevice(c->device));
+  if (c->arena.base && c->arena.cap) HIP_TRY(hipMemsetAsync(c->arena.base, byte, c->arena.cap, c->stream));
+  if (c->staging && c->staging_cap) HIP_TRY(hipMemsetAsync(c->staging, byte, c->staging_cap, c->stream));
+  return TSD_OK;
+}
+
 extern "C" int tsd_ctx_synchronize(tsd_ctx* c) {
   if (!c) TSD_FAIL(TSD_E_ARG, "tsd_ctx_synchronize: ctx is NULL");
   HIP_TRY(hipSetDevice(c->device));
@@ -239,5 +250,6 @@ int ctx_reserve_staging(tsd_ctx* c, size_t bytes) {
   hipError_t e = hipMalloc(&c->staging, bytes);
   if (e != hipSuccess) TSD_FAIL(TSD_E_ALLOC, "staging: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
   c->staging_cap = bytes;
+  if (c->opt.debug_poison >= 0 && (c->opt.debug_poison_what & 16)) HIP_TRY(hipMemsetAsync(c->staging, c->opt.debug_poison & 255, bytes, c->stream));
   return TSD_OK;
 }

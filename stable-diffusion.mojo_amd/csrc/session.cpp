@@ -172,12 +172,13 @@ static void session_latents_changed(tsd_session* s) {
   s->decoded = false;
 }
 // One of the session's own growable device buffers holds `bytes`: kept while large enough, else replaced (the contents are lost).
-static int session_grow(void** ptr, size_t* cap, size_t bytes, const char* what) {
+static int session_grow(tsd_ctx* ctx, void** ptr, size_t* cap, size_t bytes, const char* what) {
   if (bytes <= *cap) return TSD_OK;
   if (*ptr) HIP_TRY(hipFree(*ptr));
   *ptr = nullptr; *cap = 0;
   if (hipMalloc(ptr, bytes) != hipSuccess) TSD_FAIL(TSD_E_ALLOC, "session: %s hipMalloc(%zu) failed", what, bytes);
   *cap = bytes;
+  if (ctx->opt.debug_poison >= 0 && (ctx->opt.debug_poison_what & 8)) HIP_TRY(hipMemsetAsync(*ptr, ctx->opt.debug_poison & 255, bytes, ctx->stream));
   return TSD_OK;
 }
 // `samples` host contexts [T][W] fp32 -> rows first .. first + samples of ctx16, fp16 [Tp][W] with ZERO pad rows: the conversion the
@@ -471,9 +472,9 @@ static int session_control_prepare(tsd_session* s) {
   if (s->hoist) {
     const int CK = s->cn->unet.kproj_all.N, N = s->cn->unet.tproj.N;
     const size_t kc_bytes = ((size_t)Bu * Tp * CK * 2 + 255) & ~size_t(255);
-    TSD_TRY(session_grow((void**)&s->cn_kv, &s->cn_kv_cap, 2 * kc_bytes, "ControlNet context K/V"));
+    TSD_TRY(session_grow(ctx, (void**)&s->cn_kv, &s->cn_kv_cap, 2 * kc_bytes, "ControlNet context K/V"));
     s->cn_kc = (half_t*)s->cn_kv; s->cn_vtc = (half_t*)(s->cn_kv + kc_bytes);
-    TSD_TRY(session_grow((void**)&s->cn_ttab, &s->cn_ttab_cap, s->timesteps.size() * (size_t)N * 4, "ControlNet time table"));
+    TSD_TRY(session_grow(ctx, (void**)&s->cn_ttab, &s->cn_ttab_cap, s->timesteps.size() * (size_t)N * 4, "ControlNet time table"));
   }
   Arena& a = ctx->arena;
   a.planning = true; a.top = 0; a.peak = 0;
@@ -518,9 +519,9 @@ static int session_prepare(tsd_session* s) {
   if (s->hoist) {  // the buffers of session_build_invariants; sizes depend on the session's shape and the schedule's length only
     const int CK = s->unet->unet.kproj_all.N, N = s->unet->unet.tproj.N;
     const size_t kc_bytes = ((size_t)Bu * Tp * CK * 2 + 255) & ~size_t(255);
-    TSD_TRY(session_grow((void**)&s->kv, &s->kv_cap, 2 * kc_bytes, "context K/V"));
+    TSD_TRY(session_grow(ctx, (void**)&s->kv, &s->kv_cap, 2 * kc_bytes, "context K/V"));
     s->kc_all = (half_t*)s->kv; s->vtc_all = (half_t*)(s->kv + kc_bytes);
-    TSD_TRY(session_grow((void**)&s->ttab, &s->ttab_cap, s->timesteps.size() * (size_t)N * 4, "time table"));
+    TSD_TRY(session_grow(ctx, (void**)&s->ttab, &s->ttab_cap, s->timesteps.size() * (size_t)N * 4, "time table"));
   }
   a.planning = true; a.top = 0; a.peak = 0;
   const UNetPre pre0 = s->hoist ? session_pre(s, 0) : UNetPre();
@@ -567,7 +568,7 @@ extern "C" int tsd_session_upload(tsd_session* s, const float* latents, const fl
   s->has_noise = noise != nullptr;
   if (noise) {
     const size_t bytes = s->timesteps.size() * nl * 4;
-    TSD_TRY(session_grow((void**)&s->noise, &s->noise_cap, bytes, "noise"));
+    TSD_TRY(session_grow(ctx, (void**)&s->noise, &s->noise_cap, bytes, "noise"));
     HIP_TRY(hipMemcpyAsync(s->noise, noise, bytes, hipMemcpyHostToDevice, ctx->stream));
   }
   HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -723,7 +724,7 @@ extern "C" int tsd_session_set_control(tsd_session* s, tsd_model* cn, const floa
   const int B = s->B, Bu = s->Bu, LH = s->LH, LW = s->LW;
   const size_t hw = (size_t)LH * LW, nh = (size_t)B * 3 * 64 * hw, feat_bytes = (size_t)Bu * hw * 320 * 2;
   s->cn = nullptr;  // until everything below succeeded
-  TSD_TRY(session_grow((void**)&s->ctl, &s->ctl_cap, 256 + feat_bytes, "control"));
+  TSD_TRY(session_grow(ctx, (void**)&s->ctl, &s->ctl_cap, 256 + feat_bytes, "control"));
   s->ctl_scale = (float*)s->ctl; s->ctl_feat = (half_t*)(s->ctl + 256);
   float sc[16] = {};
   for (int b = 0; b < Bu; b++) sc[b] = (b >= B && cond_only) ? 0.f : scale;
@@ -776,7 +777,7 @@ extern "C" int tsd_session_set_ip_adapter(tsd_session* s, tsd_model* ip, const f
   const int IK = ip->unet.kproj_all.N;
   const size_t ntok = (size_t)B * N * IP_CTX_DIM, k_bytes = ((size_t)Bu * IP_MAX_TOKENS * IK * 2 + 255) & ~size_t(255);
   s->ip = nullptr;  // until everything below succeeded
-  TSD_TRY(session_grow((void**)&s->ipb, &s->ipb_cap, 256 + 2 * k_bytes, "IP-Adapter K/V"));
+  TSD_TRY(session_grow(ctx, (void**)&s->ipb, &s->ipb_cap, 256 + 2 * k_bytes, "IP-Adapter K/V"));
   s->ip_scale = (float*)s->ipb; s->ip_k = (half_t*)(s->ipb + 256); s->ip_vt = (half_t*)(s->ipb + 256 + k_bytes);
   float sc[16] = {};
   for (int b = 0; b < Bu; b++) sc[b] = scale;
@@ -1003,7 +1004,7 @@ extern "C" int tsd_session_slots_open(tsd_session* s) {
   HIP_TRY(hipMemsetAsync(s->ctx16, 0, (size_t)Bu * s->Tp * s->W * 2, ctx->stream));
   HIP_TRY(hipStreamSynchronize(ctx->stream));
   if (ctx->opt.session_hoist)  // the per-sample time rows of an advance: sized by the session's shape alone
-    TSD_TRY(session_grow((void**)&s->trows, &s->trows_cap, (size_t)Bu * s->unet->unet.tproj.N * 4, "time rows"));
+    TSD_TRY(session_grow(ctx, (void**)&s->trows, &s->trows_cap, (size_t)Bu * s->unet->unet.tproj.N * 4, "time rows"));
   // the planning pass and the hoist buffers of upload(), K / V^T of the zero context, the whole time table; every slot idle, no request
   TSD_TRY(session_prepare(s));
   s->uploaded = false;  // the lockstep entry points stay closed

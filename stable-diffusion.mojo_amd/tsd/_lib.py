@@ -199,6 +199,7 @@ def _declare(l):
         "tsd_debug_splitk_errors": ([vp], i),
         "tsd_debug_xcd_round_robin": ([], i),
         "tsd_debug_nonfinite_count": ([vp, i], i),
+        "tsd_debug_scribble": ([vp, i], i),
         "tsd_debug_set_fused_attention": ([vp, i], i),
         "tsd_debug_gemm_bench": ([vp, i, i, i, i, i, i, i, i, i, i, fp], i),
         "tsd_debug_attn_bench": ([vp, i, i, i, i, i, i, fp], i),
@@ -334,6 +335,11 @@ class Context:
             check(n)
         return [(self.KERNEL_CLASSES[rec[5 * i]], rec[5 * i + 1], rec[5 * i + 2], rec[5 * i + 3], rec[5 * i + 4], ms[i])
                 for i in range(n)]
+
+    def scribble(self, byte):
+        """Overwrite the whole workspace arena and the whole staging buffer with `byte` (tsd_debug_scribble; for tests: both are
+        per-call scratch, so no result may change)."""
+        check(lib().tsd_debug_scribble(self.h, int(byte)))
 
     def close(self):
         if self.h:
