@@ -734,6 +734,8 @@ int tsd_session_slots_active(tsd_session* s); /* number of active slots (0 outsi
 /* ---- multi-GPU: RCCL over xGMI (one process per GPU) ----------------------------------- */
 /* unique_id: 128 bytes from tsd_dist_unique_id on rank 0, shared out-of-band (e.g. torch.distributed). */
 int tsd_dist_unique_id(void* id128);
+/* A context holds at most one communicator: TSD_E_STATE, and nothing changes, on a context that already has one (tsd_dist_finalize
+ * first).  tsd_ctx_destroy finalizes a communicator that is still live. */
 int tsd_dist_init(tsd_ctx* ctx, int rank, int nranks, const void* id128);
 int tsd_dist_broadcast_weights(tsd_model* m, int root); /* ncclBroadcast of the packed blob */
 /* ranks of the communicator tsd_dist_init created (ncclCommCount): what RCCL itself holds, not what the caller passed in */
@@ -742,7 +744,8 @@ int tsd_dist_finalize(tsd_ctx* ctx);
 
 /* ---- debug / tuning -------------------------------------------------------------------- */
 /* Every switch below belongs to ONE context: the library keeps no process-global mutable state besides the thread-local error
- * string, so two contexts (one per GPU, each driven by its own host thread) may run different settings side by side.  The
+ * string and the ledger of device resources (tsd_debug_device_ledger below: counters behind a mutex that no call reads to decide
+ * anything), so two contexts (one per GPU, each driven by its own host thread) may run different settings side by side.  The
  * TSD_* environment variables named here are read once, by tsd_ctx_create, into that context.  A denoise session sizes its
  * workspace for the settings active at upload(): after a tsd_debug_set_* call that CHANGES a setting of its context, step() /
  * decode() fail with TSD_E_STATE until upload() is called again (setting the value that is already there changes nothing).
@@ -1086,6 +1089,19 @@ int tsd_debug_session_hoist_info(tsd_session* s, int64_t* info);
  * `ms_target` ms at 4 waves per SIMD; reports the achieved TFLOP/s and the shader clock (GHz) during the run.  The nominal
  * dense peak assumes the boost clock; under matrix-pipe load the board's power limit sets the clock. */
 int tsd_debug_mfma_sustained(tsd_ctx* ctx, float ms_target, float* tflops, float* clock_ghz);
+/* The ledger of device resources: what the library as a whole - every context, model and session of the process - holds on the device
+ * now, and what it has ever allocated and released.  Every device allocation, event and stream the library makes or releases is recorded
+ * as the runtime reports it; the ledger only counts and never changes what a call does.  LIVE fields go up and down; the others are
+ * monotone.  ALLOCS_LIVE == ALLOCS_TOTAL - FREES_TOTAL.  FREES_UNKNOWN counts releases of a pointer, event or stream the ledger does not
+ * hold (a double or a foreign release), RELEASE_ERRORS releases the runtime refused: both must stay 0.  A step of a session that keeps
+ * its "no allocation" promise leaves ALLOCS_TOTAL and FREES_TOTAL where they were.  What RCCL allocates for a communicator is its own
+ * and is not counted.  Writes the first min(n, TSD_DL_COUNT) fields to out and returns TSD_DL_COUNT; TSD_E_ARG for a NULL out or n < 0.
+ * Needs no device; safe from any thread. */
+enum tsd_device_ledger_field {
+  TSD_DL_ALLOCS_LIVE = 0, TSD_DL_BYTES_LIVE, TSD_DL_EVENTS_LIVE, TSD_DL_STREAMS_LIVE, TSD_DL_CTX_LIVE, TSD_DL_MODELS_LIVE,
+  TSD_DL_SESSIONS_LIVE, TSD_DL_ALLOCS_TOTAL, TSD_DL_FREES_TOTAL, TSD_DL_FREES_UNKNOWN, TSD_DL_RELEASE_ERRORS, TSD_DL_COUNT
+};
+/* debug */ int tsd_debug_device_ledger(int64_t* out, int n);
 
 /* ---- census -------------------------------------------------------------------------- */
 /* Algorithmic GFLOP (2*MAC of conv + linear + attention core) of one forward per sample

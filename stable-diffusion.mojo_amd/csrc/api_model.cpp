@@ -433,6 +433,8 @@ extern "C" int tsd_dist_unique_id(void* id128) {
 extern "C" int tsd_dist_init(tsd_ctx* ctx, int rank, int nranks, const void* id128) {
   NOTNULL(ctx); NOTNULL(id128);
   if (nranks <= 0 || rank < 0 || rank >= nranks) TSD_FAIL(TSD_E_ARG, "dist: rank %d / %d", rank, nranks);
+  if (ctx->rccl_comm)  // a second communicator would overwrite - and so leak - the first; nothing changes
+    TSD_FAIL(TSD_E_STATE, "dist: this context already holds a communicator (rank %d / %d); call tsd_dist_finalize first", ctx->rank, ctx->nranks);
   TSD_TRY(rccl_load());
   HIP_TRY(hipSetDevice(ctx->device));
   nccl_uid id;
@@ -462,9 +464,12 @@ extern "C" int tsd_dist_comm_count(tsd_ctx* ctx, int* nranks) {
   return TSD_OK;
 }
 
-extern "C" int tsd_dist_finalize(tsd_ctx* ctx) {
-  NOTNULL(ctx);
+void dist_release(tsd_ctx* ctx) {
   if (ctx->rccl_comm && g_rccl.destroy) g_rccl.destroy(ctx->rccl_comm);
   ctx->rccl_comm = nullptr;
+}
+extern "C" int tsd_dist_finalize(tsd_ctx* ctx) {
+  NOTNULL(ctx);
+  dist_release(ctx);
   return TSD_OK;
 }

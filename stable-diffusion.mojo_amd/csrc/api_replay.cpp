@@ -20,7 +20,7 @@ constexpr size_t GUARD = 4096;  // bytes of NaN pattern before and after every o
 class GuardedOperands {
  public:
   GuardedOperands(tsd_ctx* ctx, int slots) : st_(ctx->stream), s_((size_t)slots) {}
-  ~GuardedOperands() { for (Slot& s : s_) if (s.p) (void)hipFree(s.p); }
+  ~GuardedOperands() { for (Slot& s : s_) if (s.p) (void)dev_free(s.p); }
   GuardedOperands(const GuardedOperands&) = delete;
   // ext elements of es (2 or 4) bytes; payload: ext host elements to upload, or NULL; out: where read_back copies the extent - what
   // makes the slot an output - whose logical elements are `box`
@@ -28,7 +28,7 @@ class GuardedOperands {
     Slot& s = s_[(size_t)slot];
     s.ext = ext; s.es = es; s.payload = payload; s.out = out; s.box = box;
     const size_t bytes = 2 * GUARD + (size_t)ext * es;
-    HIP_TRY(hipMalloc((void**)&s.p, bytes));
+    HIP_TRY(dev_malloc((void**)&s.p, bytes));
     if (es == 2) HIP_TRY(hipMemsetD16Async((hipDeviceptr_t)s.p, replay::NAN16, bytes / 2, st_));
     else HIP_TRY(hipMemsetD32Async((hipDeviceptr_t)s.p, (int)replay::NAN32, bytes / 4, st_));
     if (payload) HIP_TRY(hipMemcpyAsync(s.p + GUARD, payload, (size_t)ext * es, hipMemcpyHostToDevice, st_));

@@ -29,6 +29,20 @@ void tsd_set_error(const char* fmt, ...);
     if (r__ != TSD_OK) return r__; \
   } while (0)
 
+// ---- device resources --------------------------------------------------------------------
+// Every device allocation, event and stream of the library is made and released through these (runtime.cpp): each calls HIP and then
+// records the outcome in the process-wide ledger (device_ledger.h) that tsd_debug_device_ledger reports.  They change nothing about the
+// call: arguments, result and error are HIP's.  No file of the library calls the runtime's own functions for these.
+hipError_t dev_malloc(void** p, size_t bytes);
+hipError_t dev_free(void* p);
+hipError_t dev_event_create(hipEvent_t* e);
+hipError_t dev_event_destroy(hipEvent_t e);
+hipError_t dev_stream_create(hipStream_t* s, unsigned flags);
+hipError_t dev_stream_destroy(hipStream_t s);
+// the create / destroy entry of a handle type: one more, one fewer
+enum DevHandle : int { DEV_CTX = 0, DEV_MODEL = 1, DEV_SESSION = 2 };
+void dev_handle_count(DevHandle kind, int delta);
+
 // ---- workspace arena: stack allocator over one big device allocation ------------------
 // All kernels of a context run on one stream, so releasing to a mark and re-using the bytes is
 // ordered by the stream.  `planning` mode only tracks the high-water mark (no launches).
@@ -170,7 +184,7 @@ struct tsd_ctx {
   bool launch() const { return !arena.planning; }
   // built-in per-kernel-class timer (hipEvents on THIS stream; bench.py's roofline leg)
   bool profile = false;
-  std::vector<hipEvent_t> prof_ev;  // pairs (start, stop)
+  std::vector<hipEvent_t> prof_ev;  // pairs (start, stop): created by ProfScope as a pass needs them, kept for the next pass, destroyed with the context
   std::vector<int> prof_cls;
   std::vector<int> prof_kern;   // kernel dispatches per record
   std::vector<int> prof_shape;  // 4 ints per record (M, N, K, batch) - 0 when not a GEMM
@@ -199,7 +213,8 @@ struct ProfScope {
     if (!on) return;
     if (c->prof_n * 2 + 2 > c->prof_ev.size()) {
       hipEvent_t a, b;
-      if (hipEventCreate(&a) != hipSuccess || hipEventCreate(&b) != hipSuccess) { on = false; return; }
+      if (dev_event_create(&a) != hipSuccess) { on = false; return; }
+      if (dev_event_create(&b) != hipSuccess) { (void)dev_event_destroy(a); on = false; return; }
       c->prof_ev.push_back(a); c->prof_ev.push_back(b);
     }
     if (c->prof_cls.size() <= c->prof_n) { c->prof_cls.push_back(cls); c->prof_shape.resize(4 * c->prof_cls.size()); }
@@ -236,6 +251,8 @@ inline int ctx_set_option(tsd_ctx* ctx, int TsdOptions::*field, int v, int lo, i
 }
 
 int ctx_reserve_staging(tsd_ctx* ctx, size_t bytes);
+// destroys the communicator of the context, if it holds one (api_model.cpp: tsd_dist_finalize and tsd_ctx_destroy)
+void dist_release(tsd_ctx* ctx);
 
 // ---- device tensor views (NHWC fp16 activations) ---------------------------------------
 struct Act {  // [B][H][W][C] with row pitch ld (elements) between pixels

@@ -1212,7 +1212,7 @@ static bool xcd_round_robin() {
   int ok = 0;
   const int nb = 1024;
   int* d = nullptr;
-  if (hipMalloc((void**)&d, nb * sizeof(int)) != hipSuccess) return false;
+  if (dev_malloc((void**)&d, nb * sizeof(int)) != hipSuccess) return false;
   std::vector<int> h(nb, -1);
   hipLaunchKernelGGL(k_probe_xcc, dim3(nb), dim3(64), 0, 0, d);
   if (hipMemcpy(h.data(), d, nb * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess) {
@@ -1220,7 +1220,7 @@ static bool xcd_round_robin() {
     for (int b = 0; b < nb; b++) if (h[b] < 0 || h[b] != h[b & 7]) ok = 0;
     for (int i = 0; i < 8; i++) for (int j = 0; j < i; j++) if (h[i] == h[j]) ok = 0;
   }
-  hipFree(d);
+  (void)dev_free(d);
   cached.store(ok, std::memory_order_relaxed);
   return ok != 0;
 }
@@ -1276,15 +1276,20 @@ extern "C" int tsd_debug_gemm_bench(tsd_ctx* ctx, int conv, int B, int H, int W,
   if (ctx->opt.gemm_ts) {
     const int nblk = 1 << 16;
     unsigned long long* dts = nullptr;
-    HIP_TRY(hipMalloc((void**)&dts, (size_t)nblk * 64));
-    HIP_TRY(hipMemset(dts, 0, (size_t)nblk * 64));
-    g_ts = dts;
-    r = launch_gemm(ctx, g);
-    g_ts = nullptr;
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(dev_malloc((void**)&dts, (size_t)nblk * 64));
     std::vector<unsigned long long> h((size_t)nblk * 8);
-    HIP_TRY(hipMemcpy(h.data(), dts, (size_t)nblk * 64, hipMemcpyDeviceToHost));
-    hipFree(dts);
+    // everything between the allocation and its release fails into `probed`: the buffer is freed on every way out
+    const int probed = [&]() -> int {
+      HIP_TRY(hipMemset(dts, 0, (size_t)nblk * 64));
+      g_ts = dts;
+      r = launch_gemm(ctx, g);
+      g_ts = nullptr;
+      HIP_TRY(hipStreamSynchronize(ctx->stream));
+      HIP_TRY(hipMemcpy(h.data(), dts, (size_t)nblk * 64, hipMemcpyDeviceToHost));
+      return TSD_OK;
+    }();
+    (void)dev_free(dts);
+    if (probed != TSD_OK) return probed;
     unsigned long long tmin = ~0ull, tmax = 0; int n = 0;
     for (int b = 0; b < nblk; b++) if (h[b * 8]) { n++; tmin = std::min(tmin, h[b * 8 + 5]); tmax = std::max(tmax, h[b * 8 + 6]); }
     fprintf(stderr, "[ts] blocks=%d span first-start..last-end = %.2f us (100 MHz realtime)\n", n, (tmax - tmin) * 0.01);
@@ -1457,7 +1462,7 @@ int launch_gemm(tsd_ctx* ctx, const GemmArgs& a) {
   k.splitk = plan.ways; k.sk_cfg = splitk ? plan.cfg : 0; k.sk_ws = sk_ws; k.sk_flags = nullptr; k.sk_epoch = 0;
   if (splitk) {
     if (!ctx->sk_flags) {
-      HIP_TRY(hipMalloc((void**)&ctx->sk_flags, 4096 * sizeof(int)));
+      HIP_TRY(dev_malloc((void**)&ctx->sk_flags, 4096 * sizeof(int)));
       HIP_TRY(hipMemsetAsync(ctx->sk_flags, 0, 4096 * sizeof(int), ctx->stream));
     }
     k.sk_flags = ctx->sk_flags;

@@ -139,13 +139,13 @@ int vision_tab(tsd_ctx* ctx, int H, int W, VisionTab* out) {
   HIP_TRY(hipSetDevice(ctx->device));
   if (ctx->vision_tabs.size() >= 32) {  // a bounded cache: the oldest table goes once nothing in flight can read it
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    (void)hipFree(ctx->vision_tabs.front().dev);
+    (void)dev_free(ctx->vision_tabs.front().dev);
     ctx->vision_tabs.erase(ctx->vision_tabs.begin());
   }
-  HIP_TRY(hipMalloc(&t.dev, host.size()));
+  HIP_TRY(dev_malloc(&t.dev, host.size()));
   hipError_t e = hipMemcpyAsync(t.dev, host.data(), host.size(), hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);  // `host` goes out of scope
-  if (e != hipSuccess) { (void)hipFree(t.dev); TSD_FAIL(TSD_E_HIP, "clip image: table upload failed: %s", hipGetErrorString(e)); }
+  if (e != hipSuccess) { (void)dev_free(t.dev); TSD_FAIL(TSD_E_HIP, "clip image: table upload failed: %s", hipGetErrorString(e)); }
   ctx->vision_tabs.push_back(t);
   *out = t;
   return TSD_OK;

@@ -174,6 +174,26 @@ static size_t packed_bytes(const ParamSpec& p) {
   }
 }
 
+// the zeroed blob of a laid-out model and the views into it ...
+static int model_init_blob(tsd_model* m) {
+  tsd_ctx* ctx = m->ctx;
+  HIP_TRY(hipSetDevice(ctx->device));
+  hipError_t e = dev_malloc((void**)&m->blob, m->blob_bytes);
+  if (e != hipSuccess) TSD_FAIL(TSD_E_ALLOC, "weights: allocating %zu bytes failed: %s", m->blob_bytes, hipGetErrorString(e));
+  HIP_TRY(hipMemsetAsync(m->blob, 0, m->blob_bytes, ctx->stream));
+  return model_resolve(m);
+}
+// ... and everything a model owns on the device, released once the context's stream is idle: whatever exists of a model that failed
+// half-way, or all of a live one (adapter snapshots included: a model may be destroyed merged).  The object itself goes too.
+static void model_release(tsd_model* m) {
+  (void)hipSetDevice(m->ctx->device);
+  (void)hipStreamSynchronize(m->ctx->stream);
+  if (m->blob) (void)dev_free(m->blob);
+  if (m->derived) (void)dev_free(m->derived);
+  for (auto& kv : m->lora_base) (void)dev_free(kv.second);
+  delete m;
+}
+
 extern "C" int tsd_model_create(tsd_ctx* ctx, int kind, tsd_model** out) {
   if (!ctx || !out) TSD_FAIL(TSD_E_ARG, "tsd_model_create: NULL argument");
   if (!is_model_kind(kind)) TSD_FAIL(TSD_E_ARG, "bad model kind %d", kind);
@@ -201,26 +221,17 @@ extern "C" int tsd_model_create(tsd_ctx* ctx, int kind, tsd_model** out) {
   m->blob_bytes = off;
   for (size_t i = 0; i < m->params.size(); i++) m->index[m->params[i].name] = (int)i;
   m->loaded.assign(m->params.size(), 0);
-  HIP_TRY(hipSetDevice(ctx->device));
-  hipError_t e = hipMalloc((void**)&m->blob, m->blob_bytes);
-  if (e != hipSuccess) {
-    delete m;
-    TSD_FAIL(TSD_E_ALLOC, "weights: hipMalloc(%zu) failed: %s", off, hipGetErrorString(e));
-  }
-  HIP_TRY(hipMemsetAsync(m->blob, 0, m->blob_bytes, ctx->stream));
-  TSD_TRY(model_resolve(m));
+  const int r = model_init_blob(m);
+  if (r != TSD_OK) { model_release(m); return r; }  // the one way out of a model that did not come to be: nothing of it stays
+  dev_handle_count(DEV_MODEL, +1);
   *out = m;
   return TSD_OK;
 }
 
 extern "C" int tsd_model_destroy(tsd_model* m) {
   if (!m) return TSD_OK;
-  hipSetDevice(m->ctx->device);
-  hipStreamSynchronize(m->ctx->stream);
-  if (m->blob) hipFree(m->blob);
-  if (m->derived) hipFree(m->derived);
-  for (auto& kv : m->lora_base) hipFree(kv.second);
-  delete m;
+  model_release(m);
+  dev_handle_count(DEV_MODEL, -1);
   return TSD_OK;
 }
 
@@ -229,7 +240,7 @@ extern "C" int tsd_model_destroy(tsd_model* m) {
 static void lora_drop(tsd_model* m, int index = -1) {
   for (auto it = m->lora_base.begin(); it != m->lora_base.end();) {
     if (index >= 0 && it->first != index) { ++it; continue; }
-    (void)hipFree(it->second);
+    (void)dev_free(it->second);
     it = m->lora_base.erase(it);
   }
 }
@@ -408,12 +419,12 @@ extern "C" int tsd_model_lora_add(tsd_model* m, int index, int row0, int rows, c
   TSD_TRY(ctx_check_status(ctx));  // TSD_E_NONFINITE (reported once, then cleared): a merged weight left fp16, or up / down held inf / NaN
   if (!m->lora_base.count(index)) {
     char* snap = nullptr;
-    hipError_t e = hipMalloc((void**)&snap, p.bytes);
-    if (e != hipSuccess) TSD_FAIL(TSD_E_ALLOC, "lora_add: hipMalloc(%zu) for the base of %s failed: %s", p.bytes, p.name.c_str(), hipGetErrorString(e));
+    hipError_t e = dev_malloc((void**)&snap, p.bytes);
+    if (e != hipSuccess) TSD_FAIL(TSD_E_ALLOC, "lora_add: allocating %zu bytes for the base of %s failed: %s", p.bytes, p.name.c_str(), hipGetErrorString(e));
     // on the context's stream, like the copy over the parameter below: a device-to-device hipMemcpy on the null stream may still be reading
     // the base when that copy starts
     e = hipMemcpyAsync(snap, m->blob + p.off, p.bytes, hipMemcpyDeviceToDevice, ctx->stream);
-    if (e != hipSuccess) { (void)hipFree(snap); TSD_FAIL(TSD_E_HIP, "lora_add: snapshot of %s: %s", p.name.c_str(), hipGetErrorString(e)); }
+    if (e != hipSuccess) { (void)dev_free(snap); TSD_FAIL(TSD_E_HIP, "lora_add: snapshot of %s: %s", p.name.c_str(), hipGetErrorString(e)); }
     m->lora_base[index] = snap;
   }
   HIP_TRY(hipMemcpyAsync(m->blob + p.off, st, p.bytes, hipMemcpyDeviceToDevice, ctx->stream));
@@ -454,10 +465,10 @@ static int model_build_derived(tsd_model* m) {
     const size_t need = (size_t)c0.Opad * 64 * sizeof(half_t);
     HIP_TRY(hipSetDevice(ctx->device));
     if (m->derived_bytes < need) {
-      if (m->derived) HIP_TRY(hipFree(m->derived));
+      if (m->derived) HIP_TRY(dev_free(m->derived));
       m->derived = nullptr; m->derived_bytes = 0;
-      hipError_t e = hipMalloc((void**)&m->derived, need);
-      if (e != hipSuccess) TSD_FAIL(TSD_E_ALLOC, "derived weights: hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
+      hipError_t e = dev_malloc((void**)&m->derived, need);
+      if (e != hipSuccess) TSD_FAIL(TSD_E_ALLOC, "derived weights: allocating %zu bytes failed: %s", need, hipGetErrorString(e));
       m->derived_bytes = need;
       if (ctx->opt.debug_poison >= 0 && (ctx->opt.debug_poison_what & 2)) HIP_TRY(hipMemsetAsync(m->derived, ctx->opt.debug_poison & 255, need, ctx->stream));
     }
@@ -558,10 +569,10 @@ static int model_build_derived(tsd_model* m) {
   const size_t each = tail_b + head_b, need = each * el.size() + cin_b + tm_b + fold_b + dup_w1_b + dup_sk_b + dup_tm_b + uf_b;
   HIP_TRY(hipSetDevice(ctx->device));
   if (m->derived_bytes < need) {
-    if (m->derived) HIP_TRY(hipFree(m->derived));
+    if (m->derived) HIP_TRY(dev_free(m->derived));
     m->derived = nullptr; m->derived_bytes = 0;
-    hipError_t e = hipMalloc((void**)&m->derived, need);
-    if (e != hipSuccess) TSD_FAIL(TSD_E_ALLOC, "derived weights: hipMalloc(%zu) failed: %s", need, hipGetErrorString(e));
+    hipError_t e = dev_malloc((void**)&m->derived, need);
+    if (e != hipSuccess) TSD_FAIL(TSD_E_ALLOC, "derived weights: allocating %zu bytes failed: %s", need, hipGetErrorString(e));
     m->derived_bytes = need;
     if (ctx->opt.debug_poison >= 0 && (ctx->opt.debug_poison_what & 2)) HIP_TRY(hipMemsetAsync(m->derived, ctx->opt.debug_poison & 255, need, ctx->stream));
   }

@@ -5,8 +5,60 @@
 #include <string.h>
 
 #include "common.h"
+#include "device_ledger.h"
 
 static thread_local char g_err[512] = "";
+
+// ---- the ledger of device resources and the only calls of the runtime that make or release one ---------------------------------------
+static ledger::DeviceLedger& the_ledger() {
+  static ledger::DeviceLedger l;
+  return l;
+}
+hipError_t dev_malloc(void** p, size_t bytes) {
+  const hipError_t e = hipMalloc(p, bytes);
+  if (e == hipSuccess) the_ledger().alloc(*p, bytes);
+  return e;
+}
+hipError_t dev_free(void* p) {
+  const hipError_t e = hipFree(p);
+  the_ledger().free(p, e == hipSuccess);
+  return e;
+}
+hipError_t dev_event_create(hipEvent_t* ev) {
+  const hipError_t e = hipEventCreate(ev);
+  if (e == hipSuccess) the_ledger().event_create(*ev);
+  return e;
+}
+hipError_t dev_event_destroy(hipEvent_t ev) {
+  const hipError_t e = hipEventDestroy(ev);
+  the_ledger().event_destroy(ev, e == hipSuccess);
+  return e;
+}
+hipError_t dev_stream_create(hipStream_t* s, unsigned flags) {
+  const hipError_t e = hipStreamCreateWithFlags(s, flags);
+  if (e == hipSuccess) the_ledger().stream_create(*s);
+  return e;
+}
+hipError_t dev_stream_destroy(hipStream_t s) {
+  const hipError_t e = hipStreamDestroy(s);
+  the_ledger().stream_destroy(s, e == hipSuccess);
+  return e;
+}
+void dev_handle_count(DevHandle kind, int delta) { the_ledger().handle((ledger::Handle)kind, delta); }
+
+static_assert((int)ledger::ALLOCS_LIVE == TSD_DL_ALLOCS_LIVE && (int)ledger::BYTES_LIVE == TSD_DL_BYTES_LIVE &&
+              (int)ledger::EVENTS_LIVE == TSD_DL_EVENTS_LIVE && (int)ledger::STREAMS_LIVE == TSD_DL_STREAMS_LIVE &&
+              (int)ledger::CTX_LIVE == TSD_DL_CTX_LIVE && (int)ledger::MODELS_LIVE == TSD_DL_MODELS_LIVE &&
+              (int)ledger::SESSIONS_LIVE == TSD_DL_SESSIONS_LIVE && (int)ledger::ALLOCS_TOTAL == TSD_DL_ALLOCS_TOTAL &&
+              (int)ledger::FREES_TOTAL == TSD_DL_FREES_TOTAL && (int)ledger::FREES_UNKNOWN == TSD_DL_FREES_UNKNOWN &&
+              (int)ledger::RELEASE_ERRORS == TSD_DL_RELEASE_ERRORS && (int)ledger::COUNT == TSD_DL_COUNT,
+              "tsd_device_ledger_field (include/tsd.h) and ledger::Field (device_ledger.h) name the same fields in the same order");
+static_assert((int)ledger::CTX == DEV_CTX && (int)ledger::MODEL == DEV_MODEL && (int)ledger::SESSION == DEV_SESSION, "DevHandle == ledger::Handle");
+// The first min(n, TSD_DL_COUNT) fields of the ledger; returns TSD_DL_COUNT.  Needs no device and no context.
+extern "C" int tsd_debug_device_ledger(int64_t* out, int n) {
+  if (!out || n < 0) TSD_FAIL(TSD_E_ARG, "tsd_debug_device_ledger: out is NULL or n < 0");
+  return the_ledger().snapshot(out, n);
+}
 
 void tsd_set_error(const char* fmt, ...) {
   va_list ap;
@@ -70,6 +122,35 @@ extern "C" int tsd_device_count(void) {
   return n;
 }
 
+// what tsd_ctx_create makes on the device, each into its field as soon as it exists ...
+static int ctx_init(tsd_ctx* c) {
+  HIP_TRY(dev_stream_create(&c->stream, hipStreamNonBlocking));
+  HIP_TRY(dev_event_create(&c->ev0));
+  HIP_TRY(dev_event_create(&c->ev1));
+  HIP_TRY(dev_malloc((void**)&c->status, 16 * sizeof(int)));
+  HIP_TRY(hipMemsetAsync(c->status, 0, 16 * sizeof(int), c->stream));
+  HIP_TRY(dev_malloc((void**)&c->zeros, 4096));
+  HIP_TRY(hipMemsetAsync(c->zeros, 0, 4096, c->stream));
+  HIP_TRY(hipMemsetD16Async((hipDeviceptr_t)(c->zeros + 1024), 0x3C00, 64, c->stream));  // 64 halves of 1.0 (attention row sums)
+  HIP_TRY(hipStreamSynchronize(c->stream));
+  return TSD_OK;
+}
+// ... and everything a context owns on the device, released: whatever exists of a context that failed half-way, or all of a live one
+// whose stream is idle.  The object itself goes too.
+static void ctx_release(tsd_ctx* c) {
+  if (c->arena.base) (void)dev_free(c->arena.base);
+  if (c->staging) (void)dev_free(c->staging);
+  if (c->zeros) (void)dev_free(c->zeros);
+  if (c->status) (void)dev_free(c->status);
+  if (c->sk_flags) (void)dev_free(c->sk_flags);
+  for (VisionTab& t : c->vision_tabs) if (t.dev) (void)dev_free(t.dev);
+  for (hipEvent_t e : c->prof_ev) (void)dev_event_destroy(e);
+  if (c->ev0) (void)dev_event_destroy(c->ev0);
+  if (c->ev1) (void)dev_event_destroy(c->ev1);
+  if (c->stream) (void)dev_stream_destroy(c->stream);
+  delete c;
+}
+
 extern "C" int tsd_ctx_create(int device, tsd_ctx** out) {
   if (!out) TSD_FAIL(TSD_E_ARG, "tsd_ctx_create: out is NULL");
   *out = nullptr;
@@ -88,15 +169,9 @@ extern "C" int tsd_ctx_create(int device, tsd_ctx** out) {
   tsd_ctx* c = new tsd_ctx();
   c->device = device;
   options_from_env(c->opt);
-  HIP_TRY(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-  HIP_TRY(hipEventCreate(&c->ev0));
-  HIP_TRY(hipEventCreate(&c->ev1));
-  HIP_TRY(hipMalloc((void**)&c->status, 16 * sizeof(int)));
-  HIP_TRY(hipMemsetAsync(c->status, 0, 16 * sizeof(int), c->stream));
-  HIP_TRY(hipMalloc((void**)&c->zeros, 4096));
-  HIP_TRY(hipMemsetAsync(c->zeros, 0, 4096, c->stream));
-  HIP_TRY(hipMemsetD16Async((hipDeviceptr_t)(c->zeros + 1024), 0x3C00, 64, c->stream));  // 64 halves of 1.0 (attention row sums)
-  HIP_TRY(hipStreamSynchronize(c->stream));
+  const int r = ctx_init(c);
+  if (r != TSD_OK) { ctx_release(c); return r; }  // the one way out of a context that did not come to be: nothing of it stays
+  dev_handle_count(DEV_CTX, +1);
   *out = c;
   return TSD_OK;
 }
@@ -105,16 +180,9 @@ extern "C" int tsd_ctx_destroy(tsd_ctx* c) {
   if (!c) return TSD_OK;
   hipSetDevice(c->device);
   hipStreamSynchronize(c->stream);
-  if (c->arena.base) hipFree(c->arena.base);
-  if (c->staging) hipFree(c->staging);
-  if (c->zeros) hipFree(c->zeros);
-  if (c->status) hipFree(c->status);
-  if (c->sk_flags) hipFree(c->sk_flags);
-  for (VisionTab& t : c->vision_tabs) if (t.dev) hipFree(t.dev);
-  hipEventDestroy(c->ev0);
-  hipEventDestroy(c->ev1);
-  hipStreamDestroy(c->stream);
-  delete c;
+  dist_release(c);  // a communicator the caller did not finalize
+  ctx_release(c);
+  dev_handle_count(DEV_CTX, -1);
   return TSD_OK;
 }
 
@@ -229,12 +297,12 @@ int ctx_reserve_arena(tsd_ctx* c, size_t bytes) {
   if (c->arena.cap >= bytes) return TSD_OK;
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if (c->arena.base) HIP_TRY(hipFree(c->arena.base));
+  if (c->arena.base) HIP_TRY(dev_free(c->arena.base));
   c->arena.base = nullptr;
   c->arena.cap = 0;
   const size_t want = bytes + (bytes >> 4) + (1 << 20);
-  hipError_t e = hipMalloc((void**)&c->arena.base, want);
-  if (e != hipSuccess) TSD_FAIL(TSD_E_ALLOC, "workspace arena: hipMalloc(%zu) failed: %s", want, hipGetErrorString(e));
+  hipError_t e = dev_malloc((void**)&c->arena.base, want);
+  if (e != hipSuccess) TSD_FAIL(TSD_E_ALLOC, "workspace arena: allocating %zu bytes failed: %s", want, hipGetErrorString(e));
   c->arena.cap = want;
   if (c->opt.debug_poison >= 0 && (c->opt.debug_poison_what & 1)) HIP_TRY(hipMemsetAsync(c->arena.base, c->opt.debug_poison & 255, want, c->stream));  // on the context's stream: ordered before everything that uses the arena
   return TSD_OK;
@@ -244,11 +312,11 @@ int ctx_reserve_staging(tsd_ctx* c, size_t bytes) {
   if (c->staging_cap >= bytes) return TSD_OK;
   HIP_TRY(hipSetDevice(c->device));
   HIP_TRY(hipStreamSynchronize(c->stream));
-  if (c->staging) HIP_TRY(hipFree(c->staging));
+  if (c->staging) HIP_TRY(dev_free(c->staging));
   c->staging = nullptr;
   c->staging_cap = 0;
-  hipError_t e = hipMalloc(&c->staging, bytes);
-  if (e != hipSuccess) TSD_FAIL(TSD_E_ALLOC, "staging: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+  hipError_t e = dev_malloc(&c->staging, bytes);
+  if (e != hipSuccess) TSD_FAIL(TSD_E_ALLOC, "staging: allocating %zu bytes failed: %s", bytes, hipGetErrorString(e));
   c->staging_cap = bytes;
   if (c->opt.debug_poison >= 0 && (c->opt.debug_poison_what & 16)) HIP_TRY(hipMemsetAsync(c->staging, c->opt.debug_poison & 255, bytes, c->stream));
   return TSD_OK;

@@ -174,9 +174,9 @@ static void session_latents_changed(tsd_session* s) {
 // One of the session's own growable device buffers holds `bytes`: kept while large enough, else replaced (the contents are lost).
 static int session_grow(tsd_ctx* ctx, void** ptr, size_t* cap, size_t bytes, const char* what) {
   if (bytes <= *cap) return TSD_OK;
-  if (*ptr) HIP_TRY(hipFree(*ptr));
+  if (*ptr) HIP_TRY(dev_free(*ptr));
   *ptr = nullptr; *cap = 0;
-  if (hipMalloc(ptr, bytes) != hipSuccess) TSD_FAIL(TSD_E_ALLOC, "session: %s hipMalloc(%zu) failed", what, bytes);
+  if (dev_malloc(ptr, bytes) != hipSuccess) TSD_FAIL(TSD_E_ALLOC, "session: allocating the %s buffer (%zu bytes) failed", what, bytes);
   *cap = bytes;
   if (ctx->opt.debug_poison >= 0 && (ctx->opt.debug_poison_what & 8)) HIP_TRY(hipMemsetAsync(*ptr, ctx->opt.debug_poison & 255, bytes, ctx->stream));
   return TSD_OK;
@@ -356,6 +356,15 @@ extern "C" int tsd_debug_session_hoist_info(tsd_session* s, int64_t* info) {
   return TSD_OK;
 }
 
+// Every device buffer a session can own - the state block of create and the eight that session_grow sizes later - released, and the
+// object with them.  The one list: tsd_session_destroy and the failure path of create go through it.
+static void session_release(tsd_session* s) {
+  void* const owned[] = {s->state, s->noise, s->kv, s->ttab, s->trows, s->ctl, s->cn_kv, s->cn_ttab, s->ipb};
+  for (void* p : owned)
+    if (p) (void)dev_free(p);
+  delete s;
+}
+
 extern "C" int tsd_session_create_hw(tsd_model* diffusion, tsd_model* decoder, int B, int LH, int LW, int T, int cfg,
                                      tsd_session** out) {
   NOTNULL(diffusion); NOTNULL(out);
@@ -380,8 +389,8 @@ extern "C" int tsd_session_create_hw(tsd_model* diffusion, tsd_model* decoder, i
                o_img = carve(decoder ? (size_t)B * 3 * 64 * hw * 4 : 0), o_hist = carve(nl * 4),
                o_ipm = carve((size_t)B * hw * 4), o_ipk = carve(nl * 4), o_ipn = carve(nl * 4),
                o_grp = carve((size_t)CFG_RESCALE_PARTIAL_DOUBLES * sizeof(double));
-  hipError_t e = hipMalloc((void**)&s->state, off);
-  if (e != hipSuccess) { delete s; TSD_FAIL(TSD_E_ALLOC, "session: hipMalloc(%zu) failed: %s", off, hipGetErrorString(e)); }
+  hipError_t e = dev_malloc((void**)&s->state, off);
+  if (e != hipSuccess) { delete s; TSD_FAIL(TSD_E_ALLOC, "session: allocating %zu bytes failed: %s", off, hipGetErrorString(e)); }
   if (ctx->opt.debug_poison >= 0 && (ctx->opt.debug_poison_what & 4)) hipMemsetAsync(s->state, ctx->opt.debug_poison & 255, off, ctx->stream);
   s->latents = (float*)(s->state + o_lat); s->lat2 = (float*)(s->state + o_lat2);
   s->ctx16 = (half_t*)(s->state + o_ctx); s->eps = (float*)(s->state + o_eps);
@@ -390,7 +399,8 @@ extern "C" int tsd_session_create_hw(tsd_model* diffusion, tsd_model* decoder, i
   s->hist = (float*)(s->state + o_hist);
   s->ip_mask = (float*)(s->state + o_ipm); s->ip_known = (float*)(s->state + o_ipk); s->ip_noise = (float*)(s->state + o_ipn);
   s->gr_part = (double*)(s->state + o_grp);
-  if (session_configure(s, session_config(s)) != TSD_OK) { hipFree(s->state); delete s; return TSD_E_ARG; }
+  if (session_configure(s, session_config(s)) != TSD_OK) { session_release(s); return TSD_E_ARG; }
+  dev_handle_count(DEV_SESSION, +1);
   *out = s;
   return TSD_OK;
 }
@@ -408,16 +418,8 @@ extern "C" int tsd_session_destroy(tsd_session* s) {
   if (!s) return TSD_OK;
   hipSetDevice(s->ctx->device);
   hipStreamSynchronize(s->ctx->stream);
-  if (s->state) hipFree(s->state);
-  if (s->noise) hipFree(s->noise);
-  if (s->kv) hipFree(s->kv);
-  if (s->ttab) hipFree(s->ttab);
-  if (s->trows) hipFree(s->trows);
-  if (s->ctl) hipFree(s->ctl);
-  if (s->cn_kv) hipFree(s->cn_kv);
-  if (s->cn_ttab) hipFree(s->cn_ttab);
-  if (s->ipb) hipFree(s->ipb);
-  delete s;
+  session_release(s);
+  dev_handle_count(DEV_SESSION, -1);
   return TSD_OK;
 }
 

@@ -20,7 +20,7 @@ There is no CPU fallback.
 """
 from . import _lib, rng  # noqa: F401
 from . import ext  # noqa: F401  (non-reference extensions: torch-style norms)
-from ._lib import Context, TsdError, default_context, set_default_context, set_strict  # noqa: F401
+from ._lib import Context, TsdError, default_context, device_ledger, set_default_context, set_strict  # noqa: F401
 from .model import Model, Session, flop_count, param_specs  # noqa: F401
 from .utils import (Conv2D, Gelu, GroupNorm, LayerNorm, Linear, SiLU, Softmax, Upsample, alphas_cumprod, cfg_rescale, concat,  # noqa: F401
                     control_inject, ddpm_step, get_time_embedding, inpaint_blend, ip_attn_add, latent_mask, matmul, normal_fill, pad, rescale, sampler_step_v)

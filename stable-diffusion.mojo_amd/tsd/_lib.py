@@ -229,6 +229,7 @@ def _declare(l):
         "tsd_debug_elem_run": ([vp, C.POINTER(i64), i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)], i),
         "tsd_debug_gn_path_counts": ([vp, C.POINTER(i64), i, i], i),
         "tsd_debug_jitter_selftest": ([vp, i], i),
+        "tsd_debug_device_ledger": ([C.POINTER(i64), i], i),
     }
     for name, (args, res) in sig.items():
         fn = getattr(l, name)
@@ -239,13 +240,54 @@ def _declare(l):
 EXPORTS = None  # filled lazily for the symbol test
 
 
+def _header():
+    """include/tsd.h without its comments."""
+    import re
+    hdr = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "tsd.h")
+    return re.sub(r"/\*.*?\*/", "", open(hdr).read(), flags=re.S)
+
+
 def declared_symbols():
     """Names of every function declared in include/tsd.h (parsed, so the test cannot drift)."""
     import re
-    hdr = os.path.join(os.path.dirname(os.path.dirname(_HERE)), "include", "tsd.h")
-    txt = open(hdr).read()
-    txt = re.sub(r"/\*.*?\*/", "", txt, flags=re.S)
-    return sorted(set(re.findall(r"\b(tsd_[a-z0-9_]+)\s*\(", txt)))
+    return sorted(set(re.findall(r"\b(tsd_[a-z0-9_]+)\s*\(", _header())))
+
+
+def header_enum(name, prefix=""):
+    """{enumerator without `prefix`: value} of `enum name` in include/tsd.h (parsed, so the names cannot drift from the library's)."""
+    import re
+    out, v = {}, 0
+    for item in re.search(r"enum\s+" + name + r"\s*\{(.*?)\}", _header(), re.S).group(1).split(","):
+        item = item.strip()
+        if not item:
+            continue
+        if "=" in item:
+            item, val = (s.strip() for s in item.split("="))
+            v = int(val, 0)
+        out[item[len(prefix):] if item.startswith(prefix) else item] = v
+        v += 1
+    return out
+
+
+_ledger_fields = None
+
+
+def device_ledger():
+    """The library's ledger of device resources (tsd_debug_device_ledger) as {field: value}, the fields named as in
+    tsd_device_ledger_field without the TSD_DL_ prefix: ALLOCS_LIVE, BYTES_LIVE, EVENTS_LIVE, STREAMS_LIVE, CTX_LIVE, MODELS_LIVE,
+    SESSIONS_LIVE (what the whole process holds now) and ALLOCS_TOTAL, FREES_TOTAL, FREES_UNKNOWN, RELEASE_ERRORS (monotone).  Needs no GPU."""
+    global _ledger_fields
+    if _ledger_fields is None:
+        f = header_enum("tsd_device_ledger_field", "TSD_DL_")
+        n = f.pop("COUNT")
+        assert sorted(f.values()) == list(range(n)), f
+        _ledger_fields = f
+    n = len(_ledger_fields)
+    out = (C.c_int64 * n)()
+    got = lib().tsd_debug_device_ledger(out, n)
+    if got != n:
+        raise TsdError(got if got < 0 else TSD_E_STATE, f"tsd_debug_device_ledger reports {got} fields, include/tsd.h names {n}")
+    return {k: int(out[v]) for k, v in _ledger_fields.items()}
 
 
 def last_error():

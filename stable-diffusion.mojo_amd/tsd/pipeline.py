@@ -134,77 +134,77 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
     if input_image is not None and np.shape(input_image)[-2:] != (8 * LH, 8 * LW):
         raise ValueError(f"input_image must be {(8 * LH, 8 * LW)} pixels (rows, columns), got {np.shape(input_image)}")
     sess = Session(diffusion.model, decoder.model if decoder is not None else None, B, L, T, cfg=cfg)
-    start = 0
-    if input_image is not None:
-        start = inference_steps - int(inference_steps * strength)  # sampler.mojo:68-70
-    if (prediction, bool(zero_terminal_snr)) != ("epsilon", False):  # likewise: the default session never hears of it
-        sess.set_prediction(prediction, zero_terminal_snr)
-    if (sampler, eta, spacing) != ("ddpm", 0.0, "leading"):  # the default session is the reference's: nothing to set
-        sess.set_sampler(sampler, eta, spacing)
-    sess.set_schedule(num_training_steps, inference_steps, start)
-    n = sess.num_steps
-    nl = B * 4 * LH * LW
-    if input_image is not None:  # pipeline.mojo:66-79
-        img = rescale(input_image, (0, 255), (-1, 1))
-        enc_noise = rng.normal(seed_val, 1, nl).reshape(B, 4, LH, LW)
-        latents = encoder.forward(img, enc_noise)
-        if mask is not None:
-            mask_lat = latent_mask(mask, mask_mode, diffusion.model.ctx)
-    elif latents is None:
-        latents = np.zeros((B, 4, LH, LW), dtype=np.float32) if seeds is not None else rng.normal(seed_val, 2, nl).reshape(B, 4, LH, LW)
-    if noise is None and seeds is None:
-        noise = rng.normal(seed_val, 3, n * nl).reshape(n, B, 4, LH, LW)
-    sess.upload(latents, context, uncond_context if cfg else None, noise, cfg_scale)
-    if seeds is not None:
-        sess.set_seeds(seeds)
-        if input_image is None:
-            sess.seed_latents()
-        else:
-            sess.add_noise_seeded(0)
+    try:
+        start = 0
+        if input_image is not None:
+            start = inference_steps - int(inference_steps * strength)  # sampler.mojo:68-70
+        if (prediction, bool(zero_terminal_snr)) != ("epsilon", False):  # likewise: the default session never hears of it
+            sess.set_prediction(prediction, zero_terminal_snr)
+        if (sampler, eta, spacing) != ("ddpm", 0.0, "leading"):  # the default session is the reference's: nothing to set
+            sess.set_sampler(sampler, eta, spacing)
+        sess.set_schedule(num_training_steps, inference_steps, start)
+        n = sess.num_steps
+        nl = B * 4 * LH * LW
+        if input_image is not None:  # pipeline.mojo:66-79
+            img = rescale(input_image, (0, 255), (-1, 1))
+            enc_noise = rng.normal(seed_val, 1, nl).reshape(B, 4, LH, LW)
+            latents = encoder.forward(img, enc_noise)
             if mask is not None:
-                sess.set_inpaint(mask_lat, latents, seeded=True)
-    elif input_image is not None:
-        z4 = rng.normal(seed_val, 4, nl).reshape(B, 4, LH, LW)
-        sess.add_noise(0, z4)  # sampler.mojo:111-124 at timesteps[0]
-        if mask is not None:
-            sess.set_inpaint(mask_lat, latents, z4)
-    if guidance_rescale > 0.0:
-        sess.set_guidance_rescale(guidance_rescale)
-    if controlnet is not None:  # step i of n is controlled when control_start <= i / n and (i + 1) / n <= control_end, as diffusers keeps it
-        first = int(np.ceil(control_start * n - 1e-9))
-        last = int(np.floor(control_end * n + 1e-9)) - 1
-        if last >= first:
-            sess.set_control(controlnet, control_image, control_scale, control_cond_only, first, last)
-    if ip_adapter is not None:
-        first = int(np.ceil(ip_start * n - 1e-9))
-        last = int(np.floor(ip_end * n + 1e-9)) - 1
-        if last >= first and plus:
-            def hidden_rows(h, what):
-                h = np.asarray(h, dtype=np.float32)
-                h = np.repeat(h[None], B, axis=0) if h.ndim == 2 else h
-                if h.ndim != 3 or h.shape[0] != B or h.shape[2] != 1280:
-                    raise ValueError(f"generate: {what} must have shape (S, 1280) or ({B}, S, 1280), got {h.shape}")
-                return h
-            h = hidden_rows(image_encoder.forward(ip_image, hidden=True)[1] if ip_image is not None else ip_hidden, "the hidden states")
-            hu = None
-            if cfg:  # the published pipelines' resample(hidden(encoder(zeros_like(normalised pixels))))
-                from .clip import clip_neutral_image
-                hu = hidden_rows(ip_uncond_hidden if ip_uncond_hidden is not None else image_encoder.forward(clip_neutral_image(), hidden=True)[1],
-                                 "ip_uncond_hidden")
-            sess.set_ip_adapter(ip_adapter, ip_adapter.resample(h), ip_adapter.resample(hu) if cfg else None, ip_scale, first, last)
-        elif last >= first:
-            e = np.asarray(image_encoder.forward(ip_image) if ip_image is not None else ip_image_embeds, dtype=np.float32)
-            e = np.repeat(e[None], B, axis=0) if e.ndim == 1 else e
-            if e.shape != (B, 1024):
-                raise ValueError(f"generate: the image embeddings must have shape (1024,) or ({B}, 1024), got {e.shape}")
-            sess.set_ip_adapter(ip_adapter, ip_adapter.project(e), ip_adapter.project(np.zeros_like(e)) if cfg else None, ip_scale, first, last)
-    for i in range(n):  # pipeline.mojo:87-122
-        sess.step(i)
-    out_lat = sess.latents()
-    if decoder is None or return_latents:
-        sess.close()
-        return out_lat
-    sess.decode()
-    images = sess.images(rescale=True)
-    sess.close()
-    return images
+                mask_lat = latent_mask(mask, mask_mode, diffusion.model.ctx)
+        elif latents is None:
+            latents = np.zeros((B, 4, LH, LW), dtype=np.float32) if seeds is not None else rng.normal(seed_val, 2, nl).reshape(B, 4, LH, LW)
+        if noise is None and seeds is None:
+            noise = rng.normal(seed_val, 3, n * nl).reshape(n, B, 4, LH, LW)
+        sess.upload(latents, context, uncond_context if cfg else None, noise, cfg_scale)
+        if seeds is not None:
+            sess.set_seeds(seeds)
+            if input_image is None:
+                sess.seed_latents()
+            else:
+                sess.add_noise_seeded(0)
+                if mask is not None:
+                    sess.set_inpaint(mask_lat, latents, seeded=True)
+        elif input_image is not None:
+            z4 = rng.normal(seed_val, 4, nl).reshape(B, 4, LH, LW)
+            sess.add_noise(0, z4)  # sampler.mojo:111-124 at timesteps[0]
+            if mask is not None:
+                sess.set_inpaint(mask_lat, latents, z4)
+        if guidance_rescale > 0.0:
+            sess.set_guidance_rescale(guidance_rescale)
+        if controlnet is not None:  # step i of n is controlled when control_start <= i / n and (i + 1) / n <= control_end, as diffusers keeps it
+            first = int(np.ceil(control_start * n - 1e-9))
+            last = int(np.floor(control_end * n + 1e-9)) - 1
+            if last >= first:
+                sess.set_control(controlnet, control_image, control_scale, control_cond_only, first, last)
+        if ip_adapter is not None:
+            first = int(np.ceil(ip_start * n - 1e-9))
+            last = int(np.floor(ip_end * n + 1e-9)) - 1
+            if last >= first and plus:
+                def hidden_rows(h, what):
+                    h = np.asarray(h, dtype=np.float32)
+                    h = np.repeat(h[None], B, axis=0) if h.ndim == 2 else h
+                    if h.ndim != 3 or h.shape[0] != B or h.shape[2] != 1280:
+                        raise ValueError(f"generate: {what} must have shape (S, 1280) or ({B}, S, 1280), got {h.shape}")
+                    return h
+                h = hidden_rows(image_encoder.forward(ip_image, hidden=True)[1] if ip_image is not None else ip_hidden, "the hidden states")
+                hu = None
+                if cfg:  # the published pipelines' resample(hidden(encoder(zeros_like(normalised pixels))))
+                    from .clip import clip_neutral_image
+                    hu = hidden_rows(ip_uncond_hidden if ip_uncond_hidden is not None else image_encoder.forward(clip_neutral_image(), hidden=True)[1],
+                                     "ip_uncond_hidden")
+                sess.set_ip_adapter(ip_adapter, ip_adapter.resample(h), ip_adapter.resample(hu) if cfg else None, ip_scale, first, last)
+            elif last >= first:
+                e = np.asarray(image_encoder.forward(ip_image) if ip_image is not None else ip_image_embeds, dtype=np.float32)
+                e = np.repeat(e[None], B, axis=0) if e.ndim == 1 else e
+                if e.shape != (B, 1024):
+                    raise ValueError(f"generate: the image embeddings must have shape (1024,) or ({B}, 1024), got {e.shape}")
+                sess.set_ip_adapter(ip_adapter, ip_adapter.project(e), ip_adapter.project(np.zeros_like(e)) if cfg else None, ip_scale, first, last)
+        for i in range(n):  # pipeline.mojo:87-122
+            sess.step(i)
+        out_lat = sess.latents()
+        if decoder is None or return_latents:
+            return out_lat
+        sess.decode()
+        return sess.images(rescale=True)
+    finally:
+        sess.close()   # on every way out: a refused argument or a failed step leaves no session behind

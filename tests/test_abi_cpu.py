@@ -19,6 +19,18 @@ def test_library_exports_every_declared_symbol(tsd_mod):
     assert lib.tsd_version() == 100
 
 
+def test_device_ledger_symbol_and_enum(tsd_mod):
+    """The ledger entry is declared, exported and bound, and the package reads its field names from the header's enum."""
+    lib = tsd_mod._lib.lib()
+    assert "tsd_debug_device_ledger" in tsd_mod._lib.declared_symbols() and hasattr(lib, "tsd_debug_device_ledger")
+    assert lib.tsd_debug_device_ledger.restype is C.c_int and len(lib.tsd_debug_device_ledger.argtypes) == 2
+    fields = tsd_mod._lib.header_enum("tsd_device_ledger_field", "TSD_DL_")
+    assert fields == {"ALLOCS_LIVE": 0, "BYTES_LIVE": 1, "EVENTS_LIVE": 2, "STREAMS_LIVE": 3, "CTX_LIVE": 4, "MODELS_LIVE": 5, "SESSIONS_LIVE": 6,
+                      "ALLOCS_TOTAL": 7, "FREES_TOTAL": 8, "FREES_UNKNOWN": 9, "RELEASE_ERRORS": 10, "COUNT": 11}
+    assert lib.tsd_debug_device_ledger((C.c_int64 * 11)(), 11) == fields["COUNT"]
+    assert set(tsd_mod.device_ledger()) == set(fields) - {"COUNT"}
+
+
 def test_param_inventory_matches_oracle_spec(tsd_mod):
     for kind, plist in (("diffusion", spec.diffusion_params()), ("decoder", spec.decoder_params()),
                         ("encoder", spec.encoder_params()), ("clip", spec.clip_params()),
