@@ -1103,6 +1103,49 @@ enum tsd_device_ledger_field {
 };
 /* debug */ int tsd_debug_device_ledger(int64_t* out, int n);
 
+/* ---- FreeU (EXTENSION: Si et al. 2023, "FreeU: Free Lunch in Diffusion U-Net"; diffusers' `enable_freeu`) on the full-size UNets
+ * (kinds 5 / 6 / 16).  In front of every decoder concat the two inputs are re-weighted in place: the backbone half of the hidden tensor
+ * is scaled up, the lowest spatial frequencies of the popped skip are scaled down.  No weights, no training.
+ * Number the decoder residual blocks j = 0 .. 11 in pop order (flat layers 22, 23, 24, 26, 28, 30, 33, 35, 37, 40, 42, 44 of the step
+ * tables); block j sees the hidden tensor h [B][H*W][Ch] and the popped skip r [B][H*W][Cr], fp16 NHWC, and a table gives it (b_j, s_j).
+ *   skip (s_j != 1; otherwise r is neither read nor written): diffusers' fourier_filter(r, threshold = 1, scale = s_j) - the four bins
+ *     (fy, fx) in {0, -1}^2 of each (sample, channel) plane's 2-D DFT times s_j - evaluated without a transform: with
+ *     cy[y] = cos(2 pi y / H), sy[y] = sin(2 pi y / H), cx / sx likewise over W, cxy = cy cx - sy sx, sxy = sy cx + cy sx,
+ *       S0 = sum r, Ay = sum r cy, By = sum r sy, Ax = sum r cx, Bx = sum r sx, Axy = sum r cxy, Bxy = sum r sxy   (over the plane)
+ *       P = (S0 + Ay cy + By sy + Ax cx + Bx sx + Axy cxy + Bxy sxy) / (H W),   r' = rn16(r + (s_j - 1) P)
+ *     fp32 sums in a fixed order, one rounding to fp16; the four tables are built on the host in double, rounded once to fp32 and kept on
+ *     the context per (H, W) (released with it).
+ *   hidden (b_j != 1; otherwise h is neither read nor written), channels c < Ch / 2 only - the other half is never written:
+ *     TSD_FREEU_CONSTANT (diffusers): h' = rn16(b_j h).
+ *     TSD_FREEU_MODULATED (the "v2" form of the authors' repository): m[p] = (1 / Ch) sum_c h[p][c] over all Ch channels, lo / hi its
+ *     per-sample minimum / maximum over the pixels, n[p] = (m[p] - lo) / (hi - lo), h' = rn16(((b_j - 1) n[p] + 1) h).  Where hi == lo,
+ *     n = 0 (h stays as it is): the published code divides by zero there - a deliberate deviation.
+ * One launch per decoder block with an active entry, one more in the modulated mode; no atomics, no synchronisation; a sample's bits do
+ * not depend on B or on its batch position.  A ControlNet's injection runs before FreeU, as in diffusers.  The GroupNorm statistics the
+ * producers of a rewritten tensor emitted are dropped: the block's first GroupNorm runs its own statistics pass.
+ * FreeU is state of the UNet MODEL: tsd_diffusion_forward_hw, _control_hw, _ip_hw, sessions and slot sessions of the model all run it.
+ * tsd_model_set_freeu: b, s fp32 [TSD_FREEU_BLOCKS]; both NULL turns it off, and so does a table of all ones: an off model enqueues
+ * exactly the launches it did before and gives the bits it gave.  It takes effect on the next forward, also the next step() / advance()
+ * of an open session, which needs no upload(): the workspace a forward needs does not depend on the table.  TSD_E_ARG: a kind other
+ * than 5 / 6 / 16 (Tiny-SD, ControlNets, adapters, encoders), a non-finite b or s, an unknown mode, exactly one of b, s NULL; the
+ * model's table stays as it was.
+ * tsd_model_freeu: 1 when a table is active, 0 when off (negative: TSD_E_ARG, a NULL model or a wrong kind); b, s ([12]) and mode are
+ * filled when not NULL - ones and TSD_FREEU_CONSTANT when off.
+ * tsd_freeu_f16: the launch alone on host fp16 tensors, synchronous: h [B][H][W][Ch], r [B][H][W][Cr] -> h_out, r_out (either pair may be
+ * NULL together: that tensor is skipped).  1 <= B <= 64, H, W >= 2, Ch a multiple of 16, Cr of 8 (TSD_E_SHAPE). */
+#define TSD_FREEU_BLOCKS 12
+enum { TSD_FREEU_CONSTANT = 0, TSD_FREEU_MODULATED = 1 };
+int tsd_model_set_freeu(tsd_model* unet, const float* b, const float* s, int mode);
+int tsd_model_freeu(tsd_model* unet, float* b, float* s, int* mode);
+int tsd_freeu_f16(tsd_ctx* ctx, const void* h, const void* r, int B, int H, int W, int Ch, int Cr, float b, float s, int mode, void* h_out,
+                  void* r_out);
+/* The same launch on operands with pitches and guard bands (test infrastructure: tests/test_gpu_freeu.py).  h / r: host fp16 buffers of
+ * guard + B * H * W * ld + guard elements (ldh >= Ch, ldr >= Cr, pitches and guard multiples of 8, guard >= 0); the launch is given the
+ * address behind the leading guard.  h_out / r_out receive the WHOLE buffers back, guards and pitch gaps included: what the launch may
+ * write is columns < Ch / 2 of h and < Cr of r, nothing else. */
+int tsd_debug_freeu_run(tsd_ctx* ctx, const void* h, const void* r, int B, int H, int W, int Ch, int Cr, int ldh, int ldr, int guard, float b,
+                        float s, int mode, void* h_out, void* r_out);
+
 /* ---- census -------------------------------------------------------------------------- */
 /* Algorithmic GFLOP (2*MAC of conv + linear + attention core) of one forward per sample
  * (SURVEY.md Appendix B): kind, latent side L, context tokens T. */

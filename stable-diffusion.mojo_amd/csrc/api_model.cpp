@@ -281,6 +281,37 @@ extern "C" int tsd_diffusion_forward_ip_hw(tsd_model* unet, tsd_model* ip, const
   });
 }
 
+// FreeU: the model's table.  Nothing on the device changes here: unet_full_steps reads the table when a forward is enqueued, and the
+// workspace a forward needs is the same with and without it (graph.cpp), so an open session's next step just runs the new graph.
+extern "C" int tsd_model_set_freeu(tsd_model* unet, const float* b, const float* s, int mode) {
+  NOTNULL(unet);
+  if (!is_full_unet_kind(unet->kind)) TSD_FAIL(TSD_E_ARG, "tsd_model_set_freeu: FreeU belongs to the full-size UNets (kinds 5, 6, 16), this model is kind %d", unet->kind);
+  if (!b != !s) TSD_FAIL(TSD_E_ARG, "tsd_model_set_freeu: b and s are given together (both NULL turns FreeU off)");
+  if (mode != TSD_FREEU_CONSTANT && mode != TSD_FREEU_MODULATED) TSD_FAIL(TSD_E_ARG, "tsd_model_set_freeu: mode %d (0 constant, 1 modulated)", mode);
+  bool on = false;
+  for (int j = 0; b && j < TSD_FREEU_BLOCKS; j++) {
+    if (!isfinite(b[j]) || !isfinite(s[j])) TSD_FAIL(TSD_E_ARG, "tsd_model_set_freeu: block %d: b = %g, s = %g must be finite", j, (double)b[j], (double)s[j]);
+    on |= b[j] != 1.f || s[j] != 1.f;
+  }
+  for (int j = 0; j < TSD_FREEU_BLOCKS; j++) {
+    unet->freeu_b[j] = on ? b[j] : 1.f;
+    unet->freeu_s[j] = on ? s[j] : 1.f;
+  }
+  unet->freeu_on = on;
+  unet->freeu_mode = on ? mode : TSD_FREEU_CONSTANT;
+  return TSD_OK;
+}
+extern "C" int tsd_model_freeu(tsd_model* unet, float* b, float* s, int* mode) {
+  NOTNULL(unet);
+  if (!is_full_unet_kind(unet->kind)) TSD_FAIL(TSD_E_ARG, "tsd_model_freeu: FreeU belongs to the full-size UNets (kinds 5, 6, 16), this model is kind %d", unet->kind);
+  for (int j = 0; j < TSD_FREEU_BLOCKS; j++) {
+    if (b) b[j] = unet->freeu_b[j];
+    if (s) s[j] = unet->freeu_s[j];
+  }
+  if (mode) *mode = unet->freeu_mode;
+  return unet->freeu_on ? 1 : 0;
+}
+
 extern "C" int tsd_decoder_forward_hw(tsd_model* m, const float* latents, int B, int LH, int LW, float* images) {
   NOTNULL(m); NOTNULL(latents); NOTNULL(images);
   if (!is_decoder_kind(m->kind)) TSD_FAIL(TSD_E_ARG, "tsd_decoder_forward: model is not a Decoder");

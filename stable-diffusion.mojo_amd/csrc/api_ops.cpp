@@ -406,6 +406,54 @@ extern "C" int tsd_ip_attn_add_f16(tsd_ctx* ctx, const void* q, const void* k_ip
   });
 }
 
+// FreeU (kernels_freeu.hip) on host fp16 tensors: the launch a decoder block with an active table entry adds (two in the modulated mode).
+// h [B][H][W][Ch], r [B][H][W][Cr]; h_out / r_out receive the tensors as the launch left them.
+extern "C" int tsd_freeu_f16(tsd_ctx* ctx, const void* h, const void* r, int B, int H, int W, int Ch, int Cr, float b, float s, int mode,
+                             void* h_out, void* r_out) {
+  NOTNULL(ctx);
+  if (!h != !h_out || !r != !r_out || (!h && !r)) TSD_FAIL(TSD_E_ARG, "freeu: h / h_out and r / r_out are given in pairs, at least one pair");
+  if (B <= 0 || B > 64 || H < 2 || W < 2 || H > 4096 || W > 4096) TSD_FAIL(TSD_E_SHAPE, "freeu: B=%d (1..64) plane %d x %d (sides 2..4096)", B, H, W);
+  if ((h && (Ch <= 0 || Ch % 16)) || (r && (Cr <= 0 || Cr % 8))) TSD_FAIL(TSD_E_SHAPE, "freeu: Ch=%d (a multiple of 16) Cr=%d (a multiple of 8)", Ch, Cr);
+  return run_op(ctx, [&]() -> int {
+    Dev dv{ctx};
+    const int64_t nh = (int64_t)B * H * W * Ch, nr = (int64_t)B * H * W * Cr;
+    FreeuOp op;
+    op.B = B; op.H = H; op.W = W; op.mode = mode;
+    if (h) { op.h = (half_t*)dv.in((const uint16_t*)h, nh); op.Ch = op.ldh = Ch; op.b = b; }
+    if (r) { op.r = (half_t*)dv.in((const uint16_t*)r, nr); op.Cr = op.ldr = Cr; op.s = s; }
+    op.mean = dv.buf<float>((int64_t)B * H * W);
+    if (dv.err) return dv.err;
+    TSD_TRY(launch_freeu(ctx, op));
+    if (h) TSD_TRY(dv.out((uint16_t*)h_out, (const uint16_t*)op.h, nh));
+    if (r) TSD_TRY(dv.out((uint16_t*)r_out, (const uint16_t*)op.r, nr));
+    return TSD_OK;
+  });
+}
+
+extern "C" int tsd_debug_freeu_run(tsd_ctx* ctx, const void* h, const void* r, int B, int H, int W, int Ch, int Cr, int ldh, int ldr, int guard,
+                                   float b, float s, int mode, void* h_out, void* r_out) {
+  NOTNULL(ctx); NOTNULL(h); NOTNULL(r); NOTNULL(h_out); NOTNULL(r_out);
+  if (B <= 0 || B > 64 || H < 2 || W < 2 || H > 4096 || W > 4096 || guard < 0 || guard % 8 || guard > (1 << 20))
+    TSD_FAIL(TSD_E_SHAPE, "freeu run: B=%d (1..64) plane %d x %d (sides 2..4096) guard %d (a multiple of 8)", B, H, W, guard);
+  if (Ch <= 0 || Ch % 16 || Cr <= 0 || Cr % 8 || ldh < Ch || ldr < Cr || ldh % 8 || ldr % 8 || ldh > 8192 || ldr > 8192)
+    TSD_FAIL(TSD_E_SHAPE, "freeu run: Ch=%d (a multiple of 16) Cr=%d (a multiple of 8) pitches %d / %d", Ch, Cr, ldh, ldr);
+  return run_op(ctx, [&]() -> int {
+    Dev dv{ctx};
+    const int64_t nh = (int64_t)B * H * W * ldh + 2 * guard, nr = (int64_t)B * H * W * ldr + 2 * guard;
+    uint16_t* dh = dv.in((const uint16_t*)h, nh);
+    uint16_t* dr = dv.in((const uint16_t*)r, nr);
+    FreeuOp op;
+    op.B = B; op.H = H; op.W = W; op.mode = mode;
+    op.h = (half_t*)dh + guard; op.Ch = Ch; op.ldh = ldh; op.b = b;
+    op.r = (half_t*)dr + guard; op.Cr = Cr; op.ldr = ldr; op.s = s;
+    op.mean = dv.buf<float>((int64_t)B * H * W);
+    if (dv.err) return dv.err;
+    TSD_TRY(launch_freeu(ctx, op));
+    TSD_TRY(dv.out((uint16_t*)h_out, (const uint16_t*)dh, nh));
+    return dv.out((uint16_t*)r_out, (const uint16_t*)dr, nr);
+  });
+}
+
 // The CLIP vision encoder's image front end (kernels_vision.hip) on host tensors: images fp32 [B][3][H][W] on 0 .. 255 -> patch rows fp16
 // [B * 256][592], the ONE launch in front of the patch-embedding GEMM.
 extern "C" int tsd_clip_image_patches_f16(tsd_ctx* ctx, const float* images, int B, int H, int W, void* patches_out) {

@@ -165,6 +165,13 @@ struct VisionTab {
   void* dev = nullptr;
 };
 
+// cos / sin tables of FreeU's four-bin filter for one plane size (kernels_freeu.hip freeu_tab builds and caches them): one device
+// allocation, float cy[H], sy[H], cx[W], sx[W].
+struct FreeuTab {
+  int H = 0, W = 0;
+  float* dev = nullptr;
+};
+
 struct tsd_ctx {
   int device = 0;
   TsdOptions opt;
@@ -198,6 +205,7 @@ struct tsd_ctx {
   AttnPlan attn_last;         // plan of the last attention-core / row-softmax launch enqueued (tsd_debug_attn_run)
   SmallLinearPlan sl_last;    // the last tiny-M linear launch enqueued (tsd_debug_elem_run)
   std::vector<VisionTab> vision_tabs;  // resize coefficient tables of the CLIP image front end, one per input size (kernels_vision.hip)
+  std::vector<FreeuTab> freeu_tabs;    // cos / sin tables of FreeU's skip filter, one per plane size (kernels_freeu.hip)
 };
 
 enum KernelClass : int {
@@ -538,6 +546,21 @@ struct ControlTable {
 };
 // scale: device fp32 [B]
 int launch_control_inject(tsd_ctx* ctx, ControlTable tab, int B, const float* scale);
+
+// ---- FreeU (kernels_freeu.hip states the formulas): in place on the two inputs of a decoder concat, h [B][H*W][ldh] (channels < Ch / 2
+// scaled by b, or by (b - 1) n[p] + 1 in the modulated mode) and r [B][H*W][ldr] (its four lowest spatial frequencies scaled by s).  b == 1
+// leaves h unread and unwritten, s == 1 leaves r so (either pointer may then be nullptr).  mean: [B][H*W] floats of scratch, read and
+// written under TSD_FREEU_MODULATED with b != 1 only.  ONE launch, one more in front of it in the modulated mode; Ch a multiple of 16, Cr
+// of 8, pitches multiples of 8, both tensors 16-byte aligned, H, W >= 2.
+struct FreeuOp {
+  half_t* h = nullptr; half_t* r = nullptr;
+  float* mean = nullptr;
+  int B = 0, H = 0, W = 0, Ch = 0, Cr = 0, ldh = 0, ldr = 0;
+  float b = 1.f, s = 1.f;
+  int mode = 0;  // TSD_FREEU_CONSTANT / TSD_FREEU_MODULATED
+};
+int launch_freeu(tsd_ctx* ctx, const FreeuOp& op);
+int freeu_tab(tsd_ctx* ctx, int H, int W, const float** dev_out);
 
 // alphas_cumprod of the scaled-linear beta schedule (sampler.mojo:28-32), fp32 like the reference's Tensor
 void sampler_alphas_cumprod(int n_train, std::vector<float>& out);

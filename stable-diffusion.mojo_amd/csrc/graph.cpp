@@ -633,6 +633,29 @@ struct FullRun {
   const IpRun* ip = nullptr;  // IP-Adapter: every attention block of the run reads its slice (the UNet only: a ControlNet's blocks never do)
 };
 
+// FreeU on the two inputs of a decoder concat, in place, just before cat2 reads them (kernels_freeu.hip; after the ControlNet injection, as
+// in diffusers).  Writing in place is safe for the reason given above unet_control_inject's call: the arena is a bump allocator within a
+// forward, so neither tensor is handed out again before the forward returns - and nobody else reads the old values: a popped skip has this
+// block as its one reader left (its encoder-side readers ran long ago), and `cur` is read by the next step only, which is this block.
+// The statistics the producers emitted (EPI_GNSTATS) describe the tensors before the rewrite: they are dropped for every tensor the
+// launch writes, so the block's first GroupNorm runs its own statistics pass (what TSD_CONTROL_STATS = 0 does after the injection).
+// The modulated mode's [B][HW] means live in the arena between a mark and a release in front of the block's output: B * HW * 4 bytes where
+// the output then takes B * HW * C * 2 at the same offset, so the forward's high-water mark - every workspace plan made with FreeU off,
+// a session's included - is the same with FreeU on.
+static int unet_freeu(tsd_ctx* ctx, Act& cur, Act& sk, int B, float b, float s, int mode) {
+  FreeuOp op;
+  op.B = B; op.H = cur.H; op.W = cur.W; op.mode = mode;
+  op.h = cur.p; op.ldh = cur.ld; op.Ch = cur.C; op.b = b;
+  op.r = sk.p; op.ldr = sk.ld; op.Cr = sk.C; op.s = s;
+  const size_t mark = ctx->arena.mark();
+  if (b != 1.f && mode == TSD_FREEU_MODULATED) { op.mean = arena_alloc<float>(ctx, (int64_t)B * cur.H * cur.W); CHECK_ALLOC(op.mean); }
+  const int rc = launch_freeu(ctx, op);
+  ctx->arena.release(mark);
+  if (b != 1.f) { cur.gn_part = nullptr; cur.gn_nslab = 0; }
+  if (s != 1.f) { sk.gn_part = nullptr; sk.gn_nslab = 0; }
+  return rc;
+}
+
 // Steps [i0, i1) of SD15_STEPS on `cur` and the skip stack: the UNet runs [0, SD15_ENC_N) and [SD15_ENC_N, SD15_N), a ControlNet the first
 // range on weights of its own.
 static int unet_full_steps(const FullRun& f, int i0, int i1, Act& cur, std::vector<Act>& skips) {
@@ -640,6 +663,8 @@ static int unet_full_steps(const FullRun& f, int i0, int i1, Act& cur, std::vect
   tsd_ctx* ctx = m->ctx;
   const UNetW& u = m->unet;
   const int B = f.B, CK = u.kproj_all.N;
+  int pops = 0;  // decoder residual blocks in front of step i0, in pop order: FreeU's block index j
+  for (int i = 0; i < i0; i++) pops += full_unet_steps(m->kind)[i].l.kind == L_RES && (full_unet_steps(m->kind)[i].flags & U_POP);
   for (int i = i0; i < i1; i++) {
     const UNetStep* steps = full_unet_steps(m->kind);  // (a ControlNet: SD15_STEPS; the tables differ in the attention blocks' head split only)
     const UNetStep& st = steps[i];
@@ -669,8 +694,11 @@ static int unet_full_steps(const FullRun& f, int i0, int i1, Act& cur, std::vect
       CatSrc src = cat1(cur);
       if (st.flags & U_POP) {
         if (skips.empty()) TSD_FAIL(TSD_E_STATE, "full-size UNet: skip stack underflow at layer %d", i + 1);
-        const Act sk = skips.back(); skips.pop_back();
+        Act sk = skips.back(); skips.pop_back();
         if (sk.H != cur.H || sk.W != cur.W || cur.C + sk.C != l.a) TSD_FAIL(TSD_E_STATE, "full-size UNet: skip mismatch at layer %d", i + 1);
+        const int j = pops++;
+        if (m->freeu_on && j < TSD_FREEU_BLOCKS && (m->freeu_b[j] != 1.f || m->freeu_s[j] != 1.f))
+          TSD_TRY(unet_freeu(ctx, cur, sk, B, m->freeu_b[j], m->freeu_s[j], m->freeu_mode));
         src = cat2(cur, sk);
       }
       y = act_alloc_gn(ctx, B, cur.H, cur.W, l.b, stat_groups(l.b)); CHECK_ALLOC(y.p);

@@ -220,6 +220,11 @@ struct tsd_model {
   // base).  tsd_model_lora_clear copies them back bit for bit; set_param drops the entry of its parameter (the new value is the new base),
   // init_random / mark_loaded drop all of them.
   std::map<int, char*> lora_base;
+  // FreeU (tsd_model_set_freeu; full-size UNets only): (b_j, s_j) of the twelve decoder residual blocks in pop order.  Read by
+  // unet_full_steps when the forward is enqueued; off (or all ones): the forward enqueues what it always did.
+  bool freeu_on = false;
+  int freeu_mode = 0;
+  float freeu_b[TSD_FREEU_BLOCKS] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1}, freeu_s[TSD_FREEU_BLOCKS] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
 };
 
 int model_resolve(tsd_model* m);                      // fill unet / vae from the packed blob

@@ -144,6 +144,7 @@ static void ctx_release(tsd_ctx* c) {
   if (c->status) (void)dev_free(c->status);
   if (c->sk_flags) (void)dev_free(c->sk_flags);
   for (VisionTab& t : c->vision_tabs) if (t.dev) (void)dev_free(t.dev);
+  for (FreeuTab& t : c->freeu_tabs) if (t.dev) (void)dev_free(t.dev);
   for (hipEvent_t e : c->prof_ev) (void)dev_event_destroy(e);
   if (c->ev0) (void)dev_event_destroy(c->ev0);
   if (c->ev1) (void)dev_event_destroy(c->ev1);

@@ -12,6 +12,7 @@
   tsd.tokenizer  <-> helpers/utils.mojo     Tokenizer, bpe_encode (host-only logic inside libtsd)
   tsd.pipeline   <-> pipeline.mojo          generate (hot loop; the context embedding is an input)
   tsd.serve      (no reference counterpart) continuous batching over a slot session: SlotScheduler, generate_stream
+  tsd.free_u     (no reference counterpart) FreeU on the full-size UNets: freeu_table, Diffusion.set_freeu, generate(freeu=...)
   tsd.lora       (no reference counterpart) LoRA adapters merged into the packed weights on the device, removable exactly
   tsd.ext        (no reference counterpart) torch-style GroupNorm / LayerNorm for real checkpoints
 
@@ -33,4 +34,5 @@ from .tokenizer import Tokenizer, process_prompt  # noqa: F401
 from .sampler import DDIMSampler, DDPMSampler, DPMSolverMultistepSampler  # noqa: F401
 from .pipeline import encode_prompts, generate  # noqa: F401
 from .serve import Request, SlotScheduler, generate_stream  # noqa: F401
+from .free_u import freeu, freeu_table  # noqa: F401
 from .lora import load_lora, lora_targets, merge_reference, read_lora  # noqa: F401

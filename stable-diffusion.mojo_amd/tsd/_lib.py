@@ -153,6 +153,9 @@ def _declare(l):
         "tsd_debug_ip_attn_run": ([vp, C.POINTER(i64), i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)], i),
         "tsd_debug_ip_attn_bench": ([vp, i, i, i, i, i, i, fp], i),
         "tsd_clip_image_patches_f16": ([vp, fp, i, i, i, vp], i),
+        "tsd_model_set_freeu": ([vp, fp, fp, i], i), "tsd_model_freeu": ([vp, fp, fp, C.POINTER(i)], i),
+        "tsd_freeu_f16": ([vp, vp, vp, i, i, i, i, i, f, f, i, vp, vp], i),
+        "tsd_debug_freeu_run": ([vp, vp, vp, i, i, i, i, i, i, i, i, f, f, i, vp, vp], i),
         "tsd_clip_vision_forward": ([vp, fp, i, i, i, fp, fp], i),
         "tsd_debug_image_patches_run": ([vp, C.POINTER(i64), i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)], i),
         "tsd_tokenizer_create": ([C.c_char_p, i, C.POINTER(vp)], i),

@@ -202,6 +202,28 @@ class Diffusion:
             return NULL_MATRIX()
         return out[0] if single else out
 
+    def set_freeu(self, b1=None, b2=None, s1=None, s2=None, convention="diffusers", modulated=False, table=None):
+        """FreeU (Si et al. 2023; diffusers' `enable_freeu(s1, s2, b1, b2)`) on a full-size variant: from the next forward on - a step of an
+        open `Session` included - every decoder concat scales the backbone half of its hidden input by b and the four lowest spatial
+        frequencies of its skip by s (`tsd_model_set_freeu`).  b1 / b2 / s1 / s2 fill the 12-entry table by `convention`
+        (`tsd.freeu_table`: "diffusers" | "channels"), or table=(b[12], s[12]) gives it directly; modulated=True is the "v2" form of the
+        authors' repository (b modulated per pixel by the min-max normalised channel mean).  A table of all ones is off."""
+        from .free_u import freeu_arguments
+        b, s, mode = freeu_arguments(b1, b2, s1, s2, convention, modulated, table)
+        check(lib().tsd_model_set_freeu(self.model.h, ptr(b), ptr(s), mode))
+
+    def clear_freeu(self):
+        check(lib().tsd_model_set_freeu(self.model.h, None, None, 0))
+
+    @property
+    def freeu(self):
+        """None when FreeU is off, else (b[12], s[12], mode) as the model holds them (`tsd_model_freeu`)."""
+        b, s, mode = np.empty(12, np.float32), np.empty(12, np.float32), C.c_int(0)
+        on = lib().tsd_model_freeu(self.model.h, ptr(b), ptr(s), C.byref(mode))
+        if on < 0:
+            check(on)
+        return (b, s, mode.value) if on else None
+
 
 def _ip_tokens_input(tokens, B):
     """Image tokens as a contiguous fp32 (B, N, 768) array, 1 <= N <= 16; (N, 768) is repeated for every sample."""

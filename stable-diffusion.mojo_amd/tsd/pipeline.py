@@ -29,7 +29,7 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
              mask_mode="any", seeds=None, guidance_rescale=0.0, prediction="epsilon", zero_terminal_snr=False, controlnet=None,
              control_image=None, control_scale=1.0, control_cond_only=False, control_start=0.0, control_end=1.0, ip_adapter=None,
              ip_image_embeds=None, ip_scale=1.0, ip_start=0.0, ip_end=1.0, ip_image=None, image_encoder=None, ip_hidden=None,
-             ip_uncond_hidden=None):
+             ip_uncond_hidden=None, freeu=None):
     """context (B,T,768); returns images (B,3,8LH,8LW) in [0,255] like pipeline.mojo:127.  L is the latent side (64: 512x512) or a pair
     (LH, LW) for a rectangular image ((96, 64): 512 wide, 768 high); where the text below says L,L the tensor is LH,LW.
 
@@ -77,7 +77,19 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
     reads, as the published plus pipelines do, the resampled hidden states of the image that normalises to zero
     (`tsd.clip_neutral_image()`, a 224x224 constant the front end does not resample; its single fma leaves a few fp16 subnormals where
     the published code has exact zeros): computed here when image_encoder is given, or passed as ip_uncond_hidden, same shapes as
-    ip_hidden."""
+    ip_hidden.
+
+    freeu, a dict of `Diffusion.set_freeu`'s keywords (dict(b1=1.5, b2=1.6, s1=0.9, s2=0.2) are the paper's SD-1.x values): the
+    model runs FreeU for this call, and holds the table it held before - or none - on every way out."""
+    from .free_u import freeu_scope
+    with freeu_scope(diffusion, freeu):
+        return _generate(**{k: v for k, v in locals().items() if k not in ("freeu", "freeu_scope")})
+
+
+def _generate(diffusion, decoder, context, uncond_context, strength, cfg, cfg_scale, inference_steps, seed_val, input_image, encoder, latents,
+              noise, num_training_steps, L, return_latents, sampler, eta, spacing, mask, mask_mode, seeds, guidance_rescale, prediction,
+              zero_terminal_snr, controlnet, control_image, control_scale, control_cond_only, control_start, control_end, ip_adapter,
+              ip_image_embeds, ip_scale, ip_start, ip_end, ip_image, image_encoder, ip_hidden, ip_uncond_hidden):
     plus = bool(getattr(ip_adapter, "is_plus", False))
     if ip_hidden is not None and (ip_image is not None or ip_image_embeds is not None):
         raise ValueError("generate: pass one of ip_image, ip_image_embeds and ip_hidden, not both")

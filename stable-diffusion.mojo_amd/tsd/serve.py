@@ -141,7 +141,7 @@ class SlotScheduler:
 
 def generate_stream(diffusion, decoder, requests, B, L, T=77, cfg=True, inference_steps=50, num_training_steps=1000, sampler="ddpm",
                     eta=0.0, spacing="leading", return_latents=False, stats=None, prediction="epsilon", zero_terminal_snr=False, controlnet=None,
-                    control_image=None, **control_keywords):
+                    control_image=None, freeu=None, **control_keywords):
     """Continuous batching of `generate`: `requests` is an iterator of `Request`s (or tuples in its field order); yields (id, image
     (3,8LH,8LW) in [0,255]) - or (id, latents) with return_latents or without a decoder - as requests finish, B at a time on the device.
     L is the latent side or a pair (LH, LW): one shape for the whole stream.
@@ -155,13 +155,23 @@ def generate_stream(diffusion, decoder, requests, B, L, T=77, cfg=True, inferenc
     Finished latents are decoded through `decoder.forward`, one image per call.  `stats`, a dict, receives advances / active_ticks / occupancy when the stream ends.
     controlnet / control_image (and generate's other control_* keywords) are refused: the stream runs on a slot session, and per-slot
     control is not supported (`generate` runs lockstep sessions and takes them).  generate's ip_adapter / ip_image_embeds / ip_scale /
-    ip_start / ip_end / ip_image / ip_hidden / ip_uncond_hidden are refused for the same reason: per-slot adapters are not supported."""
+    ip_start / ip_end / ip_image / ip_hidden / ip_uncond_hidden are refused for the same reason: per-slot adapters are not supported.
+    freeu is `generate`'s keyword: FreeU is state of the model, so of the whole stream; the model's previous table is back when the stream
+    ends, however it ends."""
     if any(k.startswith("ip_") for k in control_keywords):
         raise ValueError("generate_stream runs on a slot session, which has no IP-Adapter (per-slot adapters are not supported); use generate()")
     if controlnet is not None or control_image is not None or control_keywords:
         raise ValueError("generate_stream runs on a slot session, which has no ControlNet (per-slot control is not supported); use generate()")
+    from .free_u import freeu_scope
     from .model import Session
     from .utils import _unary
+    with freeu_scope(diffusion, freeu):
+        yield from _stream(diffusion, decoder, requests, B, L, T, cfg, inference_steps, num_training_steps, sampler, eta, spacing, return_latents,
+                           stats, prediction, zero_terminal_snr, Session, _unary)
+
+
+def _stream(diffusion, decoder, requests, B, L, T, cfg, inference_steps, num_training_steps, sampler, eta, spacing, return_latents, stats,
+            prediction, zero_terminal_snr, Session, _unary):
     sess = Session(diffusion.model, None, B, L, T, cfg=cfg)
     try:
         if (prediction, bool(zero_terminal_snr)) != ("epsilon", False):
