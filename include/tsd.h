@@ -1146,6 +1146,31 @@ int tsd_freeu_f16(tsd_ctx* ctx, const void* h, const void* r, int B, int H, int 
 int tsd_debug_freeu_run(tsd_ctx* ctx, const void* h, const void* r, int B, int H, int W, int Ch, int Cr, int ldh, int ldr, int guard, float b,
                         float s, int mode, void* h_out, void* r_out);
 
+/* ---- FP8 feed-forward (EXTENSION, opt-in): the two GEGLU linears of the attention blocks that run op by op on OCP e4m3 operands
+ * (v_mfma_f32_16x16x128_f8f6f4), per-row dynamic activation scales, per-output-channel weight scales, fp32 accumulation.
+ * Quantiser, per row of x [M][K] fp16 (pitch ld), all in fp32:
+ *     amax = max |x|    scale = amax / 448 (1 where amax == 0)    inv = 448 / amax    q[k] = e4m3_rne(clamp(x[k] * inv, -448, 448))
+ *   q is [M][Kp] bytes, Kp = K rounded up to 128, bytes K .. Kp - 1 zero.  A row holding an inf or a NaN: scale = NaN and zero bytes, so
+ *   every product with it is NaN and the non-finite latch reports it.  1 <= K <= 5120.
+ * GEMM: out[m][n] = rn16(epi(sa[m] * sw[n] * sum_k a8[m][k] w8[n][k])), a8 [M][Kp], w8 [N][Kp], N a multiple of 16; the epilogue in fp32:
+ *   + bias[n] (bias != NULL), + residual[m][n] (fp16, pitch ldr a multiple of 4; residual != NULL), and under TSD_FP8_EPI_GEGLU
+ *   out[m][j] = v[m][2j] * gelu_tanh(v[m][2j + 1]) of width N / 2 (no residual).  ldo: a multiple of 4 (2 under GEGLU).
+ * tsd_quant_rows_e4m3, tsd_fp8_gemm_f16: the launches alone on host arrays (x, residual, out fp16; q / a8 / w8 bytes), synchronous.
+ * tsd_linear_fp8_f32: tsd_linear_f32's signature; both operands are rounded to fp16 and quantised on the device, N is padded to 16 inside.
+ * tsd_model_set_ff_fp8 (Diffusion and ControlNet kinds, TSD_E_ARG otherwise): state of the MODEL, like FreeU.  On: the next
+ *   preparation quantises geglu1 / geglu2 of every attention block from the packed fp16 rows as they stand (LoRA merges included), and
+ *   every block that runs op by op (C = 640 / 1280; C = 320 where the fused tail kernel does not apply) runs LayerNorm -> quantise ->
+ *   e4m3 GEMM (GEGLU) -> quantise -> e4m3 GEMM (+ bias + residual) -> the fp16 output convolution; the residual stream never passes through
+ *   8 bits.  Setting it is a parameter change: an open session picks it up at its next upload().  Off (the default, and after turning it
+ *   off again): the launches and bits of before.  tsd_model_ff_fp8: 1 / 0, negative for a NULL model or a wrong kind. */
+enum { TSD_FP8_EPI_NONE = 0, TSD_FP8_EPI_GEGLU = 1 };
+int tsd_model_set_ff_fp8(tsd_model* m, int on);
+int tsd_model_ff_fp8(const tsd_model* m);
+int tsd_quant_rows_e4m3(tsd_ctx* ctx, const void* x_f16, int M, int K, int ld, void* q_out, float* scale_out);
+int tsd_fp8_gemm_f16(tsd_ctx* ctx, const void* a8, const float* sa, const void* w8, const float* sw, const float* bias, const void* residual,
+                     int ldr, int M, int N, int K, int epi, void* out, int ldo);
+int tsd_linear_fp8_f32(tsd_ctx* ctx, const float* x, int M, int K, const float* w, const float* bias, int N, float* y);
+
 /* ---- census -------------------------------------------------------------------------- */
 /* Algorithmic GFLOP (2*MAC of conv + linear + attention core) of one forward per sample
  * (SURVEY.md Appendix B): kind, latent side L, context tokens T. */

@@ -454,6 +454,85 @@ extern "C" int tsd_debug_freeu_run(tsd_ctx* ctx, const void* h, const void* r, i
   });
 }
 
+// ---- FP8 feed-forward (kernels_fp8.hip) on host arrays: the two launches alone, and a linear layer through both ----
+extern "C" int tsd_quant_rows_e4m3(tsd_ctx* ctx, const void* x_f16, int M, int K, int ld, void* q_out, float* scale_out) {
+  NOTNULL(ctx); NOTNULL(x_f16); NOTNULL(q_out); NOTNULL(scale_out);
+  if (M <= 0 || M > (1 << 24) || K <= 0 || K > FP8_MAX_K || ld < K || ld > (1 << 16))
+    TSD_FAIL(TSD_E_SHAPE, "quant_rows_e4m3: M=%d K=%d (1..%d) pitch %d", M, K, FP8_MAX_K, ld);
+  return run_op(ctx, [&]() -> int {
+    Dev d{ctx};
+    const int Kp = round_up(K, 128);
+    const uint16_t* dx = d.in((const uint16_t*)x_f16, (int64_t)M * ld);
+    uint8_t* dq = d.buf<uint8_t>((int64_t)M * Kp);
+    float* ds = d.buf<float>(M);
+    if (d.err) return d.err;
+    TSD_TRY(launch_quant_rows_e4m3(ctx, (const half_t*)dx, M, K, ld, dq, ds));
+    TSD_TRY(d.out((uint8_t*)q_out, (const uint8_t*)dq, (int64_t)M * Kp));
+    return d.out(scale_out, (const float*)ds, M);
+  });
+}
+
+extern "C" int tsd_fp8_gemm_f16(tsd_ctx* ctx, const void* a8, const float* sa, const void* w8, const float* sw, const float* bias,
+                                const void* residual, int ldr, int M, int N, int K, int epi, void* out, int ldo) {
+  NOTNULL(ctx); NOTNULL(a8); NOTNULL(sa); NOTNULL(w8); NOTNULL(sw); NOTNULL(out);
+  if (epi != TSD_FP8_EPI_NONE && epi != TSD_FP8_EPI_GEGLU) TSD_FAIL(TSD_E_ARG, "fp8_gemm: epilogue %d (0 none, 1 GEGLU)", epi);
+  if (M <= 0 || M > (1 << 24) || N <= 0 || N % 16 || N > (1 << 20) || K <= 0 || K > (1 << 20) || ldo <= 0 || ldo > (1 << 20) || (residual && (ldr <= 0 || ldr > (1 << 20))))
+    TSD_FAIL(TSD_E_SHAPE, "fp8_gemm: M=%d N=%d (a multiple of 16) K=%d pitches %d / %d", M, N, K, ldo, ldr);
+  return run_op(ctx, [&]() -> int {
+    Dev d{ctx};
+    const int Kp = round_up(K, 128);
+    Fp8GemmArgs g;
+    g.A8 = d.in((const uint8_t*)a8, (int64_t)M * Kp); g.sa = d.in(sa, M);
+    g.W8 = d.in((const uint8_t*)w8, (int64_t)N * Kp); g.sw = d.in(sw, N);
+    g.M = M; g.N = N; g.K = K; g.ldo = ldo;
+    if (bias) { g.bias = d.in(bias, N); g.epi |= EPI_BIAS_N; }
+    if (residual) { g.R = (const half_t*)d.in((const uint16_t*)residual, (int64_t)M * ldr); g.ldr = ldr; g.epi |= EPI_RESIDUAL; }
+    if (epi == TSD_FP8_EPI_GEGLU) g.epi |= EPI_GEGLU;
+    // the caller's output goes up first: what the launch leaves alone (the pitch gap) comes back as it was
+    uint16_t* dout = d.in((const uint16_t*)out, (int64_t)M * ldo);
+    g.out = (half_t*)dout;
+    if (d.err) return d.err;
+    TSD_TRY(launch_gemm_e4m3(ctx, g));
+    return d.out((uint16_t*)out, (const uint16_t*)dout, (int64_t)M * ldo);
+  });
+}
+
+extern "C" int tsd_linear_fp8_f32(tsd_ctx* ctx, const float* x, int M, int K, const float* w, const float* bias, int N, float* y) {
+  NOTNULL(x); NOTNULL(w); NOTNULL(y);
+  if (M <= 0 || K <= 0 || K > FP8_MAX_K || N <= 0) TSD_FAIL(TSD_E_SHAPE, "linear_fp8: bad dims M=%d K=%d (1..%d) N=%d", M, K, FP8_MAX_K, N);
+  return run_op(ctx, [&]() -> int {
+    Dev d{ctx};
+    const int Kp = round_up(K, 128), Np = round_up(N, 16);
+    float* dx = d.in(x, (int64_t)M * K);
+    float* dw = d.in(w, (int64_t)N * K);
+    half_t* x16 = d.buf<half_t>((int64_t)M * Kp);
+    half_t* w16 = d.buf<half_t>((int64_t)Np * Kp);
+    uint8_t* x8 = d.buf<uint8_t>((int64_t)M * Kp);
+    uint8_t* w8 = d.buf<uint8_t>((int64_t)Np * Kp);
+    float* sx = d.buf<float>(M);
+    float* sw = d.buf<float>(Np);
+    float* pb = d.buf<float>(Np);
+    half_t* y16 = d.buf<half_t>((int64_t)M * Np);
+    float* y32 = d.buf<float>((int64_t)M * Np);
+    if (d.err) return d.err;
+    TSD_TRY(launch_f32_to_f16_rows(ctx, dx, M, K, x16, Kp, M));
+    TSD_TRY(launch_f32_to_f16_rows(ctx, dw, N, K, w16, Kp, Np));  // rows N .. Np - 1 are zeros: scale 1, zero bytes
+    TSD_TRY(launch_quant_rows_e4m3(ctx, x16, M, K, Kp, x8, sx));
+    TSD_TRY(launch_quant_rows_e4m3(ctx, w16, Np, K, Kp, w8, sw));
+    Fp8GemmArgs g;
+    g.A8 = x8; g.sa = sx; g.W8 = w8; g.sw = sw; g.M = M; g.N = Np; g.K = K; g.out = y16; g.ldo = Np;
+    if (bias) {
+      float* db = d.in(bias, N);
+      if (d.err) return d.err;
+      TSD_TRY(launch_pack_bias(ctx, db, N, pb, Np, 0));
+      g.bias = pb; g.epi = EPI_BIAS_N;
+    }
+    TSD_TRY(launch_gemm_e4m3(ctx, g));
+    TSD_TRY(launch_f16_to_f32_rows(ctx, y16, M, Np, Np, y32));
+    return d.out2d(y, y32, M, N, Np);
+  });
+}
+
 // The CLIP vision encoder's image front end (kernels_vision.hip) on host tensors: images fp32 [B][3][H][W] on 0 .. 255 -> patch rows fp16
 // [B * 256][592], the ONE launch in front of the patch-embedding GEMM.
 extern "C" int tsd_clip_image_patches_f16(tsd_ctx* ctx, const float* images, int B, int H, int W, void* patches_out) {

@@ -562,6 +562,23 @@ struct FreeuOp {
 int launch_freeu(tsd_ctx* ctx, const FreeuOp& op);
 int freeu_tab(tsd_ctx* ctx, int H, int W, const float** dev_out);
 
+// ---- FP8 feed-forward (kernels_fp8.hip states the arithmetic): OCP e4m3 rows with one fp32 scale each, and the GEMM over them ----
+// x [M][K] fp16 (pitch ld >= K) -> q [M][round_up(K, 128)] bytes (16-byte aligned; the pad bytes are +0), scale [M].  K <= FP8_MAX_K.
+constexpr int FP8_MAX_K = 5120;
+int launch_quant_rows_e4m3(tsd_ctx* ctx, const half_t* x, int64_t M, int K, int ld, uint8_t* q, float* scale);
+// out[m][n] = rn16(epi(sa[m] sw[n] sum_k A8[m][k] W8[n][k])): A8 [M][Kp], W8 [N][Kp] e4m3 bytes, Kp = round_up(K, 128), N a multiple of 16.
+// epi: EPI_BIAS_N | EPI_RESIDUAL (R fp16, pitch ldr, a multiple of 4) | EPI_GEGLU (output width N / 2; no residual), in fp32, one rounding.
+struct Fp8GemmArgs {
+  const uint8_t* A8 = nullptr; const float* sa = nullptr;
+  const uint8_t* W8 = nullptr; const float* sw = nullptr;
+  const float* bias = nullptr;
+  const half_t* R = nullptr; int ldr = 0;
+  half_t* out = nullptr; int ldo = 0;
+  int64_t M = 0; int N = 0, K = 0;
+  int epi = 0;
+};
+int launch_gemm_e4m3(tsd_ctx* ctx, const Fp8GemmArgs& a);
+
 // alphas_cumprod of the scaled-linear beta schedule (sampler.mojo:28-32), fp32 like the reference's Tensor
 void sampler_alphas_cumprod(int n_train, std::vector<float>& out);
 // the same table (zero_terminal_snr = 0, bitwise) or its zero-terminal-SNR rescale (1; Lin et al. 2023, algorithm 1 on sqrt(abar), in
@@ -591,6 +608,15 @@ int sampler_coeffs_ex(int kind, double eta, const std::vector<float>& alphas_cum
 __device__ __forceinline__ bool nonfinite_f(float v) { return !(fabsf(v) <= 3.4028234e38f); }  // inf or NaN
 __device__ __forceinline__ void nonfinite_report(int* counter, int nbad) {
   if (nbad) atomicAdd(counter, nbad);  // rare path
+}
+// GELU (tanh form) of the GEGLU epilogues: the fp16 GEMM's (kernels_gemm.hip) and the e4m3 GEMM's (kernels_fp8.hip)
+__device__ __forceinline__ float gelu_tanh_f(float x) {
+  // 0.5 x (1 + tanh(u)) = x * sigmoid(2u) = x / (1 + 2^(-2 u log2 e)), u = sqrt(2/pi) (x + 0.044715 x^3)  (helpers/utils.mojo:1914).
+  // One v_exp_f32 + one v_rcp_f32 (1 ulp) instead of expf + an IEEE division: the GEGLU epilogue evaluates this 80 times
+  // per lane and tile, and the division sequence alone made it cost more than the K loop of the short-K GEMM it ends.
+  const float c2 = -2.f * 0.7978845608028654f * 1.4426950408889634f;
+  const float t = __builtin_amdgcn_exp2f(c2 * (x + 0.044715f * x * x * x));
+  return x * __builtin_amdgcn_rcpf(1.f + t);
 }
 int launch_encoder_sample(tsd_ctx* ctx, const float* moments_nhwc, int B, int HW, int ld, const float* noise_chw,
                           float* latents_chw);

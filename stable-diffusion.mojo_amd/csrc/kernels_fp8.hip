@@ -1,0 +1,255 @@
+// kernels_fp8.hip - the opt-in FP8 feed-forward: an OCP e4m3 row quantiser and a GEMM on v_mfma_f32_16x16x128_f8f6f4.
+//
+// k_quant_rows_e4m3: x [M][K] fp16 (pitch ld) -> q [M][Kp] e4m3 bytes, Kp = round_up(K, 128), and one fp32 scale per row.  Per row, in fp32:
+//     amax = max |x|     scale = amax / 448 (1 where amax == 0)     inv = 448 / amax
+//     q[k] = e4m3_rne(clamp(float(x[k]) * inv, -448, 448))          bytes K .. Kp - 1 are +0
+// A row that holds an inf or a NaN gets scale = NaN and bytes of zero: whatever multiplies it comes out NaN, never silently finite.
+// One wave owns one row and four waves share a workgroup (they never meet: no LDS, no barrier).  Lane l holds the 16-byte chunks
+// l, l + 64, .. of the row in registers (NI chunks: K <= 512 NI, so 5120 columns are 80 halves per lane) between the amax reduction - a
+// butterfly over the 64 lanes, exact in any order - and the conversion: ONE pass over HBM, 16-byte loads, 8-byte stores.  Packed LinW rows
+// [N][Kpad] go through the same kernel; their scales are then per output channel.
+//
+// k_gemm_e4m3: out[m][n] = rn16(epi(sa[m] * sw[n] * sum_k A8[m][k] W8[n][k])) over Kp bytes per row, fp32 accumulation.
+//   * 256 threads, a 128 x 128 output tile, K steps of 128 bytes.  The four waves own 64 x 64 each as 4 x 4 MFMA tiles: 64 accumulator
+//     registers, 8 per operand fragment.
+//   * The operands are SWAPPED into the instruction: the W rows go in as its A matrix and the activation rows as its B matrix, so
+//     accumulator r of lane l is out[m = l % 16][n = 4 (l / 16) + r].  A lane then owns four CONSECUTIVE output columns of one row: bias is
+//     one 16-byte load, the residual one 8-byte load, the store one 8-byte store, and GEGLU's interleaved (a, gate) pairs sit in one lane -
+//     no cross-lane traffic in any epilogue.
+//   * Fragment of a 16-row group: lane l supplies row l % 16, k-bytes 32 (l / 16) .. + 31 (two ds_read_b128).  Both operands use the same
+//     k map, so the sum does not depend on how the instruction numbers k inside a lane.
+//   * LDS: A and W tiles of 128 rows x 128 bytes, double-buffered: 4 x 16 KB = 64 KB.  Rows are 128 bytes, so the 16 lanes of a quarter
+//     wave reading the same chunk of 16 consecutive rows would hit two bank groups 8 times each.  The 16-byte chunk index is XOR-swizzled
+//     with (row >> 1) & 7 instead of padding the pitch (padding would leave the 64 KB): row parity picks the half of the banks, the
+//     swizzle one of 8 chunks - 16 rows, 64 banks, no conflict, for the fragment reads and for the staging writes alike.
+//   * Global -> LDS through registers: four 16-byte loads per operand and thread for tile t + 1 are issued before the MFMAs of tile t
+//     and written to the other buffer after them; one barrier per K step.  The compiler's own waits; no counted s_waitcnt.
+//   * Partial tiles: rows >= M / >= N are staged as zeros and never stored.  N is a multiple of 16, so a lane's four columns are all in
+//     or all out.  No scratch, no atomics.
+#include <math.h>
+
+#include "common.h"
+#include "lds_dma.h"
+
+typedef _Float16 h8 __attribute__((ext_vector_type(8)));
+typedef _Float16 h4 __attribute__((ext_vector_type(4)));
+typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+typedef int v8i __attribute__((ext_vector_type(8)));
+typedef int v4i __attribute__((ext_vector_type(4)));
+typedef float v4f __attribute__((ext_vector_type(4)));
+
+constexpr int Q8_THREADS = 256, Q8_ROWS = Q8_THREADS / 64;
+constexpr float E4M3_MAX = 448.f;
+
+template <int NI>
+__global__ void __launch_bounds__(Q8_THREADS) k_quant_rows_e4m3(const half_t* __restrict__ x, long long M, int K, int ld, int Kp, int vec,
+                                                                uint8_t* __restrict__ q, float* __restrict__ scale) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long long row = (long long)blockIdx.x * Q8_ROWS + wave;
+  if (row >= M) return;  // uniform for the wave; the waves of a workgroup never meet
+  const half_t* xr = x + row * ld;
+  h8 v[NI];
+  float amax = 0.f;
+  bool bad = false;
+#pragma unroll
+  for (int i = 0; i < NI; i++) {
+    const int k0 = (lane + 64 * i) * 8;
+    if (vec && k0 + 8 <= K) {
+      v[i] = *(const h8*)(xr + k0);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; j++) v[i][j] = k0 + j < K ? xr[k0 + j] : (half_t)0.f;
+    }
+#pragma unroll
+    for (int j = 0; j < 8; j++) {
+      const float a = fabsf((float)v[i][j]);
+      bad |= !(a <= 65504.f);
+      amax = fmaxf(amax, a);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o; o >>= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
+  bad = __builtin_amdgcn_ballot_w64(bad) != 0;
+  const bool flat = bad || amax == 0.f;
+  const float inv = flat ? 0.f : E4M3_MAX / amax;
+  if (lane == 0) scale[row] = bad ? __builtin_nanf("") : (amax == 0.f ? 1.f : amax / E4M3_MAX);
+  uint8_t* qr = q + row * Kp;
+#pragma unroll
+  for (int i = 0; i < NI; i++) {
+    const int k0 = (lane + 64 * i) * 8;
+    if (k0 >= Kp) continue;
+    int w[2] = {0, 0};
+    if (!bad) {
+#pragma unroll
+      for (int j = 0; j < 8; j += 2) {
+        const float f0 = fminf(fmaxf((float)v[i][j] * inv, -E4M3_MAX), E4M3_MAX);
+        const float f1 = fminf(fmaxf((float)v[i][j + 1] * inv, -E4M3_MAX), E4M3_MAX);
+        w[j >> 2] = (j & 2) ? __builtin_amdgcn_cvt_pk_fp8_f32(f0, f1, w[j >> 2], true) : __builtin_amdgcn_cvt_pk_fp8_f32(f0, f1, w[j >> 2], false);
+      }
+    }
+    *(int2*)(qr + k0) = make_int2(w[0], w[1]);
+  }
+}
+
+int launch_quant_rows_e4m3(tsd_ctx* ctx, const half_t* x, int64_t M, int K, int ld, uint8_t* q, float* scale) {
+  if (M <= 0 || M > ((int64_t)1 << 31) - 1 || K <= 0 || K > FP8_MAX_K || ld < K)
+    TSD_FAIL(TSD_E_SHAPE, "quant_rows_e4m3: M=%lld K=%d (1..%d) pitch %d", (long long)M, K, FP8_MAX_K, ld);
+  if (!ctx->launch()) return TSD_OK;
+  if (((uintptr_t)q & 15) || ((uintptr_t)scale & 3)) TSD_FAIL(TSD_E_ARG, "quant_rows_e4m3: the byte rows are not 16-byte aligned");
+  const int Kp = round_up(K, 128);
+  const int vec = !((uintptr_t)x & 15) && ld % 8 == 0;
+  const dim3 grid((unsigned)((M + Q8_ROWS - 1) / Q8_ROWS)), block(Q8_THREADS);
+  ProfScope prof(ctx, KC_ELEMENTWISE);
+  if (Kp <= 1024) hipLaunchKernelGGL(k_quant_rows_e4m3<2>, grid, block, 0, ctx->stream, x, (long long)M, K, ld, Kp, vec, q, scale);
+  else if (Kp <= 2560) hipLaunchKernelGGL(k_quant_rows_e4m3<5>, grid, block, 0, ctx->stream, x, (long long)M, K, ld, Kp, vec, q, scale);
+  else hipLaunchKernelGGL(k_quant_rows_e4m3<10>, grid, block, 0, ctx->stream, x, (long long)M, K, ld, Kp, vec, q, scale);
+  HIP_TRY(hipGetLastError());
+  return TSD_OK;
+}
+
+// ---- the GEMM ---------------------------------------------------------------------------------------------------------------------------
+constexpr int G8_THREADS = 256, G8_BM = 128, G8_BN = 128, G8_BK = 128;
+constexpr int G8_TILE = G8_BM * G8_BK;               // bytes of one operand tile (BM == BN)
+constexpr int G8_CHUNKS = G8_TILE / 16 / G8_THREADS;  // 16-byte chunks a thread stages per operand and K step: 4
+
+struct Fp8GemmK {
+  const uint8_t* A8; const uint8_t* W8;
+  const float* sa; const float* sw; const float* bias;
+  const half_t* R; half_t* out;
+  int M, N, Kp, ldr, ldo, epi;
+};
+
+// byte offset of 16-byte chunk c of row r in a swizzled tile
+__device__ __forceinline__ int g8_off(int r, int c) { return r * G8_BK + ((c ^ ((r >> 1) & 7)) << 4); }
+
+__device__ __forceinline__ v8i g8_frag(const uint8_t* tile, int r, int g) {
+  const v4i lo = *(const v4i*)(tile + g8_off(r, 2 * g)), hi = *(const v4i*)(tile + g8_off(r, 2 * g + 1));
+  v8i f;
+  f[0] = lo[0]; f[1] = lo[1]; f[2] = lo[2]; f[3] = lo[3]; f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
+  return f;
+}
+
+__global__ void __launch_bounds__(G8_THREADS) k_gemm_e4m3(Fp8GemmK p) {
+  __shared__ __attribute__((aligned(16))) uint8_t sA[2][G8_TILE];
+  __shared__ __attribute__((aligned(16))) uint8_t sW[2][G8_TILE];
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+  const int wm = wave >> 1, wn = wave & 1, lr = lane & 15, lg = lane >> 4;
+  const int n0 = blockIdx.x * G8_BN, m0 = blockIdx.y * G8_BM;
+  const int nk = p.Kp / G8_BK;
+
+  // staging map: chunk id = tid + 256 i -> tile row id / 8, 16-byte chunk id % 8; rows beyond the operand are zeros
+  const uint8_t* ga[G8_CHUNKS]; const uint8_t* gw[G8_CHUNKS];
+  int so[G8_CHUNKS];
+#pragma unroll
+  for (int i = 0; i < G8_CHUNKS; i++) {
+    const int id = tid + G8_THREADS * i, r = id >> 3, c = id & 7;
+    so[i] = g8_off(r, c);
+    ga[i] = m0 + r < p.M ? p.A8 + (int64_t)(m0 + r) * p.Kp + c * 16 : nullptr;
+    gw[i] = n0 + r < p.N ? p.W8 + (int64_t)(n0 + r) * p.Kp + c * 16 : nullptr;
+  }
+  v4i ra[G8_CHUNKS], rw[G8_CHUNKS];
+  auto fetch = [&](int kt) {
+#pragma unroll
+    for (int i = 0; i < G8_CHUNKS; i++) {
+      ra[i] = ga[i] ? *(const v4i*)(ga[i] + (int64_t)kt * G8_BK) : v4i{0, 0, 0, 0};
+      rw[i] = gw[i] ? *(const v4i*)(gw[i] + (int64_t)kt * G8_BK) : v4i{0, 0, 0, 0};
+    }
+  };
+  auto stage = [&](int buf) {
+#pragma unroll
+    for (int i = 0; i < G8_CHUNKS; i++) {
+      *(v4i*)(sA[buf] + so[i]) = ra[i];
+      *(v4i*)(sW[buf] + so[i]) = rw[i];
+    }
+  };
+
+  v4f acc[4][4];  // [jn][im]
+#pragma unroll
+  for (int j = 0; j < 4; j++)
+#pragma unroll
+    for (int i = 0; i < 4; i++) acc[j][i] = v4f{0.f, 0.f, 0.f, 0.f};
+
+  fetch(0);
+  stage(0);
+  __syncthreads();
+  for (int kt = 0; kt < nk; kt++) {
+    const int buf = kt & 1;
+    if (kt + 1 < nk) fetch(kt + 1);
+    v8i fa[4];
+#pragma unroll
+    for (int i = 0; i < 4; i++) fa[i] = g8_frag(sA[buf], wm * 64 + i * 16 + lr, lg);
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const v8i fw = g8_frag(sW[buf], wn * 64 + j * 16 + lr, lg);
+#pragma unroll
+      for (int i = 0; i < 4; i++)
+        acc[j][i] = __builtin_amdgcn_mfma_scale_f32_16x16x128_f8f6f4(fw, fa[i], acc[j][i], 0, 0, 0, 0, 0, 0);  // e4m3 x e4m3, neutral block scales
+    }
+    tsd_jitter();
+    if (kt + 1 < nk) stage(buf ^ 1);  // the other buffer: every wave left it at the barrier that ended step kt - 1
+    tsd_jitter();
+    __syncthreads();
+  }
+
+  // epilogue: lane owns out[m][n .. n + 3], m = .. + lane % 16, n = .. + 4 (lane / 16)
+  const bool geglu = p.epi & EPI_GEGLU;
+#pragma unroll
+  for (int i = 0; i < 4; i++) {
+    const int m = m0 + wm * 64 + i * 16 + lr;
+    if (m >= p.M) continue;
+    const float sam = p.sa[m];
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+      const int n = n0 + wn * 64 + j * 16 + 4 * lg;
+      if (n >= p.N) continue;
+      const v4f swn = *(const v4f*)(p.sw + n);
+      float v[4];
+#pragma unroll
+      for (int r = 0; r < 4; r++) v[r] = acc[j][i][r] * (sam * swn[r]);
+      if (p.epi & EPI_BIAS_N) {
+        const v4f b = *(const v4f*)(p.bias + n);
+#pragma unroll
+        for (int r = 0; r < 4; r++) v[r] += b[r];
+      }
+      if (p.epi & EPI_RESIDUAL) {
+        const h4 rr = *(const h4*)(p.R + (int64_t)m * p.ldr + n);
+#pragma unroll
+        for (int r = 0; r < 4; r++) v[r] += (float)rr[r];
+      }
+      if (geglu) {
+        h2 o;
+        o[0] = (half_t)(v[0] * gelu_tanh_f(v[1]));
+        o[1] = (half_t)(v[2] * gelu_tanh_f(v[3]));
+        *(h2*)(p.out + (int64_t)m * p.ldo + (n >> 1)) = o;
+      } else {
+        h4 o;
+#pragma unroll
+        for (int r = 0; r < 4; r++) o[r] = (half_t)v[r];
+        *(h4*)(p.out + (int64_t)m * p.ldo + n) = o;
+      }
+    }
+  }
+}
+
+int launch_gemm_e4m3(tsd_ctx* ctx, const Fp8GemmArgs& a) {
+  if (a.M <= 0 || a.N <= 0 || a.N % 16 || a.K <= 0 || a.M > (1 << 30) / G8_BM || a.N > 65535 * G8_BN)
+    TSD_FAIL(TSD_E_SHAPE, "gemm_e4m3: M=%lld N=%d (a multiple of 16) K=%d", (long long)a.M, a.N, a.K);
+  if (a.epi & ~(EPI_BIAS_N | EPI_RESIDUAL | EPI_GEGLU)) TSD_FAIL(TSD_E_ARG, "gemm_e4m3: epilogue %d (bias, residual, GEGLU)", a.epi);
+  if ((a.epi & EPI_GEGLU) && (a.epi & EPI_RESIDUAL)) TSD_FAIL(TSD_E_ARG, "gemm_e4m3: GEGLU takes no residual");
+  const int width = (a.epi & EPI_GEGLU) ? a.N / 2 : a.N, lda = (a.epi & EPI_GEGLU) ? 2 : 4;
+  if (a.ldo < width || a.ldo % lda) TSD_FAIL(TSD_E_SHAPE, "gemm_e4m3: output pitch %d (>= %d, a multiple of %d)", a.ldo, width, lda);
+  if ((a.epi & EPI_RESIDUAL) && (a.ldr < a.N || a.ldr % 4)) TSD_FAIL(TSD_E_SHAPE, "gemm_e4m3: residual pitch %d (>= %d, a multiple of 4)", a.ldr, a.N);
+  if (!ctx->launch()) return TSD_OK;
+  if (!a.A8 || !a.W8 || !a.sa || !a.sw || !a.out || ((a.epi & EPI_BIAS_N) && !a.bias) || ((a.epi & EPI_RESIDUAL) && !a.R))
+    TSD_FAIL(TSD_E_ARG, "gemm_e4m3: NULL operand");
+  if (((uintptr_t)a.A8 & 15) || ((uintptr_t)a.W8 & 15) || ((uintptr_t)a.sw & 15) || ((uintptr_t)a.bias & 15) || ((uintptr_t)a.R & 7) ||
+      ((uintptr_t)a.out & 7))
+    TSD_FAIL(TSD_E_ARG, "gemm_e4m3: an operand is not aligned (16 bytes: byte rows, scales, bias; 8: residual, output)");
+  Fp8GemmK k;
+  k.A8 = a.A8; k.W8 = a.W8; k.sa = a.sa; k.sw = a.sw; k.bias = a.bias; k.R = a.R; k.out = a.out;
+  k.M = (int)a.M; k.N = a.N; k.Kp = round_up(a.K, 128); k.ldr = a.ldr; k.ldo = a.ldo; k.epi = a.epi;
+  ProfScope prof(ctx, KC_GEMM, (int)a.M, a.N, k.Kp, 1);
+  hipLaunchKernelGGL(k_gemm_e4m3, dim3((unsigned)ceil_div(a.N, G8_BN), (unsigned)ceil_div((int)a.M, G8_BM)), dim3(G8_THREADS), 0, ctx->stream, k);
+  HIP_TRY(hipGetLastError());
+  return TSD_OK;
+}

@@ -153,6 +153,7 @@ static void model_invalidate_derived(tsd_model* m) {
   m->gen++;
   m->unet.res_dup_on = false; m->unet.res_dup = ResW();
   for (auto& a : m->unet.attn) { a.tail_stream = nullptr; a.head_stream = nullptr; a.fold_w = nullptr; a.fold_w_tm = nullptr; a.fold_b = nullptr; }
+  for (auto& a : m->unet.attn) { a.ff8_w1 = nullptr; a.ff8_s1 = nullptr; a.ff8_w2 = nullptr; a.ff8_s2 = nullptr; }
   m->unet.conv_in_im2col = nullptr;
   m->vae.conv_in_im2col = nullptr;
   for (auto& r : m->unet.res) { r.conv1.w_tm = nullptr; r.conv2.w_tm = nullptr; r.conv1.w_uf = nullptr; }
@@ -455,6 +456,10 @@ extern "C" int tsd_model_lora_count(tsd_model* m) {
   return (int)m->lora_base.size();
 }
 
+// bytes of a linear layer's e4m3 rows / of its per-channel scales in the derived buffer (256-byte granules)
+static size_t ff8_bytes(const LinW& l) { return ((size_t)l.N * round_up(l.Kpad, 128) + 255) & ~size_t(255); }
+static size_t ff8_scale_bytes(const LinW& l) { return ((size_t)l.N * sizeof(float) + 255) & ~size_t(255); }
+
 // derived device buffers (not part of the broadcast blob: every rank rebuilds them from the packed weights)
 static int model_build_derived(tsd_model* m) {
   tsd_ctx* ctx = m->ctx;
@@ -564,9 +569,20 @@ static int model_build_derived(tsd_model* m) {
         uf.push_back(c);
         uf_b += (((size_t)16 * c->Opad * c->Ipad * 2) + 255) & ~size_t(255);
       }
-  if (el.empty() && !cin_ok && tm.empty() && tml.empty() && !kv && fold.empty() && !dup && uf.empty()) return TSD_OK;
+  // FP8 feed-forward (tsd_model_set_ff_fp8): e4m3 rows and per-channel scales of geglu1 / geglu2 of every attention block, behind
+  // everything else in the buffer
+  std::vector<AttnW*> ff8;
+  size_t ff8_b = 0;
+  if (m->ff_fp8)
+    for (auto& a : m->unet.attn)
+      if (a.C && a.geglu1.w && a.geglu2.w && a.geglu1.N % 16 == 0 && a.geglu2.N % 16 == 0 && a.geglu1.Kpad <= FP8_MAX_K && a.geglu2.Kpad <= FP8_MAX_K) {
+        ff8.push_back(&a);
+        for (const LinW* l : {&a.geglu1, &a.geglu2}) ff8_b += ff8_bytes(*l) + ff8_scale_bytes(*l);
+      }
+  if (el.empty() && !cin_ok && tm.empty() && tml.empty() && !kv && fold.empty() && !dup && uf.empty() && ff8.empty()) return TSD_OK;
   const size_t tail_b = (attn_tail_stream_bytes() + 255) & ~size_t(255), head_b = (attn_head_stream_bytes() + 255) & ~size_t(255);
-  const size_t each = tail_b + head_b, need = each * el.size() + cin_b + tm_b + fold_b + dup_w1_b + dup_sk_b + dup_tm_b + uf_b;
+  const size_t each = tail_b + head_b, ff8_off = each * el.size() + cin_b + tm_b + fold_b + dup_w1_b + dup_sk_b + dup_tm_b + uf_b;
+  const size_t need = ff8_off + ff8_b;
   HIP_TRY(hipSetDevice(ctx->device));
   if (m->derived_bytes < need) {
     if (m->derived) HIP_TRY(dev_free(m->derived));
@@ -700,6 +716,22 @@ static int model_build_derived(tsd_model* m) {
       }
     }
   }
+  {
+    size_t off = ff8_off;
+    for (size_t i = 0; i < ff8.size() && r == TSD_OK; i++) {
+      AttnW* a = ff8[i];
+      const uint8_t* wq[2]; const float* ws[2];
+      int j = 0;
+      for (const LinW* l : {&a->geglu1, &a->geglu2}) {
+        uint8_t* q = (uint8_t*)(m->derived + off);
+        float* sc = (float*)(m->derived + off + ff8_bytes(*l));
+        off += ff8_bytes(*l) + ff8_scale_bytes(*l);
+        if (r == TSD_OK) r = launch_quant_rows_e4m3(ctx, l->w, l->N, l->Kpad, l->Kpad, q, sc);
+        wq[j] = q; ws[j] = sc; j++;
+      }
+      if (r == TSD_OK) { a->ff8_w1 = wq[0]; a->ff8_s1 = ws[0]; a->ff8_w2 = wq[1]; a->ff8_s2 = ws[1]; }
+    }
+  }
   // A folded weight is a product of two weight matrices rounded to fp16 once: one that leaves fp16 (or a non-finite bias) must not be
   // silent.  Host-side scan, once per build of the derived buffers.
   if (r == TSD_OK && !fold.empty()) {
@@ -738,6 +770,25 @@ int model_check_ready(tsd_model* m) {
   TSD_TRY(model_build_derived(m));
   m->ready = true;
   return TSD_OK;
+}
+
+// FP8 feed-forward: the switch.  A parameter change as far as everything derived is concerned: `ready` clears, the generation moves (an
+// open session re-plans at its next upload()), the plans go; the e4m3 copies are built - or not - by the next model_check_ready().
+extern "C" int tsd_model_set_ff_fp8(tsd_model* m, int on) {
+  if (!m) TSD_FAIL(TSD_E_ARG, "tsd_model_set_ff_fp8: NULL model");
+  if (!is_diffusion_kind(m->kind) && !is_controlnet_kind(m->kind))
+    TSD_FAIL(TSD_E_ARG, "tsd_model_set_ff_fp8: the FP8 feed-forward belongs to the UNets and ControlNets, this model is kind %d", m->kind);
+  if (on != 0 && on != 1) TSD_FAIL(TSD_E_ARG, "tsd_model_set_ff_fp8: on = %d (0 or 1)", on);
+  m->ff_fp8 = on != 0;
+  m->plans.clear();
+  model_invalidate_derived(m);
+  return TSD_OK;
+}
+extern "C" int tsd_model_ff_fp8(const tsd_model* m) {
+  if (!m) TSD_FAIL(TSD_E_ARG, "tsd_model_ff_fp8: NULL model");
+  if (!is_diffusion_kind(m->kind) && !is_controlnet_kind(m->kind))
+    TSD_FAIL(TSD_E_ARG, "tsd_model_ff_fp8: the FP8 feed-forward belongs to the UNets and ControlNets, this model is kind %d", m->kind);
+  return m->ff_fp8 ? 1 : 0;
 }
 
 extern "C" int tsd_model_prepare(tsd_model* m) {

@@ -112,6 +112,11 @@ struct AttnW {  // Unet_Attention_Block, diffusion.mojo:87-98
   // derived, blocks that run op by op (C = 640 / 1280): `conv_out(geglu2(h) + r) + x` (diffusion.mojo:143-146) is linear in [h | r], so the two
   // GEMMs run as ONE over the channel concat with folded weights [C][4C + C] (row-major and K-tile-major) and bias conv_out.w . geglu2.b + conv_out.b
   const half_t* fold_w = nullptr; const half_t* fold_w_tm = nullptr; const float* fold_b = nullptr;
+  // derived, under tsd_model_set_ff_fp8 only (nullptr otherwise): geglu1 / geglu2 as OCP e4m3 rows [N][round_up(Kpad, 128)] with one fp32
+  // scale per output channel, quantised from the packed fp16 rows (GEGLU interleave included) by k_quant_rows_e4m3.  Present, the op-by-op
+  // tail of the block runs its feed-forward on k_gemm_e4m3 (graph.cpp g_unet_attn) and does not take the fold_w shortcut.
+  const uint8_t* ff8_w1 = nullptr; const float* ff8_s1 = nullptr;
+  const uint8_t* ff8_w2 = nullptr; const float* ff8_s2 = nullptr;
 };
 // true when the fused tail kernel can run this block's weights (reference norms, tanh GELU, C = 8 x 40)
 bool attn_tail_weights_ok(const AttnW& w);
@@ -224,6 +229,8 @@ struct tsd_model {
   // unet_full_steps when the forward is enqueued; off (or all ones): the forward enqueues what it always did.
   bool freeu_on = false;
   int freeu_mode = 0;
+  // FP8 feed-forward (tsd_model_set_ff_fp8; Diffusion and ControlNet kinds): read by model_build_derived, which fills AttnW::ff8_*
+  bool ff_fp8 = false;
   float freeu_b[TSD_FREEU_BLOCKS] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1}, freeu_s[TSD_FREEU_BLOCKS] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
 };
 

@@ -224,6 +224,19 @@ class Diffusion:
             check(on)
         return (b, s, mode.value) if on else None
 
+    def set_ff_fp8(self, on=True):
+        """The opt-in FP8 feed-forward (`tsd_model_set_ff_fp8`): the GEGLU linears of the attention blocks that run op by op run on e4m3
+        operands - per-row activation scales, per-channel weight scales, fp32 accumulation.  A parameter change: an open `Session`
+        picks it up at its next `upload()`.  Off gives the bits of a model that never had it on."""
+        check(lib().tsd_model_set_ff_fp8(self.model.h, 1 if on else 0))
+
+    @property
+    def ff_fp8(self):
+        on = lib().tsd_model_ff_fp8(self.model.h)
+        if on < 0:
+            check(on)
+        return bool(on)
+
 
 def _ip_tokens_input(tokens, B):
     """Image tokens as a contiguous fp32 (B, N, 768) array, 1 <= N <= 16; (N, 768) is repeated for every sample."""
@@ -348,6 +361,19 @@ class ControlNet:
         self.model = Model(variant, ctx=ctx, seed=None if params is not None else seed)
         if params is not None:
             self.model.load_params(params)
+
+    def set_ff_fp8(self, on=True):
+        """The opt-in FP8 feed-forward (`tsd_model_set_ff_fp8`): the GEGLU linears of the attention blocks that run op by op run on e4m3
+        operands - per-row activation scales, per-channel weight scales, fp32 accumulation.  A parameter change: an open `Session`
+        picks it up at its next `upload()`.  Off gives the bits of a model that never had it on."""
+        check(lib().tsd_model_set_ff_fp8(self.model.h, 1 if on else 0))
+
+    @property
+    def ff_fp8(self):
+        on = lib().tsd_model_ff_fp8(self.model.h)
+        if on < 0:
+            check(on)
+        return bool(on)
 
     def hint(self, hint):
         """The hint encoder alone (`tsd_controlnet_hint_hw`): (3,8LH,8LW) or (B,3,8LH,8LW) -> features (320,LH,LW) / (B,320,LH,LW).

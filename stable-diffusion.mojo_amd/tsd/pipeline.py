@@ -29,7 +29,7 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
              mask_mode="any", seeds=None, guidance_rescale=0.0, prediction="epsilon", zero_terminal_snr=False, controlnet=None,
              control_image=None, control_scale=1.0, control_cond_only=False, control_start=0.0, control_end=1.0, ip_adapter=None,
              ip_image_embeds=None, ip_scale=1.0, ip_start=0.0, ip_end=1.0, ip_image=None, image_encoder=None, ip_hidden=None,
-             ip_uncond_hidden=None, freeu=None):
+             ip_uncond_hidden=None, freeu=None, ff_fp8=None):
     """context (B,T,768); returns images (B,3,8LH,8LW) in [0,255] like pipeline.mojo:127.  L is the latent side (64: 512x512) or a pair
     (LH, LW) for a rectangular image ((96, 64): 512 wide, 768 high); where the text below says L,L the tensor is LH,LW.
 
@@ -80,10 +80,14 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
     ip_hidden.
 
     freeu, a dict of `Diffusion.set_freeu`'s keywords (dict(b1=1.5, b2=1.6, s1=0.9, s2=0.2) are the paper's SD-1.x values): the
-    model runs FreeU for this call, and holds the table it held before - or none - on every way out."""
+    model runs FreeU for this call, and holds the table it held before - or none - on every way out.
+
+    ff_fp8=True: the model runs its GEGLU feed-forwards on e4m3 operands for this call (`Diffusion.set_ff_fp8`); None leaves the
+    model's setting alone, and the setting it had is back on every way out."""
+    from .fp8 import ff_fp8_scope
     from .free_u import freeu_scope
-    with freeu_scope(diffusion, freeu):
-        return _generate(**{k: v for k, v in locals().items() if k not in ("freeu", "freeu_scope")})
+    with freeu_scope(diffusion, freeu), ff_fp8_scope(diffusion, ff_fp8):
+        return _generate(**{k: v for k, v in locals().items() if k not in ("freeu", "freeu_scope", "ff_fp8", "ff_fp8_scope")})
 
 
 def _generate(diffusion, decoder, context, uncond_context, strength, cfg, cfg_scale, inference_steps, seed_val, input_image, encoder, latents,
