@@ -775,7 +775,9 @@ int tsd_debug_scribble(tsd_ctx* ctx, int byte);
  * finite check and no effect on the session's state.  Synchronises. */
 int tsd_debug_session_latents(tsd_session* s, float* latents);
 /* A/B switch for the fused attention-block kernels of the 64x64 level (kernels_chain.hip): 0 = op-by-op graph, 1 = fused
- * (default; TSD_CHAIN=0 in the environment has the same effect).  Returns the previous setting. */
+ * (default; TSD_CHAIN=0 in the environment has the same effect), 2 = fused for the torch-norm blocks as well
+ * (TSD_MODEL_DIFFUSION_SD15_TORCH and its ControlNet: attn_chain_kernel<KIND_HEAD_T> / <KIND_TAIL_T>; TSD_CHAIN=2).  Any other non-zero value
+ * means 1.  Returns the previous setting. */
 int tsd_debug_set_fused_attention(tsd_ctx* ctx, int on);
 /* Time one GEMM (conv = 0: M = B*H*W, K = Cin) or conv3x3 problem on synthetic device data with tile
  * configuration `cfg` (< 0: dispatcher's choice); average ms per launch over `iters` launches. */
@@ -959,6 +961,16 @@ enum tsd_chain_info { TSD_CI_CHANGED = 0, TSD_CI_RAN, TSD_CI_COUNT };
  * returned even when the launch is refused (its status is the return value). */
 int tsd_debug_chain_run(tsd_ctx* ctx, const int64_t* desc, int n, const void* const* host_in, void* const* host_out, int64_t* ext,
                         int64_t* info);
+/* The same launch through the torch-norm kernels (attn_chain_kernel<KIND_HEAD_T> / <KIND_TAIL_T>: per-channel GroupNorm / LayerNorm affine,
+ * LayerNorm rstd = rsqrt(var + eps), exact GELU); the context must be at tsd_debug_set_fused_attention(ctx, 2), otherwise the launchers
+ * refuse.  desc, n, host_in, host_out and ext are tsd_debug_chain_run's, unchanged; info receives n_info >= TSD_CI_COUNT fields, RAN = 2
+ * when the torch-norm kernel was launched.  affine_in: TSD_CA_COUNT vectors of 320 fp32 (gamma, beta of the head's GroupNorm and
+ * LayerNorm 0, of the tail's LayerNorm 1 and 2); the vectors of the other mode may be NULL.  flags: TSD_CAF_REF_RSTD keeps the
+ * LayerNorms at 1 / (sigma + eps), so that gamma = 1, beta = 0 gives the head exactly tsd_debug_chain_run's arithmetic. */
+enum tsd_chain_affine { TSD_CA_GN_W = 0, TSD_CA_GN_B, TSD_CA_LN0_W, TSD_CA_LN0_B, TSD_CA_LN1_W, TSD_CA_LN1_B, TSD_CA_LN2_W, TSD_CA_LN2_B, TSD_CA_COUNT };
+#define TSD_CAF_REF_RSTD 1
+int tsd_debug_chain_run_affine(tsd_ctx* ctx, const int64_t* desc, int n, const void* const* host_in, void* const* host_out, int64_t* ext,
+                               int64_t* info, int n_info, const float* const* affine_in, int flags);
 /* ---- elementwise / layout / packing launch descriptors (test infrastructure: tests/elem_ref.py holds the time path, the activations,
  * the boundary conversions and the packers of csrc/kernels_elementwise.hip to an fp64 reference, element-wise) ----
  * One descriptor is one launch of the launch_* function its MODE names; the other fields are that function's arguments (unused ones 0).

@@ -631,10 +631,10 @@ int cd_extents(const int64_t* d, int64_t* e) {
 #undef CD_REQ
   return TSD_OK;
 }
-}  // namespace
-
-extern "C" int tsd_debug_chain_run(tsd_ctx* ctx, const int64_t* desc, int n, const void* const* host_in, void* const* host_out,
-                                   int64_t* ext, int64_t* info) {
+// Both chain entries.  affine != nullptr: the torch-norm kernels (KIND_HEAD_T / KIND_TAIL_T) with the eight gamma / beta vectors as further
+// guarded inputs; the descriptor, the operand slots and the weight streams are the same.
+int chain_run(tsd_ctx* ctx, const int64_t* desc, int n, const void* const* host_in, void* const* host_out, int64_t* ext, int64_t* info,
+              const float* const* affine, int flags) {
   NOTNULL(desc); NOTNULL(ext);
   TSD_TRY(check_fields("chain_run", n, TSD_CD_COUNT));
   TSD_TRY(cd_extents(desc, ext));
@@ -646,10 +646,18 @@ extern "C" int tsd_debug_chain_run(tsd_ctx* ctx, const int64_t* desc, int n, con
   HIP_TRY(hipSetDevice(ctx->device));
   const bool tail = d[TSD_CD_MODE] == TSD_CM_TAIL;
   const int64_t B = d[TSD_CD_B], S = d[TSD_CD_S], M = B * S, C = d[TSD_CD_C];
-  enum { W_STREAM = TSD_CO_COUNT, SLOTS };  // the packed weight stream the model path would have made: an input like the others
+  enum { W_STREAM = TSD_CO_COUNT, AFFINE0, SLOTS = AFFINE0 + TSD_CA_COUNT };  // the packed weight stream the model path would have made: an input like the others
   GuardedOperands ops(ctx, SLOTS);
   for (int s = 0; s < TSD_CO_OUT; s++)
     if (ext[s]) TSD_TRY(ops.add(s, ext[s], cd_elem_bytes(s), host_in[s]));
+  if (affine) {  // the vectors of the described mode must be there; those of the other mode are not looked at
+    for (int v : {TSD_CA_GN_W, TSD_CA_GN_B, TSD_CA_LN0_W, TSD_CA_LN0_B, TSD_CA_LN1_W, TSD_CA_LN1_B, TSD_CA_LN2_W, TSD_CA_LN2_B}) {
+      if ((v >= TSD_CA_LN1_W) != tail) continue;
+      if (!affine[v]) TSD_FAIL(TSD_E_ARG, "chain_run_affine: affine vector %d is NULL", v);
+      TSD_TRY(ops.add(AFFINE0 + v, 320, 4, affine[v]));
+    }
+  }
+  auto av = [&](int v) { return (const float*)ops.at(AFFINE0 + v); };
   const replay::Box logical[] = {{1, 0, M, d[TSD_CD_LD_OUT], C},
                                  replay::Box::dense(ext[TSD_CO_GN_PART]),
                                  {1, 0, M, d[TSD_CD_LD_TOK], C},
@@ -684,6 +692,10 @@ extern "C" int tsd_debug_chain_run(tsd_ctx* ctx, const int64_t* desc, int n, con
         a.C = (int)C; a.d = (int)d[TSD_CD_D]; a.heads = (int)d[TSD_CD_HEADS]; a.T = (int)d[TSD_CD_T]; a.S = (int)S; a.M = M;
         a.scale = f32_of(d[TSD_CD_SCALE]); a.eps = f32_of(d[TSD_CD_EPS]);
         if (d[TSD_CD_GN]) { a.gn_part = (float*)ops.at(TSD_CO_GN_PART); a.gn_nslab = (int)(S / 32); }
+        if (affine) {
+          a.torch = 1; a.ref_rstd = flags & TSD_CAF_REF_RSTD ? 1 : 0;
+          a.ln1_w = av(TSD_CA_LN1_W); a.ln1_b = av(TSD_CA_LN1_B); a.ln2_w = av(TSD_CA_LN2_W); a.ln2_b = av(TSD_CA_LN2_B);
+        }
         TSD_TRY(launch_attn_tail(ctx, a));
       } else {
         // launch_attn_head takes no width: its callers ask attn_tail_supported first (g_unet_attn), and so does this one
@@ -694,15 +706,34 @@ extern "C" int tsd_debug_chain_run(tsd_ctx* ctx, const int64_t* desc, int n, con
         a.tok = (half_t*)ops.at(TSD_CO_HTOK); a.ld_tok = (int)d[TSD_CD_LD_TOK]; a.qk = (half_t*)ops.at(TSD_CO_QK); a.ld_qk = (int)d[TSD_CD_LD_QK];
         a.vt = (half_t*)ops.at(TSD_CO_HVT); a.ld_vt = (int)d[TSD_CD_LD_VT]; a.s_vt = d[TSD_CD_S_VT];
         a.M = M; a.S = (int)S; a.eps = f32_of(d[TSD_CD_EPS]);
+        if (affine) {
+          a.torch = 1; a.ref_rstd = flags & TSD_CAF_REF_RSTD ? 1 : 0;
+          a.gn_w = av(TSD_CA_GN_W); a.gn_b = av(TSD_CA_GN_B); a.ln0_w = av(TSD_CA_LN0_W); a.ln0_b = av(TSD_CA_LN0_B);
+        }
         TSD_TRY(launch_attn_head(ctx, a));
       }
       ran = ctx->launch();
       return TSD_OK;
     });
   HIP_TRY(hipStreamSynchronize(ctx->stream));
-  info[TSD_CI_RAN] = ran ? 1 : 0;
+  info[TSD_CI_RAN] = ran ? (affine ? 2 : 1) : 0;
   TSD_TRY(ops.read_back(&info[TSD_CI_CHANGED]));
   return r;
+}
+}  // namespace
+
+extern "C" int tsd_debug_chain_run(tsd_ctx* ctx, const int64_t* desc, int n, const void* const* host_in, void* const* host_out,
+                                   int64_t* ext, int64_t* info) {
+  return chain_run(ctx, desc, n, host_in, host_out, ext, info, nullptr, 0);
+}
+
+extern "C" int tsd_debug_chain_run_affine(tsd_ctx* ctx, const int64_t* desc, int n, const void* const* host_in, void* const* host_out,
+                                          int64_t* ext, int64_t* info, int n_info, const float* const* affine_in, int flags) {
+  if (info && n_info < TSD_CI_COUNT) TSD_FAIL(TSD_E_ARG, "chain_run_affine: info holds %d fields, %d are written", n_info, (int)TSD_CI_COUNT);
+  if (flags & ~TSD_CAF_REF_RSTD) TSD_FAIL(TSD_E_ARG, "chain_run_affine: unknown flags 0x%x", flags);
+  if (host_in) NOTNULL(affine_in);
+  static const float* const none[TSD_CA_COUNT] = {};
+  return chain_run(ctx, desc, n, host_in, host_out, ext, info, affine_in ? affine_in : none, flags);
 }
 
 // ---- time path / activations / layout conversions / packers on caller operands (tests/elem_ref.py holds each to an fp64 reference) ----

@@ -72,7 +72,7 @@ struct TsdOptions {
   int res_fuse_skip = 1;   // TSD_RES_FUSE_SKIP: residual block's 1x1 skip convolution as extra K of its second 3x3 convolution
   int gn_composite = 1;    // TSD_GN_COMPOSITE: GroupNorm over a channel concat from the two producers' partial statistics
   int conv_in_im2col = 1;  // TSD_CONV_IN_IM2COL: the 4-channel input convolution as one im2col K tile
-  int chain = 1;           // TSD_CHAIN: fused head / tail kernels of the 64x64-level attention blocks
+  int chain = 1;           // TSD_CHAIN: fused head / tail kernels of the 64x64-level attention blocks (2: for torch-norm blocks as well)
   int fold_out = 1;        // TSD_FOLD_OUT: op-by-op attention blocks (C = 640 / 1280): GEGLU's second linear + the output 1x1 conv as one GEMM over [h | r]
   int ups_fold = 1;        // TSD_UPS_FOLD: conv1 of the residual blocks behind a nearest-2x upsample as four 2x2 parity convolutions on folded weights (ConvW::w_uf): K = 4 Cin instead of 9 Cin
   int fold_dup = 1;        // TSD_FOLD_DUP: layer 10's concat(x, x) folded into its conv1 / skip weights (UNetW::res_dup): a 1280 -> 1280 block instead of 2560 -> 1280
@@ -618,6 +618,15 @@ __device__ __forceinline__ float gelu_tanh_f(float x) {
   const float t = __builtin_amdgcn_exp2f(c2 * (x + 0.044715f * x * x * x));
   return x * __builtin_amdgcn_rcpf(1.f + t);
 }
+// exact GELU 0.5 x (1 + erf(x / sqrt 2)), erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7): the ONE evaluation of k_geglu_erf, k_gelu_erf_f16
+// (kernels_elementwise.hip) and the torch-norm fused tail (kernels_chain.hip), so that the fused and op-by-op activations agree to rounding
+__device__ __forceinline__ float gelu_erf_f(float x) {
+  const float z = fabsf(x) * 0.7071067811865476f;
+  const float t = __builtin_amdgcn_rcpf(1.f + 0.3275911f * z);
+  const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
+  const float erf_abs = 1.f - poly * __builtin_amdgcn_exp2f(-1.4426950408889634f * z * z);
+  return 0.5f * x * (1.f + copysignf(erf_abs, x));
+}
 int launch_encoder_sample(tsd_ctx* ctx, const float* moments_nhwc, int B, int HW, int ld, const float* noise_chw,
                           float* latents_chw);
 
@@ -686,6 +695,10 @@ struct AttnTailArgs {
   int C = 0, d = 0, heads = 0, T = 0, S = 0; int64_t M = 0;
   float scale = 1.f, eps = 1e-5f;
   float* gn_part = nullptr; int gn_nslab = 0;  // GroupNorm(32) statistics of the output, one slab per 32 rows
+  // torch != 0: the torch-norm kernel (attn_chain_kernel<KIND_TAIL_T>; needs TsdOptions::chain == 2): gamma / beta of LayerNorm 1 and 2 ([C] fp32),
+  // rsqrt(var + eps) and the exact GELU.  ref_rstd = 1 keeps the reference's 1 / (sigma + eps) (the replay entry's comparison with the plain kernel).
+  int torch = 0, ref_rstd = 0;
+  const float *ln1_w = nullptr, *ln1_b = nullptr, *ln2_w = nullptr, *ln2_b = nullptr;
 };
 bool attn_tail_supported(const tsd_ctx* ctx, int C, int d, int heads, int T, int64_t M, int S);
 int launch_attn_tail(tsd_ctx* ctx, const AttnTailArgs& a);
@@ -701,14 +714,19 @@ struct AttnHeadArgs {
   half_t* qk = nullptr; int ld_qk = 0;              // [M][2C]: q | k
   half_t* vt = nullptr; int ld_vt = 0; int64_t s_vt = 0;  // [B][C][ld_vt]
   int64_t M = 0; int S = 0; float eps = 1e-5f;
+  // torch != 0: attn_chain_kernel<KIND_HEAD_T> - GroupNorm gamma / beta on top of the given statistics, LayerNorm 0 gamma / beta ([C] fp32 each)
+  int torch = 0, ref_rstd = 0;
+  const float *gn_w = nullptr, *gn_b = nullptr, *ln0_w = nullptr, *ln0_b = nullptr;
 };
 size_t attn_head_stream_bytes();
 int launch_attn_head_pack(tsd_ctx* ctx, const half_t* Wc, int ld_c, const half_t* Win, int ld_in, half_t* dst);
 int launch_attn_head(tsd_ctx* ctx, const AttnHeadArgs& a);
 // finish GroupNorm statistics from producer-emitted partials [B][nslab][groups][2] -> stats [B][groups][2] (mean, gamma/(sigma+eps))
-int launch_gn_stats(tsd_ctx* ctx, const half_t* x, int ld, int B, int HW, int C, int groups, float eps, float gamma, float* stats);
+// torch_rstd: gamma / sqrt(var + eps) instead (NormAffine::torch_rstd)
+int launch_gn_stats(tsd_ctx* ctx, const half_t* x, int ld, int B, int HW, int C, int groups, float eps, float gamma, float* stats,
+                    int torch_rstd = 0);
 int launch_gn_finalize(tsd_ctx* ctx, const float* partial, int nslab, int B, int HW, int C, int groups, float eps, float gamma,
-                       float* stats);
+                       float* stats, int torch_rstd = 0);
 int launch_attn_tail_pack(tsd_ctx* ctx, const half_t* Wso, int ld_so, const half_t* Wq, int ld_q, const half_t* Wco, int ld_co,
                           const half_t* W1, int ld_1, const half_t* W2, int ld_2, const half_t* Wout, int ld_out, half_t* dst);
 int launch_flash_attention(tsd_ctx* ctx, const AttnArgs& a);

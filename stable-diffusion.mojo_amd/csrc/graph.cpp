@@ -209,7 +209,9 @@ int g_unet_attn(tsd_ctx* ctx, const Act& x, const AttnW& w, const half_t* ctx16,
   // the GroupNorm statistics are known (the producer's epilogue emitted them): one kernel at the 64x64 level.
   const half_t* head_stream = w.head_stream;
   // an IP-Adapter block runs op by op: its launch sits between the cross-attention core and out_proj, inside what the tail kernel fuses
-  const bool head_ok = !ipkv && Sp == S && x.ld % 8 == 0 && attn_tail_supported(ctx, C, d, Hh, 1, M, S) && attn_head_weights_ok(w);
+  const int head_kind = attn_head_weights_ok(w), tail_kind = attn_tail_weights_ok(w);  // torch-norm blocks: under TSD_CHAIN=2 only
+  const bool head_ok = !ipkv && Sp == S && x.ld % 8 == 0 && attn_tail_supported(ctx, C, d, Hh, 1, M, S) &&
+                       (head_kind == ATTN_FUSE_PLAIN || (head_kind == ATTN_FUSE_TORCH && ctx->opt.chain >= 2));
   if (head_ok && !head_stream && !pre) {  // block-level entry: no model, pack on the fly
     half_t* hs = arena_alloc<half_t>(ctx, (int64_t)attn_head_stream_bytes() / 2); CHECK_ALLOC(hs);
     TSD_TRY(launch_attn_head_pack(ctx, w.conv_in.w, w.conv_in.Ipad, w.sa_in.w, w.sa_in.Kpad, hs));
@@ -217,9 +219,11 @@ int g_unet_attn(tsd_ctx* ctx, const Act& x, const AttnW& w, const half_t* ctx16,
   }
   if (head_ok && head_stream) {
     float* st = arena_alloc<float>(ctx, (int64_t)B * 32 * 2); CHECK_ALLOC(st);
-    if (x_stats) TSD_TRY(launch_gn_finalize(ctx, x.gn_part, x.gn_nslab, B, S, C, 32, 1e-6f, 1.f, st));  // :89
-    else TSD_TRY(launch_gn_stats(ctx, x.p, x.ld, B, S, C, 32, 1e-6f, 1.f, st));  // no producer statistics: one read of x
+    const int trs = head_kind == ATTN_FUSE_TORCH ? w.gn.torch_rstd : 0;  // eps 1e-6 either way, as launch_groupnorm below is given it
+    if (x_stats) TSD_TRY(launch_gn_finalize(ctx, x.gn_part, x.gn_nslab, B, S, C, 32, 1e-6f, 1.f, st, trs));  // :89
+    else TSD_TRY(launch_gn_stats(ctx, x.p, x.ld, B, S, C, 32, 1e-6f, 1.f, st, trs));  // no producer statistics: one read of x
     AttnHeadArgs ha;
+    if (head_kind == ATTN_FUSE_TORCH) { ha.torch = 1; ha.gn_w = w.gn.w; ha.gn_b = w.gn.b; ha.ln0_w = w.ln[0].w; ha.ln0_b = w.ln[0].b; }
     ha.x = x.p; ha.ld_x = x.ld; ha.gn_stats = st; ha.wstream = head_stream; ha.b_in = w.conv_in.b;
     ha.tok = tok; ha.ld_tok = C; ha.qk = qk; ha.ld_qk = 2 * C; ha.vt = vt; ha.ld_vt = Sp; ha.s_vt = (int64_t)C * Sp;
     ha.M = M; ha.S = S; ha.eps = 1e-5f;
@@ -282,11 +286,12 @@ int g_unet_attn(tsd_ctx* ctx, const Act& x, const AttnW& w, const half_t* ctx16,
     TSD_TRY(launch_gemm(ctx, v));
   }
   // Everything after the self-attention core is local to a token row: at the 64x64 level (C = 320) it runs as ONE kernel
-  // (kernels_chain.hip) instead of nine launches.  Reference norms / tanh-GELU only (the torch-norm extension keeps the
-  // op-by-op path).
+  // (kernels_chain.hip) instead of nine launches.  Reference norms / tanh-GELU by default; the torch-norm extension has kernels of its
+  // own (KIND_HEAD_T / KIND_TAIL_T) that TSD_CHAIN=2 switches on, and keeps the op-by-op path otherwise.
   // The block-level entry (no model) packs the stream into the workspace on the fly.
   const half_t* tail_stream = w.tail_stream;
-  const bool tail_ok = !ipkv && attn_tail_supported(ctx, C, d, Hh, T, M, S) && attn_tail_weights_ok(w);
+  const bool tail_ok = !ipkv && attn_tail_supported(ctx, C, d, Hh, T, M, S) &&
+                       (tail_kind == ATTN_FUSE_PLAIN || (tail_kind == ATTN_FUSE_TORCH && ctx->opt.chain >= 2));
   if (tail_ok && !tail_stream && !pre) {
     half_t* ts = arena_alloc<half_t>(ctx, (int64_t)attn_tail_stream_bytes() / 2); CHECK_ALLOC(ts);
     TSD_TRY(launch_attn_tail_pack(ctx, w.sa_out.w, w.sa_out.Kpad, w.ca_q.w, w.ca_q.Kpad, w.ca_out.w, w.ca_out.Kpad, w.geglu1.w,
@@ -297,6 +302,7 @@ int g_unet_attn(tsd_ctx* ctx, const Act& x, const AttnW& w, const half_t* ctx16,
     AttnTailArgs ta;
     ta.ao = ao; ta.ld_ao = C; ta.tok = tok; ta.ld_tok = C; ta.x = x.p; ta.ld_x = x.ld; ta.out = out.p; ta.ld_out = out.ld;
     ta.wstream = tail_stream;
+    if (tail_kind == ATTN_FUSE_TORCH) { ta.torch = 1; ta.ln1_w = w.ln[1].w; ta.ln1_b = w.ln[1].b; ta.ln2_w = w.ln[2].w; ta.ln2_b = w.ln[2].b; }
     ta.bso = w.sa_out.b; ta.bco = w.ca_out.b; ta.b1 = w.geglu1.b; ta.b2 = w.geglu2.b; ta.bout = w.conv_out.b;
     ta.Kc = kv.K; ta.ldk = kv.ldk; ta.sK = kv.sK; ta.Vt = kv.Vt; ta.ldvt = kv.ldvt; ta.sVt = kv.sVt;
     ta.C = C; ta.d = d; ta.heads = Hh; ta.T = T; ta.S = S; ta.M = M; ta.scale = scale; ta.eps = 1e-5f;

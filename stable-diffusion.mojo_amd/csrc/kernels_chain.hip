@@ -69,6 +69,10 @@ struct TailK {
   const float* gn_stats;                      // [B][32][2] (mean, 1 / (sigma + eps)) of the block input
   const float* b_in;
   half_t* tok_out; half_t* qk; int ld_qk; half_t* vt; int ld_vt; long long s_vt;
+  // torch-norm kinds only (KIND_HEAD_T / KIND_TAIL_T): per-channel affine of the GroupNorm (head) and of LayerNorm 0 (head), 1 and 2 (tail)
+  const float *gn_w, *gn_b;
+  const float* ln_w[3]; const float* ln_b[3];
+  int ref_rstd;                               // 1: the LayerNorms divide by sigma + eps like the reference (replay only); 0: rsqrt(var + eps)
 };
 
 namespace {
@@ -88,6 +92,8 @@ constexpr int SEG1_TILES = 10 + 10 * 14 + 10;                     // Wco, 10 x (
 constexpr int SEG1_BYTES = 10 * TILE_FULL + 10 * FFN_CHUNK_BYTES + 10 * TILE_FULL;
 constexpr int STREAM_BYTES = SEG0_BYTES + SEG1_BYTES;
 constexpr int KIND_TAIL = 0, KIND_HEAD = 1;
+// the torch-norm extension (real SD-1.x checkpoints): GroupNorm / LayerNorm affine, rsqrt(var + eps), exact GELU - same design, same streams
+constexpr int KIND_HEAD_T = 2, KIND_TAIL_T = 3;
 constexpr int HEAD_TILES = 40;                                    // conv_in (10), Wq (10), Wk (10), Wv (10)
 constexpr int HEAD_STREAM_BYTES = HEAD_TILES * TILE_FULL;
 
@@ -208,7 +214,7 @@ __global__ void k_attn_head_pack(PackSrc cin, PackSrc inproj, half_t* dst) {
 }
 
 #ifdef TSD_CHAIN_TS
-__device__ unsigned long long g_chain_ts[2 * 1024 * 16];  // per kernel kind and block: s_memtime at the phase marks (experiment build only)
+__device__ unsigned long long g_chain_ts[4 * 1024 * 16];  // per kernel kind and block: s_memtime at the phase marks (experiment build only)
 #define CTS(i) do { if (threadIdx.x == 0 && blockIdx.x < 1024) g_chain_ts[(KIND * 1024 + blockIdx.x) * 16 + (i)] = (i) >= 14 ? __builtin_amdgcn_s_memrealtime() : __builtin_amdgcn_s_memtime(); } while (0)
 #else
 #define CTS(i) do { } while (0)
@@ -224,6 +230,7 @@ __global__ __launch_bounds__(256, 1) void attn_chain_kernel(const TailK p) {
   const int lrow = lane >> 3, cch = (lane & 7) ^ lrow;  // gather DMA: LDS row within an 8-row piece, logical 16-B chunk fetched
   const int m0 = blockIdx.x * BM;
   const int bsmp = m0 / p.S;
+  constexpr bool IS_HEAD = KIND == KIND_HEAD || KIND == KIND_HEAD_T, TORCH = KIND == KIND_HEAD_T || KIND == KIND_TAIL_T;
   CTS(0);
   CTS(14);
 
@@ -231,7 +238,7 @@ __global__ __launch_bounds__(256, 1) void attn_chain_kernel(const TailK p) {
   // byte offset / size class of tile gi of a segment (wave-uniform)
   auto tile_off = [&](int seg, int gi, bool& g1, bool& live) {
     g1 = false; live = true;
-    if (KIND == KIND_HEAD) { live = gi < HEAD_TILES; return gi * TILE_FULL; }
+    if (IS_HEAD) { live = gi < HEAD_TILES; return gi * TILE_FULL; }
     if (seg == 0) { live = gi < SEG0_TILES; return gi * TILE_FULL; }
     if (gi < 10) return SEG0_BYTES + gi * TILE_FULL;
     if (gi < 150) {
@@ -252,7 +259,7 @@ __global__ __launch_bounds__(256, 1) void attn_chain_kernel(const TailK p) {
 #ifdef TSD_CHAIN_NODMA  // ablation build: zero-size descriptor = no weight traffic (results are wrong, the timing is the point)
   const rsrc_t rw = make_rsrc(p.wstream, 0), rdead = make_rsrc(p.wstream, 0);
 #else
-  const rsrc_t rw = make_rsrc(p.wstream, KIND == KIND_HEAD ? HEAD_STREAM_BYTES : STREAM_BYTES), rdead = make_rsrc(p.wstream, 0);
+  const rsrc_t rw = make_rsrc(p.wstream, IS_HEAD ? HEAD_STREAM_BYTES : STREAM_BYTES), rdead = make_rsrc(p.wstream, 0);
 #endif
   const unsigned lane16 = lane * 16;
   // piece i (of 5 per wave; 4 for a GEMM-1 tile) of tile gi -> ring slot.  Round 4: a wave fetches ITS OWN quarter of the tile image
@@ -418,12 +425,31 @@ __global__ __launch_bounds__(256, 1) void attn_chain_kernel(const TailK p) {
       }
     }
   };
+  // torch-norm kinds: fp16(((v - sub) * mul) * gamma_c + beta_c) - the affine in fp32 before the one rounding, as k_layernorm<AFFINE> applies it;
+  // gamma / beta are per-column vectors in the accumulator layout (lane-local, like the biases)
+  auto store_a_tile_affine = [&](const f4 (&v)[4][5], const float (&mul)[4], const float (&sub)[4], const f4 (&gw)[5], const f4 (&gb)[5]) {
+#pragma unroll
+    for (int a = 0; a < 4; a++) {
+#pragma unroll
+      for (int b = 0; b < 5; b++) {
+        h4 o;
+#pragma unroll
+        for (int r = 0; r < 4; r++) o[r] = (half_t)__builtin_fmaf((v[a][b][r] - sub[a]) * mul[a], gw[b][r], gb[b][r]);
+        *(h4*)(smem + apo[b] + a * 2048) = o;
+      }
+    }
+  };
   // LayerNorm of the residual stream into the A tile: (x - mean) / (sigma + eps), population sigma, no affine
   // (helpers/utils.mojo:2052-2061 via :1845-1885; App.A D8).  Each column wave computes the exact two-pass mean / M2
   // of its 80 columns; the four are merged after ONE exchange (Chan et al., equal counts).
   float* scr = (float*)(smem + SCR_OFF);
-  auto layernorm_to_a = [&](const f4 (&v)[4][5]) {
+  // Torch-norm kinds: LayerNorm `li` of the block with its gamma / beta.  The 10 loads are issued HERE, after the stage's GEMM has returned
+  // (no counted wait is outstanding: the next one is the next GEMM's first tile wait) and consumed by the tile store below, before that GEMM
+  // starts - the compiler's own wait for them sits in front of every counted wait, so none of those ever has them in its window.
+  auto layernorm_to_a = [&](const f4 (&v)[4][5], int li = 0) {
     float mw[4], m2w[4];
+    f4 lw[5], lb[5];
+    if constexpr (TORCH) { load_cols(p.ln_w[li], lw); load_cols(p.ln_b[li], lb); }
 #pragma unroll
     for (int a = 0; a < 4; a++) {
       float t = 0.f;
@@ -449,13 +475,14 @@ __global__ __launch_bounds__(256, 1) void attn_chain_kernel(const TailK p) {
       const float d0 = p01[0] - mu, d1 = p01[2] - mu, d2 = p23[0] - mu, d3 = p23[2] - mu;
       const float m2 = ((p01[1] + p01[3]) + (p23[1] + p23[3])) + 80.f * ((d0 * d0 + d1 * d1) + (d2 * d2 + d3 * d3));
       mean[a] = mu;
-      rs[a] = 1.f / (sqrtf(m2 * (1.f / C)) + p.eps);
+      if constexpr (TORCH) rs[a] = p.ref_rstd ? 1.f / (sqrtf(m2 * (1.f / C)) + p.eps) : rsqrtf(m2 * (1.f / C) + p.eps);  // torch: eps joins the variance
+      else rs[a] = 1.f / (sqrtf(m2 * (1.f / C)) + p.eps);
     }
-    store_a_tile(v, rs, mean);
+    if constexpr (TORCH) store_a_tile_affine(v, rs, mean, lw, lb); else store_a_tile(v, rs, mean);
   };
   const float one4[4] = {1.f, 1.f, 1.f, 1.f}, zero4[4] = {0.f, 0.f, 0.f, 0.f};
 
-  if constexpr (KIND == KIND_HEAD) {
+  if constexpr (IS_HEAD) {
     // =============================================================================================================
     // head of the block (diffusion.mojo:116-124): GroupNorm-apply -> conv_in (1x1) -> tok ; LayerNorm -> q, k, V^T
     f4 T[4][5], acc[4][5], accq[4][5], bv[5];
@@ -464,6 +491,17 @@ __global__ __launch_bounds__(256, 1) void attn_chain_kernel(const TailK p) {
     f2 gst[2];  // (mean, 1/(sigma+eps)) of this lane's two groups of 10 channels
 #pragma unroll
     for (int k = 0; k < 2; k++) gst[k] = *(const f2*)(p.gn_stats + ((long long)bsmp * 32 + wn * 8 + g * 2 + k) * 2);
+    // torch-norm kind: gamma_c (x - mean) rstd + beta_c as a subtraction and ONE fma with the per-channel pair (gamma_c rstd_g, beta_c), formed
+    // once per lane for its 20 columns and used for its four rows (with gamma = 1, beta = 0 these are KIND_HEAD's bits).  The loads sit with the
+    // statistics, in front of the first DMA piece.
+    f4 gsc[5], gsh[5];
+    if constexpr (TORCH) {
+      load_cols(p.gn_w, gsc); load_cols(p.gn_b, gsh);
+#pragma unroll
+      for (int b = 0; b < 5; b++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) gsc[b][r] *= gst[(b * 4 + r) / 10][1];
+    }
     load_cols(p.b_in, bv);
     seg_begin(0);
     // GroupNorm (32 groups, eps 1e-6, no SiLU; helpers/utils.mojo:1845-1885) of the x tile -> A tile
@@ -476,7 +514,8 @@ __global__ __launch_bounds__(256, 1) void attn_chain_kernel(const TailK p) {
 #pragma unroll
         for (int r = 0; r < 4; r++) {
           const int grp = (b * 4 + r) / 10;
-          o[r] = (half_t)(((float)raw[a][b][r] - gst[grp][0]) * gst[grp][1]);
+          if constexpr (TORCH) o[r] = (half_t)__builtin_fmaf((float)raw[a][b][r] - gst[grp][0], gsc[b][r], gsh[b][r]);
+          else o[r] = (half_t)(((float)raw[a][b][r] - gst[grp][0]) * gst[grp][1]);
         }
         *(h4*)(smem + apo[b] + a * 2048) = o;
       }
@@ -595,7 +634,7 @@ __global__ __launch_bounds__(256, 1) void attn_chain_kernel(const TailK p) {
 #pragma unroll
       for (int r = 0; r < 4; r++) T[a][b][r] = (float)raw[a][b][r] + (acc[a][b][r] + bv[b][r]);
   CTS(2);
-  layernorm_to_a(T);
+  layernorm_to_a(T, 1);
   CTS(3);
   // ---- q = LN(tok2) . Wq^T  (scaled by softmax scale * log2 e) -----------------------------------------------------------
   gemm(I0{}, Yes{}, I0{}, acc, A_OFF, 10, No{});
@@ -771,7 +810,7 @@ __global__ __launch_bounds__(256, 1) void attn_chain_kernel(const TailK p) {
   for (int a = 0; a < 4; a++)
 #pragma unroll
     for (int b = 0; b < 5; b++) T[a][b] += acc[a][b] + bv[b];
-  layernorm_to_a(T);
+  layernorm_to_a(T, 2);
   CTS(6);
   // ---- GEGLU feed-forward: ten chunks of 128 hidden units; the second GEMM accumulates over the chunks ------------------
   f4 acc2[4][5];
@@ -820,7 +859,9 @@ __global__ __launch_bounds__(256, 1) void attn_chain_kernel(const TailK p) {
     // in the accumulator.  The asm use keeps the arithmetic HERE (see (i) above).
     auto act_pair = [&](int u, int jp) {
       const f4 v = acc[u][jp];
-      const float o0 = v[0] * gelu_tanh_c(v[1]), o1 = v[2] * gelu_tanh_c(v[3]);
+      // torch-norm kind: the exact GELU, by the erf evaluation of the op-by-op path (gelu_erf_f, common.h: 17 VALU instructions per activation
+      // with the multiply by a, two of them transcendental, against 8 for the tanh form)
+      const float o0 = v[0] * (TORCH ? gelu_erf_f(v[1]) : gelu_tanh_c(v[1])), o1 = v[2] * (TORCH ? gelu_erf_f(v[3]) : gelu_tanh_c(v[3]));
       h2 pk = {(half_t)o0, (half_t)o1};
       oreg[u][jp] = pin_here(__builtin_bit_cast(unsigned, pk));
     };
@@ -1074,9 +1115,10 @@ extern "C" int tsd_debug_chain_ts(unsigned long long* out, int n, int kind) {
 // ---- host side ----------------------------------------------------------------------------------------------------
 size_t attn_tail_stream_bytes() { return (size_t)STREAM_BYTES; }
 
-// debug / A-B switch of ONE context: 1 = fused head / tail kernels at the 64x64 level (default), 0 = the op-by-op graph; returns the old value
+// debug / A-B switch of ONE context: 1 = fused head / tail kernels at the 64x64 level (default), 0 = the op-by-op graph, 2 = fused kernels for
+// torch-norm blocks (real SD-1.x checkpoints) as well; returns the old value
 extern "C" int tsd_debug_set_fused_attention(tsd_ctx* ctx, int on) {
-  return ctx_set_option(ctx, &TsdOptions::chain, on ? 1 : 0, 0, 1);
+  return ctx_set_option(ctx, &TsdOptions::chain, on == 2 ? 2 : (on ? 1 : 0), 0, 2);
 }
 bool attn_tail_supported(const tsd_ctx* ctx, int C_, int d, int heads, int T, int64_t M, int S) {
   return ctx->opt.chain && C_ == 320 && d == 40 && heads == 8 && T >= 1 && T <= 80 && S % 64 == 0 && M % 64 == 0 && M < (1 << 24);
@@ -1101,6 +1143,8 @@ int launch_attn_tail(tsd_ctx* ctx, const AttnTailArgs& a) {
   if (a.ld_ao % 8 || a.ld_tok % 8 || a.ld_x % 8 || a.ld_out % 8 || a.ldk % 8 || a.ldvt % 8 || a.ld_ao < 320 || a.ld_tok < 320 ||
       a.ld_x < 320 || a.ld_out < 320 || a.ldk < 320 || a.ldvt < ((a.T + 7) & ~7))
     TSD_FAIL(TSD_E_SHAPE, "attention tail: misaligned or too narrow pitches");
+  if (a.torch && ctx->opt.chain < 2) TSD_FAIL(TSD_E_SHAPE, "attention tail: the torch-norm kernel is switched off (TSD_CHAIN=2)");
+  if (a.torch && (!a.ln1_w || !a.ln1_b || !a.ln2_w || !a.ln2_b)) TSD_FAIL(TSD_E_ARG, "attention tail: NULL LayerNorm affine");
   // the ao tile is DMA'd through ONE descriptor based at a.ao with 32-bit byte offsets (m0 + row) * ld_ao * 2
   if ((long long)a.M * a.ld_ao * 2 >= 0x7ffffff0LL) TSD_FAIL(TSD_E_SHAPE, "attention tail: ao operand exceeds the 2 GiB addressing window");
   if (!a.ao || !a.tok || !a.x || !a.out || !a.Kc || !a.Vt || !a.bso || !a.bco || !a.b1 || !a.b2 || !a.bout)
@@ -1117,12 +1161,16 @@ int launch_attn_tail(tsd_ctx* ctx, const AttnTailArgs& a) {
   k.qscale = a.scale * 1.4426950408889634f; k.eps = a.eps;
   k.gn_part = a.gn_part; k.gn_nslab = a.gn_nslab;
   k.gn_stats = nullptr; k.b_in = nullptr; k.tok_out = nullptr; k.qk = nullptr; k.ld_qk = 0; k.vt = nullptr; k.ld_vt = 0; k.s_vt = 0;
+  k.gn_w = k.gn_b = nullptr; k.ln_w[0] = k.ln_b[0] = nullptr;
+  k.ln_w[1] = a.ln1_w; k.ln_b[1] = a.ln1_b; k.ln_w[2] = a.ln2_w; k.ln_b[2] = a.ln2_b; k.ref_rstd = a.ref_rstd;
   static std::atomic<unsigned long long> attr{0};  // one bit per device (setting the attribute twice is harmless; the mask is only a shortcut)
   if (!((attr.load(std::memory_order_relaxed) >> (ctx->device & 63)) & 1)) {
     HIP_TRY(hipFuncSetAttribute((const void*)attn_chain_kernel<KIND_TAIL>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
+    HIP_TRY(hipFuncSetAttribute((const void*)attn_chain_kernel<KIND_TAIL_T>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
     attr.fetch_or(1ull << (ctx->device & 63), std::memory_order_relaxed);
   }
-  hipLaunchKernelGGL(attn_chain_kernel<KIND_TAIL>, dim3((unsigned)(a.M / BM)), dim3(256), LDS_BYTES, ctx->stream, k);
+  if (a.torch) hipLaunchKernelGGL(attn_chain_kernel<KIND_TAIL_T>, dim3((unsigned)(a.M / BM)), dim3(256), LDS_BYTES, ctx->stream, k);
+  else hipLaunchKernelGGL(attn_chain_kernel<KIND_TAIL>, dim3((unsigned)(a.M / BM)), dim3(256), LDS_BYTES, ctx->stream, k);
   HIP_TRY(hipGetLastError());
   return TSD_OK;
 }
@@ -1145,6 +1193,8 @@ int launch_attn_head(tsd_ctx* ctx, const AttnHeadArgs& a) {
   if (a.ld_x % 8 || a.ld_tok % 8 || a.ld_qk % 8 || a.ld_vt % 8 || a.ld_x < 320 || a.ld_tok < 320 || a.ld_qk < 640 || a.ld_vt < a.S)
     TSD_FAIL(TSD_E_SHAPE, "attention head: misaligned or too narrow pitches");
   if (!a.x || !a.tok || !a.qk || !a.vt || !a.b_in) TSD_FAIL(TSD_E_ARG, "attention head: NULL operand");
+  if (a.torch && ctx->opt.chain < 2) TSD_FAIL(TSD_E_SHAPE, "attention head: the torch-norm kernel is switched off (TSD_CHAIN=2)");
+  if (a.torch && (!a.gn_w || !a.gn_b || !a.ln0_w || !a.ln0_b)) TSD_FAIL(TSD_E_ARG, "attention head: NULL norm affine");
   if (!ctx->launch()) return TSD_OK;
   ProfScope prof(ctx, KC_CHAIN, (int)a.M, 320, 1, 1);
   TailK k = {};
@@ -1152,12 +1202,15 @@ int launch_attn_head(tsd_ctx* ctx, const AttnHeadArgs& a) {
   k.vt = a.vt; k.ld_vt = a.ld_vt; k.s_vt = a.s_vt;
   k.wstream = a.wstream; k.b_in = a.b_in; k.gn_stats = a.gn_stats;
   k.M = (int)a.M; k.S = a.S; k.eps = a.eps; k.T = 1;
+  k.gn_w = a.gn_w; k.gn_b = a.gn_b; k.ln_w[0] = a.ln0_w; k.ln_b[0] = a.ln0_b; k.ref_rstd = a.ref_rstd;
   static std::atomic<unsigned long long> attr{0};  // one bit per device
   if (!((attr.load(std::memory_order_relaxed) >> (ctx->device & 63)) & 1)) {
     HIP_TRY(hipFuncSetAttribute((const void*)attn_chain_kernel<KIND_HEAD>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
+    HIP_TRY(hipFuncSetAttribute((const void*)attn_chain_kernel<KIND_HEAD_T>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES));
     attr.fetch_or(1ull << (ctx->device & 63), std::memory_order_relaxed);
   }
-  hipLaunchKernelGGL(attn_chain_kernel<KIND_HEAD>, dim3((unsigned)(a.M / BM)), dim3(256), LDS_BYTES, ctx->stream, k);
+  if (a.torch) hipLaunchKernelGGL(attn_chain_kernel<KIND_HEAD_T>, dim3((unsigned)(a.M / BM)), dim3(256), LDS_BYTES, ctx->stream, k);
+  else hipLaunchKernelGGL(attn_chain_kernel<KIND_HEAD>, dim3((unsigned)(a.M / BM)), dim3(256), LDS_BYTES, ctx->stream, k);
   HIP_TRY(hipGetLastError());
   return TSD_OK;
 }

@@ -594,14 +594,7 @@ __global__ void k_fill_uniform(float* __restrict__ dst, int64_t n, uint64_t base
     dst[i] = __fmul_rn(v, bound);
   }
 }
-// erf by Abramowitz-Stegun 7.1.26 (|error| <= 1.5e-7)
-__device__ __forceinline__ float gelu_erf_f(float x) {
-  const float z = fabsf(x) * 0.7071067811865476f;
-  const float t = __builtin_amdgcn_rcpf(1.f + 0.3275911f * z);
-  const float poly = t * (0.254829592f + t * (-0.284496736f + t * (1.421413741f + t * (-1.453152027f + t * 1.061405429f))));
-  const float erf_abs = 1.f - poly * __builtin_amdgcn_exp2f(-1.4426950408889634f * z * z);
-  return 0.5f * x * (1.f + copysignf(erf_abs, x));
-}
+// (gelu_erf_f: common.h)
 __global__ void k_geglu_erf(const half_t* __restrict__ x, int64_t n_pairs8, half_t* __restrict__ out) {
   typedef _Float16 h8v __attribute__((ext_vector_type(8)));
   typedef _Float16 h4v __attribute__((ext_vector_type(4)));

@@ -367,12 +367,12 @@ int launch_groupnorm(tsd_ctx* ctx, const NormSrc& src, int B, int HW, int C, int
 }
 
 int launch_gn_finalize(tsd_ctx* ctx, const float* partial, int nslab, int B, int HW, int C, int groups, float eps, float gamma,
-                       float* stats) {
+                       float* stats, int torch_rstd) {
   if (!partial || nslab <= 0 || !stats || C % groups) TSD_FAIL(TSD_E_ARG, "gn_finalize: bad argument");
   if (!ctx->launch()) return TSD_OK;
   GnK k = {};
   k.C = C; k.HW = HW; k.G = groups; k.cpg = C / groups; k.nslab = nslab;
-  k.partial = const_cast<float*>(partial); k.stats = stats; k.eps = eps; k.gamma = gamma; k.torch_rstd = 0;
+  k.partial = const_cast<float*>(partial); k.stats = stats; k.eps = eps; k.gamma = gamma; k.torch_rstd = torch_rstd;
   ProfScope prof(ctx, KC_GROUPNORM, B * groups, nslab, 0, 1);
   hipLaunchKernelGGL(k_gn_finalize, dim3(ceil_div(groups, 32), B), dim3(256), 0, ctx->stream, k);
   HIP_TRY(hipGetLastError());
@@ -380,7 +380,7 @@ int launch_gn_finalize(tsd_ctx* ctx, const float* partial, int nslab, int B, int
 }
 
 // statistics only (no apply pass): partial sums over pixel slabs, then the finalize above -> stats [B][groups][2]
-int launch_gn_stats(tsd_ctx* ctx, const half_t* x, int ld, int B, int HW, int C, int groups, float eps, float gamma, float* stats) {
+int launch_gn_stats(tsd_ctx* ctx, const half_t* x, int ld, int B, int HW, int C, int groups, float eps, float gamma, float* stats, int torch_rstd) {
   if (C % 8 || C % groups || C > 256 * 8 * GN_MAX_CPT || ld % 8) TSD_FAIL(TSD_E_SHAPE, "gn_stats: C=%d groups=%d unsupported", C, groups);
   GnK k = {};
   k.x0 = x; k.ld0 = ld; k.C0 = C; k.C = C; k.HW = HW; k.G = groups; k.cpg = C / groups;
@@ -391,7 +391,7 @@ int launch_gn_stats(tsd_ctx* ctx, const half_t* x, int ld, int B, int HW, int C,
   k.nslab = pl.nslab;
   k.partial = arena_alloc<float>(ctx, (int64_t)B * k.nslab * groups * 2);
   if (!k.partial) TSD_FAIL(TSD_E_ALLOC, "gn_stats: workspace exhausted");
-  k.stats = stats; k.eps = eps; k.gamma = gamma;
+  k.stats = stats; k.eps = eps; k.gamma = gamma; k.torch_rstd = torch_rstd;
   if (!ctx->launch()) return TSD_OK;
   ctx->gn_last = pl;
   ProfScope prof(ctx, KC_GROUPNORM, B * HW, C, 0, 1);

@@ -7,18 +7,35 @@
 
 #include "model.h"
 
-bool attn_tail_weights_ok(const AttnW& w) {
-  const int C = w.C;
-  const bool plain = !w.ln[1].w && !w.ln[1].b && !w.ln[2].w && !w.ln[2].b && !w.gelu_erf;
-  return plain && C == 320 && w.n_head == 8 && w.n_embed == 40 && w.sa_out.b && w.ca_out.b && w.geglu1.b && w.geglu2.b &&
-         w.conv_out.b && !w.ca_q.b && w.sa_out.Kpad == C && w.ca_q.Kpad == C && w.ca_out.Kpad == C && w.geglu1.Kpad == C &&
-         w.geglu2.Kpad == 4 * C && w.conv_out.Ipad == C && w.conv_out.k == 1;
+// A torch-norm block (ATTN_FUSE_TORCH) has EVERY norm with both gamma and beta and rsqrt(var + eps), the exact GELU and no FP8 feed-forward (the
+// converted blocks keep the e4m3 GEMMs); a plain one (ATTN_FUSE_PLAIN) has none of the four.  A mix of the two stays op by op.
+static bool norm_torch(const NormAffine& n) { return n.w && n.b && n.torch_rstd == 1; }
+static bool norm_plain(const NormAffine& n) { return !n.w && !n.b; }
+static int attn_block_kind(const AttnW& w) {
+  if (norm_plain(w.gn) && norm_plain(w.ln[0]) && norm_plain(w.ln[1]) && norm_plain(w.ln[2]) && !w.gelu_erf) return ATTN_FUSE_PLAIN;
+  if (norm_torch(w.gn) && norm_torch(w.ln[0]) && norm_torch(w.ln[1]) && norm_torch(w.ln[2]) && w.gelu_erf && !w.ff8_w1 && !w.ff8_w2)
+    return ATTN_FUSE_TORCH;
+  return ATTN_FUSE_NONE;
 }
 
-bool attn_head_weights_ok(const AttnW& w) {
+int attn_tail_weights_ok(const AttnW& w) {
   const int C = w.C;
-  return C == 320 && w.n_head == 8 && w.n_embed == 40 && !w.gn.w && !w.gn.b && !w.ln[0].w && !w.ln[0].b && w.conv_in.b &&
-         w.conv_in.k == 1 && w.conv_in.Ipad == C && w.conv_in.Opad == C && !w.sa_in.b && w.sa_in.Kpad == C && w.sa_in.N == 3 * C;
+  // (the plain tail looks at its own norms only, as before the torch kinds: a block whose head norms alone carry an affine keeps the fused tail)
+  const bool plain = !w.ln[1].w && !w.ln[1].b && !w.ln[2].w && !w.ln[2].b && !w.gelu_erf;
+  const bool shape = C == 320 && w.n_head == 8 && w.n_embed == 40 && w.sa_out.b && w.ca_out.b && w.geglu1.b && w.geglu2.b &&
+                     w.conv_out.b && !w.ca_q.b && w.sa_out.Kpad == C && w.ca_q.Kpad == C && w.ca_out.Kpad == C && w.geglu1.Kpad == C &&
+                     w.geglu2.Kpad == 4 * C && w.conv_out.Ipad == C && w.conv_out.k == 1;
+  if (!shape) return ATTN_FUSE_NONE;
+  return plain ? ATTN_FUSE_PLAIN : (attn_block_kind(w) == ATTN_FUSE_TORCH ? ATTN_FUSE_TORCH : ATTN_FUSE_NONE);
+}
+
+int attn_head_weights_ok(const AttnW& w) {
+  const int C = w.C;
+  const bool plain = !w.gn.w && !w.gn.b && !w.ln[0].w && !w.ln[0].b;
+  const bool shape = C == 320 && w.n_head == 8 && w.n_embed == 40 && w.conv_in.b && w.conv_in.k == 1 && w.conv_in.Ipad == C &&
+                     w.conv_in.Opad == C && !w.sa_in.b && w.sa_in.Kpad == C && w.sa_in.N == 3 * C;
+  if (!shape) return ATTN_FUSE_NONE;
+  return plain ? ATTN_FUSE_PLAIN : (attn_block_kind(w) == ATTN_FUSE_TORCH ? ATTN_FUSE_TORCH : ATTN_FUSE_NONE);
 }
 
 // ---- duplicate-concat fold (UNetW::res_dup): host arithmetic on fp16 bit patterns, no HIP -------------------------------------------
@@ -486,6 +503,8 @@ static int model_build_derived(tsd_model* m) {
   }
   if (!is_diffusion_kind(m->kind) && !is_controlnet_kind(m->kind)) return TSD_OK;
   const bool full_graph = is_full_unet_kind(m->kind) || is_controlnet_kind(m->kind);  // a ControlNet is the full-size graph's encoder half
+  // Blocks with a fused kernel get its weight streams.  A torch-norm block keeps its tile-major and folded copies below as well: the fused kernels
+  // run for it only under TsdOptions::chain == 2, and the default context must find the op-by-op path exactly as it was.
   std::vector<AttnW*> el;
   for (auto& a : m->unet.attn) if (a.C && (attn_tail_weights_ok(a) || attn_head_weights_ok(a))) el.push_back(&a);
   // input convolution (4 latent channels): [Opad][64] im2col weights
@@ -531,7 +550,7 @@ static int model_build_derived(tsd_model* m) {
   }
   if (tm_mib > 0 && ctx->opt.lin_w_tm != 0)
     for (auto& a : m->unet.attn)
-      if (a.C && !(attn_tail_weights_ok(a) && attn_head_weights_ok(a)))
+      if (a.C && !(attn_tail_weights_ok(a) == ATTN_FUSE_PLAIN && attn_head_weights_ok(a) == ATTN_FUSE_PLAIN))
         for (ConvW* c : {&a.conv_in, &a.conv_out})
           if (c->w && c->k == 1 && c->Ipad % 64 == 0 && (size_t)c->Opad * c->Ipad * 2 >= tml_bytes) { tm.push_back(c); tm_b += (((size_t)c->Opad * c->Ipad * 2) + 255) & ~size_t(255); }
   // ... and of the attention blocks' linear layers (TSD_LIN_W_TM MiB; the 64x64-level blocks read theirs through the fused kernels' streams)
@@ -539,7 +558,7 @@ static int model_build_derived(tsd_model* m) {
   std::vector<LinW*> tml;
   if (tml_mib > 0)
     for (auto& a : m->unet.attn)
-      if (a.C && !(attn_tail_weights_ok(a) && attn_head_weights_ok(a)))
+      if (a.C && !(attn_tail_weights_ok(a) == ATTN_FUSE_PLAIN && attn_head_weights_ok(a) == ATTN_FUSE_PLAIN))
         for (LinW* l : {&a.sa_in, &a.sa_out, &a.ca_q, &a.ca_out, &a.geglu1, &a.geglu2})
           if (l->w && l->Kpad % 64 == 0 && l->Kpad == l->K && (size_t)l->N * l->Kpad * 2 >= tml_bytes) { tml.push_back(l); tm_b += (((size_t)l->N * l->Kpad * 2) + 255) & ~size_t(255); }
   LinW* kv = nullptr;  // k_proj | v_proj rows of all blocks (adjacent in the blob: the fused context projection of g_unet_forward)
@@ -553,7 +572,7 @@ static int model_build_derived(tsd_model* m) {
   size_t fold_b = 0;
   if (ctx->opt.fold_out)
     for (auto& a : m->unet.attn)
-      if (a.C && !attn_tail_weights_ok(a) && a.geglu2.w && a.conv_out.w && a.conv_out.k == 1 && a.conv_out.Ipad == a.C && a.conv_out.Opad == a.C &&
+      if (a.C && attn_tail_weights_ok(a) != ATTN_FUSE_PLAIN && a.geglu2.w && a.conv_out.w && a.conv_out.k == 1 && a.conv_out.Ipad == a.C && a.conv_out.Opad == a.C &&
           a.geglu2.N == a.C && a.geglu2.Kpad == 4 * a.C && a.geglu2.K == 4 * a.C && a.C % 64 == 0) {
         fold.push_back(&a);
         fold_b += 2 * ((((size_t)a.C * 5 * a.C * 2) + 255) & ~size_t(255)) + ((((size_t)a.C * 4) + 255) & ~size_t(255));

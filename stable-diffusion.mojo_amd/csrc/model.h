@@ -118,9 +118,10 @@ struct AttnW {  // Unet_Attention_Block, diffusion.mojo:87-98
   const uint8_t* ff8_w1 = nullptr; const float* ff8_s1 = nullptr;
   const uint8_t* ff8_w2 = nullptr; const float* ff8_s2 = nullptr;
 };
-// true when the fused tail kernel can run this block's weights (reference norms, tanh GELU, C = 8 x 40)
-bool attn_tail_weights_ok(const AttnW& w);
-bool attn_head_weights_ok(const AttnW& w);
+// which fused kernel (C = 8 x 40 only) serves the block's tail / head: none (0, false), the reference's norms and tanh GELU, or the torch-norm extension
+enum { ATTN_FUSE_NONE = 0, ATTN_FUSE_PLAIN = 1, ATTN_FUSE_TORCH = 2 };
+int attn_tail_weights_ok(const AttnW& w);
+int attn_head_weights_ok(const AttnW& w);
 struct VaeAttnW {  // vae.mojo:9-11
   int C = 0;
   LinW in_proj, out_proj;

@@ -74,7 +74,7 @@ void options_from_env(TsdOptions& o) {
   o.res_fuse_skip = env_int("TSD_RES_FUSE_SKIP", o.res_fuse_skip);
   o.gn_composite = env_int("TSD_GN_COMPOSITE", o.gn_composite);
   o.conv_in_im2col = env_int("TSD_CONV_IN_IM2COL", o.conv_in_im2col);
-  o.chain = env_int("TSD_CHAIN", o.chain) ? 1 : 0;
+  { const int ch = env_int("TSD_CHAIN", o.chain); o.chain = ch == 2 ? 2 : (ch ? 1 : 0); }
   o.fold_out = env_int("TSD_FOLD_OUT", o.fold_out) ? 1 : 0;
   o.ups_fold = env_int("TSD_UPS_FOLD", o.ups_fold) ? 1 : 0;
   o.fold_dup = env_int("TSD_FOLD_DUP", o.fold_dup) ? 1 : 0;
