@@ -898,6 +898,12 @@ enum tsd_attn_desc_field {
 /* Version 2 has the fields of version 1 and admits head dimension 64 (flash_attn_kernel<64, 1>, TSD_AK_64).  A version-1 descriptor keeps
  * what it always did with d = 64: it is sized, the run is refused with the launcher's status, reports kernel 0 and writes nothing. */
 #define TSD_AD_VERSION_2 2
+/* Version 3 has the fields of version 2 and, BEHIND them (n >= TSD_AD3_COUNT), the window of a windowed self-attention launch
+ * (tsd_model_set_attn_window): WIN the window side in tokens (0 = not windowed: the launch of a version-2 descriptor), GRID_H x GRID_W the
+ * token grid, SQ = SK = GRID_H * GRID_W.  The operands keep the whole grid's layout, so they are sized as for version 2.  A windowed run
+ * reports in TSD_AI_KERNEL the plain sibling of the instantiation that ran; the sizing mode plans on the window's shape. */
+#define TSD_AD_VERSION_3 3
+enum tsd_attn_desc_field_v3 { TSD_AD3_WIN = TSD_AD_COUNT, TSD_AD3_GRID_H, TSD_AD3_GRID_W, TSD_AD3_COUNT };
 enum tsd_attn_mode { TSD_AM_ATTN = 0, TSD_AM_SOFTMAX_ROWS };
 /* Operand slots: inputs Q [B][Sq][ldq], K [B][Sk][ldk], V^T [B][H*d][ldvt] (fp16), X (softmax_rows input: fp32, or the fp16 rows the
  * launch overwrites); output O (attention: [B][Sq][ldo] fp16; softmax_rows: the rows, in X's type and layout). */
@@ -1157,6 +1163,25 @@ int tsd_freeu_f16(tsd_ctx* ctx, const void* h, const void* r, int B, int H, int 
  * write is columns < Ch / 2 of h and < Cr of r, nothing else. */
 int tsd_debug_freeu_run(tsd_ctx* ctx, const void* h, const void* r, int B, int H, int W, int Ch, int Cr, int ldh, int ldr, int guard, float b,
                         float s, int mode, void* h_out, void* r_out);
+
+/* ---- Windowed self attention (EXTENSION: HyperTile, training-free) on the UNets and ControlNets.  The token grid of a self-attention
+ * layer is cut into non-overlapping win x win windows and every query attends to the keys of its own window only; cross attention and
+ * everything else is untouched.  One launch per block as before (flash_attn_win_kernel walks the windows itself).
+ * win[l] is the window side in tokens (0, 8, 16, 32, 64 or 128) of the blocks whose token grid is LH / 2^l x LW / 2^l.  NULL or all
+ * zeros turns it off: the model then enqueues exactly the launches it did before and gives the bits it gave.  A level whose grid IS one
+ * window, or one the model has no attention at, runs as without a table.  State of the MODEL, like FreeU: every forward, session and slot
+ * session of the model runs it, from the next forward / step() / advance() on, with no upload() and the same workspace.  A forward
+ * whose grid an active window does not divide is refused with TSD_E_SHAPE.  TSD_E_ARG: a kind that is neither a UNet nor a ControlNet,
+ * a side outside the list; the model's table stays as it was.
+ * tsd_model_attn_window: 1 when some level is windowed, 0 when off (negative: TSD_E_ARG); out[4], when not NULL, receives the table. */
+#define TSD_ATTN_WINDOW_LEVELS 4
+int tsd_model_set_attn_window(tsd_model* unet, const int win[4]);
+int tsd_model_attn_window(tsd_model* unet, int out[4]);
+/* Debug / bench entry like tsd_debug_attn_bench: time `iters` self-attention launches on synthetic device data over a grid_h x grid_w
+ * token grid (Sq = Sk = grid_h * grid_w <= 2^20) cut into win x win windows; win = 0 times the plain call over the whole grid.  *ms is the
+ * mean per launch.  TSD_E_ARG: NULL ctx / ms, iters <= 0, an empty or oversized grid, a side outside the list; TSD_E_SHAPE: a head
+ * dimension without a fused kernel, a window that does not divide the grid (both from the launcher). */
+int tsd_debug_attn_bench_win(tsd_ctx* ctx, int B, int H, int d, int grid_h, int grid_w, int win, int iters, float* ms);
 
 /* ---- FP8 feed-forward (EXTENSION, opt-in): the two GEGLU linears of the attention blocks that run op by op on OCP e4m3 operands
  * (v_mfma_f32_16x16x128_f8f6f4), per-row dynamic activation scales, per-output-channel weight scales, fp32 accumulation.

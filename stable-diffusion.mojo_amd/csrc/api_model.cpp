@@ -312,6 +312,29 @@ extern "C" int tsd_model_freeu(tsd_model* unet, float* b, float* s, int* mode) {
   return unet->freeu_on ? 1 : 0;
 }
 
+// Windowed self attention: the model's table.  Like FreeU's, it is read when a forward is enqueued (attn_window_for, graph.cpp).
+extern "C" int tsd_model_set_attn_window(tsd_model* unet, const int win[4]) {
+  NOTNULL(unet);
+  if (!is_diffusion_kind(unet->kind) && !is_controlnet_kind(unet->kind))
+    TSD_FAIL(TSD_E_ARG, "tsd_model_set_attn_window: windowed self attention belongs to the UNets and ControlNets, this model is kind %d", unet->kind);
+  for (int l = 0; win && l < 4; l++)
+    if (win[l] != 0 && !attn_window_side_ok(win[l]))
+      TSD_FAIL(TSD_E_ARG, "tsd_model_set_attn_window: level %d: window side %d (0, 8, 16, 32, 64 or 128)", l, win[l]);
+  for (int l = 0; l < 4; l++) unet->attn_win[l] = win ? win[l] : 0;
+  return TSD_OK;
+}
+extern "C" int tsd_model_attn_window(tsd_model* unet, int out[4]) {
+  NOTNULL(unet);
+  if (!is_diffusion_kind(unet->kind) && !is_controlnet_kind(unet->kind))
+    TSD_FAIL(TSD_E_ARG, "tsd_model_attn_window: windowed self attention belongs to the UNets and ControlNets, this model is kind %d", unet->kind);
+  int on = 0;
+  for (int l = 0; l < 4; l++) {
+    if (out) out[l] = unet->attn_win[l];
+    on |= unet->attn_win[l] != 0;
+  }
+  return on;
+}
+
 extern "C" int tsd_decoder_forward_hw(tsd_model* m, const float* latents, int B, int LH, int LW, float* images) {
   NOTNULL(m); NOTNULL(latents); NOTNULL(images);
   if (!is_decoder_kind(m->kind)) TSD_FAIL(TSD_E_ARG, "tsd_decoder_forward: model is not a Decoder");

@@ -479,7 +479,7 @@ int ad_extents(const int64_t* d, int64_t* e) {
   for (int i = 0; i < TSD_AO_COUNT; i++) e[i] = 0;
 #define AD_REQ(cond) \
   if (!(cond)) TSD_FAIL(TSD_E_ARG, "attn_run: descriptor cannot be sized (%s)", #cond)
-  AD_REQ(d[TSD_AD_VERSION] == TSD_AD_VERSION_1 || d[TSD_AD_VERSION] == TSD_AD_VERSION_2);
+  AD_REQ(d[TSD_AD_VERSION] == TSD_AD_VERSION_1 || d[TSD_AD_VERSION] == TSD_AD_VERSION_2 || d[TSD_AD_VERSION] == TSD_AD_VERSION_3);
   const int64_t mode = d[TSD_AD_MODE], lim = 1LL << 28;
   AD_REQ(mode == TSD_AM_ATTN || mode == TSD_AM_SOFTMAX_ROWS);
   if (mode == TSD_AM_ATTN) {
@@ -495,6 +495,11 @@ int ad_extents(const int64_t* d, int64_t* e) {
     AD_REQ(d[TSD_AD_SQB] >= Sq * d[TSD_AD_LDQ] && d[TSD_AD_SKB] >= Sk * d[TSD_AD_LDK] && d[TSD_AD_SVTB] >= C * d[TSD_AD_LDVT] &&
            d[TSD_AD_SOB] >= Sq * d[TSD_AD_LDO]);
     for (int f : {TSD_AD_SQB, TSD_AD_SKB, TSD_AD_SVTB, TSD_AD_SOB}) AD_REQ(d[f] < lim);
+    if (d[TSD_AD_VERSION] == TSD_AD_VERSION_3 && d[TSD_AD3_WIN] != 0) {  // (the caller has checked that a version-3 descriptor has these fields)
+      const int64_t w = d[TSD_AD3_WIN], gh = d[TSD_AD3_GRID_H], gw = d[TSD_AD3_GRID_W];
+      AD_REQ(attn_window_side_ok((int)std::min<int64_t>(std::max<int64_t>(w, 0), 1 << 20)));
+      AD_REQ(gh > 0 && gw > 0 && gh <= (1 << 20) && gw <= (1 << 20) && gh * gw == d[TSD_AD_SQ] && d[TSD_AD_SQ] == d[TSD_AD_SK]);
+    }
     e[TSD_AO_Q] = (B - 1) * d[TSD_AD_SQB] + (Sq - 1) * d[TSD_AD_LDQ] + C;
     e[TSD_AO_K] = (B - 1) * d[TSD_AD_SKB] + (Sk - 1) * d[TSD_AD_LDK] + C;
     e[TSD_AO_VT] = (B - 1) * d[TSD_AD_SVTB] + (C - 1) * d[TSD_AD_LDVT] + Skv;
@@ -519,9 +524,11 @@ extern "C" int tsd_debug_attn_run(tsd_ctx* ctx, const int64_t* desc, int n, cons
                                   int64_t* ext, int64_t* info) {
   NOTNULL(desc); NOTNULL(ext);
   TSD_TRY(check_fields("attn_run", n, TSD_AD_COUNT));
+  if (desc[TSD_AD_VERSION] == TSD_AD_VERSION_3) TSD_TRY(check_fields("attn_run (version 3)", n, TSD_AD3_COUNT));
   TSD_TRY(ad_extents(desc, ext));
   const int64_t* d = desc;
   const bool attn = d[TSD_AD_MODE] == TSD_AM_ATTN;
+  const int win = attn && d[TSD_AD_VERSION] == TSD_AD_VERSION_3 ? (int)d[TSD_AD3_WIN] : 0;  // 0: the launch of a version-2 descriptor
   // head dimension 64 came with version 2: a version-1 descriptor is sized and refused as it was before the d = 64 kernel existed
   const bool v1_d64 = attn && d[TSD_AD_VERSION] == TSD_AD_VERSION_1 && d[TSD_AD_D] == 64;
   if (info) for (int i = 0; i < TSD_AI_COUNT; i++) info[i] = 0;
@@ -529,7 +536,11 @@ extern "C" int tsd_debug_attn_run(tsd_ctx* ctx, const int64_t* desc, int n, cons
     if (info && attn && !v1_d64 && attn_fused_supported((int)d[TSD_AD_D]) && d[TSD_AD_SQ] > 0 && d[TSD_AD_SK] > 0) {
       TsdOptions o;
       o.attn_qb_force = (int)d[TSD_AD_KERNEL]; o.attn_diag = (int)d[TSD_AD_DIAG];
-      const AttnPlan p = attn_plan(o, (int)d[TSD_AD_B], (int)d[TSD_AD_H], (int)d[TSD_AD_D], (int)d[TSD_AD_SQ], (int)d[TSD_AD_SK]);
+      const int gh = win ? (int)d[TSD_AD3_GRID_H] : 0, gw = win ? (int)d[TSD_AD3_GRID_W] : 0;
+      const bool tiles = win && gh % win == 0 && gw % win == 0;  // a grid the window does not divide is planned as the launcher refuses it: not at all
+      if (win && !tiles) return TSD_OK;
+      const AttnPlan p = win ? attn_plan(o, (int)d[TSD_AD_B], (int)d[TSD_AD_H], (int)d[TSD_AD_D], win * win, win * win, (gh / win) * (gw / win))
+                             : attn_plan(o, (int)d[TSD_AD_B], (int)d[TSD_AD_H], (int)d[TSD_AD_D], (int)d[TSD_AD_SQ], (int)d[TSD_AD_SK]);
       info[TSD_AI_KERNEL] = p.kernel; info[TSD_AI_DIAG] = p.diag; info[TSD_AI_XCD_MAP] = p.xcd_map;
     }
     return TSD_OK;
@@ -558,6 +569,7 @@ extern "C" int tsd_debug_attn_run(tsd_ctx* ctx, const int64_t* desc, int n, cons
     a.O = (half_t*)ops.at(TSD_AO_O); a.ldo = (int)d[TSD_AD_LDO]; a.sO = d[TSD_AD_SOB];
     a.B = (int)d[TSD_AD_B]; a.H = (int)d[TSD_AD_H]; a.d = (int)d[TSD_AD_D]; a.Sq = (int)d[TSD_AD_SQ]; a.Sk = (int)d[TSD_AD_SK];
     a.scale = f32_of(d[TSD_AD_SCALE]);
+    if (win) { a.win = win; a.grid_h = (int)d[TSD_AD3_GRID_H]; a.grid_w = (int)d[TSD_AD3_GRID_W]; }
     r = run_planned(ctx, [&]() -> int {
       if (v1_d64) TSD_FAIL(TSD_E_SHAPE, "flash attention: head dim %d unsupported", a.d);
       return launch_flash_attention(ctx, a);

@@ -20,6 +20,9 @@ struct AttnK {
   int xcd_map;         // 1: (head, query tile) remapped so that every XCD (dispatch id % 8) owns whole heads - its L2 then pulls a head's
                        // K / V^T once instead of every XCD pulling every head's (needs B*H % 8 == 0)
   int* exact_ctr;      // the context's count of workgroups that had to run the exact pass (tsd_debug_attn_exact_passes)
+  // windowed self attention (flash_attn_win_kernel only; 0 = not windowed): the sample's tokens are a grid_h x grid_w grid cut into
+  // win x win windows, Sq = Sk = Skv = win * win is ONE window's problem and Q / K / V^T / O keep the whole grid's rows
+  int win, grid_h, grid_w;
 };
 
 // Largest score (log2 units, relative to the running reference) a tile may reach before the reference is moved.

@@ -127,7 +127,9 @@ struct AttnPlan {
   int diag = 0, xcd_map = 0;
   int softmax = 0;
 };
-AttnPlan attn_plan(const TsdOptions& opt, int B, int H, int d, int Sq, int Sk);
+// nwin > 0: a windowed launch (AttnArgs::win) - Sq = Sk = win * win is one window's shape and the nwin windows of a sample stand in the
+// grid test beside its heads; the 8-wave kernel is never chosen.
+AttnPlan attn_plan(const TsdOptions& opt, int B, int H, int d, int Sq, int Sk, int nwin = 0);
 // What launch_small_linear launched (kernels_elementwise.hip), left in tsd_ctx::sl_last; tsd_debug_elem_run reports it.
 struct SmallLinearPlan {
   int nb = 0;      // the k_small_linear<NB> instance: 1, 2, 4, 8 or 16; 0 = none ran
@@ -663,8 +665,12 @@ struct AttnArgs {
   half_t* O = nullptr; int ldo = 0; int64_t sO = 0;          // O[b][s][h*d + j]
   int B = 0, H = 0, d = 0, Sq = 0, Sk = 0;
   float scale = 1.f;
+  // windowed self attention (HyperTile): win > 0 cuts the grid_h x grid_w token grid (Sq = Sk = grid_h * grid_w, row-major) into
+  // win x win windows and every query attends to the keys of its own window only.  win in {8, 16, 32, 64, 128} divides both sides.
+  int win = 0, grid_h = 0, grid_w = 0;
 };
 bool attn_fused_supported(int d);
+bool attn_window_side_ok(int win);  // 8, 16, 32, 64, 128
 
 // IP-Adapter's decoupled cross attention (kernels_ipattn.hip states the formula): O <- rn16(O + s_b * Attn(Q, K_ip, V_ip)) in place over
 // N <= 16 image tokens, one launch.  K: [b][j][h*d + c] token-major, at least N rows; Vt: [b][h*d + c][j], ldvt >= 16 (keys j >= N of

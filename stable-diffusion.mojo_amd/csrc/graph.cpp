@@ -187,9 +187,30 @@ int g_resblock(tsd_ctx* ctx, const CatSrc& x, int B, int Hin, int Win, int ups, 
   return TSD_OK;
 }
 
+// The window side of a self-attention block whose token grid is H x W in a forward at LH latent rows: the model's table entry of the
+// level the grid belongs to (the stride-2 convolutions halve rounding up, so level l has ceil(LH / 2^l) rows); 0 (whole grid) without an
+// entry or when the grid is one window.  An active window that does not divide the grid is refused, and so is a grid that is no level
+// of this forward while any entry is set - never a silent fall-back to the whole grid.
+int attn_window_for(const tsd_model* m, int LH, int H, int W, int* win) {
+  *win = 0;
+  int l = 0, h = LH;
+  while (l < 3 && h > H) { h = (h + 1) / 2; l++; }
+  if (h != H) {
+    if (m->attn_win[0] || m->attn_win[1] || m->attn_win[2] || m->attn_win[3])
+      TSD_FAIL(TSD_E_SHAPE, "windowed attention: a %d x %d token grid is no level of a forward at %d latent rows", H, W, LH);
+    return TSD_OK;
+  }
+  const int w = m->attn_win[l];
+  if (!w || (H == w && W == w)) return TSD_OK;
+  if (H % w || W % w)
+    TSD_FAIL(TSD_E_SHAPE, "windowed attention: window side %d of level %d does not divide its %d x %d token grid", w, l, H, W);
+  *win = w;
+  return TSD_OK;
+}
+
 // `Unet_Attention_Block.forward` diffusion.mojo:112-147 on NHWC tokens
 int g_unet_attn(tsd_ctx* ctx, const Act& x, const AttnW& w, const half_t* ctx16, int T, int Tp, Act& out,
-                const CtxKV* pre, const IpKV* ipkv) {
+                const CtxKV* pre, const IpKV* ipkv, int win) {
   const int C = w.C, B = x.B, S = x.H * x.W, d = w.n_embed, Hh = w.n_head;
   const int64_t M = (int64_t)B * S;
   if (C % 64 || x.C != C) TSD_FAIL(TSD_E_SHAPE, "attention block: C=%d (input %d) unsupported", C, x.C);
@@ -264,7 +285,9 @@ int g_unet_attn(tsd_ctx* ctx, const Act& x, const AttnW& w, const half_t* ctx16,
   fa.Vt = vt; fa.ldvt = Sp; fa.sVt = (int64_t)C * Sp;
   fa.O = ao; fa.ldo = C; fa.sO = (int64_t)S * C;
   fa.B = B; fa.H = Hh; fa.d = d; fa.Sq = S; fa.Sk = S; fa.scale = scale;
+  if (win) { fa.win = win; fa.grid_h = x.H; fa.grid_w = x.W; }  // self attention only: the cross-attention launch below clears it
   TSD_TRY(launch_flash_attention(ctx, fa));
+  fa.win = 0; fa.grid_h = 0; fa.grid_w = 0;
   // context keys / values of this block: projected once for all blocks by g_unet_forward, or here (block-level entry)
   CtxKV kv;
   if (pre) kv = *pre;  // context K / V^T of all nine blocks were projected in two batched GEMMs (g_unet_forward)
@@ -602,7 +625,9 @@ int g_unet_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, 
     CtxKV kv;
     kv.K = kc_all + w.kv_off; kv.ldk = CK; kv.sK = (int64_t)Tp * CK;
     kv.Vt = vtc_all + (int64_t)w.kv_off * Tp; kv.ldvt = Tp; kv.sVt = (int64_t)CK * Tp;
-    return g_unet_attn(ctx, a[i - 1], w, ctx16, T, Tp, a[i], &kv);
+    int win = 0;
+    TSD_TRY(attn_window_for(m, LH, a[i - 1].H, a[i - 1].W, &win));
+    return g_unet_attn(ctx, a[i - 1], w, ctx16, T, Tp, a[i], &kv, nullptr, win);
   };
   // encoders (diffusion.mojo:236-250)
   TSD_TRY(alloc_out(1, LH, LW, 320));
@@ -756,7 +781,9 @@ static int unet_full_steps(const FullRun& f, int i0, int i1, Act& cur, std::vect
         ik.Vt = f.ip->vt_all + (int64_t)iw.kv_off[i] * IP_MAX_TOKENS; ik.ldvt = IP_MAX_TOKENS; ik.sVt = (int64_t)IK * IP_MAX_TOKENS;
         ik.N = f.ip->N; ik.scale = f.ip->scale;
       }
-      TSD_TRY(g_unet_attn(ctx, cur, w, f.ctx16, f.T, f.Tp, y, &kv, f.ip ? &ik : nullptr));
+      int win = 0;
+      TSD_TRY(attn_window_for(m, f.LH, cur.H, cur.W, &win));
+      TSD_TRY(g_unet_attn(ctx, cur, w, f.ctx16, f.T, f.Tp, y, &kv, f.ip ? &ik : nullptr, win));
     }
     cur = y;
     if (st.flags & U_PUSH) {

@@ -69,8 +69,10 @@ struct IpKV {
   int N = 0;
   const float* scale = nullptr;
 };
+// win: the window side of the block's self attention (0 = whole grid), as attn_window_for gives it
+int attn_window_for(const tsd_model* m, int LH, int H, int W, int* win);
 int g_unet_attn(tsd_ctx* ctx, const Act& x, const AttnW& w, const half_t* ctx16, int T, int Tp, Act& out,
-                const CtxKV* pre = nullptr, const IpKV* ipkv = nullptr);
+                const CtxKV* pre = nullptr, const IpKV* ipkv = nullptr, int win = 0);
 int g_vae_attn(tsd_ctx* ctx, const Act& x, const VaeAttnW& w, Act& out);
 int g_attn_core(tsd_ctx* ctx, const AttnArgs& fa);
 int g_qkv_proj(tsd_ctx* ctx, const half_t* x, int B, int S, int C, const LinW& in_proj, half_t* qk, half_t* vt, int Sp);

@@ -56,8 +56,16 @@ __device__ unsigned long long g_attn_ts[4 * 65536];  // per block: memtime start
 // CU's whole LDS bandwidth, before the tile DMA writes.  QB = 2 (d = 40: 64 queries per wave, 256 per workgroup) halves
 // that at the price of 2 waves per SIMD instead of 4.
 
-template <int D, int QB>
-__global__ __launch_bounds__(256, D == 40 ? 6 - 2 * QB : D == 64 ? TSD_ATTN64_WGS : 2) void flash_attn_kernel(const AttnK p) {
+// WIN (windowed self attention, HyperTile): the token grid grid_h x grid_w of a sample is cut into win x win windows and the kernel solves
+// one plain Sq = Sk = win^2 problem per (sample, head, window) on the rows where they lie - no gather, no scatter.  blockIdx.x counts
+// (window, query tile of the window); window-local index i is token (wy*win + i / win) * grid_w + wx*win + i % win.  What makes this free
+// in the key loop: win is a power of two >= 8, so a 64-key tile is 64 / win whole window rows (win <= 64) or a piece of one (win >= 64)
+// and a 16-byte V^T chunk of 8 keys never straddles a window row - the per-lane DMA offsets of a tile are the same for every tile of
+// every window and only the scalar tile offset moves.  A window holds whole 64-key tiles: no partial tile, no pad column, no masking.
+// Everything else - swizzles, pitches, ones row, both softmax passes, the counter - is the plain kernel's on the window's problem, so a
+// windowed launch gives the bits of the plain instantiation on window-major gathered operands.
+template <int D, int QB, bool WIN>
+__device__ __forceinline__ void flash_attn_body(const AttnK& p) {
   constexpr int NST = 2;                   // K / V^T tile buffers
   constexpr int DCH = D / 8;               // 16-B chunks per K row
   constexpr int KSTEPS = (DCH + 1) / 2;    // QK^T k-steps (16 wide)
@@ -96,6 +104,16 @@ __global__ __launch_bounds__(256, D == 40 ? 6 - 2 * QB : D == 64 ? TSD_ATTN64_WG
     bh = (id & 7) + 8 * (j / nq);
   }
   const int b = bh / p.H, h = bh - b * p.H;
+  // windowed: p.Sq = p.Sk = win^2 (the window's problem); tok() maps a window-local index to its token row, all of it scalar but i
+  int wbase = 0, wsh = 0, wmask = 0;
+  if constexpr (WIN) {
+    const int nqt = (p.Sq + 128 * QB - 1) / (128 * QB), wdw = bx / nqt, nwx = p.grid_w / p.win;
+    bx -= wdw * nqt;
+    const int wy = wdw / nwx, wx = wdw - wy * nwx;
+    wbase = (wy * p.grid_w + wx) * p.win;
+    wsh = __builtin_ctz(p.win); wmask = p.win - 1;
+  }
+  auto tok = [&](int i) { return WIN ? wbase + (i >> wsh) * p.grid_w + (i & wmask) : i; };
   const int q0 = bx * (128 * QB) + wave * (32 * QB);
 
   const half_t* Qb = p.Q + b * p.sQ + h * D;
@@ -108,7 +126,7 @@ __global__ __launch_bounds__(256, D == 40 ? 6 - 2 * QB : D == 64 ? TSD_ATTN64_WG
   for (int qb = 0; qb < QB; qb++) {
     int qrow = q0 + qb * 32 + l31;
     if (qrow >= p.Sq) qrow = p.Sq - 1;
-    const half_t* qp = Qb + (long long)qrow * p.ldq;
+    const half_t* qp = Qb + (long long)tok(qrow) * p.ldq;
 #pragma unroll
     for (int ks = 0; ks < KSTEPS; ks++) {
       const int ch = ks * 2 + hi;
@@ -134,14 +152,14 @@ __global__ __launch_bounds__(256, D == 40 ? 6 - 2 * QB : D == 64 ? TSD_ATTN64_WG
   // tile position in the scalar offset, zero fill from the range check - no address VALU in the loop.
   // K tile: slot = row*KPITCH + pos ; LDS row `row` holds key k0 + pi(row), pi swaps bits 2 and 3.  Keys >= Sk fall
   // outside the descriptor (it ends after row Sk-1) and read as zeros; their scores are masked below anyway.
-  const rsrc_t rK = make_rsrc(Kb, p.Sk * p.ldk * 2);
+  const rsrc_t rK = make_rsrc(Kb, (WIN ? p.grid_h * p.grid_w : p.Sk) * p.ldk * 2);
   unsigned k_voff[K_PW];
 #pragma unroll
   for (int i = 0; i < K_PW; i++) {
     const int slot = (wave + 4 * i) * 64 + lane;
     const int row = slot / KPITCH, pos = slot - row * KPITCH;
     const int key = (row & ~12) | ((row & 4) << 1) | ((row & 8) >> 1);
-    k_voff[i] = pos < DCH ? (unsigned)(key * p.ldk + pos * 8) * 2 : PAD_OFF;
+    k_voff[i] = pos < DCH ? (unsigned)((WIN ? tok(key) - wbase : key) * p.ldk + pos * 8) * 2 : PAD_OFF;
   }
   // V^T tile: LDS row R (= channel within head) x 8 chunks; phys pos holds logical chunk pos ^ ((R>>1)&7).  A row
   // is a run of keys inside a longer pitch, so a chunk past the last valid key is NOT out of the descriptor's
@@ -153,7 +171,7 @@ __global__ __launch_bounds__(256, D == 40 ? 6 - 2 * QB : D == 64 ? TSD_ATTN64_WG
   for (int i = 0; i < V_PW; i++) {
     const int R = (wave + 4 * i) * 8 + (lane >> 3);
     const int c = (lane & 7) ^ ((R >> 1) & 7);
-    v_voff[i] = R < D ? (unsigned)(R * p.ldvt + c * 8) * 2 : PAD_OFF;
+    v_voff[i] = R < D ? (unsigned)(R * p.ldvt + (WIN ? tok(c * 8) - wbase : c * 8)) * 2 : PAD_OFF;
     v_voff_last[i] = ((ntiles - 1) * 64 + c * 8 + 8 <= p.Skv) ? v_voff[i] : PAD_OFF;
   }
 
@@ -163,7 +181,7 @@ __global__ __launch_bounds__(256, D == 40 ? 6 - 2 * QB : D == 64 ? TSD_ATTN64_WG
 #endif
     char* sK = smem + buf * BUF_BYTES;
     char* sV = sK + K_BYTES;
-    const int k0 = t * 64;
+    const int k0 = tok(t * 64);  // first token of the tile (windowed: of its first window row)
     const bool last = t == ntiles - 1;  // wave-uniform
 #pragma unroll
     for (int i = 0; i < K_PW; i++) {
@@ -203,7 +221,7 @@ __global__ __launch_bounds__(256, D == 40 ? 6 - 2 * QB : D == 64 ? TSD_ATTN64_WG
     if (p.diag) {
       int krow = q0 + qb * 32 + l31;
       if (krow >= p.Sk) krow = p.Sk - 1;
-      const half_t* kp = Kb + (long long)krow * p.ldk;
+      const half_t* kp = Kb + (long long)tok(krow) * p.ldk;
       f16v sd;
 #pragma unroll
       for (int r = 0; r < 16; r++) sd[r] = 0.f;
@@ -486,7 +504,7 @@ __global__ __launch_bounds__(256, D == 40 ? 6 - 2 * QB : D == 64 ? TSD_ATTN64_WG
     const float inv = 1.f / l_tot[qb];
     const int qrow = q0 + qb * 32 + l31;
     if (qrow < p.Sq) {
-      half_t* op = p.O + b * p.sO + (long long)qrow * p.ldo + h * D;
+      half_t* op = p.O + b * p.sO + (long long)tok(qrow) * p.ldo + h * D;
 #pragma unroll
       for (int d = 0; d < DBLK; d++)
 #pragma unroll
@@ -503,6 +521,17 @@ __global__ __launch_bounds__(256, D == 40 ? 6 - 2 * QB : D == 64 ? TSD_ATTN64_WG
   }
 }
 
+template <int D, int QB>
+__global__ __launch_bounds__(256, D == 40 ? 6 - 2 * QB : D == 64 ? TSD_ATTN64_WGS : 2) void flash_attn_kernel(const AttnK p) {
+  flash_attn_body<D, QB, false>(p);
+}
+// The windowed sibling of every instantiation (AttnK::win > 0): same LDS, same registers-per-wave budget - but <40, 1>, which is built for
+// 3 workgroups per CU (168 VGPRs) where the plain kernel is held to 4 (128) and spills one register: no new kernel may touch scratch.
+template <int D, int QB>
+__global__ __launch_bounds__(256, D == 40 ? 4 - QB : D == 64 ? TSD_ATTN64_WGS : 2) void flash_attn_win_kernel(const AttnK p) {
+  flash_attn_body<D, QB, true>(p);
+}
+
 bool attn_fused_supported(int d) { return d == 40 || d == 64 || d == 80 || d == 160; }
 // per-context switches (TsdOptions): attn_diag 0 = optimistic reference from key tile 0 only (the round-2 behaviour);
 // attn_qb_force 0 = kernel chosen by the layer shape, 1 / 2 = that many query blocks per wave (4-wave workgroups) whenever d = 40,
@@ -513,24 +542,28 @@ extern "C" int tsd_debug_set_attn_diag(tsd_ctx* ctx, int on) {
 extern "C" int tsd_debug_set_attn_qb(tsd_ctx* ctx, int mode) {
   return ctx_set_option(ctx, &TsdOptions::attn_qb_force, mode, 0, 3);
 }
-template <int D, int QB>
+// WIN: the windowed sibling (k.Sq = k.Sk = win^2) - one workgroup per (sample, head, window, 128 * QB-query tile of the window)
+template <int D, int QB, bool WIN = false>
 static int launch_fa(tsd_ctx* ctx, const AttnK& k, int B, int H, int Sq) {
   constexpr int DCH = D / 8, KSTEPS = (DCH + 1) / 2, KPITCH = (DCH & 1) ? DCH : ((2 * KSTEPS) | 1), DBLK = (D + 31) / 32;
   constexpr int LDS = 2 * (64 * KPITCH * 16 + DBLK * 32 * 128) + 16;  // + the early-abort flag word
-  auto fn = flash_attn_kernel<D, QB>;
+  auto fn = WIN ? flash_attn_win_kernel<D, QB> : flash_attn_kernel<D, QB>;
   static std::atomic<unsigned long long> attr{0};  // one bit per device
   if (!((attr.load(std::memory_order_relaxed) >> (ctx->device & 63)) & 1)) {
     HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
     attr.fetch_or(1ull << (ctx->device & 63), std::memory_order_relaxed);
   }
-  hipLaunchKernelGGL(fn, dim3(ceil_div(Sq, 128 * QB), B * H), dim3(256), LDS, ctx->stream, k);
+  const int nwin = WIN ? (k.grid_h / k.win) * (k.grid_w / k.win) : 1;
+  hipLaunchKernelGGL(fn, dim3(ceil_div(Sq, 128 * QB) * nwin, B * H), dim3(256), LDS, ctx->stream, k);
   HIP_TRY(hipGetLastError());
   return TSD_OK;
 }
+bool attn_window_side_ok(int win) { return win == 8 || win == 16 || win == 32 || win == 64 || win == 128; }
 
 // The kernel and the switches of one launch, from the options and the layer shape alone (d is a supported head dim).
-AttnPlan attn_plan(const TsdOptions& opt, int B, int H, int d, int Sq, int Sk) {
+AttnPlan attn_plan(const TsdOptions& opt, int B, int H, int d, int Sq, int Sk, int nwin) {
   AttnPlan p;
+  const long long units = (long long)H * (nwin > 0 ? nwin : 1);  // (head, window) pairs of a sample: what fills the grid beside the query tiles
   p.diag = (opt.attn_diag && Sq == Sk) ? 1 : 0;
   // long key loops only (the K / V^T stream of a head is what the remap saves); results do not depend on the block order.
   // Measured (profiles/r03_attn_xcd_ab.txt): FETCH_SIZE of the 4096 x 4096 d = 40 call 366 -> 144 MB, of the 1024 x 1024 d = 80 call
@@ -545,8 +578,9 @@ AttnPlan attn_plan(const TsdOptions& opt, int B, int H, int d, int Sq, int Sk) {
       // workgroup repeats exactly (the repeat is decided per 128- / 256-query workgroup and moves the reference per 32 / 64
       // rows), so a sample computed alone must run the same variant as its row of a batch (bitwise batch invariance).
       // Eight waves in two staggered groups (kernels_attn8.hip) for the long key loops of a big grid - the 64x64 level's 4096 x 4096 call
-      if (opt.attn_qb_force ? opt.attn_qb_force == 3 : (opt.attn_wg8 && Sk >= 512 && (long long)ceil_div(Sq, 512) * H >= 64)) p.kernel = 3;
-      else if (opt.attn_qb_force ? opt.attn_qb_force == 2 : (opt.attn_qb == 2 && Sk >= 512 && (long long)ceil_div(Sq, 256) * H >= 64)) p.kernel = 2;
+      // A windowed launch (nwin > 0) is held to the same rules on the window's shape, its windows counting like heads; it has no 8-wave form.
+      if (nwin <= 0 && (opt.attn_qb_force ? opt.attn_qb_force == 3 : (opt.attn_wg8 && Sk >= 512 && (long long)ceil_div(Sq, 512) * H >= 64))) p.kernel = 3;
+      else if (opt.attn_qb_force ? opt.attn_qb_force == 2 : (opt.attn_qb == 2 && Sk >= 512 && (long long)ceil_div(Sq, 256) * units >= 64)) p.kernel = 2;
       else p.kernel = 1;
       break;
     case 80: p.kernel = 4; break;
@@ -560,6 +594,14 @@ int launch_flash_attention(tsd_ctx* ctx, const AttnArgs& a) {
   if (!attn_fused_supported(a.d)) TSD_FAIL(TSD_E_SHAPE, "flash attention: head dim %d unsupported", a.d);
   if (a.ldq % 8 || a.ldk % 8 || a.ldvt % 8 || a.ldo % 4) TSD_FAIL(TSD_E_SHAPE, "flash attention: misaligned pitches");
   if (a.Sq <= 0 || a.Sk <= 0) TSD_FAIL(TSD_E_SHAPE, "flash attention: empty sequence");
+  if (a.win) {  // every tile of a window must lie inside the grid: checked here, the kernel masks nothing
+    if (!attn_window_side_ok(a.win)) TSD_FAIL(TSD_E_ARG, "windowed attention: window side %d (8, 16, 32, 64 or 128)", a.win);
+    if (a.grid_h <= 0 || a.grid_w <= 0 || (long long)a.grid_h * a.grid_w != a.Sq || a.Sq != a.Sk)
+      TSD_FAIL(TSD_E_SHAPE, "windowed attention: a %d x %d grid with Sq = %d, Sk = %d (self attention over the whole grid)", a.grid_h, a.grid_w, a.Sq, a.Sk);
+    if (a.grid_h % a.win || a.grid_w % a.win)
+      TSD_FAIL(TSD_E_SHAPE, "windowed attention: window side %d does not divide the %d x %d token grid", a.win, a.grid_h, a.grid_w);
+    if (a.ldvt < a.Sk) TSD_FAIL(TSD_E_SHAPE, "windowed attention: V^T pitch %d below the %d tokens of the grid", a.ldvt, a.Sk);
+  }
   if (!ctx->launch()) return TSD_OK;
   ProfScope prof(ctx, KC_ATTN, a.Sq, a.Sk, a.d, a.B * a.H);
   AttnK k;
@@ -569,6 +611,22 @@ int launch_flash_attention(tsd_ctx* ctx, const AttnArgs& a) {
   k.H = a.H; k.Sq = a.Sq; k.Sk = a.Sk; k.Skv = std::min(round_up(a.Sk, 8), a.ldvt);
   k.c = a.scale * 1.4426950408889634f;
   k.exact_ctr = ctx->status + 2;
+  k.win = 0; k.grid_h = 0; k.grid_w = 0;
+  if (a.win) {
+    k.win = a.win; k.grid_h = a.grid_h; k.grid_w = a.grid_w;
+    k.Sq = k.Sk = k.Skv = a.win * a.win;
+    const AttnPlan wp = attn_plan(ctx->opt, a.B, a.H, a.d, k.Sq, k.Sk, (a.grid_h / a.win) * (a.grid_w / a.win));
+    ctx->attn_last = wp;
+    k.diag = wp.diag;
+    k.xcd_map = wp.xcd_map;
+    switch (wp.kernel) {
+      case 2: return launch_fa<40, 2, true>(ctx, k, a.B, a.H, k.Sq);
+      case 1: return launch_fa<40, 1, true>(ctx, k, a.B, a.H, k.Sq);
+      case 4: return launch_fa<80, 1, true>(ctx, k, a.B, a.H, k.Sq);
+      case 6: return launch_fa<64, 1, true>(ctx, k, a.B, a.H, k.Sq);
+      default: return launch_fa<160, 1, true>(ctx, k, a.B, a.H, k.Sq);
+    }
+  }
   const AttnPlan plan = attn_plan(ctx->opt, a.B, a.H, a.d, a.Sq, a.Sk);
   ctx->attn_last = plan;
   k.diag = plan.diag;
@@ -594,7 +652,7 @@ extern "C" int tsd_debug_attn_exact_passes(tsd_ctx* ctx, int reset) {
 }
 
 // Debug/bench entry: time `iters` launches of the fused attention core on synthetic device data.
-extern "C" int tsd_debug_attn_bench(tsd_ctx* ctx, int B, int H, int d, int Sq, int Sk, int iters, float* ms) {
+static int attn_bench(tsd_ctx* ctx, int B, int H, int d, int Sq, int Sk, int iters, float* ms, int win, int grid_h, int grid_w) {
   if (!ctx || !ms || iters <= 0) TSD_FAIL(TSD_E_ARG, "attn_bench: bad argument");
   HIP_TRY(hipSetDevice(ctx->device));
   const int C = H * d, Skp = round_up(Sk, 8);
@@ -617,6 +675,7 @@ extern "C" int tsd_debug_attn_bench(tsd_ctx* ctx, int B, int H, int d, int Sq, i
   a.Q = Q; a.ldq = C; a.sQ = (int64_t)Sq * C; a.K = K; a.ldk = C; a.sK = (int64_t)Sk * C;
   a.Vt = Vt; a.ldvt = Skp; a.sVt = (int64_t)C * Skp; a.O = O; a.ldo = C; a.sO = (int64_t)Sq * C;
   a.B = B; a.H = H; a.d = d; a.Sq = Sq; a.Sk = Sk; a.scale = 1.f / sqrtf((float)d);
+  a.win = win; a.grid_h = grid_h; a.grid_w = grid_w;
   int r = launch_flash_attention(ctx, a);
   if (r != TSD_OK) return r;
   HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
@@ -644,4 +703,12 @@ extern "C" int tsd_debug_attn_bench(tsd_ctx* ctx, int B, int H, int d, int Sq, i
 #endif
   ctx->arena.top = 0;
   return r;
+}
+extern "C" int tsd_debug_attn_bench(tsd_ctx* ctx, int B, int H, int d, int Sq, int Sk, int iters, float* ms) {
+  return attn_bench(ctx, B, H, d, Sq, Sk, iters, ms, 0, 0, 0);
+}
+// The same on a grid_h x grid_w token grid cut into win x win windows (win = 0: the plain call over the whole grid).
+extern "C" int tsd_debug_attn_bench_win(tsd_ctx* ctx, int B, int H, int d, int grid_h, int grid_w, int win, int iters, float* ms) {
+  if (grid_h <= 0 || grid_w <= 0 || (long long)grid_h * grid_w > (1 << 20)) TSD_FAIL(TSD_E_ARG, "attn_bench_win: bad grid");
+  return attn_bench(ctx, B, H, d, grid_h * grid_w, grid_h * grid_w, iters, ms, win, win ? grid_h : 0, win ? grid_w : 0);
 }

@@ -233,6 +233,9 @@ struct tsd_model {
   // FP8 feed-forward (tsd_model_set_ff_fp8; Diffusion and ControlNet kinds): read by model_build_derived, which fills AttnW::ff8_*
   bool ff_fp8 = false;
   float freeu_b[TSD_FREEU_BLOCKS] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1}, freeu_s[TSD_FREEU_BLOCKS] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
+  // Windowed self attention (tsd_model_set_attn_window; UNets and ControlNets): window side per level l (token grid LH / 2^l x LW / 2^l),
+  // 0 = off.  Read by g_unet_attn's callers at enqueue time through attn_window_for.
+  int attn_win[4] = {0, 0, 0, 0};
 };
 
 int model_resolve(tsd_model* m);                      // fill unet / vae from the packed blob

@@ -153,6 +153,7 @@ def _declare(l):
         "tsd_debug_ip_attn_run": ([vp, C.POINTER(i64), i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)], i),
         "tsd_debug_ip_attn_bench": ([vp, i, i, i, i, i, i, fp], i),
         "tsd_clip_image_patches_f16": ([vp, fp, i, i, i, vp], i),
+        "tsd_model_set_attn_window": ([vp, C.POINTER(i)], i), "tsd_model_attn_window": ([vp, C.POINTER(i)], i),
         "tsd_model_set_freeu": ([vp, fp, fp, i], i), "tsd_model_freeu": ([vp, fp, fp, C.POINTER(i)], i),
         "tsd_freeu_f16": ([vp, vp, vp, i, i, i, i, i, f, f, i, vp, vp], i),
         "tsd_debug_freeu_run": ([vp, vp, vp, i, i, i, i, i, i, i, i, f, f, i, vp, vp], i),
@@ -210,6 +211,7 @@ def _declare(l):
         "tsd_debug_set_fused_attention": ([vp, i], i),
         "tsd_debug_gemm_bench": ([vp, i, i, i, i, i, i, i, i, i, i, fp], i),
         "tsd_debug_attn_bench": ([vp, i, i, i, i, i, i, fp], i),
+        "tsd_debug_attn_bench_win": ([vp, i, i, i, i, i, i, i, fp], i),
         "tsd_debug_attn_exact_passes": ([vp, i], i),
         "tsd_debug_set_attn_qb": ([vp, i], i),
         "tsd_debug_set_attn_diag": ([vp, i], i),

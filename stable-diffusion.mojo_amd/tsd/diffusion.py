@@ -5,6 +5,7 @@ structs (`Time_Embedding`, `Unet_Residual_Block`, `Unet_Attention_Block`, `UNet_
 one C call per block with host weights, and `UNet` composes them exactly like diffusion.mojo:228-273 -
 the per-struct drop-in surface.
 """
+import contextlib
 import ctypes as C
 
 import numpy as np
@@ -150,7 +151,54 @@ class UNet_Output_Layer:
         return self.layer2.forward(out)
 
 
-class Diffusion:
+def attn_window_table(win):
+    """None | int (level 0) | 4 ints -> the table of `tsd_model_set_attn_window`."""
+    if win is None:
+        return (0, 0, 0, 0)
+    if isinstance(win, (int, np.integer)):
+        return (int(win), 0, 0, 0)
+    t = tuple(int(v) for v in win)
+    if len(t) != 4:
+        raise ValueError(f"attn_window is an int (the top level's window side) or 4 sides, one per level; got {win!r}")
+    return t
+
+
+@contextlib.contextmanager
+def attn_window_scope(model, win):
+    """`generate(attn_window=...)`: the model's previous table is back on every way out."""
+    if win is None:
+        yield
+        return
+    prev = model.attn_window
+    model.set_attn_window(win)
+    try:
+        yield
+    finally:
+        model.set_attn_window(prev)
+
+
+class _AttnWindow:
+    """`set_attn_window` / `attn_window` of the models that have self-attention blocks (Diffusion, ControlNet)."""
+
+    def set_attn_window(self, win=None):
+        """Windowed self attention (HyperTile; `tsd_model_set_attn_window`): an int is the window side in tokens of the top level's
+        self-attention blocks, a 4-tuple gives one side per level l (token grid LH / 2^l x LW / 2^l); sides are 0 (off), 8, 16, 32, 64 or 128
+        and must divide the grid of every forward.  None or zeros turn it off.  State of the model: it acts from the next forward on, a
+        step of an open `Session` included."""
+        t = attn_window_table(win)
+        check(lib().tsd_model_set_attn_window(self.model.h, (C.c_int * 4)(*t)))
+
+    @property
+    def attn_window(self):
+        """The model's window table, a 4-tuple of sides (all zeros = off)."""
+        out = (C.c_int * 4)()
+        on = lib().tsd_model_attn_window(self.model.h, out)
+        if on < 0:
+            check(on)
+        return tuple(int(v) for v in out)
+
+
+class Diffusion(_AttnWindow):
     """`Diffusion` diffusion.mojo:294-318 - device-resident weights; forward is ONE libtsd call.
 
     forward(x, context, time): x (4,LH,LW) or (B,4,LH,LW), square or not; context (T,768)/(1,T,768) or (B,T,768);
@@ -346,7 +394,7 @@ CONTROL_RESIDUAL_SHAPES = ((320, 1), (320, 1), (320, 1), (320, 2), (640, 2), (64
                            (1280, 8), (1280, 8))
 
 
-class ControlNet:
+class ControlNet(_AttnWindow):
     """ControlNet of the full-size UNet (Zhang et al. 2023; the layout of diffusers' `ControlNetModel`) - device-resident weights.
 
     variant: "controlnet_sd15" (the reference's norms, pairs with "diffusion_sd15") or "controlnet_sd15_torch" (the norm semantics and
