@@ -1199,7 +1199,18 @@ int tsd_debug_attn_bench_win(tsd_ctx* ctx, int B, int H, int d, int grid_h, int 
  *   every block that runs op by op (C = 640 / 1280; C = 320 where the fused tail kernel does not apply) runs LayerNorm -> quantise ->
  *   e4m3 GEMM (GEGLU) -> quantise -> e4m3 GEMM (+ bias + residual) -> the fp16 output convolution; the residual stream never passes through
  *   8 bits.  Setting it is a parameter change: an open session picks it up at its next upload().  Off (the default, and after turning it
- *   off again): the launches and bits of before.  tsd_model_ff_fp8: 1 / 0, negative for a NULL model or a wrong kind. */
+ *   off again): the launches and bits of before.  tsd_model_ff_fp8: 2 / 1 / 0, negative for a NULL model or a wrong kind.
+ * MXFP4 weights (W4A8), tsd_model_set_ff_fp8(m, 2): the same blocks and launches as under 1, the activations e4m3 as above, the weights of
+ *   geglu1 / geglu2 in OCP MX v1.0 form and the GEMM on the same instruction with the e2m1 format and e8m0 block scales on the weight side.
+ *   Weight format, per row of w [N][K] fp16 (pitch ld; K a multiple of 32, TSD_E_SHAPE otherwise) and block b of 32 consecutive k:
+ *     amax = max |w|    scale byte s = floor(log2 amax) - 2 + 127 (e8m0: X = 2^(s - 127))    element = e2m1_rne(w / X) saturated to +-6
+ *   e2m1 codes 0 .. 7 = 0, 0.5, 1, 1.5, 2, 3, 4, 6 with bit 3 the sign, ties to the even code; two elements to a byte, element 2i in the low
+ *   nibble of byte i.  An all-zero block: s = 127 and zero nibbles.  Columns K .. Kp - 1 (Kp = K rounded up to 128): zero nibbles, s = 127.
+ *   A non-finite weight has no e2m1 form: TSD_E_NONFINITE (from tsd_quant_weights_mxfp4, and from the model's preparation under mode 2).
+ * tsd_quant_weights_mxfp4: w_f16 [N][ld] -> elems_out [N][Kp / 2] bytes and scales_out [N][Kp / 32] bytes, plain row-major.
+ * tsd_mxfp4_gemm_f16: out[m][n] = rn16(epi(sa[m] * sum_k a8[m][k] * X[n][k / 32] * w4[n][k])) on a8 [M][Kp] e4m3 bytes and that plain form
+ *   (w4 [N][Kp / 2], scales [N][Kp / 32]), which it re-lays tile-major on the device as the model's streams are; bias, residual, epi, pitches as
+ *   for tsd_fp8_gemm_f16; there is no per-channel weight scale.  Both on host arrays, synchronous. */
 enum { TSD_FP8_EPI_NONE = 0, TSD_FP8_EPI_GEGLU = 1 };
 int tsd_model_set_ff_fp8(tsd_model* m, int on);
 int tsd_model_ff_fp8(const tsd_model* m);
@@ -1207,6 +1218,9 @@ int tsd_quant_rows_e4m3(tsd_ctx* ctx, const void* x_f16, int M, int K, int ld, v
 int tsd_fp8_gemm_f16(tsd_ctx* ctx, const void* a8, const float* sa, const void* w8, const float* sw, const float* bias, const void* residual,
                      int ldr, int M, int N, int K, int epi, void* out, int ldo);
 int tsd_linear_fp8_f32(tsd_ctx* ctx, const float* x, int M, int K, const float* w, const float* bias, int N, float* y);
+int tsd_quant_weights_mxfp4(tsd_ctx* ctx, const void* w_f16, int N, int K, int ld, void* elems_out, void* scales_out);
+int tsd_mxfp4_gemm_f16(tsd_ctx* ctx, const void* a8, const float* sa, const void* w4, const void* scales, const float* bias,
+                       const void* residual, int ldr, int M, int N, int K, int epi, void* out, int ldo);
 
 /* ---- census -------------------------------------------------------------------------- */
 /* Algorithmic GFLOP (2*MAC of conv + linear + attention core) of one forward per sample

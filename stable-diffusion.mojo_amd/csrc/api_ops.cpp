@@ -497,6 +497,55 @@ extern "C" int tsd_fp8_gemm_f16(tsd_ctx* ctx, const void* a8, const float* sa, c
   });
 }
 
+// MXFP4 weights: the quantiser in its plain row-major form, and the W4A8 GEMM on that form - tiled here by the launch the model's streams
+// share their layout code with (kernels_fp8.hip)
+extern "C" int tsd_quant_weights_mxfp4(tsd_ctx* ctx, const void* w_f16, int N, int K, int ld, void* elems_out, void* scales_out) {
+  NOTNULL(ctx); NOTNULL(w_f16); NOTNULL(elems_out); NOTNULL(scales_out);
+  if (N <= 0 || N > (1 << 20) || K <= 0 || K % 32 || K > (1 << 17) || ld < K || ld > (1 << 18))
+    TSD_FAIL(TSD_E_SHAPE, "quant_weights_mxfp4: N=%d K=%d (a multiple of 32) pitch %d", N, K, ld);
+  return run_op(ctx, [&]() -> int {
+    Dev d{ctx};
+    const int Kp = round_up(K, 128);
+    const uint16_t* dw = d.in((const uint16_t*)w_f16, (int64_t)N * ld);
+    uint8_t* de = d.buf<uint8_t>((int64_t)N * (Kp / 2));
+    uint8_t* ds = d.buf<uint8_t>((int64_t)N * (Kp / 32));
+    if (d.err) return d.err;
+    TSD_TRY(launch_quant_weights_mxfp4(ctx, (const half_t*)dw, N, K, ld, de, ds));
+    TSD_TRY(d.out((uint8_t*)elems_out, (const uint8_t*)de, (int64_t)N * (Kp / 2)));
+    return d.out((uint8_t*)scales_out, (const uint8_t*)ds, (int64_t)N * (Kp / 32));
+  });
+}
+
+extern "C" int tsd_mxfp4_gemm_f16(tsd_ctx* ctx, const void* a8, const float* sa, const void* w4, const void* scales, const float* bias,
+                                  const void* residual, int ldr, int M, int N, int K, int epi, void* out, int ldo) {
+  NOTNULL(ctx); NOTNULL(a8); NOTNULL(sa); NOTNULL(w4); NOTNULL(scales); NOTNULL(out);
+  if (epi != TSD_FP8_EPI_NONE && epi != TSD_FP8_EPI_GEGLU) TSD_FAIL(TSD_E_ARG, "mxfp4_gemm: epilogue %d (0 none, 1 GEGLU)", epi);
+  if (M <= 0 || M > (1 << 24) || N <= 0 || N % 16 || N > (1 << 20) || K <= 0 || K % 32 || K > (1 << 17) || ldo <= 0 || ldo > (1 << 20) ||
+      (residual && (ldr <= 0 || ldr > (1 << 20))))
+    TSD_FAIL(TSD_E_SHAPE, "mxfp4_gemm: M=%d N=%d (a multiple of 16) K=%d (a multiple of 32) pitches %d / %d", M, N, K, ldo, ldr);
+  return run_op(ctx, [&]() -> int {
+    Dev d{ctx};
+    const int Kp = round_up(K, 128);
+    Fp8GemmArgs g;
+    g.A8 = d.in((const uint8_t*)a8, (int64_t)M * Kp); g.sa = d.in(sa, M);
+    const uint8_t* de = d.in((const uint8_t*)w4, (int64_t)N * (Kp / 2));
+    const uint8_t* ds = d.in((const uint8_t*)scales, (int64_t)N * (Kp / 32));
+    uint8_t* stream = d.buf<uint8_t>((int64_t)mxfp4_stream_bytes(N, K));
+    g.W4 = stream;
+    g.M = M; g.N = N; g.K = K; g.ldo = ldo;
+    if (bias) { g.bias = d.in(bias, N); g.epi |= EPI_BIAS_N; }
+    if (residual) { g.R = (const half_t*)d.in((const uint16_t*)residual, (int64_t)M * ldr); g.ldr = ldr; g.epi |= EPI_RESIDUAL; }
+    if (epi == TSD_FP8_EPI_GEGLU) g.epi |= EPI_GEGLU;
+    // the caller's output goes up first: what the launch leaves alone (the pitch gap) comes back as it was
+    uint16_t* dout = d.in((const uint16_t*)out, (int64_t)M * ldo);
+    g.out = (half_t*)dout;
+    if (d.err) return d.err;
+    TSD_TRY(launch_tile_mxfp4(ctx, de, ds, N, K, stream));
+    TSD_TRY(launch_gemm_e4m3_mxfp4(ctx, g));
+    return d.out((uint16_t*)out, (const uint16_t*)dout, (int64_t)M * ldo);
+  });
+}
+
 extern "C" int tsd_linear_fp8_f32(tsd_ctx* ctx, const float* x, int M, int K, const float* w, const float* bias, int N, float* y) {
   NOTNULL(x); NOTNULL(w); NOTNULL(y);
   if (M <= 0 || K <= 0 || K > FP8_MAX_K || N <= 0) TSD_FAIL(TSD_E_SHAPE, "linear_fp8: bad dims M=%d K=%d (1..%d) N=%d", M, K, FP8_MAX_K, N);

@@ -578,8 +578,19 @@ struct Fp8GemmArgs {
   half_t* out = nullptr; int ldo = 0;
   int64_t M = 0; int N = 0, K = 0;
   int epi = 0;
+  const uint8_t* W4 = nullptr;  // launch_gemm_e4m3_mxfp4 only, in place of W8 / sw: the tile-major MXFP4 stream of the [N][K] weights
 };
 int launch_gemm_e4m3(tsd_ctx* ctx, const Fp8GemmArgs& a);
+// MXFP4 weights (OCP MX v1.0: e2m1 elements, two to a byte, low nibble first; one e8m0 scale byte per 32 consecutive k of a row; K a
+// multiple of 32, padded to Kp = round_up(K, 128) with zero nibbles under scale byte 127).  w [N][K] fp16 (pitch ld) -> with `scales`:
+// plain row-major elems [N][Kp / 2] and scales [N][Kp / 32]; with scales == nullptr: `elems` is the tile-major stream of
+// mxfp4_stream_bytes(N, K) bytes that launch_gemm_e4m3_mxfp4 reads (kernels_fp8.hip states the layout).  launch_tile_mxfp4 re-lays the
+// plain form as that stream.  A non-finite weight counts into ctx->status: TSD_E_NONFINITE at the caller's ctx_check_status().
+size_t mxfp4_stream_bytes(int N, int K);
+int launch_quant_weights_mxfp4(tsd_ctx* ctx, const half_t* w, int N, int K, int ld, uint8_t* elems, uint8_t* scales);
+int launch_tile_mxfp4(tsd_ctx* ctx, const uint8_t* elems, const uint8_t* scales, int N, int K, uint8_t* stream);
+// out[m][n] = rn16(epi(sa[m] sum_k A8[m][k] X[n][k / 32] W4[n][k])): Fp8GemmArgs with W4 set; W8 and sw are not read
+int launch_gemm_e4m3_mxfp4(tsd_ctx* ctx, const Fp8GemmArgs& a);
 
 // alphas_cumprod of the scaled-linear beta schedule (sampler.mojo:28-32), fp32 like the reference's Tensor
 void sampler_alphas_cumprod(int n_train, std::vector<float>& out);

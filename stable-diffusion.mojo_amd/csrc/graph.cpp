@@ -366,33 +366,35 @@ int g_unet_attn(tsd_ctx* ctx, const Act& x, const AttnW& w, const half_t* ctx16,
   TSD_TRY(launch_layernorm(ctx, tok3, M, C, C, 1e-5f, ln, C, w.ln[2].w ? &w.ln[2] : nullptr));
   half_t* gg = arena_alloc<half_t>(ctx, M * 4 * C); CHECK_ALLOC(gg);
   a.p0 = ln;
-  if (w.ff8_w1 && w.ff8_w2) {
+  const bool ffmx = w.ffmx_w1 && w.ffmx_w2;
+  if ((w.ff8_w1 && w.ff8_w2) || ffmx) {
     // FP8 feed-forward (tsd_model_set_ff_fp8; kernels_fp8.hip): both linears on e4m3 operands, each input quantised per token row just
     // before its GEMM.  The residual tok3 is added in fp32 in the second GEMM's epilogue and the output convolution stays fp16 and
-    // un-folded: the residual stream never passes through 8 bits.
+    // un-folded: the residual stream never passes through 8 bits.  Mode 2 (ffmx): the same launches with the weights as MXFP4 streams.
+    auto ff_gemm = [&](const Fp8GemmArgs& g) { return ffmx ? launch_gemm_e4m3_mxfp4(ctx, g) : launch_gemm_e4m3(ctx, g); };
     uint8_t* q1 = arena_alloc<uint8_t>(ctx, M * round_up(C, 128)); CHECK_ALLOC(q1);
     float* s1 = arena_alloc<float>(ctx, M); CHECK_ALLOC(s1);
     uint8_t* q2 = arena_alloc<uint8_t>(ctx, M * round_up(4 * C, 128)); CHECK_ALLOC(q2);
     float* s2 = arena_alloc<float>(ctx, M); CHECK_ALLOC(s2);
     TSD_TRY(launch_quant_rows_e4m3(ctx, ln, M, C, C, q1, s1));
     Fp8GemmArgs f;
-    f.A8 = q1; f.sa = s1; f.W8 = w.ff8_w1; f.sw = w.ff8_s1; f.bias = w.geglu1.b; f.M = M; f.N = 8 * C; f.K = C;
+    f.A8 = q1; f.sa = s1; f.W8 = w.ff8_w1; f.sw = w.ff8_s1; f.W4 = w.ffmx_w1; f.bias = w.geglu1.b; f.M = M; f.N = 8 * C; f.K = C;
     const int bias1 = w.geglu1.b ? EPI_BIAS_N : 0;
     if (w.gelu_erf) {
       half_t* pre = arena_alloc<half_t>(ctx, M * 8 * C); CHECK_ALLOC(pre);
       f.epi = bias1; f.out = pre; f.ldo = 8 * C;
-      TSD_TRY(launch_gemm_e4m3(ctx, f));
+      TSD_TRY(ff_gemm(f));
       TSD_TRY(launch_geglu_erf_f16(ctx, pre, M, 4 * C, gg));
     } else {
       f.epi = bias1 | EPI_GEGLU; f.out = gg; f.ldo = 4 * C;
-      TSD_TRY(launch_gemm_e4m3(ctx, f));
+      TSD_TRY(ff_gemm(f));
     }
     TSD_TRY(launch_quant_rows_e4m3(ctx, gg, M, 4 * C, 4 * C, q2, s2));
     half_t* tok4 = tok2;  // tok2 is dead after tok3
     Fp8GemmArgs h;
-    h.A8 = q2; h.sa = s2; h.W8 = w.ff8_w2; h.sw = w.ff8_s2; h.bias = w.geglu2.b; h.R = tok3; h.ldr = C; h.M = M; h.N = C; h.K = 4 * C;
+    h.A8 = q2; h.sa = s2; h.W8 = w.ff8_w2; h.sw = w.ff8_s2; h.W4 = w.ffmx_w2; h.bias = w.geglu2.b; h.R = tok3; h.ldr = C; h.M = M; h.N = C; h.K = 4 * C;
     h.epi = (w.geglu2.b ? EPI_BIAS_N : 0) | EPI_RESIDUAL; h.out = tok4; h.ldo = C;
-    TSD_TRY(launch_gemm_e4m3(ctx, h));
+    TSD_TRY(ff_gemm(h));
     a.p0 = tok4;
     TSD_TRY(g_linear(ctx, a, M, w.conv_out.w, w.conv_out.Ipad, C, C, w.conv_out.b, x.p, x.ld, 0, out.p, out.ld, &out, S, w.conv_out.w_tm));
     ctx->arena.release(mark);

@@ -13,7 +13,8 @@ static bool norm_torch(const NormAffine& n) { return n.w && n.b && n.torch_rstd 
 static bool norm_plain(const NormAffine& n) { return !n.w && !n.b; }
 static int attn_block_kind(const AttnW& w) {
   if (norm_plain(w.gn) && norm_plain(w.ln[0]) && norm_plain(w.ln[1]) && norm_plain(w.ln[2]) && !w.gelu_erf) return ATTN_FUSE_PLAIN;
-  if (norm_torch(w.gn) && norm_torch(w.ln[0]) && norm_torch(w.ln[1]) && norm_torch(w.ln[2]) && w.gelu_erf && !w.ff8_w1 && !w.ff8_w2)
+  if (norm_torch(w.gn) && norm_torch(w.ln[0]) && norm_torch(w.ln[1]) && norm_torch(w.ln[2]) && w.gelu_erf && !w.ff8_w1 && !w.ff8_w2 &&
+      !w.ffmx_w1 && !w.ffmx_w2)
     return ATTN_FUSE_TORCH;
   return ATTN_FUSE_NONE;
 }
@@ -170,7 +171,7 @@ static void model_invalidate_derived(tsd_model* m) {
   m->gen++;
   m->unet.res_dup_on = false; m->unet.res_dup = ResW();
   for (auto& a : m->unet.attn) { a.tail_stream = nullptr; a.head_stream = nullptr; a.fold_w = nullptr; a.fold_w_tm = nullptr; a.fold_b = nullptr; }
-  for (auto& a : m->unet.attn) { a.ff8_w1 = nullptr; a.ff8_s1 = nullptr; a.ff8_w2 = nullptr; a.ff8_s2 = nullptr; }
+  for (auto& a : m->unet.attn) { a.ff8_w1 = nullptr; a.ff8_s1 = nullptr; a.ff8_w2 = nullptr; a.ff8_s2 = nullptr; a.ffmx_w1 = nullptr; a.ffmx_w2 = nullptr; }
   m->unet.conv_in_im2col = nullptr;
   m->vae.conv_in_im2col = nullptr;
   for (auto& r : m->unet.res) { r.conv1.w_tm = nullptr; r.conv2.w_tm = nullptr; r.conv1.w_uf = nullptr; }
@@ -476,6 +477,8 @@ extern "C" int tsd_model_lora_count(tsd_model* m) {
 // bytes of a linear layer's e4m3 rows / of its per-channel scales in the derived buffer (256-byte granules)
 static size_t ff8_bytes(const LinW& l) { return ((size_t)l.N * round_up(l.Kpad, 128) + 255) & ~size_t(255); }
 static size_t ff8_scale_bytes(const LinW& l) { return ((size_t)l.N * sizeof(float) + 255) & ~size_t(255); }
+// ... and of its tile-major MXFP4 stream (tsd_model_set_ff_fp8(m, 2))
+static size_t ffmx_bytes(const LinW& l) { return (mxfp4_stream_bytes(l.N, l.Kpad) + 255) & ~size_t(255); }
 
 // derived device buffers (not part of the broadcast blob: every rank rebuilds them from the packed weights)
 static int model_build_derived(tsd_model* m) {
@@ -589,14 +592,15 @@ static int model_build_derived(tsd_model* m) {
         uf_b += (((size_t)16 * c->Opad * c->Ipad * 2) + 255) & ~size_t(255);
       }
   // FP8 feed-forward (tsd_model_set_ff_fp8): e4m3 rows and per-channel scales of geglu1 / geglu2 of every attention block, behind
-  // everything else in the buffer
+  // everything else in the buffer.  Mode 2: their tile-major MXFP4 streams in the same place (the e4m3 rows are then not built).
   std::vector<AttnW*> ff8;
   size_t ff8_b = 0;
+  const bool mx = m->ff_fp8 == 2;
   if (m->ff_fp8)
     for (auto& a : m->unet.attn)
       if (a.C && a.geglu1.w && a.geglu2.w && a.geglu1.N % 16 == 0 && a.geglu2.N % 16 == 0 && a.geglu1.Kpad <= FP8_MAX_K && a.geglu2.Kpad <= FP8_MAX_K) {
         ff8.push_back(&a);
-        for (const LinW* l : {&a.geglu1, &a.geglu2}) ff8_b += ff8_bytes(*l) + ff8_scale_bytes(*l);
+        for (const LinW* l : {&a.geglu1, &a.geglu2}) ff8_b += mx ? ffmx_bytes(*l) : ff8_bytes(*l) + ff8_scale_bytes(*l);
       }
   if (el.empty() && !cin_ok && tm.empty() && tml.empty() && !kv && fold.empty() && !dup && uf.empty() && ff8.empty()) return TSD_OK;
   const size_t tail_b = (attn_tail_stream_bytes() + 255) & ~size_t(255), head_b = (attn_head_stream_bytes() + 255) & ~size_t(255);
@@ -737,7 +741,25 @@ static int model_build_derived(tsd_model* m) {
   }
   {
     size_t off = ff8_off;
-    for (size_t i = 0; i < ff8.size() && r == TSD_OK; i++) {
+    for (size_t i = 0; i < ff8.size() && r == TSD_OK && mx; i++) {
+      AttnW* a = ff8[i];
+      uint8_t* st[2];
+      int j = 0;
+      for (const LinW* l : {&a->geglu1, &a->geglu2}) {
+        st[j] = (uint8_t*)(m->derived + off);
+        off += ffmx_bytes(*l);
+        if (r == TSD_OK) r = launch_quant_weights_mxfp4(ctx, l->w, l->N, l->Kpad, l->Kpad, st[j], nullptr);
+        j++;
+      }
+      if (r == TSD_OK) { a->ffmx_w1 = st[0]; a->ffmx_w2 = st[1]; }
+    }
+    if (mx && r == TSD_OK && !ff8.empty()) {  // a non-finite weight has no MXFP4 form: reported here, once, never as finite garbage later
+      hipError_t e = hipStreamSynchronize(ctx->stream);
+      if (e != hipSuccess) { tsd_set_error("MXFP4 weight quantiser: %s", hipGetErrorString(e)); r = TSD_E_HIP; }
+      else r = ctx_check_status(ctx);
+      if (r != TSD_OK) for (AttnW* a : ff8) { a->ffmx_w1 = nullptr; a->ffmx_w2 = nullptr; }
+    }
+    for (size_t i = 0; i < ff8.size() && r == TSD_OK && !mx; i++) {
       AttnW* a = ff8[i];
       const uint8_t* wq[2]; const float* ws[2];
       int j = 0;
@@ -797,8 +819,8 @@ extern "C" int tsd_model_set_ff_fp8(tsd_model* m, int on) {
   if (!m) TSD_FAIL(TSD_E_ARG, "tsd_model_set_ff_fp8: NULL model");
   if (!is_diffusion_kind(m->kind) && !is_controlnet_kind(m->kind))
     TSD_FAIL(TSD_E_ARG, "tsd_model_set_ff_fp8: the FP8 feed-forward belongs to the UNets and ControlNets, this model is kind %d", m->kind);
-  if (on != 0 && on != 1) TSD_FAIL(TSD_E_ARG, "tsd_model_set_ff_fp8: on = %d (0 or 1)", on);
-  m->ff_fp8 = on != 0;
+  if (on < 0 || on > 2) TSD_FAIL(TSD_E_ARG, "tsd_model_set_ff_fp8: on = %d (0 off, 1 e4m3 weights, 2 MXFP4 weights)", on);
+  m->ff_fp8 = on;
   m->plans.clear();
   model_invalidate_derived(m);
   return TSD_OK;
@@ -807,7 +829,7 @@ extern "C" int tsd_model_ff_fp8(const tsd_model* m) {
   if (!m) TSD_FAIL(TSD_E_ARG, "tsd_model_ff_fp8: NULL model");
   if (!is_diffusion_kind(m->kind) && !is_controlnet_kind(m->kind))
     TSD_FAIL(TSD_E_ARG, "tsd_model_ff_fp8: the FP8 feed-forward belongs to the UNets and ControlNets, this model is kind %d", m->kind);
-  return m->ff_fp8 ? 1 : 0;
+  return m->ff_fp8;
 }
 
 extern "C" int tsd_model_prepare(tsd_model* m) {

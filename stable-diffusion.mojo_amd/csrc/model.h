@@ -117,6 +117,9 @@ struct AttnW {  // Unet_Attention_Block, diffusion.mojo:87-98
   // tail of the block runs its feed-forward on k_gemm_e4m3 (graph.cpp g_unet_attn) and does not take the fold_w shortcut.
   const uint8_t* ff8_w1 = nullptr; const float* ff8_s1 = nullptr;
   const uint8_t* ff8_w2 = nullptr; const float* ff8_s2 = nullptr;
+  // derived, under tsd_model_set_ff_fp8(m, 2) only: geglu1 / geglu2 as tile-major MXFP4 streams (k_quant_weights_mxfp4).  Present, the same
+  // branch of the op-by-op tail runs k_gemm_e4m3_mxfp4; the e4m3 rows above are then absent.
+  const uint8_t* ffmx_w1 = nullptr; const uint8_t* ffmx_w2 = nullptr;
 };
 // which fused kernel (C = 8 x 40 only) serves the block's tail / head: none (0, false), the reference's norms and tanh GELU, or the torch-norm extension
 enum { ATTN_FUSE_NONE = 0, ATTN_FUSE_PLAIN = 1, ATTN_FUSE_TORCH = 2 };
@@ -230,8 +233,9 @@ struct tsd_model {
   // unet_full_steps when the forward is enqueued; off (or all ones): the forward enqueues what it always did.
   bool freeu_on = false;
   int freeu_mode = 0;
-  // FP8 feed-forward (tsd_model_set_ff_fp8; Diffusion and ControlNet kinds): read by model_build_derived, which fills AttnW::ff8_*
-  bool ff_fp8 = false;
+  // FP8 feed-forward (tsd_model_set_ff_fp8; Diffusion and ControlNet kinds): 0 off, 1 e4m3 weights, 2 MXFP4 weights.  Read by
+  // model_build_derived, which fills AttnW::ff8_* (1) or AttnW::ffmx_* (2)
+  int ff_fp8 = 0;
   float freeu_b[TSD_FREEU_BLOCKS] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1}, freeu_s[TSD_FREEU_BLOCKS] = {1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
   // Windowed self attention (tsd_model_set_attn_window; UNets and ControlNets): window side per level l (token grid LH / 2^l x LW / 2^l),
   // 0 = off.  Read by g_unet_attn's callers at enqueue time through attn_window_for.

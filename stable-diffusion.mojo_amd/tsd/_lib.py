@@ -161,6 +161,8 @@ def _declare(l):
         "tsd_quant_rows_e4m3": ([vp, vp, i, i, i, vp, fp], i),
         "tsd_fp8_gemm_f16": ([vp, vp, fp, vp, fp, fp, vp, i, i, i, i, i, vp, i], i),
         "tsd_linear_fp8_f32": ([vp, fp, i, i, fp, fp, i, fp], i),
+        "tsd_quant_weights_mxfp4": ([vp, vp, i, i, i, vp, vp], i),
+        "tsd_mxfp4_gemm_f16": ([vp, vp, fp, vp, vp, fp, vp, i, i, i, i, i, vp, i], i),
         "tsd_clip_vision_forward": ([vp, fp, i, i, i, fp, fp], i),
         "tsd_debug_image_patches_run": ([vp, C.POINTER(i64), i, C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)], i),
         "tsd_tokenizer_create": ([C.c_char_p, i, C.POINTER(vp)], i),

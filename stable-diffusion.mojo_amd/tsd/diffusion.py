@@ -13,6 +13,7 @@ import numpy as np
 from . import _lib
 from ._lib import NULL_MATRIX, check, f32, fp, lib, ptr
 from .attention import Cross_Attention, Self_Attention
+from .fp8 import ff_fp8_mode
 from .model import Model
 from .utils import Conv2D, GroupNorm, LayerNorm, Linear, SiLU, Upsample, _ctx, concat
 
@@ -275,15 +276,16 @@ class Diffusion(_AttnWindow):
     def set_ff_fp8(self, on=True):
         """The opt-in FP8 feed-forward (`tsd_model_set_ff_fp8`): the GEGLU linears of the attention blocks that run op by op run on e4m3
         operands - per-row activation scales, per-channel weight scales, fp32 accumulation.  A parameter change: an open `Session`
-        picks it up at its next `upload()`.  Off gives the bits of a model that never had it on."""
-        check(lib().tsd_model_set_ff_fp8(self.model.h, 1 if on else 0))
+        picks it up at its next `upload()`.  Off gives the bits of a model that never had it on.  on="mxfp4": the same launches with the
+        weights in MXFP4 (e2m1 elements under e8m0 block-32 scales) instead of e4m3 rows."""
+        check(lib().tsd_model_set_ff_fp8(self.model.h, ff_fp8_mode(on)))
 
     @property
     def ff_fp8(self):
         on = lib().tsd_model_ff_fp8(self.model.h)
         if on < 0:
             check(on)
-        return bool(on)
+        return "mxfp4" if on == 2 else bool(on)
 
 
 def _ip_tokens_input(tokens, B):
@@ -413,15 +415,16 @@ class ControlNet(_AttnWindow):
     def set_ff_fp8(self, on=True):
         """The opt-in FP8 feed-forward (`tsd_model_set_ff_fp8`): the GEGLU linears of the attention blocks that run op by op run on e4m3
         operands - per-row activation scales, per-channel weight scales, fp32 accumulation.  A parameter change: an open `Session`
-        picks it up at its next `upload()`.  Off gives the bits of a model that never had it on."""
-        check(lib().tsd_model_set_ff_fp8(self.model.h, 1 if on else 0))
+        picks it up at its next `upload()`.  Off gives the bits of a model that never had it on.  on="mxfp4": the same launches with the
+        weights in MXFP4 (e2m1 elements under e8m0 block-32 scales) instead of e4m3 rows."""
+        check(lib().tsd_model_set_ff_fp8(self.model.h, ff_fp8_mode(on)))
 
     @property
     def ff_fp8(self):
         on = lib().tsd_model_ff_fp8(self.model.h)
         if on < 0:
             check(on)
-        return bool(on)
+        return "mxfp4" if on == 2 else bool(on)
 
     def hint(self, hint):
         """The hint encoder alone (`tsd_controlnet_hint_hw`): (3,8LH,8LW) or (B,3,8LH,8LW) -> features (320,LH,LW) / (B,320,LH,LW).

@@ -82,7 +82,7 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
     freeu, a dict of `Diffusion.set_freeu`'s keywords (dict(b1=1.5, b2=1.6, s1=0.9, s2=0.2) are the paper's SD-1.x values): the
     model runs FreeU for this call, and holds the table it held before - or none - on every way out.
 
-    ff_fp8=True: the model runs its GEGLU feed-forwards on e4m3 operands for this call (`Diffusion.set_ff_fp8`); None leaves the
+    ff_fp8=True: the model runs its GEGLU feed-forwards on e4m3 operands for this call (`Diffusion.set_ff_fp8`), ff_fp8="mxfp4" with MXFP4 weights; None leaves the
     model's setting alone, and the setting it had is back on every way out.
 
     attn_window, an int (the top level's window side in tokens) or 4 sides per level (`Diffusion.set_attn_window`): the UNet's self
