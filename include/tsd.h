@@ -1183,6 +1183,58 @@ int tsd_model_attn_window(tsd_model* unet, int out[4]);
  * dimension without a fused kernel, a window that does not divide the grid (both from the launcher). */
 int tsd_debug_attn_bench_win(tsd_ctx* ctx, int B, int H, int d, int grid_h, int grid_w, int win, int iters, float* ms);
 
+/* ---- Token merging (EXTENSION: ToMe for Stable Diffusion, Bolya & Hoffman 2023; tomesd's bipartite_soft_matching_random2d with
+ * sx = sy = 2, self attention only, training-free).  In front of a block's self attention the r most similar source tokens are merged
+ * into destination tokens, the q | k | V^T projection and the attention core run on the N - r merged rows, and the result is copied
+ * back to all N tokens in front of the output projection.  Cross attention and the feed-forward are untouched.
+ * Partition: the H x W token grid (N = H W, both sides even, 64 <= N <= 32768) is cut into 2 x 2 cells, numbered row-major (cell c = (y / 2)
+ * (W / 2) + x / 2).  One token of a cell is its DESTINATION: the top-left one when seed == 0, else the one at position
+ * (hash(seed, c) & 3) of the cell in raster order (0 top-left, 1 top-right, 2 bottom-left, 3 bottom-right), with, on uint32_t,
+ *     hash(seed, c):  x = seed ^ (c * 0x9E3779B9);  x ^= x >> 16;  x *= 0x85EBCA6B;  x ^= x >> 13;  x *= 0xC2B2AE35;  x ^= x >> 16;  return x
+ * Destination j is cell j's; the other three tokens of cell c are SOURCES 3 c + k, k in raster order.  Nd = N / 4, Ns = 3 N / 4.
+ * Match, on the metric rows (fp16, fp32 accumulation): score(i, j) = a_i . b_j / (|a_i| |b_j|), a zero row has inverse norm 0;
+ * node_idx[i] = argmax_j score(i, j), the smallest j on equal scores; node_max[i] that score.  r = 8 floor(ratio N / 8) (in double).  The r
+ * sources of largest node_max - the smaller source index first on equal values - merge into destination node_idx[i].
+ * Merged sequence, N - r rows: the Ns - r unmerged sources in ascending source index, then the Nd destinations in order.  row_of[t] is
+ * the row of TOKEN t (a merged source: its destination's).  members lists the tokens of every row, rows in order and a row's tokens
+ * ascending; row i owns members[start[i] .. start[i + 1]).  A merged row is rn16(sum x[t] / count): fp32, ascending token order, one
+ * division, one rounding; a row with one member is a copy.  Unmerge: out[t] = y[row_of[t]].
+ *
+ * tsd_model_set_token_merge: ratio[l] in [0, 0.75] is the share of tokens merged in the self-attention blocks whose token grid is
+ * LH / 2^l x LW / 2^l (levels as for tsd_model_set_attn_window); the metric is the block's hidden state behind conv_in.  NULL or all zeros
+ * turn it off: the model then enqueues exactly the launches it did before and gives the bits it gave, and so does a level whose r is 0.
+ * State of the MODEL: it acts from the next forward / step() / advance() on, an open session's included, with no upload(): a merged
+ * block lives in the plain block's buffers plus 4 B N bytes, inside the margin every workspace reservation carries.  A merged block runs its head op by op (never the fused head kernel) and keeps every launch behind the attention core.
+ * TSD_E_ARG: a kind that is neither a UNet nor a ControlNet, a ratio outside [0, 0.75] or not finite, a level that is windowed
+ * (tsd_model_set_attn_window refuses a level that merges likewise); the table stays as it was.  A forward whose grid at a merging level
+ * has an odd side, fewer than 64 or more than 32768 tokens is refused with TSD_E_SHAPE.
+ * tsd_model_token_merge: 1 when some level merges, 0 when off (negative: TSD_E_ARG); out[4] / seed, when not NULL, receive the table. */
+int tsd_model_set_token_merge(tsd_model* unet, const float ratio[4], uint32_t seed);
+int tsd_model_token_merge(tsd_model* unet, float out[4], uint32_t* seed);
+/* The launches alone on host tensors, synchronous.  x [B][H*W][C] fp16 (C a multiple of 64, B <= 64) -> node_max / node_idx [B][Ns],
+ * row_of [B][N], start [B][N - r + 1], members [B][N] (k_tome_match + k_tome_select).  TSD_E_ARG: ratio outside [0, 0.75]; TSD_E_SHAPE:
+ * the grid (above) or C. */
+int tsd_token_merge_plan_f16(tsd_ctx* ctx, const void* x, int B, int H, int W, int C, float ratio, uint32_t seed, float* node_max,
+                             int32_t* node_idx, int32_t* row_of, int32_t* start, int32_t* members);
+/* x [B][N][C] fp16 (C a multiple of 8) -> y [B][rows][C], the member means (k_tome_merge).  TSD_E_ARG: start is not an increasing
+ * list from 0 to N, a member outside [0, N). */
+int tsd_token_merge_rows_f16(tsd_ctx* ctx, const void* x, int B, int N, int C, int rows, const int32_t* start, const int32_t* members, void* y);
+/* y [B][rows][C] fp16 -> out [B][N][C], out[t] = y[row_of[t]] (k_tome_unmerge).  TSD_E_ARG: a row outside [0, rows). */
+int tsd_token_unmerge_rows_f16(tsd_ctx* ctx, const void* y, int B, int N, int C, int rows, const int32_t* row_of, void* out);
+/* Debug: while on, every merged attention block enqueued on the context keeps a copy of its row_of table [B][N] (device to device, on the
+ * stream; with recording off no launch and no copy is added).  Each table is a device allocation made while the block is enqueued:
+ * a tool for eager test forwards, not for a measured loop.  Turning it on drops what was recorded; returns the number of tables held.
+ * tsd_debug_token_merge_recorded: table i in execution order into row_of_out (cap ints; NULL: nothing is copied); returns its rows per
+ * sample N - r, or TSD_E_ARG (no such table, cap too small). */
+int tsd_debug_token_merge_record(tsd_ctx* ctx, int on);
+/* Debug / replay: the plan on x, the merge of v [B][H*W][C] through it and the unmerge of the merged rows, on caller buffers laid out
+ * [guard | tensor | guard] (guard elements of the tensor's type, a multiple of 8) that are uploaded, handed to the four kernels behind
+ * their front guard, and copied back whole - whatever a kernel wrote outside its tensor shows in the guards.  Tensors as in
+ * tsd_token_merge_plan_f16 / _rows_f16 / tsd_token_unmerge_rows_f16: y [B][N - r][C], out [B][N][C]. */
+int tsd_debug_token_merge_run(tsd_ctx* ctx, const void* x, const void* v, int B, int H, int W, int C, float ratio, uint32_t seed, int guard,
+                              float* node_max, int32_t* node_idx, int32_t* row_of, int32_t* start, int32_t* members, void* y, void* out);
+int tsd_debug_token_merge_recorded(tsd_ctx* ctx, int i, int32_t* row_of_out, int cap);
+
 /* ---- FP8 feed-forward (EXTENSION, opt-in): the two GEGLU linears of the attention blocks that run op by op on OCP e4m3 operands
  * (v_mfma_f32_16x16x128_f8f6f4), per-row dynamic activation scales, per-output-channel weight scales, fp32 accumulation.
  * Quantiser, per row of x [M][K] fp16 (pitch ld), all in fp32:

@@ -320,8 +320,38 @@ extern "C" int tsd_model_set_attn_window(tsd_model* unet, const int win[4]) {
   for (int l = 0; win && l < 4; l++)
     if (win[l] != 0 && !attn_window_side_ok(win[l]))
       TSD_FAIL(TSD_E_ARG, "tsd_model_set_attn_window: level %d: window side %d (0, 8, 16, 32, 64 or 128)", l, win[l]);
+  for (int l = 0; win && l < 4; l++)
+    if (win[l] != 0 && unet->tome_ratio[l] > 0.f)
+      TSD_FAIL(TSD_E_ARG, "tsd_model_set_attn_window: level %d merges tokens (tsd_model_set_token_merge): a level has a window or a merge ratio, not both", l);
   for (int l = 0; l < 4; l++) unet->attn_win[l] = win ? win[l] : 0;
   return TSD_OK;
+}
+
+// Token merging: the model's table, read like the window table when a forward is enqueued (token_merge_for, graph.cpp).
+extern "C" int tsd_model_set_token_merge(tsd_model* unet, const float ratio[4], uint32_t seed) {
+  NOTNULL(unet);
+  if (!is_diffusion_kind(unet->kind) && !is_controlnet_kind(unet->kind))
+    TSD_FAIL(TSD_E_ARG, "tsd_model_set_token_merge: token merging belongs to the UNets and ControlNets, this model is kind %d", unet->kind);
+  for (int l = 0; ratio && l < 4; l++) {
+    if (!(ratio[l] >= 0.f && ratio[l] <= 0.75f)) TSD_FAIL(TSD_E_ARG, "tsd_model_set_token_merge: level %d: ratio %g (0 .. 0.75)", l, (double)ratio[l]);
+    if (ratio[l] > 0.f && unet->attn_win[l])
+      TSD_FAIL(TSD_E_ARG, "tsd_model_set_token_merge: level %d is windowed (tsd_model_set_attn_window): a level has a window or a merge ratio, not both", l);
+  }
+  for (int l = 0; l < 4; l++) unet->tome_ratio[l] = ratio ? ratio[l] : 0.f;
+  unet->tome_seed = ratio ? seed : 0;
+  return TSD_OK;
+}
+extern "C" int tsd_model_token_merge(tsd_model* unet, float out[4], uint32_t* seed) {
+  NOTNULL(unet);
+  if (!is_diffusion_kind(unet->kind) && !is_controlnet_kind(unet->kind))
+    TSD_FAIL(TSD_E_ARG, "tsd_model_token_merge: token merging belongs to the UNets and ControlNets, this model is kind %d", unet->kind);
+  int on = 0;
+  for (int l = 0; l < 4; l++) {
+    if (out) out[l] = unet->tome_ratio[l];
+    on |= unet->tome_ratio[l] > 0.f;
+  }
+  if (seed) *seed = unet->tome_seed;
+  return on;
 }
 extern "C" int tsd_model_attn_window(tsd_model* unet, int out[4]) {
   NOTNULL(unet);

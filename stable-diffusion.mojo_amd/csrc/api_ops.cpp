@@ -454,6 +454,142 @@ extern "C" int tsd_debug_freeu_run(tsd_ctx* ctx, const void* h, const void* r, i
   });
 }
 
+// ---- Token merging (kernels_tome.hip) on host fp16 tensors in the device layout: the plan (match + select), the merge and the unmerge ----
+extern "C" int tsd_token_merge_plan_f16(tsd_ctx* ctx, const void* x, int B, int H, int W, int C, float ratio, uint32_t seed, float* node_max,
+                                        int32_t* node_idx, int32_t* row_of, int32_t* start, int32_t* members) {
+  NOTNULL(ctx); NOTNULL(x); NOTNULL(node_max); NOTNULL(node_idx); NOTNULL(row_of); NOTNULL(start); NOTNULL(members);
+  if (!(ratio >= 0.f && ratio <= 0.75f)) TSD_FAIL(TSD_E_ARG, "token merge plan: ratio %g (0 .. 0.75)", (double)ratio);
+  if (B <= 0 || B > 64 || H < 2 || W < 2 || H > TOME_MAX_TOKENS || W > TOME_MAX_TOKENS) TSD_FAIL(TSD_E_SHAPE, "token merge plan: B=%d (1..64) grid %d x %d", B, H, W);
+  if (C <= 0 || C % 64 || C > 8192) TSD_FAIL(TSD_E_SHAPE, "token merge plan: C=%d (a multiple of 64 up to 8192)", C);
+  return run_op(ctx, [&]() -> int {
+    Dev dv{ctx};
+    TomeOp op;
+    op.B = B; op.H = H; op.W = W; op.C = C; op.ldx = C; op.seed = seed;
+    if ((int64_t)H * W > TOME_MAX_TOKENS) return launch_tome_plan(ctx, op);  // (the launcher's refusal)
+    const int N = H * W, Ns = N - N / 4;
+    op.r = tome_r(ratio, N);
+    op.x = (const half_t*)dv.in((const uint16_t*)x, (int64_t)B * N * C);
+    op.node_max = dv.buf<float>((int64_t)B * Ns); op.node_idx = dv.buf<int>((int64_t)B * Ns);
+    op.row_of = dv.buf<int>((int64_t)B * N); op.start = dv.buf<int>((int64_t)B * (N - op.r + 1)); op.members = dv.buf<int>((int64_t)B * N);
+    if (dv.err) return dv.err;
+    TSD_TRY(launch_tome_plan(ctx, op));
+    TSD_TRY(dv.out(node_max, (const float*)op.node_max, (int64_t)B * Ns));
+    TSD_TRY(dv.out((int*)node_idx, (const int*)op.node_idx, (int64_t)B * Ns));
+    TSD_TRY(dv.out((int*)row_of, (const int*)op.row_of, (int64_t)B * N));
+    TSD_TRY(dv.out((int*)start, (const int*)op.start, (int64_t)B * (N - op.r + 1)));
+    return dv.out((int*)members, (const int*)op.members, (int64_t)B * N);
+  });
+}
+
+// The tables come from the caller here: they are checked on the host before a kernel indexes with them.
+extern "C" int tsd_token_merge_rows_f16(tsd_ctx* ctx, const void* x, int B, int N, int C, int Sm, const int32_t* start, const int32_t* members,
+                                        void* y) {
+  NOTNULL(ctx); NOTNULL(x); NOTNULL(start); NOTNULL(members); NOTNULL(y);
+  if (B <= 0 || B > 64 || N < 1 || N > TOME_MAX_TOKENS || Sm < 1 || Sm > N) TSD_FAIL(TSD_E_SHAPE, "token merge rows: B=%d (1..64) N=%d rows %d", B, N, Sm);
+  if (C <= 0 || C % 8 || C > 8192) TSD_FAIL(TSD_E_SHAPE, "token merge rows: C=%d (a multiple of 8 up to 8192)", C);
+  for (int b = 0; b < B; b++) {
+    const int32_t* st = start + (int64_t)b * (Sm + 1);
+    bool ok = st[0] == 0 && st[Sm] == N;
+    for (int i = 0; ok && i < Sm; i++) ok = st[i + 1] > st[i];
+    for (int i = 0; ok && i < N; i++) ok = members[(int64_t)b * N + i] >= 0 && members[(int64_t)b * N + i] < N;
+    if (!ok) TSD_FAIL(TSD_E_ARG, "token merge rows: sample %d: start is not an increasing 0 .. N list or a member is outside [0, N)", b);
+  }
+  return run_op(ctx, [&]() -> int {
+    Dev dv{ctx};
+    const half_t* dx = (const half_t*)dv.in((const uint16_t*)x, (int64_t)B * N * C);
+    const int* ds = dv.in((const int*)start, (int64_t)B * (Sm + 1));
+    const int* dm = dv.in((const int*)members, (int64_t)B * N);
+    uint16_t* dy = dv.buf<uint16_t>((int64_t)B * Sm * C);
+    if (dv.err) return dv.err;
+    TSD_TRY(launch_tome_merge(ctx, dx, C, B, N, C, Sm, ds, dm, (half_t*)dy, C));
+    return dv.out((uint16_t*)y, (const uint16_t*)dy, (int64_t)B * Sm * C);
+  });
+}
+
+extern "C" int tsd_token_unmerge_rows_f16(tsd_ctx* ctx, const void* y, int B, int N, int C, int Sm, const int32_t* row_of, void* out) {
+  NOTNULL(ctx); NOTNULL(y); NOTNULL(row_of); NOTNULL(out);
+  if (B <= 0 || B > 64 || N < 1 || N > TOME_MAX_TOKENS || Sm < 1 || Sm > N) TSD_FAIL(TSD_E_SHAPE, "token unmerge rows: B=%d (1..64) N=%d rows %d", B, N, Sm);
+  if (C <= 0 || C % 8 || C > 8192) TSD_FAIL(TSD_E_SHAPE, "token unmerge rows: C=%d (a multiple of 8 up to 8192)", C);
+  for (int64_t i = 0; i < (int64_t)B * N; i++)
+    if (row_of[i] < 0 || row_of[i] >= Sm) TSD_FAIL(TSD_E_ARG, "token unmerge rows: row_of[%lld] = %d is outside [0, %d)", (long long)i, row_of[i], Sm);
+  return run_op(ctx, [&]() -> int {
+    Dev dv{ctx};
+    const half_t* dy = (const half_t*)dv.in((const uint16_t*)y, (int64_t)B * Sm * C);
+    const int* dr = dv.in((const int*)row_of, (int64_t)B * N);
+    uint16_t* dout = dv.buf<uint16_t>((int64_t)B * N * C);
+    if (dv.err) return dv.err;
+    TSD_TRY(launch_tome_unmerge(ctx, dy, C, B, N, C, Sm, dr, (half_t*)dout, C));
+    return dv.out((uint16_t*)out, (const uint16_t*)dout, (int64_t)B * N * C);
+  });
+}
+
+// Plan on x, merge of v through the plan, unmerge of the merged rows - on buffers [guard | tensor | guard] that go to the device and
+// come back whole, so that a test sees every element beside what the four kernels may write (tsd_debug_freeu_run's pattern).
+extern "C" int tsd_debug_token_merge_run(tsd_ctx* ctx, const void* x, const void* v, int B, int H, int W, int C, float ratio, uint32_t seed,
+                                         int guard, float* node_max, int32_t* node_idx, int32_t* row_of, int32_t* start, int32_t* members,
+                                         void* y, void* out) {
+  NOTNULL(ctx); NOTNULL(x); NOTNULL(v); NOTNULL(node_max); NOTNULL(node_idx); NOTNULL(row_of); NOTNULL(start); NOTNULL(members); NOTNULL(y); NOTNULL(out);
+  if (!(ratio >= 0.f && ratio <= 0.75f)) TSD_FAIL(TSD_E_ARG, "token merge run: ratio %g (0 .. 0.75)", (double)ratio);
+  if (B <= 0 || B > 64 || H < 2 || W < 2 || (H | W) & 1 || (int64_t)H * W < 64 || (int64_t)H * W > TOME_MAX_TOKENS || C <= 0 || C % 64 || C > 8192 ||
+      guard < 0 || guard % 8 || guard > (1 << 20))
+    TSD_FAIL(TSD_E_SHAPE, "token merge run: B=%d (1..64) grid %d x %d C=%d guard %d (a multiple of 8)", B, H, W, C, guard);
+  return run_op(ctx, [&]() -> int {
+    Dev dv{ctx};
+    const int N = H * W, Ns = N - N / 4, r = tome_r(ratio, N), Sm = N - r;
+    const int64_t g2 = 2 * guard, n_ns = (int64_t)B * Ns + g2, n_n = (int64_t)B * N + g2, n_st = (int64_t)B * (Sm + 1) + g2;
+    const int64_t n_y = (int64_t)B * Sm * C + g2, n_o = (int64_t)B * N * C + g2;
+    const half_t* dx = (const half_t*)dv.in((const uint16_t*)x, (int64_t)B * N * C);
+    const half_t* dvv = (const half_t*)dv.in((const uint16_t*)v, (int64_t)B * N * C);
+    float* d_max = dv.in((const float*)node_max, n_ns);
+    int* d_idx = dv.in((const int*)node_idx, n_ns);
+    int* d_row = dv.in((const int*)row_of, n_n);
+    int* d_st = dv.in((const int*)start, n_st);
+    int* d_mem = dv.in((const int*)members, n_n);
+    uint16_t* d_y = dv.in((const uint16_t*)y, n_y);
+    uint16_t* d_out = dv.in((const uint16_t*)out, n_o);
+    if (dv.err) return dv.err;
+    TomeOp op;
+    op.x = dx; op.ldx = C; op.B = B; op.H = H; op.W = W; op.C = C; op.r = r; op.seed = seed;
+    op.node_max = d_max + guard; op.node_idx = d_idx + guard; op.row_of = d_row + guard; op.start = d_st + guard; op.members = d_mem + guard;
+    TSD_TRY(launch_tome_plan(ctx, op));
+    TSD_TRY(launch_tome_merge(ctx, dvv, C, B, N, C, Sm, op.start, op.members, (half_t*)d_y + guard, C));
+    TSD_TRY(launch_tome_unmerge(ctx, (const half_t*)d_y + guard, C, B, N, C, Sm, op.row_of, (half_t*)d_out + guard, C));
+    TSD_TRY(dv.out(node_max, (const float*)d_max, n_ns));
+    TSD_TRY(dv.out((int*)node_idx, (const int*)d_idx, n_ns));
+    TSD_TRY(dv.out((int*)row_of, (const int*)d_row, n_n));
+    TSD_TRY(dv.out((int*)start, (const int*)d_st, n_st));
+    TSD_TRY(dv.out((int*)members, (const int*)d_mem, n_n));
+    TSD_TRY(dv.out((uint16_t*)y, (const uint16_t*)d_y, n_y));
+    return dv.out((uint16_t*)out, (const uint16_t*)d_out, n_o);
+  });
+}
+
+// Recording of the row_of tables of a forward's merged blocks (tsd_debug_gemm_record's pattern); g_unet_attn copies them on the stream.
+extern "C" int tsd_debug_token_merge_record(tsd_ctx* ctx, int on) {
+  NOTNULL(ctx);
+  if (on) {
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (TomeRec& t : ctx->tome_rec) if (t.dev) (void)dev_free(t.dev);
+    ctx->tome_rec.clear();
+  }
+  ctx->tome_rec_on = on != 0;
+  return (int)ctx->tome_rec.size();
+}
+
+extern "C" int tsd_debug_token_merge_recorded(tsd_ctx* ctx, int i, int32_t* row_of_out, int cap) {
+  NOTNULL(ctx);
+  if (i < 0 || (size_t)i >= ctx->tome_rec.size()) TSD_FAIL(TSD_E_ARG, "token_merge_recorded: no table %d (%d recorded)", i, (int)ctx->tome_rec.size());
+  const TomeRec& t = ctx->tome_rec[i];
+  const int n = t.B * t.N;
+  if (row_of_out) {
+    if (cap < n) TSD_FAIL(TSD_E_ARG, "token_merge_recorded: table %d has %d entries, capacity %d", i, n, cap);
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(row_of_out, t.dev, (size_t)n * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+  }
+  return t.Sm;
+}
+
 // ---- FP8 feed-forward (kernels_fp8.hip) on host arrays: the two launches alone, and a linear layer through both ----
 extern "C" int tsd_quant_rows_e4m3(tsd_ctx* ctx, const void* x_f16, int M, int K, int ld, void* q_out, float* scale_out) {
   NOTNULL(ctx); NOTNULL(x_f16); NOTNULL(q_out); NOTNULL(scale_out);

@@ -174,6 +174,13 @@ struct FreeuTab {
   float* dev = nullptr;
 };
 
+// tsd_debug_token_merge_record: the row_of table [B][N] of a merged attention block (Sm rows per sample), copied on the stream while
+// recording is on; one device allocation each, freed when recording restarts or with the context
+struct TomeRec {
+  int* dev = nullptr;
+  int B = 0, N = 0, Sm = 0;
+};
+
 struct tsd_ctx {
   int device = 0;
   TsdOptions opt;
@@ -208,6 +215,9 @@ struct tsd_ctx {
   SmallLinearPlan sl_last;    // the last tiny-M linear launch enqueued (tsd_debug_elem_run)
   std::vector<VisionTab> vision_tabs;  // resize coefficient tables of the CLIP image front end, one per input size (kernels_vision.hip)
   std::vector<FreeuTab> freeu_tabs;    // cos / sin tables of FreeU's skip filter, one per plane size (kernels_freeu.hip)
+  // tsd_debug_token_merge_record: the row_of tables of the merged attention blocks enqueued while on, in execution order
+  bool tome_rec_on = false;
+  std::vector<TomeRec> tome_rec;
 };
 
 enum KernelClass : int {
@@ -563,6 +573,24 @@ struct FreeuOp {
 };
 int launch_freeu(tsd_ctx* ctx, const FreeuOp& op);
 int freeu_tab(tsd_ctx* ctx, int H, int W, const float** dev_out);
+
+// ---- Token merging (kernels_tome.hip; include/tsd.h "Token merging" states the semantics).  launch_tome_plan: match + select on the
+// metric x [B][H*W][ldx] (C a multiple of 64, 16-byte aligned) -> node_max / node_idx [B][Ns], row_of [B][N], start [B][N - r + 1],
+// members [B][N]; two launches.  launch_tome_merge: y [B][Sm][ldy] = member means of x [B][N][ldx]; launch_tome_unmerge: out [B][N][ldo] =
+// y [B][Sm][ldy] gathered through row_of.  One launch each; C a multiple of 8.
+constexpr int TOME_MAX_TOKENS = 32768;
+struct TomeOp {
+  const half_t* x = nullptr; int ldx = 0;
+  int B = 0, H = 0, W = 0, C = 0;
+  int r = 0;             // sources merged per sample: tome_r(ratio, H * W)
+  uint32_t seed = 0;
+  float* node_max = nullptr; int* node_idx = nullptr;
+  int* row_of = nullptr; int* start = nullptr; int* members = nullptr;
+};
+int tome_r(float ratio, int N);  // 8 * floor(ratio * N / 8), in double
+int launch_tome_plan(tsd_ctx* ctx, const TomeOp& op);
+int launch_tome_merge(tsd_ctx* ctx, const half_t* x, int ldx, int B, int N, int C, int Sm, const int* start, const int* members, half_t* y, int ldy);
+int launch_tome_unmerge(tsd_ctx* ctx, const half_t* y, int ldy, int B, int N, int C, int Sm, const int* row_of, half_t* out, int ldo);
 
 // ---- FP8 feed-forward (kernels_fp8.hip states the arithmetic): OCP e4m3 rows with one fp32 scale each, and the GEMM over them ----
 // x [M][K] fp16 (pitch ld >= K) -> q [M][round_up(K, 128)] bytes (16-byte aligned; the pad bytes are +0), scale [M].  K <= FP8_MAX_K.

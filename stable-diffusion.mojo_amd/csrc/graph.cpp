@@ -208,11 +208,31 @@ int attn_window_for(const tsd_model* m, int LH, int H, int W, int* win) {
   return TSD_OK;
 }
 
+// Token merging of a self-attention block whose token grid is H x W in a forward at LH latent rows: the level is found as
+// attn_window_for finds it; r = 8 floor(ratio N / 8) sources merge.  A level with a ratio needs an even-sided grid of 64 .. 32768 tokens.
+int token_merge_for(const tsd_model* m, int LH, int H, int W, TomeSel* tm) {
+  *tm = TomeSel();
+  const float* ratio = m->tome_ratio;
+  if (!(ratio[0] > 0.f || ratio[1] > 0.f || ratio[2] > 0.f || ratio[3] > 0.f)) return TSD_OK;
+  int l = 0, h = LH;
+  while (l < 3 && h > H) { h = (h + 1) / 2; l++; }
+  if (h != H) TSD_FAIL(TSD_E_SHAPE, "token merging: a %d x %d token grid is no level of a forward at %d latent rows", H, W, LH);
+  if (!(ratio[l] > 0.f)) return TSD_OK;
+  if ((H | W) & 1 || (int64_t)H * W < 64 || (int64_t)H * W > TOME_MAX_TOKENS)
+    TSD_FAIL(TSD_E_SHAPE, "token merging: level %d has a %d x %d token grid (even sides, 64 .. %d tokens)", l, H, W, TOME_MAX_TOKENS);
+  tm->r = tome_r(ratio[l], H * W);
+  tm->seed = m->tome_seed;
+  return TSD_OK;
+}
+
 // `Unet_Attention_Block.forward` diffusion.mojo:112-147 on NHWC tokens
 int g_unet_attn(tsd_ctx* ctx, const Act& x, const AttnW& w, const half_t* ctx16, int T, int Tp, Act& out,
-                const CtxKV* pre, const IpKV* ipkv, int win) {
+                const CtxKV* pre, const IpKV* ipkv, int win, TomeSel tm) {
   const int C = w.C, B = x.B, S = x.H * x.W, d = w.n_embed, Hh = w.n_head;
   const int64_t M = (int64_t)B * S;
+  const int Sa = S - tm.r;  // rows per sample of the self-attention projections and core: the merged sequence when tokens merge (tm.r > 0)
+  const int64_t Ma = (int64_t)B * Sa;
+  if (tm.r && win) TSD_FAIL(TSD_E_ARG, "attention block: a window and token merging on the same block");
   if (C % 64 || x.C != C) TSD_FAIL(TSD_E_SHAPE, "attention block: C=%d (input %d) unsupported", C, x.C);
   if (!attn_fused_supported(d)) TSD_FAIL(TSD_E_SHAPE, "attention block: head dim %d unsupported (40/64/80/160)", d);
   if (S % 4) TSD_FAIL(TSD_E_SHAPE, "attention block: H*W=%d must be a multiple of 4", S);
@@ -231,7 +251,29 @@ int g_unet_attn(tsd_ctx* ctx, const Act& x, const AttnW& w, const half_t* ctx16,
   const half_t* head_stream = w.head_stream;
   // an IP-Adapter block runs op by op: its launch sits between the cross-attention core and out_proj, inside what the tail kernel fuses
   const int head_kind = attn_head_weights_ok(w), tail_kind = attn_tail_weights_ok(w);  // torch-norm blocks: under TSD_CHAIN=2 only
-  const bool head_ok = !ipkv && Sp == S && x.ld % 8 == 0 && attn_tail_supported(ctx, C, d, Hh, 1, M, S) &&
+  // Token merging: the plan is taken on tok and the merge reads ln, so a merged block's head runs op by op; its self-attention
+  // projections and core then see Sa = S - r rows per sample (pitch Spa of V^T), and ao is gathered back in front of sa_out.
+  // A merged block lives in the plain block's buffers, so that a table set on an open session needs no larger workspace than the one
+  // sized without it: GroupNorm writes into ao (dead until the unmerge), the merged rows of ln go there too once conv_in has read it,
+  // the merged attention output goes into ln (dead behind the merge), and every table but row_of sits in qk, which nothing reads before
+  // the projection overwrites it.  Only row_of [B][S] ints is new - 4 B S bytes against the 12 B S C of the five buffers above, well
+  // inside the sixteenth that ctx_reserve_arena adds to every plan.  The stream orders each reuse behind the last reader.
+  const int Spa = round_up(Sa, 8);
+  half_t* const lnm = ao; half_t* const aom = ln;
+  int* tm_row_of = nullptr; int* tm_start = nullptr; int* tm_members = nullptr;
+  float* tm_nmax = nullptr; int* tm_nidx = nullptr;
+  const size_t tm_mark = ctx->arena.mark();  // row_of is released behind the unmerge, before the tail allocates
+  if (tm.r) {
+    tm_row_of = arena_alloc<int>(ctx, M); CHECK_ALLOC(tm_row_of);
+    const int64_t Ns = (int64_t)B * (S - S / 4), step = 64;  // table offsets in qk, in ints, each rounded up to 256 bytes
+    auto up = [&](int64_t n) { return (n + step - 1) / step * step; };
+    int* t = (int*)qk;   // 3 Ns / 2 + 2 M + B ints <= 4 B S ints < the 4 B S C bytes of qk (C >= 64)
+    tm_nmax = (float*)t; t += up(Ns);
+    tm_nidx = t; t += up(Ns);
+    tm_start = t; t += up((int64_t)B * (Sa + 1));
+    tm_members = t;
+  }
+  const bool head_ok = !tm.r && !ipkv && Sp == S && x.ld % 8 == 0 && attn_tail_supported(ctx, C, d, Hh, 1, M, S) &&
                        (head_kind == ATTN_FUSE_PLAIN || (head_kind == ATTN_FUSE_TORCH && ctx->opt.chain >= 2));
   if (head_ok && !head_stream && !pre) {  // block-level entry: no model, pack on the fly
     half_t* hs = arena_alloc<half_t>(ctx, (int64_t)attn_head_stream_bytes() / 2); CHECK_ALLOC(hs);
@@ -250,7 +292,8 @@ int g_unet_attn(tsd_ctx* ctx, const Act& x, const AttnW& w, const half_t* ctx16,
     ha.M = M; ha.S = S; ha.eps = 1e-5f;
     TSD_TRY(launch_attn_head(ctx, ha));
   } else {
-    half_t* h0 = arena_alloc<half_t>(ctx, M * C); CHECK_ALLOC(h0);
+    half_t* h0 = ao;  // a merged block: see above
+    if (!tm.r) { h0 = arena_alloc<half_t>(ctx, M * C); CHECK_ALLOC(h0); }
     TSD_TRY(launch_groupnorm(ctx, norm_src(cat1(x), C), B, S, C, 32, 1e-6f, 1.f, 0, h0, C, x_stats ? x.gn_part : nullptr,
                              x.gn_nslab, w.gn.w ? &w.gn : nullptr));  // :89,:116
     a.p0 = h0; a.ld0 = C; a.C0 = C;
@@ -258,36 +301,57 @@ int g_unet_attn(tsd_ctx* ctx, const Act& x, const AttnW& w, const half_t* ctx16,
     if (Sp != S) TSD_TRY(zero_async(ctx, vt, (size_t)B * C * Sp * sizeof(half_t)));  // pad keys must be finite (P = 0 there)
     // ---- self attention (:122-126) ----
     TSD_TRY(launch_layernorm(ctx, tok, M, C, C, 1e-5f, ln, C, w.ln[0].w ? &w.ln[0] : nullptr));
-    a.p0 = ln; a.ld0 = C; a.C0 = C;
-    if (qkv_fused_ok(ctx, S, Sp, C)) {  // q | k token-major and V^T channel-major from ONE GEMM over in_proj's 3C rows (transposed tail)
+    const half_t* sx = ln;  // what the self-attention projections read: ln, or its merged rows
+    if (tm.r) {
+      TomeOp op;
+      op.x = tok; op.ldx = C; op.B = B; op.H = x.H; op.W = x.W; op.C = C; op.r = tm.r; op.seed = tm.seed;
+      op.node_max = tm_nmax; op.node_idx = tm_nidx; op.row_of = tm_row_of; op.start = tm_start; op.members = tm_members;
+      TSD_TRY(launch_tome_plan(ctx, op));
+      TSD_TRY(launch_tome_merge(ctx, ln, C, B, S, C, Sa, tm_start, tm_members, lnm, C));
+      sx = lnm;
+    }
+    a.p0 = sx; a.ld0 = C; a.C0 = C;
+    if (qkv_fused_ok(ctx, Sa, Spa, C)) {  // q | k token-major and V^T channel-major from ONE GEMM over in_proj's 3C rows (transposed tail)
       GemmArgs g;
-      g.A0 = ln; g.lda0 = C; g.Wt = w.sa_in.w; g.ldw = w.sa_in.Kpad; g.M = (int)M; g.N = 3 * C; g.K = C;
+      g.A0 = sx; g.lda0 = C; g.Wt = w.sa_in.w; g.ldw = w.sa_in.Kpad; g.M = (int)Ma; g.N = 3 * C; g.K = C;
       if (w.sa_in.w_tm) { g.Wt = w.sa_in.w_tm; g.ldw = 64; g.w_kts = 3 * C * 128; }
-      g.C = qk; g.ldc = 2 * C; g.rows_per_sample_hint = S;
-      g.Vt = vt; g.vt_n0 = 2 * C; g.vt_ld = Sp; g.vt_S = S; g.vt_sB = (int64_t)C * Sp;
+      g.C = qk; g.ldc = 2 * C; g.rows_per_sample_hint = Sa;
+      g.Vt = vt; g.vt_n0 = 2 * C; g.vt_ld = Spa; g.vt_S = Sa; g.vt_sB = (int64_t)C * Spa;
       TSD_TRY(launch_gemm(ctx, g));
     } else {
-    TSD_TRY(g_linear(ctx, a, M, w.sa_in.w, w.sa_in.Kpad, 2 * C, C, nullptr, nullptr, 0, 0, qk, 2 * C, nullptr, S));  // q,k
+    TSD_TRY(g_linear(ctx, a, Ma, w.sa_in.w, w.sa_in.Kpad, 2 * C, C, nullptr, nullptr, 0, 0, qk, 2 * C, nullptr, Sa));  // q,k
     {  // V^T[b] = W_v . ln_b^T  -> [B][C][S]
       GemmArgs g;
       g.A0 = w.sa_in.w + (int64_t)2 * C * w.sa_in.Kpad; g.lda0 = w.sa_in.Kpad; g.sA = 0;
-      g.Wt = ln; g.ldw = C; g.sW = (int64_t)S * C;
-      g.M = C; g.N = S; g.K = C; g.batch = B;
-      g.C = vt; g.ldc = Sp; g.sC = (int64_t)C * Sp;
+      g.Wt = sx; g.ldw = C; g.sW = (int64_t)Sa * C;
+      g.M = C; g.N = Sa; g.K = C; g.batch = B;
+      g.C = vt; g.ldc = Spa; g.sC = (int64_t)C * Spa;
       TSD_TRY(launch_gemm(ctx, g));
     }
     }
   }
   a.ld0 = C; a.C0 = C;
   AttnArgs fa;
-  fa.Q = qk; fa.ldq = 2 * C; fa.sQ = (int64_t)S * 2 * C;
-  fa.K = qk + C; fa.ldk = 2 * C; fa.sK = (int64_t)S * 2 * C;
-  fa.Vt = vt; fa.ldvt = Sp; fa.sVt = (int64_t)C * Sp;
-  fa.O = ao; fa.ldo = C; fa.sO = (int64_t)S * C;
-  fa.B = B; fa.H = Hh; fa.d = d; fa.Sq = S; fa.Sk = S; fa.scale = scale;
+  fa.Q = qk; fa.ldq = 2 * C; fa.sQ = (int64_t)Sa * 2 * C;
+  fa.K = qk + C; fa.ldk = 2 * C; fa.sK = (int64_t)Sa * 2 * C;
+  fa.Vt = vt; fa.ldvt = Spa; fa.sVt = (int64_t)C * Spa;
+  fa.O = tm.r ? aom : ao; fa.ldo = C; fa.sO = (int64_t)Sa * C;
+  fa.B = B; fa.H = Hh; fa.d = d; fa.Sq = Sa; fa.Sk = Sa; fa.scale = scale;
   if (win) { fa.win = win; fa.grid_h = x.H; fa.grid_w = x.W; }  // self attention only: the cross-attention launch below clears it
   TSD_TRY(launch_flash_attention(ctx, fa));
   fa.win = 0; fa.grid_h = 0; fa.grid_w = 0;
+  if (tm.r) {  // out[t] = y[row_of[t]] in front of sa_out (linear per row): everything behind the core keeps its launches
+    TSD_TRY(launch_tome_unmerge(ctx, aom, C, B, S, C, Sa, tm_row_of, ao, C));
+    fa.O = ao; fa.sO = (int64_t)S * C; fa.Sq = S;
+    if (ctx->tome_rec_on && ctx->launch()) {  // (an eager enqueue: the library captures no graphs, and tsd.h says so of the recorder)
+      TomeRec rec;
+      rec.B = B; rec.N = S; rec.Sm = Sa;
+      HIP_TRY(dev_malloc((void**)&rec.dev, (size_t)M * sizeof(int)));
+      ctx->tome_rec.push_back(rec);
+      HIP_TRY(hipMemcpyAsync(rec.dev, tm_row_of, (size_t)M * sizeof(int), hipMemcpyDeviceToDevice, ctx->stream));
+    }
+    ctx->arena.release(tm_mark);  // (the stream orders the launches above in front of whatever writes this memory next)
+  }
   // context keys / values of this block: projected once for all blocks by g_unet_forward, or here (block-level entry)
   CtxKV kv;
   if (pre) kv = *pre;  // context K / V^T of all nine blocks were projected in two batched GEMMs (g_unet_forward)
@@ -629,7 +693,9 @@ int g_unet_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, 
     kv.Vt = vtc_all + (int64_t)w.kv_off * Tp; kv.ldvt = Tp; kv.sVt = (int64_t)CK * Tp;
     int win = 0;
     TSD_TRY(attn_window_for(m, LH, a[i - 1].H, a[i - 1].W, &win));
-    return g_unet_attn(ctx, a[i - 1], w, ctx16, T, Tp, a[i], &kv, nullptr, win);
+    TomeSel tm;
+    TSD_TRY(token_merge_for(m, LH, a[i - 1].H, a[i - 1].W, &tm));
+    return g_unet_attn(ctx, a[i - 1], w, ctx16, T, Tp, a[i], &kv, nullptr, win, tm);
   };
   // encoders (diffusion.mojo:236-250)
   TSD_TRY(alloc_out(1, LH, LW, 320));
@@ -785,7 +851,9 @@ static int unet_full_steps(const FullRun& f, int i0, int i1, Act& cur, std::vect
       }
       int win = 0;
       TSD_TRY(attn_window_for(m, f.LH, cur.H, cur.W, &win));
-      TSD_TRY(g_unet_attn(ctx, cur, w, f.ctx16, f.T, f.Tp, y, &kv, f.ip ? &ik : nullptr, win));
+      TomeSel tm;
+      TSD_TRY(token_merge_for(m, f.LH, cur.H, cur.W, &tm));
+      TSD_TRY(g_unet_attn(ctx, cur, w, f.ctx16, f.T, f.Tp, y, &kv, f.ip ? &ik : nullptr, win, tm));
     }
     cur = y;
     if (st.flags & U_PUSH) {

@@ -71,8 +71,15 @@ struct IpKV {
 };
 // win: the window side of the block's self attention (0 = whole grid), as attn_window_for gives it
 int attn_window_for(const tsd_model* m, int LH, int H, int W, int* win);
+// Token merging of the block's self attention, as token_merge_for gives it: r sources of every sample join their destinations (0 = off,
+// the plain path launch for launch); seed picks the destination of each 2 x 2 cell.
+struct TomeSel {
+  int r = 0;
+  uint32_t seed = 0;
+};
+int token_merge_for(const tsd_model* m, int LH, int H, int W, TomeSel* tm);
 int g_unet_attn(tsd_ctx* ctx, const Act& x, const AttnW& w, const half_t* ctx16, int T, int Tp, Act& out,
-                const CtxKV* pre = nullptr, const IpKV* ipkv = nullptr, int win = 0);
+                const CtxKV* pre = nullptr, const IpKV* ipkv = nullptr, int win = 0, TomeSel tm = TomeSel());
 int g_vae_attn(tsd_ctx* ctx, const Act& x, const VaeAttnW& w, Act& out);
 int g_attn_core(tsd_ctx* ctx, const AttnArgs& fa);
 int g_qkv_proj(tsd_ctx* ctx, const half_t* x, int B, int S, int C, const LinW& in_proj, half_t* qk, half_t* vt, int Sp);

@@ -13,6 +13,8 @@
   tsd.pipeline   <-> pipeline.mojo          generate (hot loop; the context embedding is an input)
   tsd.serve      (no reference counterpart) continuous batching over a slot session: SlotScheduler, generate_stream
   tsd.free_u     (no reference counterpart) FreeU on the full-size UNets: freeu_table, Diffusion.set_freeu, generate(freeu=...)
+  tsd.token_merge (no reference counterpart) token merging in front of self attention: Diffusion.set_token_merge, token_merge_plan,
+                 token_merge_rows, token_unmerge_rows, generate(token_merge=...)
   tsd.fp8        (no reference counterpart) the opt-in FP8 feed-forward: quant_rows_e4m3, fp8_gemm, linear_fp8, Diffusion.set_ff_fp8;
                  MXFP4 weights for it: quant_weights_mxfp4, mxfp4_gemm, set_ff_fp8("mxfp4")
   tsd.lora       (no reference counterpart) LoRA adapters merged into the packed weights on the device, removable exactly
@@ -37,5 +39,6 @@ from .sampler import DDIMSampler, DDPMSampler, DPMSolverMultistepSampler  # noqa
 from .pipeline import encode_prompts, generate  # noqa: F401
 from .serve import Request, SlotScheduler, generate_stream  # noqa: F401
 from .free_u import freeu, freeu_table  # noqa: F401
+from .token_merge import token_merge_plan, token_merge_rows, token_unmerge_rows  # noqa: F401
 from .fp8 import fp8_gemm, linear_fp8, mxfp4_gemm, quant_rows_e4m3, quant_weights_mxfp4  # noqa: F401
 from .lora import load_lora, lora_targets, merge_reference, read_lora  # noqa: F401

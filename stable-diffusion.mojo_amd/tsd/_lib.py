@@ -154,6 +154,12 @@ def _declare(l):
         "tsd_debug_ip_attn_bench": ([vp, i, i, i, i, i, i, fp], i),
         "tsd_clip_image_patches_f16": ([vp, fp, i, i, i, vp], i),
         "tsd_model_set_attn_window": ([vp, C.POINTER(i)], i), "tsd_model_attn_window": ([vp, C.POINTER(i)], i),
+        "tsd_model_set_token_merge": ([vp, fp, C.c_uint32], i), "tsd_model_token_merge": ([vp, fp, C.POINTER(C.c_uint32)], i),
+        "tsd_token_merge_plan_f16": ([vp, vp, i, i, i, i, f, C.c_uint32, vp, vp, vp, vp, vp], i),
+        "tsd_token_merge_rows_f16": ([vp, vp, i, i, i, i, vp, vp, vp], i),
+        "tsd_token_unmerge_rows_f16": ([vp, vp, i, i, i, i, vp, vp], i),
+        "tsd_debug_token_merge_run": ([vp, vp, vp, i, i, i, i, f, C.c_uint32, i, vp, vp, vp, vp, vp, vp, vp], i),
+        "tsd_debug_token_merge_record": ([vp, i], i), "tsd_debug_token_merge_recorded": ([vp, i, vp, i], i),
         "tsd_model_set_freeu": ([vp, fp, fp, i], i), "tsd_model_freeu": ([vp, fp, fp, C.POINTER(i)], i),
         "tsd_freeu_f16": ([vp, vp, vp, i, i, i, i, i, f, f, i, vp, vp], i),
         "tsd_debug_freeu_run": ([vp, vp, vp, i, i, i, i, i, i, i, i, f, f, i, vp, vp], i),

@@ -15,6 +15,7 @@ from ._lib import NULL_MATRIX, check, f32, fp, lib, ptr
 from .attention import Cross_Attention, Self_Attention
 from .fp8 import ff_fp8_mode
 from .model import Model
+from .token_merge import _TokenMerge
 from .utils import Conv2D, GroupNorm, LayerNorm, Linear, SiLU, Upsample, _ctx, concat
 
 
@@ -199,7 +200,7 @@ class _AttnWindow:
         return tuple(int(v) for v in out)
 
 
-class Diffusion(_AttnWindow):
+class Diffusion(_AttnWindow, _TokenMerge):
     """`Diffusion` diffusion.mojo:294-318 - device-resident weights; forward is ONE libtsd call.
 
     forward(x, context, time): x (4,LH,LW) or (B,4,LH,LW), square or not; context (T,768)/(1,T,768) or (B,T,768);
@@ -396,7 +397,7 @@ CONTROL_RESIDUAL_SHAPES = ((320, 1), (320, 1), (320, 1), (320, 2), (640, 2), (64
                            (1280, 8), (1280, 8))
 
 
-class ControlNet(_AttnWindow):
+class ControlNet(_AttnWindow, _TokenMerge):
     """ControlNet of the full-size UNet (Zhang et al. 2023; the layout of diffusers' `ControlNetModel`) - device-resident weights.
 
     variant: "controlnet_sd15" (the reference's norms, pairs with "diffusion_sd15") or "controlnet_sd15_torch" (the norm semantics and

@@ -29,7 +29,7 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
              mask_mode="any", seeds=None, guidance_rescale=0.0, prediction="epsilon", zero_terminal_snr=False, controlnet=None,
              control_image=None, control_scale=1.0, control_cond_only=False, control_start=0.0, control_end=1.0, ip_adapter=None,
              ip_image_embeds=None, ip_scale=1.0, ip_start=0.0, ip_end=1.0, ip_image=None, image_encoder=None, ip_hidden=None,
-             ip_uncond_hidden=None, freeu=None, ff_fp8=None, attn_window=None):
+             ip_uncond_hidden=None, freeu=None, ff_fp8=None, attn_window=None, token_merge=None):
     """context (B,T,768); returns images (B,3,8LH,8LW) in [0,255] like pipeline.mojo:127.  L is the latent side (64: 512x512) or a pair
     (LH, LW) for a rectangular image ((96, 64): 512 wide, 768 high); where the text below says L,L the tensor is LH,LW.
 
@@ -87,14 +87,19 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
 
     attn_window, an int (the top level's window side in tokens) or 4 sides per level (`Diffusion.set_attn_window`): the UNet's self
     attention runs in windows for this call, and so does the self attention of `controlnet` when one is given; the tables the models
-    held are back on every way out."""
+    held are back on every way out.
+
+    token_merge, a ratio (the top level's), 4 ratios per level or (ratios, seed) (`Diffusion.set_token_merge`): the UNet's self attention
+    runs on merged tokens for this call, and so does `controlnet`'s; the tables the models held are back on every way out."""
     from .fp8 import ff_fp8_scope
+    from .token_merge import token_merge_scope
     from .diffusion import attn_window_scope
     from .free_u import freeu_scope
     with freeu_scope(diffusion, freeu), ff_fp8_scope(diffusion, ff_fp8), attn_window_scope(diffusion, attn_window), \
-            attn_window_scope(controlnet, attn_window if hasattr(controlnet, "set_attn_window") else None):  # (anything else: refused below)
+            attn_window_scope(controlnet, attn_window if hasattr(controlnet, "set_attn_window") else None), \
+            token_merge_scope(diffusion, token_merge), token_merge_scope(controlnet, token_merge):  # (any other controlnet: refused below)
         return _generate(**{k: v for k, v in locals().items() if k not in ("freeu", "freeu_scope", "ff_fp8", "ff_fp8_scope", "attn_window",
-                                                                           "attn_window_scope")})
+                                                                           "attn_window_scope", "token_merge", "token_merge_scope")})
 
 
 def _generate(diffusion, decoder, context, uncond_context, strength, cfg, cfg_scale, inference_steps, seed_val, input_image, encoder, latents,

@@ -141,7 +141,7 @@ class SlotScheduler:
 
 def generate_stream(diffusion, decoder, requests, B, L, T=77, cfg=True, inference_steps=50, num_training_steps=1000, sampler="ddpm",
                     eta=0.0, spacing="leading", return_latents=False, stats=None, prediction="epsilon", zero_terminal_snr=False, controlnet=None,
-                    control_image=None, freeu=None, attn_window=None, **control_keywords):
+                    control_image=None, freeu=None, attn_window=None, token_merge=None, **control_keywords):
     """Continuous batching of `generate`: `requests` is an iterator of `Request`s (or tuples in its field order); yields (id, image
     (3,8LH,8LW) in [0,255]) - or (id, latents) with return_latents or without a decoder - as requests finish, B at a time on the device.
     L is the latent side or a pair (LH, LW): one shape for the whole stream.
@@ -157,7 +157,8 @@ def generate_stream(diffusion, decoder, requests, B, L, T=77, cfg=True, inferenc
     control is not supported (`generate` runs lockstep sessions and takes them).  generate's ip_adapter / ip_image_embeds / ip_scale /
     ip_start / ip_end / ip_image / ip_hidden / ip_uncond_hidden are refused for the same reason: per-slot adapters are not supported.
     freeu is `generate`'s keyword: FreeU is state of the model, so of the whole stream; the model's previous table is back when the stream
-    ends, however it ends.  attn_window is `generate`'s keyword too (windowed self attention: an int or 4 sides), held the same way."""
+    ends, however it ends.  attn_window is `generate`'s keyword too (windowed self attention: an int or 4 sides), held the same way, and
+    so is token_merge (a ratio, 4 ratios or (ratios, seed))."""
     if any(k.startswith("ip_") for k in control_keywords):
         raise ValueError("generate_stream runs on a slot session, which has no IP-Adapter (per-slot adapters are not supported); use generate()")
     if controlnet is not None or control_image is not None or control_keywords:
@@ -166,7 +167,8 @@ def generate_stream(diffusion, decoder, requests, B, L, T=77, cfg=True, inferenc
     from .model import Session
     from .utils import _unary
     from .diffusion import attn_window_scope
-    with freeu_scope(diffusion, freeu), attn_window_scope(diffusion, attn_window):
+    from .token_merge import token_merge_scope
+    with freeu_scope(diffusion, freeu), attn_window_scope(diffusion, attn_window), token_merge_scope(diffusion, token_merge):
         yield from _stream(diffusion, decoder, requests, B, L, T, cfg, inference_steps, num_training_steps, sampler, eta, spacing, return_latents,
                            stats, prediction, zero_terminal_snr, Session, _unary)
 
