@@ -904,6 +904,13 @@ enum tsd_attn_desc_field {
  * reports in TSD_AI_KERNEL the plain sibling of the instantiation that ran; the sizing mode plans on the window's shape. */
 #define TSD_AD_VERSION_3 3
 enum tsd_attn_desc_field_v3 { TSD_AD3_WIN = TSD_AD_COUNT, TSD_AD3_GRID_H, TSD_AD3_GRID_W, TSD_AD3_COUNT };
+/* Version 4 has the fields of version 3 (WIN must be 0) and, BEHIND them (n >= TSD_AD4_COUNT), the table of a shared self-attention launch
+ * (tsd_model_set_attn_share): SHARE_N entries (0 = not shared: the launch of a version-2 descriptor; at most 8 here, B % SHARE_N == 0,
+ * SQ == SK) in SHARE_0 .. SHARE_0 + 7, each -1 or the index inside its group of SHARE_N samples of the sample whose keys sample
+ * j (entry j % SHARE_N) also attends to.  Operands are sized as for version 2.  A shared run reports in TSD_AI_KERNEL the plain sibling of
+ * the instantiation that ran; the plan counts the keys of both segments (Sk = 2 SQ). */
+#define TSD_AD_VERSION_4 4
+enum tsd_attn_desc_field_v4 { TSD_AD4_SHARE_N = TSD_AD3_COUNT, TSD_AD4_SHARE_0, TSD_AD4_COUNT = TSD_AD4_SHARE_0 + 8 };
 enum tsd_attn_mode { TSD_AM_ATTN = 0, TSD_AM_SOFTMAX_ROWS };
 /* Operand slots: inputs Q [B][Sq][ldq], K [B][Sk][ldk], V^T [B][H*d][ldvt] (fp16), X (softmax_rows input: fp32, or the fp16 rows the
  * launch overwrites); output O (attention: [B][Sq][ldo] fp16; softmax_rows: the rows, in X's type and layout). */
@@ -1182,6 +1189,33 @@ int tsd_model_attn_window(tsd_model* unet, int out[4]);
  * mean per launch.  TSD_E_ARG: NULL ctx / ms, iters <= 0, an empty or oversized grid, a side outside the list; TSD_E_SHAPE: a head
  * dimension without a fused kernel, a window that does not divide the grid (both from the launcher). */
 int tsd_debug_attn_bench_win(tsd_ctx* ctx, int B, int H, int d, int grid_h, int grid_w, int win, int iters, float* ms);
+
+/* ---- Shared self attention (EXTENSION, training-free: reference-only control, StyleAligned, cross-frame attention) on the UNets.  A
+ * sample b with an entry r also attends to sample r's keys and values in every self-attention block of the chosen levels:
+ *   O_b = softmax(c Q_b [K_b ; K_r]^T) [V_b ; V_r], one softmax over 2 S keys per head;
+ * cross attention, IP-Adapter and everything else is untouched.  Still one launch per block and no copy: flash_attn_share_kernel walks the
+ * reference's K / V^T where the projection of the same forward has written them.
+ * share[n] (n <= 32): -1, or an index < n other than the entry's own (anything else, entries below -1 included, is TSD_E_ARG).  One hop: the reference's own attention follows ITS entry, normally
+ * -1.  A forward of batch Bf uses share[j % n] for sample j, inside j's own group of n consecutive samples, and needs Bf % n == 0
+ * (TSD_E_SHAPE otherwise).  levels[l] != 0 turns sharing on for the blocks whose token grid is LH / 2^l x LW / 2^l.
+ * cond_only != 0: only the FIRST half of a forward's batch shares and the table is applied to that half (Bf / 2 % n == 0).  A CFG session
+ * runs the UNet on [conditional samples ; unconditional samples] (the order tsd_session_set_control's cond_only goes by), so this leaves
+ * the unconditional half plain - reference-only's usual setting.  Without CFG it has no use.
+ * A sample without an entry runs one key segment in the same launch: the bits of the plain kernel OF THE SAME INSTANTIATION.  The launch is
+ * planned on 2 S keys and never takes the 8-wave kernel, so where a plain forward would pick another instantiation (d = 40: the 8-wave
+ * kernel at 4096 tokens, QB = 1 at 256) that sample equals its plain-forward result only while no workgroup repeats exactly.
+ * NULL, n = 0, all -1 or all-zero levels turn it off: the model then enqueues exactly the launches it did before and gives the bits it
+ * gave.  State of the MODEL, like the window table: from the next forward / step() / advance() on, no upload(), the same workspace.
+ * TSD_E_ARG, the model's state staying as it was: a kind that is no UNet (ControlNets included), n > 32 or n < 0, an entry that is its own
+ * index or >= n, a level that carries a window or a merge ratio (and those setters refuse a level that shares).
+ * tsd_model_attn_share: the number of entries n (0 = off; negative: TSD_E_ARG); up to cap entries go to share_out, the levels and the
+ * flag to levels_out / cond_only_out, each when not NULL. */
+#define TSD_ATTN_SHARE_MAX 32
+int tsd_model_set_attn_share(tsd_model* unet, const int* share, int n, const int levels[4], int cond_only);
+int tsd_model_attn_share(tsd_model* unet, int* share_out, int cap, int levels_out[4], int* cond_only_out);
+/* Debug / bench entry like tsd_debug_attn_bench: time `iters` self-attention launches (Sq = Sk = S) on synthetic device data; share != 0:
+ * samples 1 .. B - 1 also attend to sample 0's keys (2 <= B <= 32).  *ms is the mean per launch. */
+int tsd_debug_attn_bench_share(tsd_ctx* ctx, int B, int H, int d, int S, int share, int iters, float* ms);
 
 /* ---- Token merging (EXTENSION: ToMe for Stable Diffusion, Bolya & Hoffman 2023; tomesd's bipartite_soft_matching_random2d with
  * sx = sy = 2, self attention only, training-free).  In front of a block's self attention the r most similar source tokens are merged

@@ -323,6 +323,9 @@ extern "C" int tsd_model_set_attn_window(tsd_model* unet, const int win[4]) {
   for (int l = 0; win && l < 4; l++)
     if (win[l] != 0 && unet->tome_ratio[l] > 0.f)
       TSD_FAIL(TSD_E_ARG, "tsd_model_set_attn_window: level %d merges tokens (tsd_model_set_token_merge): a level has a window or a merge ratio, not both", l);
+  for (int l = 0; win && l < 4; l++)
+    if (win[l] != 0 && unet->share_n && unet->share_levels[l])
+      TSD_FAIL(TSD_E_ARG, "tsd_model_set_attn_window: level %d shares keys (tsd_model_set_attn_share): a level has a window, a merge ratio or sharing, never two", l);
   for (int l = 0; l < 4; l++) unet->attn_win[l] = win ? win[l] : 0;
   return TSD_OK;
 }
@@ -336,6 +339,8 @@ extern "C" int tsd_model_set_token_merge(tsd_model* unet, const float ratio[4], 
     if (!(ratio[l] >= 0.f && ratio[l] <= 0.75f)) TSD_FAIL(TSD_E_ARG, "tsd_model_set_token_merge: level %d: ratio %g (0 .. 0.75)", l, (double)ratio[l]);
     if (ratio[l] > 0.f && unet->attn_win[l])
       TSD_FAIL(TSD_E_ARG, "tsd_model_set_token_merge: level %d is windowed (tsd_model_set_attn_window): a level has a window or a merge ratio, not both", l);
+    if (ratio[l] > 0.f && unet->share_n && unet->share_levels[l])
+      TSD_FAIL(TSD_E_ARG, "tsd_model_set_token_merge: level %d shares keys (tsd_model_set_attn_share): a level has a window, a merge ratio or sharing, never two", l);
   }
   for (int l = 0; l < 4; l++) unet->tome_ratio[l] = ratio ? ratio[l] : 0.f;
   unet->tome_seed = ratio ? seed : 0;
@@ -363,6 +368,40 @@ extern "C" int tsd_model_attn_window(tsd_model* unet, int out[4]) {
     on |= unet->attn_win[l] != 0;
   }
   return on;
+}
+
+// Shared self attention: the model's table, read like the window table when a forward is enqueued (attn_share_for, graph.cpp).  A table
+// that shares nothing (no entry >= 0, or no level) is stored as "off", so that off is one state.
+extern "C" int tsd_model_set_attn_share(tsd_model* unet, const int* share, int n, const int levels[4], int cond_only) {
+  NOTNULL(unet);
+  if (!is_diffusion_kind(unet->kind))
+    TSD_FAIL(TSD_E_ARG, "tsd_model_set_attn_share: shared self attention belongs to the UNets, this model is kind %d", unet->kind);
+  if (n < 0 || n > TSD_ATTN_SHARE_MAX) TSD_FAIL(TSD_E_ARG, "tsd_model_set_attn_share: %d entries (0 .. %d)", n, TSD_ATTN_SHARE_MAX);
+  bool any = false, lev = false;
+  for (int i = 0; share && i < n; i++) {
+    if (share[i] < -1 || share[i] >= n || share[i] == i)
+      TSD_FAIL(TSD_E_ARG, "tsd_model_set_attn_share: entry %d is %d (-1, or another index below %d)", i, share[i], n);
+    any = any || share[i] >= 0;
+  }
+  for (int l = 0; levels && l < 4; l++) lev = lev || levels[l] != 0;
+  const bool on = share && any && lev;
+  for (int l = 0; on && l < 4; l++)
+    if (levels[l] && (unet->attn_win[l] || unet->tome_ratio[l] > 0.f))
+      TSD_FAIL(TSD_E_ARG, "tsd_model_set_attn_share: level %d has a window or a merge ratio: a level has a window, a merge ratio or sharing, never two", l);
+  unet->share_n = on ? n : 0;
+  unet->share_cond_only = on && cond_only ? 1 : 0;
+  for (int l = 0; l < 4; l++) unet->share_levels[l] = on && levels[l] ? 1 : 0;
+  for (int i = 0; i < TSD_ATTN_SHARE_MAX; i++) unet->share[i] = (signed char)(on && i < n && share[i] >= 0 ? share[i] : -1);
+  return TSD_OK;
+}
+extern "C" int tsd_model_attn_share(tsd_model* unet, int* share_out, int cap, int levels_out[4], int* cond_only_out) {
+  NOTNULL(unet);
+  if (!is_diffusion_kind(unet->kind))
+    TSD_FAIL(TSD_E_ARG, "tsd_model_attn_share: shared self attention belongs to the UNets, this model is kind %d", unet->kind);
+  for (int i = 0; share_out && i < cap && i < unet->share_n; i++) share_out[i] = unet->share[i];
+  for (int l = 0; levels_out && l < 4; l++) levels_out[l] = unet->share_levels[l];
+  if (cond_only_out) *cond_only_out = unet->share_cond_only;
+  return unet->share_n;
 }
 
 extern "C" int tsd_decoder_forward_hw(tsd_model* m, const float* latents, int B, int LH, int LW, float* images) {

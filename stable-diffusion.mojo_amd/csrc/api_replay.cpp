@@ -479,7 +479,8 @@ int ad_extents(const int64_t* d, int64_t* e) {
   for (int i = 0; i < TSD_AO_COUNT; i++) e[i] = 0;
 #define AD_REQ(cond) \
   if (!(cond)) TSD_FAIL(TSD_E_ARG, "attn_run: descriptor cannot be sized (%s)", #cond)
-  AD_REQ(d[TSD_AD_VERSION] == TSD_AD_VERSION_1 || d[TSD_AD_VERSION] == TSD_AD_VERSION_2 || d[TSD_AD_VERSION] == TSD_AD_VERSION_3);
+  AD_REQ(d[TSD_AD_VERSION] == TSD_AD_VERSION_1 || d[TSD_AD_VERSION] == TSD_AD_VERSION_2 || d[TSD_AD_VERSION] == TSD_AD_VERSION_3 ||
+         d[TSD_AD_VERSION] == TSD_AD_VERSION_4);
   const int64_t mode = d[TSD_AD_MODE], lim = 1LL << 28;
   AD_REQ(mode == TSD_AM_ATTN || mode == TSD_AM_SOFTMAX_ROWS);
   if (mode == TSD_AM_ATTN) {
@@ -499,6 +500,12 @@ int ad_extents(const int64_t* d, int64_t* e) {
       const int64_t w = d[TSD_AD3_WIN], gh = d[TSD_AD3_GRID_H], gw = d[TSD_AD3_GRID_W];
       AD_REQ(attn_window_side_ok((int)std::min<int64_t>(std::max<int64_t>(w, 0), 1 << 20)));
       AD_REQ(gh > 0 && gw > 0 && gh <= (1 << 20) && gw <= (1 << 20) && gh * gw == d[TSD_AD_SQ] && d[TSD_AD_SQ] == d[TSD_AD_SK]);
+    }
+    if (d[TSD_AD_VERSION] == TSD_AD_VERSION_4) {  // (the caller has checked that a version-4 descriptor has these fields)
+      const int64_t sn = d[TSD_AD4_SHARE_N];
+      AD_REQ(d[TSD_AD3_WIN] == 0 && sn >= 0 && sn <= 8);
+      if (sn) AD_REQ(B % sn == 0 && d[TSD_AD_SQ] == d[TSD_AD_SK]);
+      for (int64_t i = 0; i < sn; i++) AD_REQ(d[TSD_AD4_SHARE_0 + i] >= -1 && d[TSD_AD4_SHARE_0 + i] < sn && d[TSD_AD4_SHARE_0 + i] != i);
     }
     e[TSD_AO_Q] = (B - 1) * d[TSD_AD_SQB] + (Sq - 1) * d[TSD_AD_LDQ] + C;
     e[TSD_AO_K] = (B - 1) * d[TSD_AD_SKB] + (Sk - 1) * d[TSD_AD_LDK] + C;
@@ -525,10 +532,12 @@ extern "C" int tsd_debug_attn_run(tsd_ctx* ctx, const int64_t* desc, int n, cons
   NOTNULL(desc); NOTNULL(ext);
   TSD_TRY(check_fields("attn_run", n, TSD_AD_COUNT));
   if (desc[TSD_AD_VERSION] == TSD_AD_VERSION_3) TSD_TRY(check_fields("attn_run (version 3)", n, TSD_AD3_COUNT));
+  if (desc[TSD_AD_VERSION] == TSD_AD_VERSION_4) TSD_TRY(check_fields("attn_run (version 4)", n, TSD_AD4_COUNT));
   TSD_TRY(ad_extents(desc, ext));
   const int64_t* d = desc;
   const bool attn = d[TSD_AD_MODE] == TSD_AM_ATTN;
   const int win = attn && d[TSD_AD_VERSION] == TSD_AD_VERSION_3 ? (int)d[TSD_AD3_WIN] : 0;  // 0: the launch of a version-2 descriptor
+  const int share_n = attn && d[TSD_AD_VERSION] == TSD_AD_VERSION_4 ? (int)d[TSD_AD4_SHARE_N] : 0;  // 0: the same
   // head dimension 64 came with version 2: a version-1 descriptor is sized and refused as it was before the d = 64 kernel existed
   const bool v1_d64 = attn && d[TSD_AD_VERSION] == TSD_AD_VERSION_1 && d[TSD_AD_D] == 64;
   if (info) for (int i = 0; i < TSD_AI_COUNT; i++) info[i] = 0;
@@ -540,6 +549,7 @@ extern "C" int tsd_debug_attn_run(tsd_ctx* ctx, const int64_t* desc, int n, cons
       const bool tiles = win && gh % win == 0 && gw % win == 0;  // a grid the window does not divide is planned as the launcher refuses it: not at all
       if (win && !tiles) return TSD_OK;
       const AttnPlan p = win ? attn_plan(o, (int)d[TSD_AD_B], (int)d[TSD_AD_H], (int)d[TSD_AD_D], win * win, win * win, (gh / win) * (gw / win))
+                         : share_n ? attn_plan(o, (int)d[TSD_AD_B], (int)d[TSD_AD_H], (int)d[TSD_AD_D], (int)d[TSD_AD_SQ], 2 * (int)d[TSD_AD_SK], 0, true)
                              : attn_plan(o, (int)d[TSD_AD_B], (int)d[TSD_AD_H], (int)d[TSD_AD_D], (int)d[TSD_AD_SQ], (int)d[TSD_AD_SK]);
       info[TSD_AI_KERNEL] = p.kernel; info[TSD_AI_DIAG] = p.diag; info[TSD_AI_XCD_MAP] = p.xcd_map;
     }
@@ -570,6 +580,10 @@ extern "C" int tsd_debug_attn_run(tsd_ctx* ctx, const int64_t* desc, int n, cons
     a.B = (int)d[TSD_AD_B]; a.H = (int)d[TSD_AD_H]; a.d = (int)d[TSD_AD_D]; a.Sq = (int)d[TSD_AD_SQ]; a.Sk = (int)d[TSD_AD_SK];
     a.scale = f32_of(d[TSD_AD_SCALE]);
     if (win) { a.win = win; a.grid_h = (int)d[TSD_AD3_GRID_H]; a.grid_w = (int)d[TSD_AD3_GRID_W]; }
+    if (share_n) {
+      a.share_n = share_n; a.share_lo = 0; a.share_hi = a.B;
+      for (int i = 0; i < share_n; i++) a.share[i] = (signed char)d[TSD_AD4_SHARE_0 + i];
+    }
     r = run_planned(ctx, [&]() -> int {
       if (v1_d64) TSD_FAIL(TSD_E_SHAPE, "flash attention: head dim %d unsupported", a.d);
       return launch_flash_attention(ctx, a);

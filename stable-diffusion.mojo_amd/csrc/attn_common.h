@@ -23,6 +23,11 @@ struct AttnK {
   // windowed self attention (flash_attn_win_kernel only; 0 = not windowed): the sample's tokens are a grid_h x grid_w grid cut into
   // win x win windows, Sq = Sk = Skv = win * win is ONE window's problem and Q / K / V^T / O keep the whole grid's rows
   int win, grid_h, grid_w;
+  // shared self attention (flash_attn_share_kernel only; share_n = 0 otherwise): sample b of [share_lo, share_hi) reads entry b % share_n
+  // of the table - byte (b % share_n) of share_w, little endian, holds 1 + the index inside b's group of share_n samples of the sample
+  // whose keys b also attends to, 0 = none.  In scalar registers all the way: no memory is indexed.
+  int share_n, share_lo, share_hi;
+  unsigned long long share_w[4];
 };
 
 // Largest score (log2 units, relative to the running reference) a tile may reach before the reference is moved.

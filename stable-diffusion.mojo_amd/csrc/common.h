@@ -129,7 +129,9 @@ struct AttnPlan {
 };
 // nwin > 0: a windowed launch (AttnArgs::win) - Sq = Sk = win * win is one window's shape and the nwin windows of a sample stand in the
 // grid test beside its heads; the 8-wave kernel is never chosen.
-AttnPlan attn_plan(const TsdOptions& opt, int B, int H, int d, int Sq, int Sk, int nwin = 0);
+// share: a shared launch (AttnArgs::share_n) - Sk = 2 Sq counts both key segments, the launch is still self attention for `diag`, and the
+// 8-wave kernel is never chosen.
+AttnPlan attn_plan(const TsdOptions& opt, int B, int H, int d, int Sq, int Sk, int nwin = 0, bool share = false);
 // What launch_small_linear launched (kernels_elementwise.hip), left in tsd_ctx::sl_last; tsd_debug_elem_run reports it.
 struct SmallLinearPlan {
   int nb = 0;      // the k_small_linear<NB> instance: 1, 2, 4, 8 or 16; 0 = none ran
@@ -707,7 +709,12 @@ struct AttnArgs {
   // windowed self attention (HyperTile): win > 0 cuts the grid_h x grid_w token grid (Sq = Sk = grid_h * grid_w, row-major) into
   // win x win windows and every query attends to the keys of its own window only.  win in {8, 16, 32, 64, 128} divides both sides.
   int win = 0, grid_h = 0, grid_w = 0;
+  // shared self attention: share_n > 0 (<= ATTN_SHARE_MAX, divides B, Sq == Sk, no window) makes sample b of [share_lo, share_hi) with
+  // r = share[b % share_n] >= 0 attend to [its own keys ; the keys of sample b - b % share_n + r] under one softmax; r < 0: its own only.
+  int share_n = 0, share_lo = 0, share_hi = 0;
+  signed char share[32] = {};
 };
+constexpr int ATTN_SHARE_MAX = 32;
 bool attn_fused_supported(int d);
 bool attn_window_side_ok(int win);  // 8, 16, 32, 64, 128
 

@@ -225,14 +225,33 @@ int token_merge_for(const tsd_model* m, int LH, int H, int W, TomeSel* tm) {
   return TSD_OK;
 }
 
+// Shared self attention of a self-attention block whose token grid is H x W in a forward of B samples at LH latent rows: the level is
+// found as attn_window_for finds it.  The table covers the whole batch in groups of n samples, or its first half under cond_only (a CFG
+// session's conditional samples); a batch the groups do not fill is refused - never a silent plain launch.
+int attn_share_for(const tsd_model* m, int LH, int H, int W, int B, ShareSel* sh) {
+  *sh = ShareSel();
+  if (!m->share_n) return TSD_OK;
+  int l = 0, h = LH;
+  while (l < 3 && h > H) { h = (h + 1) / 2; l++; }
+  if (h != H) TSD_FAIL(TSD_E_SHAPE, "shared attention: a %d x %d token grid is no level of a forward at %d latent rows", H, W, LH);
+  const int Bs = m->share_cond_only ? B / 2 : B;  // the samples the table is applied to
+  if ((m->share_cond_only && B % 2) || Bs % m->share_n)
+    TSD_FAIL(TSD_E_SHAPE, "shared attention: a table of %d entries over %s%d samples of a forward (a multiple)", m->share_n,
+             m->share_cond_only ? "the first half of " : "", B);
+  if (!m->share_levels[l]) return TSD_OK;
+  sh->n = m->share_n; sh->lo = 0; sh->hi = Bs; sh->table = m->share;
+  return TSD_OK;
+}
+
 // `Unet_Attention_Block.forward` diffusion.mojo:112-147 on NHWC tokens
 int g_unet_attn(tsd_ctx* ctx, const Act& x, const AttnW& w, const half_t* ctx16, int T, int Tp, Act& out,
-                const CtxKV* pre, const IpKV* ipkv, int win, TomeSel tm) {
+                const CtxKV* pre, const IpKV* ipkv, int win, TomeSel tm, ShareSel sh) {
   const int C = w.C, B = x.B, S = x.H * x.W, d = w.n_embed, Hh = w.n_head;
   const int64_t M = (int64_t)B * S;
   const int Sa = S - tm.r;  // rows per sample of the self-attention projections and core: the merged sequence when tokens merge (tm.r > 0)
   const int64_t Ma = (int64_t)B * Sa;
   if (tm.r && win) TSD_FAIL(TSD_E_ARG, "attention block: a window and token merging on the same block");
+  if (sh.n && (tm.r || win)) TSD_FAIL(TSD_E_ARG, "attention block: shared keys with a window or token merging on the same block");
   if (C % 64 || x.C != C) TSD_FAIL(TSD_E_SHAPE, "attention block: C=%d (input %d) unsupported", C, x.C);
   if (!attn_fused_supported(d)) TSD_FAIL(TSD_E_SHAPE, "attention block: head dim %d unsupported (40/64/80/160)", d);
   if (S % 4) TSD_FAIL(TSD_E_SHAPE, "attention block: H*W=%d must be a multiple of 4", S);
@@ -338,8 +357,13 @@ int g_unet_attn(tsd_ctx* ctx, const Act& x, const AttnW& w, const half_t* ctx16,
   fa.O = tm.r ? aom : ao; fa.ldo = C; fa.sO = (int64_t)Sa * C;
   fa.B = B; fa.H = Hh; fa.d = d; fa.Sq = Sa; fa.Sk = Sa; fa.scale = scale;
   if (win) { fa.win = win; fa.grid_h = x.H; fa.grid_w = x.W; }  // self attention only: the cross-attention launch below clears it
+  if (sh.n) {  // the reference's K / V^T are rows of qk / vt of this very launch: nothing is copied (cleared for cross attention below)
+    fa.share_n = sh.n; fa.share_lo = sh.lo; fa.share_hi = sh.hi;
+    for (int i = 0; i < sh.n; i++) fa.share[i] = sh.table[i];
+  }
   TSD_TRY(launch_flash_attention(ctx, fa));
   fa.win = 0; fa.grid_h = 0; fa.grid_w = 0;
+  fa.share_n = 0; fa.share_lo = 0; fa.share_hi = 0;
   if (tm.r) {  // out[t] = y[row_of[t]] in front of sa_out (linear per row): everything behind the core keeps its launches
     TSD_TRY(launch_tome_unmerge(ctx, aom, C, B, S, C, Sa, tm_row_of, ao, C));
     fa.O = ao; fa.sO = (int64_t)S * C; fa.Sq = S;
@@ -695,7 +719,9 @@ int g_unet_forward(tsd_model* m, const float* latents_chw, const half_t* ctx16, 
     TSD_TRY(attn_window_for(m, LH, a[i - 1].H, a[i - 1].W, &win));
     TomeSel tm;
     TSD_TRY(token_merge_for(m, LH, a[i - 1].H, a[i - 1].W, &tm));
-    return g_unet_attn(ctx, a[i - 1], w, ctx16, T, Tp, a[i], &kv, nullptr, win, tm);
+    ShareSel sh;
+    TSD_TRY(attn_share_for(m, LH, a[i - 1].H, a[i - 1].W, a[i - 1].B, &sh));
+    return g_unet_attn(ctx, a[i - 1], w, ctx16, T, Tp, a[i], &kv, nullptr, win, tm, sh);
   };
   // encoders (diffusion.mojo:236-250)
   TSD_TRY(alloc_out(1, LH, LW, 320));
@@ -853,7 +879,9 @@ static int unet_full_steps(const FullRun& f, int i0, int i1, Act& cur, std::vect
       TSD_TRY(attn_window_for(m, f.LH, cur.H, cur.W, &win));
       TomeSel tm;
       TSD_TRY(token_merge_for(m, f.LH, cur.H, cur.W, &tm));
-      TSD_TRY(g_unet_attn(ctx, cur, w, f.ctx16, f.T, f.Tp, y, &kv, f.ip ? &ik : nullptr, win, tm));
+      ShareSel sh;
+      TSD_TRY(attn_share_for(m, f.LH, cur.H, cur.W, cur.B, &sh));
+      TSD_TRY(g_unet_attn(ctx, cur, w, f.ctx16, f.T, f.Tp, y, &kv, f.ip ? &ik : nullptr, win, tm, sh));
     }
     cur = y;
     if (st.flags & U_PUSH) {

@@ -78,8 +78,15 @@ struct TomeSel {
   uint32_t seed = 0;
 };
 int token_merge_for(const tsd_model* m, int LH, int H, int W, TomeSel* tm);
+// Shared self attention of the block, as attn_share_for gives it: n table entries (0 = off, the plain launch) applied to samples [lo, hi)
+// of the forward's batch; the table is the model's.
+struct ShareSel {
+  int n = 0, lo = 0, hi = 0;
+  const signed char* table = nullptr;
+};
+int attn_share_for(const tsd_model* m, int LH, int H, int W, int B, ShareSel* sh);
 int g_unet_attn(tsd_ctx* ctx, const Act& x, const AttnW& w, const half_t* ctx16, int T, int Tp, Act& out,
-                const CtxKV* pre = nullptr, const IpKV* ipkv = nullptr, int win = 0, TomeSel tm = TomeSel());
+                const CtxKV* pre = nullptr, const IpKV* ipkv = nullptr, int win = 0, TomeSel tm = TomeSel(), ShareSel sh = ShareSel());
 int g_vae_attn(tsd_ctx* ctx, const Act& x, const VaeAttnW& w, Act& out);
 int g_attn_core(tsd_ctx* ctx, const AttnArgs& fa);
 int g_qkv_proj(tsd_ctx* ctx, const half_t* x, int B, int S, int C, const LinW& in_proj, half_t* qk, half_t* vt, int Sp);

@@ -64,8 +64,22 @@ __device__ unsigned long long g_attn_ts[4 * 65536];  // per block: memtime start
 // every window and only the scalar tile offset moves.  A window holds whole 64-key tiles: no partial tile, no pad column, no masking.
 // Everything else - swizzles, pitches, ones row, both softmax passes, the counter - is the plain kernel's on the window's problem, so a
 // windowed launch gives the bits of the plain instantiation on window-major gathered operands.
-template <int D, int QB, bool WIN>
+//
+// SHARE (shared self attention: reference-only control, StyleAligned, cross-frame attention): a sample b whose table entry names a
+// reference sample r attends to [K_b ; K_r] / [V_b ; V_r] under ONE softmax.  The projection GEMM has written every sample's K / V^T at a
+// constant sample stride, so the reference's keys are the same base pointers at another batch index: the key loop walks two SEGMENTS of
+// ceil(Sk / 64) tiles each, and what changes at the boundary is scalar - the descriptor base (own sample / reference) and the tile index
+// inside the segment.  The per-lane DMA offsets, the LDS ring, the MFMA schedule and the V^T offsets of a segment's last tile are the
+// plain kernel's.  Each segment is walked as the plain kernel walks its keys: its K descriptor ends behind key Sk - 1 of ITS sample, the
+// keys >= Sk of its last tile are masked and its V^T pad chunks are zero-filled - so a masked tail can sit in the middle of the key stream.
+// The tile counter t that drives the softmax (reference from tile 0, the early look every CHECK_EVERY tiles, the exact repeat) runs on
+// through both segments: segment 1 continues the running reference and the row sums, and a peaked key there repeats the workgroup
+// exactly like one in segment 0.  With Sk % 64 == 0 the tile stream is that of the plain kernel on the concatenated keys, hence the
+// same bits.  A sample without an entry (or outside [share_lo, share_hi)) has one segment: the plain kernel's loop and bits.  The table
+// arrives by value in the kernel arguments and is decoded with scalar shifts; p.Sk and p.Skv are ONE segment's counts.
+template <int D, int QB, bool WIN, bool SHARE = false>
 __device__ __forceinline__ void flash_attn_body(const AttnK& p) {
+  static_assert(!(WIN && SHARE), "a launch is windowed or shared, not both");
   constexpr int NST = 2;                   // K / V^T tile buffers
   constexpr int DCH = D / 8;               // 16-B chunks per K row
   constexpr int KSTEPS = (DCH + 1) / 2;    // QK^T k-steps (16 wide)
@@ -119,6 +133,22 @@ __device__ __forceinline__ void flash_attn_body(const AttnK& p) {
   const half_t* Qb = p.Q + b * p.sQ + h * D;
   const half_t* Kb = p.K + b * p.sK + h * D;
   const half_t* Vb = p.Vt + b * p.sVt + (long long)h * D * p.ldvt;
+  // shared: the second segment's bases (the reference sample's K / V^T of the same head); ref < 0 = one segment.  All of it scalar.
+  int ref = -1;
+  const half_t* Kb1 = Kb;
+  const half_t* Vb1 = Vb;
+  if constexpr (SHARE) {
+    if (b >= p.share_lo && b < p.share_hi) {
+      const int g = b % p.share_n, i = g >> 3;
+      const unsigned long long w = i == 0 ? p.share_w[0] : i == 1 ? p.share_w[1] : i == 2 ? p.share_w[2] : p.share_w[3];
+      const int e = (int)((w >> ((g & 7) * 8)) & 0xff);
+      if (e) ref = b - g + e - 1;
+    }
+    if (ref >= 0) {
+      Kb1 = p.K + ref * p.sK + h * D;
+      Vb1 = p.Vt + ref * p.sVt + (long long)h * D * p.ldvt;
+    }
+  }
 
   // ---- Q fragments (B operand of S^T = K.Q^T): lane holds Q[q][chunk ks*2+hi] -----------------
   h8 qf[QB][KSTEPS];
@@ -165,15 +195,18 @@ __device__ __forceinline__ void flash_attn_body(const AttnK& p) {
   // is a run of keys inside a longer pitch, so a chunk past the last valid key is NOT out of the descriptor's
   // linear range: the last tile uses its own offset set with those chunks padded.
   const rsrc_t rV = make_rsrc(Vb);
-  const int ntiles = (p.Sk + 63) >> 6;
+  const int nt1 = (p.Sk + 63) >> 6;                            // tiles of one segment
+  const int ntiles = SHARE && ref >= 0 ? 2 * nt1 : nt1;        // of the key stream
   unsigned v_voff[V_PW], v_voff_last[V_PW];
 #pragma unroll
   for (int i = 0; i < V_PW; i++) {
     const int R = (wave + 4 * i) * 8 + (lane >> 3);
     const int c = (lane & 7) ^ ((R >> 1) & 7);
     v_voff[i] = R < D ? (unsigned)(R * p.ldvt + (WIN ? tok(c * 8) - wbase : c * 8)) * 2 : PAD_OFF;
-    v_voff_last[i] = ((ntiles - 1) * 64 + c * 8 + 8 <= p.Skv) ? v_voff[i] : PAD_OFF;
+    v_voff_last[i] = ((nt1 - 1) * 64 + c * 8 + 8 <= p.Skv) ? v_voff[i] : PAD_OFF;
   }
+  // shared: tile t of the key stream is tile seg_tile(t) of its segment
+  auto seg_tile = [&](int t) { return SHARE && t >= nt1 ? t - nt1 : t; };
 
   auto stage = [&](int t, int buf) {
 #if TSD_ATTN_ABL & 128
@@ -181,17 +214,21 @@ __device__ __forceinline__ void flash_attn_body(const AttnK& p) {
 #endif
     char* sK = smem + buf * BUF_BYTES;
     char* sV = sK + K_BYTES;
-    const int k0 = tok(t * 64);  // first token of the tile (windowed: of its first window row)
-    const bool last = t == ntiles - 1;  // wave-uniform
+    const int ts = seg_tile(t);
+    const int k0 = tok(ts * 64);  // first token of the tile (windowed: of its first window row; shared: inside its segment)
+    const bool last = ts == nt1 - 1;  // wave-uniform
+    // shared: the descriptors of the tile's segment, rebuilt from the scalar bases (a few SALU instructions a tile, no register held)
+    const rsrc_t rKt = SHARE && t >= nt1 ? make_rsrc(Kb1, p.Sk * p.ldk * 2) : rK;
+    const rsrc_t rVt = SHARE && t >= nt1 ? make_rsrc(Vb1) : rV;
 #pragma unroll
     for (int i = 0; i < K_PW; i++) {
       const int j = wave + 4 * i;
-      if (K_INSTR % 4 == 0 || j < K_INSTR) blds16(rK, k_voff[i], (unsigned)(k0 * p.ldk) * 2, sK + j * 1024);
+      if (K_INSTR % 4 == 0 || j < K_INSTR) blds16(rKt, k_voff[i], (unsigned)(k0 * p.ldk) * 2, sK + j * 1024);
     }
 #pragma unroll
     for (int i = 0; i < V_PW; i++) {
       const int j = wave + 4 * i;
-      if (V_INSTR % 4 == 0 || j < V_INSTR) blds16(rV, last ? v_voff_last[i] : v_voff[i], (unsigned)k0 * 2, sV + j * 1024);
+      if (V_INSTR % 4 == 0 || j < V_INSTR) blds16(rVt, last ? v_voff_last[i] : v_voff[i], (unsigned)k0 * 2, sV + j * 1024);
     }
   };
 
@@ -315,8 +352,8 @@ __device__ __forceinline__ void flash_attn_body(const AttnK& p) {
     for (int qb = 0; qb < QB; qb++) keep_alive(nm[qb]);
     const char* sV = smem + (t & 1) * BUF_BYTES + K_BYTES;
     // lane (hi, r) of block kb holds key kb*32 + (r&3) + 4*((r>>2)&1) + 8*hi + 16*(r>>3)
-    if ((t + 1) * 64 > p.Sk) {
-      const int k0 = t * 64;
+    if ((seg_tile(t) + 1) * 64 > p.Sk) {  // (shared: the partial last tile of EITHER segment)
+      const int k0 = seg_tile(t) * 64;
 #pragma unroll
       for (int kb = 0; kb < 2; kb++)
 #pragma unroll
@@ -531,6 +568,12 @@ template <int D, int QB>
 __global__ __launch_bounds__(256, D == 40 ? 4 - QB : D == 64 ? TSD_ATTN64_WGS : 2) void flash_attn_win_kernel(const AttnK p) {
   flash_attn_body<D, QB, true>(p);
 }
+// The shared sibling (AttnK::share_n > 0): two key segments for the samples with a table entry.  Register budgets as the windowed kernels',
+// <40, 1> at 3 workgroups per CU for the same reason: no new kernel may touch scratch.
+template <int D, int QB>
+__global__ __launch_bounds__(256, D == 40 ? 4 - QB : D == 64 ? TSD_ATTN64_WGS : 2) void flash_attn_share_kernel(const AttnK p) {
+  flash_attn_body<D, QB, false, true>(p);
+}
 
 bool attn_fused_supported(int d) { return d == 40 || d == 64 || d == 80 || d == 160; }
 // per-context switches (TsdOptions): attn_diag 0 = optimistic reference from key tile 0 only (the round-2 behaviour);
@@ -543,11 +586,12 @@ extern "C" int tsd_debug_set_attn_qb(tsd_ctx* ctx, int mode) {
   return ctx_set_option(ctx, &TsdOptions::attn_qb_force, mode, 0, 3);
 }
 // WIN: the windowed sibling (k.Sq = k.Sk = win^2) - one workgroup per (sample, head, window, 128 * QB-query tile of the window)
-template <int D, int QB, bool WIN = false>
+// SHARE: the shared sibling - the plain grid; a workgroup finds its segment count in the table
+template <int D, int QB, bool WIN = false, bool SHARE = false>
 static int launch_fa(tsd_ctx* ctx, const AttnK& k, int B, int H, int Sq) {
   constexpr int DCH = D / 8, KSTEPS = (DCH + 1) / 2, KPITCH = (DCH & 1) ? DCH : ((2 * KSTEPS) | 1), DBLK = (D + 31) / 32;
   constexpr int LDS = 2 * (64 * KPITCH * 16 + DBLK * 32 * 128) + 16;  // + the early-abort flag word
-  auto fn = WIN ? flash_attn_win_kernel<D, QB> : flash_attn_kernel<D, QB>;
+  auto fn = SHARE ? flash_attn_share_kernel<D, QB> : WIN ? flash_attn_win_kernel<D, QB> : flash_attn_kernel<D, QB>;
   static std::atomic<unsigned long long> attr{0};  // one bit per device
   if (!((attr.load(std::memory_order_relaxed) >> (ctx->device & 63)) & 1)) {
     HIP_TRY(hipFuncSetAttribute((const void*)fn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));
@@ -561,10 +605,11 @@ static int launch_fa(tsd_ctx* ctx, const AttnK& k, int B, int H, int Sq) {
 bool attn_window_side_ok(int win) { return win == 8 || win == 16 || win == 32 || win == 64 || win == 128; }
 
 // The kernel and the switches of one launch, from the options and the layer shape alone (d is a supported head dim).
-AttnPlan attn_plan(const TsdOptions& opt, int B, int H, int d, int Sq, int Sk, int nwin) {
+AttnPlan attn_plan(const TsdOptions& opt, int B, int H, int d, int Sq, int Sk, int nwin, bool share) {
   AttnPlan p;
   const long long units = (long long)H * (nwin > 0 ? nwin : 1);  // (head, window) pairs of a sample: what fills the grid beside the query tiles
-  p.diag = (opt.attn_diag && Sq == Sk) ? 1 : 0;
+  // (a shared launch is self attention over its first segment: Sk counts both, the own-block reference looks at segment 0)
+  p.diag = (opt.attn_diag && (share ? Sk == 2 * Sq : Sq == Sk)) ? 1 : 0;
   // long key loops only (the K / V^T stream of a head is what the remap saves); results do not depend on the block order.
   // Measured (profiles/r03_attn_xcd_ab.txt): FETCH_SIZE of the 4096 x 4096 d = 40 call 366 -> 144 MB, of the 1024 x 1024 d = 80 call
   // 103 -> 33 MB (-0.9 GB of a step's 10.9 GB) and 201.1 against 201.5 steps/s - the kernel is not bound by that stream (all of it
@@ -579,7 +624,8 @@ AttnPlan attn_plan(const TsdOptions& opt, int B, int H, int d, int Sq, int Sk, i
       // rows), so a sample computed alone must run the same variant as its row of a batch (bitwise batch invariance).
       // Eight waves in two staggered groups (kernels_attn8.hip) for the long key loops of a big grid - the 64x64 level's 4096 x 4096 call
       // A windowed launch (nwin > 0) is held to the same rules on the window's shape, its windows counting like heads; it has no 8-wave form.
-      if (nwin <= 0 && (opt.attn_qb_force ? opt.attn_qb_force == 3 : (opt.attn_wg8 && Sk >= 512 && (long long)ceil_div(Sq, 512) * H >= 64))) p.kernel = 3;
+      // A shared launch is held to them with Sk = 2 Sq, the keys a sharing sample walks; it has no 8-wave form either.
+      if (nwin <= 0 && !share && (opt.attn_qb_force ? opt.attn_qb_force == 3 : (opt.attn_wg8 && Sk >= 512 && (long long)ceil_div(Sq, 512) * H >= 64))) p.kernel = 3;
       else if (opt.attn_qb_force ? opt.attn_qb_force == 2 : (opt.attn_qb == 2 && Sk >= 512 && (long long)ceil_div(Sq, 256) * units >= 64)) p.kernel = 2;
       else p.kernel = 1;
       break;
@@ -602,6 +648,15 @@ int launch_flash_attention(tsd_ctx* ctx, const AttnArgs& a) {
       TSD_FAIL(TSD_E_SHAPE, "windowed attention: window side %d does not divide the %d x %d token grid", a.win, a.grid_h, a.grid_w);
     if (a.ldvt < a.Sk) TSD_FAIL(TSD_E_SHAPE, "windowed attention: V^T pitch %d below the %d tokens of the grid", a.ldvt, a.Sk);
   }
+  if (a.share_n) {  // every address of segment 1 is another sample's of this launch: checked here, the kernel trusts the table
+    if (a.share_n < 0 || a.share_n > ATTN_SHARE_MAX || a.B % a.share_n)
+      TSD_FAIL(TSD_E_SHAPE, "shared attention: a table of %d entries (1 .. %d) over %d samples (a multiple)", a.share_n, ATTN_SHARE_MAX, a.B);
+    if (a.win || a.Sq != a.Sk) TSD_FAIL(TSD_E_SHAPE, "shared attention: self attention over the whole grid only (Sq = %d, Sk = %d, window %d)", a.Sq, a.Sk, a.win);
+    if (a.share_lo < 0 || a.share_hi > a.B || a.share_lo > a.share_hi || a.share_lo % a.share_n || a.share_hi % a.share_n)
+      TSD_FAIL(TSD_E_SHAPE, "shared attention: samples [%d, %d) of %d in groups of %d", a.share_lo, a.share_hi, a.B, a.share_n);
+    for (int i = 0; i < a.share_n; i++)
+      if (a.share[i] < -1 || a.share[i] >= a.share_n || a.share[i] == i) TSD_FAIL(TSD_E_ARG, "shared attention: entry %d is %d (-1, or another index below %d)", i, a.share[i], a.share_n);
+  }
   if (!ctx->launch()) return TSD_OK;
   ProfScope prof(ctx, KC_ATTN, a.Sq, a.Sk, a.d, a.B * a.H);
   AttnK k;
@@ -612,6 +667,24 @@ int launch_flash_attention(tsd_ctx* ctx, const AttnArgs& a) {
   k.c = a.scale * 1.4426950408889634f;
   k.exact_ctr = ctx->status + 2;
   k.win = 0; k.grid_h = 0; k.grid_w = 0;
+  k.share_n = 0; k.share_lo = 0; k.share_hi = 0;
+  for (int i = 0; i < 4; i++) k.share_w[i] = 0;
+  if (a.share_n) {  // one launch whether every sample shares or only some: the segment count is per workgroup
+    k.share_n = a.share_n; k.share_lo = a.share_lo; k.share_hi = a.share_hi;
+    for (int i = 0; i < a.share_n; i++)
+      if (a.share[i] >= 0) k.share_w[i >> 3] |= (unsigned long long)(a.share[i] + 1) << ((i & 7) * 8);
+    const AttnPlan sp = attn_plan(ctx->opt, a.B, a.H, a.d, a.Sq, 2 * a.Sk, 0, true);
+    ctx->attn_last = sp;
+    k.diag = sp.diag;
+    k.xcd_map = sp.xcd_map;
+    switch (sp.kernel) {
+      case 2: return launch_fa<40, 2, false, true>(ctx, k, a.B, a.H, a.Sq);
+      case 1: return launch_fa<40, 1, false, true>(ctx, k, a.B, a.H, a.Sq);
+      case 4: return launch_fa<80, 1, false, true>(ctx, k, a.B, a.H, a.Sq);
+      case 6: return launch_fa<64, 1, false, true>(ctx, k, a.B, a.H, a.Sq);
+      default: return launch_fa<160, 1, false, true>(ctx, k, a.B, a.H, a.Sq);
+    }
+  }
   if (a.win) {
     k.win = a.win; k.grid_h = a.grid_h; k.grid_w = a.grid_w;
     k.Sq = k.Sk = k.Skv = a.win * a.win;
@@ -652,7 +725,7 @@ extern "C" int tsd_debug_attn_exact_passes(tsd_ctx* ctx, int reset) {
 }
 
 // Debug/bench entry: time `iters` launches of the fused attention core on synthetic device data.
-static int attn_bench(tsd_ctx* ctx, int B, int H, int d, int Sq, int Sk, int iters, float* ms, int win, int grid_h, int grid_w) {
+static int attn_bench(tsd_ctx* ctx, int B, int H, int d, int Sq, int Sk, int iters, float* ms, int win, int grid_h, int grid_w, int share = 0) {
   if (!ctx || !ms || iters <= 0) TSD_FAIL(TSD_E_ARG, "attn_bench: bad argument");
   HIP_TRY(hipSetDevice(ctx->device));
   const int C = H * d, Skp = round_up(Sk, 8);
@@ -676,6 +749,10 @@ static int attn_bench(tsd_ctx* ctx, int B, int H, int d, int Sq, int Sk, int ite
   a.Vt = Vt; a.ldvt = Skp; a.sVt = (int64_t)C * Skp; a.O = O; a.ldo = C; a.sO = (int64_t)Sq * C;
   a.B = B; a.H = H; a.d = d; a.Sq = Sq; a.Sk = Sk; a.scale = 1.f / sqrtf((float)d);
   a.win = win; a.grid_h = grid_h; a.grid_w = grid_w;
+  if (share) {  // one group of B samples: sample 0 is the reference of all the others
+    a.share_n = B; a.share_lo = 0; a.share_hi = B;
+    for (int i = 0; i < B && i < ATTN_SHARE_MAX; i++) a.share[i] = i ? 0 : -1;
+  }
   int r = launch_flash_attention(ctx, a);
   if (r != TSD_OK) return r;
   HIP_TRY(hipEventRecord(ctx->ev0, ctx->stream));
@@ -711,4 +788,9 @@ extern "C" int tsd_debug_attn_bench(tsd_ctx* ctx, int B, int H, int d, int Sq, i
 extern "C" int tsd_debug_attn_bench_win(tsd_ctx* ctx, int B, int H, int d, int grid_h, int grid_w, int win, int iters, float* ms) {
   if (grid_h <= 0 || grid_w <= 0 || (long long)grid_h * grid_w > (1 << 20)) TSD_FAIL(TSD_E_ARG, "attn_bench_win: bad grid");
   return attn_bench(ctx, B, H, d, grid_h * grid_w, grid_h * grid_w, iters, ms, win, win ? grid_h : 0, win ? grid_w : 0);
+}
+// The same with samples 1 .. B - 1 also attending to sample 0's keys (share = 0: the plain S x S call); 2 <= B <= 32.
+extern "C" int tsd_debug_attn_bench_share(tsd_ctx* ctx, int B, int H, int d, int S, int share, int iters, float* ms) {
+  if (S <= 0 || S > (1 << 20) || (share && (B < 2 || B > ATTN_SHARE_MAX))) TSD_FAIL(TSD_E_ARG, "attn_bench_share: bad argument");
+  return attn_bench(ctx, B, H, d, S, S, iters, ms, 0, 0, 0, share);
 }

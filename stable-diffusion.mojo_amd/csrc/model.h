@@ -240,6 +240,10 @@ struct tsd_model {
   // Windowed self attention (tsd_model_set_attn_window; UNets and ControlNets): window side per level l (token grid LH / 2^l x LW / 2^l),
   // 0 = off.  Read by g_unet_attn's callers at enqueue time through attn_window_for.
   int attn_win[4] = {0, 0, 0, 0};
+  // Shared self attention (tsd_model_set_attn_share; UNets): share_n entries (0 = off), the levels that share, the conditional-half flag.
+  // Read by g_unet_attn's callers at enqueue time through attn_share_for; the table travels to the kernel by value.
+  int share_n = 0, share_levels[4] = {0, 0, 0, 0}, share_cond_only = 0;
+  signed char share[TSD_ATTN_SHARE_MAX] = {};
   // Token merging (tsd_model_set_token_merge; the same kinds): share of a level's tokens merged in front of its self attention, 0 = off,
   // and the seed of the 2 x 2 partition.  Read at enqueue time through token_merge_for.  No level carries both a window and a ratio.
   float tome_ratio[4] = {0, 0, 0, 0};

@@ -154,6 +154,8 @@ def _declare(l):
         "tsd_debug_ip_attn_bench": ([vp, i, i, i, i, i, i, fp], i),
         "tsd_clip_image_patches_f16": ([vp, fp, i, i, i, vp], i),
         "tsd_model_set_attn_window": ([vp, C.POINTER(i)], i), "tsd_model_attn_window": ([vp, C.POINTER(i)], i),
+        "tsd_model_set_attn_share": ([vp, C.POINTER(i), i, C.POINTER(i), i], i),
+        "tsd_model_attn_share": ([vp, C.POINTER(i), i, C.POINTER(i), C.POINTER(i)], i),
         "tsd_model_set_token_merge": ([vp, fp, C.c_uint32], i), "tsd_model_token_merge": ([vp, fp, C.POINTER(C.c_uint32)], i),
         "tsd_token_merge_plan_f16": ([vp, vp, i, i, i, i, f, C.c_uint32, vp, vp, vp, vp, vp], i),
         "tsd_token_merge_rows_f16": ([vp, vp, i, i, i, i, vp, vp, vp], i),
@@ -220,6 +222,7 @@ def _declare(l):
         "tsd_debug_gemm_bench": ([vp, i, i, i, i, i, i, i, i, i, i, fp], i),
         "tsd_debug_attn_bench": ([vp, i, i, i, i, i, i, fp], i),
         "tsd_debug_attn_bench_win": ([vp, i, i, i, i, i, i, i, fp], i),
+        "tsd_debug_attn_bench_share": ([vp, i, i, i, i, i, i, fp], i),
         "tsd_debug_attn_exact_passes": ([vp, i], i),
         "tsd_debug_set_attn_qb": ([vp, i], i),
         "tsd_debug_set_attn_diag": ([vp, i], i),

@@ -200,7 +200,49 @@ class _AttnWindow:
         return tuple(int(v) for v in out)
 
 
-class Diffusion(_AttnWindow, _TokenMerge):
+@contextlib.contextmanager
+def attn_share_scope(model, share):
+    """`generate(attn_share=dict(...))`, the keywords of `Diffusion.set_attn_share`: the model's previous table is back on every way out."""
+    if share is None:
+        yield
+        return
+    prev = model.attn_share
+    model.set_attn_share(**share)
+    try:
+        yield
+    finally:
+        model.set_attn_share(**prev) if prev else model.clear_attn_share()
+
+
+class _AttnShare:
+    """`set_attn_share` / `attn_share` / `clear_attn_share` of the UNets."""
+
+    def set_attn_share(self, share, levels=(1, 1, 1, 1), cond_only=False):
+        """Shared self attention (reference-only control, StyleAligned, cross-frame attention; `tsd_model_set_attn_share`): share is a
+        sequence of n <= 32 entries, -1 or the index inside its group of n samples of the sample whose keys and values that sample ALSO
+        attends to - (-1, 0, 0): samples 1 and 2 read sample 0's.  A forward's batch is a multiple of n.  levels: one flag per level l
+        (token grid LH / 2^l x LW / 2^l).  cond_only: under cfg only the conditional half shares.  None, all -1 or no level turn it off.
+        State of the model: it acts from the next forward on, a step of an open `Session` included."""
+        t = [] if share is None else [int(v) for v in share]
+        lv = tuple(int(bool(v)) for v in levels)
+        if len(lv) != 4:
+            raise ValueError(f"levels is 4 flags, one per level; got {levels!r}")
+        check(lib().tsd_model_set_attn_share(self.model.h, (C.c_int * max(len(t), 1))(*t), len(t), (C.c_int * 4)(*lv), int(bool(cond_only))))
+
+    def clear_attn_share(self):
+        check(lib().tsd_model_set_attn_share(self.model.h, None, 0, None, 0))
+
+    @property
+    def attn_share(self):
+        """The model's table as the keywords of `set_attn_share`: dict(share=, levels=, cond_only=), or None when off."""
+        t, lv, co = (C.c_int * 32)(), (C.c_int * 4)(), C.c_int(0)
+        n = lib().tsd_model_attn_share(self.model.h, t, 32, lv, C.byref(co))
+        if n < 0:
+            check(n)
+        return dict(share=tuple(int(v) for v in t[:n]), levels=tuple(int(v) for v in lv), cond_only=bool(co.value)) if n else None
+
+
+class Diffusion(_AttnWindow, _TokenMerge, _AttnShare):
     """`Diffusion` diffusion.mojo:294-318 - device-resident weights; forward is ONE libtsd call.
 
     forward(x, context, time): x (4,LH,LW) or (B,4,LH,LW), square or not; context (T,768)/(1,T,768) or (B,T,768);

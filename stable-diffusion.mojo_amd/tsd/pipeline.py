@@ -29,7 +29,8 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
              mask_mode="any", seeds=None, guidance_rescale=0.0, prediction="epsilon", zero_terminal_snr=False, controlnet=None,
              control_image=None, control_scale=1.0, control_cond_only=False, control_start=0.0, control_end=1.0, ip_adapter=None,
              ip_image_embeds=None, ip_scale=1.0, ip_start=0.0, ip_end=1.0, ip_image=None, image_encoder=None, ip_hidden=None,
-             ip_uncond_hidden=None, freeu=None, ff_fp8=None, attn_window=None, token_merge=None):
+             ip_uncond_hidden=None, freeu=None, ff_fp8=None, attn_window=None, token_merge=None, attn_share=None,
+             reference_image=None, reference_levels=(1, 1, 1, 1), reference_cond_only=True):
     """context (B,T,768); returns images (B,3,8LH,8LW) in [0,255] like pipeline.mojo:127.  L is the latent side (64: 512x512) or a pair
     (LH, LW) for a rectangular image ((96, 64): 512 wide, 768 high); where the text below says L,L the tensor is LH,LW.
 
@@ -90,16 +91,115 @@ def generate(diffusion, decoder, context, uncond_context=None, strength=0.8, cfg
     held are back on every way out.
 
     token_merge, a ratio (the top level's), 4 ratios per level or (ratios, seed) (`Diffusion.set_token_merge`): the UNet's self attention
-    runs on merged tokens for this call, and so does `controlnet`'s; the tables the models held are back on every way out."""
+    runs on merged tokens for this call, and so does `controlnet`'s; the tables the models held are back on every way out.
+
+    attn_share, a dict of `Diffusion.set_attn_share`'s keywords (dict(share=(-1, 0, 0)): samples 1 and 2 also attend to sample 0's keys):
+    the UNet's self attention shares keys for this call; the table the model held - or none - is back on every way out.
+
+    reference_image (3,8LH,8LW) on the 0 .. 255 scale, with encoder: reference-only control.  The image is encoded and rides as sample B
+    of a session at batch B + 1, held at its own latents re-noised to every step's timestep (an all-zero inpainting mask; with seeds its
+    noise comes from seed seeds[-1] + 1), with sample 0's context; the B samples also attend to its keys and values in the self
+    attention of reference_levels (share = (B, ..., B, -1)), under cfg in the conditional half only unless reference_cond_only=False.
+    The first B images come back.  input_image / mask keep their meaning for the B samples; without input_image they start from
+    their noise as always.  Not together with attn_share, controlnet or ip_adapter."""
     from .fp8 import ff_fp8_scope
     from .token_merge import token_merge_scope
-    from .diffusion import attn_window_scope
+    from .diffusion import attn_share_scope, attn_window_scope
     from .free_u import freeu_scope
+    ref_kw = ("reference_image", "reference_levels", "reference_cond_only")
+    if reference_image is not None and (attn_share is not None or controlnet is not None or ip_adapter is not None):
+        raise ValueError("generate: reference_image sets the share table itself and runs without controlnet / ip_adapter")
     with freeu_scope(diffusion, freeu), ff_fp8_scope(diffusion, ff_fp8), attn_window_scope(diffusion, attn_window), \
+            attn_share_scope(diffusion, attn_share), \
             attn_window_scope(controlnet, attn_window if hasattr(controlnet, "set_attn_window") else None), \
             token_merge_scope(diffusion, token_merge), token_merge_scope(controlnet, token_merge):  # (any other controlnet: refused below)
-        return _generate(**{k: v for k, v in locals().items() if k not in ("freeu", "freeu_scope", "ff_fp8", "ff_fp8_scope", "attn_window",
-                                                                           "attn_window_scope", "token_merge", "token_merge_scope")})
+        kw = {k: v for k, v in locals().items() if k not in ("freeu", "freeu_scope", "ff_fp8", "ff_fp8_scope", "attn_window", "attn_window_scope",
+                                                             "token_merge", "token_merge_scope", "attn_share", "attn_share_scope", "ref_kw")}
+        if reference_image is not None:
+            return _generate_reference(**{k: v for k, v in kw.items() if not k.startswith(("control", "ip_")) and k != "image_encoder"})
+        return _generate(**{k: v for k, v in kw.items() if k not in ref_kw})
+
+
+def _generate_reference(diffusion, decoder, context, uncond_context, strength, cfg, cfg_scale, inference_steps, seed_val, input_image, encoder,
+                        latents, noise, num_training_steps, L, return_latents, sampler, eta, spacing, mask, mask_mode, seeds, guidance_rescale,
+                        prediction, zero_terminal_snr, reference_image, reference_levels, reference_cond_only):
+    """`generate(reference_image=...)`: the session at B + 1 with the reference as its last sample (see `generate`)."""
+    from .diffusion import attn_share_scope
+    from .utils import normal_fill
+    if encoder is None:
+        raise ValueError("generate(reference_image=...) needs encoder: the reference rides along as latents")
+    if seeds is not None and (noise is not None or latents is not None):
+        raise ValueError("generate(seeds=...) draws latents and noise on the device: pass neither noise nor latents")
+    if mask is not None and input_image is None:
+        raise ValueError("generate(mask=...) needs input_image and encoder: the mask says which part of that image to keep")
+    guidance_rescale = check_guidance_rescale(guidance_rescale, cfg)
+    context = np.asarray(context, dtype=np.float32)
+    context = context[None] if context.ndim == 2 else context
+    B, T, W = context.shape
+    LH, LW = latent_shape(L)
+    one = 4 * LH * LW
+    ref = np.asarray(reference_image, dtype=np.float32)
+    ref = ref[None] if ref.ndim == 3 else ref
+    if ref.shape != (1, 3, 8 * LH, 8 * LW):
+        raise ValueError(f"reference_image must have shape {(3, 8 * LH, 8 * LW)}, got {np.shape(reference_image)}")
+    cx, uc = np.concatenate([context, context[:1]]), None
+    if cfg:
+        if uncond_context is None:
+            raise ValueError("a CFG session needs uncond_context")
+        uc = np.broadcast_to(np.asarray(uncond_context, dtype=np.float32).reshape(-1, T, W), (B, T, W)) if np.size(uncond_context) == T * W \
+            else np.asarray(uncond_context, dtype=np.float32)
+        uc = np.concatenate([uc, uc[:1]])
+    shape1 = (1, 4, LH, LW)
+    ref_lat = encoder.forward(rescale(ref, (0, 255), (-1, 1)), rng.normal(seed_val, 5, one).reshape(shape1))
+    sess = Session(diffusion.model, decoder.model if decoder is not None else None, B + 1, L, T, cfg=cfg)
+    try:
+        start = inference_steps - int(inference_steps * strength) if input_image is not None else 0
+        if (prediction, bool(zero_terminal_snr)) != ("epsilon", False):
+            sess.set_prediction(prediction, zero_terminal_snr)
+        if (sampler, eta, spacing) != ("ddpm", 0.0, "leading"):
+            sess.set_sampler(sampler, eta, spacing)
+        sess.set_schedule(num_training_steps, inference_steps, start)
+        n = sess.num_steps
+        x0 = np.zeros((B, 4, LH, LW), dtype=np.float32)
+        if input_image is not None:
+            x0 = encoder.forward(rescale(input_image, (0, 255), (-1, 1)), rng.normal(seed_val, 1, B * one).reshape(B, 4, LH, LW))
+        known = np.concatenate([x0, ref_lat]).astype(np.float32)
+        m = np.ones((B + 1, LH, LW), dtype=np.float32)      # the B samples: regenerate (or the caller's mask); the reference: keep
+        m[B] = 0.0
+        if mask is not None:
+            m[:B] = latent_mask(mask, mask_mode, diffusion.model.ctx)
+        sd = None if seeds is None else [int(v) for v in seeds] + [(int(seeds[-1]) + 1) % (1 << 64)]
+        if noise is None and sd is None:
+            noise = rng.normal(seed_val, 3, n * B * one).reshape(n, B, 4, LH, LW)
+        nz = None if noise is None else np.concatenate([noise, np.zeros((n,) + shape1, dtype=np.float32)], axis=1)
+        z4 = None if sd else np.concatenate([rng.normal(seed_val, 4, B * one).reshape(B, 4, LH, LW), rng.normal(seed_val, 6, one).reshape(shape1)])
+
+        def load(x):
+            sess.upload(x, cx, uc, nz, cfg_scale)
+            if sd:
+                sess.set_seeds(sd)
+
+        load(known)
+        sess.add_noise_seeded(0) if sd else sess.add_noise(0, z4)      # every sample to timesteps[0]: img2img's start, and the reference's
+        if input_image is None:      # the B samples start from their noise as without a reference; only the reference keeps what add_noise gave
+            x = sess.latents()
+            x[:B] = latents if latents is not None else \
+                np.stack([normal_fill(v, 2, one, ctx=diffusion.model.ctx) for v in sd[:B]]).reshape(B, 4, LH, LW) if sd else \
+                rng.normal(seed_val, 2, B * one).reshape(B, 4, LH, LW)
+            load(x)
+        sess.set_inpaint(m, known, None if sd else z4, seeded=bool(sd))
+        if guidance_rescale > 0.0:
+            sess.set_guidance_rescale(guidance_rescale)
+        table = dict(share=(B,) * B + (-1,), levels=reference_levels, cond_only=bool(reference_cond_only and cfg))
+        with attn_share_scope(diffusion, table):
+            for i in range(n):
+                sess.step(i)
+        if decoder is None or return_latents:
+            return sess.latents()[:B]
+        sess.decode()
+        return sess.images(rescale=True)[:B]
+    finally:
+        sess.close()
 
 
 def _generate(diffusion, decoder, context, uncond_context, strength, cfg, cfg_scale, inference_steps, seed_val, input_image, encoder, latents,

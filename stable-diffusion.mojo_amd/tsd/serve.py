@@ -141,7 +141,7 @@ class SlotScheduler:
 
 def generate_stream(diffusion, decoder, requests, B, L, T=77, cfg=True, inference_steps=50, num_training_steps=1000, sampler="ddpm",
                     eta=0.0, spacing="leading", return_latents=False, stats=None, prediction="epsilon", zero_terminal_snr=False, controlnet=None,
-                    control_image=None, freeu=None, attn_window=None, token_merge=None, **control_keywords):
+                    control_image=None, freeu=None, attn_window=None, token_merge=None, attn_share=None, **control_keywords):
     """Continuous batching of `generate`: `requests` is an iterator of `Request`s (or tuples in its field order); yields (id, image
     (3,8LH,8LW) in [0,255]) - or (id, latents) with return_latents or without a decoder - as requests finish, B at a time on the device.
     L is the latent side or a pair (LH, LW): one shape for the whole stream.
@@ -166,9 +166,10 @@ def generate_stream(diffusion, decoder, requests, B, L, T=77, cfg=True, inferenc
     from .free_u import freeu_scope
     from .model import Session
     from .utils import _unary
-    from .diffusion import attn_window_scope
+    from .diffusion import attn_share_scope, attn_window_scope
     from .token_merge import token_merge_scope
-    with freeu_scope(diffusion, freeu), attn_window_scope(diffusion, attn_window), token_merge_scope(diffusion, token_merge):
+    with freeu_scope(diffusion, freeu), attn_window_scope(diffusion, attn_window), token_merge_scope(diffusion, token_merge), \
+            attn_share_scope(diffusion, attn_share):
         yield from _stream(diffusion, decoder, requests, B, L, T, cfg, inference_steps, num_training_steps, sampler, eta, spacing, return_latents,
                            stats, prediction, zero_terminal_snr, Session, _unary)
 
